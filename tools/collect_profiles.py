@@ -77,7 +77,7 @@ fetch_raw = tot["FETCH_SIZE"] * 1024.0  # KB -> bytes
 write = tot["WRITE_SIZE"] * 1024.0
 traffic = 2.0 * fetch_raw + write
 rec = {
-    "command": "rocprofv3 --pmc <COUNTER> --kernel-trace --output-format csv -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-single-instance  (separate passes for FETCH_SIZE and WRITE_SIZE; tools/profile_round.sh)",
+    "command": "rocprofv3 --pmc <COUNTER> --kernel-trace --output-format csv -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-single-instance  (separate passes for FETCH_SIZE and WRITE_SIZE; tools/profile_round.sh)",
     "workload": cfg["workload"],
     "workload_key": wkey,
     "solves_per_launch": spl,
@@ -110,7 +110,7 @@ derived = {
     "note": "utilisation at the 2.4 GHz peak clock over 256 CUs x 4 SIMDs for the kernel's duration under the profiler; SQ_* cycle counters are quad-cycles",
 }
 json.dump({"command": "rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAIT_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY (pass 1); "
-                      "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SMEM SQ_WAIT_INST_ANY (pass 2) --kernel-trace -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-single-instance",
+                      "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SMEM SQ_WAIT_INST_ANY (pass 2) --kernel-trace -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-single-instance",
            "workload": cfg["workload"], "workload_key": wkey, "solves_per_launch": spl, "kernel_ms_under_profiler": kms,
            "kernel": kernel, "vgpr": row0["VGPR_Count"], "sgpr": row0["SGPR_Count"], "lds_block": row0["LDS_Block_Size"],
            "counters": {**sq, **lds}, "derived": derived}, open(os.path.join(DST, f"{rnd}_pmc_sq_lds.json"), "w"), indent=1)
