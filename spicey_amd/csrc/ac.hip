@@ -14,6 +14,7 @@
 
 #include "../../include/spicey_hip.h"
 #include "ac_exec.h"
+#include "devbuf.h"
 #include "kernels.h"
 #include "symbolic.h"
 
@@ -92,7 +93,7 @@ struct SpiceyAcHandle {
   HostProgram hp;
   HostResident hres;       // resident layout of the 16-bit records (batched sweeps)
   SpiceyResident dres{};
-  void *d_res = nullptr;
+  DevBuf<uint8_t> d_res;
   bool resident_ok = false;
   int ncu = 256;
   int last_mode = 0;       // 1 = one workgroup per (instance, frequency), 2 = resident sweep
@@ -102,8 +103,8 @@ struct SpiceyAcHandle {
   int n_inst = 0, T = 256, device = 0;
   bool lds = true;
   size_t lds_bytes = 0;
-  void *d_blob = nullptr;
-  double *d_R = nullptr, *d_C = nullptr, *d_L = nullptr;
+  DevBuf<uint8_t> d_blob;
+  DevBuf<double> d_R, d_C, d_L;
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   double last_ms = 0.0;
@@ -117,29 +118,10 @@ extern "C" const char *spicey_ac_last_error(SpiceyAcHandle *h) { return h ? h->e
 
 extern "C" void spicey_ac_destroy(SpiceyAcHandle *h) {
   if (!h) return;
-  void *ptrs[] = {h->d_blob, h->d_R, h->d_C, h->d_L, h->d_res};
-  for (void *p : ptrs)
-    if (p) (void)hipFree(p);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
   if (h->stream) (void)hipStreamDestroy(h->stream);
-  delete h;
-}
-
-#define ACCHK(h, call)                                                 \
-  do {                                                                 \
-    hipError_t e__ = (call);                                           \
-    if (e__ != hipSuccess) {                                           \
-      (h)->err = std::string(#call) + ": " + hipGetErrorString(e__);   \
-      return SPICEY_ERR_HIP;                                           \
-    }                                                                  \
-  } while (0)
-
-static int32_t ac_upload(SpiceyAcHandle *h, double **dst, const double *src, size_t count) {
-  *dst = nullptr;
-  ACCHK(h, hipMalloc((void **)dst, (count ? count : 1) * sizeof(double)));
-  if (count && src) ACCHK(h, hipMemcpy(*dst, src, count * sizeof(double), hipMemcpyHostToDevice));
-  return SPICEY_OK;
+  delete h;  // (and with it every device buffer)
 }
 
 extern "C" int32_t spicey_ac_create(const SpiceyDesc *desc, const SpiceyOptions *opt, SpiceyAcHandle **out) {
@@ -180,8 +162,7 @@ extern "C" int32_t spicey_ac_create(const SpiceyDesc *desc, const SpiceyOptions 
   // measured on rc_ladder(1000) x 201 frequencies: 256 / 512 / 1024 threads = 62 / 43 / 35 us per sweep (one wave of workgroups)
   h->T = h->opt.threads > 0 ? h->opt.threads : (n <= 48 ? 64 : n <= 160 ? 128 : n <= 400 ? 256 : 1024);
   if (h->T > 1024 || (h->T & 63) || h->T < 64) { h->err = "threads must be a multiple of 64 in [64, 1024]"; return fail(SPICEY_ERR_BAD_DESC); }
-  if (hipMalloc(&h->d_blob, h->hp.blob.size()) != hipSuccess ||
-      hipMemcpy(h->d_blob, h->hp.blob.data(), h->hp.blob.size(), hipMemcpyHostToDevice) != hipSuccess) {
+  if (dev_upload(h->d_blob, h->hp.blob.size(), h->hp.blob.data()) != hipSuccess) {
     h->err = "upload of the program failed";
     return fail(SPICEY_ERR_HIP);
   }
@@ -192,8 +173,7 @@ extern "C" int32_t spicey_ac_create(const SpiceyDesc *desc, const SpiceyOptions 
   h->Tres = std::min(h->T, 512);
   if (h->lds && P.has16 && P.nLU <= SPICEY_AC_NSE * h->Tres && (int)h->hp.ph_cnt.size() <= 254) {
     spicey_build_resident(h->hp, h->Tres, SPICEY_AC_RMAX, h->hres, 0, false);  // (the complex executor knows generic records only)
-    if (hipMalloc(&h->d_res, h->hres.blob.size()) == hipSuccess &&
-        hipMemcpy(h->d_res, h->hres.blob.data(), h->hres.blob.size(), hipMemcpyHostToDevice) == hipSuccess) {
+    if (dev_upload(h->d_res, h->hres.blob.size(), h->hres.blob.data()) == hipSuccess) {
       h->dres = h->hres.bind(h->d_res);
       h->resident_ok = true;
     }
@@ -202,10 +182,12 @@ extern "C" int32_t spicey_ac_create(const SpiceyDesc *desc, const SpiceyOptions 
   {
     std::vector<double> rinv(ni * (size_t)P.nR);
     for (size_t i = 0; i < rinv.size(); i++) rinv[i] = 1.0 / desc->R_val[i];
-    if ((rc = ac_upload(h, &h->d_R, rinv.data(), rinv.size())) != SPICEY_OK) return fail(rc);
+    if (dev_upload(h->d_R, rinv.size(), rinv.data()) != hipSuccess || dev_upload(h->d_C, ni * P.nC, desc->C_val) != hipSuccess ||
+        dev_upload(h->d_L, ni * P.nL, desc->L_val) != hipSuccess) {
+      h->err = "upload of the element values failed";
+      return fail(SPICEY_ERR_HIP);
+    }
   }
-  if ((rc = ac_upload(h, &h->d_C, desc->C_val, ni * P.nC)) != SPICEY_OK) return fail(rc);
-  if ((rc = ac_upload(h, &h->d_L, desc->L_val, ni * P.nL)) != SPICEY_OK) return fail(rc);
   if (hipStreamCreate(&h->stream) != hipSuccess || hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess) {
     h->err = "stream/event creation failed";
     return fail(SPICEY_ERR_HIP);
@@ -246,29 +228,28 @@ extern "C" int32_t spicey_ac_run(SpiceyAcHandle *h, int64_t n_freq, const double
   if (h->hp.structurally_singular) { h->err = "Singular matrix (complex): structurally singular"; return SPICEY_ERR_SINGULAR; }
   const size_t slots = (size_t)h->n_inst * (size_t)n_freq;
   if (slots > 0x7fffffffull) { h->err = "n_inst * n_freq exceeds the grid limit"; return SPICEY_ERR_BAD_DESC; }
-  ACCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipSetDevice(h->device));
   const int nCur = P.nR + P.nC + P.nL + P.nV;
-  double *d_f = nullptr, *d_ph = nullptr, *d_ov = nullptr, *d_oi = nullptr, *d_gW = nullptr;
-  int32_t *d_status = nullptr;
   std::vector<int32_t> status(slots);
-  int32_t rc = SPICEY_OK;
-  auto body = [&]() -> int32_t {
-    ACCHK(h, hipMalloc((void **)&d_f, (size_t)n_freq * sizeof(double)));
-    ACCHK(h, hipMalloc((void **)&d_ph, std::max<size_t>(1, (size_t)h->n_inst * P.nV * 2) * sizeof(double)));
-    ACCHK(h, hipMalloc((void **)&d_ov, std::max<size_t>(1, slots * (size_t)P.nOut * 2) * sizeof(double)));
-    if (out_i) ACCHK(h, hipMalloc((void **)&d_oi, std::max<size_t>(1, slots * (size_t)nCur * 2) * sizeof(double)));
-    ACCHK(h, hipMalloc((void **)&d_status, slots * sizeof(int32_t)));
+  {
+    DevBuf<double> d_f, d_ph, d_ov, d_oi, d_gW;
+    DevBuf<int32_t> d_status;
+    HIPCHK(h, d_f.alloc((size_t)n_freq));
+    HIPCHK(h, d_ph.alloc(std::max<size_t>(1, (size_t)h->n_inst * P.nV * 2)));
+    HIPCHK(h, d_ov.alloc(std::max<size_t>(1, slots * (size_t)P.nOut * 2)));
+    if (out_i) HIPCHK(h, d_oi.alloc(std::max<size_t>(1, slots * (size_t)nCur * 2)));
+    HIPCHK(h, d_status.alloc(slots));
     // global workspace: one slice per workgroup of a launch; sweeps whose slices would exceed 16 GiB run in chunks
     const size_t slice = (size_t)P.nW * sizeof(SpiceyCx);
     const size_t chunk = h->lds ? slots : std::min(slots, std::max<size_t>(1, ((size_t)16 << 30) / slice));
-    if (!h->lds) ACCHK(h, hipMalloc((void **)&d_gW, chunk * slice));
-    ACCHK(h, hipMemcpyAsync(d_f, freqs, (size_t)n_freq * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    if (P.nV > 0) ACCHK(h, hipMemcpyAsync(d_ph, vph, (size_t)h->n_inst * P.nV * 2 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if (!h->lds) HIPCHK(h, d_gW.alloc(chunk * slice / sizeof(double)));
+    HIPCHK(h, hipMemcpyAsync(d_f, freqs, (size_t)n_freq * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if (P.nV > 0) HIPCHK(h, hipMemcpyAsync(d_ph, vph, (size_t)h->n_inst * P.nV * 2 * sizeof(double), hipMemcpyHostToDevice, h->stream));
     SpiceyAcRun R{};
     R.R_inv = h->d_R; R.C_val = h->d_C; R.L_val = h->d_L;
     R.freqs = d_f; R.vph = d_ph; R.out_v = d_ov; R.out_i = d_oi; R.gW = d_gW; R.status = d_status;
     R.n_freq = n_freq; R.n_inst = h->n_inst;
-    ACCHK(h, hipEventRecord(h->ev0, h->stream));
+    HIPCHK(h, hipEventRecord(h->ev0, h->stream));
     // batches that outnumber the CUs (one workgroup per CU at this LDS size): persistent workgroups, ~2 per CU, each
     // keeping its share of the program in registers across its frequencies
     const bool resident = h->resident_ok && !(h->opt.debug & 16) && slots > (size_t)2 * (size_t)h->ncu;
@@ -277,10 +258,10 @@ extern "C" int32_t spicey_ac_run(SpiceyAcHandle *h, int64_t n_freq, const double
       const int n_chunk = (int)std::min<int64_t>(n_freq, std::max<int64_t>(1, ((int64_t)2 * h->ncu + h->n_inst - 1) / h->n_inst));
       auto kern = spicey_ac_kernel_res<SPICEY_AC_RMAX, SPICEY_AC_NSE>;
       if (h->lds_bytes > 48 * 1024)
-        ACCHK(h, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes));
+        HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes));
       R.slot_base = 0;
       hipLaunchKernelGGL(kern, dim3((unsigned)(h->n_inst * n_chunk)), dim3(h->Tres), h->lds_bytes, h->stream, h->dprog, h->dres, R, n_chunk);
-      ACCHK(h, hipGetLastError());
+      HIPCHK(h, hipGetLastError());
     } else
     for (size_t base = 0; base < slots; base += chunk) {
       const unsigned grid = (unsigned)std::min(chunk, slots - base);
@@ -288,16 +269,16 @@ extern "C" int32_t spicey_ac_run(SpiceyAcHandle *h, int64_t n_freq, const double
       if (h->lds) {
         auto kern = spicey_ac_kernel<true>;
         if (h->lds_bytes > 48 * 1024)
-          ACCHK(h, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes));
+          HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes));
         hipLaunchKernelGGL(kern, dim3(grid), dim3(h->T), h->lds_bytes, h->stream, h->dprog, R);
       } else {
         hipLaunchKernelGGL(spicey_ac_kernel<false>, dim3(grid), dim3(h->T), 0, h->stream, h->dprog, R);
       }
-      ACCHK(h, hipGetLastError());
+      HIPCHK(h, hipGetLastError());
     }
-    ACCHK(h, hipEventRecord(h->ev1, h->stream));
-    ACCHK(h, hipMemcpyAsync(status.data(), d_status, slots * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    ACCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+    HIPCHK(h, hipMemcpyAsync(status.data(), d_status, slots * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
     // Solves that tripped a pivot guard of the static order (a diagonal cancelling at a resonance) are repeated with
     // partial pivoting, dense, the way the reference solves every frequency; whatever fails there fails in the reference
     // too.  (diagnostics: SpiceyOptions.debug bit 7 = off; circuits beyond 4096 unknowns keep the error)
@@ -309,21 +290,12 @@ extern "C" int32_t spicey_ac_run(SpiceyAcHandle *h, int64_t n_freq, const double
       if (!bad.empty()) {
         const size_t per = (size_t)P.n * ((size_t)P.n + 1) * sizeof(SpiceyCx);
         const size_t nb = std::min(bad.size(), std::max<size_t>(1, ((size_t)1 << 30) / per));
-        int64_t *d_slots = nullptr;
-        SpiceyCx *d_A = nullptr, *d_Ws = nullptr;
-        SpiceyProg *d_P = nullptr;
-        SpiceyAcRun *d_R = nullptr;
-        auto freed = [&]() {
-          void *ps[] = {d_slots, d_A, d_Ws, d_P, d_R};
-          for (void *q : ps)
-            if (q) (void)hipFree(q);
-        };
-        if (hipMalloc((void **)&d_slots, nb * sizeof(int64_t)) != hipSuccess || hipMalloc((void **)&d_A, nb * per) != hipSuccess ||
-            hipMalloc((void **)&d_Ws, nb * (size_t)P.nW * sizeof(SpiceyCx)) != hipSuccess || hipMalloc((void **)&d_P, sizeof(SpiceyProg)) != hipSuccess ||
-            hipMalloc((void **)&d_R, sizeof(SpiceyAcRun)) != hipSuccess ||
-            hipMemcpy(d_P, &h->dprog, sizeof(SpiceyProg), hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(d_R, &R, sizeof(SpiceyAcRun), hipMemcpyHostToDevice) != hipSuccess) {
-          freed();
+        DevBuf<int64_t> d_slots;
+        DevBuf<SpiceyCx> d_A, d_Ws;
+        DevBuf<SpiceyProg> d_P;
+        DevBuf<SpiceyAcRun> d_R;
+        if (d_slots.alloc(nb) != hipSuccess || d_A.alloc(nb * per / sizeof(SpiceyCx)) != hipSuccess || d_Ws.alloc(nb * (size_t)P.nW) != hipSuccess ||
+            dev_upload(d_P, 1, &h->dprog) != hipSuccess || dev_upload(d_R, 1, &R) != hipSuccess) {
           h->err = "allocation of the dense fallback workspace failed";
           return SPICEY_ERR_HIP;
         }
@@ -340,24 +312,17 @@ extern "C" int32_t spicey_ac_run(SpiceyAcHandle *h, int64_t n_freq, const double
           e2 = hipGetLastError();
           if (e2 == hipSuccess) e2 = hipStreamSynchronize(h->stream);
         }
-        freed();
         if (e2 != hipSuccess) { h->err = std::string("dense fallback: ") + hipGetErrorString(e2); return SPICEY_ERR_HIP; }
         h->last_dense = (int64_t)bad.size();
-        ACCHK(h, hipMemcpyAsync(status.data(), d_status, slots * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(status.data(), d_status, slots * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
       }
     }
-    ACCHK(h, hipMemcpyAsync(out_v, d_ov, slots * (size_t)P.nOut * 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (out_i) ACCHK(h, hipMemcpyAsync(out_i, d_oi, slots * (size_t)nCur * 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    ACCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpyAsync(out_v, d_ov, slots * (size_t)P.nOut * 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (out_i) HIPCHK(h, hipMemcpyAsync(out_i, d_oi, slots * (size_t)nCur * 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
     float ms = 0.f;
     if (hipEventElapsedTime(&ms, h->ev0, h->ev1) == hipSuccess) h->last_ms = ms;
-    return SPICEY_OK;
-  };
-  rc = body();
-  void *tmp[] = {d_f, d_ph, d_ov, d_oi, d_status, d_gW};
-  for (void *p : tmp)
-    if (p) (void)hipFree(p);
-  if (rc != SPICEY_OK) return rc;
+  }
   // the reference stops at the first frequency that throws (simulateAC.ts:80-83): report the first failing slot
   for (size_t s = 0; s < slots; s++)
     if (status[s] != 0) {

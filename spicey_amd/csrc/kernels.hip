@@ -578,29 +578,6 @@ hipError_t launch_t(const SpiceyProg &P, const SpiceyRun &R, int grid, int threa
 
 }  // namespace
 
-// LDS scratch of the dense fronts: the widest panel (U rows 16 x ld, L rows (Mp - 16) x 17, the 16 x 16 block of L and
-// the reciprocal pivots), which also covers the backward solve's vectors
-size_t spicey_front_lds_bytes(const SpiceyProg &P) {
-  if (P.nFronts <= 0) return 0;
-  return (size_t)SPICEY_FRONT_LDS_DOUBLES * sizeof(double);  // fronts of up to 128 rows live here whole; larger ones stage panels (max_front_mp <= 448)
-}
-
-size_t spicey_lds_bytes(const SpiceyProg &P, int K, bool lds, int tail_n) {
-  if (!lds) return 64 + spicey_front_lds_bytes(P);
-  size_t b = ((size_t)P.nW + P.nU + P.nGdyn) * K * sizeof(double) + ((size_t)P.nS * K + 4) * sizeof(int32_t);
-  if (P.hybrid)  // hybrid workspace: leaf-owned entries and the element vectors are in global memory
-    b = ((size_t)P.nW - P.hyb_g0 - P.hyb_g2) * K * sizeof(double) + ((size_t)P.nS * K + 4) * sizeof(int32_t);
-  b = ((b + 15) & ~size_t(15)) + SPICEY_PH_SLOTS * sizeof(unsigned long long);  // + profiling accumulators
-  if (P.pcr_n > 0 && tail_n < 5) tail_n = 5;                                         // tridiagonal top: two 2 KB row buffers + its index table
-  b = ((b + 15) & ~size_t(15)) + (size_t)tail_n * 64 * 16;                          // + tail task records
-  b += spicey_front_lds_bytes(P);                                                    // + dense-front scratch (32-bit interpreter only)
-  return (b + 15) & ~size_t(15);
-}
-
-size_t spicey_gw_doubles_per_wg(const SpiceyProg &P, int K) {
-  return ((size_t)P.nW + P.nU + P.nGdyn) * K + (((size_t)P.nS * K + 1) >> 1);
-}
-
 template <int K, bool FRONTS>
 static hipError_t launch_grp_t(const SpiceyProg &P, const SpiceyRun &R, int grid, int threads, size_t lds, hipStream_t st, int *blocks_per_cu = nullptr) {
   auto kern = spicey_tran_kernel_grp<K, FRONTS>;
@@ -661,44 +638,19 @@ hipError_t spicey_launch_tran(const SpiceyProg &P, const SpiceyRun &R, int K, bo
   return hipErrorInvalidValue;
 }
 
-// v2 geometry per workgroup size.  MINW (waves per SIMD the register budget is cut for) is chosen so that
-// NO variant spills: ROCm 7.2's hipcc places spill stores of values defined in divergent loops where EXEC can
-// be zero (the store is lost and a later reload returns a previous kernel's scratch) — observed as stale vPrev
-// registers; the Makefile therefore fails the build if any kernel reports a non-zero ScratchSize.
-//   T <= 256 : 28 slots, 12 entries, 4 elements per thread (one wave per SIMD, 256 VGPRs, no spills to AGPRs)
-//   (K = 2 interleaved instances: every variant tried — 16 to 32 slots — spilled 9 vector registers to AGPRs; the 16-bit
-//   interpreter is therefore built for K = 1 only and interleaved instances run on interpreter 1)
-//   T <= 512 : 16 slots,  8 entries, 2 elements per thread (<= 256 VGPRs)
-//   T <= 1024:  8 slots,  4 entries, 1 element  per thread (<= 128 VGPRs)
-// `packed` = the two-workgroups-per-CU geometry: 512 threads, <= 128 VGPRs; only 4 slots stay resident (the small,
-// latency-critical phases), the wide bottom levels are streamed from L2 with the records prefetched in batches.
-#define SPICEY_V2_RMAX256 28  // (32 slots spilled 6 vector registers to AGPRs: refused by check_no_spills.py)
-// (hybrid workspace at 1024 threads: 4 slots — with 8 the build spills 10 registers at the 128-register cap)
-int spicey_v2_rmax(int threads, bool packed, bool hybrid) { return packed ? 4 : (threads <= 256 ? SPICEY_V2_RMAX256 : (threads <= 512 ? 16 : (hybrid ? 4 : 8))); }
-int spicey_v2_nsv(int threads, bool packed) { return packed ? 6 : (threads <= 256 ? 12 : (threads <= 512 ? 8 : 4)); }
-int spicey_v2_nel(int threads, bool packed) { return packed ? 2 : (threads <= 256 ? 4 : (threads <= 512 ? 2 : 1)); }
-int spicey_v2_max_threads(int K) { return K == 1 ? 1024 : 0; }
+// one launcher per entry of SPICEY_V2_SHAPES (launch_plan.h)
+template <int I>
+static hipError_t launch_v2_shape(const SpiceyProg *P, const SpiceyResident *Q, const SpiceyRun *R, int grid, int threads, size_t lds, hipStream_t st) {
+  constexpr SpiceyV2Shape s = SPICEY_V2_SHAPES[I];
+  return launch_v2_t<1, s.rmax, s.nsv, s.nel, s.threads, s.minw, s.hybrid>(P, Q, R, grid, threads, lds, st);
+}
+static decltype(&launch_v2_shape<0>) const launch_v2_by_shape[] = {launch_v2_shape<0>, launch_v2_shape<1>, launch_v2_shape<2>,
+                                                                    launch_v2_shape<3>, launch_v2_shape<4>, launch_v2_shape<5>};
+static_assert(sizeof(launch_v2_by_shape) / sizeof(launch_v2_by_shape[0]) == SPICEY_V2_NSHAPES, "one launcher per v2 build");
 
 hipError_t spicey_launch_tran_v2(const SpiceyProg &Ph, const SpiceyResident &Qh, const SpiceyProg *P, const SpiceyResident *Q, const SpiceyRun *R, int K, int grid,
                                  int threads, hipStream_t st, bool packed) {
-  const size_t bytes = spicey_lds_bytes(Ph, K, true, Qh.tail_n);
-  if (packed) {
-    if (K == 1 && threads == 512) return launch_v2_t<1, 4, 6, 2, 512, 4>(P, Q, R, grid, threads, bytes, st);
-    return hipErrorInvalidValue;
-  }
-  if (Ph.hybrid) {
-    // hybrid workspace: 1024 threads (4 slots, 4 entries, 1 element per thread, loads of the beyond-resident loops two at a
-    // time: what fits 128 registers) or 512 threads (16 slots, 8 entries, 2 elements, four at a time)
-    if (K == 1 && threads == 512) return launch_v2_t<1, 16, 8, 2, 512, 2, true>(P, Q, R, grid, threads, bytes, st);
-    if (K == 1 && threads == 1024) return launch_v2_t<1, 4, 4, 1, 1024, 4, true>(P, Q, R, grid, threads, bytes, st);
-    return hipErrorInvalidValue;
-  }
-  if (threads <= 256) {
-    if (K == 1) return launch_v2_t<1, SPICEY_V2_RMAX256, 12, 4, 256, 1>(P, Q, R, grid, threads, bytes, st);
-  } else if (threads <= 512) {
-    if (K == 1) return launch_v2_t<1, 16, 8, 2, 512, 2>(P, Q, R, grid, threads, bytes, st);
-  } else if (K == 1) {
-    return launch_v2_t<1, 8, 4, 1, 1024, 4>(P, Q, R, grid, threads, bytes, st);
-  }
-  return hipErrorInvalidValue;
+  const int shape = K == 1 ? spicey_v2_shape(threads, packed, Ph.hybrid != 0) : -1;
+  if (shape < 0) return hipErrorInvalidValue;
+  return launch_v2_by_shape[shape](P, Q, R, grid, threads, spicey_lds_bytes(Ph, K, true, Qh.tail_n), st);
 }

@@ -1,0 +1,234 @@
+// launch_plan.cpp — see launch_plan.h.
+#include "launch_plan.h"
+
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+
+#include "fronts_exec_consts.h"
+
+// LDS scratch of the dense fronts: the widest panel (U rows 16 x ld, L rows (Mp - 16) x 17, the 16 x 16 block of L and
+// the reciprocal pivots), which also covers the backward solve's vectors
+size_t spicey_front_lds_bytes(const SpiceyProg &P) {
+  if (P.nFronts <= 0) return 0;
+  return (size_t)SPICEY_FRONT_LDS_DOUBLES * sizeof(double);  // fronts of up to 128 rows live here whole; larger ones stage panels (max_front_mp <= 448)
+}
+
+size_t spicey_lds_bytes(const SpiceyProg &P, int K, bool lds, int tail_n) {
+  if (!lds) return 64 + spicey_front_lds_bytes(P);
+  size_t b = ((size_t)P.nW + P.nU + P.nGdyn) * K * sizeof(double) + ((size_t)P.nS * K + 4) * sizeof(int32_t);
+  if (P.hybrid)  // hybrid workspace: leaf-owned entries and the element vectors are in global memory
+    b = ((size_t)P.nW - P.hyb_g0 - P.hyb_g2) * K * sizeof(double) + ((size_t)P.nS * K + 4) * sizeof(int32_t);
+  b = ((b + 15) & ~size_t(15)) + SPICEY_PH_SLOTS * sizeof(unsigned long long);  // + profiling accumulators
+  if (P.pcr_n > 0 && tail_n < 5) tail_n = 5;                                         // tridiagonal top: two 2 KB row buffers + its index table
+  b = ((b + 15) & ~size_t(15)) + (size_t)tail_n * 64 * 16;                          // + tail task records
+  b += spicey_front_lds_bytes(P);                                                    // + dense-front scratch (32-bit interpreter only)
+  return (b + 15) & ~size_t(15);
+}
+
+size_t spicey_gw_doubles_per_wg(const SpiceyProg &P, int K) {
+  return ((size_t)P.nW + P.nU + P.nGdyn) * K + (((size_t)P.nS * K + 1) >> 1);
+}
+
+int spicey_v2_shape(int threads, bool packed, bool hybrid) {
+  for (int i = 0; i < SPICEY_V2_NSHAPES; i++) {
+    const SpiceyV2Shape &s = SPICEY_V2_SHAPES[i];
+    if (s.packed == packed && s.hybrid == hybrid && threads <= s.threads) return i;
+  }
+  return -1;
+}
+// (beyond every build of the kind: the numbers of the widest plain build, the last entry)
+static const SpiceyV2Shape &v2_build(int threads, bool packed = false, bool hybrid = false) {
+  const int i = spicey_v2_shape(threads, packed, hybrid);
+  return SPICEY_V2_SHAPES[i >= 0 ? i : SPICEY_V2_NSHAPES - 1];
+}
+
+SpiceyKnobs spicey_read_knobs() {
+  const char *ms = getenv("SPICEY_GROUP_TIMEOUT_MS");
+  return {getenv("SPICEY_NO_HYBRID") != nullptr, getenv("SPICEY_FRONT_RIGHT_LOOKING") != nullptr, getenv("SPICEY_TEST_FORCE_GROUP_ABORT") != nullptr,
+          ms ? atoi(ms) : 0};
+}
+
+static int pick_threads(const HostProgram &hp, bool v2) {
+  const SpiceyProg &P = hp.hdr;
+  if (v2) {
+    // smallest workgroup in which the whole program is register-resident: all factor/backward tasks in the
+    // RMAX slots, one right-hand-side row, one element of each kind and NSV re-stamped entries per thread
+    int64_t chunks = 0;  // 64-lane chunks of task records
+    for (uint32_t c : hp.ph_cnt) chunks += (c + 63) / 64;
+    const int widest = std::max(std::max(P.n, P.nOut), std::max(std::max(P.nR, P.nC), P.nD));
+    // measured on diode_chain(1000): per-step time T=1024 < T=512 < T=256 (more waves hide the issue-bound
+    // phases B/Z); small circuits take the smallest workgroup that holds everything
+    const int tmax = SPICEY_V2_SHAPES[SPICEY_V2_NSHAPES - 1].threads;  // (v2 runs one instance per workgroup)
+    for (int T = 64; T <= tmax; T *= 2) {
+      const SpiceyV2Shape &b = v2_build(T);
+      const bool fits = chunks <= (int64_t)b.rmax * (T / 64) && widest <= b.nel * T && P.nRestore <= b.nsv * T;
+      if (fits && (T >= tmax || widest <= T)) return T;  // prefer one element per thread when a larger T offers it
+    }
+    return tmax;
+  }
+  const int n = P.n;
+  if (n <= 48) return 64;
+  if (n <= 160) return 128;
+  if (n <= 400) return 256;
+  if (n <= 4000) return 512;
+  return 1024;
+}
+
+int32_t spicey_plan(const SpiceyDesc *desc, const SpiceyOptions &opt, const SpiceyKnobs &knobs, const PlanDevice &dev, HostProgram &hp,
+                    HostResident &hres, LaunchPlan &plan, std::string &err) {
+  auto fail = [&](int32_t code, const char *msg) { err = msg; return code; };
+  // dense fronts: explicit level, or automatic for large nonlinear circuits that run one instance per workgroup (the
+  // interleaved K > 1 layouts and forced interpreter 2 keep the task lists); -1 = never
+  int front_cut = opt.front_cut > 0 ? opt.front_cut : (opt.front_cut == 0 ? -1 : 0);
+  if (opt.inst_per_wg > 1 || opt.interpreter == 2) front_cut = 0;
+  if (front_cut < 0 && desc && desc->n_inst >= 512) front_cut = 0;  // big batches fill the chip with interleaved instances instead
+  // tridiagonal top by cyclic reduction (16-bit records, one instance per workgroup); diagnostics: bit 5 = never
+  const bool pcr_top = !((opt.debug >> 5) & 1) && opt.inst_per_wg <= 1;
+  int32_t rc = spicey_build_program(desc, hp, err, !((opt.debug >> 2) & 1), front_cut, pcr_top);  // diagnostics: bit 2 = plain CSR numbering
+  if (rc != SPICEY_OK) return rc;
+  plan.n_inst = desc->n_inst;
+  plan.algo_bytes = spicey_algorithmic_bytes(desc, hp.nnzA, hp.hdr.nLU);
+  int ncu = 256;
+  if ((rc = dev.open(opt.device, &ncu, err)) != SPICEY_OK) return rc;
+
+  // ---- geometry: instances per workgroup, threads, LDS or global workspace --------------------
+  const SpiceyProg &P = hp.hdr;  // (follows hp through the hybrid rebuild)
+  int K = opt.inst_per_wg;
+  const bool want_lds = !opt.force_global;
+  if (K != 0 && K != 1 && K != 2 && K != 4) return fail(SPICEY_ERR_BAD_DESC, "inst_per_wg must be 0, 1, 2 or 4");
+  // diagnostics are compiled into the kernels with at most two interleaved instances and not into the two-workgroups-per-CU
+  // geometry (tran_exec.h, DIAG): a handle with the option stays out of both
+  const bool diag = opt.diagnostics != 0;
+  if (diag && (K == 4 || opt.geometry == 2)) return fail(SPICEY_ERR_BAD_DESC, "diagnostics need inst_per_wg <= 2 and geometry != 2");
+  if (P.nS > 0) K = 1;  // the switch iteration count is per instance: no interleaving
+  if (P.nFronts > 0) K = 1;  // dense fronts: one instance per workgroup (group)
+  if (K == 0) {
+    // LDS path: one instance per workgroup (measured faster than two interleaved ones: VGPR pressure in phase Z).
+    // Global-workspace path (large circuits): once the batch exceeds the CUs, interleaving 2-4 instances shares
+    // the index stream and fills more of every gathered cache line (rcd_mesh(50) x 1024: ~3x with K = 4).
+    K = 1;
+    if (!want_lds || spicey_lds_bytes(P, 1, true) > SPICEY_LDS_MAX) K = (plan.n_inst >= 4 * ncu && !diag) ? 4 : (plan.n_inst >= 2 * ncu ? 2 : 1);
+  }
+  if (K > plan.n_inst) K = 1;
+  // Hybrid workspace (program.h, SpiceyProg::hybrid): a circuit whose L+U no longer fits the LDS of one CU but whose upper
+  // elimination tree does keeps the 16-bit register-resident interpreter — the entries the LEAVES own (half of L+U under
+  // nested dissection) and the element vectors move to global memory, read by one factor phase and one backward phase.
+  // Without it such a circuit falls to the 32-bit task lists on a global workspace (diode_chain(2600): 56 us per step on 16
+  // cooperating workgroups against ~16 for the 2000-node chain that still fits).  One instance per workgroup; 1024 threads
+  // (SpiceyOptions.threads = 512 selects the 512-thread build of the same kernel).
+  if (want_lds && (opt.inst_per_wg == 0 || opt.inst_per_wg == 1) && opt.interpreter != 1 && opt.geometry != 2 && P.has16 && P.nFronts == 0 &&
+      (opt.threads == 0 || opt.threads == 512 || opt.threads == 1024) && opt.wgs_per_inst <= 1 && !diag && !knobs.no_hybrid &&
+      spicey_lds_bytes(P, 1, true, 5) > SPICEY_LDS_MAX) {
+    HostProgram hyb;
+    std::string err2;
+    if (spicey_build_program(desc, hyb, err2, true, 0, pcr_top, true) == SPICEY_OK && hyb.hdr.hybrid && !hyb.ph_cnt.empty() && hyb.ph_cnt[0] > 64 &&
+        spicey_lds_bytes(hyb.hdr, 1, true, 5) <= SPICEY_LDS_MAX) {
+      hp = std::move(hyb);
+      K = 1;
+    }
+  }
+  plan.lds = want_lds && spicey_lds_bytes(P, K, true) <= SPICEY_LDS_MAX;
+  if (!plan.lds && want_lds && K > 1 && spicey_lds_bytes(P, 1, true) <= SPICEY_LDS_MAX) {
+    K = 1;  // one instance fits LDS where K interleaved ones do not: LDS wins
+    plan.lds = true;
+  }
+  plan.K = K;
+  // interpreter: v2 needs the LDS workspace, 16-bit records and one instance per workgroup (the K = 2 build of the
+  // register-resident kernel spilled vector registers whatever its geometry: kernels.hip)
+  const bool v2_ok = plan.lds && P.has16 && K == 1;
+  if (opt.interpreter == 2 && !v2_ok) return fail(SPICEY_ERR_BAD_DESC, "interpreter 2 needs the LDS workspace, < 65536 workspace entries and inst_per_wg = 1");
+  plan.interp = (opt.interpreter == 1 || !v2_ok) ? 1 : 2;
+  plan.T = opt.threads > 0 ? opt.threads : pick_threads(hp, plan.interp == 2);
+  if (P.hybrid) {
+    if (plan.interp != 2) return fail(SPICEY_ERR_BAD_DESC, "internal: hybrid layout without the 16-bit interpreter");
+    plan.T = opt.threads == 512 ? 512 : 1024;  // (the two geometries the hybrid kernel is built for: SPICEY_V2_SHAPES)
+  }
+  if (P.nFronts > 0 && plan.T > 512) {  // kernels with the dense-front code are built for <= 512 threads (256 VGPRs)
+    if (opt.threads > 512) return fail(SPICEY_ERR_BAD_DESC, "front_cut needs threads <= 512");
+    plan.T = 512;
+  }
+  if (plan.T > 1024 || (plan.T & 63) || plan.T < 64) return fail(SPICEY_ERR_BAD_DESC, "threads must be a multiple of 64 in [64, 1024]");
+  plan.grid = (plan.n_inst + K - 1) / K;
+  plan.lds_bytes = spicey_lds_bytes(P, K, plan.lds);
+  if (plan.interp == 2) {
+    // geometry: "throughput" packs two 512-thread workgroups on a CU (needs K = 1, half the LDS, and the per-thread
+    // resident items of a 512-thread workgroup); chosen automatically once the batch can fill every CU twice
+    const size_t base = spicey_lds_bytes(P, K, true, 0);
+    const int widest = std::max(std::max(P.n, P.nOut), std::max(std::max(P.nR, P.nC), P.nD));
+    const bool packable = K == 1 && base <= SPICEY_LDS_MAX / 2 && widest <= v2_build(512, true).nel * 512 &&
+                          P.nRestore <= v2_build(512, true).nsv * 512 && (opt.threads == 0 || opt.threads == 512);
+    if (opt.geometry == 2 && !packable) return fail(SPICEY_ERR_BAD_DESC, "geometry 2 needs inst_per_wg = 1, <= 80 KB of LDS per instance and <= 1024 unknowns");
+    if (opt.geometry < 0 || opt.geometry > 2) return fail(SPICEY_ERR_BAD_DESC, "geometry must be 0, 1 or 2");
+    plan.packed = packable && !diag && !P.hybrid && (opt.geometry == 2 || (opt.geometry == 0 && plan.n_inst >= 2 * ncu && opt.threads == 0));
+    if (plan.packed) plan.T = 512;
+    // tail levels go to LDS: as many as fit beside the workspace (1 KB each), at most 24; the packed geometry
+    // must leave room for a second workgroup on the CU
+    const size_t lds_cap = plan.packed ? SPICEY_LDS_MAX / 2 : SPICEY_LDS_MAX;
+    int max_tail = (int)std::min<size_t>(24, base < lds_cap ? (lds_cap - base) / 1024 : 0);
+    if (opt.debug & 1) max_tail = 0;  // diagnostics: disable the tail merge
+    spicey_build_resident(hp, plan.T, v2_build(plan.T, plan.packed, P.hybrid != 0).rmax, hres, max_tail, !((opt.debug >> 6) & 1));  // diagnostics: bit 6 = no row records
+    plan.lds_bytes = spicey_lds_bytes(P, K, true, hres.tail_n);
+  }
+  if (!plan.lds) {
+    // group mode: several CUs per instance when the batch leaves CUs idle and the circuit is large enough for the
+    // cross-workgroup barrier (~3 us per phase) to pay; all workgroups must be co-resident: grid * G <= #CU
+    int G = opt.wgs_per_inst;
+    if (G < 0 || G > 256 || (G > 1 && K > 2)) return fail(SPICEY_ERR_BAD_DESC, "wgs_per_inst must be in [0, 256] (and inst_per_wg <= 2 with it)");
+    if (G == 0) {
+      G = 1;
+      // (with dense fronts the group barriers that are left belong to a dozen wide levels, and the front tree wants one
+      // workgroup per subtree: up to 128 CUs for a single instance (measured on rcd_mesh(100): 32 / 48 / 64 / 96 / 128
+      // workgroups = 0.78 / 0.71 / 0.70 / 0.69 / 0.68 ms per step); without them every one of ~600 barriers per step grows with G)
+      const int gmax = P.nFronts > 0 ? 128 : 16;
+      // (the workspace is in HBM / L2 here: from ~10 k entries on (what no longer fits LDS) the extra CUs pay for the group barriers also without
+      // fronts — one diode_chain(4000) 68 -> 60 us per step, (8000) 119 -> 77, rc_ladder(8000) 80 -> 66 at G = 16)
+      if (K <= 2 && (P.nLU >= 10000 || P.nFronts > 0))
+        while (G * 2 <= gmax && plan.grid * G * 2 <= ncu) G *= 2;
+    }
+    if (plan.grid * G > ncu) G = std::max(1, ncu / plan.grid);
+    if (G > 1) {
+      // residency: ask the runtime how many workgroups of THIS kernel (its LDS size, these threads) a CU holds; the group
+      // is laid out for one per CU, so any answer >= 1 means grid * G <= #CU workgroups are co-resident on an idle device
+      const int T_grp = (P.nFronts > 0 && plan.T > 512) ? 512 : plan.T;
+      if (dev.grp_blocks_per_cu(P, K, T_grp) < 1) {
+        if (opt.wgs_per_inst > 1) return fail(SPICEY_ERR_HIP, "wgs_per_inst: the group-mode kernel cannot be resident on this device (occupancy query says 0 workgroups per CU)");
+        G = 1;
+      }
+    }
+    plan.G = G;
+  }
+  return SPICEY_OK;
+}
+
+void fill_info(const LaunchPlan &plan, const HostProgram &hp, const HostResident &hres, const SpiceyOptions &opt, SpiceyInfo *info) {
+  const SpiceyProg &P = hp.hdr;
+  memset(info, 0, sizeof(*info));
+  info->n_var = P.n;
+  info->nnz_a = hp.nnzA;
+  info->nnz_lu = P.nLU;
+  info->n_levels = P.nLevels;
+  info->threads = plan.T;
+  info->inst_per_wg = plan.K;
+  info->lds_bytes = plan.lds ? (int32_t)plan.lds_bytes : 0;
+  info->n_cur = P.nCur;
+  info->n_out = P.nOut;
+  info->n_workgroups = plan.grid;
+  info->interpreter = plan.interp;
+  info->geometry = plan.interp == 2 ? (plan.packed ? 2 : 1) : 0;
+  info->tail_levels = hres.tail_n;
+  info->wgs_per_inst = plan.G;
+  info->resident_slots = plan.interp == 2 ? hres.rmax : 0;
+  info->resident_tasks = hres.resident_tasks;
+  info->streamed_tasks = hres.streamed_tasks;
+  info->program_bytes = (int64_t)hp.blob.size();
+  info->algorithmic_bytes_solve = plan.algo_bytes;
+  info->factor_reuse = (P.nD == 0 && P.nS == 0 && P.nDynEnt == 0 && !((opt.debug >> 1) & 1)) ? 1 : 0;
+  info->n_fronts = P.nFronts;
+  info->front_cut = P.front_cut;
+  info->max_front = P.max_front_mp;
+  info->front_ws_bytes = P.front_ws * (int64_t)sizeof(double);
+  info->pcr_rows = (plan.interp == 2 && plan.K == 1) ? P.pcr_n : 0;
+  info->pcr_level = info->pcr_rows ? P.pcr_level : 0;
+  info->hybrid_entries = P.hybrid ? P.hyb_g0 + P.hyb_g2 : 0;
+}

@@ -1,0 +1,75 @@
+// launch_plan.h — the launch plan of a transient handle (every shape decision of spicey_create) and the shape helpers it
+// reads.  No HIP header: the emulator library and the CPU tests run the very policy the product runs.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include <functional>
+#include <string>
+
+#include "../../include/spicey_hip.h"
+#include "program.h"
+#include "symbolic.h"
+
+#define SPICEY_LDS_MAX 163840  // 160 KiB per CU on MI355X (MI355X_MICROARCH.md "Chip-level parameters")
+
+size_t spicey_lds_bytes(const SpiceyProg &P, int K, bool lds, int tail_n = 0);
+size_t spicey_front_lds_bytes(const SpiceyProg &P);
+size_t spicey_gw_doubles_per_wg(const SpiceyProg &P, int K);
+
+// v2 builds (register-resident program, one instance per workgroup).  MINW (waves per SIMD the register budget is cut
+// for) is chosen so that NO variant spills: ROCm 7.2's hipcc places spill stores of values defined in divergent loops
+// where EXEC can be zero (the store is lost and a later reload returns a previous kernel's scratch) — observed as stale
+// vPrev registers; the Makefile therefore fails the build if any kernel reports a non-zero ScratchSize.
+//   T <= 256 : 28 slots, 12 entries, 4 elements per thread (one wave per SIMD, 256 VGPRs, no spills to AGPRs)
+//   (K = 2 interleaved instances: every variant tried — 16 to 32 slots — spilled 9 vector registers to AGPRs; the 16-bit
+//   interpreter is therefore built for K = 1 only and interleaved instances run on interpreter 1)
+//   T <= 512 : 16 slots,  8 entries, 2 elements per thread (<= 256 VGPRs)
+//   T <= 1024:  8 slots,  4 entries, 1 element  per thread (<= 128 VGPRs)
+// `packed` = the two-workgroups-per-CU geometry: 512 threads, <= 128 VGPRs; only 4 slots stay resident (the small,
+// latency-critical phases), the wide bottom levels are streamed from L2 with the records prefetched in batches.
+// Hybrid workspace: 512 threads as the plain build, or 1024 threads with 4 slots (with 8 the build spills 10 registers
+// at the 128-register cap).
+#define SPICEY_V2_RMAX256 28  // (32 slots spilled 6 vector registers to AGPRs: refused by check_no_spills.py)
+struct SpiceyV2Shape {
+  bool packed, hybrid;
+  int threads, rmax, nsv, nel, minw;  // workgroup size (launch bound), slots, re-stamped entries and elements per thread, waves per SIMD
+};
+// (spicey_launch_tran_v2 instantiates one kernel per entry; each kind in ascending threads)
+constexpr SpiceyV2Shape SPICEY_V2_SHAPES[] = {{true, false, 512, 4, 6, 2, 4},    {false, true, 512, 16, 8, 2, 2},
+                                              {false, true, 1024, 4, 4, 1, 4},   {false, false, 256, SPICEY_V2_RMAX256, 12, 4, 1},
+                                              {false, false, 512, 16, 8, 2, 2},  {false, false, 1024, 8, 4, 1, 4}};
+constexpr int SPICEY_V2_NSHAPES = (int)(sizeof(SPICEY_V2_SHAPES) / sizeof(SPICEY_V2_SHAPES[0]));
+// index of the build that runs `threads` threads: the first of the kind that holds them; -1 = none
+int spicey_v2_shape(int threads, bool packed, bool hybrid);
+
+// Environment knobs of the transient handle, read once by spicey_create.
+struct SpiceyKnobs {
+  bool no_hybrid = false;            // SPICEY_NO_HYBRID: never take the hybrid workspace
+  bool front_right_looking = false;  // SPICEY_FRONT_RIGHT_LOOKING: experiments, the round-2 sweep of staged fronts
+  bool force_group_abort = false;    // SPICEY_TEST_FORCE_GROUP_ABORT: tests, the first attempt of every group launch aborts
+  int group_timeout_ms = 0;          // SPICEY_GROUP_TIMEOUT_MS: group-mode wait bound when SpiceyOptions leaves it 0
+};
+SpiceyKnobs spicey_read_knobs();
+
+// What the plan asks of the device: `open` runs once the descriptor is validated (select device `device`, report its CU
+// count, or an error code and message); `grp_blocks_per_cu` is the group kernel's occupancy (spicey_grp_blocks_per_cu).
+struct PlanDevice {
+  std::function<int32_t(int device, int *ncu, std::string &err)> open;
+  std::function<int(const SpiceyProg &P, int K, int threads)> grp_blocks_per_cu;
+};
+
+struct LaunchPlan {
+  int n_inst = 0, K = 1, T = 256, grid = 1, interp = 1;
+  int G = 1;             // workgroups per instance group (group mode: global workspace only)
+  bool packed = false;   // two 512-thread workgroups per CU
+  bool lds = true;       // workspace in LDS (else global memory)
+  size_t lds_bytes = 0;
+  int64_t algo_bytes = 0;
+};
+
+// Every decision of spicey_create, in its order and with its error codes and messages (err).  Builds hp (and, for the
+// 16-bit interpreter, hres).
+int32_t spicey_plan(const SpiceyDesc *desc, const SpiceyOptions &opt, const SpiceyKnobs &knobs, const PlanDevice &dev, HostProgram &hp,
+                    HostResident &hres, LaunchPlan &plan, std::string &err);
+void fill_info(const LaunchPlan &plan, const HostProgram &hp, const HostResident &hres, const SpiceyOptions &opt, SpiceyInfo *info);

@@ -19,6 +19,7 @@
 #define SPICEY_EPS 1e-15
 #define SPICEY_VT300 0.02585
 #define SPICEY_MAX_ITER 20
+#define SPICEY_PH_SLOTS 72  // profiling slots per workgroup (phase tags: tran_exec.h)
 
 // flags in the top bits of an update-task target
 #define SPICEY_TGT_RECIP 0x80000000u  // diagonal becomes final in this task: store 1/pivot, check singularity

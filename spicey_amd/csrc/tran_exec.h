@@ -117,7 +117,6 @@ static __device__ __forceinline__ double spicey_quad_bcast_f64(double v, int q) 
 #define SPICEY_PH_Z 4
 #define SPICEY_PH_U0 8
 #define SPICEY_PH_K0 40
-#define SPICEY_PH_SLOTS 72
 
 template <int K>
 struct WgCtx {

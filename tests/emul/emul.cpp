@@ -13,6 +13,7 @@
 
 #include "../../spicey_amd/csrc/symbolic.h"
 #include "../../spicey_amd/csrc/ac_exec.h"
+#include "../../spicey_amd/csrc/launch_plan.h"
 #include "../../spicey_amd/csrc/tran_exec.h"
 
 namespace {
@@ -294,6 +295,23 @@ extern "C" int32_t spicey_emul_symbolic(const SpiceyDesc *d, int32_t *cpos, int3
   }
   if (products) { products[0] = hp.n_products; products[1] = hp.n_bk_products; }
   return hp.structurally_singular ? SPICEY_ERR_SINGULAR : SPICEY_OK;
+}
+
+// spicey_create's launch plan (launch_plan.cpp) on a device of `ncu` CUs whose group kernel holds `occupancy` workgroups
+// per CU; the knobs come from the environment as in spicey_create.  A refused plan leaves its message in err[cap].
+extern "C" int32_t spicey_emul_plan(const SpiceyDesc *d, const SpiceyOptions *opt, int32_t ncu, int32_t occupancy, SpiceyInfo *info, char *err,
+                                    int32_t cap) {
+  const SpiceyOptions o = opt ? *opt : SpiceyOptions{};
+  const PlanDevice dev{[ncu](int, int *n, std::string &) { *n = ncu; return (int32_t)SPICEY_OK; },
+                       [occupancy](const SpiceyProg &, int, int) { return (int)occupancy; }};
+  HostProgram hp;
+  HostResident hres;
+  LaunchPlan plan;
+  std::string msg;
+  const int32_t rc = spicey_plan(d, o, spicey_read_knobs(), dev, hp, hres, plan, msg);
+  if (err && cap > 0) snprintf(err, (size_t)cap, "%s", rc == SPICEY_OK ? "" : msg.c_str());
+  if (rc == SPICEY_OK && info) fill_info(plan, hp, hres, o, info);
+  return rc;
 }
 
 // Resident-layout introspection for structural tests: phase of every (wave, slot), per-phase counts and tail.

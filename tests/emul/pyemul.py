@@ -35,6 +35,9 @@ def lib():
                                            C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), i32p, C.c_int32]
         L.spicey_emul_bank_cost.restype = C.c_int32
         L.spicey_emul_bank_cost.argtypes = [C.POINTER(abi.SpiceyDesc), i64p]
+        L.spicey_emul_plan.restype = C.c_int32
+        L.spicey_emul_plan.argtypes = [C.POINTER(abi.SpiceyDesc), C.POINTER(abi.SpiceyOptions), C.c_int32, C.c_int32, C.POINTER(abi.SpiceyInfo),
+                                       C.c_char_p, C.c_int32]
         L.spicey_emul_ac.restype = C.c_int32
         L.spicey_emul_ac.argtypes = [C.POINTER(abi.SpiceyDesc), C.c_int32, C.c_int64, f64p, f64p, f64p, f64p, C.c_int32,
                                      C.POINTER(abi.SpiceyInfo)]
