@@ -99,7 +99,16 @@ typedef struct SpiceyOptions {
   int32_t want_currents; /* 1: record element currents (out_i) */
   int32_t force_global;  /* 1: keep the LU workspace in HBM/L2 even if it fits LDS (testing) */
   int32_t profile;       /* 1: accumulate per-phase shader-clock cycles (spicey_debug_phase_cycles) */
-  int32_t interpreter;   /* 0 auto; 1 = v1 (32-bit sliced task lists from L2); 2 = v2 (register-resident 16-bit records) */
+  int32_t interpreter;   /* 0 auto; 1 = v1 (32-bit sliced task lists from L2); 2 = v2 (register-resident 16-bit records);
+                            3 = reference order: the reference's own algorithm (fresh dense stamp in element order, solveReal
+                            with partial pivoting and its |f| < EPS row-update skip, back substitution in its order), one
+                            workgroup per instance — every result bit, the end state and SPICEY_ERR_SINGULAR exactly where
+                            the reference has them.  A | b in LDS up to n ~ 138 unknowns, else an n x (n + 1) slab per
+                            instance in global memory (force_global = 1: always).  threads: 0 = 64 for n <= 64, else 256;
+                            64..1024 honoured (same bits).  inst_per_wg > 1, geometry != 0, front_cut > 0, wgs_per_inst > 1
+                            and profile are refused (SPICEY_ERR_BAD_DESC).  diagnostics bit 0 then counts the nonzero
+                            multipliers the skip dropped (spicey_last_skip_risk), bit 1 records lin_err as for the others.
+                            Never chosen automatically. */
   int32_t geometry;      /* v2 only. 0 auto; 1 = latency: one workgroup per CU, whole program in registers;
                             2 = throughput: two 512-thread workgroups per CU (<= 128 VGPRs, wide levels streamed) */
   int32_t debug;         /* diagnostics: bit 0 = no tail merge; bit 1 = refactor every step even for linear circuits;
@@ -119,7 +128,7 @@ typedef struct SpiceyOptions {
                             started with (spicey_sync); 0 (default) = the abort is reported as SPICEY_ERR_HIP */
   int32_t group_timeout_ms; /* group mode: longest single cross-workgroup wait before the launch aborts; 0 = 5000 */
   int32_t diagnostics;   /* bit 0: count the solves whose stamped matrix has a column with 0 < |a_ik| < 1e-15 max_j |a_jk| — the
-                                   situation in which the reference's `if (Math.abs(f) < EPS) continue` (solveReal.ts:45) drops a
+                                   situation in which the reference's `if (Math.abs(f) < EPS) continue` (solveReal.ts:46) drops a
                                    row update that this library performs (spicey_last_skip_risk);
                             bit 1: record per step the one-shot linearisation error max_d |vd_new - vd_lin| over the diodes
                                    (spicey_get_lin_err); diagnostic only, never changes an iteration count */
@@ -136,7 +145,8 @@ typedef struct SpiceyInfo {
   int32_t n_cur;       /* element-current columns */
   int32_t n_out;       /* recorded node-voltage columns */
   int32_t n_workgroups;
-  int32_t interpreter;      /* 1 or 2, see SpiceyOptions */
+  int32_t interpreter;      /* 1, 2 or 3, see SpiceyOptions (3: n_workgroups = n_inst, inst_per_wg = wgs_per_inst = 1, lds_bytes 0 on
+                               the global slab, the fields of the sparse program 0) */
   int32_t geometry;         /* 1 or 2 (v2), see SpiceyOptions */
   int32_t tail_levels;      /* v2: elimination-tree levels merged into the single-wave tail phase */
   int32_t wgs_per_inst;     /* workgroups cooperating on one instance (group mode), else 1 */
@@ -209,14 +219,16 @@ int32_t spicey_reset_state(SpiceyHandle *h, void *stream);
 /* Total solves (= sum of iterations) executed by the last run, all instances. */
 int64_t spicey_last_solve_count(SpiceyHandle *h);
 /* Diagnostics (SpiceyOptions.diagnostics bit 0).  The reference eliminates with partial pivoting and skips a row update whose
- * multiplier a_ik / pivot is below 1e-15 (`if (Math.abs(f) < EPS) continue`, solveReal.ts:45): a nonzero coupling dropped —
+ * multiplier a_ik / pivot is below 1e-15 (`if (Math.abs(f) < EPS) continue`, solveReal.ts:46): a nonzero coupling dropped —
  * floor conductances (diode gd 1e-12 S, switch 1/Roff) next to a clamped diode, a milliohm resistor or a large C/dt.  A sparse
  * static pivot order cannot reproduce that entry for entry; this library PERFORMS those updates (the physically consistent
  * answer) and says when the situation occurs: the number of (solve, column) pairs of the last run in which the stamped
  * matrix column held a nonzero entry below 1e-15 x the column's largest magnitude (per instance in per_inst[n_inst] if not
  * NULL; the return value is the sum; -1 without the option).  0 means the reference took no such shortcut on the stamped
  * matrix and the two results agree to the 1e-9 parity bar; > 0 means the reference's own result may differ from this one by
- * up to |v_k| * |a_ik| / a_ii per flagged coupling ("Where the reference skips row updates"). */
+ * up to |v_k| * |a_ik| / a_ii per flagged coupling ("Where the reference skips row updates").
+ * With SpiceyOptions.interpreter = 3 (reference order) the count is exact instead: the nonzero multipliers the skip dropped in
+ * the run's completed solves, per instance. */
 int64_t spicey_last_skip_risk(SpiceyHandle *h, int64_t *per_inst);
 /* Diagnostics (SpiceyOptions.diagnostics bit 1): out[n_inst][steps+1] = per step the largest |vd(x) - vd_lin| over the diodes,
  * vd_lin being the junction voltage the step's LAST solve was linearised at (vdPrev on iteration 0, the previous iterate

@@ -18,3 +18,8 @@ hipError_t spicey_launch_tran_v2(const SpiceyProg &Ph, const SpiceyResident &Qh,
 // group mode: R.wgs_per_group workgroups per K instances, workspace in global memory (large circuits)
 hipError_t spicey_launch_tran_grp(const SpiceyProg &P, const SpiceyRun &R, int K, int n_groups, int threads, hipStream_t st);
 int spicey_grp_blocks_per_cu(const SpiceyProg &P, int K, int threads);  // occupancy of that kernel (0: cannot run)
+
+// reference-order engine (exact.hip): one workgroup per instance; P, R in DEVICE memory; lds = dynamic LDS bytes, 0 = the
+// workspace is R->gW
+struct SpiceyExactProg;
+hipError_t spicey_launch_exact(const SpiceyExactProg *P, const SpiceyRun *R, int grid, int threads, size_t lds, hipStream_t st);

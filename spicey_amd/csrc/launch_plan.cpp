@@ -75,8 +75,63 @@ static int pick_threads(const HostProgram &hp, bool v2) {
   return 1024;
 }
 
+SpiceyExactWs spicey_exact_ws(const SpiceyDesc &d) {
+  SpiceyExactWs w{};
+  const int64_t n = (int64_t)d.n_nodes + d.nV;
+  w.ld = (int32_t)((n + 1) | 1);
+  w.mw = (int32_t)((n + 31) / 32);
+  int32_t o = 0;
+  auto slots = [&](int32_t &at, int32_t cnt) { at = o; o += cnt; };
+  slots(w.qR, d.nR); slots(w.qGc, d.nC); slots(w.qIc, d.nC); slots(w.qGl, d.nL); slots(w.qIl, d.nL);
+  slots(w.qS, d.nS); slots(w.qV, d.nV); slots(w.qGd, d.nD); slots(w.qIeq, d.nD); slots(w.qOne, 1);
+  w.nq = o;
+  int64_t at = 0;
+  auto carve = [&](int64_t &off, int64_t doubles) { off = at; at += doubles; };
+  carve(w.A, n * w.ld); carve(w.x, n); carve(w.q, w.nq); carve(w.vdlin, d.nD); carve(w.act_f, n);
+  carve(w.perm, (n + 1) / 2); carve(w.act_r, (n + 1) / 2); carve(w.mask, (n * w.mw + 1) / 2);
+  w.doubles = (at + 1) & ~int64_t(1);  // (16-byte multiple: the next instance's slab stays aligned)
+  return w;
+}
+
+// interpreter 3: the reference-order engine (exact_exec.h).  Sizes and options only; no symbolic program, no structural
+// pre-check (the reference throws only where its own pivot search does).
+static int32_t plan_exact(const SpiceyDesc *desc, const SpiceyOptions &opt, const PlanDevice &dev, HostProgram &hp, LaunchPlan &plan,
+                          std::string &err) {
+  auto fail = [&](int32_t code, const char *msg) { err = msg; return code; };
+  int32_t rc = spicey_check_desc(desc, err);
+  if (rc != SPICEY_OK) return rc;
+  if (opt.inst_per_wg > 1) return fail(SPICEY_ERR_BAD_DESC, "interpreter 3 (reference order) runs one instance per workgroup: inst_per_wg must be 0 or 1");
+  if (opt.geometry != 0) return fail(SPICEY_ERR_BAD_DESC, "interpreter 3 (reference order) has no geometry option: geometry must be 0");
+  if (opt.front_cut > 0) return fail(SPICEY_ERR_BAD_DESC, "interpreter 3 (reference order) has no dense fronts: front_cut must be <= 0");
+  if (opt.wgs_per_inst > 1) return fail(SPICEY_ERR_BAD_DESC, "interpreter 3 (reference order) runs one workgroup per instance: wgs_per_inst must be 0 or 1");
+  if (opt.profile) return fail(SPICEY_ERR_BAD_DESC, "interpreter 3 (reference order) has no phase profile: profile must be 0");
+  if (opt.threads != 0 && (opt.threads > 1024 || opt.threads < 64 || (opt.threads & 63)))
+    return fail(SPICEY_ERR_BAD_DESC, "threads must be a multiple of 64 in [64, 1024]");
+  SpiceyProg &P = hp.hdr;
+  P.n = desc->n_nodes + desc->nV;
+  P.nR = desc->nR; P.nC = desc->nC; P.nL = desc->nL; P.nV = desc->nV; P.nS = desc->nS; P.nD = desc->nD;
+  P.nOut = (desc->n_out > 0 && desc->out_nodes) ? desc->n_out : desc->n_nodes;
+  P.nCur = P.nR + P.nC + P.nL + P.nV + P.nS + P.nD;
+  if ((int64_t)P.n * ((P.n + 1) | 1) >= ((int64_t)1 << 32)) return fail(SPICEY_ERR_BAD_DESC, "interpreter 3 (reference order): n x (n + 1) must stay below 2^32 entries");
+  int ncu = 256;
+  if ((rc = dev.open(opt.device, &ncu, err)) != SPICEY_OK) return rc;
+  plan.n_inst = desc->n_inst;
+  plan.interp = 3;
+  plan.K = 1;
+  plan.G = 1;
+  plan.grid = desc->n_inst;
+  // 64 threads up to n = 64 (one wave: its barriers cost next to nothing), 256 above
+  plan.T = opt.threads > 0 ? opt.threads : (P.n <= 64 ? 64 : 256);
+  plan.xws = spicey_exact_ws(*desc);
+  const size_t bytes = (size_t)plan.xws.doubles * sizeof(double);
+  plan.lds = !opt.force_global && bytes + SPICEY_EXACT_STATIC_LDS <= SPICEY_LDS_MAX;
+  plan.lds_bytes = plan.lds ? bytes : 0;
+  return SPICEY_OK;
+}
+
 int32_t spicey_plan(const SpiceyDesc *desc, const SpiceyOptions &opt, const SpiceyKnobs &knobs, const PlanDevice &dev, HostProgram &hp,
                     HostResident &hres, LaunchPlan &plan, std::string &err) {
+  if (opt.interpreter == 3) return plan_exact(desc, opt, dev, hp, plan, err);
   auto fail = [&](int32_t code, const char *msg) { err = msg; return code; };
   // dense fronts: explicit level, or automatic for large nonlinear circuits that run one instance per workgroup (the
   // interleaved K > 1 layouts and forced interpreter 2 keep the task lists); -1 = never
@@ -205,6 +260,17 @@ void fill_info(const LaunchPlan &plan, const HostProgram &hp, const HostResident
   const SpiceyProg &P = hp.hdr;
   memset(info, 0, sizeof(*info));
   info->n_var = P.n;
+  if (plan.interp == 3) {  // reference-order engine: one workgroup per instance, no program; the rest does not apply
+    info->threads = plan.T;
+    info->inst_per_wg = 1;
+    info->lds_bytes = plan.lds ? (int32_t)plan.lds_bytes : 0;
+    info->n_cur = P.nCur;
+    info->n_out = P.nOut;
+    info->n_workgroups = plan.grid;
+    info->interpreter = 3;
+    info->wgs_per_inst = 1;
+    return;
+  }
   info->nnz_a = hp.nnzA;
   info->nnz_lu = P.nLU;
   info->n_levels = P.nLevels;

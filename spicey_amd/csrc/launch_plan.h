@@ -59,6 +59,18 @@ struct PlanDevice {
   std::function<int(const SpiceyProg &P, int K, int threads)> grp_blocks_per_cu;
 };
 
+// Reference-order engine (SpiceyOptions.interpreter = 3, exact_exec.h): the per-instance workspace, offsets in doubles
+// from its base (the int32 arrays start at a double boundary).  A | b is n rows of stride ld (n + 1 padded to an odd
+// count: column reads of the pivot search stay off one LDS bank); q = the stamp quantities of one iteration (R 1/R | C Gc
+// | C Ieq | L Gl | L iPrev | S 1/R | V source | D gd | D ieq | 1.0), slot offsets of each kind below.
+struct SpiceyExactWs {
+  int32_t ld, mw;  // row stride of A | b; 32-bit words of one row's nonzero-column mask
+  int32_t nq, qR, qGc, qIc, qGl, qIl, qS, qV, qGd, qIeq, qOne;
+  int64_t A, x, q, vdlin, act_f, perm, act_r, mask, doubles;
+};
+SpiceyExactWs spicey_exact_ws(const SpiceyDesc &d);
+#define SPICEY_EXACT_STATIC_LDS 256  // bytes of static LDS of the exact kernel (reduction scratch, counters)
+
 struct LaunchPlan {
   int n_inst = 0, K = 1, T = 256, grid = 1, interp = 1;
   int G = 1;             // workgroups per instance group (group mode: global workspace only)
@@ -66,6 +78,7 @@ struct LaunchPlan {
   bool lds = true;       // workspace in LDS (else global memory)
   size_t lds_bytes = 0;
   int64_t algo_bytes = 0;
+  SpiceyExactWs xws{};   // interpreter 3 only
 };
 
 // Every decision of spicey_create, in its order and with its error codes and messages (err).  Builds hp (and, for the

@@ -276,7 +276,7 @@ struct SpiceyRun {
   unsigned long long *front_ticks;
   // diagnostics (null = off; none of them feeds back into the solve)
   //   skip_risk [n_inst]: (solve, column) pairs whose stamped matrix column holds a nonzero entry below 1e-15 x the column's
-  //     largest — where the reference's partial pivoting makes `|f| < EPS` (solveReal.ts:45) drop a row update this build performs
+  //     largest — where the reference's partial pivoting makes `|f| < EPS` (solveReal.ts:46) drop a row update this build performs
   //   lin_vd [n_inst][nD]: junction voltage every diode was linearised at for the solve in progress (simulateTRAN.ts:85);
   //   lin_err [n_inst][steps+1]: max over the diodes of |vd(x) - lin_vd| after the step's last solve, as the bit pattern of a
   //     non-negative double (combined with integer atomic max; zeroed by the host before the launch)

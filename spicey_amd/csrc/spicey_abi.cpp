@@ -16,6 +16,7 @@
 
 #include "../../include/spicey_hip.h"
 #include "devbuf.h"
+#include "exact_plan.h"
 #include "kernels.h"
 #include "launch_plan.h"
 #include "symbolic.h"
@@ -65,6 +66,9 @@ struct SpiceyHandle {
   // live, the descriptor's (spicey_reset_state), and in group mode the state as it entered the launch in flight (a launch
   // that ends in the bounded-spin abort is repeated once)
   StateBufs state, state0, state_s;
+  // reference-order engine (interpreter 3): stamp lists and terminals, their device copy and descriptor, global workspace
+  HostExactProg xp;
+  DevBuf<uint32_t> d_xblob; DevBuf<SpiceyExactProg> d_xprog; DevBuf<double> d_xws;
   DevBuf<unsigned int> d_gsync; DevBuf<int32_t> d_gflags;
   // dense fronts: workspace [grid][front_ws], schedule of the G workgroups, done flags [grid][2 nFronts]
   DevBuf<double> d_front_ws;
@@ -211,8 +215,62 @@ static int32_t open_device(int device, int *ncu, std::string &err) {
   return SPICEY_OK;
 }
 
+// per-instance element values and the state (live and as the descriptor carried it)
+static int32_t upload_values(SpiceyHandle *h, const SpiceyDesc *desc) {
+  const SpiceyProg &P = h->hp.hdr;
+  const size_t ni = (size_t)h->plan.n_inst;
+  HIPCHK(h, dev_upload(h->d_R, ni * P.nR, desc->R_val));
+  HIPCHK(h, dev_upload(h->d_C, ni * P.nC, desc->C_val));
+  HIPCHK(h, dev_upload(h->d_L, ni * P.nL, desc->L_val));
+  HIPCHK(h, dev_upload(h->d_Sron, ni * P.nS, desc->S_ron));
+  HIPCHK(h, dev_upload(h->d_Sroff, ni * P.nS, desc->S_roff));
+  HIPCHK(h, dev_upload(h->d_Svon, ni * P.nS, desc->S_von));
+  HIPCHK(h, dev_upload(h->d_Svoff, ni * P.nS, desc->S_voff));
+  HIPCHK(h, dev_upload(h->d_Dis, ni * P.nD, desc->D_is));
+  HIPCHK(h, dev_upload(h->d_Dn, ni * P.nD, desc->D_n));
+  HIPCHK(h, upload_state(h->state, desc, P, ni));
+  HIPCHK(h, upload_state(h->state0, desc, P, ni));
+  return SPICEY_OK;
+}
+
+static int32_t create_stream(SpiceyHandle *h) {
+  if (hipStreamCreate(&h->stream) != hipSuccess || hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess) {
+    h->err = "stream/event creation failed";
+    return SPICEY_ERR_HIP;
+  }
+  return SPICEY_OK;
+}
+
+// the device side of a reference-order handle: stamp lists, argument structs, values and state, status words, workspace
+static int32_t allocate_exact(SpiceyHandle *h, const SpiceyDesc *desc) {
+  const LaunchPlan &pl = h->plan;
+  const size_t ni = (size_t)pl.n_inst;
+  spicey_build_exact(*desc, pl.xws, h->xp);
+  HIPCHK(h, dev_upload(h->d_xblob, h->xp.blob.size(), h->xp.blob.data()));
+  const SpiceyExactProg xd = h->xp.bind(h->d_xblob);
+  HIPCHK(h, dev_upload(h->d_xprog, 1, &xd));
+  HIPCHK(h, dev_upload(h->d_Rstruct, 1));
+  if (const int32_t rc = upload_values(h, desc); rc != SPICEY_OK) return rc;
+  HIPCHK(h, dev_upload(h->d_status, (size_t)pl.grid * 4));
+  HIPCHK(h, dev_upload(h->d_solves, (size_t)pl.grid));
+  if (h->opt.diagnostics & 1) HIPCHK(h, dev_upload(h->d_skip, ni));
+  if (!pl.lds) {  // one n x (n + 1) slab (and the vectors beside it) per instance
+    const size_t per = (size_t)pl.xws.doubles;
+    if (per > (SIZE_MAX / sizeof(double)) / ni || h->d_xws.alloc(per * ni) != hipSuccess) {
+      (void)hipGetLastError();
+      char buf[256];
+      snprintf(buf, sizeof(buf), "interpreter 3 (reference order): cannot allocate the global workspace of %zu instances x %zu bytes (n = %d: a dense n x (n + 1) matrix each)",
+               ni, per * sizeof(double), h->hp.hdr.n);
+      h->err = buf;
+      return SPICEY_ERR_HIP;
+    }
+  }
+  return create_stream(h);
+}
+
 // the device side of a planned handle: program, argument structs, per-instance values and state, workspaces, stream, events
 static int32_t allocate(SpiceyHandle *h, const SpiceyDesc *desc) {
+  if (h->plan.interp == 3) return allocate_exact(h, desc);
   const SpiceyProg &P = h->hp.hdr;
   const LaunchPlan &pl = h->plan;
   const size_t ni = (size_t)pl.n_inst;
@@ -225,17 +283,7 @@ static int32_t allocate(SpiceyHandle *h, const SpiceyDesc *desc) {
     HIPCHK(h, dev_upload(h->d_Qstruct, 1, &h->dres));
     HIPCHK(h, dev_upload(h->d_Rstruct, 1));
   }
-  HIPCHK(h, dev_upload(h->d_R, ni * P.nR, desc->R_val));
-  HIPCHK(h, dev_upload(h->d_C, ni * P.nC, desc->C_val));
-  HIPCHK(h, dev_upload(h->d_L, ni * P.nL, desc->L_val));
-  HIPCHK(h, dev_upload(h->d_Sron, ni * P.nS, desc->S_ron));
-  HIPCHK(h, dev_upload(h->d_Sroff, ni * P.nS, desc->S_roff));
-  HIPCHK(h, dev_upload(h->d_Svon, ni * P.nS, desc->S_von));
-  HIPCHK(h, dev_upload(h->d_Svoff, ni * P.nS, desc->S_voff));
-  HIPCHK(h, dev_upload(h->d_Dis, ni * P.nD, desc->D_is));
-  HIPCHK(h, dev_upload(h->d_Dn, ni * P.nD, desc->D_n));
-  HIPCHK(h, upload_state(h->state, desc, P, ni));
-  HIPCHK(h, upload_state(h->state0, desc, P, ni));
+  if (const int32_t rc = upload_values(h, desc); rc != SPICEY_OK) return rc;
   HIPCHK(h, dev_upload(h->d_gstat, ni * P.nGstat));
   HIPCHK(h, dev_upload(h->d_statv, ni * P.nLU));
   HIPCHK(h, dev_upload(h->d_rcoef, ni * (size_t)(P.nRhsIdx + 1)));
@@ -268,11 +316,7 @@ static int32_t allocate(SpiceyHandle *h, const SpiceyDesc *desc) {
   }
   if (h->opt.diagnostics & 1) HIPCHK(h, dev_upload(h->d_skip, ni));
   if ((h->opt.diagnostics & 2) && P.nD > 0) HIPCHK(h, dev_upload(h->d_linvd, ni * P.nD));
-  if (hipStreamCreate(&h->stream) != hipSuccess || hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess) {
-    h->err = "stream/event creation failed";
-    return SPICEY_ERR_HIP;
-  }
-  return SPICEY_OK;
+  return create_stream(h);
 }
 
 extern "C" int32_t spicey_create(const SpiceyDesc *desc, const SpiceyOptions *opt, SpiceyHandle **out) {
@@ -312,7 +356,9 @@ static int32_t enqueue_kernel(SpiceyHandle *h, const SpiceyRun &R, hipStream_t s
   int slot = -1;
   HIPCHK(h, gate_before_launch(g, group, st, &slot));
   HIPCHK(h, hipEventRecord(h->ev0, st));  // (argument upload, flag resets and admission waits stay outside the timed kernel)
-  if (h->plan.interp == 2) {
+  if (h->plan.interp == 3) {
+    HIPCHK(h, spicey_launch_exact(h->d_xprog, h->d_Rstruct, h->plan.grid, h->plan.T, h->plan.lds ? h->plan.lds_bytes : 0, st));
+  } else if (h->plan.interp == 2) {
     HIPCHK(h, spicey_launch_tran_v2(h->dprog, h->dres, h->d_Pstruct, h->d_Qstruct, h->d_Rstruct, h->plan.K, h->plan.grid, h->plan.T, st, h->plan.packed));
   } else if (group) {
     HIPCHK(h, spicey_launch_tran_grp(h->dprog, R, h->plan.K, h->plan.grid, h->plan.T, st));
@@ -366,7 +412,7 @@ extern "C" int32_t spicey_run_device(SpiceyHandle *h, int64_t steps, double dt, 
   R.S_ron = h->d_Sron; R.S_roff = h->d_Sroff; R.S_von = h->d_Svon; R.S_voff = h->d_Svoff;
   R.D_is = h->d_Dis; R.D_n = h->d_Dn;
   R.C_vprev = h->state.Cv; R.L_iprev = h->state.Li; R.D_vdprev = h->state.Dv; R.S_ison = h->state.Son;
-  R.gstat = h->d_gstat; R.statv = h->d_statv; R.rcoef = h->d_rcoef; R.gW = h->d_gW; R.dpar = h->d_dpar;
+  R.gstat = h->d_gstat; R.statv = h->d_statv; R.rcoef = h->d_rcoef; R.gW = pl.interp == 3 ? h->d_xws : h->d_gW; R.dpar = h->d_dpar;
   R.src = d_src_table; R.out_v = d_out_v; R.out_i = d_out_i; R.iters = d_iters;
   R.status = h->d_status; R.solves = h->d_solves; R.prof = h->d_prof;
   // diagnostics: counters and per-step maxima start from zero in every run (reset_launch_words)
@@ -410,7 +456,7 @@ extern "C" int32_t spicey_run_device(SpiceyHandle *h, int64_t steps, double dt, 
     R.force_abort = h->knobs.force_group_abort ? 1 : 0;
     h->grp_R = R;
   }
-  if (pl.interp == 2) {
+  if (pl.interp == 2 || pl.interp == 3) {  // (these kernels read their SpiceyRun from device memory)
     h->run_args = R;
     HIPCHK(h, hipMemcpyAsync(h->d_Rstruct, &h->run_args, sizeof(SpiceyRun), hipMemcpyHostToDevice, st));
   }

@@ -386,7 +386,7 @@ int32_t spicey_build_program(const SpiceyDesc *d, HostProgram &hp, std::string &
   return rc;
 }
 
-static int32_t build_program_impl(const SpiceyDesc *d, HostProgram &hp, std::string &err, const bool slot_major, int front_cut, const bool pcr_top, const bool hybrid) {
+int32_t spicey_check_desc(const SpiceyDesc *d, std::string &err) {
   if (!d) { err = "null descriptor"; return SPICEY_ERR_BAD_DESC; }
   if (d->abi_version != SPICEY_ABI_VERSION) { err = "abi_version mismatch"; return SPICEY_ERR_BAD_DESC; }
   const int nN = d->n_nodes, nR = d->nR, nC = d->nC, nL = d->nL, nV = d->nV, nS = d->nS, nD = d->nD;
@@ -411,11 +411,18 @@ static int32_t build_program_impl(const SpiceyDesc *d, HostProgram &hp, std::str
     err = "null value array";
     return SPICEY_ERR_BAD_DESC;
   }
-  const int nOut = (d->n_out > 0 && d->out_nodes) ? d->n_out : nN;
   if (d->n_out > 0 && d->out_nodes)
-    for (int i = 0; i < nOut; i++)
+    for (int i = 0; i < d->n_out; i++)
       if (d->out_nodes[i] < 0 || d->out_nodes[i] > nN) { err = "out_nodes id out of range"; return SPICEY_ERR_BAD_DESC; }
+  return SPICEY_OK;
+}
 
+static int32_t build_program_impl(const SpiceyDesc *d, HostProgram &hp, std::string &err, const bool slot_major, int front_cut, const bool pcr_top, const bool hybrid) {
+  const int32_t rc0 = spicey_check_desc(d, err);
+  if (rc0 != SPICEY_OK) return rc0;
+  const int nN = d->n_nodes, nR = d->nR, nC = d->nC, nL = d->nL, nV = d->nV, nS = d->nS, nD = d->nD;
+  const int n = nN + nV;
+  const int nOut = (d->n_out > 0 && d->out_nodes) ? d->n_out : nN;
   // ---- 1. pattern of A, by rows and by columns (original numbering) ---------------------------
   Adj arow(n), acol(n);
   auto add = [&](int r, int c) {

@@ -50,6 +50,10 @@ struct HostProgram {
   std::vector<size_t> offsets;  // section offsets in pack() order
 };
 
+// The descriptor checks every handle starts with (counts, node ids, value arrays, out_nodes): SPICEY_OK or
+// SPICEY_ERR_BAD_DESC with the message in err.
+int32_t spicey_check_desc(const SpiceyDesc *d, std::string &err);
+
 // Builds the program for `d`'s topology.  Returns SPICEY_OK or SPICEY_ERR_BAD_DESC (err filled).
 // A structurally singular matrix is not an error here: hp.structurally_singular is set and the
 // run reports SPICEY_ERR_SINGULAR, like the reference throws at the first solve.

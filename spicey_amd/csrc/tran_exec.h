@@ -181,7 +181,7 @@ SPICEY_HD double spicey_switch_g(int on, double ron, double roff) {  // simulate
 // ---- diagnostics -------------------------------------------------------------------------------------------------------
 // Right after phase B the workspace holds the stamped matrix A (leaf diagonals as reciprocals).  The reference eliminates
 // with partial pivoting, so its multiplier for row i at column k is a_ik / max_j |a_jk| (of the matrix as updated so far)
-// and `if (Math.abs(f) < EPS) continue` (solveReal.ts:45) SKIPS the row update when that is below 1e-15 — a nonzero
+// and `if (Math.abs(f) < EPS) continue` (solveReal.ts:46) SKIPS the row update when that is below 1e-15 — a nonzero
 // coupling silently dropped, which a static sparse order does not reproduce (deviations).  This pass counts the
 // columns of the STAMPED matrix in which some nonzero entry is below 1e-15 x the column's largest: the first-order
 // indicator of that situation (exact for the first pivot; fills and updated entries are not looked at).  One thread per

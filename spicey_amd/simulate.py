@@ -34,7 +34,20 @@ def _default_backend():
     return HipBackend(diagnostics=1)
 
 
-def simulateTRAN(ckt: ParsedCircuit, backend=None, as_lists: bool = True) -> Optional[dict]:
+def _exact_backend():
+    from .lib import HipBackend
+
+    # interpreter 3: the reference-order engine (include/spicey_hip.h); diagnostics bit 0 then counts the multipliers that
+    # the reference's `if (Math.abs(f) < EPS) continue` (solveReal.ts:46) dropped
+    return HipBackend(diagnostics=1, interpreter=3)
+
+
+def simulateTRAN(ckt: ParsedCircuit, backend=None, as_lists: bool = True, exact_order: bool = False) -> Optional[dict]:
+    """exact_order=True runs the reference's own algorithm on the GPU (dense stamp, partial pivoting, its row-update skip):
+    the reference's numbers bit for bit, its singular-matrix errors included; `skipRisk` is then the number of nonzero
+    multipliers that skip dropped.  The default is the sparse static-order path."""
+    if exact_order and backend is not None:
+        raise ValueError("simulateTRAN: pass either backend= or exact_order=True, not both")
     tran = ckt.analyses.get("tran")
     if not tran:
         return None
@@ -43,7 +56,7 @@ def simulateTRAN(ckt: ParsedCircuit, backend=None, as_lists: bool = True) -> Opt
     # afterwards (simulateTRAN.ts:240-249); here only the probed columns are written, moved and re-keyed
     flat = abi.flatten(ckt, probe_filter=True)
     src = abi.source_table(ckt, dt, steps)
-    be = backend if backend is not None else _default_backend()
+    be = backend if backend is not None else (_exact_backend() if exact_order else _default_backend())
     res = be.run(flat, steps, dt, src, want_currents=True)
     if res["status"] == abi.ERR_SINGULAR:
         raise SingularMatrixError(res.get("detail", ""))
@@ -102,20 +115,24 @@ def simulateTRAN(ckt: ParsedCircuit, backend=None, as_lists: bool = True) -> Opt
     # (probes, if any, were applied on the device: node_voltages holds exactly the probed nodes, in JS key order)
     # Beyond the reference's three keys: `iterations` (solves per step) and `skipRisk` — the number of (solve, column) pairs
     # in which the stamped matrix had a nonzero entry below 1e-15 x its column's largest, i.e. where the reference's
-    # `if (Math.abs(f) < EPS) continue` (solveReal.ts:45) drops a row update that this solver performs (0: the two agree to
-    # the 1e-9 bar; > 0: the reference's own numbers may differ, include/spicey_hip.h spicey_last_skip_risk)
+    # `if (Math.abs(f) < EPS) continue` (solveReal.ts:46) drops a row update that this solver performs (0: the two agree to
+    # the 1e-9 bar; > 0: the reference's own numbers may differ, include/spicey_hip.h spicey_last_skip_risk); with exact_order
+    # the count of nonzero multipliers that line dropped
     skip = res.get("skip_risk")
     return {"times": times, "nodeVoltages": node_voltages, "elementCurrents": element_currents,
             "iterations": res.get("iters"), "skipRisk": int(skip[0]) if skip is not None else 0}
 
 
-def simulate(netlist_text: str, backend=None) -> dict:
-    """simulate.ts:5-10: parse, AC sweep (if an .ac card is present), transient (if a .tran card is present)."""
+def simulate(netlist_text: str, backend=None, exact_order: bool = False) -> dict:
+    """simulate.ts:5-10: parse, AC sweep (if an .ac card is present), transient (if a .tran card is present).
+    exact_order: the transient runs the reference-order engine (simulateTRAN); the AC sweep is unaffected."""
     from .ac import simulateAC  # (ac.py imports this module's number formatter)
 
+    if exact_order and backend is not None:
+        raise ValueError("simulate: pass either backend= or exact_order=True, not both")
     circuit = parseNetlist(netlist_text)
     ac = simulateAC(circuit, backend=backend)
-    tran = simulateTRAN(circuit, backend=backend)
+    tran = simulateTRAN(circuit, backend=backend, exact_order=exact_order)
     return {"circuit": circuit, "ac": ac, "tran": tran}
 
 

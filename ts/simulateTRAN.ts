@@ -36,7 +36,13 @@ function flatten(ckt: ParsedCircuit): FlatCircuit {
   }
 }
 
-function simulateTRAN(ckt: ParsedCircuit) {
+export type SimulateTranOptions = {
+  /** run the reference's own algorithm on the GPU (dense stamp, partial pivoting, its |f| < EPS row-update skip): the
+   *  reference's numbers bit for bit, its "Singular matrix (real)" included; skipRisk = the multipliers that skip dropped */
+  exactOrder?: boolean
+}
+
+function simulateTRAN(ckt: ParsedCircuit, options?: SimulateTranOptions) {
   if (!ckt.analyses.tran) return null
   const { dt: dtRequested, tstop } = ckt.analyses.tran
   const { dt, steps } = computeEffectiveTimeStep(dtRequested, tstop)
@@ -63,7 +69,7 @@ function simulateTRAN(ckt: ParsedCircuit) {
     if (wanted.length === 0 || wanted.includes(ckt.nodes.rev[id]!.toUpperCase())) recorded.push(id)
   }
   if (wanted.length > 0) flat.outNodes = Int32Array.from(recorded)
-  const res = runTransientNative(flat, steps, dt, src)
+  const res = runTransientNative(flat, steps, dt, src, options?.exactOrder ? { interpreter: 3 } : undefined)
 
   // re-key: one strided column copy per recorded node / per element, then a plain number[] (the reference's result type);
   // keys enter the objects in the reference's insertion order so that JS key order (integer-like names first) matches
@@ -108,7 +114,7 @@ function simulateTRAN(ckt: ParsedCircuit) {
   ckt.S.filter((s) => s.model).forEach((s, i) => (s.isOn = res.state.isOn[i] !== 0))
 
   // (`skipRisk` is this solver's addition to the reference's three keys: > 0 says that the reference's own row-update skip,
-  // solveReal.ts:45, may have made ITS numbers differ from these — ts/spiceyHip.ts, NativeTranResult.skipRisk)
+  // solveReal.ts:46, may have made ITS numbers differ from these — ts/spiceyHip.ts, NativeTranResult.skipRisk)
   return { times, nodeVoltages, elementCurrents, skipRisk: res.skipRisk }
 }
 

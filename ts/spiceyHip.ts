@@ -107,16 +107,23 @@ export type NativeTranResult = {
   iters: Int32Array // [steps+1]
   state: { vPrev: Float64Array; iPrev: Float64Array; vdPrev: Float64Array; isOn: Int32Array }
   /** (solve, column) pairs in which the stamped matrix had a nonzero entry below 1e-15 x its column's largest: where the
-   *  reference's `if (Math.abs(f) < EPS) continue` (solveReal.ts:45) drops a row update this solver performs; 0 = none */
+   *  reference's `if (Math.abs(f) < EPS) continue` (solveReal.ts:46) drops a row update this solver performs; 0 = none */
   skipRisk: number
 }
 
+export type NativeTranOptions = {
+  /** SpiceyOptions.interpreter: 0 = automatic (default), 3 = the reference-order engine — the reference's own dense
+   *  elimination on the GPU, bit-identical to it; skipRisk then counts the multipliers its |f| < EPS test dropped */
+  interpreter?: number
+}
+
 /** One transient run on the GPU.  Throws Error("Singular matrix (real)") like solveReal.ts:28. */
-export function runTransientNative(f: FlatCircuit, steps: number, dt: number, srcTable: Float64Array): NativeTranResult {
+export function runTransientNative(f: FlatCircuit, steps: number, dt: number, srcTable: Float64Array, options?: NativeTranOptions): NativeTranResult {
   const { buf, keep } = packDesc(f)
   const opt = new ArrayBuffer(SpiceyOptionsLayout.size) // zeros: device 0, auto geometry
   new DataView(opt).setInt32(SpiceyOptionsLayout.fields.want_currents.offset, 1, true)
   new DataView(opt).setInt32(SpiceyOptionsLayout.fields.diagnostics.offset, 1, true)
+  if (options?.interpreter) new DataView(opt).setInt32(SpiceyOptionsLayout.fields.interpreter.offset, options.interpreter, true)
   const hOut = new BigUint64Array(1)
   let rc = C.spicey_create(ptr(buf), ptr(opt), ptr(hOut))
   void keep
