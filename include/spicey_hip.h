@@ -299,9 +299,19 @@ const char *spicey_version(void);
  *   out_i   [n_inst][n_freq][nR+nC+nL+nV][2] complex currents in the reference's recording order R, C, L, V, or NULL
  * HOST buffers; blocking.  Status: SPICEY_ERR_SINGULAR -> Error("Singular matrix (complex)") (solveComplex.ts:28),
  * SPICEY_ERR_COMPLEX_DIV -> Error("Complex divide by ~0") (a pivot with |z|^2 < 1e-15, Complex.ts:40-42); the message of
- * spicey_ac_last_error names the first failing (instance, frequency), the one at which the reference would throw. */
+ * spicey_ac_last_error names the first failing (instance, frequency), the one at which the reference would throw.
+ * spicey_ac_create reads SpiceyOptions.device, threads, force_global, debug bits 4 and 7, and interpreter: 3 selects the
+ * reference-order AC engine — the reference's own solveComplex (dense stamp in element order, partial pivoting on V8's
+ * Math.hypot, its |f| < EPS row-update skip, back substitution in its order), one workgroup per (instance, frequency):
+ * every output bit and every SPICEY_ERR_SINGULAR / SPICEY_ERR_COMPLEX_DIV exactly where the reference has them (an
+ * inductor's "Complex divide by ~0" included, frequency by frequency; no structural pre-check).  A | b in LDS up to n ~ 97
+ * unknowns, else an n x (n + 1) slab per slot in global memory, at most 1 GiB per launch (force_global = 1: always).
+ * threads: 0 = 64 for n <= 64, else 256; 64..1024 honoured (same bits), others refused with SPICEY_ERR_BAD_DESC.
+ * spicey_ac_get_info then reports interpreter = 3, threads, lds_bytes (0 on the slab) and n_workgroups (the slots of
+ * the last run).  Never chosen automatically; any other interpreter value keeps the default path. */
 typedef struct SpiceyAcHandle SpiceyAcHandle;
-int32_t spicey_ac_create(const SpiceyDesc *desc, const SpiceyOptions *opt /* device, threads, force_global */, SpiceyAcHandle **out);
+int32_t spicey_ac_create(const SpiceyDesc *desc, const SpiceyOptions *opt /* device, threads, force_global, debug, interpreter */,
+                         SpiceyAcHandle **out);
 int32_t spicey_ac_run(SpiceyAcHandle *h, int64_t n_freq, const double *freqs, const double *vph, double *out_v, double *out_i);
 int32_t spicey_ac_get_info(SpiceyAcHandle *h, SpiceyInfo *info);
 double spicey_ac_last_kernel_ms(SpiceyAcHandle *h);

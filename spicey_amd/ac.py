@@ -57,13 +57,19 @@ def source_phasors(ckt: ParsedCircuit) -> np.ndarray:
     return out
 
 
-def _host_checks(ckt: ParsedCircuit, freqs: List[float]) -> None:
-    """Errors the reference throws while building the system, before any solve (simulateAC.ts:39,51-53)."""
+def _check_resistors(ckt: ParsedCircuit, freqs: List[float]) -> None:
     if not len(freqs):
         return
     for r in ckt.R:  # :39, thrown at the first frequency
         if r.R <= 0:
             raise ValueError(f"R {r.name} must be > 0")
+
+
+def _host_checks(ckt: ParsedCircuit, freqs: List[float]) -> None:
+    """Errors the reference throws while building the system, before any solve (simulateAC.ts:39,51-53)."""
+    if not len(freqs):
+        return
+    _check_resistors(ckt, freqs)
     if ckt.L:  # Complex.from(1,0).div(denom) throws when |denom|^2 < EPS although |denom| >= EPS (Complex.ts:40-42)
         w = (2 * math.pi) * np.asarray(freqs, dtype=np.float64)[:, None] * np.array([ind.L for ind in ckt.L])[None, :]
         if np.any(~(np.abs(w) < EPS) & (w * w < EPS)):
@@ -84,16 +90,30 @@ class SingularComplexMatrixError(RuntimeError):
         self.detail = detail
 
 
-def simulateAC(ckt: ParsedCircuit, backend=None, freqs: Optional[List[float]] = None) -> Optional[dict]:
+def _exact_backend():
+    from .lib import HipAcExactBackend
+
+    return HipAcExactBackend()
+
+
+def simulateAC(ckt: ParsedCircuit, backend=None, freqs: Optional[List[float]] = None, exact_order: bool = False) -> Optional[dict]:
+    """exact_order=True runs the reference's own solveComplex on the GPU (dense stamp in element order, partial pivoting on
+    V8's Math.hypot, its |f| < EPS row-update skip): the reference's numbers bit for bit and its errors at the frequency
+    where it throws them ("Complex divide by ~0" of an inductor included).  The default is the sparse static-order path."""
+    if exact_order and backend is not None:
+        raise ValueError("simulateAC: pass either backend= or exact_order=True, not both")
     ac = ckt.analyses.get("ac")
     if not ac:
         return None
     if freqs is None:
         freqs = buildFrequencyArray(ac["mode"], ac["N"], ac["f1"], ac["f2"])
-    _host_checks(ckt, freqs)
+    if exact_order or getattr(backend, "exact_order", False):
+        _check_resistors(ckt, freqs)  # (the reference-order engine raises the inductors' divide errors itself, slot by slot)
+    else:
+        _host_checks(ckt, freqs)
     flat = abi.flatten(ckt)
     vph = source_phasors(ckt)
-    be = backend if backend is not None else _default_backend()
+    be = backend if backend is not None else (_exact_backend() if exact_order else _default_backend())
     res = be.run_ac(flat, np.asarray(freqs, dtype=np.float64), vph, want_currents=True)
     if res["status"] == abi.ERR_SINGULAR:
         raise SingularComplexMatrixError(res.get("detail", ""))

@@ -109,6 +109,7 @@ struct SpiceyAcHandle {
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   double last_ms = 0.0;
   int64_t last_dense = 0;  // solves of the last run that went through the dense partial-pivoting fallback
+  SpiceyAcExact *exact = nullptr;  // interpreter 3: the reference-order engine (ac_exact.hip) serves this handle
   std::string err;
 };
 
@@ -118,6 +119,7 @@ extern "C" const char *spicey_ac_last_error(SpiceyAcHandle *h) { return h ? h->e
 
 extern "C" void spicey_ac_destroy(SpiceyAcHandle *h) {
   if (!h) return;
+  spicey_ac_exact_destroy(h->exact);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
   if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -130,6 +132,17 @@ extern "C" int32_t spicey_ac_create(const SpiceyDesc *desc, const SpiceyOptions 
   if (!desc) { g_ac_err = "null descriptor"; return SPICEY_ERR_BAD_DESC; }
   SpiceyAcHandle *h = new SpiceyAcHandle();
   if (opt) h->opt = *opt;
+  if (h->opt.interpreter == 3) {  // the reference-order engine: no sparse program, no structural pre-check
+    std::string err;
+    const int32_t rc = spicey_ac_exact_create(desc, h->opt, &h->exact, err);
+    if (rc != SPICEY_OK) {
+      g_ac_err = err;
+      delete h;
+      return rc;
+    }
+    *out = h;
+    return SPICEY_OK;
+  }
   SpiceyDesc d = *desc;  // simulateAC.ts:38-59 stamps R, C, L and V only
   d.nS = 0;
   d.nD = 0;
@@ -198,6 +211,10 @@ extern "C" int32_t spicey_ac_create(const SpiceyDesc *desc, const SpiceyOptions 
 
 extern "C" int32_t spicey_ac_get_info(SpiceyAcHandle *h, SpiceyInfo *info) {
   if (!h || !info) return SPICEY_ERR_BAD_DESC;
+  if (h->exact) {
+    spicey_ac_exact_info(h->exact, info);
+    return SPICEY_OK;
+  }
   memset(info, 0, sizeof(*info));
   info->n_var = h->hp.hdr.n;
   info->nnz_a = h->hp.nnzA;
@@ -222,6 +239,11 @@ extern "C" double spicey_ac_last_kernel_ms(SpiceyAcHandle *h) { return h ? h->la
 
 extern "C" int32_t spicey_ac_run(SpiceyAcHandle *h, int64_t n_freq, const double *freqs, const double *vph, double *out_v, double *out_i) {
   if (!h) return SPICEY_ERR_BAD_DESC;
+  if (h->exact) {
+    const int32_t rc = spicey_ac_exact_run(h->exact, n_freq, freqs, vph, out_v, out_i, &h->last_ms);
+    if (rc != SPICEY_OK) h->err = spicey_ac_exact_error(h->exact);
+    return rc;
+  }
   const SpiceyProg &P = h->hp.hdr;
   if (n_freq < 0 || (n_freq > 0 && (!freqs || !out_v)) || (P.nV > 0 && !vph)) { h->err = "bad run arguments"; return SPICEY_ERR_BAD_DESC; }
   if (n_freq == 0) return SPICEY_OK;

@@ -23,3 +23,12 @@ int spicey_grp_blocks_per_cu(const SpiceyProg &P, int K, int threads);  // occup
 // workspace is R->gW
 struct SpiceyExactProg;
 hipError_t spicey_launch_exact(const SpiceyExactProg *P, const SpiceyRun *R, int grid, int threads, size_t lds, hipStream_t st);
+
+// reference-order AC engine (ac_exact.hip): one workgroup per (instance, frequency) slot.  The spicey_ac_* entry points of
+// ac.hip hand a handle created with SpiceyOptions.interpreter = 3 to these; `err` / spicey_ac_exact_error carry the message.
+struct SpiceyAcExact;
+int32_t spicey_ac_exact_create(const SpiceyDesc *desc, const SpiceyOptions &opt, SpiceyAcExact **out, std::string &err);
+int32_t spicey_ac_exact_run(SpiceyAcExact *x, int64_t n_freq, const double *freqs, const double *vph, double *out_v, double *out_i, double *ms);
+void spicey_ac_exact_info(const SpiceyAcExact *x, SpiceyInfo *info);
+const char *spicey_ac_exact_error(const SpiceyAcExact *x);
+void spicey_ac_exact_destroy(SpiceyAcExact *x);

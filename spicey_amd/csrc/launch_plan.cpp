@@ -129,6 +129,52 @@ static int32_t plan_exact(const SpiceyDesc *desc, const SpiceyOptions &opt, cons
   return SPICEY_OK;
 }
 
+SpiceyAcExactWs spicey_ac_exact_ws(const SpiceyDesc &d) {
+  SpiceyAcExactWs w{};
+  const int64_t n = (int64_t)d.n_nodes + d.nV;
+  w.ld = (int32_t)((n + 1) | 1);
+  int32_t o = 0;
+  auto slots = [&](int32_t &at, int32_t cnt) { at = o; o += cnt; };
+  slots(w.qR, d.nR); slots(w.qC, d.nC); slots(w.qL, d.nL); slots(w.qV, d.nV); slots(w.qOne, 1);
+  w.nq = o;
+  int64_t at = 0;
+  auto carve = [&](int64_t &off, int64_t cx) { off = at; at += cx; };
+  carve(w.A, n * w.ld); carve(w.x, n); carve(w.q, w.nq); carve(w.f, n); carve(w.perm, (n + 3) / 4); carve(w.act, (n + 3) / 4);
+  w.cx = at;
+  return w;
+}
+
+// interpreter 3 of an AC handle: sizes and threads only; no sparse program, no structural pre-check (the reference throws
+// only where its own pivot search or divisions do)
+int32_t spicey_ac_exact_plan(const SpiceyDesc *desc, const SpiceyOptions &opt, AcExactPlan &plan, std::string &err) {
+  SpiceyDesc d = *desc;  // simulateAC.ts:38-59 stamps R, C, L and V only
+  d.nS = 0;
+  d.nD = 0;
+  int32_t rc = spicey_check_desc(&d, err);
+  if (rc != SPICEY_OK) return rc;
+  if (opt.threads != 0 && (opt.threads > 1024 || opt.threads < 64 || (opt.threads & 63))) {
+    err = "threads must be a multiple of 64 in [64, 1024]";
+    return SPICEY_ERR_BAD_DESC;
+  }
+  const int64_t n = (int64_t)d.n_nodes + d.nV;
+  if (n * ((n + 1) | 1) >= ((int64_t)1 << 32)) {
+    err = "interpreter 3 (reference order): n x (n + 1) must stay below 2^32 entries";
+    return SPICEY_ERR_BAD_DESC;
+  }
+  // 64 threads up to n = 64 (one wave: the pivot search needs no barrier), 256 above
+  plan.T = opt.threads > 0 ? opt.threads : (n <= 64 ? 64 : 256);
+  plan.ws = spicey_ac_exact_ws(d);
+  const size_t bytes = (size_t)plan.ws.cx * 16;
+  plan.lds = !opt.force_global && bytes + SPICEY_AC_EXACT_STATIC_LDS <= SPICEY_LDS_MAX;
+  plan.lds_bytes = plan.lds ? bytes : 0;
+  return SPICEY_OK;
+}
+
+int64_t spicey_ac_exact_chunk(const AcExactPlan &plan, int64_t slots) {
+  if (plan.lds || slots <= 0) return slots;
+  return std::min<int64_t>(slots, std::max<int64_t>(1, SPICEY_AC_EXACT_SLAB_MAX / (plan.ws.cx * 16)));
+}
+
 int32_t spicey_plan(const SpiceyDesc *desc, const SpiceyOptions &opt, const SpiceyKnobs &knobs, const PlanDevice &dev, HostProgram &hp,
                     HostResident &hres, LaunchPlan &plan, std::string &err) {
   if (opt.interpreter == 3) return plan_exact(desc, opt, dev, hp, plan, err);

@@ -71,6 +71,29 @@ struct SpiceyExactWs {
 SpiceyExactWs spicey_exact_ws(const SpiceyDesc &d);
 #define SPICEY_EXACT_STATIC_LDS 256  // bytes of static LDS of the exact kernel (reduction scratch, counters)
 
+// Reference-order AC engine (spicey_ac_create with interpreter = 3, ac_exact_exec.h): the workspace of one (instance,
+// frequency) slot, offsets in complex (16-byte) units from its base.  A | b is n rows of stride ld (n + 1 padded to an
+// odd count); q = the stamp quantities of one frequency (R 1/R | C jwC | L 1/(jwL) | V phasor | (1, 0)); f = the
+// multipliers of the active rows; perm and the active rows' indices are int32 arrays.
+struct SpiceyAcExactWs {
+  int32_t ld, nq, qR, qC, qL, qV, qOne;
+  int64_t A, x, q, f, perm, act, cx;
+};
+SpiceyAcExactWs spicey_ac_exact_ws(const SpiceyDesc &d);
+#define SPICEY_AC_EXACT_STATIC_LDS 256            // bytes of static LDS of the exact AC kernel (reduction scratch, counters)
+#define SPICEY_AC_EXACT_SLAB_MAX ((int64_t)1 << 30)  // global slab of one launch: at most 1 GiB (a larger slot runs alone)
+
+struct AcExactPlan {
+  int T = 64;
+  bool lds = true;       // workspace in LDS (else each slot's slab of a global buffer)
+  size_t lds_bytes = 0;  // dynamic LDS per workgroup (0 on the slab)
+  SpiceyAcExactWs ws{};
+};
+// Shape of an exact AC handle: validates the descriptor and the options it reads (threads, force_global).
+int32_t spicey_ac_exact_plan(const SpiceyDesc *desc, const SpiceyOptions &opt, AcExactPlan &plan, std::string &err);
+// slots (workgroups) per launch of a sweep over `slots` (instance, frequency) pairs
+int64_t spicey_ac_exact_chunk(const AcExactPlan &plan, int64_t slots);
+
 struct LaunchPlan {
   int n_inst = 0, K = 1, T = 256, grid = 1, interp = 1;
   int G = 1;             // workgroups per instance group (group mode: global workspace only)

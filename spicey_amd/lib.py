@@ -375,11 +375,14 @@ def to_precision6_native(x: float) -> str:
 class AcHandle:
     """spicey_ac_* of include/spicey_hip.h: AC sweep of n_inst instances of one topology."""
 
-    def __init__(self, flat: abi.FlatCircuit, device: int = 0, threads: int = 0, force_global: bool = False, no_resident: bool = False, no_dense: bool = False):
+    def __init__(self, flat: abi.FlatCircuit, device: int = 0, threads: int = 0, force_global: bool = False, no_resident: bool = False, no_dense: bool = False,
+                 interpreter: int = 0):
         self.L = load()
         self.flat = flat
         opt = abi.SpiceyOptions()
         opt.device, opt.threads, opt.force_global = int(device), int(threads), int(bool(force_global))
+        # interpreter 3: the reference-order engine (the reference's own solveComplex, bit for bit; include/spicey_hip.h)
+        opt.interpreter = int(interpreter)
         # bit 4: one workgroup per (instance, frequency) even for large batches; bit 7: no dense partial-pivoting fallback
         opt.debug = (16 if no_resident else 0) | (128 if no_dense else 0)
         d = flat.desc()
@@ -450,5 +453,26 @@ class HipBackend:
         try:
             self.info = h.info()
             return h.run(freqs, vph, want_currents)
+        finally:
+            h.close()
+
+
+class HipAcExactBackend:
+    """run_ac through the reference-order AC engine (AcHandle(interpreter=3)): the reference's numbers and errors bit for
+    bit.  Used by simulateAC(ckt, exact_order=True)."""
+
+    exact_order = True  # (simulateAC leaves the inductors' "Complex divide by ~0" to the engine, frequency by frequency)
+
+    def __init__(self, device: int = 0, threads: int = 0, force_global: bool = False):
+        self.kw = dict(device=device, threads=threads, force_global=force_global)
+        self.info: Optional[dict] = None
+
+    def run_ac(self, flat: abi.FlatCircuit, freqs, vph, want_currents: bool = True) -> dict:
+        h = AcHandle(flat, interpreter=3, **self.kw)
+        try:
+            self.info = h.info()
+            res = h.run(freqs, vph, want_currents)
+            self.info = h.info()
+            return res
         finally:
             h.close()

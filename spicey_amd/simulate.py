@@ -123,15 +123,16 @@ def simulateTRAN(ckt: ParsedCircuit, backend=None, as_lists: bool = True, exact_
             "iterations": res.get("iters"), "skipRisk": int(skip[0]) if skip is not None else 0}
 
 
-def simulate(netlist_text: str, backend=None, exact_order: bool = False) -> dict:
+def simulate(netlist_text: str, backend=None, exact_order: bool = False, ac_exact_order: bool = False) -> dict:
     """simulate.ts:5-10: parse, AC sweep (if an .ac card is present), transient (if a .tran card is present).
-    exact_order: the transient runs the reference-order engine (simulateTRAN); the AC sweep is unaffected."""
+    exact_order: the transient runs the reference-order engine (simulateTRAN); the AC sweep is unaffected.
+    ac_exact_order: the AC sweep runs the reference-order AC engine (simulateAC); the transient is unaffected."""
     from .ac import simulateAC  # (ac.py imports this module's number formatter)
 
-    if exact_order and backend is not None:
-        raise ValueError("simulate: pass either backend= or exact_order=True, not both")
+    if (exact_order or ac_exact_order) and backend is not None:
+        raise ValueError("simulate: pass either backend= or exact_order=True / ac_exact_order=True, not both")
     circuit = parseNetlist(netlist_text)
-    ac = simulateAC(circuit, backend=backend)
+    ac = simulateAC(circuit, backend=backend, exact_order=ac_exact_order)
     tran = simulateTRAN(circuit, backend=backend, exact_order=exact_order)
     return {"circuit": circuit, "ac": ac, "tran": tran}
 

@@ -4,9 +4,16 @@ import { parseNetlist } from "./parseNetlist"
 import { simulateAC } from "./simulateAC"
 import { simulateTRAN } from "./simulateTRAN"
 
-export function simulate(netlistText: string) {
+export type SimulateOptions = {
+  /** the transient runs the reference-order engine (simulateTRAN); the AC sweep is unaffected */
+  exactOrder?: boolean
+  /** the AC sweep runs the reference-order AC engine (simulateAC); the transient is unaffected */
+  acExactOrder?: boolean
+}
+
+export function simulate(netlistText: string, options?: SimulateOptions) {
   const circuit = parseNetlist(netlistText)
-  const ac = simulateAC(circuit)
-  const tran = simulateTRAN(circuit)
+  const ac = simulateAC(circuit, { exactOrder: !!options?.acExactOrder })
+  const tran = simulateTRAN(circuit, { exactOrder: !!options?.exactOrder })
   return { circuit, ac, tran }
 }

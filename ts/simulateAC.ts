@@ -32,17 +32,26 @@ function flattenLinear(ckt: ParsedCircuit): FlatCircuit {
   }
 }
 
-function simulateAC(ckt: ParsedCircuit) {
+export type SimulateAcOptions = {
+  /** run the reference's own solveComplex on the GPU (dense stamp in element order, partial pivoting on Math.hypot, its
+   *  |f| < EPS row-update skip): the reference's numbers bit for bit and its errors at the frequency where it throws them */
+  exactOrder?: boolean
+}
+
+function simulateAC(ckt: ParsedCircuit, options?: SimulateAcOptions) {
   if (!ckt.analyses.ac) return null
   const freqs = frequencies(ckt.analyses.ac)
+  const exact = !!options?.exactOrder
 
-  // errors the reference throws while building the system (simulateAC.ts:39, :51-53 via Complex.div)
+  // errors the reference throws while building the system (simulateAC.ts:39, :51-53 via Complex.div; in exact mode the
+  // inductors' divide errors come from the device, frequency by frequency)
   for (const r of ckt.R) if (r.R <= 0) throw new Error(`R ${r.name} must be > 0`)
-  for (const f of freqs)
-    for (const l of ckt.L) {
-      const w = 2 * Math.PI * f * l.L
-      if (!(Math.abs(w) < EPS) && w * w < EPS) throw new Error("Complex divide by ~0")
-    }
+  if (!exact)
+    for (const f of freqs)
+      for (const l of ckt.L) {
+        const w = 2 * Math.PI * f * l.L
+        if (!(Math.abs(w) < EPS) && w * w < EPS) throw new Error("Complex divide by ~0")
+      }
 
   const nV = ckt.V.length
   const vph = new Float64Array(nV * 2)
@@ -53,7 +62,7 @@ function simulateAC(ckt: ParsedCircuit) {
   })
 
   const flat = flattenLinear(ckt)
-  const res = runAcNative(flat, Float64Array.from(freqs), vph)
+  const res = runAcNative(flat, Float64Array.from(freqs), vph, exact ? { interpreter: 3 } : undefined)
 
   const nNodes = flat.nNodes
   const nodeVoltages: Record<string, Complex[]> = {}

@@ -157,11 +157,18 @@ export type NativeAcResult = {
   outI: Float64Array // [nFreq][nR+nC+nL+nV][2], order R, C, L, V
 }
 
+export type NativeAcOptions = {
+  /** SpiceyOptions.interpreter: 0 = the sparse static-order path (default), 3 = the reference-order AC engine — the
+   *  reference's own solveComplex on the GPU, bit-identical to it, its errors at the frequency where it throws them */
+  interpreter?: number
+}
+
 /** One AC sweep on the GPU: every frequency is an independent complex solve (simulateAC.ts:80-126), one launch.
  *  vph = [nV][2] source phasors.  Throws the reference's Error messages (solveComplex.ts:28, Complex.ts:42). */
-export function runAcNative(f: FlatCircuit, freqs: Float64Array, vph: Float64Array): NativeAcResult {
+export function runAcNative(f: FlatCircuit, freqs: Float64Array, vph: Float64Array, options?: NativeAcOptions): NativeAcResult {
   const { buf, keep } = packDesc(f)
   const opt = new ArrayBuffer(SpiceyOptionsLayout.size)
+  if (options?.interpreter) new DataView(opt).setInt32(SpiceyOptionsLayout.fields.interpreter.offset, options.interpreter, true)
   const hOut = new BigUint64Array(1)
   let rc = C.spicey_ac_create(ptr(buf), ptr(opt), ptr(hOut))
   void keep
