@@ -188,6 +188,27 @@ int32_t spicey_run(SpiceyHandle *h, int64_t steps, double dt, const double *src_
  * synchronising: the error word is checked by spicey_sync(). */
 int32_t spicey_run_device(SpiceyHandle *h, int64_t steps, double dt, const double *d_src_table,
                           double *d_out_v, double *d_out_i, int32_t *d_iters, void *stream);
+
+/* Batched sweeps whose instances differ in their stimulus (a supply corner, an input amplitude, one PWL vector each):
+ * src_per_inst = 0: src_table [steps+1][nV], shared by all instances (exactly spicey_run);
+ *                1: src_table [n_inst][steps+1][nV], instance i reads block i.  Other values: SPICEY_ERR_BAD_DESC.
+ * Every interpreter, workspace layout, K and group mode honours the layout.  Unlike spicey_run, the output buffers are
+ * also filled when the call returns SPICEY_ERR_SINGULAR: the rows of every instance whose spicey_last_inst_status entry
+ * is 0 are complete, the others are undefined. */
+int32_t spicey_run_src(SpiceyHandle *h, int64_t steps, double dt, const double *src_table, int32_t src_per_inst,
+                       double *out_v, double *out_i, int32_t *iters);
+/* The same with DEVICE buffers, enqueued on `stream` without synchronising (as spicey_run_device). */
+int32_t spicey_run_device_src(SpiceyHandle *h, int64_t steps, double dt, const double *d_src_table, int32_t src_per_inst,
+                              double *d_out_v, double *d_out_i, int32_t *d_iters, void *stream);
+/* Per instance of the last run (after spicey_run* / spicey_sync), status[n_inst]: 0 = reached its last step;
+ * SPICEY_ERR_SINGULAR = its own solve was singular (where the reference throws); -1 = stopped unfinished because another
+ * instance in its workgroup failed (only when SpiceyInfo.inst_per_wg > 1); SPICEY_ERR_HIP = its launch aborted (group
+ * mode).  A workgroup has one error flag, so the first singular solve stops all of its instances; the status words name
+ * only that one.  The device state of an instance that did not reach its last step is undefined (some paths write state
+ * during the run, e.g. capacitors beyond the register-resident ones): run it again from the state it entered with.  Returns
+ * the number of nonzero entries; -1 without a handle or a buffer, before any run, and when the last run was refused or
+ * failed before its launch finished (a structurally singular descriptor is answered: every instance SPICEY_ERR_SINGULAR). */
+int32_t spicey_last_inst_status(SpiceyHandle *h, int32_t *status /* [n_inst] */);
 /* Wait for enqueued runs; returns SPICEY_ERR_SINGULAR etc. like spicey_run.
  * Group mode (several workgroups per instance): every cross-workgroup wait is bounded in time; a launch whose wait runs
  * out aborts as a whole (nothing of it is kept): SPICEY_ERR_HIP with the first waiter's position (which wait, which
@@ -272,6 +293,9 @@ typedef struct SpiceyMulti SpiceyMulti;
 int32_t spicey_create_multi(const SpiceyDesc *desc, const SpiceyOptions *opt, const int32_t *devices, int32_t n_dev, SpiceyMulti **out);
 /* Same buffers as spicey_run, for ALL instances: out_v [n_inst][steps+1][n_out], out_i, iters likewise or NULL. Blocking. */
 int32_t spicey_run_multi(SpiceyMulti *m, int64_t steps, double dt, const double *src_table, double *out_v, double *out_i, int32_t *iters);
+/* With per-instance source tables (src_per_inst as for spicey_run_src): each shard gets its slice of the tables. */
+int32_t spicey_run_multi_src(SpiceyMulti *m, int64_t steps, double dt, const double *src_table, int32_t src_per_inst,
+                             double *out_v, double *out_i, int32_t *iters);
 int32_t spicey_get_state_multi(SpiceyMulti *m, double *C_vprev, double *L_iprev, double *D_vdprev, int32_t *S_ison);
 /* Shard `shard` (0 .. n_shards-1): its SpiceyInfo, first instance and instance count; returns SPICEY_ERR_BAD_DESC past the end. */
 int32_t spicey_multi_get_shard(SpiceyMulti *m, int32_t shard, SpiceyInfo *info, int32_t *device, int32_t *first_inst, int32_t *n_inst);

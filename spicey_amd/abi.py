@@ -189,3 +189,12 @@ def source_table(ckt: ParsedCircuit, dt: float, steps: int) -> np.ndarray:
             dc = vs.dc
             tab[:, k] = 0.0 if (dc == 0 or dc != dc) else dc
     return tab
+
+
+def source_tables(ckts: Sequence[ParsedCircuit], dt: float, steps: int) -> np.ndarray:
+    """One source table per circuit, stacked: [len(ckts)][steps+1][nV] — the per-instance layout of spicey_run_src.  The
+    circuits must have the same number of voltage sources."""
+    tabs = [source_table(c, dt, steps) for c in ckts]
+    if len({t.shape for t in tabs}) > 1:
+        raise ValueError("source_tables: the circuits differ in their number of voltage sources")
+    return np.stack(tabs) if tabs else np.zeros((0, steps + 1, 0))

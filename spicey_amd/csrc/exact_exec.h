@@ -124,7 +124,7 @@ SPICEY_HD void spicey_exact_run(Exec &ex, const SpiceyExactProg &P, const Spicey
     if (tid == 0) { scal[4] = 0; scal[5] = 0; }
   });
   for (; step <= R.steps && code == 0; step++) {
-    const double *src = R.src + (size_t)step * P.nV;
+    const double *src = R.src + in * R.src_stride + (size_t)step * P.nV;
     int iter = 0;
     for (; iter < SPICEY_MAX_ITER; iter++) {
       // ---- the iteration's quantities (one thread per element; diodes linearised at vdPrev or the last iterate), a zero

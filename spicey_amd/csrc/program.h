@@ -248,7 +248,7 @@ struct SpiceyRun {
   // global-memory fallback for W/u/gdyn when LDS is too small: [n_workgroups][...]
   double *gW;
   // io
-  const double *src;  // [steps+1][nV]
+  const double *src;  // [steps+1][nV], or [n_inst][steps+1][nV] (src_stride)
   double *out_v;      // [n_inst][steps+1][nOut]
   double *out_i;      // [n_inst][steps+1][nCur] or null
   int32_t *iters;     // [n_inst][steps+1] or null
@@ -285,4 +285,7 @@ struct SpiceyRun {
   unsigned long long *lin_err;
   // hybrid workspace (SpiceyProg::hybrid): leaf-owned entries [n_inst][nLU] and the element vectors u | gd [n_inst][nU + nGdyn]
   double *hyb_G, *hyb_ug;
+  // io (appended last so that the offsets of the fields above do not move): distance in doubles between the source tables
+  // of consecutive instances — 0 = ONE table [steps+1][nV] shared by every instance, (steps+1) nV = [n_inst][steps+1][nV]
+  int64_t src_stride;
 };

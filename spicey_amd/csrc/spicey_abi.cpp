@@ -92,6 +92,10 @@ struct SpiceyHandle {
   bool pending = false;
   int64_t last_solves = 0;
   double last_ms = 0.0;
+  // status words [grid][4] of the last finished launch (spicey_sync), and whether the last run was refused as structurally
+  // singular before any launch (every instance then fails): the per-instance answer of spicey_last_inst_status
+  std::vector<int32_t> last_status;
+  bool last_structural = false;
   std::string err;
 };
 
@@ -383,12 +387,22 @@ static int32_t reset_launch_words(SpiceyHandle *h, hipStream_t st) {
   return SPICEY_OK;
 }
 
-extern "C" int32_t spicey_run_device(SpiceyHandle *h, int64_t steps, double dt, const double *d_src_table, double *d_out_v,
-                                     double *d_out_i, int32_t *d_iters, void *stream) {
+// A new run begins: what spicey_last_inst_status reported about the previous one no longer holds (until this run's launch
+// has finished, or it was refused as structurally singular, there is no per-instance answer).
+static void forget_last_run(SpiceyHandle *h) {
+  h->last_status.clear();
+  h->last_structural = false;
+}
+
+extern "C" int32_t spicey_run_device_src(SpiceyHandle *h, int64_t steps, double dt, const double *d_src_table, int32_t src_per_inst,
+                                         double *d_out_v, double *d_out_i, int32_t *d_iters, void *stream) {
   if (!h) return SPICEY_ERR_BAD_DESC;
+  forget_last_run(h);
   if (steps < 0 || !d_out_v || (h->hp.hdr.nV > 0 && !d_src_table)) { h->err = "bad run arguments"; return SPICEY_ERR_BAD_DESC; }
+  if (src_per_inst != 0 && src_per_inst != 1) { h->err = "src_per_inst must be 0 (one shared table) or 1 (one table per instance)"; return SPICEY_ERR_BAD_DESC; }
   if (h->hp.structurally_singular) {
     h->err = "singular at inst 0 step 0 iter 0 (structurally singular matrix)";
+    h->last_structural = true;
     return SPICEY_ERR_SINGULAR;
   }
   HIPCHK(h, hipSetDevice(h->device));
@@ -397,6 +411,7 @@ extern "C" int32_t spicey_run_device(SpiceyHandle *h, int64_t steps, double dt, 
   // it — finish it first (its result is then reported here instead of by the next spicey_sync)
   if (h->pending && h->last_stream != st) {
     const int32_t rc0 = spicey_sync(h);
+    forget_last_run(h);  // (that run's words are not this one's)
     if (rc0 != SPICEY_OK) return rc0;
   }
   const LaunchPlan &pl = h->plan;
@@ -414,6 +429,7 @@ extern "C" int32_t spicey_run_device(SpiceyHandle *h, int64_t steps, double dt, 
   R.C_vprev = h->state.Cv; R.L_iprev = h->state.Li; R.D_vdprev = h->state.Dv; R.S_ison = h->state.Son;
   R.gstat = h->d_gstat; R.statv = h->d_statv; R.rcoef = h->d_rcoef; R.gW = pl.interp == 3 ? h->d_xws : h->d_gW; R.dpar = h->d_dpar;
   R.src = d_src_table; R.out_v = d_out_v; R.out_i = d_out_i; R.iters = d_iters;
+  R.src_stride = src_per_inst ? (int64_t)(steps + 1) * P.nV : 0;
   R.status = h->d_status; R.solves = h->d_solves; R.prof = h->d_prof;
   // diagnostics: counters and per-step maxima start from zero in every run (reset_launch_words)
   h->last_steps = steps;
@@ -421,7 +437,7 @@ extern "C" int32_t spicey_run_device(SpiceyHandle *h, int64_t steps, double dt, 
   if (h->opt.diagnostics & 2) {
     const size_t need = (size_t)pl.n_inst * (size_t)(steps + 1);
     if (need > h->linerr_cap) {
-      if (h->pending) { const int32_t rc0 = spicey_sync(h); if (rc0 != SPICEY_OK) return rc0; }
+      if (h->pending) { const int32_t rc0 = spicey_sync(h); forget_last_run(h); if (rc0 != SPICEY_OK) return rc0; }
       h->linerr_cap = 0;
       HIPCHK(h, h->d_linerr.alloc(need));
       h->linerr_cap = need;
@@ -467,6 +483,11 @@ extern "C" int32_t spicey_run_device(SpiceyHandle *h, int64_t steps, double dt, 
   return SPICEY_OK;
 }
 
+extern "C" int32_t spicey_run_device(SpiceyHandle *h, int64_t steps, double dt, const double *d_src_table, double *d_out_v,
+                                     double *d_out_i, int32_t *d_iters, void *stream) {
+  return spicey_run_device_src(h, steps, dt, d_src_table, 0, d_out_v, d_out_i, d_iters, stream);
+}
+
 extern "C" int32_t spicey_sync(SpiceyHandle *h) {
   if (!h) return SPICEY_ERR_BAD_DESC;
   if (!h->pending) return SPICEY_OK;
@@ -482,6 +503,7 @@ extern "C" int32_t spicey_sync(SpiceyHandle *h) {
     if (hipEventElapsedTime(&ms, h->ev0, h->ev1) == hipSuccess) h->last_ms = ms;
     HIPCHK(h, hipMemcpy(status.data(), h->d_status, status.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
     HIPCHK(h, hipMemcpy(solves.data(), h->d_solves, solves.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    h->last_status = status;
     h->last_solves = 0;
     for (auto s : solves) h->last_solves += (int64_t)s;
     std::vector<unsigned int> gsync;
@@ -534,38 +556,76 @@ extern "C" int32_t spicey_sync(SpiceyHandle *h) {
 extern "C" int32_t spicey_group_retries(const SpiceyHandle *h) { return h ? h->group_retries : 0; }
 extern "C" int64_t spicey_group_stale_polls(const SpiceyHandle *h) { return h ? h->stale_polls : 0; }
 
-extern "C" int32_t spicey_run(SpiceyHandle *h, int64_t steps, double dt, const double *src_table, double *out_v, double *out_i,
-                              int32_t *iters) {
+// Per instance of the last run, from the status words {code, inst, step, iter} of its workgroups: workgroup (or group) g
+// ran instances g K .. g K + K - 1 (kernels.hip, exact.hip), and its code names only the instance that failed first — the
+// others of that workgroup stopped with it, unfinished.
+extern "C" int32_t spicey_last_inst_status(SpiceyHandle *h, int32_t *status) {
+  if (!h || !status) return -1;
+  if (h->pending) spicey_sync(h);
+  if (h->last_status.empty() && !h->last_structural) return -1;  // no run yet, a run refused before its launch, or a lost one
+  const int ni = h->plan.n_inst, K = h->plan.K;
+  int32_t bad = 0;
+  for (int i = 0; i < ni; i++) status[i] = h->last_structural ? SPICEY_ERR_SINGULAR : 0;
+  if (h->last_structural) return ni;
+  const int grid = std::min<int>(h->plan.grid, (int)(h->last_status.size() / 4));
+  for (int g = 0; g < grid; g++) {
+    const int32_t code = h->last_status[(size_t)g * 4], who = h->last_status[(size_t)g * 4 + 1];
+    if (code == 0) continue;
+    for (int k = 0; k < K && g * K + k < ni; k++) {
+      const int in = g * K + k;
+      status[in] = code != 1 ? SPICEY_ERR_HIP : in == who ? SPICEY_ERR_SINGULAR : -1;
+    }
+  }
+  for (int i = 0; i < ni; i++) bad += status[i] != 0;
+  return bad;
+}
+
+// keep_partial: the results also come back after SPICEY_ERR_SINGULAR (spicey_run_src: the instances that finished are complete)
+static int32_t run_host(SpiceyHandle *h, int64_t steps, double dt, const double *src_table, int32_t src_per_inst, double *out_v,
+                        double *out_i, int32_t *iters, bool keep_partial) {
   if (!h) return SPICEY_ERR_BAD_DESC;
+  forget_last_run(h);
   if (steps < 0 || !out_v || (h->hp.hdr.nV > 0 && !src_table)) { h->err = "bad run arguments"; return SPICEY_ERR_BAD_DESC; }
+  if (src_per_inst != 0 && src_per_inst != 1) { h->err = "src_per_inst must be 0 (one shared table) or 1 (one table per instance)"; return SPICEY_ERR_BAD_DESC; }
   if (h->hp.structurally_singular) {
     h->err = "singular at inst 0 step 0 iter 0 (structurally singular matrix)";
+    h->last_structural = true;
     return SPICEY_ERR_SINGULAR;
   }
   HIPCHK(h, hipSetDevice(h->device));
   Roctx range_run("spicey_run");
   const SpiceyProg &P = h->hp.hdr;
-  const size_t np = (size_t)steps + 1, ni = (size_t)h->plan.n_inst;
+  const size_t np = (size_t)steps + 1, ni = (size_t)h->plan.n_inst, ntab = src_per_inst ? ni : 1;
   DevBuf<double> d_src, d_v, d_i;
   DevBuf<int32_t> d_it;
-  HIPCHK(h, d_src.alloc(std::max<size_t>(np * P.nV, 1)));
-  if (P.nV) HIPCHK(h, hipMemcpyAsync(d_src, src_table, np * P.nV * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, d_src.alloc(std::max<size_t>(ntab * np * P.nV, 1)));
+  if (P.nV) HIPCHK(h, hipMemcpyAsync(d_src, src_table, ntab * np * P.nV * sizeof(double), hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, d_v.alloc(std::max<size_t>(ni * np * P.nOut, 1)));
   if (out_i) HIPCHK(h, d_i.alloc(std::max<size_t>(ni * np * P.nCur, 1)));
   if (iters) HIPCHK(h, d_it.alloc(ni * np));
   int32_t rc;
   {
     Roctx range_kernel("spicey_run:kernel");
-    rc = spicey_run_device(h, steps, dt, d_src, d_v, d_i, d_it, h->stream);
+    rc = spicey_run_device_src(h, steps, dt, d_src, src_per_inst, d_v, d_i, d_it, h->stream);
     if (rc == SPICEY_OK) rc = spicey_sync(h);
   }
-  if (rc == SPICEY_OK) {
+  if (rc == SPICEY_OK || (keep_partial && rc == SPICEY_ERR_SINGULAR)) {
     Roctx range_copy("spicey_run:results");
     HIPCHK(h, hipMemcpy(out_v, d_v, ni * np * P.nOut * sizeof(double), hipMemcpyDeviceToHost));
     if (out_i) HIPCHK(h, hipMemcpy(out_i, d_i, ni * np * P.nCur * sizeof(double), hipMemcpyDeviceToHost));
     if (iters) HIPCHK(h, hipMemcpy(iters, d_it, ni * np * sizeof(int32_t), hipMemcpyDeviceToHost));
   }
   return rc;
+}
+
+extern "C" int32_t spicey_run_src(SpiceyHandle *h, int64_t steps, double dt, const double *src_table, int32_t src_per_inst, double *out_v,
+                                  double *out_i, int32_t *iters) {
+  return run_host(h, steps, dt, src_table, src_per_inst, out_v, out_i, iters, true);
+}
+
+extern "C" int32_t spicey_run(SpiceyHandle *h, int64_t steps, double dt, const double *src_table, double *out_v, double *out_i,
+                              int32_t *iters) {
+  return run_host(h, steps, dt, src_table, 0, out_v, out_i, iters, false);
 }
 
 extern "C" int32_t spicey_get_state(SpiceyHandle *h, double *C_vprev, double *L_iprev, double *D_vdprev, int32_t *S_ison) {
@@ -674,7 +734,7 @@ struct SpiceyMulti {
   struct Shard { SpiceyHandle *h = nullptr; int device = 0, first = 0, count = 0; };
   std::vector<Shard> shards;
   int n_inst = 0;
-  int nC = 0, nL = 0, nD = 0, nS = 0, nOut = 0, nCur = 0;
+  int nC = 0, nL = 0, nD = 0, nS = 0, nV = 0, nOut = 0, nCur = 0;
   int64_t last_solves = 0;
   double last_ms = 0.0;
   std::string err;
@@ -728,22 +788,27 @@ extern "C" int32_t spicey_create_multi(const SpiceyDesc *desc, const SpiceyOptio
     m->shards.push_back(s);
   }
   const SpiceyProg &P = m->shards[0].h->hp.hdr;
-  m->nC = P.nC; m->nL = P.nL; m->nD = P.nD; m->nS = P.nS; m->nOut = P.nOut; m->nCur = P.nCur;
+  m->nC = P.nC; m->nL = P.nL; m->nD = P.nD; m->nS = P.nS; m->nV = P.nV; m->nOut = P.nOut; m->nCur = P.nCur;
   *out = m;
   return SPICEY_OK;
 }
 
-extern "C" int32_t spicey_run_multi(SpiceyMulti *m, int64_t steps, double dt, const double *src_table, double *out_v, double *out_i, int32_t *iters) {
+extern "C" int32_t spicey_run_multi_src(SpiceyMulti *m, int64_t steps, double dt, const double *src_table, int32_t src_per_inst, double *out_v,
+                                        double *out_i, int32_t *iters) {
   if (!m) return SPICEY_ERR_BAD_DESC;
   if (steps < 0 || !out_v) { m->err = "bad run arguments"; return SPICEY_ERR_BAD_DESC; }
+  if (src_per_inst != 0 && src_per_inst != 1) { m->err = "src_per_inst must be 0 (one shared table) or 1 (one table per instance)"; return SPICEY_ERR_BAD_DESC; }
   const size_t np = (size_t)steps + 1;
   std::vector<int32_t> rcs(m->shards.size(), SPICEY_OK);
   std::vector<std::thread> th;
   for (size_t i = 0; i < m->shards.size(); i++) {
     th.emplace_back([&, i]() {
       const SpiceyMulti::Shard &s = m->shards[i];
-      rcs[i] = spicey_run(s.h, steps, dt, src_table, out_v + (size_t)s.first * np * (size_t)m->nOut,
-                          out_i ? out_i + (size_t)s.first * np * (size_t)m->nCur : nullptr, iters ? iters + (size_t)s.first * np : nullptr);
+      // (per-instance tables: the shard's slice, instances first .. first + count - 1)
+      const double *tab = src_table && src_per_inst ? src_table + (size_t)s.first * np * (size_t)m->nV : src_table;
+      // (the shared layout keeps spicey_run's behaviour: no results come back after an error)
+      rcs[i] = run_host(s.h, steps, dt, tab, src_per_inst, out_v + (size_t)s.first * np * (size_t)m->nOut,
+                        out_i ? out_i + (size_t)s.first * np * (size_t)m->nCur : nullptr, iters ? iters + (size_t)s.first * np : nullptr, src_per_inst != 0);
     });
   }
   for (auto &t : th) t.join();
@@ -762,6 +827,10 @@ extern "C" int32_t spicey_run_multi(SpiceyMulti *m, int64_t steps, double dt, co
     m->last_ms = std::max(m->last_ms, spicey_last_kernel_ms(s.h));
   }
   return rc;
+}
+
+extern "C" int32_t spicey_run_multi(SpiceyMulti *m, int64_t steps, double dt, const double *src_table, double *out_v, double *out_i, int32_t *iters) {
+  return spicey_run_multi_src(m, steps, dt, src_table, 0, out_v, out_i, iters);
 }
 
 extern "C" int32_t spicey_get_state_multi(SpiceyMulti *m, double *C_vprev, double *L_iprev, double *D_vdprev, int32_t *S_ison) {

@@ -295,7 +295,7 @@ struct TranPhases {
       SPICEY_NOUNROLL
       for (int i = tid; i < P.nL; i += T) c.u[(size_t)(oL + i) * K + k] = R.L_iprev[in * P.nL + i];
       SPICEY_NOUNROLL
-      for (int i = tid; i < P.nV; i += T) c.u[(size_t)(oV + i) * K + k] = R.src[i];
+      for (int i = tid; i < P.nV; i += T) c.u[(size_t)(oV + i) * K + k] = R.src[in * R.src_stride + i];
       SPICEY_NOUNROLL
       for (int i = tid; i < P.nS; i += T) {
         const int on = R.S_ison[in * P.nS + i];
@@ -563,7 +563,7 @@ struct TranPhases {
       SPICEY_NOUNROLL
       for (int i = tid; i < P.nV; i += T) {
         if (cur) oi[cV + i] = c.W[(size_t)P.V_x[i] * K + k];
-        if (!last) c.u[(size_t)(oV + i) * K + k] = R.src[(size_t)(step + 1) * P.nV + i];
+        if (!last) c.u[(size_t)(oV + i) * K + k] = R.src[in * R.src_stride + (size_t)(step + 1) * P.nV + i];
       }
       SPICEY_NOUNROLL
       for (int i = tid; i < P.nS; i += T) {
@@ -1021,7 +1021,7 @@ struct TranPhases2 {
       SPICEY_NOUNROLL
       for (int i = tid; i < P.nL; i += T) c.u[(size_t)(oL + i) * K + k] = R.L_iprev[in * P.nL + i];
       SPICEY_NOUNROLL
-      for (int i = tid; i < P.nV; i += T) c.u[(size_t)(oV + i) * K + k] = R.src[i];
+      for (int i = tid; i < P.nV; i += T) c.u[(size_t)(oV + i) * K + k] = R.src[in * R.src_stride + i];
       SPICEY_NOUNROLL
       for (int i = tid; i < P.nS; i += T) {
         const int on = R.S_ison[in * P.nS + i];
@@ -1393,8 +1393,8 @@ struct TranPhases2 {
     }
   }
   // next step's source values: issued before the tasks of the last backward phase, parked in LDS after them
-  SPICEY_HD double z_src_fetch(int tid, int64_t step) const {
-    return (tid < P.nV && step != R.steps) ? R.src[(size_t)(step + 1) * P.nV + tid] : 0.0;
+  SPICEY_HD double z_src_fetch(int tid, int64_t step, size_t in) const {
+    return (tid < P.nV && step != R.steps) ? R.src[in * R.src_stride + (size_t)(step + 1) * P.nV + tid] : 0.0;
   }
   SPICEY_HD void z_src_park(int tid, double v) const {
     if (tid < P.nV) c.u[(size_t)(P.nC + P.nL + P.nV + P.nD + tid) * K] = v;
@@ -1427,7 +1427,7 @@ struct TranPhases2 {
       if (!(K == 1 && prefetched)) z_prefetch(tid, step, k, rr);
       double pR[NEL], pC[NEL], pIs[NEL], pD0[NEL], pD1[NEL];
       for (int j = 0; j < NEL; j++) { pR[j] = rr.pf[j][0]; pC[j] = rr.pf[j][1]; pIs[j] = rr.pf[j][2]; pD0[j] = rr.pf[j][3]; pD1[j] = rr.pf[j][4]; }
-      double srcn = (K == 1 && prefetched) ? 0.0 : z_src_fetch(tid, step);
+      double srcn = (K == 1 && prefetched) ? 0.0 : z_src_fetch(tid, step, in);
       // ... and all of them are WAITED for here, before the first result store is issued: gfx9 has one counter
       // (vmcnt) for loads and stores, which may complete out of order, so once a store is in flight a wait for any
       // load becomes vmcnt(0) = "until every result store has been acknowledged" (~1 us each time).
@@ -1580,7 +1580,7 @@ struct TranPhases2 {
       SPICEY_NOUNROLL
       for (int i = tid + T; i < P.nV; i += T) {
         if (oi) oi[cV + i] = c.W[(size_t)P.V_x[i] * K + k];
-        if (!last) c.u[(size_t)(oV + i) * K + k] = R.src[(size_t)(step + 1) * P.nV + i];
+        if (!last) c.u[(size_t)(oV + i) * K + k] = R.src[in * R.src_stride + (size_t)(step + 1) * P.nV + i];
       }
       if (zrem & 32u)
       SPICEY_NOUNROLL
@@ -1787,7 +1787,7 @@ SPICEY_HD void spicey_tran_run_v2(Exec &ex, const SpiceyProg &P, const SpiceyRes
         Ph2 p2{Pf, Rf, c, T, brem, zrem};
         // the next step's source values ride on B (a long phase with few live registers): fetched first, parked in
         // LDS last; Z moves them into place
-        double sn = K == 1 ? p2.z_src_fetch(tid, step) : 0.0;
+        double sn = K == 1 ? p2.z_src_fetch(tid, step, (size_t)c.inst[0]) : 0.0;
         SPICEY_SCHED_FENCE;
         p2.b_stamp(tid, ex.template regs<Regs>(tid), linear && step > 0);
         SPICEY_SCHED_FENCE;

@@ -18,11 +18,11 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SPICEY_HIP_LIB") or os.path.join(_HERE, "libspicey_hip.so")  # same override as ts/spiceyHip.ts
 _LIB = None
 
-EXPORTS = ["spicey_create", "spicey_run", "spicey_run_device", "spicey_sync", "spicey_get_state", "spicey_set_state", "spicey_reset_state",
+EXPORTS = ["spicey_create", "spicey_run", "spicey_run_device", "spicey_run_src", "spicey_run_device_src", "spicey_last_inst_status", "spicey_sync", "spicey_get_state", "spicey_set_state", "spicey_reset_state",
            "spicey_last_solve_count", "spicey_group_retries", "spicey_group_stale_polls", "spicey_last_skip_risk", "spicey_get_lin_err",
            "spicey_last_kernel_ms", "spicey_get_info", "spicey_last_error", "spicey_destroy", "spicey_version",
            "spicey_debug_phase_cycles", "spicey_debug_phase_cycles_wg", "spicey_debug_front_ticks",
-           "spicey_create_multi", "spicey_run_multi", "spicey_get_state_multi", "spicey_multi_get_shard", "spicey_multi_last_solve_count", "spicey_multi_group_retries", "spicey_multi_group_stale_polls",
+           "spicey_create_multi", "spicey_run_multi", "spicey_run_multi_src", "spicey_get_state_multi", "spicey_multi_get_shard", "spicey_multi_last_solve_count", "spicey_multi_group_retries", "spicey_multi_group_stale_polls",
            "spicey_multi_last_kernel_ms", "spicey_multi_last_error", "spicey_destroy_multi",
            "spicey_ac_create", "spicey_ac_run", "spicey_ac_get_info", "spicey_ac_last_kernel_ms", "spicey_ac_last_error", "spicey_ac_destroy",
            "spicey_format_tran", "spicey_to_precision6"]
@@ -53,6 +53,12 @@ def load():
     L.spicey_run.argtypes = [vp, C.c_int64, C.c_double, f64p, f64p, f64p, i32p]
     L.spicey_run_device.restype = C.c_int32
     L.spicey_run_device.argtypes = [vp, C.c_int64, C.c_double, vp, vp, vp, vp, vp]
+    L.spicey_run_src.restype = C.c_int32
+    L.spicey_run_src.argtypes = [vp, C.c_int64, C.c_double, f64p, C.c_int32, f64p, f64p, i32p]
+    L.spicey_run_device_src.restype = C.c_int32
+    L.spicey_run_device_src.argtypes = [vp, C.c_int64, C.c_double, vp, C.c_int32, vp, vp, vp, vp]
+    L.spicey_last_inst_status.restype = C.c_int32
+    L.spicey_last_inst_status.argtypes = [vp, i32p]
     L.spicey_sync.restype = C.c_int32
     L.spicey_sync.argtypes = [vp]
     L.spicey_group_retries.restype = C.c_int32
@@ -88,6 +94,8 @@ def load():
     L.spicey_create_multi.argtypes = [C.POINTER(abi.SpiceyDesc), C.POINTER(abi.SpiceyOptions), i32p, C.c_int32, C.POINTER(vp)]
     L.spicey_run_multi.restype = C.c_int32
     L.spicey_run_multi.argtypes = [vp, C.c_int64, C.c_double, f64p, f64p, f64p, i32p]
+    L.spicey_run_multi_src.restype = C.c_int32
+    L.spicey_run_multi_src.argtypes = [vp, C.c_int64, C.c_double, f64p, C.c_int32, f64p, f64p, i32p]
     L.spicey_get_state_multi.restype = C.c_int32
     L.spicey_get_state_multi.argtypes = [vp, f64p, f64p, f64p, i32p]
     L.spicey_multi_get_shard.restype = C.c_int32
@@ -128,6 +136,16 @@ def _p(a, t):
     return a.ctypes.data_as(C.POINTER(t)) if a is not None else None
 
 
+def _src_layout(src: np.ndarray, f: abi.FlatCircuit, steps: int) -> bool:
+    """True for one table per instance [n_inst][steps+1][nV], False for one shared [steps+1][nV]; anything else raises."""
+    if src.shape == (steps + 1, f.nV):
+        return False
+    if src.shape == (f.n_inst, steps + 1, f.nV):
+        return True
+    raise ValueError(f"src_table must be [steps+1][nV] = {(steps + 1, f.nV)} or [n_inst][steps+1][nV] = {(f.n_inst, steps + 1, f.nV)}, "
+                     f"got {src.shape}")
+
+
 class Handle:
     """Owns one SpiceyHandle (one topology, n_inst instances, one device)."""
 
@@ -165,20 +183,31 @@ class Handle:
         return m.decode() if m else ""
 
     def run(self, steps: int, dt: float, src: np.ndarray, want_currents: bool = True, want_iters: bool = True) -> dict:
+        """src: [steps+1][nV], shared by every instance (spicey_run), or [n_inst][steps+1][nV], one table per instance
+        (spicey_run_src).  The result carries `inst_status` (spicey_last_inst_status); with per-instance tables it is
+        `partial` = True, and after a singular run out_v / out_i / iters / state then hold the instances that finished."""
         f = self.flat
         src = np.ascontiguousarray(src, dtype=np.float64)
-        if src.shape != (steps + 1, f.nV):
-            raise ValueError(f"src_table must be [steps+1][nV] = {(steps + 1, f.nV)}, got {src.shape}")
+        per_inst = _src_layout(src, f, steps)
         out_v = np.empty((f.n_inst, steps + 1, f.n_out))
         out_i = np.empty((f.n_inst, steps + 1, f.n_cur)) if want_currents else None
         iters = np.zeros((f.n_inst, steps + 1), np.int32) if want_iters else None
-        rc = self.L.spicey_run(self.h, steps, dt, _p(src, C.c_double), _p(out_v, C.c_double), _p(out_i, C.c_double),
-                               _p(iters, C.c_int32))
-        res = {"status": rc, "detail": self.error() if rc != abi.OK else "", "out_v": out_v, "out_i": out_i, "iters": iters}
+        if per_inst:
+            rc = self.L.spicey_run_src(self.h, steps, dt, _p(src, C.c_double), 1, _p(out_v, C.c_double), _p(out_i, C.c_double),
+                                       _p(iters, C.c_int32))
+        else:
+            rc = self.L.spicey_run(self.h, steps, dt, _p(src, C.c_double), _p(out_v, C.c_double), _p(out_i, C.c_double),
+                                   _p(iters, C.c_int32))
+        res = {"status": rc, "detail": self.error() if rc != abi.OK else "", "out_v": out_v, "out_i": out_i, "iters": iters,
+               "partial": per_inst}
+        res["inst_status"] = self.inst_status() if rc in (abi.OK, abi.ERR_SINGULAR) else np.full(f.n_inst, rc, np.int32)
         if rc == abi.OK:
-            res["state"] = self.state()
             res["solves"] = self.L.spicey_last_solve_count(self.h)
             res["kernel_ms"] = self.L.spicey_last_kernel_ms(self.h)
+        # (after a singular run with per-instance tables, the instances that finished keep everything a success reports:
+        # results, end state and their diagnostics)
+        if rc == abi.OK or (per_inst and rc == abi.ERR_SINGULAR):
+            res["state"] = self.state()
             if self.diagnostics & 1:
                 per = np.zeros(f.n_inst, np.int64)
                 self.L.spicey_last_skip_risk(self.h, _p(per, C.c_int64))
@@ -190,11 +219,24 @@ class Handle:
                 res["lin_err"] = le
         return res
 
-    def run_device(self, steps: int, dt: float, d_src: int, d_out_v: int, d_out_i: int = 0, d_iters: int = 0, stream: int = 0) -> None:
-        """Enqueue with raw device pointers (e.g. torch tensors' data_ptr()); no synchronisation."""
-        rc = self.L.spicey_run_device(self.h, steps, dt, d_src, d_out_v, d_out_i or None, d_iters or None, stream or None)
+    def run_device(self, steps: int, dt: float, d_src: int, d_out_v: int, d_out_i: int = 0, d_iters: int = 0, stream: int = 0,
+                   src_per_inst: bool = False) -> None:
+        """Enqueue with raw device pointers (e.g. torch tensors' data_ptr()); no synchronisation.  src_per_inst: d_src holds
+        [n_inst][steps+1][nV] (spicey_run_device_src) instead of one shared [steps+1][nV] table."""
+        if src_per_inst:
+            rc = self.L.spicey_run_device_src(self.h, steps, dt, d_src, 1, d_out_v, d_out_i or None, d_iters or None, stream or None)
+        else:
+            rc = self.L.spicey_run_device(self.h, steps, dt, d_src, d_out_v, d_out_i or None, d_iters or None, stream or None)
         if rc != abi.OK:
             raise SpiceyNativeError(f"spicey_run_device failed ({rc}): {self.error()}")
+
+    def inst_status(self) -> np.ndarray:
+        """Per instance of the last run (spicey_last_inst_status): 0 finished, 1 = SPICEY_ERR_SINGULAR (its own solve), -1 =
+        stopped because another instance of its workgroup failed, 3 = the launch aborted."""
+        st = np.zeros(self.flat.n_inst, np.int32)
+        if self.L.spicey_last_inst_status(self.h, _p(st, C.c_int32)) < 0:
+            raise SpiceyNativeError(f"spicey_last_inst_status failed: {self.error()}")
+        return st
 
     def sync(self) -> int:
         return self.L.spicey_sync(self.h)
@@ -309,12 +351,18 @@ class MultiHandle:
             i += 1
 
     def run(self, steps: int, dt: float, src: np.ndarray, want_currents: bool = True, want_iters: bool = True) -> dict:
+        """src: [steps+1][nV] shared, or [n_inst][steps+1][nV] per instance (spicey_run_multi_src: each shard its slice)."""
         f = self.flat
         src = np.ascontiguousarray(src, dtype=np.float64)
+        per_inst = src.ndim == 3 and _src_layout(src, f, steps)
         out_v = np.empty((f.n_inst, steps + 1, f.n_out))
         out_i = np.empty((f.n_inst, steps + 1, f.n_cur)) if want_currents else None
         iters = np.zeros((f.n_inst, steps + 1), np.int32) if want_iters else None
-        rc = self.L.spicey_run_multi(self.h, steps, dt, _p(src, C.c_double), _p(out_v, C.c_double), _p(out_i, C.c_double), _p(iters, C.c_int32))
+        if per_inst:
+            rc = self.L.spicey_run_multi_src(self.h, steps, dt, _p(src, C.c_double), 1, _p(out_v, C.c_double), _p(out_i, C.c_double),
+                                             _p(iters, C.c_int32))
+        else:
+            rc = self.L.spicey_run_multi(self.h, steps, dt, _p(src, C.c_double), _p(out_v, C.c_double), _p(out_i, C.c_double), _p(iters, C.c_int32))
         detail = self.L.spicey_multi_last_error(self.h).decode() if rc != abi.OK else ""
         res = {"status": rc, "detail": detail, "out_v": out_v, "out_i": out_i, "iters": iters}
         if rc == abi.OK:

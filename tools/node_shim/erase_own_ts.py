@@ -11,7 +11,7 @@ import re
 import sys
 
 REPO = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-FILES = ["abiLayout.ts", "spiceyHip.ts", "simulateTRAN.ts", "simulateAC.ts", "constants.ts", "types.ts", "NodeIndex.ts", "numbers.ts",
+FILES = ["abiLayout.ts", "spiceyHip.ts", "simulateTRAN.ts", "simulateTRANBatch.ts", "simulateAC.ts", "constants.ts", "types.ts", "NodeIndex.ts", "numbers.ts",
          "waveforms.ts", "parseNetlist.ts", "Complex.ts", "logspace.ts", "format.ts", "simulate.ts", "index.ts"]
 STUBS = {}  # (ts/ is self-contained since round 3: nothing is imported from the reference's lib/ any more)
 

@@ -6,14 +6,14 @@ import type { ParsedCircuit } from "./types"
 import { runTransientNative, type FlatCircuit } from "./spiceyHip"
 
 /** simulateTRAN.ts:14-19 verbatim semantics: must be the same double operations in the same order. */
-function computeEffectiveTimeStep(dtRequested: number, tstop: number) {
+export function computeEffectiveTimeStep(dtRequested: number, tstop: number) {
   const dtEff = dtRequested > EPS ? dtRequested : Math.max(tstop / 1000, EPS)
   const steps = Math.max(1, Math.ceil(tstop / Math.max(dtEff, EPS)))
   const dt = steps > 0 ? tstop / steps : tstop
   return { dt, steps }
 }
 
-function flatten(ckt: ParsedCircuit): FlatCircuit {
+export function flatten(ckt: ParsedCircuit): FlatCircuit {
   const S = ckt.S.filter((s) => s.model)
   const D = ckt.D.filter((d) => d.model)
   const i32 = (a: number[]) => Int32Array.from(a)

@@ -27,6 +27,12 @@ const { symbols: C } = dlopen(libPath, {
     args: [FFIType.ptr, FFIType.i64, FFIType.f64, FFIType.ptr, FFIType.ptr, FFIType.ptr, FFIType.ptr],
     returns: FFIType.i32,
   },
+  // per-instance source tables (src_per_inst = 1: [n_inst][steps+1][nV]) and the per-instance outcome of the last run
+  spicey_run_src: {
+    args: [FFIType.ptr, FFIType.i64, FFIType.f64, FFIType.ptr, FFIType.i32, FFIType.ptr, FFIType.ptr, FFIType.ptr],
+    returns: FFIType.i32,
+  },
+  spicey_last_inst_status: { args: [FFIType.ptr, FFIType.ptr], returns: FFIType.i32 },
   spicey_get_state: { args: [FFIType.ptr, FFIType.ptr, FFIType.ptr, FFIType.ptr, FFIType.ptr], returns: FFIType.i32 },
   // several devices behind one handle: instances block-partitioned over `devices`, results gathered into one buffer
   spicey_create_multi: { args: [FFIType.ptr, FFIType.ptr, FFIType.ptr, FFIType.i32, FFIType.ptr], returns: FFIType.i32 },
@@ -68,7 +74,7 @@ export type FlatCircuit = {
 // bun:ffi cannot take a pointer to an empty TypedArray; zero-length arrays are passed as NULL
 const P = (a: ArrayBufferView): bigint => (a.byteLength === 0 ? 0n : BigInt(ptr(a as any) as unknown as number))
 
-function packDesc(f: FlatCircuit): { buf: ArrayBuffer; keep: ArrayBufferView[] } {
+function packDesc(f: FlatCircuit, nInst = 1): { buf: ArrayBuffer; keep: ArrayBufferView[] } {
   const L = SpiceyDescLayout.fields
   const buf = new ArrayBuffer(SpiceyDescLayout.size)
   const dv = new DataView(buf)
@@ -76,7 +82,7 @@ function packDesc(f: FlatCircuit): { buf: ArrayBuffer; keep: ArrayBufferView[] }
   const p64 = (k: keyof typeof L, a: ArrayBufferView) => dv.setBigUint64(L[k].offset, P(a), true)
   i32("abi_version", SPICEY_ABI_VERSION)
   i32("n_nodes", f.nNodes)
-  i32("n_inst", 1)
+  i32("n_inst", nInst)
   i32("nR", f.R.n1.length); i32("nC", f.C.n1.length); i32("nL", f.L.n1.length)
   i32("nV", f.V.n1.length); i32("nS", f.S.n1.length); i32("nD", f.D.np.length)
   p64("R_n1", f.R.n1); p64("R_n2", f.R.n2); p64("R_val", f.R.val)
@@ -147,6 +153,91 @@ export function runTransientNative(f: FlatCircuit, steps: number, dt: number, sr
     if (rc !== SPICEY_OK) throw new Error(`spicey_get_state failed (${rc}): ${lastError(h)}`)
     const skipRisk = Number(C.spicey_last_skip_risk(h, null))
     return { outV, outI, iters, state, skipRisk }
+  } finally {
+    C.spicey_destroy(h)
+  }
+}
+
+/** Instances of one topology (the first one's node ids and element order) as one descriptor: value and state arrays
+ *  concatenated instance-major ([n_inst][n<kind>], include/spicey_hip.h). */
+type ValuesOf = (f: FlatCircuit) => Float64Array | Int32Array
+
+function stackFlats(fs: FlatCircuit[]): FlatCircuit {
+  const f0 = fs[0]!
+  const cat = (pick: ValuesOf): any => {
+    const parts = fs.map(pick)
+    const out = parts[0] instanceof Int32Array ? new Int32Array(parts.reduce((n, a) => n + a.length, 0)) : new Float64Array(parts.reduce((n, a) => n + a.length, 0))
+    let o = 0
+    for (const a of parts) { out.set(a, o); o += a.length }
+    return out
+  }
+  return {
+    nNodes: f0.nNodes, outNodes: f0.outNodes,
+    R: { ...f0.R, val: cat((f) => f.R.val) },
+    C: { ...f0.C, val: cat((f) => f.C.val), vPrev: cat((f) => f.C.vPrev) },
+    L: { ...f0.L, val: cat((f) => f.L.val), iPrev: cat((f) => f.L.iPrev) },
+    V: f0.V,
+    S: { ...f0.S, ron: cat((f) => f.S.ron), roff: cat((f) => f.S.roff), von: cat((f) => f.S.von), voff: cat((f) => f.S.voff), isOn: cat((f) => f.S.isOn) },
+    D: { ...f0.D, is: cat((f) => f.D.is), n: cat((f) => f.D.n), vdPrev: cat((f) => f.D.vdPrev) },
+  }
+}
+
+export type NativeBatchResult = {
+  /** per instance: its result when it reached its last step (status 0), else null */
+  results: (NativeTranResult | null)[]
+  /** spicey_last_inst_status: 0 finished, SPICEY_ERR_SINGULAR = its own solve was singular, -1 = stopped because another
+   *  instance of its workgroup failed (run it again) */
+  status: Int32Array
+}
+
+export type NativeBatchOptions = NativeTranOptions & {
+  /** SpiceyOptions.diagnostics bit 0 (skipRisk); without it the handle may take the throughput geometry, K = 4, the hybrid kernel */
+  diagnostics?: boolean
+}
+
+/** Several instances of one topology in one launch (spicey_run_src).  srcTables: one shared [steps+1][nV] table, or one per
+ *  instance [n_inst][steps+1][nV] when perInstance.  Never throws for a singular instance: see `status`. */
+export function runTransientBatchNative(fs: FlatCircuit[], steps: number, dt: number, srcTables: Float64Array, perInstance: boolean,
+                                        options?: NativeBatchOptions): NativeBatchResult {
+  const ni = fs.length
+  const flat = stackFlats(fs)
+  const { buf, keep } = packDesc(flat, ni)
+  const opt = new ArrayBuffer(SpiceyOptionsLayout.size)
+  new DataView(opt).setInt32(SpiceyOptionsLayout.fields.want_currents.offset, 1, true)
+  if (options?.diagnostics !== false) new DataView(opt).setInt32(SpiceyOptionsLayout.fields.diagnostics.offset, 1, true)
+  if (options?.interpreter) new DataView(opt).setInt32(SpiceyOptionsLayout.fields.interpreter.offset, options.interpreter, true)
+  const hOut = new BigUint64Array(1)
+  let rc = C.spicey_create(ptr(buf), ptr(opt), ptr(hOut))
+  void keep
+  if (rc !== SPICEY_OK) throw new Error(`spicey_create failed (${rc}): ${lastError(null)}`)
+  const h = Number(hOut[0]) as unknown as Pointer
+  try {
+    const f0 = fs[0]!
+    const nC = f0.C.n1.length, nL = f0.L.n1.length, nD = f0.D.np.length, nS = f0.S.n1.length
+    const nCur = f0.R.n1.length + nC + nL + f0.V.n1.length + nS + nD
+    const nOut = f0.outNodes && f0.outNodes.length ? f0.outNodes.length : f0.nNodes
+    const np1 = steps + 1
+    const outV = new Float64Array(ni * np1 * Math.max(nOut, 1))
+    const outI = new Float64Array(ni * np1 * Math.max(nCur, 1))
+    const iters = new Int32Array(ni * np1)
+    rc = C.spicey_run_src(h, BigInt(steps), dt, srcTables.length ? ptr(srcTables) : null, perInstance ? 1 : 0, ptr(outV), ptr(outI), ptr(iters))
+    if (rc !== SPICEY_OK && rc !== SPICEY_ERR_SINGULAR) throw new Error(`spicey_run_src failed (${rc}): ${lastError(h)}`)
+    const status = new Int32Array(ni)
+    if (C.spicey_last_inst_status(h, ptr(status)) < 0) throw new Error(`spicey_last_inst_status failed: ${lastError(h)}`)
+    const vPrev = new Float64Array(ni * nC), iPrev = new Float64Array(ni * nL), vdPrev = new Float64Array(ni * nD), isOn = new Int32Array(ni * nS)
+    rc = C.spicey_get_state(h, vPrev.length ? ptr(vPrev) : null, iPrev.length ? ptr(iPrev) : null, vdPrev.length ? ptr(vdPrev) : null,
+      isOn.length ? ptr(isOn) : null)
+    if (rc !== SPICEY_OK) throw new Error(`spicey_get_state failed (${rc}): ${lastError(h)}`)
+    const skip = new BigInt64Array(ni)
+    if (options?.diagnostics !== false) C.spicey_last_skip_risk(h, ptr(skip))
+    const results = Array.from(status, (s, j): NativeTranResult | null => s !== 0 ? null : {
+      outV: outV.slice(j * np1 * nOut, (j + 1) * np1 * nOut), outI: outI.slice(j * np1 * nCur, (j + 1) * np1 * nCur),
+      iters: iters.slice(j * np1, (j + 1) * np1),
+      state: { vPrev: vPrev.slice(j * nC, (j + 1) * nC), iPrev: iPrev.slice(j * nL, (j + 1) * nL), vdPrev: vdPrev.slice(j * nD, (j + 1) * nD),
+               isOn: isOn.slice(j * nS, (j + 1) * nS) },
+      skipRisk: Number(skip[j]),
+    })
+    return { results, status }
   } finally {
     C.spicey_destroy(h)
   }
