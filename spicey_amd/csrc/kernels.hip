@@ -492,7 +492,8 @@ struct GpuExecV2 {
   }
 };
 
-template <int K, int RMAX, int NSV, int NEL, int MAXT, int MINW, bool HYB = false>
+// PT: 1 = the phases take their run-invariant arguments from the phase table in LDS (tran_exec.h), 0 = by scalar loads
+template <int K, int RMAX, int NSV, int NEL, int MAXT, int MINW, bool HYB = false, int PT = 0>
 __global__ void __launch_bounds__(MAXT, MINW) spicey_tran_kernel_v2(const SpiceyProg *__restrict__ Pg, const SpiceyResident *__restrict__ Qg,
                                                                     const SpiceyRun *__restrict__ Rg) {
   const SpiceyProg &P = *Pg;
@@ -541,7 +542,7 @@ __global__ void __launch_bounds__(MAXT, MINW) spicey_tran_kernel_v2(const Spicey
     // start stamps wait in their own slots (not in registers: nothing may stay live around the whole run)
     if (threadIdx.x == 0) { lprof[5] = (unsigned long long)clock64(); lprof[6] = (unsigned long long)wall_clock64(); }
   }
-  spicey_tran_run_v2<K, RMAX, NSV, NEL, HYB>(ex, P, Q, R, c, wg);
+  spicey_tran_run_v2<K, RMAX, NSV, NEL, HYB, PT>(ex, P, Q, R, c, wg);
   if (R.prof) {
     __syncthreads();
     if (threadIdx.x == 0) {  // slots 5/6: whole-run shader cycles and 100 MHz wall ticks -> effective clock
@@ -553,9 +554,9 @@ __global__ void __launch_bounds__(MAXT, MINW) spicey_tran_kernel_v2(const Spicey
   }
 }
 
-template <int K, int RMAX, int NSV, int NEL, int MAXT, int MINW, bool HYB = false>
+template <int K, int RMAX, int NSV, int NEL, int MAXT, int MINW, bool HYB = false, int PT = 0>
 hipError_t launch_v2_t(const SpiceyProg *P, const SpiceyResident *Q, const SpiceyRun *R, int grid, int threads, size_t lds, hipStream_t st) {
-  auto kern = spicey_tran_kernel_v2<K, RMAX, NSV, NEL, MAXT, MINW, HYB>;
+  auto kern = spicey_tran_kernel_v2<K, RMAX, NSV, NEL, MAXT, MINW, HYB, PT>;
   if (lds > 48 * 1024) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
@@ -639,18 +640,24 @@ hipError_t spicey_launch_tran(const SpiceyProg &P, const SpiceyRun &R, int K, bo
 }
 
 // one launcher per entry of SPICEY_V2_SHAPES (launch_plan.h)
-template <int I>
+template <int I, int PT = 0>
 static hipError_t launch_v2_shape(const SpiceyProg *P, const SpiceyResident *Q, const SpiceyRun *R, int grid, int threads, size_t lds, hipStream_t st) {
   constexpr SpiceyV2Shape s = SPICEY_V2_SHAPES[I];
-  return launch_v2_t<1, s.rmax, s.nsv, s.nel, s.threads, s.minw, s.hybrid>(P, Q, R, grid, threads, lds, st);
+  return launch_v2_t<1, s.rmax, s.nsv, s.nel, s.threads, s.minw, s.hybrid, PT>(P, Q, R, grid, threads, lds, st);
 }
 static decltype(&launch_v2_shape<0>) const launch_v2_by_shape[] = {launch_v2_shape<0>, launch_v2_shape<1>, launch_v2_shape<2>,
                                                                     launch_v2_shape<3>, launch_v2_shape<4>, launch_v2_shape<5>};
 static_assert(sizeof(launch_v2_by_shape) / sizeof(launch_v2_by_shape[0]) == SPICEY_V2_NSHAPES, "one launcher per v2 build");
+// the same builds with the phase table (null: that shape has none and keeps the scalar loads — SPICEY_V2_SHAPES order)
+static decltype(&launch_v2_shape<0>) const launch_v2_pt_by_shape[] = {launch_v2_shape<0, 1>, launch_v2_shape<1, 1>, launch_v2_shape<2, 1>,
+                                                                       launch_v2_shape<3, 1>, launch_v2_shape<4, 1>, launch_v2_shape<5, 1>};
+static_assert(sizeof(launch_v2_pt_by_shape) / sizeof(launch_v2_pt_by_shape[0]) == SPICEY_V2_NSHAPES, "one entry per v2 build");
 
 hipError_t spicey_launch_tran_v2(const SpiceyProg &Ph, const SpiceyResident &Qh, const SpiceyProg *P, const SpiceyResident *Q, const SpiceyRun *R, int K, int grid,
-                                 int threads, hipStream_t st, bool packed) {
+                                 int threads, hipStream_t st, bool packed, bool phase_table) {
   const int shape = K == 1 ? spicey_v2_shape(threads, packed, Ph.hybrid != 0) : -1;
   if (shape < 0) return hipErrorInvalidValue;
-  return launch_v2_by_shape[shape](P, Q, R, grid, threads, spicey_lds_bytes(Ph, K, true, Qh.tail_n), st);
+  // the table sits in the tail area behind the tridiagonal top's index table: only where it fits there (tran_exec.h)
+  const bool pt = phase_table && launch_v2_pt_by_shape[shape] != nullptr && spicey_pt_fits(Ph.pcr_n, Ph.pcr_level, Qh.tail_n);
+  return (pt ? launch_v2_pt_by_shape : launch_v2_by_shape)[shape](P, Q, R, grid, threads, spicey_lds_bytes(Ph, K, true, Qh.tail_n), st);
 }

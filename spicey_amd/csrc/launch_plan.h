@@ -49,6 +49,7 @@ struct SpiceyKnobs {
   bool front_right_looking = false;  // SPICEY_FRONT_RIGHT_LOOKING: experiments, the round-2 sweep of staged fronts
   bool force_group_abort = false;    // SPICEY_TEST_FORCE_GROUP_ABORT: tests, the first attempt of every group launch aborts
   int group_timeout_ms = 0;          // SPICEY_GROUP_TIMEOUT_MS: group-mode wait bound when SpiceyOptions leaves it 0
+  bool no_phase_table = false;       // SPICEY_NO_PHASE_TABLE: the 16-bit interpreter fetches its phase arguments by scalar loads in every phase (tran_exec.h)
 };
 SpiceyKnobs spicey_read_knobs();
 

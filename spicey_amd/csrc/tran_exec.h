@@ -19,7 +19,9 @@
 //   Z    recording, state update, and the NEXT step's element evaluation          simulateTRAN.ts:164-237
 #pragma once
 #include <math.h>
+#include <stddef.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #include "program.h"
 
@@ -132,6 +134,111 @@ struct WgCtx {
 #endif
   int32_t inst[K];
   int32_t valid[K];
+};
+
+// A copy of an argument struct that lives in global memory, through an address the compiler cannot trace back: the fields
+// the surrounding code uses are scalar-loaded HERE (s_load, scalar cache), the rest of the copy is dead (see GpuExecV2::fresh).
+// On the host (the emulator) it is the struct itself.
+template <class X>
+SPICEY_HD X spicey_fresh(const X &x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  typedef const X __attribute__((address_space(4))) *cptr;
+  cptr p = (cptr)(&x);
+  asm volatile("" : "+s"(p));
+  X v;
+  __builtin_memcpy(&v, p, sizeof(X));
+  return v;
+#else
+  return x;
+#endif
+}
+
+// ---- run-invariant phase arguments, kept on chip (16-bit interpreter, K = 1, tridiagonal-top builds) -------------------
+// What a phase of the time loop needs from SpiceyProg / SpiceyResident / SpiceyRun never changes during a run, yet every
+// phase of every step used to fetch it again through scalar loads.  Where those loads were CHAINED they stood exposed in
+// front of the phase's first work: three dependent round trips in front of a streamed phase's first record, two in front
+// of Z's parameter fetch, three and four at the heads of B and Z (profiles/NOTES_r04.md).  The prologue now writes the
+// values ONCE into a table in LDS.  A phase head reads them with one ds_read_b32 — lane l reads word l — and moves each
+// word to a scalar by v_readlane (SpiceyPtLanes); the rare reads inside divergent code are same-address broadcast reads.
+// The table lives in space that is reserved already: the tail area of a tridiagonal-top build is 5 KB (launch_plan.cpp),
+// of which the two row buffers take 4 KB and the top's index table pcr_n * 8 <= 512 B.  Layout, in 32-bit words from
+// c.tail + 1024 + (pcr_n * 2 rounded up to 4): SPICEY_PT_RUN run-wide words (below), then one 8-word row per phase that
+// can be streamed — the factor phases [0, pcr_level) and the backward phases [2 nLevels - pcr_level, 2 nLevels) — holding
+// that phase's SpiceyResident::st_desc row.  A program whose rows do not fit (deep elimination trees), one without a top
+// (its tail area is full of tail records) or a handle created with SPICEY_NO_PHASE_TABLE set keeps the scalar loads: both paths
+// are compiled and give identical bits (same operands, same order; only addresses and counts come from elsewhere).
+#define SPICEY_PT_RUN 48
+enum {
+  SPICEY_PT_XOFF = 0, SPICEY_PT_NRESTORE, SPICEY_PT_NDYNENT, SPICEY_PT_NGSTAT, SPICEY_PT_NR, SPICEY_PT_NC, SPICEY_PT_NL, SPICEY_PT_NV,
+  // 64-bit values, two words each.  (Words 8..13: what a streamed phase needs beside its row — SpiceyPtLanes::row.)
+  SPICEY_PT_OVF16 = 8, SPICEY_PT_REC16 = 10, SPICEY_PT_FUS16 = 12,
+  SPICEY_PT_NS = 14, SPICEY_PT_ND, SPICEY_PT_NOUT, SPICEY_PT_NCUR,
+  SPICEY_PT_STEPS = 18, SPICEY_PT_SRC = 20, SPICEY_PT_SRC_STRIDE = 22, SPICEY_PT_OUT_V = 24, SPICEY_PT_OUT_I = 26, SPICEY_PT_GSTAT = 28,
+  SPICEY_PT_DPAR = 30, SPICEY_PT_D_IS = 32, SPICEY_PT_C_VPREV = 34, SPICEY_PT_D_VDPREV = 36, SPICEY_PT_ITERS = 38, SPICEY_PT_LIN_VD = 40,
+  SPICEY_PT_LIN_ERR = 42,
+  SPICEY_PT_USED = 44
+};
+static_assert(SPICEY_PT_USED <= SPICEY_PT_RUN && SPICEY_PT_RUN <= 64 && SPICEY_PT_RUN % 4 == 0, "run-wide block of the phase table: at most one word per lane of a wave");
+SPICEY_HD int spicey_pt_base_words(int pcr_n) { return 1024 + ((pcr_n * 2 + 3) & ~3); }
+// rows of the table of a program with its top at level `pcr_level`, and whether they fit behind the top's index table
+SPICEY_HD int spicey_pt_words(int pcr_level) { return SPICEY_PT_RUN + 16 * pcr_level; }
+SPICEY_HD bool spicey_pt_fits(int pcr_n, int pcr_level, int tail_n) {
+  // (a phase head reads 64 consecutive words from the start of the table, SpiceyPtLanes: with pcr_level >= 1 they lie inside it)
+  return pcr_n > 0 && pcr_n <= 64 && pcr_level >= 1 && tail_n == 0 && spicey_pt_base_words(pcr_n) + spicey_pt_words(pcr_level) <= 5 * 256;
+}
+SPICEY_HD uint32_t spicey_pt_u32(const uint32_t *pt, int i) { return (uint32_t)SPICEY_UNIFORM((int)pt[i]); }
+SPICEY_HD uint64_t spicey_pt_u64(const uint32_t *pt, int i) { return (uint64_t)spicey_pt_u32(pt, i) | ((uint64_t)spicey_pt_u32(pt, i + 1) << 32); }
+template <class X>
+SPICEY_HD X *spicey_pt_ptr(const uint32_t *pt, int i) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  typedef X __attribute__((address_space(1))) *gptr;  // (a global-memory pointer: accesses through it stay global_load / global_store, not flat)
+  return (X *)(gptr)(uintptr_t)spicey_pt_u64(pt, i);
+#else
+  return (X *)(uintptr_t)spicey_pt_u64(pt, i);
+#endif
+}
+SPICEY_HD void spicey_pt_put64(uint32_t *pt, int i, uint64_t v) { pt[i] = (uint32_t)v; pt[i + 1] = (uint32_t)(v >> 32); }
+// (the three above: one word, read by every ACTIVE lane from the same address — for the rare reads inside divergent code)
+// Many words at a phase head, where the whole wave is active: lane l reads word l — ONE ds_read_b32, one vector register —
+// and each word goes to a scalar by v_readlane at a constant lane.  (Broadcast reads would hold a vector register per
+// word until it has been moved: the 128-register builds have none to give.)
+struct SpiceyPtLanes {
+#if defined(__HIP_DEVICE_COMPILE__)
+  int v;
+  __device__ __forceinline__ uint32_t u32(int i) const { return (uint32_t)__builtin_amdgcn_readlane(v, i); }
+#else
+  const uint32_t *run, *rowp;
+  uint32_t u32(int i) const { return (rowp && i < 8) ? rowp[i] : run[i]; }
+#endif
+  SPICEY_HD uint64_t u64(int i) const { return (uint64_t)u32(i) | ((uint64_t)u32(i + 1) << 32); }
+  template <class X>
+  SPICEY_HD X *ptr(int i) const {
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef X __attribute__((address_space(1))) *gptr;
+    return (X *)(gptr)(uintptr_t)u64(i);
+#else
+    return (X *)(uintptr_t)u64(i);
+#endif
+  }
+  // the run-wide block
+  static SPICEY_HD SpiceyPtLanes run_block(const uint32_t *pt, int tid) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return SpiceyPtLanes{(int)pt[tid & 63]};
+#else
+    (void)tid;
+    return SpiceyPtLanes{pt, nullptr};
+#endif
+  }
+  // words 0..7 = row `row` of the per-phase rows, words 8.. = the run-wide block's
+  static SPICEY_HD SpiceyPtLanes row(const uint32_t *pt, int tid, int row) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const int l = tid & 63;
+    return SpiceyPtLanes{(int)pt[l < 8 ? SPICEY_PT_RUN + row * 8 + l : l]};
+#else
+    (void)tid;
+    return SpiceyPtLanes{pt, pt + SPICEY_PT_RUN + row * 8};
+#endif
+  }
 };
 
 // 1/x for pivots: hardware reciprocal seed + two Newton steps (<= 1 ulp; the result feeds a 1e-9 parity
@@ -639,8 +746,10 @@ struct ResRegs {
 // the pivot's own entries (L, reciprocal diagonal, U) are read from the global array c.G by entry id, every target and
 // every right-hand-side / solution operand from LDS as always (`xoff` = first LDS index of the right-hand side: the third
 // operand of a right-hand-side task is y_k, not an entry).
-template <int K, bool KTASK, bool OPG = false>
-SPICEY_HD void spicey_exec_rec16(const WgCtx<K> &c, const uint16_t *ovf, uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3,
+// `ovf()` yields the overflow list (SpiceyProg::ovf16): asked for only by a task of more than two products, so that a phase
+// without one fetches nothing for it.
+template <int K, bool KTASK, bool OPG = false, class OV>
+SPICEY_HD void spicey_exec_rec16(const WgCtx<K> &c, OV ovf, uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3,
                                  uint32_t keep_from = 0u, uint32_t xoff = 0u) {
   const uint32_t meta = w0 >> 16;
   if (!(meta & (SPICEY_R16_VALID << 8))) return;
@@ -674,7 +783,7 @@ SPICEY_HD void spicey_exec_rec16(const WgCtx<K> &c, const uint16_t *ovf, uint32_
       }
     } else {
       for (int k = 0; k < K; k++) acc[k] = c.W[(size_t)tgt * K + k];
-      const uint16_t *o = ovf + w3;
+      const uint16_t *o = ovf() + w3;
       for (uint32_t j = 0; j < cnt; j++) {
         const uint32_t u = o[2 * j], x = o[2 * j + 1];
         for (int k = 0; k < K; k++) acc[k] = fma(-E[(size_t)u * K + k], c.W[(size_t)x * K + k], acc[k]);
@@ -710,7 +819,7 @@ SPICEY_HD void spicey_exec_rec16(const WgCtx<K> &c, const uint16_t *ovf, uint32_
       }
     } else {
       for (int k = 0; k < K; k++) acc[k] = c.W[(size_t)tgt * K + k];
-      const uint16_t *o = ovf + w3;
+      const uint16_t *o = ovf() + w3;
       for (uint32_t j = 0; j < cnt; j++) {
         const uint32_t l = o[3 * j], d = o[3 * j + 1], u = o[3 * j + 2];
         for (int k = 0; k < K; k++) {
@@ -810,10 +919,21 @@ SPICEY_HD void spicey_exec_row16_x2(const WgCtx<K> &c, const uint32_t *wa, const
   }
 }
 
+// the phase table of this workgroup (`on`: wave-uniform, fixed for the run) and the row of the phase at hand
+struct SpiceyPt {
+  const uint32_t *w;
+  bool on;
+  int row;
+};
+
+// P, Q: the argument structs where they live (global memory on the GPU).  Nothing is fetched from them, or from the phase
+// table, before it is needed: a resident phase of tasks with at most two products reads no argument at all.
 template <int K, int RMAX, int NSV, int NEL, bool KTASK, bool OPG = false>
-SPICEY_HD void spicey_uk_phase(const SpiceyProg &P, const SpiceyResident &Q, const WgCtx<K> &c, ResRegs<K, RMAX, NSV, NEL> &rr, int tid,
+SPICEY_HD void spicey_uk_phase(const SpiceyProg &P, const SpiceyResident &Q, const SpiceyPt pt, const WgCtx<K> &c, ResRegs<K, RMAX, NSV, NEL> &rr, int tid,
                                int T, int p, bool streamed, bool reuse = false) {
-  const uint32_t xoff = (uint32_t)P.xoff;  // first LDS index of the right-hand side (= nLU without the hybrid layout)
+  auto ovf = [&]() -> const uint16_t * { return pt.on ? spicey_pt_ptr<const uint16_t>(pt.w, SPICEY_PT_OVF16) : spicey_fresh(P).ovf16; };
+  uint32_t xoff = 0u;  // first LDS index of the right-hand side (= nLU without the hybrid layout)
+  if (OPG || (!KTASK && reuse)) xoff = pt.on ? spicey_pt_u32(pt.w, SPICEY_PT_XOFF) : (uint32_t)spicey_fresh(P).xoff;
   const uint32_t keep_from = (!KTASK && reuse) ? xoff : 0u;
   if (RMAX <= 8) {
     // few slots: a static compare chain (scalar compares on the wave-uniform phase bytes).  Measured faster than
@@ -831,7 +951,7 @@ SPICEY_HD void spicey_uk_phase(const SpiceyProg &P, const SpiceyResident &Q, con
           SPICEY_OPAQUE(w[4]); SPICEY_OPAQUE(w[5]); SPICEY_OPAQUE(w[6]); SPICEY_OPAQUE(w[7]);
           spicey_exec_row16<K, OPG>(c, w, reuse);
         } else {
-          spicey_exec_rec16<K, KTASK, OPG>(c, P.ovf16, w0, w1, w2, w3, keep_from, xoff);
+          spicey_exec_rec16<K, KTASK, OPG>(c, ovf, w0, w1, w2, w3, keep_from, xoff);
         }
       }
     }
@@ -851,23 +971,37 @@ SPICEY_HD void spicey_uk_phase(const SpiceyProg &P, const SpiceyResident &Q, con
         spicey_exec_row16<K, OPG>(c, w, reuse);
         q += 2;
       } else {
-        spicey_exec_rec16<K, KTASK, OPG>(c, P.ovf16, w0, w1, w2, w3, keep_from, xoff);
+        spicey_exec_rec16<K, KTASK, OPG>(c, ovf, w0, w1, w2, w3, keep_from, xoff);
         q++;
       }
     }
     rr.cursor = q;
   }
   if (!streamed) return;
-  // one 32-byte descriptor says where the phase's records are (SpiceyResident::st_desc)
-  const uint32_t *dsc = Q.st_desc + (size_t)p * 8;
-  const uint32_t d_rows = dsc[0], d_first = dsc[1], d_cnt = dsc[2], d_rhs = dsc[3], d_rfirst = dsc[4], d_rcnt = dsc[5], d_rrhs = dsc[6];
+  // one 32-byte descriptor says where the phase's records are (SpiceyResident::st_desc): from the phase table in LDS — one
+  // round trip between the phase head and the first record fetch — or through the argument structs (three)
+  uint32_t d_rows, d_first, d_cnt, d_rhs, d_rfirst, d_rcnt, d_rrhs;
+  const uint32_t *rec16, *fus16;
+  if (pt.on) {
+    const SpiceyPtLanes d = SpiceyPtLanes::row(pt.w, tid, pt.row);  // (the whole wave is here: `streamed` is wave-uniform)
+    d_rows = d.u32(0); d_first = d.u32(1); d_cnt = d.u32(2); d_rhs = d.u32(3); d_rfirst = d.u32(4); d_rcnt = d.u32(5); d_rrhs = d.u32(6);
+    rec16 = d.template ptr<const uint32_t>(SPICEY_PT_REC16);
+    fus16 = KTASK ? nullptr : d.template ptr<const uint32_t>(SPICEY_PT_FUS16);
+  } else {
+    const SpiceyResident Qf = spicey_fresh(Q);
+    const SpiceyProg Pf = spicey_fresh(P);
+    const uint32_t *dsc = Qf.st_desc + (size_t)p * 8;
+    d_rows = dsc[0]; d_first = dsc[1]; d_cnt = dsc[2]; d_rhs = dsc[3]; d_rfirst = dsc[4]; d_rcnt = dsc[5]; d_rrhs = dsc[6];
+    rec16 = Pf.rec16;
+    fus16 = Pf.fus16;
+  }
   uint32_t sc = (!KTASK && reuse) ? d_rhs : d_cnt;  // right-hand-side tasks lead every factor phase
-  const uint32_t *base = P.rec16 + (size_t)d_first * 4;
+  const uint32_t *base = rec16 + (size_t)d_first * 4;
   if (!KTASK && sc && d_rows) {
     // the phase's row-record encoding: its 32-byte row records (one per thread on the chains this is for), then the few
     // generic records of rows that do not fit the pattern
     const uint32_t npair = d_cnt;
-    const uint32_t *pb = P.fus16 + (size_t)d_first * 4;
+    const uint32_t *pb = fus16 + (size_t)d_first * 4;
     if constexpr (OPG && NEL >= 2) {
       // (hybrid workspace: the leaves' own entries come from L2 — two row records at a time, both fetched before either is
       // executed, so that the operand loads of the second are in flight under the first; the 1024-thread build — NEL = 1 —
@@ -888,7 +1022,7 @@ SPICEY_HD void spicey_uk_phase(const SpiceyProg &P, const SpiceyResident &Q, con
       for (int i = 0; i < 8; i++) w[i] = pb[(size_t)j * 8 + i];
       spicey_exec_row16<K, OPG>(c, w, reuse);
     }
-    base = P.fus16 + (size_t)d_rfirst * 4;
+    base = fus16 + (size_t)d_rfirst * 4;
     sc = reuse ? d_rrhs : d_rcnt;
   }
   if (sc) {
@@ -904,7 +1038,7 @@ SPICEY_HD void spicey_uk_phase(const SpiceyProg &P, const SpiceyResident &Q, con
         const bool more = jn < sc;
         const uint32_t *rn = base + (size_t)(more ? jn : j) * 4;
         const uint32_t n0 = rn[0], n1 = rn[1], n2 = rn[2], n3 = rn[3];
-        spicey_exec_rec16<K, KTASK, OPG>(c, P.ovf16, c0, c1, c2, c3, keep_from, xoff);
+        spicey_exec_rec16<K, KTASK, OPG>(c, ovf, c0, c1, c2, c3, keep_from, xoff);
         if (!more) break;
         c0 = n0; c1 = n1; c2 = n2; c3 = n3;
         j = jn;
@@ -940,6 +1074,22 @@ struct TranPhases2 {
   // circuits the resident geometry is sized for they are all empty, yet each one costs a bound fetch, address
   // arithmetic and a branch: ~1200 cycles per step in Z alone before they were put behind one test.
   uint32_t brem, zrem;
+  // With the phase table, P and R above are LOCAL structs that hold only the fields the always-executed code of B, Z and
+  // the parameter prefetch reads (spicey_pt_args), and Pg / Rg point to the complete argument structs in global memory:
+  // the beyond-resident-capacity loops and the diagnostics, which read many more fields on few circuits, take a fresh copy
+  // from there inside their own branch (SPICEY_COLD_ARGS).  Null: P and R are complete.
+  const SpiceyProg *Pg = nullptr;
+  const SpiceyRun *Rg = nullptr;
+#if defined(__HIP_DEVICE_COMPILE__)
+#define SPICEY_COLD_STRUCT(whole, here) ((whole) ? spicey_fresh(*(whole)) : (here))
+#else
+#define SPICEY_COLD_STRUCT(whole, here) ((whole) ? *(whole) : (here))
+#endif
+#define SPICEY_COLD_ARGS                                             \
+  const SpiceyProg &P = SPICEY_COLD_STRUCT(this->Pg, this->P); \
+  const SpiceyRun &R = SPICEY_COLD_STRUCT(this->Rg, this->R);  \
+  (void)P;                                                           \
+  (void)R
   typedef ResRegs<K, RMAX, NSV, NEL> Regs;
   // the diagnostics of SpiceyOptions.diagnostics are compiled into every geometry but the two-workgroups-per-CU one (NSV = 6:
   // 128 VGPRs and nothing to spare — with them that kernel spills, which the build refuses); the host keeps a handle with
@@ -1079,6 +1229,15 @@ struct TranPhases2 {
     rr.cursor = 0;  // a new solve walks the resident slots from the start
     if (!reuse) stamp_matrix(tid, rr);  // a linear circuit keeps the factors of step 0 in W
     rhs_rows(tid, rr);
+  }
+  // the whole of phase B: the next step's source values ride on it (a long phase with few live registers): fetched first,
+  // parked in LDS last; Z moves them into place
+  SPICEY_HD void b_phase(int tid, int64_t step, Regs &rr, bool reuse) const {
+    double sn = K == 1 ? z_src_fetch(tid, step, (size_t)c.inst[0]) : 0.0;
+    SPICEY_SCHED_FENCE;
+    b_stamp(tid, rr, reuse);
+    SPICEY_SCHED_FENCE;
+    if (K == 1) z_src_park(tid, sn);
   }
   // ---- batched forms of the beyond-resident-capacity loops (HYB builds, K = 1) -------------------------------------------
   // Hybrid workspace: circuits of several thousand unknowns on 512 threads — most entries lie beyond the resident slots, and
@@ -1236,6 +1395,8 @@ struct TranPhases2 {
         for (int k = 0; k < K; k++) put_entry((uint32_t)e, k, rr.sv[j][k]);
     }
     SPICEY_MARK(c, 8);
+    if (!(brem & (16u | 1u | 2u))) return;
+    SPICEY_COLD_ARGS;
     if (brem & 16u)
     SPICEY_NOUNROLL
     for (int e = tid + Regs::NDD * T; e < P.nDynEnt; e += T) {  // dynamic entries beyond the descriptor slots
@@ -1306,9 +1467,10 @@ struct TranPhases2 {
       if (d1 != 0xFFFFFFFFu) rhs_row((uint32_t)(tid + j * T), d0, d1);
     }
     SPICEY_MARK(c, 10);
-    if (HYB) {
-      if (brem & 4u) rhs_rest_batched(tid);
-    } else if (brem & 4u)
+    if (HYB && (brem & 4u)) rhs_rest_batched(tid);
+    if (!(brem & (HYB ? 8u : 12u))) return;
+    SPICEY_COLD_ARGS;
+    if (!HYB && (brem & 4u))
     SPICEY_NOUNROLL
     for (int r = tid + NEL * T; r < P.n; r += T) {
       const uint32_t d0 = P.row_desc[(size_t)r * 2], d1 = P.row_desc[(size_t)r * 2 + 1];
@@ -1368,6 +1530,7 @@ struct TranPhases2 {
   // diagnostics pass of Z (SpiceyRun::lin_vd set; its own loop so that the production path carries no extra state):
   // |vd(x) - vd_lin| of this thread's diodes, and the new linearisation point
   SPICEY_HD double z_lin_err(int tid, int k, size_t in) const {
+    SPICEY_COLD_ARGS;
     double lerr = 0.0;
     SPICEY_NOUNROLL
     for (int i = tid; i < P.nD; i += T) {
@@ -1486,6 +1649,7 @@ struct TranPhases2 {
       }
       SPICEY_MARK(c, 3);
       if ((SPICEY_EXP & 32) || !zrem) continue;
+      SPICEY_COLD_ARGS;
       if (HYB) {
         // (hybrid workspace: four items of every kind at a time — indices and parameters of all four in flight before the
         // first terminal voltage is read; the same arithmetic per item as the loops below)
@@ -1700,12 +1864,84 @@ __device__ __forceinline__ void spicey_pcr_all(const WgCtx<K> &c, double *buf, c
 }
 #endif
 
+// ---- the phase table (see the top of this file) ---------------------------------------------------------------------------
+// Whether a run keeps one is decided on the host.  The GPU kernels are built twice, with the table (PT = 1) and with the
+// scalar loads (PT = 0) — one kernel holding both paths of B and Z does not fit the 128 registers of the two-workgroups-
+// per-CU build —, and spicey_launch_tran_v2 picks the build: spicey_pt_fits and no SPICEY_NO_PHASE_TABLE in the
+// environment of spicey_create.  PT = -1 (the test emulator, which instantiates the interpreter itself) decides per run:
+SPICEY_HD bool spicey_pt_runtime_choice(const SpiceyProg &P, const SpiceyResident &Q) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  (void)P; (void)Q;
+  return false;
+#else
+  return spicey_pt_fits(P.pcr_n, P.pcr_level, Q.tail_n) && getenv("SPICEY_NO_PHASE_TABLE") == nullptr;
+#endif
+}
+// Written once, in the prologue.  Every word of the run-wide block is a 32-bit piece of one field of SpiceyProg or
+// SpiceyRun: lane l copies word l from where the struct lives (a vector load: no scalar registers, which the prologue
+// phase that fills the resident registers has none to spare of either).
+struct SpiceyPtWord {
+  uint16_t from_run;  // 0: SpiceyProg, 1: SpiceyRun
+  uint16_t off;       // byte offset of the word
+};
+#define SPICEY_PT_P32(f) {0, (uint16_t)offsetof(SpiceyProg, f)}
+#define SPICEY_PT_P64(f) {0, (uint16_t)offsetof(SpiceyProg, f)}, {0, (uint16_t)(offsetof(SpiceyProg, f) + 4)}
+#define SPICEY_PT_R64(f) {1, (uint16_t)offsetof(SpiceyRun, f)}, {1, (uint16_t)(offsetof(SpiceyRun, f) + 4)}
+template <int K>
+SPICEY_HD void spicey_pt_build(const SpiceyProg &P, const SpiceyResident &Q, const SpiceyRun &R, const WgCtx<K> &c, int tid, int T) {
+  static constexpr SpiceyPtWord words[SPICEY_PT_USED] = {
+      SPICEY_PT_P32(xoff), SPICEY_PT_P32(nRestore), SPICEY_PT_P32(nDynEnt), SPICEY_PT_P32(nGstat), SPICEY_PT_P32(nR), SPICEY_PT_P32(nC),
+      SPICEY_PT_P32(nL), SPICEY_PT_P32(nV), SPICEY_PT_P64(ovf16), SPICEY_PT_P64(rec16), SPICEY_PT_P64(fus16), SPICEY_PT_P32(nS),
+      SPICEY_PT_P32(nD), SPICEY_PT_P32(nOut), SPICEY_PT_P32(nCur), SPICEY_PT_R64(steps), SPICEY_PT_R64(src), SPICEY_PT_R64(src_stride),
+      SPICEY_PT_R64(out_v), SPICEY_PT_R64(out_i), SPICEY_PT_R64(gstat), SPICEY_PT_R64(dpar), SPICEY_PT_R64(D_is), SPICEY_PT_R64(C_vprev),
+      SPICEY_PT_R64(D_vdprev), SPICEY_PT_R64(iters), SPICEY_PT_R64(lin_vd), SPICEY_PT_R64(lin_err)};
+  uint32_t *pt = c.tail + spicey_pt_base_words(P.pcr_n);
+  if (tid < SPICEY_PT_USED) {
+    const SpiceyPtWord w = words[tid];
+    const char *src = (w.from_run ? (const char *)&R : (const char *)&P) + w.off;
+    uint32_t v;
+    __builtin_memcpy(&v, src, 4);
+    pt[tid] = v;
+  }
+  const int L = P.pcr_level, kb = 2 * P.nLevels - L;  // rows: factor phases [0, L), then backward phases [kb, kb + L)
+  for (int i = tid; i < 2 * L * 8; i += T) {
+    const int r = i >> 3, p = r < L ? r : kb + (r - L);
+    pt[SPICEY_PT_RUN + i] = Q.st_desc[(size_t)p * 8 + (i & 7)];
+  }
+}
+// The fields that the always-executed code of B, Z and Z's parameter prefetch reads (TranPhases2, K = 1, LDS workspace), from
+// the table into two LOCAL structs; every other field stays zero and is never looked at there (TranPhases2::Pg).  What a
+// phase does not use of this is dead code.
+SPICEY_HD void spicey_pt_args(const uint32_t *pt, int tid, SpiceyProg &P, SpiceyRun &R) {
+  const SpiceyPtLanes a = SpiceyPtLanes::run_block(pt, tid);  // (called at a phase head: the whole wave is here)
+  P.xoff = (int32_t)a.u32(SPICEY_PT_XOFF); P.nRestore = (int32_t)a.u32(SPICEY_PT_NRESTORE);
+  P.nDynEnt = (int32_t)a.u32(SPICEY_PT_NDYNENT); P.nGstat = (int32_t)a.u32(SPICEY_PT_NGSTAT);
+  P.nR = (int32_t)a.u32(SPICEY_PT_NR); P.nC = (int32_t)a.u32(SPICEY_PT_NC); P.nL = (int32_t)a.u32(SPICEY_PT_NL);
+  P.nV = (int32_t)a.u32(SPICEY_PT_NV); P.nS = (int32_t)a.u32(SPICEY_PT_NS); P.nD = (int32_t)a.u32(SPICEY_PT_ND);
+  P.nOut = (int32_t)a.u32(SPICEY_PT_NOUT); P.nCur = (int32_t)a.u32(SPICEY_PT_NCUR);
+  R.steps = (int64_t)a.u64(SPICEY_PT_STEPS);
+  R.src = a.template ptr<const double>(SPICEY_PT_SRC);
+  R.src_stride = (int64_t)a.u64(SPICEY_PT_SRC_STRIDE);
+  R.out_v = a.template ptr<double>(SPICEY_PT_OUT_V);
+  R.out_i = a.template ptr<double>(SPICEY_PT_OUT_I);
+  R.gstat = a.template ptr<double>(SPICEY_PT_GSTAT);
+  R.dpar = a.template ptr<double>(SPICEY_PT_DPAR);
+  R.D_is = a.template ptr<const double>(SPICEY_PT_D_IS);
+  R.C_vprev = a.template ptr<double>(SPICEY_PT_C_VPREV);
+  R.D_vdprev = a.template ptr<double>(SPICEY_PT_D_VDPREV);
+  R.iters = a.template ptr<int32_t>(SPICEY_PT_ITERS);
+  R.lin_vd = a.template ptr<double>(SPICEY_PT_LIN_VD);
+  R.lin_err = a.template ptr<unsigned long long>(SPICEY_PT_LIN_ERR);
+}
+
 // The three argument structs hold ~110 pointers: kept in SGPRs across the time loop they overflow the 102 scalar registers
 // of a wave and the compiler parks them in VGPR lanes (round 1: 274 spilled SGPRs, 1 209 v_readlane in the kernel — 13 % of
-// its instructions).  Every phase therefore takes the structs through `ex.fresh()`: on the GPU they live in global memory and
-// `fresh` makes their address opaque for this phase, so the fields a phase needs are fetched by scalar loads inside it
-// (scalar cache) and are dead at its barrier; only a handful of loop-control scalars stay live around the loop.
-template <int K, int RMAX, int NSV, int NEL, bool HYB = false, class Exec>
+// its instructions).  No phase of the time loop therefore sees the structs themselves.  Where the run keeps a phase table
+// (top of this file) a phase reads the words it needs from LDS; otherwise, and in the rarely taken branches, it takes the
+// structs through `ex.fresh()` / spicey_fresh(): on the GPU they live in global memory and `fresh` makes their address
+// opaque for this phase, so the fields it needs are fetched by scalar loads inside it (scalar cache).  Either way the
+// values are dead at the phase's barrier; only a handful of loop-control scalars stay live around the loop.
+template <int K, int RMAX, int NSV, int NEL, bool HYB = false, int PT = -1, class Exec>
 SPICEY_HD void spicey_tran_run_v2(Exec &ex, const SpiceyProg &P, const SpiceyResident &Q, const SpiceyRun &R, WgCtx<K> &c, int wg) {
   const int T = ex.threads();
   typedef TranPhases2<K, RMAX, NSV, NEL, HYB> Ph2;
@@ -1716,6 +1952,10 @@ SPICEY_HD void spicey_tran_run_v2(Exec &ex, const SpiceyProg &P, const SpiceyRes
     brem = p2.brem; zrem = p2.zrem;
   }
   typedef ResRegs<K, RMAX, NSV, NEL> Regs;
+  // the phase table: tridiagonal-top builds whose rows fit behind the top's index table (wave-uniform, fixed for the run)
+  static_assert(PT <= 0 || K == 1, "the phase table is built for one instance per workgroup");
+  const bool pt_run = PT >= 0 ? PT == 1 : (K == 1 && spicey_pt_runtime_choice(P, Q));
+  if (pt_run) ex.phase(SPICEY_PH_PRO, [&](int tid) { spicey_pt_build<K>(P, Q, R, c, tid, T); });  // (the structs where they live: see there)
   ex.phase(SPICEY_PH_PRO, [&](int tid) {
     const SpiceyProg Pf = ex.fresh(P); const SpiceyResident Qf = ex.fresh(Q); const SpiceyRun Rf = ex.fresh(R);
     TranPhases<K> ph{Pf, Rf, c, T};
@@ -1773,6 +2013,7 @@ SPICEY_HD void spicey_tran_run_v2(Exec &ex, const SpiceyProg &P, const SpiceyRes
   top_pack |= (P.nD == 0 && nS == 0 && P.nDynEnt == 0 && !R.no_reuse) ? 1 << 17 : 0;  // bit 17 = linear
   top_pack |= (Ph2::DIAG && R.skip_risk != nullptr) ? 1 << 18 : 0;  // bit 18 = diagnostics: look at the stamped matrix after B (spicey_skip_risk)
   top_pack |= (K == 1 && pcr_n > 0 && Q.k_merge == k_begin && k_begin < 2 * nL - 1) ? 1 << 19 : 0;  // bit 19 = the first backward phase runs in the top's wave
+  top_pack |= (PT < 0 && pt_run) ? 1 << 20 : 0;  // bit 20 = the phases take their arguments from the phase table (where that is a run-time choice)
   top_pack = SPICEY_UNIFORM(top_pack);
   for (int64_t step = 0; step <= steps && code == 0; step++) {
     int iter = 0;
@@ -1781,17 +2022,23 @@ SPICEY_HD void spicey_tran_run_v2(Exec &ex, const SpiceyProg &P, const SpiceyRes
       SPICEY_OPAQUE_S(tp);
       const int pcr_n = tp & 0xff, pcr_S = (tp >> 8) & 0xff;
       const bool linear = (tp >> 17) & 1;
+      // (with a table u_end = pcr_level rows of factor phases come first, the backward phases from k_begin on follow)
+      const bool pt_on = PT >= 0 ? PT == 1 : ((tp >> 20) & 1) != 0;
+      const uint32_t *ptw = c.tail + spicey_pt_base_words(pcr_n);
+      const bool pt_bz = !HYB && pt_on;  // (hybrid builds: B and Z read many more fields; they keep the scalar loads)
       ex.phase(SPICEY_PH_B, [&](int tid) {
-        const SpiceyProg Pf = ex.fresh(P);
-        const SpiceyRun Rf = ex.fresh(R);
-        Ph2 p2{Pf, Rf, c, T, brem, zrem};
-        // the next step's source values ride on B (a long phase with few live registers): fetched first, parked in
-        // LDS last; Z moves them into place
-        double sn = K == 1 ? p2.z_src_fetch(tid, step, (size_t)c.inst[0]) : 0.0;
-        SPICEY_SCHED_FENCE;
-        p2.b_stamp(tid, ex.template regs<Regs>(tid), linear && step > 0);
-        SPICEY_SCHED_FENCE;
-        if (K == 1) p2.z_src_park(tid, sn);
+        if (pt_bz) {
+          SpiceyProg Pt{};
+          SpiceyRun Rt{};
+          spicey_pt_args(ptw, tid, Pt, Rt);
+          Ph2 p2{Pt, Rt, c, T, brem, zrem, &P, &R};
+          p2.b_phase(tid, step, ex.template regs<Regs>(tid), linear && step > 0);
+        } else {
+          const SpiceyProg Pf = ex.fresh(P);
+          const SpiceyRun Rf = ex.fresh(R);
+          Ph2 p2{Pf, Rf, c, T, brem, zrem};
+          p2.b_phase(tid, step, ex.template regs<Regs>(tid), linear && step > 0);
+        }
       });
       if (Ph2::DIAG && ((tp >> 18) & 1) && !(linear && step > 0))
         ex.phase(SPICEY_PH_S, [&](int tid) {
@@ -1807,16 +2054,12 @@ SPICEY_HD void spicey_tran_run_v2(Exec &ex, const SpiceyProg &P, const SpiceyRes
           // hybrid workspace: phase 0 eliminates the leaves, whose own entries are read from the global array (one L2 round
           // trip for the whole level; every target is in LDS)
           ex.phase(SPICEY_PH_U0, [&](int tid) {
-            const SpiceyProg Pf = ex.fresh(P);
-            const SpiceyResident Qf = ex.fresh(Q);
-            spicey_uk_phase<K, RMAX, NSV, NEL, false, HYB>(Pf, Qf, c, ex.template regs<Regs>(tid), tid, T, 0, ((smask >> 0) & 1) != 0, linear && step > 0);
+            spicey_uk_phase<K, RMAX, NSV, NEL, false, HYB>(P, Q, SpiceyPt{ptw, pt_on, 0}, c, ex.template regs<Regs>(tid), tid, T, 0, ((smask >> 0) & 1) != 0, linear && step > 0);
           });
           continue;
         }
         ex.phase(SPICEY_PH_U0 + (p < 30 ? p : 30), [&](int tid) {
-          const SpiceyProg Pf = ex.fresh(P);
-          const SpiceyResident Qf = ex.fresh(Q);
-          spicey_uk_phase<K, RMAX, NSV, NEL, false>(Pf, Qf, c, ex.template regs<Regs>(tid), tid, T, p, p < 64 ? ((smask >> p) & 1) != 0 : true, linear && step > 0);
+          spicey_uk_phase<K, RMAX, NSV, NEL, false>(P, Q, SpiceyPt{ptw, pt_on, p}, c, ex.template regs<Regs>(tid), tid, T, p, p < 64 ? ((smask >> p) & 1) != 0 : true, linear && step > 0);
         });
       }
       const int kmerge = (tp >> 19) & 1;
@@ -1824,9 +2067,7 @@ SPICEY_HD void spicey_tran_run_v2(Exec &ex, const SpiceyProg &P, const SpiceyRes
         // (kmerge: wave 0 goes on with the first backward phase below the top — its records are resident in this wave's
         // slots, its rows need unknowns of the top only, and the LDS operations of one wave execute in order)
         auto merged_k = [&](int lane) {
-          const SpiceyProg Pf = ex.fresh(P);
-          const SpiceyResident Qf = ex.fresh(Q);
-          spicey_uk_phase<K, RMAX, NSV, NEL, true>(Pf, Qf, c, ex.template regs<Regs>(lane), lane, T, k_begin, false);
+          spicey_uk_phase<K, RMAX, NSV, NEL, true>(P, Q, SpiceyPt{ptw, pt_on, u_end}, c, ex.template regs<Regs>(lane), lane, T, k_begin, false);
         };
 #if defined(__HIP_DEVICE_COMPILE__)
         if (pcr_S >= 1 && pcr_S <= 6) {
@@ -1852,17 +2093,15 @@ SPICEY_HD void spicey_tran_run_v2(Exec &ex, const SpiceyProg &P, const SpiceyRes
                         r[0] = q[0]; r[1] = q[1]; r[2] = q[2]; r[3] = q[3];
                       },
                       [&](int, int lvl, const uint32_t *r) {
-                        const SpiceyProg Pf = ex.fresh(P);
-                        if (u_end + lvl < nL) spicey_exec_rec16<K, false>(c, Pf.ovf16, r[0], r[1], r[2], r[3], (linear && step > 0) ? (uint32_t)Pf.xoff : 0u);
-                        else spicey_exec_rec16<K, true>(c, Pf.ovf16, r[0], r[1], r[2], r[3]);
+                        auto ovf = [&]() -> const uint16_t * { return spicey_fresh(P).ovf16; };
+                        if (u_end + lvl < nL) spicey_exec_rec16<K, false>(c, ovf, r[0], r[1], r[2], r[3], (linear && step > 0) ? (uint32_t)spicey_fresh(P).xoff : 0u);
+                        else spicey_exec_rec16<K, true>(c, ovf, r[0], r[1], r[2], r[3]);
                       });
       }
       for (int p = k_begin + kmerge; p < 2 * nL - 1; p++) {
         const int l = 2 * nL - 1 - p;
         ex.phase(SPICEY_PH_K0 + (l < 31 ? l : 31), [&](int tid) {
-          const SpiceyProg Pf = ex.fresh(P);
-          const SpiceyResident Qf = ex.fresh(Q);
-          spicey_uk_phase<K, RMAX, NSV, NEL, true>(Pf, Qf, c, ex.template regs<Regs>(tid), tid, T, p, p < 64 ? ((smask >> p) & 1) != 0 : true);
+          spicey_uk_phase<K, RMAX, NSV, NEL, true>(P, Q, SpiceyPt{ptw, pt_on, p - k_begin + u_end}, c, ex.template regs<Regs>(tid), tid, T, p, p < 64 ? ((smask >> p) & 1) != 0 : true);
         });
       }
       // the last backward phase (level 0) is peeled: it also issues Z's parameter fetch.  (Every path through the
@@ -1870,11 +2109,22 @@ SPICEY_HD void spicey_tran_run_v2(Exec &ex, const SpiceyProg &P, const SpiceyRes
       if (k_begin < 2 * nL) {
         const int p = 2 * nL - 1;
         ex.phase(SPICEY_PH_K0, [&](int tid) {
-          const SpiceyProg Pf = ex.fresh(P);
-          const SpiceyResident Qf = ex.fresh(Q);
-          spicey_uk_phase<K, RMAX, NSV, NEL, true, HYB>(Pf, Qf, c, ex.template regs<Regs>(tid), tid, T, p, p < 64 ? ((smask >> p) & 1) != 0 : true);  // (level 0: the leaves)
+          spicey_uk_phase<K, RMAX, NSV, NEL, true, HYB>(P, Q, SpiceyPt{ptw, pt_on, p - k_begin + u_end}, c, ex.template regs<Regs>(tid), tid, T, p, p < 64 ? ((smask >> p) & 1) != 0 : true);  // (level 0: the leaves)
           SPICEY_SCHED_FENCE;  // after the tasks, not among them: their registers are free by now
-          if (K == 1) { const SpiceyRun Rf = ex.fresh(R); Ph2 p2{Pf, Rf, c, T, brem, zrem}; p2.z_prefetch(tid, step, 0, ex.template regs<Regs>(tid)); }
+          if (K == 1) {
+            if (pt_bz) {
+              SpiceyProg Pt{};
+              SpiceyRun Rt{};
+              spicey_pt_args(ptw, tid, Pt, Rt);
+              Ph2 p2{Pt, Rt, c, T, brem, zrem, &P, &R};
+              p2.z_prefetch(tid, step, 0, ex.template regs<Regs>(tid));
+            } else {
+              const SpiceyProg Pf = ex.fresh(P);
+              const SpiceyRun Rf = ex.fresh(R);
+              Ph2 p2{Pf, Rf, c, T, brem, zrem};
+              p2.z_prefetch(tid, step, 0, ex.template regs<Regs>(tid));
+            }
+          }
         });
       } else if (K == 1) {
         Ph2 p2{P, R, c, T, brem, zrem};
@@ -1895,13 +2145,24 @@ SPICEY_HD void spicey_tran_run_v2(Exec &ex, const SpiceyProg &P, const SpiceyRes
       solves += (unsigned long long)(iter + 1) * (unsigned long long)nvalid;
     }
     ex.phase(SPICEY_PH_Z, [&](int tid) {
-      const SpiceyRun Rf = ex.fresh(R);
-      const SpiceyProg Pf = ex.fresh(P);
-      Ph2 p2{Pf, Rf, c, T, brem, zrem};
-      if (tid == 0 && Rf.iters)
-        for (int k = 0; k < K; k++)
-          if (c.valid[k]) Rf.iters[(size_t)c.inst[k] * (size_t)(steps + 1) + (size_t)step] = iter + 1;
-      p2.z_record(tid, step, ex.template regs<Regs>(tid), ((top_pack >> 16) & 1) != 0);
+      if (!HYB && (PT >= 0 ? PT == 1 : ((top_pack >> 20) & 1) != 0)) {
+        SpiceyProg Pt{};
+        SpiceyRun Rt{};
+        spicey_pt_args(c.tail + spicey_pt_base_words(top_pack & 0xff), tid, Pt, Rt);
+        Ph2 p2{Pt, Rt, c, T, brem, zrem, &P, &R};
+        if (tid == 0 && Rt.iters)
+          for (int k = 0; k < K; k++)
+            if (c.valid[k]) Rt.iters[(size_t)c.inst[k] * (size_t)(steps + 1) + (size_t)step] = iter + 1;
+        p2.z_record(tid, step, ex.template regs<Regs>(tid), ((top_pack >> 16) & 1) != 0);
+      } else {
+        const SpiceyRun Rf = ex.fresh(R);
+        const SpiceyProg Pf = ex.fresh(P);
+        Ph2 p2{Pf, Rf, c, T, brem, zrem};
+        if (tid == 0 && Rf.iters)
+          for (int k = 0; k < K; k++)
+            if (c.valid[k]) Rf.iters[(size_t)c.inst[k] * (size_t)(steps + 1) + (size_t)step] = iter + 1;
+        p2.z_record(tid, step, ex.template regs<Regs>(tid), ((top_pack >> 16) & 1) != 0);
+      }
     });
   }
   ex.phase(SPICEY_PH_PRO, [&](int tid) {
