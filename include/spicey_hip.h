@@ -306,6 +306,56 @@ double spicey_multi_last_kernel_ms(SpiceyMulti *m);     /* the slowest shard's k
 const char *spicey_multi_last_error(SpiceyMulti *m);    /* NULL handle -> the calling thread's last failed create */
 void spicey_destroy_multi(SpiceyMulti *m);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Waveform measurements on the device (what SPICE users know as .meas): a reduction pass of its own over the step-major
+ * waveform buffers a transient run wrote, stream-ordered behind it; only [n_inst][n_req][8] doubles leave the device.
+ * One request = one signal, one window of steps, one kind:
+ *   kind       0 = stats, 1 = crossings
+ *   signal     0 = column of out_v, 1 = column of out_i
+ *   col        the measured column; col_ref = -1: none, else the signal is x[col] - x[col_ref] of the same array (one
+ *              rounded subtraction)
+ *   step_from, step_to   inclusive window; step_to = -1: the last point
+ *   level, dir crossings: the threshold, and +1 = rises, -1 = falls, 0 = both
+ * Results, 8 doubles per (instance, request):
+ *   stats      {min, max, step_min, step_max, sum, sumsq, first, last}.  step_min / step_max: the step of the FIRST
+ *              occurrence of the extreme, as a double.  The extremes use the plain comparisons x < m and x > m: a NaN sample
+ *              is ignored by them and propagates into the sums.
+ *   crossings  {count, t_first, t_last, 0, 0, 0, 0, 0} over the intervals (k, k + 1) with both steps inside the window; rise:
+ *              x_k < level && x_k+1 >= level, fall: x_k > level && x_k+1 <= level; the crossing time is
+ *              ((double)k + (level - x_k) / (x_k+1 - x_k)) * dt; t_first = t_last = -1.0 when count = 0.
+ * Every field is a function of the window's samples, dt and the request only (the summation order is fixed: chunks of 256
+ * steps counted from step_from, sequential inside a chunk, chunk partials added in ascending order): it does not depend on
+ * n_inst, on the other requests of the list or on the launch.  No FMA contraction. */
+typedef struct SpiceyMeasReq {
+  int32_t kind, signal, col, col_ref;
+  int64_t step_from, step_to;
+  double level;
+  int32_t dir, reserved; /* reserved: 0 */
+} SpiceyMeasReq;
+
+/* Bytes of device workspace spicey_measure_device needs (request table + chunk partials); -1 for counts <= 0. */
+int64_t spicey_measure_workspace_bytes(int32_t n_inst, int64_t n_points, int32_t n_req);
+/* The reduction alone, on any DEVICE buffers d_v [n_inst][n_points][n_v] and d_i [n_inst][n_points][n_i] (or NULL):
+ * needs no handle.  reqs is a HOST array; d_meas [n_inst][n_req][8] and d_work (work_bytes >=
+ * spicey_measure_workspace_bytes) are DEVICE buffers.  Enqueued on `stream` (a hipStream_t, NULL = default stream)
+ * without synchronising; the request table travels into the head of the workspace.  SPICEY_ERR_BAD_DESC, with a text in
+ * spicey_last_error(NULL) and nothing launched, for: an unknown kind, signal or dir; a column out of range; signal = 1
+ * with d_i == NULL; a window outside [0, n_points) or with step_from > step_to; a workspace that is too small;
+ * n_req <= 0. */
+int32_t spicey_measure_device(int32_t device, int32_t n_inst, int64_t n_points, double dt, const double *d_v, int32_t n_v,
+                              const double *d_i, int32_t n_i, const SpiceyMeasReq *reqs, int32_t n_req, double *d_meas,
+                              void *d_work, int64_t work_bytes, void *stream);
+/* One transient run (as spicey_run_src) whose waveforms stay on the device: out_v (and out_i only if a request has
+ * signal = 1) are allocated there, reduced by spicey_measure_device on the handle's stream, and only
+ * meas [n_inst][n_req][8] and iters [n_inst][steps+1] (or NULL) come back — also after SPICEY_ERR_SINGULAR, where the
+ * rows of the instances whose spicey_last_inst_status entry is nonzero are undefined.  Columns are those of the handle
+ * (SpiceyInfo.n_out, n_cur); n_points = steps + 1.  State, solve count, skip risk and kernel ms are queried as after
+ * spicey_run. */
+int32_t spicey_run_measure(SpiceyHandle *h, int64_t steps, double dt, const double *src_table, int32_t src_per_inst,
+                           const SpiceyMeasReq *reqs, int32_t n_req, double *meas, int32_t *iters);
+/* Duration in ms of the last spicey_run_measure's reduction (both of its kernels), measured with HIP events. */
+double spicey_last_measure_ms(SpiceyHandle *h);
+
 /* Library build info: "spicey_hip <abi> gfx950 …" */
 const char *spicey_version(void);
 

@@ -55,6 +55,18 @@ class SpiceyInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class SpiceyMeasReq(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("signal", C.c_int32), ("col", C.c_int32), ("col_ref", C.c_int32),
+                ("step_from", C.c_int64), ("step_to", C.c_int64), ("level", C.c_double), ("dir", C.c_int32), ("reserved", C.c_int32)]
+
+
+# the same record as a numpy dtype: a request list is one array of these (spicey_amd/measure.py builds them)
+MEAS_REQ_DTYPE = np.dtype([("kind", "<i4"), ("signal", "<i4"), ("col", "<i4"), ("col_ref", "<i4"), ("step_from", "<i8"), ("step_to", "<i8"),
+                           ("level", "<f8"), ("dir", "<i4"), ("reserved", "<i4")])
+assert MEAS_REQ_DTYPE.itemsize == C.sizeof(SpiceyMeasReq) == 48
+MEAS_STATS, MEAS_CROSS = 0, 1
+
+
 def _i32(a) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.int32)
 

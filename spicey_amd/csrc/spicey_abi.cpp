@@ -19,6 +19,8 @@
 #include "exact_plan.h"
 #include "kernels.h"
 #include "launch_plan.h"
+#include "measure.h"
+#include "measure_exec.h"
 #include "symbolic.h"
 #include "fronts_exec_consts.h"
 
@@ -89,6 +91,8 @@ struct SpiceyHandle {
   hipStream_t stream = nullptr;  // owned stream for spicey_run
   hipStream_t last_stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  hipEvent_t mev0 = nullptr, mev1 = nullptr;  // around the reduction of spicey_run_measure (created on first use)
+  double last_measure_ms = 0.0;
   bool pending = false;
   int64_t last_solves = 0;
   double last_ms = 0.0;
@@ -204,6 +208,8 @@ extern "C" void spicey_destroy(SpiceyHandle *h) {
   }
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
+  if (h->mev0) (void)hipEventDestroy(h->mev0);
+  if (h->mev1) (void)hipEventDestroy(h->mev1);
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;  // (and with it every device buffer)
 }
@@ -725,6 +731,102 @@ extern "C" int32_t spicey_debug_front_ticks(SpiceyHandle *h, int32_t grp, uint64
   }
   return nf;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Waveform measurements (include/spicey_hip.h): the reduction pass of measure.hip behind a transient run.
+
+extern "C" int64_t spicey_measure_workspace_bytes(int32_t n_inst, int64_t n_points, int32_t n_req) {
+  return spicey_meas_workspace_bytes(n_inst, n_points, n_req);
+}
+
+// every refusal of a measurement call: counts, buffers, the request list (-> the kernels' sorted table), the workspace size
+static int32_t measure_plan(int32_t n_inst, int64_t n_points, bool have_v, int32_t n_v, bool have_i, int32_t n_i, const SpiceyMeasReq *reqs, int32_t n_req,
+                            bool have_out, int64_t work_bytes, std::vector<SpiceyMeasDevReq> &table, std::string &err) {
+  if (n_inst <= 0 || n_v < 0 || n_i < 0 || !have_out) { err = "measure: bad arguments (n_inst >= 1, result and workspace buffers)"; return SPICEY_ERR_BAD_DESC; }
+  if (!spicey_meas_plan(reqs, n_req, n_points, have_v ? n_v : 0, n_i, have_i, table, err)) return SPICEY_ERR_BAD_DESC;
+  const int64_t need = spicey_meas_workspace_bytes(n_inst, n_points, n_req);
+  if (work_bytes < need) {
+    char buf[160];
+    snprintf(buf, sizeof(buf), "measure: workspace of %lld bytes is too small, %lld needed (spicey_measure_workspace_bytes)", (long long)work_bytes, (long long)need);
+    err = buf;
+    return SPICEY_ERR_BAD_DESC;
+  }
+  return SPICEY_OK;
+}
+
+extern "C" int32_t spicey_measure_device(int32_t device, int32_t n_inst, int64_t n_points, double dt, const double *d_v, int32_t n_v, const double *d_i,
+                                         int32_t n_i, const SpiceyMeasReq *reqs, int32_t n_req, double *d_meas, void *d_work, int64_t work_bytes,
+                                         void *stream) {
+  // (the call is judged before the device is touched: a refusal launches nothing)
+  std::vector<SpiceyMeasDevReq> table;
+  if (const int32_t rc = measure_plan(n_inst, n_points, d_v != nullptr, n_v, d_i != nullptr, n_i, reqs, n_req, d_meas && d_work, work_bytes, table, g_err); rc != SPICEY_OK)
+    return rc;
+  int ncu = 0;
+  if (const int32_t rc = open_device(device, &ncu, g_err); rc != SPICEY_OK) return rc;
+  const hipError_t e = spicey_launch_measure(device, n_inst, n_points, dt, d_v, n_v, d_i, n_i, table.data(), n_req, d_meas, d_work, (hipStream_t)stream);
+  if (e != hipSuccess) { g_err = std::string("spicey_launch_measure: ") + hipGetErrorString(e); return SPICEY_ERR_HIP; }
+  return SPICEY_OK;
+}
+
+extern "C" int32_t spicey_run_measure(SpiceyHandle *h, int64_t steps, double dt, const double *src_table, int32_t src_per_inst, const SpiceyMeasReq *reqs,
+                                      int32_t n_req, double *meas, int32_t *iters) {
+  if (!h) return SPICEY_ERR_BAD_DESC;
+  forget_last_run(h);
+  if (steps < 0 || !meas || (h->hp.hdr.nV > 0 && !src_table)) { h->err = "bad run arguments"; return SPICEY_ERR_BAD_DESC; }
+  if (src_per_inst != 0 && src_per_inst != 1) { h->err = "src_per_inst must be 0 (one shared table) or 1 (one table per instance)"; return SPICEY_ERR_BAD_DESC; }
+  const SpiceyProg &P = h->hp.hdr;
+  const size_t np = (size_t)steps + 1, ni = (size_t)h->plan.n_inst, ntab = src_per_inst ? ni : 1;
+  // (a refused request list runs nothing; the buffers are this call's own)
+  const int64_t work_bytes = spicey_meas_workspace_bytes((int32_t)ni, (int64_t)np, n_req);
+  std::vector<SpiceyMeasDevReq> table;
+  if (const int32_t rc = measure_plan((int32_t)ni, (int64_t)np, true, P.nOut, true, P.nCur, reqs, n_req, true, work_bytes, table, h->err); rc != SPICEY_OK) return rc;
+  bool need_i = false;
+  for (const SpiceyMeasDevReq &q : table) need_i = need_i || q.signal == 1;
+  if (h->hp.structurally_singular) {
+    h->err = "singular at inst 0 step 0 iter 0 (structurally singular matrix)";
+    h->last_structural = true;
+    return SPICEY_ERR_SINGULAR;
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  Roctx range_run("spicey_run_measure");
+  if (!h->mev0) HIPCHK(h, hipEventCreate(&h->mev0));
+  if (!h->mev1) HIPCHK(h, hipEventCreate(&h->mev1));
+  DevBuf<double> d_src, d_v, d_i, d_meas;
+  DevBuf<int32_t> d_it;
+  DevBuf<uint8_t> d_work;
+  HIPCHK(h, d_src.alloc(std::max<size_t>(ntab * np * P.nV, 1)));
+  if (P.nV) HIPCHK(h, hipMemcpyAsync(d_src, src_table, ntab * np * P.nV * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, d_v.alloc(std::max<size_t>(ni * np * P.nOut, 1)));
+  if (need_i) HIPCHK(h, d_i.alloc(std::max<size_t>(ni * np * P.nCur, 1)));  // (no current request: the run records no currents)
+  if (iters) HIPCHK(h, d_it.alloc(ni * np));
+  HIPCHK(h, d_meas.alloc(ni * (size_t)n_req * 8));
+  HIPCHK(h, d_work.alloc((size_t)work_bytes));
+  h->last_measure_ms = 0.0;
+  int32_t rc = spicey_run_device_src(h, steps, dt, d_src, src_per_inst, d_v, d_i, d_it, h->stream);
+  if (rc != SPICEY_OK) return rc;
+  auto reduce = [&]() {
+    hipError_t e = hipEventRecord(h->mev0, h->stream);
+    if (e == hipSuccess) e = spicey_launch_measure(h->device, (int32_t)ni, (int64_t)np, dt, d_v, P.nOut, d_i, P.nCur, table.data(), n_req, d_meas, d_work, h->stream);
+    if (e == hipSuccess) e = hipEventRecord(h->mev1, h->stream);
+    return e;
+  };
+  const int retries = h->group_retries;
+  hipError_t e = reduce();
+  rc = spicey_sync(h);  // (the stream's end: the transient's status, with the reduction behind it; also before the buffers go)
+  // (group mode with group_retry: spicey_sync repeated the transient behind the reduction, so the reduction runs again)
+  if (e == hipSuccess && h->group_retries != retries && rc == SPICEY_OK && (e = reduce()) == hipSuccess) e = hipStreamSynchronize(h->stream);
+  if (e != hipSuccess) { h->err = std::string("spicey_launch_measure: ") + hipGetErrorString(e); return SPICEY_ERR_HIP; }
+  if (rc == SPICEY_OK || rc == SPICEY_ERR_SINGULAR) {
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, h->mev0, h->mev1) == hipSuccess) h->last_measure_ms = ms;
+    Roctx range_copy("spicey_run_measure:results");
+    HIPCHK(h, hipMemcpy(meas, d_meas, ni * (size_t)n_req * 8 * sizeof(double), hipMemcpyDeviceToHost));
+    if (iters) HIPCHK(h, hipMemcpy(iters, d_it, ni * np * sizeof(int32_t), hipMemcpyDeviceToHost));
+  }
+  return rc;
+}
+
+extern "C" double spicey_last_measure_ms(SpiceyHandle *h) { return h ? h->last_measure_ms : 0.0; }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Several devices behind one handle: instance shards, one SpiceyHandle per shard, host threads around the blocking runs.

@@ -25,7 +25,8 @@ EXPORTS = ["spicey_create", "spicey_run", "spicey_run_device", "spicey_run_src",
            "spicey_create_multi", "spicey_run_multi", "spicey_run_multi_src", "spicey_get_state_multi", "spicey_multi_get_shard", "spicey_multi_last_solve_count", "spicey_multi_group_retries", "spicey_multi_group_stale_polls",
            "spicey_multi_last_kernel_ms", "spicey_multi_last_error", "spicey_destroy_multi",
            "spicey_ac_create", "spicey_ac_run", "spicey_ac_get_info", "spicey_ac_last_kernel_ms", "spicey_ac_last_error", "spicey_ac_destroy",
-           "spicey_format_tran", "spicey_to_precision6"]
+           "spicey_format_tran", "spicey_to_precision6",
+           "spicey_measure_workspace_bytes", "spicey_measure_device", "spicey_run_measure", "spicey_last_measure_ms"]
 
 
 class SpiceyNativeError(RuntimeError):
@@ -128,6 +129,14 @@ def load():
     L.spicey_format_tran.argtypes = [C.c_int64, C.c_int32, f64p, f64p, C.c_int64, i32p, C.c_char_p, C.c_char_p, C.c_int64]
     L.spicey_to_precision6.restype = C.c_int32
     L.spicey_to_precision6.argtypes = [C.c_double, C.c_char_p]
+    L.spicey_measure_workspace_bytes.restype = C.c_int64
+    L.spicey_measure_workspace_bytes.argtypes = [C.c_int32, C.c_int64, C.c_int32]
+    L.spicey_measure_device.restype = C.c_int32
+    L.spicey_measure_device.argtypes = [C.c_int32, C.c_int32, C.c_int64, C.c_double, vp, C.c_int32, vp, C.c_int32, vp, C.c_int32, vp, vp, C.c_int64, vp]
+    L.spicey_run_measure.restype = C.c_int32
+    L.spicey_run_measure.argtypes = [vp, C.c_int64, C.c_double, f64p, C.c_int32, vp, C.c_int32, f64p, i32p]
+    L.spicey_last_measure_ms.restype = C.c_double
+    L.spicey_last_measure_ms.argtypes = [vp]
     _LIB = L
     return L
 
@@ -144,6 +153,33 @@ def _src_layout(src: np.ndarray, f: abi.FlatCircuit, steps: int) -> bool:
         return True
     raise ValueError(f"src_table must be [steps+1][nV] = {(steps + 1, f.nV)} or [n_inst][steps+1][nV] = {(f.n_inst, steps + 1, f.nV)}, "
                      f"got {src.shape}")
+
+
+def _reqs(reqs) -> np.ndarray:
+    """A request list as one contiguous array of SpiceyMeasReq records (abi.MEAS_REQ_DTYPE)."""
+    a = np.ascontiguousarray(reqs, dtype=abi.MEAS_REQ_DTYPE).reshape(-1)
+    return a
+
+
+def measure_workspace_bytes(n_inst: int, n_points: int, n_req: int) -> int:
+    return load().spicey_measure_workspace_bytes(n_inst, n_points, n_req)
+
+
+def measure_device(n_inst: int, n_points: int, dt: float, d_v: int, n_v: int, d_i: int, n_i: int, reqs, d_meas: int, d_work: int,
+                   work_bytes: int, device: int = 0, stream: int = 0) -> None:
+    """spicey_measure_device: the reduction alone on raw device pointers (e.g. torch tensors' data_ptr()): d_v
+    [n_inst][n_points][n_v], d_i [n_inst][n_points][n_i] or 0, d_meas [n_inst][n_req][8], d_work of `work_bytes` >=
+    measure_workspace_bytes(...).  Enqueued on `stream`, no synchronisation.  A refusal raises SpiceyNativeError whose
+    `status` is the library's code (abi.ERR_BAD_DESC for a bad request list)."""
+    L = load()
+    r = _reqs(reqs)
+    rc = L.spicey_measure_device(device, n_inst, n_points, dt, d_v or None, n_v, d_i or None, n_i, r.ctypes.data if len(r) else None, len(r),
+                                 d_meas or None, d_work or None, work_bytes, stream or None)
+    if rc != abi.OK:
+        msg = L.spicey_last_error(None)
+        err = SpiceyNativeError(f"spicey_measure_device failed ({rc}): {msg.decode() if msg else ''}")
+        err.status = rc
+        raise err
 
 
 class Handle:
@@ -217,6 +253,32 @@ class Handle:
                 if self.L.spicey_get_lin_err(self.h, _p(le, C.c_double)) != abi.OK:
                     raise SpiceyNativeError(f"spicey_get_lin_err failed: {self.error()}")
                 res["lin_err"] = le
+        return res
+
+    def run_measure(self, steps: int, dt: float, src: np.ndarray, reqs, want_iters: bool = True) -> dict:
+        """spicey_run_measure: the transient with its waveforms kept on the device and reduced there; only `meas`
+        [n_inst][n_req][8] (include/spicey_hip.h) and the iteration counts come back.  reqs: records of abi.MEAS_REQ_DTYPE
+        (spicey_amd/measure.py), columns as in this handle's out_v / out_i.  Like run() with per-instance tables, the rows of
+        the instances that finished are also there after a singular run (`inst_status`); `partial` says so."""
+        f = self.flat
+        src = np.ascontiguousarray(src, dtype=np.float64)
+        per_inst = _src_layout(src, f, steps)
+        r = _reqs(reqs)
+        meas = np.zeros((f.n_inst, len(r), 8))
+        iters = np.zeros((f.n_inst, steps + 1), np.int32) if want_iters else None
+        rc = self.L.spicey_run_measure(self.h, steps, dt, _p(src, C.c_double), 1 if per_inst else 0, r.ctypes.data if len(r) else None, len(r),
+                                       _p(meas, C.c_double), _p(iters, C.c_int32))
+        res = {"status": rc, "detail": self.error() if rc != abi.OK else "", "meas": meas, "iters": iters, "partial": True}
+        res["inst_status"] = self.inst_status() if rc in (abi.OK, abi.ERR_SINGULAR) else np.full(f.n_inst, rc, np.int32)
+        if rc in (abi.OK, abi.ERR_SINGULAR):
+            res["solves"] = self.L.spicey_last_solve_count(self.h)
+            res["kernel_ms"] = self.L.spicey_last_kernel_ms(self.h)
+            res["measure_ms"] = self.L.spicey_last_measure_ms(self.h)
+            res["state"] = self.state()
+            if self.diagnostics & 1:
+                per = np.zeros(f.n_inst, np.int64)
+                self.L.spicey_last_skip_risk(self.h, _p(per, C.c_int64))
+                res["skip_risk"] = per
         return res
 
     def run_device(self, steps: int, dt: float, d_src: int, d_out_v: int, d_out_i: int = 0, d_iters: int = 0, stream: int = 0,
@@ -489,6 +551,19 @@ class HipBackend:
         try:
             self.info = h.info()
             res = h.run(steps, dt, src, want_currents, want_iters)
+            self.group_retries += h.group_retries()
+            self.group_stale_polls += h.group_stale_polls()
+            res["group_retries"], res["group_stale_polls"] = h.group_retries(), h.group_stale_polls()
+            return res
+        finally:
+            h.close()
+
+    def run_measure(self, flat: abi.FlatCircuit, steps: int, dt: float, src: np.ndarray, reqs, want_iters: bool = True) -> dict:
+        """Handle.run_measure on a handle of its own: the waveforms never leave the device."""
+        h = Handle(flat, **self.kw)
+        try:
+            self.info = h.info()
+            res = h.run_measure(steps, dt, src, reqs, want_iters)
             self.group_retries += h.group_retries()
             self.group_stale_polls += h.group_stale_polls()
             res["group_retries"], res["group_stale_polls"] = h.group_retries(), h.group_stale_polls()

@@ -1,0 +1,321 @@
+"""measureTRAN() / measureTRANBatch(): a few numbers per circuit instead of every sample (what SPICE calls .meas).
+
+simulateTRAN returns whole waveforms; a sweep is usually run for the peak of an output, its ripple, an average current,
+the first time a node crosses a threshold, the period of an oscillator.  Here the transient's waveforms stay on the
+device and a reduction pass (spicey_run_measure, include/spicey_hip.h) brings back 8 doubles per (circuit, measure).  Only
+the measured nodes are recorded (SpiceyDesc.out_nodes; .PRINT cards are ignored) and element currents only if a measure
+names one.
+
+Specs
+    stats("v(out)")                        min, max, pp, t_min, t_max, first, final, integ, avg, rms
+    cross("v(a,b)", 2.5, dir="rise")       count, t_first, t_last, freq
+`signal` is "v(a)", "v(a,b)" (= v(a) - v(b), one rounded subtraction per sample; v(a,0) is v(a)) or "i(R1)" (the element
+current simulateTRAN records under that name).  Node names resolve case-insensitively like the parser's; element names
+too, and a name that several elements share is an error.
+
+Windows.  t_from / t_to (seconds, None = the run's first / last point) select the inclusive window of steps
+floor(t / dt + 0.5) — the nearest step, a tie going to the later one — clamped to [0, steps]; dt is the run's effective
+step (abi.computeEffectiveTimeStep).
+
+Derived values (on the host, from the device's {min, max, step_min, step_max, sum, sumsq, first, last}; n = samples in
+the window): pp = max - min, t_min / t_max = step * dt (first occurrence), integ = dt (sum - (first + last) / 2) — the
+trapezoidal rule on the uniform grid —, avg = integ / ((n - 1) dt), rms = sqrt(dt (sumsq - (first^2 + last^2) / 2) /
+((n - 1) dt)); a one-sample window gives integ = 0, avg = first, rms = |first|.  Crossings: rise is x_k < level <=
+x_k+1, fall x_k > level >= x_k+1, at linearly interpolated times; freq = (count - 1) / (t_last - t_first) for count >=
+2, else None; t_first / t_last are None without a crossing.
+
+reduce_reference() is the same definition in plain numpy; it is what the tests compare the device with, and what runs
+behind a backend that has no run_measure (backend.run, then reduce_reference: the CPU oracle works unchanged).
+"""
+from __future__ import annotations
+
+import math
+import re
+from dataclasses import dataclass
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+
+from . import abi
+from .batch import group_launches, run_launch, write_state
+from .netlist import ParsedCircuit
+from .simulate import SingularMatrixError
+
+_DIRS = {"rise": 1, "fall": -1, "either": 0}
+
+
+@dataclass(frozen=True)
+class Stats:
+    signal: str
+    t_from: Optional[float] = None
+    t_to: Optional[float] = None
+
+
+@dataclass(frozen=True)
+class Cross:
+    signal: str
+    level: float
+    dir: int = 1
+    t_from: Optional[float] = None
+    t_to: Optional[float] = None
+
+
+def stats(signal: str, t_from: Optional[float] = None, t_to: Optional[float] = None) -> Stats:
+    return Stats(str(signal), t_from, t_to)
+
+
+def cross(signal: str, level: float, dir="rise", t_from: Optional[float] = None, t_to: Optional[float] = None) -> Cross:
+    if dir not in _DIRS:
+        raise ValueError(f"cross: dir must be 'rise', 'fall' or 'either', got {dir!r}")
+    return Cross(str(signal), float(level), _DIRS[dir], t_from, t_to)
+
+
+def make_reqs(rows: Sequence[tuple]) -> np.ndarray:
+    """Request records (abi.MEAS_REQ_DTYPE) from tuples (kind, signal, col, col_ref, step_from, step_to, level, dir)."""
+    a = np.zeros(len(rows), abi.MEAS_REQ_DTYPE)
+    for k, r in enumerate(rows):
+        a[k] = tuple(r) + (0,)
+    return a
+
+
+def time_to_step(t: Optional[float], dt: float, steps: int, default: int) -> int:
+    """The window rule of the module text: nearest step, ties to the later one, clamped to the run."""
+    if t is None:
+        return default
+    return int(min(max(math.floor(t / dt + 0.5), 0), steps))
+
+
+_SIGNAL = re.compile(r"^\s*([vi])\s*\(\s*([^,()\s]+)\s*(?:,\s*([^,()\s]+)\s*)?\)\s*$", re.I)
+
+
+def _element_names(ckt: ParsedCircuit) -> List[str]:
+    # simulateTRAN's recording order (R, C, L, V, S, D): the columns of out_i
+    return ([e.name for e in ckt.R] + [e.name for e in ckt.C] + [e.name for e in ckt.L] + [e.name for e in ckt.V]
+            + [e.name for e in ckt.S if e.model is not None] + [e.name for e in ckt.D if e.model is not None])
+
+
+def _parse_signal(ckt: ParsedCircuit, text: str) -> Tuple[int, int, int]:
+    """(signal, a, b): signal 0 -> node ids a and b (b = 0: none); signal 1 -> out_i column a."""
+    m = _SIGNAL.match(text)
+    if not m:
+        raise ValueError(f"measure: cannot read the signal {text!r} (v(node), v(node,node) or i(element))")
+    kind, a, b = m.group(1).lower(), m.group(2), m.group(3)
+    if kind == "i":
+        if b is not None:
+            raise ValueError(f"measure: {text!r}: i() takes one element name")
+        hits = [k for k, nm in enumerate(_element_names(ckt)) if nm.upper() == a.upper()]
+        if not hits:
+            raise ValueError(f"measure: {text!r}: no element named {a!r} records a current")
+        if len(hits) > 1:
+            raise ValueError(f"measure: {text!r}: {len(hits)} elements share the name {a!r}")
+        return 1, hits[0], 0
+    ids = []
+    for nm in (a, b):
+        if nm is None:
+            ids.append(0)
+            continue
+        i = ckt.nodes.get(nm)
+        if i is None:
+            raise ValueError(f"measure: {text!r}: no node named {nm!r}")
+        ids.append(i)
+    if ids[0] == 0:
+        raise ValueError(f"measure: {text!r}: the first node is ground")
+    return 0, ids[0], ids[1]
+
+
+class _Plan:
+    """A circuit's measures resolved: the recorded nodes, whether currents are needed, the request records."""
+
+    def __init__(self, ckt: ParsedCircuit, measures: Dict[str, object], dt: float, steps: int):
+        if not measures:
+            raise ValueError("measure: no measures given")
+        parsed = []
+        for name, spec in measures.items():
+            if not isinstance(spec, (Stats, Cross)):
+                raise TypeError(f"measure {name!r}: expected stats(...) or cross(...), got {type(spec).__name__}")
+            parsed.append((name, spec, _parse_signal(ckt, spec.signal)))
+        nodes = sorted({n for _, _, (sig, a, b) in parsed if sig == 0 for n in (a, b) if n != 0})
+        self.need_i = any(sig == 1 for _, _, (sig, _, _) in parsed)
+        # (a device descriptor records at least one node; with current measures only, the first one)
+        self.out_nodes = nodes if nodes else [1]
+        col = {n: c for c, n in enumerate(self.out_nodes)}
+        rows = []
+        self.names = []
+        for name, spec, (sig, a, b) in parsed:
+            s0 = time_to_step(spec.t_from, dt, steps, 0)
+            s1 = time_to_step(spec.t_to, dt, steps, steps)
+            if s0 > s1:
+                raise ValueError(f"measure {name!r}: the window is empty (t_from maps to step {s0}, t_to to step {s1})")
+            c, cr = (col[a], col[b] if b else -1) if sig == 0 else (a, -1)
+            if isinstance(spec, Stats):
+                rows.append((abi.MEAS_STATS, sig, c, cr, s0, s1, 0.0, 0))
+            else:
+                rows.append((abi.MEAS_CROSS, sig, c, cr, s0, s1, spec.level, spec.dir))
+            self.names.append(name)
+        self.reqs = make_reqs(rows)
+
+    def flatten(self, ckt: ParsedCircuit) -> abi.FlatCircuit:
+        flat = abi.flatten(ckt)
+        flat.out_nodes = np.ascontiguousarray(self.out_nodes, dtype=np.int32)
+        return flat
+
+    def values(self, meas: np.ndarray, dt: float) -> Dict[str, dict]:
+        """meas [n_req][8] of one instance -> {name: {...}}."""
+        return {name: derive(self.reqs[k], meas[k], dt) for k, name in enumerate(self.names)}
+
+
+def derive(req, m, dt: float) -> dict:
+    """The values of one measure from its 8 doubles (module text)."""
+    if int(req["kind"]) == abi.MEAS_STATS:
+        mn, mx, smn, smx, s, sq, first, last = (float(v) for v in m)
+        n = int(req["step_to"]) - int(req["step_from"]) + 1
+        if n > 1:
+            span = (n - 1) * dt
+            integ = dt * (s - (first + last) / 2)
+            avg = integ / span
+            rms = math.sqrt(max(dt * (sq - (first * first + last * last) / 2) / span, 0.0))
+        else:
+            integ, avg, rms = 0.0, first, abs(first)
+        return {"min": mn, "max": mx, "pp": mx - mn, "t_min": smn * dt, "t_max": smx * dt, "first": first, "final": last,
+                "integ": integ, "avg": avg, "rms": rms}
+    count = int(m[0])
+    tf, tl = (float(m[1]), float(m[2])) if count > 0 else (None, None)
+    freq = (count - 1) / (tl - tf) if count >= 2 and tl > tf else None
+    return {"count": count, "t_first": tf, "t_last": tl, "freq": freq}
+
+
+def reduce_reference(out_v: np.ndarray, out_i: Optional[np.ndarray], reqs, dt: float) -> np.ndarray:
+    """The definition of spicey_measure_device in numpy, independent of the kernels: out_v [n_inst][n_points][n_v], out_i
+    likewise or None, reqs records of abi.MEAS_REQ_DTYPE with step_to resolved or -1 -> meas [n_inst][n_req][8].  The sums
+    are plain Python sums in step order; everything else has one value whatever the order."""
+    reqs = np.ascontiguousarray(reqs, dtype=abi.MEAS_REQ_DTYPE).reshape(-1)
+    out_v = np.asarray(out_v, dtype=np.float64)
+    ni, n_points = out_v.shape[0], out_v.shape[1]
+    meas = np.zeros((ni, len(reqs), 8))
+    for r, q in enumerate(reqs):
+        a = out_i if int(q["signal"]) == 1 else out_v
+        if a is None:
+            raise ValueError("reduce_reference: a request names a current, but there is no out_i")
+        a = np.asarray(a, dtype=np.float64)
+        s0 = int(q["step_from"])
+        s1 = n_points - 1 if int(q["step_to"]) == -1 else int(q["step_to"])
+        if not (0 <= s0 <= s1 < n_points):
+            raise ValueError(f"reduce_reference: request {r}: window [{s0}, {s1}] outside the run")
+        x = a[:, s0:s1 + 1, int(q["col"])]
+        if int(q["col_ref"]) >= 0:
+            x = x - a[:, s0:s1 + 1, int(q["col_ref"])]
+        for i in range(ni):
+            xi = x[i]
+            if int(q["kind"]) == abi.MEAS_STATS:
+                if np.isnan(xi).any():  # (the comparisons x < m, x > m skip a NaN; numpy's argmin would return it)
+                    mn = mx = float(xi[0])
+                    kmn = kmx = 0
+                    for k, v in enumerate(xi.tolist()):
+                        if v < mn:
+                            mn, kmn = v, k
+                        if v > mx:
+                            mx, kmx = v, k
+                else:
+                    kmn, kmx = int(np.argmin(xi)), int(np.argmax(xi))  # (first occurrence)
+                    mn, mx = float(xi[kmn]), float(xi[kmx])
+                vals = xi.tolist()
+                s = 0.0
+                sq = 0.0
+                for v in vals:
+                    s += v
+                    sq += v * v
+                meas[i, r] = (mn, mx, s0 + kmn, s0 + kmx, s, sq, vals[0], vals[-1])
+            else:
+                lv, d = float(q["level"]), int(q["dir"])
+                xa, xb = xi[:-1], xi[1:]
+                hit = np.zeros(len(xa), bool)
+                if d >= 0:
+                    hit |= (xa < lv) & (xb >= lv)
+                if d <= 0:
+                    hit |= (xa > lv) & (xb <= lv)
+                ks = np.nonzero(hit)[0]
+                if len(ks):
+                    t = ((s0 + ks).astype(np.float64) + (lv - xa[ks]) / (xb[ks] - xa[ks])) * dt
+                    meas[i, r, :3] = (len(ks), t[0], t[-1])
+                else:
+                    meas[i, r, :3] = (0.0, -1.0, -1.0)
+    return meas
+
+
+def backend_measure(be, flat: abi.FlatCircuit, steps: int, dt: float, src: np.ndarray, reqs: np.ndarray, need_i: bool) -> dict:
+    """The backend's run_measure, or for a backend without one its run followed by reduce_reference."""
+    if hasattr(be, "run_measure"):
+        return be.run_measure(flat, steps, dt, src, reqs)
+    res = be.run(flat, steps, dt, src, want_currents=need_i)
+    if res["status"] == abi.OK or (res["status"] == abi.ERR_SINGULAR and res.get("partial")):
+        res["meas"] = reduce_reference(res["out_v"], res.get("out_i"), reqs, dt)
+    return res
+
+
+def _backend(backend, exact_order: bool, device: int, diagnostics: bool, who: str):
+    if exact_order and backend is not None:
+        raise ValueError(f"{who}: pass either backend= or exact_order=True, not both")
+    if backend is not None:
+        return backend
+    from .lib import HipBackend  # fails loudly if the extension is missing
+
+    return HipBackend(device=device, diagnostics=1 if diagnostics else 0, interpreter=3 if exact_order else 0)
+
+
+def measureTRAN(ckt: ParsedCircuit, measures: Dict[str, object], *, exact_order: bool = False, device: int = 0, backend=None) -> Optional[dict]:
+    """The transient of `ckt` reduced to {name: {...}} for measures = {name: stats(...) | cross(...)} (module text).  None
+    without a .tran card; SingularMatrixError and the circuit's state write-back exactly as simulateTRAN; exact_order=True
+    runs the reference-order engine."""
+    be = _backend(backend, exact_order, device, True, "measureTRAN")
+    tran = ckt.analyses.get("tran")
+    if not tran:
+        return None
+    dt, steps = abi.computeEffectiveTimeStep(tran["dt"], tran["tstop"])
+    plan = _Plan(ckt, measures, dt, steps)
+    flat = plan.flatten(ckt)
+    src = abi.source_table(ckt, dt, steps)
+    res = backend_measure(be, flat, steps, dt, src, plan.reqs, plan.need_i)
+    if res["status"] == abi.ERR_SINGULAR:
+        raise SingularMatrixError(res.get("detail", ""))
+    if res["status"] != abi.OK:
+        raise RuntimeError(res.get("detail", f"spicey native error {res['status']}"))
+    write_state(ckt, res["state"], 0)
+    return plan.values(res["meas"][0], dt)
+
+
+def measureTRANBatch(ckts: Sequence[ParsedCircuit], measures: Dict[str, object], *, exact_order: bool = False, diagnostics: bool = True,
+                     device: int = 0, max_instances: int = 4096, backend=None) -> List[Optional[object]]:
+    """measureTRAN for many circuits in as few launches as simulateTRANBatch would make (spicey_amd/batch.py): circuits that
+    share topology, measured columns, windows, dt and step count are the instances of one handle, with the measured nodes as
+    the recorded nodes; groups above max_instances are split; instances a failing workgroup mate stopped run again.  Slot i
+    is measureTRAN(ckts[i], measures)'s dict, None without .tran, or — returned, not raised, with the circuit's state left
+    alone — its SingularMatrixError."""
+    seen = set()
+    for c in ckts:
+        if id(c) in seen:
+            raise ValueError("measureTRANBatch: the same circuit object appears twice (its state would be written twice)")
+        seen.add(id(c))
+    be = _backend(backend, exact_order, device, diagnostics, "measureTRANBatch")
+    out: List[Optional[object]] = [None] * len(ckts)
+    plans: Dict[int, _Plan] = {}
+
+    def plan_of(c: ParsedCircuit) -> _Plan:
+        if id(c) not in plans:
+            tran = c.analyses["tran"]
+            dt, steps = abi.computeEffectiveTimeStep(tran["dt"], tran["tstop"])
+            plans[id(c)] = _Plan(c, measures, dt, steps)
+        return plans[id(c)]
+
+    # (names resolve per circuit: two circuits of one topology may call its elements differently — the request records
+    # are part of the group's key, so one launch has one request table)
+    launches = group_launches(ckts, max_instances, lambda c: plan_of(c).flatten(c), lambda c, dt, steps: plan_of(c).reqs.tobytes())
+    for idx in launches:
+        plan = plan_of(ckts[idx[0]])
+
+        def result(i, flat_i, dt, steps, res, j, sk):
+            write_state(ckts[i], res["state"], j)
+            return plan_of(ckts[i]).values(res["meas"][j], dt)
+
+        run_launch(lambda flat, steps, dt, src: backend_measure(be, flat, steps, dt, src, plan.reqs, plan.need_i), ckts, idx, out, diagnostics,
+                   lambda c: plan_of(c).flatten(c), result, "measureTRANBatch")
+    return out
