@@ -392,6 +392,81 @@ double spicey_ac_last_kernel_ms(SpiceyAcHandle *h);
 const char *spicey_ac_last_error(SpiceyAcHandle *h);
 void spicey_ac_destroy(SpiceyAcHandle *h);
 
+/* Per instance of the last sweep (spicey_ac_run / spicey_ac_run_measure), status[n_inst]: 0, or the code
+ * (SPICEY_ERR_SINGULAR / SPICEY_ERR_COMPLEX_DIV) of the instance's LOWEST failing frequency index, and in
+ * first_freq[n_inst] (or NULL) that index, -1 for an instance that is fine.  Both engines answer; for the sparse engine the
+ * words are those after the dense partial-pivoting fallback has repeated the solves that tripped a pivot guard.  Returns the
+ * number of nonzero entries; -1 without a handle or a status buffer, before any run, and when the last run was refused
+ * before its launch (bad arguments, a HIP error).  A structurally singular descriptor is answered: every instance
+ * SPICEY_ERR_SINGULAR at frequency index 0.
+ * When spicey_ac_run returns SPICEY_ERR_SINGULAR / SPICEY_ERR_COMPLEX_DIV, out_v / out_i have still been copied: the rows
+ * of every instance whose status is 0 are complete (each (instance, frequency) solve is independent; a failed solve leaves
+ * only its own slot undefined). */
+int32_t spicey_ac_last_inst_status(SpiceyAcHandle *h, int32_t *status /* [n_inst] */, int64_t *first_freq /* [n_inst] or NULL */);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Measurements over an AC sweep on the device (the -3 dB corner, the peak, the phase at unity gain): a reduction pass over
+ * the complex buffers [n_inst][n_freq][n][2] a sweep wrote; only [n_inst][n_req][8] doubles leave the device.
+ * One request = one complex signal H_k over the frequency indices k, one inclusive window, one kind:
+ *   num_signal   0 = out_v, 1 = out_i; num_col the column; num_col_ref = -1: none, else the numerator is
+ *                a[num_col] - a[num_col_ref] of the same array, one rounded subtraction per part
+ *   den_signal   -1 = no denominator (H = numerator), else 0 / 1 with den_col / den_col_ref likewise: H = num / den by the
+ *                reference's Complex.div arithmetic (math/Complex.ts:38-47) without its |d| < EPS throw,
+ *                  d = b.re b.re + b.im b.im;  re = (a.re b.re + a.im b.im) / d;  im = (a.im b.re - a.re b.im) / d
+ *                — a zero denominator gives the IEEE result (NaN or infinity)
+ *   what         the measured real quantity q_k: 0 = |H|^2 = re re + im im, 1 = re, 2 = im.  No sqrt, log or atan2 runs on
+ *                the device: magnitudes, decibels and phases are the host's to derive from the returned re / im, so a CPU
+ *                and the device can agree on every bit
+ *   k_from, k_to inclusive window of frequency indices; k_to = -1: the last index
+ *   kind         0 = extrema, 1 = crossings
+ *   level, dir, which, rel   crossings only (0 otherwise): dir +1 = rises, -1 = falls, 0 = both; which 0 = report the
+ *                first crossing's bracket, 1 = the last one's; rel 0: the threshold is `level`, rel 1: it is
+ *                level * q_{k_from}, one rounded product ("3 dB below the passband", per instance)
+ *   reserved     0
+ * Results, 8 doubles per (instance, request):
+ *   extrema    {min, max, k_min, k_max, re@k_min, im@k_min, re@k_max, im@k_max}: the result of m = q_{k_from}, then the
+ *              plain comparisons q < m and q > m in ascending k — the FIRST occurrence wins and a NaN sample never replaces
+ *              an extreme (a window whose first sample is NaN keeps that NaN as both extremes, at k_from).  A one-sample
+ *              window is the point read-out "H at this frequency".
+ *   crossings  {count, k_first, k_last, re_k, im_k, re_k+1, im_k+1, thr} over the intervals (k, k + 1) with both ends in
+ *              the window: a rise is q_k < thr && q_k+1 >= thr, a fall q_k > thr && q_k+1 <= thr; k_first / k_last are
+ *              the lower ends of the first / last such interval, the four H parts those of the interval `which` names, thr
+ *              the threshold actually used.  count = 0: k_first = k_last = -1 and the H parts are 0.
+ * No field is a floating-point accumulation (counts are integers), so every result is a function of the window's samples
+ * and the request alone: it does not depend on the launch geometry, on n_inst or on the other requests of the list.  The
+ * implementation keeps that true: no atomics, no FMA contraction. */
+typedef struct SpiceyAcMeasReq {
+  int32_t num_signal, num_col, num_col_ref;
+  int32_t den_signal, den_col, den_col_ref;
+  int32_t what, kind;
+  int64_t k_from, k_to;
+  double level;
+  int32_t dir, which, rel, reserved;
+} SpiceyAcMeasReq;
+
+/* Bytes of device workspace spicey_ac_measure_device needs (the request table: the kernel keeps no partials); -1 for
+ * counts <= 0. */
+int64_t spicey_ac_measure_workspace_bytes(int32_t n_inst, int64_t n_freq, int32_t n_req);
+/* The reduction alone, on any DEVICE buffers d_v [n_inst][n_freq][n_v][2] and d_i [n_inst][n_freq][n_i][2] (or NULL): needs
+ * no handle.  reqs is a HOST array; d_meas [n_inst][n_req][8] and d_work (work_bytes >= spicey_ac_measure_workspace_bytes)
+ * are DEVICE buffers.  Enqueued on `stream` (a hipStream_t, NULL = default stream) without synchronising.
+ * SPICEY_ERR_BAD_DESC, with a text containing "ac measure" in spicey_last_error(NULL) and nothing launched, for: an unknown
+ * kind, signal, what, dir, which or rel; a column out of range; a current signal with d_i == NULL; a window outside
+ * [0, n_freq) or with k_from > k_to; n_req <= 0; a nonzero reserved word; a workspace that is too small. */
+int32_t spicey_ac_measure_device(int32_t device, int32_t n_inst, int64_t n_freq, const double *d_v, int32_t n_v, const double *d_i,
+                                 int32_t n_i, const SpiceyAcMeasReq *reqs, int32_t n_req, double *d_meas, void *d_work,
+                                 int64_t work_bytes, void *stream);
+/* One sweep — exactly that of spicey_ac_run, in either engine — whose results stay on the device: out_v (and out_i only if
+ * a request has a current signal) are allocated there and reduced on the handle's stream after the dense fallback has
+ * repaired its slots; only meas [n_inst][n_req][8] (HOST) comes back.  Columns are those of the handle (SpiceyInfo.n_out,
+ * n_cur).  The return value and spicey_ac_last_inst_status are as after spicey_ac_run; meas is also filled when the sweep
+ * reports SPICEY_ERR_SINGULAR / SPICEY_ERR_COMPLEX_DIV, where the rows of instances whose status is nonzero are undefined.
+ * A refused request list (SPICEY_ERR_BAD_DESC, text in spicey_ac_last_error) runs nothing. */
+int32_t spicey_ac_run_measure(SpiceyAcHandle *h, int64_t n_freq, const double *freqs, const double *vph, const SpiceyAcMeasReq *reqs,
+                              int32_t n_req, double *meas);
+/* Duration in ms of the last spicey_ac_run_measure's reduction, measured with HIP events. */
+double spicey_ac_last_measure_ms(SpiceyAcHandle *h);
+
 /* ---------------------------------------------------------------------------------------------------------------
  * Result formatting fast path (host code, no GPU): the CSV text of
  *   formatTranResult(tran)       /root/reference/lib/formatting/formatTranResult.ts:1-23

@@ -67,6 +67,22 @@ assert MEAS_REQ_DTYPE.itemsize == C.sizeof(SpiceyMeasReq) == 48
 MEAS_STATS, MEAS_CROSS = 0, 1
 
 
+class SpiceyAcMeasReq(C.Structure):
+    _fields_ = [("num_signal", C.c_int32), ("num_col", C.c_int32), ("num_col_ref", C.c_int32),
+                ("den_signal", C.c_int32), ("den_col", C.c_int32), ("den_col_ref", C.c_int32), ("what", C.c_int32), ("kind", C.c_int32),
+                ("k_from", C.c_int64), ("k_to", C.c_int64), ("level", C.c_double),
+                ("dir", C.c_int32), ("which", C.c_int32), ("rel", C.c_int32), ("reserved", C.c_int32)]
+
+
+# one request of an AC measurement (include/spicey_hip.h, SpiceyAcMeasReq; spicey_amd/ac_measure.py builds them)
+AC_MEAS_REQ_DTYPE = np.dtype([("num_signal", "<i4"), ("num_col", "<i4"), ("num_col_ref", "<i4"), ("den_signal", "<i4"), ("den_col", "<i4"),
+                              ("den_col_ref", "<i4"), ("what", "<i4"), ("kind", "<i4"), ("k_from", "<i8"), ("k_to", "<i8"), ("level", "<f8"),
+                              ("dir", "<i4"), ("which", "<i4"), ("rel", "<i4"), ("reserved", "<i4")])
+assert AC_MEAS_REQ_DTYPE.itemsize == C.sizeof(SpiceyAcMeasReq) == 72
+AC_MEAS_EXTREMA, AC_MEAS_CROSS = 0, 1
+AC_WHAT_MAG2, AC_WHAT_RE, AC_WHAT_IM = 0, 1, 2
+
+
 def _i32(a) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.int32)
 

@@ -121,9 +121,11 @@ def simulateAC(ckt: ParsedCircuit, backend=None, freqs: Optional[List[float]] = 
         raise ZeroDivisionError("Complex divide by ~0")
     if res["status"] != abi.OK:
         raise RuntimeError(res.get("detail", f"spicey native error {res['status']}"))
-    out_v = res["out_v"][0]  # [n_freq][n_nodes] complex
-    out_i = res["out_i"][0]  # [n_freq][nR+nC+nL+nV]
+    return ac_result(ckt, freqs, res["out_v"][0], res["out_i"][0])
 
+
+def ac_result(ckt: ParsedCircuit, freqs, out_v: np.ndarray, out_i: np.ndarray) -> dict:
+    """simulateAC's result from one instance's out_v [n_freq][n_nodes] and out_i [n_freq][nR+nC+nL+nV] (complex)."""
     names = ckt.nodes.rev
     order = js_object_key_order([names[i] for i in range(1, ckt.nodes.count())])
     col = {names[i]: i - 1 for i in range(1, ckt.nodes.count())}

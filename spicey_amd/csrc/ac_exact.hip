@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "ac_exact_exec.h"
+#include "ac_sweep.h"
 #include "devbuf.h"
 #include "kernels.h"
 
@@ -173,24 +174,31 @@ const char *spicey_ac_exact_error(const SpiceyAcExact *x) { return x->err.c_str(
 
 #define XCHK(call) HIPCHK(x, call)
 
-int32_t spicey_ac_exact_run(SpiceyAcExact *x, int64_t n_freq, const double *freqs, const double *vph, double *out_v, double *out_i, double *ms) {
+hipStream_t spicey_ac_exact_stream(const SpiceyAcExact *x) { return x->stream; }
+void spicey_ac_exact_dims(const SpiceyAcExact *x, int32_t *n_inst, int32_t *n_out, int32_t *n_cur, int32_t *n_v) {
+  *n_inst = x->n_inst;
+  *n_out = x->xp.hdr.nOut;
+  *n_cur = x->xp.hdr.nCur;
+  *n_v = x->xp.hdr.nV;
+}
+
+// The sweep into device buffers: every slot solved, o.status on the host, the stream idle.  The caller copies out or reduces.
+int32_t spicey_ac_exact_sweep(SpiceyAcExact *x, int64_t n_freq, const double *freqs, const double *vph, bool want_i, SpiceyAcSweep &o, double *ms) {
   const SpiceyAcExactProg &H = x->xp.hdr;
-  if (n_freq < 0 || (n_freq > 0 && (!freqs || !out_v)) || (H.nV > 0 && !vph)) { x->err = "bad run arguments"; return SPICEY_ERR_BAD_DESC; }
-  if (n_freq == 0) return SPICEY_OK;
   const int64_t slots = (int64_t)x->n_inst * n_freq;
   if (slots > 0x7fffffffll) { x->err = "n_inst * n_freq exceeds the grid limit"; return SPICEY_ERR_BAD_DESC; }
   XCHK(hipSetDevice(x->device));
   const int64_t chunk = spicey_ac_exact_chunk(x->plan, slots);
-  std::vector<int32_t> status((size_t)slots);
+  o.status.assign((size_t)slots, 0);
   {
-    DevBuf<double> d_f, d_ph, d_ov, d_oi;
+    DevBuf<double> d_f, d_ph;
     DevBuf<SpiceyCx> d_gW;
     DevBuf<int32_t> d_status;
     DevBuf<SpiceyAcExactRun> d_run;
     XCHK(d_f.alloc((size_t)n_freq));
     XCHK(d_ph.alloc(std::max<size_t>(1, (size_t)x->n_inst * H.nV * 2)));
-    XCHK(d_ov.alloc(std::max<size_t>(1, (size_t)slots * H.nOut * 2)));
-    if (out_i) XCHK(d_oi.alloc(std::max<size_t>(1, (size_t)slots * H.nCur * 2)));
+    XCHK(o.d_ov.alloc(std::max<size_t>(1, (size_t)slots * H.nOut * 2)));
+    if (want_i) XCHK(o.d_oi.alloc(std::max<size_t>(1, (size_t)slots * H.nCur * 2)));
     XCHK(d_status.alloc((size_t)slots));
     if (!x->plan.lds && d_gW.alloc((size_t)chunk * (size_t)H.ws_cx) != hipSuccess) {
       x->err = "allocation of the global slab failed (" + std::to_string((size_t)chunk * (size_t)H.ws_cx * 16) + " bytes)";
@@ -200,7 +208,7 @@ int32_t spicey_ac_exact_run(SpiceyAcExact *x, int64_t n_freq, const double *freq
     if (H.nV > 0) XCHK(hipMemcpyAsync(d_ph, vph, (size_t)x->n_inst * H.nV * 2 * sizeof(double), hipMemcpyHostToDevice, x->stream));
     SpiceyAcExactRun R{};
     R.R_inv = x->d_R; R.C_val = x->d_C; R.L_val = x->d_L;
-    R.freqs = d_f; R.vph = d_ph; R.out_v = d_ov; R.out_i = d_oi; R.gW = d_gW; R.status = d_status; R.skipped = nullptr;
+    R.freqs = d_f; R.vph = d_ph; R.out_v = o.d_ov; R.out_i = o.d_oi; R.gW = d_gW; R.status = d_status; R.skipped = nullptr;
     R.n_freq = n_freq; R.n_inst = x->n_inst;
     XCHK(d_run.alloc(1));
     XCHK(hipMemcpyAsync(d_run, &R, sizeof(R), hipMemcpyHostToDevice, x->stream));
@@ -208,21 +216,11 @@ int32_t spicey_ac_exact_run(SpiceyAcExact *x, int64_t n_freq, const double *freq
     for (int64_t base = 0; base < slots; base += chunk)
       XCHK(spicey_launch_ac_exact(x->d_P, d_run, base, (int)std::min(chunk, slots - base), x->plan.T, x->plan.lds_bytes, x->stream));
     XCHK(hipEventRecord(x->ev1, x->stream));
-    XCHK(hipMemcpyAsync(status.data(), d_status, (size_t)slots * sizeof(int32_t), hipMemcpyDeviceToHost, x->stream));
-    XCHK(hipMemcpyAsync(out_v, d_ov, (size_t)slots * H.nOut * 2 * sizeof(double), hipMemcpyDeviceToHost, x->stream));
-    if (out_i) XCHK(hipMemcpyAsync(out_i, d_oi, (size_t)slots * H.nCur * 2 * sizeof(double), hipMemcpyDeviceToHost, x->stream));
+    XCHK(hipMemcpyAsync(o.status.data(), d_status, (size_t)slots * sizeof(int32_t), hipMemcpyDeviceToHost, x->stream));
     XCHK(hipStreamSynchronize(x->stream));
     float f = 0.f;
     if (hipEventElapsedTime(&f, x->ev0, x->ev1) == hipSuccess) *ms = f;
   }
   x->last_slots = slots;
-  // the reference stops at the first frequency that throws (simulateAC.ts:80-83): report the first failing slot
-  for (int64_t s = 0; s < slots; s++)
-    if (status[(size_t)s] != 0) {
-      const bool sing = status[(size_t)s] == SPICEY_ERR_SINGULAR;
-      x->err = std::string(sing ? "Singular matrix (complex)" : "Complex divide by ~0") + " at inst " + std::to_string(s / n_freq) + " frequency index " +
-               std::to_string(s % n_freq);
-      return sing ? SPICEY_ERR_SINGULAR : SPICEY_ERR_COMPLEX_DIV;
-    }
   return SPICEY_OK;
 }

@@ -29,7 +29,10 @@ hipError_t spicey_launch_exact(const SpiceyExactProg *P, const SpiceyRun *R, int
 // ac.hip hand a handle created with SpiceyOptions.interpreter = 3 to these; `err` / spicey_ac_exact_error carry the message.
 struct SpiceyAcExact;
 int32_t spicey_ac_exact_create(const SpiceyDesc *desc, const SpiceyOptions &opt, SpiceyAcExact **out, std::string &err);
-int32_t spicey_ac_exact_run(SpiceyAcExact *x, int64_t n_freq, const double *freqs, const double *vph, double *out_v, double *out_i, double *ms);
+struct SpiceyAcSweep;
+int32_t spicey_ac_exact_sweep(SpiceyAcExact *x, int64_t n_freq, const double *freqs, const double *vph, bool want_i, SpiceyAcSweep &o, double *ms);
+hipStream_t spicey_ac_exact_stream(const SpiceyAcExact *x);
+void spicey_ac_exact_dims(const SpiceyAcExact *x, int32_t *n_inst, int32_t *n_out, int32_t *n_cur, int32_t *n_v);
 void spicey_ac_exact_info(const SpiceyAcExact *x, SpiceyInfo *info);
 const char *spicey_ac_exact_error(const SpiceyAcExact *x);
 void spicey_ac_exact_destroy(SpiceyAcExact *x);

@@ -54,39 +54,42 @@ TableRing &table_ring() {
 
 }  // namespace
 
+hipError_t spicey_upload_table_async(int device, void *d_dst, const void *table, size_t bytes, hipStream_t st) {
+  hipError_t e;
+  TableRing &ring = table_ring();
+  std::lock_guard<std::mutex> lk(ring.mu);
+  TableRing::Slot &s = ring.slot[ring.next];
+  ring.next = (ring.next + 1) % TableRing::SLOTS;
+  if (s.used) {
+    if ((e = hipEventSynchronize(s.ev)) != hipSuccess) return e;
+    s.used = false;
+  }
+  if (s.ev && s.device != device) {  // (an event belongs to the device it was created on)
+    (void)hipEventDestroy(s.ev);
+    s.ev = nullptr;
+  }
+  if (!s.ev) {
+    if ((e = hipEventCreateWithFlags(&s.ev, hipEventDisableTiming)) != hipSuccess) return e;
+    s.device = device;
+  }
+  if (s.cap < bytes) {
+    if (s.p) (void)hipHostFree(s.p);
+    s.p = nullptr;
+    s.cap = 0;
+    if ((e = hipHostMalloc(&s.p, bytes, hipHostMallocDefault)) != hipSuccess) return e;
+    s.cap = bytes;
+  }
+  memcpy(s.p, table, bytes);
+  if ((e = hipMemcpyAsync(d_dst, s.p, bytes, hipMemcpyHostToDevice, st)) != hipSuccess) return e;
+  if ((e = hipEventRecord(s.ev, st)) != hipSuccess) return e;
+  s.used = true;
+  return hipSuccess;
+}
+
 hipError_t spicey_launch_measure(int device, int32_t n_inst, int64_t n_points, double dt, const double *d_v, int32_t n_v, const double *d_i, int32_t n_i,
                                  const SpiceyMeasDevReq *table, int32_t n_req, double *d_meas, void *d_work, hipStream_t st) {
   hipError_t e;
-  const size_t bytes = (size_t)n_req * sizeof(SpiceyMeasDevReq);
-  {
-    TableRing &ring = table_ring();
-    std::lock_guard<std::mutex> lk(ring.mu);
-    TableRing::Slot &s = ring.slot[ring.next];
-    ring.next = (ring.next + 1) % TableRing::SLOTS;
-    if (s.used) {
-      if ((e = hipEventSynchronize(s.ev)) != hipSuccess) return e;
-      s.used = false;
-    }
-    if (s.ev && s.device != device) {  // (an event belongs to the device it was created on)
-      (void)hipEventDestroy(s.ev);
-      s.ev = nullptr;
-    }
-    if (!s.ev) {
-      if ((e = hipEventCreateWithFlags(&s.ev, hipEventDisableTiming)) != hipSuccess) return e;
-      s.device = device;
-    }
-    if (s.cap < bytes) {
-      if (s.p) (void)hipHostFree(s.p);
-      s.p = nullptr;
-      s.cap = 0;
-      if ((e = hipHostMalloc(&s.p, bytes, hipHostMallocDefault)) != hipSuccess) return e;
-      s.cap = bytes;
-    }
-    memcpy(s.p, table, bytes);
-    if ((e = hipMemcpyAsync(d_work, s.p, bytes, hipMemcpyHostToDevice, st)) != hipSuccess) return e;
-    if ((e = hipEventRecord(s.ev, st)) != hipSuccess) return e;
-    s.used = true;
-  }
+  if ((e = spicey_upload_table_async(device, d_work, table, (size_t)n_req * sizeof(SpiceyMeasDevReq), st)) != hipSuccess) return e;
   const SpiceyMeasDevReq *d_table = (const SpiceyMeasDevReq *)d_work;
   double *partials = (double *)((char *)d_work + spicey_meas_head_bytes(n_req));
   const SpiceyMeasGeom g = spicey_meas_geom(n_inst, n_points, n_req, SPICEY_MEAS_THREADS);

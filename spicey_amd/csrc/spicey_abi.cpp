@@ -19,6 +19,8 @@
 #include "exact_plan.h"
 #include "kernels.h"
 #include "launch_plan.h"
+#include "ac_measure.h"
+#include "ac_measure_exec.h"
 #include "measure.h"
 #include "measure_exec.h"
 #include "symbolic.h"
@@ -827,6 +829,35 @@ extern "C" int32_t spicey_run_measure(SpiceyHandle *h, int64_t steps, double dt,
 }
 
 extern "C" double spicey_last_measure_ms(SpiceyHandle *h) { return h ? h->last_measure_ms : 0.0; }
+
+// The same for an AC sweep's complex buffers (include/spicey_hip.h): the reduction of ac_measure.hip, no handle.
+extern "C" int64_t spicey_ac_measure_workspace_bytes(int32_t n_inst, int64_t n_freq, int32_t n_req) {
+  return spicey_acm_workspace_bytes(n_inst, n_freq, n_req);
+}
+
+extern "C" int32_t spicey_ac_measure_device(int32_t device, int32_t n_inst, int64_t n_freq, const double *d_v, int32_t n_v, const double *d_i, int32_t n_i,
+                                            const SpiceyAcMeasReq *reqs, int32_t n_req, double *d_meas, void *d_work, int64_t work_bytes, void *stream) {
+  // (the call is judged before the device is touched: a refusal launches nothing)
+  if (n_inst <= 0 || n_v < 0 || n_i < 0 || !d_meas || !d_work) {
+    g_err = "ac measure: bad arguments (n_inst >= 1, result and workspace buffers)";
+    return SPICEY_ERR_BAD_DESC;
+  }
+  std::vector<SpiceyAcMeasDevReq> table;
+  if (!spicey_acm_plan(reqs, n_req, n_freq, d_v ? n_v : 0, n_i, d_i != nullptr, table, g_err)) return SPICEY_ERR_BAD_DESC;
+  const int64_t need = spicey_acm_workspace_bytes(n_inst, n_freq, n_req);
+  if (work_bytes < need) {
+    char buf[160];
+    snprintf(buf, sizeof(buf), "ac measure: workspace of %lld bytes is too small, %lld needed (spicey_ac_measure_workspace_bytes)", (long long)work_bytes,
+             (long long)need);
+    g_err = buf;
+    return SPICEY_ERR_BAD_DESC;
+  }
+  int ncu = 0;
+  if (const int32_t rc = open_device(device, &ncu, g_err); rc != SPICEY_OK) return rc;
+  const hipError_t e = spicey_launch_ac_measure(device, n_inst, n_freq, d_v, n_v, d_i, n_i, table.data(), n_req, d_meas, d_work, (hipStream_t)stream);
+  if (e != hipSuccess) { g_err = std::string("spicey_launch_ac_measure: ") + hipGetErrorString(e); return SPICEY_ERR_HIP; }
+  return SPICEY_OK;
+}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Several devices behind one handle: instance shards, one SpiceyHandle per shard, host threads around the blocking runs.

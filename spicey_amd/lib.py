@@ -26,7 +26,9 @@ EXPORTS = ["spicey_create", "spicey_run", "spicey_run_device", "spicey_run_src",
            "spicey_multi_last_kernel_ms", "spicey_multi_last_error", "spicey_destroy_multi",
            "spicey_ac_create", "spicey_ac_run", "spicey_ac_get_info", "spicey_ac_last_kernel_ms", "spicey_ac_last_error", "spicey_ac_destroy",
            "spicey_format_tran", "spicey_to_precision6",
-           "spicey_measure_workspace_bytes", "spicey_measure_device", "spicey_run_measure", "spicey_last_measure_ms"]
+           "spicey_measure_workspace_bytes", "spicey_measure_device", "spicey_run_measure", "spicey_last_measure_ms",
+           "spicey_ac_last_inst_status", "spicey_ac_measure_workspace_bytes", "spicey_ac_measure_device", "spicey_ac_run_measure",
+           "spicey_ac_last_measure_ms"]
 
 
 class SpiceyNativeError(RuntimeError):
@@ -137,6 +139,16 @@ def load():
     L.spicey_run_measure.argtypes = [vp, C.c_int64, C.c_double, f64p, C.c_int32, vp, C.c_int32, f64p, i32p]
     L.spicey_last_measure_ms.restype = C.c_double
     L.spicey_last_measure_ms.argtypes = [vp]
+    L.spicey_ac_last_inst_status.restype = C.c_int32
+    L.spicey_ac_last_inst_status.argtypes = [vp, i32p, C.POINTER(C.c_int64)]
+    L.spicey_ac_measure_workspace_bytes.restype = C.c_int64
+    L.spicey_ac_measure_workspace_bytes.argtypes = [C.c_int32, C.c_int64, C.c_int32]
+    L.spicey_ac_measure_device.restype = C.c_int32
+    L.spicey_ac_measure_device.argtypes = [C.c_int32, C.c_int32, C.c_int64, vp, C.c_int32, vp, C.c_int32, vp, C.c_int32, vp, vp, C.c_int64, vp]
+    L.spicey_ac_run_measure.restype = C.c_int32
+    L.spicey_ac_run_measure.argtypes = [vp, C.c_int64, f64p, f64p, vp, C.c_int32, f64p]
+    L.spicey_ac_last_measure_ms.restype = C.c_double
+    L.spicey_ac_last_measure_ms.argtypes = [vp]
     _LIB = L
     return L
 
@@ -178,6 +190,32 @@ def measure_device(n_inst: int, n_points: int, dt: float, d_v: int, n_v: int, d_
     if rc != abi.OK:
         msg = L.spicey_last_error(None)
         err = SpiceyNativeError(f"spicey_measure_device failed ({rc}): {msg.decode() if msg else ''}")
+        err.status = rc
+        raise err
+
+
+def _ac_reqs(reqs) -> np.ndarray:
+    """A request list as one contiguous array of SpiceyAcMeasReq records (abi.AC_MEAS_REQ_DTYPE)."""
+    return np.ascontiguousarray(reqs, dtype=abi.AC_MEAS_REQ_DTYPE).reshape(-1)
+
+
+def ac_measure_workspace_bytes(n_inst: int, n_freq: int, n_req: int) -> int:
+    return load().spicey_ac_measure_workspace_bytes(n_inst, n_freq, n_req)
+
+
+def ac_measure_device(n_inst: int, n_freq: int, d_v: int, n_v: int, d_i: int, n_i: int, reqs, d_meas: int, d_work: int, work_bytes: int,
+                      device: int = 0, stream: int = 0) -> None:
+    """spicey_ac_measure_device: the reduction alone on raw device pointers (e.g. torch tensors' data_ptr()): d_v
+    [n_inst][n_freq][n_v] complex128, d_i likewise or 0, d_meas [n_inst][n_req][8], d_work of `work_bytes` >=
+    ac_measure_workspace_bytes(...).  Enqueued on `stream`, no synchronisation.  A refusal raises SpiceyNativeError whose
+    `status` is the library's code (abi.ERR_BAD_DESC for a bad request list)."""
+    L = load()
+    r = _ac_reqs(reqs)
+    rc = L.spicey_ac_measure_device(device, n_inst, n_freq, d_v or None, n_v, d_i or None, n_i, r.ctypes.data if len(r) else None, len(r),
+                                    d_meas or None, d_work or None, work_bytes, stream or None)
+    if rc != abi.OK:
+        msg = L.spicey_last_error(None)
+        err = SpiceyNativeError(f"spicey_ac_measure_device failed ({rc}): {msg.decode() if msg else ''}")
         err.status = rc
         raise err
 
@@ -518,7 +556,38 @@ class AcHandle:
         rc = self.L.spicey_ac_run(self.h, nf, _p(freqs, C.c_double), _p(ph.view(np.float64), C.c_double),
                                   _p(out_v.view(np.float64), C.c_double), _p(out_i.view(np.float64), C.c_double) if want_currents else None)
         detail = self.L.spicey_ac_last_error(self.h).decode() if rc != abi.OK else ""
-        return {"status": rc, "detail": detail, "out_v": out_v, "out_i": out_i, "kernel_ms": self.L.spicey_ac_last_kernel_ms(self.h)}
+        ist, first = self.inst_status(rc)
+        return {"status": rc, "detail": detail, "out_v": out_v, "out_i": out_i, "kernel_ms": self.L.spicey_ac_last_kernel_ms(self.h),
+                "inst_status": ist, "first_freq": first}
+
+    def inst_status(self, rc: int = abi.OK):
+        """(status[n_inst], first_freq[n_inst]) of the last sweep (spicey_ac_last_inst_status): per instance 0, or the code of
+        its lowest failing frequency index and that index (-1 when fine).  A sweep that was refused before its launch (`rc` is
+        that call's status) answers every instance with `rc`."""
+        st = np.zeros(self.flat.n_inst, np.int32)
+        first = np.full(self.flat.n_inst, -1, np.int64)
+        if self.L.spicey_ac_last_inst_status(self.h, _p(st, C.c_int32), _p(first, C.c_int64)) < 0:
+            if rc == abi.OK:
+                raise SpiceyNativeError("spicey_ac_last_inst_status: no sweep has run on this handle")
+            st[:] = rc
+        return st, first
+
+    def run_measure(self, freqs, vph, reqs) -> dict:
+        """spicey_ac_run_measure: the sweep of run() with its results kept on the device and reduced there; only `meas`
+        [n_inst][n_req][8] (include/spicey_hip.h) comes back, also after a failing sweep (`inst_status` names the instances
+        whose rows are undefined).  reqs: records of abi.AC_MEAS_REQ_DTYPE, columns as in this handle's out_v / out_i."""
+        f = self.flat
+        ni, nf = f.n_inst, len(freqs)
+        freqs = np.ascontiguousarray(freqs, dtype=np.float64)
+        ph = np.ascontiguousarray(np.broadcast_to(np.asarray(vph, np.complex128).reshape(-1, f.nV), (ni, f.nV)))
+        r = _ac_reqs(reqs)
+        meas = np.zeros((ni, len(r), 8))
+        rc = self.L.spicey_ac_run_measure(self.h, nf, _p(freqs, C.c_double), _p(ph.view(np.float64), C.c_double), r.ctypes.data if len(r) else None,
+                                          len(r), _p(meas, C.c_double))
+        detail = self.L.spicey_ac_last_error(self.h).decode() if rc != abi.OK else ""
+        ist, first = self.inst_status(rc)
+        return {"status": rc, "detail": detail, "meas": meas, "kernel_ms": self.L.spicey_ac_last_kernel_ms(self.h),
+                "measure_ms": self.L.spicey_ac_last_measure_ms(self.h), "inst_status": ist, "first_freq": first}
 
     def close(self) -> None:
         if getattr(self, "h", None):
@@ -544,6 +613,7 @@ class HipBackend:
         self.info: Optional[dict] = None
         self.group_retries = 0      # summed over this backend's runs (group mode; 0 when healthy)
         self.group_stale_polls = 0
+        self.ac_launches: list = []  # instances of every AC handle this backend opened (one handle = one launch)
 
     def run(self, flat: abi.FlatCircuit, steps: int, dt: float, src: np.ndarray, want_currents: bool = True,
             want_iters: bool = True) -> dict:
@@ -573,9 +643,21 @@ class HipBackend:
 
     def run_ac(self, flat: abi.FlatCircuit, freqs, vph, want_currents: bool = True) -> dict:
         h = AcHandle(flat, device=self.kw["device"], threads=self.kw["threads"], force_global=self.kw["force_global"])
+        self.ac_launches.append(flat.n_inst)
         try:
             self.info = h.info()
             return h.run(freqs, vph, want_currents)
+        finally:
+            h.close()
+
+    def run_ac_measure(self, flat: abi.FlatCircuit, freqs, vph, reqs) -> dict:
+        """AcHandle.run_measure on a handle of its own: the sweep's results never leave the device."""
+        h = AcHandle(flat, device=self.kw["device"], threads=self.kw["threads"], force_global=self.kw["force_global"])
+        self.ac_launches.append(flat.n_inst)
+        try:
+            res = h.run_measure(freqs, vph, reqs)
+            self.info = h.info()
+            return res
         finally:
             h.close()
 
@@ -589,12 +671,24 @@ class HipAcExactBackend:
     def __init__(self, device: int = 0, threads: int = 0, force_global: bool = False):
         self.kw = dict(device=device, threads=threads, force_global=force_global)
         self.info: Optional[dict] = None
+        self.ac_launches: list = []  # instances of every AC handle this backend opened (one handle = one launch)
 
     def run_ac(self, flat: abi.FlatCircuit, freqs, vph, want_currents: bool = True) -> dict:
         h = AcHandle(flat, interpreter=3, **self.kw)
+        self.ac_launches.append(flat.n_inst)
         try:
             self.info = h.info()
             res = h.run(freqs, vph, want_currents)
+            self.info = h.info()
+            return res
+        finally:
+            h.close()
+
+    def run_ac_measure(self, flat: abi.FlatCircuit, freqs, vph, reqs) -> dict:
+        h = AcHandle(flat, interpreter=3, **self.kw)
+        self.ac_launches.append(flat.n_inst)
+        try:
+            res = h.run_measure(freqs, vph, reqs)
             self.info = h.info()
             return res
         finally:

@@ -94,8 +94,9 @@ def _element_names(ckt: ParsedCircuit) -> List[str]:
             + [e.name for e in ckt.S if e.model is not None] + [e.name for e in ckt.D if e.model is not None])
 
 
-def _parse_signal(ckt: ParsedCircuit, text: str) -> Tuple[int, int, int]:
-    """(signal, a, b): signal 0 -> node ids a and b (b = 0: none); signal 1 -> out_i column a."""
+def _parse_signal(ckt: ParsedCircuit, text: str, elements: Optional[List[str]] = None) -> Tuple[int, int, int]:
+    """(signal, a, b): signal 0 -> node ids a and b (b = 0: none); signal 1 -> out_i column a.  elements: the names of the
+    out_i columns (default: the transient's recording order)."""
     m = _SIGNAL.match(text)
     if not m:
         raise ValueError(f"measure: cannot read the signal {text!r} (v(node), v(node,node) or i(element))")
@@ -103,7 +104,7 @@ def _parse_signal(ckt: ParsedCircuit, text: str) -> Tuple[int, int, int]:
     if kind == "i":
         if b is not None:
             raise ValueError(f"measure: {text!r}: i() takes one element name")
-        hits = [k for k, nm in enumerate(_element_names(ckt)) if nm.upper() == a.upper()]
+        hits = [k for k, nm in enumerate(_element_names(ckt) if elements is None else elements) if nm.upper() == a.upper()]
         if not hits:
             raise ValueError(f"measure: {text!r}: no element named {a!r} records a current")
         if len(hits) > 1:
