@@ -23,7 +23,7 @@ from typing import Callable, Dict, List, Optional, Sequence
 import numpy as np
 
 from . import abi
-from .ac import (ERR_COMPLEX_DIV, SingularComplexMatrixError, _check_resistors, _default_backend, _exact_backend,
+from .ac import (ERR_COMPLEX_DIV, SingularComplexMatrixError, _check_resistors,
                  ac_result, buildFrequencyArray, source_phasors)
 from .netlist import ParsedCircuit
 
@@ -101,8 +101,6 @@ def batch_backend(backend, exact_order: bool, device: int, who: str):
         raise ValueError(f"{who}: pass either backend= or exact_order=True, not both")
     if backend is not None:
         return backend
-    if device == 0:
-        return _exact_backend() if exact_order else _default_backend()
     from .lib import HipAcExactBackend, HipBackend
 
     return HipAcExactBackend(device=device) if exact_order else HipBackend(device=device)

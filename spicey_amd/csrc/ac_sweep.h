@@ -1,5 +1,5 @@
-// ac_sweep.h — what the two AC engines (ac.hip, ac_exact.hip) hand to the entry points that follow a sweep: the results
-// still on the device, the status word of every (instance, frequency) slot, and the per-instance summary of
+// ac_sweep.h — what a sweep of either AC engine (ac_abi.cpp) hands to the entry points that follow it: the results still
+// on the device, the status word of every (instance, frequency) slot, and the per-instance summary of
 // spicey_ac_last_inst_status.
 #pragma once
 #include <stdint.h>

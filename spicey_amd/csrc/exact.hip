@@ -77,10 +77,7 @@ __global__ void __launch_bounds__(1024) spicey_exact_kernel(const SpiceyExactPro
 }  // namespace
 
 hipError_t spicey_launch_exact(const SpiceyExactProg *P, const SpiceyRun *R, int grid, int threads, size_t lds, hipStream_t st) {
-  if (lds > 48 * 1024) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(spicey_exact_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
+  if (const hipError_t e = spicey_allow_dyn_lds(spicey_exact_kernel, lds); e != hipSuccess) return e;
   hipLaunchKernelGGL(spicey_exact_kernel, dim3(grid), dim3(threads), lds, st, P, R, lds > 0 ? 1 : 0);
   return hipGetLastError();
 }

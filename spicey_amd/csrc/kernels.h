@@ -1,8 +1,9 @@
-// kernels.h — host-callable launchers of kernels.hip
+// kernels.h — host-callable launchers of kernels.hip, exact.hip, ac.hip and ac_exact.hip
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <stddef.h>
 
+#include "devbuf.h"
 #include "launch_plan.h"
 #include "program.h"
 
@@ -25,14 +26,22 @@ int spicey_grp_blocks_per_cu(const SpiceyProg &P, int K, int threads);  // occup
 struct SpiceyExactProg;
 hipError_t spicey_launch_exact(const SpiceyExactProg *P, const SpiceyRun *R, int grid, int threads, size_t lds, hipStream_t st);
 
-// reference-order AC engine (ac_exact.hip): one workgroup per (instance, frequency) slot.  The spicey_ac_* entry points of
-// ac.hip hand a handle created with SpiceyOptions.interpreter = 3 to these; `err` / spicey_ac_exact_error carry the message.
-struct SpiceyAcExact;
-int32_t spicey_ac_exact_create(const SpiceyDesc *desc, const SpiceyOptions &opt, SpiceyAcExact **out, std::string &err);
-struct SpiceyAcSweep;
-int32_t spicey_ac_exact_sweep(SpiceyAcExact *x, int64_t n_freq, const double *freqs, const double *vph, bool want_i, SpiceyAcSweep &o, double *ms);
-hipStream_t spicey_ac_exact_stream(const SpiceyAcExact *x);
-void spicey_ac_exact_dims(const SpiceyAcExact *x, int32_t *n_inst, int32_t *n_out, int32_t *n_cur, int32_t *n_v);
-void spicey_ac_exact_info(const SpiceyAcExact *x, SpiceyInfo *info);
-const char *spicey_ac_exact_error(const SpiceyAcExact *x);
-void spicey_ac_exact_destroy(SpiceyAcExact *x);
+// AC sweep (ac.hip), one workgroup per (instance, frequency) slot from R.slot_base on: lds_bytes = dynamic LDS of the
+// workspace, 0 = each workgroup's slice of R.gW
+struct SpiceyAcRun;
+struct SpiceyCx;
+hipError_t spicey_launch_ac(const SpiceyProg &P, const SpiceyAcRun &R, int grid, int threads, size_t lds_bytes, hipStream_t st);
+// resident sweep: n_inst * n_chunk workgroups of <= 512 threads, each running frequencies c, c + n_chunk, ... of its instance
+// with SPICEY_AC_RMAX task records and the stamp parts of SPICEY_AC_NSE entries per thread in registers (256 VGPRs, no spills)
+#define SPICEY_AC_RMAX 12
+#define SPICEY_AC_NSE 10
+hipError_t spicey_launch_ac_resident(const SpiceyProg &P, const SpiceyResident &Q, const SpiceyAcRun &R, int n_chunk, int threads, size_t lds_bytes, hipStream_t st);
+// dense partial-pivoting re-solve of the `count` slots listed in d_slots (P, R in DEVICE memory; n = P->n): Ws [count][nW]
+// sparse scratch, A [count][n (n + 1)]
+hipError_t spicey_launch_ac_dense(const SpiceyProg *P, const SpiceyAcRun *R, int n, const int64_t *d_slots, int count, SpiceyCx *Ws, SpiceyCx *A, hipStream_t st);
+
+// reference-order AC engine (ac_exact.hip): one workgroup per (instance, frequency) slot from slot_base on; P, R in DEVICE
+// memory; lds = dynamic LDS bytes, 0 = the workspace is R->gW
+struct SpiceyAcExactProg;
+struct SpiceyAcExactRun;
+hipError_t spicey_launch_ac_exact(const SpiceyAcExactProg *P, const SpiceyAcExactRun *R, int64_t slot_base, int grid, int threads, size_t lds, hipStream_t st);

@@ -557,10 +557,7 @@ __global__ void __launch_bounds__(MAXT, MINW) spicey_tran_kernel_v2(const Spicey
 template <int K, int RMAX, int NSV, int NEL, int MAXT, int MINW, bool HYB = false, int PT = 0>
 hipError_t launch_v2_t(const SpiceyProg *P, const SpiceyResident *Q, const SpiceyRun *R, int grid, int threads, size_t lds, hipStream_t st) {
   auto kern = spicey_tran_kernel_v2<K, RMAX, NSV, NEL, MAXT, MINW, HYB, PT>;
-  if (lds > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
+  if (const hipError_t e = spicey_allow_dyn_lds(kern, lds); e != hipSuccess) return e;
   hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, st, P, Q, R);
   return hipGetLastError();
 }
@@ -569,10 +566,7 @@ template <int K, bool LDS, bool FRONTS = false>
 hipError_t launch_t(const SpiceyProg &P, const SpiceyRun &R, int grid, int threads, size_t lds, hipStream_t st) {
   auto kern = spicey_tran_kernel<K, LDS, FRONTS>;
   if (FRONTS && threads > 512) return hipErrorInvalidValue;
-  if (lds > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
+  if (const hipError_t e = spicey_allow_dyn_lds(kern, lds); e != hipSuccess) return e;
   hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, st, P, R);
   return hipGetLastError();
 }
@@ -583,10 +577,7 @@ template <int K, bool FRONTS>
 static hipError_t launch_grp_t(const SpiceyProg &P, const SpiceyRun &R, int grid, int threads, size_t lds, hipStream_t st, int *blocks_per_cu = nullptr) {
   auto kern = spicey_tran_kernel_grp<K, FRONTS>;
   if (FRONTS && threads > 512) return hipErrorInvalidValue;
-  if (lds > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
+  if (const hipError_t e = spicey_allow_dyn_lds(kern, lds); e != hipSuccess) return e;
   if (blocks_per_cu)  // residency query only (spicey_grp_blocks_per_cu)
     return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, reinterpret_cast<const void *>(kern), threads, lds);
   hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, st, P, R);

@@ -90,10 +90,7 @@ struct SpiceyHandle {
   bool gated = false;     // this handle is counted in its device's group-mode handles (DeviceGate)
   DevBuf<double> d_gstat, d_statv, d_rcoef, d_gW, d_dpar;
   DevBuf<int32_t> d_status; DevBuf<unsigned long long> d_solves, d_prof;
-  hipStream_t stream = nullptr;  // owned stream for spicey_run
   hipStream_t last_stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  hipEvent_t mev0 = nullptr, mev1 = nullptr;  // around the reduction of spicey_run_measure (created on first use)
   double last_measure_ms = 0.0;
   bool pending = false;
   int64_t last_solves = 0;
@@ -103,6 +100,7 @@ struct SpiceyHandle {
   std::vector<int32_t> last_status;
   bool last_structural = false;
   std::string err;
+  StreamTimers q;  // the owned stream of spicey_run and its events (last: they go before the device buffers)
 };
 
 static thread_local std::string g_err;  // message of the calling thread's last failed spicey_create (no handle to hang it on)
@@ -208,23 +206,7 @@ extern "C" void spicey_destroy(SpiceyHandle *h) {
     std::lock_guard<std::mutex> lk(g.mu);
     g.group_handles--;
   }
-  if (h->ev0) (void)hipEventDestroy(h->ev0);
-  if (h->ev1) (void)hipEventDestroy(h->ev1);
-  if (h->mev0) (void)hipEventDestroy(h->mev0);
-  if (h->mev1) (void)hipEventDestroy(h->mev1);
-  if (h->stream) (void)hipStreamDestroy(h->stream);
-  delete h;  // (and with it every device buffer)
-}
-
-// spicey_plan's view of the device: ordinal check, selection and CU count (after the descriptor checks), and the group
-// kernel's occupancy
-static int32_t open_device(int device, int *ncu, std::string &err) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { err = "no HIP device: libspicey_hip has no CPU path"; return SPICEY_ERR_NO_DEVICE; }
-  if (device < 0 || device >= ndev) { err = "device ordinal out of range"; return SPICEY_ERR_BAD_DESC; }
-  if (hipSetDevice(device) != hipSuccess) { err = "hipSetDevice failed"; return SPICEY_ERR_HIP; }
-  (void)hipDeviceGetAttribute(ncu, hipDeviceAttributeMultiprocessorCount, device);
-  return SPICEY_OK;
+  delete h;  // (events and stream, then every device buffer)
 }
 
 // per-instance element values and the state (live and as the descriptor carried it)
@@ -242,14 +224,6 @@ static int32_t upload_values(SpiceyHandle *h, const SpiceyDesc *desc) {
   HIPCHK(h, dev_upload(h->d_Dn, ni * P.nD, desc->D_n));
   HIPCHK(h, upload_state(h->state, desc, P, ni));
   HIPCHK(h, upload_state(h->state0, desc, P, ni));
-  return SPICEY_OK;
-}
-
-static int32_t create_stream(SpiceyHandle *h) {
-  if (hipStreamCreate(&h->stream) != hipSuccess || hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess) {
-    h->err = "stream/event creation failed";
-    return SPICEY_ERR_HIP;
-  }
   return SPICEY_OK;
 }
 
@@ -277,7 +251,7 @@ static int32_t allocate_exact(SpiceyHandle *h, const SpiceyDesc *desc) {
       return SPICEY_ERR_HIP;
     }
   }
-  return create_stream(h);
+  return h->q.create(h);
 }
 
 // the device side of a planned handle: program, argument structs, per-instance values and state, workspaces, stream, events
@@ -328,7 +302,7 @@ static int32_t allocate(SpiceyHandle *h, const SpiceyDesc *desc) {
   }
   if (h->opt.diagnostics & 1) HIPCHK(h, dev_upload(h->d_skip, ni));
   if ((h->opt.diagnostics & 2) && P.nD > 0) HIPCHK(h, dev_upload(h->d_linvd, ni * P.nD));
-  return create_stream(h);
+  return h->q.create(h);
 }
 
 extern "C" int32_t spicey_create(const SpiceyDesc *desc, const SpiceyOptions *opt, SpiceyHandle **out) {
@@ -339,7 +313,7 @@ extern "C" int32_t spicey_create(const SpiceyDesc *desc, const SpiceyOptions *op
   h->knobs = spicey_read_knobs();
   h->device = h->opt.device;
   Roctx range_create("spicey_create");
-  const PlanDevice dev{open_device, spicey_grp_blocks_per_cu};
+  const PlanDevice dev{spicey_open_device, spicey_grp_blocks_per_cu};
   int32_t rc = spicey_plan(desc, h->opt, h->knobs, dev, h->hp, h->hres, h->plan, h->err);
   if (rc == SPICEY_OK && h->plan.G > 1) {
     // the first group-mode handle on a device drains it once: launches enqueued before were not recorded (DeviceGate)
@@ -367,7 +341,7 @@ static int32_t enqueue_kernel(SpiceyHandle *h, const SpiceyRun &R, hipStream_t s
   const bool group = h->plan.G > 1;
   int slot = -1;
   HIPCHK(h, gate_before_launch(g, group, st, &slot));
-  HIPCHK(h, hipEventRecord(h->ev0, st));  // (argument upload, flag resets and admission waits stay outside the timed kernel)
+  HIPCHK(h, hipEventRecord(h->q.ev0, st));  // (argument upload, flag resets and admission waits stay outside the timed kernel)
   if (h->plan.interp == 3) {
     HIPCHK(h, spicey_launch_exact(h->d_xprog, h->d_Rstruct, h->plan.grid, h->plan.T, h->plan.lds ? h->plan.lds_bytes : 0, st));
   } else if (h->plan.interp == 2) {
@@ -377,7 +351,7 @@ static int32_t enqueue_kernel(SpiceyHandle *h, const SpiceyRun &R, hipStream_t s
   } else {
     HIPCHK(h, spicey_launch_tran(h->dprog, R, h->plan.K, h->plan.lds, h->plan.grid, h->plan.T, st));
   }
-  HIPCHK(h, hipEventRecord(h->ev1, st));
+  HIPCHK(h, hipEventRecord(h->q.ev1, st));
   HIPCHK(h, gate_after_launch(g, group, st, slot));
   return SPICEY_OK;
 }
@@ -402,17 +376,26 @@ static void forget_last_run(SpiceyHandle *h) {
   h->last_structural = false;
 }
 
+// The refusals of every transient entry point, in their order: the run arguments (out: the call's result buffer, src: its
+// source table), then a matrix that is singular by its structure (every instance then fails: spicey_last_inst_status).
+static int32_t check_run_args(SpiceyHandle *h, int64_t steps, const void *out, const void *src, int32_t src_per_inst) {
+  forget_last_run(h);
+  if (steps < 0 || !out || (h->hp.hdr.nV > 0 && !src)) { h->err = "bad run arguments"; return SPICEY_ERR_BAD_DESC; }
+  if (src_per_inst != 0 && src_per_inst != 1) { h->err = "src_per_inst must be 0 (one shared table) or 1 (one table per instance)"; return SPICEY_ERR_BAD_DESC; }
+  return SPICEY_OK;
+}
+static int32_t check_structure(SpiceyHandle *h) {
+  if (!h->hp.structurally_singular) return SPICEY_OK;
+  h->err = "singular at inst 0 step 0 iter 0 (structurally singular matrix)";
+  h->last_structural = true;
+  return SPICEY_ERR_SINGULAR;
+}
+
 extern "C" int32_t spicey_run_device_src(SpiceyHandle *h, int64_t steps, double dt, const double *d_src_table, int32_t src_per_inst,
                                          double *d_out_v, double *d_out_i, int32_t *d_iters, void *stream) {
   if (!h) return SPICEY_ERR_BAD_DESC;
-  forget_last_run(h);
-  if (steps < 0 || !d_out_v || (h->hp.hdr.nV > 0 && !d_src_table)) { h->err = "bad run arguments"; return SPICEY_ERR_BAD_DESC; }
-  if (src_per_inst != 0 && src_per_inst != 1) { h->err = "src_per_inst must be 0 (one shared table) or 1 (one table per instance)"; return SPICEY_ERR_BAD_DESC; }
-  if (h->hp.structurally_singular) {
-    h->err = "singular at inst 0 step 0 iter 0 (structurally singular matrix)";
-    h->last_structural = true;
-    return SPICEY_ERR_SINGULAR;
-  }
+  if (const int32_t rc0 = check_run_args(h, steps, d_out_v, d_src_table, src_per_inst); rc0 != SPICEY_OK) return rc0;
+  if (const int32_t rc0 = check_structure(h); rc0 != SPICEY_OK) return rc0;
   HIPCHK(h, hipSetDevice(h->device));
   hipStream_t st = (hipStream_t)stream;
   // a run still in flight on ANOTHER stream: this launch would reset status words, barrier words and front flags under
@@ -507,8 +490,7 @@ extern "C" int32_t spicey_sync(SpiceyHandle *h) {
   for (int attempt = 0;; attempt++) {
     HIPCHK(h, hipStreamSynchronize(h->last_stream));
     h->pending = false;
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, h->ev0, h->ev1) == hipSuccess) h->last_ms = ms;
+    StreamTimers::elapsed(h->q.ev0, h->q.ev1, &h->last_ms);
     HIPCHK(h, hipMemcpy(status.data(), h->d_status, status.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
     HIPCHK(h, hipMemcpy(solves.data(), h->d_solves, solves.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     h->last_status = status;
@@ -588,40 +570,52 @@ extern "C" int32_t spicey_last_inst_status(SpiceyHandle *h, int32_t *status) {
   return bad;
 }
 
+// The device side of a run on host buffers (run_host, spicey_run_measure): the source table up on the handle's stream,
+// the buffers the run records into, and the way back.
+struct HostRun {
+  size_t np = 0, ni = 0;
+  DevBuf<double> d_src, d_v, d_i;
+  DevBuf<int32_t> d_it;
+  int32_t stage(SpiceyHandle *h, int64_t steps, const double *src_table, int32_t src_per_inst, bool want_i, bool want_iters) {
+    const SpiceyProg &P = h->hp.hdr;
+    np = (size_t)steps + 1, ni = (size_t)h->plan.n_inst;
+    const size_t ntab = src_per_inst ? ni : 1;
+    HIPCHK(h, d_src.alloc(std::max<size_t>(ntab * np * P.nV, 1)));
+    if (P.nV) HIPCHK(h, hipMemcpyAsync(d_src, src_table, ntab * np * P.nV * sizeof(double), hipMemcpyHostToDevice, h->q.stream));
+    HIPCHK(h, d_v.alloc(std::max<size_t>(ni * np * P.nOut, 1)));
+    if (want_i) HIPCHK(h, d_i.alloc(std::max<size_t>(ni * np * P.nCur, 1)));
+    if (want_iters) HIPCHK(h, d_it.alloc(ni * np));
+    return SPICEY_OK;
+  }
+  // (blocking copies behind a finished run; null: not wanted)
+  int32_t copy_out(SpiceyHandle *h, double *out_v, double *out_i, int32_t *iters) const {
+    const SpiceyProg &P = h->hp.hdr;
+    if (out_v) HIPCHK(h, hipMemcpy(out_v, d_v, ni * np * P.nOut * sizeof(double), hipMemcpyDeviceToHost));
+    if (out_i) HIPCHK(h, hipMemcpy(out_i, d_i, ni * np * P.nCur * sizeof(double), hipMemcpyDeviceToHost));
+    if (iters) HIPCHK(h, hipMemcpy(iters, d_it, ni * np * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return SPICEY_OK;
+  }
+};
+
 // keep_partial: the results also come back after SPICEY_ERR_SINGULAR (spicey_run_src: the instances that finished are complete)
 static int32_t run_host(SpiceyHandle *h, int64_t steps, double dt, const double *src_table, int32_t src_per_inst, double *out_v,
                         double *out_i, int32_t *iters, bool keep_partial) {
   if (!h) return SPICEY_ERR_BAD_DESC;
-  forget_last_run(h);
-  if (steps < 0 || !out_v || (h->hp.hdr.nV > 0 && !src_table)) { h->err = "bad run arguments"; return SPICEY_ERR_BAD_DESC; }
-  if (src_per_inst != 0 && src_per_inst != 1) { h->err = "src_per_inst must be 0 (one shared table) or 1 (one table per instance)"; return SPICEY_ERR_BAD_DESC; }
-  if (h->hp.structurally_singular) {
-    h->err = "singular at inst 0 step 0 iter 0 (structurally singular matrix)";
-    h->last_structural = true;
-    return SPICEY_ERR_SINGULAR;
-  }
+  if (const int32_t rc0 = check_run_args(h, steps, out_v, src_table, src_per_inst); rc0 != SPICEY_OK) return rc0;
+  if (const int32_t rc0 = check_structure(h); rc0 != SPICEY_OK) return rc0;
   HIPCHK(h, hipSetDevice(h->device));
   Roctx range_run("spicey_run");
-  const SpiceyProg &P = h->hp.hdr;
-  const size_t np = (size_t)steps + 1, ni = (size_t)h->plan.n_inst, ntab = src_per_inst ? ni : 1;
-  DevBuf<double> d_src, d_v, d_i;
-  DevBuf<int32_t> d_it;
-  HIPCHK(h, d_src.alloc(std::max<size_t>(ntab * np * P.nV, 1)));
-  if (P.nV) HIPCHK(h, hipMemcpyAsync(d_src, src_table, ntab * np * P.nV * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, d_v.alloc(std::max<size_t>(ni * np * P.nOut, 1)));
-  if (out_i) HIPCHK(h, d_i.alloc(std::max<size_t>(ni * np * P.nCur, 1)));
-  if (iters) HIPCHK(h, d_it.alloc(ni * np));
+  HostRun r;
+  if (const int32_t rc0 = r.stage(h, steps, src_table, src_per_inst, out_i != nullptr, iters != nullptr); rc0 != SPICEY_OK) return rc0;
   int32_t rc;
   {
     Roctx range_kernel("spicey_run:kernel");
-    rc = spicey_run_device_src(h, steps, dt, d_src, src_per_inst, d_v, d_i, d_it, h->stream);
+    rc = spicey_run_device_src(h, steps, dt, r.d_src, src_per_inst, r.d_v, r.d_i, r.d_it, h->q.stream);
     if (rc == SPICEY_OK) rc = spicey_sync(h);
   }
   if (rc == SPICEY_OK || (keep_partial && rc == SPICEY_ERR_SINGULAR)) {
     Roctx range_copy("spicey_run:results");
-    HIPCHK(h, hipMemcpy(out_v, d_v, ni * np * P.nOut * sizeof(double), hipMemcpyDeviceToHost));
-    if (out_i) HIPCHK(h, hipMemcpy(out_i, d_i, ni * np * P.nCur * sizeof(double), hipMemcpyDeviceToHost));
-    if (iters) HIPCHK(h, hipMemcpy(iters, d_it, ni * np * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (const int32_t rc0 = r.copy_out(h, out_v, out_i, iters); rc0 != SPICEY_OK) return rc0;
   }
   return rc;
 }
@@ -741,30 +735,16 @@ extern "C" int64_t spicey_measure_workspace_bytes(int32_t n_inst, int64_t n_poin
   return spicey_meas_workspace_bytes(n_inst, n_points, n_req);
 }
 
-// every refusal of a measurement call: counts, buffers, the request list (-> the kernels' sorted table), the workspace size
-static int32_t measure_plan(int32_t n_inst, int64_t n_points, bool have_v, int32_t n_v, bool have_i, int32_t n_i, const SpiceyMeasReq *reqs, int32_t n_req,
-                            bool have_out, int64_t work_bytes, std::vector<SpiceyMeasDevReq> &table, std::string &err) {
-  if (n_inst <= 0 || n_v < 0 || n_i < 0 || !have_out) { err = "measure: bad arguments (n_inst >= 1, result and workspace buffers)"; return SPICEY_ERR_BAD_DESC; }
-  if (!spicey_meas_plan(reqs, n_req, n_points, have_v ? n_v : 0, n_i, have_i, table, err)) return SPICEY_ERR_BAD_DESC;
-  const int64_t need = spicey_meas_workspace_bytes(n_inst, n_points, n_req);
-  if (work_bytes < need) {
-    char buf[160];
-    snprintf(buf, sizeof(buf), "measure: workspace of %lld bytes is too small, %lld needed (spicey_measure_workspace_bytes)", (long long)work_bytes, (long long)need);
-    err = buf;
-    return SPICEY_ERR_BAD_DESC;
-  }
-  return SPICEY_OK;
-}
-
 extern "C" int32_t spicey_measure_device(int32_t device, int32_t n_inst, int64_t n_points, double dt, const double *d_v, int32_t n_v, const double *d_i,
                                          int32_t n_i, const SpiceyMeasReq *reqs, int32_t n_req, double *d_meas, void *d_work, int64_t work_bytes,
                                          void *stream) {
   // (the call is judged before the device is touched: a refusal launches nothing)
   std::vector<SpiceyMeasDevReq> table;
-  if (const int32_t rc = measure_plan(n_inst, n_points, d_v != nullptr, n_v, d_i != nullptr, n_i, reqs, n_req, d_meas && d_work, work_bytes, table, g_err); rc != SPICEY_OK)
+  if (const int32_t rc = spicey_judge_measure("measure", spicey_meas_plan, spicey_meas_workspace_bytes, n_inst, n_points, d_v != nullptr, n_v, d_i != nullptr, n_i, reqs,
+                                              n_req, d_meas && d_work, work_bytes, table, g_err); rc != SPICEY_OK)
     return rc;
   int ncu = 0;
-  if (const int32_t rc = open_device(device, &ncu, g_err); rc != SPICEY_OK) return rc;
+  if (const int32_t rc = spicey_open_device(device, &ncu, g_err); rc != SPICEY_OK) return rc;
   const hipError_t e = spicey_launch_measure(device, n_inst, n_points, dt, d_v, n_v, d_i, n_i, table.data(), n_req, d_meas, d_work, (hipStream_t)stream);
   if (e != hipSuccess) { g_err = std::string("spicey_launch_measure: ") + hipGetErrorString(e); return SPICEY_ERR_HIP; }
   return SPICEY_OK;
@@ -773,57 +753,50 @@ extern "C" int32_t spicey_measure_device(int32_t device, int32_t n_inst, int64_t
 extern "C" int32_t spicey_run_measure(SpiceyHandle *h, int64_t steps, double dt, const double *src_table, int32_t src_per_inst, const SpiceyMeasReq *reqs,
                                       int32_t n_req, double *meas, int32_t *iters) {
   if (!h) return SPICEY_ERR_BAD_DESC;
-  forget_last_run(h);
-  if (steps < 0 || !meas || (h->hp.hdr.nV > 0 && !src_table)) { h->err = "bad run arguments"; return SPICEY_ERR_BAD_DESC; }
-  if (src_per_inst != 0 && src_per_inst != 1) { h->err = "src_per_inst must be 0 (one shared table) or 1 (one table per instance)"; return SPICEY_ERR_BAD_DESC; }
+  if (const int32_t rc0 = check_run_args(h, steps, meas, src_table, src_per_inst); rc0 != SPICEY_OK) return rc0;
   const SpiceyProg &P = h->hp.hdr;
-  const size_t np = (size_t)steps + 1, ni = (size_t)h->plan.n_inst, ntab = src_per_inst ? ni : 1;
+  const int32_t ni = h->plan.n_inst;
+  const int64_t np = steps + 1;
   // (a refused request list runs nothing; the buffers are this call's own)
-  const int64_t work_bytes = spicey_meas_workspace_bytes((int32_t)ni, (int64_t)np, n_req);
+  const int64_t work_bytes = spicey_meas_workspace_bytes(ni, np, n_req);
   std::vector<SpiceyMeasDevReq> table;
-  if (const int32_t rc = measure_plan((int32_t)ni, (int64_t)np, true, P.nOut, true, P.nCur, reqs, n_req, true, work_bytes, table, h->err); rc != SPICEY_OK) return rc;
+  if (const int32_t rc0 = spicey_judge_measure("measure", spicey_meas_plan, spicey_meas_workspace_bytes, ni, np, true, P.nOut, true, P.nCur, reqs, n_req, true,
+                                               work_bytes, table, h->err); rc0 != SPICEY_OK)
+    return rc0;
   bool need_i = false;
   for (const SpiceyMeasDevReq &q : table) need_i = need_i || q.signal == 1;
-  if (h->hp.structurally_singular) {
-    h->err = "singular at inst 0 step 0 iter 0 (structurally singular matrix)";
-    h->last_structural = true;
-    return SPICEY_ERR_SINGULAR;
-  }
+  if (const int32_t rc0 = check_structure(h); rc0 != SPICEY_OK) return rc0;
   HIPCHK(h, hipSetDevice(h->device));
   Roctx range_run("spicey_run_measure");
-  if (!h->mev0) HIPCHK(h, hipEventCreate(&h->mev0));
-  if (!h->mev1) HIPCHK(h, hipEventCreate(&h->mev1));
-  DevBuf<double> d_src, d_v, d_i, d_meas;
-  DevBuf<int32_t> d_it;
+  HIPCHK(h, h->q.want_measure_events());
+  HostRun r;
+  DevBuf<double> d_meas;
   DevBuf<uint8_t> d_work;
-  HIPCHK(h, d_src.alloc(std::max<size_t>(ntab * np * P.nV, 1)));
-  if (P.nV) HIPCHK(h, hipMemcpyAsync(d_src, src_table, ntab * np * P.nV * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, d_v.alloc(std::max<size_t>(ni * np * P.nOut, 1)));
-  if (need_i) HIPCHK(h, d_i.alloc(std::max<size_t>(ni * np * P.nCur, 1)));  // (no current request: the run records no currents)
-  if (iters) HIPCHK(h, d_it.alloc(ni * np));
-  HIPCHK(h, d_meas.alloc(ni * (size_t)n_req * 8));
+  // (no current request: the run records no currents)
+  if (const int32_t rc0 = r.stage(h, steps, src_table, src_per_inst, need_i, iters != nullptr); rc0 != SPICEY_OK) return rc0;
+  HIPCHK(h, d_meas.alloc((size_t)ni * (size_t)n_req * 8));
   HIPCHK(h, d_work.alloc((size_t)work_bytes));
   h->last_measure_ms = 0.0;
-  int32_t rc = spicey_run_device_src(h, steps, dt, d_src, src_per_inst, d_v, d_i, d_it, h->stream);
+  hipStream_t st = h->q.stream;
+  int32_t rc = spicey_run_device_src(h, steps, dt, r.d_src, src_per_inst, r.d_v, r.d_i, r.d_it, st);
   if (rc != SPICEY_OK) return rc;
   auto reduce = [&]() {
-    hipError_t e = hipEventRecord(h->mev0, h->stream);
-    if (e == hipSuccess) e = spicey_launch_measure(h->device, (int32_t)ni, (int64_t)np, dt, d_v, P.nOut, d_i, P.nCur, table.data(), n_req, d_meas, d_work, h->stream);
-    if (e == hipSuccess) e = hipEventRecord(h->mev1, h->stream);
+    hipError_t e = hipEventRecord(h->q.mev0, st);
+    if (e == hipSuccess) e = spicey_launch_measure(h->device, ni, np, dt, r.d_v, P.nOut, r.d_i, P.nCur, table.data(), n_req, d_meas, d_work, st);
+    if (e == hipSuccess) e = hipEventRecord(h->q.mev1, st);
     return e;
   };
   const int retries = h->group_retries;
   hipError_t e = reduce();
   rc = spicey_sync(h);  // (the stream's end: the transient's status, with the reduction behind it; also before the buffers go)
   // (group mode with group_retry: spicey_sync repeated the transient behind the reduction, so the reduction runs again)
-  if (e == hipSuccess && h->group_retries != retries && rc == SPICEY_OK && (e = reduce()) == hipSuccess) e = hipStreamSynchronize(h->stream);
+  if (e == hipSuccess && h->group_retries != retries && rc == SPICEY_OK && (e = reduce()) == hipSuccess) e = hipStreamSynchronize(st);
   if (e != hipSuccess) { h->err = std::string("spicey_launch_measure: ") + hipGetErrorString(e); return SPICEY_ERR_HIP; }
   if (rc == SPICEY_OK || rc == SPICEY_ERR_SINGULAR) {
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, h->mev0, h->mev1) == hipSuccess) h->last_measure_ms = ms;
+    StreamTimers::elapsed(h->q.mev0, h->q.mev1, &h->last_measure_ms);
     Roctx range_copy("spicey_run_measure:results");
-    HIPCHK(h, hipMemcpy(meas, d_meas, ni * (size_t)n_req * 8 * sizeof(double), hipMemcpyDeviceToHost));
-    if (iters) HIPCHK(h, hipMemcpy(iters, d_it, ni * np * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(meas, d_meas, (size_t)ni * (size_t)n_req * 8 * sizeof(double), hipMemcpyDeviceToHost));
+    if (const int32_t rc0 = r.copy_out(h, nullptr, nullptr, iters); rc0 != SPICEY_OK) return rc0;
   }
   return rc;
 }
@@ -838,22 +811,12 @@ extern "C" int64_t spicey_ac_measure_workspace_bytes(int32_t n_inst, int64_t n_f
 extern "C" int32_t spicey_ac_measure_device(int32_t device, int32_t n_inst, int64_t n_freq, const double *d_v, int32_t n_v, const double *d_i, int32_t n_i,
                                             const SpiceyAcMeasReq *reqs, int32_t n_req, double *d_meas, void *d_work, int64_t work_bytes, void *stream) {
   // (the call is judged before the device is touched: a refusal launches nothing)
-  if (n_inst <= 0 || n_v < 0 || n_i < 0 || !d_meas || !d_work) {
-    g_err = "ac measure: bad arguments (n_inst >= 1, result and workspace buffers)";
-    return SPICEY_ERR_BAD_DESC;
-  }
   std::vector<SpiceyAcMeasDevReq> table;
-  if (!spicey_acm_plan(reqs, n_req, n_freq, d_v ? n_v : 0, n_i, d_i != nullptr, table, g_err)) return SPICEY_ERR_BAD_DESC;
-  const int64_t need = spicey_acm_workspace_bytes(n_inst, n_freq, n_req);
-  if (work_bytes < need) {
-    char buf[160];
-    snprintf(buf, sizeof(buf), "ac measure: workspace of %lld bytes is too small, %lld needed (spicey_ac_measure_workspace_bytes)", (long long)work_bytes,
-             (long long)need);
-    g_err = buf;
-    return SPICEY_ERR_BAD_DESC;
-  }
+  if (const int32_t rc = spicey_judge_measure("ac measure", spicey_acm_plan, spicey_acm_workspace_bytes, n_inst, n_freq, d_v != nullptr, n_v, d_i != nullptr, n_i, reqs,
+                                              n_req, d_meas && d_work, work_bytes, table, g_err); rc != SPICEY_OK)
+    return rc;
   int ncu = 0;
-  if (const int32_t rc = open_device(device, &ncu, g_err); rc != SPICEY_OK) return rc;
+  if (const int32_t rc = spicey_open_device(device, &ncu, g_err); rc != SPICEY_OK) return rc;
   const hipError_t e = spicey_launch_ac_measure(device, n_inst, n_freq, d_v, n_v, d_i, n_i, table.data(), n_req, d_meas, d_work, (hipStream_t)stream);
   if (e != hipSuccess) { g_err = std::string("spicey_launch_ac_measure: ") + hipGetErrorString(e); return SPICEY_ERR_HIP; }
   return SPICEY_OK;

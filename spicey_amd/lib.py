@@ -18,21 +18,75 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SPICEY_HIP_LIB") or os.path.join(_HERE, "libspicey_hip.so")  # same override as ts/spiceyHip.ts
 _LIB = None
 
-EXPORTS = ["spicey_create", "spicey_run", "spicey_run_device", "spicey_run_src", "spicey_run_device_src", "spicey_last_inst_status", "spicey_sync", "spicey_get_state", "spicey_set_state", "spicey_reset_state",
-           "spicey_last_solve_count", "spicey_group_retries", "spicey_group_stale_polls", "spicey_last_skip_risk", "spicey_get_lin_err",
-           "spicey_last_kernel_ms", "spicey_get_info", "spicey_last_error", "spicey_destroy", "spicey_version",
-           "spicey_debug_phase_cycles", "spicey_debug_phase_cycles_wg", "spicey_debug_front_ticks",
-           "spicey_create_multi", "spicey_run_multi", "spicey_run_multi_src", "spicey_get_state_multi", "spicey_multi_get_shard", "spicey_multi_last_solve_count", "spicey_multi_group_retries", "spicey_multi_group_stale_polls",
-           "spicey_multi_last_kernel_ms", "spicey_multi_last_error", "spicey_destroy_multi",
-           "spicey_ac_create", "spicey_ac_run", "spicey_ac_get_info", "spicey_ac_last_kernel_ms", "spicey_ac_last_error", "spicey_ac_destroy",
-           "spicey_format_tran", "spicey_to_precision6",
-           "spicey_measure_workspace_bytes", "spicey_measure_device", "spicey_run_measure", "spicey_last_measure_ms",
-           "spicey_ac_last_inst_status", "spicey_ac_measure_workspace_bytes", "spicey_ac_measure_device", "spicey_ac_run_measure",
-           "spicey_ac_last_measure_ms"]
+_i32, _i64, _f64, _vp, _str = C.c_int32, C.c_int64, C.c_double, C.c_void_p, C.c_char_p
+_f64p, _i32p, _i64p, _u64p = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_uint64)
+_descp, _optp, _infop, _outp = C.POINTER(abi.SpiceyDesc), C.POINTER(abi.SpiceyOptions), C.POINTER(abi.SpiceyInfo), C.POINTER(C.c_void_p)
+# name -> (restype, argtypes) of every function include/spicey_hip.h declares: load() binds them, EXPORTS lists them
+SIGNATURES = {
+    "spicey_create": (_i32, [_descp, _optp, _outp]),
+    "spicey_run": (_i32, [_vp, _i64, _f64, _f64p, _f64p, _f64p, _i32p]),
+    "spicey_run_device": (_i32, [_vp, _i64, _f64, _vp, _vp, _vp, _vp, _vp]),
+    "spicey_run_src": (_i32, [_vp, _i64, _f64, _f64p, _i32, _f64p, _f64p, _i32p]),
+    "spicey_run_device_src": (_i32, [_vp, _i64, _f64, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "spicey_last_inst_status": (_i32, [_vp, _i32p]),
+    "spicey_sync": (_i32, [_vp]),
+    "spicey_get_state": (_i32, [_vp, _f64p, _f64p, _f64p, _i32p]),
+    "spicey_set_state": (_i32, [_vp, _f64p, _f64p, _f64p, _i32p]),
+    "spicey_reset_state": (_i32, [_vp, _vp]),
+    "spicey_last_solve_count": (_i64, [_vp]),
+    "spicey_group_retries": (_i32, [_vp]),
+    "spicey_group_stale_polls": (_i64, [_vp]),
+    "spicey_last_skip_risk": (_i64, [_vp, _i64p]),
+    "spicey_get_lin_err": (_i32, [_vp, _f64p]),
+    "spicey_last_kernel_ms": (_f64, [_vp]),
+    "spicey_get_info": (_i32, [_vp, _infop]),
+    "spicey_last_error": (_str, [_vp]),
+    "spicey_destroy": (None, [_vp]),
+    "spicey_version": (_str, []),
+    "spicey_debug_phase_cycles": (_i32, [_vp, _u64p, _i32]),
+    "spicey_debug_phase_cycles_wg": (_i32, [_vp, _i32, _u64p, _i32]),
+    "spicey_debug_front_ticks": (_i32, [_vp, _i32, _u64p, _i32p, _i32]),
+    "spicey_create_multi": (_i32, [_descp, _optp, _i32p, _i32, _outp]),
+    "spicey_run_multi": (_i32, [_vp, _i64, _f64, _f64p, _f64p, _f64p, _i32p]),
+    "spicey_run_multi_src": (_i32, [_vp, _i64, _f64, _f64p, _i32, _f64p, _f64p, _i32p]),
+    "spicey_get_state_multi": (_i32, [_vp, _f64p, _f64p, _f64p, _i32p]),
+    "spicey_multi_get_shard": (_i32, [_vp, _i32, _infop, _i32p, _i32p, _i32p]),
+    "spicey_multi_last_solve_count": (_i64, [_vp]),
+    "spicey_multi_group_retries": (_i32, [_vp]),
+    "spicey_multi_group_stale_polls": (_i64, [_vp]),
+    "spicey_multi_last_kernel_ms": (_f64, [_vp]),
+    "spicey_multi_last_error": (_str, [_vp]),
+    "spicey_destroy_multi": (None, [_vp]),
+    "spicey_ac_create": (_i32, [_descp, _optp, _outp]),
+    "spicey_ac_run": (_i32, [_vp, _i64, _f64p, _f64p, _f64p, _f64p]),
+    "spicey_ac_get_info": (_i32, [_vp, _infop]),
+    "spicey_ac_last_kernel_ms": (_f64, [_vp]),
+    "spicey_ac_last_error": (_str, [_vp]),
+    "spicey_ac_destroy": (None, [_vp]),
+    "spicey_format_tran": (_i64, [_i64, _i32, _f64p, _f64p, _i64, _i32p, _str, _str, _i64]),
+    "spicey_to_precision6": (_i32, [_f64, _str]),
+    "spicey_measure_workspace_bytes": (_i64, [_i32, _i64, _i32]),
+    "spicey_measure_device": (_i32, [_i32, _i32, _i64, _f64, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i64, _vp]),
+    "spicey_run_measure": (_i32, [_vp, _i64, _f64, _f64p, _i32, _vp, _i32, _f64p, _i32p]),
+    "spicey_last_measure_ms": (_f64, [_vp]),
+    "spicey_ac_last_inst_status": (_i32, [_vp, _i32p, _i64p]),
+    "spicey_ac_measure_workspace_bytes": (_i64, [_i32, _i64, _i32]),
+    "spicey_ac_measure_device": (_i32, [_i32, _i32, _i64, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i64, _vp]),
+    "spicey_ac_run_measure": (_i32, [_vp, _i64, _f64p, _f64p, _vp, _i32, _f64p]),
+    "spicey_ac_last_measure_ms": (_f64, [_vp]),
+}
+EXPORTS = list(SIGNATURES)
 
 
 class SpiceyNativeError(RuntimeError):
     pass
+
+
+def _fail(what: str, rc: int, msg) -> None:
+    """Raises SpiceyNativeError for the library's status `rc` (kept as `.status`) and its message (bytes or str)."""
+    err = SpiceyNativeError(f"{what} failed ({rc}): {msg.decode() if isinstance(msg, bytes) else msg or ''}")
+    err.status = rc
+    raise err
 
 
 # Group mode health of this process: launches repeated after a bounded-wait abort and waits that only the read-modify-write
@@ -49,106 +103,9 @@ def load():
         raise SpiceyNativeError(f"{LIB_PATH} not built: run __graft_entry__.build() (hipcc --offload-arch=gfx950); "
                                 "spicey_amd has no CPU fallback")
     L = C.CDLL(LIB_PATH)
-    f64p, i32p, vp = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_void_p
-    L.spicey_create.restype = C.c_int32
-    L.spicey_create.argtypes = [C.POINTER(abi.SpiceyDesc), C.POINTER(abi.SpiceyOptions), C.POINTER(vp)]
-    L.spicey_run.restype = C.c_int32
-    L.spicey_run.argtypes = [vp, C.c_int64, C.c_double, f64p, f64p, f64p, i32p]
-    L.spicey_run_device.restype = C.c_int32
-    L.spicey_run_device.argtypes = [vp, C.c_int64, C.c_double, vp, vp, vp, vp, vp]
-    L.spicey_run_src.restype = C.c_int32
-    L.spicey_run_src.argtypes = [vp, C.c_int64, C.c_double, f64p, C.c_int32, f64p, f64p, i32p]
-    L.spicey_run_device_src.restype = C.c_int32
-    L.spicey_run_device_src.argtypes = [vp, C.c_int64, C.c_double, vp, C.c_int32, vp, vp, vp, vp]
-    L.spicey_last_inst_status.restype = C.c_int32
-    L.spicey_last_inst_status.argtypes = [vp, i32p]
-    L.spicey_sync.restype = C.c_int32
-    L.spicey_sync.argtypes = [vp]
-    L.spicey_group_retries.restype = C.c_int32
-    L.spicey_group_retries.argtypes = [vp]
-    L.spicey_group_stale_polls.restype = C.c_int64
-    L.spicey_group_stale_polls.argtypes = [vp]
-    L.spicey_last_skip_risk.restype = C.c_int64
-    L.spicey_last_skip_risk.argtypes = [vp, C.POINTER(C.c_int64)]
-    L.spicey_get_lin_err.restype = C.c_int32
-    L.spicey_get_lin_err.argtypes = [vp, f64p]
-    L.spicey_get_state.restype = C.c_int32
-    L.spicey_get_state.argtypes = [vp, f64p, f64p, f64p, i32p]
-    L.spicey_set_state.restype = C.c_int32
-    L.spicey_set_state.argtypes = [vp, f64p, f64p, f64p, i32p]
-    L.spicey_reset_state.restype = C.c_int32
-    L.spicey_reset_state.argtypes = [vp, vp]
-    L.spicey_last_solve_count.restype = C.c_int64
-    L.spicey_last_solve_count.argtypes = [vp]
-    L.spicey_last_kernel_ms.restype = C.c_double
-    L.spicey_last_kernel_ms.argtypes = [vp]
-    L.spicey_get_info.restype = C.c_int32
-    L.spicey_get_info.argtypes = [vp, C.POINTER(abi.SpiceyInfo)]
-    L.spicey_last_error.restype = C.c_char_p
-    L.spicey_last_error.argtypes = [vp]
-    L.spicey_destroy.restype = None
-    L.spicey_destroy.argtypes = [vp]
-    L.spicey_version.restype = C.c_char_p
-    L.spicey_debug_phase_cycles.restype = C.c_int32
-    L.spicey_debug_phase_cycles.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int32]
-    L.spicey_debug_phase_cycles_wg.restype = C.c_int32
-    L.spicey_debug_phase_cycles_wg.argtypes = [vp, C.c_int32, C.POINTER(C.c_uint64), C.c_int32]
-    L.spicey_create_multi.restype = C.c_int32
-    L.spicey_create_multi.argtypes = [C.POINTER(abi.SpiceyDesc), C.POINTER(abi.SpiceyOptions), i32p, C.c_int32, C.POINTER(vp)]
-    L.spicey_run_multi.restype = C.c_int32
-    L.spicey_run_multi.argtypes = [vp, C.c_int64, C.c_double, f64p, f64p, f64p, i32p]
-    L.spicey_run_multi_src.restype = C.c_int32
-    L.spicey_run_multi_src.argtypes = [vp, C.c_int64, C.c_double, f64p, C.c_int32, f64p, f64p, i32p]
-    L.spicey_get_state_multi.restype = C.c_int32
-    L.spicey_get_state_multi.argtypes = [vp, f64p, f64p, f64p, i32p]
-    L.spicey_multi_get_shard.restype = C.c_int32
-    L.spicey_multi_get_shard.argtypes = [vp, C.c_int32, C.POINTER(abi.SpiceyInfo), i32p, i32p, i32p]
-    L.spicey_multi_last_solve_count.restype = C.c_int64
-    L.spicey_multi_last_solve_count.argtypes = [vp]
-    L.spicey_multi_group_retries.restype = C.c_int32
-    L.spicey_multi_group_retries.argtypes = [vp]
-    L.spicey_multi_group_stale_polls.restype = C.c_int64
-    L.spicey_multi_group_stale_polls.argtypes = [vp]
-    L.spicey_multi_last_kernel_ms.restype = C.c_double
-    L.spicey_multi_last_kernel_ms.argtypes = [vp]
-    L.spicey_multi_last_error.restype = C.c_char_p
-    L.spicey_multi_last_error.argtypes = [vp]
-    L.spicey_destroy_multi.restype = None
-    L.spicey_destroy_multi.argtypes = [vp]
-    L.spicey_ac_create.restype = C.c_int32
-    L.spicey_ac_create.argtypes = [C.POINTER(abi.SpiceyDesc), C.POINTER(abi.SpiceyOptions), C.POINTER(vp)]
-    L.spicey_ac_run.restype = C.c_int32
-    L.spicey_ac_run.argtypes = [vp, C.c_int64, f64p, f64p, f64p, f64p]
-    L.spicey_ac_get_info.restype = C.c_int32
-    L.spicey_ac_get_info.argtypes = [vp, C.POINTER(abi.SpiceyInfo)]
-    L.spicey_ac_last_kernel_ms.restype = C.c_double
-    L.spicey_ac_last_kernel_ms.argtypes = [vp]
-    L.spicey_ac_last_error.restype = C.c_char_p
-    L.spicey_ac_last_error.argtypes = [vp]
-    L.spicey_ac_destroy.restype = None
-    L.spicey_ac_destroy.argtypes = [vp]
-    L.spicey_format_tran.restype = C.c_int64
-    L.spicey_format_tran.argtypes = [C.c_int64, C.c_int32, f64p, f64p, C.c_int64, i32p, C.c_char_p, C.c_char_p, C.c_int64]
-    L.spicey_to_precision6.restype = C.c_int32
-    L.spicey_to_precision6.argtypes = [C.c_double, C.c_char_p]
-    L.spicey_measure_workspace_bytes.restype = C.c_int64
-    L.spicey_measure_workspace_bytes.argtypes = [C.c_int32, C.c_int64, C.c_int32]
-    L.spicey_measure_device.restype = C.c_int32
-    L.spicey_measure_device.argtypes = [C.c_int32, C.c_int32, C.c_int64, C.c_double, vp, C.c_int32, vp, C.c_int32, vp, C.c_int32, vp, vp, C.c_int64, vp]
-    L.spicey_run_measure.restype = C.c_int32
-    L.spicey_run_measure.argtypes = [vp, C.c_int64, C.c_double, f64p, C.c_int32, vp, C.c_int32, f64p, i32p]
-    L.spicey_last_measure_ms.restype = C.c_double
-    L.spicey_last_measure_ms.argtypes = [vp]
-    L.spicey_ac_last_inst_status.restype = C.c_int32
-    L.spicey_ac_last_inst_status.argtypes = [vp, i32p, C.POINTER(C.c_int64)]
-    L.spicey_ac_measure_workspace_bytes.restype = C.c_int64
-    L.spicey_ac_measure_workspace_bytes.argtypes = [C.c_int32, C.c_int64, C.c_int32]
-    L.spicey_ac_measure_device.restype = C.c_int32
-    L.spicey_ac_measure_device.argtypes = [C.c_int32, C.c_int32, C.c_int64, vp, C.c_int32, vp, C.c_int32, vp, C.c_int32, vp, vp, C.c_int64, vp]
-    L.spicey_ac_run_measure.restype = C.c_int32
-    L.spicey_ac_run_measure.argtypes = [vp, C.c_int64, f64p, f64p, vp, C.c_int32, f64p]
-    L.spicey_ac_last_measure_ms.restype = C.c_double
-    L.spicey_ac_last_measure_ms.argtypes = [vp]
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _LIB = L
     return L
 
@@ -167,14 +124,42 @@ def _src_layout(src: np.ndarray, f: abi.FlatCircuit, steps: int) -> bool:
                      f"got {src.shape}")
 
 
-def _reqs(reqs) -> np.ndarray:
+def _reqs(reqs, dtype=abi.MEAS_REQ_DTYPE) -> np.ndarray:
     """A request list as one contiguous array of SpiceyMeasReq records (abi.MEAS_REQ_DTYPE)."""
-    a = np.ascontiguousarray(reqs, dtype=abi.MEAS_REQ_DTYPE).reshape(-1)
-    return a
+    return np.ascontiguousarray(reqs, dtype=dtype).reshape(-1)
+
+
+def _ac_reqs(reqs) -> np.ndarray:
+    """A request list as one contiguous array of SpiceyAcMeasReq records (abi.AC_MEAS_REQ_DTYPE)."""
+    return _reqs(reqs, abi.AC_MEAS_REQ_DTYPE)
+
+
+def _reqs_ptr(r: np.ndarray):
+    return r.ctypes.data if len(r) else None
+
+
+def _state_arrays(f: abi.FlatCircuit):
+    """A zeroed state dict of `f`'s instances and its arrays as the arguments of spicey_get_state(_multi)."""
+    st = {"C_vprev": np.zeros((f.n_inst, f.nC)), "L_iprev": np.zeros((f.n_inst, f.nL)), "D_vdprev": np.zeros((f.n_inst, f.nD)),
+          "S_ison": np.zeros((f.n_inst, f.nS), np.int32)}
+    return st, (_p(st["C_vprev"], C.c_double), _p(st["L_iprev"], C.c_double), _p(st["D_vdprev"], C.c_double), _p(st["S_ison"], C.c_int32))
 
 
 def measure_workspace_bytes(n_inst: int, n_points: int, n_req: int) -> int:
     return load().spicey_measure_workspace_bytes(n_inst, n_points, n_req)
+
+
+def ac_measure_workspace_bytes(n_inst: int, n_freq: int, n_req: int) -> int:
+    return load().spicey_ac_measure_workspace_bytes(n_inst, n_freq, n_req)
+
+
+def _measure_device(fn: str, shape: tuple, d_v: int, n_v: int, d_i: int, n_i: int, r: np.ndarray, d_meas: int, d_work: int, work_bytes: int,
+                    device: int, stream: int) -> None:
+    L = load()
+    rc = getattr(L, fn)(device, *shape, d_v or None, n_v, d_i or None, n_i, _reqs_ptr(r), len(r), d_meas or None, d_work or None, work_bytes,
+                        stream or None)
+    if rc != abi.OK:
+        _fail(fn, rc, L.spicey_last_error(None))
 
 
 def measure_device(n_inst: int, n_points: int, dt: float, d_v: int, n_v: int, d_i: int, n_i: int, reqs, d_meas: int, d_work: int,
@@ -183,41 +168,14 @@ def measure_device(n_inst: int, n_points: int, dt: float, d_v: int, n_v: int, d_
     [n_inst][n_points][n_v], d_i [n_inst][n_points][n_i] or 0, d_meas [n_inst][n_req][8], d_work of `work_bytes` >=
     measure_workspace_bytes(...).  Enqueued on `stream`, no synchronisation.  A refusal raises SpiceyNativeError whose
     `status` is the library's code (abi.ERR_BAD_DESC for a bad request list)."""
-    L = load()
-    r = _reqs(reqs)
-    rc = L.spicey_measure_device(device, n_inst, n_points, dt, d_v or None, n_v, d_i or None, n_i, r.ctypes.data if len(r) else None, len(r),
-                                 d_meas or None, d_work or None, work_bytes, stream or None)
-    if rc != abi.OK:
-        msg = L.spicey_last_error(None)
-        err = SpiceyNativeError(f"spicey_measure_device failed ({rc}): {msg.decode() if msg else ''}")
-        err.status = rc
-        raise err
-
-
-def _ac_reqs(reqs) -> np.ndarray:
-    """A request list as one contiguous array of SpiceyAcMeasReq records (abi.AC_MEAS_REQ_DTYPE)."""
-    return np.ascontiguousarray(reqs, dtype=abi.AC_MEAS_REQ_DTYPE).reshape(-1)
-
-
-def ac_measure_workspace_bytes(n_inst: int, n_freq: int, n_req: int) -> int:
-    return load().spicey_ac_measure_workspace_bytes(n_inst, n_freq, n_req)
+    _measure_device("spicey_measure_device", (n_inst, n_points, dt), d_v, n_v, d_i, n_i, _reqs(reqs), d_meas, d_work, work_bytes, device, stream)
 
 
 def ac_measure_device(n_inst: int, n_freq: int, d_v: int, n_v: int, d_i: int, n_i: int, reqs, d_meas: int, d_work: int, work_bytes: int,
                       device: int = 0, stream: int = 0) -> None:
-    """spicey_ac_measure_device: the reduction alone on raw device pointers (e.g. torch tensors' data_ptr()): d_v
-    [n_inst][n_freq][n_v] complex128, d_i likewise or 0, d_meas [n_inst][n_req][8], d_work of `work_bytes` >=
-    ac_measure_workspace_bytes(...).  Enqueued on `stream`, no synchronisation.  A refusal raises SpiceyNativeError whose
-    `status` is the library's code (abi.ERR_BAD_DESC for a bad request list)."""
-    L = load()
-    r = _ac_reqs(reqs)
-    rc = L.spicey_ac_measure_device(device, n_inst, n_freq, d_v or None, n_v, d_i or None, n_i, r.ctypes.data if len(r) else None, len(r),
-                                    d_meas or None, d_work or None, work_bytes, stream or None)
-    if rc != abi.OK:
-        msg = L.spicey_last_error(None)
-        err = SpiceyNativeError(f"spicey_ac_measure_device failed ({rc}): {msg.decode() if msg else ''}")
-        err.status = rc
-        raise err
+    """The same for an AC sweep's buffers (spicey_ac_measure_device): d_v [n_inst][n_freq][n_v] complex128, d_i likewise or
+    0, d_work of `work_bytes` >= ac_measure_workspace_bytes(...)."""
+    _measure_device("spicey_ac_measure_device", (n_inst, n_freq), d_v, n_v, d_i, n_i, _ac_reqs(reqs), d_meas, d_work, work_bytes, device, stream)
 
 
 class Handle:
@@ -243,8 +201,7 @@ class Handle:
         hp = C.c_void_p()
         rc = self.L.spicey_create(C.byref(d), C.byref(opt), C.byref(hp))
         if rc != abi.OK:
-            msg = self.L.spicey_last_error(None)
-            raise SpiceyNativeError(f"spicey_create failed ({rc}): {msg.decode() if msg else ''}")
+            _fail("spicey_create", rc, self.L.spicey_last_error(None))
         self.h = hp
 
     def info(self) -> dict:
@@ -274,20 +231,26 @@ class Handle:
                                    _p(iters, C.c_int32))
         res = {"status": rc, "detail": self.error() if rc != abi.OK else "", "out_v": out_v, "out_i": out_i, "iters": iters,
                "partial": per_inst}
-        res["inst_status"] = self.inst_status() if rc in (abi.OK, abi.ERR_SINGULAR) else np.full(f.n_inst, rc, np.int32)
-        if rc == abi.OK:
-            res["solves"] = self.L.spicey_last_solve_count(self.h)
-            res["kernel_ms"] = self.L.spicey_last_kernel_ms(self.h)
         # (after a singular run with per-instance tables, the instances that finished keep everything a success reports:
         # results, end state and their diagnostics)
-        if rc == abi.OK or (per_inst and rc == abi.ERR_SINGULAR):
+        return self._dress(res, rc, rc == abi.OK, rc == abi.OK or (per_inst and rc == abi.ERR_SINGULAR), steps)
+
+    def _dress(self, res: dict, rc: int, timed: bool, kept: bool, lin_err_steps: Optional[int] = None) -> dict:
+        """What every transient result carries besides its buffers: `inst_status`; when `timed`, `solves` and `kernel_ms`;
+        when `kept` (the run's results stand), the end `state` and the diagnostics this handle was opened with."""
+        f = self.flat
+        res["inst_status"] = self.inst_status() if rc in (abi.OK, abi.ERR_SINGULAR) else np.full(f.n_inst, rc, np.int32)
+        if timed:
+            res["solves"] = self.L.spicey_last_solve_count(self.h)
+            res["kernel_ms"] = self.L.spicey_last_kernel_ms(self.h)
+        if kept:
             res["state"] = self.state()
             if self.diagnostics & 1:
                 per = np.zeros(f.n_inst, np.int64)
                 self.L.spicey_last_skip_risk(self.h, _p(per, C.c_int64))
                 res["skip_risk"] = per
-            if self.diagnostics & 2:
-                le = np.zeros((f.n_inst, steps + 1))
+            if self.diagnostics & 2 and lin_err_steps is not None:
+                le = np.zeros((f.n_inst, lin_err_steps + 1))
                 if self.L.spicey_get_lin_err(self.h, _p(le, C.c_double)) != abi.OK:
                     raise SpiceyNativeError(f"spicey_get_lin_err failed: {self.error()}")
                 res["lin_err"] = le
@@ -304,20 +267,13 @@ class Handle:
         r = _reqs(reqs)
         meas = np.zeros((f.n_inst, len(r), 8))
         iters = np.zeros((f.n_inst, steps + 1), np.int32) if want_iters else None
-        rc = self.L.spicey_run_measure(self.h, steps, dt, _p(src, C.c_double), 1 if per_inst else 0, r.ctypes.data if len(r) else None, len(r),
+        rc = self.L.spicey_run_measure(self.h, steps, dt, _p(src, C.c_double), 1 if per_inst else 0, _reqs_ptr(r), len(r),
                                        _p(meas, C.c_double), _p(iters, C.c_int32))
         res = {"status": rc, "detail": self.error() if rc != abi.OK else "", "meas": meas, "iters": iters, "partial": True}
-        res["inst_status"] = self.inst_status() if rc in (abi.OK, abi.ERR_SINGULAR) else np.full(f.n_inst, rc, np.int32)
-        if rc in (abi.OK, abi.ERR_SINGULAR):
-            res["solves"] = self.L.spicey_last_solve_count(self.h)
-            res["kernel_ms"] = self.L.spicey_last_kernel_ms(self.h)
+        kept = rc in (abi.OK, abi.ERR_SINGULAR)
+        if kept:
             res["measure_ms"] = self.L.spicey_last_measure_ms(self.h)
-            res["state"] = self.state()
-            if self.diagnostics & 1:
-                per = np.zeros(f.n_inst, np.int64)
-                self.L.spicey_last_skip_risk(self.h, _p(per, C.c_int64))
-                res["skip_risk"] = per
-        return res
+        return self._dress(res, rc, kept, kept)
 
     def run_device(self, steps: int, dt: float, d_src: int, d_out_v: int, d_out_i: int = 0, d_iters: int = 0, stream: int = 0,
                    src_per_inst: bool = False) -> None:
@@ -328,7 +284,7 @@ class Handle:
         else:
             rc = self.L.spicey_run_device(self.h, steps, dt, d_src, d_out_v, d_out_i or None, d_iters or None, stream or None)
         if rc != abi.OK:
-            raise SpiceyNativeError(f"spicey_run_device failed ({rc}): {self.error()}")
+            _fail("spicey_run_device", rc, self.error())
 
     def inst_status(self) -> np.ndarray:
         """Per instance of the last run (spicey_last_inst_status): 0 finished, 1 = SPICEY_ERR_SINGULAR (its own solve), -1 =
@@ -350,8 +306,6 @@ class Handle:
         nf = self.info()["n_fronts"]
         t = np.zeros((max(nf, 1), 4), np.uint64)
         m = np.zeros((max(nf, 1), 4), np.int32)
-        self.L.spicey_debug_front_ticks.restype = C.c_int32
-        self.L.spicey_debug_front_ticks.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.c_int32]
         got = self.L.spicey_debug_front_ticks(self.h, grp, t.ctypes.data_as(C.POINTER(C.c_uint64)), m.ctypes.data_as(C.POINTER(C.c_int32)), nf)
         return t[:got], m[:got]
 
@@ -381,13 +335,10 @@ class Handle:
         return list(buf)
 
     def state(self) -> dict:
-        f = self.flat
-        st = {"C_vprev": np.zeros((f.n_inst, f.nC)), "L_iprev": np.zeros((f.n_inst, f.nL)), "D_vdprev": np.zeros((f.n_inst, f.nD)),
-              "S_ison": np.zeros((f.n_inst, f.nS), np.int32)}
-        rc = self.L.spicey_get_state(self.h, _p(st["C_vprev"], C.c_double), _p(st["L_iprev"], C.c_double),
-                                     _p(st["D_vdprev"], C.c_double), _p(st["S_ison"], C.c_int32))
+        st, ptrs = _state_arrays(self.flat)
+        rc = self.L.spicey_get_state(self.h, *ptrs)
         if rc != abi.OK:
-            raise SpiceyNativeError(f"spicey_get_state failed ({rc}): {self.error()}")
+            _fail("spicey_get_state", rc, self.error())
         return st
 
     def set_state(self, st: dict) -> None:
@@ -397,13 +348,13 @@ class Handle:
         rc = self.L.spicey_set_state(self.h, _p(a["C_vprev"], C.c_double), _p(a["L_iprev"], C.c_double), _p(a["D_vdprev"], C.c_double),
                                      _p(a["S_ison"], C.c_int32))
         if rc != abi.OK:
-            raise SpiceyNativeError(f"spicey_set_state failed ({rc}): {self.error()}")
+            _fail("spicey_set_state", rc, self.error())
 
     def reset_state(self, stream: int = 0) -> None:
         """Back to the state the handle was created with (device-to-device, enqueued on `stream`)."""
         rc = self.L.spicey_reset_state(self.h, stream or None)
         if rc != abi.OK:
-            raise SpiceyNativeError(f"spicey_reset_state failed ({rc}): {self.error()}")
+            _fail("spicey_reset_state", rc, self.error())
 
     def close(self) -> None:
         if getattr(self, "h", None):
@@ -435,8 +386,7 @@ class MultiHandle:
         hp = C.c_void_p()
         rc = self.L.spicey_create_multi(C.byref(d), C.byref(opt), _p(devs, C.c_int32) if len(devs) else None, len(devs), C.byref(hp))
         if rc != abi.OK:
-            msg = self.L.spicey_multi_last_error(None)
-            raise SpiceyNativeError(f"spicey_create_multi failed ({rc}): {msg.decode() if msg else ''}")
+            _fail("spicey_create_multi", rc, self.L.spicey_multi_last_error(None))
         self.h = hp
 
     def shards(self) -> list:
@@ -466,11 +416,8 @@ class MultiHandle:
         detail = self.L.spicey_multi_last_error(self.h).decode() if rc != abi.OK else ""
         res = {"status": rc, "detail": detail, "out_v": out_v, "out_i": out_i, "iters": iters}
         if rc == abi.OK:
-            st = {"C_vprev": np.zeros((f.n_inst, f.nC)), "L_iprev": np.zeros((f.n_inst, f.nL)), "D_vdprev": np.zeros((f.n_inst, f.nD)),
-                  "S_ison": np.zeros((f.n_inst, f.nS), np.int32)}
-            self.L.spicey_get_state_multi(self.h, _p(st["C_vprev"], C.c_double), _p(st["L_iprev"], C.c_double), _p(st["D_vdprev"], C.c_double),
-                                          _p(st["S_ison"], C.c_int32))
-            res["state"] = st
+            res["state"], ptrs = _state_arrays(f)
+            self.L.spicey_get_state_multi(self.h, *ptrs)
             res["solves"] = self.L.spicey_multi_last_solve_count(self.h)
             res["kernel_ms"] = self.L.spicey_multi_last_kernel_ms(self.h)
         return res
@@ -537,7 +484,7 @@ class AcHandle:
         h = C.c_void_p()
         rc = self.L.spicey_ac_create(C.byref(d), C.byref(opt), C.byref(h))
         if rc != abi.OK:
-            raise SpiceyNativeError(f"spicey_ac_create failed ({rc}): {self.L.spicey_ac_last_error(None).decode()}")
+            _fail("spicey_ac_create", rc, self.L.spicey_ac_last_error(None))
         self.h = h
 
     def info(self) -> dict:
@@ -545,20 +492,27 @@ class AcHandle:
         self.L.spicey_ac_get_info(self.h, C.byref(info))
         return info.as_dict()
 
+    def _sweep_args(self, freqs, vph):
+        """(freqs float64, phasors [n_inst][nV] complex128): one phasor set for every instance, or one per instance."""
+        f = self.flat
+        return (np.ascontiguousarray(freqs, dtype=np.float64),
+                np.ascontiguousarray(np.broadcast_to(np.asarray(vph, np.complex128).reshape(-1, f.nV), (f.n_inst, f.nV))))
+
+    def _dress(self, res: dict, rc: int) -> dict:
+        res["status"], res["detail"] = rc, self.L.spicey_ac_last_error(self.h).decode() if rc != abi.OK else ""
+        res["kernel_ms"] = self.L.spicey_ac_last_kernel_ms(self.h)
+        res["inst_status"], res["first_freq"] = self.inst_status(rc)
+        return res
+
     def run(self, freqs, vph, want_currents: bool = True) -> dict:
         f = self.flat
+        freqs, ph = self._sweep_args(freqs, vph)
         ni, nf = f.n_inst, len(freqs)
-        freqs = np.ascontiguousarray(freqs, dtype=np.float64)
-        # one phasor set for every instance, or one per instance
-        ph = np.ascontiguousarray(np.broadcast_to(np.asarray(vph, np.complex128).reshape(-1, f.nV), (ni, f.nV)))
         out_v = np.zeros((ni, nf, f.n_out), np.complex128)
         out_i = np.zeros((ni, nf, f.nR + f.nC + f.nL + f.nV), np.complex128) if want_currents else None
         rc = self.L.spicey_ac_run(self.h, nf, _p(freqs, C.c_double), _p(ph.view(np.float64), C.c_double),
                                   _p(out_v.view(np.float64), C.c_double), _p(out_i.view(np.float64), C.c_double) if want_currents else None)
-        detail = self.L.spicey_ac_last_error(self.h).decode() if rc != abi.OK else ""
-        ist, first = self.inst_status(rc)
-        return {"status": rc, "detail": detail, "out_v": out_v, "out_i": out_i, "kernel_ms": self.L.spicey_ac_last_kernel_ms(self.h),
-                "inst_status": ist, "first_freq": first}
+        return self._dress({"out_v": out_v, "out_i": out_i}, rc)
 
     def inst_status(self, rc: int = abi.OK):
         """(status[n_inst], first_freq[n_inst]) of the last sweep (spicey_ac_last_inst_status): per instance 0, or the code of
@@ -576,18 +530,12 @@ class AcHandle:
         """spicey_ac_run_measure: the sweep of run() with its results kept on the device and reduced there; only `meas`
         [n_inst][n_req][8] (include/spicey_hip.h) comes back, also after a failing sweep (`inst_status` names the instances
         whose rows are undefined).  reqs: records of abi.AC_MEAS_REQ_DTYPE, columns as in this handle's out_v / out_i."""
-        f = self.flat
-        ni, nf = f.n_inst, len(freqs)
-        freqs = np.ascontiguousarray(freqs, dtype=np.float64)
-        ph = np.ascontiguousarray(np.broadcast_to(np.asarray(vph, np.complex128).reshape(-1, f.nV), (ni, f.nV)))
+        freqs, ph = self._sweep_args(freqs, vph)
         r = _ac_reqs(reqs)
-        meas = np.zeros((ni, len(r), 8))
-        rc = self.L.spicey_ac_run_measure(self.h, nf, _p(freqs, C.c_double), _p(ph.view(np.float64), C.c_double), r.ctypes.data if len(r) else None,
-                                          len(r), _p(meas, C.c_double))
-        detail = self.L.spicey_ac_last_error(self.h).decode() if rc != abi.OK else ""
-        ist, first = self.inst_status(rc)
-        return {"status": rc, "detail": detail, "meas": meas, "kernel_ms": self.L.spicey_ac_last_kernel_ms(self.h),
-                "measure_ms": self.L.spicey_ac_last_measure_ms(self.h), "inst_status": ist, "first_freq": first}
+        meas = np.zeros((self.flat.n_inst, len(r), 8))
+        rc = self.L.spicey_ac_run_measure(self.h, len(freqs), _p(freqs, C.c_double), _p(ph.view(np.float64), C.c_double), _reqs_ptr(r), len(r),
+                                          _p(meas, C.c_double))
+        return self._dress({"meas": meas, "measure_ms": self.L.spicey_ac_last_measure_ms(self.h)}, rc)
 
     def close(self) -> None:
         if getattr(self, "h", None):
@@ -601,7 +549,31 @@ class AcHandle:
             pass
 
 
-class HipBackend:
+class _AcCalls:
+    """run_ac / run_ac_measure of a backend (`kw`, `info`, `ac_launches`): every call on an AC handle of its own."""
+
+    ac_interpreter = 0  # SpiceyOptions.interpreter of the handles
+
+    def _on_ac_handle(self, flat: abi.FlatCircuit, call) -> dict:
+        """call(handle) on an AC handle of its own (one handle = one launch); `info` is the handle's after the sweep."""
+        h = AcHandle(flat, interpreter=self.ac_interpreter, **{k: self.kw[k] for k in ("device", "threads", "force_global")})
+        self.ac_launches.append(flat.n_inst)
+        try:
+            res = call(h)
+            self.info = h.info()
+            return res
+        finally:
+            h.close()
+
+    def run_ac(self, flat: abi.FlatCircuit, freqs, vph, want_currents: bool = True) -> dict:
+        return self._on_ac_handle(flat, lambda h: h.run(freqs, vph, want_currents))
+
+    def run_ac_measure(self, flat: abi.FlatCircuit, freqs, vph, reqs) -> dict:
+        """AcHandle.run_measure on a handle of its own: the sweep's results never leave the device."""
+        return self._on_ac_handle(flat, lambda h: h.run_measure(freqs, vph, reqs))
+
+
+class HipBackend(_AcCalls):
     """Backend interface used by spicey_amd.simulate: one handle per call (the reference API is stateless)."""
 
     def __init__(self, device: int = 0, threads: int = 0, inst_per_wg: int = 0, force_global: bool = False, interpreter: int = 0,
@@ -615,81 +587,36 @@ class HipBackend:
         self.group_stale_polls = 0
         self.ac_launches: list = []  # instances of every AC handle this backend opened (one handle = one launch)
 
-    def run(self, flat: abi.FlatCircuit, steps: int, dt: float, src: np.ndarray, want_currents: bool = True,
-            want_iters: bool = True) -> dict:
+    def _on_handle(self, flat: abi.FlatCircuit, call) -> dict:
+        """call(handle) on a handle of its own: its info and its group-mode counters recorded, closed afterwards."""
         h = Handle(flat, **self.kw)
         try:
             self.info = h.info()
-            res = h.run(steps, dt, src, want_currents, want_iters)
-            self.group_retries += h.group_retries()
-            self.group_stale_polls += h.group_stale_polls()
+            res = call(h)
             res["group_retries"], res["group_stale_polls"] = h.group_retries(), h.group_stale_polls()
+            self.group_retries += res["group_retries"]
+            self.group_stale_polls += res["group_stale_polls"]
             return res
         finally:
             h.close()
+
+    def run(self, flat: abi.FlatCircuit, steps: int, dt: float, src: np.ndarray, want_currents: bool = True,
+            want_iters: bool = True) -> dict:
+        return self._on_handle(flat, lambda h: h.run(steps, dt, src, want_currents, want_iters))
 
     def run_measure(self, flat: abi.FlatCircuit, steps: int, dt: float, src: np.ndarray, reqs, want_iters: bool = True) -> dict:
         """Handle.run_measure on a handle of its own: the waveforms never leave the device."""
-        h = Handle(flat, **self.kw)
-        try:
-            self.info = h.info()
-            res = h.run_measure(steps, dt, src, reqs, want_iters)
-            self.group_retries += h.group_retries()
-            self.group_stale_polls += h.group_stale_polls()
-            res["group_retries"], res["group_stale_polls"] = h.group_retries(), h.group_stale_polls()
-            return res
-        finally:
-            h.close()
-
-    def run_ac(self, flat: abi.FlatCircuit, freqs, vph, want_currents: bool = True) -> dict:
-        h = AcHandle(flat, device=self.kw["device"], threads=self.kw["threads"], force_global=self.kw["force_global"])
-        self.ac_launches.append(flat.n_inst)
-        try:
-            self.info = h.info()
-            return h.run(freqs, vph, want_currents)
-        finally:
-            h.close()
-
-    def run_ac_measure(self, flat: abi.FlatCircuit, freqs, vph, reqs) -> dict:
-        """AcHandle.run_measure on a handle of its own: the sweep's results never leave the device."""
-        h = AcHandle(flat, device=self.kw["device"], threads=self.kw["threads"], force_global=self.kw["force_global"])
-        self.ac_launches.append(flat.n_inst)
-        try:
-            res = h.run_measure(freqs, vph, reqs)
-            self.info = h.info()
-            return res
-        finally:
-            h.close()
+        return self._on_handle(flat, lambda h: h.run_measure(steps, dt, src, reqs, want_iters))
 
 
-class HipAcExactBackend:
+class HipAcExactBackend(_AcCalls):
     """run_ac through the reference-order AC engine (AcHandle(interpreter=3)): the reference's numbers and errors bit for
     bit.  Used by simulateAC(ckt, exact_order=True)."""
 
     exact_order = True  # (simulateAC leaves the inductors' "Complex divide by ~0" to the engine, frequency by frequency)
+    ac_interpreter = 3
 
     def __init__(self, device: int = 0, threads: int = 0, force_global: bool = False):
         self.kw = dict(device=device, threads=threads, force_global=force_global)
         self.info: Optional[dict] = None
         self.ac_launches: list = []  # instances of every AC handle this backend opened (one handle = one launch)
-
-    def run_ac(self, flat: abi.FlatCircuit, freqs, vph, want_currents: bool = True) -> dict:
-        h = AcHandle(flat, interpreter=3, **self.kw)
-        self.ac_launches.append(flat.n_inst)
-        try:
-            self.info = h.info()
-            res = h.run(freqs, vph, want_currents)
-            self.info = h.info()
-            return res
-        finally:
-            h.close()
-
-    def run_ac_measure(self, flat: abi.FlatCircuit, freqs, vph, reqs) -> dict:
-        h = AcHandle(flat, interpreter=3, **self.kw)
-        self.ac_launches.append(flat.n_inst)
-        try:
-            res = h.run_measure(freqs, vph, reqs)
-            self.info = h.info()
-            return res
-        finally:
-            h.close()
