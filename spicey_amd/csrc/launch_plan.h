@@ -26,8 +26,10 @@ size_t spicey_gw_doubles_per_wg(const SpiceyProg &P, int K);
 //   interpreter is therefore built for K = 1 only and interleaved instances run on interpreter 1)
 //   T <= 512 : 16 slots,  8 entries, 2 elements per thread (<= 256 VGPRs)
 //   T <= 1024:  8 slots,  4 entries, 1 element  per thread (<= 128 VGPRs)
-// `packed` = the two-workgroups-per-CU geometry: 512 threads, <= 128 VGPRs; only 4 slots stay resident (the small,
-// latency-critical phases), the wide bottom levels are streamed from L2 with the records prefetched in batches.
+// `packed` = the two-workgroups-per-CU geometry: 512 threads, <= 128 VGPRs; only 4 slots stay resident.  A streamed phase
+// costs an exposed L2 round trip per solve whatever its size, so spicey_build_resident fills the slots for the fewest
+// streamed PHASES (chunks go wherever slots are free, a level as row records where two slots of a wave are): on the
+// 1000-node chains only the widest factor level is streamed, with the next record fetched behind the one at hand.
 // Hybrid workspace: 512 threads as the plain build, or 1024 threads with 4 slots (with 8 the build spills 10 registers
 // at the 128-register cap).
 #define SPICEY_V2_RMAX256 28  // (32 slots spilled 6 vector registers to AGPRs: refused by check_no_spills.py)

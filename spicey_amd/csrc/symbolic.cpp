@@ -1589,8 +1589,15 @@ SpiceyProg HostProgram::bind(const void *base) const {
 }
 
 // ---------------------------------------------------------------------------------------------
-// Resident layout: chunks of 64 lanes; chunk c lives in (wave c % nWaves, slot c / nWaves), so the
-// chunks of one phase spread over the waves.  Smallest phases first (they are pure latency).
+// Resident layout: chunks of 64 lanes, one phase each, smallest phases first (they are pure latency).  A streamed phase
+// costs one exposed L2 round trip per solve whatever its size, so the aim is as few streamed phases as possible, then as
+// few streamed tasks.  First, chunk c of the running count goes to wave c % nWaves, so the chunks of one phase spread
+// over the waves; a phase that does not fit there is set aside.  Then the phases set aside go wherever slots are still
+// free — a generic chunk in any wave with a free slot, a chunk of row records in any wave with two, one chunk of the
+// phase per wave while waves remain — and a level narrower than the workgroup whose generic form does not fit is tried
+// as row records.  What fits nowhere is streamed.  A layout therefore differs from the round-robin one only by phases
+// it streams no longer.  The slots of a wave are compact and in phase order with a continuation right behind its head,
+// a phase is all resident or all streamed, and k_merge sits in wave 0.
 void spicey_build_resident(const HostProgram &hp, int T, int rmax, HostResident &out, int max_tail, bool row_records) {
   out = HostResident();
   out.rmax = rmax; out.T = T;
@@ -1614,8 +1621,7 @@ void spicey_build_resident(const HostProgram &hp, int T, int rmax, HostResident 
     if (b - a >= 3) { out.tail_first = a; out.tail_n = b - a; }
   }
   if (hp.hdr.has16 && nPh <= 254) {
-    // 1. which phases become resident: smallest first (they are pure latency) while chunks remain;
-    //    chunk c of the running count goes to wave c % nWaves, so a phase spreads over the waves.
+    // 1. which phases become resident: smallest first (they are pure latency) while chunks remain.
     //    A factor phase with a row-record encoding (program.h: fus16) is taken in that form: its generic remainder in
     //    one-slot chunks, its row records in chunks that own TWO consecutive slots of a wave (head + continuation).
     // (only where the generic form would give a thread more than one task: a level narrower than the workgroup is bound by
@@ -1640,6 +1646,16 @@ void spicey_build_resident(const HostProgram &hp, int T, int rmax, HostResident 
         out.resident_tasks += hp.ph_cnt[pm];
       }
     }
+    auto put_gen = [&](int w, int p, int i, int ngen, bool fus) {
+      per_wave[w].push_back({p, i * 64, std::min(64, ngen - i * 64), fus ? 1 : 0});
+      load[w]++;
+    };
+    auto put_rows = [&](int w, int p, int i, int nrow) {
+      per_wave[w].push_back({p, i * 64, std::min(64, nrow - i * 64), 2});
+      per_wave[w].push_back({p, i * 64, std::min(64, nrow - i * 64), 3});
+      load[w] += 2;
+    };
+    std::vector<int> left;  // phases that do not fit at the cursor
     for (int p : order) {
       const int cnt = (int)hp.ph_cnt[p];
       if (cnt == 0) continue;
@@ -1653,29 +1669,50 @@ void spicey_build_resident(const HostProgram &hp, int T, int rmax, HostResident 
         for (int i = 0; i < cg; i++) if (++l2[(next_chunk + i) % nWaves] > rmax) fits = false;
         for (int i = 0; i < cr; i++) if ((l2[(next_chunk + cg + i) % nWaves] += 2) > rmax) fits = false;
       }
-      if (!fits) {  // stays streamed
-        out.st_first[p] = hp.ph_first[p];
-        out.st_cnt[p] = hp.ph_cnt[p];
-        out.st_rhs[p] = p < (int)hp.ph_rhs.size() ? hp.ph_rhs[p] : hp.ph_cnt[p];
-        // streamed anyway: take the row records — where they keep most threads busy (a level with fewer rows than half the
-        // workgroup is latency-bound on the one exposed record fetch; its generic records, several per thread, overlap theirs)
-        out.st_fus[p] = (nrow > 0 && 2 * nrow > T) ? 1u : 0u;
-        out.streamed_tasks += cnt;
-        continue;
-      }
-      for (int i = 0; i < cg; i++) {
-        const int w = (next_chunk + i) % nWaves;
-        per_wave[w].push_back({p, i * 64, std::min(64, ngen - i * 64), nrow > 0 ? 1 : 0});
-        load[w]++;
-      }
-      for (int i = 0; i < cr; i++) {
-        const int w = (next_chunk + cg + i) % nWaves;
-        per_wave[w].push_back({p, i * 64, std::min(64, nrow - i * 64), 2});
-        per_wave[w].push_back({p, i * 64, std::min(64, nrow - i * 64), 3});
-        load[w] += 2;
-      }
+      if (!fits) { left.push_back(p); continue; }
+      for (int i = 0; i < cg; i++) put_gen((next_chunk + i) % nWaves, p, i, ngen, nrow > 0);
+      for (int i = 0; i < cr; i++) put_rows((next_chunk + cg + i) % nWaves, p, i, nrow);
       next_chunk += cg + cr;
       out.resident_tasks += cnt;
+    }
+    // The phases set aside, smallest first again, into the slots that are still free.  Row chunks first (they need two free
+    // slots of one wave); every chunk goes to the wave that holds the fewest chunks of its phase — the phase spreads over as
+    // many waves as possible, and a wave gets a second chunk only where the phase would be streamed otherwise —, the nearest
+    // such wave behind the cursor.  Feasible exactly when the free slot pairs cover the row chunks and the rest the others.
+    auto place_anywhere = [&](int p, int ngen, int nrow) -> bool {
+      const int cg = (ngen + 63) / 64, cr = (nrow + 63) / 64;
+      int pairs = 0, room = 0;
+      for (int w = 0; w < nWaves; w++) { pairs += (rmax - load[w]) / 2; room += rmax - load[w]; }
+      if (pairs < cr || room - 2 * cr < cg) return false;
+      std::vector<int> mine(nWaves, 0);
+      for (int i = 0; i < cr + cg; i++) {
+        const int need = i < cr ? 2 : 1;
+        int best = -1;
+        for (int k = 0; k < nWaves; k++) {
+          const int w = (next_chunk + k) % nWaves;
+          if (rmax - load[w] >= need && (best < 0 || mine[w] < mine[best])) best = w;
+        }
+        if (i < cr) put_rows(best, p, i, nrow);
+        else put_gen(best, p, i - cr, ngen, nrow > 0);
+        mine[best]++;
+      }
+      return true;
+    };
+    for (int p : left) {
+      const int nrow = rows_of(p);
+      bool fits = place_anywhere(p, nrow > 0 ? (int)hp.fus_gen[p] : (int)hp.ph_cnt[p], nrow);
+      // a level narrower than the workgroup whose generic form does not fit: its row records may
+      if (!fits && nrow == 0 && row_records && p < (int)hp.fus_pairs.size() && hp.fus_pairs[p] > 0)
+        fits = place_anywhere(p, (int)hp.fus_gen[p], (int)hp.fus_pairs[p]);
+      if (fits) { out.resident_tasks += hp.ph_cnt[p]; continue; }
+      // stays streamed
+      out.st_first[p] = hp.ph_first[p];
+      out.st_cnt[p] = hp.ph_cnt[p];
+      out.st_rhs[p] = p < (int)hp.ph_rhs.size() ? hp.ph_rhs[p] : hp.ph_cnt[p];
+      // streamed anyway: take the row records — where they keep most threads busy (a level with fewer rows than half the
+      // workgroup is latency-bound on the one exposed record fetch; its generic records, several per thread, overlap theirs)
+      out.st_fus[p] = (nrow > 0 && 2 * nrow > T) ? 1u : 0u;
+      out.streamed_tasks += hp.ph_cnt[p];
     }
     // 2. per wave: slots in execution (phase) order, so that the kernel walks them with a cursor (stable: a row chunk's
     //    continuation stays right behind its head)
