@@ -12,6 +12,21 @@
 //   5. compilation into gather-form task lists (no atomics, deterministic summation order):
 //      static/dynamic stamp lists, right-hand-side lists, per-level update tasks (factorisation with
 //      the forward elimination fused in as an extra column), per-level backward-substitution tasks.
+//   6. optionally the hybrid workspace layout: every index re-mapped to its side (LDS / global).
+//
+// Layout of this file.  build_program_impl is a short driver over one free function per stage; the stages hand their
+// products on in two plain structs, and a stage's signature says what it reads (const &) and what it fills (&):
+//   Pattern  n, arow, cand, row_of_col / col_of_row, forced, g          (stages 1 - 3)
+//   Factor   upper, children, by_level, E (EntryIndex), diag, nLU, nLevels, Lc, front_of, bin_of, nBins, in_top, pcrL,
+//            stat / dyn                                                  (stages 4 - 5a, read by everything behind)
+//   1    build_pattern            2a   match_sources        2b  match_rows          3    order_pivots
+//   4    symbolic_factor          4b   choose_front_cut, build_fronts, build_bins
+//   5a   build_stamps, build_rhs  5b   build_factor_slices  5c  build_backward_slices
+//   5c'  build_records16 (tridiagonal_top, level_factor_tasks, emit_factor, build_row_records, build_backward_records)
+//   5c'' build_b_descriptors      5d   build_terminals      6   layout_hybrid
+// Shared by the stages: level_products (the multiply-adds of a factor level, for 5b and 5c'), group_by_target,
+// pack_by_bin.  FactorRec / BackRec / RowRec are the one host-side view of the 16-bit records (emitters, spicey_bank_cost,
+// hybrid re-indexing).  SPICEY_PROG_SECTIONS / SPICEY_RESIDENT_SECTIONS list the blob sections once, for pack() and bind().
 #include "symbolic.h"
 
 #include <algorithm>
@@ -21,6 +36,7 @@
 #include <functional>
 #include <map>
 #include <numeric>
+#include <type_traits>
 
 namespace {
 
@@ -320,6 +336,81 @@ void pack_slices(std::vector<std::pair<uint32_t, std::vector<uint32_t>>> &tasks,
   }
 }
 
+
+// ---------------------------------------------------------------------------------------------
+// Host view of the 16-bit records (program.h has the layout, tran_exec.h the device-side decoders).  Every host place that
+// writes or reads a record goes through these: the emitters of stage 5c', spicey_bank_cost and the hybrid re-indexing.
+//
+// Generic record, four words: w0 = head | (count | flags << 8) << 16, then six half-words, or — count > 2 — the offset of
+// the operand list in ovf16 as w3.  A FACTOR record's head is its target and the half-words are up to two (l, d, u)
+// triples; a BACKWARD record's head is x, the first half-word its diagonal (inline even when the pairs overflow) and the
+// next four up to two (u, xb) pairs.
+inline void put_rec16(uint32_t *w, uint32_t head, uint32_t cnt, uint32_t flags, const uint32_t h[6], uint32_t ovf) {
+  w[0] = head | ((std::min(cnt, 255u) | (flags << 8)) << 16);
+  w[1] = h[0] | (h[1] << 16);
+  w[2] = h[2] | (h[3] << 16);
+  w[3] = cnt > 2 ? ovf : h[4] | (h[5] << 16);
+}
+inline void get_rec16(const uint32_t *w, uint32_t &head, uint32_t &cnt, uint32_t &flags, uint32_t h[6], uint32_t &ovf) {
+  head = w[0] & 0xffffu; cnt = (w[0] >> 16) & 0xffu; flags = w[0] >> 24;
+  h[0] = w[1] & 0xffffu; h[1] = w[1] >> 16; h[2] = w[2] & 0xffffu; h[3] = w[2] >> 16; h[4] = w[3] & 0xffffu; h[5] = w[3] >> 16;
+  ovf = w[3];
+}
+struct FactorRec {
+  uint32_t tgt = 0, cnt = 0, flags = 0;
+  uint32_t ldu[2][3] = {};  // cnt <= 2: the products
+  uint32_t ovf = 0;         // cnt > 2: cnt triples from ovf16[ovf]
+  void pack(uint32_t *w) const { put_rec16(w, tgt, cnt, flags, &ldu[0][0], ovf); }
+  static FactorRec unpack(const uint32_t *w) {
+    FactorRec r;
+    get_rec16(w, r.tgt, r.cnt, r.flags, &r.ldu[0][0], r.ovf);
+    return r;
+  }
+  // the operand reads of an inline record in role order (target, then l, d, u per product)
+  int operands(uint32_t f[7]) const {
+    f[0] = tgt;
+    for (uint32_t j = 0; j < cnt; j++) for (int w = 0; w < 3; w++) f[1 + 3 * j + w] = ldu[j][w];
+    return 1 + 3 * (int)cnt;
+  }
+};
+struct BackRec {
+  uint32_t x = 0, cnt = 0, flags = 0;
+  uint32_t d = 0, uxb[2][2] = {};  // cnt <= 2: the products
+  uint32_t ovf = 0;                // cnt > 2: cnt pairs from ovf16[ovf]
+  void pack(uint32_t *w) const {
+    const uint32_t h[6] = {d, uxb[0][0], uxb[0][1], uxb[1][0], uxb[1][1], 0u};
+    put_rec16(w, x, cnt, flags, h, ovf);
+  }
+  static BackRec unpack(const uint32_t *w) {
+    BackRec r;
+    uint32_t h[6];
+    get_rec16(w, r.x, r.cnt, r.flags, h, r.ovf);
+    r.d = h[0]; r.uxb[0][0] = h[1]; r.uxb[0][1] = h[2]; r.uxb[1][0] = h[3]; r.uxb[1][1] = h[4];
+    return r;
+  }
+  int operands(uint32_t f[7]) const {  // x, d, then u, xb per product
+    f[0] = x; f[1] = d;
+    for (uint32_t j = 0; j < cnt; j++) { f[2 + 2 * j] = uxb[j][0]; f[3 + 2 * j] = uxb[j][1]; }
+    return 2 + 2 * (int)cnt;
+  }
+};
+// Row record, sixteen half-words in eight words: [0] a_ii  [1] meta = pivots | has_o << (4 + i) | flags << 8  [2] y_i, then
+// per pivot k six half-words L_ik, d_k, U_ki, y_k, U_k,o, a_i,o; [15] spare.
+struct RowRec {
+  uint16_t h[16] = {0};
+  uint16_t &a_ii() { return h[0]; }
+  uint16_t &meta() { return h[1]; }
+  uint16_t &y_i() { return h[2]; }
+  uint16_t *pivot(size_t i) { return h + 3 + 6 * i; }
+  uint32_t pivots() const { return h[1] & 3u; }
+  bool has_other(size_t i) const { return (h[1] >> (4 + i)) & 1u; }
+  void pack(uint32_t *w) const { for (int q = 0; q < 8; q++) w[q] = (uint32_t)h[2 * q] | ((uint32_t)h[2 * q + 1] << 16); }
+  static RowRec unpack(const uint32_t *w) {
+    RowRec r;
+    for (int q = 0; q < 8; q++) { r.h[2 * q] = (uint16_t)(w[q] & 0xffffu); r.h[2 * q + 1] = (uint16_t)(w[q] >> 16); }
+    return r;
+  }
+};
 }  // namespace
 
 int64_t spicey_algorithmic_bytes(const SpiceyDesc *d, int32_t nnzA, int32_t nnzLU) {
@@ -342,18 +433,20 @@ void spicey_bank_cost(const HostProgram &hp, int64_t *cycles, int64_t *ideal) {
     const bool ktask = p >= nL;
     for (uint32_t g0 = 0; g0 < hp.ph_cnt[p]; g0 += 32) {
       const uint32_t g1 = std::min(hp.ph_cnt[p], g0 + 32);
+      uint32_t f[32][7];
+      int nf[32];  // operand reads of every lane's record (0: its operands are in the overflow list)
+      for (uint32_t t = g0; t < g1; t++) {
+        const uint32_t *r = &hp.rec16[((size_t)hp.ph_first[p] + t) * 4];
+        if (FactorRec::unpack(r).cnt > 2) nf[t - g0] = 0;  // (the count sits in the same place in both kinds)
+        else nf[t - g0] = ktask ? BackRec::unpack(r).operands(f[t - g0]) : FactorRec::unpack(r).operands(f[t - g0]);
+      }
       for (int role = 0; role < 7; role++) {
         std::vector<std::vector<uint32_t>> bank(32);
         bool any = false;
-        for (uint32_t t = g0; t < g1; t++) {
-          const uint32_t *r = &hp.rec16[((size_t)hp.ph_first[p] + t) * 4];
-          const uint32_t cnt = (r[0] >> 16) & 0xffu;
-          if (cnt > 2) continue;
-          const uint32_t f[7] = {r[0] & 0xffffu, r[1] & 0xffffu, r[1] >> 16, r[2] & 0xffffu, r[2] >> 16, r[3] & 0xffffu, r[3] >> 16};
-          const int nf = ktask ? (cnt == 0 ? 2 : cnt == 1 ? 4 : 6) : (cnt == 0 ? 1 : cnt == 1 ? 4 : 7);
-          if (role >= nf) continue;
-          auto &b = bank[f[role] & 31];
-          if (std::find(b.begin(), b.end(), f[role]) == b.end()) b.push_back(f[role]);
+        for (uint32_t t = 0; t < g1 - g0; t++) {
+          if (role >= nf[t]) continue;
+          auto &b = bank[f[t][role] & 31];
+          if (std::find(b.begin(), b.end(), f[t][role]) == b.end()) b.push_back(f[t][role]);
           any = true;
         }
         if (!any) continue;
@@ -366,7 +459,7 @@ void spicey_bank_cost(const HostProgram &hp, int64_t *cycles, int64_t *ideal) {
   }
 }
 
-// Two candidate numberings of the L+U entries (see build_program_impl): slot-major ("bank-aware") and plain CSR
+// Two candidate numberings of the L+U entries (see symbolic_factor): slot-major ("bank-aware") and plain CSR
 // order.  For programs that run from LDS (16-bit records) both are compiled and the one whose operand reads cost fewer
 // LDS cycles is kept (chains: 2.65 -> 1.88 conflict factor; small meshes are sometimes better off in CSR order).
 // Circuits on the global-workspace path keep the CSR order: LDS banks do not matter there.
@@ -417,14 +510,109 @@ int32_t spicey_check_desc(const SpiceyDesc *d, std::string &err) {
   return SPICEY_OK;
 }
 
-static int32_t build_program_impl(const SpiceyDesc *d, HostProgram &hp, std::string &err, const bool slot_major, int front_cut, const bool pcr_top, const bool hybrid) {
-  const int32_t rc0 = spicey_check_desc(d, err);
-  if (rc0 != SPICEY_OK) return rc0;
-  const int nN = d->n_nodes, nR = d->nR, nC = d->nC, nL = d->nL, nV = d->nV, nS = d->nS, nD = d->nD;
+// =============================================================================================
+// The builder.  build_program_impl (below) is the list of stages; each stage is one function whose signature says what it
+// reads (const &) and what it fills (&).  Two plain structs carry the products from stage to stage; what the device or the
+// host runtime consumes goes straight into the HostProgram.
+namespace {
+
+struct Pattern {
+  int n = 0, nN = 0, nOut = 0;
+  Adj arow;   // A by rows, original numbering (stage 2b gives a structurally singular matrix a full diagonal)
+  Adj cand;   // candidate pivot rows of every column, the voltage-source incidence rows (numerically +-1) first
+  std::vector<int> row_of_col, col_of_row;  // the zero-free diagonal: column c is pivoted on row row_of_col[c]
+  std::vector<int> forced;  // vertices eliminated first: matched nodes of floating sources, then their branch unknowns
+  Adj g;      // symmetrised pattern of B = P A (B[c][*] = A[row_of_col[c]][*]), original column numbering
+};
+
+struct Factor {
+  Adj upper;     // struct of row k right of the diagonal = struct of column k below it (pivot positions)
+  Adj children;  // elimination tree (hp.parent the other way round)
+  std::vector<std::vector<int>> by_level;  // pivots of every elimination-tree level, ascending
+  EntryIndex E;
+  std::vector<int> diag;  // entry id of every pivot's diagonal
+  int nLU = 0, nLevels = 1;
+  int Lc = 0;                  // the front cut in effect (0: no fronts)
+  std::vector<int> front_of;   // front of every pivot at or above the cut, -1 below
+  std::vector<int> bin_of;     // bin of every pivot below the cut (nBins > 0), -1 above
+  int nBins = 0;
+  std::vector<char> in_top;    // pivots of the tridiagonal top
+  int pcrL = 0;                // its first level (0: none)
+  std::vector<std::vector<uint32_t>> stat, dyn;  // per entry: static / dynamic stamps (conductance index | sign)
+};
+
+typedef std::pair<uint32_t, std::vector<uint32_t>> Task;  // (target, its products as flat (l, d, u) triples)
+struct SliceLists {  // one sliced-ELL task list of the HostProgram
+  std::vector<SpiceySlice> &slice;
+  std::vector<uint32_t> &tgt, &cnt, &pairs;
+  uint32_t size() const { return (uint32_t)slice.size(); }
+  void pack(std::vector<Task> &tasks) const { pack_slices<3>(tasks, slice, tgt, cnt, pairs); }
+};
+
+// The multiply-adds of factor level l in generation order: per pivot k of the level and row a of its structure the
+// entries (a, b) for every b of the structure, then the fused forward elimination of the right-hand side.
+// emit(target, L entry, diagonal, U entry, slot of a in upper[k], slot of b (-1: right-hand side), k)
+template <class Emit>
+void level_products(const Factor &F, int l, Emit &&emit) {
+  for (int k : F.by_level[l]) {
+    const std::vector<int> &S = F.upper[k];
+    for (int ia = 0; ia < (int)S.size(); ia++) {
+      const int a = S[ia];
+      const uint32_t le = (uint32_t)F.E.find(a, k);
+      for (int ib = 0; ib < (int)S.size(); ib++)
+        emit((uint32_t)F.E.find(a, S[ib]), le, (uint32_t)F.diag[k], (uint32_t)F.E.find(k, S[ib]), ia, ib, k);
+      emit((uint32_t)(F.nLU + a), le, (uint32_t)F.diag[k], (uint32_t)(F.nLU + k), ia, -1, k);
+    }
+  }
+}
+
+// Runs of equal target in a sorted product list (fields tgt, l, d, u): emit(first product of the run, its flat triples)
+template <class P, class Emit>
+void group_by_target(const std::vector<P> &prods, Emit &&emit) {
+  for (size_t i = 0; i < prods.size();) {
+    size_t j = i;
+    std::vector<uint32_t> flat;
+    while (j < prods.size() && prods[j].tgt == prods[i].tgt) {
+      flat.push_back(prods[j].l); flat.push_back(prods[j].d); flat.push_back(prods[j].u);
+      j++;
+    }
+    emit(prods[i], std::move(flat));
+    i = j;
+  }
+}
+
+// Tasks dealt to their bins and every bin packed on its own; bin_first receives the first slice of each bin and the end.
+// A task whose bin is negative goes to rest() instead.  Returns the products packed.
+template <class Bin, class Rest>
+int64_t pack_by_bin(std::vector<Task> &tasks, int nBins, Bin &&bin, Rest &&rest, std::vector<uint32_t> &bin_first, const SliceLists &out) {
+  std::vector<std::vector<Task>> per_bin(nBins);
+  int64_t products = 0;
+  for (auto &tk : tasks) {
+    const int b = bin(tk);
+    if (b < 0) { rest(tk); continue; }
+    products += (int64_t)tk.second.size() / 3;
+    per_bin[b].push_back(std::move(tk));
+  }
+  for (int b = 0; b < nBins; b++) {
+    bin_first.push_back(out.size());
+    out.pack(per_bin[b]);
+  }
+  bin_first.push_back(out.size());
+  return products;
+}
+
+struct Prod { uint32_t tgt, l, d, u; };
+inline bool by_target(const Prod &x, const Prod &y) { return x.tgt < y.tgt; }
+
+// ---- 1. pattern of A, by rows and by columns (original numbering); header counts ----------------
+void build_pattern(const SpiceyDesc &d, Pattern &P, HostProgram &hp) {
+  const int nN = d.n_nodes, nR = d.nR, nC = d.nC, nL = d.nL, nV = d.nV, nS = d.nS, nD = d.nD;
   const int n = nN + nV;
-  const int nOut = (d->n_out > 0 && d->out_nodes) ? d->n_out : nN;
-  // ---- 1. pattern of A, by rows and by columns (original numbering) ---------------------------
-  Adj arow(n), acol(n);
+  P.n = n; P.nN = nN;
+  P.nOut = (d.n_out > 0 && d.out_nodes) ? d.n_out : nN;
+  Adj &arow = P.arow;
+  Adj acol(n);
+  arow.assign(n, {});
   auto add = [&](int r, int c) {
     if (r < 0 || c < 0) return;
     arow[r].push_back(c);
@@ -437,126 +625,130 @@ static int32_t build_program_impl(const SpiceyDesc *d, HostProgram &hp, std::str
       if (i1 >= 0 && i2 >= 0) { add(i1, i2); add(i2, i1); }
     }
   };
-  two_terminal(d->R_n1, d->R_n2, nR);
-  two_terminal(d->C_n1, d->C_n2, nC);
-  two_terminal(d->L_n1, d->L_n2, nL);
-  two_terminal(d->S_n1, d->S_n2, nS);
-  two_terminal(d->D_np, d->D_nm, nD);
+  two_terminal(d.R_n1, d.R_n2, nR);
+  two_terminal(d.C_n1, d.C_n2, nC);
+  two_terminal(d.L_n1, d.L_n2, nL);
+  two_terminal(d.S_n1, d.S_n2, nS);
+  two_terminal(d.D_np, d.D_nm, nD);
   // rows of each column with the voltage-source incidence rows FIRST (numerically +-1: preferred pivots)
   Adj vrows(n);
   for (int k = 0; k < nV; k++) {
-    int i1 = d->V_n1[k] - 1, i2 = d->V_n2[k] - 1, j = nN + k;
+    int i1 = d.V_n1[k] - 1, i2 = d.V_n2[k] - 1, j = nN + k;
     if (i1 == i2) continue;  // +1-1 cancels numerically; leave the branch row empty -> singular
     add(i1, j); add(i2, j); add(j, i1); add(j, i2);
     if (i1 >= 0) { vrows[i1].push_back(j); vrows[j].push_back(i1); }
     if (i2 >= 0) { vrows[i2].push_back(j); vrows[j].push_back(i2); }
   }
-  hp.nnzA = 0;
   for (int r = 0; r < n; r++) { sort_unique(arow[r]); hp.nnzA += (int)arow[r].size(); }
-  Adj cand(n);
+  P.cand.assign(n, {});
   for (int c = 0; c < n; c++) {
     sort_unique(acol[c]);
     std::vector<int> pref = vrows[c];
     sort_unique(pref);
-    cand[c] = pref;
+    P.cand[c] = pref;
     for (int r : acol[c])
-      if (!std::binary_search(pref.begin(), pref.end(), r)) cand[c].push_back(r);
+      if (!std::binary_search(pref.begin(), pref.end(), r)) P.cand[c].push_back(r);
   }
 
-  hp.hdr = SpiceyProg{};
   hp.hdr.n = n; hp.hdr.nR = nR; hp.hdr.nC = nC; hp.hdr.nL = nL; hp.hdr.nV = nV; hp.hdr.nS = nS; hp.hdr.nD = nD;
   hp.hdr.nU = nC + nL + nV + nD + nV;  /* + one slot per source for the NEXT step's value (v2, written during the last backward phase) */ hp.hdr.nGdyn = nS + nD; hp.hdr.nGstat = nR + nC + nL + 1;
-  hp.hdr.nOut = nOut; hp.hdr.nCur = nR + nC + nL + nV + nS + nD;
+  hp.hdr.nOut = P.nOut; hp.hdr.nCur = nR + nC + nL + nV + nS + nD;
+}
 
-  // ---- 2. zero-free diagonal ------------------------------------------------------------------
-  // 2a. STRUCTURED matching (numerically safe static pivots, replaces what partial pivoting does in solveReal.ts:15-34):
-  // every source k is paired with one of its non-ground terminals n_k by a bipartite matching sources <-> nodes; column
-  // n_k takes the branch row j_k (pivot +-1), column j_k takes the KCL row of n_k (pivot +-1), every other node keeps its
-  // own KCL row.  A GROUNDED source's two pivots can never be touched by another elimination (its branch row and branch
-  // column hold a single entry each), so it may sit anywhere in the order.  A FLOATING source's pair is eliminated before
-  // everything else (all node columns n_k, then all branch columns j_k): the branch rows restricted to the matched nodes
-  // are the incidence matrix of a forest with a unique perfect matching, so every leading minor is +-1 and both pivots of
-  // every pair are exactly +-1 in any order; what remains is the conductance matrix of the circuit with those sources
-  // contracted (v(n_k) = v(m_k) + V_k) — a symmetric M-matrix, safe under any diagonal pivot order.  (With a generic
-  // transversal and the pair left inside the nested dissection, eliminating a neighbour first turned the +-1 pivot into
-  // 1 - g/g = 0: `V1 a b / R1 a b / R2 a 0` was reported singular.)
-  std::vector<int> row_of_col(n, -1);
-  std::vector<int> forced;  // vertices eliminated first: matched nodes of floating sources, then their branch unknowns
-  bool structured = true;
-  {
-    std::vector<int> node_of_src(nV, -1), src_of_node(nN, -1);
-    std::vector<std::vector<int>> src_at(nN);
-    std::vector<std::array<int, 2>> term(nV);
-    std::vector<int> deg(nN, 0);
-    for (int c = 0; c < nN; c++) deg[c] = (int)arow[c].size();
-    for (int k = 0; k < nV; k++) {
-      int i1 = d->V_n1[k] - 1, i2 = d->V_n2[k] - 1;
-      if (i1 == i2) { structured = false; break; }  // shorted source: empty branch row
-      // lower-degree terminal first: eliminating the matched node early makes a clique of its neighbours
-      if (i1 >= 0 && i2 >= 0 && deg[i2] < deg[i1]) std::swap(i1, i2);
-      if (i1 < 0) std::swap(i1, i2);
-      term[k] = {i1, i2};
-      if (i1 >= 0) src_at[i1].push_back(k);
-      if (i2 >= 0) src_at[i2].push_back(k);
-    }
-    std::vector<int> seen_s(nV, -1), seen_n(nN, -1);
-    // augment from a node: the node takes one of its sources, which may push that source's node elsewhere
-    std::function<bool(int, int)> try_node = [&](int node, int stamp) -> bool {
-      for (int s2 : src_at[node]) {
-        if (seen_s[s2] == stamp) continue;
-        seen_s[s2] = stamp;
-        const int other = node_of_src[s2];
-        if (other < 0 || try_node(other, stamp)) { node_of_src[s2] = node; src_of_node[node] = s2; return true; }
-      }
-      return false;
-    };
-    std::function<bool(int, int)> try_src = [&](int s2, int stamp) -> bool {
-      for (int t : term[s2]) {
-        if (t < 0 || seen_n[t] == stamp) continue;
-        seen_n[t] = stamp;
-        const int other = src_of_node[t];
-        if (other < 0 || try_src(other, stamp)) { node_of_src[s2] = t; src_of_node[t] = s2; return true; }
-      }
-      return false;
-    };
-    if (structured) {
-      // nodes without a structural diagonal (only sources attached) must be a source's matched node
-      for (int c = 0; c < nN && structured; c++)
-        if (!std::binary_search(arow[c].begin(), arow[c].end(), c) && !try_node(c, c)) structured = false;
-      for (int k = 0; k < nV && structured; k++)
-        if (node_of_src[k] < 0 && !try_src(k, k)) structured = false;
-    }
-    if (structured) {
-      for (int c = 0; c < nN; c++) row_of_col[c] = src_of_node[c] >= 0 ? nN + src_of_node[c] : c;
-      for (int k = 0; k < nV; k++) row_of_col[nN + k] = node_of_src[k];
-      for (int k = 0; k < nV; k++)
-        if (term[k][0] >= 0 && term[k][1] >= 0) forced.push_back(node_of_src[k]);
-      const size_t nf = forced.size();
-      for (size_t i = 0; i < nf; i++) forced.push_back(nN + src_of_node[forced[i]]);
-    }
+// ---- 2. zero-free diagonal ------------------------------------------------------------------
+// 2a. STRUCTURED matching (numerically safe static pivots, replaces what partial pivoting does in solveReal.ts:15-34):
+// every source k is paired with one of its non-ground terminals n_k by a bipartite matching sources <-> nodes; column
+// n_k takes the branch row j_k (pivot +-1), column j_k takes the KCL row of n_k (pivot +-1), every other node keeps its
+// own KCL row.  A GROUNDED source's two pivots can never be touched by another elimination (its branch row and branch
+// column hold a single entry each), so it may sit anywhere in the order.  A FLOATING source's pair is eliminated before
+// everything else (all node columns n_k, then all branch columns j_k): the branch rows restricted to the matched nodes
+// are the incidence matrix of a forest with a unique perfect matching, so every leading minor is +-1 and both pivots of
+// every pair are exactly +-1 in any order; what remains is the conductance matrix of the circuit with those sources
+// contracted (v(n_k) = v(m_k) + V_k) — a symmetric M-matrix, safe under any diagonal pivot order.  (With a generic
+// transversal and the pair left inside the nested dissection, eliminating a neighbour first turned the +-1 pivot into
+// 1 - g/g = 0: `V1 a b / R1 a b / R2 a 0` was reported singular.)
+// Fills row_of_col and forced; false: the matching cannot express this circuit (stage 2b takes over).
+bool match_sources(const SpiceyDesc &d, const Adj &arow, std::vector<int> &row_of_col, std::vector<int> &forced) {
+  const int nN = d.n_nodes, nV = d.nV;
+  std::vector<int> node_of_src(nV, -1), src_of_node(nN, -1);
+  std::vector<std::vector<int>> src_at(nN);
+  std::vector<std::array<int, 2>> term(nV);
+  std::vector<int> deg(nN, 0);
+  for (int c = 0; c < nN; c++) deg[c] = (int)arow[c].size();
+  for (int k = 0; k < nV; k++) {
+    int i1 = d.V_n1[k] - 1, i2 = d.V_n2[k] - 1;
+    if (i1 == i2) return false;  // shorted source: empty branch row
+    // lower-degree terminal first: eliminating the matched node early makes a clique of its neighbours
+    if (i1 >= 0 && i2 >= 0 && deg[i2] < deg[i1]) std::swap(i1, i2);
+    if (i1 < 0) std::swap(i1, i2);
+    term[k] = {i1, i2};
+    if (i1 >= 0) src_at[i1].push_back(k);
+    if (i2 >= 0) src_at[i2].push_back(k);
   }
+  std::vector<int> seen_s(nV, -1), seen_n(nN, -1);
+  // augment from a node: the node takes one of its sources, which may push that source's node elsewhere
+  std::function<bool(int, int)> try_node = [&](int node, int stamp) -> bool {
+    for (int s2 : src_at[node]) {
+      if (seen_s[s2] == stamp) continue;
+      seen_s[s2] = stamp;
+      const int other = node_of_src[s2];
+      if (other < 0 || try_node(other, stamp)) { node_of_src[s2] = node; src_of_node[node] = s2; return true; }
+    }
+    return false;
+  };
+  std::function<bool(int, int)> try_src = [&](int s2, int stamp) -> bool {
+    for (int t : term[s2]) {
+      if (t < 0 || seen_n[t] == stamp) continue;
+      seen_n[t] = stamp;
+      const int other = src_of_node[t];
+      if (other < 0 || try_src(other, stamp)) { node_of_src[s2] = t; src_of_node[t] = s2; return true; }
+    }
+    return false;
+  };
+  // nodes without a structural diagonal (only sources attached) must be a source's matched node
+  for (int c = 0; c < nN; c++)
+    if (!std::binary_search(arow[c].begin(), arow[c].end(), c) && !try_node(c, c)) return false;
+  for (int k = 0; k < nV; k++)
+    if (node_of_src[k] < 0 && !try_src(k, k)) return false;
+  for (int c = 0; c < nN; c++) row_of_col[c] = src_of_node[c] >= 0 ? nN + src_of_node[c] : c;
+  for (int k = 0; k < nV; k++) row_of_col[nN + k] = node_of_src[k];
+  for (int k = 0; k < nV; k++)
+    if (term[k][0] >= 0 && term[k][1] >= 0) forced.push_back(node_of_src[k]);
+  const size_t nf = forced.size();
+  for (size_t i = 0; i < nf; i++) forced.push_back(nN + src_of_node[forced[i]]);
+  return true;
+}
+
+void match_rows(const SpiceyDesc &d, Pattern &P, HostProgram &hp) {
+  const int n = P.n;
+  P.row_of_col.assign(n, -1);
   // 2b. anything the structured matching cannot express (it fails exactly when sources form a loop or a node hangs on
   // nothing but an over-subscribed source): generic maximum transversal; a failure there is a structurally singular matrix
-  if (!structured && !max_transversal(n, cand, row_of_col)) {
+  if (!match_sources(d, P.arow, P.row_of_col, P.forced) && !max_transversal(n, P.cand, P.row_of_col)) {
     hp.structurally_singular = true;
     // keep a trivially valid (identity) program so that the handle can exist; run() reports singular
-    row_of_col.resize(n);
-    std::iota(row_of_col.begin(), row_of_col.end(), 0);
-    for (int c = 0; c < n; c++) { arow[c].push_back(c); sort_unique(arow[c]); }
+    P.row_of_col.resize(n);
+    std::iota(P.row_of_col.begin(), P.row_of_col.end(), 0);
+    for (int c = 0; c < n; c++) { P.arow[c].push_back(c); sort_unique(P.arow[c]); }
   }
-  std::vector<int> col_of_row(n);
-  for (int c = 0; c < n; c++) col_of_row[row_of_col[c]] = c;
+  P.col_of_row.assign(n, 0);
+  for (int c = 0; c < n; c++) P.col_of_row[P.row_of_col[c]] = c;
+}
 
-  // ---- 3. ordering on the symmetrised pattern of B = P A (B[c][*] = A[row_of_col[c]][*]) -------
-  Adj g(n);
+// ---- 3. ordering on the symmetrised pattern of B = P A (B[c][*] = A[row_of_col[c]][*]) -------
+// Fills P.g, hp.cpos and hp.rpos; false: the ordering lost vertices.
+bool order_pivots(Pattern &P, HostProgram &hp) {
+  const int n = P.n;
+  Adj &g = P.g;
+  g.assign(n, {});
   for (int c = 0; c < n; c++)
-    for (int c2 : arow[row_of_col[c]])
+    for (int c2 : P.arow[P.row_of_col[c]])
       if (c2 != c) { g[c].push_back(c2); g[c2].push_back(c); }
   for (int c = 0; c < n; c++) sort_unique(g[c]);
   // the forced vertices leave the graph first (their fill joins their remaining neighbours); nested dissection orders the rest
   Adj g2 = g;
   std::vector<char> gone(n, 0);
-  for (int v : forced) {
+  for (int v : P.forced) {
     std::vector<int> nb;
     for (int w : g2[v])
       if (!gone[w]) nb.push_back(w);
@@ -567,27 +759,32 @@ static int32_t build_program_impl(const SpiceyDesc *d, HostProgram &hp, std::str
     gone[v] = 1;
   }
   NDOrder nd(g2);
-  for (int v : forced) nd.owner[v] = -1;
+  for (int v : P.forced) nd.owner[v] = -1;
   nd.run();
-  if (nd.order.size() + forced.size() != (size_t)n) { err = "internal: ordering lost vertices"; return SPICEY_ERR_BAD_DESC; }
+  if (nd.order.size() + P.forced.size() != (size_t)n) return false;
   hp.cpos.assign(n, -1);
   {
     int p = 0;
-    for (int v : forced) hp.cpos[v] = p++;
+    for (int v : P.forced) hp.cpos[v] = p++;
     for (int v : nd.order) hp.cpos[v] = p++;
   }
   hp.rpos.assign(n, -1);
-  for (int r = 0; r < n; r++) hp.rpos[r] = hp.cpos[col_of_row[r]];
+  for (int r = 0; r < n; r++) hp.rpos[r] = hp.cpos[P.col_of_row[r]];
+  return true;
+}
 
-  // ---- 4. symbolic factorisation (symmetric pattern), etree, levels ----------------------------
-  Adj upper(n);  // struct of row k right of the diagonal = struct of column k below it
+// ---- 4. symbolic factorisation (symmetric pattern), etree, levels, entry numbering --------------
+void symbolic_factor(const SpiceyDesc &d, const Pattern &P, bool slot_major, Factor &F, HostProgram &hp) {
+  const int n = P.n;
+  Adj &upper = F.upper, &children = F.children;
+  upper.assign(n, {});
   for (int c = 0; c < n; c++)
-    for (int c2 : g[c]) {
+    for (int c2 : P.g[c]) {
       int a = hp.cpos[c], b = hp.cpos[c2];
       if (b > a) upper[a].push_back(b);
     }
   hp.parent.assign(n, -1);
-  Adj children(n);
+  children.assign(n, {});
   for (int k = 0; k < n; k++) {
     std::vector<int> &S = upper[k];
     for (int c : children[k])
@@ -607,8 +804,11 @@ static int32_t build_program_impl(const SpiceyDesc *d, HostProgram &hp, std::str
     hp.level[k] = l;
     nLevels = std::max(nLevels, l + 1);
   }
+  F.nLevels = nLevels;
+  F.by_level.assign(nLevels, {});
+  for (int k = 0; k < n; k++) F.by_level[hp.level[k]].push_back(k);
   // CSR of L+U rows
-  EntryIndex E;
+  EntryIndex &E = F.E;
   {
     Adj rows(n);
     for (int k = 0; k < n; k++) {
@@ -624,6 +824,7 @@ static int32_t build_program_impl(const SpiceyDesc *d, HostProgram &hp, std::str
     for (int r = 0; r < n; r++) E.col.insert(E.col.end(), rows[r].begin(), rows[r].end());
   }
   const int nLU = E.ptr[n];
+  F.nLU = nLU;
   hp.hdr.nLU = nLU; hp.hdr.nW = nLU + n; hp.hdr.nLevels = nLevels;  // (nW grows by the constant-one slot when fronts are on, step 4b)
   {
     // classes of the CSR positions
@@ -637,8 +838,8 @@ static int32_t build_program_impl(const SpiceyDesc *d, HostProgram &hp, std::str
         if (i1 >= 0 && i2 >= 0) { m(i1, i2); m(i2, i1); }
       }
     };
-    mark2(d->S_n1, d->S_n2, nS);
-    mark2(d->D_np, d->D_nm, nD);
+    mark2(d.S_n1, d.S_n2, d.nS);
+    mark2(d.D_np, d.D_nm, d.nD);
     for (int k = 0; k < n; k++)
       for (int a : upper[k])
         for (int b : upper[k]) is_tgt[E.pos(a, b)] = 1;
@@ -674,12 +875,16 @@ static int32_t build_program_impl(const SpiceyDesc *d, HostProgram &hp, std::str
     for (int r = 0; r < n; r++)
       for (int p = E.ptr[r]; p < E.ptr[r + 1]; p++) { E.row_of_id[E.id_of_pos[p]] = r; E.col_of_id[E.id_of_pos[p]] = E.col[p]; }
   }
-  std::vector<int> diag(n);
-  for (int k = 0; k < n; k++) diag[k] = E.find(k, k);
+  F.diag.assign(n, 0);
+  for (int k = 0; k < n; k++) F.diag[k] = E.find(k, k);
+}
 
-  // ---- 4b. dense fronts above the cut (multifrontal upper tree, fronts_exec.h) -------------------------------
-  // Pivots of level >= Lc leave the level-scheduled task lists: consecutive pivots whose row structures nest
-  // (upper[k-1] = {k} + upper[k]: a separator of the nested dissection) form one supernode = one dense front.
+// ---- 4b. dense fronts above the cut (multifrontal upper tree, fronts_exec.h) -------------------------------
+// Pivots of level >= Lc leave the level-scheduled task lists: consecutive pivots whose row structures nest
+// (upper[k-1] = {k} + upper[k]: a separator of the nested dissection) form one supernode = one dense front.
+// The level of the cut for a request `front_cut` (-1: automatic).
+int choose_front_cut(const SpiceyDesc &d, int front_cut, int n, const Factor &F, const HostProgram &hp) {
+  const int nD = d.nD, nS = d.nS, nLU = F.nLU, nLevels = F.nLevels;
   int Lc = front_cut;
   if (Lc < 0) {
     // automatic: only where the long single-pivot chains of the top separators dominate (large, nonlinear circuits;
@@ -693,7 +898,7 @@ static int32_t build_program_impl(const SpiceyDesc *d, HostProgram &hp, std::str
     // Where the circuit fits LDS, the 16-bit interpreter (one workgroup per instance) is the alternative and wins once a
     // group would be smaller than 8 workgroups (24 x 24: 32 instances 0.225 -> 0.186 with fronts, 64: 0.225 -> 0.209, 128:
     // 0.225 -> 0.304; 20 x 20 x 64: 0.152 -> 0.185): below ~16 k entries the fronts are for up to 32 instances only.
-    const int64_t min_lu = d->n_inst <= 32 ? 6000 : 16000;
+    const int64_t min_lu = d.n_inst <= 32 ? 6000 : 16000;
     // Level of the cut: 10, and 11 from ~7 000 unknowns on (round 3, after the front phases were rewritten for instruction
     // count; R/C/diode meshes, one instance, ms per step at cut 9 / 10 / 11 / 12: 34 x 34 0.156 / 0.146 / 0.150 / 0.153,
     // 70 x 70 0.241 / 0.232 / 0.238 / 0.241, 85 x 85 - / 0.323 / 0.321 / 0.332, 100 x 100 0.379 / 0.381 / 0.368 / 0.376,
@@ -703,9 +908,19 @@ static int32_t build_program_impl(const SpiceyDesc *d, HostProgram &hp, std::str
     if (const char *e = getenv("SPICEY_FRONT_CUT")) Lc = atoi(e);  // experiments
   }
   if (Lc >= nLevels || hp.structurally_singular) Lc = 0;
-  std::vector<int> front_of(n, -1);
-  hp.fronts.clear(); hp.fr_asm.clear(); hp.fr_bnd.clear(); hp.fr_child.clear(); hp.fr_rel.clear(); hp.front_work.clear();
-  if (Lc > 0) {
+  return Lc;
+}
+
+// Supernode merging, front geometry and assembly lists, child order, relative indices for the cut F.Lc.  A structure the
+// dense kernels cannot take falls back to F.Lc = 0.  Fills F.front_of, the front sections and the front header fields.
+void build_fronts(int n, Factor &F, HostProgram &hp) {
+  const Adj &upper = F.upper;
+  const EntryIndex &E = F.E;
+  const int nLU = F.nLU;
+  std::vector<int> &front_of = F.front_of;
+  front_of.assign(n, -1);
+  if (F.Lc > 0) {
+    const int Lc = F.Lc;
     auto pad16 = [](int x) { return (x + 15) & ~15; };
     const bool relax_fronts = !getenv("SPICEY_FRONT_EXACT");  // experiments: exact supernodes only
     int staged_mp = 176;
@@ -768,7 +983,7 @@ static int32_t build_program_impl(const SpiceyDesc *d, HostProgram &hp, std::str
       double work = 0;
       for (int i = 0; i < f.p; i++) {
         const int k = f.k0 + i;
-        hp.fr_asm.push_back((uint32_t)diag[k]); hp.fr_asm.push_back(((uint32_t)i << 16) | (uint32_t)i);  // row << 16 | column
+        hp.fr_asm.push_back((uint32_t)F.diag[k]); hp.fr_asm.push_back(((uint32_t)i << 16) | (uint32_t)i);  // row << 16 | column
         for (int b : upper[k]) {
           const int lb = loc(b);
           hp.fr_asm.push_back((uint32_t)E.find(k, b)); hp.fr_asm.push_back(((uint32_t)i << 16) | (uint32_t)lb);
@@ -819,7 +1034,7 @@ static int32_t build_program_impl(const SpiceyDesc *d, HostProgram &hp, std::str
       }
     }
     if (!ok) {  // structure the dense kernels cannot take: keep the task lists for everything
-      Lc = 0;
+      F.Lc = 0;
       hp.fronts.clear(); hp.fr_asm.clear(); hp.fr_bnd.clear(); hp.fr_child.clear(); hp.fr_rel.clear(); hp.front_work.clear();
       std::fill(front_of.begin(), front_of.end(), -1);
     } else {
@@ -828,12 +1043,17 @@ static int32_t build_program_impl(const SpiceyDesc *d, HostProgram &hp, std::str
     }
   }
   hp.hdr.nFronts = (int32_t)hp.fronts.size();
-  hp.hdr.front_cut = Lc;
+  hp.hdr.front_cut = F.Lc;
   hp.hdr.one_slot = nLU + n;
-  if (Lc > 0) hp.hdr.nW = nLU + n + 1;  // + the constant-one slot
-  // Subtree-local levels below the cut (program.h): bin_of[k] for every pivot below the cut.  The subtrees (rooted where
-  // the parent's level reaches the cut) are dealt into bins largest first, each to the lightest bin so far.
-  std::vector<int> bin_of(n, -1);
+  if (F.Lc > 0) hp.hdr.nW = nLU + n + 1;  // + the constant-one slot
+}
+
+// Subtree-local levels below the cut (program.h): bin_of[k] for every pivot below the cut.  The subtrees (rooted where
+// the parent's level reaches the cut) are dealt into bins largest first, each to the lightest bin so far.
+void build_bins(int n, Factor &F, HostProgram &hp) {
+  const int Lc = F.Lc;
+  std::vector<int> &bin_of = F.bin_of;
+  bin_of.assign(n, -1);
   int nBins = 0;
   if (Lc > 0) {
     int want = 128;
@@ -845,7 +1065,7 @@ static int32_t build_program_impl(const SpiceyDesc *d, HostProgram &hp, std::str
       const int p = hp.parent[k];
       if (p < 0 || hp.level[p] >= Lc) { sub_of[k] = (int)sub_work.size(); sub_work.push_back(0.0); }
       else sub_of[k] = sub_of[p];
-      const double u = (double)upper[k].size();
+      const double u = (double)F.upper[k].size();
       sub_work[sub_of[k]] += u * (u + 1.0) + 4.0;
     }
     nBins = std::min<int>(want, (int)sub_work.size());
@@ -863,12 +1083,17 @@ static int32_t build_program_impl(const SpiceyDesc *d, HostProgram &hp, std::str
       for (int k = 0; k < n; k++) if (sub_of[k] >= 0) bin_of[k] = bin_of_sub[sub_of[k]];
     }
   }
+  F.nBins = nBins;
   hp.hdr.nBins = nBins;
-  hp.bin_upd.clear(); hp.bin_bk.clear();
+}
 
-  // ---- 5a. stamp lists --------------------------------------------------------------------------
-  auto ent = [&](int r_orig, int c_orig) { return E.find(hp.rpos[r_orig], hp.cpos[c_orig]); };
-  std::vector<std::vector<uint32_t>> stat(nLU), dyn(nLU);
+// ---- 5a. stamp lists --------------------------------------------------------------------------
+// Fills F.stat / F.dyn and the stamp sections; false: a stamp fell outside the symbolic pattern.
+bool build_stamps(const SpiceyDesc &d, const Pattern &P, Factor &F, HostProgram &hp) {
+  const int nN = P.nN, n = P.n, nR = d.nR, nC = d.nC, nL = d.nL, nV = d.nV, nS = d.nS, nD = d.nD, nLU = F.nLU;
+  auto ent = [&](int r_orig, int c_orig) { return F.E.find(hp.rpos[r_orig], hp.cpos[c_orig]); };
+  std::vector<std::vector<uint32_t>> &stat = F.stat, &dyn = F.dyn;
+  stat.assign(nLU, {}); dyn.assign(nLU, {});
   bool lookup_failed = false;
   auto stamp2 = [&](std::vector<std::vector<uint32_t>> &dst, int n1, int n2, uint32_t gi) {
     int i1 = n1 - 1, i2 = n2 - 1;
@@ -881,14 +1106,14 @@ static int32_t build_program_impl(const SpiceyDesc *d, HostProgram &hp, std::str
     if (i2 >= 0) put(i2, i2, gi);
     if (i1 >= 0 && i2 >= 0) { put(i1, i2, gi | SPICEY_NEG); put(i2, i1, gi | SPICEY_NEG); }
   };
-  for (int i = 0; i < nR; i++) stamp2(stat, d->R_n1[i], d->R_n2[i], (uint32_t)i);
-  for (int i = 0; i < nC; i++) stamp2(stat, d->C_n1[i], d->C_n2[i], (uint32_t)(nR + i));
-  for (int i = 0; i < nL; i++) stamp2(stat, d->L_n1[i], d->L_n2[i], (uint32_t)(nR + nC + i));
-  for (int i = 0; i < nS; i++) stamp2(dyn, d->S_n1[i], d->S_n2[i], (uint32_t)i);
+  for (int i = 0; i < nR; i++) stamp2(stat, d.R_n1[i], d.R_n2[i], (uint32_t)i);
+  for (int i = 0; i < nC; i++) stamp2(stat, d.C_n1[i], d.C_n2[i], (uint32_t)(nR + i));
+  for (int i = 0; i < nL; i++) stamp2(stat, d.L_n1[i], d.L_n2[i], (uint32_t)(nR + nC + i));
+  for (int i = 0; i < nS; i++) stamp2(dyn, d.S_n1[i], d.S_n2[i], (uint32_t)i);
   if (!hp.structurally_singular) {
     const uint32_t one = (uint32_t)(nR + nC + nL);
     for (int k = 0; k < nV; k++) {  // stampVoltageSourceReal.ts:12-31
-      int i1 = d->V_n1[k] - 1, i2 = d->V_n2[k] - 1, j = nN + k;
+      int i1 = d.V_n1[k] - 1, i2 = d.V_n2[k] - 1, j = nN + k;
       if (i1 == i2) continue;
       auto put = [&](int r, int c, uint32_t v) {
         int e = ent(r, c);
@@ -901,15 +1126,14 @@ static int32_t build_program_impl(const SpiceyDesc *d, HostProgram &hp, std::str
       if (i2 >= 0) put(j, i2, one | SPICEY_NEG);
     }
   }
-  for (int i = 0; i < nD; i++) stamp2(dyn, d->D_np[i], d->D_nm[i], (uint32_t)(nS + i));
-  if (lookup_failed) { err = "internal: stamp outside the symbolic pattern"; return SPICEY_ERR_BAD_DESC; }
+  for (int i = 0; i < nD; i++) stamp2(dyn, d.D_np[i], d.D_nm[i], (uint32_t)(nS + i));
+  if (lookup_failed) return false;
 
   hp.ent_flag.assign(nLU, 0);
   for (int k = 0; k < n; k++)
-    if (hp.level[k] == 0) hp.ent_flag[diag[k]] |= 1;
-  hp.stat_ptr.assign(1, 0);
-  hp.stat_idx.clear();
-  hp.dyn_ent.clear(); hp.dyn_ptr.assign(1, 0); hp.dyn_idx.clear();
+    if (hp.level[k] == 0) hp.ent_flag[F.diag[k]] |= 1;
+  hp.stat_ptr = {0};
+  hp.dyn_ptr = {0};
   for (int e = 0; e < nLU; e++) {
     hp.stat_idx.insert(hp.stat_idx.end(), stat[e].begin(), stat[e].end());
     hp.stat_ptr.push_back((uint32_t)hp.stat_idx.size());
@@ -921,125 +1145,103 @@ static int32_t build_program_impl(const SpiceyDesc *d, HostProgram &hp, std::str
     }
   }
   hp.hdr.nDynEnt = (int32_t)hp.dyn_ent.size();
+  return true;
+}
 
-  // right-hand side (stampCurrentReal.ts:3-14: b[i+] -= I, b[i-] += I; order C, L, V, D)
-  {
-    std::vector<std::vector<std::pair<uint32_t, uint32_t>>> rows(n);  // (u idx|sign, gstat coef idx)
-    const uint32_t one = (uint32_t)(nR + nC + nL);
-    auto cur = [&](int np, int nm, uint32_t ui, uint32_t cof, bool negate_value) {
-      // contributes  -I to row np-1 and +I to row nm-1, where I = (negate_value ? -1 : 1) * cof * u[ui]
-      int ip = np - 1, im = nm - 1;
-      if (ip >= 0) rows[hp.rpos[ip]].emplace_back(ui | (negate_value ? 0u : SPICEY_NEG), cof);
-      if (im >= 0) rows[hp.rpos[im]].emplace_back(ui | (negate_value ? SPICEY_NEG : 0u), cof);
-    };
-    for (int i = 0; i < nC; i++) cur(d->C_n1[i], d->C_n2[i], (uint32_t)i, (uint32_t)(nR + i), true);  // Ieq = -Gc*vPrev
-    for (int i = 0; i < nL; i++) cur(d->L_n1[i], d->L_n2[i], (uint32_t)(nC + i), one, false);          // I = iPrev
-    for (int k = 0; k < nV; k++) rows[hp.rpos[nN + k]].emplace_back((uint32_t)(nC + nL + k), one);     // b[j] += V
-    for (int i = 0; i < nD; i++) cur(d->D_np[i], d->D_nm[i], (uint32_t)(nC + nL + nV + i), one, false);  // I = ieq
-    hp.rhs_ptr.assign(1, 0);
-    hp.rhs_idx.clear(); hp.rhs_cof.clear();
-    for (int r = 0; r < n; r++) {
-      for (auto &p : rows[r]) { hp.rhs_idx.push_back(p.first); hp.rhs_cof.push_back(p.second); }
-      hp.rhs_ptr.push_back((uint32_t)hp.rhs_idx.size());
-    }
-    hp.hdr.nRhsIdx = (int32_t)hp.rhs_idx.size();
+// right-hand side (stampCurrentReal.ts:3-14: b[i+] -= I, b[i-] += I; order C, L, V, D)
+void build_rhs(const SpiceyDesc &d, const Pattern &P, HostProgram &hp) {
+  const int nN = P.nN, n = P.n, nR = d.nR, nC = d.nC, nL = d.nL, nV = d.nV, nD = d.nD;
+  std::vector<std::vector<std::pair<uint32_t, uint32_t>>> rows(n);  // (u idx|sign, gstat coef idx)
+  const uint32_t one = (uint32_t)(nR + nC + nL);
+  auto cur = [&](int np, int nm, uint32_t ui, uint32_t cof, bool negate_value) {
+    // contributes  -I to row np-1 and +I to row nm-1, where I = (negate_value ? -1 : 1) * cof * u[ui]
+    int ip = np - 1, im = nm - 1;
+    if (ip >= 0) rows[hp.rpos[ip]].emplace_back(ui | (negate_value ? 0u : SPICEY_NEG), cof);
+    if (im >= 0) rows[hp.rpos[im]].emplace_back(ui | (negate_value ? SPICEY_NEG : 0u), cof);
+  };
+  for (int i = 0; i < nC; i++) cur(d.C_n1[i], d.C_n2[i], (uint32_t)i, (uint32_t)(nR + i), true);  // Ieq = -Gc*vPrev
+  for (int i = 0; i < nL; i++) cur(d.L_n1[i], d.L_n2[i], (uint32_t)(nC + i), one, false);          // I = iPrev
+  for (int k = 0; k < nV; k++) rows[hp.rpos[nN + k]].emplace_back((uint32_t)(nC + nL + k), one);   // b[j] += V
+  for (int i = 0; i < nD; i++) cur(d.D_np[i], d.D_nm[i], (uint32_t)(nC + nL + nV + i), one, false);  // I = ieq
+  hp.rhs_ptr = {0};
+  for (int r = 0; r < n; r++) {
+    for (auto &p : rows[r]) { hp.rhs_idx.push_back(p.first); hp.rhs_cof.push_back(p.second); }
+    hp.rhs_ptr.push_back((uint32_t)hp.rhs_idx.size());
   }
+  hp.hdr.nRhsIdx = (int32_t)hp.rhs_idx.size();
+}
 
-  // ---- 5b. factorisation tasks per level ---------------------------------------------------------
-  hp.lvl_slice.assign(1, 0);
-  hp.upd_slice.clear(); hp.upd_tgt.clear(); hp.upd_cnt.clear(); hp.upd_pairs.clear();
-  hp.n_products = 0;
-  std::vector<std::vector<int>> by_level(nLevels);
-  for (int k = 0; k < n; k++) by_level[hp.level[k]].push_back(k);
+// ---- 5b. factorisation tasks per level ---------------------------------------------------------
+void build_factor_slices(const Factor &F, HostProgram &hp) {
+  const EntryIndex &E = F.E;
+  const int nLU = F.nLU, nLevels = F.nLevels, Lc = F.Lc, nBins = F.nBins;
+  const SliceLists out{hp.upd_slice, hp.upd_tgt, hp.upd_cnt, hp.upd_pairs};
+  hp.lvl_slice = {0};
   std::map<uint32_t, std::vector<uint32_t>> iface;  // nBins > 0: products of the targets above the cut, by target
   // the pivot that owns a factor target: the smaller index of an entry, the row of a right-hand side
   auto owner_of = [&](uint32_t t) { return (int)t < nLU ? std::min(E.row_of_id[t], E.col_of_id[t]) : (int)t - nLU; };
   for (int l = 0; l < nLevels; l++) {
-    // (target, pivot, L entry, U entry) tuples, grouped by target in pivot order
-    struct Prod { uint32_t tgt, l, d, u; };
-    std::vector<Prod> prods;
     if (Lc > 0 && l >= Lc) {  // factored as dense fronts
       if (l == Lc && nBins > 0) {
         // the targets above the cut: one task each with the products of every level below the cut, in level order
-        std::vector<std::pair<uint32_t, std::vector<uint32_t>>> tasks;
+        std::vector<Task> tasks;
         for (auto &kv : iface) { hp.n_products += (int64_t)kv.second.size() / 3; tasks.emplace_back(kv.first, std::move(kv.second)); }
         iface.clear();
-        pack_slices<3>(tasks, hp.upd_slice, hp.upd_tgt, hp.upd_cnt, hp.upd_pairs);
+        out.pack(tasks);
       }
-      hp.lvl_slice.push_back((uint32_t)hp.upd_slice.size());
+      hp.lvl_slice.push_back(out.size());
       continue;
     }
-    for (int k : by_level[l]) {
-      const std::vector<int> &S = upper[k];
-      for (int a : S) {
-        uint32_t le = (uint32_t)E.find(a, k);
-        for (int b : S) prods.push_back({(uint32_t)E.find(a, b), le, (uint32_t)diag[k], (uint32_t)E.find(k, b)});
-        prods.push_back({(uint32_t)(nLU + a), le, (uint32_t)diag[k], (uint32_t)(nLU + k)});  // fused forward elimination
-      }
-    }
-    std::stable_sort(prods.begin(), prods.end(), [](const Prod &x, const Prod &y) { return x.tgt < y.tgt; });
-    std::vector<std::pair<uint32_t, std::vector<uint32_t>>> tasks;
-    for (size_t i = 0; i < prods.size();) {
-      size_t j = i;
-      std::vector<uint32_t> flat;
-      while (j < prods.size() && prods[j].tgt == prods[i].tgt) {
-        flat.push_back(prods[j].l); flat.push_back(prods[j].d); flat.push_back(prods[j].u);
-        j++;
-      }
-      uint32_t t = prods[i].tgt;
+    // (target, L entry, diagonal, U entry) tuples, grouped by target in pivot order
+    std::vector<Prod> prods;
+    level_products(F, l, [&](uint32_t t, uint32_t le, uint32_t dg, uint32_t ue, int, int, int) { prods.push_back({t, le, dg, ue}); });
+    std::stable_sort(prods.begin(), prods.end(), by_target);
+    std::vector<Task> tasks;
+    group_by_target(prods, [&](const Prod &p, std::vector<uint32_t> &&flat) {
+      uint32_t t = p.tgt;
       if ((int)t < nLU) {
         // diagonal that becomes final now?
         const int r = E.row_of_id[t];
         if (E.col_of_id[t] == r && hp.level[r] == l + 1 && !(Lc > 0 && hp.level[r] >= Lc)) t |= SPICEY_TGT_RECIP;  // (a front inverts its own pivots)
       }
       tasks.emplace_back(t, std::move(flat));
-      i = j;
-    }
+    });
     if (nBins > 0) {
-      std::vector<std::vector<std::pair<uint32_t, std::vector<uint32_t>>>> per_bin(nBins);
-      for (auto &tk : tasks) {
-        const int b = bin_of[owner_of(SPICEY_IDX(tk.first))];
-        if (b < 0) {
-          std::vector<uint32_t> &dst = iface[tk.first];
-          dst.insert(dst.end(), tk.second.begin(), tk.second.end());
-        } else {
-          hp.n_products += (int64_t)tk.second.size() / 3;
-          per_bin[b].push_back(std::move(tk));
-        }
-      }
-      for (int b = 0; b < nBins; b++) {
-        hp.bin_upd.push_back((uint32_t)hp.upd_slice.size());
-        pack_slices<3>(per_bin[b], hp.upd_slice, hp.upd_tgt, hp.upd_cnt, hp.upd_pairs);
-      }
-      hp.bin_upd.push_back((uint32_t)hp.upd_slice.size());
-      hp.lvl_slice.push_back((uint32_t)hp.upd_slice.size());
-      continue;
+      hp.n_products += pack_by_bin(tasks, nBins, [&](const Task &tk) { return F.bin_of[owner_of(SPICEY_IDX(tk.first))]; },
+                                   [&](const Task &tk) {
+                                     std::vector<uint32_t> &dst = iface[tk.first];
+                                     dst.insert(dst.end(), tk.second.begin(), tk.second.end());
+                                   },
+                                   hp.bin_upd, out);
+    } else {
+      hp.n_products += (int64_t)prods.size();
+      out.pack(tasks);
     }
-    hp.n_products += (int64_t)prods.size();
-    pack_slices<3>(tasks, hp.upd_slice, hp.upd_tgt, hp.upd_cnt, hp.upd_pairs);
-    hp.lvl_slice.push_back((uint32_t)hp.upd_slice.size());
+    hp.lvl_slice.push_back(out.size());
   }
   hp.hdr.nUpdSlices = (int32_t)hp.upd_slice.size();
+}
 
-  // ---- 5c. backward substitution, v1 (32-bit) form: COLUMN-oriented -----------------------------------
-  // x[k] = (y[k] - sum_b U[k][b] x[b]) / U[k][k] row by row means one thread walks a pivot's whole row; on a
-  // mesh the top separator rows have > 100 entries and that serial walk dominated the step.  Instead, level by
-  // level from the top, every row r below receives  y[r] -= U[r][k] * (y[k] * dinv[k])  from the pivots k of the
-  // level (gather by target row: short lists, wide parallelism, the same 3-operand task as the factor levels);
-  // one final phase scales x[i] = y[i] * dinv[i].  (The 16-bit records of the LDS path stay row-oriented: on
-  // circuits that fit LDS the rows are short and one phase fewer matters more.)
-  hp.bk_lvl_slice.assign(1, 0);
-  hp.bk_slice.clear(); hp.bk_x.clear(); hp.bk_d.clear(); hp.bk_cnt.clear(); hp.bk_pairs.clear();
-  hp.n_bk_products = 0;
+// ---- 5c. backward substitution, v1 (32-bit) form: COLUMN-oriented -----------------------------------
+// x[k] = (y[k] - sum_b U[k][b] x[b]) / U[k][k] row by row means one thread walks a pivot's whole row; on a
+// mesh the top separator rows have > 100 entries and that serial walk dominated the step.  Instead, level by
+// level from the top, every row r below receives  y[r] -= U[r][k] * (y[k] * dinv[k])  from the pivots k of the
+// level (gather by target row: short lists, wide parallelism, the same 3-operand task as the factor levels);
+// one final phase scales x[i] = y[i] * dinv[i].  (The 16-bit records of the LDS path stay row-oriented: on
+// circuits that fit LDS the rows are short and one phase fewer matters more.)
+void build_backward_slices(int n, const Factor &F, HostProgram &hp) {
+  const EntryIndex &E = F.E;
+  const int nLU = F.nLU, nLevels = F.nLevels, Lc = F.Lc, nBins = F.nBins;
+  const SliceLists out{hp.bk_slice, hp.bk_x, hp.bk_cnt, hp.bk_pairs};
+  hp.bk_lvl_slice = {0};
   for (int l = 0; l < nLevels; l++) {
-    struct Prod { uint32_t tgt, l, d, u; };
     std::vector<Prod> prods;
-    if (Lc > 0 && l > Lc) { hp.bk_lvl_slice.push_back((uint32_t)hp.bk_slice.size()); continue; }
+    if (Lc > 0 && l > Lc) { hp.bk_lvl_slice.push_back(out.size()); continue; }
     // with fronts, "level Lc" holds the INTERFACE: every row below the cut receives its products with ALL upper
     // unknowns (solved by the fronts: W[nLU + k] = x[k], diagonal operand = the constant-one slot), highest level first
     const int l_hi = (Lc > 0 && l == Lc) ? nLevels - 1 : l;
     for (int ll = l_hi; ll >= l; ll--)
-    for (int k : by_level[ll])
+    for (int k : F.by_level[ll])
       for (int p = E.ptr[k]; p < E.ptr[k + 1]; p++) {
         const int r = E.col[p];
         if (r >= k) break;  // columns of row k left of the diagonal = rows r with U[r][k] != 0
@@ -1048,256 +1250,248 @@ static int32_t build_program_impl(const SpiceyDesc *d, HostProgram &hp, std::str
           prods.push_back({(uint32_t)(nLU + r), (uint32_t)(nLU + k), (uint32_t)hp.hdr.one_slot, (uint32_t)E.find(r, k)});
           continue;
         }
-        prods.push_back({(uint32_t)(nLU + r), (uint32_t)(nLU + k), (uint32_t)diag[k], (uint32_t)E.find(r, k)});
+        prods.push_back({(uint32_t)(nLU + r), (uint32_t)(nLU + k), (uint32_t)F.diag[k], (uint32_t)E.find(r, k)});
       }
-    std::stable_sort(prods.begin(), prods.end(), [](const Prod &x, const Prod &y) { return x.tgt < y.tgt; });
-    std::vector<std::pair<uint32_t, std::vector<uint32_t>>> tasks;
-    for (size_t i = 0; i < prods.size();) {
-      size_t j = i;
-      std::vector<uint32_t> flat;
-      while (j < prods.size() && prods[j].tgt == prods[i].tgt) { flat.push_back(prods[j].l); flat.push_back(prods[j].d); flat.push_back(prods[j].u); j++; }
-      tasks.emplace_back(prods[i].tgt, std::move(flat));
-      i = j;
-    }
+    std::stable_sort(prods.begin(), prods.end(), by_target);
+    std::vector<Task> tasks;
+    group_by_target(prods, [&](const Prod &p, std::vector<uint32_t> &&flat) { tasks.emplace_back(p.tgt, std::move(flat)); });
     hp.n_bk_products += (int64_t)prods.size();
-    if (nBins > 0 && l <= Lc) {  // rows of one bin's subtrees together (program.h); l == Lc: the interface tasks, whose rows lie below the cut too
-      std::vector<std::vector<std::pair<uint32_t, std::vector<uint32_t>>>> per_bin(nBins);
-      for (auto &tk : tasks) per_bin[bin_of[(int)tk.first - nLU]].push_back(std::move(tk));
-      for (int b = 0; b < nBins; b++) {
-        hp.bin_bk.push_back((uint32_t)hp.bk_slice.size());
-        pack_slices<3>(per_bin[b], hp.bk_slice, hp.bk_x, hp.bk_cnt, hp.bk_pairs);
-      }
-      hp.bin_bk.push_back((uint32_t)hp.bk_slice.size());
-      hp.bk_lvl_slice.push_back((uint32_t)hp.bk_slice.size());
-      continue;
-    }
-    pack_slices<3>(tasks, hp.bk_slice, hp.bk_x, hp.bk_cnt, hp.bk_pairs);
-    hp.bk_lvl_slice.push_back((uint32_t)hp.bk_slice.size());
+    if (nBins > 0 && l <= Lc)  // rows of one bin's subtrees together (program.h); l == Lc: the interface tasks, whose rows lie below the cut too
+      pack_by_bin(tasks, nBins, [&](const Task &tk) { return F.bin_of[(int)tk.first - nLU]; }, [](const Task &) {}, hp.bin_bk, out);
+    else
+      out.pack(tasks);
+    hp.bk_lvl_slice.push_back(out.size());
   }
   hp.hdr.nBkSlices = (int32_t)hp.bk_slice.size();
-  hp.bk_d.assign(diag.begin(), diag.end());  // [n]: entry id of every pivot's (reciprocal) diagonal
+  hp.bk_d.assign(F.diag.begin(), F.diag.end());  // [n]: entry id of every pivot's (reciprocal) diagonal
   if (Lc > 0)
     for (int k = 0; k < n; k++)
       if (hp.level[k] >= Lc) hp.bk_d[k] = (uint32_t)hp.hdr.one_slot;  // the fronts leave x itself in W[nLU + k]
+}
 
-  // ---- 5c'. compact 16-bit records of the same tasks, phases in execution order -------------------
-  hp.rec16.clear(); hp.ovf16.clear(); hp.ph_first.clear(); hp.ph_cnt.clear(); hp.ph_rhs.clear();
-  hp.fus16.clear(); hp.fus_first.assign(nLevels, 0u); hp.fus_gen.assign(nLevels, 0u); hp.fus_rhs.assign(nLevels, 0u); hp.fus_pairs.assign(nLevels, 0u);
-  hp.hdr.has16 = ((nLU + n) < 65535 && Lc == 0) ? 1 : 0;  // 0xFFFF = ground in the packed terminal words; fronts run under the 32-bit interpreter
-  // Tridiagonal top: T = the pivots of the highest levels, at most 64 of them (one row per lane of a wave).  Two of them are coupled, once everything
-  // below is eliminated, iff the original matrix couples them or some lower pivot has both in its row structure.  If that
-  // coupling graph is a path, the Schur complement on T is tridiagonal in path order and the records stop below T.
-  hp.pcr_tab.clear();
-  hp.hdr.pcr_n = 0; hp.hdr.pcr_level = 0;
+// ---- 5c'. compact 16-bit records of the same tasks, phases in execution order -------------------
+// Tridiagonal top: T = the pivots of the highest levels, at most 64 of them (one row per lane of a wave).  Two of them are coupled, once everything
+// below is eliminated, iff the original matrix couples them or some lower pivot has both in its row structure.  If that
+// coupling graph is a path, the Schur complement on T is tridiagonal in path order and the records stop below T.
+// Returns T in path order and its first level L0, or nothing.
+std::vector<int> tridiagonal_top(const Pattern &P, const Factor &F, const HostProgram &hp, int &L0) {
+  const int n = P.n, nLevels = F.nLevels;
+  int cnt = 0;
+  L0 = nLevels;
+  while (L0 > 1 && cnt + (int)F.by_level[L0 - 1].size() <= 64) { L0--; cnt += (int)F.by_level[L0].size(); }  // one row per lane of the solving wave
+  if (!(cnt >= 15 && L0 >= 1 && L0 < nLevels)) return {};
   std::vector<char> in_top(n, 0);
-  int pcrL = 0;
-  if (pcr_top && hp.hdr.has16 && nLevels >= 4 && !hp.structurally_singular) {
-    int cnt = 0, L0 = nLevels;
-    while (L0 > 1 && cnt + (int)by_level[L0 - 1].size() <= 64) { L0--; cnt += (int)by_level[L0].size(); }  // one row per lane of the solving wave
-    if (cnt >= 15 && L0 >= 1 && L0 < nLevels) {
-      std::vector<int> T;
-      for (int k = 0; k < n; k++)
-        if (hp.level[k] >= L0) { in_top[k] = 1; T.push_back(k); }
-      std::vector<std::vector<int>> H(n);
-      auto link = [&](int a, int b) { if (a != b) { H[a].push_back(b); H[b].push_back(a); } };
-      for (int c = 0; c < n; c++)  // original couplings
-        for (int c2 : g[c]) {
-          const int a = hp.cpos[c], b = hp.cpos[c2];
-          if (a < b && in_top[a] && in_top[b]) link(a, b);
-        }
-      for (int k = 0; k < n; k++) {  // fill through the pivots below
-        if (in_top[k]) continue;
-        std::vector<int> tk;
-        for (int a : upper[k]) if (in_top[a]) tk.push_back(a);
-        for (size_t i = 0; i < tk.size(); i++)
-          for (size_t j = i + 1; j < tk.size(); j++) link(tk[i], tk[j]);
-      }
-      bool path = true;
-      size_t edges = 0;
-      int end0 = -1;
-      for (int t : T) {
-        sort_unique(H[t]);
-        edges += H[t].size();
-        if (H[t].size() > 2) path = false;
-        if (H[t].size() <= 1 && (end0 < 0 || t < end0)) end0 = t;
-      }
-      if (edges != 2 * (T.size() - 1) || end0 < 0) path = false;
-      std::vector<int> ord;
-      if (path) {
-        int prev = -1, cur = end0;
-        while (cur >= 0) {
-          ord.push_back(cur);
-          int nxt = -1;
-          for (int w : H[cur]) if (w != prev) nxt = w;
-          prev = cur; cur = nxt;
-          if (ord.size() > T.size()) { path = false; break; }
-        }
-        if (ord.size() != T.size()) path = false;  // (a cycle-free walk that covers T: connected)
-      }
-      if (path) {
-        for (size_t i = 0; i < ord.size(); i++) {
-          const int t = ord[i];
-          const int a = i > 0 ? E.find(t, ord[i - 1]) : -2, c2 = i + 1 < ord.size() ? E.find(t, ord[i + 1]) : -2;
-          if (a == -1 || c2 == -1) { path = false; break; }
-          hp.pcr_tab.push_back(a < 0 ? (uint16_t)0xFFFF : (uint16_t)a);
-          hp.pcr_tab.push_back((uint16_t)diag[t]);
-          hp.pcr_tab.push_back(c2 < 0 ? (uint16_t)0xFFFF : (uint16_t)c2);
-          hp.pcr_tab.push_back((uint16_t)(nLU + t));
-        }
-      }
-      if (path) { hp.hdr.pcr_n = (int32_t)ord.size(); hp.hdr.pcr_level = L0; pcrL = L0; }
-      else { hp.pcr_tab.clear(); std::fill(in_top.begin(), in_top.end(), 0); }
+  std::vector<int> T;
+  for (int k = 0; k < n; k++)
+    if (hp.level[k] >= L0) { in_top[k] = 1; T.push_back(k); }
+  std::vector<std::vector<int>> H(n);
+  auto link = [&](int a, int b) { if (a != b) { H[a].push_back(b); H[b].push_back(a); } };
+  for (int c = 0; c < n; c++)  // original couplings
+    for (int c2 : P.g[c]) {
+      const int a = hp.cpos[c], b = hp.cpos[c2];
+      if (a < b && in_top[a] && in_top[b]) link(a, b);
     }
+  for (int k = 0; k < n; k++) {  // fill through the pivots below
+    if (in_top[k]) continue;
+    std::vector<int> tk;
+    for (int a : F.upper[k]) if (in_top[a]) tk.push_back(a);
+    for (size_t i = 0; i < tk.size(); i++)
+      for (size_t j = i + 1; j < tk.size(); j++) link(tk[i], tk[j]);
   }
-  if (pcrL == 0) std::fill(in_top.begin(), in_top.end(), 0);
+  size_t edges = 0;
+  int end0 = -1;
+  for (int t : T) {
+    sort_unique(H[t]);
+    edges += H[t].size();
+    if (H[t].size() > 2) return {};
+    if (H[t].size() <= 1 && (end0 < 0 || t < end0)) end0 = t;
+  }
+  if (edges != 2 * (T.size() - 1) || end0 < 0) return {};
+  std::vector<int> ord;
+  int prev = -1, cur = end0;
+  while (cur >= 0) {
+    ord.push_back(cur);
+    int nxt = -1;
+    for (int w : H[cur]) if (w != prev) nxt = w;
+    prev = cur; cur = nxt;
+    if (ord.size() > T.size()) return {};
+  }
+  if (ord.size() != T.size()) return {};  // (a cycle-free walk that covers T: connected)
+  for (size_t i = 0; i + 1 < ord.size(); i++)  // both off-diagonals of every link are entries of L+U
+    if (F.E.find(ord[i], ord[i + 1]) < 0 || F.E.find(ord[i + 1], ord[i]) < 0) return {};
+  return ord;
+}
+
+// One factor task of the 16-bit records
+struct FactorTask { uint32_t t; bool recip; std::vector<uint32_t> tr; int32_t si, sj, k; };  // tr = (l, d, u)*; si / sj: slots of the L / U operand in upper[k] (sj = -1: rhs)
+
+// The tasks of factor level l in record order; sets too_long where a task has more products than a record's count holds.
+std::vector<FactorTask> level_factor_tasks(const Factor &F, const HostProgram &hp, int l, bool slot_major, bool &too_long) {
+  const EntryIndex &E = F.E;
+  const int nLU = F.nLU;
+  struct Prod7 { uint32_t tgt, l, d, u; int32_t si, sj, k; };
+  std::vector<Prod7> prods;
+  level_products(F, l, [&](uint32_t t, uint32_t le, uint32_t dg, uint32_t ue, int ia, int ib, int k) { prods.push_back({t, le, dg, ue, ia, ib, k}); });
+  // grouped by target in MATRIX-POSITION order (independent of the entry numbering, see spicey_build_program)
+  auto poskey = [&](uint32_t t) -> uint64_t {
+    return (int)t >= nLU ? (((uint64_t)1 << 62) | t) : (((uint64_t)E.row_of_id[t] << 31) | (uint64_t)E.col_of_id[t]);
+  };
+  std::stable_sort(prods.begin(), prods.end(), [&](const Prod7 &x, const Prod7 &y) { return poskey(x.tgt) < poskey(y.tgt); });
+  std::vector<FactorTask> uts;
+  group_by_target(prods, [&](const Prod7 &p, std::vector<uint32_t> &&tr) {
+    bool recip = false;
+    if ((int)p.tgt < nLU) {
+      const int r = E.row_of_id[p.tgt];
+      recip = E.col_of_id[p.tgt] == r && hp.level[r] == l + 1 && !F.in_top[r];  // (the cyclic reduction wants the diagonal itself)
+    }
+    if (tr.size() / 3 > 255) too_long = true;
+    uts.push_back({p.tgt, recip, std::move(tr), p.si, p.sj, p.k});
+  });
+  // right-hand-side tasks first (a linear circuit's reused factorisation runs only those), then the same
+  // (recip, count) next to each other: the 64-lane chunks then take one code path
+  std::stable_sort(uts.begin(), uts.end(), [&](const FactorTask &x, const FactorTask &y) {
+    const bool xr = (int)x.t >= nLU, yr = (int)y.t >= nLU;
+    if (xr != yr) return xr;
+    if (x.recip != y.recip) return x.recip > y.recip;
+    if (x.tr.size() != y.tr.size()) return x.tr.size() > y.tr.size();
+    if (!slot_major) return false;
+    // lanes = the same operand slots of consecutive pivots (see the entry numbering): conflict-free L, d, U reads
+    if (x.si != y.si) return x.si < y.si;
+    if (x.sj != y.sj) return x.sj < y.sj;
+    return x.k < y.k;
+  });
+  return uts;
+}
+
+// Appends the record of a factor task to dst (rec16 or fus16); a task of more than two products puts them into ovf16
+void emit_factor(const FactorTask &u, std::vector<uint32_t> &dst, std::vector<uint16_t> &ovf16) {
+  FactorRec r;
+  r.tgt = u.t; r.cnt = (uint32_t)(u.tr.size() / 3);
+  r.flags = SPICEY_R16_VALID | (u.recip ? SPICEY_R16_RECIP : 0u);
+  if (r.cnt <= 2) std::copy(u.tr.begin(), u.tr.end(), &r.ldu[0][0]);
+  else {
+    r.ovf = (uint32_t)ovf16.size();
+    for (uint32_t v : u.tr) ovf16.push_back((uint16_t)v);
+  }
+  dst.resize(dst.size() + 4);
+  r.pack(&dst[dst.size() - 4]);
+}
+
+// Factor level l as row records (program.h: fus16), where at least 64 rows fit the pattern
+void build_row_records(int n, const Factor &F, int l, const std::vector<FactorTask> &uts, HostProgram &hp) {
+  const Adj &upper = F.upper;
+  const EntryIndex &E = F.E;
+  const int nLU = F.nLU;
+  // pivots of this level that reach row a; a row fits if it has <= 2 of them, each with <= 2 neighbours, and the
+  // neighbours on the far side are distinct
+  std::vector<std::vector<int>> reach(n);
+  for (int k : F.by_level[l])
+    for (int a : upper[k]) reach[a].push_back(k);
+  auto other = [&](int k, int a) -> int {  // the neighbour of pivot k that is not a (-1: none)
+    for (int b : upper[k]) if (b != a) return b;
+    return -1;
+  };
+  std::vector<char> fits(n, 0);
+  std::vector<int> rows;
+  for (int a = 0; a < n; a++) {
+    if (reach[a].empty() || reach[a].size() > 2) continue;
+    bool ok = true;
+    for (int k : reach[a]) ok = ok && upper[k].size() <= 2;
+    if (ok && reach[a].size() == 2) {
+      const int o0 = other(reach[a][0], a), o1 = other(reach[a][1], a);
+      if (o0 >= 0 && o0 == o1) ok = false;
+    }
+    if (ok) { fits[a] = 1; rows.push_back(a); }
+  }
+  if (rows.size() < 64) return;  // (fewer: not worth a second encoding)
+  hp.fus_first[l] = (uint32_t)(hp.fus16.size() / 4);
+  uint32_t ngen = 0, ngrhs = 0;
+  for (auto &u : uts) {
+    const int row = (int)u.t >= nLU ? (int)u.t - nLU : E.row_of_id[u.t];
+    if (fits[row]) continue;
+    emit_factor(u, hp.fus16, hp.ovf16);
+    ngen++;
+    ngrhs += (int)u.t >= nLU ? 1u : 0u;
+  }
+  hp.fus_gen[l] = ngen; hp.fus_rhs[l] = ngrhs;
+  for (int a : rows) {
+    std::sort(reach[a].begin(), reach[a].end());
+    RowRec rr;
+    const bool recip = hp.level[a] == l + 1 && !F.in_top[a];
+    uint32_t meta = (uint32_t)reach[a].size() | ((SPICEY_R16_VALID | SPICEY_R16_FUSED | (recip ? SPICEY_R16_RECIP : 0u)) << 8);
+    rr.a_ii() = (uint16_t)F.diag[a]; rr.y_i() = (uint16_t)(nLU + a);
+    for (size_t i = 0; i < reach[a].size(); i++) {
+      const int k = reach[a][i], o = other(k, a);
+      uint16_t *q = rr.pivot(i);
+      q[0] = (uint16_t)E.find(a, k); q[1] = (uint16_t)F.diag[k]; q[2] = (uint16_t)E.find(k, a); q[3] = (uint16_t)(nLU + k);
+      if (o >= 0) { q[4] = (uint16_t)E.find(k, o); q[5] = (uint16_t)E.find(a, o); meta |= 1u << (4 + i); }
+    }
+    rr.meta() = (uint16_t)meta;
+    hp.fus16.resize(hp.fus16.size() + 8);
+    rr.pack(&hp.fus16[hp.fus16.size() - 8]);
+  }
+  hp.fus_pairs[l] = (uint32_t)rows.size();
+}
+
+// The backward phases (row-oriented: one record per pivot), top level first
+void build_backward_records(const Factor &F, HostProgram &hp, bool &too_long) {
+  const int nLU = F.nLU;
+  for (int l = F.nLevels - 1; l >= 0; l--) {
+    hp.ph_first.push_back((uint32_t)(hp.rec16.size() / 4));
+    if (F.pcrL > 0 && l >= F.pcrL) { hp.ph_cnt.push_back(0u); continue; }
+    std::vector<int> ks = F.by_level[l];
+    std::stable_sort(ks.begin(), ks.end(), [&](int x, int y) { return F.upper[x].size() > F.upper[y].size(); });
+    for (int k : ks) {
+      const std::vector<int> &S = F.upper[k];
+      BackRec r;
+      r.x = (uint32_t)(nLU + k); r.d = (uint32_t)F.diag[k]; r.cnt = (uint32_t)S.size();
+      r.flags = SPICEY_R16_VALID | SPICEY_R16_K;
+      if (r.cnt > 255) too_long = true;
+      if (r.cnt > 2) r.ovf = (uint32_t)hp.ovf16.size();
+      for (size_t j = 0; j < S.size(); j++) {  // (u, xb) per product
+        const uint32_t u = (uint32_t)F.E.find(k, S[j]), xb = (uint32_t)(nLU + S[j]);
+        if (r.cnt <= 2) { r.uxb[j][0] = u; r.uxb[j][1] = xb; }
+        else { hp.ovf16.push_back((uint16_t)u); hp.ovf16.push_back((uint16_t)xb); }
+      }
+      hp.rec16.resize(hp.rec16.size() + 4);
+      r.pack(&hp.rec16[hp.rec16.size() - 4]);
+    }
+    hp.ph_cnt.push_back((uint32_t)(hp.rec16.size() / 4) - hp.ph_first.back());
+  }
+}
+
+void build_records16(const Pattern &P, Factor &F, HostProgram &hp, bool slot_major, bool pcr_top) {
+  const int n = P.n, nLU = F.nLU, nLevels = F.nLevels;
+  hp.fus_first.assign(nLevels, 0u); hp.fus_gen.assign(nLevels, 0u); hp.fus_rhs.assign(nLevels, 0u); hp.fus_pairs.assign(nLevels, 0u);
+  hp.hdr.has16 = ((nLU + n) < 65535 && F.Lc == 0) ? 1 : 0;  // 0xFFFF = ground in the packed terminal words; fronts run under the 32-bit interpreter
+  F.in_top.assign(n, 0);
+  if (pcr_top && hp.hdr.has16 && nLevels >= 4 && !hp.structurally_singular) {
+    int L0 = 0;
+    const std::vector<int> ord = tridiagonal_top(P, F, hp, L0);
+    for (size_t i = 0; i < ord.size(); i++) {
+      const int t = ord[i];
+      F.in_top[t] = 1;
+      hp.pcr_tab.push_back(i > 0 ? (uint16_t)F.E.find(t, ord[i - 1]) : (uint16_t)0xFFFF);
+      hp.pcr_tab.push_back((uint16_t)F.diag[t]);
+      hp.pcr_tab.push_back(i + 1 < ord.size() ? (uint16_t)F.E.find(t, ord[i + 1]) : (uint16_t)0xFFFF);
+      hp.pcr_tab.push_back((uint16_t)(nLU + t));
+    }
+    if (!ord.empty()) { hp.hdr.pcr_n = (int32_t)ord.size(); hp.hdr.pcr_level = L0; F.pcrL = L0; }
+  }
   if (hp.hdr.has16) {
-    auto emit_u = [&](uint32_t tgt, bool recip, const std::vector<uint32_t> &tr, std::vector<uint32_t> &dst) {  // tr = (l,d,u)*
-      const uint32_t cnt = (uint32_t)(tr.size() / 3);
-      uint32_t flags = SPICEY_R16_VALID | (recip ? SPICEY_R16_RECIP : 0u);
-      uint32_t w0 = tgt | ((std::min(cnt, 255u) | (flags << 8)) << 16), w1 = 0, w2 = 0, w3 = 0;
-      if (cnt <= 2) {
-        if (cnt >= 1) { w1 = tr[0] | (tr[1] << 16); w2 = tr[2]; }
-        if (cnt == 2) { w2 |= tr[3] << 16; w3 = tr[4] | (tr[5] << 16); }
-      } else {
-        w3 = (uint32_t)hp.ovf16.size();
-        for (uint32_t v : tr) hp.ovf16.push_back((uint16_t)v);
-      }
-      dst.insert(dst.end(), {w0, w1, w2, w3});
-    };
-    auto emit_k = [&](uint32_t x, uint32_t dg, const std::vector<uint32_t> &pr) {  // pr = (u,xb)*
-      const uint32_t cnt = (uint32_t)(pr.size() / 2);
-      uint32_t flags = SPICEY_R16_VALID | SPICEY_R16_K;
-      uint32_t w0 = x | ((std::min(cnt, 255u) | (flags << 8)) << 16), w1 = dg, w2 = 0, w3 = 0;
-      if (cnt <= 2) {
-        if (cnt >= 1) { w1 |= pr[0] << 16; w2 = pr[1]; }
-        if (cnt == 2) { w2 |= pr[2] << 16; w3 = pr[3]; }
-      } else {
-        w3 = (uint32_t)hp.ovf16.size();
-        for (uint32_t v : pr) hp.ovf16.push_back((uint16_t)v);
-      }
-      hp.rec16.insert(hp.rec16.end(), {w0, w1, w2, w3});
-    };
     bool too_long = false;
-    for (int l = 0; l < nLevels; l++) {  // factor phases: re-derive the grouped tasks of level l
+    for (int l = 0; l < nLevels; l++) {  // factor phases
       hp.ph_first.push_back((uint32_t)(hp.rec16.size() / 4));
-      if (pcrL > 0 && l >= pcrL) { hp.ph_rhs.push_back(0u); hp.ph_cnt.push_back(0u); continue; }  // solved by cyclic reduction
-      struct Prod { uint32_t tgt, l, d, u; int32_t si, sj, k; };  // si / sj: slots of the L / U operand in upper[k] (sj = -1: rhs)
-      std::vector<Prod> prods;
-      for (int k : by_level[l]) {
-        const std::vector<int> &S = upper[k];
-        for (int ia = 0; ia < (int)S.size(); ia++) {
-          const int a = S[ia];
-          uint32_t le = (uint32_t)E.find(a, k);
-          for (int ib = 0; ib < (int)S.size(); ib++)
-            prods.push_back({(uint32_t)E.find(a, S[ib]), le, (uint32_t)diag[k], (uint32_t)E.find(k, S[ib]), ia, ib, k});
-          prods.push_back({(uint32_t)(nLU + a), le, (uint32_t)diag[k], (uint32_t)(nLU + k), ia, -1, k});
-        }
-      }
-      // grouped by target in MATRIX-POSITION order (independent of the entry numbering, see spicey_build_program)
-      auto poskey = [&](uint32_t t) -> uint64_t {
-        return (int)t >= nLU ? (((uint64_t)1 << 62) | t) : (((uint64_t)E.row_of_id[t] << 31) | (uint64_t)E.col_of_id[t]);
-      };
-      std::stable_sort(prods.begin(), prods.end(), [&](const Prod &x, const Prod &y) { return poskey(x.tgt) < poskey(y.tgt); });
-      struct UT { uint32_t t; bool recip; std::vector<uint32_t> tr; int32_t si, sj, k; };
-      std::vector<UT> uts;
-      for (size_t i = 0; i < prods.size();) {
-        size_t j = i;
-        std::vector<uint32_t> tr;
-        while (j < prods.size() && prods[j].tgt == prods[i].tgt) { tr.push_back(prods[j].l); tr.push_back(prods[j].d); tr.push_back(prods[j].u); j++; }
-        uint32_t t = prods[i].tgt;
-        bool recip = false;
-        if ((int)t < nLU) {
-          const int r = E.row_of_id[t];
-          recip = E.col_of_id[t] == r && hp.level[r] == l + 1 && !in_top[r];  // (the cyclic reduction wants the diagonal itself)
-        }
-        if (tr.size() / 3 > 255) too_long = true;
-        uts.push_back({t, recip, std::move(tr), prods[i].si, prods[i].sj, prods[i].k});
-        i = j;
-      }
-      // right-hand-side tasks first (a linear circuit's reused factorisation runs only those), then the same
-      // (recip, count) next to each other: the 64-lane chunks then take one code path
-      std::stable_sort(uts.begin(), uts.end(), [&](const UT &x, const UT &y) {
-        const bool xr = (int)x.t >= nLU, yr = (int)y.t >= nLU;
-        if (xr != yr) return xr;
-        if (x.recip != y.recip) return x.recip > y.recip;
-        if (x.tr.size() != y.tr.size()) return x.tr.size() > y.tr.size();
-        if (!slot_major) return false;
-        // lanes = the same operand slots of consecutive pivots (see the entry numbering): conflict-free L, d, U reads
-        if (x.si != y.si) return x.si < y.si;
-        if (x.sj != y.sj) return x.sj < y.sj;
-        return x.k < y.k;
-      });
+      if (F.pcrL > 0 && l >= F.pcrL) { hp.ph_rhs.push_back(0u); hp.ph_cnt.push_back(0u); continue; }  // solved by cyclic reduction
+      const std::vector<FactorTask> uts = level_factor_tasks(F, hp, l, slot_major, too_long);
       uint32_t nrhs = 0;
       for (auto &u : uts) nrhs += (int)u.t >= nLU ? 1u : 0u;
       hp.ph_rhs.push_back(nrhs);
-      for (auto &u : uts) emit_u(u.t, u.recip, u.tr, hp.rec16);
+      for (auto &u : uts) emit_factor(u, hp.rec16, hp.ovf16);
       hp.ph_cnt.push_back((uint32_t)(hp.rec16.size() / 4) - hp.ph_first.back());
-      // ---- the same phase as row records (program.h: fus16) -------------------------------------------------------------
-      {
-        // pivots of this level that reach row a; a row fits if it has <= 2 of them, each with <= 2 neighbours, and the
-        // neighbours on the far side are distinct
-        std::vector<std::vector<int>> reach(n);
-        for (int k : by_level[l])
-          for (int a : upper[k]) reach[a].push_back(k);
-        auto other = [&](int k, int a) -> int {  // the neighbour of pivot k that is not a (-1: none)
-          for (int b : upper[k]) if (b != a) return b;
-          return -1;
-        };
-        std::vector<char> fits(n, 0);
-        std::vector<int> rows;
-        for (int a = 0; a < n; a++) {
-          if (reach[a].empty() || reach[a].size() > 2) continue;
-          bool ok = true;
-          for (int k : reach[a]) ok = ok && upper[k].size() <= 2;
-          if (ok && reach[a].size() == 2) {
-            const int o0 = other(reach[a][0], a), o1 = other(reach[a][1], a);
-            if (o0 >= 0 && o0 == o1) ok = false;
-          }
-          if (ok) { fits[a] = 1; rows.push_back(a); }
-        }
-        if (rows.size() >= 64) {  // (fewer: not worth a second encoding)
-          hp.fus_first[l] = (uint32_t)(hp.fus16.size() / 4);
-          uint32_t ngen = 0, ngrhs = 0;
-          for (auto &u : uts) {
-            const int row = (int)u.t >= nLU ? (int)u.t - nLU : E.row_of_id[u.t];
-            if (fits[row]) continue;
-            emit_u(u.t, u.recip, u.tr, hp.fus16);
-            ngen++;
-            ngrhs += (int)u.t >= nLU ? 1u : 0u;
-          }
-          hp.fus_gen[l] = ngen; hp.fus_rhs[l] = ngrhs;
-          for (int a : rows) {
-            std::sort(reach[a].begin(), reach[a].end());
-            uint16_t h[16] = {0};
-            const bool recip = hp.level[a] == l + 1 && !in_top[a];
-            uint32_t meta = (uint32_t)reach[a].size() | ((SPICEY_R16_VALID | SPICEY_R16_FUSED | (recip ? SPICEY_R16_RECIP : 0u)) << 8);
-            h[0] = (uint16_t)diag[a]; h[2] = (uint16_t)(nLU + a);
-            for (size_t i = 0; i < reach[a].size(); i++) {
-              const int k = reach[a][i], o = other(k, a);
-              uint16_t *q = h + 3 + 6 * i;
-              q[0] = (uint16_t)E.find(a, k); q[1] = (uint16_t)diag[k]; q[2] = (uint16_t)E.find(k, a); q[3] = (uint16_t)(nLU + k);
-              if (o >= 0) { q[4] = (uint16_t)E.find(k, o); q[5] = (uint16_t)E.find(a, o); meta |= 1u << (4 + i); }
-            }
-            h[1] = (uint16_t)meta;
-            for (int w = 0; w < 8; w++) hp.fus16.push_back((uint32_t)h[2 * w] | ((uint32_t)h[2 * w + 1] << 16));
-          }
-          hp.fus_pairs[l] = (uint32_t)rows.size();
-        }
-      }
+      build_row_records(n, F, l, uts, hp);  // the same phase as row records
     }
-    for (int l = nLevels - 1; l >= 0; l--) {  // backward phases, top level first
-      hp.ph_first.push_back((uint32_t)(hp.rec16.size() / 4));
-      if (pcrL > 0 && l >= pcrL) { hp.ph_cnt.push_back(0u); continue; }
-      std::vector<int> ks = by_level[l];
-      std::stable_sort(ks.begin(), ks.end(), [&](int x, int y) { return upper[x].size() > upper[y].size(); });
-      for (int k : ks) {
-        std::vector<uint32_t> pr;
-        for (int b : upper[k]) { pr.push_back((uint32_t)E.find(k, b)); pr.push_back((uint32_t)(nLU + b)); }
-        if (pr.size() / 2 > 255) too_long = true;
-        emit_k((uint32_t)(nLU + k), (uint32_t)diag[k], pr);
-      }
-      hp.ph_cnt.push_back((uint32_t)(hp.rec16.size() / 4) - hp.ph_first.back());
-    }
+    build_backward_records(F, hp, too_long);
     if (too_long || hp.ovf16.size() >= (size_t)1 << 31) {  // count field is 8 bits: such circuits use the 32-bit path
       hp.hdr.has16 = 0;
       hp.fus16.clear(); std::fill(hp.fus_pairs.begin(), hp.fus_pairs.end(), 0u);
@@ -1306,10 +1500,14 @@ static int32_t build_program_impl(const SpiceyDesc *d, HostProgram &hp, std::str
     }
   }
   hp.hdr.nRec16 = (int32_t)(hp.rec16.size() / 4);
+}
 
-  // ---- 5c''. v2 B-phase descriptors: per-entry dynamic stamps, per-row right-hand side -----------
+// ---- 5c''. v2 B-phase descriptors: per-entry dynamic stamps, per-row right-hand side -----------
+void build_b_descriptors(int n, const Factor &F, HostProgram &hp) {
+  const int nLU = F.nLU;
+  const std::vector<std::vector<uint32_t>> &dyn = F.dyn;
   hp.ent_dd.assign(nLU, 0u);
-  hp.dynx_ent.clear(); hp.dynx_ptr.assign(1, 0u); hp.dynx_idx.clear();
+  hp.dynx_ptr = {0u};
   for (int e = 0; e < nLU; e++) {
     uint32_t dd = (hp.ent_flag[e] & 1) && !dyn[e].empty() ? (1u << 30) : 0u;
     bool ovf = dyn[e].size() > 2;
@@ -1329,7 +1527,6 @@ static int32_t build_program_impl(const SpiceyDesc *d, HostProgram &hp, std::str
   }
   hp.hdr.nDynX = (int32_t)hp.dynx_ent.size();
   hp.row_desc.assign((size_t)n * 2, 0u);
-  hp.rowx.clear();
   for (int r = 0; r < n; r++) {
     const uint32_t j0 = hp.rhs_ptr[r], j1 = hp.rhs_ptr[r + 1];
     bool ovf = j1 - j0 > 4;
@@ -1345,19 +1542,22 @@ static int32_t build_program_impl(const SpiceyDesc *d, HostProgram &hp, std::str
     }
   }
   hp.hdr.nRowX = (int32_t)hp.rowx.size();
+}
 
-  // ---- 5d. element terminals and outputs as W indices -------------------------------------------
+// ---- 5d. element terminals and outputs as W indices; natural numbering; A by natural column ------
+void build_terminals(const SpiceyDesc &d, const Pattern &P, const Factor &F, HostProgram &hp) {
+  const int nN = P.nN, n = P.n, nV = d.nV, nLU = F.nLU;
   auto xpos = [&](int node) -> int32_t { return node == 0 ? -1 : (int32_t)(nLU + hp.cpos[node - 1]); };
   auto map2 = [&](const int32_t *a, const int32_t *b, int cnt, std::vector<int32_t> &oa, std::vector<int32_t> &ob) {
     oa.resize(cnt); ob.resize(cnt);
     for (int i = 0; i < cnt; i++) { oa[i] = xpos(a[i]); ob[i] = xpos(b[i]); }
   };
-  map2(d->R_n1, d->R_n2, nR, hp.R_a, hp.R_b);
-  map2(d->C_n1, d->C_n2, nC, hp.C_a, hp.C_b);
-  map2(d->L_n1, d->L_n2, nL, hp.L_a, hp.L_b);
-  map2(d->S_n1, d->S_n2, nS, hp.S_a, hp.S_b);
-  map2(d->S_cp, d->S_cn, nS, hp.S_cp, hp.S_cn);
-  map2(d->D_np, d->D_nm, nD, hp.D_a, hp.D_b);
+  map2(d.R_n1, d.R_n2, d.nR, hp.R_a, hp.R_b);
+  map2(d.C_n1, d.C_n2, d.nC, hp.C_a, hp.C_b);
+  map2(d.L_n1, d.L_n2, d.nL, hp.L_a, hp.L_b);
+  map2(d.S_n1, d.S_n2, d.nS, hp.S_a, hp.S_b);
+  map2(d.S_cp, d.S_cn, d.nS, hp.S_cp, hp.S_cn);
+  map2(d.D_np, d.D_nm, d.nD, hp.D_a, hp.D_b);
   auto pack2 = [&](const std::vector<int32_t> &a, const std::vector<int32_t> &b, std::vector<uint32_t> &o) {
     o.resize(a.size());
     for (size_t i = 0; i < a.size(); i++)
@@ -1366,192 +1566,184 @@ static int32_t build_program_impl(const SpiceyDesc *d, HostProgram &hp, std::str
   pack2(hp.R_a, hp.R_b, hp.R_ab); pack2(hp.C_a, hp.C_b, hp.C_ab); pack2(hp.L_a, hp.L_b, hp.L_ab); pack2(hp.D_a, hp.D_b, hp.D_ab);
   hp.V_x.resize(nV);
   for (int k = 0; k < nV; k++) hp.V_x[k] = nLU + hp.cpos[nN + k];
-  hp.out_x.resize(nOut);
-  for (int i = 0; i < nOut; i++) hp.out_x[i] = (d->n_out > 0 && d->out_nodes) ? xpos(d->out_nodes[i]) : (int32_t)(nLU + hp.cpos[i]);
+  hp.out_x.resize(P.nOut);
+  for (int i = 0; i < P.nOut; i++) hp.out_x[i] = (d.n_out > 0 && d.out_nodes) ? xpos(d.out_nodes[i]) : (int32_t)(nLU + hp.cpos[i]);
 
   // natural numbering of entries and pivot positions (AC dense fallback)
   hp.pos_row.assign(n, 0); hp.pos_col.assign(n, 0);
   for (int r = 0; r < n; r++) hp.pos_row[hp.rpos[r]] = r;
   for (int c = 0; c < n; c++) hp.pos_col[hp.cpos[c]] = c;
   hp.ent_ro.assign(nLU, 0); hp.ent_co.assign(nLU, 0);
-  for (int e = 0; e < nLU; e++) { hp.ent_ro[e] = hp.pos_row[E.row_of_id[e]]; hp.ent_co[e] = hp.pos_col[E.col_of_id[e]]; }
+  for (int e = 0; e < nLU; e++) { hp.ent_ro[e] = hp.pos_row[F.E.row_of_id[e]]; hp.ent_co[e] = hp.pos_col[F.E.col_of_id[e]]; }
   // structural entries of A by natural column (diagnostics: program.h, col_ptr / col_ent)
-  {
-    std::vector<std::vector<uint32_t>> by_col(n);
-    for (int e = 0; e < nLU; e++)
-      if (!stat[e].empty() || !dyn[e].empty()) by_col[hp.ent_co[e]].push_back((uint32_t)e | ((hp.ent_flag[e] & 1) ? SPICEY_TGT_RECIP : 0u));
-    hp.col_ptr.assign(1, 0u);
-    hp.col_ent.clear();
-    for (int c = 0; c < n; c++) {
-      hp.col_ent.insert(hp.col_ent.end(), by_col[c].begin(), by_col[c].end());
-      hp.col_ptr.push_back((uint32_t)hp.col_ent.size());
-    }
+  std::vector<std::vector<uint32_t>> by_col(n);
+  for (int e = 0; e < nLU; e++)
+    if (!F.stat[e].empty() || !F.dyn[e].empty()) by_col[hp.ent_co[e]].push_back((uint32_t)e | ((hp.ent_flag[e] & 1) ? SPICEY_TGT_RECIP : 0u));
+  hp.col_ptr = {0u};
+  for (int c = 0; c < n; c++) {
+    hp.col_ent.insert(hp.col_ent.end(), by_col[c].begin(), by_col[c].end());
+    hp.col_ptr.push_back((uint32_t)hp.col_ent.size());
   }
+}
 
-  // ---- 6. hybrid workspace layout (program.h: SpiceyProg::hybrid) ---------------------------------------------------------
-  hp.hdr.hybrid = 0; hp.hdr.hyb_g0 = 0; hp.hdr.hyb_g2 = 0; hp.hdr.xoff = nLU;
-  if (hybrid && slot_major && hp.hdr.has16 && Lc == 0 && nLevels >= 3 && !hp.structurally_singular) {
-    // the leaf-owned entries: ids [0, g0) of the dynamic class and [nRestore, nRestore + g2) of the never-modified class
-    // (inside a class the slot-major numbering sorts by the level of the owning pivot; a leaf-owned entry is never an
-    // update target: targets lie among the ancestors of the eliminated pivot)
-    const int nRest = hp.hdr.nRestore;
-    auto leaf_owned = [&](int e) { return hp.level[std::min(E.row_of_id[e], E.col_of_id[e])] == 0; };
-    int g0 = 0, g2 = 0;
-    while (g0 < nRest && leaf_owned(g0)) g0++;
-    while (nRest + g2 < nLU && leaf_owned(nRest + g2)) g2++;
-    bool ok = true;
-    for (int e = 0; e < nLU && ok; e++) ok = leaf_owned(e) == (e < g0 || (e >= nRest && e < nRest + g2));
-    if (ok && g0 + g2 > 0) {
-      const uint32_t G0 = (uint32_t)g0, G2 = (uint32_t)g2, NR = (uint32_t)nRest;
-      auto is_glob = [&](uint32_t w) { return w < G0 || (w >= NR && w < NR + G2); };
-      auto lds = [&](uint32_t w) -> uint32_t { return w < NR ? w - G0 : w - G0 - G2; };  // (w must not be a leaf-owned entry)
-      bool bad = false;
-      auto L16 = [&](uint32_t w) -> uint32_t { if (is_glob(w)) bad = true; return lds(w); };
-      auto G16 = [&](uint32_t w) -> uint32_t { if (!is_glob(w)) bad = true; return w; };
-      // 16-bit records of one phase, `count` of them from 16-byte unit `first` of `arr`; opg: the pivot operands are leaf-owned
-      auto fix_generic = [&](std::vector<uint32_t> &arr, size_t first, size_t count, bool ktask, bool opg) {
-        for (size_t i = 0; i < count; i++) {
-          uint32_t *r = &arr[(first + i) * 4];
-          const uint32_t meta = r[0] >> 16, cnt = meta & 0xffu;
-          if (!(meta & (SPICEY_R16_VALID << 8))) continue;
-          const uint32_t tgt_old = r[0] & 0xffffu;
-          const bool rhs_task = tgt_old >= (uint32_t)nLU;
-          r[0] = L16(tgt_old) | (meta << 16);
-          if (ktask) {
-            const uint32_t dg = r[1] & 0xffffu;
-            const uint32_t dnew = opg ? G16(dg) : L16(dg);
-            if (cnt <= 2) {
-              uint32_t u0 = r[1] >> 16, x0 = r[2] & 0xffffu, u1 = r[2] >> 16, x1 = r[3] & 0xffffu;
-              if (cnt >= 1) { u0 = opg ? G16(u0) : L16(u0); x0 = L16(x0); }
-              if (cnt == 2) { u1 = opg ? G16(u1) : L16(u1); x1 = L16(x1); }
-              r[1] = dnew | (u0 << 16); r[2] = x0 | (u1 << 16); r[3] = x1;
-            } else {
-              r[1] = dnew;
-              for (uint32_t j = 0; j < cnt; j++) {
-                uint16_t &u = hp.ovf16[r[3] + 2 * j], &x = hp.ovf16[r[3] + 2 * j + 1];
-                u = (uint16_t)(opg ? G16(u) : L16(u)); x = (uint16_t)L16(x);
-              }
-            }
-          } else {
-            // third operand of a right-hand-side task: y_k, an LDS index in every phase
-            auto third = [&](uint32_t u) { return (opg && !rhs_task) ? G16(u) : L16(u); };
-            if (cnt <= 2) {
-              uint32_t l0 = r[1] & 0xffffu, d0 = r[1] >> 16, u0 = r[2] & 0xffffu, l1 = r[2] >> 16, d1 = r[3] & 0xffffu, u1 = r[3] >> 16;
-              if (cnt >= 1) { l0 = opg ? G16(l0) : L16(l0); d0 = opg ? G16(d0) : L16(d0); u0 = third(u0); }
-              if (cnt == 2) { l1 = opg ? G16(l1) : L16(l1); d1 = opg ? G16(d1) : L16(d1); u1 = third(u1); }
-              r[1] = l0 | (d0 << 16); r[2] = u0 | (l1 << 16); r[3] = d1 | (u1 << 16);
-            } else {
-              for (uint32_t j = 0; j < cnt; j++) {
-                uint16_t *t = &hp.ovf16[r[3] + 3 * j];
-                t[0] = (uint16_t)(opg ? G16(t[0]) : L16(t[0])); t[1] = (uint16_t)(opg ? G16(t[1]) : L16(t[1])); t[2] = (uint16_t)third(t[2]);
-              }
-            }
-          }
-        }
-      };
-      // (an overflow list belongs to ONE record of rec16 and, when the phase has a row-record encoding, to its twin in fus16,
-      // which was emitted with its own copy: emit_u appends to ovf16 per call — so every list is fixed exactly once)
-      for (int p = 0; p < 2 * nLevels; p++) {
-        const bool ktask = p >= nLevels;
-        const int lvl = ktask ? 2 * nLevels - 1 - p : p;
-        fix_generic(hp.rec16, hp.ph_first[p], hp.ph_cnt[p], ktask, lvl == 0);
-        if (!ktask && hp.fus_pairs[p] > 0) {
-          fix_generic(hp.fus16, hp.fus_first[p], hp.fus_gen[p], false, lvl == 0);
-          for (uint32_t i = 0; i < hp.fus_pairs[p]; i++) {
-            uint32_t *w = &hp.fus16[((size_t)hp.fus_first[p] + hp.fus_gen[p]) * 4 + (size_t)i * 8];
-            uint16_t h[16];
-            for (int q = 0; q < 8; q++) { h[2 * q] = (uint16_t)(w[q] & 0xffffu); h[2 * q + 1] = (uint16_t)(w[q] >> 16); }
-            const uint32_t meta = h[1], np = meta & 3u;
-            h[0] = (uint16_t)L16(h[0]); h[2] = (uint16_t)L16(h[2]);
-            for (uint32_t i2 = 0; i2 < np; i2++) {
-              uint16_t *q = h + 3 + 6 * i2;
-              const bool opg = lvl == 0;
-              q[0] = (uint16_t)(opg ? G16(q[0]) : L16(q[0])); q[1] = (uint16_t)(opg ? G16(q[1]) : L16(q[1])); q[2] = (uint16_t)(opg ? G16(q[2]) : L16(q[2]));
-              q[3] = (uint16_t)L16(q[3]);
-              if ((meta >> (4 + i2)) & 1u) { q[4] = (uint16_t)(opg ? G16(q[4]) : L16(q[4])); q[5] = (uint16_t)L16(q[5]); }
-            }
-            for (int q = 0; q < 8; q++) w[q] = (uint32_t)h[2 * q] | ((uint32_t)h[2 * q + 1] << 16);
-          }
-        }
+// ---- 6. hybrid workspace layout (program.h: SpiceyProg::hybrid) ---------------------------------------------------------
+// Re-indexes every W index of the records, tables and terminals: unpack, map each index through L16 (an LDS index) or
+// G16 (a leaf-owned entry, which keeps its id) according to its role, pack.  Leaves hp.hdr.hybrid = 0 where the
+// leaf-owned entries are not the two id ranges; false: an index was on the wrong side.
+bool layout_hybrid(const Factor &F, HostProgram &hp) {
+  const EntryIndex &E = F.E;
+  const int nLU = F.nLU, nLevels = F.nLevels;
+  // the leaf-owned entries: ids [0, g0) of the dynamic class and [nRestore, nRestore + g2) of the never-modified class
+  // (inside a class the slot-major numbering sorts by the level of the owning pivot; a leaf-owned entry is never an
+  // update target: targets lie among the ancestors of the eliminated pivot)
+  const int nRest = hp.hdr.nRestore;
+  auto leaf_owned = [&](int e) { return hp.level[std::min(E.row_of_id[e], E.col_of_id[e])] == 0; };
+  int g0 = 0, g2 = 0;
+  while (g0 < nRest && leaf_owned(g0)) g0++;
+  while (nRest + g2 < nLU && leaf_owned(nRest + g2)) g2++;
+  bool ok = true;
+  for (int e = 0; e < nLU && ok; e++) ok = leaf_owned(e) == (e < g0 || (e >= nRest && e < nRest + g2));
+  if (!ok || g0 + g2 == 0) return true;
+  const uint32_t G0 = (uint32_t)g0, G2 = (uint32_t)g2, NR = (uint32_t)nRest;
+  auto is_glob = [&](uint32_t w) { return w < G0 || (w >= NR && w < NR + G2); };
+  auto lds = [&](uint32_t w) -> uint32_t { return w < NR ? w - G0 : w - G0 - G2; };  // (w must not be a leaf-owned entry)
+  bool bad = false;
+  auto L16 = [&](uint32_t w) -> uint32_t { if (is_glob(w)) bad = true; return lds(w); };
+  auto G16 = [&](uint32_t w) -> uint32_t { if (!is_glob(w)) bad = true; return w; };
+  // generic records of one phase, `count` of them from 16-byte unit `first` of `arr`; opg: the pivot operands are leaf-owned
+  // (in place, on inline words and on the 16-bit overflow lists alike)
+  auto fix_generic = [&](std::vector<uint32_t> &arr, size_t first, size_t count, bool ktask, bool opg) {
+    auto op = [&](uint32_t w) { return opg ? G16(w) : L16(w); };
+    for (size_t i = 0; i < count; i++) {
+      uint32_t *w = &arr[(first + i) * 4];
+      if (ktask) {
+        BackRec r = BackRec::unpack(w);
+        if (!(r.flags & SPICEY_R16_VALID)) continue;
+        auto pair = [&](auto *p) {  // (u, xb)
+          typedef std::remove_reference_t<decltype(*p)> T;
+          p[0] = (T)op(p[0]); p[1] = (T)L16(p[1]);
+        };
+        r.x = L16(r.x);
+        r.d = op(r.d);
+        if (r.cnt <= 2) for (uint32_t j = 0; j < r.cnt; j++) pair(r.uxb[j]);
+        else for (uint32_t j = 0; j < r.cnt; j++) pair(&hp.ovf16[r.ovf + 2 * j]);
+        r.pack(w);
+      } else {
+        FactorRec r = FactorRec::unpack(w);
+        if (!(r.flags & SPICEY_R16_VALID)) continue;
+        // third operand of a right-hand-side task: y_k, an LDS index in every phase
+        const bool rhs_task = r.tgt >= (uint32_t)nLU;
+        auto triple = [&](auto *t) {  // (l, d, u)
+          typedef std::remove_reference_t<decltype(*t)> T;
+          t[0] = (T)op(t[0]); t[1] = (T)op(t[1]); t[2] = (T)(rhs_task ? L16(t[2]) : op(t[2]));
+        };
+        r.tgt = L16(r.tgt);
+        if (r.cnt <= 2) for (uint32_t j = 0; j < r.cnt; j++) triple(r.ldu[j]);
+        else for (uint32_t j = 0; j < r.cnt; j++) triple(&hp.ovf16[r.ovf + 3 * j]);
+        r.pack(w);
       }
-      for (auto &v : hp.pcr_tab) if (v != 0xFFFFu) v = (uint16_t)L16(v);
-      auto fix_i32 = [&](std::vector<int32_t> &a) { for (auto &v : a) if (v >= 0) v = (int32_t)L16((uint32_t)v); };
-      fix_i32(hp.R_a); fix_i32(hp.R_b); fix_i32(hp.C_a); fix_i32(hp.C_b); fix_i32(hp.L_a); fix_i32(hp.L_b); fix_i32(hp.S_a); fix_i32(hp.S_b);
-      fix_i32(hp.S_cp); fix_i32(hp.S_cn); fix_i32(hp.D_a); fix_i32(hp.D_b); fix_i32(hp.V_x); fix_i32(hp.out_x);
-      auto fix_ab = [&](std::vector<uint32_t> &a) {
-        for (auto &v : a) {
-          uint32_t lo = v & 0xffffu, hi = v >> 16;
-          if (lo != 0xFFFFu) lo = L16(lo);
-          if (hi != 0xFFFFu) hi = L16(hi);
-          v = lo | (hi << 16);
+    }
+  };
+  // (an overflow list belongs to ONE record of rec16 and, when the phase has a row-record encoding, to its twin in fus16,
+  // which was emitted with its own copy: emit_factor appends to ovf16 per call — so every list is fixed exactly once)
+  for (int p = 0; p < 2 * nLevels; p++) {
+    const bool ktask = p >= nLevels;
+    const int lvl = ktask ? 2 * nLevels - 1 - p : p;
+    const bool opg = lvl == 0;
+    auto op = [&](uint32_t w) { return opg ? G16(w) : L16(w); };
+    fix_generic(hp.rec16, hp.ph_first[p], hp.ph_cnt[p], ktask, opg);
+    if (!ktask && hp.fus_pairs[p] > 0) {
+      fix_generic(hp.fus16, hp.fus_first[p], hp.fus_gen[p], false, opg);
+      for (uint32_t i = 0; i < hp.fus_pairs[p]; i++) {
+        uint32_t *w = &hp.fus16[((size_t)hp.fus_first[p] + hp.fus_gen[p]) * 4 + (size_t)i * 8];
+        RowRec rr = RowRec::unpack(w);
+        rr.a_ii() = (uint16_t)L16(rr.a_ii()); rr.y_i() = (uint16_t)L16(rr.y_i());
+        for (uint32_t i2 = 0; i2 < rr.pivots(); i2++) {
+          uint16_t *q = rr.pivot(i2);
+          q[0] = (uint16_t)op(q[0]); q[1] = (uint16_t)op(q[1]); q[2] = (uint16_t)op(q[2]);
+          q[3] = (uint16_t)L16(q[3]);
+          if (rr.has_other(i2)) { q[4] = (uint16_t)op(q[4]); q[5] = (uint16_t)L16(q[5]); }
         }
-      };
-      fix_ab(hp.R_ab); fix_ab(hp.C_ab); fix_ab(hp.L_ab); fix_ab(hp.D_ab);
-      if (bad) { err = "internal: hybrid layout met an index on the wrong side"; return SPICEY_ERR_BAD_DESC; }
-      hp.hdr.hybrid = 1; hp.hdr.hyb_g0 = g0; hp.hdr.hyb_g2 = g2; hp.hdr.xoff = nLU - g0 - g2;
+        rr.pack(w);
+      }
     }
   }
+  for (auto &v : hp.pcr_tab) if (v != 0xFFFFu) v = (uint16_t)L16(v);
+  auto fix_i32 = [&](std::vector<int32_t> &a) { for (auto &v : a) if (v >= 0) v = (int32_t)L16((uint32_t)v); };
+  fix_i32(hp.R_a); fix_i32(hp.R_b); fix_i32(hp.C_a); fix_i32(hp.C_b); fix_i32(hp.L_a); fix_i32(hp.L_b); fix_i32(hp.S_a); fix_i32(hp.S_b);
+  fix_i32(hp.S_cp); fix_i32(hp.S_cn); fix_i32(hp.D_a); fix_i32(hp.D_b); fix_i32(hp.V_x); fix_i32(hp.out_x);
+  auto fix_ab = [&](std::vector<uint32_t> &a) {
+    for (auto &v : a) {
+      uint32_t lo = v & 0xffffu, hi = v >> 16;
+      if (lo != 0xFFFFu) lo = L16(lo);
+      if (hi != 0xFFFFu) hi = L16(hi);
+      v = lo | (hi << 16);
+    }
+  };
+  fix_ab(hp.R_ab); fix_ab(hp.C_ab); fix_ab(hp.L_ab); fix_ab(hp.D_ab);
+  if (bad) return false;
+  hp.hdr.hybrid = 1; hp.hdr.hyb_g0 = g0; hp.hdr.hyb_g2 = g2; hp.hdr.xoff = nLU - g0 - g2;
+  return true;
+}
 
+}  // namespace
+
+// The driver: the stages in order, with the early returns between them.  hp is a fresh HostProgram (all three callers in
+// spicey_build_program pass one), so no stage clears what it is about to fill; only the front fall-back (build_fronts) and
+// the retreat from the 16-bit records (build_records16) undo earlier work.
+static int32_t build_program_impl(const SpiceyDesc *dp, HostProgram &hp, std::string &err, const bool slot_major, int front_cut, const bool pcr_top, const bool hybrid) {
+  const int32_t rc0 = spicey_check_desc(dp, err);
+  if (rc0 != SPICEY_OK) return rc0;
+  const SpiceyDesc &d = *dp;
+  Pattern P;
+  Factor F;
+  build_pattern(d, P, hp);                                   // 1
+  match_rows(d, P, hp);                                      // 2a, 2b
+  if (!order_pivots(P, hp)) { err = "internal: ordering lost vertices"; return SPICEY_ERR_BAD_DESC; }  // 3
+  symbolic_factor(d, P, slot_major, F, hp);                  // 4
+  F.Lc = choose_front_cut(d, front_cut, P.n, F, hp);         // 4b
+  build_fronts(P.n, F, hp);
+  build_bins(P.n, F, hp);
+  if (!build_stamps(d, P, F, hp)) { err = "internal: stamp outside the symbolic pattern"; return SPICEY_ERR_BAD_DESC; }  // 5a
+  build_rhs(d, P, hp);
+  build_factor_slices(F, hp);                                // 5b
+  build_backward_slices(P.n, F, hp);                         // 5c
+  build_records16(P, F, hp, slot_major, pcr_top);            // 5c'
+  build_b_descriptors(P.n, F, hp);                           // 5c''
+  build_terminals(d, P, F, hp);                              // 5d
+  hp.hdr.xoff = F.nLU;                                       // 6
+  const bool lay_out_hybrid = hybrid && slot_major && hp.hdr.has16 && F.Lc == 0 && F.nLevels >= 3 && !hp.structurally_singular;
+  if (lay_out_hybrid && !layout_hybrid(F, hp)) { err = "internal: hybrid layout met an index on the wrong side"; return SPICEY_ERR_BAD_DESC; }
   hp.pack();
   return SPICEY_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// The sections of the program blob, in blob order: X(host vector, SpiceyProg pointer it binds to).  pack() and bind() both
+// walk this one list, so a new section is one line here and their order cannot drift apart.  offsets[i] (and the index
+// SPICEY_DUMP_SECTIONS prints) is the position in this list.
+#define SPICEY_PROG_SECTIONS(X)                                                                                        \
+  X(stat_ptr, stat_ptr) X(stat_idx, stat_idx) X(ent_flag, ent_flag) X(dyn_ent, dyn_ent) X(dyn_ptr, dyn_ptr)            \
+  X(dyn_idx, dyn_idx) X(rhs_ptr, rhs_ptr) X(rhs_idx, rhs_idx) X(rhs_cof, rhs_cof) X(lvl_slice, lvl_slice)              \
+  X(upd_slice, upd_slice) X(upd_tgt, upd_tgt) X(upd_cnt, upd_cnt) X(upd_pairs, upd_pairs)                              \
+  X(bk_lvl_slice, bk_lvl_slice) X(bk_slice, bk_slice) X(bk_x, bk_x) X(bk_d, bk_d) X(bk_cnt, bk_cnt) X(bk_pairs, bk_pairs) \
+  X(R_a, R_a) X(R_b, R_b) X(C_a, C_a) X(C_b, C_b) X(L_a, L_a) X(L_b, L_b) X(S_a, S_a) X(S_b, S_b) X(S_cp, S_cp)       \
+  X(S_cn, S_cn) X(D_a, D_a) X(D_b, D_b) X(V_x, V_x) X(out_x, out_x)                                                    \
+  X(rec16, rec16) X(ovf16, ovf16) X(ph_first, ph_first) X(ph_cnt, ph_cnt)                                              \
+  X(ent_dd, ent_dd) X(dynx_ent, dynx_ent) X(dynx_ptr, dynx_ptr) X(dynx_idx, dynx_idx) X(row_desc, row_desc) X(rowx, rowx) \
+  X(R_ab, R_ab) X(C_ab, C_ab) X(L_ab, L_ab) X(D_ab, D_ab)                                                              \
+  X(fronts, fr) X(fr_asm, fr_asm) X(fr_bnd, fr_bnd) X(fr_child, fr_child) X(fr_rel, fr_rel)                            \
+  X(pcr_tab, pcr_tab)                                                                                                  \
+  X(fus16, fus16) X(fus_first, fus_first) X(fus_gen, fus_gen) X(fus_rhs, fus_rhs) X(fus_pairs, fus_pairs)              \
+  X(ent_ro, ent_ro) X(ent_co, ent_co) X(pos_row, pos_row) X(pos_col, pos_col)                                          \
+  X(bin_upd, bin_upd) X(bin_bk, bin_bk) X(col_ptr, col_ptr) X(col_ent, col_ent)
+
 void HostProgram::pack() {
   blob.clear();
   offsets.clear();
-  add_section(blob, offsets, stat_ptr);   // 0
-  add_section(blob, offsets, stat_idx);   // 1
-  add_section(blob, offsets, ent_flag);   // 2
-  add_section(blob, offsets, dyn_ent);    // 3
-  add_section(blob, offsets, dyn_ptr);    // 4
-  add_section(blob, offsets, dyn_idx);    // 5
-  add_section(blob, offsets, rhs_ptr);    // 6
-  add_section(blob, offsets, rhs_idx);    // 7
-  add_section(blob, offsets, rhs_cof);    // 8
-  add_section(blob, offsets, lvl_slice);  // 9
-  add_section(blob, offsets, upd_slice);  // 10
-  add_section(blob, offsets, upd_tgt);    // 11
-  add_section(blob, offsets, upd_cnt);    // 12
-  add_section(blob, offsets, upd_pairs);  // 13
-  add_section(blob, offsets, bk_lvl_slice);  // 14
-  add_section(blob, offsets, bk_slice);   // 15
-  add_section(blob, offsets, bk_x);       // 16
-  add_section(blob, offsets, bk_d);       // 17
-  add_section(blob, offsets, bk_cnt);     // 18
-  add_section(blob, offsets, bk_pairs);   // 19
-  add_section(blob, offsets, R_a); add_section(blob, offsets, R_b);    // 20 21
-  add_section(blob, offsets, C_a); add_section(blob, offsets, C_b);    // 22 23
-  add_section(blob, offsets, L_a); add_section(blob, offsets, L_b);    // 24 25
-  add_section(blob, offsets, S_a); add_section(blob, offsets, S_b);    // 26 27
-  add_section(blob, offsets, S_cp); add_section(blob, offsets, S_cn);  // 28 29
-  add_section(blob, offsets, D_a); add_section(blob, offsets, D_b);    // 30 31
-  add_section(blob, offsets, V_x);    // 32
-  add_section(blob, offsets, out_x);  // 33
-  add_section(blob, offsets, rec16);     // 34
-  add_section(blob, offsets, ovf16);     // 35
-  add_section(blob, offsets, ph_first);  // 36
-  add_section(blob, offsets, ph_cnt);    // 37
-  add_section(blob, offsets, ent_dd);    // 38
-  add_section(blob, offsets, dynx_ent);  // 39
-  add_section(blob, offsets, dynx_ptr);  // 40
-  add_section(blob, offsets, dynx_idx);  // 41
-  add_section(blob, offsets, row_desc);  // 42
-  add_section(blob, offsets, rowx);      // 43
-  add_section(blob, offsets, R_ab); add_section(blob, offsets, C_ab);  // 44 45
-  add_section(blob, offsets, L_ab); add_section(blob, offsets, D_ab);  // 46 47
-  add_section(blob, offsets, fronts);    // 48
-  add_section(blob, offsets, fr_asm);    // 49
-  add_section(blob, offsets, fr_bnd);    // 50
-  add_section(blob, offsets, fr_child);  // 51
-  add_section(blob, offsets, fr_rel);    // 52
-  add_section(blob, offsets, pcr_tab);   // 53
-  add_section(blob, offsets, fus16);     // 54
-  add_section(blob, offsets, fus_first); add_section(blob, offsets, fus_gen);    // 55 56
-  add_section(blob, offsets, fus_rhs); add_section(blob, offsets, fus_pairs);    // 57 58
-  add_section(blob, offsets, ent_ro); add_section(blob, offsets, ent_co);        // 59 60
-  add_section(blob, offsets, pos_row); add_section(blob, offsets, pos_col);      // 61 62
-  add_section(blob, offsets, bin_upd); add_section(blob, offsets, bin_bk);       // 63 64
-  add_section(blob, offsets, col_ptr); add_section(blob, offsets, col_ent);      // 65 66
+#define X(vec, ptr) add_section(blob, offsets, vec);
+  SPICEY_PROG_SECTIONS(X)
+#undef X
   if (getenv("SPICEY_DUMP_SECTIONS")) {  // experiments: bytes per section of the program blob
     for (size_t i = 0; i < offsets.size(); i++) {
       const size_t end = i + 1 < offsets.size() ? offsets[i + 1] : blob.size();
@@ -1563,28 +1755,10 @@ void HostProgram::pack() {
 SpiceyProg HostProgram::bind(const void *base) const {
   SpiceyProg p = hdr;
   const uint8_t *b = (const uint8_t *)base;
-  auto u32 = [&](int i) { return (const uint32_t *)(b + offsets[i]); };
-  auto i32 = [&](int i) { return (const int32_t *)(b + offsets[i]); };
-  p.stat_ptr = u32(0); p.stat_idx = u32(1); p.ent_flag = (const uint8_t *)(b + offsets[2]);
-  p.dyn_ent = u32(3); p.dyn_ptr = u32(4); p.dyn_idx = u32(5);
-  p.rhs_ptr = u32(6); p.rhs_idx = u32(7); p.rhs_cof = u32(8);
-  p.lvl_slice = u32(9); p.upd_slice = (const SpiceySlice *)(b + offsets[10]);
-  p.upd_tgt = u32(11); p.upd_cnt = u32(12); p.upd_pairs = u32(13);
-  p.bk_lvl_slice = u32(14); p.bk_slice = (const SpiceySlice *)(b + offsets[15]);
-  p.bk_x = u32(16); p.bk_d = u32(17); p.bk_cnt = u32(18); p.bk_pairs = u32(19);
-  p.R_a = i32(20); p.R_b = i32(21); p.C_a = i32(22); p.C_b = i32(23); p.L_a = i32(24); p.L_b = i32(25);
-  p.S_a = i32(26); p.S_b = i32(27); p.S_cp = i32(28); p.S_cn = i32(29); p.D_a = i32(30); p.D_b = i32(31);
-  p.V_x = i32(32); p.out_x = i32(33);
-  p.rec16 = u32(34); p.ovf16 = (const uint16_t *)(b + offsets[35]); p.ph_first = u32(36); p.ph_cnt = u32(37);
-  p.ent_dd = u32(38); p.dynx_ent = u32(39); p.dynx_ptr = u32(40); p.dynx_idx = u32(41); p.row_desc = u32(42); p.rowx = u32(43);
-  p.R_ab = u32(44); p.C_ab = u32(45); p.L_ab = u32(46); p.D_ab = u32(47);
-  p.fr = (const SpiceyFront *)(b + offsets[48]);
-  p.fr_asm = u32(49); p.fr_bnd = u32(50); p.fr_child = u32(51); p.fr_rel = u32(52);
-  p.pcr_tab = (const uint16_t *)(b + offsets[53]);
-  p.fus16 = u32(54); p.fus_first = u32(55); p.fus_gen = u32(56); p.fus_rhs = u32(57); p.fus_pairs = u32(58);
-  p.ent_ro = i32(59); p.ent_co = i32(60); p.pos_row = i32(61); p.pos_col = i32(62);
-  p.bin_upd = u32(63); p.bin_bk = u32(64);
-  p.col_ptr = u32(65); p.col_ent = u32(66);
+  size_t i = 0;
+#define X(vec, ptr) p.ptr = (decltype(p.ptr))(b + offsets[i++]);
+  SPICEY_PROG_SECTIONS(X)
+#undef X
   return p;
 }
 
@@ -1753,28 +1927,25 @@ void spicey_build_resident(const HostProgram &hp, int T, int rmax, HostResident 
   out.pack();
 }
 
+// The sections of the resident blob, in blob order (host vector = SpiceyResident pointer of the same name): one list for
+// pack() and bind(), like SPICEY_PROG_SECTIONS.
+#define SPICEY_RESIDENT_SECTIONS(X) X(res) X(res_phase) X(st_first) X(st_cnt) X(st_rhs) X(st_fus) X(st_desc)
+
 void HostResident::pack() {
   blob.clear();
   offsets.clear();
-  add_section(blob, offsets, res);
-  add_section(blob, offsets, res_phase);
-  add_section(blob, offsets, st_first);
-  add_section(blob, offsets, st_cnt);
-  add_section(blob, offsets, st_rhs);
-  add_section(blob, offsets, st_fus);
-  add_section(blob, offsets, st_desc);
+#define X(name) add_section(blob, offsets, name);
+  SPICEY_RESIDENT_SECTIONS(X)
+#undef X
 }
 
 SpiceyResident HostResident::bind(const void *base) const {
   SpiceyResident r{};
   const uint8_t *b = (const uint8_t *)base;
-  r.res = (const uint32_t *)(b + offsets[0]);
-  r.res_phase = (const int32_t *)(b + offsets[1]);
-  r.st_first = (const uint32_t *)(b + offsets[2]);
-  r.st_cnt = (const uint32_t *)(b + offsets[3]);
-  r.st_rhs = (const uint32_t *)(b + offsets[4]);
-  r.st_fus = (const uint32_t *)(b + offsets[5]);
-  r.st_desc = (const uint32_t *)(b + offsets[6]);
+  size_t i = 0;
+#define X(name) r.name = (decltype(r.name))(b + offsets[i++]);
+  SPICEY_RESIDENT_SECTIONS(X)
+#undef X
   r.rmax = rmax;
   r.T = T;
   r.tail_first = tail_first;

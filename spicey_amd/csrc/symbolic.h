@@ -44,10 +44,11 @@ struct HostProgram {
 
   // Serialise all arrays into one blob (16-byte aligned sections) and return a SpiceyProg whose
   // pointers are `base + offset`.  `base` may be a device address: the blob is then memcpy'd there.
+  // Both walk the one section list of symbolic.cpp (SPICEY_PROG_SECTIONS; HostResident: SPICEY_RESIDENT_SECTIONS).
   std::vector<uint8_t> blob;
   void pack();
   SpiceyProg bind(const void *base) const;
-  std::vector<size_t> offsets;  // section offsets in pack() order
+  std::vector<size_t> offsets;  // section offsets in the order of the section list
 };
 
 // The descriptor checks every handle starts with (counts, node ids, value arrays, out_nodes): SPICEY_OK or

@@ -495,3 +495,71 @@ extern "C" int32_t spicey_emul_front_stats(const SpiceyDesc *d, int32_t front_cu
   }
   return SPICEY_OK;
 }
+
+// Everything the rest of the library consumes of spicey_build_program(d, bank_aware, front_cut, pcr_top, hybrid), as one
+// byte string (tests/test_program_identity.py compares its digest with what the commit before a refactor of the symbolic
+// phase gave).  Public interface of symbolic.h only.  Every item is written as an 8-byte length and its bytes: return code
+// and error text; on SPICEY_OK also the host-side counts, the header scalars field by field (the struct holds pointers and
+// padding), blob, offsets, cpos, rpos, level, parent, ph_rhs, front_work and, where the program has 16-bit records, the
+// resident layouts of the two transient geometries (blob, offsets, scalars).
+// scalars[16]: rc, structurally_singular, has16, hybrid, pcr_n, nFronts, nBins, max_front_mp, row records (all levels),
+// ovf16 length, numbering (bank_aware programs with 16-bit records: 1 = the CSR order was kept, 2 = slot-major; else 0),
+// nLevels, nLU, blob bytes, resident layouts written, 0.
+// Returns the length of the string, which spicey_emul_program_dump_copy hands out.
+static std::vector<uint8_t> g_dump;
+extern "C" int64_t spicey_emul_program_dump(const SpiceyDesc *d, int32_t bank_aware, int32_t front_cut, int32_t pcr_top, int32_t hybrid,
+                                            int64_t *scalars /*[16]*/) {
+  std::vector<uint8_t> &o = g_dump;
+  o.clear();
+  auto raw = [&](const void *p, size_t bytes) {
+    const uint64_t len = bytes;
+    o.insert(o.end(), (const uint8_t *)&len, (const uint8_t *)&len + 8);
+    if (bytes) o.insert(o.end(), (const uint8_t *)p, (const uint8_t *)p + bytes);
+  };
+  auto i64s = [&](std::initializer_list<int64_t> v) { raw(v.begin(), v.size() * 8); };
+  auto sizes = [&](const std::vector<size_t> &v) { std::vector<uint64_t> w(v.begin(), v.end()); raw(w.data(), w.size() * 8); };
+  for (int i = 0; i < 16; i++) scalars[i] = 0;
+  HostProgram hp;
+  std::string err;
+  const int32_t rc = spicey_build_program(d, hp, err, bank_aware != 0, front_cut, pcr_top != 0, hybrid != 0);
+  scalars[0] = rc;
+  i64s({rc});
+  raw(err.data(), err.size());
+  if (rc != SPICEY_OK) return (int64_t)o.size();
+  const SpiceyProg &h = hp.hdr;
+  i64s({hp.structurally_singular ? 1 : 0, hp.nnzA, hp.n_products, hp.n_bk_products});
+  i64s({h.n, h.nLU, h.nRestore, h.nW, h.nLevels, h.nR, h.nC, h.nL, h.nV, h.nS, h.nD, h.nU, h.nGdyn, h.nGstat, h.nOut, h.nCur,
+        h.nDynEnt, h.nRhsIdx, h.nUpdSlices, h.nBkSlices, h.nDynX, h.nRowX, h.nRec16, h.has16, h.pcr_n, h.pcr_level,
+        h.nFronts, h.front_cut, h.one_slot, h.max_front_mp, h.front_ws, h.nBins, h.hybrid, h.hyb_g0, h.hyb_g2, h.xoff});
+  raw(hp.blob.data(), hp.blob.size());
+  sizes(hp.offsets);
+  raw(hp.cpos.data(), hp.cpos.size() * 4); raw(hp.rpos.data(), hp.rpos.size() * 4);
+  raw(hp.level.data(), hp.level.size() * 4); raw(hp.parent.data(), hp.parent.size() * 4);
+  raw(hp.ph_rhs.data(), hp.ph_rhs.size() * 4);
+  raw(hp.front_work.data(), hp.front_work.size() * 8);
+  int n_res = 0;
+  if (h.has16) {
+    const int geo[2][2] = {{512, 4}, {1024, 8}};
+    for (auto &g : geo) {
+      HostResident hr;
+      spicey_build_resident(hp, g[0], g[1], hr, 24, true);
+      raw(hr.blob.data(), hr.blob.size());
+      sizes(hr.offsets);
+      i64s({hr.rmax, hr.T, hr.tail_first, hr.tail_n, hr.k_merge, hr.resident_tasks, hr.streamed_tasks});
+      n_res++;
+    }
+  }
+  int64_t rows = 0;
+  for (uint32_t v : hp.fus_pairs) rows += v;
+  int numbering = 0;
+  if (bank_aware && !hybrid && h.has16 && !hp.structurally_singular) {
+    HostProgram csr;
+    std::string err2;
+    if (spicey_build_program(d, csr, err2, false, front_cut, pcr_top != 0, false) == SPICEY_OK) numbering = csr.blob == hp.blob ? 1 : 2;
+  }
+  const int64_t sc[16] = {rc, hp.structurally_singular ? 1 : 0, h.has16, h.hybrid, h.pcr_n, h.nFronts, h.nBins, h.max_front_mp, rows,
+                          (int64_t)hp.ovf16.size(), numbering, h.nLevels, h.nLU, (int64_t)hp.blob.size(), n_res, 0};
+  for (int i = 0; i < 16; i++) scalars[i] = sc[i];
+  return (int64_t)o.size();
+}
+extern "C" void spicey_emul_program_dump_copy(uint8_t *out) { if (!g_dump.empty()) memcpy(out, g_dump.data(), g_dump.size()); }

@@ -179,3 +179,24 @@ def bin_stats(flat: abi.FlatCircuit, front_cut: int = -1) -> dict:
     rc = L.spicey_emul_bin_stats(C.byref(d), front_cut, out)
     assert rc == 0, rc
     return dict(zip(("bins", "cut", "factor_slices", "interface_slices", "backward_slices", "widest_bin_slices"), list(out)))
+
+
+PROGRAM_SCALARS = ("rc", "structurally_singular", "has16", "hybrid", "pcr_n", "nFronts", "nBins", "max_front_mp", "fus_pairs",
+                   "ovf16", "numbering", "nLevels", "nLU", "blob_bytes", "resident_layouts")
+
+
+def program_dump(flat: abi.FlatCircuit, bank_aware: bool = True, front_cut: int = 0, pcr_top: bool = True, hybrid: bool = False,
+                 desc=None):
+    """(bytes, scalars) of spicey_emul_program_dump: everything spicey_build_program hands to the rest of the library, and the
+    few counts of PROGRAM_SCALARS (numbering: 1 = CSR order kept, 2 = slot-major kept, 0 = not compared)."""
+    L = lib()
+    L.spicey_emul_program_dump.restype = C.c_int64
+    L.spicey_emul_program_dump.argtypes = [C.POINTER(abi.SpiceyDesc), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]
+    L.spicey_emul_program_dump_copy.restype = None
+    L.spicey_emul_program_dump_copy.argtypes = [C.c_void_p]
+    d = flat.desc() if desc is None else desc
+    sc = np.zeros(16, np.int64)
+    size = L.spicey_emul_program_dump(C.byref(d), int(bank_aware), int(front_cut), int(pcr_top), int(hybrid), _p(sc, C.c_int64))
+    out = np.zeros(max(size, 1), np.uint8)
+    L.spicey_emul_program_dump_copy(out.ctypes.data)
+    return out[:size].tobytes(), dict(zip(PROGRAM_SCALARS, (int(x) for x in sc)))
