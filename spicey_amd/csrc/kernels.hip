@@ -636,17 +636,17 @@ static hipError_t launch_v2_shape(const SpiceyProg *P, const SpiceyResident *Q, 
   constexpr SpiceyV2Shape s = SPICEY_V2_SHAPES[I];
   return launch_v2_t<1, s.rmax, s.nsv, s.nel, s.threads, s.minw, s.hybrid, PT>(P, Q, R, grid, threads, lds, st);
 }
-static decltype(&launch_v2_shape<0>) const launch_v2_by_shape[] = {launch_v2_shape<0>, launch_v2_shape<1>, launch_v2_shape<2>,
-                                                                    launch_v2_shape<3>, launch_v2_shape<4>, launch_v2_shape<5>};
+static decltype(&launch_v2_shape<0>) const launch_v2_by_shape[] = {launch_v2_shape<0>, launch_v2_shape<1>, launch_v2_shape<2>, launch_v2_shape<3>,
+                                                                    launch_v2_shape<4>, launch_v2_shape<5>, launch_v2_shape<6>};
 static_assert(sizeof(launch_v2_by_shape) / sizeof(launch_v2_by_shape[0]) == SPICEY_V2_NSHAPES, "one launcher per v2 build");
 // the same builds with the phase table (null: that shape has none and keeps the scalar loads — SPICEY_V2_SHAPES order)
-static decltype(&launch_v2_shape<0>) const launch_v2_pt_by_shape[] = {launch_v2_shape<0, 1>, launch_v2_shape<1, 1>, launch_v2_shape<2, 1>,
-                                                                       launch_v2_shape<3, 1>, launch_v2_shape<4, 1>, launch_v2_shape<5, 1>};
+static decltype(&launch_v2_shape<0>) const launch_v2_pt_by_shape[] = {launch_v2_shape<0, 1>, launch_v2_shape<1, 1>, launch_v2_shape<2, 1>, launch_v2_shape<3, 1>,
+                                                                       launch_v2_shape<4, 1>, launch_v2_shape<5, 1>, launch_v2_shape<6, 1>};
 static_assert(sizeof(launch_v2_pt_by_shape) / sizeof(launch_v2_pt_by_shape[0]) == SPICEY_V2_NSHAPES, "one entry per v2 build");
 
 hipError_t spicey_launch_tran_v2(const SpiceyProg &Ph, const SpiceyResident &Qh, const SpiceyProg *P, const SpiceyResident *Q, const SpiceyRun *R, int K, int grid,
                                  int threads, hipStream_t st, bool packed, bool phase_table) {
-  const int shape = K == 1 ? spicey_v2_shape(threads, packed, Ph.hybrid != 0) : -1;
+  const int shape = K == 1 ? spicey_v2_shape(threads, packed, Ph.hybrid != 0, packed && Ph.fresh_fill != 0) : -1;  // (a fresh-fill program runs on the build that decodes its flags: spicey_plan makes one for the packed geometry only)
   if (shape < 0) return hipErrorInvalidValue;
   // the table sits in the tail area behind the tridiagonal top's index table: only where it fits there (tran_exec.h)
   const bool pt = phase_table && launch_v2_pt_by_shape[shape] != nullptr && spicey_pt_fits(Ph.pcr_n, Ph.pcr_level, Qh.tail_n);

@@ -30,10 +30,10 @@ size_t spicey_gw_doubles_per_wg(const SpiceyProg &P, int K) {
   return ((size_t)P.nW + P.nU + P.nGdyn) * K + (((size_t)P.nS * K + 1) >> 1);
 }
 
-int spicey_v2_shape(int threads, bool packed, bool hybrid) {
+int spicey_v2_shape(int threads, bool packed, bool hybrid, bool fresh) {
   for (int i = 0; i < SPICEY_V2_NSHAPES; i++) {
     const SpiceyV2Shape &s = SPICEY_V2_SHAPES[i];
-    if (s.packed == packed && s.hybrid == hybrid && threads <= s.threads) return i;
+    if (s.packed == packed && s.hybrid == hybrid && s.fresh == fresh && threads <= s.threads) return i;
   }
   return -1;
 }
@@ -46,7 +46,7 @@ static const SpiceyV2Shape &v2_build(int threads, bool packed = false, bool hybr
 SpiceyKnobs spicey_read_knobs() {
   const char *ms = getenv("SPICEY_GROUP_TIMEOUT_MS");
   return {getenv("SPICEY_NO_HYBRID") != nullptr, getenv("SPICEY_FRONT_RIGHT_LOOKING") != nullptr, getenv("SPICEY_TEST_FORCE_GROUP_ABORT") != nullptr,
-          ms ? atoi(ms) : 0, getenv("SPICEY_NO_PHASE_TABLE") != nullptr};
+          ms ? atoi(ms) : 0, getenv("SPICEY_NO_PHASE_TABLE") != nullptr, getenv("SPICEY_NO_FRESH_FILL") != nullptr, getenv("SPICEY_FRESH_FILL_LINEAR") != nullptr};
 }
 
 static int pick_threads(const HostProgram &hp, bool v2) {
@@ -186,7 +186,8 @@ int32_t spicey_plan(const SpiceyDesc *desc, const SpiceyOptions &opt, const Spic
   if (front_cut < 0 && desc && desc->n_inst >= 512) front_cut = 0;  // big batches fill the chip with interleaved instances instead
   // tridiagonal top by cyclic reduction (16-bit records, one instance per workgroup); diagnostics: bit 5 = never
   const bool pcr_top = !((opt.debug >> 5) & 1) && opt.inst_per_wg <= 1;
-  int32_t rc = spicey_build_program(desc, hp, err, !((opt.debug >> 2) & 1), front_cut, pcr_top);  // diagnostics: bit 2 = plain CSR numbering
+  const bool bank_aware = !((opt.debug >> 2) & 1);  // diagnostics: bit 2 = plain CSR numbering
+  int32_t rc = spicey_build_program(desc, hp, err, bank_aware, front_cut, pcr_top);
   if (rc != SPICEY_OK) return rc;
   plan.n_inst = desc->n_inst;
   plan.algo_bytes = spicey_algorithmic_bytes(desc, hp.nnzA, hp.hdr.nLU);
@@ -263,6 +264,23 @@ int32_t spicey_plan(const SpiceyDesc *desc, const SpiceyOptions &opt, const Spic
     if (opt.geometry < 0 || opt.geometry > 2) return fail(SPICEY_ERR_BAD_DESC, "geometry must be 0, 1 or 2");
     plan.packed = packable && !diag && !P.hybrid && (opt.geometry == 2 || (opt.geometry == 0 && plan.n_inst >= 2 * ncu && opt.threads == 0));
     if (plan.packed) plan.T = 512;
+    // The packed geometry runs a FRESH-FILL program (program.h: nKeep) on the build made for it where the entries phase B
+    // still restores — the kept ones, the dynamic ones among them — fit its two per thread.  Geometry and threads were
+    // decided above on nRestore, which the option does not move; nor does it move the records' order, so the resident
+    // layout below is the default program's.  A linear circuit keeps the default program: its matrix is stamped and
+    // factored once per run (factor reuse), so the re-stamping that the fresh class saves does not happen there.
+    const bool linear = P.nD == 0 && P.nS == 0 && P.nDynEnt == 0;
+    if (plan.packed && !knobs.no_fresh_fill && (!linear || knobs.fresh_fill_linear)) {
+      const SpiceyV2Shape &fs = SPICEY_V2_SHAPES[spicey_v2_shape(plan.T, true, false, true)];
+      HostProgram fp;
+      std::string err2;
+      if (spicey_build_program(desc, fp, err2, bank_aware, front_cut, pcr_top, false, true) == SPICEY_OK && fp.hdr.has16 && fp.hdr.fresh_fill &&
+          !fp.structurally_singular && fp.hdr.nRestore == P.nRestore && fp.hdr.nW == P.nW && fp.hdr.nKeep <= fs.nsv * plan.T &&
+          fp.hdr.nDynEnt <= fs.nsv * plan.T) {
+        hp = std::move(fp);
+        plan.fresh = true;
+      }
+    }
     // tail levels go to LDS: as many as fit beside the workspace (1 KB each), at most 24; the packed geometry
     // must leave room for a second workgroup on the CU
     const size_t lds_cap = plan.packed ? SPICEY_LDS_MAX / 2 : SPICEY_LDS_MAX;

@@ -32,18 +32,26 @@ size_t spicey_gw_doubles_per_wg(const SpiceyProg &P, int K);
 // 1000-node chains only the widest factor level is streamed, with the next record fetched behind the one at hand.
 // Hybrid workspace: 512 threads as the plain build, or 1024 threads with 4 slots (with 8 the build spills 10 registers
 // at the 128-register cap).
+// `fresh` = the packed build for FRESH-FILL programs (program.h: nKeep): phase B restores the kept entries only, two per
+// thread, both with a dynamic-stamp descriptor — 8 vector registers fewer than the 6-entry packed build, which pay for
+// keeping the first streamed record of factor level 0 in flight under B (tran_exec.h).  spicey_plan takes it, with a
+// program built with fresh_fill, where the kept and the dynamic entries fit 2 x 512 and the circuit is not linear (a
+// linear circuit reuses the factors of step 0: B re-stamps nothing after it, so there is nothing to save, and the
+// build's few extra instructions per record showed as -1.7 % on rc_ladder(1000) x 512); otherwise the 6-entry build.
 #define SPICEY_V2_RMAX256 28  // (32 slots spilled 6 vector registers to AGPRs: refused by check_no_spills.py)
 struct SpiceyV2Shape {
   bool packed, hybrid;
   int threads, rmax, nsv, nel, minw;  // workgroup size (launch bound), slots, re-stamped entries and elements per thread, waves per SIMD
+  bool fresh = false;
 };
 // (spicey_launch_tran_v2 instantiates one kernel per entry; each kind in ascending threads)
-constexpr SpiceyV2Shape SPICEY_V2_SHAPES[] = {{true, false, 512, 4, 6, 2, 4},    {false, true, 512, 16, 8, 2, 2},
-                                              {false, true, 1024, 4, 4, 1, 4},   {false, false, 256, SPICEY_V2_RMAX256, 12, 4, 1},
+constexpr SpiceyV2Shape SPICEY_V2_SHAPES[] = {{true, false, 512, 4, 6, 2, 4},    {true, false, 512, 4, 2, 2, 4, true},
+                                              {false, true, 512, 16, 8, 2, 2},   {false, true, 1024, 4, 4, 1, 4},
+                                              {false, false, 256, SPICEY_V2_RMAX256, 12, 4, 1},
                                               {false, false, 512, 16, 8, 2, 2},  {false, false, 1024, 8, 4, 1, 4}};
 constexpr int SPICEY_V2_NSHAPES = (int)(sizeof(SPICEY_V2_SHAPES) / sizeof(SPICEY_V2_SHAPES[0]));
 // index of the build that runs `threads` threads: the first of the kind that holds them; -1 = none
-int spicey_v2_shape(int threads, bool packed, bool hybrid);
+int spicey_v2_shape(int threads, bool packed, bool hybrid, bool fresh = false);
 
 // Environment knobs of the transient handle, read once by spicey_create.
 struct SpiceyKnobs {
@@ -52,6 +60,8 @@ struct SpiceyKnobs {
   bool force_group_abort = false;    // SPICEY_TEST_FORCE_GROUP_ABORT: tests, the first attempt of every group launch aborts
   int group_timeout_ms = 0;          // SPICEY_GROUP_TIMEOUT_MS: group-mode wait bound when SpiceyOptions leaves it 0
   bool no_phase_table = false;       // SPICEY_NO_PHASE_TABLE: the 16-bit interpreter fetches its phase arguments by scalar loads in every phase (tran_exec.h)
+  bool no_fresh_fill = false;        // SPICEY_NO_FRESH_FILL: the packed geometry keeps the default program and the 6-entry build (the in-library A/B switch)
+  bool fresh_fill_linear = false;    // SPICEY_FRESH_FILL_LINEAR: tests, a linear circuit (factor reuse) takes the fresh build too
 };
 SpiceyKnobs spicey_read_knobs();
 
@@ -101,6 +111,7 @@ struct LaunchPlan {
   int n_inst = 0, K = 1, T = 256, grid = 1, interp = 1;
   int G = 1;             // workgroups per instance group (group mode: global workspace only)
   bool packed = false;   // two 512-thread workgroups per CU
+  bool fresh = false;    // packed: hp is a fresh-fill program and runs on the fresh build (SPICEY_V2_SHAPES)
   bool lds = true;       // workspace in LDS (else global memory)
   size_t lds_bytes = 0;
   int64_t algo_bytes = 0;

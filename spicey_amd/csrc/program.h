@@ -30,6 +30,11 @@
 #define SPICEY_R16_RECIP 0x02u
 #define SPICEY_R16_K 0x01u
 #define SPICEY_R16_FUSED 0x04u  // a ROW record of two 16-byte halves (fus16, below)
+#define SPICEY_R16_FRESH 0x08u  // factor record: the FIRST task of the solve that targets a fresh-fill entry (SpiceyProg::nKeep) — it starts from 0.0 instead of reading the target
+// the same for the (up to three) fill targets of a row record, in its meta half-word (bits 0-1 pivots, 4-5 has_o, 8-15 flags)
+#define SPICEY_ROW_FRESH_AII 0x04u
+#define SPICEY_ROW_FRESH_O0 0x40u
+#define SPICEY_ROW_FRESH_O1 0x80u
 
 // Dense front of the upper elimination tree (large instances, fronts_exec.h): a supernode — `p` consecutive pivots
 // whose rows share one structure — with its `q` boundary unknowns, stored as a dense (Mp x ld) row-major block of the
@@ -195,6 +200,16 @@ struct SpiceyProg {
   const int32_t *R_a, *R_b, *C_a, *C_b, *L_a, *L_b, *S_a, *S_b, *S_cp, *S_cn, *D_a, *D_b;
   const int32_t *V_x;   // [nV] W index of the branch current
   const int32_t *out_x; // [nOut] W index of each recorded node voltage
+
+  // --- fresh fill (spicey_build_program's fresh_fill; 16-bit interpreter, packed geometry): the update targets are numbered
+  //     [dynamic | kept targets | fresh fill | never modified] and nKeep is the start of the fresh class, nRestore its end.  A
+  //     fresh entry is zero in A (no static, no dynamic stamp), so nothing has to put the zero back before every solve: the
+  //     first factor task that targets it — flagged SPICEY_R16_FRESH / SPICEY_ROW_FRESH_* in BOTH encodings of its phase —
+  //     starts from 0.0, phase B restores [0, nKeep) only, and no record of that or an earlier phase reads the entry.  The
+  //     32-bit lists are not flagged: their interpreter restores [0, nRestore) as ever (a fresh entry's static value is 0).
+  //     Without the option nKeep == nRestore, fresh_fill == 0 and no record carries a flag.
+  //     (Last in the struct: the offsets of every field above are what they were.)
+  int32_t nKeep, fresh_fill;
 };
 
 // Register-resident part of the program, built for one workgroup size T (spicey_build_resident):
@@ -207,7 +222,8 @@ struct SpiceyResident {
   // everything a streamed phase needs to find its records, in ONE 32-byte descriptor per phase (one scalar load instead of a
   // chain of dependent ones in front of the first record fetch): {rows (0 | 1), first, count, rhs_count, rem_first, rem_count,
   // rem_rhs, 0} — first / rem_first in 16-byte units of rec16 (rows = 0) or fus16 (rows = 1: `first` = the row pairs,
-  // `rem_*` = the generic remainder); *_rhs = the leading right-hand-side records a reused factorisation runs
+  // `rem_*` = the generic remainder); *_rhs = the leading right-hand-side records a reused factorisation runs; the last word
+  // of phase 0's descriptor carries SpiceyProg::nKeep of a fresh-fill program
   const uint32_t *st_desc; // [2L][8]
   const uint32_t *res;        // [RMAX][T][4]
   const int32_t *res_phase;   // [T/64][RMAX]

@@ -280,6 +280,7 @@ struct EntryIndex {
   // CSR of the permuted L+U pattern.  Entry IDS (the W indices the device uses) are a renumbering of the
   // CSR positions by class: [dynamic | static update targets | static never-modified], so that only the first
   // two classes have to be re-stamped every step and the dynamic ones are contiguous (wave-uniform paths).
+  // With fresh_fill the update targets split into [kept | fresh fill] (symbolic_factor, program.h: nKeep).
   std::vector<int> ptr, col, id_of_pos, row_of_id, col_of_id;
   int pos(int r, int c) const {
     auto b = col.begin() + ptr[r], e = col.begin() + ptr[r + 1];
@@ -421,7 +422,8 @@ int64_t spicey_algorithmic_bytes(const SpiceyDesc *d, int32_t nnzA, int32_t nnzL
          16 * ((int64_t)d->nC + d->nL + d->nD) + 8 * ((int64_t)d->n_nodes + etot);
 }
 
-static int32_t build_program_impl(const SpiceyDesc *d, HostProgram &hp, std::string &err, bool slot_major, int front_cut, bool pcr_top, bool hybrid = false);
+static int32_t build_program_impl(const SpiceyDesc *d, HostProgram &hp, std::string &err, bool slot_major, int front_cut, bool pcr_top, bool hybrid = false,
+                                  bool fresh_fill = false);
 
 
 // LDS cycles the operand reads of the compact records cost per solve (every half-wave group and operand role: the
@@ -463,14 +465,14 @@ void spicey_bank_cost(const HostProgram &hp, int64_t *cycles, int64_t *ideal) {
 // order.  For programs that run from LDS (16-bit records) both are compiled and the one whose operand reads cost fewer
 // LDS cycles is kept (chains: 2.65 -> 1.88 conflict factor; small meshes are sometimes better off in CSR order).
 // Circuits on the global-workspace path keep the CSR order: LDS banks do not matter there.
-int32_t spicey_build_program(const SpiceyDesc *d, HostProgram &hp, std::string &err, bool bank_aware, int front_cut, bool pcr_top, bool hybrid) {
+int32_t spicey_build_program(const SpiceyDesc *d, HostProgram &hp, std::string &err, bool bank_aware, int front_cut, bool pcr_top, bool hybrid, bool fresh_fill) {
   hp = HostProgram();
   if (hybrid) return build_program_impl(d, hp, err, true, 0, pcr_top, true);  // (the leaf-owned id ranges need the slot-major numbering)
-  int32_t rc = build_program_impl(d, hp, err, false, front_cut, pcr_top);
+  int32_t rc = build_program_impl(d, hp, err, false, front_cut, pcr_top, false, fresh_fill);
   if (rc != SPICEY_OK || hp.structurally_singular || !hp.hdr.has16 || !bank_aware) return rc;
   HostProgram alt;
   std::string err2;
-  if (build_program_impl(d, alt, err2, true, 0, pcr_top) == SPICEY_OK && alt.hdr.has16) {
+  if (build_program_impl(d, alt, err2, true, 0, pcr_top, false, fresh_fill) == SPICEY_OK && alt.hdr.has16) {
     int64_t c0, i0, c1, i1;
     spicey_bank_cost(hp, &c0, &i0);
     spicey_bank_cost(alt, &c1, &i1);
@@ -539,6 +541,7 @@ struct Factor {
   std::vector<char> in_top;    // pivots of the tridiagonal top
   int pcrL = 0;                // its first level (0: none)
   std::vector<std::vector<uint32_t>> stat, dyn;  // per entry: static / dynamic stamps (conductance index | sign)
+  std::vector<char> fresh;     // per entry: of the fresh-fill class (all 0 without the option)
 };
 
 typedef std::pair<uint32_t, std::vector<uint32_t>> Task;  // (target, its products as flat (l, d, u) triples)
@@ -774,7 +777,12 @@ bool order_pivots(Pattern &P, HostProgram &hp) {
 }
 
 // ---- 4. symbolic factorisation (symmetric pattern), etree, levels, entry numbering --------------
-void symbolic_factor(const SpiceyDesc &d, const Pattern &P, bool slot_major, Factor &F, HostProgram &hp) {
+// fresh_fill: the update targets that are zero in A (no stamp of either kind: pure fill) become a class of their own behind
+// the kept targets (program.h: nKeep).  The first factor task on such an entry creates it (build_records16 flags it).  Under
+// a tridiagonal top the fills that only the top's own pivots would make have no task at all — the top is solved by cyclic
+// reduction, which forms no such entry — and no record or table reads them: they are of the class as well, dead weight
+// that phase B no longer restores.
+void symbolic_factor(const SpiceyDesc &d, const Pattern &P, bool slot_major, bool fresh_fill, Factor &F, HostProgram &hp) {
   const int n = P.n;
   Adj &upper = F.upper, &children = F.children;
   upper.assign(n, {});
@@ -843,6 +851,16 @@ void symbolic_factor(const SpiceyDesc &d, const Pattern &P, bool slot_major, Fac
     for (int k = 0; k < n; k++)
       for (int a : upper[k])
         for (int b : upper[k]) is_tgt[E.pos(a, b)] = 1;
+    std::vector<uint8_t> is_fresh(nLU, 0);
+    if (fresh_fill && !hp.structurally_singular) {
+      std::vector<uint8_t> in_A(nLU, 0);  // every structural entry of A carries a stamp (build_stamps walks the same elements)
+      for (int r = 0; r < n; r++)
+        for (int c : P.arow[r]) {
+          const int p = E.pos(hp.rpos[r], hp.cpos[c]);
+          if (p >= 0) in_A[p] = 1;
+        }
+      for (int p = 0; p < nLU; p++) is_fresh[p] = is_tgt[p] && !is_dyn[p] && !in_A[p];
+    }
     // Numbering inside each class: SLOT-MAJOR over the pivots of a level — (level of the owning pivot m = min(row,
     // col), diagonal / L / U, position of the other index in upper[m], m).  The factor tasks of a phase are ordered
     // by (slot pair, pivot), so the 32 lanes of a half-wave read the same slot of 32 consecutive pivots: consecutive
@@ -856,7 +874,7 @@ void symbolic_factor(const SpiceyDesc &d, const Pattern &P, bool slot_major, Fac
       std::vector<std::array<int64_t, 2>> key(nLU);
       for (int p = 0; p < nLU; p++) {
         const int r = posr[p], c = E.col[p], m = std::min(r, c), o = std::max(r, c);
-        const int cls = is_dyn[p] ? 0 : (is_tgt[p] ? 1 : 2);
+        const int cls = is_dyn[p] ? 0 : (is_tgt[p] ? (is_fresh[p] ? 2 : 1) : 3);
         int64_t slot = 0;
         if (o != m) slot = std::lower_bound(upper[m].begin(), upper[m].end(), o) - upper[m].begin();
         const int kind = r == c ? 0 : (c < r ? 1 : 2);
@@ -871,6 +889,12 @@ void symbolic_factor(const SpiceyDesc &d, const Pattern &P, bool slot_major, Fac
     int nrest = 0;
     for (int p = 0; p < nLU; p++) nrest += (is_dyn[p] || is_tgt[p]) ? 1 : 0;
     hp.hdr.nRestore = nrest;
+    int nfresh = 0;
+    F.fresh.assign(nLU, 0);
+    for (int p = 0; p < nLU; p++)
+      if (is_fresh[p]) { nfresh++; F.fresh[E.id_of_pos[p]] = 1; }
+    hp.hdr.nKeep = nrest - nfresh;
+    hp.hdr.fresh_fill = fresh_fill ? 1 : 0;
     E.row_of_id.assign(nLU, 0); E.col_of_id.assign(nLU, 0);
     for (int r = 0; r < n; r++)
       for (int p = E.ptr[r]; p < E.ptr[r + 1]; p++) { E.row_of_id[E.id_of_pos[p]] = r; E.col_of_id[E.id_of_pos[p]] = E.col[p]; }
@@ -1323,7 +1347,7 @@ std::vector<int> tridiagonal_top(const Pattern &P, const Factor &F, const HostPr
 }
 
 // One factor task of the 16-bit records
-struct FactorTask { uint32_t t; bool recip; std::vector<uint32_t> tr; int32_t si, sj, k; };  // tr = (l, d, u)*; si / sj: slots of the L / U operand in upper[k] (sj = -1: rhs)
+struct FactorTask { uint32_t t; bool recip; std::vector<uint32_t> tr; int32_t si, sj, k; bool fresh = false; };  // tr = (l, d, u)*; si / sj: slots of the L / U operand in upper[k] (sj = -1: rhs); fresh: the first task on a fresh-fill target
 
 // The tasks of factor level l in record order; sets too_long where a task has more products than a record's count holds.
 std::vector<FactorTask> level_factor_tasks(const Factor &F, const HostProgram &hp, int l, bool slot_major, bool &too_long) {
@@ -1345,7 +1369,7 @@ std::vector<FactorTask> level_factor_tasks(const Factor &F, const HostProgram &h
       recip = E.col_of_id[p.tgt] == r && hp.level[r] == l + 1 && !F.in_top[r];  // (the cyclic reduction wants the diagonal itself)
     }
     if (tr.size() / 3 > 255) too_long = true;
-    uts.push_back({p.tgt, recip, std::move(tr), p.si, p.sj, p.k});
+    uts.push_back({p.tgt, recip, std::move(tr), p.si, p.sj, p.k, false});
   });
   // right-hand-side tasks first (a linear circuit's reused factorisation runs only those), then the same
   // (recip, count) next to each other: the 64-lane chunks then take one code path
@@ -1367,7 +1391,7 @@ std::vector<FactorTask> level_factor_tasks(const Factor &F, const HostProgram &h
 void emit_factor(const FactorTask &u, std::vector<uint32_t> &dst, std::vector<uint16_t> &ovf16) {
   FactorRec r;
   r.tgt = u.t; r.cnt = (uint32_t)(u.tr.size() / 3);
-  r.flags = SPICEY_R16_VALID | (u.recip ? SPICEY_R16_RECIP : 0u);
+  r.flags = SPICEY_R16_VALID | (u.recip ? SPICEY_R16_RECIP : 0u) | (u.fresh ? SPICEY_R16_FRESH : 0u);
   if (r.cnt <= 2) std::copy(u.tr.begin(), u.tr.end(), &r.ldu[0][0]);
   else {
     r.ovf = (uint32_t)ovf16.size();
@@ -1377,8 +1401,9 @@ void emit_factor(const FactorTask &u, std::vector<uint32_t> &dst, std::vector<ui
   r.pack(&dst[dst.size() - 4]);
 }
 
-// Factor level l as row records (program.h: fus16), where at least 64 rows fit the pattern
-void build_row_records(int n, const Factor &F, int l, const std::vector<FactorTask> &uts, HostProgram &hp) {
+// Factor level l as row records (program.h: fus16), where at least 64 rows fit the pattern.  first_fresh[entry]: this level
+// holds the first task on that fresh-fill entry (the row record that stands for the task carries the flag instead)
+void build_row_records(int n, const Factor &F, int l, const std::vector<FactorTask> &uts, const std::vector<char> &first_fresh, HostProgram &hp) {
   const Adj &upper = F.upper;
   const EntryIndex &E = F.E;
   const int nLU = F.nLU;
@@ -1420,11 +1445,15 @@ void build_row_records(int n, const Factor &F, int l, const std::vector<FactorTa
     const bool recip = hp.level[a] == l + 1 && !F.in_top[a];
     uint32_t meta = (uint32_t)reach[a].size() | ((SPICEY_R16_VALID | SPICEY_R16_FUSED | (recip ? SPICEY_R16_RECIP : 0u)) << 8);
     rr.a_ii() = (uint16_t)F.diag[a]; rr.y_i() = (uint16_t)(nLU + a);
+    if (first_fresh[F.diag[a]]) meta |= SPICEY_ROW_FRESH_AII;
     for (size_t i = 0; i < reach[a].size(); i++) {
       const int k = reach[a][i], o = other(k, a);
       uint16_t *q = rr.pivot(i);
       q[0] = (uint16_t)E.find(a, k); q[1] = (uint16_t)F.diag[k]; q[2] = (uint16_t)E.find(k, a); q[3] = (uint16_t)(nLU + k);
-      if (o >= 0) { q[4] = (uint16_t)E.find(k, o); q[5] = (uint16_t)E.find(a, o); meta |= 1u << (4 + i); }
+      if (o >= 0) {
+        q[4] = (uint16_t)E.find(k, o); q[5] = (uint16_t)E.find(a, o); meta |= 1u << (4 + i);
+        if (first_fresh[q[5]]) meta |= i == 0 ? SPICEY_ROW_FRESH_O0 : SPICEY_ROW_FRESH_O1;
+      }
     }
     rr.meta() = (uint16_t)meta;
     hp.fus16.resize(hp.fus16.size() + 8);
@@ -1480,16 +1509,21 @@ void build_records16(const Pattern &P, Factor &F, HostProgram &hp, bool slot_maj
   }
   if (hp.hdr.has16) {
     bool too_long = false;
+    std::vector<char> fresh_seen(nLU, 0), first_fresh(nLU, 0);
     for (int l = 0; l < nLevels; l++) {  // factor phases
       hp.ph_first.push_back((uint32_t)(hp.rec16.size() / 4));
       if (F.pcrL > 0 && l >= F.pcrL) { hp.ph_rhs.push_back(0u); hp.ph_cnt.push_back(0u); continue; }  // solved by cyclic reduction
-      const std::vector<FactorTask> uts = level_factor_tasks(F, hp, l, slot_major, too_long);
+      std::vector<FactorTask> uts = level_factor_tasks(F, hp, l, slot_major, too_long);
+      // the lowest phase that targets a fresh-fill entry creates it: flagged in both encodings of the phase
+      std::fill(first_fresh.begin(), first_fresh.end(), 0);
+      for (auto &u : uts)
+        if ((int)u.t < nLU && F.fresh[u.t] && !fresh_seen[u.t]) { u.fresh = true; first_fresh[u.t] = 1; fresh_seen[u.t] = 1; }
       uint32_t nrhs = 0;
       for (auto &u : uts) nrhs += (int)u.t >= nLU ? 1u : 0u;
       hp.ph_rhs.push_back(nrhs);
       for (auto &u : uts) emit_factor(u, hp.rec16, hp.ovf16);
       hp.ph_cnt.push_back((uint32_t)(hp.rec16.size() / 4) - hp.ph_first.back());
-      build_row_records(n, F, l, uts, hp);  // the same phase as row records
+      build_row_records(n, F, l, uts, first_fresh, hp);  // the same phase as row records
     }
     build_backward_records(F, hp, too_long);
     if (too_long || hp.ovf16.size() >= (size_t)1 << 31) {  // count field is 8 bits: such circuits use the 32-bit path
@@ -1691,7 +1725,8 @@ bool layout_hybrid(const Factor &F, HostProgram &hp) {
 // The driver: the stages in order, with the early returns between them.  hp is a fresh HostProgram (all three callers in
 // spicey_build_program pass one), so no stage clears what it is about to fill; only the front fall-back (build_fronts) and
 // the retreat from the 16-bit records (build_records16) undo earlier work.
-static int32_t build_program_impl(const SpiceyDesc *dp, HostProgram &hp, std::string &err, const bool slot_major, int front_cut, const bool pcr_top, const bool hybrid) {
+static int32_t build_program_impl(const SpiceyDesc *dp, HostProgram &hp, std::string &err, const bool slot_major, int front_cut, const bool pcr_top, const bool hybrid,
+                                  const bool fresh_fill) {
   const int32_t rc0 = spicey_check_desc(dp, err);
   if (rc0 != SPICEY_OK) return rc0;
   const SpiceyDesc &d = *dp;
@@ -1700,7 +1735,7 @@ static int32_t build_program_impl(const SpiceyDesc *dp, HostProgram &hp, std::st
   build_pattern(d, P, hp);                                   // 1
   match_rows(d, P, hp);                                      // 2a, 2b
   if (!order_pivots(P, hp)) { err = "internal: ordering lost vertices"; return SPICEY_ERR_BAD_DESC; }  // 3
-  symbolic_factor(d, P, slot_major, F, hp);                  // 4
+  symbolic_factor(d, P, slot_major, fresh_fill && !hybrid, F, hp);  // 4
   F.Lc = choose_front_cut(d, front_cut, P.n, F, hp);         // 4b
   build_fronts(P.n, F, hp);
   build_bins(P.n, F, hp);
@@ -1924,6 +1959,9 @@ void spicey_build_resident(const HostProgram &hp, int T, int rmax, HostResident 
       dsc[0] = 0u; dsc[1] = out.st_first[p]; dsc[2] = out.st_cnt[p]; dsc[3] = out.st_rhs[p];
     }
   }
+  // fresh-fill program: nKeep in the spare word of phase 0's descriptor — the phase table hands the descriptor rows on as
+  // they are, and phase B of the fresh build reads its bound from there (tran_exec.h); streamed or not, the row is there
+  if (hp.hdr.fresh_fill && nPh > 0) out.st_desc[7] = (uint32_t)hp.hdr.nKeep;
   out.pack();
 }
 

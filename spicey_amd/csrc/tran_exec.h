@@ -719,6 +719,17 @@ template <int N> struct U32Arr { uint32_t v[N]; uint32_t &operator[](int i) { re
 template <int N> struct U32Vec { typedef U32Arr<N> type; };  // (host build: a plain array; gcc's vector types want a power of two)
 #endif
 
+// What a (RMAX, NSV, NEL) build is, for the few places where the shapes differ in kind (launch_plan.h: SPICEY_V2_SHAPES):
+//   packed  the two-workgroups-per-CU builds — four slots, two elements per thread: 128 VGPRs and nothing to spare
+//   fresh   the packed build that runs FRESH-FILL programs (program.h: nKeep) — two re-stamped entries per thread, both with
+//           a dynamic-stamp descriptor.  Only this build decodes the fresh flags of the records and restores [0, nKeep) in
+//           B: every other build is compiled exactly as without the option and never sees such a program.
+template <int RMAX, int NSV, int NEL>
+struct SpiceyShapeKind {
+  static constexpr bool packed = RMAX == 4 && NEL == 2;
+  static constexpr bool fresh = packed && NSV == 2;
+};
+
 template <int K, int RMAX, int NSV, int NEL>
 struct ResRegs {
   // factor / backward task records, one 16-byte record per slot, word-major; the slots of a wave are sorted
@@ -727,7 +738,7 @@ struct ResRegs {
   typename U32Vec<(RMAX + 3) / 4>::type phv;
   int32_t cursor;
   // entries with dynamic stamps are numbered first: only the first NDD slots can hold one and need a descriptor
-  static constexpr int NDD = NSV == 6 ? 2 : NSV / 2;
+  static constexpr int NDD = SpiceyShapeKind<RMAX, NSV, NEL>::packed ? 2 : NSV / 2;
   double sv[NSV][K];    // static part of the entries this thread re-stamps (e = tid + j T)
   uint32_t dd[NDD];     // dynamic-stamp descriptors of the first NDD of them
   uint32_t rhs[NEL][2]; // right-hand-side descriptors of rows tid + j T
@@ -737,6 +748,10 @@ struct ResRegs {
   // fetched at the end of the last backward phase so that the L2 round trip (~1900 cycles measured) overlaps that
   // phase's barrier; live only from there to Z (K == 1 geometries)
   double pf[NEL][5];
+  // fresh build: this thread's first streamed record of factor phase 0 (a 32-byte row record), fetched under phase B —
+  // TranPhases2::u0_fetch writes all eight words on every path of B, spicey_uk_phase consumes them in phase 0 and clears
+  // them at the end of every factor phase, so they are live from B to U_0 only.  Untouched in every other build.
+  uint32_t u0[SpiceyShapeKind<RMAX, NSV, NEL>::fresh ? 8 : 1];
 };
 
 // One task.  For the common inline case (<= 2 products) ALL operands are fetched up front — unused index fields
@@ -748,7 +763,9 @@ struct ResRegs {
 // operand of a right-hand-side task is y_k, not an entry).
 // `ovf()` yields the overflow list (SpiceyProg::ovf16): asked for only by a task of more than two products, so that a phase
 // without one fetches nothing for it.
-template <int K, bool KTASK, bool OPG = false, class OV>
+// FRESH (fresh-fill builds): a factor task flagged SPICEY_R16_FRESH creates its target — it starts from 0.0 and does not
+// read it (the entry's static value IS 0.0, so the fma chain and its bits are those of the unflagged task).
+template <int K, bool KTASK, bool OPG = false, bool FRESH = false, class OV>
 SPICEY_HD void spicey_exec_rec16(const WgCtx<K> &c, OV ovf, uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3,
                                  uint32_t keep_from = 0u, uint32_t xoff = 0u) {
   const uint32_t meta = w0 >> 16;
@@ -795,12 +812,14 @@ SPICEY_HD void spicey_exec_rec16(const WgCtx<K> &c, OV ovf, uint32_t w0, uint32_
     // (hybrid: the third operand is an entry of the pivot's U row — global — for a matrix target, y_k — LDS — for a
     // right-hand-side target)
     const bool third_lds = !OPG || tgt >= xoff;
+    const bool keep_old = !FRESH || !(meta & (SPICEY_R16_FRESH << 8));
     if (cnt <= 2) {
       const uint32_t l0 = w1 & 0xffffu, d0 = w1 >> 16, u0 = w2 & 0xffffu, l1 = w2 >> 16, d1 = w3 & 0xffffu, u1 = w3 >> 16;
       const bool two = SPICEY_WAVE_ANY(cnt == 2);
       double p0[K], q0[K], r0[K], p1[K], q1[K], r1[K];
       for (int k = 0; k < K; k++) {
-        acc[k] = c.W[(size_t)tgt * K + k];
+        acc[k] = 0.0;
+        if (keep_old) acc[k] = c.W[(size_t)tgt * K + k];
         p0[k] = E[(size_t)l0 * K + k]; q0[k] = E[(size_t)d0 * K + k];
         r0[k] = (!OPG || third_lds) ? c.W[(size_t)u0 * K + k] : c.G[(size_t)u0 * K + k];
       }
@@ -818,7 +837,10 @@ SPICEY_HD void spicey_exec_rec16(const WgCtx<K> &c, OV ovf, uint32_t w0, uint32_
         }
       }
     } else {
-      for (int k = 0; k < K; k++) acc[k] = c.W[(size_t)tgt * K + k];
+      for (int k = 0; k < K; k++) {
+        acc[k] = 0.0;
+        if (keep_old) acc[k] = c.W[(size_t)tgt * K + k];
+      }
       const uint16_t *o = ovf() + w3;
       for (uint32_t j = 0; j < cnt; j++) {
         const uint32_t l = o[3 * j], d = o[3 * j + 1], u = o[3 * j + 2];
@@ -841,7 +863,8 @@ SPICEY_HD void spicey_exec_rec16(const WgCtx<K> &c, OV ovf, uint32_t w0, uint32_
 // One ROW record of a factor phase (program.h: fus16): the targets a_ii, y_i and the (at most two) fills of row i from its
 // (at most two) pivots of this level, sharing the multipliers -(L_ik d_k).  The products and their order are those of the
 // generic tasks it stands for.  rhs_only: a reused factorisation updates y_i alone.
-template <int K, bool OPG = false>
+// FRESH: a fill target flagged SPICEY_ROW_FRESH_* is created here — started from 0.0, not read.
+template <int K, bool OPG = false, bool FRESH = false>
 SPICEY_HD void spicey_exec_row16(const WgCtx<K> &c, const uint32_t *w, bool rhs_only) {
   const double *E = OPG ? c.G : c.W;  // (hybrid workspace: the pivots' own entries L_ik, d_k, U_ki, U_k,o come from the global array)
   const uint32_t meta = w[0] >> 16;
@@ -850,12 +873,19 @@ SPICEY_HD void spicey_exec_row16(const WgCtx<K> &c, const uint32_t *w, bool rhs_
   const uint32_t l0 = w[1] >> 16, d0 = w[2] & 0xffffu, u0 = w[2] >> 16, y0 = w[3] & 0xffffu, f0 = w[3] >> 16, t0 = w[4] & 0xffffu;
   const uint32_t l1 = w[4] >> 16, d1 = w[5] & 0xffffu, u1 = w[5] >> 16, y1 = w[6] & 0xffffu, f1 = w[6] >> 16, t1 = w[7] & 0xffffu;
   const bool two = (meta & 3u) == 2u, o0 = (meta >> 4) & 1u, o1 = (meta >> 5) & 1u;
+  const bool new_aii = FRESH && (meta & SPICEY_ROW_FRESH_AII), new_t0 = FRESH && (meta & SPICEY_ROW_FRESH_O0), new_t1 = FRESH && (meta & SPICEY_ROW_FRESH_O1);
   for (int k = 0; k < K; k++) {
     // every operand in one LDS round trip (an unused second pivot / fill: index 0, a valid address; results masked)
-    double aii = c.W[(size_t)iaa * K + k], yi = c.W[(size_t)iy * K + k];
+    double aii = 0.0;
+    if (!new_aii) aii = c.W[(size_t)iaa * K + k];
+    double yi = c.W[(size_t)iy * K + k];
     const double vl0 = E[(size_t)l0 * K + k], vd0 = E[(size_t)d0 * K + k], vy0 = c.W[(size_t)y0 * K + k], vu0 = E[(size_t)u0 * K + k];
     const double vl1 = E[(size_t)l1 * K + k], vd1 = E[(size_t)d1 * K + k], vy1 = c.W[(size_t)y1 * K + k], vu1 = E[(size_t)u1 * K + k];
-    const double vf0 = E[(size_t)f0 * K + k], vt0 = c.W[(size_t)t0 * K + k], vf1 = E[(size_t)f1 * K + k], vt1 = c.W[(size_t)t1 * K + k];
+    const double vf0 = E[(size_t)f0 * K + k];
+    double vt0 = 0.0, vt1 = 0.0;
+    if (!new_t0) vt0 = c.W[(size_t)t0 * K + k];
+    const double vf1 = E[(size_t)f1 * K + k];
+    if (!new_t1) vt1 = c.W[(size_t)t1 * K + k];
     const double m0 = -(vl0 * vd0), m1 = -(vl1 * vd1);
     yi = fma(m0, vy0, yi);
     aii = fma(m0, vu0, aii);
@@ -931,6 +961,7 @@ struct SpiceyPt {
 template <int K, int RMAX, int NSV, int NEL, bool KTASK, bool OPG = false>
 SPICEY_HD void spicey_uk_phase(const SpiceyProg &P, const SpiceyResident &Q, const SpiceyPt pt, const WgCtx<K> &c, ResRegs<K, RMAX, NSV, NEL> &rr, int tid,
                                int T, int p, bool streamed, bool reuse = false) {
+  constexpr bool FRESH = SpiceyShapeKind<RMAX, NSV, NEL>::fresh;
   auto ovf = [&]() -> const uint16_t * { return pt.on ? spicey_pt_ptr<const uint16_t>(pt.w, SPICEY_PT_OVF16) : spicey_fresh(P).ovf16; };
   uint32_t xoff = 0u;  // first LDS index of the right-hand side (= nLU without the hybrid layout)
   if (OPG || (!KTASK && reuse)) xoff = pt.on ? spicey_pt_u32(pt.w, SPICEY_PT_XOFF) : (uint32_t)spicey_fresh(P).xoff;
@@ -949,9 +980,9 @@ SPICEY_HD void spicey_uk_phase(const SpiceyProg &P, const SpiceyResident &Q, con
         if (!KTASK && s + 1 < RMAX && SPICEY_UNIFORM((int)((rr.phv[(s + 1) >> 2] >> (((s + 1) & 3) * 8)) & 0xffu)) == 0xFE) {  // a chunk of row records: this slot + its continuation
           uint32_t w[8] = {w0, w1, w2, w3, rr.w0[s + 1 < RMAX ? s + 1 : s], rr.w1[s + 1 < RMAX ? s + 1 : s], rr.w2[s + 1 < RMAX ? s + 1 : s], rr.w3[s + 1 < RMAX ? s + 1 : s]};
           SPICEY_OPAQUE(w[4]); SPICEY_OPAQUE(w[5]); SPICEY_OPAQUE(w[6]); SPICEY_OPAQUE(w[7]);
-          spicey_exec_row16<K, OPG>(c, w, reuse);
+          spicey_exec_row16<K, OPG, FRESH>(c, w, reuse);
         } else {
-          spicey_exec_rec16<K, KTASK, OPG>(c, ovf, w0, w1, w2, w3, keep_from, xoff);
+          spicey_exec_rec16<K, KTASK, OPG, FRESH>(c, ovf, w0, w1, w2, w3, keep_from, xoff);
         }
       }
     }
@@ -968,16 +999,19 @@ SPICEY_HD void spicey_uk_phase(const SpiceyProg &P, const SpiceyResident &Q, con
       if (!KTASK && q + 1 < RMAX && SPICEY_UNIFORM((int)((rr.phv[(q + 1) >> 2] >> (((q + 1) & 3) * 8)) & 0xffu)) == 0xFE) {  // a chunk of row records: this slot + its continuation
         uint32_t w[8] = {w0, w1, w2, w3, rr.w0[q + 1], rr.w1[q + 1], rr.w2[q + 1], rr.w3[q + 1]};
         SPICEY_OPAQUE(w[4]); SPICEY_OPAQUE(w[5]); SPICEY_OPAQUE(w[6]); SPICEY_OPAQUE(w[7]);
-        spicey_exec_row16<K, OPG>(c, w, reuse);
+        spicey_exec_row16<K, OPG, FRESH>(c, w, reuse);
         q += 2;
       } else {
-        spicey_exec_rec16<K, KTASK, OPG>(c, ovf, w0, w1, w2, w3, keep_from, xoff);
+        spicey_exec_rec16<K, KTASK, OPG, FRESH>(c, ovf, w0, w1, w2, w3, keep_from, xoff);
         q++;
       }
     }
     rr.cursor = q;
   }
-  if (!streamed) return;
+  if (!streamed) {
+    if (FRESH && !KTASK) for (int i = 0; i < 8; i++) rr.u0[FRESH ? i : 0] = 0u;
+    return;
+  }
   // one 32-byte descriptor says where the phase's records are (SpiceyResident::st_desc): from the phase table in LDS — one
   // round trip between the phase head and the first record fetch — or through the argument structs (three)
   uint32_t d_rows, d_first, d_cnt, d_rhs, d_rfirst, d_rcnt, d_rrhs;
@@ -1019,8 +1053,11 @@ SPICEY_HD void spicey_uk_phase(const SpiceyProg &P, const SpiceyResident &Q, con
     SPICEY_NOUNROLL
     for (uint32_t j = (uint32_t)tid; j < npair; j += (uint32_t)T) {
       uint32_t w[8];
-      for (int i = 0; i < 8; i++) w[i] = pb[(size_t)j * 8 + i];
-      spicey_exec_row16<K, OPG>(c, w, reuse);
+      // (fresh build, phase 0: record `tid` has been in flight since phase B — TranPhases2::u0_fetch, same address — a
+      // run-time test, not a second copy of the phase body: profiles/NOTES_r05.md §6)
+      if (FRESH && p == 0 && j == (uint32_t)tid) for (int i = 0; i < 8; i++) w[i] = rr.u0[FRESH ? i : 0];
+      else for (int i = 0; i < 8; i++) w[i] = pb[(size_t)j * 8 + i];
+      spicey_exec_row16<K, OPG, FRESH>(c, w, reuse);
     }
     base = fus16 + (size_t)d_rfirst * 4;
     sc = reuse ? d_rrhs : d_rcnt;
@@ -1038,13 +1075,14 @@ SPICEY_HD void spicey_uk_phase(const SpiceyProg &P, const SpiceyResident &Q, con
         const bool more = jn < sc;
         const uint32_t *rn = base + (size_t)(more ? jn : j) * 4;
         const uint32_t n0 = rn[0], n1 = rn[1], n2 = rn[2], n3 = rn[3];
-        spicey_exec_rec16<K, KTASK, OPG>(c, ovf, c0, c1, c2, c3, keep_from, xoff);
+        spicey_exec_rec16<K, KTASK, OPG, FRESH>(c, ovf, c0, c1, c2, c3, keep_from, xoff);
         if (!more) break;
         c0 = n0; c1 = n1; c2 = n2; c3 = n3;
         j = jn;
       }
     }
   }
+  if (FRESH && !KTASK) for (int i = 0; i < 8; i++) rr.u0[FRESH ? i : 0] = 0u;  // (consumed, or not for this phase: dead until the next B)
 }
 
 // v2 versions of the B and Z phases: everything step-invariant that a thread needs (static entry values,
@@ -1080,6 +1118,10 @@ struct TranPhases2 {
   // from there inside their own branch (SPICEY_COLD_ARGS).  Null: P and R are complete.
   const SpiceyProg *Pg = nullptr;
   const SpiceyRun *Rg = nullptr;
+  // fresh build, for u0_fetch: the phase table (null: none — then Qg, the resident struct where it lives, says where phase
+  // 0's records are)
+  const uint32_t *ptab = nullptr;
+  const SpiceyResident *Qg = nullptr;
 #if defined(__HIP_DEVICE_COMPILE__)
 #define SPICEY_COLD_STRUCT(whole, here) ((whole) ? spicey_fresh(*(whole)) : (here))
 #else
@@ -1094,12 +1136,16 @@ struct TranPhases2 {
   // the diagnostics of SpiceyOptions.diagnostics are compiled into every geometry but the two-workgroups-per-CU one (NSV = 6:
   // 128 VGPRs and nothing to spare — with them that kernel spills, which the build refuses); the host keeps a handle with
   // the option out of that geometry
-  static constexpr bool DIAG = NSV != 6 && !HYB;  // (nor into the hybrid-workspace build, for the same reason)
+  static constexpr bool DIAG = !SpiceyShapeKind<RMAX, NSV, NEL>::packed && !HYB;  // (nor into the hybrid-workspace build, for the same reason)
+  // fresh-fill build: B, and the copy that fills the registers it restores from, stop at the kept targets — the fresh class
+  // [nKeep, nRestore) is created by its flagged factor tasks in every solve and nothing reads it before them
+  static constexpr bool FRESH = SpiceyShapeKind<RMAX, NSV, NEL>::fresh;
+  SPICEY_HD int n_stamped() const { return FRESH ? P.nKeep : P.nRestore; }
   // hybrid builds: items of a beyond-resident loop whose loads are in flight together (the 1024-thread build has 128 registers)
   static constexpr int BW = NEL >= 2 ? 4 : 2;   // (phase Z)
   static constexpr int BWB = BW;                 // (phase B; four at a time in the 1024-thread build compiled — 126 registers — and was 5 % slower per step)
   SPICEY_HD void set_remainders() {
-    brem = (P.nRestore > NSV * T ? 1u : 0u) | (P.nDynX > 0 ? 2u : 0u) | (P.n > NEL * T ? 4u : 0u) | (P.nRowX > 0 ? 8u : 0u) |
+    brem = (n_stamped() > NSV * T ? 1u : 0u) | (P.nDynX > 0 ? 2u : 0u) | (P.n > NEL * T ? 4u : 0u) | (P.nRowX > 0 ? 8u : 0u) |
            (P.nDynEnt > Regs::NDD * T ? 16u : 0u);
     zrem = (P.nOut > NEL * T ? 1u : 0u) | (P.nR > NEL * T ? 2u : 0u) | (P.nC > NEL * T ? 4u : 0u) | (P.nL > 0 ? 8u : 0u) |
            (P.nV > T ? 16u : 0u) | (P.nS > 0 ? 32u : 0u) | (P.nD > NEL * T ? 64u : 0u);
@@ -1147,8 +1193,8 @@ struct TranPhases2 {
     const int oL = P.nC, oV = P.nC + P.nL, oD = P.nC + P.nL + P.nV;
     for (int j = 0; j < NSV; j++) {
       const int e = tid + j * T;
-      if (j < Regs::NDD) rr.dd[j] = e < P.nRestore ? P.ent_dd[e] : 0x80000000u;  // bit 31 = "not mine to stamp"
-      for (int k = 0; k < K; k++) rr.sv[j][k] = e < P.nRestore ? R.statv[(size_t)c.inst[k] * P.nLU + e] : 0.0;
+      if (j < Regs::NDD) rr.dd[j] = e < n_stamped() ? P.ent_dd[e] : 0x80000000u;  // bit 31 = "not mine to stamp"
+      for (int k = 0; k < K; k++) rr.sv[j][k] = e < n_stamped() ? R.statv[(size_t)c.inst[k] * P.nLU + e] : 0.0;
     }
     for (int k = 0; k < K; k++) {  // entries that no phase ever writes: stamped once per run
       const double *sv = R.statv + (size_t)c.inst[k] * P.nLU;
@@ -1232,8 +1278,32 @@ struct TranPhases2 {
   }
   // the whole of phase B: the next step's source values ride on it (a long phase with few live registers): fetched first,
   // parked in LDS last; Z moves them into place
+  // Fresh build: factor phase 0 is the one phase of the packed chains that is still streamed, and the fetch of its first
+  // record used to be an exposed L2 round trip at its head.  The record (row record `tid` of the phase: 32 bytes) is
+  // loaded here instead, next to the source fetch, and has the whole of B to arrive.  Lanes without a record, and a phase
+  // 0 that is resident or streams generic records, fetch nothing.
+  SPICEY_HD void u0_fetch(int tid, Regs &rr) const {
+    uint32_t rows, first, cnt;
+    const uint32_t *fus16;
+    if (ptab) {
+      const SpiceyPtLanes d = SpiceyPtLanes::row(ptab, tid, 0);  // (row 0 = factor phase 0; the whole wave is here)
+      rows = d.u32(0); first = d.u32(1); cnt = d.u32(2);
+      fus16 = d.template ptr<const uint32_t>(SPICEY_PT_FUS16);
+    } else {
+      const uint32_t *dsc = spicey_fresh(*Qg).st_desc;
+      rows = dsc[0]; first = dsc[1]; cnt = dsc[2];
+      fus16 = P.fus16;
+    }
+    const bool have = rows != 0u && (uint32_t)tid < cnt;
+    for (int i = 0; i < 8; i++) rr.u0[FRESH ? i : 0] = 0u;
+    if (have) {
+      const uint32_t *src = fus16 + (size_t)first * 4 + (size_t)tid * 8;
+      for (int i = 0; i < 8; i++) rr.u0[FRESH ? i : 0] = src[i];
+    }
+  }
   SPICEY_HD void b_phase(int tid, int64_t step, Regs &rr, bool reuse) const {
     double sn = K == 1 ? z_src_fetch(tid, step, (size_t)c.inst[0]) : 0.0;
+    if (FRESH) u0_fetch(tid, rr);
     SPICEY_SCHED_FENCE;
     b_stamp(tid, rr, reuse);
     SPICEY_SCHED_FENCE;
@@ -1391,7 +1461,7 @@ struct TranPhases2 {
     }
     for (int j = Regs::NDD; j < NSV; j++) {  // plain restores (a dynamic entry this far up is left to the loop below)
       const int e = tid + j * T;
-      if (e >= P.nDynEnt && e < P.nRestore)
+      if (e >= P.nDynEnt && e < n_stamped())
         for (int k = 0; k < K; k++) put_entry((uint32_t)e, k, rr.sv[j][k]);
     }
     SPICEY_MARK(c, 8);
@@ -1408,7 +1478,7 @@ struct TranPhases2 {
     }
     if (brem & 1u)
     SPICEY_NOUNROLL
-    for (int e = tid + NSV * T; e < P.nRestore; e += T) {  // entries beyond the resident capacity
+    for (int e = tid + NSV * T, ne = n_stamped(); e < ne; e += T) {  // entries beyond the resident capacity
       if (e < P.nDynEnt) continue;  // done above
       const uint32_t dd = P.ent_dd[e];
       if (dd >> 31) continue;
@@ -2031,12 +2101,15 @@ SPICEY_HD void spicey_tran_run_v2(Exec &ex, const SpiceyProg &P, const SpiceyRes
           SpiceyProg Pt{};
           SpiceyRun Rt{};
           spicey_pt_args(ptw, tid, Pt, Rt);
-          Ph2 p2{Pt, Rt, c, T, brem, zrem, &P, &R};
+          // (fresh build: nKeep rides in the spare word of phase 0's row — spicey_build_resident — so that the run-wide block,
+          // and with it every other build, is what it was)
+          if (Ph2::FRESH) Pt.nKeep = (int32_t)SpiceyPtLanes::row(ptw, tid, 0).u32(7);
+          Ph2 p2{Pt, Rt, c, T, brem, zrem, &P, &R, ptw, nullptr};
           p2.b_phase(tid, step, ex.template regs<Regs>(tid), linear && step > 0);
         } else {
           const SpiceyProg Pf = ex.fresh(P);
           const SpiceyRun Rf = ex.fresh(R);
-          Ph2 p2{Pf, Rf, c, T, brem, zrem};
+          Ph2 p2{Pf, Rf, c, T, brem, zrem, nullptr, nullptr, nullptr, &Q};
           p2.b_phase(tid, step, ex.template regs<Regs>(tid), linear && step > 0);
         }
       });
@@ -2094,7 +2167,7 @@ SPICEY_HD void spicey_tran_run_v2(Exec &ex, const SpiceyProg &P, const SpiceyRes
                       },
                       [&](int, int lvl, const uint32_t *r) {
                         auto ovf = [&]() -> const uint16_t * { return spicey_fresh(P).ovf16; };
-                        if (u_end + lvl < nL) spicey_exec_rec16<K, false>(c, ovf, r[0], r[1], r[2], r[3], (linear && step > 0) ? (uint32_t)spicey_fresh(P).xoff : 0u);
+                        if (u_end + lvl < nL) spicey_exec_rec16<K, false, false, SpiceyShapeKind<RMAX, NSV, NEL>::fresh>(c, ovf, r[0], r[1], r[2], r[3], (linear && step > 0) ? (uint32_t)spicey_fresh(P).xoff : 0u);
                         else spicey_exec_rec16<K, true>(c, ovf, r[0], r[1], r[2], r[3]);
                       });
       }

@@ -1,0 +1,72 @@
+"""ctypes view of the CPU harness of the fresh-fill programs (tests/fresh_host/harness.cpp)."""
+import ctypes as C
+import fcntl
+import os
+import subprocess
+
+import numpy as np
+
+from spicey_amd import abi
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+_LIB = None
+
+CHECK_FIELDS = ("nKeep", "nRestore", "nLU", "fresh_entries", "stamped_in_class", "not_one_flag", "flag_not_in_first_phase",
+                "read_before_created", "flag_outside_class", "encodings_differ", "has16", "untargeted_but_touched")
+PLAN_FIELDS = ("fresh", "packed", "threads", "nKeep", "nRestore", "nDynEnt", "program_fresh_fill", "shape")
+RUN_FIELDS = ("nKeep", "nRestore", "streamed_tasks", "resident_tasks", "nDynEnt", "fresh_fill")
+
+
+def lib():
+    global _LIB
+    if _LIB is None:
+        os.makedirs(os.path.join(HERE, "_build"), exist_ok=True)
+        with open(os.path.join(HERE, "_build", ".lock"), "w") as lk:
+            fcntl.flock(lk, fcntl.LOCK_EX)
+            subprocess.run(["make", "-s", "-C", HERE], check=True, stderr=subprocess.DEVNULL)
+        L = C.CDLL(os.path.join(HERE, "_build", "libspicey_fresh_host.so"))
+        i64p = C.POINTER(C.c_int64)
+        L.spicey_fresh_check.restype = C.c_int32
+        L.spicey_fresh_check.argtypes = [C.POINTER(abi.SpiceyDesc), C.c_int32, C.c_int32, i64p]
+        L.spicey_fresh_run.restype = C.c_int32
+        L.spicey_fresh_run.argtypes = [C.POINTER(abi.SpiceyDesc), C.c_int32, C.c_int32, C.c_int64, C.c_double] + [C.c_void_p] * 8 + [C.c_int32, i64p]
+        L.spicey_fresh_plan.restype = C.c_int32
+        L.spicey_fresh_plan.argtypes = [C.POINTER(abi.SpiceyDesc), C.POINTER(abi.SpiceyOptions), C.c_int32, C.POINTER(abi.SpiceyInfo), i64p]
+        _LIB = L
+    return _LIB
+
+
+def check(flat: abi.FlatCircuit, pcr_top: bool = True, fresh: bool = True) -> dict:
+    """The builder's invariants on the program of `flat` (harness.cpp: spicey_fresh_check)."""
+    out = np.zeros(12, np.int64)
+    d = flat.desc()
+    rc = lib().spicey_fresh_check(C.byref(d), int(pcr_top), int(fresh), out.ctypes.data_as(C.POINTER(C.c_int64)))
+    return {"rc": rc, **dict(zip(CHECK_FIELDS, (int(x) for x in out)))}
+
+
+def run(flat: abi.FlatCircuit, steps: int, dt: float, src, fresh: bool, T: int = 512, reverse: bool = False, nan_fill: bool = False) -> dict:
+    """One emulated run at the packed layout (T threads, 4 slots) of the default or the fresh-fill program."""
+    ni = flat.n_inst
+    src = np.ascontiguousarray(src, dtype=np.float64)
+    out_v = np.zeros((ni, steps + 1, flat.n_out))
+    out_i = np.zeros((ni, steps + 1, flat.n_cur))
+    iters = np.zeros((ni, steps + 1), np.int32)
+    st = {"C_vprev": flat.C_vprev.copy(), "L_iprev": flat.L_iprev.copy(), "D_vdprev": flat.D_vdprev.copy(), "S_ison": flat.S_ison.copy()}
+    info = np.zeros(6, np.int64)
+    d = flat.desc()
+    rc = lib().spicey_fresh_run(C.byref(d), int(fresh), T, steps, dt, src.ctypes.data, out_v.ctypes.data, out_i.ctypes.data, iters.ctypes.data,
+                                st["C_vprev"].ctypes.data, st["L_iprev"].ctypes.data, st["D_vdprev"].ctypes.data, st["S_ison"].ctypes.data,
+                                (1 if reverse else 0) | (2 if nan_fill else 0), info.ctypes.data_as(C.POINTER(C.c_int64)))
+    return {"status": rc, "out_v": out_v, "out_i": out_i, "iters": iters, "state": st, **dict(zip(RUN_FIELDS, (int(x) for x in info)))}
+
+
+def plan(flat: abi.FlatCircuit, ncu: int = 256, **options) -> dict:
+    """spicey_create's plan for `flat` on a device of `ncu` CUs (environment knobs as in spicey_create)."""
+    opt = abi.SpiceyOptions()
+    for k, v in options.items():
+        setattr(opt, k, v)
+    info = abi.SpiceyInfo()
+    out = np.zeros(8, np.int64)
+    d = flat.desc()
+    rc = lib().spicey_fresh_plan(C.byref(d), C.byref(opt), ncu, C.byref(info), out.ctypes.data_as(C.POINTER(C.c_int64)))
+    return {"rc": rc, "info": info.as_dict(), **dict(zip(PLAN_FIELDS, (int(x) for x in out)))}
