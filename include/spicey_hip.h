@@ -356,6 +356,56 @@ int32_t spicey_run_measure(SpiceyHandle *h, int64_t steps, double dt, const doub
 /* Duration in ms of the last spicey_run_measure's reduction (both of its kernels), measured with HIP events. */
 double spicey_last_measure_ms(SpiceyHandle *h);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Harmonics of a transient's waveforms on the device (what SPICE users know as .four): a third reduction pass over the
+ * same step-major buffers.  One request = one signal (signal, col, col_ref exactly as in SpiceyMeasReq), a fundamental
+ * f0 in Hz, a harmonic count n_harm and a window of steps: the N = step_to - step_from samples step_from .. step_to - 1
+ * enter the sums — the sample at step_to closes the last period and is left out (the rectangular rule, exact for a
+ * waveform that is periodic in the window); step_to = -1: n_points - 1.
+ * Results, 1 + 2 n_harm doubles per (instance, request) at the head of a row of out_stride doubles, the rest of the row 0:
+ *   {C0, C1, S1, ..., CH, SH}   C0 = sum x_s,  C_h = sum x_s c(h, s),  S_h = sum x_s s(h, s)
+ * over the ABSOLUTE step s (phases refer to t = 0, not to the window), with the twiddles
+ *   r = (double)(h s) (f0 dt), the integer product in 64 bits;  r = r - floor(r);  a = 2 pi r;  c = cos(a), s = sin(a)
+ * evaluated by the HOST's libm: the device reads a table the host built, one per basis (f0, step_from, step_to), uploaded
+ * into the head of the workspace.  So a_h = 2 C_h / N, b_h = 2 S_h / N give the harmonic M cos(2 pi h f0 t + phi) with
+ * M = hypot(a_h, b_h), phi = atan2(-b_h, a_h), and C0 / N is the mean.  A window that is no whole number of periods leaks;
+ * that is the caller's business and not refused.
+ * Every row is a function of the window's samples, dt and the request only (the summation order is that of the
+ * measurements above: chunks of 256 steps counted from step_from, sequential inside a chunk with sums that start at 0.0,
+ * chunk partials added in ascending order; every product and sum rounded on its own, no FMA contraction): it does not
+ * depend on n_inst, on the other requests of the list or of its basis, or on the launch. */
+#define SPICEY_FOUR_MAX_HARM 16
+typedef struct SpiceyFourReq {
+  int32_t signal, col, col_ref, n_harm; /* n_harm in 1..SPICEY_FOUR_MAX_HARM */
+  int64_t step_from, step_to;           /* samples step_from .. step_to-1 are summed; step_to = -1: n_points-1 */
+  double f0;                            /* Hz, > 0 and finite */
+} SpiceyFourReq;
+
+/* Bytes of device workspace spicey_fourier_device needs for this request list (request table, bases, twiddles, chunk
+ * partials); -1 for a list whose windows, harmonic counts or fundamentals no launch accepts, and for counts <= 0. */
+int64_t spicey_fourier_workspace_bytes(int32_t n_inst, int64_t n_points, const SpiceyFourReq *reqs, int32_t n_req);
+/* The reduction alone, on any DEVICE buffers d_v [n_inst][n_points][n_v] and d_i [n_inst][n_points][n_i] (or NULL):
+ * needs no handle.  reqs is a HOST array; d_out [n_inst][n_req][out_stride] and d_work (work_bytes >=
+ * spicey_fourier_workspace_bytes) are DEVICE buffers.  Enqueued on `stream` (a hipStream_t, NULL = default stream)
+ * without synchronising.  SPICEY_ERR_BAD_DESC, with a text containing "fourier" in spicey_last_error(NULL), nothing
+ * launched and the buffers untouched, for: an unknown signal; a column out of range; signal = 1 with d_i == NULL;
+ * step_from < 0, step_to beyond the run or step_from >= step_to; n_harm outside 1..16; f0 or dt not finite or <= 0;
+ * n_harm f0 dt > 0.5 (above Nyquist); out_stride < 1 + 2 max n_harm; a workspace that is too small; n_req <= 0; null
+ * buffers. */
+int32_t spicey_fourier_device(int32_t device, int32_t n_inst, int64_t n_points, double dt, const double *d_v, int32_t n_v,
+                              const double *d_i, int32_t n_i, const SpiceyFourReq *reqs, int32_t n_req, double *d_out,
+                              int32_t out_stride, void *d_work, int64_t work_bytes, void *stream);
+/* spicey_run_measure with the harmonics pass on the same stream behind the measurements: one transient run, currents
+ * recorded only if a request of either list has signal = 1, both reductions over the same device waveforms; only meas
+ * [n_inst][n_req][8] (n_req may be 0: meas may then be NULL and no measurement pass runs), four
+ * [n_inst][n_four][four_stride] (n_four >= 1) and iters (or NULL) come back.  Everything else — SPICEY_ERR_SINGULAR, the
+ * repeated launch of group_retry, the queries afterwards — is as for spicey_run_measure. */
+int32_t spicey_run_measure_fourier(SpiceyHandle *h, int64_t steps, double dt, const double *src_table, int32_t src_per_inst,
+                                   const SpiceyMeasReq *reqs, int32_t n_req, double *meas, const SpiceyFourReq *freqs,
+                                   int32_t n_four, double *four, int32_t four_stride, int32_t *iters);
+/* Duration in ms of the last spicey_run_measure_fourier's harmonics pass (both of its kernels), measured with HIP events. */
+double spicey_last_fourier_ms(SpiceyHandle *h);
+
 /* Library build info: "spicey_hip <abi> gfx950 …" */
 const char *spicey_version(void);
 

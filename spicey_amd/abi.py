@@ -67,6 +67,18 @@ assert MEAS_REQ_DTYPE.itemsize == C.sizeof(SpiceyMeasReq) == 48
 MEAS_STATS, MEAS_CROSS = 0, 1
 
 
+class SpiceyFourReq(C.Structure):
+    _fields_ = [("signal", C.c_int32), ("col", C.c_int32), ("col_ref", C.c_int32), ("n_harm", C.c_int32),
+                ("step_from", C.c_int64), ("step_to", C.c_int64), ("f0", C.c_double)]
+
+
+# a harmonics request list (spicey_fourier_device) is one array of these
+FOUR_REQ_DTYPE = np.dtype([("signal", "<i4"), ("col", "<i4"), ("col_ref", "<i4"), ("n_harm", "<i4"), ("step_from", "<i8"), ("step_to", "<i8"),
+                           ("f0", "<f8")])
+assert FOUR_REQ_DTYPE.itemsize == C.sizeof(SpiceyFourReq) == 40
+FOUR_MAX_HARM = 16
+
+
 class SpiceyAcMeasReq(C.Structure):
     _fields_ = [("num_signal", C.c_int32), ("num_col", C.c_int32), ("num_col_ref", C.c_int32),
                 ("den_signal", C.c_int32), ("den_col", C.c_int32), ("den_col_ref", C.c_int32), ("what", C.c_int32), ("kind", C.c_int32),

@@ -21,6 +21,8 @@
 #include "launch_plan.h"
 #include "ac_measure.h"
 #include "ac_measure_exec.h"
+#include "fourier.h"
+#include "fourier_exec.h"
 #include "measure.h"
 #include "measure_exec.h"
 #include "symbolic.h"
@@ -91,7 +93,7 @@ struct SpiceyHandle {
   DevBuf<double> d_gstat, d_statv, d_rcoef, d_gW, d_dpar;
   DevBuf<int32_t> d_status; DevBuf<unsigned long long> d_solves, d_prof;
   hipStream_t last_stream = nullptr;
-  double last_measure_ms = 0.0;
+  double last_measure_ms = 0.0, last_fourier_ms = 0.0;
   bool pending = false;
   int64_t last_solves = 0;
   double last_ms = 0.0;
@@ -750,58 +752,118 @@ extern "C" int32_t spicey_measure_device(int32_t device, int32_t n_inst, int64_t
   return SPICEY_OK;
 }
 
-extern "C" int32_t spicey_run_measure(SpiceyHandle *h, int64_t steps, double dt, const double *src_table, int32_t src_per_inst, const SpiceyMeasReq *reqs,
-                                      int32_t n_req, double *meas, int32_t *iters) {
+// What spicey_run_measure and spicey_run_measure_fourier share: one transient run into device buffers of this call's own,
+// the reductions on the handle's stream behind it, and only their results and `iters` on the way back.  four_pass: the
+// second entry point (the measurement list may then be empty; the harmonics list may not).
+static int32_t run_reduced(SpiceyHandle *h, int64_t steps, double dt, const double *src_table, int32_t src_per_inst, const SpiceyMeasReq *reqs, int32_t n_req,
+                           double *meas, bool four_pass, const SpiceyFourReq *freqs, int32_t n_four, double *four, int32_t four_stride, int32_t *iters) {
   if (!h) return SPICEY_ERR_BAD_DESC;
-  if (const int32_t rc0 = check_run_args(h, steps, meas, src_table, src_per_inst); rc0 != SPICEY_OK) return rc0;
+  if (const int32_t rc0 = check_run_args(h, steps, four_pass ? (const void *)four : (const void *)meas, src_table, src_per_inst); rc0 != SPICEY_OK) return rc0;
+  const bool meas_pass = !four_pass || n_req != 0;
+  if (four_pass && (n_req < 0 || (n_req > 0 && !meas))) { h->err = "fourier: n_req must be >= 0, and meas not null when n_req > 0"; return SPICEY_ERR_BAD_DESC; }
   const SpiceyProg &P = h->hp.hdr;
   const int32_t ni = h->plan.n_inst;
   const int64_t np = steps + 1;
   // (a refused request list runs nothing; the buffers are this call's own)
-  const int64_t work_bytes = spicey_meas_workspace_bytes(ni, np, n_req);
+  const int64_t work_bytes = meas_pass ? spicey_meas_workspace_bytes(ni, np, n_req) : 0;
   std::vector<SpiceyMeasDevReq> table;
-  if (const int32_t rc0 = spicey_judge_measure("measure", spicey_meas_plan, spicey_meas_workspace_bytes, ni, np, true, P.nOut, true, P.nCur, reqs, n_req, true,
-                                               work_bytes, table, h->err); rc0 != SPICEY_OK)
-    return rc0;
+  if (meas_pass)
+    if (const int32_t rc0 = spicey_judge_measure("measure", spicey_meas_plan, spicey_meas_workspace_bytes, ni, np, true, P.nOut, true, P.nCur, reqs, n_req, true,
+                                                 work_bytes, table, h->err); rc0 != SPICEY_OK)
+      return rc0;
+  SpiceyFourPlan fplan;
+  if (four_pass && !spicey_four_judge(ni, np, dt, true, P.nOut, true, P.nCur, freqs, n_four, true, four_stride, INT64_MAX, fplan, h->err)) return SPICEY_ERR_BAD_DESC;
   bool need_i = false;
   for (const SpiceyMeasDevReq &q : table) need_i = need_i || q.signal == 1;
+  for (const SpiceyFourDevReq &q : fplan.table) need_i = need_i || q.signal == 1;
   if (const int32_t rc0 = check_structure(h); rc0 != SPICEY_OK) return rc0;
   HIPCHK(h, hipSetDevice(h->device));
-  Roctx range_run("spicey_run_measure");
+  Roctx range_run(four_pass ? "spicey_run_measure_fourier" : "spicey_run_measure");
   HIPCHK(h, h->q.want_measure_events());
+  if (four_pass) HIPCHK(h, h->q.want_fourier_events());
   HostRun r;
-  DevBuf<double> d_meas;
-  DevBuf<uint8_t> d_work;
+  DevBuf<double> d_meas, d_four;
+  DevBuf<uint8_t> d_work, d_fwork;
   // (no current request: the run records no currents)
   if (const int32_t rc0 = r.stage(h, steps, src_table, src_per_inst, need_i, iters != nullptr); rc0 != SPICEY_OK) return rc0;
-  HIPCHK(h, d_meas.alloc((size_t)ni * (size_t)n_req * 8));
-  HIPCHK(h, d_work.alloc((size_t)work_bytes));
+  if (meas_pass) {
+    HIPCHK(h, d_meas.alloc((size_t)ni * (size_t)n_req * 8));
+    HIPCHK(h, d_work.alloc((size_t)work_bytes));
+  }
+  if (four_pass) {
+    HIPCHK(h, d_four.alloc((size_t)ni * (size_t)n_four * (size_t)four_stride));
+    HIPCHK(h, d_fwork.alloc((size_t)fplan.workspace_bytes(ni)));
+  }
   h->last_measure_ms = 0.0;
+  h->last_fourier_ms = 0.0;
   hipStream_t st = h->q.stream;
   int32_t rc = spicey_run_device_src(h, steps, dt, r.d_src, src_per_inst, r.d_v, r.d_i, r.d_it, st);
   if (rc != SPICEY_OK) return rc;
+  const char *failed = "spicey_launch_measure: ";
   auto reduce = [&]() {
-    hipError_t e = hipEventRecord(h->q.mev0, st);
-    if (e == hipSuccess) e = spicey_launch_measure(h->device, ni, np, dt, r.d_v, P.nOut, r.d_i, P.nCur, table.data(), n_req, d_meas, d_work, st);
-    if (e == hipSuccess) e = hipEventRecord(h->q.mev1, st);
+    hipError_t e = hipSuccess;
+    if (meas_pass) {
+      e = hipEventRecord(h->q.mev0, st);
+      if (e == hipSuccess) e = spicey_launch_measure(h->device, ni, np, dt, r.d_v, P.nOut, r.d_i, P.nCur, table.data(), n_req, d_meas, d_work, st);
+      if (e == hipSuccess) e = hipEventRecord(h->q.mev1, st);
+    }
+    if (four_pass && e == hipSuccess) {
+      failed = "spicey_launch_fourier: ";
+      e = hipEventRecord(h->q.fev0, st);
+      if (e == hipSuccess) e = spicey_launch_fourier(h->device, ni, np, dt, r.d_v, P.nOut, r.d_i, P.nCur, fplan, d_four, four_stride, d_fwork, st);
+      if (e == hipSuccess) e = hipEventRecord(h->q.fev1, st);
+    }
     return e;
   };
   const int retries = h->group_retries;
   hipError_t e = reduce();
-  rc = spicey_sync(h);  // (the stream's end: the transient's status, with the reduction behind it; also before the buffers go)
-  // (group mode with group_retry: spicey_sync repeated the transient behind the reduction, so the reduction runs again)
+  rc = spicey_sync(h);  // (the stream's end: the transient's status, with the reductions behind it; also before the buffers go)
+  // (group mode with group_retry: spicey_sync repeated the transient behind the reductions, so the reductions run again)
   if (e == hipSuccess && h->group_retries != retries && rc == SPICEY_OK && (e = reduce()) == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) { h->err = std::string("spicey_launch_measure: ") + hipGetErrorString(e); return SPICEY_ERR_HIP; }
+  if (e != hipSuccess) { h->err = std::string(failed) + hipGetErrorString(e); return SPICEY_ERR_HIP; }
   if (rc == SPICEY_OK || rc == SPICEY_ERR_SINGULAR) {
-    StreamTimers::elapsed(h->q.mev0, h->q.mev1, &h->last_measure_ms);
+    if (meas_pass) StreamTimers::elapsed(h->q.mev0, h->q.mev1, &h->last_measure_ms);
+    if (four_pass) StreamTimers::elapsed(h->q.fev0, h->q.fev1, &h->last_fourier_ms);
     Roctx range_copy("spicey_run_measure:results");
-    HIPCHK(h, hipMemcpy(meas, d_meas, (size_t)ni * (size_t)n_req * 8 * sizeof(double), hipMemcpyDeviceToHost));
+    if (meas_pass) HIPCHK(h, hipMemcpy(meas, d_meas, (size_t)ni * (size_t)n_req * 8 * sizeof(double), hipMemcpyDeviceToHost));
+    if (four_pass) HIPCHK(h, hipMemcpy(four, d_four, (size_t)ni * (size_t)n_four * (size_t)four_stride * sizeof(double), hipMemcpyDeviceToHost));
     if (const int32_t rc0 = r.copy_out(h, nullptr, nullptr, iters); rc0 != SPICEY_OK) return rc0;
   }
   return rc;
 }
 
+extern "C" int32_t spicey_run_measure(SpiceyHandle *h, int64_t steps, double dt, const double *src_table, int32_t src_per_inst, const SpiceyMeasReq *reqs,
+                                      int32_t n_req, double *meas, int32_t *iters) {
+  return run_reduced(h, steps, dt, src_table, src_per_inst, reqs, n_req, meas, false, nullptr, 0, nullptr, 0, iters);
+}
+
+extern "C" int32_t spicey_run_measure_fourier(SpiceyHandle *h, int64_t steps, double dt, const double *src_table, int32_t src_per_inst, const SpiceyMeasReq *reqs,
+                                              int32_t n_req, double *meas, const SpiceyFourReq *freqs, int32_t n_four, double *four, int32_t four_stride,
+                                              int32_t *iters) {
+  return run_reduced(h, steps, dt, src_table, src_per_inst, reqs, n_req, meas, true, freqs, n_four, four, four_stride, iters);
+}
+
 extern "C" double spicey_last_measure_ms(SpiceyHandle *h) { return h ? h->last_measure_ms : 0.0; }
+extern "C" double spicey_last_fourier_ms(SpiceyHandle *h) { return h ? h->last_fourier_ms : 0.0; }
+
+// Harmonics (include/spicey_hip.h): the reduction of fourier.hip on any device buffers, no handle.
+extern "C" int64_t spicey_fourier_workspace_bytes(int32_t n_inst, int64_t n_points, const SpiceyFourReq *reqs, int32_t n_req) {
+  return spicey_four_workspace_bytes(n_inst, n_points, reqs, n_req);
+}
+
+extern "C" int32_t spicey_fourier_device(int32_t device, int32_t n_inst, int64_t n_points, double dt, const double *d_v, int32_t n_v, const double *d_i,
+                                         int32_t n_i, const SpiceyFourReq *reqs, int32_t n_req, double *d_out, int32_t out_stride, void *d_work,
+                                         int64_t work_bytes, void *stream) {
+  // (the call is judged before the device is touched: a refusal launches nothing)
+  SpiceyFourPlan plan;
+  if (!spicey_four_judge(n_inst, n_points, dt, d_v != nullptr, n_v, d_i != nullptr, n_i, reqs, n_req, d_out && d_work, out_stride, work_bytes, plan, g_err))
+    return SPICEY_ERR_BAD_DESC;
+  int ncu = 0;
+  if (const int32_t rc = spicey_open_device(device, &ncu, g_err); rc != SPICEY_OK) return rc;
+  const hipError_t e = spicey_launch_fourier(device, n_inst, n_points, dt, d_v, n_v, d_i, n_i, plan, d_out, out_stride, d_work, (hipStream_t)stream);
+  if (e != hipSuccess) { g_err = std::string("spicey_launch_fourier: ") + hipGetErrorString(e); return SPICEY_ERR_HIP; }
+  return SPICEY_OK;
+}
 
 // The same for an AC sweep's complex buffers (include/spicey_hip.h): the reduction of ac_measure.hip, no handle.
 extern "C" int64_t spicey_ac_measure_workspace_bytes(int32_t n_inst, int64_t n_freq, int32_t n_req) {

@@ -69,6 +69,10 @@ SIGNATURES = {
     "spicey_measure_device": (_i32, [_i32, _i32, _i64, _f64, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i64, _vp]),
     "spicey_run_measure": (_i32, [_vp, _i64, _f64, _f64p, _i32, _vp, _i32, _f64p, _i32p]),
     "spicey_last_measure_ms": (_f64, [_vp]),
+    "spicey_fourier_workspace_bytes": (_i64, [_i32, _i64, _vp, _i32]),
+    "spicey_fourier_device": (_i32, [_i32, _i32, _i64, _f64, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i64, _vp]),
+    "spicey_run_measure_fourier": (_i32, [_vp, _i64, _f64, _f64p, _i32, _vp, _i32, _f64p, _vp, _i32, _f64p, _i32, _i32p]),
+    "spicey_last_fourier_ms": (_f64, [_vp]),
     "spicey_ac_last_inst_status": (_i32, [_vp, _i32p, _i64p]),
     "spicey_ac_measure_workspace_bytes": (_i64, [_i32, _i64, _i32]),
     "spicey_ac_measure_device": (_i32, [_i32, _i32, _i64, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i64, _vp]),
@@ -134,6 +138,11 @@ def _ac_reqs(reqs) -> np.ndarray:
     return _reqs(reqs, abi.AC_MEAS_REQ_DTYPE)
 
 
+def _four_reqs(reqs) -> np.ndarray:
+    """A request list as one contiguous array of SpiceyFourReq records (abi.FOUR_REQ_DTYPE)."""
+    return _reqs(reqs, abi.FOUR_REQ_DTYPE)
+
+
 def _reqs_ptr(r: np.ndarray):
     return r.ctypes.data if len(r) else None
 
@@ -176,6 +185,32 @@ def ac_measure_device(n_inst: int, n_freq: int, d_v: int, n_v: int, d_i: int, n_
     """The same for an AC sweep's buffers (spicey_ac_measure_device): d_v [n_inst][n_freq][n_v] complex128, d_i likewise or
     0, d_work of `work_bytes` >= ac_measure_workspace_bytes(...)."""
     _measure_device("spicey_ac_measure_device", (n_inst, n_freq), d_v, n_v, d_i, n_i, _ac_reqs(reqs), d_meas, d_work, work_bytes, device, stream)
+
+
+def fourier_row_doubles(reqs) -> int:
+    """Doubles of a result row that holds every request of the list: 1 + 2 max n_harm."""
+    r = _four_reqs(reqs)
+    return 1 + 2 * int(r["n_harm"].max()) if len(r) else 1
+
+
+def fourier_workspace_bytes(n_inst: int, n_points: int, reqs) -> int:
+    """spicey_fourier_workspace_bytes: device workspace of fourier_device for this request list; -1 for a refused one."""
+    r = _four_reqs(reqs)
+    return load().spicey_fourier_workspace_bytes(n_inst, n_points, _reqs_ptr(r), len(r))
+
+
+def fourier_device(n_inst: int, n_points: int, dt: float, d_v: int, n_v: int, d_i: int, n_i: int, reqs, d_out: int, out_stride: int, d_work: int,
+                   work_bytes: int, device: int = 0, stream: int = 0) -> None:
+    """spicey_fourier_device: the harmonics pass alone on raw device pointers (e.g. torch tensors' data_ptr()): d_v
+    [n_inst][n_points][n_v], d_i [n_inst][n_points][n_i] or 0, d_out [n_inst][n_req][out_stride], d_work of `work_bytes` >=
+    fourier_workspace_bytes(...).  reqs: records of abi.FOUR_REQ_DTYPE.  Enqueued on `stream`, no synchronisation.  A
+    refusal raises SpiceyNativeError whose `status` is the library's code (abi.ERR_BAD_DESC for a bad request list)."""
+    L = load()
+    r = _four_reqs(reqs)
+    rc = L.spicey_fourier_device(device, n_inst, n_points, dt, d_v or None, n_v, d_i or None, n_i, _reqs_ptr(r), len(r), d_out or None, out_stride,
+                                 d_work or None, work_bytes, stream or None)
+    if rc != abi.OK:
+        _fail("spicey_fourier_device", rc, L.spicey_last_error(None))
 
 
 class Handle:
@@ -273,6 +308,29 @@ class Handle:
         kept = rc in (abi.OK, abi.ERR_SINGULAR)
         if kept:
             res["measure_ms"] = self.L.spicey_last_measure_ms(self.h)
+        return self._dress(res, rc, kept, kept)
+
+    def run_measure_fourier(self, steps: int, dt: float, src: np.ndarray, reqs, freqs, want_iters: bool = True) -> dict:
+        """spicey_run_measure_fourier: run_measure with the harmonics pass behind the measurements, over the same device
+        waveforms.  reqs: records of abi.MEAS_REQ_DTYPE (may be empty), freqs: records of abi.FOUR_REQ_DTYPE (at least one).
+        Beside what run_measure returns: `four` [n_inst][n_four][1 + 2 max n_harm] = {C0, C1, S1, ...} per request, the rest
+        of a row 0 (include/spicey_hip.h), and `fourier_ms`."""
+        f = self.flat
+        src = np.ascontiguousarray(src, dtype=np.float64)
+        per_inst = _src_layout(src, f, steps)
+        r, fr = _reqs(reqs), _four_reqs(freqs)
+        stride = fourier_row_doubles(fr)
+        meas = np.zeros((f.n_inst, len(r), 8))
+        four = np.zeros((f.n_inst, len(fr), stride))
+        iters = np.zeros((f.n_inst, steps + 1), np.int32) if want_iters else None
+        rc = self.L.spicey_run_measure_fourier(self.h, steps, dt, _p(src, C.c_double), 1 if per_inst else 0, _reqs_ptr(r), len(r),
+                                               _p(meas, C.c_double) if len(r) else None, _reqs_ptr(fr), len(fr), _p(four, C.c_double), stride,
+                                               _p(iters, C.c_int32))
+        res = {"status": rc, "detail": self.error() if rc != abi.OK else "", "meas": meas, "four": four, "iters": iters, "partial": True}
+        kept = rc in (abi.OK, abi.ERR_SINGULAR)
+        if kept:
+            res["measure_ms"] = self.L.spicey_last_measure_ms(self.h)
+            res["fourier_ms"] = self.L.spicey_last_fourier_ms(self.h)
         return self._dress(res, rc, kept, kept)
 
     def run_device(self, steps: int, dt: float, d_src: int, d_out_v: int, d_out_i: int = 0, d_iters: int = 0, stream: int = 0,
@@ -607,6 +665,10 @@ class HipBackend(_AcCalls):
     def run_measure(self, flat: abi.FlatCircuit, steps: int, dt: float, src: np.ndarray, reqs, want_iters: bool = True) -> dict:
         """Handle.run_measure on a handle of its own: the waveforms never leave the device."""
         return self._on_handle(flat, lambda h: h.run_measure(steps, dt, src, reqs, want_iters))
+
+    def run_measure_fourier(self, flat: abi.FlatCircuit, steps: int, dt: float, src: np.ndarray, reqs, freqs, want_iters: bool = True) -> dict:
+        """Handle.run_measure_fourier on a handle of its own: the waveforms never leave the device."""
+        return self._on_handle(flat, lambda h: h.run_measure_fourier(steps, dt, src, reqs, freqs, want_iters))
 
 
 class HipAcExactBackend(_AcCalls):

@@ -9,6 +9,7 @@ names one.
 Specs
     stats("v(out)")                        min, max, pp, t_min, t_max, first, final, integ, avg, rms
     cross("v(a,b)", 2.5, dir="rise")       count, t_first, t_last, freq
+    fourier("v(out)", 50e3, harmonics=9)   f0, periods, dc, mag[], phase_deg[], thd   (see "Harmonics" below)
 `signal` is "v(a)", "v(a,b)" (= v(a) - v(b), one rounded subtraction per sample; v(a,0) is v(a)) or "i(R1)" (the element
 current simulateTRAN records under that name).  Node names resolve case-insensitively like the parser's; element names
 too, and a name that several elements share is an error.
@@ -24,8 +25,22 @@ trapezoidal rule on the uniform grid —, avg = integ / ((n - 1) dt), rms = sqrt
 x_k+1, fall x_k > level >= x_k+1, at linearly interpolated times; freq = (count - 1) / (t_last - t_first) for count >=
 2, else None; t_first / t_last are None without a crossing.
 
+Harmonics.  fourier(signal, f0, harmonics=9, t_from=None, t_to=None, periods=None) is what SPICE calls .four: the device
+(spicey_run_measure_fourier, a second reduction behind the first over the same waveforms) sums C0 = sum x_s, C_h = sum x_s
+cos(2 pi h f0 s dt), S_h = sum x_s sin(2 pi h f0 s dt) for h = 1..harmonics over the N samples step_from .. step_to - 1 —
+the sample at step_to closes the last period and is left out (the rectangular rule, exact for a waveform periodic in the
+window) — with s the ABSOLUTE step, so phases refer to t = 0.  The window is t_from / t_to by the rule above, or, with
+periods=n, the last n periods that end at t_to: step_from = step_to - round(n / (f0 dt)).  On the host: dc = C0 / N, a_h =
+2 C_h / N, b_h = 2 S_h / N, mag[h-1] = hypot(a_h, b_h), phase_deg[h-1] = degrees(atan2(-b_h, a_h)) — x(t) = M cos(2 pi h f0
+t + phi) gives back M and phi —, thd = sqrt(sum_{h>=2} mag_h^2) / mag_1 (None when mag_1 == 0 or harmonics == 1), and
+`periods` = N dt f0 as a float: a window that is no whole number of periods LEAKS (every harmonic picks up some of the
+others); that is reported by this number and not refused.  ValueError for a window that is empty, reaches before the run
+or is more than half a step shorter than one period, for harmonics outside 1..16 or above Nyquist (harmonics f0 > 1 / (2
+dt)), and for periods= together with t_from=.  A dict without a fourier spec takes the path it always took.
+
 reduce_reference() is the same definition in plain numpy; it is what the tests compare the device with, and what runs
-behind a backend that has no run_measure (backend.run, then reduce_reference: the CPU oracle works unchanged).
+behind a backend that has no run_measure (backend.run, then reduce_reference: the CPU oracle works unchanged);
+reduce_reference_fourier() is the same for the harmonics.
 """
 from __future__ import annotations
 
@@ -60,6 +75,16 @@ class Cross:
     t_to: Optional[float] = None
 
 
+@dataclass(frozen=True)
+class Fourier:
+    signal: str
+    f0: float
+    harmonics: int = 9
+    t_from: Optional[float] = None
+    t_to: Optional[float] = None
+    periods: Optional[int] = None
+
+
 def stats(signal: str, t_from: Optional[float] = None, t_to: Optional[float] = None) -> Stats:
     return Stats(str(signal), t_from, t_to)
 
@@ -68,6 +93,45 @@ def cross(signal: str, level: float, dir="rise", t_from: Optional[float] = None,
     if dir not in _DIRS:
         raise ValueError(f"cross: dir must be 'rise', 'fall' or 'either', got {dir!r}")
     return Cross(str(signal), float(level), _DIRS[dir], t_from, t_to)
+
+
+def fourier(signal: str, f0: float, harmonics: int = 9, t_from: Optional[float] = None, t_to: Optional[float] = None,
+            periods: Optional[int] = None) -> Fourier:
+    f0 = float(f0)
+    if not (math.isfinite(f0) and f0 > 0):
+        raise ValueError(f"fourier: f0 must be finite and > 0, got {f0!r}")
+    if isinstance(harmonics, bool) or int(harmonics) != harmonics or not 1 <= int(harmonics) <= abi.FOUR_MAX_HARM:
+        raise ValueError(f"fourier: harmonics must be an integer in 1..{abi.FOUR_MAX_HARM}, got {harmonics!r}")
+    if periods is not None:
+        if t_from is not None:
+            raise ValueError("fourier: give periods= or t_from=, not both (periods counts back from t_to)")
+        if isinstance(periods, bool) or int(periods) != periods or int(periods) < 1:
+            raise ValueError(f"fourier: periods must be an integer >= 1, got {periods!r}")
+        periods = int(periods)
+    return Fourier(str(signal), f0, int(harmonics), t_from, t_to, periods)
+
+
+def make_four_reqs(rows: Sequence[tuple]) -> np.ndarray:
+    """Request records (abi.FOUR_REQ_DTYPE) from tuples (signal, col, col_ref, n_harm, step_from, step_to, f0)."""
+    a = np.zeros(len(rows), abi.FOUR_REQ_DTYPE)
+    for k, r in enumerate(rows):
+        a[k] = tuple(r)
+    return a
+
+
+def fourier_window(spec: Fourier, dt: float, steps: int, name: str = "") -> Tuple[int, int]:
+    """(step_from, step_to) of a fourier spec in a run of `steps` steps of dt, or ValueError (module text)."""
+    if spec.harmonics * spec.f0 > 1.0 / (2.0 * dt):
+        raise ValueError(f"measure {name!r}: harmonic {spec.harmonics} of {spec.f0} Hz is above Nyquist, 1 / (2 dt) = {1.0 / (2.0 * dt)} Hz")
+    s1 = time_to_step(spec.t_to, dt, steps, steps)
+    s0 = s1 - int(round(spec.periods / (spec.f0 * dt))) if spec.periods is not None else time_to_step(spec.t_from, dt, steps, 0)
+    if s0 < 0:
+        raise ValueError(f"measure {name!r}: {spec.periods} periods of {spec.f0} Hz before step {s1} reach before the run")
+    if s0 >= s1:
+        raise ValueError(f"measure {name!r}: the window is empty (it starts at step {s0} and ends at step {s1})")
+    if (s1 - s0 + 0.5) * dt * spec.f0 < 1.0:
+        raise ValueError(f"measure {name!r}: the window of {s1 - s0} steps is shorter than one period of {spec.f0} Hz")
+    return s0, s1
 
 
 def make_reqs(rows: Sequence[tuple]) -> np.ndarray:
@@ -132,37 +196,53 @@ class _Plan:
             raise ValueError("measure: no measures given")
         parsed = []
         for name, spec in measures.items():
-            if not isinstance(spec, (Stats, Cross)):
-                raise TypeError(f"measure {name!r}: expected stats(...) or cross(...), got {type(spec).__name__}")
+            if not isinstance(spec, (Stats, Cross, Fourier)):
+                raise TypeError(f"measure {name!r}: expected stats(...), cross(...) or fourier(...), got {type(spec).__name__}")
             parsed.append((name, spec, _parse_signal(ckt, spec.signal)))
         nodes = sorted({n for _, _, (sig, a, b) in parsed if sig == 0 for n in (a, b) if n != 0})
         self.need_i = any(sig == 1 for _, _, (sig, _, _) in parsed)
         # (a device descriptor records at least one node; with current measures only, the first one)
         self.out_nodes = nodes if nodes else [1]
         col = {n: c for c, n in enumerate(self.out_nodes)}
-        rows = []
-        self.names = []
+        rows, frows = [], []
+        self.names = []  # (name, is a fourier spec, its place in reqs / freqs), in the dict's order
         for name, spec, (sig, a, b) in parsed:
+            c, cr = (col[a], col[b] if b else -1) if sig == 0 else (a, -1)
+            if isinstance(spec, Fourier):
+                s0, s1 = fourier_window(spec, dt, steps, name)
+                self.names.append((name, True, len(frows)))
+                frows.append((sig, c, cr, spec.harmonics, s0, s1, spec.f0))
+                continue
             s0 = time_to_step(spec.t_from, dt, steps, 0)
             s1 = time_to_step(spec.t_to, dt, steps, steps)
             if s0 > s1:
                 raise ValueError(f"measure {name!r}: the window is empty (t_from maps to step {s0}, t_to to step {s1})")
-            c, cr = (col[a], col[b] if b else -1) if sig == 0 else (a, -1)
+            self.names.append((name, False, len(rows)))
             if isinstance(spec, Stats):
                 rows.append((abi.MEAS_STATS, sig, c, cr, s0, s1, 0.0, 0))
             else:
                 rows.append((abi.MEAS_CROSS, sig, c, cr, s0, s1, spec.level, spec.dir))
-            self.names.append(name)
         self.reqs = make_reqs(rows)
+        self.freqs = make_four_reqs(frows)  # (empty: the dict takes the path without the harmonics pass)
 
     def flatten(self, ckt: ParsedCircuit) -> abi.FlatCircuit:
         flat = abi.flatten(ckt)
         flat.out_nodes = np.ascontiguousarray(self.out_nodes, dtype=np.int32)
         return flat
 
-    def values(self, meas: np.ndarray, dt: float) -> Dict[str, dict]:
-        """meas [n_req][8] of one instance -> {name: {...}}."""
-        return {name: derive(self.reqs[k], meas[k], dt) for k, name in enumerate(self.names)}
+    def key(self) -> bytes:
+        """What a batch groups by beside topology and run: both resolved request tables."""
+        return self.reqs.tobytes() + b"|" + self.freqs.tobytes()
+
+    def run(self, be, flat: abi.FlatCircuit, steps: int, dt: float, src: np.ndarray) -> dict:
+        if len(self.freqs):
+            return backend_measure_fourier(be, flat, steps, dt, src, self.reqs, self.freqs, self.need_i)
+        return backend_measure(be, flat, steps, dt, src, self.reqs, self.need_i)
+
+    def values(self, res: dict, j: int, dt: float) -> Dict[str, dict]:
+        """Instance j of a result (meas [n_inst][n_req][8], four [n_inst][n_four][row]) -> {name: {...}}."""
+        return {name: derive_fourier(self.freqs[k], res["four"][j][k], dt) if four else derive(self.reqs[k], res["meas"][j][k], dt)
+                for name, four, k in self.names}
 
 
 def derive(req, m, dt: float) -> dict:
@@ -183,6 +263,19 @@ def derive(req, m, dt: float) -> dict:
     tf, tl = (float(m[1]), float(m[2])) if count > 0 else (None, None)
     freq = (count - 1) / (tl - tf) if count >= 2 and tl > tf else None
     return {"count": count, "t_first": tf, "t_last": tl, "freq": freq}
+
+
+def derive_fourier(req, row, dt: float) -> dict:
+    """The values of one fourier spec from its row {C0, C1, S1, ...} (module text)."""
+    n = int(req["step_to"]) - int(req["step_from"])
+    H, f0 = int(req["n_harm"]), float(req["f0"])
+    mag, ph = [], []
+    for h in range(1, H + 1):
+        a, b = 2.0 * float(row[2 * h - 1]) / n, 2.0 * float(row[2 * h]) / n
+        mag.append(math.hypot(a, b))
+        ph.append(math.degrees(math.atan2(-b, a)))
+    thd = math.sqrt(sum(m * m for m in mag[1:])) / mag[0] if H > 1 and mag[0] != 0.0 else None
+    return {"f0": f0, "periods": n * dt * f0, "dc": float(row[0]) / n, "mag": mag, "phase_deg": ph, "thd": thd}
 
 
 def reduce_reference(out_v: np.ndarray, out_i: Optional[np.ndarray], reqs, dt: float) -> np.ndarray:
@@ -243,6 +336,58 @@ def reduce_reference(out_v: np.ndarray, out_i: Optional[np.ndarray], reqs, dt: f
     return meas
 
 
+def reduce_reference_fourier(out_v: np.ndarray, out_i: Optional[np.ndarray], reqs, dt: float) -> np.ndarray:
+    """The definition of spicey_fourier_device in numpy, independent of the kernels: out_v [n_inst][n_points][n_v], out_i
+    likewise or None, reqs records of abi.FOUR_REQ_DTYPE with step_to resolved or -1 -> [n_inst][n_req][1 + 2 max n_harm],
+    {C0, C1, S1, ...} and zeros behind a request's own 1 + 2 n_harm.  The twiddle argument is formed by the same three
+    operations as the library's (r = float(h s) (f0 dt); r -= floor(r); a = 2 pi r), cos / sin are numpy's; every product is
+    rounded on its own and every sum runs over the window in step order, one addition after the other from 0.0
+    (np.add.accumulate: no pairwise regrouping) — no chunks."""
+    reqs = np.ascontiguousarray(reqs, dtype=abi.FOUR_REQ_DTYPE).reshape(-1)
+    out_v = np.asarray(out_v, dtype=np.float64)
+    ni, n_points = out_v.shape[0], out_v.shape[1]
+    width = 1 + 2 * int(reqs["n_harm"].max()) if len(reqs) else 1
+    rows = np.zeros((ni, len(reqs), width))
+    tw_cache: Dict[tuple, tuple] = {}
+    for r, q in enumerate(reqs):
+        a = out_i if int(q["signal"]) == 1 else out_v
+        if a is None:
+            raise ValueError("reduce_reference_fourier: a request names a current, but there is no out_i")
+        a = np.asarray(a, dtype=np.float64)
+        s0, H, f0 = int(q["step_from"]), int(q["n_harm"]), float(q["f0"])
+        s1 = n_points - 1 if int(q["step_to"]) == -1 else int(q["step_to"])
+        if not (0 <= s0 < s1 < n_points) or not 1 <= H <= abi.FOUR_MAX_HARM:
+            raise ValueError(f"reduce_reference_fourier: request {r}: window [{s0}, {s1}) outside the run, or n_harm {H}")
+        x = a[:, s0:s1, int(q["col"])]
+        if int(q["col_ref"]) >= 0:
+            x = x - a[:, s0:s1, int(q["col_ref"])]
+        key = (f0, s0, s1, H)
+        if key not in tw_cache:
+            hs = np.arange(1, H + 1, dtype=np.int64)[:, None] * np.arange(s0, s1, dtype=np.int64)[None, :]
+            t = hs.astype(np.float64) * (f0 * dt)
+            t = t - np.floor(t)
+            ang = (2.0 * np.pi) * t
+            tw_cache[key] = (np.cos(ang), np.sin(ang))
+        c, sn = tw_cache[key]
+        zero = np.zeros(x.shape[:1] + (1,))
+        rows[:, r, 0] = np.add.accumulate(np.concatenate([zero, x], axis=1), axis=1)[:, -1]
+        z3 = np.zeros((ni, H, 1))
+        rows[:, r, 1:2 * H + 1:2] = np.add.accumulate(np.concatenate([z3, x[:, None, :] * c[None]], axis=2), axis=2)[:, :, -1]
+        rows[:, r, 2:2 * H + 2:2] = np.add.accumulate(np.concatenate([z3, x[:, None, :] * sn[None]], axis=2), axis=2)[:, :, -1]
+    return rows
+
+
+def backend_measure_fourier(be, flat: abi.FlatCircuit, steps: int, dt: float, src: np.ndarray, reqs: np.ndarray, freqs: np.ndarray, need_i: bool) -> dict:
+    """The backend's run_measure_fourier, or for a backend without one its run followed by both numpy reductions."""
+    if hasattr(be, "run_measure_fourier"):
+        return be.run_measure_fourier(flat, steps, dt, src, reqs, freqs)
+    res = be.run(flat, steps, dt, src, want_currents=need_i)
+    if res["status"] == abi.OK or (res["status"] == abi.ERR_SINGULAR and res.get("partial")):
+        res["meas"] = reduce_reference(res["out_v"], res.get("out_i"), reqs, dt) if len(reqs) else np.zeros((res["out_v"].shape[0], 0, 8))
+        res["four"] = reduce_reference_fourier(res["out_v"], res.get("out_i"), freqs, dt)
+    return res
+
+
 def backend_measure(be, flat: abi.FlatCircuit, steps: int, dt: float, src: np.ndarray, reqs: np.ndarray, need_i: bool) -> dict:
     """The backend's run_measure, or for a backend without one its run followed by reduce_reference."""
     if hasattr(be, "run_measure"):
@@ -264,7 +409,7 @@ def _backend(backend, exact_order: bool, device: int, diagnostics: bool, who: st
 
 
 def measureTRAN(ckt: ParsedCircuit, measures: Dict[str, object], *, exact_order: bool = False, device: int = 0, backend=None) -> Optional[dict]:
-    """The transient of `ckt` reduced to {name: {...}} for measures = {name: stats(...) | cross(...)} (module text).  None
+    """The transient of `ckt` reduced to {name: {...}} for measures = {name: stats(...) | cross(...) | fourier(...)} (module text).  None
     without a .tran card; SingularMatrixError and the circuit's state write-back exactly as simulateTRAN; exact_order=True
     runs the reference-order engine."""
     be = _backend(backend, exact_order, device, True, "measureTRAN")
@@ -275,13 +420,13 @@ def measureTRAN(ckt: ParsedCircuit, measures: Dict[str, object], *, exact_order:
     plan = _Plan(ckt, measures, dt, steps)
     flat = plan.flatten(ckt)
     src = abi.source_table(ckt, dt, steps)
-    res = backend_measure(be, flat, steps, dt, src, plan.reqs, plan.need_i)
+    res = plan.run(be, flat, steps, dt, src)
     if res["status"] == abi.ERR_SINGULAR:
         raise SingularMatrixError(res.get("detail", ""))
     if res["status"] != abi.OK:
         raise RuntimeError(res.get("detail", f"spicey native error {res['status']}"))
     write_state(ckt, res["state"], 0)
-    return plan.values(res["meas"][0], dt)
+    return plan.values(res, 0, dt)
 
 
 def measureTRANBatch(ckts: Sequence[ParsedCircuit], measures: Dict[str, object], *, exact_order: bool = False, diagnostics: bool = True,
@@ -309,14 +454,14 @@ def measureTRANBatch(ckts: Sequence[ParsedCircuit], measures: Dict[str, object],
 
     # (names resolve per circuit: two circuits of one topology may call its elements differently — the request records
     # are part of the group's key, so one launch has one request table)
-    launches = group_launches(ckts, max_instances, lambda c: plan_of(c).flatten(c), lambda c, dt, steps: plan_of(c).reqs.tobytes())
+    launches = group_launches(ckts, max_instances, lambda c: plan_of(c).flatten(c), lambda c, dt, steps: plan_of(c).key())
     for idx in launches:
         plan = plan_of(ckts[idx[0]])
 
         def result(i, flat_i, dt, steps, res, j, sk):
             write_state(ckts[i], res["state"], j)
-            return plan_of(ckts[i]).values(res["meas"][j], dt)
+            return plan_of(ckts[i]).values(res, j, dt)
 
-        run_launch(lambda flat, steps, dt, src: backend_measure(be, flat, steps, dt, src, plan.reqs, plan.need_i), ckts, idx, out, diagnostics,
+        run_launch(lambda flat, steps, dt, src: plan.run(be, flat, steps, dt, src), ckts, idx, out, diagnostics,
                    lambda c: plan_of(c).flatten(c), result, "measureTRANBatch")
     return out
