@@ -27,9 +27,9 @@ def _switched_text():
     return flat
 
 
-BUILDER_CASES = {f"diode_chain({n})": (lambda n=n: _flat(synth.diode_chain(n))) for n in (20, 100, 333, 1000)}
+BUILDER_CASES = {f"diode_chain({n})": (lambda n=n: _flat(synth.diode_chain(n))) for n in (20, 100, 333, 1000, 1023)}
 BUILDER_CASES.update({f"rc_ladder({n})": (lambda n=n: _flat(synth.rc_ladder(n))) for n in (20, 1000)})
-BUILDER_CASES.update({f"rcd_mesh({r})": (lambda r=r: _flat(synth.rcd_mesh(r))) for r in (6, 12)})
+BUILDER_CASES.update({f"rcd_mesh({r})": (lambda r=r: _flat(synth.rcd_mesh(r))) for r in (6, 12, 15)})
 BUILDER_CASES["switched_ladder"] = _switched_text
 BUILDER_CASES.update({f"golden:{g}": (lambda g=g: _flat(golden_netlist(load_golden(g)))) for g in SMALL_GOLDENS})
 
@@ -72,6 +72,19 @@ def _mesh12():
     return abi.flatten(ckt), dt, abi.source_table(ckt, dt, steps)[: STEPS + 1]
 
 
+def _mesh15():
+    ckt = parseNetlist(synth.rcd_mesh(15, tran=".tran 1e-6 3.2e-5"))
+    dt, steps = abi.computeEffectiveTimeStep(ckt.analyses["tran"]["dt"], ckt.analyses["tran"]["tstop"])
+    return abi.flatten(ckt), dt, abi.source_table(ckt, dt, steps)
+
+
+def _golden(name):
+    """A small golden over its own .tran (the run's length is the table's)."""
+    ckt = parseNetlist(golden_netlist(load_golden(name)))
+    dt, steps = abi.computeEffectiveTimeStep(ckt.analyses["tran"]["dt"], ckt.analyses["tran"]["tstop"])
+    return abi.flatten(ckt), dt, abi.source_table(ckt, dt, steps)
+
+
 def _switched_one():
     flat, dt, src = _switched_ladder()
     from batch_variants import instance
@@ -84,7 +97,15 @@ RUN_CASES = {
     "rc_ladder_1000": lambda: _chain("rc_ladder", 1000),      # factor reuse: the fills of step 0 are kept
     "switched_ladder": _switched_one,                         # iterations > 1
     "rcd_mesh_12": _mesh12,                                   # overflow lists, entries targeted at several levels
+    # the CPU twins of tests/test_packed_topologies_gpu.py: when a case fails there, these say whether the program is wrong
+    "diode_chain_1023": lambda: _chain("diode_chain", 1023),  # nKeep == 2 x 512, more than one streamed phase
+    "diode_chain_511": lambda: _chain("diode_chain", 511),    # n around the workgroup size
+    "diode_chain_513": lambda: _chain("diode_chain", 513),
+    "rcd_mesh_15": _mesh15,                                   # nRestore just under 6 x 512
 }
+# small goldens with a fresh class: switches, inductors, diodes, everything in the LDS tail levels
+TAIL_GOLDENS = ("boost_probe", "half_bridge", "diode_switch", "switch_vt_vh", "vswitch_pwl", "relay_osc", "star_hub", "bridge_bleed", "dchain20", "mesh9x5")
+RUN_CASES.update({f"golden:{g}": (lambda g=g: _golden(g)) for g in TAIL_GOLDENS})
 _DEFAULT: dict = {}
 
 
@@ -92,7 +113,7 @@ def _default_run(case):
     """The default program on the default packed build: computed once per case, never modified."""
     if case not in _DEFAULT:
         flat, dt, src = RUN_CASES[case]()
-        r = pyfresh.run(flat, STEPS, dt, src, fresh=False)
+        r = pyfresh.run(flat, len(src) - 1, dt, src, fresh=False)
         assert r["status"] == 0 and r["fresh_fill"] == 0 and r["nKeep"] == r["nRestore"]
         for a in (r["out_v"], r["out_i"], r["iters"], *r["state"].values()):
             a.setflags(write=False)
@@ -104,7 +125,7 @@ def _default_run(case):
 @pytest.mark.parametrize("case", sorted(RUN_CASES))
 def test_fresh_program_gives_the_default_programs_bits(case, nan_fill):
     flat, dt, src, ref = _default_run(case)
-    got = pyfresh.run(flat, STEPS, dt, src, fresh=True, nan_fill=nan_fill)
+    got = pyfresh.run(flat, len(src) - 1, dt, src, fresh=True, nan_fill=nan_fill)
     assert got["status"] == 0 and got["fresh_fill"] == 1
     assert got["nRestore"] == ref["nRestore"] and got["nKeep"] < got["nRestore"]
     assert (got["streamed_tasks"], got["resident_tasks"]) == (ref["streamed_tasks"], ref["resident_tasks"])
@@ -117,11 +138,45 @@ def test_fresh_program_gives_the_default_programs_bits(case, nan_fill):
         assert int(got["iters"].max()) > 1
     if case == "diode_chain_1000":
         assert got["streamed_tasks"] == 2000 and got["resident_tasks"] == 2719
+    if case == "diode_chain_1023":
+        assert got["nKeep"] == 2 * 512 and got["streamed_tasks"] == 3070
+    if case == "rcd_mesh_15":
+        assert (got["nKeep"], got["nRestore"], got["streamed_tasks"]) == (266, 2930, 17188)
+    if case in ("golden:half_bridge", "golden:diode_switch", "golden:switch_vt_vh", "golden:vswitch_pwl", "golden:relay_osc"):
+        assert int(got["iters"].max()) > 1  # (a switch flips within the golden's own .tran)
+
+
+RANDOM_BLOCK = 40
+
+
+@pytest.mark.parametrize("nan_fill", [False, True], ids=["zeroed", "nan_arena"])
+@pytest.mark.parametrize("floating,first", [(False, s) for s in range(0, 200, RANDOM_BLOCK)] + [(True, s) for s in range(0, 120, RANDOM_BLOCK)],
+                         ids=lambda v: {False: "grounded", True: "floating"}[v] if isinstance(v, bool) else f"seeds_{v}")
+def test_fresh_program_gives_the_default_programs_bits_on_random_circuits(floating, first, nan_fill):
+    """tests/random_circuits.py, seeds 0..199 and 0..119 with floating sources (every one packable): R / C / L / V / D / S
+    mixes of a few unknowns, everything in the LDS tail levels."""
+    from random_circuits import random_netlist
+    with_class = 0
+    for seed in range(first, first + RANDOM_BLOCK):
+        ckt = parseNetlist(random_netlist(seed, floating_sources=floating))
+        dt, steps = abi.computeEffectiveTimeStep(ckt.analyses["tran"]["dt"], ckt.analyses["tran"]["tstop"])
+        flat, src = abi.flatten(ckt), abi.source_table(ckt, dt, steps)
+        ref = pyfresh.run(flat, steps, dt, src, fresh=False)
+        got = pyfresh.run(flat, steps, dt, src, fresh=True, nan_fill=nan_fill)
+        assert ref["status"] == got["status"] == 0 and ref["fresh_fill"] == 0 and got["fresh_fill"] == 1, seed
+        assert ref["nKeep"] == ref["nRestore"] == got["nRestore"] and got["nKeep"] <= got["nRestore"], seed
+        with_class += int(got["nKeep"] < got["nRestore"])
+        assert np.isfinite(got["out_v"]).all(), seed
+        for k in ("out_v", "out_i", "iters"):
+            assert np.array_equal(got[k], ref[k], equal_nan=(k == "out_i")), (seed, k)
+        for k, v in ref["state"].items():
+            assert np.array_equal(got["state"][k], v), (seed, k)
+    assert with_class >= RANDOM_BLOCK - 1  # (one seed of the 200 has no fill to create)
 
 
 def test_threads_in_reverse_order_change_nothing():
     flat, dt, src, ref = _default_run("diode_chain_600")
-    got = pyfresh.run(flat, STEPS, dt, src, fresh=True, nan_fill=True, reverse=True)
+    got = pyfresh.run(flat, len(src) - 1, dt, src, fresh=True, nan_fill=True, reverse=True)
     assert got["status"] == 0
     for k in ("out_v", "out_i", "iters"):
         assert np.array_equal(got[k], ref[k])
