@@ -406,6 +406,77 @@ int32_t spicey_run_measure_fourier(SpiceyHandle *h, int64_t steps, double dt, co
 /* Duration in ms of the last spicey_run_measure_fourier's harmonics pass (both of its kernels), measured with HIP events. */
 double spicey_last_fourier_ms(SpiceyHandle *h);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Edge timing on the device (propagation delay, rise time, settling time, pulse width, period): a fourth reduction pass
+ * over the same step-major buffers.
+ * An EDGE names one signal (signal, col, col_ref exactly as in SpiceyMeasReq: one rounded subtraction per sample), a
+ * direction dir (+1 rise, -1 fall, 0 either), an occurrence n != 0 (n >= 1: the n-th crossing from the start of the edge's
+ * search range, n <= -1: the |n|-th from its end) and a level:
+ *   level_kind 0   absolute: L = level
+ *   level_kind 1   L = lo + level * (hi - lo) with (lo, hi) = (min, max) of the same signal over the inclusive base window
+ *                  [base_from, base_to] (base_to = -1: n_points - 1) of THAT instance
+ *   level_kind 2   the same with (lo, hi) = (first, last) sample of the base window
+ * the difference, the product and the sum each rounded on its own; `level` is then any finite fraction (1.02 is legal).  A
+ * flat signal gives L = lo and no crossing.  base_from / base_to are not read for level_kind 0.
+ * A crossing is that of SpiceyMeasReq's kind 1: a rise is x_k < L && x_k+1 >= L, a fall x_k > L && x_k+1 <= L; it lies in
+ * interval k, at the time ((double)k + (L - x_k) / (x_k+1 - x_k)) * dt, evaluated in that order.  A NaN sample or level
+ * never makes a crossing.
+ * A REQUEST has a window [step_from, step_to] (step_to = -1: n_points - 1; the intervals with both ends inside), a targ
+ * edge and, with has_trig = 1, a trig edge.  The trig's search range is the window.  So is the targ's (SPICE's rule, the
+ * default); with targ_from_trig = 1 it is the window's intervals k >= k_trig.  All selection is by the integer interval
+ * index; interpolated times are never compared, so a targ crossing in the trigger's own interval counts, even where its
+ * interpolated time lies a fraction of a step before the trigger's.  With the same edge as trig and targ and
+ * targ_from_trig = 1, n = 1 therefore finds the trigger's own crossing: a period is asked for as trig n = 1, targ n = 2
+ * under the default rule.
+ * Results, 8 doubles per (instance, request):
+ *   {k_trig, t_trig, L_trig, k_targ, t_targ, L_targ, n_trig, n_targ}
+ * k_* the selected interval as a double, -1.0 when not found (t_* = -1.0 then); L_* the level used in that instance; n_*
+ * the number of crossings of that edge in its search range.  Without a trig: k_trig = t_trig = -1, L_trig = 0, n_trig = 0.
+ * With targ_from_trig = 1 and no trig found the targ is not searched: k_targ = t_targ = -1, n_targ = 0, L_targ still the
+ * level.
+ * Every field has one value in any evaluation order (integer counts, min / max / first / last, two fixed formulas; no FMA
+ * contraction), so a row is a function of the window's samples, dt and the request alone: it does not depend on n_inst,
+ * the launch or the other requests of the list. */
+typedef struct SpiceyTimingEdge {
+  int32_t signal, col, col_ref, dir;
+  int32_t n, level_kind;
+  int64_t base_from, base_to;
+  double level;
+} SpiceyTimingEdge;
+typedef struct SpiceyTimingReq {
+  int64_t step_from, step_to;
+  int32_t has_trig, targ_from_trig; /* 0 / 1 each */
+  SpiceyTimingEdge trig, targ;      /* trig is not read when has_trig = 0 */
+} SpiceyTimingReq;
+
+/* Bytes of device workspace spicey_timing_device needs for this request list (edge and request tables, the base windows'
+ * results and the measurement pass's workspace for them, chunk counts); -1 for counts <= 0 or a list no launch accepts. */
+int64_t spicey_timing_workspace_bytes(int32_t n_inst, int64_t n_points, const SpiceyTimingReq *reqs, int32_t n_req);
+/* The reduction alone, on any DEVICE buffers d_v [n_inst][n_points][n_v] and d_i [n_inst][n_points][n_i] (or NULL):
+ * needs no handle.  reqs is a HOST array; d_out [n_inst][n_req][8] and d_work (work_bytes >=
+ * spicey_timing_workspace_bytes) are DEVICE buffers.  The base windows of the relative levels go through the kernels of
+ * spicey_measure_device as stats requests into the workspace, then two kernels of this pass; all enqueued on `stream` (a
+ * hipStream_t, NULL = default stream) without synchronising.  SPICEY_ERR_BAD_DESC, with a text containing "timing" in
+ * spicey_last_error(NULL), nothing launched and the buffers untouched, for: an unknown signal, dir or level_kind; n = 0;
+ * a level or fraction that is not finite; a column out of range; signal = 1 with d_i == NULL; a window or base window
+ * outside the run or with from > to; a window of one point (no interval); targ_from_trig without has_trig (or either not
+ * 0 / 1); dt not finite or <= 0; a workspace that is too small; n_req <= 0; null buffers. */
+int32_t spicey_timing_device(int32_t device, int32_t n_inst, int64_t n_points, double dt, const double *d_v, int32_t n_v,
+                             const double *d_i, int32_t n_i, const SpiceyTimingReq *reqs, int32_t n_req, double *d_out,
+                             void *d_work, int64_t work_bytes, void *stream);
+/* spicey_run_measure_fourier with the timing pass behind the other two: one transient run, currents recorded only if a
+ * request of any list has signal = 1, then the measurement pass (if n_req > 0), the harmonics pass (if n_four > 0) and
+ * the timing pass (n_timing >= 1) on the handle's stream over the same device waveforms; only meas [n_inst][n_req][8],
+ * four [n_inst][n_four][four_stride], timing [n_inst][n_timing][8] and iters (or NULL) come back — also after
+ * SPICEY_ERR_SINGULAR.  meas / four may be NULL when their count is 0.  Everything else is as for spicey_run_measure. */
+int32_t spicey_run_measure_timing(SpiceyHandle *h, int64_t steps, double dt, const double *src_table, int32_t src_per_inst,
+                                  const SpiceyMeasReq *reqs, int32_t n_req, double *meas, const SpiceyFourReq *freqs,
+                                  int32_t n_four, double *four, int32_t four_stride, const SpiceyTimingReq *treqs,
+                                  int32_t n_timing, double *timing, int32_t *iters);
+/* Duration in ms of the last spicey_run_measure_timing's timing pass (the base windows' kernels included), measured with
+ * HIP events. */
+double spicey_last_timing_ms(SpiceyHandle *h);
+
 /* Library build info: "spicey_hip <abi> gfx950 …" */
 const char *spicey_version(void);
 

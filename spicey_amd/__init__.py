@@ -6,8 +6,8 @@ and AC) run in libspicey_hip.so (include/spicey_hip.h); nothing here computes on
 not load the library: spicey_amd.lib does on first use, and fails loudly when it is missing.
 
 Beyond the reference's surface: measureTRAN / measureTRANBatch (spicey_amd.measure) reduce a transient to a few numbers
-per circuit on the device instead of returning every sample — extremes, averages and crossings (stats, cross) and
-harmonics with THD (fourier); simulateACBatch (spicey_amd.ac_batch) runs many circuits' AC
+per circuit on the device instead of returning every sample — extremes, averages and crossings (stats, cross),
+harmonics with THD (fourier) and edge timing (when, delay, rise_time, fall_time, settle); simulateACBatch (spicey_amd.ac_batch) runs many circuits' AC
 sweeps as the instances of one launch, and measureAC / measureACBatch (spicey_amd.ac_measure) reduce such sweeps on the
 device to corner frequencies, peaks and point read-outs.
 """

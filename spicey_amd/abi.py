@@ -79,6 +79,25 @@ assert FOUR_REQ_DTYPE.itemsize == C.sizeof(SpiceyFourReq) == 40
 FOUR_MAX_HARM = 16
 
 
+class SpiceyTimingEdge(C.Structure):
+    _fields_ = [("signal", C.c_int32), ("col", C.c_int32), ("col_ref", C.c_int32), ("dir", C.c_int32), ("n", C.c_int32), ("level_kind", C.c_int32),
+                ("base_from", C.c_int64), ("base_to", C.c_int64), ("level", C.c_double)]
+
+
+class SpiceyTimingReq(C.Structure):
+    _fields_ = [("step_from", C.c_int64), ("step_to", C.c_int64), ("has_trig", C.c_int32), ("targ_from_trig", C.c_int32),
+                ("trig", SpiceyTimingEdge), ("targ", SpiceyTimingEdge)]
+
+
+# an edge-timing request list (spicey_timing_device) is one array of these; trig / targ are nested edge records
+TIMING_EDGE_DTYPE = np.dtype([("signal", "<i4"), ("col", "<i4"), ("col_ref", "<i4"), ("dir", "<i4"), ("n", "<i4"), ("level_kind", "<i4"),
+                              ("base_from", "<i8"), ("base_to", "<i8"), ("level", "<f8")])
+TIMING_REQ_DTYPE = np.dtype([("step_from", "<i8"), ("step_to", "<i8"), ("has_trig", "<i4"), ("targ_from_trig", "<i4"),
+                             ("trig", TIMING_EDGE_DTYPE), ("targ", TIMING_EDGE_DTYPE)])
+assert TIMING_EDGE_DTYPE.itemsize == C.sizeof(SpiceyTimingEdge) == 48 and TIMING_REQ_DTYPE.itemsize == C.sizeof(SpiceyTimingReq) == 120
+TIMING_ABS, TIMING_MINMAX, TIMING_ENDS = 0, 1, 2
+
+
 class SpiceyAcMeasReq(C.Structure):
     _fields_ = [("num_signal", C.c_int32), ("num_col", C.c_int32), ("num_col_ref", C.c_int32),
                 ("den_signal", C.c_int32), ("den_col", C.c_int32), ("den_col_ref", C.c_int32), ("what", C.c_int32), ("kind", C.c_int32),

@@ -54,15 +54,16 @@ inline int32_t spicey_open_device(int device, int *ncu, std::string &err) {
 }
 
 // A handle's stream and its timing events: ev0 / ev1 bracket the kernel of a run, mev0 / mev1 the reduction of a
-// *_run_measure, fev0 / fev1 the harmonics pass of spicey_run_measure_fourier (created on first use).  Destroys what it created.  A handle declares it AFTER its DevBufs: members go in
+// *_run_measure, fev0 / fev1 the harmonics pass of spicey_run_measure_fourier, tev0 / tev1 the timing pass of
+// spicey_run_measure_timing (created on first use).  Destroys what it created.  A handle declares it AFTER its DevBufs: members go in
 // reverse order, so events and stream are destroyed before the device memory is freed.
 struct StreamTimers {
   hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr, mev0 = nullptr, mev1 = nullptr, fev0 = nullptr, fev1 = nullptr;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr, mev0 = nullptr, mev1 = nullptr, fev0 = nullptr, fev1 = nullptr, tev0 = nullptr, tev1 = nullptr;
   StreamTimers() = default;
   StreamTimers(const StreamTimers &) = delete;
   ~StreamTimers() {
-    for (hipEvent_t e : {ev0, ev1, mev0, mev1, fev0, fev1})
+    for (hipEvent_t e : {ev0, ev1, mev0, mev1, fev0, fev1, tev0, tev1})
       if (e) (void)hipEventDestroy(e);
     if (stream) (void)hipStreamDestroy(stream);
   }
@@ -79,6 +80,10 @@ struct StreamTimers {
   hipError_t want_fourier_events() {
     const hipError_t e = fev0 ? hipSuccess : hipEventCreate(&fev0);
     return e != hipSuccess || fev1 ? e : hipEventCreate(&fev1);
+  }
+  hipError_t want_timing_events() {
+    const hipError_t e = tev0 ? hipSuccess : hipEventCreate(&tev0);
+    return e != hipSuccess || tev1 ? e : hipEventCreate(&tev1);
   }
   // elapsed milliseconds of a finished pair into *ms (left alone when the runtime cannot tell)
   static void elapsed(hipEvent_t a, hipEvent_t b, double *ms) {

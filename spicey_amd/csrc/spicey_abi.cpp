@@ -25,6 +25,8 @@
 #include "fourier_exec.h"
 #include "measure.h"
 #include "measure_exec.h"
+#include "timing.h"
+#include "timing_exec.h"
 #include "symbolic.h"
 #include "fronts_exec_consts.h"
 
@@ -93,7 +95,7 @@ struct SpiceyHandle {
   DevBuf<double> d_gstat, d_statv, d_rcoef, d_gW, d_dpar;
   DevBuf<int32_t> d_status; DevBuf<unsigned long long> d_solves, d_prof;
   hipStream_t last_stream = nullptr;
-  double last_measure_ms = 0.0, last_fourier_ms = 0.0;
+  double last_measure_ms = 0.0, last_fourier_ms = 0.0, last_timing_ms = 0.0;
   bool pending = false;
   int64_t last_solves = 0;
   double last_ms = 0.0;
@@ -752,15 +754,25 @@ extern "C" int32_t spicey_measure_device(int32_t device, int32_t n_inst, int64_t
   return SPICEY_OK;
 }
 
-// What spicey_run_measure and spicey_run_measure_fourier share: one transient run into device buffers of this call's own,
-// the reductions on the handle's stream behind it, and only their results and `iters` on the way back.  four_pass: the
-// second entry point (the measurement list may then be empty; the harmonics list may not).
+// What spicey_run_measure, spicey_run_measure_fourier and spicey_run_measure_timing share: one transient run into device
+// buffers of this call's own, the reductions on the handle's stream behind it, and only their results and `iters` on the way
+// back.  entry: 0 = the first entry point (the measurement pass alone), 1 = the second (the measurement list may be empty;
+// the harmonics list may not), 2 = the third (either of those lists may be empty; the timing list may not).
 static int32_t run_reduced(SpiceyHandle *h, int64_t steps, double dt, const double *src_table, int32_t src_per_inst, const SpiceyMeasReq *reqs, int32_t n_req,
-                           double *meas, bool four_pass, const SpiceyFourReq *freqs, int32_t n_four, double *four, int32_t four_stride, int32_t *iters) {
+                           double *meas, int entry, const SpiceyFourReq *freqs, int32_t n_four, double *four, int32_t four_stride,
+                           const SpiceyTimingReq *treqs, int32_t n_tim, double *timing, int32_t *iters) {
   if (!h) return SPICEY_ERR_BAD_DESC;
-  if (const int32_t rc0 = check_run_args(h, steps, four_pass ? (const void *)four : (const void *)meas, src_table, src_per_inst); rc0 != SPICEY_OK) return rc0;
-  const bool meas_pass = !four_pass || n_req != 0;
-  if (four_pass && (n_req < 0 || (n_req > 0 && !meas))) { h->err = "fourier: n_req must be >= 0, and meas not null when n_req > 0"; return SPICEY_ERR_BAD_DESC; }
+  const bool tim_pass = entry == 2;
+  if (const int32_t rc0 = check_run_args(h, steps, tim_pass ? (const void *)timing : entry == 1 ? (const void *)four : (const void *)meas, src_table, src_per_inst);
+      rc0 != SPICEY_OK)
+    return rc0;
+  const bool meas_pass = entry == 0 || n_req != 0;
+  const bool four_pass = entry == 1 || (tim_pass && n_four != 0);
+  if (entry == 1 && (n_req < 0 || (n_req > 0 && !meas))) { h->err = "fourier: n_req must be >= 0, and meas not null when n_req > 0"; return SPICEY_ERR_BAD_DESC; }
+  if (tim_pass && (n_req < 0 || (n_req > 0 && !meas) || n_four < 0 || (n_four > 0 && !four))) {
+    h->err = "timing: n_req and n_four must be >= 0, and meas / four not null when their count is > 0";
+    return SPICEY_ERR_BAD_DESC;
+  }
   const SpiceyProg &P = h->hp.hdr;
   const int32_t ni = h->plan.n_inst;
   const int64_t np = steps + 1;
@@ -773,17 +785,21 @@ static int32_t run_reduced(SpiceyHandle *h, int64_t steps, double dt, const doub
       return rc0;
   SpiceyFourPlan fplan;
   if (four_pass && !spicey_four_judge(ni, np, dt, true, P.nOut, true, P.nCur, freqs, n_four, true, four_stride, INT64_MAX, fplan, h->err)) return SPICEY_ERR_BAD_DESC;
+  SpiceyTimPlan tplan;
+  if (tim_pass && !spicey_tim_judge(ni, np, dt, true, P.nOut, true, P.nCur, treqs, n_tim, true, INT64_MAX, tplan, h->err)) return SPICEY_ERR_BAD_DESC;
   bool need_i = false;
   for (const SpiceyMeasDevReq &q : table) need_i = need_i || q.signal == 1;
   for (const SpiceyFourDevReq &q : fplan.table) need_i = need_i || q.signal == 1;
+  for (const SpiceyTimDevEdge &q : tplan.edges) need_i = need_i || q.signal == 1;
   if (const int32_t rc0 = check_structure(h); rc0 != SPICEY_OK) return rc0;
   HIPCHK(h, hipSetDevice(h->device));
-  Roctx range_run(four_pass ? "spicey_run_measure_fourier" : "spicey_run_measure");
+  Roctx range_run(tim_pass ? "spicey_run_measure_timing" : four_pass ? "spicey_run_measure_fourier" : "spicey_run_measure");
   HIPCHK(h, h->q.want_measure_events());
   if (four_pass) HIPCHK(h, h->q.want_fourier_events());
+  if (tim_pass) HIPCHK(h, h->q.want_timing_events());
   HostRun r;
-  DevBuf<double> d_meas, d_four;
-  DevBuf<uint8_t> d_work, d_fwork;
+  DevBuf<double> d_meas, d_four, d_tim;
+  DevBuf<uint8_t> d_work, d_fwork, d_twork;
   // (no current request: the run records no currents)
   if (const int32_t rc0 = r.stage(h, steps, src_table, src_per_inst, need_i, iters != nullptr); rc0 != SPICEY_OK) return rc0;
   if (meas_pass) {
@@ -794,8 +810,13 @@ static int32_t run_reduced(SpiceyHandle *h, int64_t steps, double dt, const doub
     HIPCHK(h, d_four.alloc((size_t)ni * (size_t)n_four * (size_t)four_stride));
     HIPCHK(h, d_fwork.alloc((size_t)fplan.workspace_bytes(ni)));
   }
+  if (tim_pass) {
+    HIPCHK(h, d_tim.alloc((size_t)ni * (size_t)n_tim * 8));
+    HIPCHK(h, d_twork.alloc((size_t)tplan.workspace_bytes(ni, np)));
+  }
   h->last_measure_ms = 0.0;
   h->last_fourier_ms = 0.0;
+  h->last_timing_ms = 0.0;
   hipStream_t st = h->q.stream;
   int32_t rc = spicey_run_device_src(h, steps, dt, r.d_src, src_per_inst, r.d_v, r.d_i, r.d_it, st);
   if (rc != SPICEY_OK) return rc;
@@ -813,6 +834,12 @@ static int32_t run_reduced(SpiceyHandle *h, int64_t steps, double dt, const doub
       if (e == hipSuccess) e = spicey_launch_fourier(h->device, ni, np, dt, r.d_v, P.nOut, r.d_i, P.nCur, fplan, d_four, four_stride, d_fwork, st);
       if (e == hipSuccess) e = hipEventRecord(h->q.fev1, st);
     }
+    if (tim_pass && e == hipSuccess) {
+      failed = "spicey_launch_timing: ";
+      e = hipEventRecord(h->q.tev0, st);
+      if (e == hipSuccess) e = spicey_launch_timing(h->device, ni, np, dt, r.d_v, P.nOut, r.d_i, P.nCur, tplan, d_tim, d_twork, st);
+      if (e == hipSuccess) e = hipEventRecord(h->q.tev1, st);
+    }
     return e;
   };
   const int retries = h->group_retries;
@@ -824,9 +851,11 @@ static int32_t run_reduced(SpiceyHandle *h, int64_t steps, double dt, const doub
   if (rc == SPICEY_OK || rc == SPICEY_ERR_SINGULAR) {
     if (meas_pass) StreamTimers::elapsed(h->q.mev0, h->q.mev1, &h->last_measure_ms);
     if (four_pass) StreamTimers::elapsed(h->q.fev0, h->q.fev1, &h->last_fourier_ms);
+    if (tim_pass) StreamTimers::elapsed(h->q.tev0, h->q.tev1, &h->last_timing_ms);
     Roctx range_copy("spicey_run_measure:results");
     if (meas_pass) HIPCHK(h, hipMemcpy(meas, d_meas, (size_t)ni * (size_t)n_req * 8 * sizeof(double), hipMemcpyDeviceToHost));
     if (four_pass) HIPCHK(h, hipMemcpy(four, d_four, (size_t)ni * (size_t)n_four * (size_t)four_stride * sizeof(double), hipMemcpyDeviceToHost));
+    if (tim_pass) HIPCHK(h, hipMemcpy(timing, d_tim, (size_t)ni * (size_t)n_tim * 8 * sizeof(double), hipMemcpyDeviceToHost));
     if (const int32_t rc0 = r.copy_out(h, nullptr, nullptr, iters); rc0 != SPICEY_OK) return rc0;
   }
   return rc;
@@ -834,17 +863,44 @@ static int32_t run_reduced(SpiceyHandle *h, int64_t steps, double dt, const doub
 
 extern "C" int32_t spicey_run_measure(SpiceyHandle *h, int64_t steps, double dt, const double *src_table, int32_t src_per_inst, const SpiceyMeasReq *reqs,
                                       int32_t n_req, double *meas, int32_t *iters) {
-  return run_reduced(h, steps, dt, src_table, src_per_inst, reqs, n_req, meas, false, nullptr, 0, nullptr, 0, iters);
+  return run_reduced(h, steps, dt, src_table, src_per_inst, reqs, n_req, meas, 0, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, iters);
 }
 
 extern "C" int32_t spicey_run_measure_fourier(SpiceyHandle *h, int64_t steps, double dt, const double *src_table, int32_t src_per_inst, const SpiceyMeasReq *reqs,
                                               int32_t n_req, double *meas, const SpiceyFourReq *freqs, int32_t n_four, double *four, int32_t four_stride,
                                               int32_t *iters) {
-  return run_reduced(h, steps, dt, src_table, src_per_inst, reqs, n_req, meas, true, freqs, n_four, four, four_stride, iters);
+  return run_reduced(h, steps, dt, src_table, src_per_inst, reqs, n_req, meas, 1, freqs, n_four, four, four_stride, nullptr, 0, nullptr, iters);
 }
 
 extern "C" double spicey_last_measure_ms(SpiceyHandle *h) { return h ? h->last_measure_ms : 0.0; }
 extern "C" double spicey_last_fourier_ms(SpiceyHandle *h) { return h ? h->last_fourier_ms : 0.0; }
+
+extern "C" int32_t spicey_run_measure_timing(SpiceyHandle *h, int64_t steps, double dt, const double *src_table, int32_t src_per_inst, const SpiceyMeasReq *reqs,
+                                             int32_t n_req, double *meas, const SpiceyFourReq *freqs, int32_t n_four, double *four, int32_t four_stride,
+                                             const SpiceyTimingReq *treqs, int32_t n_timing, double *timing, int32_t *iters) {
+  return run_reduced(h, steps, dt, src_table, src_per_inst, reqs, n_req, meas, 2, freqs, n_four, four, four_stride, treqs, n_timing, timing, iters);
+}
+
+extern "C" double spicey_last_timing_ms(SpiceyHandle *h) { return h ? h->last_timing_ms : 0.0; }
+
+// Edge timing (include/spicey_hip.h): the reduction of timing.hip on any device buffers, no handle.
+extern "C" int64_t spicey_timing_workspace_bytes(int32_t n_inst, int64_t n_points, const SpiceyTimingReq *reqs, int32_t n_req) {
+  return spicey_tim_workspace_bytes(n_inst, n_points, reqs, n_req);
+}
+
+extern "C" int32_t spicey_timing_device(int32_t device, int32_t n_inst, int64_t n_points, double dt, const double *d_v, int32_t n_v, const double *d_i,
+                                        int32_t n_i, const SpiceyTimingReq *reqs, int32_t n_req, double *d_out, void *d_work, int64_t work_bytes,
+                                        void *stream) {
+  // (the call is judged before the device is touched: a refusal launches nothing)
+  SpiceyTimPlan plan;
+  if (!spicey_tim_judge(n_inst, n_points, dt, d_v != nullptr, n_v, d_i != nullptr, n_i, reqs, n_req, d_out && d_work, work_bytes, plan, g_err))
+    return SPICEY_ERR_BAD_DESC;
+  int ncu = 0;
+  if (const int32_t rc = spicey_open_device(device, &ncu, g_err); rc != SPICEY_OK) return rc;
+  const hipError_t e = spicey_launch_timing(device, n_inst, n_points, dt, d_v, n_v, d_i, n_i, plan, d_out, d_work, (hipStream_t)stream);
+  if (e != hipSuccess) { g_err = std::string("spicey_launch_timing: ") + hipGetErrorString(e); return SPICEY_ERR_HIP; }
+  return SPICEY_OK;
+}
 
 // Harmonics (include/spicey_hip.h): the reduction of fourier.hip on any device buffers, no handle.
 extern "C" int64_t spicey_fourier_workspace_bytes(int32_t n_inst, int64_t n_points, const SpiceyFourReq *reqs, int32_t n_req) {

@@ -73,6 +73,10 @@ SIGNATURES = {
     "spicey_fourier_device": (_i32, [_i32, _i32, _i64, _f64, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i64, _vp]),
     "spicey_run_measure_fourier": (_i32, [_vp, _i64, _f64, _f64p, _i32, _vp, _i32, _f64p, _vp, _i32, _f64p, _i32, _i32p]),
     "spicey_last_fourier_ms": (_f64, [_vp]),
+    "spicey_timing_workspace_bytes": (_i64, [_i32, _i64, _vp, _i32]),
+    "spicey_timing_device": (_i32, [_i32, _i32, _i64, _f64, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i64, _vp]),
+    "spicey_run_measure_timing": (_i32, [_vp, _i64, _f64, _f64p, _i32, _vp, _i32, _f64p, _vp, _i32, _f64p, _i32, _vp, _i32, _f64p, _i32p]),
+    "spicey_last_timing_ms": (_f64, [_vp]),
     "spicey_ac_last_inst_status": (_i32, [_vp, _i32p, _i64p]),
     "spicey_ac_measure_workspace_bytes": (_i64, [_i32, _i64, _i32]),
     "spicey_ac_measure_device": (_i32, [_i32, _i32, _i64, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i64, _vp]),
@@ -100,6 +104,10 @@ GROUP_TOTALS = {"retries": 0, "stale_polls": 0}
 
 
 def load():
+    """The library, opened on first use.  In a process that also uses torch, whose wheel brings a HIP runtime of its own:
+    open the library (any function of this module) either after torch has touched the device or by a call that itself
+    initialises HIP (a Handle); opening it first, letting torch initialise, and only then making the first HIP call through
+    the library has been seen to answer "no HIP device"."""
     global _LIB
     if _LIB is not None:
         return _LIB
@@ -141,6 +149,11 @@ def _ac_reqs(reqs) -> np.ndarray:
 def _four_reqs(reqs) -> np.ndarray:
     """A request list as one contiguous array of SpiceyFourReq records (abi.FOUR_REQ_DTYPE)."""
     return _reqs(reqs, abi.FOUR_REQ_DTYPE)
+
+
+def _timing_reqs(reqs) -> np.ndarray:
+    """A request list as one contiguous array of SpiceyTimingReq records (abi.TIMING_REQ_DTYPE)."""
+    return _reqs(reqs, abi.TIMING_REQ_DTYPE)
 
 
 def _reqs_ptr(r: np.ndarray):
@@ -211,6 +224,21 @@ def fourier_device(n_inst: int, n_points: int, dt: float, d_v: int, n_v: int, d_
                                  d_work or None, work_bytes, stream or None)
     if rc != abi.OK:
         _fail("spicey_fourier_device", rc, L.spicey_last_error(None))
+
+
+def timing_workspace_bytes(n_inst: int, n_points: int, reqs) -> int:
+    """spicey_timing_workspace_bytes: device workspace of timing_device for this request list; -1 for a refused one."""
+    r = _timing_reqs(reqs)
+    return load().spicey_timing_workspace_bytes(n_inst, n_points, _reqs_ptr(r), len(r))
+
+
+def timing_device(n_inst: int, n_points: int, dt: float, d_v: int, n_v: int, d_i: int, n_i: int, reqs, d_out: int, d_work: int, work_bytes: int,
+                  device: int = 0, stream: int = 0) -> None:
+    """spicey_timing_device: the edge-timing pass alone on raw device pointers (e.g. torch tensors' data_ptr()): d_v
+    [n_inst][n_points][n_v], d_i [n_inst][n_points][n_i] or 0, d_out [n_inst][n_req][8], d_work of `work_bytes` >=
+    timing_workspace_bytes(...).  reqs: records of abi.TIMING_REQ_DTYPE.  Enqueued on `stream`, no synchronisation.  A
+    refusal raises SpiceyNativeError whose `status` is the library's code (abi.ERR_BAD_DESC for a bad request list)."""
+    _measure_device("spicey_timing_device", (n_inst, n_points, dt), d_v, n_v, d_i, n_i, _timing_reqs(reqs), d_out, d_work, work_bytes, device, stream)
 
 
 class Handle:
@@ -331,6 +359,34 @@ class Handle:
         if kept:
             res["measure_ms"] = self.L.spicey_last_measure_ms(self.h)
             res["fourier_ms"] = self.L.spicey_last_fourier_ms(self.h)
+        return self._dress(res, rc, kept, kept)
+
+    def run_measure_timing(self, steps: int, dt: float, src: np.ndarray, reqs, freqs, treqs, want_iters: bool = True) -> dict:
+        """spicey_run_measure_timing: run_measure_fourier with the edge-timing pass behind the other two, over the same device
+        waveforms.  reqs: records of abi.MEAS_REQ_DTYPE (may be empty), freqs: records of abi.FOUR_REQ_DTYPE (may be empty),
+        treqs: records of abi.TIMING_REQ_DTYPE (at least one).  Beside what run_measure_fourier returns: `timing`
+        [n_inst][n_timing][8] = {k_trig, t_trig, L_trig, k_targ, t_targ, L_targ, n_trig, n_targ} (include/spicey_hip.h) and
+        `timing_ms`."""
+        f = self.flat
+        src = np.ascontiguousarray(src, dtype=np.float64)
+        per_inst = _src_layout(src, f, steps)
+        r, fr, tr = _reqs(reqs), _four_reqs(freqs), _timing_reqs(treqs)
+        stride = fourier_row_doubles(fr)
+        meas = np.zeros((f.n_inst, len(r), 8))
+        four = np.zeros((f.n_inst, len(fr), stride))
+        timing = np.zeros((f.n_inst, len(tr), 8))
+        iters = np.zeros((f.n_inst, steps + 1), np.int32) if want_iters else None
+        rc = self.L.spicey_run_measure_timing(self.h, steps, dt, _p(src, C.c_double), 1 if per_inst else 0, _reqs_ptr(r), len(r),
+                                              _p(meas, C.c_double) if len(r) else None, _reqs_ptr(fr), len(fr),
+                                              _p(four, C.c_double) if len(fr) else None, stride, _reqs_ptr(tr), len(tr), _p(timing, C.c_double),
+                                              _p(iters, C.c_int32))
+        res = {"status": rc, "detail": self.error() if rc != abi.OK else "", "meas": meas, "four": four, "timing": timing, "iters": iters,
+               "partial": True}
+        kept = rc in (abi.OK, abi.ERR_SINGULAR)
+        if kept:
+            res["measure_ms"] = self.L.spicey_last_measure_ms(self.h)
+            res["fourier_ms"] = self.L.spicey_last_fourier_ms(self.h)
+            res["timing_ms"] = self.L.spicey_last_timing_ms(self.h)
         return self._dress(res, rc, kept, kept)
 
     def run_device(self, steps: int, dt: float, d_src: int, d_out_v: int, d_out_i: int = 0, d_iters: int = 0, stream: int = 0,
@@ -669,6 +725,10 @@ class HipBackend(_AcCalls):
     def run_measure_fourier(self, flat: abi.FlatCircuit, steps: int, dt: float, src: np.ndarray, reqs, freqs, want_iters: bool = True) -> dict:
         """Handle.run_measure_fourier on a handle of its own: the waveforms never leave the device."""
         return self._on_handle(flat, lambda h: h.run_measure_fourier(steps, dt, src, reqs, freqs, want_iters))
+
+    def run_measure_timing(self, flat: abi.FlatCircuit, steps: int, dt: float, src: np.ndarray, reqs, freqs, treqs, want_iters: bool = True) -> dict:
+        """Handle.run_measure_timing on a handle of its own: the waveforms never leave the device."""
+        return self._on_handle(flat, lambda h: h.run_measure_timing(steps, dt, src, reqs, freqs, treqs, want_iters))
 
 
 class HipAcExactBackend(_AcCalls):

@@ -38,9 +38,29 @@ others); that is reported by this number and not refused.  ValueError for a wind
 or is more than half a step shorter than one period, for harmonics outside 1..16 or above Nyquist (harmonics f0 > 1 / (2
 dt)), and for periods= together with t_from=.  A dict without a fourier spec takes the path it always took.
 
+Edge timing.  A third family, reduced on the device by a pass of its own (spicey_run_measure_timing, behind the other two
+over the same waveforms; include/spicey_hip.h has the definition):
+    when("v(out)", 2.5, dir="rise", n=1)                         t, level, count
+    delay(trig=edge("v(g)", rel(0.5)), targ=edge("v(sw)", rel(0.5)))   t_trig, t_targ, delay, level_trig, level_targ,
+                                                                 count_trig, count_targ
+    rise_time("v(out)", lo=0.1, hi=0.9) / fall_time(...)         t_start, t_end, time, level_start, level_end
+    settle("v(out)", tol=0.02)                                   t, level_lo, level_hi
+A level is a number or rel(frac, of="minmax" | "ends", t_from=None, t_to=None): lo + frac * (hi - lo) with (lo, hi) the
+signal's (min, max) or (first, last) sample over the base window (default: the whole run) of EACH circuit — a batch of
+supply-scaled variants stays one launch.  n >= 1 is the n-th crossing of the window, n <= -1 the |n|-th from its end; dir
+is "rise", "fall" or "either"; crossings and their interpolated times are cross()'s.  delay() searches the trig in the
+window [t_from, t_to] and the targ from the trigger's own interval on (after_trig=True; a targ crossing in that interval
+counts even if its interpolated time is a fraction of a step earlier, so the delay of two edges inside one step may be
+slightly negative) or, with after_trig=False, in the whole window like SPICE's .meas trig/targ — a period is delay(trig=
+edge(s, L, n=1), targ=edge(s, L, n=2), after_trig=False); with after_trig=True the same edge as trig and targ with n=1
+finds the trigger's own crossing.  t / delay / time are None when an edge is not found; count is the number of crossings
+in the edge's search range.  rise_time is the delay from the first rise through rel(lo) to the first rise through rel(hi)
+at or after it (fall_time: falls through hi, then lo); settle is the later of the last crossings (either direction) of
+rel(1 - tol, of="ends") and rel(1 + tol, of="ends"), 0.0 if the signal never leaves that band.  A window needs two steps.
+
 reduce_reference() is the same definition in plain numpy; it is what the tests compare the device with, and what runs
 behind a backend that has no run_measure (backend.run, then reduce_reference: the CPU oracle works unchanged);
-reduce_reference_fourier() is the same for the harmonics.
+reduce_reference_fourier() is the same for the harmonics, reduce_reference_timing() for the edge timing.
 """
 from __future__ import annotations
 
@@ -83,6 +103,134 @@ class Fourier:
     t_from: Optional[float] = None
     t_to: Optional[float] = None
     periods: Optional[int] = None
+
+
+_OF = {"minmax": abi.TIMING_MINMAX, "ends": abi.TIMING_ENDS}
+
+
+@dataclass(frozen=True)
+class Rel:
+    frac: float
+    of: int = abi.TIMING_MINMAX
+    t_from: Optional[float] = None
+    t_to: Optional[float] = None
+
+
+@dataclass(frozen=True)
+class Edge:
+    signal: str
+    level: object  # a float or a Rel
+    dir: int = 1
+    n: int = 1
+
+
+@dataclass(frozen=True)
+class When:
+    edge: Edge
+    t_from: Optional[float] = None
+    t_to: Optional[float] = None
+
+    def requests(self):
+        return [(None, self.edge, False)]
+
+
+@dataclass(frozen=True)
+class Delay:
+    trig: Edge
+    targ: Edge
+    after_trig: bool = True
+    t_from: Optional[float] = None
+    t_to: Optional[float] = None
+
+    def requests(self):
+        return [(self.trig, self.targ, self.after_trig)]
+
+
+@dataclass(frozen=True)
+class Transition:
+    """rise_time / fall_time: from the first crossing of `start` to the first crossing of `end` at or after it."""
+    start: Edge
+    end: Edge
+    t_from: Optional[float] = None
+    t_to: Optional[float] = None
+
+    def requests(self):
+        return [(self.start, self.end, True)]
+
+
+@dataclass(frozen=True)
+class Settle:
+    lo: Edge
+    hi: Edge
+    t_from: Optional[float] = None
+    t_to: Optional[float] = None
+
+    def requests(self):
+        return [(None, self.lo, False), (None, self.hi, False)]
+
+
+_TIMING = (When, Delay, Transition, Settle)
+
+
+def rel(frac: float, of: str = "minmax", t_from: Optional[float] = None, t_to: Optional[float] = None) -> Rel:
+    """A level relative to the signal's own swing in each circuit: lo + frac * (hi - lo), (lo, hi) = (min, max) for
+    of="minmax", (first, last) for of="ends", over the base window [t_from, t_to] (default: the whole run)."""
+    if of not in _OF:
+        raise ValueError(f"rel: of must be 'minmax' or 'ends', got {of!r}")
+    frac = float(frac)
+    if not math.isfinite(frac):
+        raise ValueError(f"rel: the fraction must be finite, got {frac!r}")
+    return Rel(frac, _OF[of], t_from, t_to)
+
+
+def edge(signal: str, level, dir="rise", n: int = 1) -> Edge:
+    """The n-th crossing (n <= -1: the |n|-th from the end) of `level` (a number or rel(...)) by `signal`."""
+    if dir not in _DIRS:
+        raise ValueError(f"edge: dir must be 'rise', 'fall' or 'either', got {dir!r}")
+    if isinstance(n, bool) or int(n) != n or int(n) == 0:
+        raise ValueError(f"edge: n must be a nonzero integer, got {n!r}")
+    if not isinstance(level, Rel):
+        level = float(level)
+        if not math.isfinite(level):
+            raise ValueError(f"edge: the level must be finite, got {level!r}")
+    return Edge(str(signal), level, _DIRS[dir], int(n))
+
+
+def when(signal: str, level, dir="rise", n: int = 1, t_from: Optional[float] = None, t_to: Optional[float] = None) -> When:
+    return When(edge(signal, level, dir, n), t_from, t_to)
+
+
+def delay(trig: Edge, targ: Edge, after_trig: bool = True, t_from: Optional[float] = None, t_to: Optional[float] = None) -> Delay:
+    if not isinstance(trig, Edge) or not isinstance(targ, Edge):
+        raise TypeError("delay: trig and targ must be edge(...)")
+    return Delay(trig, targ, bool(after_trig), t_from, t_to)
+
+
+def rise_time(signal: str, lo: float = 0.1, hi: float = 0.9, of: str = "minmax", t_from: Optional[float] = None, t_to: Optional[float] = None) -> Transition:
+    return Transition(edge(signal, rel(lo, of), "rise"), edge(signal, rel(hi, of), "rise"), t_from, t_to)
+
+
+def fall_time(signal: str, lo: float = 0.1, hi: float = 0.9, of: str = "minmax", t_from: Optional[float] = None, t_to: Optional[float] = None) -> Transition:
+    return Transition(edge(signal, rel(hi, of), "fall"), edge(signal, rel(lo, of), "fall"), t_from, t_to)
+
+
+def settle(signal: str, tol: float = 0.02, t_from: Optional[float] = None, t_to: Optional[float] = None) -> Settle:
+    tol = float(tol)
+    if not (math.isfinite(tol) and tol > 0):
+        raise ValueError(f"settle: tol must be finite and > 0, got {tol!r}")
+    return Settle(edge(signal, rel(1.0 - tol, "ends"), "either", -1), edge(signal, rel(1.0 + tol, "ends"), "either", -1), t_from, t_to)
+
+
+_NO_EDGE = (0, 0, -1, 1, 1, 0, 0, 0, 0.0)
+
+
+def make_timing_reqs(rows: Sequence[tuple]) -> np.ndarray:
+    """Request records (abi.TIMING_REQ_DTYPE) from tuples (step_from, step_to, trig, targ, targ_from_trig) with trig (None:
+    has_trig = 0) and targ tuples (signal, col, col_ref, dir, n, level_kind, base_from, base_to, level)."""
+    a = np.zeros(len(rows), abi.TIMING_REQ_DTYPE)
+    for k, (s0, s1, trig, targ, from_trig) in enumerate(rows):
+        a[k] = (s0, s1, 0 if trig is None else 1, int(from_trig), tuple(_NO_EDGE if trig is None else trig), tuple(targ))
+    return a
 
 
 def stats(signal: str, t_from: Optional[float] = None, t_to: Optional[float] = None) -> Stats:
@@ -196,34 +344,66 @@ class _Plan:
             raise ValueError("measure: no measures given")
         parsed = []
         for name, spec in measures.items():
+            if isinstance(spec, _TIMING):
+                # (every edge of the spec's requests, resolved: a list in the place of the one signal)
+                parsed.append((name, spec, [tuple(None if e is None else _parse_signal(ckt, e.signal) for e in rq[:2]) for rq in spec.requests()]))
+                continue
             if not isinstance(spec, (Stats, Cross, Fourier)):
-                raise TypeError(f"measure {name!r}: expected stats(...), cross(...) or fourier(...), got {type(spec).__name__}")
+                raise TypeError(f"measure {name!r}: expected stats(...), cross(...), fourier(...), when(...), delay(...), rise_time(...), "
+                                f"fall_time(...) or settle(...), got {type(spec).__name__}")
             parsed.append((name, spec, _parse_signal(ckt, spec.signal)))
-        nodes = sorted({n for _, _, (sig, a, b) in parsed if sig == 0 for n in (a, b) if n != 0})
-        self.need_i = any(sig == 1 for _, _, (sig, _, _) in parsed)
+        sigs = [s for _, _, p in parsed for s in ([e for rq in p for e in rq if e is not None] if isinstance(p, list) else [p])]
+        nodes = sorted({n for sig, a, b in sigs if sig == 0 for n in (a, b) if n != 0})
+        self.need_i = any(sig == 1 for sig, _, _ in sigs)
         # (a device descriptor records at least one node; with current measures only, the first one)
         self.out_nodes = nodes if nodes else [1]
         col = {n: c for c, n in enumerate(self.out_nodes)}
-        rows, frows = [], []
-        self.names = []  # (name, is a fourier spec, its place in reqs / freqs), in the dict's order
-        for name, spec, (sig, a, b) in parsed:
-            c, cr = (col[a], col[b] if b else -1) if sig == 0 else (a, -1)
+        rows, frows, trows = [], [], []
+        self.names = []  # (name, "meas" | "four" | the timing spec, its (first) place in reqs / freqs / treqs), in the dict's order
+
+        def columns(sig, a, b):
+            return (col[a], col[b] if b else -1) if sig == 0 else (a, -1)
+
+        def edge_row(name, e: Edge, where):
+            sig = where[0]
+            c, cr = columns(*where)
+            if isinstance(e.level, Rel):
+                b0 = time_to_step(e.level.t_from, dt, steps, 0)
+                b1 = time_to_step(e.level.t_to, dt, steps, steps)
+                if b0 > b1:
+                    raise ValueError(f"measure {name!r}: the base window of rel() is empty (t_from maps to step {b0}, t_to to step {b1})")
+                return (sig, c, cr, e.dir, e.n, e.level.of, b0, b1, e.level.frac)
+            return (sig, c, cr, e.dir, e.n, abi.TIMING_ABS, 0, 0, e.level)
+
+        for name, spec, where in parsed:
+            if isinstance(spec, _TIMING):
+                s0 = time_to_step(spec.t_from, dt, steps, 0)
+                s1 = time_to_step(spec.t_to, dt, steps, steps)
+                if s0 >= s1:
+                    raise ValueError(f"measure {name!r}: the window has no interval (t_from maps to step {s0}, t_to to step {s1})")
+                self.names.append((name, spec, len(trows)))
+                for (trig, targ, from_trig), (w_trig, w_targ) in zip(spec.requests(), where):
+                    trows.append((s0, s1, None if trig is None else edge_row(name, trig, w_trig), edge_row(name, targ, w_targ), from_trig))
+                continue
+            sig, a, b = where
+            c, cr = columns(sig, a, b)
             if isinstance(spec, Fourier):
                 s0, s1 = fourier_window(spec, dt, steps, name)
-                self.names.append((name, True, len(frows)))
+                self.names.append((name, "four", len(frows)))
                 frows.append((sig, c, cr, spec.harmonics, s0, s1, spec.f0))
                 continue
             s0 = time_to_step(spec.t_from, dt, steps, 0)
             s1 = time_to_step(spec.t_to, dt, steps, steps)
             if s0 > s1:
                 raise ValueError(f"measure {name!r}: the window is empty (t_from maps to step {s0}, t_to to step {s1})")
-            self.names.append((name, False, len(rows)))
+            self.names.append((name, "meas", len(rows)))
             if isinstance(spec, Stats):
                 rows.append((abi.MEAS_STATS, sig, c, cr, s0, s1, 0.0, 0))
             else:
                 rows.append((abi.MEAS_CROSS, sig, c, cr, s0, s1, spec.level, spec.dir))
         self.reqs = make_reqs(rows)
         self.freqs = make_four_reqs(frows)  # (empty: the dict takes the path without the harmonics pass)
+        self.treqs = make_timing_reqs(trows)  # (empty: the dict takes the path without the timing pass)
 
     def flatten(self, ckt: ParsedCircuit) -> abi.FlatCircuit:
         flat = abi.flatten(ckt)
@@ -231,18 +411,22 @@ class _Plan:
         return flat
 
     def key(self) -> bytes:
-        """What a batch groups by beside topology and run: both resolved request tables."""
-        return self.reqs.tobytes() + b"|" + self.freqs.tobytes()
+        """What a batch groups by beside topology and run: the resolved request tables."""
+        return self.reqs.tobytes() + b"|" + self.freqs.tobytes() + (b"|" + self.treqs.tobytes() if len(self.treqs) else b"")
 
     def run(self, be, flat: abi.FlatCircuit, steps: int, dt: float, src: np.ndarray) -> dict:
+        if len(self.treqs):
+            return backend_measure_timing(be, flat, steps, dt, src, self.reqs, self.freqs, self.treqs, self.need_i)
         if len(self.freqs):
             return backend_measure_fourier(be, flat, steps, dt, src, self.reqs, self.freqs, self.need_i)
         return backend_measure(be, flat, steps, dt, src, self.reqs, self.need_i)
 
     def values(self, res: dict, j: int, dt: float) -> Dict[str, dict]:
-        """Instance j of a result (meas [n_inst][n_req][8], four [n_inst][n_four][row]) -> {name: {...}}."""
-        return {name: derive_fourier(self.freqs[k], res["four"][j][k], dt) if four else derive(self.reqs[k], res["meas"][j][k], dt)
-                for name, four, k in self.names}
+        """Instance j of a result (meas [n_inst][n_req][8], four [n_inst][n_four][row], timing [n_inst][n_timing][8]) ->
+        {name: {...}}."""
+        return {name: derive(self.reqs[k], res["meas"][j][k], dt) if kind == "meas" else derive_fourier(self.freqs[k], res["four"][j][k], dt)
+                if kind == "four" else derive_timing(kind, res["timing"][j][k:k + len(kind.requests())])
+                for name, kind, k in self.names}
 
 
 def derive(req, m, dt: float) -> dict:
@@ -276,6 +460,123 @@ def derive_fourier(req, row, dt: float) -> dict:
         ph.append(math.degrees(math.atan2(-b, a)))
     thd = math.sqrt(sum(m * m for m in mag[1:])) / mag[0] if H > 1 and mag[0] != 0.0 else None
     return {"f0": f0, "periods": n * dt * f0, "dc": float(row[0]) / n, "mag": mag, "phase_deg": ph, "thd": thd}
+
+
+def derive_timing(spec, rows) -> dict:
+    """The values of one timing spec from the rows {k_trig, t_trig, L_trig, k_targ, t_targ, L_targ, n_trig, n_targ} of its
+    requests (module text)."""
+    def t(row, o):
+        return float(row[o + 1]) if row[o] >= 0 else None
+
+    r = rows[0]
+    if isinstance(spec, When):
+        return {"t": t(r, 3), "level": float(r[5]), "count": int(r[7])}
+    if isinstance(spec, Settle):
+        ts = [v for v in (t(rows[0], 3), t(rows[1], 3)) if v is not None]
+        return {"t": max(ts) if ts else 0.0, "level_lo": float(rows[0][5]), "level_hi": float(rows[1][5])}
+    t0, t1 = t(r, 0), t(r, 3)
+    d = t1 - t0 if t0 is not None and t1 is not None else None
+    if isinstance(spec, Transition):
+        return {"t_start": t0, "t_end": t1, "time": d, "level_start": float(r[2]), "level_end": float(r[5])}
+    return {"t_trig": t0, "t_targ": t1, "delay": d, "level_trig": float(r[2]), "level_targ": float(r[5]), "count_trig": int(r[6]),
+            "count_targ": int(r[7])}
+
+
+def reduce_reference_timing(out_v: np.ndarray, out_i: Optional[np.ndarray], reqs, dt: float) -> np.ndarray:
+    """The definition of spicey_timing_device in numpy, independent of the kernels: out_v [n_inst][n_points][n_v], out_i
+    likewise or None, reqs records of abi.TIMING_REQ_DTYPE (step_to / base_to resolved or -1) -> [n_inst][n_req][8] =
+    {k_trig, t_trig, L_trig, k_targ, t_targ, L_targ, n_trig, n_targ}.  Every crossing of the window at once, no chunks;
+    every field has one value whatever the order."""
+    reqs = np.ascontiguousarray(reqs, dtype=abi.TIMING_REQ_DTYPE).reshape(-1)
+    out_v = np.asarray(out_v, dtype=np.float64)
+    ni, n_points = out_v.shape[0], out_v.shape[1]
+    out = np.zeros((ni, len(reqs), 8))
+
+    def samples(e, r):
+        a = out_i if int(e["signal"]) == 1 else out_v
+        if a is None:
+            raise ValueError("reduce_reference_timing: a request names a current, but there is no out_i")
+        a = np.asarray(a, dtype=np.float64)
+        x = a[:, :, int(e["col"])]
+        return x - a[:, :, int(e["col_ref"])] if int(e["col_ref"]) >= 0 else x
+
+    def level(e, xi, r):
+        kind, frac = int(e["level_kind"]), float(e["level"])
+        if kind == abi.TIMING_ABS:
+            return frac
+        b0 = int(e["base_from"])
+        b1 = n_points - 1 if int(e["base_to"]) == -1 else int(e["base_to"])
+        if not (0 <= b0 <= b1 < n_points):
+            raise ValueError(f"reduce_reference_timing: request {r}: base window [{b0}, {b1}] outside the run")
+        w = xi[b0:b1 + 1].tolist()
+        if kind == abi.TIMING_MINMAX:
+            lo = hi = w[0]
+            for v in w:  # (the comparisons v < lo, v > hi skip a NaN, like the device's)
+                if v < lo:
+                    lo = v
+                if v > hi:
+                    hi = v
+        else:
+            lo, hi = w[0], w[-1]
+        span = hi - lo
+        part = frac * span
+        return lo + part
+
+    def find(e, xi, L, k0, k1):
+        """(k, t, count) of edge e among the crossings in the intervals k0 .. k1 - 1."""
+        xa, xb = xi[k0:k1], xi[k0 + 1:k1 + 1]
+        hit = np.zeros(len(xa), bool)
+        d, n = int(e["dir"]), int(e["n"])
+        if d >= 0:
+            hit |= (xa < L) & (xb >= L)
+        if d <= 0:
+            hit |= (xa > L) & (xb <= L)
+        ks = np.nonzero(hit)[0]
+        m = n - 1 if n >= 1 else len(ks) + n
+        if not 0 <= m < len(ks):
+            return -1.0, -1.0, float(len(ks))
+        k = k0 + int(ks[m])
+        a, b = float(xi[k]), float(xi[k + 1])
+        return float(k), (float(k) + (L - a) / (b - a)) * dt, float(len(ks))
+
+    for r, q in enumerate(reqs):
+        s0 = int(q["step_from"])
+        s1 = n_points - 1 if int(q["step_to"]) == -1 else int(q["step_to"])
+        if not (0 <= s0 < s1 < n_points):
+            raise ValueError(f"reduce_reference_timing: request {r}: window [{s0}, {s1}] outside the run or without an interval")
+        x_targ = samples(q["targ"], r)
+        x_trig = samples(q["trig"], r) if int(q["has_trig"]) else None
+        for i in range(ni):
+            row = [-1.0, -1.0, 0.0, -1.0, -1.0, 0.0, 0.0, 0.0]
+            k0 = s0
+            search = True
+            if x_trig is not None:
+                L = level(q["trig"], x_trig[i], r)
+                row[0], row[1], row[6] = find(q["trig"], x_trig[i], L, s0, s1)
+                row[2] = L
+                if int(q["targ_from_trig"]):
+                    search = row[0] >= 0
+                    k0 = int(row[0])
+            L = level(q["targ"], x_targ[i], r)
+            row[5] = L
+            if search:
+                row[3], row[4], row[7] = find(q["targ"], x_targ[i], L, k0, s1)
+            out[i, r] = row
+    return out
+
+
+def backend_measure_timing(be, flat: abi.FlatCircuit, steps: int, dt: float, src: np.ndarray, reqs: np.ndarray, freqs: np.ndarray, treqs: np.ndarray,
+                           need_i: bool) -> dict:
+    """The backend's run_measure_timing, or for a backend without one its run followed by the numpy reductions."""
+    if hasattr(be, "run_measure_timing"):
+        return be.run_measure_timing(flat, steps, dt, src, reqs, freqs, treqs)
+    res = be.run(flat, steps, dt, src, want_currents=need_i)
+    if res["status"] == abi.OK or (res["status"] == abi.ERR_SINGULAR and res.get("partial")):
+        ni = res["out_v"].shape[0]
+        res["meas"] = reduce_reference(res["out_v"], res.get("out_i"), reqs, dt) if len(reqs) else np.zeros((ni, 0, 8))
+        res["four"] = reduce_reference_fourier(res["out_v"], res.get("out_i"), freqs, dt) if len(freqs) else np.zeros((ni, 0, 1))
+        res["timing"] = reduce_reference_timing(res["out_v"], res.get("out_i"), treqs, dt)
+    return res
 
 
 def reduce_reference(out_v: np.ndarray, out_i: Optional[np.ndarray], reqs, dt: float) -> np.ndarray:
@@ -409,7 +710,7 @@ def _backend(backend, exact_order: bool, device: int, diagnostics: bool, who: st
 
 
 def measureTRAN(ckt: ParsedCircuit, measures: Dict[str, object], *, exact_order: bool = False, device: int = 0, backend=None) -> Optional[dict]:
-    """The transient of `ckt` reduced to {name: {...}} for measures = {name: stats(...) | cross(...) | fourier(...)} (module text).  None
+    """The transient of `ckt` reduced to {name: {...}} for measures = {name: stats(...) | cross(...) | fourier(...) | when(...) | delay(...) | ...} (module text).  None
     without a .tran card; SingularMatrixError and the circuit's state write-back exactly as simulateTRAN; exact_order=True
     runs the reference-order engine."""
     be = _backend(backend, exact_order, device, True, "measureTRAN")

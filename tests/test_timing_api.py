@@ -1,0 +1,280 @@
+"""when() / delay() / rise_time() / fall_time() / settle() through measureTRAN / measureTRANBatch on the CPU: the oracle is
+a backend without run_measure_timing, so the waveforms come from backend.run and the rows from reduce_reference_timing.
+Every returned value is recomputed here, in plain Python, from the recorded waveforms of tests/golden and compared with
+==; nothing is hard-coded."""
+import numpy as np
+import pytest
+
+from batch_variants import PerInstanceOracle, variant
+from conftest import farr, golden_netlist, load_golden
+from spicey_amd import abi
+from spicey_amd import measure as M
+from spicey_amd.measure import (cross, delay, edge, fall_time, fourier, measureTRAN, measureTRANBatch, rel, rise_time, settle, stats, time_to_step,
+                                when)
+from spicey_amd.netlist import parseNetlist
+from spicey_amd.simulate import SingularMatrixError, simulateTRAN
+
+
+class _Oracle(PerInstanceOracle):
+    """The per-instance oracle (it always computes the currents, and hands them out only when asked)."""
+
+    def run(self, flat, steps, dt, src, want_currents=True, want_iters=True):
+        res = super().run(flat, steps, dt, src, True, want_iters)
+        if not want_currents:
+            res["out_i"] = None
+        return res
+
+
+def _golden(name):
+    g = load_golden(name)
+    text = golden_netlist(g)
+    ckt = parseNetlist(text)
+    dt, steps = abi.computeEffectiveTimeStep(ckt.analyses["tran"]["dt"], ckt.analyses["tran"]["tstop"])
+    run = g["runs"][0]
+    return text, dt, steps, {k: farr(v).tolist() for k, v in run["V"].items()}, {k: farr(v).tolist() for k, v in run["I"].items()}
+
+
+def _state(ckt):
+    return ([c.vPrev for c in ckt.C], [l.iPrev for l in ckt.L], [d.vdPrev for d in ckt.D], [s.isOn for s in ckt.S])
+
+
+# the definition once more, in plain Python on a list of samples
+def _level(x, frac, of="minmax", b0=0, b1=None):
+    w = x[b0:len(x) if b1 is None else b1 + 1]
+    lo, hi = (min(w), max(w)) if of == "minmax" else (w[0], w[-1])
+    return lo + frac * (hi - lo)
+
+
+def _crossings(x, L, d, dt, s0=0, s1=None):
+    """[(k, t)] of the window's intervals s0 .. s1 - 1, d = +1 rises, -1 falls, 0 both."""
+    s1 = len(x) - 1 if s1 is None else s1
+    return [(k, (float(k) + (L - x[k]) / (x[k + 1] - x[k])) * dt) for k in range(s0, s1)
+            if (d >= 0 and x[k] < L <= x[k + 1]) or (d <= 0 and x[k] > L >= x[k + 1])]
+
+
+def _pick(c, n):
+    m = n - 1 if n >= 1 else len(c) + n
+    return c[m] if 0 <= m < len(c) else None
+
+
+def _delay(xa, La, da, na, xb, Lb, db, nb, dt, after=True, s0=0, s1=None):
+    ca = _crossings(xa, La, da, dt, s0, s1)
+    a = _pick(ca, na)
+    cb = _crossings(xb, Lb, db, dt, s0, s1)
+    if after:
+        cb = [c for c in cb if a is not None and c[0] >= a[0]]
+    b = _pick(cb, nb)
+    return {"t_trig": a[1] if a else None, "t_targ": b[1] if b else None, "delay": b[1] - a[1] if a and b else None, "level_trig": La,
+            "level_targ": Lb, "count_trig": len(ca), "count_targ": len(cb)}, a, b
+
+
+def test_half_bridge_gate_to_switch_node_delays(oracle_backend):
+    text, dt, steps, V, _ = _golden("half_bridge")
+    Lg, Ls = _level(V["g1"], 0.5), _level(V["sw"], 0.5)
+    m = {f"{d}{n}": delay(trig=edge("v(g1)", rel(0.5), d, n), targ=edge("v(sw)", rel(0.5), d)) for d in ("rise", "fall") for n in range(1, 7)}
+    got = measureTRAN(parseNetlist(text), m, backend=oracle_backend)
+    assert list(got) == list(m)
+    same_interval_and_earlier = []
+    for d, sgn in (("rise", 1), ("fall", -1)):
+        for n in range(1, 7):
+            want, a, b = _delay(V["g1"], Lg, sgn, n, V["sw"], Ls, sgn, 1, dt)
+            assert a is not None and b is not None and got[f"{d}{n}"] == want, (d, n, got[f"{d}{n}"], want)
+            assert b[0] == a[0]  # (the sw edge follows within the same step)
+            if b[1] < a[1]:
+                same_interval_and_earlier.append((d, n))
+    assert ("fall", 2) in same_interval_and_earlier and got["fall2"]["delay"] < 0  # (selected by interval, not by interpolated time)
+    assert got["rise1"]["count_trig"] == got["fall1"]["count_trig"] == 6
+    # the supply: flat to the last bits, and every jitter crossing of its own mid-level is reproduced
+    w = measureTRAN(parseNetlist(text), {"w": when("v(vin)", rel(0.5), dir="either", n=-1), "s": stats("v(vin)")}, backend=oracle_backend)
+    c = _crossings(V["vin"], _level(V["vin"], 0.5), 0, dt)
+    assert w["w"] == {"t": c[-1][1], "level": _level(V["vin"], 0.5), "count": len(c)} and len(c) >= 2 and w["s"]["pp"] < 1e-12
+    r = measureTRAN(parseNetlist(text), {"w": when("v(vin)", rel(0.5), n=-1)}, backend=oracle_backend)["w"]
+    cr = _crossings(V["vin"], _level(V["vin"], 0.5), 1, dt)
+    assert r == {"t": cr[-1][1], "level": _level(V["vin"], 0.5), "count": len(cr)} and len(cr) >= 2
+    print("half_bridge v(vin): jitter crossings at rel(0.5):", len(cr), "rises,", len(c), "in either direction")
+
+
+def test_switch_vt_vh_coincident_pairs(oracle_backend):
+    text, dt, steps, V, _ = _golden("switch_vt_vh")
+    xc, xo = V["NCTRL_SW1"], V["N2"]
+    m = {f"p{n}": delay(trig=edge("v(nctrl_sw1)", rel(0.5), n=n), targ=edge("v(n2)", rel(0.5))) for n in range(1, 5)}
+    got = measureTRAN(parseNetlist(text), m, backend=oracle_backend)
+    for n in range(1, 5):
+        want, a, b = _delay(xc, _level(xc, 0.5), 1, n, xo, _level(xo, 0.5), 1, 1, dt)
+        assert got[f"p{n}"] == want and a[0] == b[0] and abs(want["delay"]) < dt, n
+
+
+def test_boost_probe_rise_time_and_settle(oracle_backend):
+    text, dt, steps, V, _ = _golden("boost_probe")
+    x = V["N3"]
+    got = measureTRAN(parseNetlist(text), {"r": rise_time("v(N3)"), "s": settle("v(N3)"), "f": fall_time("v(n3)"), "r2": rise_time("v(n3)", 0.2, 0.8, of="ends")},
+                      backend=oracle_backend)
+    for key, lo, hi, of in (("r", 0.1, 0.9, "minmax"), ("r2", 0.2, 0.8, "ends")):
+        want, a, b = _delay(x, _level(x, lo, of), 1, 1, x, _level(x, hi, of), 1, 1, dt)
+        assert got[key] == {"t_start": want["t_trig"], "t_end": want["t_targ"], "time": want["delay"], "level_start": want["level_trig"],
+                            "level_end": want["level_targ"]} and want["delay"] > dt, key
+    want, a, b = _delay(x, _level(x, 0.9), -1, 1, x, _level(x, 0.1), -1, 1, dt)
+    assert got["f"]["t_start"] == want["t_trig"] and got["f"]["t_end"] == want["t_targ"] and got["f"]["time"] == want["delay"]
+    lo, hi = _level(x, 1.0 - 0.02, "ends"), _level(x, 1.0 + 0.02, "ends")
+    last = [_pick(_crossings(x, L, 0, dt), -1) for L in (lo, hi)]
+    assert got["s"] == {"t": max(c[1] for c in last if c), "level_lo": lo, "level_hi": hi} and got["s"]["t"] > 0.0
+    print("boost_probe v(N3): 10 % / 90 % at steps", got["r"]["t_start"] / dt, got["r"]["t_end"] / dt, "settled at step", got["s"]["t"] / dt)
+    # a signal that never leaves the band has settled at 0
+    flat = measureTRAN(parseNetlist(text), {"s": settle("v(n1)")}, backend=oracle_backend)["s"]
+    assert flat["t"] == 0.0 and flat["level_lo"] == flat["level_hi"] == V["N1"][0]
+
+
+def test_diode_switch_period_and_lc_tank(oracle_backend):
+    text, dt, steps, V, _ = _golden("diode_switch")
+    x = V["N4"]
+    L = _level(x, 0.5)
+    got = measureTRAN(parseNetlist(text), {"T": delay(trig=edge("v(N4)", rel(0.5), n=1), targ=edge("v(N4)", rel(0.5), n=2), after_trig=False),
+                                           "own": delay(trig=edge("v(N4)", rel(0.5)), targ=edge("v(N4)", rel(0.5))),
+                                           "pw": delay(trig=edge("v(N4)", rel(0.5)), targ=edge("v(N4)", rel(0.5), "fall"))}, backend=oracle_backend)
+    want, _, _ = _delay(x, L, 1, 1, x, L, 1, 2, dt, after=False)
+    assert got["T"] == want and want["delay"] == pytest.approx(1e-3, rel=1e-3)
+    assert got["own"]["delay"] == 0.0 and got["own"]["t_targ"] == got["own"]["t_trig"]  # (from the trigger on, n = 1 is its own crossing)
+    assert got["pw"] == _delay(x, L, 1, 1, x, L, -1, 1, dt)[0] and got["pw"]["delay"] == pytest.approx(0.68e-3, rel=1e-2)
+    text, dt, steps, V, I = _golden("lc_tank")
+    m = {"c2": when("v(c)", rel(0.5), n=2), "bc": delay(trig=edge("v(b,a)", 1.0), targ=edge("v(c)", rel(0.25, of="ends"), "either", -1)),
+         "il": when("i(L1)", 0.0, dir="fall"), "d": when("v(c,d)", rel(0.75, t_from=50e-6, t_to=150e-6), "either", -1, t_from=20e-6), "none": when("v(a)", 5.0)}
+    got = measureTRAN(parseNetlist(text), m, backend=oracle_backend)
+    c = _crossings(V["c"], _level(V["c"], 0.5), 1, dt)
+    assert got["c2"] == {"t": c[1][1], "level": _level(V["c"], 0.5), "count": len(c)}
+    ba = [p - q for p, q in zip(V["b"], V["a"])]
+    assert got["bc"] == _delay(ba, 1.0, 1, 1, V["c"], _level(V["c"], 0.25, "ends"), 0, -1, dt)[0] and got["bc"]["delay"] is not None
+    ci = _crossings(I["L1"], 0.0, -1, dt)
+    assert got["il"] == {"t": ci[0][1] if ci else None, "level": 0.0, "count": len(ci)}
+    cd = [p - q for p, q in zip(V["c"], V["d"])]
+    Ld = _level(cd, 0.75, "minmax", 50, 150)
+    cc = _crossings(cd, Ld, 0, dt, 20)
+    assert got["d"] == {"t": cc[-1][1], "level": Ld, "count": len(cc)}
+    assert got["none"] == {"t": None, "level": 5.0, "count": 0}
+
+
+def test_name_resolution_windows_and_host_errors(oracle_backend):
+    text, dt, steps, V, _ = _golden("lc_tank")
+    x = V["c"]
+    # the window rule is time_to_step's: the nearest step, ties to the later one, clamped to the run
+    for t0, t1 in ((20.5e-6, 120.49e-6), (None, 90e-6), (33e-6, None), (-1.0, 1.0)):
+        s0, s1 = time_to_step(t0, dt, steps, 0), time_to_step(t1, dt, steps, steps)
+        got = measureTRAN(parseNetlist(text), {"w": when("V(C)", rel(0.5, "minmax", t0, t1), "either", -1, t_from=t0, t_to=t1)}, backend=oracle_backend)["w"]
+        L = _level(x, 0.5, "minmax", s0, s1)
+        c = _crossings(x, L, 0, dt, s0, s1)
+        assert got == {"t": c[-1][1] if c else None, "level": L, "count": len(c)}, (t0, t1)
+    for spec in (when("v(nope)", 1.0), when("i(nope)", 1.0), when("v(0)", 1.0), delay(trig=edge("v(c)", 1.0), targ=edge("v(zz)", 1.0)),
+                 when("v(c)", 1.0, t_from=50e-6, t_to=50e-6), when("v(c)", 1.0, t_from=60e-6, t_to=40e-6), when("v(c)", rel(0.5, t_from=60e-6, t_to=40e-6)),
+                 rise_time("v(c)", t_from=300e-6)):
+        with pytest.raises(ValueError):
+            measureTRAN(parseNetlist(text), {"x": spec}, backend=oracle_backend)
+    for bad in (lambda: edge("v(c)", 1.0, "up"), lambda: edge("v(c)", 1.0, n=0), lambda: edge("v(c)", 1.0, n=1.5), lambda: edge("v(c)", float("nan")),
+                lambda: rel(float("inf")), lambda: rel(0.5, of="span"), lambda: when("v(c)", 1.0, n=0), lambda: settle("v(c)", tol=0.0)):
+        with pytest.raises(ValueError):
+            bad()
+    with pytest.raises(TypeError):
+        delay(trig=("v(c)", 1.0), targ=edge("v(c)", 1.0))
+    with pytest.raises(TypeError):
+        measureTRAN(parseNetlist(text), {"x": edge("v(c)", 1.0)}, backend=oracle_backend)  # (an edge alone is no measure)
+    # a fraction beyond the swing is a level like any other
+    got = measureTRAN(parseNetlist(text), {"x": when("v(c)", rel(1.02, "ends"), "either")}, backend=oracle_backend)["x"]
+    assert got["level"] == _level(x, 1.02, "ends") and got["count"] == len(_crossings(x, got["level"], 0, dt))
+
+
+def test_state_write_back_equals_simulateTRAN(oracle_backend):
+    for name, spec in (("half_bridge", delay(trig=edge("v(g1)", rel(0.5)), targ=edge("v(sw)", rel(0.5)))), ("boost_probe", rise_time("v(n3)"))):
+        text = golden_netlist(load_golden(name))
+        a, b = parseNetlist(text), parseNetlist(text)
+        for rnd in range(2):  # the second call continues from the state the first one wrote
+            simulateTRAN(a, backend=oracle_backend)
+            measureTRAN(b, {"t": spec}, backend=oracle_backend)
+            assert _state(a) == _state(b), (name, rnd)
+
+
+ALL_FOUR = {"d": delay(trig=edge("v(g1)", rel(0.5)), targ=edge("v(sw)", rel(0.5))), "pp": stats("v(out)"), "r": rise_time("v(out)", 0.1, 0.5, t_to=100e-6),
+            "x": cross("v(sw)", 6.0, dir="fall"), "h": fourier("v(out)", 20e3, harmonics=3, periods=2), "s": settle("v(out)", tol=0.05),
+            "il": when("i(L1)", rel(0.5), "either"), "pw": delay(trig=edge("v(sw)", rel(0.5)), targ=edge("v(sw)", rel(0.5), "fall"), t_from=40e-6)}
+
+
+def test_batch_slots_equal_solo_calls_and_supply_scaled_variants_stay_one_group():
+    text = golden_netlist(load_golden("half_bridge"))
+    texts = [variant(text, k, values=False) for k in range(4)]  # the supply and the gate amplitude scaled; relative levels follow
+    texts.insert(2, "* no transient\nV1 in 0 DC 1\nR1 in out 1k\n.end\n")
+    batch, solo = [parseNetlist(t) for t in texts], [parseNetlist(t) for t in texts]
+    be = _Oracle()
+    for rnd in range(2):
+        got = measureTRANBatch(batch, ALL_FOUR, backend=be)
+        assert got[2] is None
+        for i, (g, c) in enumerate(zip(got, solo)):
+            if i != 2:
+                assert list(g) == list(ALL_FOUR) and g == measureTRAN(c, ALL_FOUR, backend=_Oracle()), (rnd, i)
+                assert _state(batch[i]) == _state(c), (rnd, i)
+    assert [n for n, _ in be.launches] == [4, 4]  # one launch per call: every variant has another level, none another group
+    assert len({got[i]["d"]["level_targ"] for i in (0, 1, 3, 4)}) == 4 and got[0]["d"]["delay"] is not None
+    # an ABSOLUTE level is part of the request table: circuits that differ in it do not share a launch
+    be = _Oracle()
+    measureTRANBatch([parseNetlist(texts[0]), parseNetlist(texts[0].replace(".tran 1u 300u", ".tran 1u 280u"))], {"w": when("v(sw)", 6.0)}, backend=be)
+    assert [n for n, _ in be.launches] == [1, 1]
+
+
+def test_a_singular_circuit_in_its_slot():
+    nsb = golden_netlist(load_golden("near_sing_b"))  # an island grounded through 1e16 ohm: singular; through 1k or 2k: not
+    isl = [nsb.replace("1e16", "1k"), nsb, nsb.replace("1e16", "2k")]
+    m = {"s": stats("v(a)"), "w": when("v(a)", rel(0.5), "either"), "d": delay(trig=edge("v(a)", 0.5), targ=edge("v(x)", rel(0.5, "ends"), "either"))}
+    ck = [parseNetlist(t) for t in isl]
+    before = _state(ck[1])
+    be = _Oracle()
+    got = measureTRANBatch(ck, m, backend=be)
+    assert be.launches[0][0] == 3
+    assert isinstance(got[1], SingularMatrixError) and str(got[1]) == "Singular matrix (real)" and _state(ck[1]) == before
+    for i in (0, 2):
+        assert got[i] == measureTRAN(parseNetlist(isl[i]), m, backend=_Oracle()) and set(got[i]["w"]) == {"t", "level", "count"}
+    with pytest.raises(SingularMatrixError):
+        measureTRAN(parseNetlist(nsb), m, backend=_Oracle())
+
+
+class _Spy:
+    """A backend with every run_measure* method (each the numpy reduction of the oracle's run) that notes which was called."""
+
+    def __init__(self):
+        self.be, self.calls = _Oracle(), []
+
+    def _reduced(self, which, flat, steps, dt, src, reqs, freqs, treqs):
+        self.calls.append(which)
+        need_i = any((r["signal"] == 1).any() for r in (reqs, freqs) if len(r)) or (len(treqs) and bool(((treqs["targ"]["signal"] == 1) | ((treqs["trig"]["signal"] == 1) & (treqs["has_trig"] == 1))).any()))
+        return M.backend_measure_timing(self.be, flat, steps, dt, src, reqs, freqs, treqs, need_i) if len(treqs) else \
+            M.backend_measure_fourier(self.be, flat, steps, dt, src, reqs, freqs, need_i) if len(freqs) else M.backend_measure(self.be, flat, steps, dt, src, reqs, need_i)
+
+    def run_measure(self, flat, steps, dt, src, reqs):
+        return self._reduced("run_measure", flat, steps, dt, src, reqs, M.make_four_reqs([]), M.make_timing_reqs([]))
+
+    def run_measure_fourier(self, flat, steps, dt, src, reqs, freqs):
+        return self._reduced("run_measure_fourier", flat, steps, dt, src, reqs, freqs, M.make_timing_reqs([]))
+
+    def run_measure_timing(self, flat, steps, dt, src, reqs, freqs, treqs):
+        return self._reduced("run_measure_timing", flat, steps, dt, src, reqs, freqs, treqs)
+
+
+def test_a_dict_of_all_four_kinds_and_the_paths_of_the_others(oracle_backend):
+    text = golden_netlist(load_golden("half_bridge"))
+    full = measureTRAN(parseNetlist(text), ALL_FOUR, backend=oracle_backend)
+    assert list(full) == list(ALL_FOUR) and full["d"]["delay"] is not None and full["il"]["t"] is not None and full["pw"]["delay"] > 0
+    # each entry is what the dict without the others gives
+    for keys in (("pp", "x"), ("pp", "h"), ("d",), ("s", "r"), ("h", "il")):
+        part = measureTRAN(parseNetlist(text), {k: ALL_FOUR[k] for k in keys}, backend=oracle_backend)
+        assert all(part[k] == full[k] for k in keys), keys
+    # which backend method runs: a dict without a timing spec takes exactly the path it took
+    for keys, call in ((("pp", "x"), "run_measure"), (("pp", "h"), "run_measure_fourier"), (("h",), "run_measure_fourier"), (("pp", "d"), "run_measure_timing"),
+                       (("s",), "run_measure_timing"), (tuple(ALL_FOUR), "run_measure_timing")):
+        spy = _Spy()
+        got = measureTRAN(parseNetlist(text), {k: ALL_FOUR[k] for k in keys}, backend=spy)
+        assert spy.calls == [call] and all(got[k] == full[k] for k in keys), keys
+    spy = _Spy()
+    measureTRANBatch([parseNetlist(variant(text, k, values=False)) for k in range(3)], {"pp": ALL_FOUR["pp"], "h": ALL_FOUR["h"]}, backend=spy)
+    assert spy.calls == ["run_measure_fourier"]
+    # the plan's key: unchanged without a timing spec, and the timing table is part of it with one
+    ckt = parseNetlist(text)
+    p0 = M._Plan(ckt, {"pp": ALL_FOUR["pp"], "h": ALL_FOUR["h"]}, 1e-6, 300)
+    p1 = M._Plan(ckt, {"pp": ALL_FOUR["pp"], "h": ALL_FOUR["h"], "d": ALL_FOUR["d"]}, 1e-6, 300)
+    p2 = M._Plan(ckt, {"pp": ALL_FOUR["pp"], "h": ALL_FOUR["h"], "d": ALL_FOUR["pw"]}, 1e-6, 300)
+    assert p0.key() == p0.reqs.tobytes() + b"|" + p0.freqs.tobytes() and len(p0.treqs) == 0
+    assert p1.key() != p2.key() and p1.key().endswith(b"|" + p1.treqs.tobytes()) and len(p1.treqs) == 1 and p1.treqs.dtype == abi.TIMING_REQ_DTYPE
