@@ -407,18 +407,19 @@ extern "C" int32_t spicey_ac_run_measure(SpiceyAcHandle *h, int64_t n_freq, cons
   const int32_t rc = ac_sweep(h, n_freq, freqs, vph, meas != nullptr, need_i, o, &done);
   if (rc != SPICEY_OK || done) return rc;
   hipStream_t st = h->q.stream;
-  HIPCHK(h, h->q.want_measure_events());
+  HIPCHK(h, h->q.want_pass_events(PASS_MEASURE));
+  const hipEvent_t *ev = h->q.pass_ev[PASS_MEASURE];
   DevBuf<double> d_meas;
   DevBuf<uint8_t> d_work;
   const size_t n_meas = (size_t)d.n_inst * (size_t)n_req * 8;
   HIPCHK(h, d_meas.alloc(n_meas));
   HIPCHK(h, d_work.alloc((size_t)work_bytes));
-  HIPCHK(h, hipEventRecord(h->q.mev0, st));
+  HIPCHK(h, hipEventRecord(ev[0], st));
   HIPCHK(h, spicey_launch_ac_measure(h->device, d.n_inst, n_freq, o.d_ov, d.n_out, o.d_oi, d.n_cur, table.data(), n_req, d_meas, d_work, st));
-  HIPCHK(h, hipEventRecord(h->q.mev1, st));
+  HIPCHK(h, hipEventRecord(ev[1], st));
   HIPCHK(h, hipMemcpyAsync(meas, d_meas, n_meas * sizeof(double), hipMemcpyDeviceToHost, st));
   HIPCHK(h, hipStreamSynchronize(st));
-  StreamTimers::elapsed(h->q.mev0, h->q.mev1, &h->last_measure_ms);
+  StreamTimers::elapsed(ev[0], ev[1], &h->last_measure_ms);
   return h->ist.from_slots(o.status, d.n_inst, n_freq, h->err);
 }
 

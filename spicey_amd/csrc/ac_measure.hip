@@ -57,8 +57,8 @@ hipError_t spicey_launch_ac_measure(int device, int32_t n_inst, int64_t n_freq, 
   if (e != hipSuccess) return e;
   const SpiceyAcmBufs B{d_v, d_i, n_v, n_i, n_freq};
   const int64_t total = (int64_t)n_inst * n_req, per_wg = SPICEY_ACM_THREADS / SPICEY_ACM_LANES;
-  const int64_t want = (total + per_wg - 1) / per_wg, cap = (int64_t)1 << 20;  // (workgroups beyond this take several pairs per wave)
-  hipLaunchKernelGGL(spicey_ac_measure_kernel, dim3((unsigned)(want < cap ? want : cap)), dim3(SPICEY_ACM_THREADS), 0, st, B, total,
+  // (one wave per pair; beyond the grid's cap a wave takes several pairs)
+  hipLaunchKernelGGL(spicey_ac_measure_kernel, dim3(spicey_meas_grid1((total + per_wg - 1) / per_wg)), dim3(SPICEY_ACM_THREADS), 0, st, B, total,
                      (const SpiceyAcMeasDevReq *)d_work, n_req, d_meas);
   return hipGetLastError();
 }

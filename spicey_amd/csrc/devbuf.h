@@ -1,6 +1,7 @@
 // devbuf.h — what the host runtime's sources share: DevBuf<T> (owned device memory, hipFree in its destructor), the one
-// upload helper, the HIP-call check of the C-ABI entry points, the device open, StreamTimers (a stream and its timing
-// events), the dynamic-LDS rule of every launcher and the refusals of a measurement call.
+// upload helper, the HIP-call check of the C-ABI entry points, the device open, the numbering of the reduction passes,
+// StreamTimers (a stream, the event pair of its kernel and one pair per reduction pass), the dynamic-LDS rule of the
+// transient and AC launchers and the refusals of a measurement call (spicey_judge_measure).
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <stddef.h>
@@ -53,18 +54,26 @@ inline int32_t spicey_open_device(int device, int *ncu, std::string &err) {
   return SPICEY_OK;
 }
 
-// A handle's stream and its timing events: ev0 / ev1 bracket the kernel of a run, mev0 / mev1 the reduction of a
-// *_run_measure, fev0 / fev1 the harmonics pass of spicey_run_measure_fourier, tev0 / tev1 the timing pass of
-// spicey_run_measure_timing (created on first use).  Destroys what it created.  A handle declares it AFTER its DevBufs: members go in
-// reverse order, so events and stream are destroyed before the device memory is freed.
+// The reduction passes behind a transient run, in the order they run (spicey_abi.cpp, run_reduced): the index of a pass's
+// event pair in StreamTimers and of its time in SpiceyHandle::last_pass_ms.
+enum SpiceyPass { PASS_MEASURE = 0, PASS_FOURIER = 1, PASS_TIMING = 2, N_PASS = 3 };
+
+// A handle's stream and its timing events: ev0 / ev1 bracket the kernel of a run, pass_ev[p] the reduction pass p of a
+// *_run_measure* (created on first use; an AC handle has the measurement pass only).  Destroys what it created.  A handle
+// declares it AFTER its DevBufs: members go in reverse order, so events and stream are destroyed before the device memory
+// is freed.
 struct StreamTimers {
   hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr, mev0 = nullptr, mev1 = nullptr, fev0 = nullptr, fev1 = nullptr, tev0 = nullptr, tev1 = nullptr;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  hipEvent_t pass_ev[N_PASS][2] = {};
   StreamTimers() = default;
   StreamTimers(const StreamTimers &) = delete;
   ~StreamTimers() {
-    for (hipEvent_t e : {ev0, ev1, mev0, mev1, fev0, fev1, tev0, tev1})
+    for (hipEvent_t e : {ev0, ev1})
       if (e) (void)hipEventDestroy(e);
+    for (auto &pair : pass_ev)
+      for (hipEvent_t e : pair)
+        if (e) (void)hipEventDestroy(e);
     if (stream) (void)hipStreamDestroy(stream);
   }
   template <class H>
@@ -73,17 +82,12 @@ struct StreamTimers {
     h->err = "stream/event creation failed";
     return SPICEY_ERR_HIP;
   }
-  hipError_t want_measure_events() {
-    const hipError_t e = mev0 ? hipSuccess : hipEventCreate(&mev0);
-    return e != hipSuccess || mev1 ? e : hipEventCreate(&mev1);
-  }
-  hipError_t want_fourier_events() {
-    const hipError_t e = fev0 ? hipSuccess : hipEventCreate(&fev0);
-    return e != hipSuccess || fev1 ? e : hipEventCreate(&fev1);
-  }
-  hipError_t want_timing_events() {
-    const hipError_t e = tev0 ? hipSuccess : hipEventCreate(&tev0);
-    return e != hipSuccess || tev1 ? e : hipEventCreate(&tev1);
+  hipError_t want_pass_events(int pass) {
+    for (hipEvent_t &e : pass_ev[pass]) {
+      const hipError_t err = e ? hipSuccess : hipEventCreate(&e);
+      if (err != hipSuccess) return err;
+    }
+    return hipSuccess;
   }
   // elapsed milliseconds of a finished pair into *ms (left alone when the runtime cannot tell)
   static void elapsed(hipEvent_t a, hipEvent_t b, double *ms) {

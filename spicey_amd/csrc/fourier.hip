@@ -61,15 +61,13 @@ hipError_t spicey_launch_fourier(int device, int32_t n_inst, int64_t n_points, d
   double *partials = (double *)((char *)d_work + plan.head_bytes);
   const int32_t n_req = (int32_t)plan.table.size();
   const int64_t tiles = (int64_t)n_inst * plan.tiles_per_inst;
-  const int64_t cap = (int64_t)1 << 20;  // (workgroups beyond this take several tiles each)
-  const unsigned grid1 = (unsigned)(tiles < cap ? tiles : cap);
-  hipLaunchKernelGGL(spicey_fourier_stage1, dim3(grid1), dim3(SPICEY_MEAS_THREADS), 0, st, tiles, plan.tiles_per_inst, n_points, d_v, n_v, d_i, n_i, d_table, d_bases,
+  hipLaunchKernelGGL(spicey_fourier_stage1, dim3(spicey_meas_grid1(tiles)), dim3(SPICEY_MEAS_THREADS), 0, st, tiles, plan.tiles_per_inst, n_points, d_v, n_v, d_i, n_i, d_table, d_bases,
                      (int32_t)plan.bases.size(), d_tw, partials, plan.partials_per_inst);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   const int64_t total = (int64_t)n_inst * n_req * out_stride;
-  const int64_t grid2 = (total + SPICEY_MEAS_THREADS - 1) / SPICEY_MEAS_THREADS;
-  if (grid2 > 0x7fffffffLL) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(spicey_fourier_stage2, dim3((unsigned)grid2), dim3(SPICEY_MEAS_THREADS), 0, st, total, d_table, d_bases, n_req, out_stride,
+  unsigned grid2 = 0;
+  if ((e = spicey_meas_grid2(total, SPICEY_MEAS_THREADS, &grid2)) != hipSuccess) return e;
+  hipLaunchKernelGGL(spicey_fourier_stage2, dim3(grid2), dim3(SPICEY_MEAS_THREADS), 0, st, total, d_table, d_bases, n_req, out_stride,
                      (const double *)partials, plan.partials_per_inst, d_out);
   return hipGetLastError();
 }

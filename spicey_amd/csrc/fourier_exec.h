@@ -176,8 +176,6 @@ struct SpiceyFourPlan {
   int64_t workspace_bytes(int32_t n_inst) const { return head_bytes + (int64_t)n_inst * partials_per_inst * (int64_t)sizeof(double); }
 };
 
-inline int64_t spicey_four_align(int64_t b) { return (b + SPICEY_MEAS_HEAD_ALIGN - 1) / SPICEY_MEAS_HEAD_ALIGN * SPICEY_MEAS_HEAD_ALIGN; }
-
 // The tiles of a launch with workgroups of `threads` threads (a power of two).
 inline void spicey_four_geom(SpiceyFourPlan &p, int32_t threads) {
   p.rl = threads < SPICEY_FOUR_WAVE ? threads : SPICEY_FOUR_WAVE;
@@ -241,9 +239,9 @@ inline bool spicey_four_layout(const SpiceyFourReq *reqs, int32_t n_req, int64_t
     b.p_off = p.partials_per_inst;
     p.partials_per_inst += b.chunks * (1 + 2 * b.H) * b.n_req;
   }
-  p.off_bases = spicey_four_align((int64_t)p.table.size() * (int64_t)sizeof(SpiceyFourDevReq));
-  p.off_tw = p.off_bases + spicey_four_align((int64_t)p.bases.size() * (int64_t)sizeof(SpiceyFourBasis));
-  p.head_bytes = p.off_tw + spicey_four_align(p.tw_doubles * (int64_t)sizeof(double));
+  p.off_bases = spicey_meas_align((int64_t)p.table.size() * (int64_t)sizeof(SpiceyFourDevReq));
+  p.off_tw = p.off_bases + spicey_meas_align((int64_t)p.bases.size() * (int64_t)sizeof(SpiceyFourBasis));
+  p.head_bytes = p.off_tw + spicey_meas_align(p.tw_doubles * (int64_t)sizeof(double));
   spicey_four_geom(p, SPICEY_MEAS_THREADS);
   return true;
 }

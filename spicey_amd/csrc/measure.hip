@@ -93,13 +93,11 @@ hipError_t spicey_launch_measure(int device, int32_t n_inst, int64_t n_points, d
   const SpiceyMeasDevReq *d_table = (const SpiceyMeasDevReq *)d_work;
   double *partials = (double *)((char *)d_work + spicey_meas_head_bytes(n_req));
   const SpiceyMeasGeom g = spicey_meas_geom(n_inst, n_points, n_req, SPICEY_MEAS_THREADS);
-  const int64_t cap = (int64_t)1 << 20;  // (workgroups beyond this take several tiles each)
-  const unsigned grid1 = (unsigned)(g.tiles < cap ? g.tiles : cap);
-  hipLaunchKernelGGL(spicey_measure_stage1, dim3(grid1), dim3(SPICEY_MEAS_THREADS), 0, st, n_inst, n_points, dt, d_v, n_v, d_i, n_i, d_table, n_req, partials);
+  hipLaunchKernelGGL(spicey_measure_stage1, dim3(spicey_meas_grid1(g.tiles)), dim3(SPICEY_MEAS_THREADS), 0, st, n_inst, n_points, dt, d_v, n_v, d_i, n_i, d_table, n_req, partials);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   const int64_t total = (int64_t)n_inst * n_req;
-  const int64_t grid2 = (total + SPICEY_MEAS_THREADS - 1) / SPICEY_MEAS_THREADS;
-  if (grid2 > 0x7fffffffLL) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(spicey_measure_stage2, dim3((unsigned)grid2), dim3(SPICEY_MEAS_THREADS), 0, st, total, d_table, n_req, g.max_chunks, (const double *)partials, d_meas);
+  unsigned grid2 = 0;
+  if ((e = spicey_meas_grid2(total, SPICEY_MEAS_THREADS, &grid2)) != hipSuccess) return e;
+  hipLaunchKernelGGL(spicey_measure_stage2, dim3(grid2), dim3(SPICEY_MEAS_THREADS), 0, st, total, d_table, n_req, g.max_chunks, (const double *)partials, d_meas);
   return hipGetLastError();
 }

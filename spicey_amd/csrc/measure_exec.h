@@ -182,11 +182,11 @@ SPICEY_MEAS_HD void spicey_meas_stage2(int64_t idx, const SpiceyMeasDevReq *tabl
 #include <string>
 #include <vector>
 
+// `b` bytes rounded up to the alignment of a workspace's regions (all reduction passes)
+inline int64_t spicey_meas_align(int64_t b) { return (b + SPICEY_MEAS_HEAD_ALIGN - 1) / SPICEY_MEAS_HEAD_ALIGN * SPICEY_MEAS_HEAD_ALIGN; }
+
 // bytes of the request table at the head of the workspace
-inline int64_t spicey_meas_head_bytes(int32_t n_req) {
-  const int64_t b = (int64_t)n_req * (int64_t)sizeof(SpiceyMeasDevReq);
-  return (b + SPICEY_MEAS_HEAD_ALIGN - 1) / SPICEY_MEAS_HEAD_ALIGN * SPICEY_MEAS_HEAD_ALIGN;
-}
+inline int64_t spicey_meas_head_bytes(int32_t n_req) { return spicey_meas_align((int64_t)n_req * (int64_t)sizeof(SpiceyMeasDevReq)); }
 
 // table | partials; -1 for arguments no launch accepts
 inline int64_t spicey_meas_workspace_bytes(int32_t n_inst, int64_t n_points, int32_t n_req) {

@@ -9,6 +9,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <dlfcn.h>
+#include <functional>
 #include <map>
 #include <mutex>
 #include <string>
@@ -95,7 +96,7 @@ struct SpiceyHandle {
   DevBuf<double> d_gstat, d_statv, d_rcoef, d_gW, d_dpar;
   DevBuf<int32_t> d_status; DevBuf<unsigned long long> d_solves, d_prof;
   hipStream_t last_stream = nullptr;
-  double last_measure_ms = 0.0, last_fourier_ms = 0.0, last_timing_ms = 0.0;
+  double last_pass_ms[N_PASS] = {};  // the reduction passes of the last spicey_run_measure* (0: the pass did not run)
   bool pending = false;
   int64_t last_solves = 0;
   double last_ms = 0.0;
@@ -739,6 +740,16 @@ extern "C" int64_t spicey_measure_workspace_bytes(int32_t n_inst, int64_t n_poin
   return spicey_meas_workspace_bytes(n_inst, n_points, n_req);
 }
 
+// The tail of the handle-less spicey_*_device entry points, behind their judge: the device opened, the launch enqueued, a
+// failure as "<launcher>: <the runtime's text>" in the calling thread's error.
+static int32_t launch_on_device(int32_t device, const char *launcher, const std::function<hipError_t()> &launch) {
+  int ncu = 0;
+  if (const int32_t rc = spicey_open_device(device, &ncu, g_err); rc != SPICEY_OK) return rc;
+  const hipError_t e = launch();
+  if (e != hipSuccess) { g_err = std::string(launcher) + ": " + hipGetErrorString(e); return SPICEY_ERR_HIP; }
+  return SPICEY_OK;
+}
+
 extern "C" int32_t spicey_measure_device(int32_t device, int32_t n_inst, int64_t n_points, double dt, const double *d_v, int32_t n_v, const double *d_i,
                                          int32_t n_i, const SpiceyMeasReq *reqs, int32_t n_req, double *d_meas, void *d_work, int64_t work_bytes,
                                          void *stream) {
@@ -747,98 +758,103 @@ extern "C" int32_t spicey_measure_device(int32_t device, int32_t n_inst, int64_t
   if (const int32_t rc = spicey_judge_measure("measure", spicey_meas_plan, spicey_meas_workspace_bytes, n_inst, n_points, d_v != nullptr, n_v, d_i != nullptr, n_i, reqs,
                                               n_req, d_meas && d_work, work_bytes, table, g_err); rc != SPICEY_OK)
     return rc;
-  int ncu = 0;
-  if (const int32_t rc = spicey_open_device(device, &ncu, g_err); rc != SPICEY_OK) return rc;
-  const hipError_t e = spicey_launch_measure(device, n_inst, n_points, dt, d_v, n_v, d_i, n_i, table.data(), n_req, d_meas, d_work, (hipStream_t)stream);
-  if (e != hipSuccess) { g_err = std::string("spicey_launch_measure: ") + hipGetErrorString(e); return SPICEY_ERR_HIP; }
-  return SPICEY_OK;
+  return launch_on_device(device, "spicey_launch_measure", [&]() {
+    return spicey_launch_measure(device, n_inst, n_points, dt, d_v, n_v, d_i, n_i, table.data(), n_req, d_meas, d_work, (hipStream_t)stream);
+  });
 }
 
-// What spicey_run_measure, spicey_run_measure_fourier and spicey_run_measure_timing share: one transient run into device
-// buffers of this call's own, the reductions on the handle's stream behind it, and only their results and `iters` on the way
-// back.  entry: 0 = the first entry point (the measurement pass alone), 1 = the second (the measurement list may be empty;
-// the harmonics list may not), 2 = the third (either of those lists may be empty; the timing list may not).
-static int32_t run_reduced(SpiceyHandle *h, int64_t steps, double dt, const double *src_table, int32_t src_per_inst, const SpiceyMeasReq *reqs, int32_t n_req,
-                           double *meas, int entry, const SpiceyFourReq *freqs, int32_t n_four, double *four, int32_t four_stride,
-                           const SpiceyTimingReq *treqs, int32_t n_tim, double *timing, int32_t *iters) {
+// The lists of spicey_run_measure, spicey_run_measure_fourier and spicey_run_measure_timing: per pass the caller's requests,
+// their count and the out pointer.  entry = the entry point's own pass, its last: that list may not be empty, the lists
+// before it may, and there are none behind it.
+struct ReducedLists {
+  int entry;
+  const SpiceyMeasReq *reqs; int32_t n_req; double *meas;
+  const SpiceyFourReq *freqs; int32_t n_four; double *four; int32_t four_stride;
+  const SpiceyTimingReq *treqs; int32_t n_tim; double *timing;
+};
+
+// What the three entry points share: one transient run into device buffers of this call's own, the reductions on the
+// handle's stream behind it, and only their results and `iters` on the way back.
+static int32_t run_reduced(SpiceyHandle *h, int64_t steps, double dt, const double *src_table, int32_t src_per_inst, const ReducedLists &a, int32_t *iters) {
   if (!h) return SPICEY_ERR_BAD_DESC;
-  const bool tim_pass = entry == 2;
-  if (const int32_t rc0 = check_run_args(h, steps, tim_pass ? (const void *)timing : entry == 1 ? (const void *)four : (const void *)meas, src_table, src_per_inst);
-      rc0 != SPICEY_OK)
-    return rc0;
-  const bool meas_pass = entry == 0 || n_req != 0;
-  const bool four_pass = entry == 1 || (tim_pass && n_four != 0);
-  if (entry == 1 && (n_req < 0 || (n_req > 0 && !meas))) { h->err = "fourier: n_req must be >= 0, and meas not null when n_req > 0"; return SPICEY_ERR_BAD_DESC; }
-  if (tim_pass && (n_req < 0 || (n_req > 0 && !meas) || n_four < 0 || (n_four > 0 && !four))) {
+  double *const outs[N_PASS] = {a.meas, a.four, a.timing};
+  if (const int32_t rc0 = check_run_args(h, steps, outs[a.entry], src_table, src_per_inst); rc0 != SPICEY_OK) return rc0;
+  if (a.entry == 1 && (a.n_req < 0 || (a.n_req > 0 && !a.meas))) { h->err = "fourier: n_req must be >= 0, and meas not null when n_req > 0"; return SPICEY_ERR_BAD_DESC; }
+  if (a.entry == 2 && (a.n_req < 0 || (a.n_req > 0 && !a.meas) || a.n_four < 0 || (a.n_four > 0 && !a.four))) {
     h->err = "timing: n_req and n_four must be >= 0, and meas / four not null when their count is > 0";
     return SPICEY_ERR_BAD_DESC;
   }
+  // (a pass runs if it is the entry point's own, or an earlier one whose list is not empty)
+  const int32_t counts[N_PASS] = {a.n_req, a.n_four, a.n_tim};
+  bool on[N_PASS];
+  for (int p = 0; p < N_PASS; p++) on[p] = p == a.entry || (p < a.entry && counts[p] != 0);
   const SpiceyProg &P = h->hp.hdr;
   const int32_t ni = h->plan.n_inst;
   const int64_t np = steps + 1;
   // (a refused request list runs nothing; the buffers are this call's own)
-  const int64_t work_bytes = meas_pass ? spicey_meas_workspace_bytes(ni, np, n_req) : 0;
+  const int64_t work_bytes = on[PASS_MEASURE] ? spicey_meas_workspace_bytes(ni, np, a.n_req) : 0;
   std::vector<SpiceyMeasDevReq> table;
-  if (meas_pass)
-    if (const int32_t rc0 = spicey_judge_measure("measure", spicey_meas_plan, spicey_meas_workspace_bytes, ni, np, true, P.nOut, true, P.nCur, reqs, n_req, true,
+  if (on[PASS_MEASURE])
+    if (const int32_t rc0 = spicey_judge_measure("measure", spicey_meas_plan, spicey_meas_workspace_bytes, ni, np, true, P.nOut, true, P.nCur, a.reqs, a.n_req, true,
                                                  work_bytes, table, h->err); rc0 != SPICEY_OK)
       return rc0;
   SpiceyFourPlan fplan;
-  if (four_pass && !spicey_four_judge(ni, np, dt, true, P.nOut, true, P.nCur, freqs, n_four, true, four_stride, INT64_MAX, fplan, h->err)) return SPICEY_ERR_BAD_DESC;
+  if (on[PASS_FOURIER] && !spicey_four_judge(ni, np, dt, true, P.nOut, true, P.nCur, a.freqs, a.n_four, true, a.four_stride, INT64_MAX, fplan, h->err))
+    return SPICEY_ERR_BAD_DESC;
   SpiceyTimPlan tplan;
-  if (tim_pass && !spicey_tim_judge(ni, np, dt, true, P.nOut, true, P.nCur, treqs, n_tim, true, INT64_MAX, tplan, h->err)) return SPICEY_ERR_BAD_DESC;
-  bool need_i = false;
-  for (const SpiceyMeasDevReq &q : table) need_i = need_i || q.signal == 1;
-  for (const SpiceyFourDevReq &q : fplan.table) need_i = need_i || q.signal == 1;
-  for (const SpiceyTimDevEdge &q : tplan.edges) need_i = need_i || q.signal == 1;
+  if (on[PASS_TIMING] && !spicey_tim_judge(ni, np, dt, true, P.nOut, true, P.nCur, a.treqs, a.n_tim, true, INT64_MAX, tplan, h->err)) return SPICEY_ERR_BAD_DESC;
+  const auto names_a_current = [](const auto &list) { return std::any_of(list.begin(), list.end(), [](const auto &q) { return q.signal == 1; }); };
+  const bool need_i = names_a_current(table) || names_a_current(fplan.table) || names_a_current(tplan.edges);
   if (const int32_t rc0 = check_structure(h); rc0 != SPICEY_OK) return rc0;
   HIPCHK(h, hipSetDevice(h->device));
-  Roctx range_run(tim_pass ? "spicey_run_measure_timing" : four_pass ? "spicey_run_measure_fourier" : "spicey_run_measure");
-  HIPCHK(h, h->q.want_measure_events());
-  if (four_pass) HIPCHK(h, h->q.want_fourier_events());
-  if (tim_pass) HIPCHK(h, h->q.want_timing_events());
+  static const char *const entry_name[N_PASS] = {"spicey_run_measure", "spicey_run_measure_fourier", "spicey_run_measure_timing"};
+  Roctx range_run(entry_name[a.entry]);
   HostRun r;
-  DevBuf<double> d_meas, d_four, d_tim;
-  DevBuf<uint8_t> d_work, d_fwork, d_twork;
+  hipStream_t st = h->q.stream;
+  // The pass table: what the blocks below do per pass.  A further pass is one more entry here (and its judge above).
+  struct Pass {
+    bool on;
+    size_t n_out, work_bytes;  // doubles of the result, bytes of the workspace
+    double *out;               // the caller's
+    const char *failed;        // prefix of a launch error's text
+    std::function<hipError_t(double *d_out, void *d_work)> launch;
+    DevBuf<double> d_out;
+    DevBuf<uint8_t> d_work;
+  };
+  Pass pass[N_PASS] = {
+      {on[PASS_MEASURE], (size_t)ni * (size_t)a.n_req * 8, (size_t)work_bytes, a.meas, "spicey_launch_measure: ", [&](double *d_out, void *d_work) {
+         return spicey_launch_measure(h->device, ni, np, dt, r.d_v, P.nOut, r.d_i, P.nCur, table.data(), a.n_req, d_out, d_work, st);
+       }},
+      {on[PASS_FOURIER], (size_t)ni * (size_t)a.n_four * (size_t)a.four_stride, (size_t)fplan.workspace_bytes(ni), a.four, "spicey_launch_fourier: ",
+       [&](double *d_out, void *d_work) {
+         return spicey_launch_fourier(h->device, ni, np, dt, r.d_v, P.nOut, r.d_i, P.nCur, fplan, d_out, a.four_stride, d_work, st);
+       }},
+      {on[PASS_TIMING], (size_t)ni * (size_t)a.n_tim * 8, (size_t)tplan.workspace_bytes(ni, np), a.timing, "spicey_launch_timing: ", [&](double *d_out, void *d_work) {
+         return spicey_launch_timing(h->device, ni, np, dt, r.d_v, P.nOut, r.d_i, P.nCur, tplan, d_out, d_work, st);
+       }},
+  };
+  for (int p = 0; p < N_PASS; p++)
+    if (pass[p].on) HIPCHK(h, h->q.want_pass_events(p));
   // (no current request: the run records no currents)
   if (const int32_t rc0 = r.stage(h, steps, src_table, src_per_inst, need_i, iters != nullptr); rc0 != SPICEY_OK) return rc0;
-  if (meas_pass) {
-    HIPCHK(h, d_meas.alloc((size_t)ni * (size_t)n_req * 8));
-    HIPCHK(h, d_work.alloc((size_t)work_bytes));
+  for (Pass &t : pass) {
+    if (!t.on) continue;
+    HIPCHK(h, t.d_out.alloc(t.n_out));
+    HIPCHK(h, t.d_work.alloc(t.work_bytes));
   }
-  if (four_pass) {
-    HIPCHK(h, d_four.alloc((size_t)ni * (size_t)n_four * (size_t)four_stride));
-    HIPCHK(h, d_fwork.alloc((size_t)fplan.workspace_bytes(ni)));
-  }
-  if (tim_pass) {
-    HIPCHK(h, d_tim.alloc((size_t)ni * (size_t)n_tim * 8));
-    HIPCHK(h, d_twork.alloc((size_t)tplan.workspace_bytes(ni, np)));
-  }
-  h->last_measure_ms = 0.0;
-  h->last_fourier_ms = 0.0;
-  h->last_timing_ms = 0.0;
-  hipStream_t st = h->q.stream;
+  for (double &ms : h->last_pass_ms) ms = 0.0;
   int32_t rc = spicey_run_device_src(h, steps, dt, r.d_src, src_per_inst, r.d_v, r.d_i, r.d_it, st);
   if (rc != SPICEY_OK) return rc;
-  const char *failed = "spicey_launch_measure: ";
+  const char *failed = "";
   auto reduce = [&]() {
     hipError_t e = hipSuccess;
-    if (meas_pass) {
-      e = hipEventRecord(h->q.mev0, st);
-      if (e == hipSuccess) e = spicey_launch_measure(h->device, ni, np, dt, r.d_v, P.nOut, r.d_i, P.nCur, table.data(), n_req, d_meas, d_work, st);
-      if (e == hipSuccess) e = hipEventRecord(h->q.mev1, st);
-    }
-    if (four_pass && e == hipSuccess) {
-      failed = "spicey_launch_fourier: ";
-      e = hipEventRecord(h->q.fev0, st);
-      if (e == hipSuccess) e = spicey_launch_fourier(h->device, ni, np, dt, r.d_v, P.nOut, r.d_i, P.nCur, fplan, d_four, four_stride, d_fwork, st);
-      if (e == hipSuccess) e = hipEventRecord(h->q.fev1, st);
-    }
-    if (tim_pass && e == hipSuccess) {
-      failed = "spicey_launch_timing: ";
-      e = hipEventRecord(h->q.tev0, st);
-      if (e == hipSuccess) e = spicey_launch_timing(h->device, ni, np, dt, r.d_v, P.nOut, r.d_i, P.nCur, tplan, d_tim, d_twork, st);
-      if (e == hipSuccess) e = hipEventRecord(h->q.tev1, st);
+    for (int p = 0; p < N_PASS && e == hipSuccess; p++) {
+      Pass &t = pass[p];
+      if (!t.on) continue;
+      failed = t.failed;
+      e = hipEventRecord(h->q.pass_ev[p][0], st);
+      if (e == hipSuccess) e = t.launch(t.d_out, t.d_work);
+      if (e == hipSuccess) e = hipEventRecord(h->q.pass_ev[p][1], st);
     }
     return e;
   };
@@ -849,13 +865,11 @@ static int32_t run_reduced(SpiceyHandle *h, int64_t steps, double dt, const doub
   if (e == hipSuccess && h->group_retries != retries && rc == SPICEY_OK && (e = reduce()) == hipSuccess) e = hipStreamSynchronize(st);
   if (e != hipSuccess) { h->err = std::string(failed) + hipGetErrorString(e); return SPICEY_ERR_HIP; }
   if (rc == SPICEY_OK || rc == SPICEY_ERR_SINGULAR) {
-    if (meas_pass) StreamTimers::elapsed(h->q.mev0, h->q.mev1, &h->last_measure_ms);
-    if (four_pass) StreamTimers::elapsed(h->q.fev0, h->q.fev1, &h->last_fourier_ms);
-    if (tim_pass) StreamTimers::elapsed(h->q.tev0, h->q.tev1, &h->last_timing_ms);
+    for (int p = 0; p < N_PASS; p++)
+      if (pass[p].on) StreamTimers::elapsed(h->q.pass_ev[p][0], h->q.pass_ev[p][1], &h->last_pass_ms[p]);
     Roctx range_copy("spicey_run_measure:results");
-    if (meas_pass) HIPCHK(h, hipMemcpy(meas, d_meas, (size_t)ni * (size_t)n_req * 8 * sizeof(double), hipMemcpyDeviceToHost));
-    if (four_pass) HIPCHK(h, hipMemcpy(four, d_four, (size_t)ni * (size_t)n_four * (size_t)four_stride * sizeof(double), hipMemcpyDeviceToHost));
-    if (tim_pass) HIPCHK(h, hipMemcpy(timing, d_tim, (size_t)ni * (size_t)n_tim * 8 * sizeof(double), hipMemcpyDeviceToHost));
+    for (const Pass &t : pass)
+      if (t.on) HIPCHK(h, hipMemcpy(t.out, t.d_out, t.n_out * sizeof(double), hipMemcpyDeviceToHost));
     if (const int32_t rc0 = r.copy_out(h, nullptr, nullptr, iters); rc0 != SPICEY_OK) return rc0;
   }
   return rc;
@@ -863,25 +877,24 @@ static int32_t run_reduced(SpiceyHandle *h, int64_t steps, double dt, const doub
 
 extern "C" int32_t spicey_run_measure(SpiceyHandle *h, int64_t steps, double dt, const double *src_table, int32_t src_per_inst, const SpiceyMeasReq *reqs,
                                       int32_t n_req, double *meas, int32_t *iters) {
-  return run_reduced(h, steps, dt, src_table, src_per_inst, reqs, n_req, meas, 0, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, iters);
+  return run_reduced(h, steps, dt, src_table, src_per_inst, {0, reqs, n_req, meas, nullptr, 0, nullptr, 0, nullptr, 0, nullptr}, iters);
 }
 
 extern "C" int32_t spicey_run_measure_fourier(SpiceyHandle *h, int64_t steps, double dt, const double *src_table, int32_t src_per_inst, const SpiceyMeasReq *reqs,
                                               int32_t n_req, double *meas, const SpiceyFourReq *freqs, int32_t n_four, double *four, int32_t four_stride,
                                               int32_t *iters) {
-  return run_reduced(h, steps, dt, src_table, src_per_inst, reqs, n_req, meas, 1, freqs, n_four, four, four_stride, nullptr, 0, nullptr, iters);
+  return run_reduced(h, steps, dt, src_table, src_per_inst, {1, reqs, n_req, meas, freqs, n_four, four, four_stride, nullptr, 0, nullptr}, iters);
 }
-
-extern "C" double spicey_last_measure_ms(SpiceyHandle *h) { return h ? h->last_measure_ms : 0.0; }
-extern "C" double spicey_last_fourier_ms(SpiceyHandle *h) { return h ? h->last_fourier_ms : 0.0; }
 
 extern "C" int32_t spicey_run_measure_timing(SpiceyHandle *h, int64_t steps, double dt, const double *src_table, int32_t src_per_inst, const SpiceyMeasReq *reqs,
                                              int32_t n_req, double *meas, const SpiceyFourReq *freqs, int32_t n_four, double *four, int32_t four_stride,
                                              const SpiceyTimingReq *treqs, int32_t n_timing, double *timing, int32_t *iters) {
-  return run_reduced(h, steps, dt, src_table, src_per_inst, reqs, n_req, meas, 2, freqs, n_four, four, four_stride, treqs, n_timing, timing, iters);
+  return run_reduced(h, steps, dt, src_table, src_per_inst, {2, reqs, n_req, meas, freqs, n_four, four, four_stride, treqs, n_timing, timing}, iters);
 }
 
-extern "C" double spicey_last_timing_ms(SpiceyHandle *h) { return h ? h->last_timing_ms : 0.0; }
+extern "C" double spicey_last_measure_ms(SpiceyHandle *h) { return h ? h->last_pass_ms[PASS_MEASURE] : 0.0; }
+extern "C" double spicey_last_fourier_ms(SpiceyHandle *h) { return h ? h->last_pass_ms[PASS_FOURIER] : 0.0; }
+extern "C" double spicey_last_timing_ms(SpiceyHandle *h) { return h ? h->last_pass_ms[PASS_TIMING] : 0.0; }
 
 // Edge timing (include/spicey_hip.h): the reduction of timing.hip on any device buffers, no handle.
 extern "C" int64_t spicey_timing_workspace_bytes(int32_t n_inst, int64_t n_points, const SpiceyTimingReq *reqs, int32_t n_req) {
@@ -895,11 +908,9 @@ extern "C" int32_t spicey_timing_device(int32_t device, int32_t n_inst, int64_t 
   SpiceyTimPlan plan;
   if (!spicey_tim_judge(n_inst, n_points, dt, d_v != nullptr, n_v, d_i != nullptr, n_i, reqs, n_req, d_out && d_work, work_bytes, plan, g_err))
     return SPICEY_ERR_BAD_DESC;
-  int ncu = 0;
-  if (const int32_t rc = spicey_open_device(device, &ncu, g_err); rc != SPICEY_OK) return rc;
-  const hipError_t e = spicey_launch_timing(device, n_inst, n_points, dt, d_v, n_v, d_i, n_i, plan, d_out, d_work, (hipStream_t)stream);
-  if (e != hipSuccess) { g_err = std::string("spicey_launch_timing: ") + hipGetErrorString(e); return SPICEY_ERR_HIP; }
-  return SPICEY_OK;
+  return launch_on_device(device, "spicey_launch_timing", [&]() {
+    return spicey_launch_timing(device, n_inst, n_points, dt, d_v, n_v, d_i, n_i, plan, d_out, d_work, (hipStream_t)stream);
+  });
 }
 
 // Harmonics (include/spicey_hip.h): the reduction of fourier.hip on any device buffers, no handle.
@@ -914,11 +925,9 @@ extern "C" int32_t spicey_fourier_device(int32_t device, int32_t n_inst, int64_t
   SpiceyFourPlan plan;
   if (!spicey_four_judge(n_inst, n_points, dt, d_v != nullptr, n_v, d_i != nullptr, n_i, reqs, n_req, d_out && d_work, out_stride, work_bytes, plan, g_err))
     return SPICEY_ERR_BAD_DESC;
-  int ncu = 0;
-  if (const int32_t rc = spicey_open_device(device, &ncu, g_err); rc != SPICEY_OK) return rc;
-  const hipError_t e = spicey_launch_fourier(device, n_inst, n_points, dt, d_v, n_v, d_i, n_i, plan, d_out, out_stride, d_work, (hipStream_t)stream);
-  if (e != hipSuccess) { g_err = std::string("spicey_launch_fourier: ") + hipGetErrorString(e); return SPICEY_ERR_HIP; }
-  return SPICEY_OK;
+  return launch_on_device(device, "spicey_launch_fourier", [&]() {
+    return spicey_launch_fourier(device, n_inst, n_points, dt, d_v, n_v, d_i, n_i, plan, d_out, out_stride, d_work, (hipStream_t)stream);
+  });
 }
 
 // The same for an AC sweep's complex buffers (include/spicey_hip.h): the reduction of ac_measure.hip, no handle.
@@ -933,11 +942,9 @@ extern "C" int32_t spicey_ac_measure_device(int32_t device, int32_t n_inst, int6
   if (const int32_t rc = spicey_judge_measure("ac measure", spicey_acm_plan, spicey_acm_workspace_bytes, n_inst, n_freq, d_v != nullptr, n_v, d_i != nullptr, n_i, reqs,
                                               n_req, d_meas && d_work, work_bytes, table, g_err); rc != SPICEY_OK)
     return rc;
-  int ncu = 0;
-  if (const int32_t rc = spicey_open_device(device, &ncu, g_err); rc != SPICEY_OK) return rc;
-  const hipError_t e = spicey_launch_ac_measure(device, n_inst, n_freq, d_v, n_v, d_i, n_i, table.data(), n_req, d_meas, d_work, (hipStream_t)stream);
-  if (e != hipSuccess) { g_err = std::string("spicey_launch_ac_measure: ") + hipGetErrorString(e); return SPICEY_ERR_HIP; }
-  return SPICEY_OK;
+  return launch_on_device(device, "spicey_launch_ac_measure", [&]() {
+    return spicey_launch_ac_measure(device, n_inst, n_freq, d_v, n_v, d_i, n_i, table.data(), n_req, d_meas, d_work, (hipStream_t)stream);
+  });
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

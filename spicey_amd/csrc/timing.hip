@@ -62,15 +62,13 @@ hipError_t spicey_launch_timing(int device, int32_t n_inst, int64_t n_points, do
       (e = spicey_launch_measure(device, n_inst, n_points, dt, d_v, n_v, d_i, n_i, plan.bases.data(), n_base, d_base, w + plan.off_base_work(n_inst), st)) != hipSuccess)
     return e;
   const SpiceyMeasGeom g = spicey_meas_geom(n_inst, n_points, n_edge, SPICEY_MEAS_THREADS);
-  const int64_t cap = (int64_t)1 << 20;  // (workgroups beyond this take several tiles each)
-  const unsigned grid1 = (unsigned)(g.tiles < cap ? g.tiles : cap);
-  hipLaunchKernelGGL(spicey_timing_stage1, dim3(grid1), dim3(SPICEY_MEAS_THREADS), 0, st, n_inst, n_points, d_v, n_v, d_i, n_i, d_edges, n_edge, n_base,
+  hipLaunchKernelGGL(spicey_timing_stage1, dim3(spicey_meas_grid1(g.tiles)), dim3(SPICEY_MEAS_THREADS), 0, st, n_inst, n_points, d_v, n_v, d_i, n_i, d_edges, n_edge, n_base,
                      (const double *)d_base, d_counts);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   const int64_t total = (int64_t)n_inst * n_req;
-  const int64_t grid2 = (total + SPICEY_MEAS_THREADS - 1) / SPICEY_MEAS_THREADS;
-  if (grid2 > 0x7fffffffLL) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(spicey_timing_stage2, dim3((unsigned)grid2), dim3(SPICEY_MEAS_THREADS), 0, st, total, d_reqs, n_req, d_edges, n_edge, n_base, plan.max_chunks,
+  unsigned grid2 = 0;
+  if ((e = spicey_meas_grid2(total, SPICEY_MEAS_THREADS, &grid2)) != hipSuccess) return e;
+  hipLaunchKernelGGL(spicey_timing_stage2, dim3(grid2), dim3(SPICEY_MEAS_THREADS), 0, st, total, d_reqs, n_req, d_edges, n_edge, n_base, plan.max_chunks,
                      n_points, dt, d_v, n_v, d_i, n_i, (const double *)d_base, (const int32_t *)d_counts, d_out);
   return hipGetLastError();
 }

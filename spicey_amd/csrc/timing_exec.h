@@ -193,8 +193,6 @@ SPICEY_TIM_HD void spicey_tim_stage2(int64_t idx, const SpiceyTimDevReq *reqs, i
 #include <tuple>
 #include <vector>
 
-inline int64_t spicey_tim_align(int64_t b) { return (b + SPICEY_MEAS_HEAD_ALIGN - 1) / SPICEY_MEAS_HEAD_ALIGN * SPICEY_MEAS_HEAD_ALIGN; }
-
 // Everything a launch needs, from the request list alone: the sorted edge and request tables, the base windows as stats
 // requests of the measurement pass (distinct (signal, col, col_ref, base_from, base_to), sorted like its tables), sizes.
 struct SpiceyTimPlan {
@@ -206,13 +204,13 @@ struct SpiceyTimPlan {
   // for the bases (n_base > 0) | counts [n_inst][max_chunks][n_edge] int32
   int64_t off_reqs = 0, head_bytes = 0;
   int64_t off_base_out() const { return head_bytes; }
-  int64_t off_base_work(int32_t n_inst) const { return head_bytes + spicey_tim_align((int64_t)n_inst * (int64_t)bases.size() * 8 * (int64_t)sizeof(double)); }
+  int64_t off_base_work(int32_t n_inst) const { return head_bytes + spicey_meas_align((int64_t)n_inst * (int64_t)bases.size() * 8 * (int64_t)sizeof(double)); }
   int64_t off_counts(int32_t n_inst, int64_t n_points) const {
     const int64_t w = bases.empty() ? 0 : spicey_meas_workspace_bytes(n_inst, n_points, (int32_t)bases.size());
-    return off_base_work(n_inst) + spicey_tim_align(w);
+    return off_base_work(n_inst) + spicey_meas_align(w);
   }
   int64_t workspace_bytes(int32_t n_inst, int64_t n_points) const {
-    return off_counts(n_inst, n_points) + spicey_tim_align((int64_t)n_inst * max_chunks * (int64_t)edges.size() * (int64_t)sizeof(int32_t));
+    return off_counts(n_inst, n_points) + spicey_meas_align((int64_t)n_inst * max_chunks * (int64_t)edges.size() * (int64_t)sizeof(int32_t));
   }
 };
 
@@ -281,8 +279,8 @@ inline bool spicey_tim_plan(const SpiceyTimingReq *reqs, int32_t n_req, int64_t 
   p.bases = bases;
   std::stable_sort(p.bases.begin(), p.bases.end(), [](const SpiceyMeasDevReq &a, const SpiceyMeasDevReq &b) { return a.signal != b.signal ? a.signal < b.signal : a.col < b.col; });
   p.max_chunks = (n_points + SPICEY_MEAS_CHUNK - 1) / SPICEY_MEAS_CHUNK;
-  p.off_reqs = spicey_tim_align((int64_t)p.edges.size() * (int64_t)sizeof(SpiceyTimDevEdge));
-  p.head_bytes = p.off_reqs + spicey_tim_align((int64_t)p.reqs.size() * (int64_t)sizeof(SpiceyTimDevReq));
+  p.off_reqs = spicey_meas_align((int64_t)p.edges.size() * (int64_t)sizeof(SpiceyTimDevEdge));
+  p.head_bytes = p.off_reqs + spicey_meas_align((int64_t)p.reqs.size() * (int64_t)sizeof(SpiceyTimDevReq));
   return true;
 }
 

@@ -137,23 +137,8 @@ def _src_layout(src: np.ndarray, f: abi.FlatCircuit, steps: int) -> bool:
 
 
 def _reqs(reqs, dtype=abi.MEAS_REQ_DTYPE) -> np.ndarray:
-    """A request list as one contiguous array of SpiceyMeasReq records (abi.MEAS_REQ_DTYPE)."""
+    """A request list as one contiguous array of records of `dtype` (abi.MEAS_REQ_DTYPE, FOUR_, TIMING_, AC_MEAS_REQ_DTYPE)."""
     return np.ascontiguousarray(reqs, dtype=dtype).reshape(-1)
-
-
-def _ac_reqs(reqs) -> np.ndarray:
-    """A request list as one contiguous array of SpiceyAcMeasReq records (abi.AC_MEAS_REQ_DTYPE)."""
-    return _reqs(reqs, abi.AC_MEAS_REQ_DTYPE)
-
-
-def _four_reqs(reqs) -> np.ndarray:
-    """A request list as one contiguous array of SpiceyFourReq records (abi.FOUR_REQ_DTYPE)."""
-    return _reqs(reqs, abi.FOUR_REQ_DTYPE)
-
-
-def _timing_reqs(reqs) -> np.ndarray:
-    """A request list as one contiguous array of SpiceyTimingReq records (abi.TIMING_REQ_DTYPE)."""
-    return _reqs(reqs, abi.TIMING_REQ_DTYPE)
 
 
 def _reqs_ptr(r: np.ndarray):
@@ -197,18 +182,18 @@ def ac_measure_device(n_inst: int, n_freq: int, d_v: int, n_v: int, d_i: int, n_
                       device: int = 0, stream: int = 0) -> None:
     """The same for an AC sweep's buffers (spicey_ac_measure_device): d_v [n_inst][n_freq][n_v] complex128, d_i likewise or
     0, d_work of `work_bytes` >= ac_measure_workspace_bytes(...)."""
-    _measure_device("spicey_ac_measure_device", (n_inst, n_freq), d_v, n_v, d_i, n_i, _ac_reqs(reqs), d_meas, d_work, work_bytes, device, stream)
+    _measure_device("spicey_ac_measure_device", (n_inst, n_freq), d_v, n_v, d_i, n_i, _reqs(reqs, abi.AC_MEAS_REQ_DTYPE), d_meas, d_work, work_bytes, device, stream)
 
 
 def fourier_row_doubles(reqs) -> int:
     """Doubles of a result row that holds every request of the list: 1 + 2 max n_harm."""
-    r = _four_reqs(reqs)
+    r = _reqs(reqs, abi.FOUR_REQ_DTYPE)
     return 1 + 2 * int(r["n_harm"].max()) if len(r) else 1
 
 
 def fourier_workspace_bytes(n_inst: int, n_points: int, reqs) -> int:
     """spicey_fourier_workspace_bytes: device workspace of fourier_device for this request list; -1 for a refused one."""
-    r = _four_reqs(reqs)
+    r = _reqs(reqs, abi.FOUR_REQ_DTYPE)
     return load().spicey_fourier_workspace_bytes(n_inst, n_points, _reqs_ptr(r), len(r))
 
 
@@ -219,7 +204,7 @@ def fourier_device(n_inst: int, n_points: int, dt: float, d_v: int, n_v: int, d_
     fourier_workspace_bytes(...).  reqs: records of abi.FOUR_REQ_DTYPE.  Enqueued on `stream`, no synchronisation.  A
     refusal raises SpiceyNativeError whose `status` is the library's code (abi.ERR_BAD_DESC for a bad request list)."""
     L = load()
-    r = _four_reqs(reqs)
+    r = _reqs(reqs, abi.FOUR_REQ_DTYPE)
     rc = L.spicey_fourier_device(device, n_inst, n_points, dt, d_v or None, n_v, d_i or None, n_i, _reqs_ptr(r), len(r), d_out or None, out_stride,
                                  d_work or None, work_bytes, stream or None)
     if rc != abi.OK:
@@ -228,7 +213,7 @@ def fourier_device(n_inst: int, n_points: int, dt: float, d_v: int, n_v: int, d_
 
 def timing_workspace_bytes(n_inst: int, n_points: int, reqs) -> int:
     """spicey_timing_workspace_bytes: device workspace of timing_device for this request list; -1 for a refused one."""
-    r = _timing_reqs(reqs)
+    r = _reqs(reqs, abi.TIMING_REQ_DTYPE)
     return load().spicey_timing_workspace_bytes(n_inst, n_points, _reqs_ptr(r), len(r))
 
 
@@ -238,7 +223,7 @@ def timing_device(n_inst: int, n_points: int, dt: float, d_v: int, n_v: int, d_i
     [n_inst][n_points][n_v], d_i [n_inst][n_points][n_i] or 0, d_out [n_inst][n_req][8], d_work of `work_bytes` >=
     timing_workspace_bytes(...).  reqs: records of abi.TIMING_REQ_DTYPE.  Enqueued on `stream`, no synchronisation.  A
     refusal raises SpiceyNativeError whose `status` is the library's code (abi.ERR_BAD_DESC for a bad request list)."""
-    _measure_device("spicey_timing_device", (n_inst, n_points, dt), d_v, n_v, d_i, n_i, _timing_reqs(reqs), d_out, d_work, work_bytes, device, stream)
+    _measure_device("spicey_timing_device", (n_inst, n_points, dt), d_v, n_v, d_i, n_i, _reqs(reqs, abi.TIMING_REQ_DTYPE), d_out, d_work, work_bytes, device, stream)
 
 
 class Handle:
@@ -319,47 +304,47 @@ class Handle:
                 res["lin_err"] = le
         return res
 
+    def _run_reduced(self, entry: int, steps: int, dt: float, src: np.ndarray, reqs, freqs, treqs, want_iters: bool) -> dict:
+        """What run_measure (entry 0), run_measure_fourier (1) and run_measure_timing (2) share: the result arrays of the passes
+        that entry has — an empty list of an earlier pass goes down as a null out pointer — its C function, and the dressing."""
+        f = self.flat
+        src = np.ascontiguousarray(src, dtype=np.float64)
+        per_inst = _src_layout(src, f, steps)
+        fr = _reqs(freqs, abi.FOUR_REQ_DTYPE)
+        stride = fourier_row_doubles(fr)
+        # per pass: result key, request list, row length
+        passes = [("meas", _reqs(reqs), 8), ("four", fr, stride), ("timing", _reqs(treqs, abi.TIMING_REQ_DTYPE), 8)][:entry + 1]
+        res = {"status": 0, "detail": ""}
+        args = []
+        for k, (key, r, row) in enumerate(passes):
+            res[key] = np.zeros((f.n_inst, len(r), row))
+            args += [_reqs_ptr(r), len(r), _p(res[key], C.c_double) if len(r) or k == entry else None]
+            if key == "four":
+                args.append(stride)
+        iters = np.zeros((f.n_inst, steps + 1), np.int32) if want_iters else None
+        fn = (self.L.spicey_run_measure, self.L.spicey_run_measure_fourier, self.L.spicey_run_measure_timing)[entry]
+        rc = fn(self.h, steps, dt, _p(src, C.c_double), 1 if per_inst else 0, *args, _p(iters, C.c_int32))
+        res.update(status=rc, detail=self.error() if rc != abi.OK else "", iters=iters, partial=True)
+        kept = rc in (abi.OK, abi.ERR_SINGULAR)
+        if kept:
+            for key, last_ms in (("measure_ms", self.L.spicey_last_measure_ms), ("fourier_ms", self.L.spicey_last_fourier_ms),
+                                 ("timing_ms", self.L.spicey_last_timing_ms))[:entry + 1]:
+                res[key] = last_ms(self.h)
+        return self._dress(res, rc, kept, kept)
+
     def run_measure(self, steps: int, dt: float, src: np.ndarray, reqs, want_iters: bool = True) -> dict:
         """spicey_run_measure: the transient with its waveforms kept on the device and reduced there; only `meas`
         [n_inst][n_req][8] (include/spicey_hip.h) and the iteration counts come back.  reqs: records of abi.MEAS_REQ_DTYPE
         (spicey_amd/measure.py), columns as in this handle's out_v / out_i.  Like run() with per-instance tables, the rows of
         the instances that finished are also there after a singular run (`inst_status`); `partial` says so."""
-        f = self.flat
-        src = np.ascontiguousarray(src, dtype=np.float64)
-        per_inst = _src_layout(src, f, steps)
-        r = _reqs(reqs)
-        meas = np.zeros((f.n_inst, len(r), 8))
-        iters = np.zeros((f.n_inst, steps + 1), np.int32) if want_iters else None
-        rc = self.L.spicey_run_measure(self.h, steps, dt, _p(src, C.c_double), 1 if per_inst else 0, _reqs_ptr(r), len(r),
-                                       _p(meas, C.c_double), _p(iters, C.c_int32))
-        res = {"status": rc, "detail": self.error() if rc != abi.OK else "", "meas": meas, "iters": iters, "partial": True}
-        kept = rc in (abi.OK, abi.ERR_SINGULAR)
-        if kept:
-            res["measure_ms"] = self.L.spicey_last_measure_ms(self.h)
-        return self._dress(res, rc, kept, kept)
+        return self._run_reduced(0, steps, dt, src, reqs, [], [], want_iters)
 
     def run_measure_fourier(self, steps: int, dt: float, src: np.ndarray, reqs, freqs, want_iters: bool = True) -> dict:
         """spicey_run_measure_fourier: run_measure with the harmonics pass behind the measurements, over the same device
         waveforms.  reqs: records of abi.MEAS_REQ_DTYPE (may be empty), freqs: records of abi.FOUR_REQ_DTYPE (at least one).
         Beside what run_measure returns: `four` [n_inst][n_four][1 + 2 max n_harm] = {C0, C1, S1, ...} per request, the rest
         of a row 0 (include/spicey_hip.h), and `fourier_ms`."""
-        f = self.flat
-        src = np.ascontiguousarray(src, dtype=np.float64)
-        per_inst = _src_layout(src, f, steps)
-        r, fr = _reqs(reqs), _four_reqs(freqs)
-        stride = fourier_row_doubles(fr)
-        meas = np.zeros((f.n_inst, len(r), 8))
-        four = np.zeros((f.n_inst, len(fr), stride))
-        iters = np.zeros((f.n_inst, steps + 1), np.int32) if want_iters else None
-        rc = self.L.spicey_run_measure_fourier(self.h, steps, dt, _p(src, C.c_double), 1 if per_inst else 0, _reqs_ptr(r), len(r),
-                                               _p(meas, C.c_double) if len(r) else None, _reqs_ptr(fr), len(fr), _p(four, C.c_double), stride,
-                                               _p(iters, C.c_int32))
-        res = {"status": rc, "detail": self.error() if rc != abi.OK else "", "meas": meas, "four": four, "iters": iters, "partial": True}
-        kept = rc in (abi.OK, abi.ERR_SINGULAR)
-        if kept:
-            res["measure_ms"] = self.L.spicey_last_measure_ms(self.h)
-            res["fourier_ms"] = self.L.spicey_last_fourier_ms(self.h)
-        return self._dress(res, rc, kept, kept)
+        return self._run_reduced(1, steps, dt, src, reqs, freqs, [], want_iters)
 
     def run_measure_timing(self, steps: int, dt: float, src: np.ndarray, reqs, freqs, treqs, want_iters: bool = True) -> dict:
         """spicey_run_measure_timing: run_measure_fourier with the edge-timing pass behind the other two, over the same device
@@ -367,27 +352,7 @@ class Handle:
         treqs: records of abi.TIMING_REQ_DTYPE (at least one).  Beside what run_measure_fourier returns: `timing`
         [n_inst][n_timing][8] = {k_trig, t_trig, L_trig, k_targ, t_targ, L_targ, n_trig, n_targ} (include/spicey_hip.h) and
         `timing_ms`."""
-        f = self.flat
-        src = np.ascontiguousarray(src, dtype=np.float64)
-        per_inst = _src_layout(src, f, steps)
-        r, fr, tr = _reqs(reqs), _four_reqs(freqs), _timing_reqs(treqs)
-        stride = fourier_row_doubles(fr)
-        meas = np.zeros((f.n_inst, len(r), 8))
-        four = np.zeros((f.n_inst, len(fr), stride))
-        timing = np.zeros((f.n_inst, len(tr), 8))
-        iters = np.zeros((f.n_inst, steps + 1), np.int32) if want_iters else None
-        rc = self.L.spicey_run_measure_timing(self.h, steps, dt, _p(src, C.c_double), 1 if per_inst else 0, _reqs_ptr(r), len(r),
-                                              _p(meas, C.c_double) if len(r) else None, _reqs_ptr(fr), len(fr),
-                                              _p(four, C.c_double) if len(fr) else None, stride, _reqs_ptr(tr), len(tr), _p(timing, C.c_double),
-                                              _p(iters, C.c_int32))
-        res = {"status": rc, "detail": self.error() if rc != abi.OK else "", "meas": meas, "four": four, "timing": timing, "iters": iters,
-               "partial": True}
-        kept = rc in (abi.OK, abi.ERR_SINGULAR)
-        if kept:
-            res["measure_ms"] = self.L.spicey_last_measure_ms(self.h)
-            res["fourier_ms"] = self.L.spicey_last_fourier_ms(self.h)
-            res["timing_ms"] = self.L.spicey_last_timing_ms(self.h)
-        return self._dress(res, rc, kept, kept)
+        return self._run_reduced(2, steps, dt, src, reqs, freqs, treqs, want_iters)
 
     def run_device(self, steps: int, dt: float, d_src: int, d_out_v: int, d_out_i: int = 0, d_iters: int = 0, stream: int = 0,
                    src_per_inst: bool = False) -> None:
@@ -645,7 +610,7 @@ class AcHandle:
         [n_inst][n_req][8] (include/spicey_hip.h) comes back, also after a failing sweep (`inst_status` names the instances
         whose rows are undefined).  reqs: records of abi.AC_MEAS_REQ_DTYPE, columns as in this handle's out_v / out_i."""
         freqs, ph = self._sweep_args(freqs, vph)
-        r = _ac_reqs(reqs)
+        r = _reqs(reqs, abi.AC_MEAS_REQ_DTYPE)
         meas = np.zeros((self.flat.n_inst, len(r), 8))
         rc = self.L.spicey_ac_run_measure(self.h, len(freqs), _p(freqs, C.c_double), _p(ph.view(np.float64), C.c_double), _reqs_ptr(r), len(r),
                                           _p(meas, C.c_double))
@@ -718,17 +683,18 @@ class HipBackend(_AcCalls):
             want_iters: bool = True) -> dict:
         return self._on_handle(flat, lambda h: h.run(steps, dt, src, want_currents, want_iters))
 
+    def _reduced(self, method: str, flat: abi.FlatCircuit, *args) -> dict:
+        """Handle.<method>(*args) on a handle of its own: the waveforms never leave the device."""
+        return self._on_handle(flat, lambda h: getattr(h, method)(*args))
+
     def run_measure(self, flat: abi.FlatCircuit, steps: int, dt: float, src: np.ndarray, reqs, want_iters: bool = True) -> dict:
-        """Handle.run_measure on a handle of its own: the waveforms never leave the device."""
-        return self._on_handle(flat, lambda h: h.run_measure(steps, dt, src, reqs, want_iters))
+        return self._reduced("run_measure", flat, steps, dt, src, reqs, want_iters)
 
     def run_measure_fourier(self, flat: abi.FlatCircuit, steps: int, dt: float, src: np.ndarray, reqs, freqs, want_iters: bool = True) -> dict:
-        """Handle.run_measure_fourier on a handle of its own: the waveforms never leave the device."""
-        return self._on_handle(flat, lambda h: h.run_measure_fourier(steps, dt, src, reqs, freqs, want_iters))
+        return self._reduced("run_measure_fourier", flat, steps, dt, src, reqs, freqs, want_iters)
 
     def run_measure_timing(self, flat: abi.FlatCircuit, steps: int, dt: float, src: np.ndarray, reqs, freqs, treqs, want_iters: bool = True) -> dict:
-        """Handle.run_measure_timing on a handle of its own: the waveforms never leave the device."""
-        return self._on_handle(flat, lambda h: h.run_measure_timing(steps, dt, src, reqs, freqs, treqs, want_iters))
+        return self._reduced("run_measure_timing", flat, steps, dt, src, reqs, freqs, treqs, want_iters)
 
 
 class HipAcExactBackend(_AcCalls):

@@ -415,11 +415,7 @@ class _Plan:
         return self.reqs.tobytes() + b"|" + self.freqs.tobytes() + (b"|" + self.treqs.tobytes() if len(self.treqs) else b"")
 
     def run(self, be, flat: abi.FlatCircuit, steps: int, dt: float, src: np.ndarray) -> dict:
-        if len(self.treqs):
-            return backend_measure_timing(be, flat, steps, dt, src, self.reqs, self.freqs, self.treqs, self.need_i)
-        if len(self.freqs):
-            return backend_measure_fourier(be, flat, steps, dt, src, self.reqs, self.freqs, self.need_i)
-        return backend_measure(be, flat, steps, dt, src, self.reqs, self.need_i)
+        return backend_reduce(be, flat, steps, dt, src, self.reqs, self.freqs, self.treqs, self.need_i)
 
     def values(self, res: dict, j: int, dt: float) -> Dict[str, dict]:
         """Instance j of a result (meas [n_inst][n_req][8], four [n_inst][n_four][row], timing [n_inst][n_timing][8]) ->
@@ -482,6 +478,17 @@ def derive_timing(spec, rows) -> dict:
             "count_targ": int(r[7])}
 
 
+def _signal_samples(out_v: np.ndarray, out_i: Optional[np.ndarray], req, who: str) -> np.ndarray:
+    """The signal a request (or an edge of one) names over the whole run, [n_inst][n_points]: column `col` of out_v or out_i,
+    minus column `col_ref` if there is one."""
+    a = out_i if int(req["signal"]) == 1 else out_v
+    if a is None:
+        raise ValueError(f"{who}: a request names a current, but there is no out_i")
+    a = np.asarray(a, dtype=np.float64)
+    x = a[:, :, int(req["col"])]
+    return x - a[:, :, int(req["col_ref"])] if int(req["col_ref"]) >= 0 else x
+
+
 def reduce_reference_timing(out_v: np.ndarray, out_i: Optional[np.ndarray], reqs, dt: float) -> np.ndarray:
     """The definition of spicey_timing_device in numpy, independent of the kernels: out_v [n_inst][n_points][n_v], out_i
     likewise or None, reqs records of abi.TIMING_REQ_DTYPE (step_to / base_to resolved or -1) -> [n_inst][n_req][8] =
@@ -491,14 +498,6 @@ def reduce_reference_timing(out_v: np.ndarray, out_i: Optional[np.ndarray], reqs
     out_v = np.asarray(out_v, dtype=np.float64)
     ni, n_points = out_v.shape[0], out_v.shape[1]
     out = np.zeros((ni, len(reqs), 8))
-
-    def samples(e, r):
-        a = out_i if int(e["signal"]) == 1 else out_v
-        if a is None:
-            raise ValueError("reduce_reference_timing: a request names a current, but there is no out_i")
-        a = np.asarray(a, dtype=np.float64)
-        x = a[:, :, int(e["col"])]
-        return x - a[:, :, int(e["col_ref"])] if int(e["col_ref"]) >= 0 else x
 
     def level(e, xi, r):
         kind, frac = int(e["level_kind"]), float(e["level"])
@@ -544,8 +543,8 @@ def reduce_reference_timing(out_v: np.ndarray, out_i: Optional[np.ndarray], reqs
         s1 = n_points - 1 if int(q["step_to"]) == -1 else int(q["step_to"])
         if not (0 <= s0 < s1 < n_points):
             raise ValueError(f"reduce_reference_timing: request {r}: window [{s0}, {s1}] outside the run or without an interval")
-        x_targ = samples(q["targ"], r)
-        x_trig = samples(q["trig"], r) if int(q["has_trig"]) else None
+        x_targ = _signal_samples(out_v, out_i, q["targ"], "reduce_reference_timing")
+        x_trig = _signal_samples(out_v, out_i, q["trig"], "reduce_reference_timing") if int(q["has_trig"]) else None
         for i in range(ni):
             row = [-1.0, -1.0, 0.0, -1.0, -1.0, 0.0, 0.0, 0.0]
             k0 = s0
@@ -565,20 +564,6 @@ def reduce_reference_timing(out_v: np.ndarray, out_i: Optional[np.ndarray], reqs
     return out
 
 
-def backend_measure_timing(be, flat: abi.FlatCircuit, steps: int, dt: float, src: np.ndarray, reqs: np.ndarray, freqs: np.ndarray, treqs: np.ndarray,
-                           need_i: bool) -> dict:
-    """The backend's run_measure_timing, or for a backend without one its run followed by the numpy reductions."""
-    if hasattr(be, "run_measure_timing"):
-        return be.run_measure_timing(flat, steps, dt, src, reqs, freqs, treqs)
-    res = be.run(flat, steps, dt, src, want_currents=need_i)
-    if res["status"] == abi.OK or (res["status"] == abi.ERR_SINGULAR and res.get("partial")):
-        ni = res["out_v"].shape[0]
-        res["meas"] = reduce_reference(res["out_v"], res.get("out_i"), reqs, dt) if len(reqs) else np.zeros((ni, 0, 8))
-        res["four"] = reduce_reference_fourier(res["out_v"], res.get("out_i"), freqs, dt) if len(freqs) else np.zeros((ni, 0, 1))
-        res["timing"] = reduce_reference_timing(res["out_v"], res.get("out_i"), treqs, dt)
-    return res
-
-
 def reduce_reference(out_v: np.ndarray, out_i: Optional[np.ndarray], reqs, dt: float) -> np.ndarray:
     """The definition of spicey_measure_device in numpy, independent of the kernels: out_v [n_inst][n_points][n_v], out_i
     likewise or None, reqs records of abi.MEAS_REQ_DTYPE with step_to resolved or -1 -> meas [n_inst][n_req][8].  The sums
@@ -588,17 +573,12 @@ def reduce_reference(out_v: np.ndarray, out_i: Optional[np.ndarray], reqs, dt: f
     ni, n_points = out_v.shape[0], out_v.shape[1]
     meas = np.zeros((ni, len(reqs), 8))
     for r, q in enumerate(reqs):
-        a = out_i if int(q["signal"]) == 1 else out_v
-        if a is None:
-            raise ValueError("reduce_reference: a request names a current, but there is no out_i")
-        a = np.asarray(a, dtype=np.float64)
+        x = _signal_samples(out_v, out_i, q, "reduce_reference")
         s0 = int(q["step_from"])
         s1 = n_points - 1 if int(q["step_to"]) == -1 else int(q["step_to"])
         if not (0 <= s0 <= s1 < n_points):
             raise ValueError(f"reduce_reference: request {r}: window [{s0}, {s1}] outside the run")
-        x = a[:, s0:s1 + 1, int(q["col"])]
-        if int(q["col_ref"]) >= 0:
-            x = x - a[:, s0:s1 + 1, int(q["col_ref"])]
+        x = x[:, s0:s1 + 1]
         for i in range(ni):
             xi = x[i]
             if int(q["kind"]) == abi.MEAS_STATS:
@@ -651,17 +631,12 @@ def reduce_reference_fourier(out_v: np.ndarray, out_i: Optional[np.ndarray], req
     rows = np.zeros((ni, len(reqs), width))
     tw_cache: Dict[tuple, tuple] = {}
     for r, q in enumerate(reqs):
-        a = out_i if int(q["signal"]) == 1 else out_v
-        if a is None:
-            raise ValueError("reduce_reference_fourier: a request names a current, but there is no out_i")
-        a = np.asarray(a, dtype=np.float64)
+        x = _signal_samples(out_v, out_i, q, "reduce_reference_fourier")
         s0, H, f0 = int(q["step_from"]), int(q["n_harm"]), float(q["f0"])
         s1 = n_points - 1 if int(q["step_to"]) == -1 else int(q["step_to"])
         if not (0 <= s0 < s1 < n_points) or not 1 <= H <= abi.FOUR_MAX_HARM:
             raise ValueError(f"reduce_reference_fourier: request {r}: window [{s0}, {s1}) outside the run, or n_harm {H}")
-        x = a[:, s0:s1, int(q["col"])]
-        if int(q["col_ref"]) >= 0:
-            x = x - a[:, s0:s1, int(q["col_ref"])]
+        x = x[:, s0:s1]
         key = (f0, s0, s1, H)
         if key not in tw_cache:
             hs = np.arange(1, H + 1, dtype=np.int64)[:, None] * np.arange(s0, s1, dtype=np.int64)[None, :]
@@ -678,24 +653,18 @@ def reduce_reference_fourier(out_v: np.ndarray, out_i: Optional[np.ndarray], req
     return rows
 
 
-def backend_measure_fourier(be, flat: abi.FlatCircuit, steps: int, dt: float, src: np.ndarray, reqs: np.ndarray, freqs: np.ndarray, need_i: bool) -> dict:
-    """The backend's run_measure_fourier, or for a backend without one its run followed by both numpy reductions."""
-    if hasattr(be, "run_measure_fourier"):
-        return be.run_measure_fourier(flat, steps, dt, src, reqs, freqs)
+def backend_reduce(be, flat: abi.FlatCircuit, steps: int, dt: float, src: np.ndarray, reqs: np.ndarray, freqs: np.ndarray, treqs: np.ndarray,
+                   need_i: bool) -> dict:
+    """The backend's run_measure_timing, run_measure_fourier or run_measure — the first whose own list is not empty — or for
+    a backend without that method its run followed by the numpy reductions of that method's passes."""
+    method, args = ("run_measure_timing", (reqs, freqs, treqs)) if len(treqs) else ("run_measure_fourier", (reqs, freqs)) if len(freqs) else \
+        ("run_measure", (reqs,))
+    if hasattr(be, method):
+        return getattr(be, method)(flat, steps, dt, src, *args)
     res = be.run(flat, steps, dt, src, want_currents=need_i)
     if res["status"] == abi.OK or (res["status"] == abi.ERR_SINGULAR and res.get("partial")):
-        res["meas"] = reduce_reference(res["out_v"], res.get("out_i"), reqs, dt) if len(reqs) else np.zeros((res["out_v"].shape[0], 0, 8))
-        res["four"] = reduce_reference_fourier(res["out_v"], res.get("out_i"), freqs, dt)
-    return res
-
-
-def backend_measure(be, flat: abi.FlatCircuit, steps: int, dt: float, src: np.ndarray, reqs: np.ndarray, need_i: bool) -> dict:
-    """The backend's run_measure, or for a backend without one its run followed by reduce_reference."""
-    if hasattr(be, "run_measure"):
-        return be.run_measure(flat, steps, dt, src, reqs)
-    res = be.run(flat, steps, dt, src, want_currents=need_i)
-    if res["status"] == abi.OK or (res["status"] == abi.ERR_SINGULAR and res.get("partial")):
-        res["meas"] = reduce_reference(res["out_v"], res.get("out_i"), reqs, dt)
+        for key, fn, lst in zip(("meas", "four", "timing"), (reduce_reference, reduce_reference_fourier, reduce_reference_timing), args):
+            res[key] = fn(res["out_v"], res.get("out_i"), lst, dt)  # (an empty list: [n_inst][0][8], [n_inst][0][1])
     return res
 
 

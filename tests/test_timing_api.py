@@ -241,8 +241,7 @@ class _Spy:
     def _reduced(self, which, flat, steps, dt, src, reqs, freqs, treqs):
         self.calls.append(which)
         need_i = any((r["signal"] == 1).any() for r in (reqs, freqs) if len(r)) or (len(treqs) and bool(((treqs["targ"]["signal"] == 1) | ((treqs["trig"]["signal"] == 1) & (treqs["has_trig"] == 1))).any()))
-        return M.backend_measure_timing(self.be, flat, steps, dt, src, reqs, freqs, treqs, need_i) if len(treqs) else \
-            M.backend_measure_fourier(self.be, flat, steps, dt, src, reqs, freqs, need_i) if len(freqs) else M.backend_measure(self.be, flat, steps, dt, src, reqs, need_i)
+        return M.backend_reduce(self.be, flat, steps, dt, src, reqs, freqs, treqs, need_i)
 
     def run_measure(self, flat, steps, dt, src, reqs):
         return self._reduced("run_measure", flat, steps, dt, src, reqs, M.make_four_reqs([]), M.make_timing_reqs([]))
