@@ -10,7 +10,7 @@
 // SPICEY_HD / Exec.phase() arrangement as tran_exec.h); diodes and switches do not take part (the reference's AC
 // analysis ignores them), so the program is built from the descriptor with nS = nD = 0.
 #pragma once
-#include "tran_exec.h"
+#include "tran_common.h"
 
 #define SPICEY_ERR_COMPLEX_DIV_CODE 5
 

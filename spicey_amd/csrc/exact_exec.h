@@ -25,7 +25,7 @@
 
 #include "exact_plan.h"
 #include "program.h"
-#include "tran_exec.h"
+#include "tran_common.h"
 
 
 // fdlibm e_exp.c (Sun Microsystems, 1993/2004), as V8 runs it for Math.exp: argument reduction by ln2 hi/lo, degree-5

@@ -25,8 +25,11 @@
 // release / acquire, the same form as the group barrier); a workgroup's own consecutive fronts need a workgroup
 // barrier only.  Every sum has a fixed order that does not depend on G: results are bit-identical for every G.
 #pragma once
+#include <stdint.h>
 
 #include "fronts_exec_consts.h"
+#include "program.h"
+#include "tran_common.h"
 
 template <class Exec>
 struct FrontsRun {

@@ -1,0 +1,180 @@
+// tran_common.h — what every executor header shares (tran_exec.h is the map): SPICEY_HD, the device / host macro
+// pairs, the phase tags, the workgroup context, and the element models.
+#pragma once
+#include <math.h>
+#include <stddef.h>
+#include <stdint.h>
+
+#include "program.h"
+
+#if defined(__HIPCC__)
+#define SPICEY_HD __host__ __device__ __forceinline__
+#else
+#define SPICEY_HD inline
+#endif
+#ifndef SPICEY_EXP
+#define SPICEY_EXP 0  // timing experiments only (tools/exp_build.sh): bit0 no result stores, bit1 no diode section, bit2 no capacitor section, bit3 no parameter loads, bit4 no voltage / resistor section, bit5 no remainder loops
+#endif
+#ifndef SPICEY_MARK_TID
+#define SPICEY_MARK_TID 0
+#endif
+#if (SPICEY_EXP & 64) && defined(__HIP_DEVICE_COMPILE__)
+#define SPICEY_MARK(c, n) do { if ((c).zprof && threadIdx.x == (SPICEY_MARK_TID)) { unsigned long long t_ = clock64(); if ((n) < 15) (c).zprof[n] += t_ - (c).zprof[15]; (c).zprof[15] = t_; } } while (0)
+#else
+#define SPICEY_MARK(c, n) do { } while (0)
+#endif
+#if defined(__HIP_DEVICE_COMPILE__)
+#define SPICEY_UNIFORM(x) __builtin_amdgcn_readfirstlane(x)  // value is wave-uniform by construction
+// Keeps a register-resident packed word packed: without this hipcc hoists the field decode (8+ VGPRs and
+// a mask pair per record) out of the time loop and spills.
+#define SPICEY_OPAQUE(x) asm volatile("" : "+v"(x))
+// Same for wave-uniform values (instance index): per-instance base pointers derived from it are then formed
+// inside the phase that needs them instead of living in (spilled) SGPRs across the whole time loop.
+#define SPICEY_OPAQUE_S(x) asm volatile("" : "+s"(x))
+// wave vote: true if the condition holds in any active lane (a scalar branch: whole waves skip work nobody needs)
+#define SPICEY_WAVE_ANY(c) (__builtin_amdgcn_ballot_w64(c) != 0ull)
+// result streams are written once and never read by the kernel: non-temporal stores keep them from evicting the
+// L2-resident program / parameter lines
+#if SPICEY_EXP & 1
+#define SPICEY_STREAM_STORE(ptr, val) do { if ((val) == 1.2345e-300) __builtin_nontemporal_store((val), (ptr)); } while (0)
+#else
+#define SPICEY_STREAM_STORE(ptr, val) __builtin_nontemporal_store((val), (ptr))
+#endif
+// diagnostics (SpiceyRun::skip_risk / lin_err): 64-bit integer atomics on global memory; the maximum over a wave by
+// cross-lane shuffles (every lane of the wave must arrive: call it outside divergent branches); one lane per wave reports
+#define SPICEY_ATOMIC_ADD_U64(p, v) atomicAdd((unsigned long long *)(p), (unsigned long long)(v))
+#define SPICEY_ATOMIC_MAX_U64(p, v) atomicMax((unsigned long long *)(p), (unsigned long long)(v))
+static __device__ __forceinline__ double spicey_wave_max(double x) {
+  for (int off = 32; off > 0; off >>= 1) {
+    const double y = __shfl_xor(x, off);
+    x = (y > x) ? y : x;
+  }
+  return x;
+}
+#define SPICEY_WAVE_MAX(x) spicey_wave_max(x)
+#define SPICEY_WAVE_LEADER(tid) (((tid) & 63) == 0)
+// cross-lane moves that do not go through the LDS crossbar (used on dependent chains of the dense fronts):
+// the value of ONE lane to all (wave-uniform: two v_readlane into scalars) ...
+static __device__ __forceinline__ double spicey_readlane_f64(double v, int lane) {
+  int lo = __builtin_amdgcn_readlane(__double2loint(v), lane), hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
+  asm volatile("" : "+v"(lo), "+v"(hi));  // back into vector registers at once: the kernels that use this have no scalar registers to spare
+  return __hiloint2double(hi, lo);
+}
+// ... and the value of lane q of every quad (4 consecutive lanes) to the quad (DPP quad_perm: a VALU move)
+template <int Q>
+static __device__ __forceinline__ double spicey_quad_bcast_q(double v) {
+  const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), Q * 0x55, 0xf, 0xf, true);
+  const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), Q * 0x55, 0xf, 0xf, true);
+  return __hiloint2double(hi, lo);
+}
+static __device__ __forceinline__ double spicey_quad_bcast_f64(double v, int q) {
+  switch (q & 3) {
+    case 0: return spicey_quad_bcast_q<0>(v);
+    case 1: return spicey_quad_bcast_q<1>(v);
+    case 2: return spicey_quad_bcast_q<2>(v);
+    default: return spicey_quad_bcast_q<3>(v);
+  }
+}
+#define SPICEY_NOUNROLL _Pragma("unroll 1")  // thread-strided loops run 1-2 trips: unrolling only costs VGPRs
+#define SPICEY_UNROLL _Pragma("unroll")      // small fixed-trip loops over a register array: without it the array is indexed through s_set_gpr_idx
+#define SPICEY_SCHED_FENCE __builtin_amdgcn_sched_barrier(0)  // keep the K instances' code from being interleaved
+#else
+#define SPICEY_NOUNROLL
+#define SPICEY_UNROLL
+#define SPICEY_SCHED_FENCE
+#define SPICEY_UNIFORM(x) (x)
+#define SPICEY_OPAQUE(x) (void)(x)
+#define SPICEY_OPAQUE_S(x) (void)(x)
+#define SPICEY_WAVE_ANY(c) true
+#define SPICEY_STREAM_STORE(ptr, val) (*(ptr) = (val))
+#define SPICEY_ATOMIC_ADD_U64(p, v) (*(p) += (unsigned long long)(v))
+#define SPICEY_ATOMIC_MAX_U64(p, v) do { if ((unsigned long long)(v) > *(p)) *(p) = (unsigned long long)(v); } while (0)
+#define SPICEY_WAVE_MAX(x) (x)  // (the emulator runs one thread at a time: every thread reports for itself)
+#define SPICEY_WAVE_LEADER(tid) true
+#endif
+
+// phase tags (profiling slots, SpiceyRun::prof)
+#define SPICEY_PH_PRO 0
+#define SPICEY_PH_B 1
+#define SPICEY_PH_S 2
+#define SPICEY_PH_A 3
+#define SPICEY_PH_Z 4
+#define SPICEY_PH_U0 8
+#define SPICEY_PH_K0 40
+
+template <int K>
+struct WgCtx {
+  double *W;     // [nW][K]   L+U entries, then rhs / x'
+  double *G;     // hybrid workspace (SpiceyProg::hybrid): leaf-owned entries in global memory, [nLU][K] by entry id; else null
+  double *u;     // [nU][K]   vPrev | iPrev | V(t) | diode ieq
+  double *gd;    // [nGdyn][K] switch conductances | diode gd
+  int32_t *ison; // [nS][K]
+  int32_t *flags;  // [0] switched, [1] singular code, [2] singular inst
+  uint32_t *tail;  // [tail_n][64][4] task records of the tail phases (v2), or null
+#if SPICEY_EXP & 64
+  unsigned long long *zprof;  // experiment builds: 16 profiling slots for marks inside B / Z ([15] = last timestamp)
+#endif
+  int32_t inst[K];
+  int32_t valid[K];
+};
+
+// A copy of an argument struct that lives in global memory, through an address the compiler cannot trace back: the fields
+// the surrounding code uses are scalar-loaded HERE (s_load, scalar cache), the rest of the copy is dead (see GpuExecV2::fresh).
+// On the host (the emulator) it is the struct itself.
+template <class X>
+SPICEY_HD X spicey_fresh(const X &x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  typedef const X __attribute__((address_space(4))) *cptr;
+  cptr p = (cptr)(&x);
+  asm volatile("" : "+s"(p));
+  X v;
+  __builtin_memcpy(&v, p, sizeof(X));
+  return v;
+#else
+  return x;
+#endif
+}
+
+// 1/x for pivots: hardware reciprocal seed + two Newton steps (<= 1 ulp; the result feeds a 1e-9 parity
+// budget, and the reference's own quotient order differs anyway).  The IEEE-exact quotient hipcc emits
+// for `1.0 / x` is ~3x longer and sits on the critical path of every factor level.
+SPICEY_HD double spicey_rcp(double x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  double r = __builtin_amdgcn_rcp(x);
+  r = fma(fma(-x, r, 1.0), r, r);
+  r = fma(fma(-x, r, 1.0), r, r);
+  return r;
+#else
+  return 1.0 / x;
+#endif
+}
+
+SPICEY_HD double spicey_max_nan(double a, double b) {  // Math.max semantics
+  return (a > b || a != a) ? a : b;
+}
+
+// Diode companion model, simulateTRAN.ts:87-98, and (when `want_i`) the recorded current of :214-217,
+// which uses the UNCLAMPED junction voltage.  One exp serves both whenever vd lies inside the clamp
+// window [-1, 0.8].  The per-diode constants 1/(N VT) and Is/(N VT) are formed once per evaluation
+// from Is, N (two divisions); callers on the hot path pass them precomputed.
+SPICEY_HD void spicey_diode_k(double vd, double is, double inv_vt, double is_vt, bool want_i, double &gd, double &ieq, double &irec) {
+  double vl = vd;
+  if (vd > 0.8) vl = 0.8;
+  if (vd < -1.0) vl = -1.0;
+  const double e = exp(vl * inv_vt);
+  const double id = is * (e - 1.0);
+  gd = spicey_max_nan(is_vt * e, 1e-12);
+  ieq = id - gd * vl;
+  irec = id;
+  if (want_i && vl != vd) irec = is * (exp(vd * inv_vt) - 1.0);
+}
+SPICEY_HD void spicey_diode(double vd, double is, double nn, double &gd, double &ieq) {
+  const double vt = nn * SPICEY_VT300;
+  double irec;
+  spicey_diode_k(vd, is, 1.0 / vt, is / vt, false, gd, ieq, irec);
+}
+
+SPICEY_HD double spicey_switch_g(int on, double ron, double roff) {  // simulateTRAN.ts:59-61
+  const double r = on ? ron : roff;
+  return 1.0 / spicey_max_nan(fabs(r), SPICEY_EPS);
+}

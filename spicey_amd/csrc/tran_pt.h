@@ -1,0 +1,166 @@
+// tran_pt.h — the phase table: layout, lane access, and the prologue that builds it (tran_exec.h is the map).
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+#include <stdlib.h>
+
+#include "program.h"
+#include "tran_common.h"
+
+// ---- run-invariant phase arguments, kept on chip (16-bit interpreter, K = 1, tridiagonal-top builds) -------------------
+// What a phase of the time loop needs from SpiceyProg / SpiceyResident / SpiceyRun never changes during a run, yet every
+// phase of every step used to fetch it again through scalar loads.  Where those loads were CHAINED they stood exposed in
+// front of the phase's first work: three dependent round trips in front of a streamed phase's first record, two in front
+// of Z's parameter fetch, three and four at the heads of B and Z (profiles/NOTES_r04.md).  The prologue now writes the
+// values ONCE into a table in LDS.  A phase head reads them with one ds_read_b32 — lane l reads word l — and moves each
+// word to a scalar by v_readlane (SpiceyPtLanes); the rare reads inside divergent code are same-address broadcast reads.
+// The table lives in space that is reserved already: the tail area of a tridiagonal-top build is 5 KB (launch_plan.cpp),
+// of which the two row buffers take 4 KB and the top's index table pcr_n * 8 <= 512 B.  Layout, in 32-bit words from
+// c.tail + 1024 + (pcr_n * 2 rounded up to 4): SPICEY_PT_RUN run-wide words (below), then one 8-word row per phase that
+// can be streamed — the factor phases [0, pcr_level) and the backward phases [2 nLevels - pcr_level, 2 nLevels) — holding
+// that phase's SpiceyResident::st_desc row.  A program whose rows do not fit (deep elimination trees), one without a top
+// (its tail area is full of tail records) or a handle created with SPICEY_NO_PHASE_TABLE set keeps the scalar loads: both paths
+// are compiled and give identical bits (same operands, same order; only addresses and counts come from elsewhere).
+#define SPICEY_PT_RUN 48
+enum {
+  SPICEY_PT_XOFF = 0, SPICEY_PT_NRESTORE, SPICEY_PT_NDYNENT, SPICEY_PT_NGSTAT, SPICEY_PT_NR, SPICEY_PT_NC, SPICEY_PT_NL, SPICEY_PT_NV,
+  // 64-bit values, two words each.  (Words 8..13: what a streamed phase needs beside its row — SpiceyPtLanes::row.)
+  SPICEY_PT_OVF16 = 8, SPICEY_PT_REC16 = 10, SPICEY_PT_FUS16 = 12,
+  SPICEY_PT_NS = 14, SPICEY_PT_ND, SPICEY_PT_NOUT, SPICEY_PT_NCUR,
+  SPICEY_PT_STEPS = 18, SPICEY_PT_SRC = 20, SPICEY_PT_SRC_STRIDE = 22, SPICEY_PT_OUT_V = 24, SPICEY_PT_OUT_I = 26, SPICEY_PT_GSTAT = 28,
+  SPICEY_PT_DPAR = 30, SPICEY_PT_D_IS = 32, SPICEY_PT_C_VPREV = 34, SPICEY_PT_D_VDPREV = 36, SPICEY_PT_ITERS = 38, SPICEY_PT_LIN_VD = 40,
+  SPICEY_PT_LIN_ERR = 42,
+  SPICEY_PT_USED = 44
+};
+static_assert(SPICEY_PT_USED <= SPICEY_PT_RUN && SPICEY_PT_RUN <= 64 && SPICEY_PT_RUN % 4 == 0, "run-wide block of the phase table: at most one word per lane of a wave");
+SPICEY_HD int spicey_pt_base_words(int pcr_n) { return 1024 + ((pcr_n * 2 + 3) & ~3); }
+// rows of the table of a program with its top at level `pcr_level`, and whether they fit behind the top's index table
+SPICEY_HD int spicey_pt_words(int pcr_level) { return SPICEY_PT_RUN + 16 * pcr_level; }
+SPICEY_HD bool spicey_pt_fits(int pcr_n, int pcr_level, int tail_n) {
+  // (a phase head reads 64 consecutive words from the start of the table, SpiceyPtLanes: with pcr_level >= 1 they lie inside it)
+  return pcr_n > 0 && pcr_n <= 64 && pcr_level >= 1 && tail_n == 0 && spicey_pt_base_words(pcr_n) + spicey_pt_words(pcr_level) <= 5 * 256;
+}
+SPICEY_HD uint32_t spicey_pt_u32(const uint32_t *pt, int i) { return (uint32_t)SPICEY_UNIFORM((int)pt[i]); }
+SPICEY_HD uint64_t spicey_pt_u64(const uint32_t *pt, int i) { return (uint64_t)spicey_pt_u32(pt, i) | ((uint64_t)spicey_pt_u32(pt, i + 1) << 32); }
+template <class X>
+SPICEY_HD X *spicey_pt_ptr(const uint32_t *pt, int i) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  typedef X __attribute__((address_space(1))) *gptr;  // (a global-memory pointer: accesses through it stay global_load / global_store, not flat)
+  return (X *)(gptr)(uintptr_t)spicey_pt_u64(pt, i);
+#else
+  return (X *)(uintptr_t)spicey_pt_u64(pt, i);
+#endif
+}
+SPICEY_HD void spicey_pt_put64(uint32_t *pt, int i, uint64_t v) { pt[i] = (uint32_t)v; pt[i + 1] = (uint32_t)(v >> 32); }
+// (the three above: one word, read by every ACTIVE lane from the same address — for the rare reads inside divergent code)
+// Many words at a phase head, where the whole wave is active: lane l reads word l — ONE ds_read_b32, one vector register —
+// and each word goes to a scalar by v_readlane at a constant lane.  (Broadcast reads would hold a vector register per
+// word until it has been moved: the 128-register builds have none to give.)
+struct SpiceyPtLanes {
+#if defined(__HIP_DEVICE_COMPILE__)
+  int v;
+  __device__ __forceinline__ uint32_t u32(int i) const { return (uint32_t)__builtin_amdgcn_readlane(v, i); }
+#else
+  const uint32_t *run, *rowp;
+  uint32_t u32(int i) const { return (rowp && i < 8) ? rowp[i] : run[i]; }
+#endif
+  SPICEY_HD uint64_t u64(int i) const { return (uint64_t)u32(i) | ((uint64_t)u32(i + 1) << 32); }
+  template <class X>
+  SPICEY_HD X *ptr(int i) const {
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef X __attribute__((address_space(1))) *gptr;
+    return (X *)(gptr)(uintptr_t)u64(i);
+#else
+    return (X *)(uintptr_t)u64(i);
+#endif
+  }
+  // the run-wide block
+  static SPICEY_HD SpiceyPtLanes run_block(const uint32_t *pt, int tid) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return SpiceyPtLanes{(int)pt[tid & 63]};
+#else
+    (void)tid;
+    return SpiceyPtLanes{pt, nullptr};
+#endif
+  }
+  // words 0..7 = row `row` of the per-phase rows, words 8.. = the run-wide block's
+  static SPICEY_HD SpiceyPtLanes row(const uint32_t *pt, int tid, int row) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const int l = tid & 63;
+    return SpiceyPtLanes{(int)pt[l < 8 ? SPICEY_PT_RUN + row * 8 + l : l]};
+#else
+    (void)tid;
+    return SpiceyPtLanes{pt, pt + SPICEY_PT_RUN + row * 8};
+#endif
+  }
+};
+
+// ---- the phase table (see the top of this file) ---------------------------------------------------------------------------
+// Whether a run keeps one is decided on the host.  The GPU kernels are built twice, with the table (PT = 1) and with the
+// scalar loads (PT = 0) — one kernel holding both paths of B and Z does not fit the 128 registers of the two-workgroups-
+// per-CU build —, and spicey_launch_tran_v2 picks the build: spicey_pt_fits and no SPICEY_NO_PHASE_TABLE in the
+// environment of spicey_create.  PT = -1 (the test emulator, which instantiates the interpreter itself) decides per run:
+SPICEY_HD bool spicey_pt_runtime_choice(const SpiceyProg &P, const SpiceyResident &Q) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  (void)P; (void)Q;
+  return false;
+#else
+  return spicey_pt_fits(P.pcr_n, P.pcr_level, Q.tail_n) && getenv("SPICEY_NO_PHASE_TABLE") == nullptr;
+#endif
+}
+// Written once, in the prologue.  Every word of the run-wide block is a 32-bit piece of one field of SpiceyProg or
+// SpiceyRun: lane l copies word l from where the struct lives (a vector load: no scalar registers, which the prologue
+// phase that fills the resident registers has none to spare of either).
+struct SpiceyPtWord {
+  uint16_t from_run;  // 0: SpiceyProg, 1: SpiceyRun
+  uint16_t off;       // byte offset of the word
+};
+#define SPICEY_PT_P32(f) {0, (uint16_t)offsetof(SpiceyProg, f)}
+#define SPICEY_PT_P64(f) {0, (uint16_t)offsetof(SpiceyProg, f)}, {0, (uint16_t)(offsetof(SpiceyProg, f) + 4)}
+#define SPICEY_PT_R64(f) {1, (uint16_t)offsetof(SpiceyRun, f)}, {1, (uint16_t)(offsetof(SpiceyRun, f) + 4)}
+template <int K>
+SPICEY_HD void spicey_pt_build(const SpiceyProg &P, const SpiceyResident &Q, const SpiceyRun &R, const WgCtx<K> &c, int tid, int T) {
+  static constexpr SpiceyPtWord words[SPICEY_PT_USED] = {
+      SPICEY_PT_P32(xoff), SPICEY_PT_P32(nRestore), SPICEY_PT_P32(nDynEnt), SPICEY_PT_P32(nGstat), SPICEY_PT_P32(nR), SPICEY_PT_P32(nC),
+      SPICEY_PT_P32(nL), SPICEY_PT_P32(nV), SPICEY_PT_P64(ovf16), SPICEY_PT_P64(rec16), SPICEY_PT_P64(fus16), SPICEY_PT_P32(nS),
+      SPICEY_PT_P32(nD), SPICEY_PT_P32(nOut), SPICEY_PT_P32(nCur), SPICEY_PT_R64(steps), SPICEY_PT_R64(src), SPICEY_PT_R64(src_stride),
+      SPICEY_PT_R64(out_v), SPICEY_PT_R64(out_i), SPICEY_PT_R64(gstat), SPICEY_PT_R64(dpar), SPICEY_PT_R64(D_is), SPICEY_PT_R64(C_vprev),
+      SPICEY_PT_R64(D_vdprev), SPICEY_PT_R64(iters), SPICEY_PT_R64(lin_vd), SPICEY_PT_R64(lin_err)};
+  uint32_t *pt = c.tail + spicey_pt_base_words(P.pcr_n);
+  if (tid < SPICEY_PT_USED) {
+    const SpiceyPtWord w = words[tid];
+    const char *src = (w.from_run ? (const char *)&R : (const char *)&P) + w.off;
+    uint32_t v;
+    __builtin_memcpy(&v, src, 4);
+    pt[tid] = v;
+  }
+  const int L = P.pcr_level, kb = 2 * P.nLevels - L;  // rows: factor phases [0, L), then backward phases [kb, kb + L)
+  for (int i = tid; i < 2 * L * 8; i += T) {
+    const int r = i >> 3, p = r < L ? r : kb + (r - L);
+    pt[SPICEY_PT_RUN + i] = Q.st_desc[(size_t)p * 8 + (i & 7)];
+  }
+}
+// The fields that the always-executed code of B, Z and Z's parameter prefetch reads (TranPhases2, K = 1, LDS workspace), from
+// the table into two LOCAL structs; every other field stays zero and is never looked at there (TranPhases2::Pg).  What a
+// phase does not use of this is dead code.
+SPICEY_HD void spicey_pt_args(const uint32_t *pt, int tid, SpiceyProg &P, SpiceyRun &R) {
+  const SpiceyPtLanes a = SpiceyPtLanes::run_block(pt, tid);  // (called at a phase head: the whole wave is here)
+  P.xoff = (int32_t)a.u32(SPICEY_PT_XOFF); P.nRestore = (int32_t)a.u32(SPICEY_PT_NRESTORE);
+  P.nDynEnt = (int32_t)a.u32(SPICEY_PT_NDYNENT); P.nGstat = (int32_t)a.u32(SPICEY_PT_NGSTAT);
+  P.nR = (int32_t)a.u32(SPICEY_PT_NR); P.nC = (int32_t)a.u32(SPICEY_PT_NC); P.nL = (int32_t)a.u32(SPICEY_PT_NL);
+  P.nV = (int32_t)a.u32(SPICEY_PT_NV); P.nS = (int32_t)a.u32(SPICEY_PT_NS); P.nD = (int32_t)a.u32(SPICEY_PT_ND);
+  P.nOut = (int32_t)a.u32(SPICEY_PT_NOUT); P.nCur = (int32_t)a.u32(SPICEY_PT_NCUR);
+  R.steps = (int64_t)a.u64(SPICEY_PT_STEPS);
+  R.src = a.template ptr<const double>(SPICEY_PT_SRC);
+  R.src_stride = (int64_t)a.u64(SPICEY_PT_SRC_STRIDE);
+  R.out_v = a.template ptr<double>(SPICEY_PT_OUT_V);
+  R.out_i = a.template ptr<double>(SPICEY_PT_OUT_I);
+  R.gstat = a.template ptr<double>(SPICEY_PT_GSTAT);
+  R.dpar = a.template ptr<double>(SPICEY_PT_DPAR);
+  R.D_is = a.template ptr<const double>(SPICEY_PT_D_IS);
+  R.C_vprev = a.template ptr<double>(SPICEY_PT_C_VPREV);
+  R.D_vdprev = a.template ptr<double>(SPICEY_PT_D_VDPREV);
+  R.iters = a.template ptr<int32_t>(SPICEY_PT_ITERS);
+  R.lin_vd = a.template ptr<double>(SPICEY_PT_LIN_VD);
+  R.lin_err = a.template ptr<unsigned long long>(SPICEY_PT_LIN_ERR);
+}

@@ -1,0 +1,763 @@
+// tran_v2_phases.h — the v2 B / S / Z phases, TranPhases2 (tran_exec.h is the map).
+#pragma once
+#include <math.h>
+#include <stddef.h>
+#include <stdint.h>
+
+#include "program.h"
+#include "tran_common.h"
+#include "tran_pt.h"
+#include "tran_rec16.h"
+#include "tran_v1_phases.h"
+
+// v2 versions of the B and Z phases: everything step-invariant that a thread needs (static entry values,
+// stamp / right-hand-side descriptors, element terminals, vPrev) sits in its registers; items beyond the
+// resident capacity (entries >= NSV*T, rows / elements >= T) take the streamed remainder loops.
+// Difference to v1: u[c] holds the capacitor companion CURRENT gc*vPrev (so the right-hand side is a
+// pure +-1 gather, stampCurrentReal.ts:12-13) and the exact vPrev lives in a register.
+// HYB: the hybrid workspace layout (program.h, SpiceyProg::hybrid) — entry ids below hyb_g0 and in [nRestore, nRestore + hyb_g2)
+// are leaf-owned and live in the global array c.G, all others in LDS at id - hyb_g0 (- hyb_g2 above nRestore); the
+// right-hand side starts at LDS index P.xoff; c.u / c.gd point to global memory.
+template <int K, int RMAX, int NSV, int NEL, bool HYB = false>
+struct TranPhases2 {
+  const SpiceyProg &P;
+  const SpiceyRun &R;
+  WgCtx<K> &c;
+  int T;
+  // where entry `e` (an id below nRestore: what phase B re-stamps) is stored
+  SPICEY_HD void put_entry(uint32_t e, int k, double v) const {
+    if (HYB) {
+      if (e < (uint32_t)P.hyb_g0) c.G[(size_t)e * K + k] = v;
+      else c.W[(size_t)(e - (uint32_t)P.hyb_g0) * K + k] = v;
+    } else {
+      c.W[(size_t)e * K + k] = v;
+    }
+  }
+  // Which of the beyond-resident-capacity loops of B / Z have any work (wave-uniform, fixed for the run).  On the
+  // circuits the resident geometry is sized for they are all empty, yet each one costs a bound fetch, address
+  // arithmetic and a branch: ~1200 cycles per step in Z alone before they were put behind one test.
+  uint32_t brem, zrem;
+  // With the phase table, P and R above are LOCAL structs that hold only the fields the always-executed code of B, Z and
+  // the parameter prefetch reads (spicey_pt_args), and Pg / Rg point to the complete argument structs in global memory:
+  // the beyond-resident-capacity loops and the diagnostics, which read many more fields on few circuits, take a fresh copy
+  // from there inside their own branch (SPICEY_COLD_ARGS).  Null: P and R are complete.
+  const SpiceyProg *Pg = nullptr;
+  const SpiceyRun *Rg = nullptr;
+  // fresh build, for u0_fetch: the phase table (null: none — then Qg, the resident struct where it lives, says where phase
+  // 0's records are)
+  const uint32_t *ptab = nullptr;
+  const SpiceyResident *Qg = nullptr;
+#if defined(__HIP_DEVICE_COMPILE__)
+#define SPICEY_COLD_STRUCT(whole, here) ((whole) ? spicey_fresh(*(whole)) : (here))
+#else
+#define SPICEY_COLD_STRUCT(whole, here) ((whole) ? *(whole) : (here))
+#endif
+#define SPICEY_COLD_ARGS                                             \
+  const SpiceyProg &P = SPICEY_COLD_STRUCT(this->Pg, this->P); \
+  const SpiceyRun &R = SPICEY_COLD_STRUCT(this->Rg, this->R);  \
+  (void)P;                                                           \
+  (void)R
+  typedef ResRegs<K, RMAX, NSV, NEL> Regs;
+  // the diagnostics of SpiceyOptions.diagnostics are compiled into every geometry but the two-workgroups-per-CU one (NSV = 6:
+  // 128 VGPRs and nothing to spare — with them that kernel spills, which the build refuses); the host keeps a handle with
+  // the option out of that geometry
+  static constexpr bool DIAG = !SpiceyShapeKind<RMAX, NSV, NEL>::packed && !HYB;  // (nor into the hybrid-workspace build, for the same reason)
+  // fresh-fill build: B, and the copy that fills the registers it restores from, stop at the kept targets — the fresh class
+  // [nKeep, nRestore) is created by its flagged factor tasks in every solve and nothing reads it before them
+  static constexpr bool FRESH = SpiceyShapeKind<RMAX, NSV, NEL>::fresh;
+  SPICEY_HD int n_stamped() const { return FRESH ? P.nKeep : P.nRestore; }
+  // hybrid builds: items of a beyond-resident loop whose loads are in flight together (the 1024-thread build has 128 registers)
+  static constexpr int BW = NEL >= 2 ? 4 : 2;   // (phase Z)
+  static constexpr int BWB = BW;                 // (phase B; four at a time in the 1024-thread build compiled — 126 registers — and was 5 % slower per step)
+  SPICEY_HD void set_remainders() {
+    brem = (n_stamped() > NSV * T ? 1u : 0u) | (P.nDynX > 0 ? 2u : 0u) | (P.n > NEL * T ? 4u : 0u) | (P.nRowX > 0 ? 8u : 0u) |
+           (P.nDynEnt > Regs::NDD * T ? 16u : 0u);
+    zrem = (P.nOut > NEL * T ? 1u : 0u) | (P.nR > NEL * T ? 2u : 0u) | (P.nC > NEL * T ? 4u : 0u) | (P.nL > 0 ? 8u : 0u) |
+           (P.nV > T ? 16u : 0u) | (P.nS > 0 ? 32u : 0u) | (P.nD > NEL * T ? 64u : 0u);
+    brem = (uint32_t)SPICEY_UNIFORM((int)brem);
+    zrem = (uint32_t)SPICEY_UNIFORM((int)zrem);
+  }
+
+  // branch-free: ground (0xFFFF) reads slot 0, a valid address, and is masked afterwards, so that the reads of
+  // several elements can be issued back to back instead of one exec-masked block each
+  SPICEY_HD double volt16(uint32_t xi, int k) const {
+    const double v = c.W[(size_t)(xi == 0xFFFFu ? 0u : xi) * K + k];
+    return xi == 0xFFFFu ? 0.0 : v;
+  }
+  SPICEY_HD double dv16(uint32_t ab, int k) const { return volt16(ab & 0xFFFFu, k) - volt16(ab >> 16, k); }
+
+  SPICEY_HD void load_resident(int tid, const SpiceyResident &Q, Regs &rr) const {
+    for (int s = 0; s < RMAX; s++) {
+      const bool have = s < Q.rmax;
+      const uint32_t *src = Q.res + ((size_t)(have ? s : 0) * T + tid) * 4;
+      rr.w0[s] = have ? src[0] : 0u; rr.w1[s] = have ? src[1] : 0u; rr.w2[s] = have ? src[2] : 0u; rr.w3[s] = have ? src[3] : 0u;
+    }
+    for (int s4 = 0; s4 < (RMAX + 3) / 4; s4++) {
+      uint32_t pk = 0;
+      for (int b = 0; b < 4; b++) {
+        const int s = s4 * 4 + b;
+        const int ph = s < Q.rmax && s < RMAX ? Q.res_phase[(size_t)(tid >> 6) * Q.rmax + s] : -1;
+        pk |= (uint32_t)(ph < 0 ? 0xff : (ph & 0xff)) << (8 * b);
+      }
+      rr.phv[s4] = SPICEY_UNIFORM((int)pk);
+    }
+    rr.cursor = 0;
+    for (int j = 0; j < NEL; j++) {
+      const int i = tid + j * T;
+      rr.rhs[j][0] = i < P.n ? P.row_desc[(size_t)i * 2] : 0u;
+      rr.rhs[j][1] = i < P.n ? P.row_desc[(size_t)i * 2 + 1] : 0xFFFFFFFFu;  // 0xFFFFFFFF = not a resident row
+      rr.eR[j] = i < P.nR ? P.R_ab[i] : 0xFFFFFFFFu;
+      rr.eC[j] = i < P.nC ? P.C_ab[i] : 0xFFFFFFFFu;
+      rr.eD[j] = i < P.nD ? P.D_ab[i] : 0xFFFFFFFFu;
+      rr.ox[j] = i < P.nOut ? (P.out_x[i] < 0 ? 0xFFFFu : (uint32_t)P.out_x[i]) : 0xFFFFu;
+    }
+    if (tid < P.nV) rr.ox[0] |= (uint32_t)P.V_x[tid] << 16;  // upper half of ox[0]: W index of the branch current of source tid
+  }
+  // after p1_static: static entry values into registers; elements from the state entering the run
+  SPICEY_HD void a0_initial(int tid, Regs &rr) const {
+    const int oL = P.nC, oV = P.nC + P.nL, oD = P.nC + P.nL + P.nV;
+    for (int j = 0; j < NSV; j++) {
+      const int e = tid + j * T;
+      if (j < Regs::NDD) rr.dd[j] = e < n_stamped() ? P.ent_dd[e] : 0x80000000u;  // bit 31 = "not mine to stamp"
+      for (int k = 0; k < K; k++) rr.sv[j][k] = e < n_stamped() ? R.statv[(size_t)c.inst[k] * P.nLU + e] : 0.0;
+    }
+    for (int k = 0; k < K; k++) {  // entries that no phase ever writes: stamped once per run
+      const double *sv = R.statv + (size_t)c.inst[k] * P.nLU;
+      SPICEY_NOUNROLL
+      for (int e = P.nRestore + tid; e < P.nLU; e += T) {
+        if (HYB) {
+          if (e < P.nRestore + P.hyb_g2) c.G[(size_t)e * K + k] = sv[e];  // leaf-owned: read from the global array by phase U_0 / K_0
+          else c.W[(size_t)(e - P.hyb_g0 - P.hyb_g2) * K + k] = sv[e];
+        } else {
+          c.W[(size_t)e * K + k] = sv[e];
+        }
+      }
+    }
+    for (int k = 0; k < K; k++) {
+      const size_t in = (size_t)c.inst[k];
+      const double *g = R.gstat + in * P.nGstat;
+      for (int j = 0; j < NEL; j++) rr.vprev[j][k] = tid + j * T < P.nC ? R.C_vprev[in * P.nC + tid + j * T] : 0.0;
+      SPICEY_NOUNROLL
+      for (int i = tid; i < P.nC; i += T) c.u[(size_t)i * K + k] = g[P.nR + i] * R.C_vprev[in * P.nC + i];
+      SPICEY_NOUNROLL
+      for (int i = tid; i < P.nL; i += T) c.u[(size_t)(oL + i) * K + k] = R.L_iprev[in * P.nL + i];
+      SPICEY_NOUNROLL
+      for (int i = tid; i < P.nV; i += T) c.u[(size_t)(oV + i) * K + k] = R.src[in * R.src_stride + i];
+      SPICEY_NOUNROLL
+      for (int i = tid; i < P.nS; i += T) {
+        const int on = R.S_ison[in * P.nS + i];
+        c.ison[(size_t)i * K + k] = on;
+        c.gd[(size_t)i * K + k] = spicey_switch_g(on, R.S_ron[in * P.nS + i], R.S_roff[in * P.nS + i]);
+      }
+      SPICEY_NOUNROLL
+      for (int i = tid; i < P.nD; i += T) {
+        const double *dp = R.dpar + (in * P.nD + i) * 2;
+        double g2, q, irec;
+        spicey_diode_k(R.D_vdprev[in * P.nD + i], R.D_is[in * P.nD + i], dp[0], dp[1], false, g2, q, irec);
+        c.gd[(size_t)(P.nS + i) * K + k] = g2;
+        c.u[(size_t)(oD + i) * K + k] = q;
+        if (DIAG && R.lin_vd && c.valid[k]) R.lin_vd[in * P.nD + i] = R.D_vdprev[in * P.nD + i];
+      }
+    }
+    if (tid == 0) c.flags[0] = 0;
+  }
+
+  SPICEY_HD void stamp_entry(uint32_t e, uint32_t dd, const double *sv) const {  // sv[K]
+    double v[K];
+    for (int k = 0; k < K; k++) v[k] = sv[k];
+    const uint32_t f0 = dd & 0x7fffu, f1 = (dd >> 15) & 0x7fffu;
+    if (f0) {
+      const uint32_t ix = (f0 & 0x3fffu) - 1;
+      for (int k = 0; k < K; k++) { const double g = c.gd[(size_t)ix * K + k]; v[k] = (f0 & 0x4000u) ? v[k] - g : v[k] + g; }
+    }
+    if (f1) {
+      const uint32_t ix = (f1 & 0x3fffu) - 1;
+      for (int k = 0; k < K; k++) { const double g = c.gd[(size_t)ix * K + k]; v[k] = (f1 & 0x4000u) ? v[k] - g : v[k] + g; }
+    }
+    if (dd & (1u << 30))
+      for (int k = 0; k < K; k++) {
+        if (fabs(v[k]) < SPICEY_EPS && c.valid[k]) { c.flags[1] = 1; c.flags[2] = c.inst[k]; }
+        v[k] = spicey_rcp(v[k]);
+      }
+    for (int k = 0; k < K; k++) put_entry(e, k, v[k]);
+  }
+  SPICEY_HD void rhs_row(uint32_t r, uint32_t d0, uint32_t d1) const {
+    double acc[K];
+    for (int k = 0; k < K; k++) acc[k] = 0.0;
+    const uint32_t f[4] = {d0 & 0xffffu, d0 >> 16, d1 & 0xffffu, d1 >> 16};
+    for (int i = 0; i < 4; i++)
+      if (f[i]) {
+        const uint32_t ix = (f[i] & 0x7fffu) - 1;
+        for (int k = 0; k < K; k++) { const double t = c.u[(size_t)ix * K + k]; acc[k] = (f[i] & 0x8000u) ? acc[k] - t : acc[k] + t; }
+      }
+    for (int k = 0; k < K; k++) c.W[(size_t)(P.xoff + r) * K + k] = acc[k];
+  }
+
+  // ---- B: matrix = static + dynamic stamps; right-hand side -----------------------------------------
+  SPICEY_HD void b_stamp(int tid, Regs &rr, bool reuse = false) const {
+    SPICEY_MARK(c, 15);
+    if (tid == 0) c.flags[0] = 0;
+    rr.cursor = 0;  // a new solve walks the resident slots from the start
+    if (!reuse) stamp_matrix(tid, rr);  // a linear circuit keeps the factors of step 0 in W
+    rhs_rows(tid, rr);
+  }
+  // the whole of phase B: the next step's source values ride on it (a long phase with few live registers): fetched first,
+  // parked in LDS last; Z moves them into place
+  // Fresh build: factor phase 0 is the one phase of the packed chains that is still streamed, and the fetch of its first
+  // record used to be an exposed L2 round trip at its head.  The record (row record `tid` of the phase: 32 bytes) is
+  // loaded here instead, next to the source fetch, and has the whole of B to arrive.  Lanes without a record, and a phase
+  // 0 that is resident or streams generic records, fetch nothing.
+  SPICEY_HD void u0_fetch(int tid, Regs &rr) const {
+    uint32_t rows, first, cnt;
+    const uint32_t *fus16;
+    if (ptab) {
+      const SpiceyPtLanes d = SpiceyPtLanes::row(ptab, tid, 0);  // (row 0 = factor phase 0; the whole wave is here)
+      rows = d.u32(0); first = d.u32(1); cnt = d.u32(2);
+      fus16 = d.template ptr<const uint32_t>(SPICEY_PT_FUS16);
+    } else {
+      const uint32_t *dsc = spicey_fresh(*Qg).st_desc;
+      rows = dsc[0]; first = dsc[1]; cnt = dsc[2];
+      fus16 = P.fus16;
+    }
+    const bool have = rows != 0u && (uint32_t)tid < cnt;
+    for (int i = 0; i < 8; i++) rr.u0[FRESH ? i : 0] = 0u;
+    if (have) {
+      const uint32_t *src = fus16 + (size_t)first * 4 + (size_t)tid * 8;
+      for (int i = 0; i < 8; i++) rr.u0[FRESH ? i : 0] = src[i];
+    }
+  }
+  SPICEY_HD void b_phase(int tid, int64_t step, Regs &rr, bool reuse) const {
+    double sn = K == 1 ? z_src_fetch(tid, step, (size_t)c.inst[0]) : 0.0;
+    if (FRESH) u0_fetch(tid, rr);
+    SPICEY_SCHED_FENCE;
+    b_stamp(tid, rr, reuse);
+    SPICEY_SCHED_FENCE;
+    if (K == 1) z_src_park(tid, sn);
+  }
+  // ---- batched forms of the beyond-resident-capacity loops (HYB builds, K = 1) -------------------------------------------
+  // Hybrid workspace: circuits of several thousand unknowns on 512 threads — most entries lie beyond the resident slots, and
+  // one at a time each of them costs two or three DEPENDENT round trips to L2 (descriptor, static value, conductances).
+  // Four at a time, every load of a stage issued before the first is used (the registers are there: this build is not at
+  // the 128-register cap).  Same arithmetic per entry as stamp_entry.
+  SPICEY_HD void stamp_rest_batched(int tid) const {
+    const double *sv0 = R.statv + (size_t)c.inst[0] * P.nLU;
+    // dynamic entries beyond the descriptor slots: [NDD T, nDynEnt)
+    if (brem & 16u)
+    SPICEY_NOUNROLL
+    for (int e0 = tid + Regs::NDD * T; e0 < P.nDynEnt; e0 += BWB * T) {
+      uint32_t dd[BWB];
+      double v[BWB], ga[BWB], gb[BWB];
+      SPICEY_UNROLL
+      for (int b = 0; b < BWB; b++) {
+        const int e = e0 + b * T;
+        const bool have = e < P.nDynEnt;
+        dd[b] = have ? P.ent_dd[e] : 0x80000000u;
+        v[b] = sv0[have ? e : e0];
+      }
+      SPICEY_UNROLL
+      for (int b = 0; b < BWB; b++) {
+        const uint32_t f0 = dd[b] & 0x7fffu, f1 = (dd[b] >> 15) & 0x7fffu;
+        const bool on = !(dd[b] >> 31);
+        ga[b] = c.gd[(on && f0) ? (f0 & 0x3fffu) - 1 : 0u];
+        gb[b] = c.gd[(on && f1) ? (f1 & 0x3fffu) - 1 : 0u];
+      }
+      SPICEY_UNROLL
+      for (int b = 0; b < BWB; b++) {
+        if (dd[b] >> 31) continue;
+        const uint32_t f0 = dd[b] & 0x7fffu, f1 = (dd[b] >> 15) & 0x7fffu;
+        double x = v[b];
+        if (f0) x = (f0 & 0x4000u) ? x - ga[b] : x + ga[b];
+        if (f1) x = (f1 & 0x4000u) ? x - gb[b] : x + gb[b];
+        if (dd[b] & (1u << 30)) {
+          if (fabs(x) < SPICEY_EPS && c.valid[0]) { c.flags[1] = 1; c.flags[2] = c.inst[0]; }
+          x = spicey_rcp(x);
+        }
+        put_entry((uint32_t)(e0 + b * T), 0, x);
+      }
+    }
+    // static update targets beyond the resident slots: plain copies of their static value, [max(NSV T, nDynEnt), nRestore)
+    if (brem & 1u) {
+      int e0 = tid + NSV * T;
+      if (e0 < P.nDynEnt) e0 += ((P.nDynEnt - e0 + T - 1) / T) * T;
+      SPICEY_NOUNROLL
+      for (; e0 < P.nRestore; e0 += BWB * T) {
+        double v[BWB];
+        SPICEY_UNROLL
+        for (int b = 0; b < BWB; b++) v[b] = sv0[e0 + b * T < P.nRestore ? e0 + b * T : e0];
+        SPICEY_UNROLL
+        for (int b = 0; b < BWB; b++)
+          if (e0 + b * T < P.nRestore) put_entry((uint32_t)(e0 + b * T), 0, v[b]);
+      }
+    }
+    if (brem & 2u)
+    SPICEY_NOUNROLL
+    for (int t = tid; t < P.nDynX; t += T) {  // entries with > 2 dynamic stamps (rare: kept one at a time)
+      const uint32_t et = P.dynx_ent[t], e = SPICEY_IDX(et);
+      double x = sv0[e];
+      for (uint32_t j = P.dynx_ptr[t]; j < P.dynx_ptr[t + 1]; j++) {
+        const uint32_t ix = P.dynx_idx[j];
+        const double g = c.gd[SPICEY_IDX(ix)];
+        x = (ix & SPICEY_NEG) ? x - g : x + g;
+      }
+      if (et & SPICEY_TGT_RECIP) {
+        if (fabs(x) < SPICEY_EPS && c.valid[0]) { c.flags[1] = 1; c.flags[2] = c.inst[0]; }
+        x = spicey_rcp(x);
+      }
+      put_entry(e, 0, x);
+    }
+  }
+  // right-hand-side rows beyond the resident ones, four at a time: descriptors, then all their (up to 16) contributions
+  SPICEY_HD void rhs_rest_batched(int tid) const {
+    SPICEY_NOUNROLL
+    for (int r0 = tid + NEL * T; r0 < P.n; r0 += BWB * T) {
+      uint32_t d[BWB][2];
+      double t[BWB][4];
+      SPICEY_UNROLL
+      for (int b = 0; b < BWB; b++) {
+        const int r = r0 + b * T < P.n ? r0 + b * T : r0;
+        d[b][0] = P.row_desc[(size_t)r * 2]; d[b][1] = P.row_desc[(size_t)r * 2 + 1];
+        if (r0 + b * T >= P.n) d[b][1] = 0xFFFFFFFFu;
+      }
+      SPICEY_UNROLL
+      for (int b = 0; b < BWB; b++) {
+        const bool on = d[b][1] != 0xFFFFFFFFu;
+        const uint32_t f[4] = {d[b][0] & 0xffffu, d[b][0] >> 16, d[b][1] & 0xffffu, d[b][1] >> 16};
+        SPICEY_UNROLL
+        for (int i = 0; i < 4; i++) t[b][i] = c.u[(on && f[i]) ? (f[i] & 0x7fffu) - 1 : 0u];
+      }
+      SPICEY_UNROLL
+      for (int b = 0; b < BWB; b++) {
+        if (d[b][1] == 0xFFFFFFFFu) continue;
+        const uint32_t f[4] = {d[b][0] & 0xffffu, d[b][0] >> 16, d[b][1] & 0xffffu, d[b][1] >> 16};
+        double acc = 0.0;
+        SPICEY_UNROLL
+        for (int i = 0; i < 4; i++)
+          if (f[i]) acc = (f[i] & 0x8000u) ? acc - t[b][i] : acc + t[b][i];
+        c.W[(size_t)(P.xoff + r0 + b * T)] = acc;
+      }
+    }
+  }
+
+  SPICEY_HD void stamp_matrix(int tid, Regs &rr) const {
+    if (HYB) {
+      // hybrid workspace: the conductances live in global memory — those of all descriptor slots are fetched together (one
+      // L2 round trip) before the first entry is formed; then the plain restores; then the batched rest
+      double ga[Regs::NDD], gb[Regs::NDD];
+      SPICEY_UNROLL
+      for (int j = 0; j < Regs::NDD; j++) {
+        uint32_t dd = rr.dd[j];
+        SPICEY_OPAQUE(dd);
+        const uint32_t f0 = dd & 0x7fffu, f1 = (dd >> 15) & 0x7fffu;
+        const bool on = !(dd >> 31);
+        ga[j] = c.gd[(on && f0) ? (f0 & 0x3fffu) - 1 : 0u];
+        gb[j] = c.gd[(on && f1) ? (f1 & 0x3fffu) - 1 : 0u];
+      }
+      SPICEY_UNROLL
+      for (int j = 0; j < Regs::NDD; j++) {
+        uint32_t dd = rr.dd[j];
+        SPICEY_OPAQUE(dd);
+        if (dd >> 31) continue;
+        const uint32_t f0 = dd & 0x7fffu, f1 = (dd >> 15) & 0x7fffu;
+        double x = rr.sv[j][0];
+        if (f0) x = (f0 & 0x4000u) ? x - ga[j] : x + ga[j];
+        if (f1) x = (f1 & 0x4000u) ? x - gb[j] : x + gb[j];
+        if (dd & (1u << 30)) {
+          if (fabs(x) < SPICEY_EPS && c.valid[0]) { c.flags[1] = 1; c.flags[2] = c.inst[0]; }
+          x = spicey_rcp(x);
+        }
+        put_entry((uint32_t)(tid + j * T), 0, x);
+      }
+      for (int j = Regs::NDD; j < NSV; j++) {
+        const int e = tid + j * T;
+        if (e >= P.nDynEnt && e < P.nRestore) put_entry((uint32_t)e, 0, rr.sv[j][0]);
+      }
+      stamp_rest_batched(tid);
+      return;
+    }
+    for (int j = 0; j < Regs::NDD; j++) {
+      const uint32_t e = (uint32_t)(tid + j * T);
+      uint32_t dd = rr.dd[j];
+      SPICEY_OPAQUE(dd);
+      if (SPICEY_WAVE_ANY((dd & 0x7fffffffu) != 0u)) {  // dynamic entries are numbered first: only the first slot(s) take this path
+        if (!(dd >> 31)) stamp_entry(e, dd, rr.sv[j]);
+      } else if (!(dd >> 31)) {
+        for (int k = 0; k < K; k++) put_entry(e, k, rr.sv[j][k]);
+      }
+    }
+    for (int j = Regs::NDD; j < NSV; j++) {  // plain restores (a dynamic entry this far up is left to the loop below)
+      const int e = tid + j * T;
+      if (e >= P.nDynEnt && e < n_stamped())
+        for (int k = 0; k < K; k++) put_entry((uint32_t)e, k, rr.sv[j][k]);
+    }
+    SPICEY_MARK(c, 8);
+    if (!(brem & (16u | 1u | 2u))) return;
+    SPICEY_COLD_ARGS;
+    if (brem & 16u)
+    SPICEY_NOUNROLL
+    for (int e = tid + Regs::NDD * T; e < P.nDynEnt; e += T) {  // dynamic entries beyond the descriptor slots
+      const uint32_t dd = P.ent_dd[e];
+      if (dd >> 31) continue;
+      double sv[K];
+      for (int k = 0; k < K; k++) sv[k] = R.statv[(size_t)c.inst[k] * P.nLU + e];
+      stamp_entry((uint32_t)e, dd, sv);
+    }
+    if (brem & 1u)
+    SPICEY_NOUNROLL
+    for (int e = tid + NSV * T, ne = n_stamped(); e < ne; e += T) {  // entries beyond the resident capacity
+      if (e < P.nDynEnt) continue;  // done above
+      const uint32_t dd = P.ent_dd[e];
+      if (dd >> 31) continue;
+      double sv[K];
+      for (int k = 0; k < K; k++) sv[k] = R.statv[(size_t)c.inst[k] * P.nLU + e];
+      stamp_entry((uint32_t)e, dd, sv);
+    }
+    if (brem & 2u)
+    SPICEY_NOUNROLL
+    for (int t = tid; t < P.nDynX; t += T) {  // entries with > 2 dynamic stamps
+      const uint32_t et = P.dynx_ent[t], e = SPICEY_IDX(et);
+      for (int k = 0; k < K; k++) {
+        double v = R.statv[(size_t)c.inst[k] * P.nLU + e];
+        for (uint32_t j = P.dynx_ptr[t]; j < P.dynx_ptr[t + 1]; j++) {
+          const uint32_t ix = P.dynx_idx[j];
+          const double g = c.gd[(size_t)SPICEY_IDX(ix) * K + k];
+          v = (ix & SPICEY_NEG) ? v - g : v + g;
+        }
+        if (et & SPICEY_TGT_RECIP) {
+          if (fabs(v) < SPICEY_EPS && c.valid[k]) { c.flags[1] = 1; c.flags[2] = c.inst[k]; }
+          v = spicey_rcp(v);
+        }
+        put_entry(e, k, v);
+      }
+    }
+  }
+  SPICEY_HD void rhs_rows(int tid, Regs &rr) const {
+    SPICEY_MARK(c, 9);
+    if (HYB) {  // (the contributions of all resident rows in one round trip to the global element vector)
+      double t[NEL][4];
+      SPICEY_UNROLL
+      for (int j = 0; j < NEL; j++) {
+        uint32_t d0 = rr.rhs[j][0], d1 = rr.rhs[j][1];
+        SPICEY_OPAQUE(d0); SPICEY_OPAQUE(d1);
+        const bool on = d1 != 0xFFFFFFFFu;
+        const uint32_t f[4] = {d0 & 0xffffu, d0 >> 16, d1 & 0xffffu, d1 >> 16};
+        SPICEY_UNROLL
+        for (int i = 0; i < 4; i++) t[j][i] = c.u[(on && f[i]) ? (f[i] & 0x7fffu) - 1 : 0u];
+      }
+      SPICEY_UNROLL
+      for (int j = 0; j < NEL; j++) {
+        uint32_t d0 = rr.rhs[j][0], d1 = rr.rhs[j][1];
+        SPICEY_OPAQUE(d0); SPICEY_OPAQUE(d1);
+        if (d1 == 0xFFFFFFFFu) continue;
+        const uint32_t f[4] = {d0 & 0xffffu, d0 >> 16, d1 & 0xffffu, d1 >> 16};
+        double acc = 0.0;
+        SPICEY_UNROLL
+        for (int i = 0; i < 4; i++)
+          if (f[i]) acc = (f[i] & 0x8000u) ? acc - t[j][i] : acc + t[j][i];
+        c.W[(size_t)(P.xoff + tid + j * T)] = acc;
+      }
+    } else
+    for (int j = 0; j < NEL; j++) {
+      uint32_t d0 = rr.rhs[j][0], d1 = rr.rhs[j][1];
+      SPICEY_OPAQUE(d0); SPICEY_OPAQUE(d1);
+      if (d1 != 0xFFFFFFFFu) rhs_row((uint32_t)(tid + j * T), d0, d1);
+    }
+    SPICEY_MARK(c, 10);
+    if (HYB && (brem & 4u)) rhs_rest_batched(tid);
+    if (!(brem & (HYB ? 8u : 12u))) return;
+    SPICEY_COLD_ARGS;
+    if (!HYB && (brem & 4u))
+    SPICEY_NOUNROLL
+    for (int r = tid + NEL * T; r < P.n; r += T) {
+      const uint32_t d0 = P.row_desc[(size_t)r * 2], d1 = P.row_desc[(size_t)r * 2 + 1];
+      if (d1 != 0xFFFFFFFFu) rhs_row((uint32_t)r, d0, d1);
+    }
+    if (brem & 8u)
+    SPICEY_NOUNROLL
+    for (int t = tid; t < P.nRowX; t += T) {  // rows with > 4 contributions: +-1 gather from the CSR lists
+      const uint32_t r = P.rowx[t];
+      for (int k = 0; k < K; k++) {
+        double acc = 0.0;
+        for (uint32_t j = P.rhs_ptr[r]; j < P.rhs_ptr[r + 1]; j++) {
+          const uint32_t ix = P.rhs_idx[j];
+          const double t2 = c.u[(size_t)SPICEY_IDX(ix) * K + k];
+          acc = (ix & SPICEY_NEG) ? acc - t2 : acc + t2;
+        }
+        c.W[(size_t)(P.xoff + r) * K + k] = acc;
+      }
+    }
+  }
+
+  SPICEY_HD void a_reiterate(int tid) const {  // iteration >= 1: diodes from x, switches from their new state
+    const int oD = P.nC + P.nL + P.nV;
+    for (int k = 0; k < K; k++) {
+      const size_t in = (size_t)c.inst[k];
+      SPICEY_NOUNROLL
+      for (int i = tid; i < P.nS; i += T)
+        c.gd[(size_t)i * K + k] = spicey_switch_g(c.ison[(size_t)i * K + k], R.S_ron[in * P.nS + i], R.S_roff[in * P.nS + i]);
+      SPICEY_NOUNROLL
+      for (int i = tid; i < P.nD; i += T) {
+        const double *dp = R.dpar + (in * P.nD + i) * 2;
+        double g2, q, irec;
+        const double vd = dv16(P.D_ab[i], k);
+        spicey_diode_k(vd, R.D_is[in * P.nD + i], dp[0], dp[1], false, g2, q, irec);
+        c.gd[(size_t)(P.nS + i) * K + k] = g2;
+        c.u[(size_t)(oD + i) * K + k] = q;
+        if (DIAG && R.lin_vd && c.valid[k]) R.lin_vd[in * P.nD + i] = vd;
+      }
+    }
+  }
+
+  // ---- Z: record, update state, evaluate the next step's companions --------------------------------
+  SPICEY_HD void z_cap(int i, double dv, int k, size_t in, double gc, double *oi, int cC, double &vprev, bool last) const {
+    if (oi) SPICEY_STREAM_STORE(&oi[cC + i], gc * (dv - vprev));
+    vprev = dv;
+    c.u[(size_t)i * K + k] = gc * dv;
+    if (last) R.C_vprev[in * P.nC + i] = dv;
+  }
+  SPICEY_HD void z_dio(int i, double vd, int k, size_t in, double is, double dp0, double dp1, double *oi, int cD, int oD, bool last) const {
+    double gg, q, irec;
+    spicey_diode_k(vd, is, dp0, dp1, oi != nullptr, gg, q, irec);
+    if (oi) SPICEY_STREAM_STORE(&oi[cD + i], irec);
+    c.gd[(size_t)(P.nS + i) * K + k] = gg;
+    c.u[(size_t)(oD + i) * K + k] = q;
+    if (last) R.D_vdprev[in * P.nD + i] = vd;
+  }
+  // diagnostics pass of Z (SpiceyRun::lin_vd set; its own loop so that the production path carries no extra state):
+  // |vd(x) - vd_lin| of this thread's diodes, and the new linearisation point
+  SPICEY_HD double z_lin_err(int tid, int k, size_t in) const {
+    SPICEY_COLD_ARGS;
+    double lerr = 0.0;
+    SPICEY_NOUNROLL
+    for (int i = tid; i < P.nD; i += T) {
+      const double vd = dv16(P.D_ab[i], k);
+      const double e = fabs(vd - R.lin_vd[in * P.nD + i]);
+      lerr = e > lerr ? e : lerr;
+      R.lin_vd[in * P.nD + i] = vd;
+    }
+    return lerr;
+  }
+  SPICEY_HD void z_prefetch(int tid, int64_t step, int k, Regs &rr) const {
+    const size_t in = (size_t)(K == 1 ? c.inst[0] : (k == 0 ? c.inst[0] : c.inst[K - 1]));
+    const double *g = R.gstat + in * P.nGstat;
+    for (int j = 0; j < NEL; j++) {
+      const int i = (SPICEY_EXP & 8) ? 0x7fffffff : tid + j * T;
+      rr.pf[j][0] = i < P.nR ? g[i] : 0.0;
+      rr.pf[j][1] = i < P.nC ? g[P.nR + i] : 0.0;
+      const bool hd = i < P.nD;
+      const double *dp = R.dpar + (in * P.nD + (hd ? i : 0)) * 2;
+      rr.pf[j][2] = hd ? R.D_is[in * P.nD + i] : 0.0;
+      rr.pf[j][3] = hd ? dp[0] : 0.0;
+      rr.pf[j][4] = hd ? dp[1] : 0.0;
+    }
+  }
+  // next step's source values: issued before the tasks of the last backward phase, parked in LDS after them
+  SPICEY_HD double z_src_fetch(int tid, int64_t step, size_t in) const {
+    return (tid < P.nV && step != R.steps) ? R.src[in * R.src_stride + (size_t)(step + 1) * P.nV + tid] : 0.0;
+  }
+  SPICEY_HD void z_src_park(int tid, double v) const {
+    if (tid < P.nV) c.u[(size_t)(P.nC + P.nL + P.nV + P.nD + tid) * K] = v;
+  }
+  SPICEY_HD void z_prefetch_none(Regs &rr) const {
+    for (int j = 0; j < NEL; j++)
+      for (int q = 0; q < 5; q++) rr.pf[j][q] = 0.0;
+  }
+  SPICEY_HD void z_record(int tid, int64_t step, Regs &rr, bool prefetched) const {
+    const bool last = step == R.steps;
+    const int oL = P.nC, oV = P.nC + P.nL, oD = P.nC + P.nL + P.nV;
+    const int cR = 0, cC = P.nR, cL = P.nR + P.nC, cV = cL + P.nL, cS = cV + P.nV, cD = cS + P.nS;
+    // The instance loop is kept ROLLED here (one copy of the exp / store code, one instance's working set):
+    // unrolled and interleaved it needs ~2x the VGPRs and the register-resident program spills.
+    SPICEY_NOUNROLL
+    for (int k = 0; k < K; k++) {
+      const int vk = K == 1 ? c.valid[0] : (k == 0 ? c.valid[0] : c.valid[K - 1]);
+      if (!vk) continue;
+      const size_t in = (size_t)(K == 1 ? c.inst[0] : (k == 0 ? c.inst[0] : c.inst[K - 1]));
+      double *ov = R.out_v + (in * (size_t)(R.steps + 1) + (size_t)step) * P.nOut;
+      double *oi = R.out_i ? R.out_i + (in * (size_t)(R.steps + 1) + (size_t)step) * P.nCur : nullptr;
+      const double *g = R.gstat + in * P.nGstat;
+      if (DIAG && R.lin_vd) {  // diagnostics (wave-uniform): the step's one-shot linearisation error
+        const double lerr = z_lin_err(tid, k, in);
+        if (R.lin_err) spicey_lin_err_report(R, in, step, tid, lerr);
+      }
+      SPICEY_MARK(c, 15);
+      // Element parameters of the resident items come from L2: all their loads are issued together (one round
+      // trip per step instead of one per element section), normally already during the last backward phase.
+      if (!(K == 1 && prefetched)) z_prefetch(tid, step, k, rr);
+      double pR[NEL], pC[NEL], pIs[NEL], pD0[NEL], pD1[NEL];
+      for (int j = 0; j < NEL; j++) { pR[j] = rr.pf[j][0]; pC[j] = rr.pf[j][1]; pIs[j] = rr.pf[j][2]; pD0[j] = rr.pf[j][3]; pD1[j] = rr.pf[j][4]; }
+      double srcn = (K == 1 && prefetched) ? 0.0 : z_src_fetch(tid, step, in);
+      // ... and all of them are WAITED for here, before the first result store is issued: gfx9 has one counter
+      // (vmcnt) for loads and stores, which may complete out of order, so once a store is in flight a wait for any
+      // load becomes vmcnt(0) = "until every result store has been acknowledged" (~1 us each time).
+      for (int j = 0; j < NEL; j++) { SPICEY_OPAQUE(pR[j]); SPICEY_OPAQUE(pC[j]); SPICEY_OPAQUE(pIs[j]); SPICEY_OPAQUE(pD0[j]); SPICEY_OPAQUE(pD1[j]); }
+      SPICEY_OPAQUE(srcn);
+      SPICEY_MARK(c, 0);
+      if (tid < P.nV) {  // source tid: branch current out, next step's value in (read by the next B only)
+        uint32_t vx = rr.ox[0];
+        SPICEY_OPAQUE(vx);
+        if (oi) oi[cV + tid] = c.W[(size_t)(vx >> 16) * K + k];
+        if (!last) c.u[(size_t)(oV + tid) * K + k] = (K == 1 && prefetched) ? c.u[(size_t)(oD + P.nD + tid) * K + k] : srcn;
+      }
+      SPICEY_SCHED_FENCE;
+      // resident items (element / row / output tid + j T).  All their terminal voltages are read first, back to
+      // back (one LDS round trip), then class by class so that the parameter registers die early.
+      {
+        double vo[NEL], dR[NEL];
+        for (int j = 0; j < NEL; j++) {
+          uint32_t ox = rr.ox[j], eR = rr.eR[j];
+          SPICEY_OPAQUE(ox); SPICEY_OPAQUE(eR);
+          vo[j] = volt16(ox & 0xFFFFu, k);
+          dR[j] = dv16(eR, k);
+        }
+        SPICEY_SCHED_FENCE;
+        for (int j = 0; j < NEL; j++) {
+          const int i = tid + j * T;
+          if (i < P.nOut && !(SPICEY_EXP & 16)) SPICEY_STREAM_STORE(&ov[i], vo[j]);
+          if (oi && i < P.nR && !(SPICEY_EXP & 16)) SPICEY_STREAM_STORE(&oi[cR + i], dR[j] * pR[j]);
+        }
+        SPICEY_SCHED_FENCE;
+      }
+      double dC[NEL], dD[NEL];
+      for (int j = 0; j < NEL; j++) {
+        uint32_t eC = rr.eC[j], eD = rr.eD[j];
+        SPICEY_OPAQUE(eC); SPICEY_OPAQUE(eD);
+        dC[j] = dv16(eC, k);
+        dD[j] = dv16(eD, k);
+      }
+      SPICEY_SCHED_FENCE;
+      SPICEY_MARK(c, 1);
+      for (int j = 0; j < NEL; j++) {
+        const int i = tid + j * T;
+        if (i < P.nC && !(SPICEY_EXP & 4)) {
+          double vp = K == 1 ? rr.vprev[j][0] : (k == 0 ? rr.vprev[j][0] : rr.vprev[j][K - 1]);
+          z_cap(i, dC[j], k, in, pC[j], oi, cC, vp, last);
+          if (K == 1 || k == 0) rr.vprev[j][0] = vp;
+          else rr.vprev[j][K - 1] = vp;
+        }
+      }
+      SPICEY_SCHED_FENCE;
+      SPICEY_MARK(c, 2);
+      for (int j = 0; j < NEL; j++) {
+        const int i = tid + j * T;
+        if (i < P.nD && !(SPICEY_EXP & 2)) z_dio(i, dD[j], k, in, pIs[j], pD0[j], pD1[j], oi, cD, oD, last);
+        SPICEY_SCHED_FENCE;
+      }
+      SPICEY_MARK(c, 3);
+      if ((SPICEY_EXP & 32) || !zrem) continue;
+      SPICEY_COLD_ARGS;
+      if (HYB) {
+        // (hybrid workspace: four items of every kind at a time — indices and parameters of all four in flight before the
+        // first terminal voltage is read; the same arithmetic per item as the loops below)
+        if (zrem & 1u)
+        SPICEY_NOUNROLL
+        for (int i0 = tid + NEL * T; i0 < P.nOut; i0 += BW * T) {
+          int32_t xi[BW];
+          SPICEY_UNROLL
+          for (int b = 0; b < BW; b++) xi[b] = P.out_x[i0 + b * T < P.nOut ? i0 + b * T : i0];
+          double v[BW];
+          SPICEY_UNROLL
+          for (int b = 0; b < BW; b++) v[b] = xi[b] < 0 ? 0.0 : c.W[(size_t)xi[b]];
+          SPICEY_UNROLL
+          for (int b = 0; b < BW; b++)
+            if (i0 + b * T < P.nOut) SPICEY_STREAM_STORE(&ov[i0 + b * T], v[b]);
+        }
+        if (oi && (zrem & 2u))
+        SPICEY_NOUNROLL
+        for (int i0 = tid + NEL * T; i0 < P.nR; i0 += BW * T) {
+          uint32_t ab[BW];
+          double gg[BW], dv[BW];
+          SPICEY_UNROLL
+          for (int b = 0; b < BW; b++) { const int i = i0 + b * T < P.nR ? i0 + b * T : i0; ab[b] = P.R_ab[i]; gg[b] = g[i]; }
+          SPICEY_UNROLL
+          for (int b = 0; b < BW; b++) dv[b] = dv16(ab[b], k);
+          SPICEY_UNROLL
+          for (int b = 0; b < BW; b++)
+            if (i0 + b * T < P.nR) SPICEY_STREAM_STORE(&oi[cR + i0 + b * T], dv[b] * gg[b]);
+        }
+        if (zrem & 4u)
+        SPICEY_NOUNROLL
+        for (int i0 = tid + NEL * T; i0 < P.nC; i0 += BW * T) {  // beyond the resident capacity: vPrev lives in the state array
+          uint32_t ab[BW];
+          double gc[BW], vp[BW], dv[BW];
+          SPICEY_UNROLL
+          for (int b = 0; b < BW; b++) {
+            const int i = i0 + b * T < P.nC ? i0 + b * T : i0;
+            ab[b] = P.C_ab[i]; gc[b] = g[P.nR + i]; vp[b] = R.C_vprev[in * P.nC + i];
+          }
+          SPICEY_UNROLL
+          for (int b = 0; b < BW; b++) dv[b] = dv16(ab[b], k);
+          SPICEY_UNROLL
+          for (int b = 0; b < BW; b++) {
+            const int i = i0 + b * T;
+            if (i >= P.nC) continue;
+            z_cap(i, dv[b], k, in, gc[b], oi, cC, vp[b], false);
+            R.C_vprev[in * P.nC + i] = vp[b];
+          }
+        }
+        if (zrem & 64u)
+        SPICEY_NOUNROLL
+        for (int i0 = tid + NEL * T; i0 < P.nD; i0 += BW * T) {
+          uint32_t ab[BW];
+          double is4[BW], d0[BW], d1[BW], vd[BW];
+          SPICEY_UNROLL
+          for (int b = 0; b < BW; b++) {
+            const int i = i0 + b * T < P.nD ? i0 + b * T : i0;
+            const double *dp = R.dpar + (in * P.nD + i) * 2;
+            ab[b] = P.D_ab[i]; is4[b] = R.D_is[in * P.nD + i]; d0[b] = dp[0]; d1[b] = dp[1];
+          }
+          SPICEY_UNROLL
+          for (int b = 0; b < BW; b++) vd[b] = dv16(ab[b], k);
+          SPICEY_UNROLL
+          for (int b = 0; b < BW; b++)
+            if (i0 + b * T < P.nD) z_dio(i0 + b * T, vd[b], k, in, is4[b], d0[b], d1[b], oi, cD, oD, last);
+        }
+      }
+      if (!HYB && (zrem & 1u))
+      SPICEY_NOUNROLL
+      for (int i = tid + NEL * T; i < P.nOut; i += T) ov[i] = P.out_x[i] < 0 ? 0.0 : c.W[(size_t)P.out_x[i] * K + k];
+      if (!HYB && oi && (zrem & 2u)) {
+        SPICEY_NOUNROLL
+        for (int i = tid + NEL * T; i < P.nR; i += T) oi[cR + i] = dv16(P.R_ab[i], k) * g[i];
+      }
+      if (!HYB && (zrem & 4u))
+      SPICEY_NOUNROLL
+      for (int i = tid + NEL * T; i < P.nC; i += T) {  // beyond the resident capacity: vPrev lives in the state array
+        double vp = R.C_vprev[in * P.nC + i];
+        z_cap(i, dv16(P.C_ab[i], k), k, in, g[P.nR + i], oi, cC, vp, false);
+        R.C_vprev[in * P.nC + i] = vp;
+      }
+      if (zrem & 8u)
+      SPICEY_NOUNROLL
+      for (int i = tid; i < P.nL; i += T) {
+        const double dv = dv16(P.L_ab[i], k);
+        const double il = g[P.nR + P.nC + i] * dv + c.u[(size_t)(oL + i) * K + k];
+        if (oi) oi[cL + i] = il;
+        c.u[(size_t)(oL + i) * K + k] = il;
+        if (last) R.L_iprev[in * P.nL + i] = il;
+      }
+      if (zrem & 16u)
+      SPICEY_NOUNROLL
+      for (int i = tid + T; i < P.nV; i += T) {
+        if (oi) oi[cV + i] = c.W[(size_t)P.V_x[i] * K + k];
+        if (!last) c.u[(size_t)(oV + i) * K + k] = R.src[in * R.src_stride + (size_t)(step + 1) * P.nV + i];
+      }
+      if (zrem & 32u)
+      SPICEY_NOUNROLL
+      for (int i = tid; i < P.nS; i += T) {
+        const int on = c.ison[(size_t)i * K + k];
+        const double gs = spicey_switch_g(on, R.S_ron[in * P.nS + i], R.S_roff[in * P.nS + i]);
+        const double va = P.S_a[i] < 0 ? 0.0 : c.W[(size_t)P.S_a[i] * K + k], vb = P.S_b[i] < 0 ? 0.0 : c.W[(size_t)P.S_b[i] * K + k];
+        if (oi) oi[cS + i] = (va - vb) * gs;
+        c.gd[(size_t)i * K + k] = gs;
+        if (last) R.S_ison[in * P.nS + i] = on;
+      }
+      if (!HYB && (zrem & 64u))
+      SPICEY_NOUNROLL
+      for (int i = tid + NEL * T; i < P.nD; i += T) {
+        const double *dp = R.dpar + (in * P.nD + i) * 2;
+        z_dio(i, dv16(P.D_ab[i], k), k, in, R.D_is[in * P.nD + i], dp[0], dp[1], oi, cD, oD, last);
+      }
+      SPICEY_SCHED_FENCE;
+    }
+  }
+};

@@ -1,0 +1,355 @@
+// tran_v2_run.h — the tridiagonal top and the v2 run driver, spicey_tran_run_v2 (tran_exec.h is the map).
+#pragma once
+#include <math.h>
+#include <stddef.h>
+#include <stdint.h>
+
+#include "program.h"
+#include "tran_common.h"
+#include "tran_pt.h"
+#include "tran_rec16.h"
+#include "tran_v1_phases.h"
+#include "tran_v2_phases.h"
+
+// ---- tridiagonal top by parallel cyclic reduction (program.h: pcr_n, pcr_tab) -------------------------------------------
+// One wave, lane i = row i of the tridiagonal Schur complement (path order), two SoA buffers {a, b, c, d}[64] in LDS used
+// alternately.  Stage 0 gathers the rows from W through the index table; stage st = 1 .. S (stride 1, 2, 4, ...): row i
+// eliminates its couplings to the rows i -+ stride with those rows' equations; after S = ceil(log2 n) stages every row
+// stands alone and the last stage writes x_i = d_i / b_i straight into the solution slot.
+// Replaces 2 x (S + 1) LDS-serial levels of the task lists; no U entries are formed for these pivots (nothing below needs
+// them: the backward records of lower rows read x only).  All loads of a stage are unconditional (clamped addresses, values
+// masked afterwards) so that they are issued together: one LDS round trip per stage.
+template <int K>
+SPICEY_HD void spicey_pcr_row(const WgCtx<K> &c, const uint16_t *tab, int n, int r, double &a, double &b, double &cc, double &d) {
+  const bool on = r >= 0 && r < n;
+  const int rr = on ? r : 0;
+  const uint32_t ia = tab[rr * 4], ib = tab[rr * 4 + 1], ic = tab[rr * 4 + 2], id = tab[rr * 4 + 3];
+  const double va = c.W[(size_t)(ia == 0xFFFFu ? ib : ia) * K], vb = c.W[(size_t)ib * K], vc = c.W[(size_t)(ic == 0xFFFFu ? ib : ic) * K],
+               vd = c.W[(size_t)id * K];
+  a = (on && ia != 0xFFFFu) ? va : 0.0;
+  b = on ? vb : 1.0;  // rows past the end: identity
+  cc = (on && ic != 0xFFFFu) ? vc : 0.0;
+  d = on ? vd : 0.0;
+}
+// A row without a neighbour at the stage's stride has a zero coupling on that side (a_i = 0 for i < stride, c_i = 0 for
+// i + stride >= n: by induction over the stages; rows past the end are identity rows), so the missing neighbour is not
+// masked: its index is clamped into the buffer and whatever finite row is read there is multiplied by that zero.  (Masking
+// cost 16 selects of ~70 instructions per stage, on a wave that issues one instruction per ~4.5 cycles.)
+template <int K>
+SPICEY_HD void spicey_pcr_stage(const WgCtx<K> &c, double *buf, const uint16_t *tab, int n, int S, int lane, int st, double *own) {
+  // LDS row = {a, 1/b, c, d}: a row forms the reciprocal of its own pivot once, its two neighbours multiply with it;
+  // the row's own {a, b, c, d} stay in registers (`own`) from stage to stage
+  double *wr = buf + ((st & 1) ? 256 : 0);
+  bool sing;
+  if (st == 0) {  // gather the rows from W (stage 0 writes buffer 0)
+    double a, b, cc, d;
+    spicey_pcr_row<K>(c, tab, n, lane, a, b, cc, d);
+    own[0] = a; own[1] = b; own[2] = cc; own[3] = d;
+    sing = fabs(b) < SPICEY_EPS;
+    wr[lane] = a; wr[64 + lane] = spicey_rcp(b); wr[128 + lane] = cc; wr[192 + lane] = d;
+  } else {
+    const double *rd = buf + (((st - 1) & 1) ? 256 : 0);
+    const int h = 1 << (st - 1), im = lane - h, ip = lane + h;
+    const int jm = im < 0 ? 0 : im, jp = ip > 63 ? 63 : ip;
+    const double am = rd[jm], rm = rd[64 + jm], cm = rd[128 + jm], dm = rd[192 + jm];
+    const double ap = rd[jp], rp = rd[64 + jp], cp = rd[128 + jp], dp = rd[192 + jp];
+    const double al = -own[0] * rm;  // (a = 0 where there is no such neighbour)
+    const double ga = -own[2] * rp;
+    const double na = al * am, nc = ga * cp;
+    const double nb = fma(ga, ap, fma(al, cm, own[1]));
+    const double nd = fma(ga, dp, fma(al, dm, own[3]));
+    sing = fabs(nb) < SPICEY_EPS;
+    const double nr = spicey_rcp(nb);
+    if (st < S) {
+      own[0] = na; own[1] = nb; own[2] = nc; own[3] = nd;
+      wr[lane] = na; wr[64 + lane] = nr; wr[128 + lane] = nc; wr[192 + lane] = nd;
+    } else if (lane < n) {  // the rows are decoupled: x = d / b straight into the solution slot
+      c.W[(size_t)tab[lane * 4 + 3] * K] = nd * nr;
+    }
+  }
+  if (sing && lane < n && c.valid[0]) { c.flags[1] = 1; c.flags[2] = c.inst[0]; }
+}
+#if defined(__HIP_DEVICE_COMPILE__)
+// All stages in one call for the GPU (the same arithmetic as spicey_pcr_stage, stage after stage): the stage loop is
+// unrolled — strides, buffer halves and the last-stage test are constants —, the pivots are judged once at the end by
+// their running minimum, and between two stages stands only a compiler fence (the LDS operations of one wave execute in
+// order).  ~40 instructions per stage instead of ~70.
+template <int K>
+__device__ __forceinline__ void spicey_pcr_all(const WgCtx<K> &c, double *buf, const uint16_t *tab, int n, int S, int lane) {
+  double a, b, cc, d;
+  spicey_pcr_row<K>(c, tab, n, lane, a, b, cc, d);
+  double pmin = fabs(b);  // (rows past the end: b = 1)
+  buf[lane] = a; buf[64 + lane] = spicey_rcp(b); buf[128 + lane] = cc; buf[192 + lane] = d;
+#pragma unroll
+  for (int st = 1; st <= 6; st++) {
+    if (st > S) break;  // (wave-uniform)
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    const double *rd = buf + (((st - 1) & 1) ? 256 : 0);
+    double *wr = buf + ((st & 1) ? 256 : 0);
+    const int h = 1 << (st - 1);
+    const int jm = max(lane - h, 0), jp = min(lane + h, 63);
+    const double am = rd[jm], rm = rd[64 + jm], cm = rd[128 + jm], dm = rd[192 + jm];
+    const double ap = rd[jp], rp = rd[64 + jp], cp = rd[128 + jp], dp = rd[192 + jp];
+    const double al = -a * rm, ga = -cc * rp;
+    const double na = al * am, nc = ga * cp;
+    const double nb = fma(ga, ap, fma(al, cm, b));
+    const double nd = fma(ga, dp, fma(al, dm, d));
+    pmin = fmin(pmin, fabs(nb));
+    const double nr = spicey_rcp(nb);
+    if (st < S) {
+      a = na; b = nb; cc = nc; d = nd;
+      wr[lane] = na; wr[64 + lane] = nr; wr[128 + lane] = nc; wr[192 + lane] = nd;
+    } else if (lane < n) {
+      c.W[(size_t)tab[lane * 4 + 3] * K] = nd * nr;
+    }
+  }
+  if (pmin < SPICEY_EPS && lane < n && c.valid[0]) { c.flags[1] = 1; c.flags[2] = c.inst[0]; }
+}
+#endif
+
+// The three argument structs hold ~110 pointers: kept in SGPRs across the time loop they overflow the 102 scalar registers
+// of a wave and the compiler parks them in VGPR lanes (round 1: 274 spilled SGPRs, 1 209 v_readlane in the kernel — 13 % of
+// its instructions).  No phase of the time loop therefore sees the structs themselves.  Where the run keeps a phase table
+// (tran_pt.h) a phase reads the words it needs from LDS; otherwise, and in the rarely taken branches, it takes the
+// structs through `ex.fresh()` / spicey_fresh(): on the GPU they live in global memory and `fresh` makes their address
+// opaque for this phase, so the fields it needs are fetched by scalar loads inside it (scalar cache).  Either way the
+// values are dead at the phase's barrier; only a handful of loop-control scalars stay live around the loop.
+template <int K, int RMAX, int NSV, int NEL, bool HYB = false, int PT = -1, class Exec>
+SPICEY_HD void spicey_tran_run_v2(Exec &ex, const SpiceyProg &P, const SpiceyResident &Q, const SpiceyRun &R, WgCtx<K> &c, int wg) {
+  const int T = ex.threads();
+  typedef TranPhases2<K, RMAX, NSV, NEL, HYB> Ph2;
+  uint32_t brem, zrem;
+  {
+    Ph2 p2{P, R, c, T, 0u, 0u};
+    p2.set_remainders();
+    brem = p2.brem; zrem = p2.zrem;
+  }
+  typedef ResRegs<K, RMAX, NSV, NEL> Regs;
+  // the phase table: tridiagonal-top builds whose rows fit behind the top's index table (wave-uniform, fixed for the run)
+  static_assert(PT <= 0 || K == 1, "the phase table is built for one instance per workgroup");
+  const bool pt_run = PT >= 0 ? PT == 1 : (K == 1 && spicey_pt_runtime_choice(P, Q));
+  if (pt_run) ex.phase(SPICEY_PH_PRO, [&](int tid) { spicey_pt_build<K>(P, Q, R, c, tid, T); });  // (the structs where they live: see there)
+  ex.phase(SPICEY_PH_PRO, [&](int tid) {
+    const SpiceyProg Pf = ex.fresh(P); const SpiceyResident Qf = ex.fresh(Q); const SpiceyRun Rf = ex.fresh(R);
+    TranPhases<K> ph{Pf, Rf, c, T};
+    Ph2 p2{Pf, Rf, c, T, brem, zrem};
+    if (tid == 0) { c.flags[0] = 0; c.flags[1] = 0; c.flags[2] = -1; }
+    ph.p0_gstat(tid);
+    p2.load_resident(tid, Qf, ex.template regs<Regs>(tid));
+    if (K == 1 && Pf.pcr_n > 0) {  // tridiagonal top: its index table sits behind the two 2 KB row buffers
+      uint16_t *tab = (uint16_t *)(c.tail + 1024);
+      for (int i = tid; i < Pf.pcr_n * 4; i += T) tab[i] = Pf.pcr_tab[i];
+    }
+    for (int i = tid; i < Qf.tail_n * 64; i += T) {  // tail records -> LDS (16 bytes each; no task = all zero)
+      const int p = Qf.tail_first + (i >> 6), lane = i & 63;
+      const bool have = (uint32_t)lane < Pf.ph_cnt[p];
+      const uint32_t *src = Pf.rec16 + ((size_t)Pf.ph_first[p] + (have ? lane : 0)) * 4;
+      for (int w = 0; w < 4; w++) c.tail[(size_t)i * 4 + w] = have ? src[w] : 0u;
+    }
+  });
+  ex.phase(SPICEY_PH_PRO, [&](int tid) { const SpiceyProg Pf = ex.fresh(P); const SpiceyRun Rf = ex.fresh(R); TranPhases<K> ph{Pf, Rf, c, T}; ph.p1_static(tid); });
+  ex.phase(SPICEY_PH_PRO, [&](int tid) { const SpiceyProg Pf = ex.fresh(P); const SpiceyRun Rf = ex.fresh(R); Ph2 p2{Pf, Rf, c, T, brem, zrem}; p2.a0_initial(tid, ex.template regs<Regs>(tid)); });
+  unsigned long long solves = 0;
+  int32_t code = 0;
+  int64_t err_step = 0;
+  int32_t err_iter = 0;
+  if (c.flags[1]) { code = 1; }
+  // loop control: a handful of scalars
+  const int nL = P.nLevels;
+  const int nS = P.nS;
+  const int64_t steps = R.steps;
+  const int dbg_empty = R.debug_empty_phases;
+  // which phases have work: kept in a scalar mask so that the phase loop issues no loads
+  unsigned long long active = 0, smask = 0;
+  for (int p = 0; p < 2 * nL && p < 64; p++) {
+    if (SPICEY_UNIFORM((int)P.ph_cnt[p]) != 0) active |= 1ull << p;
+    if (SPICEY_UNIFORM((int)Q.st_cnt[p]) != 0) smask |= 1ull << p;
+  }
+  const int tail_n = Q.tail_n, tail_first = Q.tail_first;
+  // (the tridiagonal top's two loop-control values ride in ONE scalar across the time loop and are unpacked inside it: every
+  // further live scalar there costs a lane of a spill VGPR, and the 128-register build has none to give)
+  int top_pack;
+  {
+    const int n0 = K == 1 ? P.pcr_n : 0;
+    int S0 = 0;
+    while ((1 << S0) < n0) S0++;
+    top_pack = n0 | (S0 << 8);
+  }
+  const int pcr_n = top_pack & 0xff;
+  // with a tridiagonal top the factor phases end at its level and the backward phases resume below it
+  const int u_end = pcr_n > 0 ? P.pcr_level : (tail_n > 0 ? tail_first : nL);
+  const int k_begin = pcr_n > 0 ? 2 * nL - P.pcr_level : (tail_n > 0 ? tail_first + tail_n : nL);
+  top_pack |= (K == 1 && k_begin < 2 * nL) ? 1 << 16 : 0;  // bit 16 = z_pre: Z's parameter fetch rides on the last backward phase
+  // No diodes and no switches: the matrix of every step is the matrix of step 0 (dt is fixed within a run), so its
+  // factors stay in W and later steps run the right-hand-side column only.  Same operands, same order: the results
+  // are bit-identical to refactoring (SURVEY.md §8(d) "solve-only" rate; the reference itself never reuses).
+  top_pack |= (P.nD == 0 && nS == 0 && P.nDynEnt == 0 && !R.no_reuse) ? 1 << 17 : 0;  // bit 17 = linear
+  top_pack |= (Ph2::DIAG && R.skip_risk != nullptr) ? 1 << 18 : 0;  // bit 18 = diagnostics: look at the stamped matrix after B (spicey_skip_risk)
+  top_pack |= (K == 1 && pcr_n > 0 && Q.k_merge == k_begin && k_begin < 2 * nL - 1) ? 1 << 19 : 0;  // bit 19 = the first backward phase runs in the top's wave
+  top_pack |= (PT < 0 && pt_run) ? 1 << 20 : 0;  // bit 20 = the phases take their arguments from the phase table (where that is a run-time choice)
+  top_pack = SPICEY_UNIFORM(top_pack);
+  for (int64_t step = 0; step <= steps && code == 0; step++) {
+    int iter = 0;
+    for (;;) {
+      int tp = top_pack;
+      SPICEY_OPAQUE_S(tp);
+      const int pcr_n = tp & 0xff, pcr_S = (tp >> 8) & 0xff;
+      const bool linear = (tp >> 17) & 1;
+      // (with a table u_end = pcr_level rows of factor phases come first, the backward phases from k_begin on follow)
+      const bool pt_on = PT >= 0 ? PT == 1 : ((tp >> 20) & 1) != 0;
+      const uint32_t *ptw = c.tail + spicey_pt_base_words(pcr_n);
+      const bool pt_bz = !HYB && pt_on;  // (hybrid builds: B and Z read many more fields; they keep the scalar loads)
+      ex.phase(SPICEY_PH_B, [&](int tid) {
+        if (pt_bz) {
+          SpiceyProg Pt{};
+          SpiceyRun Rt{};
+          spicey_pt_args(ptw, tid, Pt, Rt);
+          // (fresh build: nKeep rides in the spare word of phase 0's row — spicey_build_resident — so that the run-wide block,
+          // and with it every other build, is what it was)
+          if (Ph2::FRESH) Pt.nKeep = (int32_t)SpiceyPtLanes::row(ptw, tid, 0).u32(7);
+          Ph2 p2{Pt, Rt, c, T, brem, zrem, &P, &R, ptw, nullptr};
+          p2.b_phase(tid, step, ex.template regs<Regs>(tid), linear && step > 0);
+        } else {
+          const SpiceyProg Pf = ex.fresh(P);
+          const SpiceyRun Rf = ex.fresh(R);
+          Ph2 p2{Pf, Rf, c, T, brem, zrem, nullptr, nullptr, nullptr, &Q};
+          p2.b_phase(tid, step, ex.template regs<Regs>(tid), linear && step > 0);
+        }
+      });
+      if (Ph2::DIAG && ((tp >> 18) & 1) && !(linear && step > 0))
+        ex.phase(SPICEY_PH_S, [&](int tid) {
+          const SpiceyProg Pf = ex.fresh(P);
+          const SpiceyRun Rf = ex.fresh(R);
+          spicey_skip_risk<K, HYB>(Pf, Rf, c, tid, T, linear ? (unsigned long long)(steps + 1) : 1ull);
+        });
+      for (int d = 0; d < dbg_empty; d++) ex.phase(SPICEY_PH_S, [&](int) {});  // diagnostics: cost of a bare phase
+      // factor levels [0, u_end) | tail [u_end, k_begin) by one wave | backward levels [k_begin, 2 nL)
+      for (int p = 0; p < u_end; p++) {
+        if (p < 64 ? !((active >> p) & 1) : P.ph_cnt[p] == 0) continue;
+        if (HYB && p == 0) {
+          // hybrid workspace: phase 0 eliminates the leaves, whose own entries are read from the global array (one L2 round
+          // trip for the whole level; every target is in LDS)
+          ex.phase(SPICEY_PH_U0, [&](int tid) {
+            spicey_uk_phase<K, RMAX, NSV, NEL, false, HYB>(P, Q, SpiceyPt{ptw, pt_on, 0}, c, ex.template regs<Regs>(tid), tid, T, 0, ((smask >> 0) & 1) != 0, linear && step > 0);
+          });
+          continue;
+        }
+        ex.phase(SPICEY_PH_U0 + (p < 30 ? p : 30), [&](int tid) {
+          spicey_uk_phase<K, RMAX, NSV, NEL, false>(P, Q, SpiceyPt{ptw, pt_on, p}, c, ex.template regs<Regs>(tid), tid, T, p, p < 64 ? ((smask >> p) & 1) != 0 : true, linear && step > 0);
+        });
+      }
+      const int kmerge = (tp >> 19) & 1;
+      if (pcr_n > 0) {
+        // (kmerge: wave 0 goes on with the first backward phase below the top — its records are resident in this wave's
+        // slots, its rows need unknowns of the top only, and the LDS operations of one wave execute in order)
+        auto merged_k = [&](int lane) {
+          spicey_uk_phase<K, RMAX, NSV, NEL, true>(P, Q, SpiceyPt{ptw, pt_on, u_end}, c, ex.template regs<Regs>(lane), lane, T, k_begin, false);
+        };
+#if defined(__HIP_DEVICE_COMPILE__)
+        if (pcr_S >= 1 && pcr_S <= 6) {
+          ex.wave_lockstep_keep(64, 1, [&](int lane, int, double *) {
+            spicey_pcr_all<K>(c, (double *)c.tail, (const uint16_t *)(c.tail + 1024), pcr_n, pcr_S, lane);
+            if (kmerge) {
+              __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+              __builtin_amdgcn_wave_barrier();
+              merged_k(lane);
+            }
+          });
+        } else
+#endif
+        ex.wave_lockstep_keep(64, pcr_S + 1 + kmerge, [&](int lane, int st, double *own) {
+          if (st <= pcr_S) spicey_pcr_stage<K>(c, (double *)c.tail, (const uint16_t *)(c.tail + 1024), pcr_n, pcr_S, lane, st, own);
+          else merged_k(lane);
+        });
+      } else if (k_begin > u_end) {
+        // the record of level l + 1 is fetched (LDS) while level l executes: one round trip less on the serial chain
+        ex.tail_phase(SPICEY_PH_U0 + 31, k_begin - u_end,
+                      [&](int tid, int lvl, uint32_t *r) {
+                        const uint32_t *q = c.tail + ((size_t)lvl * 64 + tid) * 4;
+                        r[0] = q[0]; r[1] = q[1]; r[2] = q[2]; r[3] = q[3];
+                      },
+                      [&](int, int lvl, const uint32_t *r) {
+                        auto ovf = [&]() -> const uint16_t * { return spicey_fresh(P).ovf16; };
+                        if (u_end + lvl < nL) spicey_exec_rec16<K, false, false, SpiceyShapeKind<RMAX, NSV, NEL>::fresh>(c, ovf, r[0], r[1], r[2], r[3], (linear && step > 0) ? (uint32_t)spicey_fresh(P).xoff : 0u);
+                        else spicey_exec_rec16<K, true>(c, ovf, r[0], r[1], r[2], r[3]);
+                      });
+      }
+      for (int p = k_begin + kmerge; p < 2 * nL - 1; p++) {
+        const int l = 2 * nL - 1 - p;
+        ex.phase(SPICEY_PH_K0 + (l < 31 ? l : 31), [&](int tid) {
+          spicey_uk_phase<K, RMAX, NSV, NEL, true>(P, Q, SpiceyPt{ptw, pt_on, p - k_begin + u_end}, c, ex.template regs<Regs>(tid), tid, T, p, p < 64 ? ((smask >> p) & 1) != 0 : true);
+        });
+      }
+      // the last backward phase (level 0) is peeled: it also issues Z's parameter fetch.  (Every path through the
+      // iteration defines the prefetch registers, so they are not live around the time loop.)
+      if (k_begin < 2 * nL) {
+        const int p = 2 * nL - 1;
+        ex.phase(SPICEY_PH_K0, [&](int tid) {
+          spicey_uk_phase<K, RMAX, NSV, NEL, true, HYB>(P, Q, SpiceyPt{ptw, pt_on, p - k_begin + u_end}, c, ex.template regs<Regs>(tid), tid, T, p, p < 64 ? ((smask >> p) & 1) != 0 : true);  // (level 0: the leaves)
+          SPICEY_SCHED_FENCE;  // after the tasks, not among them: their registers are free by now
+          if (K == 1) {
+            if (pt_bz) {
+              SpiceyProg Pt{};
+              SpiceyRun Rt{};
+              spicey_pt_args(ptw, tid, Pt, Rt);
+              Ph2 p2{Pt, Rt, c, T, brem, zrem, &P, &R};
+              p2.z_prefetch(tid, step, 0, ex.template regs<Regs>(tid));
+            } else {
+              const SpiceyProg Pf = ex.fresh(P);
+              const SpiceyRun Rf = ex.fresh(R);
+              Ph2 p2{Pf, Rf, c, T, brem, zrem};
+              p2.z_prefetch(tid, step, 0, ex.template regs<Regs>(tid));
+            }
+          }
+        });
+      } else if (K == 1) {
+        Ph2 p2{P, R, c, T, brem, zrem};
+        p2.z_prefetch_none(ex.template regs<Regs>(0));
+      }
+      if (c.flags[1]) { code = 1; err_step = step; err_iter = iter; break; }
+      if (nS == 0) break;
+      ex.phase(SPICEY_PH_S, [&](int tid) { const SpiceyProg Pf = ex.fresh(P); const SpiceyRun Rf = ex.fresh(R); TranPhases<K> ph{Pf, Rf, c, T}; ph.s_switches(tid); });
+      const int switched = c.flags[0];
+      if (!switched || iter == SPICEY_MAX_ITER - 1) break;
+      iter++;
+      ex.phase(SPICEY_PH_A, [&](int tid) { const SpiceyProg Pf = ex.fresh(P); const SpiceyRun Rf = ex.fresh(R); Ph2 p2{Pf, Rf, c, T, brem, zrem}; p2.a_reiterate(tid); });
+    }
+    if (code) break;
+    {
+      int nvalid = 0;
+      for (int k = 0; k < K; k++) nvalid += c.valid[k];
+      solves += (unsigned long long)(iter + 1) * (unsigned long long)nvalid;
+    }
+    ex.phase(SPICEY_PH_Z, [&](int tid) {
+      if (!HYB && (PT >= 0 ? PT == 1 : ((top_pack >> 20) & 1) != 0)) {
+        SpiceyProg Pt{};
+        SpiceyRun Rt{};
+        spicey_pt_args(c.tail + spicey_pt_base_words(top_pack & 0xff), tid, Pt, Rt);
+        Ph2 p2{Pt, Rt, c, T, brem, zrem, &P, &R};
+        if (tid == 0 && Rt.iters)
+          for (int k = 0; k < K; k++)
+            if (c.valid[k]) Rt.iters[(size_t)c.inst[k] * (size_t)(steps + 1) + (size_t)step] = iter + 1;
+        p2.z_record(tid, step, ex.template regs<Regs>(tid), ((top_pack >> 16) & 1) != 0);
+      } else {
+        const SpiceyRun Rf = ex.fresh(R);
+        const SpiceyProg Pf = ex.fresh(P);
+        Ph2 p2{Pf, Rf, c, T, brem, zrem};
+        if (tid == 0 && Rf.iters)
+          for (int k = 0; k < K; k++)
+            if (c.valid[k]) Rf.iters[(size_t)c.inst[k] * (size_t)(steps + 1) + (size_t)step] = iter + 1;
+        p2.z_record(tid, step, ex.template regs<Regs>(tid), ((top_pack >> 16) & 1) != 0);
+      }
+    });
+  }
+  ex.phase(SPICEY_PH_PRO, [&](int tid) {
+    if (tid == 0) {
+      const SpiceyRun Rf = ex.fresh(R);
+      Rf.status[wg * 4 + 0] = code;
+      Rf.status[wg * 4 + 1] = c.flags[2];
+      Rf.status[wg * 4 + 2] = (int32_t)err_step;
+      Rf.status[wg * 4 + 3] = err_iter;
+      Rf.solves[wg] = solves;
+    }
+  });
+}

@@ -4,10 +4,10 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
+import harness_build
 from spicey_amd import abi
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -17,12 +17,7 @@ _LIB = None
 def lib():
     global _LIB
     if _LIB is None:
-        import fcntl
-        os.makedirs(os.path.join(_HERE, "_build"), exist_ok=True)
-        with open(os.path.join(_HERE, "_build", ".lock"), "w") as lk:  # (pytest-xdist workers: one build at a time)
-            fcntl.flock(lk, fcntl.LOCK_EX)
-            subprocess.run(["make", "-s", "-C", _HERE], check=True, stderr=subprocess.DEVNULL)
-        L = C.CDLL(os.path.join(_HERE, "_build", "libspicey_ac_exact_host.so"))
+        L = harness_build.load(_HERE, "libspicey_ac_exact_host.so")
         f64p, i32p, i64p = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int64)
         L.spicey_ac_exact_host_run.restype = C.c_int32
         L.spicey_ac_exact_host_run.argtypes = [C.POINTER(abi.SpiceyDesc), C.c_int32, C.c_int32, C.c_int32, C.c_int64, f64p, f64p, f64p, f64p,

@@ -1,12 +1,11 @@
 """ctypes view of the CPU harness of the AC measurements (tests/ac_measure_host/harness.cpp) and the buffers and request
 lists the host and GPU tests share."""
 import ctypes as C
-import fcntl
 import os
-import subprocess
 
 import numpy as np
 
+import harness_build
 from spicey_amd import abi
 from spicey_amd.ac_measure import make_ac_reqs
 
@@ -21,11 +20,7 @@ N_FREQS = (1, 2, 63, 64, 65, 129, 300)  # the lane-count edges
 def lib():
     global _LIB
     if _LIB is None:
-        os.makedirs(os.path.join(HERE, "_build"), exist_ok=True)
-        with open(os.path.join(HERE, "_build", ".lock"), "w") as lk:
-            fcntl.flock(lk, fcntl.LOCK_EX)
-            subprocess.run(["make", "-s", "-C", HERE], check=True, stderr=subprocess.DEVNULL)
-        L = C.CDLL(os.path.join(HERE, "_build", "libspicey_ac_measure_host.so"))
+        L = harness_build.load(HERE, "libspicey_ac_measure_host.so")
         L.spicey_acm_host_lanes.restype = C.c_int32
         L.spicey_acm_host_workspace_bytes.restype = C.c_int64
         L.spicey_acm_host_workspace_bytes.argtypes = [C.c_int32, C.c_int64, C.c_int32]

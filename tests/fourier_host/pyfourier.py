@@ -1,13 +1,12 @@
 """ctypes view of the CPU harness of the harmonics pass (tests/fourier_host/harness.cpp), the request lists the host and
 GPU tests share, and the one checker of every comparison with reduce_reference_fourier."""
 import ctypes as C
-import fcntl
 import math
 import os
-import subprocess
 
 import numpy as np
 
+import harness_build
 from spicey_amd import abi
 from spicey_amd.measure import make_four_reqs, reduce_reference_fourier
 
@@ -18,11 +17,7 @@ _LIB = None
 def lib():
     global _LIB
     if _LIB is None:
-        os.makedirs(os.path.join(HERE, "_build"), exist_ok=True)
-        with open(os.path.join(HERE, "_build", ".lock"), "w") as lk:
-            fcntl.flock(lk, fcntl.LOCK_EX)
-            subprocess.run(["make", "-s", "-C", HERE], check=True, stderr=subprocess.DEVNULL)
-        L = C.CDLL(os.path.join(HERE, "_build", "libspicey_fourier_host.so"))
+        L = harness_build.load(HERE, "libspicey_fourier_host.so")
         for fn in ("chunk", "threads", "max_harm"):
             getattr(L, "spicey_four_host_" + fn).restype = C.c_int32
         L.spicey_four_host_workspace_bytes.restype = C.c_int64

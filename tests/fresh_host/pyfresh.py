@@ -1,11 +1,10 @@
 """ctypes view of the CPU harness of the fresh-fill programs (tests/fresh_host/harness.cpp)."""
 import ctypes as C
-import fcntl
 import os
-import subprocess
 
 import numpy as np
 
+import harness_build
 from spicey_amd import abi
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -20,11 +19,7 @@ RUN_FIELDS = ("nKeep", "nRestore", "streamed_tasks", "resident_tasks", "nDynEnt"
 def lib():
     global _LIB
     if _LIB is None:
-        os.makedirs(os.path.join(HERE, "_build"), exist_ok=True)
-        with open(os.path.join(HERE, "_build", ".lock"), "w") as lk:
-            fcntl.flock(lk, fcntl.LOCK_EX)
-            subprocess.run(["make", "-s", "-C", HERE], check=True, stderr=subprocess.DEVNULL)
-        L = C.CDLL(os.path.join(HERE, "_build", "libspicey_fresh_host.so"))
+        L = harness_build.load(HERE, "libspicey_fresh_host.so")
         i64p = C.POINTER(C.c_int64)
         L.spicey_fresh_check.restype = C.c_int32
         L.spicey_fresh_check.argtypes = [C.POINTER(abi.SpiceyDesc), C.c_int32, C.c_int32, i64p]

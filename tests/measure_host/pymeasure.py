@@ -1,12 +1,11 @@
 """ctypes view of the CPU harness of the waveform measurements (tests/measure_host/harness.cpp) and the request lists the
 host and GPU tests share."""
 import ctypes as C
-import fcntl
 import os
-import subprocess
 
 import numpy as np
 
+import harness_build
 from spicey_amd import abi
 from spicey_amd.measure import make_reqs, reduce_reference
 
@@ -17,11 +16,7 @@ _LIB = None
 def lib():
     global _LIB
     if _LIB is None:
-        os.makedirs(os.path.join(HERE, "_build"), exist_ok=True)
-        with open(os.path.join(HERE, "_build", ".lock"), "w") as lk:
-            fcntl.flock(lk, fcntl.LOCK_EX)
-            subprocess.run(["make", "-s", "-C", HERE], check=True, stderr=subprocess.DEVNULL)
-        L = C.CDLL(os.path.join(HERE, "_build", "libspicey_measure_host.so"))
+        L = harness_build.load(HERE, "libspicey_measure_host.so")
         L.spicey_meas_host_chunk.restype = C.c_int32
         L.spicey_meas_host_threads.restype = C.c_int32
         L.spicey_meas_host_workspace_bytes.restype = C.c_int64

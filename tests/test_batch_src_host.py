@@ -2,14 +2,13 @@
 v1, v2 with K = 1 and K = 2, the hybrid layout and the reference-order engine, every instance against the oracle on its
 own table; a per-instance layout whose rows are all equal gives the bits of the shared table."""
 import ctypes as C
-import fcntl
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from batch_variants import PerInstanceOracle
+import harness_build
 from conftest import REPO, bits_equal
 from spicey_amd import abi, synth
 
@@ -20,11 +19,7 @@ _LIB = None
 def lib():
     global _LIB
     if _LIB is None:
-        os.makedirs(os.path.join(HERE, "_build"), exist_ok=True)
-        with open(os.path.join(HERE, "_build", ".lock"), "w") as lk:
-            fcntl.flock(lk, fcntl.LOCK_EX)
-            subprocess.run(["make", "-s", "-C", HERE], check=True, stderr=subprocess.DEVNULL)
-        L = C.CDLL(os.path.join(HERE, "_build", "libspicey_batch_host.so"))
+        L = harness_build.load(HERE, "libspicey_batch_host.so")
         f64p, i32p = C.POINTER(C.c_double), C.POINTER(C.c_int32)
         L.spicey_batch_emul_run.restype = C.c_int32
         L.spicey_batch_emul_run.argtypes = [C.POINTER(abi.SpiceyDesc), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_double, f64p, C.c_int64,

@@ -1,13 +1,12 @@
 """ctypes view of the CPU harness of the edge-timing pass (tests/timing_host/harness.cpp), the request pool the host and GPU
 tests share, and the sanitized self-test's build."""
 import ctypes as C
-import fcntl
 import os
-import subprocess
 import sys
 
 import numpy as np
 
+import harness_build
 from spicey_amd import abi
 from spicey_amd.measure import make_timing_reqs
 
@@ -18,20 +17,10 @@ import pymeasure as pm  # noqa: E402
 _LIB = None
 
 
-def _make(target: str) -> None:
-    os.makedirs(os.path.join(HERE, "_build"), exist_ok=True)
-    with open(os.path.join(HERE, "_build", ".lock"), "w") as lk:
-        fcntl.flock(lk, fcntl.LOCK_EX)
-        p = subprocess.run(["make", "-s", "-C", HERE, target], capture_output=True, text=True)
-        if p.returncode != 0:
-            raise RuntimeError(f"make {target} failed in {HERE}:\n{p.stdout}{p.stderr}")
-
-
 def lib():
     global _LIB
     if _LIB is None:
-        _make("_build/libspicey_timing_host.so")
-        L = C.CDLL(os.path.join(HERE, "_build", "libspicey_timing_host.so"))
+        L = harness_build.load(HERE, "libspicey_timing_host.so")
         L.spicey_tim_host_chunk.restype = C.c_int32
         L.spicey_tim_host_threads.restype = C.c_int32
         L.spicey_tim_host_workspace_bytes.restype = C.c_int64
@@ -45,7 +34,7 @@ def lib():
 
 def selftest_path() -> str:
     """The sanitized stand-alone program (selftest.cpp + harness.cpp), built on first use."""
-    _make("_build/selftest")
+    harness_build.make(HERE, "_build/selftest")
     return os.path.join(HERE, "_build", "selftest")
 
 
