@@ -477,6 +477,68 @@ int32_t spicey_run_measure_timing(SpiceyHandle *h, int64_t steps, double dt, con
  * HIP events. */
 double spicey_last_timing_ms(SpiceyHandle *h);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Spectrum of a transient's waveforms on the device (what SPICE users know as fft / spec / .meas ... FFT): a fifth pass
+ * over the same step-major buffers, for the questions fourier() cannot answer because nobody knows f0.  Unlike the other
+ * passes it is no streaming reduction but a batched FFT in LDS, one workgroup per (instance, request).
+ * One request = one signal (signal, col, col_ref exactly as in SpiceyMeasReq: one rounded subtraction per sample), a first
+ * step step_from, a length N = 2^log2n (3 <= log2n <= 13: N = 8 .. 8192), a window (0 rectangular, 1 periodic Hann), an
+ * inclusive band of bins [bin_from, bin_to] inside [0, N/2] and a kind (0 bins, 1 dominant).  The N samples x_j =
+ * signal at step step_from + j, j = 0 .. N-1, enter; they must lie inside the run.
+ * The numbers, in this order, every product, sum and difference rounded on its own (no FMA contraction):
+ *   1. y_j = x_j w_j, one rounded product (skipped for window 0), w_j = 0.5 - 0.5 cos((2.0 M_PI j) / N) from the HOST's
+ *      libm, one table per distinct (N, window).
+ *   2. Radix-2 decimation in time over N complex points (im = 0) on the bit-reversed input: for h = 1, 2, 4, ... N/2 and
+ *      every pair (a, b) = (z[i], z[i+h]), i = 2h g + j, 0 <= j < h, with W = T[j N / (2h)]:
+ *        tr = b.re W.re - b.im W.im,  ti = b.re W.im + b.im W.re,  z[i] = a + t,  z[i+h] = a - t.
+ *      T[k] = (cos((2.0 M_PI k) / N), -sin((2.0 M_PI k) / N)), k < N/2, from the HOST's libm, T[0] = (1, 0) and T[N/4] =
+ *      (0, -1) set exactly; one table per distinct N.  The device never evaluates a sine.
+ *   3. P_k = re_k re_k + im_k im_k.
+ * So X_k = sum_j y_j exp(-2 pi i j k / N): phases refer to the window's FIRST sample (fourier()'s refer to t = 0).
+ * Results, at the head of a row of out_stride doubles per (instance, request), the rest of the row 0:
+ *   kind 0   2 (bin_to - bin_from + 1) doubles {re, im} per bin of the band
+ *   kind 1   8 doubles {k, re_k, im_k, P_k-1, P_k, P_k+1, 0, 0}: k the bin of the band with the largest P by the plain
+ *            comparison P > best in ascending k from best = 0 (the first occurrence wins, a NaN never wins), as a double;
+ *            k = -1 and the other fields 0 when no bin wins (an all-zero band).  The neighbours come from the bins
+ *            0 .. N/2 whether or not they lie in the band; one that does not exist is -1.0.
+ * A row is a function of the N samples and the request alone: not of n_inst, the launch, the workgroup size or the other
+ * requests of the list. */
+#define SPICEY_SPEC_MIN_LOG2N 3
+#define SPICEY_SPEC_MAX_LOG2N 13
+typedef struct SpiceySpecReq {
+  int32_t signal, col, col_ref, kind;         /* kind: 0 bins, 1 dominant */
+  int64_t step_from;                          /* samples step_from .. step_from + N - 1 */
+  int32_t log2n, window, bin_from, bin_to;    /* N = 2^log2n; window: 0 rectangular, 1 periodic Hann */
+} SpiceySpecReq;
+
+/* Bytes of device workspace spicey_spectrum_device needs for this request list (request table, twiddle and window
+ * tables); -1 for a list whose lengths, windows, bands or first steps no launch accepts, and for counts <= 0. */
+int64_t spicey_spectrum_workspace_bytes(int32_t n_inst, int64_t n_points, const SpiceySpecReq *reqs, int32_t n_req);
+/* The pass alone, on any DEVICE buffers d_v [n_inst][n_points][n_v] and d_i [n_inst][n_points][n_i] (or NULL): needs no
+ * handle.  reqs is a HOST array; d_out [n_inst][n_req][out_stride] and d_work (work_bytes >=
+ * spicey_spectrum_workspace_bytes) are DEVICE buffers.  One kernel launch per distinct N of the list (dynamic LDS of 16 N
+ * bytes each), enqueued on `stream` (a hipStream_t, NULL = default stream) without synchronising.  SPICEY_ERR_BAD_DESC,
+ * with a text containing "spectrum" in spicey_last_error(NULL), nothing launched and the buffers untouched, for: an
+ * unknown signal, kind or window; a column out of range; signal = 1 with d_i == NULL; log2n outside 3..13; step_from < 0
+ * or step_from + N > n_points; a band outside [0, N/2] or with bin_from > bin_to; out_stride shorter than the longest row;
+ * dt not finite or <= 0; a workspace that is too small; n_req <= 0; null buffers. */
+int32_t spicey_spectrum_device(int32_t device, int32_t n_inst, int64_t n_points, double dt, const double *d_v, int32_t n_v,
+                               const double *d_i, int32_t n_i, const SpiceySpecReq *reqs, int32_t n_req, double *d_out,
+                               int32_t out_stride, void *d_work, int64_t work_bytes, void *stream);
+/* spicey_run_measure_timing with the spectrum pass behind the other three: one transient run, currents recorded only if
+ * a request of any list has signal = 1, then the measurement pass (if n_req > 0), the harmonics pass (if n_four > 0), the
+ * timing pass (if n_timing > 0) and the spectrum pass (n_spec >= 1) on the handle's stream over the same device
+ * waveforms; only meas, four, timing, spec [n_inst][n_spec][spec_stride] and iters (or NULL) come back — also after
+ * SPICEY_ERR_SINGULAR.  meas / four / timing may be NULL when their count is 0.  Everything else is as for
+ * spicey_run_measure. */
+int32_t spicey_run_measure_spectrum(SpiceyHandle *h, int64_t steps, double dt, const double *src_table, int32_t src_per_inst,
+                                    const SpiceyMeasReq *reqs, int32_t n_req, double *meas, const SpiceyFourReq *freqs,
+                                    int32_t n_four, double *four, int32_t four_stride, const SpiceyTimingReq *treqs,
+                                    int32_t n_timing, double *timing, const SpiceySpecReq *sreqs, int32_t n_spec, double *spec,
+                                    int32_t spec_stride, int32_t *iters);
+/* Duration in ms of the last spicey_run_measure_spectrum's spectrum pass (all of its launches), measured with HIP events. */
+double spicey_last_spectrum_ms(SpiceyHandle *h);
+
 /* Library build info: "spicey_hip <abi> gfx950 …" */
 const char *spicey_version(void);
 

@@ -98,6 +98,29 @@ assert TIMING_EDGE_DTYPE.itemsize == C.sizeof(SpiceyTimingEdge) == 48 and TIMING
 TIMING_ABS, TIMING_MINMAX, TIMING_ENDS = 0, 1, 2
 
 
+class SpiceySpecReq(C.Structure):
+    _fields_ = [("signal", C.c_int32), ("col", C.c_int32), ("col_ref", C.c_int32), ("kind", C.c_int32), ("step_from", C.c_int64),
+                ("log2n", C.c_int32), ("window", C.c_int32), ("bin_from", C.c_int32), ("bin_to", C.c_int32)]
+
+
+# a spectrum request list (spicey_spectrum_device) is one array of these
+SPEC_REQ_DTYPE = np.dtype([("signal", "<i4"), ("col", "<i4"), ("col_ref", "<i4"), ("kind", "<i4"), ("step_from", "<i8"),
+                           ("log2n", "<i4"), ("window", "<i4"), ("bin_from", "<i4"), ("bin_to", "<i4")])
+assert SPEC_REQ_DTYPE.itemsize == C.sizeof(SpiceySpecReq) == 40
+SPEC_BINS, SPEC_DOMINANT = 0, 1
+SPEC_RECT, SPEC_HANN = 0, 1
+SPEC_MIN_LOG2N, SPEC_MAX_LOG2N = 3, 13
+SPEC_DOM_DOUBLES = 8
+
+
+def spec_row_doubles(reqs) -> int:
+    """Doubles of a result row that holds every request of a spectrum list: 2 per bin of the widest band, 8 for a dominant."""
+    r = np.ascontiguousarray(reqs, dtype=SPEC_REQ_DTYPE).reshape(-1)
+    if not len(r):
+        return 1
+    return int(np.where(r["kind"] == SPEC_BINS, 2 * (r["bin_to"].astype(np.int64) - r["bin_from"] + 1), SPEC_DOM_DOUBLES).max())
+
+
 class SpiceyAcMeasReq(C.Structure):
     _fields_ = [("num_signal", C.c_int32), ("num_col", C.c_int32), ("num_col_ref", C.c_int32),
                 ("den_signal", C.c_int32), ("den_col", C.c_int32), ("den_col_ref", C.c_int32), ("what", C.c_int32), ("kind", C.c_int32),

@@ -58,12 +58,31 @@ in the edge's search range.  rise_time is the delay from the first rise through 
 at or after it (fall_time: falls through hi, then lo); settle is the later of the last crossings (either direction) of
 rel(1 - tol, of="ends") and rel(1 + tol, of="ends"), 0.0 if the signal never leaves that band.  A window needs two steps.
 
+Spectrum.  A fourth family, for the questions fourier() cannot answer because nobody knows f0 (what SPICE calls fft / spec):
+a batched FFT on the device (spicey_run_measure_spectrum, a pass behind the other three over the same waveforms;
+include/spicey_hip.h has the definition, bit for bit):
+    spectrum("v(out)", n=None, window="hann", f_from=None, f_to=None)   n, df, window, freq[], mag[], phase_deg[]
+    dominant("v(out)", n=None, window="hann", f_from=None, f_to=None)   bin, freq, mag, freq_bin, n, df
+The N = n samples are the LAST n of the window [t_from, t_to] (the nearest-step rule above); n=None picks the largest power
+of two that fits, at most 8192; n must be a power of two in 8..8192 and no longer than the window.  window is "hann" (the
+periodic Hann window) or "rect".  df = 1 / (N dt), freq[k] = k df.  f_from / f_to select the bins ceil(f_from N dt) ..
+floor(f_to N dt), clamped to [0, N/2] (default: all of them; dominant() starts at bin 1, so DC is excluded); an empty band
+is a ValueError.  mag = |X_k| s / sum(w) with s = 1 for k = 0 and k = N/2, else 2 — a sine of amplitude A on a bin shows as
+A — and phase_deg = degrees(atan2(im, re)) of X_k = sum_j x_j w_j exp(-2 pi i j k / N): the phase of a cosine, referred to
+the window's FIRST sample (fourier() refers its phases to t = 0).  dominant() is the band's bin with the largest power (the
+first of equals), found on the device; freq_bin = k df, and freq = (k + d) df refines it by the parabola through the
+magnitudes a, b, c of the bins k-1, k, k+1: d = 0.5 (a - c) / (a - 2 b + c), d = 0 where a neighbour does not exist or the
+denominator is 0.  Every field of dominant() is None when no bin has any power.  A dict without these specs takes the path
+it always took.
+
 reduce_reference() is the same definition in plain numpy; it is what the tests compare the device with, and what runs
 behind a backend that has no run_measure (backend.run, then reduce_reference: the CPU oracle works unchanged);
-reduce_reference_fourier() is the same for the harmonics, reduce_reference_timing() for the edge timing.
+reduce_reference_fourier() is the same for the harmonics, reduce_reference_timing() for the edge timing,
+reduce_reference_spectrum() for the spectrum (that one bit for bit: the same elementwise operations in the same order).
 """
 from __future__ import annotations
 
+import functools
 import math
 import re
 from dataclasses import dataclass
@@ -103,6 +122,22 @@ class Fourier:
     t_from: Optional[float] = None
     t_to: Optional[float] = None
     periods: Optional[int] = None
+
+
+_WINDOWS = {"rect": abi.SPEC_RECT, "hann": abi.SPEC_HANN}
+_WINDOW_NAMES = {v: k for k, v in _WINDOWS.items()}
+
+
+@dataclass(frozen=True)
+class Spectrum:
+    signal: str
+    n: Optional[int] = None
+    window: int = abi.SPEC_HANN
+    f_from: Optional[float] = None
+    f_to: Optional[float] = None
+    t_from: Optional[float] = None
+    t_to: Optional[float] = None
+    kind: int = abi.SPEC_BINS
 
 
 _OF = {"minmax": abi.TIMING_MINMAX, "ends": abi.TIMING_ENDS}
@@ -259,6 +294,64 @@ def fourier(signal: str, f0: float, harmonics: int = 9, t_from: Optional[float] 
     return Fourier(str(signal), f0, int(harmonics), t_from, t_to, periods)
 
 
+def _spectrum_spec(who: str, kind: int, signal, n, window, f_from, f_to, t_from, t_to) -> Spectrum:
+    if window not in _WINDOWS:
+        raise ValueError(f"{who}: window must be 'hann' or 'rect', got {window!r}")
+    if n is not None:
+        if isinstance(n, bool) or int(n) != n or not (1 << abi.SPEC_MIN_LOG2N) <= int(n) <= (1 << abi.SPEC_MAX_LOG2N) or int(n) & (int(n) - 1):
+            raise ValueError(f"{who}: n must be a power of two in {1 << abi.SPEC_MIN_LOG2N}..{1 << abi.SPEC_MAX_LOG2N}, got {n!r}")
+        n = int(n)
+    for nm, f in (("f_from", f_from), ("f_to", f_to)):
+        if f is not None and not (math.isfinite(float(f)) and float(f) >= 0):
+            raise ValueError(f"{who}: {nm} must be finite and >= 0, got {f!r}")
+    return Spectrum(str(signal), n, _WINDOWS[window], None if f_from is None else float(f_from), None if f_to is None else float(f_to), t_from, t_to, kind)
+
+
+def spectrum(signal: str, n: Optional[int] = None, window: str = "hann", f_from: Optional[float] = None, f_to: Optional[float] = None,
+             t_from: Optional[float] = None, t_to: Optional[float] = None) -> Spectrum:
+    """The band's bins of the n-point FFT of the window's last n samples: {n, df, window, freq[], mag[], phase_deg[]}.  The
+    phases refer to the window's FIRST sample (fourier()'s refer to t = 0); see the module text."""
+    return _spectrum_spec("spectrum", abi.SPEC_BINS, signal, n, window, f_from, f_to, t_from, t_to)
+
+
+def dominant(signal: str, n: Optional[int] = None, window: str = "hann", f_from: Optional[float] = None, f_to: Optional[float] = None,
+             t_from: Optional[float] = None, t_to: Optional[float] = None) -> Spectrum:
+    """The band's strongest bin, found on the device: {bin, freq, mag, freq_bin, n, df}; DC is excluded unless f_from says
+    otherwise; see the module text."""
+    return _spectrum_spec("dominant", abi.SPEC_DOMINANT, signal, n, window, f_from, f_to, t_from, t_to)
+
+
+def make_spec_reqs(rows: Sequence[tuple]) -> np.ndarray:
+    """Request records (abi.SPEC_REQ_DTYPE) from tuples (signal, col, col_ref, kind, step_from, log2n, window, bin_from, bin_to)."""
+    a = np.zeros(len(rows), abi.SPEC_REQ_DTYPE)
+    for k, r in enumerate(rows):
+        a[k] = tuple(r)
+    return a
+
+
+def spectrum_window(spec: Spectrum, dt: float, steps: int, name: str = "") -> Tuple[int, int, int, int]:
+    """(step_from, log2n, bin_from, bin_to) of a spectrum / dominant spec in a run of `steps` steps of dt, or ValueError
+    (module text)."""
+    s0 = time_to_step(spec.t_from, dt, steps, 0)
+    s1 = time_to_step(spec.t_to, dt, steps, steps)
+    count = s1 - s0 + 1
+    n = spec.n
+    if n is None:
+        if count < (1 << abi.SPEC_MIN_LOG2N):
+            raise ValueError(f"measure {name!r}: the window of {max(count, 0)} samples is shorter than the shortest transform of {1 << abi.SPEC_MIN_LOG2N}")
+        n = min(1 << (count.bit_length() - 1), 1 << abi.SPEC_MAX_LOG2N)
+    elif n > count:
+        raise ValueError(f"measure {name!r}: n = {n} is longer than the window of {max(count, 0)} samples")
+    half = n // 2
+    # (dominant()'s default lower edge is df = bin 1, set as a bin: df N dt need not round to 1.0)
+    b0 = (1 if spec.kind == abi.SPEC_DOMINANT else 0) if spec.f_from is None else math.ceil(spec.f_from * n * dt)
+    b1 = half if spec.f_to is None else math.floor(spec.f_to * n * dt)
+    # (a lower edge above Nyquist leaves no bin: the clamp is for an upper edge beyond it)
+    if b0 > half or b0 > b1:
+        raise ValueError(f"measure {name!r}: no bin of the {n}-point transform (df = {1.0 / (n * dt)} Hz) lies in the band [{spec.f_from}, {spec.f_to}] Hz")
+    return s1 - n + 1, n.bit_length() - 1, max(b0, 0), min(b1, half)
+
+
 def make_four_reqs(rows: Sequence[tuple]) -> np.ndarray:
     """Request records (abi.FOUR_REQ_DTYPE) from tuples (signal, col, col_ref, n_harm, step_from, step_to, f0)."""
     a = np.zeros(len(rows), abi.FOUR_REQ_DTYPE)
@@ -348,9 +441,9 @@ class _Plan:
                 # (every edge of the spec's requests, resolved: a list in the place of the one signal)
                 parsed.append((name, spec, [tuple(None if e is None else _parse_signal(ckt, e.signal) for e in rq[:2]) for rq in spec.requests()]))
                 continue
-            if not isinstance(spec, (Stats, Cross, Fourier)):
+            if not isinstance(spec, (Stats, Cross, Fourier, Spectrum)):
                 raise TypeError(f"measure {name!r}: expected stats(...), cross(...), fourier(...), when(...), delay(...), rise_time(...), "
-                                f"fall_time(...) or settle(...), got {type(spec).__name__}")
+                                f"fall_time(...), settle(...), spectrum(...) or dominant(...), got {type(spec).__name__}")
             parsed.append((name, spec, _parse_signal(ckt, spec.signal)))
         sigs = [s for _, _, p in parsed for s in ([e for rq in p for e in rq if e is not None] if isinstance(p, list) else [p])]
         nodes = sorted({n for sig, a, b in sigs if sig == 0 for n in (a, b) if n != 0})
@@ -358,8 +451,8 @@ class _Plan:
         # (a device descriptor records at least one node; with current measures only, the first one)
         self.out_nodes = nodes if nodes else [1]
         col = {n: c for c, n in enumerate(self.out_nodes)}
-        rows, frows, trows = [], [], []
-        self.names = []  # (name, "meas" | "four" | the timing spec, its (first) place in reqs / freqs / treqs), in the dict's order
+        rows, frows, trows, srows = [], [], [], []
+        self.names = []  # (name, "meas" | "four" | "spec" | the timing spec, its (first) place in reqs / freqs / sreqs / treqs), in the dict's order
 
         def columns(sig, a, b):
             return (col[a], col[b] if b else -1) if sig == 0 else (a, -1)
@@ -392,6 +485,11 @@ class _Plan:
                 self.names.append((name, "four", len(frows)))
                 frows.append((sig, c, cr, spec.harmonics, s0, s1, spec.f0))
                 continue
+            if isinstance(spec, Spectrum):
+                s0, log2n, b0, b1 = spectrum_window(spec, dt, steps, name)
+                self.names.append((name, "spec", len(srows)))
+                srows.append((sig, c, cr, spec.kind, s0, log2n, spec.window, b0, b1))
+                continue
             s0 = time_to_step(spec.t_from, dt, steps, 0)
             s1 = time_to_step(spec.t_to, dt, steps, steps)
             if s0 > s1:
@@ -404,6 +502,7 @@ class _Plan:
         self.reqs = make_reqs(rows)
         self.freqs = make_four_reqs(frows)  # (empty: the dict takes the path without the harmonics pass)
         self.treqs = make_timing_reqs(trows)  # (empty: the dict takes the path without the timing pass)
+        self.sreqs = make_spec_reqs(srows)  # (empty: the dict takes the path without the spectrum pass)
 
     def flatten(self, ckt: ParsedCircuit) -> abi.FlatCircuit:
         flat = abi.flatten(ckt)
@@ -412,16 +511,18 @@ class _Plan:
 
     def key(self) -> bytes:
         """What a batch groups by beside topology and run: the resolved request tables."""
-        return self.reqs.tobytes() + b"|" + self.freqs.tobytes() + (b"|" + self.treqs.tobytes() if len(self.treqs) else b"")
+        key = self.reqs.tobytes() + b"|" + self.freqs.tobytes() + (b"|" + self.treqs.tobytes() if len(self.treqs) else b"")
+        return key + b"|s|" + self.sreqs.tobytes() if len(self.sreqs) else key
 
     def run(self, be, flat: abi.FlatCircuit, steps: int, dt: float, src: np.ndarray) -> dict:
-        return backend_reduce(be, flat, steps, dt, src, self.reqs, self.freqs, self.treqs, self.need_i)
+        return backend_reduce(be, flat, steps, dt, src, self.reqs, self.freqs, self.treqs, self.need_i, self.sreqs)
 
     def values(self, res: dict, j: int, dt: float) -> Dict[str, dict]:
         """Instance j of a result (meas [n_inst][n_req][8], four [n_inst][n_four][row], timing [n_inst][n_timing][8]) ->
         {name: {...}}."""
         return {name: derive(self.reqs[k], res["meas"][j][k], dt) if kind == "meas" else derive_fourier(self.freqs[k], res["four"][j][k], dt)
-                if kind == "four" else derive_timing(kind, res["timing"][j][k:k + len(kind.requests())])
+                if kind == "four" else derive_spectrum(self.sreqs[k], res["spec"][j][k], dt) if kind == "spec"
+                else derive_timing(kind, res["timing"][j][k:k + len(kind.requests())])
                 for name, kind, k in self.names}
 
 
@@ -456,6 +557,112 @@ def derive_fourier(req, row, dt: float) -> dict:
         ph.append(math.degrees(math.atan2(-b, a)))
     thd = math.sqrt(sum(m * m for m in mag[1:])) / mag[0] if H > 1 and mag[0] != 0.0 else None
     return {"f0": f0, "periods": n * dt * f0, "dc": float(row[0]) / n, "mag": mag, "phase_deg": ph, "thd": thd}
+
+
+@functools.lru_cache(maxsize=None)
+def spectrum_tables(log2n: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """(T_re[N/2], T_im[N/2], w[N]) of include/spicey_hip.h for N = 2^log2n, by this process's libm (math.cos / math.sin: the
+    functions the library's host code calls): T[k] = (cos(a_k), -sin(a_k)), w_j = 0.5 - 0.5 cos(a_j), a_k = (2.0 pi k) / N,
+    T[0] and T[N/4] exact.  Read-only arrays."""
+    N = 1 << log2n
+    ang = [((2.0 * math.pi) * float(k)) / float(N) for k in range(N)]
+    t_re = np.array([math.cos(a) for a in ang[:N // 2]])
+    t_im = np.array([-math.sin(a) for a in ang[:N // 2]])
+    t_re[0], t_im[0], t_re[N // 4], t_im[N // 4] = 1.0, 0.0, 0.0, -1.0
+    w = np.array([0.5 - 0.5 * math.cos(a) for a in ang])
+    for a in (t_re, t_im, w):
+        a.setflags(write=False)
+    return t_re, t_im, w
+
+
+def _spectrum_scale(req) -> Tuple[int, float]:
+    """(N, sum of the window's N weights) of a request."""
+    N = 1 << int(req["log2n"])
+    sw = math.fsum(spectrum_tables(int(req["log2n"]))[2].tolist()) if int(req["window"]) == abi.SPEC_HANN else float(N)
+    return N, sw
+
+
+def derive_spectrum(req, row, dt: float) -> dict:
+    """The values of one spectrum / dominant spec from its row (module text)."""
+    N, sw = _spectrum_scale(req)
+    df = 1.0 / (N * dt)
+
+    def side(k):
+        return 1.0 if k == 0 or k == N // 2 else 2.0
+
+    if int(req["kind"]) == abi.SPEC_BINS:
+        b0, b1 = int(req["bin_from"]), int(req["bin_to"])
+        ks = list(range(b0, b1 + 1))
+        re_, im_ = [float(v) for v in row[0:2 * len(ks):2]], [float(v) for v in row[1:2 * len(ks):2]]
+        return {"n": N, "df": df, "window": _WINDOW_NAMES[int(req["window"])], "freq": [k * df for k in ks],
+                "mag": [math.hypot(a, b) * side(k) / sw for k, a, b in zip(ks, re_, im_)],
+                "phase_deg": [math.degrees(math.atan2(b, a)) for a, b in zip(re_, im_)]}
+    k = int(row[0])
+    if k < 0:
+        return {"bin": None, "freq": None, "mag": None, "freq_bin": None, "n": None, "df": None}
+    pa, pb, pc = float(row[3]), float(row[4]), float(row[5])
+    d = 0.0
+    if pa >= 0.0 and pc >= 0.0:
+        a, b, c = math.sqrt(pa), math.sqrt(pb), math.sqrt(pc)
+        den = a - 2.0 * b + c
+        if den != 0.0:
+            d = 0.5 * (a - c) / den
+    return {"bin": k, "freq": (k + d) * df, "mag": math.sqrt(pb) * side(k) / sw, "freq_bin": k * df, "n": N, "df": df}
+
+
+def reduce_reference_spectrum(out_v: np.ndarray, out_i: Optional[np.ndarray], reqs, dt: float) -> np.ndarray:
+    """The definition of spicey_spectrum_device in vectorised numpy: out_v [n_inst][n_points][n_v], out_i likewise or None,
+    reqs records of abi.SPEC_REQ_DTYPE -> [n_inst][n_req][row], row = the longest request's, zeros behind a request's own.
+    The same elementwise IEEE operations on the same operands as the device's (every product, sum and difference a numpy
+    operation of its own), whole stages at a time, the tables by this process's libm: the bit-for-bit yardstick."""
+    reqs = np.ascontiguousarray(reqs, dtype=abi.SPEC_REQ_DTYPE).reshape(-1)
+    out_v = np.asarray(out_v, dtype=np.float64)
+    ni, n_points = out_v.shape[0], out_v.shape[1]
+    rows = np.zeros((ni, len(reqs), abi.spec_row_doubles(reqs)))
+    for r, q in enumerate(reqs):
+        log2n, s0, kind, b0, b1 = int(q["log2n"]), int(q["step_from"]), int(q["kind"]), int(q["bin_from"]), int(q["bin_to"])
+        if not abi.SPEC_MIN_LOG2N <= log2n <= abi.SPEC_MAX_LOG2N:
+            raise ValueError(f"reduce_reference_spectrum: request {r}: log2n {log2n} outside {abi.SPEC_MIN_LOG2N}..{abi.SPEC_MAX_LOG2N}")
+        N = 1 << log2n
+        half = N // 2
+        if not (0 <= s0 and s0 + N <= n_points) or not (0 <= b0 <= b1 <= half) or kind not in (abi.SPEC_BINS, abi.SPEC_DOMINANT) \
+                or int(q["window"]) not in (abi.SPEC_RECT, abi.SPEC_HANN):
+            raise ValueError(f"reduce_reference_spectrum: request {r}: samples [{s0}, {s0 + N}) outside the run, band [{b0}, {b1}] outside [0, {half}], "
+                             f"or unknown kind / window")
+        t_re, t_im, w = spectrum_tables(log2n)
+        y = _signal_samples(out_v, out_i, q, "reduce_reference_spectrum")[:, s0:s0 + N]
+        if int(q["window"]) == abi.SPEC_HANN:
+            y = y * w[None, :]
+        j = np.arange(N)
+        rev = np.zeros(N, np.int64)
+        for b in range(log2n):
+            rev |= ((j >> b) & 1) << (log2n - 1 - b)
+        re_ = np.ascontiguousarray(y[:, rev])  # (slot bitrev(j) holds y_j; bitrev is its own inverse)
+        im_ = np.zeros_like(re_)
+        for s in range(log2n):
+            h = 1 << s
+            k = np.arange(h) << (log2n - 1 - s)
+            wr, wi = t_re[k][None, None, :], t_im[k][None, None, :]
+            re4, im4 = re_.reshape(ni, N // (2 * h), 2, h), im_.reshape(ni, N // (2 * h), 2, h)
+            ar, ai, br, bi = re4[:, :, 0, :], im4[:, :, 0, :], re4[:, :, 1, :], im4[:, :, 1, :]
+            tr = br * wr - bi * wi
+            ti = br * wi + bi * wr
+            re_ = np.stack([ar + tr, ar - tr], axis=2).reshape(ni, N)
+            im_ = np.stack([ai + ti, ai - ti], axis=2).reshape(ni, N)
+        if kind == abi.SPEC_BINS:
+            nb = b1 - b0 + 1
+            rows[:, r, 0:2 * nb:2] = re_[:, b0:b1 + 1]
+            rows[:, r, 1:2 * nb:2] = im_[:, b0:b1 + 1]
+            continue
+        P = re_[:, :half + 1] * re_[:, :half + 1] + im_[:, :half + 1] * im_[:, :half + 1]
+        band = np.where(np.isnan(P[:, b0:b1 + 1]), -1.0, P[:, b0:b1 + 1])  # (`P > best`: a NaN never wins)
+        for i in range(ni):
+            k = b0 + int(np.argmax(band[i]))  # (first occurrence)
+            if not band[i, k - b0] > 0.0:
+                rows[i, r, 0] = -1.0
+                continue
+            rows[i, r, :6] = (k, re_[i, k], im_[i, k], P[i, k - 1] if k >= 1 else -1.0, P[i, k], P[i, k + 1] if k + 1 <= half else -1.0)
+    return rows
 
 
 def derive_timing(spec, rows) -> dict:
@@ -654,16 +861,17 @@ def reduce_reference_fourier(out_v: np.ndarray, out_i: Optional[np.ndarray], req
 
 
 def backend_reduce(be, flat: abi.FlatCircuit, steps: int, dt: float, src: np.ndarray, reqs: np.ndarray, freqs: np.ndarray, treqs: np.ndarray,
-                   need_i: bool) -> dict:
-    """The backend's run_measure_timing, run_measure_fourier or run_measure — the first whose own list is not empty — or for
-    a backend without that method its run followed by the numpy reductions of that method's passes."""
-    method, args = ("run_measure_timing", (reqs, freqs, treqs)) if len(treqs) else ("run_measure_fourier", (reqs, freqs)) if len(freqs) else \
-        ("run_measure", (reqs,))
+                   need_i: bool, sreqs: Sequence = ()) -> dict:
+    """The backend's run_measure_spectrum, run_measure_timing, run_measure_fourier or run_measure — the first whose own list
+    is not empty — or for a backend without that method its run followed by the numpy reductions of that method's passes."""
+    method, args = ("run_measure_spectrum", (reqs, freqs, treqs, sreqs)) if len(sreqs) else ("run_measure_timing", (reqs, freqs, treqs)) if len(treqs) else \
+        ("run_measure_fourier", (reqs, freqs)) if len(freqs) else ("run_measure", (reqs,))
     if hasattr(be, method):
         return getattr(be, method)(flat, steps, dt, src, *args)
     res = be.run(flat, steps, dt, src, want_currents=need_i)
     if res["status"] == abi.OK or (res["status"] == abi.ERR_SINGULAR and res.get("partial")):
-        for key, fn, lst in zip(("meas", "four", "timing"), (reduce_reference, reduce_reference_fourier, reduce_reference_timing), args):
+        for key, fn, lst in zip(("meas", "four", "timing", "spec"),
+                                (reduce_reference, reduce_reference_fourier, reduce_reference_timing, reduce_reference_spectrum), args):
             res[key] = fn(res["out_v"], res.get("out_i"), lst, dt)  # (an empty list: [n_inst][0][8], [n_inst][0][1])
     return res
 
@@ -679,7 +887,7 @@ def _backend(backend, exact_order: bool, device: int, diagnostics: bool, who: st
 
 
 def measureTRAN(ckt: ParsedCircuit, measures: Dict[str, object], *, exact_order: bool = False, device: int = 0, backend=None) -> Optional[dict]:
-    """The transient of `ckt` reduced to {name: {...}} for measures = {name: stats(...) | cross(...) | fourier(...) | when(...) | delay(...) | ...} (module text).  None
+    """The transient of `ckt` reduced to {name: {...}} for measures = {name: stats(...) | cross(...) | fourier(...) | when(...) | delay(...) | spectrum(...) | dominant(...) | ...} (module text).  None
     without a .tran card; SingularMatrixError and the circuit's state write-back exactly as simulateTRAN; exact_order=True
     runs the reference-order engine."""
     be = _backend(backend, exact_order, device, True, "measureTRAN")
