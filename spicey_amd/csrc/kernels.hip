@@ -54,6 +54,27 @@ __device__ __forceinline__ void gpu_wave_lockstep_keep(int nlanes, int nsteps, F
   __syncthreads();
 }
 
+// the same with a second body that EVERY thread of the workgroup runs before the closing barrier: the waves that have no
+// part in the steps run it at once — they would only wait —, the stepping wave behind its last step
+template <class F, class G>
+__device__ __forceinline__ void gpu_wave_lockstep_keep_then(int nlanes, int nsteps, F f, G g, bool prio = false) {
+  int tid = (int)threadIdx.x;
+  asm volatile("" : "+v"(tid));
+  if (tid < 64) {
+    if (prio) __builtin_amdgcn_s_setprio(SPICEY_PRIO_TOP);
+    double keep[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int s = 0; s < nsteps; s++) {
+      if (tid < nlanes) f(tid, s, keep);
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+    }
+  }
+  __builtin_amdgcn_sched_barrier(0);  // (g's loads stay behind the steps: their registers are the steps' until then)
+  g(tid);
+  if (prio) __builtin_amdgcn_s_setprio(0);  // (the stepping wave keeps its priority through g: it is still the last to arrive)
+  __syncthreads();
+}
+
 struct GpuExec {
   // (fronts_exec.h: a root front stays in LDS between the sweeps — group kernel only: in the one-workgroup kernels with an LDS
   // workspace the same code sends this hipcc into "Illegal instruction detected: Operand has incorrect register class")
@@ -454,6 +475,16 @@ struct GpuExecV2 {
     gpu_wave_lockstep_keep(nlanes, nsteps, f, PRIO);
     if (prof && threadIdx.x == 0) { t_last = clock64(); atomicAdd(&prof[SPICEY_PH_U0 + 31], (unsigned long long)(t_last - t0)); }
   }
+  // early-prefetch builds (tran_v2_run.h): the waves beside the top's are idle for its whole length — what `g` fetches
+  // there costs no issue slot that anything else wants, and no register beside the top's
+  static constexpr bool idle_waves = true;
+  template <class F, class G>
+  __device__ __forceinline__ void wave_lockstep_keep_then(int nlanes, int nsteps, F f, G g) {
+    long long t0 = 0;
+    if (prof && threadIdx.x == 0) { t0 = clock64(); if (t_last) atomicAdd(&prof[7], (unsigned long long)(t0 - t_last)); }
+    gpu_wave_lockstep_keep_then(nlanes, nsteps, f, g, PRIO);
+    if (prof && threadIdx.x == 0) { t_last = clock64(); atomicAdd(&prof[SPICEY_PH_U0 + 31], (unsigned long long)(t_last - t0)); }
+  }
   template <class L, class F>
   __device__ __forceinline__ void tail_phase(int tag, int nlev, L load, F f) {
     long long t0 = 0;
@@ -492,7 +523,10 @@ struct GpuExecV2 {
   }
 };
 
-// PT: 1 = the phases take their run-invariant arguments from the phase table in LDS (tran_exec.h), 0 = by scalar loads
+// PT, bit 0: 1 = the phases take their run-invariant arguments from the phase table in LDS (tran_exec.h), 0 = by scalar loads
+// PT, bit 1 (SPICEY_KERNEL_EP): the early-prefetch form of the time loop (tran_v2_run.h: EP).  One more value of this
+// parameter and not a parameter of its own, so that every kernel without it keeps its name — profiles and tools know them by it.
+#define SPICEY_KERNEL_EP 2
 template <int K, int RMAX, int NSV, int NEL, int MAXT, int MINW, bool HYB = false, int PT = 0>
 __global__ void __launch_bounds__(MAXT, MINW) spicey_tran_kernel_v2(const SpiceyProg *__restrict__ Pg, const SpiceyResident *__restrict__ Qg,
                                                                     const SpiceyRun *__restrict__ Rg) {
@@ -542,7 +576,7 @@ __global__ void __launch_bounds__(MAXT, MINW) spicey_tran_kernel_v2(const Spicey
     // start stamps wait in their own slots (not in registers: nothing may stay live around the whole run)
     if (threadIdx.x == 0) { lprof[5] = (unsigned long long)clock64(); lprof[6] = (unsigned long long)wall_clock64(); }
   }
-  spicey_tran_run_v2<K, RMAX, NSV, NEL, HYB, PT>(ex, P, Q, R, c, wg);
+  spicey_tran_run_v2<K, RMAX, NSV, NEL, HYB, PT & 1, (PT & SPICEY_KERNEL_EP) != 0>(ex, P, Q, R, c, wg);
   if (R.prof) {
     __syncthreads();
     if (threadIdx.x == 0) {  // slots 5/6: whole-run shader cycles and 100 MHz wall ticks -> effective clock
@@ -554,9 +588,9 @@ __global__ void __launch_bounds__(MAXT, MINW) spicey_tran_kernel_v2(const Spicey
   }
 }
 
-template <int K, int RMAX, int NSV, int NEL, int MAXT, int MINW, bool HYB = false, int PT = 0>
+template <int K, int RMAX, int NSV, int NEL, int MAXT, int MINW, bool HYB = false, int PT = 0, bool EP = false>
 hipError_t launch_v2_t(const SpiceyProg *P, const SpiceyResident *Q, const SpiceyRun *R, int grid, int threads, size_t lds, hipStream_t st) {
-  auto kern = spicey_tran_kernel_v2<K, RMAX, NSV, NEL, MAXT, MINW, HYB, PT>;
+  auto kern = spicey_tran_kernel_v2<K, RMAX, NSV, NEL, MAXT, MINW, HYB, PT | (EP ? SPICEY_KERNEL_EP : 0)>;
   if (const hipError_t e = spicey_allow_dyn_lds(kern, lds); e != hipSuccess) return e;
   hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, st, P, Q, R);
   return hipGetLastError();
@@ -631,10 +665,11 @@ hipError_t spicey_launch_tran(const SpiceyProg &P, const SpiceyRun &R, int K, bo
 }
 
 // one launcher per entry of SPICEY_V2_SHAPES (launch_plan.h)
-template <int I, int PT = 0>
+template <int I, int PT = 0, bool EP = false>
 static hipError_t launch_v2_shape(const SpiceyProg *P, const SpiceyResident *Q, const SpiceyRun *R, int grid, int threads, size_t lds, hipStream_t st) {
   constexpr SpiceyV2Shape s = SPICEY_V2_SHAPES[I];
-  return launch_v2_t<1, s.rmax, s.nsv, s.nel, s.threads, s.minw, s.hybrid, PT>(P, Q, R, grid, threads, lds, st);
+  static_assert(!EP || s.early, "an early-prefetch kernel is built for the shapes that say so");
+  return launch_v2_t<1, s.rmax, s.nsv, s.nel, s.threads, s.minw, s.hybrid, PT, EP>(P, Q, R, grid, threads, lds, st);
 }
 static decltype(&launch_v2_shape<0>) const launch_v2_by_shape[] = {launch_v2_shape<0>, launch_v2_shape<1>, launch_v2_shape<2>, launch_v2_shape<3>,
                                                                     launch_v2_shape<4>, launch_v2_shape<5>, launch_v2_shape<6>};
@@ -644,11 +679,20 @@ static decltype(&launch_v2_shape<0>) const launch_v2_pt_by_shape[] = {launch_v2_
                                                                        launch_v2_shape<4, 1>, launch_v2_shape<5, 1>, launch_v2_shape<6, 1>};
 static_assert(sizeof(launch_v2_pt_by_shape) / sizeof(launch_v2_pt_by_shape[0]) == SPICEY_V2_NSHAPES, "one entry per v2 build");
 
+// the early-prefetch builds ([PT]; null: that shape has none — SPICEY_V2_SHAPES order, SpiceyV2Shape::early)
+static decltype(&launch_v2_shape<0>) const launch_v2_early_by_shape[2][SPICEY_V2_NSHAPES] = {
+    {nullptr, launch_v2_shape<1, 0, true>, nullptr, nullptr, nullptr, nullptr, nullptr},
+    {nullptr, launch_v2_shape<1, 1, true>, nullptr, nullptr, nullptr, nullptr, nullptr}};
+
 hipError_t spicey_launch_tran_v2(const SpiceyProg &Ph, const SpiceyResident &Qh, const SpiceyProg *P, const SpiceyResident *Q, const SpiceyRun *R, int K, int grid,
-                                 int threads, hipStream_t st, bool packed, bool phase_table) {
+                                 int threads, hipStream_t st, bool packed, bool phase_table, bool early) {
   const int shape = K == 1 ? spicey_v2_shape(threads, packed, Ph.hybrid != 0, packed && Ph.fresh_fill != 0) : -1;  // (a fresh-fill program runs on the build that decodes its flags: spicey_plan makes one for the packed geometry only)
   if (shape < 0) return hipErrorInvalidValue;
   // the table sits in the tail area behind the tridiagonal top's index table: only where it fits there (tran_exec.h)
   const bool pt = phase_table && launch_v2_pt_by_shape[shape] != nullptr && spicey_pt_fits(Ph.pcr_n, Ph.pcr_level, Qh.tail_n);
+  if (early) {  // (the run's SpiceyRun carries the parameter record: only the build that reads it may run)
+    if (!SPICEY_V2_SHAPES[shape].early || launch_v2_early_by_shape[pt][shape] == nullptr) return hipErrorInvalidValue;
+    return launch_v2_early_by_shape[pt][shape](P, Q, R, grid, threads, spicey_lds_bytes(Ph, K, true, Qh.tail_n), st);
+  }
   return (pt ? launch_v2_pt_by_shape : launch_v2_by_shape)[shape](P, Q, R, grid, threads, spicey_lds_bytes(Ph, K, true, Qh.tail_n), st);
 }

@@ -46,7 +46,7 @@ static const SpiceyV2Shape &v2_build(int threads, bool packed = false, bool hybr
 SpiceyKnobs spicey_read_knobs() {
   const char *ms = getenv("SPICEY_GROUP_TIMEOUT_MS");
   return {getenv("SPICEY_NO_HYBRID") != nullptr, getenv("SPICEY_FRONT_RIGHT_LOOKING") != nullptr, getenv("SPICEY_TEST_FORCE_GROUP_ABORT") != nullptr,
-          ms ? atoi(ms) : 0, getenv("SPICEY_NO_PHASE_TABLE") != nullptr, getenv("SPICEY_NO_FRESH_FILL") != nullptr, getenv("SPICEY_FRESH_FILL_LINEAR") != nullptr};
+          ms ? atoi(ms) : 0, getenv("SPICEY_NO_PHASE_TABLE") != nullptr, getenv("SPICEY_NO_FRESH_FILL") != nullptr, getenv("SPICEY_FRESH_FILL_LINEAR") != nullptr, getenv("SPICEY_NO_EARLY_PREFETCH") != nullptr};
 }
 
 static int pick_threads(const HostProgram &hp, bool v2) {
@@ -288,6 +288,9 @@ int32_t spicey_plan(const SpiceyDesc *desc, const SpiceyOptions &opt, const Spic
     if (opt.debug & 1) max_tail = 0;  // diagnostics: disable the tail merge
     spicey_build_resident(hp, plan.T, v2_build(plan.T, plan.packed, P.hybrid != 0).rmax, hres, max_tail, !((opt.debug >> 6) & 1));  // diagnostics: bit 6 = no row records
     plan.lds_bytes = spicey_lds_bytes(P, K, true, hres.tail_n);
+    // (the build the launch will pick — spicey_launch_tran_v2 — and whether it has an early-prefetch form)
+    const int shape = K == 1 ? spicey_v2_shape(plan.T, plan.packed, hp.hdr.hybrid != 0, plan.packed && hp.hdr.fresh_fill != 0) : -1;
+    plan.early = shape >= 0 && SPICEY_V2_SHAPES[shape].early && !knobs.no_early_prefetch;
   }
   if (!plan.lds) {
     // group mode: several CUs per instance when the batch leaves CUs idle and the circuit is large enough for the
@@ -318,6 +321,13 @@ int32_t spicey_plan(const SpiceyDesc *desc, const SpiceyOptions &opt, const Spic
     plan.G = G;
   }
   return SPICEY_OK;
+}
+
+size_t spicey_zpar_doubles(const LaunchPlan &plan, const HostProgram &hp) {
+  if (!plan.early || plan.interp != 2) return 0;
+  const int shape = spicey_v2_shape(plan.T, plan.packed, hp.hdr.hybrid != 0, plan.packed && hp.hdr.fresh_fill != 0);
+  if (shape < 0) return 0;
+  return (size_t)plan.n_inst * (size_t)SPICEY_V2_SHAPES[shape].nel * (size_t)plan.T * 5;
 }
 
 void fill_info(const LaunchPlan &plan, const HostProgram &hp, const HostResident &hres, const SpiceyOptions &opt, SpiceyInfo *info) {

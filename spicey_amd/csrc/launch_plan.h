@@ -43,9 +43,12 @@ struct SpiceyV2Shape {
   bool packed, hybrid;
   int threads, rmax, nsv, nel, minw;  // workgroup size (launch bound), slots, re-stamped entries and elements per thread, waves per SIMD
   bool fresh = false;
+  bool early = false;  // the shape also has early-prefetch kernels (tran_v2_run.h: EP), which a handle takes unless SPICEY_NO_EARLY_PREFETCH is set
 };
+// `early`: Z's element parameters come from one record per thread (SpiceyRun::zpar) and are fetched, with the next source
+// value, at the tail of the last factor phase.  The fresh packed build has it; the other builds were left as they are.
 // (spicey_launch_tran_v2 instantiates one kernel per entry; each kind in ascending threads)
-constexpr SpiceyV2Shape SPICEY_V2_SHAPES[] = {{true, false, 512, 4, 6, 2, 4},    {true, false, 512, 4, 2, 2, 4, true},
+constexpr SpiceyV2Shape SPICEY_V2_SHAPES[] = {{true, false, 512, 4, 6, 2, 4},    {true, false, 512, 4, 2, 2, 4, true, true},
                                               {false, true, 512, 16, 8, 2, 2},   {false, true, 1024, 4, 4, 1, 4},
                                               {false, false, 256, SPICEY_V2_RMAX256, 12, 4, 1},
                                               {false, false, 512, 16, 8, 2, 2},  {false, false, 1024, 8, 4, 1, 4}};
@@ -62,6 +65,7 @@ struct SpiceyKnobs {
   bool no_phase_table = false;       // SPICEY_NO_PHASE_TABLE: the 16-bit interpreter fetches its phase arguments by scalar loads in every phase (tran_exec.h)
   bool no_fresh_fill = false;        // SPICEY_NO_FRESH_FILL: the packed geometry keeps the default program and the 6-entry build (the in-library A/B switch)
   bool fresh_fill_linear = false;    // SPICEY_FRESH_FILL_LINEAR: tests, a linear circuit (factor reuse) takes the fresh build too
+  bool no_early_prefetch = false;    // SPICEY_NO_EARLY_PREFETCH: a shape with early-prefetch kernels keeps its plain build and the handle no parameter record (the in-library A/B switch)
 };
 SpiceyKnobs spicey_read_knobs();
 
@@ -112,6 +116,7 @@ struct LaunchPlan {
   int G = 1;             // workgroups per instance group (group mode: global workspace only)
   bool packed = false;   // two 512-thread workgroups per CU
   bool fresh = false;    // packed: hp is a fresh-fill program and runs on the fresh build (SPICEY_V2_SHAPES)
+  bool early = false;    // the run takes the shape's early-prefetch kernel: the handle owns a parameter record (spicey_zpar_doubles)
   bool lds = true;       // workspace in LDS (else global memory)
   size_t lds_bytes = 0;
   int64_t algo_bytes = 0;
@@ -122,4 +127,7 @@ struct LaunchPlan {
 // 16-bit interpreter, hres).
 int32_t spicey_plan(const SpiceyDesc *desc, const SpiceyOptions &opt, const SpiceyKnobs &knobs, const PlanDevice &dev, HostProgram &hp,
                     HostResident &hres, LaunchPlan &plan, std::string &err);
+// doubles of the parameter record SpiceyRun::zpar of a planned handle: five per resident item, NEL x T items per instance
+// (0: the plan runs a build without it)
+size_t spicey_zpar_doubles(const LaunchPlan &plan, const HostProgram &hp);
 void fill_info(const LaunchPlan &plan, const HostProgram &hp, const HostResident &hres, const SpiceyOptions &opt, SpiceyInfo *info);

@@ -304,4 +304,8 @@ struct SpiceyRun {
   // io (appended last so that the offsets of the fields above do not move): distance in doubles between the source tables
   // of consecutive instances — 0 = ONE table [steps+1][nV] shared by every instance, (steps+1) nV = [n_inst][steps+1][nV]
   int64_t src_stride;
+  // Z's element parameters as one record per resident item (early-prefetch builds, TranPhases2::zpar_fill): five doubles
+  // {1/R, C/dt, Is, 1/(N VT), Is/(N VT)} of item (thread t, j) at ((inst * NEL + j) * T + t) * 5, written by the prologue
+  // of every launch, 0.0 where the item does not exist.  Null: no record — the build that reads gstat / D_is / dpar runs.
+  double *zpar;
 };

@@ -95,6 +95,7 @@ struct SpiceyHandle {
   int64_t stale_polls = 0;  // group mode: waits that only the read-modify-write poll saw satisfied (spicey_group_stale_polls)
   bool gated = false;     // this handle is counted in its device's group-mode handles (DeviceGate)
   DevBuf<double> d_gstat, d_statv, d_rcoef, d_gW, d_dpar;
+  DevBuf<double> d_zpar;  // early-prefetch builds: Z's parameter record (SpiceyRun::zpar), written by every launch's prologue; else null
   DevBuf<int32_t> d_status; DevBuf<unsigned long long> d_solves, d_prof;
   hipStream_t last_stream = nullptr;
   double last_pass_ms[N_PASS] = {};  // the reduction passes of the last spicey_run_measure* (0: the pass did not run)
@@ -280,6 +281,7 @@ static int32_t allocate(SpiceyHandle *h, const SpiceyDesc *desc) {
   HIPCHK(h, dev_upload(h->d_statv, ni * P.nLU));
   HIPCHK(h, dev_upload(h->d_rcoef, ni * (size_t)(P.nRhsIdx + 1)));
   HIPCHK(h, dev_upload(h->d_dpar, ni * (size_t)P.nD * 2));
+  if (const size_t nz = spicey_zpar_doubles(pl, h->hp)) HIPCHK(h, dev_upload(h->d_zpar, nz));
   if (!pl.lds) HIPCHK(h, dev_upload(h->d_gW, (size_t)pl.grid * spicey_gw_doubles_per_wg(P, pl.K)));
   if (pl.G > 1) {
     HIPCHK(h, dev_upload(h->d_gsync, (size_t)pl.grid * SPICEY_GRP_SYNC_WORDS));
@@ -351,7 +353,7 @@ static int32_t enqueue_kernel(SpiceyHandle *h, const SpiceyRun &R, hipStream_t s
   if (h->plan.interp == 3) {
     HIPCHK(h, spicey_launch_exact(h->d_xprog, h->d_Rstruct, h->plan.grid, h->plan.T, h->plan.lds ? h->plan.lds_bytes : 0, st));
   } else if (h->plan.interp == 2) {
-    HIPCHK(h, spicey_launch_tran_v2(h->dprog, h->dres, h->d_Pstruct, h->d_Qstruct, h->d_Rstruct, h->plan.K, h->plan.grid, h->plan.T, st, h->plan.packed, !h->knobs.no_phase_table));
+    HIPCHK(h, spicey_launch_tran_v2(h->dprog, h->dres, h->d_Pstruct, h->d_Qstruct, h->d_Rstruct, h->plan.K, h->plan.grid, h->plan.T, st, h->plan.packed, !h->knobs.no_phase_table, h->d_zpar != nullptr));
   } else if (group) {
     HIPCHK(h, spicey_launch_tran_grp(h->dprog, R, h->plan.K, h->plan.grid, h->plan.T, st));
   } else {
@@ -425,6 +427,7 @@ extern "C" int32_t spicey_run_device_src(SpiceyHandle *h, int64_t steps, double 
   R.D_is = h->d_Dis; R.D_n = h->d_Dn;
   R.C_vprev = h->state.Cv; R.L_iprev = h->state.Li; R.D_vdprev = h->state.Dv; R.S_ison = h->state.Son;
   R.gstat = h->d_gstat; R.statv = h->d_statv; R.rcoef = h->d_rcoef; R.gW = pl.interp == 3 ? h->d_xws : h->d_gW; R.dpar = h->d_dpar;
+  R.zpar = h->d_zpar;
   R.src = d_src_table; R.out_v = d_out_v; R.out_i = d_out_i; R.iters = d_iters;
   R.src_stride = src_per_inst ? (int64_t)(steps + 1) * P.nV : 0;
   R.status = h->d_status; R.solves = h->d_solves; R.prof = h->d_prof;

@@ -30,9 +30,13 @@ enum {
   SPICEY_PT_STEPS = 18, SPICEY_PT_SRC = 20, SPICEY_PT_SRC_STRIDE = 22, SPICEY_PT_OUT_V = 24, SPICEY_PT_OUT_I = 26, SPICEY_PT_GSTAT = 28,
   SPICEY_PT_DPAR = 30, SPICEY_PT_D_IS = 32, SPICEY_PT_C_VPREV = 34, SPICEY_PT_D_VDPREV = 36, SPICEY_PT_ITERS = 38, SPICEY_PT_LIN_VD = 40,
   SPICEY_PT_LIN_ERR = 42,
-  SPICEY_PT_USED = 44
+  SPICEY_PT_USED = 44,
+  // early-prefetch builds only (spicey_pt_build's `ep`): SpiceyRun::zpar in two of the four words left of the block; every
+  // other build writes and reads the block up to SPICEY_PT_USED, as before
+  SPICEY_PT_ZPAR = 44,
+  SPICEY_PT_USED_EP = 46
 };
-static_assert(SPICEY_PT_USED <= SPICEY_PT_RUN && SPICEY_PT_RUN <= 64 && SPICEY_PT_RUN % 4 == 0, "run-wide block of the phase table: at most one word per lane of a wave");
+static_assert(SPICEY_PT_USED <= SPICEY_PT_ZPAR && SPICEY_PT_USED_EP <= SPICEY_PT_RUN && SPICEY_PT_RUN <= 64 && SPICEY_PT_RUN % 4 == 0, "run-wide block of the phase table: at most one word per lane of a wave");
 SPICEY_HD int spicey_pt_base_words(int pcr_n) { return 1024 + ((pcr_n * 2 + 3) & ~3); }
 // rows of the table of a program with its top at level `pcr_level`, and whether they fit behind the top's index table
 SPICEY_HD int spicey_pt_words(int pcr_level) { return SPICEY_PT_RUN + 16 * pcr_level; }
@@ -119,7 +123,7 @@ struct SpiceyPtWord {
 #define SPICEY_PT_P64(f) {0, (uint16_t)offsetof(SpiceyProg, f)}, {0, (uint16_t)(offsetof(SpiceyProg, f) + 4)}
 #define SPICEY_PT_R64(f) {1, (uint16_t)offsetof(SpiceyRun, f)}, {1, (uint16_t)(offsetof(SpiceyRun, f) + 4)}
 template <int K>
-SPICEY_HD void spicey_pt_build(const SpiceyProg &P, const SpiceyResident &Q, const SpiceyRun &R, const WgCtx<K> &c, int tid, int T) {
+SPICEY_HD void spicey_pt_build(const SpiceyProg &P, const SpiceyResident &Q, const SpiceyRun &R, const WgCtx<K> &c, int tid, int T, bool ep = false) {
   static constexpr SpiceyPtWord words[SPICEY_PT_USED] = {
       SPICEY_PT_P32(xoff), SPICEY_PT_P32(nRestore), SPICEY_PT_P32(nDynEnt), SPICEY_PT_P32(nGstat), SPICEY_PT_P32(nR), SPICEY_PT_P32(nC),
       SPICEY_PT_P32(nL), SPICEY_PT_P32(nV), SPICEY_PT_P64(ovf16), SPICEY_PT_P64(rec16), SPICEY_PT_P64(fus16), SPICEY_PT_P32(nS),
@@ -132,6 +136,11 @@ SPICEY_HD void spicey_pt_build(const SpiceyProg &P, const SpiceyResident &Q, con
     const char *src = (w.from_run ? (const char *)&R : (const char *)&P) + w.off;
     uint32_t v;
     __builtin_memcpy(&v, src, 4);
+    pt[tid] = v;
+  }
+  if (ep && tid >= SPICEY_PT_ZPAR && tid < SPICEY_PT_USED_EP) {  // (`ep`: a constant of the build)
+    uint32_t v;
+    __builtin_memcpy(&v, (const char *)&R + offsetof(SpiceyRun, zpar) + (size_t)(tid - SPICEY_PT_ZPAR) * 4, 4);
     pt[tid] = v;
   }
   const int L = P.pcr_level, kb = 2 * P.nLevels - L;  // rows: factor phases [0, L), then backward phases [kb, kb + L)
@@ -163,4 +172,5 @@ SPICEY_HD void spicey_pt_args(const uint32_t *pt, int tid, SpiceyProg &P, Spicey
   R.iters = a.template ptr<int32_t>(SPICEY_PT_ITERS);
   R.lin_vd = a.template ptr<double>(SPICEY_PT_LIN_VD);
   R.lin_err = a.template ptr<unsigned long long>(SPICEY_PT_LIN_ERR);
+  R.zpar = a.template ptr<double>(SPICEY_PT_ZPAR);  // (read by the early-prefetch builds only, which write the word)
 }

@@ -51,6 +51,9 @@ struct ResRegs {
   // fetched at the end of the last backward phase so that the L2 round trip (~1900 cycles measured) overlaps that
   // phase's barrier; live only from there to Z (K == 1 geometries)
   double pf[NEL][5];
+  // early-prefetch builds: the next step's value of source tid, fetched with pf between the factor and the backward phases and
+  // parked in LDS at the tail of the last backward phase (TranPhases2::z_early / z_src_park); live only between the two
+  double srcn;
   // fresh build: this thread's first streamed record of factor phase 0 (a 32-byte row record), fetched under phase B —
   // TranPhases2::u0_fetch writes all eight words on every path of B, spicey_uk_phase consumes them in phase 0 and clears
   // them at the end of every factor phase, so they are live from B to U_0 only.  Untouched in every other build.

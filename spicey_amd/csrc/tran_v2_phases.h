@@ -18,8 +18,13 @@
 // HYB: the hybrid workspace layout (program.h, SpiceyProg::hybrid) — entry ids below hyb_g0 and in [nRestore, nRestore + hyb_g2)
 // are leaf-owned and live in the global array c.G, all others in LDS at id - hyb_g0 (- hyb_g2 above nRestore); the
 // right-hand side starts at LDS index P.xoff; c.u / c.gd point to global memory.
-template <int K, int RMAX, int NSV, int NEL, bool HYB = false>
+// EP: the early-prefetch build (K = 1, LDS workspace) — Z's element parameters come from the per-thread record SpiceyRun::zpar
+// and are fetched, with the next step's source value, between the factor and the backward phases instead of at the tail of
+// the last backward one; B then fetches and parks nothing (spicey_tran_run_v2 places the calls: see there for where).  A compile-time property of a build, like
+// FRESH: a kernel that holds both forms of B and Z does not fit the 128 registers of the packed builds.
+template <int K, int RMAX, int NSV, int NEL, bool HYB = false, bool EP = false>
 struct TranPhases2 {
+  static_assert(!EP || (K == 1 && !HYB), "the early prefetch is built for one instance per workgroup on the LDS workspace");
   const SpiceyProg &P;
   const SpiceyRun &R;
   WgCtx<K> &c;
@@ -227,12 +232,12 @@ struct TranPhases2 {
     }
   }
   SPICEY_HD void b_phase(int tid, int64_t step, Regs &rr, bool reuse) const {
-    double sn = K == 1 ? z_src_fetch(tid, step, (size_t)c.inst[0]) : 0.0;
+    double sn = (K == 1 && !EP) ? z_src_fetch(tid, step, (size_t)c.inst[0]) : 0.0;  // (EP: fetched by z_early, parked by the last backward phase)
     if (FRESH) u0_fetch(tid, rr);
     SPICEY_SCHED_FENCE;
     b_stamp(tid, rr, reuse);
     SPICEY_SCHED_FENCE;
-    if (K == 1) z_src_park(tid, sn);
+    if (K == 1 && !EP) z_src_park(tid, sn);
   }
   // ---- batched forms of the beyond-resident-capacity loops (HYB builds, K = 1) -------------------------------------------
   // Hybrid workspace: circuits of several thousand unknowns on 512 threads — most entries lie beyond the resident slots, and
@@ -550,6 +555,53 @@ struct TranPhases2 {
       rr.pf[j][4] = hd ? dp[1] : 0.0;
     }
   }
+  // ---- early-prefetch builds: the record SpiceyRun::zpar ---------------------------------------------------------------
+  // Prologue, after p0_gstat's barrier: every thread copies the parameters of its own resident items — exactly the doubles
+  // z_prefetch reads — into its record; it alone reads them back, so nothing but program order stands between the two.
+  // Rebuilt by every launch: a second run on the handle, or new element values, see fresh parameters.
+  SPICEY_HD void zpar_fill(int tid) const {
+    const size_t in = (size_t)c.inst[0];
+    const double *g = R.gstat + in * P.nGstat;
+    for (int j = 0; j < NEL; j++) {
+      const int i = tid + j * T;
+      double *zp = R.zpar + ((in * NEL + (size_t)j) * (size_t)T + (size_t)tid) * 5;
+      const bool hd = i < P.nD;
+      const double *dp = R.dpar + (in * P.nD + (hd ? i : 0)) * 2;
+      zp[0] = i < P.nR ? g[i] : 0.0;
+      zp[1] = i < P.nC ? g[P.nR + i] : 0.0;
+      zp[2] = hd ? R.D_is[in * P.nD + i] : 0.0;
+      zp[3] = hd ? dp[0] : 0.0;
+      zp[4] = hd ? dp[1] : 0.0;
+    }
+  }
+  // one wave-uniform base per j and one 32-bit lane offset: 40 contiguous bytes per item, no bound test
+  SPICEY_HD void z_prefetch_rec(int tid, Regs &rr) const {
+    const uint32_t ob = (uint32_t)tid * 40u;  // (a BYTE offset of 32 bits: base in scalars + this + a constant is one addressing mode)
+    for (int j = 0; j < NEL; j++) {
+      const char *base = (const char *)(R.zpar + ((size_t)c.inst[0] * NEL + (size_t)j) * (size_t)T * 5);
+      const double *zp = (const double *)(base + ob);
+      for (int q = 0; q < 5; q++) rr.pf[j][q] = (SPICEY_EXP & 8) ? 0.0 : zp[q];
+    }
+  }
+  // the early fetch: Z's parameters and the next step's source value, with the backward phases to arrive in
+  SPICEY_HD void z_early(int tid, int64_t step, Regs &rr) const {
+    z_prefetch_rec(tid, rr);
+    rr.srcn = z_src_fetch(tid, step, (size_t)c.inst[0]);
+  }
+  // the same registers left UNDEFINED where nothing will read them before they are written again (Z then fetches for itself): a definition on this path for the compiler — so that the values are not
+  // live around the time loop — that costs no instruction.  The host's executors get NaN.
+  SPICEY_HD void z_early_none(Regs &rr) const {
+    for (int j = 0; j < NEL; j++)
+      for (int q = 0; q < 5; q++) spicey_undef(rr.pf[j][q]);
+    spicey_undef(rr.srcn);
+  }
+  static SPICEY_HD void spicey_undef(double &x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "=v"(x));
+#else
+    x = NAN;
+#endif
+  }
   // next step's source values: issued before the tasks of the last backward phase, parked in LDS after them
   SPICEY_HD double z_src_fetch(int tid, int64_t step, size_t in) const {
     return (tid < P.nV && step != R.steps) ? R.src[in * R.src_stride + (size_t)(step + 1) * P.nV + tid] : 0.0;
@@ -582,7 +634,10 @@ struct TranPhases2 {
       SPICEY_MARK(c, 15);
       // Element parameters of the resident items come from L2: all their loads are issued together (one round
       // trip per step instead of one per element section), normally already during the last backward phase.
-      if (!(K == 1 && prefetched)) z_prefetch(tid, step, k, rr);
+      if (!(K == 1 && prefetched)) {
+        if (EP) z_prefetch_rec(tid, rr);
+        else z_prefetch(tid, step, k, rr);
+      }
       double pR[NEL], pC[NEL], pIs[NEL], pD0[NEL], pD1[NEL];
       for (int j = 0; j < NEL; j++) { pR[j] = rr.pf[j][0]; pC[j] = rr.pf[j][1]; pIs[j] = rr.pf[j][2]; pD0[j] = rr.pf[j][3]; pD1[j] = rr.pf[j][4]; }
       double srcn = (K == 1 && prefetched) ? 0.0 : z_src_fetch(tid, step, in);

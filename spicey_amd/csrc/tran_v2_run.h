@@ -115,10 +115,27 @@ __device__ __forceinline__ void spicey_pcr_all(const WgCtx<K> &c, double *buf, c
 // structs through `ex.fresh()` / spicey_fresh(): on the GPU they live in global memory and `fresh` makes their address
 // opaque for this phase, so the fields it needs are fetched by scalar loads inside it (scalar cache).  Either way the
 // values are dead at the phase's barrier; only a handful of loop-control scalars stay live around the loop.
-template <int K, int RMAX, int NSV, int NEL, bool HYB = false, int PT = -1, class Exec>
+// EP (the early-prefetch build, TranPhases2): every thread issues the loads of Z's parameter record, and thread(s) tid < nV
+// that of the next step's source value, between the factor and the backward phases instead of at the tail of the last
+// backward one; the last backward phase parks the source value in LDS, Z reads registers that arrived long ago, and B
+// holds no global load of its own but phase 0's record.  R.zpar is not null in such a build.  Where the fetch stands:
+//   - an executor with `idle_waves` (SpiceyHasIdleWaves: the GPU's) runs it in the phase of the tridiagonal top, through
+//     wave_lockstep_keep_then: the waves that have no part in the top issue it at once and wait at the barrier, the top's
+//     wave issues it behind the top — so the 22 registers are never live beside the top's own ~50.  (At the tail of the
+//     last factor phase they are, and the packed build then spills 20 of them.  Moving the top wave's share to the head
+//     of the next backward phase was measured too: that phase grew by what the top's had, ~500 cycles, and the headline
+//     fell below the parent's.)  A program without a top gets a phase of its own for it.
+//   - any other executor peels the last factor phase below the top — or the last of all — and fetches at its tail.
+// Either way the fetch is unconditional code on every path through the iteration, so the registers are not live around
+// the time loop.
+template <class E, class = void>
+struct SpiceyHasIdleWaves { static constexpr bool value = false; };
+template <class E>
+struct SpiceyHasIdleWaves<E, decltype((void)E::idle_waves)> { static constexpr bool value = true; };
+template <int K, int RMAX, int NSV, int NEL, bool HYB = false, int PT = -1, bool EP = false, class Exec>
 SPICEY_HD void spicey_tran_run_v2(Exec &ex, const SpiceyProg &P, const SpiceyResident &Q, const SpiceyRun &R, WgCtx<K> &c, int wg) {
   const int T = ex.threads();
-  typedef TranPhases2<K, RMAX, NSV, NEL, HYB> Ph2;
+  typedef TranPhases2<K, RMAX, NSV, NEL, HYB, EP> Ph2;
   uint32_t brem, zrem;
   {
     Ph2 p2{P, R, c, T, 0u, 0u};
@@ -129,7 +146,7 @@ SPICEY_HD void spicey_tran_run_v2(Exec &ex, const SpiceyProg &P, const SpiceyRes
   // the phase table: tridiagonal-top builds whose rows fit behind the top's index table (wave-uniform, fixed for the run)
   static_assert(PT <= 0 || K == 1, "the phase table is built for one instance per workgroup");
   const bool pt_run = PT >= 0 ? PT == 1 : (K == 1 && spicey_pt_runtime_choice(P, Q));
-  if (pt_run) ex.phase(SPICEY_PH_PRO, [&](int tid) { spicey_pt_build<K>(P, Q, R, c, tid, T); });  // (the structs where they live: see there)
+  if (pt_run) ex.phase(SPICEY_PH_PRO, [&](int tid) { spicey_pt_build<K>(P, Q, R, c, tid, T, EP); });  // (the structs where they live: see there)
   ex.phase(SPICEY_PH_PRO, [&](int tid) {
     const SpiceyProg Pf = ex.fresh(P); const SpiceyResident Qf = ex.fresh(Q); const SpiceyRun Rf = ex.fresh(R);
     TranPhases<K> ph{Pf, Rf, c, T};
@@ -149,7 +166,7 @@ SPICEY_HD void spicey_tran_run_v2(Exec &ex, const SpiceyProg &P, const SpiceyRes
     }
   });
   ex.phase(SPICEY_PH_PRO, [&](int tid) { const SpiceyProg Pf = ex.fresh(P); const SpiceyRun Rf = ex.fresh(R); TranPhases<K> ph{Pf, Rf, c, T}; ph.p1_static(tid); });
-  ex.phase(SPICEY_PH_PRO, [&](int tid) { const SpiceyProg Pf = ex.fresh(P); const SpiceyRun Rf = ex.fresh(R); Ph2 p2{Pf, Rf, c, T, brem, zrem}; p2.a0_initial(tid, ex.template regs<Regs>(tid)); });
+  ex.phase(SPICEY_PH_PRO, [&](int tid) { const SpiceyProg Pf = ex.fresh(P); const SpiceyRun Rf = ex.fresh(R); Ph2 p2{Pf, Rf, c, T, brem, zrem}; p2.a0_initial(tid, ex.template regs<Regs>(tid)); if (EP) p2.zpar_fill(tid); });
   unsigned long long solves = 0;
   int32_t code = 0;
   int64_t err_step = 0;
@@ -180,7 +197,9 @@ SPICEY_HD void spicey_tran_run_v2(Exec &ex, const SpiceyProg &P, const SpiceyRes
   // with a tridiagonal top the factor phases end at its level and the backward phases resume below it
   const int u_end = pcr_n > 0 ? P.pcr_level : (tail_n > 0 ? tail_first : nL);
   const int k_begin = pcr_n > 0 ? 2 * nL - P.pcr_level : (tail_n > 0 ? tail_first + tail_n : nL);
-  top_pack |= (K == 1 && k_begin < 2 * nL) ? 1 << 16 : 0;  // bit 16 = z_pre: Z's parameter fetch rides on the last backward phase
+  // bit 16 = z_pre: Z's parameter fetch rides on the last backward phase (EP: on the last factor phase, and the source value
+  // is parked by the last backward one — both must exist)
+  top_pack |= (K == 1 && k_begin < 2 * nL && (!EP || u_end > 0)) ? 1 << 16 : 0;
   // No diodes and no switches: the matrix of every step is the matrix of step 0 (dt is fixed within a run), so its
   // factors stay in W and later steps run the right-hand-side column only.  Same operands, same order: the results
   // are bit-identical to refactoring (SURVEY.md §8(d) "solve-only" rate; the reference itself never reuses).
@@ -225,7 +244,28 @@ SPICEY_HD void spicey_tran_run_v2(Exec &ex, const SpiceyProg &P, const SpiceyRes
         });
       for (int d = 0; d < dbg_empty; d++) ex.phase(SPICEY_PH_S, [&](int) {});  // diagnostics: cost of a bare phase
       // factor levels [0, u_end) | tail [u_end, k_begin) by one wave | backward levels [k_begin, 2 nL)
-      for (int p = 0; p < u_end; p++) {
+      constexpr bool IDLE = EP && SpiceyHasIdleWaves<Exec>::value;
+      const bool z_early = EP && ((tp >> 16) & 1) != 0;
+      const int kmerge = (tp >> 19) & 1;
+      // EP: Z's parameter record and the next source value of thread tid (whole waves arrive here)
+      auto early_fetch = [&](int tid) {
+        if (!z_early) {
+          Ph2 p2{P, R, c, T, brem, zrem};
+          p2.z_early_none(ex.template regs<Regs>(tid));
+        } else if (pt_bz) {
+          SpiceyProg Pt{};
+          SpiceyRun Rt{};
+          spicey_pt_args(ptw, tid, Pt, Rt);
+          Ph2 p2{Pt, Rt, c, T, brem, zrem, &P, &R};
+          p2.z_early(tid, step, ex.template regs<Regs>(tid));
+        } else {
+          const SpiceyProg Pf = ex.fresh(P);
+          const SpiceyRun Rf = ex.fresh(R);
+          Ph2 p2{Pf, Rf, c, T, brem, zrem};
+          p2.z_early(tid, step, ex.template regs<Regs>(tid));
+        }
+      };
+      for (int p = 0, u_gen = (z_early && !IDLE) ? u_end - 1 : u_end; p < u_gen; p++) {
         if (p < 64 ? !((active >> p) & 1) : P.ph_cnt[p] == 0) continue;
         if (HYB && p == 0) {
           // hybrid workspace: phase 0 eliminates the leaves, whose own entries are read from the global array (one L2 round
@@ -239,7 +279,19 @@ SPICEY_HD void spicey_tran_run_v2(Exec &ex, const SpiceyProg &P, const SpiceyRes
           spicey_uk_phase<K, RMAX, NSV, NEL, false>(P, Q, SpiceyPt{ptw, pt_on, p}, c, ex.template regs<Regs>(tid), tid, T, p, p < 64 ? ((smask >> p) & 1) != 0 : true, linear && step > 0);
         });
       }
-      const int kmerge = (tp >> 19) & 1;
+      // EP without idle waves: the last factor phase is peeled and fetches at its tail, after its tasks (it runs for its
+      // tail even where it has no task)
+      if (EP && !IDLE && z_early) {
+        const int p = u_end - 1;
+        const bool act = p < 64 ? ((active >> p) & 1) != 0 : P.ph_cnt[p] != 0;
+        ex.phase(SPICEY_PH_U0 + (p < 30 ? p : 30), [&](int tid) {
+          if (act) spicey_uk_phase<K, RMAX, NSV, NEL, false>(P, Q, SpiceyPt{ptw, pt_on, p}, c, ex.template regs<Regs>(tid), tid, T, p, p < 64 ? ((smask >> p) & 1) != 0 : true, linear && step > 0);
+          SPICEY_SCHED_FENCE;
+          early_fetch(tid);
+        });
+      } else if (EP && !IDLE) {
+        early_fetch(0);
+      }
       if (pcr_n > 0) {
         // (kmerge: wave 0 goes on with the first backward phase below the top — its records are resident in this wave's
         // slots, its rows need unknowns of the top only, and the LDS operations of one wave execute in order)
@@ -248,21 +300,28 @@ SPICEY_HD void spicey_tran_run_v2(Exec &ex, const SpiceyProg &P, const SpiceyRes
         };
 #if defined(__HIP_DEVICE_COMPILE__)
         if (pcr_S >= 1 && pcr_S <= 6) {
-          ex.wave_lockstep_keep(64, 1, [&](int lane, int, double *) {
+          auto top_all = [&](int lane, int, double *) {
             spicey_pcr_all<K>(c, (double *)c.tail, (const uint16_t *)(c.tail + 1024), pcr_n, pcr_S, lane);
             if (kmerge) {
               __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
               __builtin_amdgcn_wave_barrier();
               merged_k(lane);
             }
-          });
+          };
+          if constexpr (IDLE) ex.wave_lockstep_keep_then(64, 1, top_all, early_fetch);
+          else ex.wave_lockstep_keep(64, 1, top_all);
         } else
 #endif
-        ex.wave_lockstep_keep(64, pcr_S + 1 + kmerge, [&](int lane, int st, double *own) {
-          if (st <= pcr_S) spicey_pcr_stage<K>(c, (double *)c.tail, (const uint16_t *)(c.tail + 1024), pcr_n, pcr_S, lane, st, own);
-          else merged_k(lane);
-        });
-      } else if (k_begin > u_end) {
+        {
+          auto top_staged = [&](int lane, int st, double *own) {
+            if (st <= pcr_S) spicey_pcr_stage<K>(c, (double *)c.tail, (const uint16_t *)(c.tail + 1024), pcr_n, pcr_S, lane, st, own);
+            else merged_k(lane);
+          };
+          if constexpr (IDLE) ex.wave_lockstep_keep_then(64, pcr_S + 1 + kmerge, top_staged, early_fetch);
+          else ex.wave_lockstep_keep(64, pcr_S + 1 + kmerge, top_staged);
+        }
+      } else {
+        if (k_begin > u_end)
         // the record of level l + 1 is fetched (LDS) while level l executes: one round trip less on the serial chain
         ex.tail_phase(SPICEY_PH_U0 + 31, k_begin - u_end,
                       [&](int tid, int lvl, uint32_t *r) {
@@ -274,6 +333,9 @@ SPICEY_HD void spicey_tran_run_v2(Exec &ex, const SpiceyProg &P, const SpiceyRes
                         if (u_end + lvl < nL) spicey_exec_rec16<K, false, false, SpiceyShapeKind<RMAX, NSV, NEL>::fresh>(c, ovf, r[0], r[1], r[2], r[3], (linear && step > 0) ? (uint32_t)spicey_fresh(P).xoff : 0u);
                         else spicey_exec_rec16<K, true>(c, ovf, r[0], r[1], r[2], r[3]);
                       });
+        // (no top to ride on: a phase of its own — in this very branch, so that every path through the iteration visibly
+        // defines the registers)
+        if (IDLE) ex.phase(SPICEY_PH_S, early_fetch);
       }
       for (int p = k_begin + kmerge; p < 2 * nL - 1; p++) {
         const int l = 2 * nL - 1 - p;
@@ -288,7 +350,21 @@ SPICEY_HD void spicey_tran_run_v2(Exec &ex, const SpiceyProg &P, const SpiceyRes
         ex.phase(SPICEY_PH_K0, [&](int tid) {
           spicey_uk_phase<K, RMAX, NSV, NEL, true, HYB>(P, Q, SpiceyPt{ptw, pt_on, p - k_begin + u_end}, c, ex.template regs<Regs>(tid), tid, T, p, p < 64 ? ((smask >> p) & 1) != 0 : true);  // (level 0: the leaves)
           SPICEY_SCHED_FENCE;  // after the tasks, not among them: their registers are free by now
-          if (K == 1) {
+          if (K == 1 && EP) {  // (the source value that early_fetch left in a register: Z reads the slot, nothing before it does)
+            if (!z_early) return;
+            if (pt_bz) {
+              SpiceyProg Pt{};
+              SpiceyRun Rt{};
+              spicey_pt_args(ptw, tid, Pt, Rt);
+              Ph2 p2{Pt, Rt, c, T, brem, zrem, &P, &R};
+              p2.z_src_park(tid, ex.template regs<Regs>(tid).srcn);
+            } else {
+              const SpiceyProg Pf = ex.fresh(P);
+              const SpiceyRun Rf = ex.fresh(R);
+              Ph2 p2{Pf, Rf, c, T, brem, zrem};
+              p2.z_src_park(tid, ex.template regs<Regs>(tid).srcn);
+            }
+          } else if (K == 1) {
             if (pt_bz) {
               SpiceyProg Pt{};
               SpiceyRun Rt{};
@@ -303,7 +379,7 @@ SPICEY_HD void spicey_tran_run_v2(Exec &ex, const SpiceyProg &P, const SpiceyRes
             }
           }
         });
-      } else if (K == 1) {
+      } else if (K == 1 && !EP) {
         Ph2 p2{P, R, c, T, brem, zrem};
         p2.z_prefetch_none(ex.template regs<Regs>(0));
       }
