@@ -6,6 +6,7 @@
 #include <cstring>
 
 #include "fronts_exec_consts.h"
+#include "tran_pt_layout.h"
 
 // LDS scratch of the dense fronts: the widest panel (U rows 16 x ld, L rows (Mp - 16) x 17, the 16 x 16 block of L and
 // the reciprocal pivots), which also covers the backward solve's vectors
@@ -46,7 +47,7 @@ static const SpiceyV2Shape &v2_build(int threads, bool packed = false, bool hybr
 SpiceyKnobs spicey_read_knobs() {
   const char *ms = getenv("SPICEY_GROUP_TIMEOUT_MS");
   return {getenv("SPICEY_NO_HYBRID") != nullptr, getenv("SPICEY_FRONT_RIGHT_LOOKING") != nullptr, getenv("SPICEY_TEST_FORCE_GROUP_ABORT") != nullptr,
-          ms ? atoi(ms) : 0, getenv("SPICEY_NO_PHASE_TABLE") != nullptr, getenv("SPICEY_NO_FRESH_FILL") != nullptr, getenv("SPICEY_FRESH_FILL_LINEAR") != nullptr, getenv("SPICEY_NO_EARLY_PREFETCH") != nullptr};
+          ms ? atoi(ms) : 0, getenv("SPICEY_NO_PHASE_TABLE") != nullptr, getenv("SPICEY_NO_FRESH_FILL") != nullptr, getenv("SPICEY_FRESH_FILL_LINEAR") != nullptr, getenv("SPICEY_NO_EARLY_PREFETCH") != nullptr, getenv("SPICEY_NO_OPERAND_SLOTS") != nullptr};
 }
 
 static int pick_threads(const HostProgram &hp, bool v2) {
@@ -291,6 +292,8 @@ int32_t spicey_plan(const SpiceyDesc *desc, const SpiceyOptions &opt, const Spic
     // (the build the launch will pick — spicey_launch_tran_v2 — and whether it has an early-prefetch form)
     const int shape = K == 1 ? spicey_v2_shape(plan.T, plan.packed, hp.hdr.hybrid != 0, plan.packed && hp.hdr.fresh_fill != 0) : -1;
     plan.early = shape >= 0 && SPICEY_V2_SHAPES[shape].early && !knobs.no_early_prefetch;
+    // (its operand-slot form needs the phase table and four free words behind it, within reach of a 16-bit index)
+    plan.slots = plan.early && SPICEY_V2_SHAPES[shape].slots && !knobs.no_operand_slots && !knobs.no_phase_table && spicey_slots_fit(hp.hdr, hres.tail_n);
   }
   if (!plan.lds) {
     // group mode: several CUs per instance when the batch leaves CUs idle and the circuit is large enough for the

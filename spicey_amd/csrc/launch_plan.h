@@ -44,11 +44,12 @@ struct SpiceyV2Shape {
   int threads, rmax, nsv, nel, minw;  // workgroup size (launch bound), slots, re-stamped entries and elements per thread, waves per SIMD
   bool fresh = false;
   bool early = false;  // the shape also has early-prefetch kernels (tran_v2_run.h: EP), which a handle takes unless SPICEY_NO_EARLY_PREFETCH is set
+  bool slots = false;  // ... and an operand-slot kernel (tran_v2_phases.h: OS), taken where the slots fit unless SPICEY_NO_OPERAND_SLOTS is set
 };
 // `early`: Z's element parameters come from one record per thread (SpiceyRun::zpar) and are fetched, with the next source
 // value, at the tail of the last factor phase.  The fresh packed build has it; the other builds were left as they are.
 // (spicey_launch_tran_v2 instantiates one kernel per entry; each kind in ascending threads)
-constexpr SpiceyV2Shape SPICEY_V2_SHAPES[] = {{true, false, 512, 4, 6, 2, 4},    {true, false, 512, 4, 2, 2, 4, true, true},
+constexpr SpiceyV2Shape SPICEY_V2_SHAPES[] = {{true, false, 512, 4, 6, 2, 4},    {true, false, 512, 4, 2, 2, 4, true, true, true},
                                               {false, true, 512, 16, 8, 2, 2},   {false, true, 1024, 4, 4, 1, 4},
                                               {false, false, 256, SPICEY_V2_RMAX256, 12, 4, 1},
                                               {false, false, 512, 16, 8, 2, 2},  {false, false, 1024, 8, 4, 1, 4}};
@@ -66,6 +67,7 @@ struct SpiceyKnobs {
   bool no_fresh_fill = false;        // SPICEY_NO_FRESH_FILL: the packed geometry keeps the default program and the 6-entry build (the in-library A/B switch)
   bool fresh_fill_linear = false;    // SPICEY_FRESH_FILL_LINEAR: tests, a linear circuit (factor reuse) takes the fresh build too
   bool no_early_prefetch = false;    // SPICEY_NO_EARLY_PREFETCH: a shape with early-prefetch kernels keeps its plain build and the handle no parameter record (the in-library A/B switch)
+  bool no_operand_slots = false;     // SPICEY_NO_OPERAND_SLOTS: an early-prefetch run keeps the kernel that masks ground by compare and select and writes no slot (the in-library A/B switch)
 };
 SpiceyKnobs spicey_read_knobs();
 
@@ -117,6 +119,7 @@ struct LaunchPlan {
   bool packed = false;   // two 512-thread workgroups per CU
   bool fresh = false;    // packed: hp is a fresh-fill program and runs on the fresh build (SPICEY_V2_SHAPES)
   bool early = false;    // the run takes the shape's early-prefetch kernel: the handle owns a parameter record (spicey_zpar_doubles)
+  bool slots = false;    // ... in its operand-slot form: the two constants of tran_pt.h (spicey_slot_index) fit behind the phase table
   bool lds = true;       // workspace in LDS (else global memory)
   size_t lds_bytes = 0;
   int64_t algo_bytes = 0;

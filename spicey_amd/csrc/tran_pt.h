@@ -6,6 +6,7 @@
 
 #include "program.h"
 #include "tran_common.h"
+#include "tran_pt_layout.h"
 
 // ---- run-invariant phase arguments, kept on chip (16-bit interpreter, K = 1, tridiagonal-top builds) -------------------
 // What a phase of the time loop needs from SpiceyProg / SpiceyResident / SpiceyRun never changes during a run, yet every
@@ -21,13 +22,12 @@
 // that phase's SpiceyResident::st_desc row.  A program whose rows do not fit (deep elimination trees), one without a top
 // (its tail area is full of tail records) or a handle created with SPICEY_NO_PHASE_TABLE set keeps the scalar loads: both paths
 // are compiled and give identical bits (same operands, same order; only addresses and counts come from elsewhere).
-#define SPICEY_PT_RUN 48
 enum {
   SPICEY_PT_XOFF = 0, SPICEY_PT_NRESTORE, SPICEY_PT_NDYNENT, SPICEY_PT_NGSTAT, SPICEY_PT_NR, SPICEY_PT_NC, SPICEY_PT_NL, SPICEY_PT_NV,
   // 64-bit values, two words each.  (Words 8..13: what a streamed phase needs beside its row — SpiceyPtLanes::row.)
   SPICEY_PT_OVF16 = 8, SPICEY_PT_REC16 = 10, SPICEY_PT_FUS16 = 12,
   SPICEY_PT_NS = 14, SPICEY_PT_ND, SPICEY_PT_NOUT, SPICEY_PT_NCUR,
-  SPICEY_PT_STEPS = 18, SPICEY_PT_SRC = 20, SPICEY_PT_SRC_STRIDE = 22, SPICEY_PT_OUT_V = 24, SPICEY_PT_OUT_I = 26, SPICEY_PT_GSTAT = 28,
+  SPICEY_PT_STEPS = 18, SPICEY_PT_SRC = 20, SPICEY_PT_SRC_STRIDE = 22, SPICEY_PT_OUT_V = 24, SPICEY_PT_OUT_I = 26, SPICEY_PT_GSTAT = 28,  // (OUT_V, OUT_I in an operand-slot build: spicey_pt_rebase_rows)
   SPICEY_PT_DPAR = 30, SPICEY_PT_D_IS = 32, SPICEY_PT_C_VPREV = 34, SPICEY_PT_D_VDPREV = 36, SPICEY_PT_ITERS = 38, SPICEY_PT_LIN_VD = 40,
   SPICEY_PT_LIN_ERR = 42,
   SPICEY_PT_USED = 44,
@@ -37,13 +37,6 @@ enum {
   SPICEY_PT_USED_EP = 46
 };
 static_assert(SPICEY_PT_USED <= SPICEY_PT_ZPAR && SPICEY_PT_USED_EP <= SPICEY_PT_RUN && SPICEY_PT_RUN <= 64 && SPICEY_PT_RUN % 4 == 0, "run-wide block of the phase table: at most one word per lane of a wave");
-SPICEY_HD int spicey_pt_base_words(int pcr_n) { return 1024 + ((pcr_n * 2 + 3) & ~3); }
-// rows of the table of a program with its top at level `pcr_level`, and whether they fit behind the top's index table
-SPICEY_HD int spicey_pt_words(int pcr_level) { return SPICEY_PT_RUN + 16 * pcr_level; }
-SPICEY_HD bool spicey_pt_fits(int pcr_n, int pcr_level, int tail_n) {
-  // (a phase head reads 64 consecutive words from the start of the table, SpiceyPtLanes: with pcr_level >= 1 they lie inside it)
-  return pcr_n > 0 && pcr_n <= 64 && pcr_level >= 1 && tail_n == 0 && spicey_pt_base_words(pcr_n) + spicey_pt_words(pcr_level) <= 5 * 256;
-}
 SPICEY_HD uint32_t spicey_pt_u32(const uint32_t *pt, int i) { return (uint32_t)SPICEY_UNIFORM((int)pt[i]); }
 SPICEY_HD uint64_t spicey_pt_u64(const uint32_t *pt, int i) { return (uint64_t)spicey_pt_u32(pt, i) | ((uint64_t)spicey_pt_u32(pt, i + 1) << 32); }
 template <class X>
@@ -148,6 +141,18 @@ SPICEY_HD void spicey_pt_build(const SpiceyProg &P, const SpiceyResident &Q, con
     const int r = i >> 3, p = r < L ? r : kb + (r - L);
     pt[SPICEY_PT_RUN + i] = Q.st_desc[(size_t)p * 8 + (i & 7)];
   }
+}
+// Operand-slot builds, behind spicey_pt_build in the same phase (thread `tid` wrote word `tid` there): the two result pointers
+// become those of row 0 of THIS workgroup's instance, so that Z adds only step x row per step instead of multiplying
+// (inst (steps + 1) + step) x row out in 64-bit scalars.  A null current pointer stays null.
+template <int K>
+SPICEY_HD void spicey_pt_rebase_rows(const SpiceyProg &P, const SpiceyRun &R, const WgCtx<K> &c, int tid) {
+  static_assert(SPICEY_PT_OUT_I == SPICEY_PT_OUT_V + 2 && SPICEY_PT_OUT_V % 2 == 0, "the two result pointers are neighbours in the table");
+  if (tid < SPICEY_PT_OUT_V || tid >= SPICEY_PT_OUT_I + 2) return;
+  const bool cur = tid >= SPICEY_PT_OUT_I;
+  const double *b = cur ? R.out_i : R.out_v;
+  const uint64_t a = b ? (uint64_t)(uintptr_t)(b + (size_t)c.inst[0] * (size_t)(R.steps + 1) * (size_t)(cur ? P.nCur : P.nOut)) : 0u;
+  (c.tail + spicey_pt_base_words(P.pcr_n))[tid] = (uint32_t)(a >> (32 * (tid & 1)));
 }
 // The fields that the always-executed code of B, Z and Z's parameter prefetch reads (TranPhases2, K = 1, LDS workspace), from
 // the table into two LOCAL structs; every other field stays zero and is never looked at there (TranPhases2::Pg).  What a

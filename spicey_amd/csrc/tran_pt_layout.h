@@ -1,0 +1,40 @@
+// tran_pt_layout.h — where the phase table and the operand slots lie in the tail area (tran_pt.h has the table itself).
+// Plain integer arithmetic on SpiceyProg's fields, free of device intrinsics: the launch plan includes it as well as the kernels.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include "program.h"
+
+#if defined(__HIPCC__)
+#define SPICEY_LAYOUT_FN __host__ __device__ inline __attribute__((always_inline))
+#else
+#define SPICEY_LAYOUT_FN inline
+#endif
+#define SPICEY_PT_RUN 48  // 32-bit words of the table's run-wide block (tran_pt.h)
+SPICEY_LAYOUT_FN int spicey_pt_base_words(int pcr_n) { return 1024 + ((pcr_n * 2 + 3) & ~3); }
+// rows of the table of a program with its top at level `pcr_level`, and whether they fit behind the top's index table
+SPICEY_LAYOUT_FN int spicey_pt_words(int pcr_level) { return SPICEY_PT_RUN + 16 * pcr_level; }
+SPICEY_LAYOUT_FN bool spicey_pt_fits(int pcr_n, int pcr_level, int tail_n) {
+  // (a phase head reads 64 consecutive words from the start of the table, SpiceyPtLanes: with pcr_level >= 1 they lie inside it)
+  return pcr_n > 0 && pcr_n <= 64 && pcr_level >= 1 && tail_n == 0 && spicey_pt_base_words(pcr_n) + spicey_pt_words(pcr_level) <= 5 * 256;
+}
+// ---- operand slots (operand-slot builds, tran_v2_run.h: OS) ---------------------------------------------------------------
+// Two read-only doubles, written by the prologue and never again: +0.0, which a ground terminal reads instead of being
+// compared and masked (v - (+0.0) and (+0.0) - v are what TranPhases2::dv16 computes, signs of zero included), and -0.0
+// behind it, the neutral element of an addition (x + (-0.0) == x for every x, both zeros included).  They take the last
+// four words of the 5 KB tail area of a tridiagonal-top build, behind the phase table, and are addressed like any other
+// operand: by their index from the start of the LDS workspace (K = 1, LDS layout of spicey_lds_bytes: the workspace, the
+// switch states and flags, the profiling slots, then the tail area).  A program whose table leaves no room there, or whose
+// slots a 16-bit index from the start of the workspace, or a 14-bit one from the start of the element vectors (phase B's
+// descriptor fields: TranPhases2::dd_slots / rhs_slots), cannot reach, keeps the builds without them (spicey_plan).
+#define SPICEY_SLOT_TAIL_WORD (5 * 256 - 4)
+SPICEY_LAYOUT_FN uint32_t spicey_slot_index(const SpiceyProg &P) {  // of +0.0; -0.0 is the next double
+  const size_t ws = ((size_t)P.nW + (size_t)P.nU + (size_t)P.nGdyn) * sizeof(double) + ((size_t)P.nS + 4) * sizeof(int32_t);
+  const size_t tail = ((ws + 15) & ~(size_t)15) + SPICEY_PH_SLOTS * sizeof(unsigned long long);
+  return (uint32_t)((tail + (size_t)SPICEY_SLOT_TAIL_WORD * 4) / sizeof(double));
+}
+SPICEY_LAYOUT_FN bool spicey_slots_fit(const SpiceyProg &P, int tail_n) {
+  return !P.hybrid && spicey_pt_fits(P.pcr_n, P.pcr_level, tail_n) && spicey_pt_base_words(P.pcr_n) + spicey_pt_words(P.pcr_level) <= SPICEY_SLOT_TAIL_WORD &&
+         spicey_slot_index(P) + 1 < 0xFFFFu && spicey_slot_index(P) + 1 - (uint32_t)P.nW <= 0x3FFFu;
+}

@@ -22,9 +22,19 @@
 // and are fetched, with the next step's source value, between the factor and the backward phases instead of at the tail of
 // the last backward one; B then fetches and parks nothing (spicey_tran_run_v2 places the calls: see there for where).  A compile-time property of a build, like
 // FRESH: a kernel that holds both forms of B and Z does not fit the 128 registers of the packed builds.
-template <int K, int RMAX, int NSV, int NEL, bool HYB = false, bool EP = false>
+// OS: the operand-slot build (an early-prefetch build with the phase table, tran_pt_layout.h: spicey_slot_index) — two read-only
+// constants in LDS take the place of conditions that were evaluated again in every step.  Z: the terminal indices that
+// load_resident keeps in registers name the +0.0 slot where the netlist says ground, so the resident section reads
+// c.W[index] and subtracts, with no compare and no select (14 index halves per thread and step: 56 vector instructions of
+// Z's ~275); its eight result stores take a 32-bit lane offset on a wave-uniform section base, and the row bases come
+// from the phase table with the instance's share already multiplied out (spicey_pt_rebase_rows).  B: an empty field of
+// a resident stamp or right-hand-side descriptor names the -0.0 slot, so all operands of a thread's entries and rows are
+// read together, one LDS round trip instead of six dependent ones (dd_slots / rhs_slots below).  Everything that
+// decodes a descriptor from global memory (the beyond-capacity loops of B and Z, a_reiterate, z_lin_err) is unchanged.
+template <int K, int RMAX, int NSV, int NEL, bool HYB = false, bool EP = false, bool OS = false>
 struct TranPhases2 {
   static_assert(!EP || (K == 1 && !HYB), "the early prefetch is built for one instance per workgroup on the LDS workspace");
+  static_assert(!OS || EP, "the operand slots are built into the early-prefetch kernels");
   const SpiceyProg &P;
   const SpiceyRun &R;
   WgCtx<K> &c;
@@ -91,6 +101,44 @@ struct TranPhases2 {
   }
   SPICEY_HD double dv16(uint32_t ab, int k) const { return volt16(ab & 0xFFFFu, k) - volt16(ab >> 16, k); }
 
+  // OS: a register-resident index (one 16-bit half; ground already names the +0.0 slot) and a pair of them
+  SPICEY_HD double volt_res(uint32_t xi) const { return c.W[(size_t)xi]; }
+  SPICEY_HD double dv_res(uint32_t ab) const { return volt_res(ab & 0xFFFFu) - volt_res(ab >> 16); }
+  static SPICEY_HD uint32_t slot_pair(uint32_t ab, uint32_t zs) {
+    const uint32_t a = ab & 0xFFFFu, b = ab >> 16;
+    return (a == 0xFFFFu ? zs : a) | ((b == 0xFFFFu ? zs : b) << 16);
+  }
+
+  // OS, phase B: the descriptors of the resident entries and rows name an operand in EVERY field — a field that the program
+  // leaves empty reads the -0.0 slot with the add sign (x + (-0.0) == x, bit for bit, for every x), so all conductances of a
+  // thread's entries and all contributions of its rows are read unconditionally and together, then combined in the
+  // order of stamp_entry / rhs_row.  Same registers, other fields:
+  //   dd     bits 0-13 / 15-28: index into c.gd (no + 1), bit 14 / 29: subtract; bit 30: reciprocal; bit 31: not mine to stamp
+  //   rhs[2] four 16-bit fields: bits 0-13 index into c.u (no + 1), bit 15: subtract; bit 14 of the LAST field: not a resident row
+  // zg / zu: the -0.0 slot as an index into c.gd / c.u; spicey_slots_fit has made sure that 14 bits hold them.
+  static SPICEY_HD uint32_t dd_slots(uint32_t dd, uint32_t zg) {
+    const bool mine = !(dd >> 31);
+    const uint32_t f0 = mine ? dd & 0x7fffu : 0u, f1 = mine ? (dd >> 15) & 0x7fffu : 0u;
+    const uint32_t g0 = f0 ? (((f0 & 0x3fffu) - 1u) | (f0 & 0x4000u)) : zg, g1 = f1 ? (((f1 & 0x3fffu) - 1u) | (f1 & 0x4000u)) : zg;
+    return g0 | (g1 << 15) | (dd & 0xC0000000u);
+  }
+  static SPICEY_HD void rhs_slots(uint32_t &d0, uint32_t &d1, uint32_t zu) {
+    const bool mine = d1 != 0xFFFFFFFFu;
+    uint32_t g[4];
+    const uint32_t f[4] = {d0 & 0xffffu, d0 >> 16, d1 & 0xffffu, d1 >> 16};
+    for (int i = 0; i < 4; i++) g[i] = (mine && f[i]) ? (((f[i] & 0x7fffu) - 1u) | (f[i] & 0x8000u)) : zu;
+    d0 = g[0] | (g[1] << 16);
+    d1 = g[2] | (g[3] << 16) | (mine ? 0u : 0x40000000u);
+  }
+  // g, or -g where bit 31 of `flip` is set (every other bit of it is ignored): x + this is x + g or, bit for bit, x - g
+  static SPICEY_HD double signed_by(double g, uint32_t flip) {
+    uint64_t b;
+    __builtin_memcpy(&b, &g, 8);
+    b ^= (uint64_t)(flip & 0x80000000u) << 32;
+    __builtin_memcpy(&g, &b, 8);
+    return g;
+  }
+
   SPICEY_HD void load_resident(int tid, const SpiceyResident &Q, Regs &rr) const {
     for (int s = 0; s < RMAX; s++) {
       const bool have = s < Q.rmax;
@@ -116,6 +164,15 @@ struct TranPhases2 {
       rr.eD[j] = i < P.nD ? P.D_ab[i] : 0xFFFFFFFFu;
       rr.ox[j] = i < P.nOut ? (P.out_x[i] < 0 ? 0xFFFFu : (uint32_t)P.out_x[i]) : 0xFFFFu;
     }
+    if (OS) {  // ground, and an item that does not exist, read the +0.0 slot; the two constants are written here, once per run
+      const uint32_t zs = spicey_slot_index(P);
+      for (int j = 0; j < NEL; j++) {
+        rr.eR[j] = slot_pair(rr.eR[j], zs); rr.eC[j] = slot_pair(rr.eC[j], zs); rr.eD[j] = slot_pair(rr.eD[j], zs);
+        rr.ox[j] = rr.ox[j] == 0xFFFFu ? zs : rr.ox[j];  // (the upper half is still empty here)
+        rhs_slots(rr.rhs[j][0], rr.rhs[j][1], zs + 1u - (uint32_t)P.nW);
+      }
+      if (tid == 0) { c.W[(size_t)zs] = 0.0; c.W[(size_t)zs + 1] = -0.0; }
+    }
     if (tid < P.nV) rr.ox[0] |= (uint32_t)P.V_x[tid] << 16;  // upper half of ox[0]: W index of the branch current of source tid
   }
   // after p1_static: static entry values into registers; elements from the state entering the run
@@ -124,6 +181,7 @@ struct TranPhases2 {
     for (int j = 0; j < NSV; j++) {
       const int e = tid + j * T;
       if (j < Regs::NDD) rr.dd[j] = e < n_stamped() ? P.ent_dd[e] : 0x80000000u;  // bit 31 = "not mine to stamp"
+      if (OS && j < Regs::NDD) rr.dd[j] = dd_slots(rr.dd[j], spicey_slot_index(P) + 1u - (uint32_t)(P.nW + P.nU));
       for (int k = 0; k < K; k++) rr.sv[j][k] = e < n_stamped() ? R.statv[(size_t)c.inst[k] * P.nLU + e] : 0.0;
     }
     for (int k = 0; k < K; k++) {  // entries that no phase ever writes: stamped once per run
@@ -379,6 +437,29 @@ struct TranPhases2 {
       stamp_rest_batched(tid);
       return;
     }
+    if (OS) {  // (every field names an operand — dd_slots: all conductances first, one LDS round trip, then entry by entry)
+      double ga[Regs::NDD], gb[Regs::NDD];
+      SPICEY_UNROLL
+      for (int j = 0; j < Regs::NDD; j++) {
+        uint32_t dd = rr.dd[j];
+        SPICEY_OPAQUE(dd);
+        ga[j] = c.gd[(size_t)(dd & 0x3fffu)];
+        gb[j] = c.gd[(size_t)((dd >> 15) & 0x3fffu)];
+      }
+      SPICEY_UNROLL
+      for (int j = 0; j < Regs::NDD; j++) {
+        uint32_t dd = rr.dd[j];
+        SPICEY_OPAQUE(dd);
+        double x = rr.sv[j][0] + signed_by(ga[j], dd << 17);
+        x = x + signed_by(gb[j], dd << 2);
+        if (dd >> 31) continue;
+        if (dd & (1u << 30)) {
+          if (fabs(x) < SPICEY_EPS && c.valid[0]) { c.flags[1] = 1; c.flags[2] = c.inst[0]; }
+          x = spicey_rcp(x);
+        }
+        put_entry((uint32_t)(tid + j * T), 0, x);
+      }
+    } else
     for (int j = 0; j < Regs::NDD; j++) {
       const uint32_t e = (uint32_t)(tid + j * T);
       uint32_t dd = rr.dd[j];
@@ -460,6 +541,27 @@ struct TranPhases2 {
           if (f[i]) acc = (f[i] & 0x8000u) ? acc - t[j][i] : acc + t[j][i];
         c.W[(size_t)(P.xoff + tid + j * T)] = acc;
       }
+    } else if (OS) {  // (every field names an operand — rhs_slots: the contributions of all resident rows in one LDS round trip)
+      double t[NEL][4];
+      SPICEY_UNROLL
+      for (int j = 0; j < NEL; j++) {
+        uint32_t d0 = rr.rhs[j][0], d1 = rr.rhs[j][1];
+        SPICEY_OPAQUE(d0); SPICEY_OPAQUE(d1);
+        t[j][0] = c.u[(size_t)(d0 & 0x3fffu)]; t[j][1] = c.u[(size_t)((d0 >> 16) & 0x3fffu)];
+        t[j][2] = c.u[(size_t)(d1 & 0x3fffu)]; t[j][3] = c.u[(size_t)((d1 >> 16) & 0x3fffu)];
+      }
+      SPICEY_UNROLL
+      for (int j = 0; j < NEL; j++) {
+        uint32_t d0 = rr.rhs[j][0], d1 = rr.rhs[j][1];
+        SPICEY_OPAQUE(d0); SPICEY_OPAQUE(d1);
+        if (d1 & 0x40000000u) continue;
+        double acc = 0.0;
+        acc = acc + signed_by(t[j][0], d0 << 16);
+        acc = acc + signed_by(t[j][1], d0);
+        acc = acc + signed_by(t[j][2], d1 << 16);
+        acc = acc + signed_by(t[j][3], d1);
+        c.W[(size_t)(P.xoff + tid + j * T)] = acc;
+      }
     } else
     for (int j = 0; j < NEL; j++) {
       uint32_t d0 = rr.rhs[j][0], d1 = rr.rhs[j][1];
@@ -525,6 +627,23 @@ struct TranPhases2 {
     if (oi) SPICEY_STREAM_STORE(&oi[cD + i], irec);
     c.gd[(size_t)(P.nS + i) * K + k] = gg;
     c.u[(size_t)(oD + i) * K + k] = q;
+    if (last) R.D_vdprev[in * P.nD + i] = vd;
+  }
+  // OS: slot `i` of a row section that starts at the wave-uniform `row` — a 32-bit lane BYTE offset on a base in scalars
+  static SPICEY_HD double *row_at(double *row, int i) { return (double *)((char *)row + (uint32_t)i * 8u); }
+  // ... and the same two element updates storing through it (`sec`: the element class's section of the current row, null: no currents wanted)
+  SPICEY_HD void z_cap_at(int i, double dv, size_t in, double gc, double *sec, double &vprev, bool last) const {
+    if (sec) SPICEY_STREAM_STORE(row_at(sec, i), gc * (dv - vprev));
+    vprev = dv;
+    c.u[(size_t)i] = gc * dv;
+    if (last) R.C_vprev[in * P.nC + i] = dv;
+  }
+  SPICEY_HD void z_dio_at(int i, double vd, size_t in, double is, double dp0, double dp1, double *sec, int oD, bool last) const {
+    double gg, q, irec;
+    spicey_diode_k(vd, is, dp0, dp1, sec != nullptr, gg, q, irec);
+    if (sec) SPICEY_STREAM_STORE(row_at(sec, i), irec);
+    c.gd[(size_t)(P.nS + i)] = gg;
+    c.u[(size_t)(oD + i)] = q;
     if (last) R.D_vdprev[in * P.nD + i] = vd;
   }
   // diagnostics pass of Z (SpiceyRun::lin_vd set; its own loop so that the production path carries no extra state):
@@ -624,8 +743,9 @@ struct TranPhases2 {
       const int vk = K == 1 ? c.valid[0] : (k == 0 ? c.valid[0] : c.valid[K - 1]);
       if (!vk) continue;
       const size_t in = (size_t)(K == 1 ? c.inst[0] : (k == 0 ? c.inst[0] : c.inst[K - 1]));
-      double *ov = R.out_v + (in * (size_t)(R.steps + 1) + (size_t)step) * P.nOut;
-      double *oi = R.out_i ? R.out_i + (in * (size_t)(R.steps + 1) + (size_t)step) * P.nCur : nullptr;
+      // (OS: the table's two result pointers are this instance's row 0 already — spicey_pt_rebase_rows)
+      double *ov = R.out_v + ((OS ? 0 : in * (size_t)(R.steps + 1)) + (size_t)step) * P.nOut;
+      double *oi = R.out_i ? R.out_i + ((OS ? 0 : in * (size_t)(R.steps + 1)) + (size_t)step) * P.nCur : nullptr;
       const double *g = R.gstat + in * P.nGstat;
       if (DIAG && R.lin_vd) {  // diagnostics (wave-uniform): the step's one-shot linearisation error
         const double lerr = z_lin_err(tid, k, in);
@@ -661,12 +781,17 @@ struct TranPhases2 {
         for (int j = 0; j < NEL; j++) {
           uint32_t ox = rr.ox[j], eR = rr.eR[j];
           SPICEY_OPAQUE(ox); SPICEY_OPAQUE(eR);
-          vo[j] = volt16(ox & 0xFFFFu, k);
-          dR[j] = dv16(eR, k);
+          vo[j] = OS ? volt_res(ox & 0xFFFFu) : volt16(ox & 0xFFFFu, k);
+          dR[j] = OS ? dv_res(eR) : dv16(eR, k);
         }
         SPICEY_SCHED_FENCE;
         for (int j = 0; j < NEL; j++) {
           const int i = tid + j * T;
+          if (OS) {
+            if (i < P.nOut && !(SPICEY_EXP & 16)) SPICEY_STREAM_STORE(row_at(ov, i), vo[j]);
+            if (oi && i < P.nR && !(SPICEY_EXP & 16)) SPICEY_STREAM_STORE(row_at(oi + cR, i), dR[j] * pR[j]);
+            continue;
+          }
           if (i < P.nOut && !(SPICEY_EXP & 16)) SPICEY_STREAM_STORE(&ov[i], vo[j]);
           if (oi && i < P.nR && !(SPICEY_EXP & 16)) SPICEY_STREAM_STORE(&oi[cR + i], dR[j] * pR[j]);
         }
@@ -676,8 +801,8 @@ struct TranPhases2 {
       for (int j = 0; j < NEL; j++) {
         uint32_t eC = rr.eC[j], eD = rr.eD[j];
         SPICEY_OPAQUE(eC); SPICEY_OPAQUE(eD);
-        dC[j] = dv16(eC, k);
-        dD[j] = dv16(eD, k);
+        dC[j] = OS ? dv_res(eC) : dv16(eC, k);
+        dD[j] = OS ? dv_res(eD) : dv16(eD, k);
       }
       SPICEY_SCHED_FENCE;
       SPICEY_MARK(c, 1);
@@ -685,7 +810,8 @@ struct TranPhases2 {
         const int i = tid + j * T;
         if (i < P.nC && !(SPICEY_EXP & 4)) {
           double vp = K == 1 ? rr.vprev[j][0] : (k == 0 ? rr.vprev[j][0] : rr.vprev[j][K - 1]);
-          z_cap(i, dC[j], k, in, pC[j], oi, cC, vp, last);
+          if (OS) z_cap_at(i, dC[j], in, pC[j], oi ? oi + cC : nullptr, vp, last);
+          else z_cap(i, dC[j], k, in, pC[j], oi, cC, vp, last);
           if (K == 1 || k == 0) rr.vprev[j][0] = vp;
           else rr.vprev[j][K - 1] = vp;
         }
@@ -694,7 +820,10 @@ struct TranPhases2 {
       SPICEY_MARK(c, 2);
       for (int j = 0; j < NEL; j++) {
         const int i = tid + j * T;
-        if (i < P.nD && !(SPICEY_EXP & 2)) z_dio(i, dD[j], k, in, pIs[j], pD0[j], pD1[j], oi, cD, oD, last);
+        if (i < P.nD && !(SPICEY_EXP & 2)) {
+          if (OS) z_dio_at(i, dD[j], in, pIs[j], pD0[j], pD1[j], oi ? oi + cD : nullptr, oD, last);
+          else z_dio(i, dD[j], k, in, pIs[j], pD0[j], pD1[j], oi, cD, oD, last);
+        }
         SPICEY_SCHED_FENCE;
       }
       SPICEY_MARK(c, 3);

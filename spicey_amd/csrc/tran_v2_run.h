@@ -132,10 +132,15 @@ template <class E, class = void>
 struct SpiceyHasIdleWaves { static constexpr bool value = false; };
 template <class E>
 struct SpiceyHasIdleWaves<E, decltype((void)E::idle_waves)> { static constexpr bool value = true; };
-template <int K, int RMAX, int NSV, int NEL, bool HYB = false, int PT = -1, bool EP = false, class Exec>
+// OS (the operand-slot build, TranPhases2): an early-prefetch build whose prologue writes the two constants of the operand
+// slots (tran_pt_layout.h), resolves ground in Z's resident terminal indices to the +0.0 slot and the empty fields of B's
+// resident descriptors to the -0.0 slot, and keeps the instance's row bases in the phase table; the caller has made sure
+// that spicey_slots_fit holds for the program (the launch plan; it implies a phase table, whose free tail the slots take).
+template <int K, int RMAX, int NSV, int NEL, bool HYB = false, int PT = -1, bool EP = false, bool OS = false, class Exec>
 SPICEY_HD void spicey_tran_run_v2(Exec &ex, const SpiceyProg &P, const SpiceyResident &Q, const SpiceyRun &R, WgCtx<K> &c, int wg) {
   const int T = ex.threads();
-  typedef TranPhases2<K, RMAX, NSV, NEL, HYB, EP> Ph2;
+  static_assert(!OS || PT != 0, "the operand slots lie behind the phase table");
+  typedef TranPhases2<K, RMAX, NSV, NEL, HYB, EP, OS> Ph2;
   uint32_t brem, zrem;
   {
     Ph2 p2{P, R, c, T, 0u, 0u};
@@ -146,7 +151,7 @@ SPICEY_HD void spicey_tran_run_v2(Exec &ex, const SpiceyProg &P, const SpiceyRes
   // the phase table: tridiagonal-top builds whose rows fit behind the top's index table (wave-uniform, fixed for the run)
   static_assert(PT <= 0 || K == 1, "the phase table is built for one instance per workgroup");
   const bool pt_run = PT >= 0 ? PT == 1 : (K == 1 && spicey_pt_runtime_choice(P, Q));
-  if (pt_run) ex.phase(SPICEY_PH_PRO, [&](int tid) { spicey_pt_build<K>(P, Q, R, c, tid, T, EP); });  // (the structs where they live: see there)
+  if (pt_run) ex.phase(SPICEY_PH_PRO, [&](int tid) { spicey_pt_build<K>(P, Q, R, c, tid, T, EP); if (OS) spicey_pt_rebase_rows<K>(P, R, c, tid); });  // (the structs where they live: see there)
   ex.phase(SPICEY_PH_PRO, [&](int tid) {
     const SpiceyProg Pf = ex.fresh(P); const SpiceyResident Qf = ex.fresh(Q); const SpiceyRun Rf = ex.fresh(R);
     TranPhases<K> ph{Pf, Rf, c, T};
