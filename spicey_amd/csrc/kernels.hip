@@ -528,7 +528,9 @@ struct GpuExecV2 {
 // parameter and not a parameter of its own, so that every kernel without it keeps its name — profiles and tools know them by it.
 // PT, bit 2 (SPICEY_KERNEL_OS): the operand-slot form of an early-prefetch kernel with the phase table (tran_v2_phases.h: OS)
 #define SPICEY_KERNEL_EP 2
+// PT, bit 3 (SPICEY_KERNEL_RA): the ready-argument form of an operand-slot kernel (tran_v2_run.h: RA)
 #define SPICEY_KERNEL_OS 4
+#define SPICEY_KERNEL_RA 8
 template <int K, int RMAX, int NSV, int NEL, int MAXT, int MINW, bool HYB = false, int PT = 0>
 __global__ void __launch_bounds__(MAXT, MINW) spicey_tran_kernel_v2(const SpiceyProg *__restrict__ Pg, const SpiceyResident *__restrict__ Qg,
                                                                     const SpiceyRun *__restrict__ Rg) {
@@ -578,7 +580,7 @@ __global__ void __launch_bounds__(MAXT, MINW) spicey_tran_kernel_v2(const Spicey
     // start stamps wait in their own slots (not in registers: nothing may stay live around the whole run)
     if (threadIdx.x == 0) { lprof[5] = (unsigned long long)clock64(); lprof[6] = (unsigned long long)wall_clock64(); }
   }
-  spicey_tran_run_v2<K, RMAX, NSV, NEL, HYB, PT & 1, (PT & SPICEY_KERNEL_EP) != 0, (PT & SPICEY_KERNEL_OS) != 0>(ex, P, Q, R, c, wg);
+  spicey_tran_run_v2<K, RMAX, NSV, NEL, HYB, PT & 1, (PT & SPICEY_KERNEL_EP) != 0, (PT & SPICEY_KERNEL_OS) != 0, (PT & SPICEY_KERNEL_RA) != 0>(ex, P, Q, R, c, wg);
   if (R.prof) {
     __syncthreads();
     if (threadIdx.x == 0) {  // slots 5/6: whole-run shader cycles and 100 MHz wall ticks -> effective clock
@@ -590,9 +592,9 @@ __global__ void __launch_bounds__(MAXT, MINW) spicey_tran_kernel_v2(const Spicey
   }
 }
 
-template <int K, int RMAX, int NSV, int NEL, int MAXT, int MINW, bool HYB = false, int PT = 0, bool EP = false, bool OS = false>
+template <int K, int RMAX, int NSV, int NEL, int MAXT, int MINW, bool HYB = false, int PT = 0, bool EP = false, bool OS = false, bool RA = false>
 hipError_t launch_v2_t(const SpiceyProg *P, const SpiceyResident *Q, const SpiceyRun *R, int grid, int threads, size_t lds, hipStream_t st) {
-  auto kern = spicey_tran_kernel_v2<K, RMAX, NSV, NEL, MAXT, MINW, HYB, PT | (EP ? SPICEY_KERNEL_EP : 0) | (OS ? SPICEY_KERNEL_OS : 0)>;
+  auto kern = spicey_tran_kernel_v2<K, RMAX, NSV, NEL, MAXT, MINW, HYB, PT | (EP ? SPICEY_KERNEL_EP : 0) | (OS ? SPICEY_KERNEL_OS : 0) | (RA ? SPICEY_KERNEL_RA : 0)>;
   if (const hipError_t e = spicey_allow_dyn_lds(kern, lds); e != hipSuccess) return e;
   hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, st, P, Q, R);
   return hipGetLastError();
@@ -667,12 +669,13 @@ hipError_t spicey_launch_tran(const SpiceyProg &P, const SpiceyRun &R, int K, bo
 }
 
 // one launcher per entry of SPICEY_V2_SHAPES (launch_plan.h)
-template <int I, int PT = 0, bool EP = false, bool OS = false>
+template <int I, int PT = 0, bool EP = false, bool OS = false, bool RA = false>
 static hipError_t launch_v2_shape(const SpiceyProg *P, const SpiceyResident *Q, const SpiceyRun *R, int grid, int threads, size_t lds, hipStream_t st) {
   constexpr SpiceyV2Shape s = SPICEY_V2_SHAPES[I];
   static_assert(!EP || s.early, "an early-prefetch kernel is built for the shapes that say so");
   static_assert(!OS || (s.slots && EP && PT == 1), "an operand-slot kernel is an early-prefetch kernel with the phase table, for the shapes that say so");
-  return launch_v2_t<1, s.rmax, s.nsv, s.nel, s.threads, s.minw, s.hybrid, PT, EP, OS>(P, Q, R, grid, threads, lds, st);
+  static_assert(!RA || (s.ready && OS), "a ready-argument kernel is an operand-slot kernel, for the shapes that say so");
+  return launch_v2_t<1, s.rmax, s.nsv, s.nel, s.threads, s.minw, s.hybrid, PT, EP, OS, RA>(P, Q, R, grid, threads, lds, st);
 }
 static decltype(&launch_v2_shape<0>) const launch_v2_by_shape[] = {launch_v2_shape<0>, launch_v2_shape<1>, launch_v2_shape<2>, launch_v2_shape<3>,
                                                                     launch_v2_shape<4>, launch_v2_shape<5>, launch_v2_shape<6>};
@@ -689,17 +692,24 @@ static decltype(&launch_v2_shape<0>) const launch_v2_early_by_shape[2][SPICEY_V2
 
 // the operand-slot builds (null: that shape has none — SPICEY_V2_SHAPES order, SpiceyV2Shape::slots)
 static decltype(&launch_v2_shape<0>) const launch_v2_slots_by_shape[SPICEY_V2_NSHAPES] = {nullptr, launch_v2_shape<1, 1, true, true>, nullptr, nullptr, nullptr, nullptr, nullptr};
+// ... and their ready-argument form (SpiceyV2Shape::ready)
+static decltype(&launch_v2_shape<0>) const launch_v2_ready_by_shape[SPICEY_V2_NSHAPES] = {nullptr, launch_v2_shape<1, 1, true, true, true>, nullptr, nullptr, nullptr, nullptr, nullptr};
 
 hipError_t spicey_launch_tran_v2(const SpiceyProg &Ph, const SpiceyResident &Qh, const SpiceyProg *P, const SpiceyResident *Q, const SpiceyRun *R, int K, int grid,
-                                 int threads, hipStream_t st, bool packed, bool phase_table, bool early, bool slots) {
+                                 int threads, hipStream_t st, bool packed, bool phase_table, bool early, bool slots, bool ready) {
   const int shape = K == 1 ? spicey_v2_shape(threads, packed, Ph.hybrid != 0, packed && Ph.fresh_fill != 0) : -1;  // (a fresh-fill program runs on the build that decodes its flags: spicey_plan makes one for the packed geometry only)
   if (shape < 0) return hipErrorInvalidValue;
   // the table sits in the tail area behind the tridiagonal top's index table: only where it fits there (tran_exec.h)
   const bool pt = phase_table && launch_v2_pt_by_shape[shape] != nullptr && spicey_pt_fits(Ph.pcr_n, Ph.pcr_level, Qh.tail_n);
   if (slots) {  // (the plan found room for the operand slots: spicey_slots_fit — checked again, the kernel writes there)
     if (!early || !pt || launch_v2_slots_by_shape[shape] == nullptr || !spicey_slots_fit(Ph, Qh.tail_n)) return hipErrorInvalidValue;
+    if (ready) {  // (the caller has checked the run's step count: spicey_ready_steps_ok)
+      if (launch_v2_ready_by_shape[shape] == nullptr) return hipErrorInvalidValue;
+      return launch_v2_ready_by_shape[shape](P, Q, R, grid, threads, spicey_lds_bytes(Ph, K, true, Qh.tail_n), st);
+    }
     return launch_v2_slots_by_shape[shape](P, Q, R, grid, threads, spicey_lds_bytes(Ph, K, true, Qh.tail_n), st);
   }
+  if (ready) return hipErrorInvalidValue;  // (only an operand-slot run has such a form)
   if (early) {  // (the run's SpiceyRun carries the parameter record: only the build that reads it may run)
     if (!SPICEY_V2_SHAPES[shape].early || launch_v2_early_by_shape[pt][shape] == nullptr) return hipErrorInvalidValue;
     return launch_v2_early_by_shape[pt][shape](P, Q, R, grid, threads, spicey_lds_bytes(Ph, K, true, Qh.tail_n), st);

@@ -47,7 +47,7 @@ static const SpiceyV2Shape &v2_build(int threads, bool packed = false, bool hybr
 SpiceyKnobs spicey_read_knobs() {
   const char *ms = getenv("SPICEY_GROUP_TIMEOUT_MS");
   return {getenv("SPICEY_NO_HYBRID") != nullptr, getenv("SPICEY_FRONT_RIGHT_LOOKING") != nullptr, getenv("SPICEY_TEST_FORCE_GROUP_ABORT") != nullptr,
-          ms ? atoi(ms) : 0, getenv("SPICEY_NO_PHASE_TABLE") != nullptr, getenv("SPICEY_NO_FRESH_FILL") != nullptr, getenv("SPICEY_FRESH_FILL_LINEAR") != nullptr, getenv("SPICEY_NO_EARLY_PREFETCH") != nullptr, getenv("SPICEY_NO_OPERAND_SLOTS") != nullptr};
+          ms ? atoi(ms) : 0, getenv("SPICEY_NO_PHASE_TABLE") != nullptr, getenv("SPICEY_NO_FRESH_FILL") != nullptr, getenv("SPICEY_FRESH_FILL_LINEAR") != nullptr, getenv("SPICEY_NO_EARLY_PREFETCH") != nullptr, getenv("SPICEY_NO_OPERAND_SLOTS") != nullptr, getenv("SPICEY_NO_READY_ARGS") != nullptr};
 }
 
 static int pick_threads(const HostProgram &hp, bool v2) {
@@ -294,6 +294,7 @@ int32_t spicey_plan(const SpiceyDesc *desc, const SpiceyOptions &opt, const Spic
     plan.early = shape >= 0 && SPICEY_V2_SHAPES[shape].early && !knobs.no_early_prefetch;
     // (its operand-slot form needs the phase table and four free words behind it, within reach of a 16-bit index)
     plan.slots = plan.early && SPICEY_V2_SHAPES[shape].slots && !knobs.no_operand_slots && !knobs.no_phase_table && spicey_slots_fit(hp.hdr, hres.tail_n);
+    plan.ready = plan.slots && SPICEY_V2_SHAPES[shape].ready && !knobs.no_ready_args;
   }
   if (!plan.lds) {
     // group mode: several CUs per instance when the batch leaves CUs idle and the circuit is large enough for the
@@ -325,6 +326,8 @@ int32_t spicey_plan(const SpiceyDesc *desc, const SpiceyOptions &opt, const Spic
   }
   return SPICEY_OK;
 }
+
+bool spicey_ready_run(const LaunchPlan &plan, int64_t steps) { return plan.slots && plan.ready && spicey_ready_steps_ok(steps); }
 
 size_t spicey_zpar_doubles(const LaunchPlan &plan, const HostProgram &hp) {
   if (!plan.early || plan.interp != 2) return 0;

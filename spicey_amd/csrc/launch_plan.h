@@ -45,11 +45,12 @@ struct SpiceyV2Shape {
   bool fresh = false;
   bool early = false;  // the shape also has early-prefetch kernels (tran_v2_run.h: EP), which a handle takes unless SPICEY_NO_EARLY_PREFETCH is set
   bool slots = false;  // ... and an operand-slot kernel (tran_v2_phases.h: OS), taken where the slots fit unless SPICEY_NO_OPERAND_SLOTS is set
+  bool ready = false;  // ... and that kernel's ready-argument form (tran_v2_run.h: RA), taken by an operand-slot run unless SPICEY_NO_READY_ARGS is set
 };
 // `early`: Z's element parameters come from one record per thread (SpiceyRun::zpar) and are fetched, with the next source
 // value, at the tail of the last factor phase.  The fresh packed build has it; the other builds were left as they are.
 // (spicey_launch_tran_v2 instantiates one kernel per entry; each kind in ascending threads)
-constexpr SpiceyV2Shape SPICEY_V2_SHAPES[] = {{true, false, 512, 4, 6, 2, 4},    {true, false, 512, 4, 2, 2, 4, true, true, true},
+constexpr SpiceyV2Shape SPICEY_V2_SHAPES[] = {{true, false, 512, 4, 6, 2, 4},    {true, false, 512, 4, 2, 2, 4, true, true, true, true},
                                               {false, true, 512, 16, 8, 2, 2},   {false, true, 1024, 4, 4, 1, 4},
                                               {false, false, 256, SPICEY_V2_RMAX256, 12, 4, 1},
                                               {false, false, 512, 16, 8, 2, 2},  {false, false, 1024, 8, 4, 1, 4}};
@@ -68,6 +69,7 @@ struct SpiceyKnobs {
   bool fresh_fill_linear = false;    // SPICEY_FRESH_FILL_LINEAR: tests, a linear circuit (factor reuse) takes the fresh build too
   bool no_early_prefetch = false;    // SPICEY_NO_EARLY_PREFETCH: a shape with early-prefetch kernels keeps its plain build and the handle no parameter record (the in-library A/B switch)
   bool no_operand_slots = false;     // SPICEY_NO_OPERAND_SLOTS: an early-prefetch run keeps the kernel that masks ground by compare and select and writes no slot (the in-library A/B switch)
+  bool no_ready_args = false;        // SPICEY_NO_READY_ARGS: an operand-slot run keeps the kernel that moves all of Z's arguments to scalars at the phase head (the in-library A/B switch)
 };
 SpiceyKnobs spicey_read_knobs();
 
@@ -120,6 +122,7 @@ struct LaunchPlan {
   bool fresh = false;    // packed: hp is a fresh-fill program and runs on the fresh build (SPICEY_V2_SHAPES)
   bool early = false;    // the run takes the shape's early-prefetch kernel: the handle owns a parameter record (spicey_zpar_doubles)
   bool slots = false;    // ... in its operand-slot form: the two constants of tran_pt.h (spicey_slot_index) fit behind the phase table
+  bool ready = false;    // ... with ready arguments (tran_v2_run.h: RA), for every run whose step count spicey_ready_steps_ok accepts: spicey_ready_run
   bool lds = true;       // workspace in LDS (else global memory)
   size_t lds_bytes = 0;
   int64_t algo_bytes = 0;
@@ -130,6 +133,9 @@ struct LaunchPlan {
 // 16-bit interpreter, hres).
 int32_t spicey_plan(const SpiceyDesc *desc, const SpiceyOptions &opt, const SpiceyKnobs &knobs, const PlanDevice &dev, HostProgram &hp,
                     HostResident &hres, LaunchPlan &plan, std::string &err);
+// whether a run of `steps` steps on a planned handle takes the ready-argument kernel: the plan said so and the per-step
+// offsets fit the 32 x 32 -> 64-bit product that kernel forms them with (tran_pt_layout.h); otherwise the operand-slot kernel
+bool spicey_ready_run(const LaunchPlan &plan, int64_t steps);
 // doubles of the parameter record SpiceyRun::zpar of a planned handle: five per resident item, NEL x T items per instance
 // (0: the plan runs a build without it)
 size_t spicey_zpar_doubles(const LaunchPlan &plan, const HostProgram &hp);

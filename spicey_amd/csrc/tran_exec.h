@@ -20,7 +20,7 @@
 //
 // The code lives in the pieces below, by layer; each includes what it uses, top to bottom:
 //   tran_common.h     SPICEY_HD, device / host macro pairs, phase tags, WgCtx, spicey_fresh, element models
-//   tran_pt_layout.h  where the phase table and the operand slots lie (plain arithmetic: the launch plan reads it too)
+//   tran_pt_layout.h  where the phase table and the operand slots lie, which step counts the ready arguments take (plain arithmetic: the launch plan reads it too)
 //   tran_pt.h         the phase table (run-invariant phase arguments in LDS)          <- common, pt_layout
 //   tran_v1_phases.h  diagnostics, TranPhases<K>                                      <- common
 //   tran_rec16.h      ResRegs, the 16-bit record interpreter, spicey_uk_phase         <- common, pt

@@ -48,6 +48,16 @@ SPICEY_HD X *spicey_pt_ptr(const uint32_t *pt, int i) {
   return (X *)(uintptr_t)spicey_pt_u64(pt, i);
 #endif
 }
+// (a 64-bit value as a pointer into global memory, the way spicey_pt_ptr makes one of two words)
+template <class X>
+SPICEY_HD X *spicey_global_ptr(uint64_t v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  typedef X __attribute__((address_space(1))) *gptr;
+  return (X *)(gptr)(uintptr_t)v;
+#else
+  return (X *)(uintptr_t)v;
+#endif
+}
 SPICEY_HD void spicey_pt_put64(uint32_t *pt, int i, uint64_t v) { pt[i] = (uint32_t)v; pt[i + 1] = (uint32_t)(v >> 32); }
 // (the three above: one word, read by every ACTIVE lane from the same address — for the rare reads inside divergent code)
 // Many words at a phase head, where the whole wave is active: lane l reads word l — ONE ds_read_b32, one vector register —
@@ -153,6 +163,44 @@ SPICEY_HD void spicey_pt_rebase_rows(const SpiceyProg &P, const SpiceyRun &R, co
   const double *b = cur ? R.out_i : R.out_v;
   const uint64_t a = b ? (uint64_t)(uintptr_t)(b + (size_t)c.inst[0] * (size_t)(R.steps + 1) * (size_t)(cur ? P.nCur : P.nOut)) : 0u;
   (c.tail + spicey_pt_base_words(P.pcr_n))[tid] = (uint32_t)(a >> (32 * (tid & 1)));
+}
+// Ready-argument builds (tran_v2_run.h: RA), behind the two above in the same phase: three more pointers become those of THIS
+// workgroup's instance, so that no phase multiplies the instance's share out again in 64-bit scalars —
+//   SPICEY_PT_ZPAR   the instance's parameter record, zpar + inst x `zrec` doubles (zrec = NEL x T x 5: TranPhases2::zpar_fill)
+//   SPICEY_PT_SRC    the instance's source table, src + inst x src_stride
+//   SPICEY_PT_ITERS  the instance's row of iteration counts, iters + inst x (steps + 1)
+// A null pointer stays null.  Only the hot readers below (spicey_pt_args_z / spicey_pt_args_early) and the lazy reads of
+// the same build see these words; what a cold branch takes from the complete structs in global memory is what it was.
+template <int K>
+SPICEY_HD void spicey_pt_rebase_ready(const SpiceyProg &P, const SpiceyRun &R, const WgCtx<K> &c, int tid, size_t zrec) {
+  static_assert(SPICEY_PT_ZPAR % 2 == 0 && SPICEY_PT_SRC % 2 == 0 && SPICEY_PT_ITERS % 2 == 0, "64-bit words of the table start at even indices");
+  const int w = tid & ~1;
+  if (w != SPICEY_PT_ZPAR && w != SPICEY_PT_SRC && w != SPICEY_PT_ITERS) return;
+  const size_t in = (size_t)c.inst[0];
+  uint64_t a;
+  if (w == SPICEY_PT_ZPAR) a = R.zpar ? (uint64_t)(uintptr_t)(R.zpar + in * zrec) : 0u;
+  else if (w == SPICEY_PT_SRC) a = R.src ? (uint64_t)(uintptr_t)(R.src + in * (size_t)R.src_stride) : 0u;
+  else a = R.iters ? (uint64_t)(uintptr_t)(R.iters + in * (size_t)(R.steps + 1)) : 0u;
+  (c.tail + spicey_pt_base_words(P.pcr_n))[tid] = (uint32_t)(a >> (32 * (tid & 1)));
+}
+// ... and what the always-executed code of these builds moves to scalars at a phase head.  Z (TranPhases2::z_record): the
+// four counts that bound resident items, nV / nL / nS, the width of a current row, the two row-0 result pointers and
+// the instance's iteration counts; whether this is the last step comes from the run loop's own scalars.  Everything else
+// that Z may touch — the end-state arrays of the last step, the record and the source table where nothing was
+// prefetched — is read where it is used, inside its branch (spicey_pt_ptr), and the beyond-capacity loops take the
+// complete structs as before.
+SPICEY_HD void spicey_pt_args_z(const SpiceyPtLanes &a, SpiceyProg &P, SpiceyRun &R) {
+  P.nR = (int32_t)a.u32(SPICEY_PT_NR); P.nC = (int32_t)a.u32(SPICEY_PT_NC); P.nD = (int32_t)a.u32(SPICEY_PT_ND); P.nOut = (int32_t)a.u32(SPICEY_PT_NOUT);
+  P.nV = (int32_t)a.u32(SPICEY_PT_NV); P.nL = (int32_t)a.u32(SPICEY_PT_NL); P.nS = (int32_t)a.u32(SPICEY_PT_NS); P.nCur = (int32_t)a.u32(SPICEY_PT_NCUR);
+  R.out_v = a.template ptr<double>(SPICEY_PT_OUT_V);
+  R.out_i = a.template ptr<double>(SPICEY_PT_OUT_I);
+  R.iters = a.template ptr<int32_t>(SPICEY_PT_ITERS);
+}
+// The early fetch (TranPhases2::z_early): the number of sources, the instance's record and its source table.
+SPICEY_HD void spicey_pt_args_early(const SpiceyPtLanes &a, SpiceyProg &P, SpiceyRun &R) {
+  P.nV = (int32_t)a.u32(SPICEY_PT_NV);
+  R.src = a.template ptr<const double>(SPICEY_PT_SRC);
+  R.zpar = a.template ptr<double>(SPICEY_PT_ZPAR);
 }
 // The fields that the always-executed code of B, Z and Z's parameter prefetch reads (TranPhases2, K = 1, LDS workspace), from
 // the table into two LOCAL structs; every other field stays zero and is never looked at there (TranPhases2::Pg).  What a

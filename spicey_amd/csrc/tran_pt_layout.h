@@ -38,3 +38,10 @@ SPICEY_LAYOUT_FN bool spicey_slots_fit(const SpiceyProg &P, int tail_n) {
   return !P.hybrid && spicey_pt_fits(P.pcr_n, P.pcr_level, tail_n) && spicey_pt_base_words(P.pcr_n) + spicey_pt_words(P.pcr_level) <= SPICEY_SLOT_TAIL_WORD &&
          spicey_slot_index(P) + 1 < 0xFFFFu && spicey_slot_index(P) + 1 - (uint32_t)P.nW <= 0x3FFFu;
 }
+// ---- ready arguments (ready-argument builds, tran_v2_run.h: RA) -----------------------------------------------------------
+// Such a build forms the per-step offsets step x nOut, step x nCur and (step + 1) x nV as ONE 32 x 32 -> 64-bit product of
+// the low words.  The row sizes are non-negative 32-bit counts; the product is exact as long as step + 1 fits 32 bits for
+// every step of the run, that is steps <= 2^32 - 2.  The step count is known per run, not per handle: the launch checks
+// it (spicey_abi.cpp: enqueue_kernel) and a run outside the condition takes the operand-slot kernel without ready arguments.
+#define SPICEY_READY_MAX_STEPS 0xFFFFFFFEll
+SPICEY_LAYOUT_FN bool spicey_ready_steps_ok(int64_t steps) { return steps >= 0 && steps <= SPICEY_READY_MAX_STEPS; }

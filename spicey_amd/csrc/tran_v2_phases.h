@@ -31,10 +31,17 @@
 // a resident stamp or right-hand-side descriptor names the -0.0 slot, so all operands of a thread's entries and rows are
 // read together, one LDS round trip instead of six dependent ones (dd_slots / rhs_slots below).  Everything that
 // decodes a descriptor from global memory (the beyond-capacity loops of B and Z, a_reiterate, z_lin_err) is unchanged.
-template <int K, int RMAX, int NSV, int NEL, bool HYB = false, bool EP = false, bool OS = false>
+// RA: the ready-argument build (an operand-slot build) — Z's head moves to scalars only what its always-executed code
+// reads (spicey_pt_args_z); the end-state arrays of the last step, and the record and the source table where nothing was
+// prefetched, are read from the table inside their own branch (`ptab`); the record and the source table are this instance's
+// already (spicey_pt_rebase_ready), so the early fetch loads with a scalar base and a 32-bit lane offset; the per-step
+// offsets step x row are one 32 x 32 -> 64-bit product (tran_pt_layout.h: spicey_ready_steps_ok).  Same values from the same
+// addresses in the same order as the OS build.
+template <int K, int RMAX, int NSV, int NEL, bool HYB = false, bool EP = false, bool OS = false, bool RA = false>
 struct TranPhases2 {
   static_assert(!EP || (K == 1 && !HYB), "the early prefetch is built for one instance per workgroup on the LDS workspace");
   static_assert(!OS || EP, "the operand slots are built into the early-prefetch kernels");
+  static_assert(!RA || OS, "the ready arguments are built into the operand-slot kernels");
   const SpiceyProg &P;
   const SpiceyRun &R;
   WgCtx<K> &c;
@@ -59,7 +66,7 @@ struct TranPhases2 {
   const SpiceyProg *Pg = nullptr;
   const SpiceyRun *Rg = nullptr;
   // fresh build, for u0_fetch: the phase table (null: none — then Qg, the resident struct where it lives, says where phase
-  // 0's records are)
+  // 0's records are); RA: Z's and the early fetch's lazy reads go there too
   const uint32_t *ptab = nullptr;
   const SpiceyResident *Qg = nullptr;
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -619,7 +626,7 @@ struct TranPhases2 {
     if (oi) SPICEY_STREAM_STORE(&oi[cC + i], gc * (dv - vprev));
     vprev = dv;
     c.u[(size_t)i * K + k] = gc * dv;
-    if (last) R.C_vprev[in * P.nC + i] = dv;
+    if (last) (RA ? spicey_pt_ptr<double>(ptab, SPICEY_PT_C_VPREV) : R.C_vprev)[in * P.nC + i] = dv;
   }
   SPICEY_HD void z_dio(int i, double vd, int k, size_t in, double is, double dp0, double dp1, double *oi, int cD, int oD, bool last) const {
     double gg, q, irec;
@@ -627,7 +634,7 @@ struct TranPhases2 {
     if (oi) SPICEY_STREAM_STORE(&oi[cD + i], irec);
     c.gd[(size_t)(P.nS + i) * K + k] = gg;
     c.u[(size_t)(oD + i) * K + k] = q;
-    if (last) R.D_vdprev[in * P.nD + i] = vd;
+    if (last) (RA ? spicey_pt_ptr<double>(ptab, SPICEY_PT_D_VDPREV) : R.D_vdprev)[in * P.nD + i] = vd;
   }
   // OS: slot `i` of a row section that starts at the wave-uniform `row` — a 32-bit lane BYTE offset on a base in scalars
   static SPICEY_HD double *row_at(double *row, int i) { return (double *)((char *)row + (uint32_t)i * 8u); }
@@ -636,7 +643,7 @@ struct TranPhases2 {
     if (sec) SPICEY_STREAM_STORE(row_at(sec, i), gc * (dv - vprev));
     vprev = dv;
     c.u[(size_t)i] = gc * dv;
-    if (last) R.C_vprev[in * P.nC + i] = dv;
+    if (last) (RA ? spicey_pt_ptr<double>(ptab, SPICEY_PT_C_VPREV) : R.C_vprev)[in * P.nC + i] = dv;
   }
   SPICEY_HD void z_dio_at(int i, double vd, size_t in, double is, double dp0, double dp1, double *sec, int oD, bool last) const {
     double gg, q, irec;
@@ -644,7 +651,7 @@ struct TranPhases2 {
     if (sec) SPICEY_STREAM_STORE(row_at(sec, i), irec);
     c.gd[(size_t)(P.nS + i)] = gg;
     c.u[(size_t)(oD + i)] = q;
-    if (last) R.D_vdprev[in * P.nD + i] = vd;
+    if (last) (RA ? spicey_pt_ptr<double>(ptab, SPICEY_PT_D_VDPREV) : R.D_vdprev)[in * P.nD + i] = vd;
   }
   // diagnostics pass of Z (SpiceyRun::lin_vd set; its own loop so that the production path carries no extra state):
   // |vd(x) - vd_lin| of this thread's diodes, and the new linearisation point
@@ -694,7 +701,27 @@ struct TranPhases2 {
     }
   }
   // one wave-uniform base per j and one 32-bit lane offset: 40 contiguous bytes per item, no bound test
-  SPICEY_HD void z_prefetch_rec(int tid, Regs &rr) const {
+  // (RA: `zrec` is this instance's record — spicey_pt_rebase_ready —, a scalar base that the loads take as such; item j
+  // starts j x T x 40 bytes behind it)
+  static SPICEY_HD uint32_t rec_offset(int tid) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __umul24((unsigned)tid, 40u);  // (tid < 2^24: a full-rate multiply, where the 32-bit one runs at a quarter)
+#else
+    return (uint32_t)tid * 40u;
+#endif
+  }
+  SPICEY_HD void z_prefetch_rec(int tid, Regs &rr, const double *zrec = nullptr) const {
+    if (RA) {
+      const uint32_t ob = rec_offset(tid);
+      for (int j = 0; j < NEL; j++) {
+        // (item j's base is formed in scalars and stays there: base + lane offset + constant is then one addressing mode)
+        uint64_t bj = (uint64_t)(uintptr_t)zrec + (uint64_t)j * (uint64_t)(uint32_t)T * 40u;
+        SPICEY_OPAQUE_S(bj);
+        const double *zp = (const double *)(spicey_global_ptr<const char>(bj) + ob);
+        for (int q = 0; q < 5; q++) rr.pf[j][q] = (SPICEY_EXP & 8) ? 0.0 : zp[q];
+      }
+      return;
+    }
     const uint32_t ob = (uint32_t)tid * 40u;  // (a BYTE offset of 32 bits: base in scalars + this + a constant is one addressing mode)
     for (int j = 0; j < NEL; j++) {
       const char *base = (const char *)(R.zpar + ((size_t)c.inst[0] * NEL + (size_t)j) * (size_t)T * 5);
@@ -704,6 +731,11 @@ struct TranPhases2 {
   }
   // the early fetch: Z's parameters and the next step's source value, with the backward phases to arrive in
   SPICEY_HD void z_early(int tid, int64_t step, Regs &rr) const {
+    if (RA) {  // (R.zpar, R.src: this instance's — spicey_pt_args_early)
+      z_prefetch_rec(tid, rr, R.zpar);
+      rr.srcn = z_src_fetch_at(tid, step, R.src);
+      return;
+    }
     z_prefetch_rec(tid, rr);
     rr.srcn = z_src_fetch(tid, step, (size_t)c.inst[0]);
   }
@@ -725,6 +757,12 @@ struct TranPhases2 {
   SPICEY_HD double z_src_fetch(int tid, int64_t step, size_t in) const {
     return (tid < P.nV && step != R.steps) ? R.src[in * R.src_stride + (size_t)(step + 1) * P.nV + tid] : 0.0;
   }
+  // RA: from the instance's own table `srcb`; (step + 1) x nV as one 32 x 32 -> 64-bit product (spicey_ready_steps_ok)
+  static SPICEY_HD uint64_t mul32(uint32_t a, uint32_t b) { return (uint64_t)a * (uint64_t)b; }
+  SPICEY_HD double z_src_fetch_at(int tid, int64_t step, const double *srcb) const {
+    const uint32_t nxt = (uint32_t)SPICEY_UNIFORM((int)((uint32_t)step + 1u));
+    return (tid < P.nV && step != R.steps) ? *row_at(const_cast<double *>(srcb) + mul32(nxt, (uint32_t)P.nV), tid) : 0.0;
+  }
   SPICEY_HD void z_src_park(int tid, double v) const {
     if (tid < P.nV) c.u[(size_t)(P.nC + P.nL + P.nV + P.nD + tid) * K] = v;
   }
@@ -734,6 +772,8 @@ struct TranPhases2 {
   }
   SPICEY_HD void z_record(int tid, int64_t step, Regs &rr, bool prefetched) const {
     const bool last = step == R.steps;
+    const uint32_t st32 = (uint32_t)SPICEY_UNIFORM((int)(uint32_t)step);  // (RA: the low word of the step, for the 32 x 32 -> 64-bit row offsets)
+    (void)st32;
     const int oL = P.nC, oV = P.nC + P.nL, oD = P.nC + P.nL + P.nV;
     const int cR = 0, cC = P.nR, cL = P.nR + P.nC, cV = cL + P.nL, cS = cV + P.nV, cD = cS + P.nS;
     // The instance loop is kept ROLLED here (one copy of the exp / store code, one instance's working set):
@@ -744,9 +784,9 @@ struct TranPhases2 {
       if (!vk) continue;
       const size_t in = (size_t)(K == 1 ? c.inst[0] : (k == 0 ? c.inst[0] : c.inst[K - 1]));
       // (OS: the table's two result pointers are this instance's row 0 already — spicey_pt_rebase_rows)
-      double *ov = R.out_v + ((OS ? 0 : in * (size_t)(R.steps + 1)) + (size_t)step) * P.nOut;
-      double *oi = R.out_i ? R.out_i + ((OS ? 0 : in * (size_t)(R.steps + 1)) + (size_t)step) * P.nCur : nullptr;
-      const double *g = R.gstat + in * P.nGstat;
+      double *ov = RA ? R.out_v + mul32(st32, (uint32_t)P.nOut) : R.out_v + ((OS ? 0 : in * (size_t)(R.steps + 1)) + (size_t)step) * P.nOut;
+      double *oi = R.out_i ? (RA ? R.out_i + mul32(st32, (uint32_t)P.nCur) : R.out_i + ((OS ? 0 : in * (size_t)(R.steps + 1)) + (size_t)step) * P.nCur) : nullptr;
+      const double *gh = RA ? nullptr : R.gstat + in * P.nGstat;  // (only the beyond-capacity loops read it: RA forms it there)
       if (DIAG && R.lin_vd) {  // diagnostics (wave-uniform): the step's one-shot linearisation error
         const double lerr = z_lin_err(tid, k, in);
         if (R.lin_err) spicey_lin_err_report(R, in, step, tid, lerr);
@@ -755,12 +795,13 @@ struct TranPhases2 {
       // Element parameters of the resident items come from L2: all their loads are issued together (one round
       // trip per step instead of one per element section), normally already during the last backward phase.
       if (!(K == 1 && prefetched)) {
-        if (EP) z_prefetch_rec(tid, rr);
+        if (RA) z_prefetch_rec(tid, rr, spicey_pt_ptr<const double>(ptab, SPICEY_PT_ZPAR));
+        else if (EP) z_prefetch_rec(tid, rr);
         else z_prefetch(tid, step, k, rr);
       }
       double pR[NEL], pC[NEL], pIs[NEL], pD0[NEL], pD1[NEL];
       for (int j = 0; j < NEL; j++) { pR[j] = rr.pf[j][0]; pC[j] = rr.pf[j][1]; pIs[j] = rr.pf[j][2]; pD0[j] = rr.pf[j][3]; pD1[j] = rr.pf[j][4]; }
-      double srcn = (K == 1 && prefetched) ? 0.0 : z_src_fetch(tid, step, in);
+      double srcn = (K == 1 && prefetched) ? 0.0 : RA ? z_src_fetch_at(tid, step, spicey_pt_ptr<const double>(ptab, SPICEY_PT_SRC)) : z_src_fetch(tid, step, in);
       // ... and all of them are WAITED for here, before the first result store is issued: gfx9 has one counter
       // (vmcnt) for loads and stores, which may complete out of order, so once a store is in flight a wait for any
       // load becomes vmcnt(0) = "until every result store has been acknowledged" (~1 us each time).
@@ -829,6 +870,7 @@ struct TranPhases2 {
       SPICEY_MARK(c, 3);
       if ((SPICEY_EXP & 32) || !zrem) continue;
       SPICEY_COLD_ARGS;
+      const double *g = RA ? R.gstat + in * P.nGstat : gh;
       if (HYB) {
         // (hybrid workspace: four items of every kind at a time — indices and parameters of all four in flight before the
         // first terminal voltage is read; the same arithmetic per item as the loops below)

@@ -136,11 +136,16 @@ struct SpiceyHasIdleWaves<E, decltype((void)E::idle_waves)> { static constexpr b
 // slots (tran_pt_layout.h), resolves ground in Z's resident terminal indices to the +0.0 slot and the empty fields of B's
 // resident descriptors to the -0.0 slot, and keeps the instance's row bases in the phase table; the caller has made sure
 // that spicey_slots_fit holds for the program (the launch plan; it implies a phase table, whose free tail the slots take).
-template <int K, int RMAX, int NSV, int NEL, bool HYB = false, int PT = -1, bool EP = false, bool OS = false, class Exec>
+// RA (the ready-argument build, TranPhases2): an operand-slot build whose prologue also makes the table's record, source and
+// iteration-count pointers this instance's own (spicey_pt_rebase_ready), whose Z and early fetch move only their hot
+// arguments to scalars (spicey_pt_args_z / spicey_pt_args_early; the last-step test comes from `steps` below) and read the
+// rest inside the branch that needs it; the caller has made sure that spicey_ready_steps_ok holds for the run.
+template <int K, int RMAX, int NSV, int NEL, bool HYB = false, int PT = -1, bool EP = false, bool OS = false, bool RA = false, class Exec>
 SPICEY_HD void spicey_tran_run_v2(Exec &ex, const SpiceyProg &P, const SpiceyResident &Q, const SpiceyRun &R, WgCtx<K> &c, int wg) {
   const int T = ex.threads();
   static_assert(!OS || PT != 0, "the operand slots lie behind the phase table");
-  typedef TranPhases2<K, RMAX, NSV, NEL, HYB, EP, OS> Ph2;
+  static_assert(!RA || OS, "the ready arguments are a form of the operand-slot build");
+  typedef TranPhases2<K, RMAX, NSV, NEL, HYB, EP, OS, RA> Ph2;
   uint32_t brem, zrem;
   {
     Ph2 p2{P, R, c, T, 0u, 0u};
@@ -151,7 +156,7 @@ SPICEY_HD void spicey_tran_run_v2(Exec &ex, const SpiceyProg &P, const SpiceyRes
   // the phase table: tridiagonal-top builds whose rows fit behind the top's index table (wave-uniform, fixed for the run)
   static_assert(PT <= 0 || K == 1, "the phase table is built for one instance per workgroup");
   const bool pt_run = PT >= 0 ? PT == 1 : (K == 1 && spicey_pt_runtime_choice(P, Q));
-  if (pt_run) ex.phase(SPICEY_PH_PRO, [&](int tid) { spicey_pt_build<K>(P, Q, R, c, tid, T, EP); if (OS) spicey_pt_rebase_rows<K>(P, R, c, tid); });  // (the structs where they live: see there)
+  if (pt_run) ex.phase(SPICEY_PH_PRO, [&](int tid) { spicey_pt_build<K>(P, Q, R, c, tid, T, EP); if (OS) spicey_pt_rebase_rows<K>(P, R, c, tid); if (RA) spicey_pt_rebase_ready<K>(P, R, c, tid, (size_t)NEL * (size_t)T * 5); });  // (the structs where they live: see there)
   ex.phase(SPICEY_PH_PRO, [&](int tid) {
     const SpiceyProg Pf = ex.fresh(P); const SpiceyResident Qf = ex.fresh(Q); const SpiceyRun Rf = ex.fresh(R);
     TranPhases<K> ph{Pf, Rf, c, T};
@@ -257,6 +262,13 @@ SPICEY_HD void spicey_tran_run_v2(Exec &ex, const SpiceyProg &P, const SpiceyRes
         if (!z_early) {
           Ph2 p2{P, R, c, T, brem, zrem};
           p2.z_early_none(ex.template regs<Regs>(tid));
+        } else if (RA && pt_bz) {
+          SpiceyProg Pt{};
+          SpiceyRun Rt{};
+          spicey_pt_args_early(SpiceyPtLanes::run_block(ptw, tid), Pt, Rt);
+          Rt.steps = steps;
+          Ph2 p2{Pt, Rt, c, T, brem, zrem, &P, &R, ptw};
+          p2.z_early(tid, step, ex.template regs<Regs>(tid));
         } else if (pt_bz) {
           SpiceyProg Pt{};
           SpiceyRun Rt{};
@@ -403,7 +415,17 @@ SPICEY_HD void spicey_tran_run_v2(Exec &ex, const SpiceyProg &P, const SpiceyRes
       solves += (unsigned long long)(iter + 1) * (unsigned long long)nvalid;
     }
     ex.phase(SPICEY_PH_Z, [&](int tid) {
-      if (!HYB && (PT >= 0 ? PT == 1 : ((top_pack >> 20) & 1) != 0)) {
+      if (RA && !HYB && (PT >= 0 ? PT == 1 : ((top_pack >> 20) & 1) != 0)) {
+        const uint32_t *ptz = c.tail + spicey_pt_base_words(top_pack & 0xff);
+        SpiceyProg Pt{};
+        SpiceyRun Rt{};
+        spicey_pt_args_z(SpiceyPtLanes::run_block(ptz, tid), Pt, Rt);
+        Rt.steps = steps;
+        Ph2 p2{Pt, Rt, c, T, brem, zrem, &P, &R, ptz};
+        const uint32_t st32 = (uint32_t)SPICEY_UNIFORM((int)(uint32_t)step);
+        if (tid == 0 && Rt.iters && c.valid[0]) Rt.iters[st32] = iter + 1;  // (this instance's row: spicey_pt_rebase_ready)
+        p2.z_record(tid, step, ex.template regs<Regs>(tid), ((top_pack >> 16) & 1) != 0);
+      } else if (!HYB && (PT >= 0 ? PT == 1 : ((top_pack >> 20) & 1) != 0)) {
         SpiceyProg Pt{};
         SpiceyRun Rt{};
         spicey_pt_args(c.tail + spicey_pt_base_words(top_pack & 0xff), tid, Pt, Rt);
