@@ -129,6 +129,50 @@ def series_diode_chain(seed: int, n: int) -> str:
     return "\n".join(lines)
 
 
+def rlc_mesh(rows: int, cols: int, seed: int) -> str:
+    """A rows x cols grid for the AC sweep: resistors along the rows, inductors and capacitors in turn along the columns, a
+    capacitor to ground on every node and a resistor to ground where (i + j) % 3 == 0; V1 (AC 1) from the corner to ground
+    and a floating V2 (AC 0.5 at 90 degrees) between the last two nodes of the last row, in place of that link's resistor.
+    A mesh fills in under elimination (task records with more than two products, streamed phases), its inductor entries
+    keep the per-stamp path, and the two sources give rows with and without a right-hand side."""
+    import math
+    rnd = random.Random(7000 + seed)
+
+    def val(lo, hi):
+        return f"{math.exp(rnd.uniform(math.log(lo), math.log(hi))):.6g}"
+
+    node = lambda i, j: f"g{i}_{j}"
+    lines = [f"* rlc_mesh {rows}x{cols} seed {seed}", f"V1 {node(0, 0)} 0 AC 1",
+             f"V2 {node(rows - 1, cols - 2)} {node(rows - 1, cols - 1)} AC 0.5 90"]
+    for i in range(rows):
+        for j in range(cols):
+            lines.append(f"CG{i}_{j} {node(i, j)} 0 {val(1e-10, 1e-8)}")
+            if (i + j) % 3 == 0:
+                lines.append(f"RG{i}_{j} {node(i, j)} 0 {val(1e2, 1e5)}")
+            if j + 1 < cols and (i, j) != (rows - 1, cols - 2):
+                lines.append(f"RH{i}_{j} {node(i, j)} {node(i, j + 1)} {val(10, 1e4)}")
+            if i + 1 < rows:
+                if (i + j) % 2 == 0:
+                    lines.append(f"LV{i}_{j} {node(i, j)} {node(i + 1, j)} {val(1e-6, 1e-3)}")
+                else:
+                    lines.append(f"CV{i}_{j} {node(i, j)} {node(i + 1, j)} {val(1e-10, 1e-8)}")
+    lines += [".ac dec 2 1e2 1e8", ".end", ""]
+    return "\n".join(lines)
+
+
+def fed_ladder(n: int, at: int) -> str:
+    """An R-C ladder of n nodes driven at node `at` instead of at its end: the fixed pivot order then eliminates the
+    source's rows late (fed_ladder(68, 47): the branch equation is row 64 of 69), which puts the one row with a right-hand
+    side beyond the first 64 rows of a 64-thread workgroup."""
+    lines = [f"* ladder of {n} fed at {at}", f"V1 c{at} 0 AC 1 30"]
+    for k in range(n):
+        lines.append(f"C{k} c{k} 0 {1e-9 * (1 + 0.03 * k)!r}")
+        if k + 1 < n:
+            lines.append(f"R{k} c{k} c{k + 1} {100.0 * (1 + 0.05 * (k % 7))!r}")
+    lines += ["RE0 c0 0 1000.0", f"RE1 c{n - 1} 0 2200.0", ".ac dec 2 1e2 1e8", ".end", ""]
+    return "\n".join(lines)
+
+
 def series_rlc_ladder(stages: int, r: float = 10.0, l: float = 1e-3, c: float = 1e-6) -> str:
     """R - L - C stages in series: the node between L and C carries 1/(jwL) + jwC, which cancels at f0 = 1/(2 pi sqrt(LC)).
     The reference's partial pivoting takes another row there; a static diagonal pivot order divides by ~0."""

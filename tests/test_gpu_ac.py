@@ -135,8 +135,10 @@ def test_ac_resonance_dense_fallback_on_gpu(oracle_backend):
     """A series L - C node cancels at its resonance: the static pivot order hits ~0 there, the reference's partial
     pivoting does not.  The HIP path repeats exactly those (instance, frequency) solves with dense partial pivoting
     (`spicey_ac_dense_kernel`) and matches the reference at, next to and away from the resonance — in a batch whose other
-    instances resonate elsewhere, through both sweep kernels; with the fallback switched off the sweep fails; what is
-    singular for the reference stays singular."""
+    instances resonate elsewhere; with the fallback switched off the sweep fails; what is singular for the reference stays
+    singular.  Its 4 x 8 = 32 slots do not outnumber the CUs, so every handle here runs the per-solve kernel (`interpreter`
+    1), from LDS and from the global workspace; the dense fallback behind the resident sweep is
+    test_ac_resident_gpu.py::test_workgroup_goes_on_after_a_failed_frequency_and_dense_fallback."""
     import math
     from random_circuits import series_rlc_ladder
     from spicey_amd.lib import AcHandle
@@ -150,9 +152,10 @@ def test_ac_resonance_dense_fallback_on_gpu(oracle_backend):
     for kw in (dict(), dict(no_resident=True), dict(force_global=True)):
         h = AcHandle(flat, **kw)
         got = h.run(freqs, vph)
-        n_dense = h.info()["tail_levels"]
+        n_dense, mode = h.info()["tail_levels"], h.info()["interpreter"]
         h.close()
         assert got["status"] == 0, got["detail"]
+        assert mode == 1, kw
         assert 4 <= n_dense <= 8                       # instance 0 next to f0 (4-5 points), instance 1 at its own resonance
         assert cratio(got["out_v"], ref["out_v"]).max() <= 1.0 and cratio(got["out_i"], ref["out_i"]).max() <= 1.0
     h = AcHandle(flat, no_dense=True)
