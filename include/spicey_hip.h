@@ -164,6 +164,9 @@ typedef struct SpiceyInfo {
   int32_t pcr_level;        /* first elimination-tree level of that top */
   int32_t hybrid_entries;   /* interpreter 2, hybrid workspace: entries of L+U (those the leaves of the elimination tree own) kept in
                                global memory because the whole L+U does not fit the LDS of one CU; 0 = everything in LDS */
+  int32_t operand_addr;     /* interpreter 2: 1 = the runs of this handle that take the ready-argument kernel take its operand-address
+                               form (LDS operands addressed in one instruction: the packed fresh shape, a program whose descriptor
+                               fields hold indices from the start of the workspace, SPICEY_NO_OPERAND_ADDR not set); 0 = no such form */
 } SpiceyInfo;
 
 typedef struct SpiceyHandle SpiceyHandle;

@@ -47,7 +47,7 @@ static const SpiceyV2Shape &v2_build(int threads, bool packed = false, bool hybr
 SpiceyKnobs spicey_read_knobs() {
   const char *ms = getenv("SPICEY_GROUP_TIMEOUT_MS");
   return {getenv("SPICEY_NO_HYBRID") != nullptr, getenv("SPICEY_FRONT_RIGHT_LOOKING") != nullptr, getenv("SPICEY_TEST_FORCE_GROUP_ABORT") != nullptr,
-          ms ? atoi(ms) : 0, getenv("SPICEY_NO_PHASE_TABLE") != nullptr, getenv("SPICEY_NO_FRESH_FILL") != nullptr, getenv("SPICEY_FRESH_FILL_LINEAR") != nullptr, getenv("SPICEY_NO_EARLY_PREFETCH") != nullptr, getenv("SPICEY_NO_OPERAND_SLOTS") != nullptr, getenv("SPICEY_NO_READY_ARGS") != nullptr};
+          ms ? atoi(ms) : 0, getenv("SPICEY_NO_PHASE_TABLE") != nullptr, getenv("SPICEY_NO_FRESH_FILL") != nullptr, getenv("SPICEY_FRESH_FILL_LINEAR") != nullptr, getenv("SPICEY_NO_EARLY_PREFETCH") != nullptr, getenv("SPICEY_NO_OPERAND_SLOTS") != nullptr, getenv("SPICEY_NO_READY_ARGS") != nullptr, getenv("SPICEY_NO_OPERAND_ADDR") != nullptr};
 }
 
 static int pick_threads(const HostProgram &hp, bool v2) {
@@ -295,6 +295,9 @@ int32_t spicey_plan(const SpiceyDesc *desc, const SpiceyOptions &opt, const Spic
     // (its operand-slot form needs the phase table and four free words behind it, within reach of a 16-bit index)
     plan.slots = plan.early && SPICEY_V2_SHAPES[shape].slots && !knobs.no_operand_slots && !knobs.no_phase_table && spicey_slots_fit(hp.hdr, hres.tail_n);
     plan.ready = plan.slots && SPICEY_V2_SHAPES[shape].ready && !knobs.no_ready_args;
+    // (operand addresses: c.W must be LDS address 0 — one instance per workgroup on the LDS workspace, no hybrid layout — and
+    // the re-encoded descriptor fields must hold the largest index, tran_pt_layout.h)
+    plan.addr = spicey_plan_addr(hp.hdr, hres.tail_n, K, plan.lds, shape, knobs);
   }
   if (!plan.lds) {
     // group mode: several CUs per instance when the batch leaves CUs idle and the circuit is large enough for the
@@ -327,7 +330,12 @@ int32_t spicey_plan(const SpiceyDesc *desc, const SpiceyOptions &opt, const Spic
   return SPICEY_OK;
 }
 
+bool spicey_plan_addr(const SpiceyProg &P, int tail_n, int K, bool lds, int shape, const SpiceyKnobs &knobs) {
+  return K == 1 && lds && shape >= 0 && shape < SPICEY_V2_NSHAPES && SPICEY_V2_SHAPES[shape].addr && !SPICEY_V2_SHAPES[shape].hybrid && !P.hybrid &&
+         !knobs.no_operand_addr && spicey_addr_fits(P, tail_n);
+}
 bool spicey_ready_run(const LaunchPlan &plan, int64_t steps) { return plan.slots && plan.ready && spicey_ready_steps_ok(steps); }
+bool spicey_addr_run(const LaunchPlan &plan, int64_t steps) { return plan.addr && spicey_ready_run(plan, steps); }
 
 size_t spicey_zpar_doubles(const LaunchPlan &plan, const HostProgram &hp) {
   if (!plan.early || plan.interp != 2) return 0;
@@ -377,4 +385,5 @@ void fill_info(const LaunchPlan &plan, const HostProgram &hp, const HostResident
   info->pcr_rows = (plan.interp == 2 && plan.K == 1) ? P.pcr_n : 0;
   info->pcr_level = info->pcr_rows ? P.pcr_level : 0;
   info->hybrid_entries = P.hybrid ? P.hyb_g0 + P.hyb_g2 : 0;
+  info->operand_addr = (plan.interp == 2 && plan.addr) ? 1 : 0;
 }

@@ -46,11 +46,12 @@ struct SpiceyV2Shape {
   bool early = false;  // the shape also has early-prefetch kernels (tran_v2_run.h: EP), which a handle takes unless SPICEY_NO_EARLY_PREFETCH is set
   bool slots = false;  // ... and an operand-slot kernel (tran_v2_phases.h: OS), taken where the slots fit unless SPICEY_NO_OPERAND_SLOTS is set
   bool ready = false;  // ... and that kernel's ready-argument form (tran_v2_run.h: RA), taken by an operand-slot run unless SPICEY_NO_READY_ARGS is set
+  bool addr = false;   // ... and that form with operand addresses (tran_v2_run.h: OA), taken by a ready-argument run where spicey_addr_fits holds unless SPICEY_NO_OPERAND_ADDR is set
 };
 // `early`: Z's element parameters come from one record per thread (SpiceyRun::zpar) and are fetched, with the next source
 // value, at the tail of the last factor phase.  The fresh packed build has it; the other builds were left as they are.
 // (spicey_launch_tran_v2 instantiates one kernel per entry; each kind in ascending threads)
-constexpr SpiceyV2Shape SPICEY_V2_SHAPES[] = {{true, false, 512, 4, 6, 2, 4},    {true, false, 512, 4, 2, 2, 4, true, true, true, true},
+constexpr SpiceyV2Shape SPICEY_V2_SHAPES[] = {{true, false, 512, 4, 6, 2, 4},    {true, false, 512, 4, 2, 2, 4, true, true, true, true, true},
                                               {false, true, 512, 16, 8, 2, 2},   {false, true, 1024, 4, 4, 1, 4},
                                               {false, false, 256, SPICEY_V2_RMAX256, 12, 4, 1},
                                               {false, false, 512, 16, 8, 2, 2},  {false, false, 1024, 8, 4, 1, 4}};
@@ -70,6 +71,7 @@ struct SpiceyKnobs {
   bool no_early_prefetch = false;    // SPICEY_NO_EARLY_PREFETCH: a shape with early-prefetch kernels keeps its plain build and the handle no parameter record (the in-library A/B switch)
   bool no_operand_slots = false;     // SPICEY_NO_OPERAND_SLOTS: an early-prefetch run keeps the kernel that masks ground by compare and select and writes no slot (the in-library A/B switch)
   bool no_ready_args = false;        // SPICEY_NO_READY_ARGS: an operand-slot run keeps the kernel that moves all of Z's arguments to scalars at the phase head (the in-library A/B switch)
+  bool no_operand_addr = false;      // SPICEY_NO_OPERAND_ADDR: a ready-argument run keeps the kernel that addresses its LDS operands as W[field] (the in-library A/B switch)
 };
 SpiceyKnobs spicey_read_knobs();
 
@@ -123,6 +125,11 @@ struct LaunchPlan {
   bool early = false;    // the run takes the shape's early-prefetch kernel: the handle owns a parameter record (spicey_zpar_doubles)
   bool slots = false;    // ... in its operand-slot form: the two constants of tran_pt.h (spicey_slot_index) fit behind the phase table
   bool ready = false;    // ... with ready arguments (tran_v2_run.h: RA), for every run whose step count spicey_ready_steps_ok accepts: spicey_ready_run
+  // the shape has an operand-address kernel (tran_v2_run.h: OA) and the program meets its conditions — K = 1, LDS workspace,
+  // no hybrid layout, spicey_addr_fits — and SPICEY_NO_OPERAND_ADDR is not set: every ready-argument run of the handle takes
+  // that kernel (spicey_addr_run).  A property of the program and its shape: the knobs of the forms below it (phase table,
+  // early prefetch, operand slots, ready arguments) decide whether a ready-argument run happens, not this flag.
+  bool addr = false;
   bool lds = true;       // workspace in LDS (else global memory)
   size_t lds_bytes = 0;
   int64_t algo_bytes = 0;
@@ -136,6 +143,11 @@ int32_t spicey_plan(const SpiceyDesc *desc, const SpiceyOptions &opt, const Spic
 // whether a run of `steps` steps on a planned handle takes the ready-argument kernel: the plan said so and the per-step
 // offsets fit the 32 x 32 -> 64-bit product that kernel forms them with (tran_pt_layout.h); otherwise the operand-slot kernel
 bool spicey_ready_run(const LaunchPlan &plan, int64_t steps);
+// LaunchPlan::addr of a program with header `P` and `tail_n` tail levels on build `shape` (an index into SPICEY_V2_SHAPES,
+// < 0: none) at K instances per workgroup, workspace in LDS or not: what spicey_plan decides, as a function of its own
+bool spicey_plan_addr(const SpiceyProg &P, int tail_n, int K, bool lds, int shape, const SpiceyKnobs &knobs);
+// ... and whether that run takes the kernel's operand-address form: a ready-argument run of a plan that says `addr`
+bool spicey_addr_run(const LaunchPlan &plan, int64_t steps);
 // doubles of the parameter record SpiceyRun::zpar of a planned handle: five per resident item, NEL x T items per instance
 // (0: the plan runs a build without it)
 size_t spicey_zpar_doubles(const LaunchPlan &plan, const HostProgram &hp);

@@ -353,7 +353,7 @@ static int32_t enqueue_kernel(SpiceyHandle *h, const SpiceyRun &R, hipStream_t s
   if (h->plan.interp == 3) {
     HIPCHK(h, spicey_launch_exact(h->d_xprog, h->d_Rstruct, h->plan.grid, h->plan.T, h->plan.lds ? h->plan.lds_bytes : 0, st));
   } else if (h->plan.interp == 2) {
-    HIPCHK(h, spicey_launch_tran_v2(h->dprog, h->dres, h->d_Pstruct, h->d_Qstruct, h->d_Rstruct, h->plan.K, h->plan.grid, h->plan.T, st, h->plan.packed, !h->knobs.no_phase_table, h->d_zpar != nullptr, h->plan.slots, spicey_ready_run(h->plan, R.steps)));
+    HIPCHK(h, spicey_launch_tran_v2(h->dprog, h->dres, h->d_Pstruct, h->d_Qstruct, h->d_Rstruct, h->plan.K, h->plan.grid, h->plan.T, st, h->plan.packed, !h->knobs.no_phase_table, h->d_zpar != nullptr, h->plan.slots, spicey_ready_run(h->plan, R.steps), spicey_addr_run(h->plan, R.steps)));
   } else if (group) {
     HIPCHK(h, spicey_launch_tran_grp(h->dprog, R, h->plan.K, h->plan.grid, h->plan.T, st));
   } else {
@@ -542,6 +542,10 @@ extern "C" int32_t spicey_sync(SpiceyHandle *h) {
   }
   // (the text of an aborted attempt stays readable although its repetition went through)
   if (!aborted.empty() && best < 0) h->err = "recovered: " + aborted;
+  if (best >= 0 && status[(size_t)best * 4] == 2) {  // (an operand-address kernel refused to run: kernels.hip, SPICEY_KERNEL_OA)
+    h->err = "internal: the operand-address kernel found its workspace away from LDS offset 0 (SPICEY_NO_OPERAND_ADDR selects the kernel without that condition)";
+    return SPICEY_ERR_HIP;
+  }
   if (best >= 0) {
     char buf[160];
     snprintf(buf, sizeof(buf), "singular at inst %d step %d iter %d", status[(size_t)best * 4 + 1], status[(size_t)best * 4 + 2],

@@ -118,6 +118,62 @@ struct WgCtx {
   int32_t valid[K];
 };
 
+// ---- operand handles (operand-address builds, tran_v2_run.h: OA) ------------------------------------------------------------
+// "The double whose index from the start of the workspace is the 16-bit half H of word w."  Through `W[field]` the GPU
+// forms its LDS address with two vector instructions — extract the half, then (index << 3) + base, a three-operand add
+// even where the base is the constant 0 — in front of every ds_read_b64 of the interpreter.  An OA build states that
+// c.W IS LDS address 0 (K = 1, LDS workspace, the dynamic array is the kernel's only LDS object: spicey_tran_kernel_v2
+// checks it once) and forms the byte address from the half in ONE instruction, a shift that selects its source half
+// (SDWA); reads and writes of the same operand share the register.  A handle is an opaque 32-bit value: the LDS byte
+// address in an OA device build, the index itself everywhere else (host code and every other build read W[index * K + k],
+// as ever).  index(i): the handle of an index that was computed, not extracted.
+template <bool OA>
+struct SpiceyOperand {
+#if defined(__HIP_DEVICE_COMPILE__)
+  static constexpr bool LDS0 = OA;
+#else
+  static constexpr bool LDS0 = false;
+#endif
+  template <int H>
+  static SPICEY_HD uint32_t half(uint32_t w) {
+    static_assert(H == 0 || H == 1, "a word has two halves");
+#if defined(__HIP_DEVICE_COMPILE__)
+    if constexpr (LDS0) {
+      // (One shift that selects its source half.  hipcc finds it by itself for the upper half, `(w >> 16) << 3`, but with the
+      // shift count in a vector register that then stays live around the whole time loop; for the lower half every C++
+      // spelling gives a shift and a mask with 0x7fff8.  Written out, the count is an inline constant.  Registers in,
+      // register out: nothing else)
+      uint32_t a;
+      if (H == 1) asm("v_lshlrev_b32_sdwa %0, 3, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_1" : "=v"(a) : "v"(w));
+      else asm("v_lshlrev_b32_sdwa %0, 3, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_0" : "=v"(a) : "v"(w));
+      return a;
+    }
+#endif
+    return H ? w >> 16 : w & 0xffffu;
+  }
+  static SPICEY_HD uint32_t index(uint32_t i) { return LDS0 ? i << 3 : i; }
+  template <int K>
+  static SPICEY_HD double ld(const double *W, uint32_t a, int k) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    if constexpr (LDS0) {
+      static_assert(!OA || K == 1, "operand addresses: one instance per workgroup");
+      return *(const double __attribute__((address_space(3))) *)(uintptr_t)a;
+    }
+#endif
+    return W[(size_t)a * K + k];
+  }
+  template <int K>
+  static SPICEY_HD void st(double *W, uint32_t a, int k, double v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    if constexpr (LDS0) {
+      *(double __attribute__((address_space(3))) *)(uintptr_t)a = v;
+      return;
+    }
+#endif
+    W[(size_t)a * K + k] = v;
+  }
+};
+
 // A copy of an argument struct that lives in global memory, through an address the compiler cannot trace back: the fields
 // the surrounding code uses are scalar-loaded HERE (s_load, scalar cache), the rest of the copy is dead (see GpuExecV2::fresh).
 // On the host (the emulator) it is the struct itself.

@@ -45,3 +45,14 @@ SPICEY_LAYOUT_FN bool spicey_slots_fit(const SpiceyProg &P, int tail_n) {
 // it (spicey_abi.cpp: enqueue_kernel) and a run outside the condition takes the operand-slot kernel without ready arguments.
 #define SPICEY_READY_MAX_STEPS 0xFFFFFFFEll
 SPICEY_LAYOUT_FN bool spicey_ready_steps_ok(int64_t steps) { return steps >= 0 && steps <= SPICEY_READY_MAX_STEPS; }
+// ---- operand addresses (operand-address builds, tran_v2_run.h: OA) ---------------------------------------------------------
+// Such a build takes c.W for LDS address 0 (K = 1, LDS workspace, no hybrid layout: the dynamic array is the kernel's only
+// LDS object) and re-encodes the fields of B's resident descriptors — 14 bits each, indices into c.gd / c.u in the
+// operand-slot build — as indices from the start of W (TranPhases2::dd_addr / rhs_addr).  The largest index any field then
+// names is the -0.0 slot's, spicey_slot_index + 1, in dd and rhs alike: 14 bits must hold it.  A program beyond that keeps
+// the ready-argument kernel without operand addresses (spicey_plan).
+#define SPICEY_ADDR_FIELD_MAX 0x3FFFu
+SPICEY_LAYOUT_FN uint32_t spicey_addr_max_index(const SpiceyProg &P) { return spicey_slot_index(P) + 1u; }
+SPICEY_LAYOUT_FN bool spicey_addr_fits(const SpiceyProg &P, int tail_n) {
+  return !P.hybrid && spicey_slots_fit(P, tail_n) && spicey_addr_max_index(P) <= SPICEY_ADDR_FIELD_MAX;
+}

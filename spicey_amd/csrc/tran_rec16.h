@@ -71,12 +71,17 @@ struct ResRegs {
 // without one fetches nothing for it.
 // FRESH (fresh-fill builds): a factor task flagged SPICEY_R16_FRESH creates its target — it starts from 0.0 and does not
 // read it (the entry's static value IS 0.0, so the fma chain and its bits are those of the unflagged task).
-template <int K, bool KTASK, bool OPG = false, bool FRESH = false, class OV>
+// OA (operand-address builds, tran_common.h: SpiceyOperand): the operands of the inline case and the target are named by
+// handles — one instruction from the record word to the LDS address, the target's shared by its read and its write.
+template <int K, bool KTASK, bool OPG = false, bool FRESH = false, bool OA = false, class OV>
 SPICEY_HD void spicey_exec_rec16(const WgCtx<K> &c, OV ovf, uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3,
                                  uint32_t keep_from = 0u, uint32_t xoff = 0u) {
+  static_assert(!OA || !OPG, "operand addresses: everything lives in the LDS workspace");
+  typedef SpiceyOperand<OA> Op;
   const uint32_t meta = w0 >> 16;
   if (!(meta & (SPICEY_R16_VALID << 8))) return;
   const uint32_t tgt = w0 & 0xffffu, cnt = meta & 0xffu;
+  const uint32_t tgt_a = OA ? Op::template half<0>(w0) : tgt;  // (the target's handle: one for its read and its write)
   // a reused factorisation (linear circuit, step > 0) runs only the right-hand-side column of the factor tasks:
   // keep_from = first right-hand-side index then, 0 otherwise
   if (!KTASK && tgt < keep_from) return;
@@ -85,16 +90,17 @@ SPICEY_HD void spicey_exec_rec16(const WgCtx<K> &c, OV ovf, uint32_t w0, uint32_
   if (KTASK) {
     const uint32_t d = w1 & 0xffffu;
     if (cnt <= 2) {
-      const uint32_t u0 = w1 >> 16, x0 = w2 & 0xffffu, u1 = w2 >> 16, x1 = w3 & 0xffffu;
+      const uint32_t u0 = Op::template half<1>(w1), x0 = Op::template half<0>(w2), u1 = Op::template half<1>(w2), x1 = Op::template half<0>(w3);
+      const uint32_t d_a = OA ? Op::template half<0>(w1) : d;
       const bool two = SPICEY_WAVE_ANY(cnt == 2);  // tasks are sorted by count: most waves are uniform
       double a0[K], b0[K], a1[K], b1[K], dv[K];
       for (int k = 0; k < K; k++) {
-        acc[k] = c.W[(size_t)tgt * K + k];
-        a0[k] = E[(size_t)u0 * K + k]; b0[k] = c.W[(size_t)x0 * K + k];
-        dv[k] = E[(size_t)d * K + k];
+        acc[k] = Op::template ld<K>(c.W, tgt_a, k);
+        a0[k] = Op::template ld<K>(E, u0, k); b0[k] = Op::template ld<K>(c.W, x0, k);
+        dv[k] = Op::template ld<K>(E, d_a, k);
       }
       if (two)
-        for (int k = 0; k < K; k++) { a1[k] = E[(size_t)u1 * K + k]; b1[k] = c.W[(size_t)x1 * K + k]; }
+        for (int k = 0; k < K; k++) { a1[k] = Op::template ld<K>(E, u1, k); b1[k] = Op::template ld<K>(c.W, x1, k); }
       for (int k = 0; k < K; k++) {  // explicit fma: the same rounding in every interpreter and geometry
         const double s0 = fma(-a0[k], b0[k], acc[k]);
         acc[k] = cnt >= 1 ? s0 : acc[k];
@@ -105,7 +111,7 @@ SPICEY_HD void spicey_exec_rec16(const WgCtx<K> &c, OV ovf, uint32_t w0, uint32_
         acc[k] *= dv[k];
       }
     } else {
-      for (int k = 0; k < K; k++) acc[k] = c.W[(size_t)tgt * K + k];
+      for (int k = 0; k < K; k++) acc[k] = Op::template ld<K>(c.W, tgt_a, k);
       const uint16_t *o = ovf() + w3;
       for (uint32_t j = 0; j < cnt; j++) {
         const uint32_t u = o[2 * j], x = o[2 * j + 1];
@@ -113,26 +119,27 @@ SPICEY_HD void spicey_exec_rec16(const WgCtx<K> &c, OV ovf, uint32_t w0, uint32_
       }
       for (int k = 0; k < K; k++) acc[k] *= E[(size_t)d * K + k];
     }
-    for (int k = 0; k < K; k++) c.W[(size_t)tgt * K + k] = acc[k];
+    for (int k = 0; k < K; k++) Op::template st<K>(c.W, tgt_a, k, acc[k]);
   } else {
     // (hybrid: the third operand is an entry of the pivot's U row — global — for a matrix target, y_k — LDS — for a
     // right-hand-side target)
     const bool third_lds = !OPG || tgt >= xoff;
     const bool keep_old = !FRESH || !(meta & (SPICEY_R16_FRESH << 8));
     if (cnt <= 2) {
-      const uint32_t l0 = w1 & 0xffffu, d0 = w1 >> 16, u0 = w2 & 0xffffu, l1 = w2 >> 16, d1 = w3 & 0xffffu, u1 = w3 >> 16;
+      const uint32_t l0 = Op::template half<0>(w1), d0 = Op::template half<1>(w1), u0 = Op::template half<0>(w2);
+      const uint32_t l1 = Op::template half<1>(w2), d1 = Op::template half<0>(w3), u1 = Op::template half<1>(w3);
       const bool two = SPICEY_WAVE_ANY(cnt == 2);
       double p0[K], q0[K], r0[K], p1[K], q1[K], r1[K];
       for (int k = 0; k < K; k++) {
         acc[k] = 0.0;
-        if (keep_old) acc[k] = c.W[(size_t)tgt * K + k];
-        p0[k] = E[(size_t)l0 * K + k]; q0[k] = E[(size_t)d0 * K + k];
-        r0[k] = (!OPG || third_lds) ? c.W[(size_t)u0 * K + k] : c.G[(size_t)u0 * K + k];
+        if (keep_old) acc[k] = Op::template ld<K>(c.W, tgt_a, k);
+        p0[k] = Op::template ld<K>(E, l0, k); q0[k] = Op::template ld<K>(E, d0, k);
+        r0[k] = (!OPG || third_lds) ? Op::template ld<K>(c.W, u0, k) : c.G[(size_t)u0 * K + k];
       }
       if (two)
         for (int k = 0; k < K; k++) {
-          p1[k] = E[(size_t)l1 * K + k]; q1[k] = E[(size_t)d1 * K + k];
-          r1[k] = (!OPG || third_lds) ? c.W[(size_t)u1 * K + k] : c.G[(size_t)u1 * K + k];
+          p1[k] = Op::template ld<K>(E, l1, k); q1[k] = Op::template ld<K>(E, d1, k);
+          r1[k] = (!OPG || third_lds) ? Op::template ld<K>(c.W, u1, k) : c.G[(size_t)u1 * K + k];
         }
       for (int k = 0; k < K; k++) {
         const double s0 = fma(-(p0[k] * q0[k]), r0[k], acc[k]);
@@ -145,7 +152,7 @@ SPICEY_HD void spicey_exec_rec16(const WgCtx<K> &c, OV ovf, uint32_t w0, uint32_
     } else {
       for (int k = 0; k < K; k++) {
         acc[k] = 0.0;
-        if (keep_old) acc[k] = c.W[(size_t)tgt * K + k];
+        if (keep_old) acc[k] = Op::template ld<K>(c.W, tgt_a, k);
       }
       const uint16_t *o = ovf() + w3;
       for (uint32_t j = 0; j < cnt; j++) {
@@ -162,7 +169,7 @@ SPICEY_HD void spicey_exec_rec16(const WgCtx<K> &c, OV ovf, uint32_t w0, uint32_
         acc[k] = spicey_rcp(acc[k]);
       }
     }
-    for (int k = 0; k < K; k++) c.W[(size_t)tgt * K + k] = acc[k];
+    for (int k = 0; k < K; k++) Op::template st<K>(c.W, tgt_a, k, acc[k]);
   }
 }
 
@@ -170,43 +177,49 @@ SPICEY_HD void spicey_exec_rec16(const WgCtx<K> &c, OV ovf, uint32_t w0, uint32_
 // (at most two) pivots of this level, sharing the multipliers -(L_ik d_k).  The products and their order are those of the
 // generic tasks it stands for.  rhs_only: a reused factorisation updates y_i alone.
 // FRESH: a fill target flagged SPICEY_ROW_FRESH_* is created here — started from 0.0, not read.
-template <int K, bool OPG = false, bool FRESH = false>
+// OA: every operand by its handle (tran_common.h: SpiceyOperand) — 14 addresses, one instruction each; the four targets'
+// are shared by their reads and writes.
+template <int K, bool OPG = false, bool FRESH = false, bool OA = false>
 SPICEY_HD void spicey_exec_row16(const WgCtx<K> &c, const uint32_t *w, bool rhs_only) {
+  static_assert(!OA || !OPG, "operand addresses: everything lives in the LDS workspace");
+  typedef SpiceyOperand<OA> Op;
   const double *E = OPG ? c.G : c.W;  // (hybrid workspace: the pivots' own entries L_ik, d_k, U_ki, U_k,o come from the global array)
   const uint32_t meta = w[0] >> 16;
   if (!(meta & (SPICEY_R16_VALID << 8))) return;
-  const uint32_t iaa = w[0] & 0xffffu, iy = w[1] & 0xffffu;
-  const uint32_t l0 = w[1] >> 16, d0 = w[2] & 0xffffu, u0 = w[2] >> 16, y0 = w[3] & 0xffffu, f0 = w[3] >> 16, t0 = w[4] & 0xffffu;
-  const uint32_t l1 = w[4] >> 16, d1 = w[5] & 0xffffu, u1 = w[5] >> 16, y1 = w[6] & 0xffffu, f1 = w[6] >> 16, t1 = w[7] & 0xffffu;
+  const uint32_t iaa = Op::template half<0>(w[0]), iy = Op::template half<0>(w[1]);
+  const uint32_t l0 = Op::template half<1>(w[1]), d0 = Op::template half<0>(w[2]), u0 = Op::template half<1>(w[2]), y0 = Op::template half<0>(w[3]);
+  const uint32_t f0 = Op::template half<1>(w[3]), t0 = Op::template half<0>(w[4]);
+  const uint32_t l1 = Op::template half<1>(w[4]), d1 = Op::template half<0>(w[5]), u1 = Op::template half<1>(w[5]), y1 = Op::template half<0>(w[6]);
+  const uint32_t f1 = Op::template half<1>(w[6]), t1 = Op::template half<0>(w[7]);
   const bool two = (meta & 3u) == 2u, o0 = (meta >> 4) & 1u, o1 = (meta >> 5) & 1u;
   const bool new_aii = FRESH && (meta & SPICEY_ROW_FRESH_AII), new_t0 = FRESH && (meta & SPICEY_ROW_FRESH_O0), new_t1 = FRESH && (meta & SPICEY_ROW_FRESH_O1);
   for (int k = 0; k < K; k++) {
     // every operand in one LDS round trip (an unused second pivot / fill: index 0, a valid address; results masked)
     double aii = 0.0;
-    if (!new_aii) aii = c.W[(size_t)iaa * K + k];
-    double yi = c.W[(size_t)iy * K + k];
-    const double vl0 = E[(size_t)l0 * K + k], vd0 = E[(size_t)d0 * K + k], vy0 = c.W[(size_t)y0 * K + k], vu0 = E[(size_t)u0 * K + k];
-    const double vl1 = E[(size_t)l1 * K + k], vd1 = E[(size_t)d1 * K + k], vy1 = c.W[(size_t)y1 * K + k], vu1 = E[(size_t)u1 * K + k];
-    const double vf0 = E[(size_t)f0 * K + k];
+    if (!new_aii) aii = Op::template ld<K>(c.W, iaa, k);
+    double yi = Op::template ld<K>(c.W, iy, k);
+    const double vl0 = Op::template ld<K>(E, l0, k), vd0 = Op::template ld<K>(E, d0, k), vy0 = Op::template ld<K>(c.W, y0, k), vu0 = Op::template ld<K>(E, u0, k);
+    const double vl1 = Op::template ld<K>(E, l1, k), vd1 = Op::template ld<K>(E, d1, k), vy1 = Op::template ld<K>(c.W, y1, k), vu1 = Op::template ld<K>(E, u1, k);
+    const double vf0 = Op::template ld<K>(E, f0, k);
     double vt0 = 0.0, vt1 = 0.0;
-    if (!new_t0) vt0 = c.W[(size_t)t0 * K + k];
-    const double vf1 = E[(size_t)f1 * K + k];
-    if (!new_t1) vt1 = c.W[(size_t)t1 * K + k];
+    if (!new_t0) vt0 = Op::template ld<K>(c.W, t0, k);
+    const double vf1 = Op::template ld<K>(E, f1, k);
+    if (!new_t1) vt1 = Op::template ld<K>(c.W, t1, k);
     const double m0 = -(vl0 * vd0), m1 = -(vl1 * vd1);
     yi = fma(m0, vy0, yi);
     aii = fma(m0, vu0, aii);
     const double y2 = fma(m1, vy1, yi), a2 = fma(m1, vu1, aii);
     yi = two ? y2 : yi;
     aii = two ? a2 : aii;
-    c.W[(size_t)iy * K + k] = yi;
+    Op::template st<K>(c.W, iy, k, yi);
     if (!rhs_only) {
-      if (o0) c.W[(size_t)t0 * K + k] = fma(m0, vf0, vt0);
-      if (two && o1) c.W[(size_t)t1 * K + k] = fma(m1, vf1, vt1);
+      if (o0) Op::template st<K>(c.W, t0, k, fma(m0, vf0, vt0));
+      if (two && o1) Op::template st<K>(c.W, t1, k, fma(m1, vf1, vt1));
       if (meta & (SPICEY_R16_RECIP << 8)) {
         if (fabs(aii) < SPICEY_EPS && c.valid[k]) { c.flags[1] = 1; c.flags[2] = c.inst[k]; }
         aii = spicey_rcp(aii);
       }
-      c.W[(size_t)iaa * K + k] = aii;
+      Op::template st<K>(c.W, iaa, k, aii);
     }
   }
 }
@@ -264,7 +277,7 @@ struct SpiceyPt {
 
 // P, Q: the argument structs where they live (global memory on the GPU).  Nothing is fetched from them, or from the phase
 // table, before it is needed: a resident phase of tasks with at most two products reads no argument at all.
-template <int K, int RMAX, int NSV, int NEL, bool KTASK, bool OPG = false>
+template <int K, int RMAX, int NSV, int NEL, bool KTASK, bool OPG = false, bool OA = false>
 SPICEY_HD void spicey_uk_phase(const SpiceyProg &P, const SpiceyResident &Q, const SpiceyPt pt, const WgCtx<K> &c, ResRegs<K, RMAX, NSV, NEL> &rr, int tid,
                                int T, int p, bool streamed, bool reuse = false) {
   constexpr bool FRESH = SpiceyShapeKind<RMAX, NSV, NEL>::fresh;
@@ -286,9 +299,9 @@ SPICEY_HD void spicey_uk_phase(const SpiceyProg &P, const SpiceyResident &Q, con
         if (!KTASK && s + 1 < RMAX && SPICEY_UNIFORM((int)((rr.phv[(s + 1) >> 2] >> (((s + 1) & 3) * 8)) & 0xffu)) == 0xFE) {  // a chunk of row records: this slot + its continuation
           uint32_t w[8] = {w0, w1, w2, w3, rr.w0[s + 1 < RMAX ? s + 1 : s], rr.w1[s + 1 < RMAX ? s + 1 : s], rr.w2[s + 1 < RMAX ? s + 1 : s], rr.w3[s + 1 < RMAX ? s + 1 : s]};
           SPICEY_OPAQUE(w[4]); SPICEY_OPAQUE(w[5]); SPICEY_OPAQUE(w[6]); SPICEY_OPAQUE(w[7]);
-          spicey_exec_row16<K, OPG, FRESH>(c, w, reuse);
+          spicey_exec_row16<K, OPG, FRESH, OA>(c, w, reuse);
         } else {
-          spicey_exec_rec16<K, KTASK, OPG, FRESH>(c, ovf, w0, w1, w2, w3, keep_from, xoff);
+          spicey_exec_rec16<K, KTASK, OPG, FRESH, OA>(c, ovf, w0, w1, w2, w3, keep_from, xoff);
         }
       }
     }
@@ -305,10 +318,10 @@ SPICEY_HD void spicey_uk_phase(const SpiceyProg &P, const SpiceyResident &Q, con
       if (!KTASK && q + 1 < RMAX && SPICEY_UNIFORM((int)((rr.phv[(q + 1) >> 2] >> (((q + 1) & 3) * 8)) & 0xffu)) == 0xFE) {  // a chunk of row records: this slot + its continuation
         uint32_t w[8] = {w0, w1, w2, w3, rr.w0[q + 1], rr.w1[q + 1], rr.w2[q + 1], rr.w3[q + 1]};
         SPICEY_OPAQUE(w[4]); SPICEY_OPAQUE(w[5]); SPICEY_OPAQUE(w[6]); SPICEY_OPAQUE(w[7]);
-        spicey_exec_row16<K, OPG, FRESH>(c, w, reuse);
+        spicey_exec_row16<K, OPG, FRESH, OA>(c, w, reuse);
         q += 2;
       } else {
-        spicey_exec_rec16<K, KTASK, OPG, FRESH>(c, ovf, w0, w1, w2, w3, keep_from, xoff);
+        spicey_exec_rec16<K, KTASK, OPG, FRESH, OA>(c, ovf, w0, w1, w2, w3, keep_from, xoff);
         q++;
       }
     }
@@ -363,7 +376,7 @@ SPICEY_HD void spicey_uk_phase(const SpiceyProg &P, const SpiceyResident &Q, con
       // run-time test, not a second copy of the phase body: profiles/NOTES_r05.md §6)
       if (FRESH && p == 0 && j == (uint32_t)tid) for (int i = 0; i < 8; i++) w[i] = rr.u0[FRESH ? i : 0];
       else for (int i = 0; i < 8; i++) w[i] = pb[(size_t)j * 8 + i];
-      spicey_exec_row16<K, OPG, FRESH>(c, w, reuse);
+      spicey_exec_row16<K, OPG, FRESH, OA>(c, w, reuse);
     }
     base = fus16 + (size_t)d_rfirst * 4;
     sc = reuse ? d_rrhs : d_rcnt;
@@ -381,7 +394,7 @@ SPICEY_HD void spicey_uk_phase(const SpiceyProg &P, const SpiceyResident &Q, con
         const bool more = jn < sc;
         const uint32_t *rn = base + (size_t)(more ? jn : j) * 4;
         const uint32_t n0 = rn[0], n1 = rn[1], n2 = rn[2], n3 = rn[3];
-        spicey_exec_rec16<K, KTASK, OPG, FRESH>(c, ovf, c0, c1, c2, c3, keep_from, xoff);
+        spicey_exec_rec16<K, KTASK, OPG, FRESH, OA>(c, ovf, c0, c1, c2, c3, keep_from, xoff);
         if (!more) break;
         c0 = n0; c1 = n1; c2 = n2; c3 = n3;
         j = jn;

@@ -37,11 +37,19 @@
 // already (spicey_pt_rebase_ready), so the early fetch loads with a scalar base and a 32-bit lane offset; the per-step
 // offsets step x row are one 32 x 32 -> 64-bit product (tran_pt_layout.h: spicey_ready_steps_ok).  Same values from the same
 // addresses in the same order as the OS build.
-template <int K, int RMAX, int NSV, int NEL, bool HYB = false, bool EP = false, bool OS = false, bool RA = false>
+// OA: the operand-address build (a ready-argument build; tran_common.h: SpiceyOperand) — c.W is LDS address 0, and the
+// always-executed reads of Z's resident section name their operands by handles made of the terminal words' halves in one
+// instruction.  B's resident descriptors are re-encoded once more in the prologue (dd_addr / rhs_addr below): their fields
+// index c.gd and c.u, which lie behind W in the same array, and become indices from the start of W, so that no scalar
+// base stands in their addresses either; spicey_addr_fits has made sure that the fields hold the largest of them, the
+// -0.0 slot.  Same operands, same order, same arithmetic as the RA build.
+template <int K, int RMAX, int NSV, int NEL, bool HYB = false, bool EP = false, bool OS = false, bool RA = false, bool OA = false>
 struct TranPhases2 {
   static_assert(!EP || (K == 1 && !HYB), "the early prefetch is built for one instance per workgroup on the LDS workspace");
   static_assert(!OS || EP, "the operand slots are built into the early-prefetch kernels");
   static_assert(!RA || OS, "the ready arguments are built into the operand-slot kernels");
+  static_assert(!OA || (RA && K == 1 && !HYB), "the operand addresses are built into the ready-argument kernels: one instance per workgroup, LDS workspace");
+  typedef SpiceyOperand<OA> Op;
   const SpiceyProg &P;
   const SpiceyRun &R;
   WgCtx<K> &c;
@@ -109,8 +117,10 @@ struct TranPhases2 {
   SPICEY_HD double dv16(uint32_t ab, int k) const { return volt16(ab & 0xFFFFu, k) - volt16(ab >> 16, k); }
 
   // OS: a register-resident index (one 16-bit half; ground already names the +0.0 slot) and a pair of them
-  SPICEY_HD double volt_res(uint32_t xi) const { return c.W[(size_t)xi]; }
-  SPICEY_HD double dv_res(uint32_t ab) const { return volt_res(ab & 0xFFFFu) - volt_res(ab >> 16); }
+  // (through the half's handle: in an OA build one instruction from the word to the LDS address)
+  template <int H>
+  SPICEY_HD double volt_res(uint32_t ab) const { return Op::template ld<1>(c.W, Op::template half<H>(ab), 0); }
+  SPICEY_HD double dv_res(uint32_t ab) const { return volt_res<0>(ab) - volt_res<1>(ab); }
   static SPICEY_HD uint32_t slot_pair(uint32_t ab, uint32_t zs) {
     const uint32_t a = ab & 0xFFFFu, b = ab >> 16;
     return (a == 0xFFFFu ? zs : a) | ((b == 0xFFFFu ? zs : b) << 16);
@@ -137,6 +147,11 @@ struct TranPhases2 {
     d0 = g[0] | (g[1] << 16);
     d1 = g[2] | (g[3] << 16) | (mine ? 0u : 0x40000000u);
   }
+  // OA, behind the two above: every field of a resident descriptor names an operand by now, and each index moves from the
+  // start of c.gd / c.u to the start of W — `base` = nW + nU for dd, nW for rhs — in all fields at once (no carry leaves a
+  // field: spicey_addr_fits).  Flags and signs stay where they are.
+  static SPICEY_HD uint32_t dd_addr(uint32_t dd, uint32_t base) { return dd + base * ((1u << 15) | 1u); }
+  static SPICEY_HD void rhs_addr(uint32_t &d0, uint32_t &d1, uint32_t base) { d0 += base * 0x10001u; d1 += base * 0x10001u; }
   // g, or -g where bit 31 of `flip` is set (every other bit of it is ignored): x + this is x + g or, bit for bit, x - g
   static SPICEY_HD double signed_by(double g, uint32_t flip) {
     uint64_t b;
@@ -177,6 +192,7 @@ struct TranPhases2 {
         rr.eR[j] = slot_pair(rr.eR[j], zs); rr.eC[j] = slot_pair(rr.eC[j], zs); rr.eD[j] = slot_pair(rr.eD[j], zs);
         rr.ox[j] = rr.ox[j] == 0xFFFFu ? zs : rr.ox[j];  // (the upper half is still empty here)
         rhs_slots(rr.rhs[j][0], rr.rhs[j][1], zs + 1u - (uint32_t)P.nW);
+        if (OA) rhs_addr(rr.rhs[j][0], rr.rhs[j][1], (uint32_t)P.nW);
       }
       if (tid == 0) { c.W[(size_t)zs] = 0.0; c.W[(size_t)zs + 1] = -0.0; }
     }
@@ -189,6 +205,7 @@ struct TranPhases2 {
       const int e = tid + j * T;
       if (j < Regs::NDD) rr.dd[j] = e < n_stamped() ? P.ent_dd[e] : 0x80000000u;  // bit 31 = "not mine to stamp"
       if (OS && j < Regs::NDD) rr.dd[j] = dd_slots(rr.dd[j], spicey_slot_index(P) + 1u - (uint32_t)(P.nW + P.nU));
+      if (OA && j < Regs::NDD) rr.dd[j] = dd_addr(rr.dd[j], (uint32_t)(P.nW + P.nU));
       for (int k = 0; k < K; k++) rr.sv[j][k] = e < n_stamped() ? R.statv[(size_t)c.inst[k] * P.nLU + e] : 0.0;
     }
     for (int k = 0; k < K; k++) {  // entries that no phase ever writes: stamped once per run
@@ -450,6 +467,11 @@ struct TranPhases2 {
       for (int j = 0; j < Regs::NDD; j++) {
         uint32_t dd = rr.dd[j];
         SPICEY_OPAQUE(dd);
+        if (OA) {  // (indices from the start of W: dd_addr)
+          ga[j] = Op::template ld<1>(c.W, Op::index(dd & 0x3fffu), 0);
+          gb[j] = Op::template ld<1>(c.W, Op::index((dd >> 15) & 0x3fffu), 0);
+          continue;
+        }
         ga[j] = c.gd[(size_t)(dd & 0x3fffu)];
         gb[j] = c.gd[(size_t)((dd >> 15) & 0x3fffu)];
       }
@@ -554,6 +576,11 @@ struct TranPhases2 {
       for (int j = 0; j < NEL; j++) {
         uint32_t d0 = rr.rhs[j][0], d1 = rr.rhs[j][1];
         SPICEY_OPAQUE(d0); SPICEY_OPAQUE(d1);
+        if (OA) {  // (indices from the start of W: rhs_addr)
+          t[j][0] = Op::template ld<1>(c.W, Op::index(d0 & 0x3fffu), 0); t[j][1] = Op::template ld<1>(c.W, Op::index((d0 >> 16) & 0x3fffu), 0);
+          t[j][2] = Op::template ld<1>(c.W, Op::index(d1 & 0x3fffu), 0); t[j][3] = Op::template ld<1>(c.W, Op::index((d1 >> 16) & 0x3fffu), 0);
+          continue;
+        }
         t[j][0] = c.u[(size_t)(d0 & 0x3fffu)]; t[j][1] = c.u[(size_t)((d0 >> 16) & 0x3fffu)];
         t[j][2] = c.u[(size_t)(d1 & 0x3fffu)]; t[j][3] = c.u[(size_t)((d1 >> 16) & 0x3fffu)];
       }
@@ -637,7 +664,13 @@ struct TranPhases2 {
     if (last) (RA ? spicey_pt_ptr<double>(ptab, SPICEY_PT_D_VDPREV) : R.D_vdprev)[in * P.nD + i] = vd;
   }
   // OS: slot `i` of a row section that starts at the wave-uniform `row` — a 32-bit lane BYTE offset on a base in scalars
-  static SPICEY_HD double *row_at(double *row, int i) { return (double *)((char *)row + (uint32_t)i * 8u); }
+  // (OA: the offset is made opaque — where hipcc sees that it is tid x 8 it widens it to 64 bits and adds the base in vector
+  // registers, one v_lshl_add_u64 per store, instead of leaving the base to the store's scalar operand)
+  static SPICEY_HD double *row_at(double *row, int i) {
+    uint32_t ob = (uint32_t)i * 8u;
+    if (OA) SPICEY_OPAQUE(ob);
+    return (double *)((char *)row + ob);
+  }
   // ... and the same two element updates storing through it (`sec`: the element class's section of the current row, null: no currents wanted)
   SPICEY_HD void z_cap_at(int i, double dv, size_t in, double gc, double *sec, double &vprev, bool last) const {
     if (sec) SPICEY_STREAM_STORE(row_at(sec, i), gc * (dv - vprev));
@@ -811,7 +844,7 @@ struct TranPhases2 {
       if (tid < P.nV) {  // source tid: branch current out, next step's value in (read by the next B only)
         uint32_t vx = rr.ox[0];
         SPICEY_OPAQUE(vx);
-        if (oi) oi[cV + tid] = c.W[(size_t)(vx >> 16) * K + k];
+        if (oi) oi[cV + tid] = OA ? volt_res<1>(vx) : c.W[(size_t)(vx >> 16) * K + k];
         if (!last) c.u[(size_t)(oV + tid) * K + k] = (K == 1 && prefetched) ? c.u[(size_t)(oD + P.nD + tid) * K + k] : srcn;
       }
       SPICEY_SCHED_FENCE;
@@ -822,7 +855,7 @@ struct TranPhases2 {
         for (int j = 0; j < NEL; j++) {
           uint32_t ox = rr.ox[j], eR = rr.eR[j];
           SPICEY_OPAQUE(ox); SPICEY_OPAQUE(eR);
-          vo[j] = OS ? volt_res(ox & 0xFFFFu) : volt16(ox & 0xFFFFu, k);
+          vo[j] = OS ? volt_res<0>(ox) : volt16(ox & 0xFFFFu, k);
           dR[j] = OS ? dv_res(eR) : dv16(eR, k);
         }
         SPICEY_SCHED_FENCE;

@@ -140,12 +140,16 @@ struct SpiceyHasIdleWaves<E, decltype((void)E::idle_waves)> { static constexpr b
 // iteration-count pointers this instance's own (spicey_pt_rebase_ready), whose Z and early fetch move only their hot
 // arguments to scalars (spicey_pt_args_z / spicey_pt_args_early; the last-step test comes from `steps` below) and read the
 // rest inside the branch that needs it; the caller has made sure that spicey_ready_steps_ok holds for the run.
-template <int K, int RMAX, int NSV, int NEL, bool HYB = false, int PT = -1, bool EP = false, bool OS = false, bool RA = false, class Exec>
+// OA (the operand-address build, TranPhases2 / tran_common.h: SpiceyOperand): a ready-argument build that names the operands
+// of its always-executed LDS reads and writes — the interpreter's inline tasks and row records, Z's and B's resident
+// sections — by handles; the caller has made sure that c.W is LDS address 0 and that spicey_addr_fits holds.
+template <int K, int RMAX, int NSV, int NEL, bool HYB = false, int PT = -1, bool EP = false, bool OS = false, bool RA = false, bool OA = false, class Exec>
 SPICEY_HD void spicey_tran_run_v2(Exec &ex, const SpiceyProg &P, const SpiceyResident &Q, const SpiceyRun &R, WgCtx<K> &c, int wg) {
   const int T = ex.threads();
   static_assert(!OS || PT != 0, "the operand slots lie behind the phase table");
   static_assert(!RA || OS, "the ready arguments are a form of the operand-slot build");
-  typedef TranPhases2<K, RMAX, NSV, NEL, HYB, EP, OS, RA> Ph2;
+  static_assert(!OA || RA, "the operand addresses are a form of the ready-argument build");
+  typedef TranPhases2<K, RMAX, NSV, NEL, HYB, EP, OS, RA, OA> Ph2;
   uint32_t brem, zrem;
   {
     Ph2 p2{P, R, c, T, 0u, 0u};
@@ -293,7 +297,7 @@ SPICEY_HD void spicey_tran_run_v2(Exec &ex, const SpiceyProg &P, const SpiceyRes
           continue;
         }
         ex.phase(SPICEY_PH_U0 + (p < 30 ? p : 30), [&](int tid) {
-          spicey_uk_phase<K, RMAX, NSV, NEL, false>(P, Q, SpiceyPt{ptw, pt_on, p}, c, ex.template regs<Regs>(tid), tid, T, p, p < 64 ? ((smask >> p) & 1) != 0 : true, linear && step > 0);
+          spicey_uk_phase<K, RMAX, NSV, NEL, false, false, OA>(P, Q, SpiceyPt{ptw, pt_on, p}, c, ex.template regs<Regs>(tid), tid, T, p, p < 64 ? ((smask >> p) & 1) != 0 : true, linear && step > 0);
         });
       }
       // EP without idle waves: the last factor phase is peeled and fetches at its tail, after its tasks (it runs for its
@@ -302,7 +306,7 @@ SPICEY_HD void spicey_tran_run_v2(Exec &ex, const SpiceyProg &P, const SpiceyRes
         const int p = u_end - 1;
         const bool act = p < 64 ? ((active >> p) & 1) != 0 : P.ph_cnt[p] != 0;
         ex.phase(SPICEY_PH_U0 + (p < 30 ? p : 30), [&](int tid) {
-          if (act) spicey_uk_phase<K, RMAX, NSV, NEL, false>(P, Q, SpiceyPt{ptw, pt_on, p}, c, ex.template regs<Regs>(tid), tid, T, p, p < 64 ? ((smask >> p) & 1) != 0 : true, linear && step > 0);
+          if (act) spicey_uk_phase<K, RMAX, NSV, NEL, false, false, OA>(P, Q, SpiceyPt{ptw, pt_on, p}, c, ex.template regs<Regs>(tid), tid, T, p, p < 64 ? ((smask >> p) & 1) != 0 : true, linear && step > 0);
           SPICEY_SCHED_FENCE;
           early_fetch(tid);
         });
@@ -313,7 +317,7 @@ SPICEY_HD void spicey_tran_run_v2(Exec &ex, const SpiceyProg &P, const SpiceyRes
         // (kmerge: wave 0 goes on with the first backward phase below the top — its records are resident in this wave's
         // slots, its rows need unknowns of the top only, and the LDS operations of one wave execute in order)
         auto merged_k = [&](int lane) {
-          spicey_uk_phase<K, RMAX, NSV, NEL, true>(P, Q, SpiceyPt{ptw, pt_on, u_end}, c, ex.template regs<Regs>(lane), lane, T, k_begin, false);
+          spicey_uk_phase<K, RMAX, NSV, NEL, true, false, OA>(P, Q, SpiceyPt{ptw, pt_on, u_end}, c, ex.template regs<Regs>(lane), lane, T, k_begin, false);
         };
 #if defined(__HIP_DEVICE_COMPILE__)
         if (pcr_S >= 1 && pcr_S <= 6) {
@@ -357,7 +361,7 @@ SPICEY_HD void spicey_tran_run_v2(Exec &ex, const SpiceyProg &P, const SpiceyRes
       for (int p = k_begin + kmerge; p < 2 * nL - 1; p++) {
         const int l = 2 * nL - 1 - p;
         ex.phase(SPICEY_PH_K0 + (l < 31 ? l : 31), [&](int tid) {
-          spicey_uk_phase<K, RMAX, NSV, NEL, true>(P, Q, SpiceyPt{ptw, pt_on, p - k_begin + u_end}, c, ex.template regs<Regs>(tid), tid, T, p, p < 64 ? ((smask >> p) & 1) != 0 : true);
+          spicey_uk_phase<K, RMAX, NSV, NEL, true, false, OA>(P, Q, SpiceyPt{ptw, pt_on, p - k_begin + u_end}, c, ex.template regs<Regs>(tid), tid, T, p, p < 64 ? ((smask >> p) & 1) != 0 : true);
         });
       }
       // the last backward phase (level 0) is peeled: it also issues Z's parameter fetch.  (Every path through the
@@ -365,7 +369,7 @@ SPICEY_HD void spicey_tran_run_v2(Exec &ex, const SpiceyProg &P, const SpiceyRes
       if (k_begin < 2 * nL) {
         const int p = 2 * nL - 1;
         ex.phase(SPICEY_PH_K0, [&](int tid) {
-          spicey_uk_phase<K, RMAX, NSV, NEL, true, HYB>(P, Q, SpiceyPt{ptw, pt_on, p - k_begin + u_end}, c, ex.template regs<Regs>(tid), tid, T, p, p < 64 ? ((smask >> p) & 1) != 0 : true);  // (level 0: the leaves)
+          spicey_uk_phase<K, RMAX, NSV, NEL, true, HYB, OA>(P, Q, SpiceyPt{ptw, pt_on, p - k_begin + u_end}, c, ex.template regs<Regs>(tid), tid, T, p, p < 64 ? ((smask >> p) & 1) != 0 : true);  // (level 0: the leaves)
           SPICEY_SCHED_FENCE;  // after the tasks, not among them: their registers are free by now
           if (K == 1 && EP) {  // (the source value that early_fetch left in a register: Z reads the slot, nothing before it does)
             if (!z_early) return;
