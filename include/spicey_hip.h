@@ -542,6 +542,59 @@ int32_t spicey_run_measure_spectrum(SpiceyHandle *h, int64_t steps, double dt, c
 /* Duration in ms of the last spicey_run_measure_spectrum's spectrum pass (all of its launches), measured with HIP events. */
 double spicey_last_spectrum_ms(SpiceyHandle *h);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Products of two signals (what SPICE users ask of a power stage: the power an element takes, P_out / P_in): a sixth
+ * pass over the same step-major buffers.  Every other pass reads ONE signal; the average of a product is not the product
+ * of the averages, so v i has to be formed sample by sample — here, on the device.
+ * One request = two factors a and b, each exactly SpiceyMeasReq's signal / col / col_ref (they may come from different
+ * arrays: a voltage times a current), a sign and an inclusive window of steps.  Per step k of the window
+ *   a_k = A[k][a_col], minus A[k][a_col_ref] when a_col_ref >= 0 (one rounded subtraction); b_k likewise from B;
+ *   p_k = a_k * b_k, one rounded product, negated (exactly) when neg = 1.
+ * Result, SPICEY_POWER_ROW doubles per (instance, request):
+ *   {min_p, max_p, step_min, step_max, sum_p, first_p, last_p, sum_aa, sum_bb, first_a, last_a, first_b, last_b, 0, 0, 0}
+ * with sum_aa = sum a_k a_k and sum_bb = sum b_k b_k (the square rounded first, then added).  The extremes and their steps
+ * follow the rule of the measurement pass's stats: the plain comparisons p < m and p > m in ascending step order, so the
+ * FIRST occurrence is named and a NaN never replaces an extreme (it does enter the sums); each chunk starts from its first
+ * sample.  Summation order, the project's fixed rule: chunks of 256 steps counted from step_from, inside a chunk one
+ * addition after the other from the chunk's first term, the chunk partials added in ascending order.  No FMA contraction,
+ * no atomics: a row is a function of the window's samples and the request alone — not of n_inst, the launch or the other
+ * requests of the list. */
+#define SPICEY_POWER_ROW 16
+typedef struct SpiceyPowerReq {
+  int32_t a_signal, a_col, a_col_ref;   /* factor a: exactly SpiceyMeasReq's signal / col / col_ref */
+  int32_t b_signal, b_col, b_col_ref;   /* factor b likewise; a and b may come from different arrays */
+  int32_t neg, reserved;                /* neg = 1: p = -(a b) (an exact negation); reserved: 0 */
+  int64_t step_from, step_to;           /* inclusive window; step_to = -1: the last point */
+} SpiceyPowerReq;                        /* 48 bytes */
+
+/* Bytes of device workspace spicey_power_device needs: the request table, then the chunk partials
+ * [n_inst][ceil(n_points / 256)][n_req][16] doubles, each region rounded up to 256 bytes; -1 for counts <= 0. */
+int64_t spicey_power_workspace_bytes(int32_t n_inst, int64_t n_points, int32_t n_req);
+/* The pass alone, on any DEVICE buffers d_v [n_inst][n_points][n_v] and d_i [n_inst][n_points][n_i] (or NULL): needs no
+ * handle.  reqs is a HOST array; d_out [n_inst][n_req][SPICEY_POWER_ROW] and d_work (work_bytes >=
+ * spicey_power_workspace_bytes) are DEVICE buffers.  Two kernels, enqueued on `stream` (a hipStream_t, NULL = default
+ * stream) without synchronising.  SPICEY_ERR_BAD_DESC, with a text that starts "power: " in spicey_last_error(NULL),
+ * nothing launched and the buffers untouched, for: an unknown signal; a column out of range; a current factor with d_i ==
+ * NULL; neg not 0 or 1; a nonzero reserved; a window outside the run or with step_from > step_to; dt not finite or <= 0; a
+ * workspace that is too small; n_req <= 0; null buffers. */
+int32_t spicey_power_device(int32_t device, int32_t n_inst, int64_t n_points, double dt, const double *d_v, int32_t n_v,
+                            const double *d_i, int32_t n_i, const SpiceyPowerReq *reqs, int32_t n_req, double *d_out,
+                            void *d_work, int64_t work_bytes, void *stream);
+/* spicey_run_measure_spectrum with the product pass behind the other four: one transient run, currents recorded only if
+ * a request of any list names one (here: a_signal = 1 or b_signal = 1), then the measurement pass (if n_req > 0), the
+ * harmonics pass (if n_four > 0), the timing pass (if n_timing > 0), the spectrum pass (if n_spec > 0) and the product
+ * pass (n_power >= 1) on the handle's stream over the same device waveforms; only meas, four, timing, spec, power
+ * [n_inst][n_power][SPICEY_POWER_ROW] and iters (or NULL) come back — also after SPICEY_ERR_SINGULAR.  meas / four /
+ * timing / spec may be NULL when their count is 0.  Everything else is as for spicey_run_measure. */
+int32_t spicey_run_measure_power(SpiceyHandle *h, int64_t steps, double dt, const double *src_table, int32_t src_per_inst,
+                                 const SpiceyMeasReq *reqs, int32_t n_req, double *meas, const SpiceyFourReq *freqs,
+                                 int32_t n_four, double *four, int32_t four_stride, const SpiceyTimingReq *treqs,
+                                 int32_t n_timing, double *timing, const SpiceySpecReq *sreqs, int32_t n_spec, double *spec,
+                                 int32_t spec_stride, const SpiceyPowerReq *preqs, int32_t n_power, double *power,
+                                 int32_t *iters);
+/* Duration in ms of the last spicey_run_measure_power's product pass (both kernels), measured with HIP events. */
+double spicey_last_power_ms(SpiceyHandle *h);
+
 /* Library build info: "spicey_hip <abi> gfx950 …" */
 const char *spicey_version(void);
 

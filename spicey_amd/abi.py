@@ -121,6 +121,19 @@ def spec_row_doubles(reqs) -> int:
     return int(np.where(r["kind"] == SPEC_BINS, 2 * (r["bin_to"].astype(np.int64) - r["bin_from"] + 1), SPEC_DOM_DOUBLES).max())
 
 
+class SpiceyPowerReq(C.Structure):
+    _fields_ = [("a_signal", C.c_int32), ("a_col", C.c_int32), ("a_col_ref", C.c_int32), ("b_signal", C.c_int32), ("b_col", C.c_int32),
+                ("b_col_ref", C.c_int32), ("neg", C.c_int32), ("reserved", C.c_int32), ("step_from", C.c_int64), ("step_to", C.c_int64)]
+
+
+# a list of products of two signals (spicey_power_device) is one array of these
+POWER_REQ_DTYPE = np.dtype([("a_signal", "<i4"), ("a_col", "<i4"), ("a_col_ref", "<i4"), ("b_signal", "<i4"), ("b_col", "<i4"), ("b_col_ref", "<i4"),
+                            ("neg", "<i4"), ("reserved", "<i4"), ("step_from", "<i8"), ("step_to", "<i8")])
+assert POWER_REQ_DTYPE.itemsize == C.sizeof(SpiceyPowerReq) == 48
+POWER_REQ = POWER_REQ_DTYPE
+POWER_ROW = 16
+
+
 class SpiceyAcMeasReq(C.Structure):
     _fields_ = [("num_signal", C.c_int32), ("num_col", C.c_int32), ("num_col_ref", C.c_int32),
                 ("den_signal", C.c_int32), ("den_col", C.c_int32), ("den_col_ref", C.c_int32), ("what", C.c_int32), ("kind", C.c_int32),

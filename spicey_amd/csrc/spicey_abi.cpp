@@ -26,6 +26,7 @@
 #include "fourier_exec.h"
 #include "measure.h"
 #include "measure_exec.h"
+#include "power.h"
 #include "spectrum.h"
 #include "timing.h"
 #include "timing_exec.h"
@@ -771,8 +772,8 @@ extern "C" int32_t spicey_measure_device(int32_t device, int32_t n_inst, int64_t
   });
 }
 
-// The lists of spicey_run_measure, spicey_run_measure_fourier, spicey_run_measure_timing and spicey_run_measure_spectrum: per pass the caller's requests,
-// their count and the out pointer.  entry = the entry point's own pass, its last: that list may not be empty, the lists
+// The lists of spicey_run_measure, spicey_run_measure_fourier, spicey_run_measure_timing, spicey_run_measure_spectrum and spicey_run_measure_power: per pass
+// the caller's requests, their count and the out pointer.  entry = the entry point's own pass, its last: that list may not be empty, the lists
 // before it may, and there are none behind it.
 struct ReducedLists {
   int entry;
@@ -780,13 +781,14 @@ struct ReducedLists {
   const SpiceyFourReq *freqs; int32_t n_four; double *four; int32_t four_stride;
   const SpiceyTimingReq *treqs; int32_t n_tim; double *timing;
   const SpiceySpecReq *sreqs = nullptr; int32_t n_spec = 0; double *spec = nullptr; int32_t spec_stride = 0;
+  const SpiceyPowerReq *preqs = nullptr; int32_t n_power = 0; double *power = nullptr;
 };
 
-// What the four entry points share: one transient run into device buffers of this call's own, the reductions on the
+// What the five entry points share: one transient run into device buffers of this call's own, the reductions on the
 // handle's stream behind it, and only their results and `iters` on the way back.
 static int32_t run_reduced(SpiceyHandle *h, int64_t steps, double dt, const double *src_table, int32_t src_per_inst, const ReducedLists &a, int32_t *iters) {
   if (!h) return SPICEY_ERR_BAD_DESC;
-  double *const outs[N_PASS] = {a.meas, a.four, a.timing, a.spec};
+  double *const outs[N_PASS] = {a.meas, a.four, a.timing, a.spec, a.power};
   if (const int32_t rc0 = check_run_args(h, steps, outs[a.entry], src_table, src_per_inst); rc0 != SPICEY_OK) return rc0;
   if (a.entry == 1 && (a.n_req < 0 || (a.n_req > 0 && !a.meas))) { h->err = "fourier: n_req must be >= 0, and meas not null when n_req > 0"; return SPICEY_ERR_BAD_DESC; }
   if (a.entry == 2 && (a.n_req < 0 || (a.n_req > 0 && !a.meas) || a.n_four < 0 || (a.n_four > 0 && !a.four))) {
@@ -797,8 +799,13 @@ static int32_t run_reduced(SpiceyHandle *h, int64_t steps, double dt, const doub
     h->err = "spectrum: n_req, n_four and n_timing must be >= 0, and meas / four / timing not null when their count is > 0";
     return SPICEY_ERR_BAD_DESC;
   }
+  if (a.entry == 4 && (a.n_req < 0 || (a.n_req > 0 && !a.meas) || a.n_four < 0 || (a.n_four > 0 && !a.four) || a.n_tim < 0 || (a.n_tim > 0 && !a.timing) ||
+                       a.n_spec < 0 || (a.n_spec > 0 && !a.spec))) {
+    h->err = "power: n_req, n_four, n_timing and n_spec must be >= 0, and meas / four / timing / spec not null when their count is > 0";
+    return SPICEY_ERR_BAD_DESC;
+  }
   // (a pass runs if it is the entry point's own, or an earlier one whose list is not empty)
-  const int32_t counts[N_PASS] = {a.n_req, a.n_four, a.n_tim, a.n_spec};
+  const int32_t counts[N_PASS] = {a.n_req, a.n_four, a.n_tim, a.n_spec, a.n_power};
   bool on[N_PASS];
   for (int p = 0; p < N_PASS; p++) on[p] = p == a.entry || (p < a.entry && counts[p] != 0);
   const SpiceyProg &P = h->hp.hdr;
@@ -819,11 +826,15 @@ static int32_t run_reduced(SpiceyHandle *h, int64_t steps, double dt, const doub
   SpiceySpecPlan splan;
   if (on[PASS_SPECTRUM] && !spicey_spec_judge(ni, np, dt, true, P.nOut, true, P.nCur, a.sreqs, a.n_spec, true, a.spec_stride, INT64_MAX, splan, h->err))
     return SPICEY_ERR_BAD_DESC;
+  std::vector<SpiceyPowerDevReq> ptable;
+  if (on[PASS_POWER] && !spicey_power_judge(ni, np, dt, true, P.nOut, true, P.nCur, a.preqs, a.n_power, true, INT64_MAX, ptable, h->err)) return SPICEY_ERR_BAD_DESC;
   const auto names_a_current = [](const auto &list) { return std::any_of(list.begin(), list.end(), [](const auto &q) { return q.signal == 1; }); };
-  const bool need_i = names_a_current(table) || names_a_current(fplan.table) || names_a_current(tplan.edges) || names_a_current(splan.table);
+  const bool need_i = names_a_current(table) || names_a_current(fplan.table) || names_a_current(tplan.edges) || names_a_current(splan.table) ||
+                      std::any_of(ptable.begin(), ptable.end(), [](const SpiceyPowerDevReq &q) { return q.a_signal == 1 || q.b_signal == 1; });
   if (const int32_t rc0 = check_structure(h); rc0 != SPICEY_OK) return rc0;
   HIPCHK(h, hipSetDevice(h->device));
-  static const char *const entry_name[N_PASS] = {"spicey_run_measure", "spicey_run_measure_fourier", "spicey_run_measure_timing", "spicey_run_measure_spectrum"};
+  static const char *const entry_name[N_PASS] = {"spicey_run_measure", "spicey_run_measure_fourier", "spicey_run_measure_timing", "spicey_run_measure_spectrum",
+                                                 "spicey_run_measure_power"};
   Roctx range_run(entry_name[a.entry]);
   HostRun r;
   hipStream_t st = h->q.stream;
@@ -851,6 +862,10 @@ static int32_t run_reduced(SpiceyHandle *h, int64_t steps, double dt, const doub
       {on[PASS_SPECTRUM], (size_t)ni * (size_t)a.n_spec * (size_t)a.spec_stride, (size_t)splan.workspace_bytes(), a.spec, "spicey_launch_spectrum: ",
        [&](double *d_out, void *d_work) {
          return spicey_launch_spectrum(h->device, ni, np, r.d_v, P.nOut, r.d_i, P.nCur, splan, d_out, a.spec_stride, d_work, st);
+       }},
+      {on[PASS_POWER], (size_t)ni * (size_t)a.n_power * SPICEY_POWER_ROW, on[PASS_POWER] ? (size_t)spicey_pow_workspace_bytes(ni, np, a.n_power) : 0, a.power,
+       "spicey_launch_power: ", [&](double *d_out, void *d_work) {
+         return spicey_launch_power(h->device, ni, np, r.d_v, P.nOut, r.d_i, P.nCur, ptable.data(), a.n_power, d_out, d_work, st);
        }},
   };
   for (int p = 0; p < N_PASS; p++)
@@ -920,10 +935,19 @@ extern "C" int32_t spicey_run_measure_spectrum(SpiceyHandle *h, int64_t steps, d
                      {3, reqs, n_req, meas, freqs, n_four, four, four_stride, treqs, n_timing, timing, sreqs, n_spec, spec, spec_stride}, iters);
 }
 
+extern "C" int32_t spicey_run_measure_power(SpiceyHandle *h, int64_t steps, double dt, const double *src_table, int32_t src_per_inst, const SpiceyMeasReq *reqs,
+                                            int32_t n_req, double *meas, const SpiceyFourReq *freqs, int32_t n_four, double *four, int32_t four_stride,
+                                            const SpiceyTimingReq *treqs, int32_t n_timing, double *timing, const SpiceySpecReq *sreqs, int32_t n_spec, double *spec,
+                                            int32_t spec_stride, const SpiceyPowerReq *preqs, int32_t n_power, double *power, int32_t *iters) {
+  return run_reduced(h, steps, dt, src_table, src_per_inst,
+                     {4, reqs, n_req, meas, freqs, n_four, four, four_stride, treqs, n_timing, timing, sreqs, n_spec, spec, spec_stride, preqs, n_power, power}, iters);
+}
+
 extern "C" double spicey_last_measure_ms(SpiceyHandle *h) { return h ? h->last_pass_ms[PASS_MEASURE] : 0.0; }
 extern "C" double spicey_last_fourier_ms(SpiceyHandle *h) { return h ? h->last_pass_ms[PASS_FOURIER] : 0.0; }
 extern "C" double spicey_last_timing_ms(SpiceyHandle *h) { return h ? h->last_pass_ms[PASS_TIMING] : 0.0; }
 extern "C" double spicey_last_spectrum_ms(SpiceyHandle *h) { return h ? h->last_pass_ms[PASS_SPECTRUM] : 0.0; }
+extern "C" double spicey_last_power_ms(SpiceyHandle *h) { return h ? h->last_pass_ms[PASS_POWER] : 0.0; }
 
 // Edge timing (include/spicey_hip.h): the reduction of timing.hip on any device buffers, no handle.
 extern "C" int64_t spicey_timing_workspace_bytes(int32_t n_inst, int64_t n_points, const SpiceyTimingReq *reqs, int32_t n_req) {
@@ -956,6 +980,23 @@ extern "C" int32_t spicey_spectrum_device(int32_t device, int32_t n_inst, int64_
     return SPICEY_ERR_BAD_DESC;
   return launch_on_device(device, "spicey_launch_spectrum", [&]() {
     return spicey_launch_spectrum(device, n_inst, n_points, d_v, n_v, d_i, n_i, plan, d_out, out_stride, d_work, (hipStream_t)stream);
+  });
+}
+
+// Products of two signals (include/spicey_hip.h): the reduction of power.hip on any device buffers, no handle.
+extern "C" int64_t spicey_power_workspace_bytes(int32_t n_inst, int64_t n_points, int32_t n_req) {
+  return spicey_pow_workspace_bytes(n_inst, n_points, n_req);
+}
+
+extern "C" int32_t spicey_power_device(int32_t device, int32_t n_inst, int64_t n_points, double dt, const double *d_v, int32_t n_v, const double *d_i,
+                                       int32_t n_i, const SpiceyPowerReq *reqs, int32_t n_req, double *d_out, void *d_work, int64_t work_bytes,
+                                       void *stream) {
+  // (the call is judged before the device is touched: a refusal launches nothing)
+  std::vector<SpiceyPowerDevReq> table;
+  if (!spicey_power_judge(n_inst, n_points, dt, d_v != nullptr, n_v, d_i != nullptr, n_i, reqs, n_req, d_out && d_work, work_bytes, table, g_err))
+    return SPICEY_ERR_BAD_DESC;
+  return launch_on_device(device, "spicey_launch_power", [&]() {
+    return spicey_launch_power(device, n_inst, n_points, d_v, n_v, d_i, n_i, table.data(), n_req, d_out, d_work, (hipStream_t)stream);
   });
 }
 

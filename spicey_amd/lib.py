@@ -82,6 +82,11 @@ SIGNATURES = {
     "spicey_run_measure_spectrum": (_i32, [_vp, _i64, _f64, _f64p, _i32, _vp, _i32, _f64p, _vp, _i32, _f64p, _i32, _vp, _i32, _f64p, _vp, _i32, _f64p, _i32,
                                            _i32p]),
     "spicey_last_spectrum_ms": (_f64, [_vp]),
+    "spicey_power_workspace_bytes": (_i64, [_i32, _i64, _i32]),
+    "spicey_power_device": (_i32, [_i32, _i32, _i64, _f64, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i64, _vp]),
+    "spicey_run_measure_power": (_i32, [_vp, _i64, _f64, _f64p, _i32, _vp, _i32, _f64p, _vp, _i32, _f64p, _i32, _vp, _i32, _f64p, _vp, _i32, _f64p, _i32,
+                                        _vp, _i32, _f64p, _i32p]),
+    "spicey_last_power_ms": (_f64, [_vp]),
     "spicey_ac_last_inst_status": (_i32, [_vp, _i32p, _i64p]),
     "spicey_ac_measure_workspace_bytes": (_i64, [_i32, _i64, _i32]),
     "spicey_ac_measure_device": (_i32, [_i32, _i32, _i64, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i64, _vp]),
@@ -251,6 +256,20 @@ def spectrum_device(n_inst: int, n_points: int, dt: float, d_v: int, n_v: int, d
         _fail("spicey_spectrum_device", rc, L.spicey_last_error(None))
 
 
+def power_workspace_bytes(n_inst: int, n_points: int, n_req: int) -> int:
+    """spicey_power_workspace_bytes: device workspace of power_device; -1 for counts <= 0."""
+    return load().spicey_power_workspace_bytes(n_inst, n_points, n_req)
+
+
+def power_device(n_inst: int, n_points: int, dt: float, d_v: int, n_v: int, d_i: int, n_i: int, reqs, d_out: int, d_work: int, work_bytes: int,
+                 device: int = 0, stream: int = 0) -> None:
+    """spicey_power_device: the product pass alone on raw device pointers (e.g. torch tensors' data_ptr()): d_v
+    [n_inst][n_points][n_v], d_i [n_inst][n_points][n_i] or 0, d_out [n_inst][n_req][abi.POWER_ROW], d_work of `work_bytes` >=
+    power_workspace_bytes(...).  reqs: records of abi.POWER_REQ_DTYPE.  Enqueued on `stream`, no synchronisation.  A refusal
+    raises SpiceyNativeError whose `status` is the library's code (abi.ERR_BAD_DESC for a bad request list)."""
+    _measure_device("spicey_power_device", (n_inst, n_points, dt), d_v, n_v, d_i, n_i, _reqs(reqs, abi.POWER_REQ_DTYPE), d_out, d_work, work_bytes, device, stream)
+
+
 class Handle:
     """Owns one SpiceyHandle (one topology, n_inst instances, one device)."""
 
@@ -329,9 +348,10 @@ class Handle:
                 res["lin_err"] = le
         return res
 
-    def _run_reduced(self, entry: int, steps: int, dt: float, src: np.ndarray, reqs, freqs, treqs, want_iters: bool, sreqs=None) -> dict:
-        """What run_measure (entry 0), run_measure_fourier (1), run_measure_timing (2) and run_measure_spectrum (3) share: the
-        result arrays of the passes that entry has — an empty list of an earlier pass goes down as a null out pointer — its C function, and the dressing."""
+    def _run_reduced(self, entry: int, steps: int, dt: float, src: np.ndarray, reqs, freqs, treqs, want_iters: bool, sreqs=None, preqs=None) -> dict:
+        """What run_measure (entry 0), run_measure_fourier (1), run_measure_timing (2), run_measure_spectrum (3) and
+        run_measure_power (4) share: the result arrays of the passes that entry has — an empty list of an earlier pass goes
+        down as a null out pointer — its C function, and the dressing."""
         f = self.flat
         src = np.ascontiguousarray(src, dtype=np.float64)
         per_inst = _src_layout(src, f, steps)
@@ -340,7 +360,8 @@ class Handle:
         # per pass: result key, request list, row length
         sr = _reqs([] if sreqs is None else sreqs, abi.SPEC_REQ_DTYPE)
         strides = {"four": stride, "spec": abi.spec_row_doubles(sr)}
-        passes = [("meas", _reqs(reqs), 8), ("four", fr, stride), ("timing", _reqs(treqs, abi.TIMING_REQ_DTYPE), 8), ("spec", sr, strides["spec"])][:entry + 1]
+        passes = [("meas", _reqs(reqs), 8), ("four", fr, stride), ("timing", _reqs(treqs, abi.TIMING_REQ_DTYPE), 8), ("spec", sr, strides["spec"]),
+                  ("power", _reqs([] if preqs is None else preqs, abi.POWER_REQ_DTYPE), abi.POWER_ROW)][:entry + 1]
         res = {"status": 0, "detail": ""}
         args = []
         for k, (key, r, row) in enumerate(passes):
@@ -349,13 +370,15 @@ class Handle:
             if key in strides:
                 args.append(strides[key])
         iters = np.zeros((f.n_inst, steps + 1), np.int32) if want_iters else None
-        fn = (self.L.spicey_run_measure, self.L.spicey_run_measure_fourier, self.L.spicey_run_measure_timing, self.L.spicey_run_measure_spectrum)[entry]
+        fn = (self.L.spicey_run_measure, self.L.spicey_run_measure_fourier, self.L.spicey_run_measure_timing, self.L.spicey_run_measure_spectrum,
+              self.L.spicey_run_measure_power)[entry]
         rc = fn(self.h, steps, dt, _p(src, C.c_double), 1 if per_inst else 0, *args, _p(iters, C.c_int32))
         res.update(status=rc, detail=self.error() if rc != abi.OK else "", iters=iters, partial=True)
         kept = rc in (abi.OK, abi.ERR_SINGULAR)
         if kept:
             for key, last_ms in (("measure_ms", self.L.spicey_last_measure_ms), ("fourier_ms", self.L.spicey_last_fourier_ms),
-                                 ("timing_ms", self.L.spicey_last_timing_ms), ("spectrum_ms", self.L.spicey_last_spectrum_ms))[:entry + 1]:
+                                 ("timing_ms", self.L.spicey_last_timing_ms), ("spectrum_ms", self.L.spicey_last_spectrum_ms),
+                                 ("power_ms", self.L.spicey_last_power_ms))[:entry + 1]:
                 res[key] = last_ms(self.h)
         return self._dress(res, rc, kept, kept)
 
@@ -387,6 +410,14 @@ class Handle:
         least one).  Beside what run_measure_timing returns: `spec` [n_inst][n_spec][row] — per request {re, im} of the band's
         bins or {k, re_k, im_k, P_k-1, P_k, P_k+1, 0, 0}, the rest of a row 0 (include/spicey_hip.h) — and `spectrum_ms`."""
         return self._run_reduced(3, steps, dt, src, reqs, freqs, treqs, want_iters, sreqs)
+
+    def run_measure_power(self, steps: int, dt: float, src: np.ndarray, reqs, freqs, treqs, sreqs, preqs, want_iters: bool = True) -> dict:
+        """spicey_run_measure_power: run_measure_spectrum with the product pass behind the other four, over the same device
+        waveforms.  reqs, freqs, treqs, sreqs: as for run_measure_spectrum, each may be empty; preqs: records of
+        abi.POWER_REQ_DTYPE (at least one).  Beside what run_measure_spectrum returns: `power` [n_inst][n_power][abi.POWER_ROW] =
+        {min_p, max_p, step_min, step_max, sum_p, first_p, last_p, sum_aa, sum_bb, first_a, last_a, first_b, last_b, 0, 0, 0}
+        (include/spicey_hip.h) and `power_ms`."""
+        return self._run_reduced(4, steps, dt, src, reqs, freqs, treqs, want_iters, sreqs, preqs)
 
     def run_device(self, steps: int, dt: float, d_src: int, d_out_v: int, d_out_i: int = 0, d_iters: int = 0, stream: int = 0,
                    src_per_inst: bool = False) -> None:
@@ -732,6 +763,10 @@ class HipBackend(_AcCalls):
 
     def run_measure_spectrum(self, flat: abi.FlatCircuit, steps: int, dt: float, src: np.ndarray, reqs, freqs, treqs, sreqs, want_iters: bool = True) -> dict:
         return self._reduced("run_measure_spectrum", flat, steps, dt, src, reqs, freqs, treqs, sreqs, want_iters)
+
+    def run_measure_power(self, flat: abi.FlatCircuit, steps: int, dt: float, src: np.ndarray, reqs, freqs, treqs, sreqs, preqs,
+                          want_iters: bool = True) -> dict:
+        return self._reduced("run_measure_power", flat, steps, dt, src, reqs, freqs, treqs, sreqs, preqs, want_iters)
 
 
 class HipAcExactBackend(_AcCalls):

@@ -75,10 +75,31 @@ magnitudes a, b, c of the bins k-1, k, k+1: d = 0.5 (a - c) / (a - 2 b + c), d =
 denominator is 0.  Every field of dominant() is None when no bin has any power.  A dict without these specs takes the path
 it always took.
 
+Products.  A fifth family, the only one with two factors: the power an element takes, the power a supply delivers, an
+efficiency, a power factor — v i formed sample by sample on the device (spicey_run_measure_power, a pass behind the other
+four over the same waveforms; include/spicey_hip.h has the definition), because the average of a product is not the product
+of the averages:
+    power("R1")                             energy, avg, peak, t_peak, min, t_min, first, final, rms_a, rms_b, apparent, pf
+    power("v(out)", "i(Rload)")             the same for any two signals (v v and i i too)
+    efficiency("Rload", "V1")               p_load, p_source, eff
+power(name) is the element form: the power the element ABSORBS under the passive sign convention, v(n1,n2) i(name) with the
+element's own terminals (n1 / n2; nPlus / nMinus for a diode) and its recorded current, which flows from the first terminal
+to the second.  A first terminal on ground gives -(v(n2) i(name)), an exact negation on the device; an element between
+ground and ground is a ValueError; the name resolves as i(name) does.  A source that delivers power shows a negative avg
+(i(V1) is the MNA branch current).  On the host, from the device's {min_p, max_p, step_min, step_max, sum_p, first_p, last_p,
+sum_aa, sum_bb, first_a, last_a, first_b, last_b} with n the samples of the window: energy = dt (sum_p - (first_p + last_p) /
+2) — the trapezoidal rule, as stats' integ —, avg = energy / ((n - 1) dt), peak = max_p at t_peak, min at t_min (first
+occurrence), first, final, rms_a / rms_b by stats' trapezoid of squares, apparent = rms_a rms_b, pf = avg / apparent (None
+when apparent == 0); a one-sample window gives energy = 0, avg = first, rms_a = |first_a|, rms_b = |first_b|.  efficiency(load,
+source) takes element names or power(...) specs, goes down as two product requests and gives p_load = avg(load), p_source =
+-avg(source), eff = p_load / p_source (None when p_source == 0); its t_from / t_to, where given, replace the parts' own.  A
+dict without these specs takes the path it always took.
+
 reduce_reference() is the same definition in plain numpy; it is what the tests compare the device with, and what runs
 behind a backend that has no run_measure (backend.run, then reduce_reference: the CPU oracle works unchanged);
 reduce_reference_fourier() is the same for the harmonics, reduce_reference_timing() for the edge timing,
-reduce_reference_spectrum() for the spectrum (that one bit for bit: the same elementwise operations in the same order).
+reduce_reference_spectrum() for the spectrum (that one bit for bit: the same elementwise operations in the same order),
+reduce_reference_power() for the products (its sums in plain step order, every other field bit for bit).
 """
 from __future__ import annotations
 
@@ -139,6 +160,32 @@ class Spectrum:
     t_to: Optional[float] = None
     kind: int = abi.SPEC_BINS
 
+
+@dataclass(frozen=True)
+class Power:
+    a: str  # the element's name when b is None (the element form), else the first factor's signal
+    b: Optional[str] = None
+    t_from: Optional[float] = None
+    t_to: Optional[float] = None
+
+    def parts(self):
+        return [self]
+
+
+@dataclass(frozen=True)
+class Efficiency:
+    load: Power
+    source: Power
+    t_from: Optional[float] = None
+    t_to: Optional[float] = None
+
+    def parts(self):
+        """The two product requests: load, source, under this spec's window where it gives one."""
+        return [Power(p.a, p.b, p.t_from if self.t_from is None else self.t_from, p.t_to if self.t_to is None else self.t_to)
+                for p in (self.load, self.source)]
+
+
+_PRODUCTS = (Power, Efficiency)
 
 _OF = {"minmax": abi.TIMING_MINMAX, "ends": abi.TIMING_ENDS}
 
@@ -321,6 +368,35 @@ def dominant(signal: str, n: Optional[int] = None, window: str = "hann", f_from:
     return _spectrum_spec("dominant", abi.SPEC_DOMINANT, signal, n, window, f_from, f_to, t_from, t_to)
 
 
+def power(a: str, b: Optional[str] = None, *, t_from: Optional[float] = None, t_to: Optional[float] = None) -> Power:
+    """power("R1"): the power the element absorbs, v(n1,n2) i(R1) (passive sign convention); power("v(out)", "i(Rload)"): the
+    product of any two signals.  {energy, avg, peak, t_peak, min, t_min, first, final, rms_a, rms_b, apparent, pf}; see the
+    module text."""
+    if not isinstance(a, str) or (b is not None and not isinstance(b, str)):
+        raise TypeError("power: an element name, or two signals")
+    return Power(a, b, t_from, t_to)
+
+
+def efficiency(load, source, *, t_from: Optional[float] = None, t_to: Optional[float] = None) -> Efficiency:
+    """avg power into `load` over avg power out of `source`, each an element name or a power(...) spec: {p_load, p_source,
+    eff}; see the module text."""
+    parts = []
+    for p in (load, source):
+        if not isinstance(p, (str, Power)):
+            raise TypeError(f"efficiency: load and source must be element names or power(...), got {type(p).__name__}")
+        parts.append(power(p) if isinstance(p, str) else p)
+    return Efficiency(parts[0], parts[1], t_from, t_to)
+
+
+def make_power_reqs(rows: Sequence[tuple]) -> np.ndarray:
+    """Request records (abi.POWER_REQ_DTYPE) from tuples (a_signal, a_col, a_col_ref, b_signal, b_col, b_col_ref, neg, step_from,
+    step_to)."""
+    a = np.zeros(len(rows), abi.POWER_REQ_DTYPE)
+    for k, r in enumerate(rows):
+        a[k] = tuple(r[:7]) + (0,) + tuple(r[7:])
+    return a
+
+
 def make_spec_reqs(rows: Sequence[tuple]) -> np.ndarray:
     """Request records (abi.SPEC_REQ_DTYPE) from tuples (signal, col, col_ref, kind, step_from, log2n, window, bin_from, bin_to)."""
     a = np.zeros(len(rows), abi.SPEC_REQ_DTYPE)
@@ -429,6 +505,31 @@ def _parse_signal(ckt: ParsedCircuit, text: str, elements: Optional[List[str]] =
     return 0, ids[0], ids[1]
 
 
+def _element_terminals(ckt: ParsedCircuit) -> List[Tuple[str, int, int]]:
+    # (name, first terminal, second terminal) of the out_i columns, in _element_names' order; the recorded current flows
+    # from the first to the second
+    return ([(e.name, e.n1, e.n2) for e in ckt.R] + [(e.name, e.n1, e.n2) for e in ckt.C] + [(e.name, e.n1, e.n2) for e in ckt.L]
+            + [(e.name, e.n1, e.n2) for e in ckt.V] + [(e.name, e.n1, e.n2) for e in ckt.S if e.model is not None]
+            + [(e.name, e.nPlus, e.nMinus) for e in ckt.D if e.model is not None])
+
+
+def _power_factors(ckt: ParsedCircuit, spec: Power) -> Tuple[Tuple[int, int, int], Tuple[int, int, int], int]:
+    """(factor a, factor b, neg) of a power spec, the factors as _parse_signal's (signal, a, b)."""
+    if spec.b is not None:
+        return _parse_signal(ckt, spec.a), _parse_signal(ckt, spec.b), 0
+    name = spec.a.strip()
+    hits = [(k, n1, n2) for k, (nm, n1, n2) in enumerate(_element_terminals(ckt)) if nm.upper() == name.upper()]
+    if not hits:
+        raise ValueError(f"measure: power({spec.a!r}): no element named {name!r} records a current")
+    if len(hits) > 1:
+        raise ValueError(f"measure: power({spec.a!r}): {len(hits)} elements share the name {name!r}")
+    k, n1, n2 = hits[0]
+    if n1 == 0 and n2 == 0:
+        raise ValueError(f"measure: power({spec.a!r}): both terminals of {name!r} are ground")
+    # (v(0,n2) i = -(v(n2) i): the first node of a recorded difference is never ground)
+    return ((0, n1, n2), (1, k, 0), 0) if n1 != 0 else ((0, n2, 0), (1, k, 0), 1)
+
+
 class _Plan:
     """A circuit's measures resolved: the recorded nodes, whether currents are needed, the request records."""
 
@@ -436,14 +537,21 @@ class _Plan:
         if not measures:
             raise ValueError("measure: no measures given")
         parsed = []
+        negs = {}  # name -> neg of each product request of a power / efficiency spec
         for name, spec in measures.items():
+            if isinstance(spec, _PRODUCTS):
+                # (the two factors of every product request, resolved: a list in the place of the one signal)
+                factors = [_power_factors(ckt, p) for p in spec.parts()]
+                parsed.append((name, spec, [f[:2] for f in factors]))
+                negs[name] = [f[2] for f in factors]
+                continue
             if isinstance(spec, _TIMING):
                 # (every edge of the spec's requests, resolved: a list in the place of the one signal)
                 parsed.append((name, spec, [tuple(None if e is None else _parse_signal(ckt, e.signal) for e in rq[:2]) for rq in spec.requests()]))
                 continue
             if not isinstance(spec, (Stats, Cross, Fourier, Spectrum)):
                 raise TypeError(f"measure {name!r}: expected stats(...), cross(...), fourier(...), when(...), delay(...), rise_time(...), "
-                                f"fall_time(...), settle(...), spectrum(...) or dominant(...), got {type(spec).__name__}")
+                                f"fall_time(...), settle(...), spectrum(...), dominant(...), power(...) or efficiency(...), got {type(spec).__name__}")
             parsed.append((name, spec, _parse_signal(ckt, spec.signal)))
         sigs = [s for _, _, p in parsed for s in ([e for rq in p for e in rq if e is not None] if isinstance(p, list) else [p])]
         nodes = sorted({n for sig, a, b in sigs if sig == 0 for n in (a, b) if n != 0})
@@ -451,8 +559,9 @@ class _Plan:
         # (a device descriptor records at least one node; with current measures only, the first one)
         self.out_nodes = nodes if nodes else [1]
         col = {n: c for c, n in enumerate(self.out_nodes)}
-        rows, frows, trows, srows = [], [], [], []
-        self.names = []  # (name, "meas" | "four" | "spec" | the timing spec, its (first) place in reqs / freqs / sreqs / treqs), in the dict's order
+        rows, frows, trows, srows, prows = [], [], [], [], []
+        # (name, "meas" | "four" | "spec" | the timing or product spec, its (first) place in reqs / freqs / sreqs / treqs / preqs), in the dict's order
+        self.names = []
 
         def columns(sig, a, b):
             return (col[a], col[b] if b else -1) if sig == 0 else (a, -1)
@@ -469,6 +578,15 @@ class _Plan:
             return (sig, c, cr, e.dir, e.n, abi.TIMING_ABS, 0, 0, e.level)
 
         for name, spec, where in parsed:
+            if isinstance(spec, _PRODUCTS):
+                self.names.append((name, spec, len(prows)))
+                for part, (fa, fb), neg in zip(spec.parts(), where, negs[name]):
+                    s0 = time_to_step(part.t_from, dt, steps, 0)
+                    s1 = time_to_step(part.t_to, dt, steps, steps)
+                    if s0 > s1:
+                        raise ValueError(f"measure {name!r}: the window is empty (t_from maps to step {s0}, t_to to step {s1})")
+                    prows.append((fa[0],) + columns(*fa) + (fb[0],) + columns(*fb) + (neg, s0, s1))
+                continue
             if isinstance(spec, _TIMING):
                 s0 = time_to_step(spec.t_from, dt, steps, 0)
                 s1 = time_to_step(spec.t_to, dt, steps, steps)
@@ -503,6 +621,7 @@ class _Plan:
         self.freqs = make_four_reqs(frows)  # (empty: the dict takes the path without the harmonics pass)
         self.treqs = make_timing_reqs(trows)  # (empty: the dict takes the path without the timing pass)
         self.sreqs = make_spec_reqs(srows)  # (empty: the dict takes the path without the spectrum pass)
+        self.preqs = make_power_reqs(prows)  # (empty: the dict takes the path without the product pass)
 
     def flatten(self, ckt: ParsedCircuit) -> abi.FlatCircuit:
         flat = abi.flatten(ckt)
@@ -512,16 +631,19 @@ class _Plan:
     def key(self) -> bytes:
         """What a batch groups by beside topology and run: the resolved request tables."""
         key = self.reqs.tobytes() + b"|" + self.freqs.tobytes() + (b"|" + self.treqs.tobytes() if len(self.treqs) else b"")
-        return key + b"|s|" + self.sreqs.tobytes() if len(self.sreqs) else key
+        key = key + b"|s|" + self.sreqs.tobytes() if len(self.sreqs) else key
+        return key + b"|p|" + self.preqs.tobytes() if len(self.preqs) else key
 
     def run(self, be, flat: abi.FlatCircuit, steps: int, dt: float, src: np.ndarray) -> dict:
-        return backend_reduce(be, flat, steps, dt, src, self.reqs, self.freqs, self.treqs, self.need_i, self.sreqs)
+        return backend_reduce(be, flat, steps, dt, src, self.reqs, self.freqs, self.treqs, self.need_i, self.sreqs, self.preqs)
 
     def values(self, res: dict, j: int, dt: float) -> Dict[str, dict]:
-        """Instance j of a result (meas [n_inst][n_req][8], four [n_inst][n_four][row], timing [n_inst][n_timing][8]) ->
-        {name: {...}}."""
+        """Instance j of a result (meas [n_inst][n_req][8], four [n_inst][n_four][row], timing [n_inst][n_timing][8], spec
+        [n_inst][n_spec][row], power [n_inst][n_power][16]) -> {name: {...}}."""
         return {name: derive(self.reqs[k], res["meas"][j][k], dt) if kind == "meas" else derive_fourier(self.freqs[k], res["four"][j][k], dt)
                 if kind == "four" else derive_spectrum(self.sreqs[k], res["spec"][j][k], dt) if kind == "spec"
+                else derive_power(self.preqs[k], res["power"][j][k], dt) if isinstance(kind, Power)
+                else derive_efficiency(self.preqs[k:k + 2], res["power"][j][k:k + 2], dt) if isinstance(kind, Efficiency)
                 else derive_timing(kind, res["timing"][j][k:k + len(kind.requests())])
                 for name, kind, k in self.names}
 
@@ -544,6 +666,30 @@ def derive(req, m, dt: float) -> dict:
     tf, tl = (float(m[1]), float(m[2])) if count > 0 else (None, None)
     freq = (count - 1) / (tl - tf) if count >= 2 and tl > tf else None
     return {"count": count, "t_first": tf, "t_last": tl, "freq": freq}
+
+
+def derive_power(req, row, dt: float) -> dict:
+    """The values of one power spec from its 16 doubles (module text)."""
+    mn, mx, smn, smx, s, first, last, saa, sbb, fa, la, fb, lb = (float(v) for v in row[:13])
+    n = int(req["step_to"]) - int(req["step_from"]) + 1
+    if n > 1:
+        span = (n - 1) * dt
+        energy = dt * (s - (first + last) / 2)
+        avg = energy / span
+        rms_a = math.sqrt(max(dt * (saa - (fa * fa + la * la) / 2) / span, 0.0))
+        rms_b = math.sqrt(max(dt * (sbb - (fb * fb + lb * lb) / 2) / span, 0.0))
+    else:
+        energy, avg, rms_a, rms_b = 0.0, first, abs(fa), abs(fb)
+    apparent = rms_a * rms_b
+    return {"energy": energy, "avg": avg, "peak": mx, "t_peak": smx * dt, "min": mn, "t_min": smn * dt, "first": first, "final": last,
+            "rms_a": rms_a, "rms_b": rms_b, "apparent": apparent, "pf": avg / apparent if apparent != 0.0 else None}
+
+
+def derive_efficiency(reqs, rows, dt: float) -> dict:
+    """The values of one efficiency spec from the rows of its two product requests, load then source (module text)."""
+    p_load = derive_power(reqs[0], rows[0], dt)["avg"]
+    p_source = -derive_power(reqs[1], rows[1], dt)["avg"]
+    return {"p_load": p_load, "p_source": p_source, "eff": p_load / p_source if p_source != 0.0 else None}
 
 
 def derive_fourier(req, row, dt: float) -> dict:
@@ -824,6 +970,49 @@ def reduce_reference(out_v: np.ndarray, out_i: Optional[np.ndarray], reqs, dt: f
     return meas
 
 
+def reduce_reference_power(out_v: np.ndarray, out_i: Optional[np.ndarray], reqs, dt: float) -> np.ndarray:
+    """The definition of spicey_power_device in numpy, independent of the kernels: out_v [n_inst][n_points][n_v], out_i
+    likewise or None, reqs records of abi.POWER_REQ_DTYPE with step_to resolved or -1 -> [n_inst][n_req][16].  The three sums
+    are plain Python sums in step order; everything else has one value whatever the order."""
+    reqs = np.ascontiguousarray(reqs, dtype=abi.POWER_REQ_DTYPE).reshape(-1)
+    out_v = np.asarray(out_v, dtype=np.float64)
+    ni, n_points = out_v.shape[0], out_v.shape[1]
+    rows = np.zeros((ni, len(reqs), abi.POWER_ROW))
+
+    def factor(q, pre):
+        return _signal_samples(out_v, out_i, {k: q[pre + k] for k in ("signal", "col", "col_ref")}, "reduce_reference_power")
+
+    for r, q in enumerate(reqs):
+        s0 = int(q["step_from"])
+        s1 = n_points - 1 if int(q["step_to"]) == -1 else int(q["step_to"])
+        if not (0 <= s0 <= s1 < n_points) or int(q["neg"]) not in (0, 1):
+            raise ValueError(f"reduce_reference_power: request {r}: window [{s0}, {s1}] outside the run, or neg {int(q['neg'])}")
+        a, b = factor(q, "a_")[:, s0:s1 + 1], factor(q, "b_")[:, s0:s1 + 1]
+        p = a * b
+        if int(q["neg"]):
+            p = -p
+        for i in range(ni):
+            pi, ai, bi = p[i].tolist(), a[i].tolist(), b[i].tolist()
+            if np.isnan(p[i]).any():  # (the comparisons p < m, p > m skip a NaN; numpy's argmin would return it)
+                mn = mx = pi[0]
+                kmn = kmx = 0
+                for k, v in enumerate(pi):
+                    if v < mn:
+                        mn, kmn = v, k
+                    if v > mx:
+                        mx, kmx = v, k
+            else:
+                kmn, kmx = int(np.argmin(p[i])), int(np.argmax(p[i]))  # (first occurrence)
+                mn, mx = pi[kmn], pi[kmx]
+            s = saa = sbb = 0.0
+            for k in range(len(pi)):
+                s += pi[k]
+                saa += ai[k] * ai[k]
+                sbb += bi[k] * bi[k]
+            rows[i, r, :13] = (mn, mx, s0 + kmn, s0 + kmx, s, pi[0], pi[-1], saa, sbb, ai[0], ai[-1], bi[0], bi[-1])
+    return rows
+
+
 def reduce_reference_fourier(out_v: np.ndarray, out_i: Optional[np.ndarray], reqs, dt: float) -> np.ndarray:
     """The definition of spicey_fourier_device in numpy, independent of the kernels: out_v [n_inst][n_points][n_v], out_i
     likewise or None, reqs records of abi.FOUR_REQ_DTYPE with step_to resolved or -1 -> [n_inst][n_req][1 + 2 max n_harm],
@@ -861,17 +1050,19 @@ def reduce_reference_fourier(out_v: np.ndarray, out_i: Optional[np.ndarray], req
 
 
 def backend_reduce(be, flat: abi.FlatCircuit, steps: int, dt: float, src: np.ndarray, reqs: np.ndarray, freqs: np.ndarray, treqs: np.ndarray,
-                   need_i: bool, sreqs: Sequence = ()) -> dict:
-    """The backend's run_measure_spectrum, run_measure_timing, run_measure_fourier or run_measure — the first whose own list
-    is not empty — or for a backend without that method its run followed by the numpy reductions of that method's passes."""
-    method, args = ("run_measure_spectrum", (reqs, freqs, treqs, sreqs)) if len(sreqs) else ("run_measure_timing", (reqs, freqs, treqs)) if len(treqs) else \
+                   need_i: bool, sreqs: Sequence = (), preqs: Sequence = ()) -> dict:
+    """The backend's run_measure_power, run_measure_spectrum, run_measure_timing, run_measure_fourier or run_measure — the
+    first whose own list is not empty — or for a backend without that method its run followed by the numpy reductions of that
+    method's passes."""
+    method, args = ("run_measure_power", (reqs, freqs, treqs, sreqs, preqs)) if len(preqs) else \
+        ("run_measure_spectrum", (reqs, freqs, treqs, sreqs)) if len(sreqs) else ("run_measure_timing", (reqs, freqs, treqs)) if len(treqs) else \
         ("run_measure_fourier", (reqs, freqs)) if len(freqs) else ("run_measure", (reqs,))
     if hasattr(be, method):
         return getattr(be, method)(flat, steps, dt, src, *args)
     res = be.run(flat, steps, dt, src, want_currents=need_i)
     if res["status"] == abi.OK or (res["status"] == abi.ERR_SINGULAR and res.get("partial")):
-        for key, fn, lst in zip(("meas", "four", "timing", "spec"),
-                                (reduce_reference, reduce_reference_fourier, reduce_reference_timing, reduce_reference_spectrum), args):
+        for key, fn, lst in zip(("meas", "four", "timing", "spec", "power"),
+                                (reduce_reference, reduce_reference_fourier, reduce_reference_timing, reduce_reference_spectrum, reduce_reference_power), args):
             res[key] = fn(res["out_v"], res.get("out_i"), lst, dt)  # (an empty list: [n_inst][0][8], [n_inst][0][1])
     return res
 
@@ -887,7 +1078,7 @@ def _backend(backend, exact_order: bool, device: int, diagnostics: bool, who: st
 
 
 def measureTRAN(ckt: ParsedCircuit, measures: Dict[str, object], *, exact_order: bool = False, device: int = 0, backend=None) -> Optional[dict]:
-    """The transient of `ckt` reduced to {name: {...}} for measures = {name: stats(...) | cross(...) | fourier(...) | when(...) | delay(...) | spectrum(...) | dominant(...) | ...} (module text).  None
+    """The transient of `ckt` reduced to {name: {...}} for measures = {name: stats(...) | cross(...) | fourier(...) | when(...) | delay(...) | spectrum(...) | dominant(...) | power(...) | efficiency(...) | ...} (module text).  None
     without a .tran card; SingularMatrixError and the circuit's state write-back exactly as simulateTRAN; exact_order=True
     runs the reference-order engine."""
     be = _backend(backend, exact_order, device, True, "measureTRAN")
