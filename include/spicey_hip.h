@@ -263,6 +263,11 @@ int32_t spicey_get_lin_err(SpiceyHandle *h, double *out);
 double spicey_last_kernel_ms(SpiceyHandle *h);
 
 int32_t spicey_get_info(SpiceyHandle *h, SpiceyInfo *info);
+/* Interpreter 2: 1 = a run of `steps` steps on this handle takes the operand-address kernel whose tridiagonal top exchanges
+ * its rows between the lanes' registers instead of through LDS (the packed fresh shape, SpiceyInfo.operand_addr = 1 and the
+ * run within the ready-argument kernel's step range, a top of 2 .. 64 rows, SPICEY_NO_TOP_REGS not set when the handle was
+ * created); 0 = it takes another kernel, or there is no handle.  The results are the same bits either way. */
+int32_t spicey_top_regs_form(const SpiceyHandle *h, int64_t steps);
 /* Human-readable description of the last error ("singular at inst 0 step 3 iter 0", the
  * hipGetErrorString text, …).  Valid until the next call on the handle. NULL handle -> global. */
 const char *spicey_last_error(SpiceyHandle *h);

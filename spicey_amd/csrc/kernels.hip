@@ -534,6 +534,8 @@ struct GpuExecV2 {
 // PT, bit 4 (SPICEY_KERNEL_OA): the operand-address form of a ready-argument kernel (tran_common.h: SpiceyOperand).  Such a
 // kernel takes `smem` for LDS address 0: it is this kernel's only LDS object (K = 1, no hybrid workspace).
 #define SPICEY_KERNEL_OA 16
+// PT, bit 5 (SPICEY_KERNEL_TR): the register-exchange top of an operand-address kernel (tran_v2_run.h: TR)
+#define SPICEY_KERNEL_TR 32
 template <int K, int RMAX, int NSV, int NEL, int MAXT, int MINW, bool HYB = false, int PT = 0>
 __global__ void __launch_bounds__(MAXT, MINW) spicey_tran_kernel_v2(const SpiceyProg *__restrict__ Pg, const SpiceyResident *__restrict__ Qg,
                                                                     const SpiceyRun *__restrict__ Rg) {
@@ -583,7 +585,7 @@ __global__ void __launch_bounds__(MAXT, MINW) spicey_tran_kernel_v2(const Spicey
     // start stamps wait in their own slots (not in registers: nothing may stay live around the whole run)
     if (threadIdx.x == 0) { lprof[5] = (unsigned long long)clock64(); lprof[6] = (unsigned long long)wall_clock64(); }
   }
-  spicey_tran_run_v2<K, RMAX, NSV, NEL, HYB, PT & 1, (PT & SPICEY_KERNEL_EP) != 0, (PT & SPICEY_KERNEL_OS) != 0, (PT & SPICEY_KERNEL_RA) != 0, (PT & SPICEY_KERNEL_OA) != 0>(ex, P, Q, R, c, wg);
+  spicey_tran_run_v2<K, RMAX, NSV, NEL, HYB, PT & 1, (PT & SPICEY_KERNEL_EP) != 0, (PT & SPICEY_KERNEL_OS) != 0, (PT & SPICEY_KERNEL_RA) != 0, (PT & SPICEY_KERNEL_OA) != 0, (PT & SPICEY_KERNEL_TR) != 0>(ex, P, Q, R, c, wg);
   if constexpr ((PT & SPICEY_KERNEL_OA) != 0) {
     static_assert(K == 1 && !HYB, "operand addresses: one instance per workgroup on the LDS workspace");
     // The one condition of SpiceyOperand that the source does not show: `smem` at LDS address 0.  Tested here, behind the run
@@ -602,9 +604,9 @@ __global__ void __launch_bounds__(MAXT, MINW) spicey_tran_kernel_v2(const Spicey
   }
 }
 
-template <int K, int RMAX, int NSV, int NEL, int MAXT, int MINW, bool HYB = false, int PT = 0, bool EP = false, bool OS = false, bool RA = false, bool OA = false>
+template <int K, int RMAX, int NSV, int NEL, int MAXT, int MINW, bool HYB = false, int PT = 0, bool EP = false, bool OS = false, bool RA = false, bool OA = false, bool TR = false>
 hipError_t launch_v2_t(const SpiceyProg *P, const SpiceyResident *Q, const SpiceyRun *R, int grid, int threads, size_t lds, hipStream_t st) {
-  auto kern = spicey_tran_kernel_v2<K, RMAX, NSV, NEL, MAXT, MINW, HYB, PT | (EP ? SPICEY_KERNEL_EP : 0) | (OS ? SPICEY_KERNEL_OS : 0) | (RA ? SPICEY_KERNEL_RA : 0) | (OA ? SPICEY_KERNEL_OA : 0)>;
+  auto kern = spicey_tran_kernel_v2<K, RMAX, NSV, NEL, MAXT, MINW, HYB, PT | (EP ? SPICEY_KERNEL_EP : 0) | (OS ? SPICEY_KERNEL_OS : 0) | (RA ? SPICEY_KERNEL_RA : 0) | (OA ? SPICEY_KERNEL_OA : 0) | (TR ? SPICEY_KERNEL_TR : 0)>;
   if (const hipError_t e = spicey_allow_dyn_lds(kern, lds); e != hipSuccess) return e;
   hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, st, P, Q, R);
   return hipGetLastError();
@@ -679,14 +681,15 @@ hipError_t spicey_launch_tran(const SpiceyProg &P, const SpiceyRun &R, int K, bo
 }
 
 // one launcher per entry of SPICEY_V2_SHAPES (launch_plan.h)
-template <int I, int PT = 0, bool EP = false, bool OS = false, bool RA = false, bool OA = false>
+template <int I, int PT = 0, bool EP = false, bool OS = false, bool RA = false, bool OA = false, bool TR = false>
 static hipError_t launch_v2_shape(const SpiceyProg *P, const SpiceyResident *Q, const SpiceyRun *R, int grid, int threads, size_t lds, hipStream_t st) {
   constexpr SpiceyV2Shape s = SPICEY_V2_SHAPES[I];
   static_assert(!EP || s.early, "an early-prefetch kernel is built for the shapes that say so");
   static_assert(!OS || (s.slots && EP && PT == 1), "an operand-slot kernel is an early-prefetch kernel with the phase table, for the shapes that say so");
   static_assert(!RA || (s.ready && OS), "a ready-argument kernel is an operand-slot kernel, for the shapes that say so");
   static_assert(!OA || (s.addr && RA && !s.hybrid), "an operand-address kernel is a ready-argument kernel on the LDS workspace, for the shapes that say so");
-  return launch_v2_t<1, s.rmax, s.nsv, s.nel, s.threads, s.minw, s.hybrid, PT, EP, OS, RA, OA>(P, Q, R, grid, threads, lds, st);
+  static_assert(!TR || (s.top_regs && OA), "a register-exchange top is a form of the operand-address kernel, for the shapes that say so");
+  return launch_v2_t<1, s.rmax, s.nsv, s.nel, s.threads, s.minw, s.hybrid, PT, EP, OS, RA, OA, TR>(P, Q, R, grid, threads, lds, st);
 }
 static decltype(&launch_v2_shape<0>) const launch_v2_by_shape[] = {launch_v2_shape<0>, launch_v2_shape<1>, launch_v2_shape<2>, launch_v2_shape<3>,
                                                                     launch_v2_shape<4>, launch_v2_shape<5>, launch_v2_shape<6>};
@@ -707,9 +710,11 @@ static decltype(&launch_v2_shape<0>) const launch_v2_slots_by_shape[SPICEY_V2_NS
 static decltype(&launch_v2_shape<0>) const launch_v2_ready_by_shape[SPICEY_V2_NSHAPES] = {nullptr, launch_v2_shape<1, 1, true, true, true>, nullptr, nullptr, nullptr, nullptr, nullptr};
 // ... and that form with operand addresses (SpiceyV2Shape::addr)
 static decltype(&launch_v2_shape<0>) const launch_v2_addr_by_shape[SPICEY_V2_NSHAPES] = {nullptr, launch_v2_shape<1, 1, true, true, true, true>, nullptr, nullptr, nullptr, nullptr, nullptr};
+// ... and that one with the register-exchange top (SpiceyV2Shape::top_regs)
+static decltype(&launch_v2_shape<0>) const launch_v2_top_regs_by_shape[SPICEY_V2_NSHAPES] = {nullptr, launch_v2_shape<1, 1, true, true, true, true, true>, nullptr, nullptr, nullptr, nullptr, nullptr};
 
 hipError_t spicey_launch_tran_v2(const SpiceyProg &Ph, const SpiceyResident &Qh, const SpiceyProg *P, const SpiceyResident *Q, const SpiceyRun *R, int K, int grid,
-                                 int threads, hipStream_t st, bool packed, bool phase_table, bool early, bool slots, bool ready, bool addr) {
+                                 int threads, hipStream_t st, bool packed, bool phase_table, bool early, bool slots, bool ready, bool addr, bool top_regs) {
   const int shape = K == 1 ? spicey_v2_shape(threads, packed, Ph.hybrid != 0, packed && Ph.fresh_fill != 0) : -1;  // (a fresh-fill program runs on the build that decodes its flags: spicey_plan makes one for the packed geometry only)
   if (shape < 0) return hipErrorInvalidValue;
   // the table sits in the tail area behind the tridiagonal top's index table: only where it fits there (tran_exec.h)
@@ -720,13 +725,19 @@ hipError_t spicey_launch_tran_v2(const SpiceyProg &Ph, const SpiceyResident &Qh,
       if (launch_v2_ready_by_shape[shape] == nullptr) return hipErrorInvalidValue;
       if (addr) {  // (the plan found that the re-encoded descriptor fields hold their indices: spicey_addr_fits — checked again, the kernel relies on it)
         if (launch_v2_addr_by_shape[shape] == nullptr || !spicey_addr_fits(Ph, Qh.tail_n)) return hipErrorInvalidValue;
+        if (top_regs) {  // (the plan found a top of 1 .. 6 stages: spicey_top_stages — checked again, only the unrolled top has that form)
+          if (launch_v2_top_regs_by_shape[shape] == nullptr || spicey_top_stages(Ph.pcr_n) < 1 || spicey_top_stages(Ph.pcr_n) > 6) return hipErrorInvalidValue;
+          return launch_v2_top_regs_by_shape[shape](P, Q, R, grid, threads, spicey_lds_bytes(Ph, K, true, Qh.tail_n), st);
+        }
         return launch_v2_addr_by_shape[shape](P, Q, R, grid, threads, spicey_lds_bytes(Ph, K, true, Qh.tail_n), st);
       }
+      if (top_regs) return hipErrorInvalidValue;  // (only an operand-address run has that form)
       return launch_v2_ready_by_shape[shape](P, Q, R, grid, threads, spicey_lds_bytes(Ph, K, true, Qh.tail_n), st);
     }
+    if (top_regs) return hipErrorInvalidValue;
     return launch_v2_slots_by_shape[shape](P, Q, R, grid, threads, spicey_lds_bytes(Ph, K, true, Qh.tail_n), st);
   }
-  if (ready || addr) return hipErrorInvalidValue;  // (only an operand-slot run has such forms)
+  if (ready || addr || top_regs) return hipErrorInvalidValue;  // (only an operand-slot run has such forms)
   if (early) {  // (the run's SpiceyRun carries the parameter record: only the build that reads it may run)
     if (!SPICEY_V2_SHAPES[shape].early || launch_v2_early_by_shape[pt][shape] == nullptr) return hipErrorInvalidValue;
     return launch_v2_early_by_shape[pt][shape](P, Q, R, grid, threads, spicey_lds_bytes(Ph, K, true, Qh.tail_n), st);

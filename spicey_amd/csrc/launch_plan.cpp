@@ -47,7 +47,7 @@ static const SpiceyV2Shape &v2_build(int threads, bool packed = false, bool hybr
 SpiceyKnobs spicey_read_knobs() {
   const char *ms = getenv("SPICEY_GROUP_TIMEOUT_MS");
   return {getenv("SPICEY_NO_HYBRID") != nullptr, getenv("SPICEY_FRONT_RIGHT_LOOKING") != nullptr, getenv("SPICEY_TEST_FORCE_GROUP_ABORT") != nullptr,
-          ms ? atoi(ms) : 0, getenv("SPICEY_NO_PHASE_TABLE") != nullptr, getenv("SPICEY_NO_FRESH_FILL") != nullptr, getenv("SPICEY_FRESH_FILL_LINEAR") != nullptr, getenv("SPICEY_NO_EARLY_PREFETCH") != nullptr, getenv("SPICEY_NO_OPERAND_SLOTS") != nullptr, getenv("SPICEY_NO_READY_ARGS") != nullptr, getenv("SPICEY_NO_OPERAND_ADDR") != nullptr};
+          ms ? atoi(ms) : 0, getenv("SPICEY_NO_PHASE_TABLE") != nullptr, getenv("SPICEY_NO_FRESH_FILL") != nullptr, getenv("SPICEY_FRESH_FILL_LINEAR") != nullptr, getenv("SPICEY_NO_EARLY_PREFETCH") != nullptr, getenv("SPICEY_NO_OPERAND_SLOTS") != nullptr, getenv("SPICEY_NO_READY_ARGS") != nullptr, getenv("SPICEY_NO_OPERAND_ADDR") != nullptr, getenv("SPICEY_NO_TOP_REGS") != nullptr};
 }
 
 static int pick_threads(const HostProgram &hp, bool v2) {
@@ -298,6 +298,8 @@ int32_t spicey_plan(const SpiceyDesc *desc, const SpiceyOptions &opt, const Spic
     // (operand addresses: c.W must be LDS address 0 — one instance per workgroup on the LDS workspace, no hybrid layout — and
     // the re-encoded descriptor fields must hold the largest index, tran_pt_layout.h)
     plan.addr = spicey_plan_addr(hp.hdr, hres.tail_n, K, plan.lds, shape, knobs);
+    // (the register-exchange top: the unrolled top of an operand-address run, 1 .. 6 stages)
+    plan.top_regs = spicey_plan_top_regs(plan.addr, hp.hdr.pcr_n, shape, knobs);
   }
   if (!plan.lds) {
     // group mode: several CUs per instance when the batch leaves CUs idle and the circuit is large enough for the
@@ -336,6 +338,11 @@ bool spicey_plan_addr(const SpiceyProg &P, int tail_n, int K, bool lds, int shap
 }
 bool spicey_ready_run(const LaunchPlan &plan, int64_t steps) { return plan.slots && plan.ready && spicey_ready_steps_ok(steps); }
 bool spicey_addr_run(const LaunchPlan &plan, int64_t steps) { return plan.addr && spicey_ready_run(plan, steps); }
+bool spicey_plan_top_regs(bool addr, int pcr_n, int shape, const SpiceyKnobs &knobs) {
+  const int S = spicey_top_stages(pcr_n);
+  return addr && shape >= 0 && shape < SPICEY_V2_NSHAPES && SPICEY_V2_SHAPES[shape].top_regs && S >= 1 && S <= 6 && !knobs.no_top_regs;
+}
+bool spicey_top_regs_run(const LaunchPlan &plan, int64_t steps) { return plan.top_regs && spicey_addr_run(plan, steps); }
 
 size_t spicey_zpar_doubles(const LaunchPlan &plan, const HostProgram &hp) {
   if (!plan.early || plan.interp != 2) return 0;

@@ -47,17 +47,25 @@ struct SpiceyV2Shape {
   bool slots = false;  // ... and an operand-slot kernel (tran_v2_phases.h: OS), taken where the slots fit unless SPICEY_NO_OPERAND_SLOTS is set
   bool ready = false;  // ... and that kernel's ready-argument form (tran_v2_run.h: RA), taken by an operand-slot run unless SPICEY_NO_READY_ARGS is set
   bool addr = false;   // ... and that form with operand addresses (tran_v2_run.h: OA), taken by a ready-argument run where spicey_addr_fits holds unless SPICEY_NO_OPERAND_ADDR is set
+  bool top_regs = false;  // ... and that one with the register-exchange top (tran_v2_run.h: TR), taken by an operand-address run whose top has 1 .. 6 stages unless SPICEY_NO_TOP_REGS is set
 };
 // `early`: Z's element parameters come from one record per thread (SpiceyRun::zpar) and are fetched, with the next source
 // value, at the tail of the last factor phase.  The fresh packed build has it; the other builds were left as they are.
 // (spicey_launch_tran_v2 instantiates one kernel per entry; each kind in ascending threads)
-constexpr SpiceyV2Shape SPICEY_V2_SHAPES[] = {{true, false, 512, 4, 6, 2, 4},    {true, false, 512, 4, 2, 2, 4, true, true, true, true, true},
+constexpr SpiceyV2Shape SPICEY_V2_SHAPES[] = {{true, false, 512, 4, 6, 2, 4},    {true, false, 512, 4, 2, 2, 4, true, true, true, true, true, true},
                                               {false, true, 512, 16, 8, 2, 2},   {false, true, 1024, 4, 4, 1, 4},
                                               {false, false, 256, SPICEY_V2_RMAX256, 12, 4, 1},
                                               {false, false, 512, 16, 8, 2, 2},  {false, false, 1024, 8, 4, 1, 4}};
 constexpr int SPICEY_V2_NSHAPES = (int)(sizeof(SPICEY_V2_SHAPES) / sizeof(SPICEY_V2_SHAPES[0]));
 // index of the build that runs `threads` threads: the first of the kind that holds them; -1 = none
 int spicey_v2_shape(int threads, bool packed, bool hybrid, bool fresh = false);
+// stages of the tridiagonal top of `pcr_n` rows, S = ceil(log2 pcr_n) (spicey_tran_run_v2 forms the same number): the
+// unrolled top, and with it its register-exchange form, runs S = 1 .. 6, i.e. 2 .. 64 rows
+inline int spicey_top_stages(int pcr_n) {
+  int S = 0;
+  while ((1 << S) < pcr_n) S++;
+  return S;
+}
 
 // Environment knobs of the transient handle, read once by spicey_create.
 struct SpiceyKnobs {
@@ -72,6 +80,7 @@ struct SpiceyKnobs {
   bool no_operand_slots = false;     // SPICEY_NO_OPERAND_SLOTS: an early-prefetch run keeps the kernel that masks ground by compare and select and writes no slot (the in-library A/B switch)
   bool no_ready_args = false;        // SPICEY_NO_READY_ARGS: an operand-slot run keeps the kernel that moves all of Z's arguments to scalars at the phase head (the in-library A/B switch)
   bool no_operand_addr = false;      // SPICEY_NO_OPERAND_ADDR: a ready-argument run keeps the kernel that addresses its LDS operands as W[field] (the in-library A/B switch)
+  bool no_top_regs = false;          // SPICEY_NO_TOP_REGS: an operand-address run keeps the kernel whose tridiagonal top exchanges its rows through LDS (the in-library A/B switch)
 };
 SpiceyKnobs spicey_read_knobs();
 
@@ -130,6 +139,9 @@ struct LaunchPlan {
   // that kernel (spicey_addr_run).  A property of the program and its shape: the knobs of the forms below it (phase table,
   // early prefetch, operand slots, ready arguments) decide whether a ready-argument run happens, not this flag.
   bool addr = false;
+  // ... and a form of that kernel with the register-exchange top (tran_v2_run.h: TR), the plan says `addr`, the program's top
+  // has 1 .. 6 stages and SPICEY_NO_TOP_REGS is not set: every operand-address run of the handle takes it (spicey_top_regs_run)
+  bool top_regs = false;
   bool lds = true;       // workspace in LDS (else global memory)
   size_t lds_bytes = 0;
   int64_t algo_bytes = 0;
@@ -148,6 +160,10 @@ bool spicey_ready_run(const LaunchPlan &plan, int64_t steps);
 bool spicey_plan_addr(const SpiceyProg &P, int tail_n, int K, bool lds, int shape, const SpiceyKnobs &knobs);
 // ... and whether that run takes the kernel's operand-address form: a ready-argument run of a plan that says `addr`
 bool spicey_addr_run(const LaunchPlan &plan, int64_t steps);
+// LaunchPlan::top_regs of a plan whose `addr` is decided, for a top of `pcr_n` rows on build `shape`: what spicey_plan decides
+bool spicey_plan_top_regs(bool addr, int pcr_n, int shape, const SpiceyKnobs &knobs);
+// ... and whether that run takes the register-exchange top: an operand-address run of a plan that says `top_regs`
+bool spicey_top_regs_run(const LaunchPlan &plan, int64_t steps);
 // doubles of the parameter record SpiceyRun::zpar of a planned handle: five per resident item, NEL x T items per instance
 // (0: the plan runs a build without it)
 size_t spicey_zpar_doubles(const LaunchPlan &plan, const HostProgram &hp);

@@ -106,6 +106,60 @@ __device__ __forceinline__ void spicey_pcr_all(const WgCtx<K> &c, double *buf, c
   }
   if (pmin < SPICEY_EPS && lane < n && c.valid[0]) { c.flags[1] = 1; c.flags[2] = c.inst[0]; }
 }
+// TR (the register-exchange top, a form of the operand-address build): the same stages with the rows in registers.  A row
+// keeps {a, b, c, d} and r = 1/b from stage to stage and reads {a, r, c, d} of the rows lane -+ stride from those lanes'
+// registers (ds_bpermute on the halves of each double: the LDS crossbar, no LDS memory), so a stage holds no ds_write, no
+// wait for it and no fence — values that only ever move between the lanes of one wave no longer make the round trip
+// through LDS.  The arithmetic is spicey_pcr_all's, operation for operation, and so is the clamped-neighbour rule: lane 0 /
+// lane 63 stand in for a missing neighbour and their finite row is multiplied by the same zero coupling.
+// Condition: ALL 64 lanes of the wave execute this (ds_bpermute returns 0 for a lane that does not) — wave 0 of
+// gpu_wave_lockstep_keep_then with nlanes = 64, which is how spicey_tran_run_v2 calls it; rows past n are identity rows in
+// their lanes' registers as they were in the buffers.  The two row buffers stay allocated (the LDS layout is every
+// build's) and unused.  The gather reads the lane's four 16-bit indices as one 8-byte word pair and forms the operand
+// addresses with the OA handles (c.W is LDS address 0); 0xFFFF, "no neighbour", is tested on the handle.
+static __device__ __forceinline__ double spicey_lane_f64(int byte_lane, double v) {
+  const int lo = __builtin_amdgcn_ds_bpermute(byte_lane, __double2loint(v));
+  const int hi = __builtin_amdgcn_ds_bpermute(byte_lane, __double2hiint(v));
+  return __hiloint2double(hi, lo);
+}
+template <int K>
+__device__ __forceinline__ void spicey_pcr_all_regs(const WgCtx<K> &c, const uint16_t *tab, int n, int S, int lane) {
+  static_assert(K == 1, "the register-exchange top is a form of the operand-address build");
+  typedef SpiceyOperand<true> Op;
+  const bool on = lane < n;
+  const uint2 t = *(const uint2 *)(tab + (on ? lane : 0) * 4);  // {ia | ib << 16, ic | id << 16}: 8-byte aligned
+  const uint32_t none = Op::index(0xFFFFu);
+  const uint32_t ha = Op::template half<0>(t.x), hb = Op::template half<1>(t.x), hc = Op::template half<0>(t.y), hd = Op::template half<1>(t.y);
+  const double va = Op::template ld<K>(c.W, ha == none ? hb : ha, 0), vb = Op::template ld<K>(c.W, hb, 0), vc = Op::template ld<K>(c.W, hc == none ? hb : hc, 0),
+               vd = Op::template ld<K>(c.W, hd, 0);
+  double a = (on && ha != none) ? va : 0.0;
+  double b = on ? vb : 1.0;  // rows past the end: identity
+  double cc = (on && hc != none) ? vc : 0.0;
+  double d = on ? vd : 0.0;
+  double pmin = fabs(b);
+  double r = spicey_rcp(b);
+#pragma unroll
+  for (int st = 1; st <= 6; st++) {
+    if (st > S) break;  // (wave-uniform)
+    const int h = 1 << (st - 1);
+    const int jm = max(lane - h, 0) << 2, jp = min(lane + h, 63) << 2;
+    // (the operands of the pivot chain first)
+    const double rm = spicey_lane_f64(jm, r), cm = spicey_lane_f64(jm, cc), rp = spicey_lane_f64(jp, r), ap = spicey_lane_f64(jp, a);
+    const double dm = spicey_lane_f64(jm, d), dp = spicey_lane_f64(jp, d), am = spicey_lane_f64(jm, a), cp = spicey_lane_f64(jp, cc);
+    const double al = -a * rm, ga = -cc * rp;
+    const double na = al * am, nc = ga * cp;
+    const double nb = fma(ga, ap, fma(al, cm, b));
+    const double nd = fma(ga, dp, fma(al, dm, d));
+    pmin = fmin(pmin, fabs(nb));
+    const double nr = spicey_rcp(nb);
+    if (st < S) {
+      a = na; b = nb; cc = nc; d = nd; r = nr;
+    } else if (on) {
+      Op::template st<K>(c.W, hd, 0, nd * nr);
+    }
+  }
+  if (pmin < SPICEY_EPS && on && c.valid[0]) { c.flags[1] = 1; c.flags[2] = c.inst[0]; }
+}
 #endif
 
 // The three argument structs hold ~110 pointers: kept in SGPRs across the time loop they overflow the 102 scalar registers
@@ -143,12 +197,16 @@ struct SpiceyHasIdleWaves<E, decltype((void)E::idle_waves)> { static constexpr b
 // OA (the operand-address build, TranPhases2 / tran_common.h: SpiceyOperand): a ready-argument build that names the operands
 // of its always-executed LDS reads and writes — the interpreter's inline tasks and row records, Z's and B's resident
 // sections — by handles; the caller has made sure that c.W is LDS address 0 and that spicey_addr_fits holds.
-template <int K, int RMAX, int NSV, int NEL, bool HYB = false, int PT = -1, bool EP = false, bool OS = false, bool RA = false, bool OA = false, class Exec>
+// TR (the register-exchange top, spicey_pcr_all_regs above): an operand-address build on the GPU whose unrolled top keeps
+// its rows in registers; the caller has made sure that the top has 1 .. 6 stages (a top outside that range runs the staged
+// form here as in every build).  Host executors run spicey_pcr_stage whatever TR says.
+template <int K, int RMAX, int NSV, int NEL, bool HYB = false, int PT = -1, bool EP = false, bool OS = false, bool RA = false, bool OA = false, bool TR = false, class Exec>
 SPICEY_HD void spicey_tran_run_v2(Exec &ex, const SpiceyProg &P, const SpiceyResident &Q, const SpiceyRun &R, WgCtx<K> &c, int wg) {
   const int T = ex.threads();
   static_assert(!OS || PT != 0, "the operand slots lie behind the phase table");
   static_assert(!RA || OS, "the ready arguments are a form of the operand-slot build");
   static_assert(!OA || RA, "the operand addresses are a form of the ready-argument build");
+  static_assert(!TR || (OA && K == 1), "the register-exchange top is a form of the operand-address build");
   typedef TranPhases2<K, RMAX, NSV, NEL, HYB, EP, OS, RA, OA> Ph2;
   uint32_t brem, zrem;
   {
@@ -322,7 +380,8 @@ SPICEY_HD void spicey_tran_run_v2(Exec &ex, const SpiceyProg &P, const SpiceyRes
 #if defined(__HIP_DEVICE_COMPILE__)
         if (pcr_S >= 1 && pcr_S <= 6) {
           auto top_all = [&](int lane, int, double *) {
-            spicey_pcr_all<K>(c, (double *)c.tail, (const uint16_t *)(c.tail + 1024), pcr_n, pcr_S, lane);
+            if constexpr (TR) spicey_pcr_all_regs<K>(c, (const uint16_t *)(c.tail + 1024), pcr_n, pcr_S, lane);  // (all 64 lanes: nlanes = 64 below)
+            else spicey_pcr_all<K>(c, (double *)c.tail, (const uint16_t *)(c.tail + 1024), pcr_n, pcr_S, lane);
             if (kmerge) {
               __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
               __builtin_amdgcn_wave_barrier();

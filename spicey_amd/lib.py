@@ -40,6 +40,7 @@ SIGNATURES = {
     "spicey_get_lin_err": (_i32, [_vp, _f64p]),
     "spicey_last_kernel_ms": (_f64, [_vp]),
     "spicey_get_info": (_i32, [_vp, _infop]),
+    "spicey_top_regs_form": (_i32, [_vp, _i64]),
     "spicey_last_error": (_str, [_vp]),
     "spicey_destroy": (None, [_vp]),
     "spicey_version": (_str, []),
@@ -300,6 +301,10 @@ class Handle:
         i = abi.SpiceyInfo()
         self.L.spicey_get_info(self.h, C.byref(i))
         return i.as_dict()
+
+    def top_regs_form(self, steps: int) -> bool:
+        """Whether a run of `steps` steps takes the kernel with the register-exchange top (spicey_top_regs_form)."""
+        return bool(self.L.spicey_top_regs_form(self.h, steps))
 
     def error(self) -> str:
         m = self.L.spicey_last_error(self.h)
