@@ -268,6 +268,11 @@ int32_t spicey_get_info(SpiceyHandle *h, SpiceyInfo *info);
  * run within the ready-argument kernel's step range, a top of 2 .. 64 rows, SPICEY_NO_TOP_REGS not set when the handle was
  * created); 0 = it takes another kernel, or there is no handle.  The results are the same bits either way. */
 int32_t spicey_top_regs_form(const SpiceyHandle *h, int64_t steps);
+/* Interpreter 2: 1 = a run of `steps` steps on this handle takes the form of that kernel which keeps the row record of factor
+ * level 0 in registers for the whole run (spicey_top_regs_form says 1, level 0 is streamed as row records, at most one per
+ * thread and nothing else, the circuit is not linear, SPICEY_NO_U0_RESIDENT not set when the handle was created); 0 = it
+ * takes another kernel, or there is no handle.  The results are the same bits either way. */
+int32_t spicey_u0_resident_form(const SpiceyHandle *h, int64_t steps);
 /* Human-readable description of the last error ("singular at inst 0 step 3 iter 0", the
  * hipGetErrorString text, …).  Valid until the next call on the handle. NULL handle -> global. */
 const char *spicey_last_error(SpiceyHandle *h);

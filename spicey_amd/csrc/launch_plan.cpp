@@ -47,7 +47,7 @@ static const SpiceyV2Shape &v2_build(int threads, bool packed = false, bool hybr
 SpiceyKnobs spicey_read_knobs() {
   const char *ms = getenv("SPICEY_GROUP_TIMEOUT_MS");
   return {getenv("SPICEY_NO_HYBRID") != nullptr, getenv("SPICEY_FRONT_RIGHT_LOOKING") != nullptr, getenv("SPICEY_TEST_FORCE_GROUP_ABORT") != nullptr,
-          ms ? atoi(ms) : 0, getenv("SPICEY_NO_PHASE_TABLE") != nullptr, getenv("SPICEY_NO_FRESH_FILL") != nullptr, getenv("SPICEY_FRESH_FILL_LINEAR") != nullptr, getenv("SPICEY_NO_EARLY_PREFETCH") != nullptr, getenv("SPICEY_NO_OPERAND_SLOTS") != nullptr, getenv("SPICEY_NO_READY_ARGS") != nullptr, getenv("SPICEY_NO_OPERAND_ADDR") != nullptr, getenv("SPICEY_NO_TOP_REGS") != nullptr};
+          ms ? atoi(ms) : 0, getenv("SPICEY_NO_PHASE_TABLE") != nullptr, getenv("SPICEY_NO_FRESH_FILL") != nullptr, getenv("SPICEY_FRESH_FILL_LINEAR") != nullptr, getenv("SPICEY_NO_EARLY_PREFETCH") != nullptr, getenv("SPICEY_NO_OPERAND_SLOTS") != nullptr, getenv("SPICEY_NO_READY_ARGS") != nullptr, getenv("SPICEY_NO_OPERAND_ADDR") != nullptr, getenv("SPICEY_NO_TOP_REGS") != nullptr, getenv("SPICEY_NO_U0_RESIDENT") != nullptr};
 }
 
 static int pick_threads(const HostProgram &hp, bool v2) {
@@ -300,6 +300,8 @@ int32_t spicey_plan(const SpiceyDesc *desc, const SpiceyOptions &opt, const Spic
     plan.addr = spicey_plan_addr(hp.hdr, hres.tail_n, K, plan.lds, shape, knobs);
     // (the register-exchange top: the unrolled top of an operand-address run, 1 .. 6 stages)
     plan.top_regs = spicey_plan_top_regs(plan.addr, hp.hdr.pcr_n, shape, knobs);
+    // (the resident level-0 record: level 0 streamed as row records, at most one per thread, and nothing else)
+    plan.u0_resident = spicey_plan_u0_resident(plan.top_regs, hp.hdr, hres.st_desc.data(), plan.T, shape, knobs);
   }
   if (!plan.lds) {
     // group mode: several CUs per instance when the batch leaves CUs idle and the circuit is large enough for the
@@ -343,6 +345,16 @@ bool spicey_plan_top_regs(bool addr, int pcr_n, int shape, const SpiceyKnobs &kn
   return addr && shape >= 0 && shape < SPICEY_V2_NSHAPES && SPICEY_V2_SHAPES[shape].top_regs && S >= 1 && S <= 6 && !knobs.no_top_regs;
 }
 bool spicey_top_regs_run(const LaunchPlan &plan, int64_t steps) { return plan.top_regs && spicey_addr_run(plan, steps); }
+bool spicey_u0_resident_fits(const SpiceyProg &P, const uint32_t *st_desc, int T) {
+  const bool linear = P.nD == 0 && P.nS == 0 && P.nDynEnt == 0;
+  return st_desc != nullptr && P.nLevels > 0 && P.pcr_n > 0 && P.pcr_level > 0 && !P.hybrid && P.fresh_fill != 0 && !linear && st_desc[0] == 1u && st_desc[2] >= 1u &&
+         st_desc[2] <= (uint32_t)T && st_desc[5] == 0u && st_desc[6] == 0u;
+}
+bool spicey_plan_u0_resident(bool top_regs, const SpiceyProg &P, const uint32_t *st_desc, int T, int shape, const SpiceyKnobs &knobs) {
+  return top_regs && shape >= 0 && shape < SPICEY_V2_NSHAPES && SPICEY_V2_SHAPES[shape].u0_resident && T == SPICEY_V2_SHAPES[shape].threads && !knobs.no_u0_resident &&
+         spicey_u0_resident_fits(P, st_desc, T);
+}
+bool spicey_u0_resident_run(const LaunchPlan &plan, int64_t steps) { return plan.u0_resident && spicey_top_regs_run(plan, steps); }
 
 size_t spicey_zpar_doubles(const LaunchPlan &plan, const HostProgram &hp) {
   if (!plan.early || plan.interp != 2) return 0;

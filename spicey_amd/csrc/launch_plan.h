@@ -48,11 +48,12 @@ struct SpiceyV2Shape {
   bool ready = false;  // ... and that kernel's ready-argument form (tran_v2_run.h: RA), taken by an operand-slot run unless SPICEY_NO_READY_ARGS is set
   bool addr = false;   // ... and that form with operand addresses (tran_v2_run.h: OA), taken by a ready-argument run where spicey_addr_fits holds unless SPICEY_NO_OPERAND_ADDR is set
   bool top_regs = false;  // ... and that one with the register-exchange top (tran_v2_run.h: TR), taken by an operand-address run whose top has 1 .. 6 stages unless SPICEY_NO_TOP_REGS is set
+  bool u0_resident = false;  // ... and that one with the resident level-0 record (tran_v2_run.h: UR), taken by a register-exchange-top run where spicey_u0_resident_fits holds unless SPICEY_NO_U0_RESIDENT is set
 };
 // `early`: Z's element parameters come from one record per thread (SpiceyRun::zpar) and are fetched, with the next source
 // value, at the tail of the last factor phase.  The fresh packed build has it; the other builds were left as they are.
 // (spicey_launch_tran_v2 instantiates one kernel per entry; each kind in ascending threads)
-constexpr SpiceyV2Shape SPICEY_V2_SHAPES[] = {{true, false, 512, 4, 6, 2, 4},    {true, false, 512, 4, 2, 2, 4, true, true, true, true, true, true},
+constexpr SpiceyV2Shape SPICEY_V2_SHAPES[] = {{true, false, 512, 4, 6, 2, 4},    {true, false, 512, 4, 2, 2, 4, true, true, true, true, true, true, true},
                                               {false, true, 512, 16, 8, 2, 2},   {false, true, 1024, 4, 4, 1, 4},
                                               {false, false, 256, SPICEY_V2_RMAX256, 12, 4, 1},
                                               {false, false, 512, 16, 8, 2, 2},  {false, false, 1024, 8, 4, 1, 4}};
@@ -81,6 +82,7 @@ struct SpiceyKnobs {
   bool no_ready_args = false;        // SPICEY_NO_READY_ARGS: an operand-slot run keeps the kernel that moves all of Z's arguments to scalars at the phase head (the in-library A/B switch)
   bool no_operand_addr = false;      // SPICEY_NO_OPERAND_ADDR: a ready-argument run keeps the kernel that addresses its LDS operands as W[field] (the in-library A/B switch)
   bool no_top_regs = false;          // SPICEY_NO_TOP_REGS: an operand-address run keeps the kernel whose tridiagonal top exchanges its rows through LDS (the in-library A/B switch)
+  bool no_u0_resident = false;       // SPICEY_NO_U0_RESIDENT: a register-exchange-top run keeps the kernel that fetches level 0's row record in every step (the in-library A/B switch)
 };
 SpiceyKnobs spicey_read_knobs();
 
@@ -142,6 +144,10 @@ struct LaunchPlan {
   // ... and a form of that kernel with the register-exchange top (tran_v2_run.h: TR), the plan says `addr`, the program's top
   // has 1 .. 6 stages and SPICEY_NO_TOP_REGS is not set: every operand-address run of the handle takes it (spicey_top_regs_run)
   bool top_regs = false;
+  // ... and a form of that kernel with the resident level-0 record (tran_v2_run.h: UR), where the plan says `top_regs`,
+  // spicey_u0_resident_fits holds for the program and its resident layout and SPICEY_NO_U0_RESIDENT is not set: every
+  // register-exchange-top run of the handle takes it (spicey_u0_resident_run)
+  bool u0_resident = false;
   bool lds = true;       // workspace in LDS (else global memory)
   size_t lds_bytes = 0;
   int64_t algo_bytes = 0;
@@ -164,6 +170,18 @@ bool spicey_addr_run(const LaunchPlan &plan, int64_t steps);
 bool spicey_plan_top_regs(bool addr, int pcr_n, int shape, const SpiceyKnobs &knobs);
 // ... and whether that run takes the register-exchange top: an operand-address run of a plan that says `top_regs`
 bool spicey_top_regs_run(const LaunchPlan &plan, int64_t steps);
+// The resident level-0 record (tran_v2_run.h: UR) is for a program P with the phase descriptors st_desc (HostResident, [2L][8])
+// on T threads where ALL of this holds — the kernel's phase 0 then runs the one record in each thread's registers and
+// nothing else:
+//   - factor phase 0 exists below the tridiagonal top and is streamed in its row-record encoding (st_desc[0] = 1);
+//   - it has at least one and at most T row records (st_desc[2]): record `tid` is thread tid's, there is no second trip;
+//   - it has no generic remainder (st_desc[5] = 0, and with it no right-hand-side remainder, st_desc[6]);
+//   - the circuit is not linear: a reused factorisation runs another share of the phase (its right-hand-side column).
+bool spicey_u0_resident_fits(const SpiceyProg &P, const uint32_t *st_desc, int T);
+// LaunchPlan::u0_resident of a plan whose `top_regs` is decided, on build `shape`: what spicey_plan decides
+bool spicey_plan_u0_resident(bool top_regs, const SpiceyProg &P, const uint32_t *st_desc, int T, int shape, const SpiceyKnobs &knobs);
+// ... and whether that run takes the resident level-0 record: a register-exchange-top run of a plan that says `u0_resident`
+bool spicey_u0_resident_run(const LaunchPlan &plan, int64_t steps);
 // doubles of the parameter record SpiceyRun::zpar of a planned handle: five per resident item, NEL x T items per instance
 // (0: the plan runs a build without it)
 size_t spicey_zpar_doubles(const LaunchPlan &plan, const HostProgram &hp);

@@ -354,7 +354,7 @@ static int32_t enqueue_kernel(SpiceyHandle *h, const SpiceyRun &R, hipStream_t s
   if (h->plan.interp == 3) {
     HIPCHK(h, spicey_launch_exact(h->d_xprog, h->d_Rstruct, h->plan.grid, h->plan.T, h->plan.lds ? h->plan.lds_bytes : 0, st));
   } else if (h->plan.interp == 2) {
-    HIPCHK(h, spicey_launch_tran_v2(h->dprog, h->dres, h->d_Pstruct, h->d_Qstruct, h->d_Rstruct, h->plan.K, h->plan.grid, h->plan.T, st, h->plan.packed, !h->knobs.no_phase_table, h->d_zpar != nullptr, h->plan.slots, spicey_ready_run(h->plan, R.steps), spicey_addr_run(h->plan, R.steps), spicey_top_regs_run(h->plan, R.steps)));
+    HIPCHK(h, spicey_launch_tran_v2(h->dprog, h->dres, h->d_Pstruct, h->d_Qstruct, h->d_Rstruct, h->plan.K, h->plan.grid, h->plan.T, st, h->plan.packed, !h->knobs.no_phase_table, h->d_zpar != nullptr, h->plan.slots, spicey_ready_run(h->plan, R.steps), spicey_addr_run(h->plan, R.steps), spicey_top_regs_run(h->plan, R.steps), spicey_u0_resident_run(h->plan, R.steps)));
   } else if (group) {
     HIPCHK(h, spicey_launch_tran_grp(h->dprog, R, h->plan.K, h->plan.grid, h->plan.T, st));
   } else {
@@ -559,6 +559,7 @@ extern "C" int32_t spicey_sync(SpiceyHandle *h) {
 
 extern "C" int32_t spicey_group_retries(const SpiceyHandle *h) { return h ? h->group_retries : 0; }
 extern "C" int32_t spicey_top_regs_form(const SpiceyHandle *h, int64_t steps) { return (h && h->plan.interp == 2 && spicey_top_regs_run(h->plan, steps)) ? 1 : 0; }
+extern "C" int32_t spicey_u0_resident_form(const SpiceyHandle *h, int64_t steps) { return (h && h->plan.interp == 2 && spicey_u0_resident_run(h->plan, steps)) ? 1 : 0; }
 extern "C" int64_t spicey_group_stale_polls(const SpiceyHandle *h) { return h ? h->stale_polls : 0; }
 
 // Per instance of the last run, from the status words {code, inst, step, iter} of its workgroups: workgroup (or group) g

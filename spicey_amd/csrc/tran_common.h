@@ -209,20 +209,111 @@ SPICEY_HD double spicey_max_nan(double a, double b) {  // Math.max semantics
   return (a > b || a != a) ? a : b;
 }
 
+// ---- exp for the diode model -------------------------------------------------------------------------------------------
+// The device library's f64 exp, operation for operation (ROCm device libs, ocml expD.cl as linked into every kernel here):
+// n = rint(x log2 e); r = x + n (-ln 2) in two fma steps (ln 2 = hi + lo); a degree-11 polynomial in r, nine Horner steps
+// and two closing fma(r, p, 1.0); ldexp(p, n); x > 1024 -> +inf; x < -1075 -> 0.  Same operations on the same constants in
+// the same order: the same bits for every argument (NaN and the infinities included; tests/test_u0_resident_gpu.py holds
+// a million arguments and the edges against the library).
+// Why a copy: inlined into a time loop, the library's exp leaves its literals to the compiler, which keeps all of them —
+// nine coefficient pairs, the reduction and clamp constants: 18 .. 24 vector registers — live around the whole loop, in
+// kernels that sit at their register cap.  Here the constants come from a table in constant memory through an address the
+// compiler cannot trace back (as spicey_fresh reads the argument structs), so they are scalar-loaded inside the phase that
+// evaluates a diode and dead behind it: no register, vector or scalar, holds one across the loop.  The diode's own
+// literals (0.8, 1e-12) ride in the same table for the same reason.  Who uses it: spicey_diode_k<PORT>.
+#define SPICEY_EXP_TAB_VALUES                                                                                                  \
+  0x1.71547652b82fep+0,  /* [0] log2 e */                                                                                      \
+  -0x1.62e42fefa39efp-1, /* [1] -ln 2, upper part (negated here, as the compiler negates the library's literal: */            \
+  -0x1.abc9e3b39803fp-56, /* [2] -ln 2, lower part   fma(-n, c, x) and fma(n, -c, x) differ in the sign of a NaN) */            \
+  0x1.ade156a5dcb37p-26, /* [3] .. [11]: the polynomial, highest power first */                                                \
+  0x1.28af3fca7ab0cp-22, 0x1.71dee623fde64p-19, 0x1.a01997c89e6b0p-16, 0x1.a01a014761f6ep-13, 0x1.6c16c1852b7b0p-10,         \
+  0x1.1111111122322p-7, 0x1.55555555502a1p-5, 0x1.5555555555511p-3, 0x1.000000000000bp-1, /* [12] */                           \
+  1024.0,                /* [13] above: +inf */                                                                                \
+  -1075.0,               /* [14] below: 0 */                                                                                   \
+  0.8,                   /* [15] spicey_diode_k: upper clamp of the junction voltage */                                        \
+  1e-12                  /* [16] spicey_diode_k: floor of the conductance */
+#define SPICEY_EXP_TAB_N 17
+#define SPICEY_EXP_TAB_VHI 15
+#define SPICEY_EXP_TAB_GMIN 16
+#if defined(__HIP_DEVICE_COMPILE__)
+static __device__ __constant__ const double spicey_exp_tab_dev[SPICEY_EXP_TAB_N] = {SPICEY_EXP_TAB_VALUES};
+typedef const double __attribute__((address_space(4))) *SpiceyExpTab;
+// the table for ONE evaluation site: everything read through the result is loaded behind this point
+static __device__ __forceinline__ SpiceyExpTab spicey_exp_tab() {
+  SpiceyExpTab t = (SpiceyExpTab)spicey_exp_tab_dev;
+  asm volatile("" : "+s"(t));
+  return t;
+}
+#else
+typedef const double *SpiceyExpTab;
+static inline SpiceyExpTab spicey_exp_tab() {
+  static const double tab[SPICEY_EXP_TAB_N] = {SPICEY_EXP_TAB_VALUES};
+  return tab;
+}
+#endif
+SPICEY_HD double spicey_exp_port(double x, SpiceyExpTab t) {
+  const double dn = __builtin_rint(x * t[0]);
+  const double r = __builtin_fma(dn, t[2], __builtin_fma(dn, t[1], x));
+  double p = __builtin_fma(r, t[3], t[4]);
+  p = __builtin_fma(r, p, t[5]);
+  p = __builtin_fma(r, p, t[6]);
+  p = __builtin_fma(r, p, t[7]);
+  p = __builtin_fma(r, p, t[8]);
+  p = __builtin_fma(r, p, t[9]);
+  p = __builtin_fma(r, p, t[10]);
+  p = __builtin_fma(r, p, t[11]);
+  p = __builtin_fma(r, p, t[12]);
+  p = __builtin_fma(r, p, 1.0);
+  p = __builtin_fma(r, p, 1.0);
+#if defined(__HIP_DEVICE_COMPILE__)
+  double z = __builtin_ldexp(p, (int)dn);
+#else
+  // (the conversion saturates on the GPU; here an argument outside the int range is one of the two cases below, or NaN)
+  double z = __builtin_ldexp(p, (dn > -4096.0 && dn < 4096.0) ? (int)dn : 0);
+#endif
+  z = x > t[13] ? __builtin_inf() : z;
+  z = x < t[14] ? 0.0 : z;
+  return z;
+}
+// exp(x) where a diode is evaluated: the port on the GPU; the host's libm in host builds (the emulators compare against an
+// oracle that uses it — spicey_exp_port compiles there too, for the test of the port itself)
+SPICEY_HD double spicey_exp(double x, SpiceyExpTab t) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return spicey_exp_port(x, t);
+#else
+  (void)t;
+  return exp(x);
+#endif
+}
+SPICEY_HD double spicey_exp(double x) { return spicey_exp(x, spicey_exp_tab()); }
+
 // Diode companion model, simulateTRAN.ts:87-98, and (when `want_i`) the recorded current of :214-217,
 // which uses the UNCLAMPED junction voltage.  One exp serves both whenever vd lies inside the clamp
 // window [-1, 0.8].  The per-diode constants 1/(N VT) and Is/(N VT) are formed once per evaluation
 // from Is, N (two divisions); callers on the hot path pass them precomputed.
+// PORT: exp is spicey_exp and the model's own literals come from its table, taken here, once per evaluation — for the
+// kernels at their register cap (the fresh packed shape: TranPhases2 asks for it there).  Measured on the MI355X
+// (profiles/NOTES_r19.md §5): the kernels with registers to spare lose by it — the table's scalar loads stand in front
+// of every evaluation, 2.7 % of a step of the single-instance 1024-thread kernel — so they keep the library's exp and the
+// literals, and are compiled exactly as before.  Same bits either way.
+template <bool PORT = false>
 SPICEY_HD void spicey_diode_k(double vd, double is, double inv_vt, double is_vt, bool want_i, double &gd, double &ieq, double &irec) {
+  SpiceyExpTab t = nullptr;
+  double vhi = 0.8, gmin = 1e-12;
+  if constexpr (PORT) {
+    t = spicey_exp_tab();
+    vhi = t[SPICEY_EXP_TAB_VHI];
+    gmin = t[SPICEY_EXP_TAB_GMIN];
+  }
   double vl = vd;
-  if (vd > 0.8) vl = 0.8;
+  if (vd > vhi) vl = vhi;
   if (vd < -1.0) vl = -1.0;
-  const double e = exp(vl * inv_vt);
+  const double e = PORT ? spicey_exp(vl * inv_vt, t) : exp(vl * inv_vt);
   const double id = is * (e - 1.0);
-  gd = spicey_max_nan(is_vt * e, 1e-12);
+  gd = spicey_max_nan(is_vt * e, gmin);
   ieq = id - gd * vl;
   irec = id;
-  if (want_i && vl != vd) irec = is * (exp(vd * inv_vt) - 1.0);
+  if (want_i && vl != vd) irec = is * ((PORT ? spicey_exp(vd * inv_vt, t) : exp(vd * inv_vt)) - 1.0);
 }
 SPICEY_HD void spicey_diode(double vd, double is, double nn, double &gd, double &ieq) {
   const double vt = nn * SPICEY_VT300;

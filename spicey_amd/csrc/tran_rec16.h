@@ -57,6 +57,9 @@ struct ResRegs {
   // fresh build: this thread's first streamed record of factor phase 0 (a 32-byte row record), fetched under phase B —
   // TranPhases2::u0_fetch writes all eight words on every path of B, spicey_uk_phase consumes them in phase 0 and clears
   // them at the end of every factor phase, so they are live from B to U_0 only.  Untouched in every other build.
+  // Resident-record form of that build (tran_v2_run.h: UR): TranPhases2::load_resident fills the eight words ONCE — the
+  // record is the same 32 bytes in every step of a run — a thread at or beyond the record count holds zeros (no VALID flag:
+  // nothing runs), spicey_u0_resident_phase executes them in phase 0 and nothing fetches or clears them: live for the run.
   uint32_t u0[SpiceyShapeKind<RMAX, NSV, NEL>::fresh ? 8 : 1];
 };
 
@@ -277,7 +280,9 @@ struct SpiceyPt {
 
 // P, Q: the argument structs where they live (global memory on the GPU).  Nothing is fetched from them, or from the phase
 // table, before it is needed: a resident phase of tasks with at most two products reads no argument at all.
-template <int K, int RMAX, int NSV, int NEL, bool KTASK, bool OPG = false, bool OA = false>
+// UR (the resident-record form of the fresh build, tran_v2_run.h): rr.u0 is not this function's — phase 0 runs
+// spicey_u0_resident_phase instead, and the other factor phases leave the words alone.
+template <int K, int RMAX, int NSV, int NEL, bool KTASK, bool OPG = false, bool OA = false, bool UR = false>
 SPICEY_HD void spicey_uk_phase(const SpiceyProg &P, const SpiceyResident &Q, const SpiceyPt pt, const WgCtx<K> &c, ResRegs<K, RMAX, NSV, NEL> &rr, int tid,
                                int T, int p, bool streamed, bool reuse = false) {
   constexpr bool FRESH = SpiceyShapeKind<RMAX, NSV, NEL>::fresh;
@@ -328,7 +333,7 @@ SPICEY_HD void spicey_uk_phase(const SpiceyProg &P, const SpiceyResident &Q, con
     rr.cursor = q;
   }
   if (!streamed) {
-    if (FRESH && !KTASK) for (int i = 0; i < 8; i++) rr.u0[FRESH ? i : 0] = 0u;
+    if (FRESH && !KTASK && !UR) for (int i = 0; i < 8; i++) rr.u0[FRESH ? i : 0] = 0u;
     return;
   }
   // one 32-byte descriptor says where the phase's records are (SpiceyResident::st_desc): from the phase table in LDS — one
@@ -401,5 +406,19 @@ SPICEY_HD void spicey_uk_phase(const SpiceyProg &P, const SpiceyResident &Q, con
       }
     }
   }
-  if (FRESH && !KTASK) for (int i = 0; i < 8; i++) rr.u0[FRESH ? i : 0] = 0u;  // (consumed, or not for this phase: dead until the next B)
+  if (FRESH && !KTASK && !UR) for (int i = 0; i < 8; i++) rr.u0[FRESH ? i : 0] = 0u;  // (consumed, or not for this phase: dead until the next B)
+}
+
+// UR: factor phase 0 of a run whose level 0 is nothing but row records, at most one per thread (the host has made sure:
+// launch_plan.h, spicey_plan_u0_resident) — the record has been in rr.u0 since the prologue.  No table row, no descriptor,
+// no loop and no streamed path; the same record through the same spicey_exec_row16 as the streamed phase runs it, so the
+// same bits.  The words are made opaque here like the resident slots', so that nothing decoded from them is kept around
+// the time loop.  (Such a run never reuses a factorisation: rhs_only = false.)
+template <int K, int RMAX, int NSV, int NEL, bool OA = false>
+SPICEY_HD void spicey_u0_resident_phase(const WgCtx<K> &c, ResRegs<K, RMAX, NSV, NEL> &rr) {
+  constexpr bool FRESH = SpiceyShapeKind<RMAX, NSV, NEL>::fresh;
+  static_assert(FRESH, "the resident level-0 record is a form of the fresh build");
+  uint32_t w[8];
+  for (int i = 0; i < 8; i++) { w[i] = rr.u0[FRESH ? i : 0]; SPICEY_OPAQUE(w[i]); }
+  spicey_exec_row16<K, false, FRESH, OA>(c, w, false);
 }

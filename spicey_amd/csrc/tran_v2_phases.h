@@ -161,7 +161,22 @@ struct TranPhases2 {
     return g;
   }
 
+  // UR (the resident-record form of the fresh build, tran_v2_run.h): row record `tid` of factor phase 0 is loaded here, once
+  // per run, from the address u0_fetch reads in every step of the other forms; a thread at or beyond the record count gets
+  // zeros — no VALID flag, nothing executes.  (The host has made sure that the phase is streamed as row records, at most
+  // one per thread and nothing else: spicey_plan_u0_resident.)
+  template <bool UR = false>
   SPICEY_HD void load_resident(int tid, const SpiceyResident &Q, Regs &rr) const {
+    if constexpr (UR) {
+      static_assert(FRESH, "the resident level-0 record is a form of the fresh build");
+      const uint32_t *dsc = Q.st_desc;  // (phase 0's descriptor: row-record flag, first record, count)
+      const bool have = dsc[0] != 0u && (uint32_t)tid < dsc[2];
+      for (int i = 0; i < 8; i++) rr.u0[FRESH ? i : 0] = 0u;
+      if (have) {
+        const uint32_t *src = P.fus16 + (size_t)dsc[1] * 4 + (size_t)tid * 8;
+        for (int i = 0; i < 8; i++) rr.u0[FRESH ? i : 0] = src[i];
+      }
+    }
     for (int s = 0; s < RMAX; s++) {
       const bool have = s < Q.rmax;
       const uint32_t *src = Q.res + ((size_t)(have ? s : 0) * T + tid) * 4;
@@ -240,7 +255,7 @@ struct TranPhases2 {
       for (int i = tid; i < P.nD; i += T) {
         const double *dp = R.dpar + (in * P.nD + i) * 2;
         double g2, q, irec;
-        spicey_diode_k(R.D_vdprev[in * P.nD + i], R.D_is[in * P.nD + i], dp[0], dp[1], false, g2, q, irec);
+        spicey_diode_k<FRESH>(R.D_vdprev[in * P.nD + i], R.D_is[in * P.nD + i], dp[0], dp[1], false, g2, q, irec);
         c.gd[(size_t)(P.nS + i) * K + k] = g2;
         c.u[(size_t)(oD + i) * K + k] = q;
         if (DIAG && R.lin_vd && c.valid[k]) R.lin_vd[in * P.nD + i] = R.D_vdprev[in * P.nD + i];
@@ -313,9 +328,11 @@ struct TranPhases2 {
       for (int i = 0; i < 8; i++) rr.u0[FRESH ? i : 0] = src[i];
     }
   }
+  // UR: the record is resident (load_resident) — B fetches nothing
+  template <bool UR = false>
   SPICEY_HD void b_phase(int tid, int64_t step, Regs &rr, bool reuse) const {
     double sn = (K == 1 && !EP) ? z_src_fetch(tid, step, (size_t)c.inst[0]) : 0.0;  // (EP: fetched by z_early, parked by the last backward phase)
-    if (FRESH) u0_fetch(tid, rr);
+    if (FRESH && !UR) u0_fetch(tid, rr);
     SPICEY_SCHED_FENCE;
     b_stamp(tid, rr, reuse);
     SPICEY_SCHED_FENCE;
@@ -640,7 +657,7 @@ struct TranPhases2 {
         const double *dp = R.dpar + (in * P.nD + i) * 2;
         double g2, q, irec;
         const double vd = dv16(P.D_ab[i], k);
-        spicey_diode_k(vd, R.D_is[in * P.nD + i], dp[0], dp[1], false, g2, q, irec);
+        spicey_diode_k<FRESH>(vd, R.D_is[in * P.nD + i], dp[0], dp[1], false, g2, q, irec);
         c.gd[(size_t)(P.nS + i) * K + k] = g2;
         c.u[(size_t)(oD + i) * K + k] = q;
         if (DIAG && R.lin_vd && c.valid[k]) R.lin_vd[in * P.nD + i] = vd;
@@ -657,7 +674,7 @@ struct TranPhases2 {
   }
   SPICEY_HD void z_dio(int i, double vd, int k, size_t in, double is, double dp0, double dp1, double *oi, int cD, int oD, bool last) const {
     double gg, q, irec;
-    spicey_diode_k(vd, is, dp0, dp1, oi != nullptr, gg, q, irec);
+    spicey_diode_k<FRESH>(vd, is, dp0, dp1, oi != nullptr, gg, q, irec);
     if (oi) SPICEY_STREAM_STORE(&oi[cD + i], irec);
     c.gd[(size_t)(P.nS + i) * K + k] = gg;
     c.u[(size_t)(oD + i) * K + k] = q;
@@ -680,7 +697,7 @@ struct TranPhases2 {
   }
   SPICEY_HD void z_dio_at(int i, double vd, size_t in, double is, double dp0, double dp1, double *sec, int oD, bool last) const {
     double gg, q, irec;
-    spicey_diode_k(vd, is, dp0, dp1, sec != nullptr, gg, q, irec);
+    spicey_diode_k<FRESH>(vd, is, dp0, dp1, sec != nullptr, gg, q, irec);
     if (sec) SPICEY_STREAM_STORE(row_at(sec, i), irec);
     c.gd[(size_t)(P.nS + i)] = gg;
     c.u[(size_t)(oD + i)] = q;

@@ -200,13 +200,20 @@ struct SpiceyHasIdleWaves<E, decltype((void)E::idle_waves)> { static constexpr b
 // TR (the register-exchange top, spicey_pcr_all_regs above): an operand-address build on the GPU whose unrolled top keeps
 // its rows in registers; the caller has made sure that the top has 1 .. 6 stages (a top outside that range runs the staged
 // form here as in every build).  Host executors run spicey_pcr_stage whatever TR says.
-template <int K, int RMAX, int NSV, int NEL, bool HYB = false, int PT = -1, bool EP = false, bool OS = false, bool RA = false, bool OA = false, bool TR = false, class Exec>
+// UR (the resident level-0 record, a form of the register-exchange-top build of the fresh shape): factor level 0 of the
+// packed chains is the one streamed phase of this shape, and its record — one 32-byte row record per thread — is the same
+// in every step.  The prologue loads it once (TranPhases2::load_resident), B fetches nothing, phase 0 executes the
+// registers (spicey_u0_resident_phase: no table row, no loop, no streamed path) and no factor phase clears them or waits
+// for a fetch.  The caller has made sure that phase 0 is streamed in its row-record encoding, has at most T row records
+// and no generic remainder, and that the run never reuses a factorisation (launch_plan.h: spicey_plan_u0_resident).
+template <int K, int RMAX, int NSV, int NEL, bool HYB = false, int PT = -1, bool EP = false, bool OS = false, bool RA = false, bool OA = false, bool TR = false, bool UR = false, class Exec>
 SPICEY_HD void spicey_tran_run_v2(Exec &ex, const SpiceyProg &P, const SpiceyResident &Q, const SpiceyRun &R, WgCtx<K> &c, int wg) {
   const int T = ex.threads();
   static_assert(!OS || PT != 0, "the operand slots lie behind the phase table");
   static_assert(!RA || OS, "the ready arguments are a form of the operand-slot build");
   static_assert(!OA || RA, "the operand addresses are a form of the ready-argument build");
   static_assert(!TR || (OA && K == 1), "the register-exchange top is a form of the operand-address build");
+  static_assert(!UR || (TR && !HYB && SpiceyShapeKind<RMAX, NSV, NEL>::fresh), "the resident level-0 record is a form of the register-exchange-top build of the fresh shape");
   typedef TranPhases2<K, RMAX, NSV, NEL, HYB, EP, OS, RA, OA> Ph2;
   uint32_t brem, zrem;
   {
@@ -225,7 +232,7 @@ SPICEY_HD void spicey_tran_run_v2(Exec &ex, const SpiceyProg &P, const SpiceyRes
     Ph2 p2{Pf, Rf, c, T, brem, zrem};
     if (tid == 0) { c.flags[0] = 0; c.flags[1] = 0; c.flags[2] = -1; }
     ph.p0_gstat(tid);
-    p2.load_resident(tid, Qf, ex.template regs<Regs>(tid));
+    p2.template load_resident<UR>(tid, Qf, ex.template regs<Regs>(tid));
     if (K == 1 && Pf.pcr_n > 0) {  // tridiagonal top: its index table sits behind the two 2 KB row buffers
       uint16_t *tab = (uint16_t *)(c.tail + 1024);
       for (int i = tid; i < Pf.pcr_n * 4; i += T) tab[i] = Pf.pcr_tab[i];
@@ -300,12 +307,12 @@ SPICEY_HD void spicey_tran_run_v2(Exec &ex, const SpiceyProg &P, const SpiceyRes
           // and with it every other build, is what it was)
           if (Ph2::FRESH) Pt.nKeep = (int32_t)SpiceyPtLanes::row(ptw, tid, 0).u32(7);
           Ph2 p2{Pt, Rt, c, T, brem, zrem, &P, &R, ptw, nullptr};
-          p2.b_phase(tid, step, ex.template regs<Regs>(tid), linear && step > 0);
+          p2.template b_phase<UR>(tid, step, ex.template regs<Regs>(tid), linear && step > 0);
         } else {
           const SpiceyProg Pf = ex.fresh(P);
           const SpiceyRun Rf = ex.fresh(R);
           Ph2 p2{Pf, Rf, c, T, brem, zrem, nullptr, nullptr, nullptr, &Q};
-          p2.b_phase(tid, step, ex.template regs<Regs>(tid), linear && step > 0);
+          p2.template b_phase<UR>(tid, step, ex.template regs<Regs>(tid), linear && step > 0);
         }
       });
       if (Ph2::DIAG && ((tp >> 18) & 1) && !(linear && step > 0))
@@ -354,8 +361,14 @@ SPICEY_HD void spicey_tran_run_v2(Exec &ex, const SpiceyProg &P, const SpiceyRes
           });
           continue;
         }
+        if constexpr (UR) {
+          if (p == 0) {  // (the record is in registers: load_resident)
+            ex.phase(SPICEY_PH_U0, [&](int tid) { spicey_u0_resident_phase<K, RMAX, NSV, NEL, OA>(c, ex.template regs<Regs>(tid)); });
+            continue;
+          }
+        }
         ex.phase(SPICEY_PH_U0 + (p < 30 ? p : 30), [&](int tid) {
-          spicey_uk_phase<K, RMAX, NSV, NEL, false, false, OA>(P, Q, SpiceyPt{ptw, pt_on, p}, c, ex.template regs<Regs>(tid), tid, T, p, p < 64 ? ((smask >> p) & 1) != 0 : true, linear && step > 0);
+          spicey_uk_phase<K, RMAX, NSV, NEL, false, false, OA, UR>(P, Q, SpiceyPt{ptw, pt_on, p}, c, ex.template regs<Regs>(tid), tid, T, p, p < 64 ? ((smask >> p) & 1) != 0 : true, linear && step > 0);
         });
       }
       // EP without idle waves: the last factor phase is peeled and fetches at its tail, after its tasks (it runs for its
@@ -364,7 +377,11 @@ SPICEY_HD void spicey_tran_run_v2(Exec &ex, const SpiceyProg &P, const SpiceyRes
         const int p = u_end - 1;
         const bool act = p < 64 ? ((active >> p) & 1) != 0 : P.ph_cnt[p] != 0;
         ex.phase(SPICEY_PH_U0 + (p < 30 ? p : 30), [&](int tid) {
-          if (act) spicey_uk_phase<K, RMAX, NSV, NEL, false, false, OA>(P, Q, SpiceyPt{ptw, pt_on, p}, c, ex.template regs<Regs>(tid), tid, T, p, p < 64 ? ((smask >> p) & 1) != 0 : true, linear && step > 0);
+          bool u0_done = false;
+          if constexpr (UR) {
+            if (act && p == 0) { spicey_u0_resident_phase<K, RMAX, NSV, NEL, OA>(c, ex.template regs<Regs>(tid)); u0_done = true; }
+          }
+          if (act && !u0_done) spicey_uk_phase<K, RMAX, NSV, NEL, false, false, OA, UR>(P, Q, SpiceyPt{ptw, pt_on, p}, c, ex.template regs<Regs>(tid), tid, T, p, p < 64 ? ((smask >> p) & 1) != 0 : true, linear && step > 0);
           SPICEY_SCHED_FENCE;
           early_fetch(tid);
         });

@@ -41,6 +41,7 @@ SIGNATURES = {
     "spicey_last_kernel_ms": (_f64, [_vp]),
     "spicey_get_info": (_i32, [_vp, _infop]),
     "spicey_top_regs_form": (_i32, [_vp, _i64]),
+    "spicey_u0_resident_form": (_i32, [_vp, _i64]),
     "spicey_last_error": (_str, [_vp]),
     "spicey_destroy": (None, [_vp]),
     "spicey_version": (_str, []),
@@ -305,6 +306,10 @@ class Handle:
     def top_regs_form(self, steps: int) -> bool:
         """Whether a run of `steps` steps takes the kernel with the register-exchange top (spicey_top_regs_form)."""
         return bool(self.L.spicey_top_regs_form(self.h, steps))
+
+    def u0_resident_form(self, steps: int) -> bool:
+        """Whether a run of `steps` steps takes the kernel that keeps level 0's row record in registers (spicey_u0_resident_form)."""
+        return bool(self.L.spicey_u0_resident_form(self.h, steps))
 
     def error(self) -> str:
         m = self.L.spicey_last_error(self.h)
