@@ -605,6 +605,101 @@ int32_t spicey_run_measure_power(SpiceyHandle *h, int64_t steps, double dt, cons
 /* Duration in ms of the last spicey_run_measure_power's product pass (both kernels), measured with HIP events. */
 double spicey_last_power_ms(SpiceyHandle *h);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Waveform VALUES (a decimated trace to plot, the waveform on the caller's own time grid, one signal's value where
+ * another crosses — SPICE's .meas FIND / DERIV ... AT / WHEN): a pass over the same step-major buffers whose answers are
+ * samples, not sums.  A request names its signal y exactly as SpiceyMeasReq does (signal, col, col_ref: one rounded
+ * subtraction per sample) and is of one of three kinds.
+ *
+ * kind 0, TRACE.  The inclusive window [step_from, step_to] (step_to = -1: the last point) of n samples in `buckets` = B
+ *   buckets, 1 <= B <= min(n, SPICEY_TRACE_MAX_BUCKETS).  Bucket b covers the steps step_from + floor(b n / B) ..
+ *   step_from + floor((b + 1) n / B) - 1, the products formed in 64-bit integers; B <= n, so no bucket is empty.  Result:
+ *   6 doubles per bucket {min, step_min, max, step_max, first, last}, 6 B in all; step_* is the absolute step of the FIRST
+ *   occurrence, as a double.  The extremes follow the rule of the measurement pass's stats inside a bucket: the bucket is
+ *   cut into sub-chunks of 256 steps counted from the bucket's own first step, each sub-chunk starts from its first sample
+ *   and uses the plain comparisons x < m and x > m in ascending step order, and the sub-chunks are combined in ascending
+ *   order by the same comparisons — so a NaN never replaces an extreme, and is one only where it is a (sub-chunk's, then
+ *   the bucket's) first sample, exactly as under stats.  With B = n the row is the waveform itself.
+ * kind 1, POINTS.  A run [first, first + count) of the call's point table (SpiceyValPoint {k, f}, shared by all
+ *   instances; 0 <= k <= n_points - 2, 0 <= f <= 1).  Per point, every operation rounded on its own (no FMA contraction):
+ *     d = y[k+1] - y[k];  value = (f == 0) ? y[k] : (f == 1) ? y[k+1] : y[k] + f d;  slope = d / dt.
+ *   Result: 4 doubles per point {k, f, value, slope}, 4 count in all.
+ * kind 2, FIND.  The same two formulas at the crossing a row of the timing pass found for THAT instance: with row =
+ *   timing[inst][timing_row] ({k_trig, t_trig, L_trig, k_targ, t_targ, L_targ, n_trig, n_targ}), k = row[3], L = row[5] and
+ *   x the edge's own signal (x_signal, x_col, x_col_ref), f = (L - x[k]) / (x[k+1] - x[k]) — the timing pass's operations in
+ *   its order, so (k + f) dt is row[4] bit for bit.  Result: 4 doubles {k, f, value, slope}.  k = -1 (edge not found), or
+ *   any k outside [0, n_points - 2], gives {-1, 0, 0, 0} and no sample is read.
+ *
+ * Each request's row sits at the head of out_stride doubles, the rest 0.  No field is a floating-point accumulation: a row
+ * is a function of the samples, dt and the request alone (kind 2: and of that instance's timing row) — not of n_inst, the
+ * launch or the other requests of the list — and is bit-identical to a plain numpy evaluation
+ * (spicey_amd.measure.reduce_reference_values).  Fields a kind does not use are ignored; reserved must be 0. */
+#define SPICEY_TRACE_MAX_BUCKETS 4096
+#define SPICEY_VAL_TRACE 0
+#define SPICEY_VAL_POINTS 1
+#define SPICEY_VAL_FIND 2
+typedef struct SpiceyValReq {
+  int32_t kind;                          /* SPICEY_VAL_TRACE, _POINTS, _FIND */
+  int32_t signal, col, col_ref;          /* y: exactly SpiceyMeasReq's signal / col / col_ref */
+  int32_t x_signal, x_col, x_col_ref;    /* kind 2: the signal of the edge (that of the timing request's targ) */
+  int32_t timing_row;                    /* kind 2: index into the timing list of the same call */
+  int64_t step_from, step_to;            /* kind 0: inclusive window; step_to = -1: the last point */
+  int64_t first, count;                  /* kind 1: the run of the point table */
+  int32_t buckets, reserved;             /* kind 0: B; reserved: 0 */
+} SpiceyValReq;                          /* 72 bytes */
+typedef struct SpiceyValPoint {
+  int64_t k;                             /* the interval [k, k + 1], 0 <= k <= n_points - 2 */
+  double f;                              /* the place in it, 0 <= f <= 1 */
+} SpiceyValPoint;                        /* 16 bytes */
+
+/* Bytes of device workspace spicey_values_device needs: the point table (n_pts x 16 bytes), the tables of the trace and of
+ * the points / find requests, then the trace partials [n_inst][sum over trace requests of B * S][6] doubles with S =
+ * ceil(ceil(n / B) / 256), each region rounded up to 256 bytes.  The partials scale with the samples the traces cover (B S
+ * <= n / 256 + 2 B), not with n_req times the chunks of the run.  -1 for a list no launch accepts (columns, buffers and the
+ * point table's values are not looked at). */
+int64_t spicey_values_workspace_bytes(int32_t n_inst, int64_t n_points, const SpiceyValReq *reqs, int32_t n_req, int64_t n_pts);
+/* The pass alone, on any DEVICE buffers d_v [n_inst][n_points][n_v] and d_i [n_inst][n_points][n_i] (or NULL): needs no
+ * handle.  reqs and pts (n_pts >= 0 records, NULL when 0) are HOST arrays; d_timing [n_inst][n_timing][8] (the result of
+ * spicey_timing_device; NULL when no request is of kind 2), d_out [n_inst][n_req][out_stride] and d_work (work_bytes >=
+ * spicey_values_workspace_bytes) are DEVICE buffers.  A clear of d_out and up to three kernels, enqueued on `stream` (a
+ * hipStream_t, NULL = default stream) without synchronising.  SPICEY_ERR_BAD_DESC, with a text that starts "values: " in
+ * spicey_last_error(NULL), nothing launched and the buffers untouched, for: an unknown kind or signal; a column out of
+ * range; a current signal with d_i == NULL; a window outside the run; buckets outside 1 .. min(n, 4096); a point run
+ * outside the table; a point's k outside [0, n_points - 2] or f outside [0, 1] or not finite; n_points < 2 with a points or
+ * find request; timing_row outside [0, n_timing) or a kind-2 request with d_timing == NULL; out_stride shorter than the
+ * longest row; dt not finite or <= 0; a workspace that is too small; n_req <= 0; null buffers; a nonzero reserved. */
+int32_t spicey_values_device(int32_t device, int32_t n_inst, int64_t n_points, double dt, const double *d_v, int32_t n_v,
+                             const double *d_i, int32_t n_i, const SpiceyValReq *reqs, int32_t n_req,
+                             const SpiceyValPoint *pts, int64_t n_pts, const double *d_timing, int32_t n_timing, double *d_out,
+                             int32_t out_stride, void *d_work, int64_t work_bytes, void *stream);
+
+/* The reduced run by struct: what the five spicey_run_measure* entry points do, with the values pass behind them and
+ * every list optional.  One transient run, currents recorded only if a request of any list names one, then on the
+ * handle's stream over the same device waveforms the passes whose count is > 0, in this order: measurement, harmonics,
+ * timing, spectrum, products, values; only their results and iters (or NULL) come back — also after SPICEY_ERR_SINGULAR.
+ * The values pass reads the timing pass's device rows as its d_timing, so a kind-2 request's timing_row indexes `treqs`.
+ * struct_bytes = sizeof(SpiceyReducedLists) of the caller's header: a later pass is appended behind the last member, and
+ * the library reads the members it knows.  SPICEY_ERR_BAD_DESC, text starting "reduced: ", nothing run, for: lists NULL;
+ * struct_bytes smaller than the 160 bytes of this version; a nonzero reserved; a negative count; every count 0; a list or
+ * result pointer NULL where its count is > 0.  A kind-2 request whose timing_row >= n_timing is refused
+ * by the values pass's own judge ("values: ...").  Everything else is as for spicey_run_measure. */
+typedef struct SpiceyReducedLists {
+  int64_t struct_bytes;
+  const SpiceyMeasReq *reqs;     double *meas;    /* [n_inst][n_req][8] */
+  const SpiceyFourReq *freqs;    double *four;    /* [n_inst][n_four][four_stride] */
+  const SpiceyTimingReq *treqs;  double *timing;  /* [n_inst][n_timing][8] */
+  const SpiceySpecReq *sreqs;    double *spec;    /* [n_inst][n_spec][spec_stride] */
+  const SpiceyPowerReq *preqs;   double *power;   /* [n_inst][n_power][SPICEY_POWER_ROW] */
+  int32_t n_req, n_four, four_stride, n_timing, n_spec, spec_stride, n_power, n_values;
+  const SpiceyValReq *vreqs;     double *values;  /* [n_inst][n_values][values_stride] */
+  const SpiceyValPoint *pts;     int64_t n_pts;
+  int32_t values_stride, reserved;                /* reserved: 0 */
+} SpiceyReducedLists;                             /* 160 bytes */
+int32_t spicey_run_reduced(SpiceyHandle *h, int64_t steps, double dt, const double *src_table, int32_t src_per_inst,
+                           const SpiceyReducedLists *lists, int32_t *iters);
+/* Duration in ms of the last spicey_run_reduced's values pass (the clear and its kernels), measured with HIP events. */
+double spicey_last_values_ms(SpiceyHandle *h);
+
 /* Library build info: "spicey_hip <abi> gfx950 …" */
 const char *spicey_version(void);
 

@@ -13,4 +13,4 @@ device to corner frequencies, peaks and point read-outs.
 """
 from .ac_batch import simulateACBatch  # noqa: F401
 from .ac_measure import measureAC, measureACBatch  # noqa: F401
-from .measure import efficiency, measureTRAN, measureTRANBatch, power  # noqa: F401
+from .measure import deriv, efficiency, find, measureTRAN, measureTRANBatch, power, sample, trace  # noqa: F401

@@ -134,6 +134,50 @@ POWER_REQ = POWER_REQ_DTYPE
 POWER_ROW = 16
 
 
+class SpiceyValReq(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("signal", C.c_int32), ("col", C.c_int32), ("col_ref", C.c_int32), ("x_signal", C.c_int32), ("x_col", C.c_int32),
+                ("x_col_ref", C.c_int32), ("timing_row", C.c_int32), ("step_from", C.c_int64), ("step_to", C.c_int64), ("first", C.c_int64),
+                ("count", C.c_int64), ("buckets", C.c_int32), ("reserved", C.c_int32)]
+
+
+class SpiceyValPoint(C.Structure):
+    _fields_ = [("k", C.c_int64), ("f", C.c_double)]
+
+
+# a list of waveform-value requests (spicey_values_device) is one array of VAL_REQ_DTYPE, its point table one of VAL_POINT_DTYPE
+VAL_REQ_DTYPE = np.dtype([("kind", "<i4"), ("signal", "<i4"), ("col", "<i4"), ("col_ref", "<i4"), ("x_signal", "<i4"), ("x_col", "<i4"), ("x_col_ref", "<i4"),
+                          ("timing_row", "<i4"), ("step_from", "<i8"), ("step_to", "<i8"), ("first", "<i8"), ("count", "<i8"), ("buckets", "<i4"),
+                          ("reserved", "<i4")])
+VAL_POINT_DTYPE = np.dtype([("k", "<i8"), ("f", "<f8")])
+assert VAL_REQ_DTYPE.itemsize == C.sizeof(SpiceyValReq) == 72 and VAL_POINT_DTYPE.itemsize == C.sizeof(SpiceyValPoint) == 16
+VAL_TRACE, VAL_POINTS, VAL_FIND = 0, 1, 2
+TRACE_MAX_BUCKETS = 4096
+VAL_TRACE_DOUBLES, VAL_POINT_DOUBLES = 6, 4
+
+
+def val_row_doubles(reqs) -> int:
+    """Doubles of a result row that holds every request of a values list: 6 per bucket, 4 per point, 4 for a find."""
+    r = np.ascontiguousarray(reqs, dtype=VAL_REQ_DTYPE).reshape(-1)
+    if not len(r):
+        return 1
+    return int(np.where(r["kind"] == VAL_TRACE, VAL_TRACE_DOUBLES * r["buckets"].astype(np.int64),
+                        np.where(r["kind"] == VAL_POINTS, VAL_POINT_DOUBLES * r["count"], VAL_POINT_DOUBLES)).max())
+
+
+class SpiceyReducedLists(C.Structure):
+    """The lists of spicey_run_reduced (include/spicey_hip.h); struct_bytes = C.sizeof(SpiceyReducedLists)."""
+    _fields_ = [("struct_bytes", C.c_int64),
+                ("reqs", C.c_void_p), ("meas", C.c_void_p), ("freqs", C.c_void_p), ("four", C.c_void_p), ("treqs", C.c_void_p), ("timing", C.c_void_p),
+                ("sreqs", C.c_void_p), ("spec", C.c_void_p), ("preqs", C.c_void_p), ("power", C.c_void_p),
+                ("n_req", C.c_int32), ("n_four", C.c_int32), ("four_stride", C.c_int32), ("n_timing", C.c_int32), ("n_spec", C.c_int32),
+                ("spec_stride", C.c_int32), ("n_power", C.c_int32), ("n_values", C.c_int32),
+                ("vreqs", C.c_void_p), ("values", C.c_void_p), ("pts", C.c_void_p), ("n_pts", C.c_int64), ("values_stride", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+assert C.sizeof(SpiceyReducedLists) == 160
+
+
 class SpiceyAcMeasReq(C.Structure):
     _fields_ = [("num_signal", C.c_int32), ("num_col", C.c_int32), ("num_col_ref", C.c_int32),
                 ("den_signal", C.c_int32), ("den_col", C.c_int32), ("den_col_ref", C.c_int32), ("what", C.c_int32), ("kind", C.c_int32),

@@ -56,7 +56,7 @@ inline int32_t spicey_open_device(int device, int *ncu, std::string &err) {
 
 // The reduction passes behind a transient run, in the order they run (spicey_abi.cpp, run_reduced): the index of a pass's
 // event pair in StreamTimers and of its time in SpiceyHandle::last_pass_ms.
-enum SpiceyPass { PASS_MEASURE = 0, PASS_FOURIER = 1, PASS_TIMING = 2, PASS_SPECTRUM = 3, PASS_POWER = 4, N_PASS = 5 };
+enum SpiceyPass { PASS_MEASURE = 0, PASS_FOURIER = 1, PASS_TIMING = 2, PASS_SPECTRUM = 3, PASS_POWER = 4, PASS_VALUES = 5, N_PASS = 6 };
 
 // A handle's stream and its timing events: ev0 / ev1 bracket the kernel of a run, pass_ev[p] the reduction pass p of a
 // *_run_measure* (created on first use; an AC handle has the measurement pass only).  Destroys what it created.  A handle

@@ -27,6 +27,7 @@
 #include "measure.h"
 #include "measure_exec.h"
 #include "power.h"
+#include "values.h"
 #include "spectrum.h"
 #include "timing.h"
 #include "timing_exec.h"
@@ -784,14 +785,28 @@ struct ReducedLists {
   const SpiceyTimingReq *treqs; int32_t n_tim; double *timing;
   const SpiceySpecReq *sreqs = nullptr; int32_t n_spec = 0; double *spec = nullptr; int32_t spec_stride = 0;
   const SpiceyPowerReq *preqs = nullptr; int32_t n_power = 0; double *power = nullptr;
+  // (spicey_run_reduced only, entry = -1: every list may be empty but not all of them, and a pass runs iff its count is > 0)
+  const SpiceyValReq *vreqs = nullptr; int32_t n_values = 0; const SpiceyValPoint *pts = nullptr; int64_t n_pts = 0; double *values = nullptr;
+  int32_t values_stride = 0;
 };
 
 // What the five entry points share: one transient run into device buffers of this call's own, the reductions on the
 // handle's stream behind it, and only their results and `iters` on the way back.
 static int32_t run_reduced(SpiceyHandle *h, int64_t steps, double dt, const double *src_table, int32_t src_per_inst, const ReducedLists &a, int32_t *iters) {
   if (!h) return SPICEY_ERR_BAD_DESC;
-  double *const outs[N_PASS] = {a.meas, a.four, a.timing, a.spec, a.power};
-  if (const int32_t rc0 = check_run_args(h, steps, outs[a.entry], src_table, src_per_inst); rc0 != SPICEY_OK) return rc0;
+  double *const outs[N_PASS] = {a.meas, a.four, a.timing, a.spec, a.power, a.values};
+  const int32_t counts[N_PASS] = {a.n_req, a.n_four, a.n_tim, a.n_spec, a.n_power, a.n_values};
+  if (a.entry < 0) {
+    int first_on = -1;
+    for (int p = N_PASS - 1; p >= 0; p--) {
+      if (counts[p] < 0) { forget_last_run(h); h->err = "reduced: every count must be >= 0"; return SPICEY_ERR_BAD_DESC; }
+      if (counts[p] > 0) first_on = p;
+    }
+    if (first_on < 0) { forget_last_run(h); h->err = "reduced: every list is empty (at least one count must be > 0)"; return SPICEY_ERR_BAD_DESC; }
+    if (const int32_t rc0 = check_run_args(h, steps, outs[first_on], src_table, src_per_inst); rc0 != SPICEY_OK) return rc0;
+    for (int p = 0; p < N_PASS; p++)
+      if (counts[p] > 0 && !outs[p]) { h->err = "reduced: a result pointer is null where its count is > 0"; return SPICEY_ERR_BAD_DESC; }
+  } else if (const int32_t rc0 = check_run_args(h, steps, outs[a.entry], src_table, src_per_inst); rc0 != SPICEY_OK) return rc0;
   if (a.entry == 1 && (a.n_req < 0 || (a.n_req > 0 && !a.meas))) { h->err = "fourier: n_req must be >= 0, and meas not null when n_req > 0"; return SPICEY_ERR_BAD_DESC; }
   if (a.entry == 2 && (a.n_req < 0 || (a.n_req > 0 && !a.meas) || a.n_four < 0 || (a.n_four > 0 && !a.four))) {
     h->err = "timing: n_req and n_four must be >= 0, and meas / four not null when their count is > 0";
@@ -807,9 +822,8 @@ static int32_t run_reduced(SpiceyHandle *h, int64_t steps, double dt, const doub
     return SPICEY_ERR_BAD_DESC;
   }
   // (a pass runs if it is the entry point's own, or an earlier one whose list is not empty)
-  const int32_t counts[N_PASS] = {a.n_req, a.n_four, a.n_tim, a.n_spec, a.n_power};
   bool on[N_PASS];
-  for (int p = 0; p < N_PASS; p++) on[p] = p == a.entry || (p < a.entry && counts[p] != 0);
+  for (int p = 0; p < N_PASS; p++) on[p] = a.entry < 0 ? counts[p] > 0 : p == a.entry || (p < a.entry && counts[p] != 0);
   const SpiceyProg &P = h->hp.hdr;
   const int32_t ni = h->plan.n_inst;
   const int64_t np = steps + 1;
@@ -830,14 +844,21 @@ static int32_t run_reduced(SpiceyHandle *h, int64_t steps, double dt, const doub
     return SPICEY_ERR_BAD_DESC;
   std::vector<SpiceyPowerDevReq> ptable;
   if (on[PASS_POWER] && !spicey_power_judge(ni, np, dt, true, P.nOut, true, P.nCur, a.preqs, a.n_power, true, INT64_MAX, ptable, h->err)) return SPICEY_ERR_BAD_DESC;
+  SpiceyValPlan vplan;
+  if (on[PASS_VALUES] && !spicey_val_judge(ni, np, dt, true, P.nOut, true, P.nCur, a.vreqs, a.n_values, a.pts, a.n_pts, on[PASS_TIMING], a.n_tim, true, a.values_stride,
+                                           INT64_MAX, vplan, h->err))
+    return SPICEY_ERR_BAD_DESC;
   const auto names_a_current = [](const auto &list) { return std::any_of(list.begin(), list.end(), [](const auto &q) { return q.signal == 1; }); };
   const bool need_i = names_a_current(table) || names_a_current(fplan.table) || names_a_current(tplan.edges) || names_a_current(splan.table) ||
-                      std::any_of(ptable.begin(), ptable.end(), [](const SpiceyPowerDevReq &q) { return q.a_signal == 1 || q.b_signal == 1; });
+                      std::any_of(ptable.begin(), ptable.end(), [](const SpiceyPowerDevReq &q) { return q.a_signal == 1 || q.b_signal == 1; }) ||
+                      names_a_current(vplan.traces) || std::any_of(vplan.points.begin(), vplan.points.end(), [](const SpiceyValDevPts &q) {
+                        return q.signal == 1 || (q.kind == SPICEY_VAL_FIND && q.x_signal == 1);
+                      });
   if (const int32_t rc0 = check_structure(h); rc0 != SPICEY_OK) return rc0;
   HIPCHK(h, hipSetDevice(h->device));
   static const char *const entry_name[N_PASS] = {"spicey_run_measure", "spicey_run_measure_fourier", "spicey_run_measure_timing", "spicey_run_measure_spectrum",
-                                                 "spicey_run_measure_power"};
-  Roctx range_run(entry_name[a.entry]);
+                                                 "spicey_run_measure_power", "spicey_run_reduced"};
+  Roctx range_run(entry_name[a.entry < 0 ? N_PASS - 1 : a.entry]);
   HostRun r;
   hipStream_t st = h->q.stream;
   // The pass table: what the blocks below do per pass.  A further pass is one more entry here (and its judge above).
@@ -850,6 +871,7 @@ static int32_t run_reduced(SpiceyHandle *h, int64_t steps, double dt, const doub
     DevBuf<double> d_out;
     DevBuf<uint8_t> d_work;
   };
+  const double *d_timing_rows = nullptr;  // (the timing pass's device rows, once they are allocated: the values pass reads them)
   Pass pass[N_PASS] = {
       {on[PASS_MEASURE], (size_t)ni * (size_t)a.n_req * 8, (size_t)work_bytes, a.meas, "spicey_launch_measure: ", [&](double *d_out, void *d_work) {
          return spicey_launch_measure(h->device, ni, np, dt, r.d_v, P.nOut, r.d_i, P.nCur, table.data(), a.n_req, d_out, d_work, st);
@@ -869,6 +891,10 @@ static int32_t run_reduced(SpiceyHandle *h, int64_t steps, double dt, const doub
        "spicey_launch_power: ", [&](double *d_out, void *d_work) {
          return spicey_launch_power(h->device, ni, np, r.d_v, P.nOut, r.d_i, P.nCur, ptable.data(), a.n_power, d_out, d_work, st);
        }},
+      {on[PASS_VALUES], (size_t)ni * (size_t)a.n_values * (size_t)a.values_stride, on[PASS_VALUES] ? (size_t)vplan.workspace_bytes(ni) : 0, a.values,
+       "spicey_launch_values: ", [&](double *d_out, void *d_work) {
+         return spicey_launch_values(h->device, ni, np, dt, r.d_v, P.nOut, r.d_i, P.nCur, vplan, a.pts, d_timing_rows, a.n_tim, d_out, a.values_stride, d_work, st);
+       }},
   };
   for (int p = 0; p < N_PASS; p++)
     if (pass[p].on) HIPCHK(h, h->q.want_pass_events(p));
@@ -879,6 +905,7 @@ static int32_t run_reduced(SpiceyHandle *h, int64_t steps, double dt, const doub
     HIPCHK(h, t.d_out.alloc(t.n_out));
     HIPCHK(h, t.d_work.alloc(t.work_bytes));
   }
+  if (on[PASS_TIMING]) d_timing_rows = pass[PASS_TIMING].d_out;
   for (double &ms : h->last_pass_ms) ms = 0.0;
   int32_t rc = spicey_run_device_src(h, steps, dt, r.d_src, src_per_inst, r.d_v, r.d_i, r.d_it, st);
   if (rc != SPICEY_OK) return rc;
@@ -945,11 +972,25 @@ extern "C" int32_t spicey_run_measure_power(SpiceyHandle *h, int64_t steps, doub
                      {4, reqs, n_req, meas, freqs, n_four, four, four_stride, treqs, n_timing, timing, sreqs, n_spec, spec, spec_stride, preqs, n_power, power}, iters);
 }
 
+extern "C" int32_t spicey_run_reduced(SpiceyHandle *h, int64_t steps, double dt, const double *src_table, int32_t src_per_inst, const SpiceyReducedLists *l,
+                                      int32_t *iters) {
+  if (!h) return SPICEY_ERR_BAD_DESC;
+  const char *what = !l ? "reduced: lists must not be null"
+                     : l->struct_bytes < (int64_t)sizeof(SpiceyReducedLists) ? "reduced: struct_bytes is smaller than sizeof(SpiceyReducedLists)"
+                     : l->reserved != 0 ? "reduced: reserved must be 0" : nullptr;
+  if (what) { forget_last_run(h); h->err = what; return SPICEY_ERR_BAD_DESC; }
+  ReducedLists a{-1, l->reqs, l->n_req, l->meas, l->freqs, l->n_four, l->four, l->four_stride, l->treqs, l->n_timing, l->timing,
+                 l->sreqs, l->n_spec, l->spec, l->spec_stride, l->preqs, l->n_power, l->power};
+  a.vreqs = l->vreqs; a.n_values = l->n_values; a.pts = l->pts; a.n_pts = l->n_pts; a.values = l->values; a.values_stride = l->values_stride;
+  return run_reduced(h, steps, dt, src_table, src_per_inst, a, iters);
+}
+
 extern "C" double spicey_last_measure_ms(SpiceyHandle *h) { return h ? h->last_pass_ms[PASS_MEASURE] : 0.0; }
 extern "C" double spicey_last_fourier_ms(SpiceyHandle *h) { return h ? h->last_pass_ms[PASS_FOURIER] : 0.0; }
 extern "C" double spicey_last_timing_ms(SpiceyHandle *h) { return h ? h->last_pass_ms[PASS_TIMING] : 0.0; }
 extern "C" double spicey_last_spectrum_ms(SpiceyHandle *h) { return h ? h->last_pass_ms[PASS_SPECTRUM] : 0.0; }
 extern "C" double spicey_last_power_ms(SpiceyHandle *h) { return h ? h->last_pass_ms[PASS_POWER] : 0.0; }
+extern "C" double spicey_last_values_ms(SpiceyHandle *h) { return h ? h->last_pass_ms[PASS_VALUES] : 0.0; }
 
 // Edge timing (include/spicey_hip.h): the reduction of timing.hip on any device buffers, no handle.
 extern "C" int64_t spicey_timing_workspace_bytes(int32_t n_inst, int64_t n_points, const SpiceyTimingReq *reqs, int32_t n_req) {
@@ -999,6 +1040,24 @@ extern "C" int32_t spicey_power_device(int32_t device, int32_t n_inst, int64_t n
     return SPICEY_ERR_BAD_DESC;
   return launch_on_device(device, "spicey_launch_power", [&]() {
     return spicey_launch_power(device, n_inst, n_points, d_v, n_v, d_i, n_i, table.data(), n_req, d_out, d_work, (hipStream_t)stream);
+  });
+}
+
+// Waveform values (include/spicey_hip.h): the pass of values.hip on any device buffers, no handle.
+extern "C" int64_t spicey_values_workspace_bytes(int32_t n_inst, int64_t n_points, const SpiceyValReq *reqs, int32_t n_req, int64_t n_pts) {
+  return spicey_val_workspace_bytes(n_inst, n_points, reqs, n_req, n_pts);
+}
+
+extern "C" int32_t spicey_values_device(int32_t device, int32_t n_inst, int64_t n_points, double dt, const double *d_v, int32_t n_v, const double *d_i,
+                                        int32_t n_i, const SpiceyValReq *reqs, int32_t n_req, const SpiceyValPoint *pts, int64_t n_pts, const double *d_timing,
+                                        int32_t n_timing, double *d_out, int32_t out_stride, void *d_work, int64_t work_bytes, void *stream) {
+  // (the call is judged before the device is touched: a refusal launches nothing)
+  SpiceyValPlan plan;
+  if (!spicey_val_judge(n_inst, n_points, dt, d_v != nullptr, n_v, d_i != nullptr, n_i, reqs, n_req, pts, n_pts, d_timing != nullptr, n_timing, d_out && d_work,
+                        out_stride, work_bytes, plan, g_err))
+    return SPICEY_ERR_BAD_DESC;
+  return launch_on_device(device, "spicey_launch_values", [&]() {
+    return spicey_launch_values(device, n_inst, n_points, dt, d_v, n_v, d_i, n_i, plan, pts, d_timing, n_timing, d_out, out_stride, d_work, (hipStream_t)stream);
   });
 }
 

@@ -89,6 +89,10 @@ SIGNATURES = {
     "spicey_run_measure_power": (_i32, [_vp, _i64, _f64, _f64p, _i32, _vp, _i32, _f64p, _vp, _i32, _f64p, _i32, _vp, _i32, _f64p, _vp, _i32, _f64p, _i32,
                                         _vp, _i32, _f64p, _i32p]),
     "spicey_last_power_ms": (_f64, [_vp]),
+    "spicey_values_workspace_bytes": (_i64, [_i32, _i64, _vp, _i32, _i64]),
+    "spicey_values_device": (_i32, [_i32, _i32, _i64, _f64, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i64, _vp, _i32, _vp, _i32, _vp, _i64, _vp]),
+    "spicey_run_reduced": (_i32, [_vp, _i64, _f64, _f64p, _i32, _vp, _i32p]),
+    "spicey_last_values_ms": (_f64, [_vp]),
     "spicey_ac_last_inst_status": (_i32, [_vp, _i32p, _i64p]),
     "spicey_ac_measure_workspace_bytes": (_i64, [_i32, _i64, _i32]),
     "spicey_ac_measure_device": (_i32, [_i32, _i32, _i64, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i64, _vp]),
@@ -272,6 +276,29 @@ def power_device(n_inst: int, n_points: int, dt: float, d_v: int, n_v: int, d_i:
     _measure_device("spicey_power_device", (n_inst, n_points, dt), d_v, n_v, d_i, n_i, _reqs(reqs, abi.POWER_REQ_DTYPE), d_out, d_work, work_bytes, device, stream)
 
 
+def values_workspace_bytes(n_inst: int, n_points: int, reqs, n_pts: int = 0) -> int:
+    """spicey_values_workspace_bytes: device workspace of values_device for this request list and a point table of n_pts
+    records; -1 for a refused one."""
+    r = _reqs(reqs, abi.VAL_REQ_DTYPE)
+    return load().spicey_values_workspace_bytes(n_inst, n_points, _reqs_ptr(r), len(r), n_pts)
+
+
+def values_device(n_inst: int, n_points: int, dt: float, d_v: int, n_v: int, d_i: int, n_i: int, reqs, pts, d_timing: int, n_timing: int, d_out: int,
+                  out_stride: int, d_work: int, work_bytes: int, device: int = 0, stream: int = 0) -> None:
+    """spicey_values_device: the values pass alone on raw device pointers (e.g. torch tensors' data_ptr()): d_v
+    [n_inst][n_points][n_v], d_i [n_inst][n_points][n_i] or 0, d_timing [n_inst][n_timing][8] (a timing pass's rows) or 0, d_out
+    [n_inst][n_req][out_stride], d_work of `work_bytes` >= values_workspace_bytes(...).  reqs: records of abi.VAL_REQ_DTYPE;
+    pts: records of abi.VAL_POINT_DTYPE (host; may be empty).  Enqueued on `stream`, no synchronisation.  A refusal raises
+    SpiceyNativeError whose `status` is the library's code (abi.ERR_BAD_DESC for a bad request list)."""
+    L = load()
+    r = _reqs(reqs, abi.VAL_REQ_DTYPE)
+    pt = _reqs(pts if len(pts) else [], abi.VAL_POINT_DTYPE)
+    rc = L.spicey_values_device(device, n_inst, n_points, dt, d_v or None, n_v, d_i or None, n_i, _reqs_ptr(r), len(r), _reqs_ptr(pt), len(pt),
+                                d_timing or None, n_timing, d_out or None, out_stride, d_work or None, work_bytes, stream or None)
+    if rc != abi.OK:
+        _fail("spicey_values_device", rc, L.spicey_last_error(None))
+
+
 class Handle:
     """Owns one SpiceyHandle (one topology, n_inst instances, one device)."""
 
@@ -428,6 +455,47 @@ class Handle:
         {min_p, max_p, step_min, step_max, sum_p, first_p, last_p, sum_aa, sum_bb, first_a, last_a, first_b, last_b, 0, 0, 0}
         (include/spicey_hip.h) and `power_ms`."""
         return self._run_reduced(4, steps, dt, src, reqs, freqs, treqs, want_iters, sreqs, preqs)
+
+    def run_reduced(self, steps: int, dt: float, src: np.ndarray, reqs=(), freqs=(), treqs=(), sreqs=(), preqs=(), vreqs=(), pts=(),
+                    want_iters: bool = True, struct_bytes: Optional[int] = None) -> dict:
+        """spicey_run_reduced: one transient run and, over the same device waveforms, every pass whose list is not empty —
+        measurement, harmonics, timing, spectrum, products, values — through one struct (abi.SpiceyReducedLists) instead of one
+        positional entry point per pass.  The lists are as for run_measure_power; vreqs: records of abi.VAL_REQ_DTYPE, pts:
+        their point table (abi.VAL_POINT_DTYPE); a find request's timing_row indexes treqs.  Returns what run_measure_power
+        returns for the passes that ran (`meas`, `four`, `timing`, `spec`, `power` are there for every list, [n_inst][0][row]
+        for an empty one) plus `values` [n_inst][n_values][abi.val_row_doubles(vreqs)] and `values_ms`.  struct_bytes: the
+        size the struct claims (tests)."""
+        f = self.flat
+        src = np.ascontiguousarray(src, dtype=np.float64)
+        per_inst = _src_layout(src, f, steps)
+        lists = {key: _reqs(r if len(r) else [], dtype) for key, r, dtype in (
+            ("meas", reqs, abi.MEAS_REQ_DTYPE), ("four", freqs, abi.FOUR_REQ_DTYPE), ("timing", treqs, abi.TIMING_REQ_DTYPE), ("spec", sreqs, abi.SPEC_REQ_DTYPE),
+            ("power", preqs, abi.POWER_REQ_DTYPE), ("values", vreqs, abi.VAL_REQ_DTYPE))}
+        pt = _reqs(pts if len(pts) else [], abi.VAL_POINT_DTYPE)
+        rows = {"meas": 8, "four": fourier_row_doubles(lists["four"]), "timing": 8, "spec": abi.spec_row_doubles(lists["spec"]), "power": abi.POWER_ROW,
+                "values": abi.val_row_doubles(lists["values"])}
+        res = {"status": 0, "detail": ""}
+        for key, r in lists.items():
+            res[key] = np.zeros((f.n_inst, len(r), rows[key]))
+        a = abi.SpiceyReducedLists()
+        a.struct_bytes = C.sizeof(a) if struct_bytes is None else struct_bytes
+        for key, lst, cnt in (("meas", "reqs", "n_req"), ("four", "freqs", "n_four"), ("timing", "treqs", "n_timing"), ("spec", "sreqs", "n_spec"),
+                              ("power", "preqs", "n_power"), ("values", "vreqs", "n_values")):
+            setattr(a, lst, _reqs_ptr(lists[key]))
+            setattr(a, cnt, len(lists[key]))
+            setattr(a, key, res[key].ctypes.data if len(lists[key]) else None)
+        a.four_stride, a.spec_stride, a.values_stride = rows["four"], rows["spec"], rows["values"]
+        a.pts, a.n_pts = _reqs_ptr(pt), len(pt)
+        iters = np.zeros((f.n_inst, steps + 1), np.int32) if want_iters else None
+        rc = self.L.spicey_run_reduced(self.h, steps, dt, _p(src, C.c_double), 1 if per_inst else 0, C.byref(a), _p(iters, C.c_int32))
+        res.update(status=rc, detail=self.error() if rc != abi.OK else "", iters=iters, partial=True)
+        kept = rc in (abi.OK, abi.ERR_SINGULAR)
+        if kept:
+            for key, last_ms in (("measure_ms", self.L.spicey_last_measure_ms), ("fourier_ms", self.L.spicey_last_fourier_ms),
+                                 ("timing_ms", self.L.spicey_last_timing_ms), ("spectrum_ms", self.L.spicey_last_spectrum_ms),
+                                 ("power_ms", self.L.spicey_last_power_ms), ("values_ms", self.L.spicey_last_values_ms)):
+                res[key] = last_ms(self.h)
+        return self._dress(res, rc, kept, kept)
 
     def run_device(self, steps: int, dt: float, d_src: int, d_out_v: int, d_out_i: int = 0, d_iters: int = 0, stream: int = 0,
                    src_per_inst: bool = False) -> None:
@@ -777,6 +845,10 @@ class HipBackend(_AcCalls):
     def run_measure_power(self, flat: abi.FlatCircuit, steps: int, dt: float, src: np.ndarray, reqs, freqs, treqs, sreqs, preqs,
                           want_iters: bool = True) -> dict:
         return self._reduced("run_measure_power", flat, steps, dt, src, reqs, freqs, treqs, sreqs, preqs, want_iters)
+
+    def run_reduced(self, flat: abi.FlatCircuit, steps: int, dt: float, src: np.ndarray, reqs=(), freqs=(), treqs=(), sreqs=(), preqs=(), vreqs=(), pts=(),
+                    want_iters: bool = True) -> dict:
+        return self._reduced("run_reduced", flat, steps, dt, src, reqs, freqs, treqs, sreqs, preqs, vreqs, pts, want_iters)
 
 
 class HipAcExactBackend(_AcCalls):

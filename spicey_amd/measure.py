@@ -95,11 +95,32 @@ source) takes element names or power(...) specs, goes down as two product reques
 -avg(source), eff = p_load / p_source (None when p_source == 0); its t_from / t_to, where given, replace the parts' own.  A
 dict without these specs takes the path it always took.
 
+Values.  A sixth family, whose answers are samples of a waveform and not sums over it (the values pass of
+spicey_run_reduced, behind the other five over the same waveforms; include/spicey_hip.h has the definition, bit for bit):
+    trace("v(out)", buckets=512)            buckets, t_first[], first[], t_min[], min[], t_max[], max[], t_last[], last[], t[], v[]
+    sample("v(out)", times)                 t[], value[], slope[]
+    find("i(L1)", when=edge("v(sw)", 6.0, "fall"))   t, value, slope, level, count
+    find("v(out)", at=1e-3) / deriv(...)    the same; deriv returns the slope as `value`
+trace() is the decimation a line chart needs: the window [t_from, t_to] (the nearest-step rule above) of n samples is cut
+into `buckets` buckets — bucket b holds the steps s0 + floor(b n / B) .. s0 + floor((b + 1) n / B) - 1 — and each gives its
+first, last, minimum and maximum sample with their times (step * dt; of equal extremes the first), so no spike is lost and
+the envelope is exact.  buckets above n is lowered to n (the waveform itself comes back); above abi.TRACE_MAX_BUCKETS after
+that it is a ValueError.  t[] / v[] is the polyline to plot: per bucket its four points in step order, points of equal step
+dropped, at most 4 B points.  sample() interpolates linearly at the given times: on the host q = t / dt (one division), k =
+min(floor(q), steps - 1), f = q - k; on the device d = y[k+1] - y[k], value = y[k] + f d (y[k] for f = 0, y[k+1] for f = 1),
+slope = d / dt.  A q less than half a step outside [0, steps] is clamped to that end (t[] reports the clamped time), further
+out is a ValueError.  find(signal, when=edge(...)) is .meas FIND ... WHEN: the edge is found per circuit by the timing pass
+(one hidden when() request in [t_from, t_to]; rel() levels work), and the signal is interpolated at that crossing's own k
+and f = (L - x[k]) / (x[k+1] - x[k]); t = (k + f) dt is when()'s t bit for bit; t, value and slope are None when the edge is
+not found; level and count are when()'s.  find(signal, at=t) is one sample() point (level and count None).  A run needs
+two points for sample() and find().  A dict without these specs takes the path it always took.
+
 reduce_reference() is the same definition in plain numpy; it is what the tests compare the device with, and what runs
 behind a backend that has no run_measure (backend.run, then reduce_reference: the CPU oracle works unchanged);
 reduce_reference_fourier() is the same for the harmonics, reduce_reference_timing() for the edge timing,
 reduce_reference_spectrum() for the spectrum (that one bit for bit: the same elementwise operations in the same order),
-reduce_reference_power() for the products (its sums in plain step order, every other field bit for bit).
+reduce_reference_power() for the products (its sums in plain step order, every other field bit for bit),
+reduce_reference_values() for the values (bit for bit: no field is a sum).
 """
 from __future__ import annotations
 
@@ -186,6 +207,33 @@ class Efficiency:
 
 
 _PRODUCTS = (Power, Efficiency)
+
+
+@dataclass(frozen=True)
+class Trace:
+    signal: str
+    buckets: int = 512
+    t_from: Optional[float] = None
+    t_to: Optional[float] = None
+
+
+@dataclass(frozen=True)
+class Sample:
+    signal: str
+    times: Tuple[float, ...]
+
+
+@dataclass(frozen=True)
+class Find:
+    signal: str
+    when: Optional["Edge"] = None  # the edge whose crossing is looked up, or
+    at: Optional[float] = None     # a time
+    t_from: Optional[float] = None
+    t_to: Optional[float] = None
+    deriv: bool = False
+
+
+_VALUES = (Trace, Sample, Find)
 
 _OF = {"minmax": abi.TIMING_MINMAX, "ends": abi.TIMING_ENDS}
 
@@ -388,6 +436,82 @@ def efficiency(load, source, *, t_from: Optional[float] = None, t_to: Optional[f
     return Efficiency(parts[0], parts[1], t_from, t_to)
 
 
+def trace(signal: str, buckets: int = 512, t_from: Optional[float] = None, t_to: Optional[float] = None) -> Trace:
+    """The window's waveform decimated to min / max / first / last per bucket, and the polyline t[] / v[] to plot; see the
+    module text."""
+    if isinstance(buckets, bool) or int(buckets) != buckets or int(buckets) < 1:
+        raise ValueError(f"trace: buckets must be an integer >= 1, got {buckets!r}")
+    return Trace(str(signal), int(buckets), t_from, t_to)
+
+
+def sample(signal: str, times) -> Sample:
+    """The signal interpolated linearly at the given times: {t[], value[], slope[]}; see the module text."""
+    ts = tuple(float(t) for t in np.asarray(times, dtype=np.float64).reshape(-1))
+    if not ts:
+        raise ValueError("sample: no times given")
+    if not all(math.isfinite(t) for t in ts):
+        raise ValueError("sample: the times must be finite")
+    return Sample(str(signal), ts)
+
+
+def _find_spec(who: str, signal, when, at, t_from, t_to, is_deriv: bool) -> Find:
+    if (when is None) == (at is None):
+        raise ValueError(f"{who}: give when=edge(...) or at=t, one of them")
+    if when is not None:
+        if not isinstance(when, Edge):
+            raise TypeError(f"{who}: when must be edge(...)")
+        return Find(str(signal), when, None, t_from, t_to, is_deriv)
+    if t_from is not None or t_to is not None:
+        raise ValueError(f"{who}: t_from / t_to go with when=, not with at=")
+    at = float(at)
+    if not math.isfinite(at):
+        raise ValueError(f"{who}: at must be finite, got {at!r}")
+    return Find(str(signal), None, at, None, None, is_deriv)
+
+
+def find(signal: str, when: Optional[Edge] = None, at: Optional[float] = None, t_from: Optional[float] = None, t_to: Optional[float] = None) -> Find:
+    """The signal's value and slope where another signal crosses a level (when=edge(...)) or at a time (at=t): {t, value,
+    slope, level, count}; see the module text."""
+    return _find_spec("find", signal, when, at, t_from, t_to, False)
+
+
+def deriv(signal: str, when: Optional[Edge] = None, at: Optional[float] = None, t_from: Optional[float] = None, t_to: Optional[float] = None) -> Find:
+    """find(...) with the slope returned as `value`."""
+    return _find_spec("deriv", signal, when, at, t_from, t_to, True)
+
+
+def make_value_reqs(rows: Sequence[tuple]) -> np.ndarray:
+    """Request records (abi.VAL_REQ_DTYPE) from tuples (kind, signal, col, col_ref, x_signal, x_col, x_col_ref, timing_row,
+    step_from, step_to, first, count, buckets)."""
+    a = np.zeros(len(rows), abi.VAL_REQ_DTYPE)
+    for k, r in enumerate(rows):
+        a[k] = tuple(r) + (0,)
+    return a
+
+
+def make_value_points(points: Sequence[tuple]) -> np.ndarray:
+    """Point records (abi.VAL_POINT_DTYPE) from tuples (k, f)."""
+    a = np.zeros(len(points), abi.VAL_POINT_DTYPE)
+    for j, kf in enumerate(points):
+        a[j] = tuple(kf)
+    return a
+
+
+def time_to_point(t: float, dt: float, steps: int, name: str = "") -> Tuple[int, float, float]:
+    """(k, f, the time it stands for) of a sample time in a run of `steps` steps of dt (module text), or ValueError."""
+    if steps < 1:
+        raise ValueError(f"measure {name!r}: a run of one point has no interval to interpolate in")
+    q = t / dt
+    if not (-0.5 < q < steps + 0.5):
+        raise ValueError(f"measure {name!r}: the time {t!r} lies half a step or more outside the run [0, {steps * dt!r}]")
+    if q < 0.0:
+        q, t = 0.0, 0.0
+    elif q > steps:
+        q, t = float(steps), steps * dt
+    k = min(int(math.floor(q)), steps - 1)
+    return k, q - k, float(t)
+
+
 def make_power_reqs(rows: Sequence[tuple]) -> np.ndarray:
     """Request records (abi.POWER_REQ_DTYPE) from tuples (a_signal, a_col, a_col_ref, b_signal, b_col, b_col_ref, neg, step_from,
     step_to)."""
@@ -549,9 +673,15 @@ class _Plan:
                 # (every edge of the spec's requests, resolved: a list in the place of the one signal)
                 parsed.append((name, spec, [tuple(None if e is None else _parse_signal(ckt, e.signal) for e in rq[:2]) for rq in spec.requests()]))
                 continue
+            if isinstance(spec, _VALUES):
+                # (the signal and, for find(when=), the edge's own: a list as above)
+                x = _parse_signal(ckt, spec.when.signal) if isinstance(spec, Find) and spec.when is not None else None
+                parsed.append((name, spec, [(_parse_signal(ckt, spec.signal), x)]))
+                continue
             if not isinstance(spec, (Stats, Cross, Fourier, Spectrum)):
                 raise TypeError(f"measure {name!r}: expected stats(...), cross(...), fourier(...), when(...), delay(...), rise_time(...), "
-                                f"fall_time(...), settle(...), spectrum(...), dominant(...), power(...) or efficiency(...), got {type(spec).__name__}")
+                                f"fall_time(...), settle(...), spectrum(...), dominant(...), power(...), efficiency(...), trace(...), sample(...), find(...) or "
+                                f"deriv(...), got {type(spec).__name__}")
             parsed.append((name, spec, _parse_signal(ckt, spec.signal)))
         sigs = [s for _, _, p in parsed for s in ([e for rq in p for e in rq if e is not None] if isinstance(p, list) else [p])]
         nodes = sorted({n for sig, a, b in sigs if sig == 0 for n in (a, b) if n != 0})
@@ -559,7 +689,7 @@ class _Plan:
         # (a device descriptor records at least one node; with current measures only, the first one)
         self.out_nodes = nodes if nodes else [1]
         col = {n: c for c, n in enumerate(self.out_nodes)}
-        rows, frows, trows, srows, prows = [], [], [], [], []
+        rows, frows, trows, srows, prows, vrows, vpts = [], [], [], [], [], [], []
         # (name, "meas" | "four" | "spec" | the timing or product spec, its (first) place in reqs / freqs / sreqs / treqs / preqs), in the dict's order
         self.names = []
 
@@ -578,6 +708,32 @@ class _Plan:
             return (sig, c, cr, e.dir, e.n, abi.TIMING_ABS, 0, 0, e.level)
 
         for name, spec, where in parsed:
+            if isinstance(spec, _VALUES):
+                ysig, xsig = where[0]
+                head = (ysig[0],) + columns(*ysig)
+                self.names.append((name, spec, len(vrows)))
+                if isinstance(spec, Trace):
+                    s0 = time_to_step(spec.t_from, dt, steps, 0)
+                    s1 = time_to_step(spec.t_to, dt, steps, steps)
+                    if s0 > s1:
+                        raise ValueError(f"measure {name!r}: the window is empty (t_from maps to step {s0}, t_to to step {s1})")
+                    B = min(spec.buckets, s1 - s0 + 1)
+                    if B > abi.TRACE_MAX_BUCKETS:
+                        raise ValueError(f"measure {name!r}: {B} buckets are more than abi.TRACE_MAX_BUCKETS = {abi.TRACE_MAX_BUCKETS}")
+                    vrows.append((abi.VAL_TRACE,) + head + (0, 0, -1, 0, s0, s1, 0, 0, B))
+                elif isinstance(spec, Sample) or spec.when is None:
+                    ts = spec.times if isinstance(spec, Sample) else (spec.at,)
+                    vrows.append((abi.VAL_POINTS,) + head + (0, 0, -1, 0, 0, 0, len(vpts), len(ts), 0))
+                    vpts += [time_to_point(t, dt, steps, name) for t in ts]
+                else:
+                    s0 = time_to_step(spec.t_from, dt, steps, 0)
+                    s1 = time_to_step(spec.t_to, dt, steps, steps)
+                    if s0 >= s1:
+                        raise ValueError(f"measure {name!r}: the window has no interval (t_from maps to step {s0}, t_to to step {s1})")
+                    # (one hidden targ-only request of the timing list, as rise_time composes its own)
+                    vrows.append((abi.VAL_FIND,) + head + (xsig[0],) + columns(*xsig) + (len(trows), 0, 0, 0, 0, 0))
+                    trows.append((s0, s1, None, edge_row(name, spec.when, xsig), False))
+                continue
             if isinstance(spec, _PRODUCTS):
                 self.names.append((name, spec, len(prows)))
                 for part, (fa, fb), neg in zip(spec.parts(), where, negs[name]):
@@ -622,6 +778,9 @@ class _Plan:
         self.treqs = make_timing_reqs(trows)  # (empty: the dict takes the path without the timing pass)
         self.sreqs = make_spec_reqs(srows)  # (empty: the dict takes the path without the spectrum pass)
         self.preqs = make_power_reqs(prows)  # (empty: the dict takes the path without the product pass)
+        self.vreqs = make_value_reqs(vrows)  # (empty: the dict takes the path without the values pass)
+        self.pts = make_value_points([p[:2] for p in vpts])
+        self.pt_times = [p[2] for p in vpts]  # the time each point of the table stands for
 
     def flatten(self, ckt: ParsedCircuit) -> abi.FlatCircuit:
         flat = abi.flatten(ckt)
@@ -632,9 +791,12 @@ class _Plan:
         """What a batch groups by beside topology and run: the resolved request tables."""
         key = self.reqs.tobytes() + b"|" + self.freqs.tobytes() + (b"|" + self.treqs.tobytes() if len(self.treqs) else b"")
         key = key + b"|s|" + self.sreqs.tobytes() if len(self.sreqs) else key
-        return key + b"|p|" + self.preqs.tobytes() if len(self.preqs) else key
+        key = key + b"|p|" + self.preqs.tobytes() if len(self.preqs) else key
+        return key + b"|v|" + self.vreqs.tobytes() + b"|" + self.pts.tobytes() if len(self.vreqs) else key
 
     def run(self, be, flat: abi.FlatCircuit, steps: int, dt: float, src: np.ndarray) -> dict:
+        if len(self.vreqs):
+            return backend_reduce(be, flat, steps, dt, src, self.reqs, self.freqs, self.treqs, self.need_i, self.sreqs, self.preqs, self.vreqs, self.pts)
         return backend_reduce(be, flat, steps, dt, src, self.reqs, self.freqs, self.treqs, self.need_i, self.sreqs, self.preqs)
 
     def values(self, res: dict, j: int, dt: float) -> Dict[str, dict]:
@@ -644,6 +806,7 @@ class _Plan:
                 if kind == "four" else derive_spectrum(self.sreqs[k], res["spec"][j][k], dt) if kind == "spec"
                 else derive_power(self.preqs[k], res["power"][j][k], dt) if isinstance(kind, Power)
                 else derive_efficiency(self.preqs[k:k + 2], res["power"][j][k:k + 2], dt) if isinstance(kind, Efficiency)
+                else derive_values(kind, self.vreqs[k], res["values"][j][k], dt, self.pt_times, res["timing"][j]) if isinstance(kind, _VALUES)
                 else derive_timing(kind, res["timing"][j][k:k + len(kind.requests())])
                 for name, kind, k in self.names}
 
@@ -666,6 +829,48 @@ def derive(req, m, dt: float) -> dict:
     tf, tl = (float(m[1]), float(m[2])) if count > 0 else (None, None)
     freq = (count - 1) / (tl - tf) if count >= 2 and tl > tf else None
     return {"count": count, "t_first": tf, "t_last": tl, "freq": freq}
+
+
+def trace_buckets(req, n_points: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
+    """(first step, last step) of every bucket of a trace request, as int64 arrays; n_points resolves step_to = -1."""
+    s0, s1, B = int(req["step_from"]), int(req["step_to"]), int(req["buckets"])
+    if s1 == -1:
+        s1 = n_points - 1
+    n = s1 - s0 + 1
+    edges = s0 + np.arange(B + 1, dtype=np.int64) * n // B
+    return edges[:-1], edges[1:] - 1
+
+
+def derive_values(spec, req, row, dt: float, pt_times: Sequence[float], timing) -> dict:
+    """The values of one trace / sample / find spec from its row (module text); pt_times: the time of every point of the
+    plan's table; timing: the instance's timing rows (find(when=) reads its hidden request's)."""
+    if isinstance(spec, Trace):
+        B = int(req["buckets"])
+        lo, hi = trace_buckets(req)
+        r = np.asarray(row[:abi.VAL_TRACE_DOUBLES * B], dtype=np.float64).reshape(B, abi.VAL_TRACE_DOUBLES)
+        # per bucket first, min, max, last in step order (a stable sort: of equal steps the earlier of that list stays)
+        st = np.stack([lo.astype(np.float64), r[:, 1], r[:, 3], hi.astype(np.float64)], axis=1)
+        vs = np.stack([r[:, 4], r[:, 0], r[:, 2], r[:, 5]], axis=1)
+        order = np.argsort(st, axis=1, kind="stable")
+        st, vs = np.take_along_axis(st, order, axis=1), np.take_along_axis(vs, order, axis=1)
+        keep = np.ones_like(st, dtype=bool)
+        keep[:, 1:] = st[:, 1:] != st[:, :-1]
+        return {"buckets": B, "t_first": (lo * dt).tolist(), "first": r[:, 4].tolist(), "t_min": (r[:, 1] * dt).tolist(), "min": r[:, 0].tolist(),
+                "t_max": (r[:, 3] * dt).tolist(), "max": r[:, 2].tolist(), "t_last": (hi * dt).tolist(), "last": r[:, 5].tolist(),
+                "t": (st[keep] * dt).tolist(), "v": vs[keep].tolist()}
+    if isinstance(spec, Sample):
+        first, count = int(req["first"]), int(req["count"])
+        r = np.asarray(row[:abi.VAL_POINT_DOUBLES * count], dtype=np.float64).reshape(count, abi.VAL_POINT_DOUBLES)
+        return {"t": list(pt_times[first:first + count]), "value": r[:, 2].tolist(), "slope": r[:, 3].tolist()}
+    k, f, value, slope = (float(v) for v in row[:4])
+    if spec.when is None:
+        t, level, count = pt_times[int(req["first"])], None, None
+    else:
+        trow = timing[int(req["timing_row"])]
+        t, level, count = ((k + f) * dt if k >= 0 else None), float(trow[5]), int(trow[7])
+        if k < 0:
+            value = slope = None
+    return {"t": t, "value": slope if spec.deriv else value, "slope": slope, "level": level, "count": count}
 
 
 def derive_power(req, row, dt: float) -> dict:
@@ -1013,6 +1218,90 @@ def reduce_reference_power(out_v: np.ndarray, out_i: Optional[np.ndarray], reqs,
     return rows
 
 
+def reduce_reference_values(out_v: np.ndarray, out_i: Optional[np.ndarray], reqs, pts, dt: float, timing: Optional[np.ndarray] = None) -> np.ndarray:
+    """The definition of spicey_values_device in plain numpy, bit for bit: out_v [n_inst][n_points][n_v], out_i likewise or
+    None, reqs records of abi.VAL_REQ_DTYPE (step_to resolved or -1), pts records of abi.VAL_POINT_DTYPE, timing
+    [n_inst][n_timing][8] (the rows of the timing pass; needed by find requests) -> [n_inst][n_req][row], row = the longest
+    request's, zeros behind a request's own.  No chunks except where a NaN makes them matter: a bucket with one is walked
+    in sub-chunks of 256 steps from its own first step, as the device does."""
+    reqs = np.ascontiguousarray(reqs, dtype=abi.VAL_REQ_DTYPE).reshape(-1)
+    pts = np.ascontiguousarray(pts, dtype=abi.VAL_POINT_DTYPE).reshape(-1)
+    out_v = np.asarray(out_v, dtype=np.float64)
+    ni, n_points = out_v.shape[0], out_v.shape[1]
+    rows = np.zeros((ni, len(reqs), abi.val_row_doubles(reqs)))
+    chunk = 256
+
+    def interpolate(y, inst, k, f):
+        """{k, f, value, slope} at the points (inst[j], k[j] + f[j]): every operation a numpy operation of its own."""
+        y0, y1 = y[inst, k], y[inst, k + 1]
+        d = y1 - y0
+        return np.stack([k.astype(np.float64), f, np.where(f == 0.0, y0, np.where(f == 1.0, y1, y0 + f * d)), d / dt], axis=-1)
+
+    for r, q in enumerate(reqs):
+        kind = int(q["kind"])
+        y = _signal_samples(out_v, out_i, q, "reduce_reference_values")
+        if kind == abi.VAL_TRACE:
+            s0, B = int(q["step_from"]), int(q["buckets"])
+            s1 = n_points - 1 if int(q["step_to"]) == -1 else int(q["step_to"])
+            if not (0 <= s0 <= s1 < n_points) or not 1 <= B <= min(s1 - s0 + 1, abi.TRACE_MAX_BUCKETS):
+                raise ValueError(f"reduce_reference_values: request {r}: window [{s0}, {s1}] outside the run, or {B} buckets")
+            lo, hi = trace_buckets(q, n_points)
+            out = rows[:, r, :abi.VAL_TRACE_DOUBLES * B].reshape(ni, B, abi.VAL_TRACE_DOUBLES)
+            for b in range(B):
+                x = y[:, lo[b]:hi[b] + 1]
+                kmn, kmx = np.argmin(x, axis=1), np.argmax(x, axis=1)  # (first occurrence)
+                for i in np.nonzero(np.isnan(x).any(axis=1))[0]:  # (the comparisons x < m, x > m skip a NaN; argmin would return it)
+                    xi = x[i].tolist()
+                    part = []
+                    for c0 in range(0, len(xi), chunk):
+                        mn = mx = xi[c0]
+                        a = z = c0
+                        for k in range(c0 + 1, min(c0 + chunk, len(xi))):
+                            if xi[k] < mn:
+                                mn, a = xi[k], k
+                            if xi[k] > mx:
+                                mx, z = xi[k], k
+                        part.append((mn, a, mx, z))
+                    mn, a, mx, z = part[0]
+                    for pmn, pa, pmx, pz in part[1:]:
+                        if pmn < mn:
+                            mn, a = pmn, pa
+                        if pmx > mx:
+                            mx, z = pmx, pz
+                    kmn[i], kmx[i] = a, z
+                ii = np.arange(ni)
+                out[:, b, 0], out[:, b, 1], out[:, b, 2], out[:, b, 3] = x[ii, kmn], lo[b] + kmn, x[ii, kmx], lo[b] + kmx
+                out[:, b, 4], out[:, b, 5] = x[:, 0], x[:, -1]
+            rows[:, r, :abi.VAL_TRACE_DOUBLES * B] = out.reshape(ni, -1)
+        elif kind == abi.VAL_POINTS:
+            first, count = int(q["first"]), int(q["count"])
+            if n_points < 2 or not (0 <= first and count >= 1 and first + count <= len(pts)):
+                raise ValueError(f"reduce_reference_values: request {r}: point run [{first}, {first + count}) outside the table, or a run of one point")
+            k, f = pts["k"][first:first + count].astype(np.int64), pts["f"][first:first + count].astype(np.float64)
+            if ((k < 0) | (k > n_points - 2) | ~((f >= 0.0) & (f <= 1.0))).any():
+                raise ValueError(f"reduce_reference_values: request {r}: a point's k outside [0, {n_points - 2}] or f outside [0, 1]")
+            ii = np.repeat(np.arange(ni), count)
+            rows[:, r, :abi.VAL_POINT_DOUBLES * count] = interpolate(y, ii, np.tile(k, ni), np.tile(f, ni)).reshape(ni, -1)
+        elif kind == abi.VAL_FIND:
+            tr = int(q["timing_row"])
+            if timing is None or not 0 <= tr < np.asarray(timing).shape[1] or n_points < 2:
+                raise ValueError(f"reduce_reference_values: request {r}: timing_row {tr} outside the timing rows given, or a run of one point")
+            x = _signal_samples(out_v, out_i, {"signal": q["x_signal"], "col": q["x_col"], "col_ref": q["x_col_ref"]}, "reduce_reference_values")
+            kd, L = np.asarray(timing)[:, tr, 3], np.asarray(timing)[:, tr, 5]
+            found = (kd >= 0.0) & (kd <= float(n_points - 2))
+            rows[:, r, 0] = -1.0
+            ii = np.nonzero(found)[0]
+            if len(ii):
+                k = kd[ii].astype(np.int64)
+                a, b = x[ii, k], x[ii, k + 1]
+                with np.errstate(all="ignore"):
+                    f = (L[ii] - a) / (b - a)
+                    rows[ii, r, :4] = interpolate(y, ii, k, f)
+        else:
+            raise ValueError(f"reduce_reference_values: request {r}: unknown kind {kind}")
+    return rows
+
+
 def reduce_reference_fourier(out_v: np.ndarray, out_i: Optional[np.ndarray], reqs, dt: float) -> np.ndarray:
     """The definition of spicey_fourier_device in numpy, independent of the kernels: out_v [n_inst][n_points][n_v], out_i
     likewise or None, reqs records of abi.FOUR_REQ_DTYPE with step_to resolved or -1 -> [n_inst][n_req][1 + 2 max n_harm],
@@ -1050,11 +1339,12 @@ def reduce_reference_fourier(out_v: np.ndarray, out_i: Optional[np.ndarray], req
 
 
 def backend_reduce(be, flat: abi.FlatCircuit, steps: int, dt: float, src: np.ndarray, reqs: np.ndarray, freqs: np.ndarray, treqs: np.ndarray,
-                   need_i: bool, sreqs: Sequence = (), preqs: Sequence = ()) -> dict:
-    """The backend's run_measure_power, run_measure_spectrum, run_measure_timing, run_measure_fourier or run_measure — the
+                   need_i: bool, sreqs: Sequence = (), preqs: Sequence = (), vreqs: Sequence = (), pts: Sequence = ()) -> dict:
+    """With a values list the backend's run_reduced (every list at once); without one, as ever, the backend's run_measure_power, run_measure_spectrum, run_measure_timing, run_measure_fourier or run_measure — the
     first whose own list is not empty — or for a backend without that method its run followed by the numpy reductions of that
     method's passes."""
-    method, args = ("run_measure_power", (reqs, freqs, treqs, sreqs, preqs)) if len(preqs) else \
+    method, args = ("run_reduced", (reqs, freqs, treqs, sreqs, preqs, vreqs, pts)) if len(vreqs) else \
+        ("run_measure_power", (reqs, freqs, treqs, sreqs, preqs)) if len(preqs) else \
         ("run_measure_spectrum", (reqs, freqs, treqs, sreqs)) if len(sreqs) else ("run_measure_timing", (reqs, freqs, treqs)) if len(treqs) else \
         ("run_measure_fourier", (reqs, freqs)) if len(freqs) else ("run_measure", (reqs,))
     if hasattr(be, method):
@@ -1064,6 +1354,8 @@ def backend_reduce(be, flat: abi.FlatCircuit, steps: int, dt: float, src: np.nda
         for key, fn, lst in zip(("meas", "four", "timing", "spec", "power"),
                                 (reduce_reference, reduce_reference_fourier, reduce_reference_timing, reduce_reference_spectrum, reduce_reference_power), args):
             res[key] = fn(res["out_v"], res.get("out_i"), lst, dt)  # (an empty list: [n_inst][0][8], [n_inst][0][1])
+        if len(vreqs):
+            res["values"] = reduce_reference_values(res["out_v"], res.get("out_i"), vreqs, pts, dt, res["timing"])
     return res
 
 
@@ -1078,7 +1370,7 @@ def _backend(backend, exact_order: bool, device: int, diagnostics: bool, who: st
 
 
 def measureTRAN(ckt: ParsedCircuit, measures: Dict[str, object], *, exact_order: bool = False, device: int = 0, backend=None) -> Optional[dict]:
-    """The transient of `ckt` reduced to {name: {...}} for measures = {name: stats(...) | cross(...) | fourier(...) | when(...) | delay(...) | spectrum(...) | dominant(...) | power(...) | efficiency(...) | ...} (module text).  None
+    """The transient of `ckt` reduced to {name: {...}} for measures = {name: stats(...) | cross(...) | fourier(...) | when(...) | delay(...) | spectrum(...) | dominant(...) | power(...) | efficiency(...) | trace(...) | sample(...) | find(...) | ...} (module text).  None
     without a .tran card; SingularMatrixError and the circuit's state write-back exactly as simulateTRAN; exact_order=True
     runs the reference-order engine."""
     be = _backend(backend, exact_order, device, True, "measureTRAN")
