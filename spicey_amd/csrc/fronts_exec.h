@@ -709,6 +709,12 @@ struct FrontsRun {
   }
   // `in_lds`: the front is still in LDS from the forward sweep (stays_in_lds: q = 0) — its rows are read where they are, the
   // scratch of this solve goes behind it (where the factorisation kept the multipliers of a diagonal block)
+  // LDS doubles of the solve's vectors — xs [Mp], tt [Pp], part [4 Pp], ibnd [q <= Mp words] — and whether the U rows of a
+  // front that is solved from the workspace (p rows of Mp + 1) fit behind them
+  SPICEY_HD static size_t solve_scratch(const SpiceyFront &F) { return (size_t)F.Mp + (size_t)F.Pp * 5 + (size_t)(F.Mp >> 1) + 1; }
+  SPICEY_HD bool solve_rows_fit(const SpiceyFront &F) const {
+    return solve_scratch(F) + (size_t)F.p * (size_t)(F.Mp + 1) <= (size_t)R.front_lds_doubles;
+  }
   // (a template, not a run-time choice: a select between an LDS and a global pointer sends this hipcc into "Illegal
   // instruction detected: Operand has incorrect register class")
   template <bool in_lds = false>
@@ -722,10 +728,10 @@ struct FrontsRun {
     // xs: the front's unknowns [Pp], behind them the boundary unknowns xb [Mp - Pp] once the parent's are there
     double *xs = lds, *tt = xs + F.Mp, *part = tt + F.Pp;
     uint32_t *ibnd = (uint32_t *)(part + (size_t)F.Pp * 4);  // the boundary's unknown ids [q]: fetched before the wait
-    double *Ul = part + (size_t)F.Pp * 4 + (F.Mp >> 1) + 1, *xb = xs + F.Pp;
+    double *Ul = lds + solve_scratch(F), *xb = xs + F.Pp;  // (behind ibnd: Mp >> 1 doubles hold its Mp words)
     const uint32_t *bnd = P.fr_bnd + F.bnd0;
     const int lul = F.Mp + 1;  // (odd: a thread-per-row walk is bank-conflict free)
-    const bool res = !in_lds && (size_t)(Ul - lds) + (size_t)F.p * (size_t)lul <= (size_t)R.front_lds_doubles;
+    const bool res = !in_lds && solve_rows_fit(F);
     const double *U;  // where the block loop reads the U rows
     if constexpr (in_lds) U = A;
     else U = res ? Ul : A;

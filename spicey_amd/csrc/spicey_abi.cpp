@@ -459,7 +459,7 @@ extern "C" int32_t spicey_run_device_src(SpiceyHandle *h, int64_t steps, double 
     R.fs_list = h->d_fs + (pl.G + 1);
     R.fs_owner = R.fs_list + P.nFronts;
     R.front_flags = h->d_front_flags;
-    R.front_lds_doubles = (h->opt.debug & 8) ? 6144 : SPICEY_FRONT_LDS_DOUBLES;  // diagnostics: bit 3 = stage every front above 64 rows through panels
+    R.front_lds_doubles = (h->opt.debug & 8) ? SPICEY_FRONT_LDS_DOUBLES_DEBUG : SPICEY_FRONT_LDS_DOUBLES;  // diagnostics: bit 3 = stage every front above 64 rows through panels
     R.front_right_looking = h->knobs.front_right_looking ? 1 : 0;
   }
   if (pl.G > 1) {

@@ -236,8 +236,8 @@ extern "C" int32_t spicey_emul_run(const SpiceyDesc *d, int32_t K, int32_t T, in
     front_flags.assign((size_t)ngroups * 2 * P.nFronts, 0u);
     R.front_ws = front_ws.data(); R.fs_first = fs_first.data(); R.fs_list = fs_list.data(); R.fs_owner = fs_owner.data();
     R.front_flags = front_flags.data();
-    R.front_lds_doubles = (reverse & 8) ? 6144 : SPICEY_FRONT_LDS_DOUBLES;
-    R.front_right_looking = getenv("SPICEY_FRONT_RIGHT_LOOKING") != nullptr ? 1 : 0;  // bit 3: force the staged path for fronts above 64 rows
+    R.front_lds_doubles = (reverse & 8) ? SPICEY_FRONT_LDS_DOUBLES_DEBUG : SPICEY_FRONT_LDS_DOUBLES;  // bit 3: force the staged path for fronts above 64 rows
+    R.front_right_looking = getenv("SPICEY_FRONT_RIGHT_LOOKING") != nullptr ? 1 : 0;
     if (info) info->tail_levels = P.nFronts;  // (diagnostic: number of fronts)
   }
   std::vector<double> hybG, hybUG;
@@ -492,6 +492,49 @@ extern "C" int32_t spicey_emul_front_stats(const SpiceyDesc *d, int32_t front_cu
       if ((int)list[s] < cap) { owner[list[s]] = w; seq[list[s]] = (int32_t)(s - first[w]); }
   for (int f = 0; f < hp.hdr.nFronts && f < cap; f++) {
     k0[f] = hp.fronts[f].k0; p[f] = hp.fronts[f].p; q[f] = hp.fronts[f].q; parent[f] = hp.fronts[f].parent;
+  }
+  return SPICEY_OK;
+}
+
+// Which path of fronts_exec.h every front takes, from FrontsRun's own predicates (tests/test_front_paths.py): per front
+// SPICEY_CENSUS_COLS words — k0, p, q, Pp, Mp, parent, owner and place in the owner's list under a G-workgroup schedule,
+// number of children; fits_lds with the product's LDS budget and with the one of the stage_fronts diagnostic;
+// left_lds_need within the budget (else the right-looking sweep is the automatic fallback); solve_rows_fit under the two
+// budgets; stays_in_lds in a group of G workgroups (the group kernel's executor: keep_root).  meta as in front_stats.
+#define SPICEY_CENSUS_COLS 16
+extern "C" int32_t spicey_emul_front_census(const SpiceyDesc *d, int32_t front_cut, int32_t G, int32_t cap, int32_t *meta /*[4]*/, int32_t *out /*[cap][16]*/) {
+  HostProgram hp;
+  std::string err;
+  int32_t rc = spicey_build_program(d, hp, err, true, front_cut);
+  if (rc != SPICEY_OK) return rc;
+  if (G < 1) return SPICEY_ERR_BAD_DESC;
+  SpiceyProg P = hp.bind(hp.blob.data());
+  meta[0] = P.nFronts; meta[1] = P.front_cut; meta[2] = P.max_front_mp; meta[3] = P.nLevels;
+  std::vector<uint32_t> first, list;
+  spicey_build_front_schedule(hp, G, first, list);
+  SeqExec ex{64, false};
+  static_assert(SeqExec::keep_root, "the census reports stays_in_lds as the group kernel sees it");
+  for (int budget = 0; budget < 2; budget++) {
+    SpiceyRun R{};
+    R.fs_first = first.data(); R.fs_list = list.data();
+    R.front_lds_doubles = budget ? SPICEY_FRONT_LDS_DOUBLES_DEBUG : SPICEY_FRONT_LDS_DOUBLES;
+    const FrontsRun<SeqExec> fr{ex, P, R, nullptr, nullptr, 0, 1, nullptr, nullptr, 64, nullptr};
+    for (int w = 0; w < G; w++)
+      for (uint32_t s = first[w]; s < first[w + 1]; s++) {
+        const int f = (int)list[s];
+        if (f >= cap) continue;
+        const SpiceyFront F = P.fr[f];
+        int32_t *o = out + (size_t)f * SPICEY_CENSUS_COLS;
+        if (!budget) {
+          o[0] = F.k0; o[1] = F.p; o[2] = F.q; o[3] = F.Pp; o[4] = F.Mp; o[5] = F.parent; o[6] = w; o[7] = (int32_t)(s - first[w]);
+          o[8] = (int32_t)F.child_n;
+          o[11] = fr.left_lds_need(F) <= SPICEY_FRONT_LDS_DOUBLES ? 1 : 0;  // (factor_global's own comparison)
+          o[14] = fr.stays_in_lds(F, s, w) ? 1 : 0;
+          o[15] = 0;
+        }
+        o[9 + budget] = fr.fits_lds(F) ? 1 : 0;
+        o[12 + budget] = fr.solve_rows_fit(F) ? 1 : 0;
+      }
   }
   return SPICEY_OK;
 }

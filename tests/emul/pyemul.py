@@ -181,6 +181,29 @@ def bin_stats(flat: abi.FlatCircuit, front_cut: int = -1) -> dict:
     return dict(zip(("bins", "cut", "factor_slices", "interface_slices", "backward_slices", "widest_bin_slices"), list(out)))
 
 
+CENSUS_COLS = ("k0", "p", "q", "Pp", "Mp", "parent", "owner", "seq", "children", "fits_lds", "fits_lds_staged", "left_fits",
+               "rows_fit", "rows_fit_staged", "stays_in_lds", "_")
+
+
+def front_census(flat: abi.FlatCircuit, front_cut: int, G: int = 1) -> dict:
+    """Which path of fronts_exec.h every front takes, from FrontsRun's own predicates (spicey_emul_front_census): a dict of
+    int arrays [n_fronts] named by CENSUS_COLS — fits_lds / rows_fit with the product's LDS budget, *_staged with the one
+    of stage_fronts=True; owner, seq and stays_in_lds for a group of G workgroups — plus n_fronts, front_cut, max_front."""
+    L = lib()
+    L.spicey_emul_front_census.restype = C.c_int32
+    L.spicey_emul_front_census.argtypes = [C.POINTER(abi.SpiceyDesc), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    cap = flat.n_var
+    meta = np.zeros(4, np.int32)
+    out = np.zeros((max(cap, 1), len(CENSUS_COLS)), np.int32)
+    d = flat.desc()
+    rc = L.spicey_emul_front_census(C.byref(d), int(front_cut), int(G), cap, _p(meta, C.c_int32), _p(out, C.c_int32))
+    assert rc == 0, rc
+    nf = int(meta[0])
+    res = {k: out[:nf, i].copy() for i, k in enumerate(CENSUS_COLS) if k != "_"}
+    res.update(n_fronts=nf, front_cut=int(meta[1]), max_front=int(meta[2]))
+    return res
+
+
 PROGRAM_SCALARS = ("rc", "structurally_singular", "has16", "hybrid", "pcr_n", "nFronts", "nBins", "max_front_mp", "fus_pairs",
                    "ovf16", "numbering", "nLevels", "nLU", "blob_bytes", "resident_layouts")
 
