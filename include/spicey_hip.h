@@ -812,6 +812,65 @@ int32_t spicey_ac_run_measure(SpiceyAcHandle *h, int64_t n_freq, const double *f
 double spicey_ac_last_measure_ms(SpiceyAcHandle *h);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Current injection and noise analysis.  The reference has no current source, so this has no reference behaviour: it is
+ * the one thing an analogue user needs on top of simulateAC to ask for an output impedance or for thermal noise.
+ *
+ * spicey_ac_run_inject is spicey_ac_run with a current I = (re, im) injected into node_p and drawn from node_n (node ids
+ * of the descriptor, 0 = ground): after the source phasors, b[node_p - 1] += I and b[node_n - 1] -= I, at every frequency
+ * and in every instance, in every path a solve can take (the dense partial-pivoting fallback included).  vph may be NULL:
+ * every phasor zero.  Refused with SPICEY_ERR_BAD_DESC, nothing run: inj NULL, struct_bytes != sizeof(SpiceyAcInject), a node
+ * outside [0, n_nodes], node_p == node_n, a non-finite amplitude, a handle of the reference-order engine (interpreter = 3).
+ * A later spicey_ac_run on the same handle injects nothing and gives the bits it gave before.
+ *
+ * With unit injection, every phasor zero and out = v(node_p) - v(node_n), the complex symmetry of the MNA matrix of R, C, L
+ * and V makes the solution the adjoint one (DESIGN.md "Noise analysis"): out is Z_out, i(V_in) the voltage gain V_in -> out,
+ * i(R_k) the gain to out of a voltage source in series with R_k.  The noise pass reduces such a sweep:
+ *   d_spec    [n_inst][n_freq][4]  {onoise = sum_k kt4 R_k |i(R_k)|^2 in V^2/Hz, gain2 = |i(V_in)|^2 (0 without an input),
+ *                                   zout_re, zout_im}
+ *   d_contrib [n_inst][nR]         every resistor's kt4 R |i(R)|^2 integrated over the window by the trapezoidal rule, V^2
+ *   d_total   [n_inst][2]          the same integral of onoise and of onoise / gain2 (an IEEE quotient: inf / NaN show)
+ * with the fixed operation and summation order of noise_exec.h, no FMA contraction, no atomics: the CPU and the device agree
+ * on every bit.  Nothing is square-rooted or compared on the device.  A window of one frequency integrates to +0.0.
+ *   out_p, out_n   columns of out_v (d_v) of the output pair, -1 = ground; not both -1, not equal
+ *   in_col         column of out_i (d_i) of the input source's current, -1 = none
+ *   k_from, k_to   inclusive window of frequency indices, k_to = -1: the last
+ *   kt4            4 k_B T, formed on the host (k_B = 1.380649e-23); finite and >= 0
+ * The resistors' currents are the first nR columns of out_i. */
+typedef struct SpiceyAcInject {
+  int64_t struct_bytes;
+  int32_t node_p, node_n;
+  double re, im;
+} SpiceyAcInject;
+typedef struct SpiceyAcNoiseReq {
+  int64_t struct_bytes;
+  int32_t out_p, out_n, in_col, reserved;
+  int64_t k_from, k_to;
+  double kt4;
+} SpiceyAcNoiseReq;
+int32_t spicey_ac_run_inject(SpiceyAcHandle *h, int64_t n_freq, const double *freqs, const double *vph, const SpiceyAcInject *inj,
+                             double *out_v, double *out_i);
+/* Bytes of device workspace spicey_ac_noise_device needs (the request record); -1 for counts <= 0. */
+int64_t spicey_ac_noise_workspace_bytes(int32_t n_inst, int64_t n_freq, int32_t nR);
+/* The reduction alone, on any DEVICE buffers (d_v [n_inst][n_freq][n_v][2], d_i [n_inst][n_freq][n_i][2], d_R [n_inst][nR] in
+ * ohms, d_freqs [n_freq], the three results, d_work): needs no handle.  req is a HOST struct.  Enqueued on `stream` without
+ * synchronising.  SPICEY_ERR_BAD_DESC with a text containing "noise" in spicey_last_error(NULL), nothing launched, for: a
+ * null buffer, counts <= 0, nR > n_i, a column out of range, out_p == out_n, a window outside [0, n_freq) or with
+ * k_from > k_to, a bad kt4, a nonzero reserved word, a wrong struct_bytes, a workspace that is too small. */
+int32_t spicey_ac_noise_device(int32_t device, int32_t n_inst, int64_t n_freq, const double *d_v, int32_t n_v, const double *d_i, int32_t n_i,
+                               const double *d_R, int32_t nR, const double *d_freqs, const SpiceyAcNoiseReq *req, double *d_spec,
+                               double *d_contrib, double *d_total, void *d_work, int64_t work_bytes, void *stream);
+/* One injected sweep (spicey_ac_run_inject; the currents are always recorded) whose out_v / out_i stay on the device and are
+ * reduced there on the handle's stream, after the dense fallback has repaired its slots; spec [n_inst][n_freq][4], contrib
+ * [n_inst][nR] and total [n_inst][2] (HOST) come back, and in gain [n_inst][n_freq][2] (HOST, or NULL) the complex i(V_in) whose
+ * squared magnitude is gain2 (untouched when in_col = -1).  Columns are those of the handle.  The return value and
+ * spicey_ac_last_inst_status are as after spicey_ac_run: an instance with a failed solve has its code and undefined rows, the
+ * others are complete.  A refused request or injection (SPICEY_ERR_BAD_DESC, text in spicey_ac_last_error) runs nothing. */
+int32_t spicey_ac_run_noise(SpiceyAcHandle *h, int64_t n_freq, const double *freqs, const double *vph, const SpiceyAcInject *inj,
+                            const SpiceyAcNoiseReq *req, double *spec, double *contrib, double *total, double *gain);
+/* Duration in ms of the last spicey_ac_run_noise's reduction, measured with HIP events. */
+double spicey_ac_last_noise_ms(SpiceyAcHandle *h);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Result formatting fast path (host code, no GPU): the CSV text of
  *   formatTranResult(tran)       /root/reference/lib/formatting/formatTranResult.ts:1-23
  * straight from the typed arrays spicey_run filled.  Every number is Number.prototype.toPrecision(6) exactly as

@@ -9,8 +9,11 @@ Beyond the reference's surface: measureTRAN / measureTRANBatch (spicey_amd.measu
 per circuit on the device instead of returning every sample — extremes, averages and crossings (stats, cross),
 harmonics with THD (fourier) and edge timing (when, delay, rise_time, fall_time, settle); simulateACBatch (spicey_amd.ac_batch) runs many circuits' AC
 sweeps as the instances of one launch, and measureAC / measureACBatch (spicey_amd.ac_measure) reduce such sweeps on the
-device to corner frequencies, peaks and point read-outs.
+device to corner frequencies, peaks and point read-outs; simulateNoise / simulateNoiseBatch (spicey_amd.noise) run one sweep
+with a current injected at the output and reduce it on the device to output impedance, gain, thermal noise and the resistors'
+shares of it.
 """
 from .ac_batch import simulateACBatch  # noqa: F401
 from .ac_measure import measureAC, measureACBatch  # noqa: F401
+from .noise import simulateNoise, simulateNoiseBatch  # noqa: F401
 from .measure import deriv, efficiency, find, measureTRAN, measureTRANBatch, power, sample, trace  # noqa: F401

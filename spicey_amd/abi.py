@@ -194,6 +194,29 @@ AC_MEAS_EXTREMA, AC_MEAS_CROSS = 0, 1
 AC_WHAT_MAG2, AC_WHAT_RE, AC_WHAT_IM = 0, 1, 2
 
 
+class SpiceyAcInject(C.Structure):
+    """The injected current of spicey_ac_run_inject / spicey_ac_run_noise; struct_bytes = C.sizeof(SpiceyAcInject)."""
+    _fields_ = [("struct_bytes", C.c_int64), ("node_p", C.c_int32), ("node_n", C.c_int32), ("re", C.c_double), ("im", C.c_double)]
+
+
+class SpiceyAcNoiseReq(C.Structure):
+    """The request of the noise pass (include/spicey_hip.h); struct_bytes = C.sizeof(SpiceyAcNoiseReq)."""
+    _fields_ = [("struct_bytes", C.c_int64), ("out_p", C.c_int32), ("out_n", C.c_int32), ("in_col", C.c_int32), ("reserved", C.c_int32),
+                ("k_from", C.c_int64), ("k_to", C.c_int64), ("kt4", C.c_double)]
+
+
+assert C.sizeof(SpiceyAcInject) == 32 and C.sizeof(SpiceyAcNoiseReq) == 48
+NOISE_SPEC = 4  # doubles of a row of d_spec: onoise, gain2, zout_re, zout_im
+
+
+def ac_inject(node_p: int, node_n: int, amp: complex = 1.0) -> SpiceyAcInject:
+    return SpiceyAcInject(C.sizeof(SpiceyAcInject), int(node_p), int(node_n), float(complex(amp).real), float(complex(amp).imag))
+
+
+def ac_noise_req(out_p: int, out_n: int, in_col: int, kt4: float, k_from: int = 0, k_to: int = -1) -> SpiceyAcNoiseReq:
+    return SpiceyAcNoiseReq(C.sizeof(SpiceyAcNoiseReq), int(out_p), int(out_n), int(in_col), 0, int(k_from), int(k_to), float(kt4))
+
+
 def _i32(a) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.int32)
 

@@ -39,20 +39,21 @@ def slot_error(code: int, detail: str = "") -> Exception:
 
 def ac_group_launches(ckts: Sequence[ParsedCircuit], out: list, max_instances: int, max_result_bytes: int,
                       flatten: Callable[[ParsedCircuit], abi.FlatCircuit], inst_bytes: Callable[[abi.FlatCircuit, int], int],
-                      extra: Optional[Callable[[ParsedCircuit, np.ndarray], object]] = None) -> List[tuple]:
+                      extra: Optional[Callable[[ParsedCircuit, np.ndarray], object]] = None, freqs_override=None) -> List[tuple]:
     """The launches of a batched AC call as (indices into ckts, freqs): one group per (node count, topology, recorded nodes,
     frequency list bits[, extra(ckt, freqs)]), groups in the order they first appear, instances in input order, groups split
     so that a launch has at most max_instances instances and inst_bytes(flat, n_freq) * instances <= max_result_bytes.
-    Circuits without .ac take part in none; neither do those the resistor check refuses — their exception goes to out[i]."""
+    Circuits without .ac take part in none; neither do those the resistor check refuses — their exception goes to out[i].
+    freqs_override: a frequency list every circuit is swept over instead of its card's (a card is then not needed)."""
     if max_instances < 1:
         raise ValueError("max_instances must be >= 1")
     groups: Dict[tuple, List[int]] = {}
     meta: Dict[tuple, tuple] = {}
     for i, c in enumerate(ckts):
         ac = c.analyses.get("ac")
-        if not ac:
+        if not ac and freqs_override is None:
             continue
-        freqs = buildFrequencyArray(ac["mode"], ac["N"], ac["f1"], ac["f2"])
+        freqs = buildFrequencyArray(ac["mode"], ac["N"], ac["f1"], ac["f2"]) if freqs_override is None else list(freqs_override)
         try:
             _check_resistors(c, freqs)  # (the engines raise the inductors' divide errors themselves, slot by slot)
         except ValueError as e:

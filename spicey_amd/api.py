@@ -2,8 +2,9 @@
 from .ac import formatAcResult, simulateAC  # noqa: F401
 from .ac_batch import simulateACBatch  # noqa: F401
 from .netlist import parseNetlist  # noqa: F401
+from .noise import simulateNoise, simulateNoiseBatch  # noqa: F401
 from .simulate import (eecEngineTranToVGraphs, formatTranResult, simulate, simulateTRAN,  # noqa: F401
                        spiceyTranToVGraphs)
 
-__all__ = ["parseNetlist", "simulate", "simulateAC", "simulateACBatch", "simulateTRAN", "formatAcResult", "formatTranResult",
+__all__ = ["parseNetlist", "simulate", "simulateAC", "simulateACBatch", "simulateNoise", "simulateNoiseBatch", "simulateTRAN", "formatAcResult", "formatTranResult",
            "spiceyTranToVGraphs", "eecEngineTranToVGraphs"]

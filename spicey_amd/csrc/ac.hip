@@ -39,23 +39,26 @@ struct GpuAcExecRes {
 
 // Resident sweep: blockIdx.x = instance * n_chunk + c; the workgroup runs frequencies c, c + n_chunk, ... of its instance
 // with the task records and the frequency-independent stamp parts in registers (ac_exec.h).
-template <int RMAX, int NSE>
+// INJ: the build with the current injection of SpiceyAcRun::inj_* (both sweep kernels exist twice: the arguments arrive in
+// scalar registers, and the build without injection never reads the fields — it is the kernel of every plain run, with the
+// registers and the code it had before).
+template <int RMAX, int NSE, bool INJ>
 __global__ void __launch_bounds__(512) spicey_ac_kernel_res(SpiceyProg P, SpiceyResident Q, SpiceyAcRun R, int n_chunk) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   __shared__ int32_t flags[2];
   GpuAcExecRes<AcResRegs<RMAX, NSE>> ex;
-  spicey_ac_sweep_resident<RMAX, NSE>(ex, P, Q, R, (SpiceyCx *)smem, flags, (size_t)(blockIdx.x / (unsigned)n_chunk), (int64_t)(blockIdx.x % (unsigned)n_chunk),
+  spicey_ac_sweep_resident<RMAX, NSE, INJ>(ex, P, Q, R, (SpiceyCx *)smem, flags, (size_t)(blockIdx.x / (unsigned)n_chunk), (int64_t)(blockIdx.x % (unsigned)n_chunk),
                                       (int64_t)n_chunk);
 }
 
-template <bool LDS>
+template <bool LDS, bool INJ>
 __global__ void __launch_bounds__(1024) spicey_ac_kernel(SpiceyProg P, SpiceyAcRun R) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   __shared__ int32_t flags[2];
   const int64_t slot = R.slot_base + (int64_t)blockIdx.x;
   SpiceyCx *W = LDS ? (SpiceyCx *)smem : (SpiceyCx *)R.gW + (size_t)blockIdx.x * (size_t)P.nW;
   GpuAcExec ex;
-  spicey_ac_solve(ex, P, R, W, flags, slot);
+  spicey_ac_solve<INJ>(ex, P, R, W, flags, slot);
 }
 
 // Dense partial-pivoting fallback (ac_exec.h): blockIdx.x = index into the list of (instance, frequency) slots whose solve
@@ -78,19 +81,22 @@ __global__ void __launch_bounds__(1024) spicey_ac_dense_kernel(const SpiceyProg 
 }  // namespace
 
 hipError_t spicey_launch_ac_resident(const SpiceyProg &P, const SpiceyResident &Q, const SpiceyAcRun &R, int n_chunk, int threads, size_t lds_bytes, hipStream_t st) {
-  auto kern = spicey_ac_kernel_res<SPICEY_AC_RMAX, SPICEY_AC_NSE>;
+  const bool inj = (R.inj_p | R.inj_n) != 0;
+  auto kern = inj ? spicey_ac_kernel_res<SPICEY_AC_RMAX, SPICEY_AC_NSE, true> : spicey_ac_kernel_res<SPICEY_AC_RMAX, SPICEY_AC_NSE, false>;
   if (const hipError_t e = spicey_allow_dyn_lds(kern, lds_bytes); e != hipSuccess) return e;
   hipLaunchKernelGGL(kern, dim3((unsigned)(R.n_inst * n_chunk)), dim3(threads), lds_bytes, st, P, Q, R, n_chunk);
   return hipGetLastError();
 }
 
 hipError_t spicey_launch_ac(const SpiceyProg &P, const SpiceyAcRun &R, int grid, int threads, size_t lds_bytes, hipStream_t st) {
+  const bool inj = (R.inj_p | R.inj_n) != 0;
   if (lds_bytes) {
-    auto kern = spicey_ac_kernel<true>;
+    auto kern = inj ? spicey_ac_kernel<true, true> : spicey_ac_kernel<true, false>;
     if (const hipError_t e = spicey_allow_dyn_lds(kern, lds_bytes); e != hipSuccess) return e;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds_bytes, st, P, R);
   } else {
-    hipLaunchKernelGGL(spicey_ac_kernel<false>, dim3(grid), dim3(threads), 0, st, P, R);
+    auto kern = inj ? spicey_ac_kernel<false, true> : spicey_ac_kernel<false, false>;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), 0, st, P, R);
   }
   return hipGetLastError();
 }

@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <memory>
 #include <string>
@@ -25,6 +26,7 @@
 #include "ac_sweep.h"
 #include "devbuf.h"
 #include "kernels.h"
+#include "noise.h"
 #include "symbolic.h"
 
 struct AcDims { int32_t n_inst = 0, n_out = 0, n_cur = 0, n_v = 0; };
@@ -48,6 +50,13 @@ struct AcEngine {
   // slots per launch of a sweep over `slots`, and the bytes of global workspace each of them needs (0: LDS)
   virtual int64_t chunk(const SpiceyAcHandle *h, int64_t slots, int64_t n_freq) = 0;
   virtual size_t slot_ws_bytes() const = 0;
+  // the current injection of the next sweep (null: none), as node ids already checked against the descriptor; an engine
+  // without injection refuses
+  virtual int32_t set_inject(const SpiceyAcInject *inj, std::string &err) {
+    if (!inj) return SPICEY_OK;
+    err = "inject: the reference-order engine (interpreter = 3) takes no current injection";
+    return SPICEY_ERR_BAD_DESC;
+  }
   virtual int32_t bind(SpiceyAcHandle *h, const AcBuffers &b, hipStream_t st) = 0;  // the run struct of this sweep
   virtual hipError_t launch(int64_t base, int64_t count, hipStream_t st) = 0;
   // after the sweep (o.status on the host, the stream idle): what the engine adds
@@ -61,6 +70,11 @@ struct SpiceyAcHandle {
   AcDims dims;
   std::unique_ptr<AcEngine> eng;
   DevBuf<double> d_R, d_C, d_L;  // 1 / R, C, L [n_inst][n<kind>]
+  int32_t n_nodes = 0, nR = 0;
+  std::vector<double> R_host;    // R [n_inst][nR] in ohms, and on the device from the first noise pass on
+  DevBuf<double> d_Rohm;
+  bool have_Rohm = false;
+  double last_noise_ms = 0.0;
   int64_t last_slots = 0;        // (instance, frequency) slots of the last sweep
   double last_ms = 0.0, last_measure_ms = 0.0;
   SpiceyAcInstStatus ist;        // per instance of the last sweep (spicey_ac_last_inst_status)
@@ -82,6 +96,8 @@ struct AcSparse : AcEngine {
   int last_mode = 0;        // 1 = one workgroup per (instance, frequency), 2 = resident sweep
   int n_chunk = 1;          // resident sweep: workgroups per instance
   int64_t last_dense = 0;   // solves of the last run that went through the dense partial-pivoting fallback
+  int32_t inj_p = 0, inj_n = 0;  // SpiceyAcRun::inj_* of the next sweep
+  double inj_re = 0.0, inj_im = 0.0;
   SpiceyAcRun R{};
 
   int32_t plan(const SpiceyDesc *desc, const SpiceyOptions &, AcDims &dims, std::string &err) override {
@@ -120,6 +136,19 @@ struct AcSparse : AcEngine {
 
   bool structurally_singular() const override { return hp.structurally_singular; }
 
+  // The right-hand-side row of a node is the pivot position of its ROW, HostProgram::rpos — not that of its column (out_x):
+  // the source <-> node matching may permute the two differently.
+  int32_t set_inject(const SpiceyAcInject *inj, std::string &) override {
+    inj_p = inj_n = 0;
+    inj_re = inj_im = 0.0;
+    if (!inj) return SPICEY_OK;
+    const int32_t nLU = hp.hdr.nLU;
+    if (inj->node_p > 0) inj_p = 1 + nLU + hp.rpos[(size_t)inj->node_p - 1];
+    if (inj->node_n > 0) inj_n = 1 + nLU + hp.rpos[(size_t)inj->node_n - 1];
+    inj_re = inj->re; inj_im = inj->im;
+    return SPICEY_OK;
+  }
+
   int64_t chunk(const SpiceyAcHandle *h, int64_t slots, int64_t n_freq) override {
     // batches that outnumber the CUs (one workgroup per CU at this LDS size): persistent workgroups, ~2 per CU, each
     // keeping its share of the program in registers across its frequencies — one launch
@@ -137,6 +166,7 @@ struct AcSparse : AcEngine {
     R.R_inv = b.R_inv; R.C_val = b.C_val; R.L_val = b.L_val;
     R.freqs = b.freqs; R.vph = b.vph; R.out_v = b.out_v; R.out_i = b.out_i; R.gW = (double *)b.gW; R.status = b.status;
     R.n_freq = b.n_freq; R.n_inst = h->dims.n_inst;
+    R.inj_p = inj_p; R.inj_n = inj_n; R.inj_re = inj_re; R.inj_im = inj_im;  // (every chunk of the sweep launches this struct)
     return SPICEY_OK;
   }
 
@@ -268,6 +298,9 @@ static int32_t ac_allocate(SpiceyAcHandle *h, const SpiceyDesc *desc) {
   if (rc == SPICEY_OK) rc = h->eng->upload(h, desc);
   if (rc != SPICEY_OK) return rc;
   const size_t ni = (size_t)h->dims.n_inst;
+  h->n_nodes = desc->n_nodes;
+  h->nR = desc->nR;
+  h->R_host.assign(desc->R_val, desc->R_val + ni * (size_t)desc->nR);
   std::vector<double> rinv(ni * (size_t)desc->nR);
   for (size_t i = 0; i < rinv.size(); i++) rinv[i] = 1.0 / desc->R_val[i];  // (1 / R in simulateAC.ts:39-41, the same quotient)
   if (dev_upload(h->d_R, rinv.size(), rinv.data()) != hipSuccess || dev_upload(h->d_C, ni * desc->nC, desc->C_val) != hipSuccess ||
@@ -313,11 +346,22 @@ extern "C" double spicey_ac_last_kernel_ms(SpiceyAcHandle *h) { return h ? h->la
 // What spicey_ac_run and spicey_ac_run_measure share: the argument checks, then ONE sweep into `o` — staged, timed,
 // launched through the engine, o.status on the host, the stream idle.  The caller copies out or reduces.
 // *done: the call is answered without a sweep (nothing to do, or structurally singular).
-static int32_t ac_sweep(SpiceyAcHandle *h, int64_t n_freq, const double *freqs, const double *vph, bool have_out, bool want_i, SpiceyAcSweep &o, bool *done) {
+// inj: the current injection of this sweep (null: none; with one, a null vph means every phasor zero).
+static int32_t ac_sweep(SpiceyAcHandle *h, int64_t n_freq, const double *freqs, const double *vph, bool have_out, bool want_i, SpiceyAcSweep &o, bool *done,
+                        const SpiceyAcInject *inj = nullptr, DevBuf<double> *keep_freqs = nullptr) {
   *done = true;
   h->ist.forget();
   const AcDims &d = h->dims;
-  if (n_freq < 0 || (n_freq > 0 && (!freqs || !have_out)) || (d.n_v > 0 && !vph)) { h->err = "bad run arguments"; return SPICEY_ERR_BAD_DESC; }
+  if (n_freq < 0 || (n_freq > 0 && (!freqs || !have_out)) || (d.n_v > 0 && !vph && !inj)) { h->err = "bad run arguments"; return SPICEY_ERR_BAD_DESC; }
+  if (inj) {
+    const char *what = nullptr;
+    if (inj->struct_bytes != (int64_t)sizeof(SpiceyAcInject)) what = "struct_bytes is not sizeof(SpiceyAcInject)";
+    else if (inj->node_p < 0 || inj->node_p > h->n_nodes || inj->node_n < 0 || inj->node_n > h->n_nodes) what = "node outside [0, n_nodes]";
+    else if (inj->node_p == inj->node_n) what = "node_p == node_n: nothing is injected";
+    else if (!std::isfinite(inj->re) || !std::isfinite(inj->im)) what = "the amplitude must be finite";
+    if (what) { h->err = std::string("inject: ") + what; return SPICEY_ERR_BAD_DESC; }
+  }
+  if (const int32_t rc = h->eng->set_inject(inj, h->err); rc != SPICEY_OK) return rc;
   if (n_freq == 0) {
     h->ist.fill(d.n_inst, 0, -1);
     return SPICEY_OK;
@@ -335,7 +379,8 @@ static int32_t ac_sweep(SpiceyAcHandle *h, int64_t n_freq, const double *freqs, 
   o.status.assign((size_t)slots, 0);
   const int64_t chunk = h->eng->chunk(h, slots, n_freq);
   const size_t ws_bytes = (size_t)chunk * h->eng->slot_ws_bytes();
-  DevBuf<double> d_f, d_ph;
+  DevBuf<double> d_f_own, d_ph;
+  DevBuf<double> &d_f = keep_freqs ? *keep_freqs : d_f_own;  // (a caller that reduces behind the sweep keeps the frequencies)
   DevBuf<uint8_t> d_gW;
   DevBuf<int32_t> d_status;
   HIPCHK(h, d_f.alloc((size_t)n_freq));
@@ -348,7 +393,8 @@ static int32_t ac_sweep(SpiceyAcHandle *h, int64_t n_freq, const double *freqs, 
     return SPICEY_ERR_HIP;
   }
   HIPCHK(h, hipMemcpyAsync(d_f, freqs, (size_t)n_freq * sizeof(double), hipMemcpyHostToDevice, st));
-  if (d.n_v > 0) HIPCHK(h, hipMemcpyAsync(d_ph, vph, (size_t)d.n_inst * d.n_v * 2 * sizeof(double), hipMemcpyHostToDevice, st));
+  if (d.n_v > 0 && vph) HIPCHK(h, hipMemcpyAsync(d_ph, vph, (size_t)d.n_inst * d.n_v * 2 * sizeof(double), hipMemcpyHostToDevice, st));
+  else if (d.n_v > 0) HIPCHK(h, hipMemsetAsync(d_ph, 0, (size_t)d.n_inst * d.n_v * 2 * sizeof(double), st));
   const AcBuffers b{h->d_R, h->d_C, h->d_L, d_f, d_ph, o.d_ov, o.d_oi, d_gW, d_status, n_freq};
   if (const int32_t rc = h->eng->bind(h, b, st); rc != SPICEY_OK) return rc;
   HIPCHK(h, hipEventRecord(h->q.ev0, st));
@@ -361,11 +407,10 @@ static int32_t ac_sweep(SpiceyAcHandle *h, int64_t n_freq, const double *freqs, 
   return h->eng->finish(h, o, st);
 }
 
-extern "C" int32_t spicey_ac_run(SpiceyAcHandle *h, int64_t n_freq, const double *freqs, const double *vph, double *out_v, double *out_i) {
-  if (!h) return SPICEY_ERR_BAD_DESC;
+static int32_t ac_run(SpiceyAcHandle *h, int64_t n_freq, const double *freqs, const double *vph, const SpiceyAcInject *inj, double *out_v, double *out_i) {
   SpiceyAcSweep o;
   bool done = false;
-  const int32_t rc = ac_sweep(h, n_freq, freqs, vph, out_v != nullptr, out_i != nullptr, o, &done);
+  const int32_t rc = ac_sweep(h, n_freq, freqs, vph, out_v != nullptr, out_i != nullptr, o, &done, inj);
   if (rc != SPICEY_OK || done) return rc;
   const AcDims &d = h->dims;
   const size_t slots = (size_t)d.n_inst * (size_t)n_freq;
@@ -375,6 +420,18 @@ extern "C" int32_t spicey_ac_run(SpiceyAcHandle *h, int64_t n_freq, const double
   if (out_i) HIPCHK(h, hipMemcpyAsync(out_i, o.d_oi, slots * (size_t)d.n_cur * 2 * sizeof(double), hipMemcpyDeviceToHost, st));
   HIPCHK(h, hipStreamSynchronize(st));
   return h->ist.from_slots(o.status, d.n_inst, n_freq, h->err);
+}
+
+extern "C" int32_t spicey_ac_run(SpiceyAcHandle *h, int64_t n_freq, const double *freqs, const double *vph, double *out_v, double *out_i) {
+  if (!h) return SPICEY_ERR_BAD_DESC;
+  return ac_run(h, n_freq, freqs, vph, nullptr, out_v, out_i);
+}
+
+extern "C" int32_t spicey_ac_run_inject(SpiceyAcHandle *h, int64_t n_freq, const double *freqs, const double *vph, const SpiceyAcInject *inj, double *out_v,
+                                        double *out_i) {
+  if (!h) return SPICEY_ERR_BAD_DESC;
+  if (!inj) { h->ist.forget(); h->err = "inject: null injection"; return SPICEY_ERR_BAD_DESC; }
+  return ac_run(h, n_freq, freqs, vph, inj, out_v, out_i);
 }
 
 extern "C" int32_t spicey_ac_last_inst_status(SpiceyAcHandle *h, int32_t *status, int64_t *first_freq) {
@@ -424,3 +481,53 @@ extern "C" int32_t spicey_ac_run_measure(SpiceyAcHandle *h, int64_t n_freq, cons
 }
 
 extern "C" double spicey_ac_last_measure_ms(SpiceyAcHandle *h) { return h ? h->last_measure_ms : 0.0; }
+
+// The injected sweep of spicey_ac_run_inject with its buffers left on the device and the noise pass of noise.hip behind it.
+extern "C" int32_t spicey_ac_run_noise(SpiceyAcHandle *h, int64_t n_freq, const double *freqs, const double *vph, const SpiceyAcInject *inj,
+                                       const SpiceyAcNoiseReq *req, double *spec, double *contrib, double *total, double *gain) {
+  if (!h) return SPICEY_ERR_BAD_DESC;
+  h->ist.forget();
+  h->last_noise_ms = 0.0;
+  const AcDims &d = h->dims;
+  if (!inj) { h->err = "inject: null injection"; return SPICEY_ERR_BAD_DESC; }
+  // (a refused request runs nothing: judged on placeholder buffers first, the sweep's own are bound below)
+  const int64_t work_bytes = spicey_noise_workspace_bytes(d.n_inst, n_freq, h->nR);
+  const double *some = h->d_R;  // (any non-null pointer: the judge looks at null-ness only)
+  SpiceyNoiseArgs A;
+  if (!spicey_noise_judge(d.n_inst, n_freq, some, d.n_out, some, d.n_cur, some, h->nR, some, req, spec && contrib && total, work_bytes, A, h->err))
+    return SPICEY_ERR_BAD_DESC;
+  SpiceyAcSweep o;
+  DevBuf<double> d_f;
+  bool done = false;
+  const int32_t rc = ac_sweep(h, n_freq, freqs, vph, true, true, o, &done, inj, &d_f);
+  if (rc != SPICEY_OK || done) return rc;
+  hipStream_t st = h->q.stream;
+  if (!h->have_Rohm) {
+    if (dev_upload(h->d_Rohm, h->R_host.size(), h->R_host.data()) != hipSuccess) { h->err = "upload of the resistances failed"; return SPICEY_ERR_HIP; }
+    h->have_Rohm = true;
+  }
+  HIPCHK(h, h->q.want_pass_events(PASS_MEASURE));
+  const hipEvent_t *ev = h->q.pass_ev[PASS_MEASURE];
+  const size_t n_spec = (size_t)d.n_inst * (size_t)n_freq * SPICEY_NOISE_SPEC, n_con = (size_t)d.n_inst * (size_t)h->nR, n_tot = (size_t)d.n_inst * 2;
+  DevBuf<double> d_spec, d_con, d_tot;
+  DevBuf<uint8_t> d_work;
+  HIPCHK(h, d_spec.alloc(n_spec));
+  HIPCHK(h, d_con.alloc(n_con));
+  HIPCHK(h, d_tot.alloc(n_tot));
+  HIPCHK(h, d_work.alloc((size_t)work_bytes));
+  A.d_i = o.d_oi; A.d_v = o.d_ov; A.R = h->d_Rohm; A.freqs = d_f;
+  HIPCHK(h, hipEventRecord(ev[0], st));
+  HIPCHK(h, spicey_launch_noise(h->device, A, d_spec, d_con, d_tot, d_work, st));
+  HIPCHK(h, hipEventRecord(ev[1], st));
+  HIPCHK(h, hipMemcpyAsync(spec, d_spec, n_spec * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(h, hipMemcpyAsync(contrib, d_con, n_con * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(h, hipMemcpyAsync(total, d_tot, n_tot * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (gain && A.in_col >= 0)  // (the one column of out_i the host wants whole: a strided copy of 16 bytes per slot)
+    HIPCHK(h, hipMemcpy2DAsync(gain, 2 * sizeof(double), (const double *)o.d_oi + (size_t)A.in_col * 2, (size_t)d.n_cur * 2 * sizeof(double), 2 * sizeof(double),
+                               (size_t)d.n_inst * (size_t)n_freq, hipMemcpyDeviceToHost, st));
+  HIPCHK(h, hipStreamSynchronize(st));
+  StreamTimers::elapsed(ev[0], ev[1], &h->last_noise_ms);
+  return h->ist.from_slots(o.status, d.n_inst, n_freq, h->err);
+}
+
+extern "C" double spicey_ac_last_noise_ms(SpiceyAcHandle *h) { return h ? h->last_noise_ms : 0.0; }

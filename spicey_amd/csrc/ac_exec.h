@@ -26,6 +26,11 @@ struct SpiceyAcRun {
   int64_t n_freq;
   int64_t slot_base;                    // first (instance, frequency) slot of this launch (large sweeps run in chunks)
   int32_t n_inst;
+  // current injection (appended last; all zero = none): inj_p / inj_n = 1 + the W index of the right-hand-side row of the
+  // node the current enters / leaves (nLU + row position), 0 = ground or absent; b[p] += I, b[n] -= I after the source
+  // phasors, I = (inj_re, inj_im).  The same for every instance and frequency of the run.
+  int32_t inj_p, inj_n;
+  double inj_re, inj_im;
 };
 
 struct SpiceyCx { double re, im; };
@@ -34,7 +39,10 @@ SPICEY_HD SpiceyCx cx_mul(SpiceyCx a, SpiceyCx b) { return SpiceyCx{a.re * b.re 
 SPICEY_HD SpiceyCx cx_sub(SpiceyCx a, SpiceyCx b) { return SpiceyCx{a.re - b.re, a.im - b.im}; }
 SPICEY_HD SpiceyCx cx_add(SpiceyCx a, SpiceyCx b) { return SpiceyCx{a.re + b.re, a.im + b.im}; }
 
-template <class Exec>
+// INJ = false: a build without the current injection — SpiceyAcRun::inj_* are never read, so a kernel that takes the run
+// struct by value keeps the registers and the code it had before the fields existed (ac.hip launches it for every run
+// without injection).  INJ = true tests the fields at run time: an all-zero tail injects nothing.
+template <class Exec, bool INJ = true>
 struct AcPhases {
   const SpiceyProg &P;
   const SpiceyAcRun &R;
@@ -71,6 +79,15 @@ struct AcPhases {
     return SpiceyCx{1.0, 0.0};
   }
   SPICEY_HD SpiceyCx volt(int32_t xi) const { return xi < 0 ? SpiceyCx{0.0, 0.0} : W[xi]; }
+  // The injected current into the right-hand side, behind the stamp loops of the same phase: row r was written by thread
+  // r % T (both stamps stride their rows by T), and that thread adds.  The test on the run struct is workgroup-uniform.
+  SPICEY_HD void inject(int tid) const {
+    if (!INJ || (R.inj_p | R.inj_n) == 0) return;
+    const SpiceyCx cur{R.inj_re, R.inj_im};
+    const int rp = R.inj_p - 1 - P.nLU, rn = R.inj_n - 1 - P.nLU;
+    if (rp >= 0 && rp % T == tid) W[P.nLU + rp] = cx_add(W[P.nLU + rp], cur);
+    if (rn >= 0 && rn % T == tid) W[P.nLU + rn] = cx_sub(W[P.nLU + rn], cur);
+  }
 
   // raw: the entries as stamped (the dense fallback wants A itself, not the reciprocals of leaf diagonals)
   SPICEY_HD void s_stamp(int tid, bool raw = false) const {
@@ -98,6 +115,7 @@ struct AcPhases {
       }
       W[P.nLU + r] = acc;
     }
+    inject(tid);
   }
   SPICEY_HD void u_level(int tid, int l) const {
     const int nw = T >> 6, wv = tid >> 6, lane = tid & 63;
@@ -311,12 +329,12 @@ SPICEY_HD void spicey_ac_dense_solve(Exec &ex, const SpiceyProg &P, const Spicey
 }
 
 // One (instance, frequency) solve by one workgroup.  All control flow is workgroup-uniform.
-template <class Exec>
+template <bool INJ = true, class Exec>
 SPICEY_HD void spicey_ac_solve(Exec &ex, const SpiceyProg &P, const SpiceyAcRun &R, SpiceyCx *W, int32_t *flags, int64_t slot) {
   const size_t inst = (size_t)(slot / R.n_freq);
   const int64_t fi = slot % R.n_freq;
   const double two_pi = 2 * 3.141592653589793;
-  AcPhases<Exec> ph{P, R, W, flags, ex.threads(), inst, two_pi * R.freqs[fi]};
+  AcPhases<Exec, INJ> ph{P, R, W, flags, ex.threads(), inst, two_pi * R.freqs[fi]};
   ex.phase(SPICEY_PH_PRO, [&](int tid) { if (tid == 0) flags[0] = 0; });
   ex.phase(SPICEY_PH_B, [&](int tid) { ph.s_stamp(tid); });
   for (int l = 0; l < P.nLevels; l++) {
@@ -354,7 +372,7 @@ struct AcResRegs {
   uint32_t rowsrc;       // bit j: row tid + j T has source contributions (its right-hand side is not zero)
 };
 
-template <class Exec, int RMAX, int NSE>
+template <class Exec, int RMAX, int NSE, bool INJ = true>
 struct AcResident {
   typedef AcResRegs<RMAX, NSE> Regs;
   const SpiceyProg &P;
@@ -365,7 +383,7 @@ struct AcResident {
   int T;
   size_t inst;
 
-  SPICEY_HD void load(int tid, Regs &rr, const AcPhases<Exec> &gen) const {
+  SPICEY_HD void load(int tid, Regs &rr, const AcPhases<Exec, INJ> &gen) const {
     for (int s = 0; s < RMAX; s++) {
       const bool have = s < Q.rmax;
       const uint32_t *src = Q.res + ((size_t)(have ? s : 0) * T + tid) * 4;
@@ -409,7 +427,7 @@ struct AcResident {
     }
   }
 
-  SPICEY_HD void stamp(int tid, const Regs &rr, const AcPhases<Exec> &gen) const {
+  SPICEY_HD void stamp(int tid, const Regs &rr, const AcPhases<Exec, INJ> &gen) const {
     const double w = gen.w;
     SPICEY_UNROLL
     for (int j = 0; j < NSE; j++) {
@@ -453,11 +471,12 @@ struct AcResident {
       }
       W[P.nLU + r] = acc;
     }
+    gen.inject(tid);
   }
 
   // one 16-byte record in complex arithmetic (formats: program.h "compact 16-bit task records")
   template <bool ktask>
-  SPICEY_HD void exec(uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3, const AcPhases<Exec> &gen) const {
+  SPICEY_HD void exec(uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3, const AcPhases<Exec, INJ> &gen) const {
     const uint32_t meta = w0 >> 16;
     if (!(meta & (SPICEY_R16_VALID << 8))) return;
     const uint32_t tgt = w0 & 0xffffu, cnt = meta & 0xffu;
@@ -485,7 +504,7 @@ struct AcResident {
     }
   }
   template <bool ktask>
-  SPICEY_HD void phase_tasks(int tid, const Regs &rr, int p, const AcPhases<Exec> &gen) const {
+  SPICEY_HD void phase_tasks(int tid, const Regs &rr, int p, const AcPhases<Exec, INJ> &gen) const {
     SPICEY_UNROLL
     for (int s = 0; s < RMAX; s++)
       if (SPICEY_UNIFORM((int)((rr.phv[s >> 2] >> ((s & 3) * 8)) & 0xffu)) == p) {
@@ -505,15 +524,15 @@ struct AcResident {
 };
 
 // All frequencies fi = f0, f0 + fstride, ... of instance `inst` by one workgroup.  Control flow is workgroup-uniform.
-template <int RMAX, int NSE, class Exec>
+template <int RMAX, int NSE, bool INJ = true, class Exec>
 SPICEY_HD void spicey_ac_sweep_resident(Exec &ex, const SpiceyProg &P, const SpiceyResident &Q, const SpiceyAcRun &R, SpiceyCx *W, int32_t *flags,
                                         size_t inst, int64_t f0, int64_t fstride) {
   typedef AcResRegs<RMAX, NSE> Regs;
   const double two_pi = 2 * 3.141592653589793;
   const int T = ex.threads();
-  AcResident<Exec, RMAX, NSE> rs{P, Q, R, W, flags, T, inst};
+  AcResident<Exec, RMAX, NSE, INJ> rs{P, Q, R, W, flags, T, inst};
   {
-    AcPhases<Exec> gen{P, R, W, flags, T, inst, 0.0};
+    AcPhases<Exec, INJ> gen{P, R, W, flags, T, inst, 0.0};
     ex.phase(SPICEY_PH_PRO, [&](int tid) {
       if (tid == 0) flags[0] = 0;
       rs.load(tid, ex.template regs<Regs>(tid), gen);
@@ -521,7 +540,7 @@ SPICEY_HD void spicey_ac_sweep_resident(Exec &ex, const SpiceyProg &P, const Spi
   }
   const int nL = P.nLevels;
   for (int64_t fi = f0; fi < R.n_freq; fi += fstride) {
-    AcPhases<Exec> gen{P, R, W, flags, T, inst, two_pi * R.freqs[fi]};
+    AcPhases<Exec, INJ> gen{P, R, W, flags, T, inst, two_pi * R.freqs[fi]};
     ex.phase(SPICEY_PH_B, [&](int tid) { rs.stamp(tid, ex.template regs<Regs>(tid), gen); });
     for (int p = 0; p < 2 * nL; p++) {
       if (P.ph_cnt[p] == 0) continue;

@@ -26,6 +26,7 @@
 #include "fourier_exec.h"
 #include "measure.h"
 #include "measure_exec.h"
+#include "noise.h"
 #include "power.h"
 #include "values.h"
 #include "spectrum.h"
@@ -1093,6 +1094,19 @@ extern "C" int32_t spicey_ac_measure_device(int32_t device, int32_t n_inst, int6
   return launch_on_device(device, "spicey_launch_ac_measure", [&]() {
     return spicey_launch_ac_measure(device, n_inst, n_freq, d_v, n_v, d_i, n_i, table.data(), n_req, d_meas, d_work, (hipStream_t)stream);
   });
+}
+
+// Thermal noise of an injected AC sweep (include/spicey_hip.h): the reduction of noise.hip on any device buffers, no handle.
+extern "C" int64_t spicey_ac_noise_workspace_bytes(int32_t n_inst, int64_t n_freq, int32_t nR) { return spicey_noise_workspace_bytes(n_inst, n_freq, nR); }
+
+extern "C" int32_t spicey_ac_noise_device(int32_t device, int32_t n_inst, int64_t n_freq, const double *d_v, int32_t n_v, const double *d_i, int32_t n_i,
+                                          const double *d_R, int32_t nR, const double *d_freqs, const SpiceyAcNoiseReq *req, double *d_spec, double *d_contrib,
+                                          double *d_total, void *d_work, int64_t work_bytes, void *stream) {
+  // (the call is judged before the device is touched: a refusal launches nothing)
+  SpiceyNoiseArgs A;
+  if (!spicey_noise_judge(n_inst, n_freq, d_v, n_v, d_i, n_i, d_R, nR, d_freqs, req, d_spec && d_contrib && d_total && d_work, work_bytes, A, g_err))
+    return SPICEY_ERR_BAD_DESC;
+  return launch_on_device(device, "spicey_launch_noise", [&]() { return spicey_launch_noise(device, A, d_spec, d_contrib, d_total, d_work, (hipStream_t)stream); });
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

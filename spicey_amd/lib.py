@@ -98,6 +98,11 @@ SIGNATURES = {
     "spicey_ac_measure_device": (_i32, [_i32, _i32, _i64, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i64, _vp]),
     "spicey_ac_run_measure": (_i32, [_vp, _i64, _f64p, _f64p, _vp, _i32, _f64p]),
     "spicey_ac_last_measure_ms": (_f64, [_vp]),
+    "spicey_ac_run_inject": (_i32, [_vp, _i64, _f64p, _f64p, _vp, _f64p, _f64p]),
+    "spicey_ac_noise_workspace_bytes": (_i64, [_i32, _i64, _i32]),
+    "spicey_ac_noise_device": (_i32, [_i32, _i32, _i64, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "spicey_ac_run_noise": (_i32, [_vp, _i64, _f64p, _f64p, _vp, _vp, _f64p, _f64p, _f64p, _f64p]),
+    "spicey_ac_last_noise_ms": (_f64, [_vp]),
 }
 EXPORTS = list(SIGNATURES)
 
@@ -199,6 +204,24 @@ def ac_measure_device(n_inst: int, n_freq: int, d_v: int, n_v: int, d_i: int, n_
     """The same for an AC sweep's buffers (spicey_ac_measure_device): d_v [n_inst][n_freq][n_v] complex128, d_i likewise or
     0, d_work of `work_bytes` >= ac_measure_workspace_bytes(...)."""
     _measure_device("spicey_ac_measure_device", (n_inst, n_freq), d_v, n_v, d_i, n_i, _reqs(reqs, abi.AC_MEAS_REQ_DTYPE), d_meas, d_work, work_bytes, device, stream)
+
+
+def ac_noise_workspace_bytes(n_inst: int, n_freq: int, nR: int) -> int:
+    return load().spicey_ac_noise_workspace_bytes(n_inst, n_freq, nR)
+
+
+def ac_noise_device(n_inst: int, n_freq: int, d_v: int, n_v: int, d_i: int, n_i: int, d_R: int, nR: int, d_freqs: int, req: abi.SpiceyAcNoiseReq,
+                    d_spec: int, d_contrib: int, d_total: int, d_work: int, work_bytes: int, device: int = 0, stream: int = 0) -> None:
+    """spicey_ac_noise_device: the noise pass alone on raw device pointers: d_v [n_inst][n_freq][n_v] and d_i
+    [n_inst][n_freq][n_i] complex128 of an injected sweep, d_R [n_inst][nR] ohms, d_freqs [n_freq], d_spec [n_inst][n_freq][4],
+    d_contrib [n_inst][nR], d_total [n_inst][2], d_work of `work_bytes` >= ac_noise_workspace_bytes(...).  Enqueued on `stream`,
+    no synchronisation.  A refusal raises SpiceyNativeError whose `status` is abi.ERR_BAD_DESC."""
+    L = load()
+    rc = L.spicey_ac_noise_device(device, n_inst, n_freq, d_v or None, n_v, d_i or None, n_i, d_R or None, nR, d_freqs or None,
+                                  C.byref(req) if req is not None else None, d_spec or None, d_contrib or None, d_total or None, d_work or None,
+                                  work_bytes, stream or None)
+    if rc != abi.OK:
+        _fail("spicey_ac_noise_device", rc, L.spicey_last_error(None))
 
 
 def fourier_row_doubles(reqs) -> int:
@@ -759,6 +782,44 @@ class AcHandle:
                                           _p(meas, C.c_double))
         return self._dress({"meas": meas, "measure_ms": self.L.spicey_ac_last_measure_ms(self.h)}, rc)
 
+    def _phasors_ptr(self, vph):
+        if vph is None:
+            return None, None
+        ph = np.ascontiguousarray(np.broadcast_to(np.asarray(vph, np.complex128).reshape(-1, self.flat.nV), (self.flat.n_inst, self.flat.nV)))
+        return ph, _p(ph.view(np.float64), C.c_double)
+
+    def run_inject(self, freqs, vph, node_p: int, node_n: int, amp: complex = 1.0, want_currents: bool = True) -> dict:
+        """spicey_ac_run_inject: run() with the current `amp` injected into node_p and drawn from node_n (node ids, 0 =
+        ground) at every frequency of every instance.  vph None: every source phasor zero."""
+        f = self.flat
+        freqs = np.ascontiguousarray(freqs, dtype=np.float64)
+        ph, php = self._phasors_ptr(vph)
+        ni, nf = f.n_inst, len(freqs)
+        out_v = np.zeros((ni, nf, f.n_out), np.complex128)
+        out_i = np.zeros((ni, nf, f.nR + f.nC + f.nL + f.nV), np.complex128) if want_currents else None
+        inj = abi.ac_inject(node_p, node_n, amp)
+        rc = self.L.spicey_ac_run_inject(self.h, nf, _p(freqs, C.c_double), php, C.byref(inj), _p(out_v.view(np.float64), C.c_double),
+                                         _p(out_i.view(np.float64), C.c_double) if want_currents else None)
+        return self._dress({"out_v": out_v, "out_i": out_i}, rc)
+
+    def run_noise(self, freqs, node_p: int, node_n: int, req: abi.SpiceyAcNoiseReq, vph=None, amp: complex = 1.0) -> dict:
+        """spicey_ac_run_noise: the injected sweep of run_inject() with its results kept on the device and reduced there;
+        `spec` [n_inst][n_freq][4], `contrib` [n_inst][nR], `total` [n_inst][2] and `gain` [n_inst][n_freq] (complex i(V_in),
+        None without an input column) (include/spicey_hip.h) come back, also
+        after a failing sweep (`inst_status` names the instances whose rows are undefined).  req: abi.ac_noise_req(...),
+        columns as in this handle's out_v / out_i."""
+        f = self.flat
+        freqs = np.ascontiguousarray(freqs, dtype=np.float64)
+        ph, php = self._phasors_ptr(vph)
+        spec = np.zeros((f.n_inst, len(freqs), abi.NOISE_SPEC))
+        contrib = np.zeros((f.n_inst, f.nR))
+        total = np.zeros((f.n_inst, 2))
+        gain = np.zeros((f.n_inst, len(freqs)), np.complex128) if req.in_col >= 0 else None
+        inj = abi.ac_inject(node_p, node_n, amp)
+        rc = self.L.spicey_ac_run_noise(self.h, len(freqs), _p(freqs, C.c_double), php, C.byref(inj), C.byref(req), _p(spec, C.c_double),
+                                        _p(contrib, C.c_double), _p(total, C.c_double), _p(gain.view(np.float64), C.c_double) if gain is not None else None)
+        return self._dress({"spec": spec, "contrib": contrib, "total": total, "gain": gain, "noise_ms": self.L.spicey_ac_last_noise_ms(self.h)}, rc)
+
     def close(self) -> None:
         if getattr(self, "h", None):
             self.L.spicey_ac_destroy(self.h)
@@ -793,6 +854,13 @@ class _AcCalls:
     def run_ac_measure(self, flat: abi.FlatCircuit, freqs, vph, reqs) -> dict:
         """AcHandle.run_measure on a handle of its own: the sweep's results never leave the device."""
         return self._on_ac_handle(flat, lambda h: h.run_measure(freqs, vph, reqs))
+
+    def run_ac_inject(self, flat: abi.FlatCircuit, freqs, vph, node_p: int, node_n: int, amp: complex = 1.0, want_currents: bool = True) -> dict:
+        return self._on_ac_handle(flat, lambda h: h.run_inject(freqs, vph, node_p, node_n, amp, want_currents))
+
+    def run_ac_noise(self, flat: abi.FlatCircuit, freqs, node_p: int, node_n: int, req: abi.SpiceyAcNoiseReq) -> dict:
+        """AcHandle.run_noise on a handle of its own: the injected sweep's results never leave the device."""
+        return self._on_ac_handle(flat, lambda h: h.run_noise(freqs, node_p, node_n, req))
 
 
 class HipBackend(_AcCalls):
