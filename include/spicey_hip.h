@@ -871,6 +871,59 @@ int32_t spicey_ac_run_noise(SpiceyAcHandle *h, int64_t n_freq, const double *fre
 double spicey_ac_last_noise_ms(SpiceyAcHandle *h);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * AC sensitivity analysis: how out = v(out_p) - v(out_n) moves when an element value moves, for every R, C and L at every
+ * frequency, from two sweeps.  Sweep D is the plain one (the netlist's phasors), sweep X has every phasor zero and a unit
+ * current injected into the output pair; both record the element currents.  The matrix is complex symmetric, so X is the
+ * adjoint solution and d out / d Y_e = -dx_e dd_e (DESIGN.md "AC sensitivities").  With prod = i_X(e) i_D(e), w = (2 pi) f and
+ * p the element's value, the absolute sensitivity S_e = p d out / d p is
+ *   R: p prod        C: j prod / (w p)  (+0 where w p == 0)        L: j prod (w p)
+ * and the relative ones are m_e = Re(S_e / H) = d ln|H| / d ln p_e and phi_e = Im(S_e / H) = d arg H / d ln p_e (radians), H = out
+ * of sweep D (IEEE quotients: H == 0 shows inf / NaN).  The pass reduces the two sweeps:
+ *   d_spec  [n_inst][n_freq][6]      {H.re, H.im, wc_mag = sum_e t_e |m_e|, var_mag = sum_e (t_e m_e)^2, wc_ph = sum_e t_e |phi_e|,
+ *                                     var_ph = sum_e (t_e phi_e)^2}, t_e = tol[e] the element's relative tolerance
+ *   d_peak  [n_inst][nE][4]          {m_e where |m_e| is largest over the window, its frequency index, phi_e where |phi_e| is
+ *                                     largest, its frequency index} — the first of equal magnitudes, indices stored as doubles
+ *   d_full  [n_inst][n_freq][nE][2]  {m_e, phi_e}, optional
+ * with the fixed operation and summation order of sens_exec.h, no FMA contraction, no atomics: the CPU and the device agree on
+ * every bit, and d_peak holds the same bits with and without d_full.  Elements are numbered as the columns of out_i: the nR
+ * resistors, the nC capacitors, the nL inductors; nE = nR + nC + nL.
+ *   out_p, out_n   columns of out_v (d_v) of the output pair, -1 = ground; not both -1, not equal
+ *   nR, nC, nL     the element counts (a handle's run wants its own)
+ *   k_from, k_to   inclusive window of frequency indices of d_peak, k_to = -1: the last */
+typedef struct SpiceyAcSensReq {
+  int64_t struct_bytes;
+  int32_t out_p, out_n, nR, nC, nL, reserved;
+  int64_t k_from, k_to;
+} SpiceyAcSensReq;
+/* Bytes of device workspace spicey_ac_sens_device needs (the request record and the tolerances); -1 for counts <= 0. */
+int64_t spicey_ac_sens_workspace_bytes(int32_t n_inst, int64_t n_freq, int32_t nE);
+/* The reduction alone, on any DEVICE buffers (d_v_dir [n_inst][n_freq][n_v][2] of sweep D, d_i_dir and d_i_adj
+ * [n_inst][n_freq][n_i][2] of sweeps D and X, d_R / d_C / d_L [n_inst][n<kind>] in ohms, farads and henries — NULL where the
+ * count is 0 —, d_freqs [n_freq], d_spec, d_peak, d_full or NULL, d_work): needs no handle.  req and tol [nE] are HOST data:
+ * the tolerances are judged here and go to the device through the workspace, behind the request record.  Enqueued on `stream`
+ * without synchronising.  SPICEY_ERR_BAD_DESC with a text containing "sens" in spicey_last_error(NULL), nothing launched,
+ * for: a null required buffer, counts <= 0, nE = 0, a negative count, nR + nC + nL > n_i, a column out of range, out_p ==
+ * out_n, a window outside [0, n_freq) or with k_from > k_to, a negative or non-finite tolerance, a nonzero reserved word, a
+ * wrong struct_bytes, a workspace that is too small. */
+int32_t spicey_ac_sens_device(int32_t device, int32_t n_inst, int64_t n_freq, const double *d_v_dir, int32_t n_v, const double *d_i_dir,
+                              const double *d_i_adj, int32_t n_i, const double *d_R, const double *d_C, const double *d_L, const double *tol,
+                              const double *d_freqs, const SpiceyAcSensReq *req, double *d_spec, double *d_peak, double *d_full, void *d_work,
+                              int64_t work_bytes, void *stream);
+/* Two sweeps on the handle — D with vph and no injection, then X with inj and every phasor zero; inj names the nodes of the
+ * output pair with amplitude 1 — whose out_v / out_i stay on the device and are reduced there on the handle's stream, after
+ * the dense fallback has repaired their slots; spec [n_inst][n_freq][6], peak [n_inst][nE][4] and, if not NULL, full
+ * [n_inst][n_freq][nE][2] (HOST) come back.  tol is HOST [nE].  Columns are those of the handle, and req's nR, nC, nL must be
+ * the handle's.  A slot's status is D's where nonzero, else X's; the return value and spicey_ac_last_inst_status follow from
+ * that merged table as after spicey_ac_run: an instance with a failed solve has its code and undefined rows, the others are
+ * complete.  A refused request, tolerance list or injection (SPICEY_ERR_BAD_DESC, text in spicey_ac_last_error; the
+ * reference-order engine, interpreter = 3, refuses every injection) runs nothing.  A later spicey_ac_run gives the bits it
+ * gave before.  spicey_ac_last_kernel_ms reports the sum of the two sweeps. */
+int32_t spicey_ac_run_sens(SpiceyAcHandle *h, int64_t n_freq, const double *freqs, const double *vph, const SpiceyAcInject *inj,
+                           const SpiceyAcSensReq *req, const double *tol, double *spec, double *peak, double *full);
+/* Duration in ms of the last spicey_ac_run_sens's reduction, measured with HIP events. */
+double spicey_ac_last_sens_ms(SpiceyAcHandle *h);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Result formatting fast path (host code, no GPU): the CSV text of
  *   formatTranResult(tran)       /root/reference/lib/formatting/formatTranResult.ts:1-23
  * straight from the typed arrays spicey_run filled.  Every number is Number.prototype.toPrecision(6) exactly as

@@ -11,9 +11,11 @@ harmonics with THD (fourier) and edge timing (when, delay, rise_time, fall_time,
 sweeps as the instances of one launch, and measureAC / measureACBatch (spicey_amd.ac_measure) reduce such sweeps on the
 device to corner frequencies, peaks and point read-outs; simulateNoise / simulateNoiseBatch (spicey_amd.noise) run one sweep
 with a current injected at the output and reduce it on the device to output impedance, gain, thermal noise and the resistors'
-shares of it.
+shares of it; simulateSens / simulateSensBatch (spicey_amd.sens) run that sweep and the plain one and reduce the two on the
+device to every element's first-order sensitivity of magnitude and phase and to worst-case and root-sum-square tolerance bounds.
 """
 from .ac_batch import simulateACBatch  # noqa: F401
 from .ac_measure import measureAC, measureACBatch  # noqa: F401
 from .noise import simulateNoise, simulateNoiseBatch  # noqa: F401
+from .sens import simulateSens, simulateSensBatch  # noqa: F401
 from .measure import deriv, efficiency, find, measureTRAN, measureTRANBatch, power, sample, trace  # noqa: F401

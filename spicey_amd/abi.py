@@ -217,6 +217,21 @@ def ac_noise_req(out_p: int, out_n: int, in_col: int, kt4: float, k_from: int = 
     return SpiceyAcNoiseReq(C.sizeof(SpiceyAcNoiseReq), int(out_p), int(out_n), int(in_col), 0, int(k_from), int(k_to), float(kt4))
 
 
+class SpiceyAcSensReq(C.Structure):
+    """The request of the sensitivity pass (include/spicey_hip.h); struct_bytes = C.sizeof(SpiceyAcSensReq)."""
+    _fields_ = [("struct_bytes", C.c_int64), ("out_p", C.c_int32), ("out_n", C.c_int32), ("nR", C.c_int32), ("nC", C.c_int32), ("nL", C.c_int32),
+                ("reserved", C.c_int32), ("k_from", C.c_int64), ("k_to", C.c_int64)]
+
+
+assert C.sizeof(SpiceyAcSensReq) == 48
+SENS_SPEC = 6  # doubles of a row of d_spec: h_re, h_im, wc_mag, var_mag, wc_ph, var_ph
+SENS_PEAK = 4  # doubles of a row of d_peak: m at its peak, its frequency index, phi at its peak, its frequency index
+
+
+def ac_sens_req(out_p: int, out_n: int, nR: int, nC: int, nL: int, k_from: int = 0, k_to: int = -1) -> SpiceyAcSensReq:
+    return SpiceyAcSensReq(C.sizeof(SpiceyAcSensReq), int(out_p), int(out_n), int(nR), int(nC), int(nL), 0, int(k_from), int(k_to))
+
+
 def _i32(a) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.int32)
 

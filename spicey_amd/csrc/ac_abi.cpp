@@ -27,6 +27,7 @@
 #include "devbuf.h"
 #include "kernels.h"
 #include "noise.h"
+#include "sens.h"
 #include "symbolic.h"
 
 struct AcDims { int32_t n_inst = 0, n_out = 0, n_cur = 0, n_v = 0; };
@@ -70,11 +71,11 @@ struct SpiceyAcHandle {
   AcDims dims;
   std::unique_ptr<AcEngine> eng;
   DevBuf<double> d_R, d_C, d_L;  // 1 / R, C, L [n_inst][n<kind>]
-  int32_t n_nodes = 0, nR = 0;
+  int32_t n_nodes = 0, nR = 0, nC = 0, nL = 0;
   std::vector<double> R_host;    // R [n_inst][nR] in ohms, and on the device from the first noise pass on
   DevBuf<double> d_Rohm;
   bool have_Rohm = false;
-  double last_noise_ms = 0.0;
+  double last_noise_ms = 0.0, last_sens_ms = 0.0;
   int64_t last_slots = 0;        // (instance, frequency) slots of the last sweep
   double last_ms = 0.0, last_measure_ms = 0.0;
   SpiceyAcInstStatus ist;        // per instance of the last sweep (spicey_ac_last_inst_status)
@@ -300,6 +301,8 @@ static int32_t ac_allocate(SpiceyAcHandle *h, const SpiceyDesc *desc) {
   const size_t ni = (size_t)h->dims.n_inst;
   h->n_nodes = desc->n_nodes;
   h->nR = desc->nR;
+  h->nC = desc->nC;
+  h->nL = desc->nL;
   h->R_host.assign(desc->R_val, desc->R_val + ni * (size_t)desc->nR);
   std::vector<double> rinv(ni * (size_t)desc->nR);
   for (size_t i = 0; i < rinv.size(); i++) rinv[i] = 1.0 / desc->R_val[i];  // (1 / R in simulateAC.ts:39-41, the same quotient)
@@ -343,6 +346,17 @@ extern "C" int32_t spicey_ac_get_info(SpiceyAcHandle *h, SpiceyInfo *info) {
 
 extern "C" double spicey_ac_last_kernel_ms(SpiceyAcHandle *h) { return h ? h->last_ms : 0.0; }
 
+// The refusals of an injection that need no engine (text in h->err).
+static bool ac_judge_inject(SpiceyAcHandle *h, const SpiceyAcInject *inj) {
+  const char *what = nullptr;
+  if (inj->struct_bytes != (int64_t)sizeof(SpiceyAcInject)) what = "struct_bytes is not sizeof(SpiceyAcInject)";
+  else if (inj->node_p < 0 || inj->node_p > h->n_nodes || inj->node_n < 0 || inj->node_n > h->n_nodes) what = "node outside [0, n_nodes]";
+  else if (inj->node_p == inj->node_n) what = "node_p == node_n: nothing is injected";
+  else if (!std::isfinite(inj->re) || !std::isfinite(inj->im)) what = "the amplitude must be finite";
+  if (what) h->err = std::string("inject: ") + what;
+  return !what;
+}
+
 // What spicey_ac_run and spicey_ac_run_measure share: the argument checks, then ONE sweep into `o` — staged, timed,
 // launched through the engine, o.status on the host, the stream idle.  The caller copies out or reduces.
 // *done: the call is answered without a sweep (nothing to do, or structurally singular).
@@ -353,14 +367,7 @@ static int32_t ac_sweep(SpiceyAcHandle *h, int64_t n_freq, const double *freqs, 
   h->ist.forget();
   const AcDims &d = h->dims;
   if (n_freq < 0 || (n_freq > 0 && (!freqs || !have_out)) || (d.n_v > 0 && !vph && !inj)) { h->err = "bad run arguments"; return SPICEY_ERR_BAD_DESC; }
-  if (inj) {
-    const char *what = nullptr;
-    if (inj->struct_bytes != (int64_t)sizeof(SpiceyAcInject)) what = "struct_bytes is not sizeof(SpiceyAcInject)";
-    else if (inj->node_p < 0 || inj->node_p > h->n_nodes || inj->node_n < 0 || inj->node_n > h->n_nodes) what = "node outside [0, n_nodes]";
-    else if (inj->node_p == inj->node_n) what = "node_p == node_n: nothing is injected";
-    else if (!std::isfinite(inj->re) || !std::isfinite(inj->im)) what = "the amplitude must be finite";
-    if (what) { h->err = std::string("inject: ") + what; return SPICEY_ERR_BAD_DESC; }
-  }
+  if (inj && !ac_judge_inject(h, inj)) return SPICEY_ERR_BAD_DESC;
   if (const int32_t rc = h->eng->set_inject(inj, h->err); rc != SPICEY_OK) return rc;
   if (n_freq == 0) {
     h->ist.fill(d.n_inst, 0, -1);
@@ -531,3 +538,64 @@ extern "C" int32_t spicey_ac_run_noise(SpiceyAcHandle *h, int64_t n_freq, const 
 }
 
 extern "C" double spicey_ac_last_noise_ms(SpiceyAcHandle *h) { return h ? h->last_noise_ms : 0.0; }
+
+// Sweep D (vph, no injection) and sweep X (inj, every phasor zero) of ac_sweep, both left on the device, and the sensitivity
+// pass of sens.hip behind them.
+extern "C" int32_t spicey_ac_run_sens(SpiceyAcHandle *h, int64_t n_freq, const double *freqs, const double *vph, const SpiceyAcInject *inj,
+                                      const SpiceyAcSensReq *req, const double *tol, double *spec, double *peak, double *full) {
+  if (!h) return SPICEY_ERR_BAD_DESC;
+  h->ist.forget();
+  h->last_sens_ms = 0.0;
+  const AcDims &d = h->dims;
+  const int32_t nE = h->nR + h->nC + h->nL;
+  if (!inj) { h->err = "inject: null injection"; return SPICEY_ERR_BAD_DESC; }
+  // (a refused request, tolerance list or injection runs nothing: judged on placeholder buffers first, the sweeps' own are
+  // bound below; the engine is asked for the injection before sweep D, which then clears it)
+  const int64_t work_bytes = spicey_sens_workspace_bytes(d.n_inst, n_freq, nE);
+  const double *some = h->d_R;  // (any non-null pointer: the judge looks at null-ness only)
+  SpiceySensArgs A;
+  if (!spicey_sens_judge(d.n_inst, n_freq, some, d.n_out, some, some, d.n_cur, some, some, some, tol, some, req, spec && peak, work_bytes, A, h->err))
+    return SPICEY_ERR_BAD_DESC;
+  if (req->nR != h->nR || req->nC != h->nC || req->nL != h->nL) { h->err = "sens: nR, nC, nL are not the handle's"; return SPICEY_ERR_BAD_DESC; }
+  if (!ac_judge_inject(h, inj)) return SPICEY_ERR_BAD_DESC;
+  if (const int32_t rc = h->eng->set_inject(inj, h->err); rc != SPICEY_OK) return rc;
+  SpiceyAcSweep dir, adj;
+  DevBuf<double> d_f;
+  bool done = false;
+  int32_t rc = ac_sweep(h, n_freq, freqs, vph, true, true, dir, &done, nullptr, &d_f);
+  if (rc != SPICEY_OK || done) return rc;
+  const double dir_ms = h->last_ms;
+  rc = ac_sweep(h, n_freq, freqs, nullptr, true, true, adj, &done, inj);
+  if (rc != SPICEY_OK || done) return rc;
+  h->last_ms += dir_ms;
+  for (size_t s = 0; s < dir.status.size(); s++)
+    if (dir.status[s] == 0) dir.status[s] = adj.status[s];
+  hipStream_t st = h->q.stream;
+  if (!h->have_Rohm) {
+    if (dev_upload(h->d_Rohm, h->R_host.size(), h->R_host.data()) != hipSuccess) { h->err = "upload of the resistances failed"; return SPICEY_ERR_HIP; }
+    h->have_Rohm = true;
+  }
+  HIPCHK(h, h->q.want_pass_events(PASS_MEASURE));
+  const hipEvent_t *ev = h->q.pass_ev[PASS_MEASURE];
+  const size_t slots = (size_t)d.n_inst * (size_t)n_freq;
+  const size_t n_spec = slots * SPICEY_SENS_SPEC, n_peak = (size_t)d.n_inst * (size_t)nE * SPICEY_SENS_PEAK, n_full = slots * (size_t)nE * 2;
+  DevBuf<double> d_spec, d_peak, d_full;
+  DevBuf<uint8_t> d_work;
+  HIPCHK(h, d_spec.alloc(n_spec));
+  HIPCHK(h, d_peak.alloc(n_peak));
+  if (full) HIPCHK(h, d_full.alloc(n_full));
+  HIPCHK(h, d_work.alloc((size_t)work_bytes));
+  // (h->d_C and h->d_L hold farads and henries as the descriptor gave them; 1 / R is the sweep's, ohms are uploaded once)
+  A.d_v = dir.d_ov; A.d_id = dir.d_oi; A.d_ix = adj.d_oi; A.R = h->d_Rohm; A.C = h->d_C; A.L = h->d_L; A.freqs = d_f;
+  HIPCHK(h, hipEventRecord(ev[0], st));
+  HIPCHK(h, spicey_launch_sens(h->device, A, tol, d_spec, d_peak, full ? (double *)d_full : nullptr, d_work, st));
+  HIPCHK(h, hipEventRecord(ev[1], st));
+  HIPCHK(h, hipMemcpyAsync(spec, d_spec, n_spec * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(h, hipMemcpyAsync(peak, d_peak, n_peak * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (full) HIPCHK(h, hipMemcpyAsync(full, d_full, n_full * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(h, hipStreamSynchronize(st));
+  StreamTimers::elapsed(ev[0], ev[1], &h->last_sens_ms);
+  return h->ist.from_slots(dir.status, d.n_inst, n_freq, h->err);
+}
+
+extern "C" double spicey_ac_last_sens_ms(SpiceyAcHandle *h) { return h ? h->last_sens_ms : 0.0; }

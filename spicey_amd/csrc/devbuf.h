@@ -58,6 +58,8 @@ inline int32_t spicey_open_device(int device, int *ncu, std::string &err) {
 // event pair in StreamTimers and of its time in SpiceyHandle::last_pass_ms.
 enum SpiceyPass { PASS_MEASURE = 0, PASS_FOURIER = 1, PASS_TIMING = 2, PASS_SPECTRUM = 3, PASS_POWER = 4, PASS_VALUES = 5, N_PASS = 6 };
 
+void spicey_table_ring_release(hipStream_t st);  // measure.hip: the staging ring of the request tables
+
 // A handle's stream and its timing events: ev0 / ev1 bracket the kernel of a run, pass_ev[p] the reduction pass p of a
 // *_run_measure* (created on first use; an AC handle has the measurement pass only).  Destroys what it created.  A handle
 // declares it AFTER its DevBufs: members go in reverse order, so events and stream are destroyed before the device memory
@@ -74,7 +76,12 @@ struct StreamTimers {
     for (auto &pair : pass_ev)
       for (hipEvent_t e : pair)
         if (e) (void)hipEventDestroy(e);
-    if (stream) (void)hipStreamDestroy(stream);
+    if (stream) {
+      // (the ring of request tables holds events recorded on this stream: they go while the stream still exists)
+      (void)hipStreamSynchronize(stream);
+      spicey_table_ring_release(stream);
+      (void)hipStreamDestroy(stream);
+    }
   }
   template <class H>
   int32_t create(H *h) {

@@ -27,3 +27,6 @@ inline hipError_t spicey_meas_grid2(int64_t total, int threads, unsigned *grid) 
 // A request table (HOST, `bytes` long) into device memory by an asynchronous copy on `st`: the bytes are staged in a small
 // ring of pinned buffers, so `table` may go away as soon as the call returns.  Shared with ac_measure.hip.
 hipError_t spicey_upload_table_async(int device, void *d_dst, const void *table, size_t bytes, hipStream_t st);
+// Before `st` is destroyed, with its work finished: the ring gives up the events it last recorded on `st` and takes the
+// slots' buffers back.  (A waited-for event is looked up through the stream it was last recorded on; that stream must exist.)
+void spicey_table_ring_release(hipStream_t st);

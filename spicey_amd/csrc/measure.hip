@@ -40,11 +40,13 @@ __global__ void __launch_bounds__(SPICEY_MEAS_THREADS) spicey_measure_stage2(int
 
 // The request table goes to the device by an asynchronous copy, so its host copy must outlive the call: a small ring of
 // pinned buffers, each reused only after the copy that last read it has finished (an event per slot; the wait happens only
-// when SLOTS launches are in flight).
+// when SLOTS launches are in flight).  An event is not touched again once the stream it was last recorded on is gone:
+// the runtime keeps that stream's address in the event and looks at it when the event is waited for, so a handle that
+// destroys its stream releases its slots first (spicey_table_ring_release).
 struct TableRing {
   static const int SLOTS = 8;
   std::mutex mu;
-  struct Slot { void *p = nullptr; size_t cap = 0; hipEvent_t ev = nullptr; bool used = false; int device = -1; } slot[SLOTS];
+  struct Slot { void *p = nullptr; size_t cap = 0; hipEvent_t ev = nullptr; bool used = false; int device = -1; hipStream_t stream = nullptr; } slot[SLOTS];
   int next = 0;
 };
 TableRing &table_ring() {
@@ -83,7 +85,20 @@ hipError_t spicey_upload_table_async(int device, void *d_dst, const void *table,
   if ((e = hipMemcpyAsync(d_dst, s.p, bytes, hipMemcpyHostToDevice, st)) != hipSuccess) return e;
   if ((e = hipEventRecord(s.ev, st)) != hipSuccess) return e;
   s.used = true;
+  s.stream = st;
   return hipSuccess;
+}
+
+void spicey_table_ring_release(hipStream_t st) {
+  TableRing &ring = table_ring();
+  std::lock_guard<std::mutex> lk(ring.mu);
+  for (TableRing::Slot &s : ring.slot)
+    if (s.ev && s.stream == st) {
+      (void)hipEventDestroy(s.ev);
+      s.ev = nullptr;
+      s.used = false;
+      s.stream = nullptr;
+    }
 }
 
 hipError_t spicey_launch_measure(int device, int32_t n_inst, int64_t n_points, double dt, const double *d_v, int32_t n_v, const double *d_i, int32_t n_i,

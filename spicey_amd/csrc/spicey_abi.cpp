@@ -27,6 +27,7 @@
 #include "measure.h"
 #include "measure_exec.h"
 #include "noise.h"
+#include "sens.h"
 #include "power.h"
 #include "values.h"
 #include "spectrum.h"
@@ -1107,6 +1108,21 @@ extern "C" int32_t spicey_ac_noise_device(int32_t device, int32_t n_inst, int64_
   if (!spicey_noise_judge(n_inst, n_freq, d_v, n_v, d_i, n_i, d_R, nR, d_freqs, req, d_spec && d_contrib && d_total && d_work, work_bytes, A, g_err))
     return SPICEY_ERR_BAD_DESC;
   return launch_on_device(device, "spicey_launch_noise", [&]() { return spicey_launch_noise(device, A, d_spec, d_contrib, d_total, d_work, (hipStream_t)stream); });
+}
+
+// AC sensitivities of a direct and an adjoint sweep (include/spicey_hip.h): the reduction of sens.hip on any device buffers, no
+// handle.  tol is a HOST array: judged here, uploaded through the workspace.
+extern "C" int64_t spicey_ac_sens_workspace_bytes(int32_t n_inst, int64_t n_freq, int32_t nE) { return spicey_sens_workspace_bytes(n_inst, n_freq, nE); }
+
+extern "C" int32_t spicey_ac_sens_device(int32_t device, int32_t n_inst, int64_t n_freq, const double *d_v_dir, int32_t n_v, const double *d_i_dir,
+                                         const double *d_i_adj, int32_t n_i, const double *d_R, const double *d_C, const double *d_L, const double *tol,
+                                         const double *d_freqs, const SpiceyAcSensReq *req, double *d_spec, double *d_peak, double *d_full, void *d_work,
+                                         int64_t work_bytes, void *stream) {
+  // (the call is judged before the device is touched: a refusal launches nothing)
+  SpiceySensArgs A;
+  if (!spicey_sens_judge(n_inst, n_freq, d_v_dir, n_v, d_i_dir, d_i_adj, n_i, d_R, d_C, d_L, tol, d_freqs, req, d_spec && d_peak && d_work, work_bytes, A, g_err))
+    return SPICEY_ERR_BAD_DESC;
+  return launch_on_device(device, "spicey_launch_sens", [&]() { return spicey_launch_sens(device, A, tol, d_spec, d_peak, d_full, d_work, (hipStream_t)stream); });
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

@@ -103,6 +103,10 @@ SIGNATURES = {
     "spicey_ac_noise_device": (_i32, [_i32, _i32, _i64, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "spicey_ac_run_noise": (_i32, [_vp, _i64, _f64p, _f64p, _vp, _vp, _f64p, _f64p, _f64p, _f64p]),
     "spicey_ac_last_noise_ms": (_f64, [_vp]),
+    "spicey_ac_sens_workspace_bytes": (_i64, [_i32, _i64, _i32]),
+    "spicey_ac_sens_device": (_i32, [_i32, _i32, _i64, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _f64p, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "spicey_ac_run_sens": (_i32, [_vp, _i64, _f64p, _f64p, _vp, _vp, _f64p, _f64p, _f64p, _f64p]),
+    "spicey_ac_last_sens_ms": (_f64, [_vp]),
 }
 EXPORTS = list(SIGNATURES)
 
@@ -222,6 +226,26 @@ def ac_noise_device(n_inst: int, n_freq: int, d_v: int, n_v: int, d_i: int, n_i:
                                   work_bytes, stream or None)
     if rc != abi.OK:
         _fail("spicey_ac_noise_device", rc, L.spicey_last_error(None))
+
+
+def ac_sens_workspace_bytes(n_inst: int, n_freq: int, nE: int) -> int:
+    return load().spicey_ac_sens_workspace_bytes(n_inst, n_freq, nE)
+
+
+def ac_sens_device(n_inst: int, n_freq: int, d_v_dir: int, n_v: int, d_i_dir: int, d_i_adj: int, n_i: int, d_R: int, d_C: int, d_L: int, tol, d_freqs: int,
+                   req: abi.SpiceyAcSensReq, d_spec: int, d_peak: int, d_full: int, d_work: int, work_bytes: int, device: int = 0, stream: int = 0) -> None:
+    """spicey_ac_sens_device: the sensitivity pass alone on raw device pointers: d_v_dir [n_inst][n_freq][n_v] and d_i_dir
+    [n_inst][n_freq][n_i] complex128 of the plain sweep, d_i_adj likewise of the injected one, d_R / d_C / d_L [n_inst][n<kind>]
+    (0 where the count is 0), d_freqs [n_freq], d_spec [n_inst][n_freq][6], d_peak [n_inst][nE][4], d_full [n_inst][n_freq][nE][2]
+    or 0, d_work of `work_bytes` >= ac_sens_workspace_bytes(...).  tol [nE] is a HOST array (None stands for a null pointer).
+    Enqueued on `stream`, no synchronisation.  A refusal raises SpiceyNativeError whose `status` is abi.ERR_BAD_DESC."""
+    L = load()
+    t = None if tol is None else np.ascontiguousarray(tol, dtype=np.float64)
+    rc = L.spicey_ac_sens_device(device, n_inst, n_freq, d_v_dir or None, n_v, d_i_dir or None, d_i_adj or None, n_i, d_R or None, d_C or None, d_L or None,
+                                 _p(t, C.c_double), d_freqs or None, C.byref(req) if req is not None else None, d_spec or None, d_peak or None,
+                                 d_full or None, d_work or None, work_bytes, stream or None)
+    if rc != abi.OK:
+        _fail("spicey_ac_sens_device", rc, L.spicey_last_error(None))
 
 
 def fourier_row_doubles(reqs) -> int:
@@ -820,6 +844,26 @@ class AcHandle:
                                         _p(contrib, C.c_double), _p(total, C.c_double), _p(gain.view(np.float64), C.c_double) if gain is not None else None)
         return self._dress({"spec": spec, "contrib": contrib, "total": total, "gain": gain, "noise_ms": self.L.spicey_ac_last_noise_ms(self.h)}, rc)
 
+    def run_sens(self, freqs, vph, node_p: int, node_n: int, req: abi.SpiceyAcSensReq, tol, full: bool = False) -> dict:
+        """spicey_ac_run_sens: the plain sweep of run() and the sweep of run_inject() with a unit current into (node_p, node_n)
+        and every phasor zero, both kept on the device and reduced there; `spec` [n_inst][n_freq][6], `peak` [n_inst][nE][4] and,
+        with full, `full` [n_inst][n_freq][nE][2] (include/spicey_hip.h) come back, also after a failing sweep (`inst_status`
+        names the instances whose rows are undefined).  req: abi.ac_sens_req(...) with this handle's columns and element
+        counts; tol [nE] relative tolerances in the order R, C, L.  `kernel_ms` is the sum of the two sweeps."""
+        f = self.flat
+        freqs, ph = self._sweep_args(freqs, vph)
+        nE = f.nR + f.nC + f.nL
+        t = None if tol is None else np.ascontiguousarray(tol, dtype=np.float64).reshape(-1)
+        if t is not None and len(t) != nE:
+            raise ValueError(f"run_sens: tol must have one entry per element ({nE}), got {len(t)}")
+        spec = np.zeros((f.n_inst, len(freqs), abi.SENS_SPEC))
+        peak = np.zeros((f.n_inst, nE, abi.SENS_PEAK))
+        fl = np.zeros((f.n_inst, len(freqs), nE, 2)) if full else None
+        inj = abi.ac_inject(node_p, node_n, 1.0)
+        rc = self.L.spicey_ac_run_sens(self.h, len(freqs), _p(freqs, C.c_double), _p(ph.view(np.float64), C.c_double), C.byref(inj), C.byref(req),
+                                       _p(t, C.c_double), _p(spec, C.c_double), _p(peak, C.c_double), _p(fl, C.c_double))
+        return self._dress({"spec": spec, "peak": peak, "full": fl, "sens_ms": self.L.spicey_ac_last_sens_ms(self.h)}, rc)
+
     def close(self) -> None:
         if getattr(self, "h", None):
             self.L.spicey_ac_destroy(self.h)
@@ -861,6 +905,10 @@ class _AcCalls:
     def run_ac_noise(self, flat: abi.FlatCircuit, freqs, node_p: int, node_n: int, req: abi.SpiceyAcNoiseReq) -> dict:
         """AcHandle.run_noise on a handle of its own: the injected sweep's results never leave the device."""
         return self._on_ac_handle(flat, lambda h: h.run_noise(freqs, node_p, node_n, req))
+
+    def run_ac_sens(self, flat: abi.FlatCircuit, freqs, vph, node_p: int, node_n: int, req: abi.SpiceyAcSensReq, tol, full: bool = False) -> dict:
+        """AcHandle.run_sens on a handle of its own: neither sweep's results leave the device."""
+        return self._on_ac_handle(flat, lambda h: h.run_sens(freqs, vph, node_p, node_n, req, tol, full))
 
 
 class HipBackend(_AcCalls):
