@@ -924,6 +924,75 @@ int32_t spicey_ac_run_sens(SpiceyAcHandle *h, int64_t n_freq, const double *freq
 double spicey_ac_last_sens_ms(SpiceyAcHandle *h);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Monte Carlo tolerance analysis (SPICE's .mc): the distribution of |H|^2, H = v(out_p) - v(out_n), over n_inst samples whose R,
+ * C and L are drawn on the device around their nominal values, swept in one batched sweep and reduced ACROSS the instances on
+ * the device: per frequency the order statistics at given ranks, the sum and the sum of squares, the number of samples outside
+ * a spec mask; per sample the number of frequencies at which it violates the mask.  Fixed operation order (mc_exec.h), integer
+ * random numbers, no FMA contraction, no atomics: the CPU and the device agree on every bit.
+ *
+ * The draw.  Sample s, element e (the column order of out_i: the nR resistors, the nC capacitors, the nL inductors; nE = nR + nC
+ * + nL) takes Philox4x32-10 of counter (s, e, 0, 0) under key (seed & 0xffffffff, seed >> 32), forms the 52-bit integer
+ * m = (x0 << 20) | (x1 >> 12), and interpolates the HOST-built table icdf [K + 1], K = 2^log2K, log2K in [0, 12], of the inverse
+ * distribution function in units of the element's tolerance: j = m >> (52 - log2K), frac = the remaining bits times 2^-(52 - log2K),
+ * d = icdf[j] + frac (icdf[j + 1] - icdf[j]).  With g = 1 + tol[e] d a capacitor or inductor becomes nom g; a resistor becomes
+ * R' = R g in ohms, and the array the sweep reads gets the quotient 1.0 / R'.  keep_first: sample 0 takes g = 1 without drawing,
+ * so its rows are the nominal bits.  The nominal values are rows per sample, [n_inst][n<kind>].
+ *
+ * The reduction.  q[s][k] = H.re H.re + H.im H.im, each part of H one rounded subtraction (a column of -1 is ground).  A sample
+ * marked invalid leaves every statistic.  A violation at k is !(q >= lo[k] && q <= hi[k]) — a NaN violates —, lo / hi being
+ * limits of |H|^2 (+-inf: none; a NULL side: none on that side; both NULL: no mask, nothing violates).
+ *   d_sample [n_inst][2] int64      {frequencies at which the sample violates, the lowest such index or -1}; {-1, -1} if invalid
+ *   d_freq   [n_freq][4 + n_rank]   {n_valid, valid samples violating at k, sum of q, sum of q q, q_(ranks[0]), q_(ranks[1]), ...}:
+ *                                   q_(r) the r-th smallest of the n_valid values (NaNs sort behind +inf); the sums run over the
+ *                                   sorted values, lane l of 64 adding x[l], x[l + 64], ... from +0.0 and the partials meeting
+ *                                   by s[l] += s[l + stride], stride 32 .. 1
+ * Each frequency is sorted by one workgroup in LDS, so n_inst <= 16384. */
+typedef struct SpiceyAcMcReq {
+  int64_t struct_bytes;
+  int32_t out_p, out_n;   /* columns of out_v (d_v) of the output pair, -1 = ground; not both -1, not equal (the draw ignores them) */
+  int32_t log2K;          /* the table has 2^log2K + 1 entries */
+  int32_t keep_first;     /* nonzero: sample 0 is the nominal circuit */
+  uint64_t seed;
+  int64_t reserved;       /* 0 */
+} SpiceyAcMcReq;
+/* Bytes of device workspace that serve spicey_ac_mc_draw_device and spicey_ac_mc_reduce_device alike; -1 for counts <= 0,
+ * n_inst > 16384, log2K outside [0, 12] or n_rank < 0. */
+int64_t spicey_ac_mc_workspace_bytes(int32_t n_inst, int64_t n_freq, int32_t nE, int32_t log2K, int32_t n_rank);
+/* The draw alone, on any DEVICE buffers (d_R in ohms, d_C, d_L: nominal [n_inst][n<kind>]; d_Rinv_out, d_C_out, d_L_out: drawn,
+ * the first as 1 / ohms; NULL where the count is 0; d_work): needs no handle.  req, tol [nE] and icdf [K + 1] are HOST data, judged
+ * here; they go to the device through the workspace.  Enqueued on `stream` without synchronising.  SPICEY_ERR_BAD_DESC with a
+ * text containing "mc" in spicey_last_error(NULL), nothing launched, for: a null required buffer, n_inst <= 0 or > 16384, a
+ * negative count, nE = 0, a negative or non-finite tolerance, tol[e] max|icdf| >= 1 (a value could turn non-positive), a
+ * non-finite or decreasing table, log2K outside [0, 12], a nonzero reserved word, a wrong struct_bytes, a workspace that is too
+ * small. */
+int32_t spicey_ac_mc_draw_device(int32_t device, int32_t n_inst, int32_t nR, int32_t nC, int32_t nL, const double *d_R, const double *d_C,
+                                 const double *d_L, const double *tol, const double *icdf, const SpiceyAcMcReq *req, double *d_Rinv_out,
+                                 double *d_C_out, double *d_L_out, void *d_work, int64_t work_bytes, void *stream);
+/* The reduction alone, on any DEVICE buffer d_v [n_inst][n_freq][n_v][2] (with d_sample, d_freq, d_work): needs no handle.  req,
+ * valid [n_inst] (one byte per sample, nonzero = valid; NULL: all), lo / hi [n_freq] (or NULL) and ranks [n_rank], each in [0,
+ * n_valid), are HOST data.  Enqueued on `stream` without synchronising.  Refused like the draw, and for: n_freq or n_v <= 0,
+ * n_rank < 0, a column out of range, out_p == out_n, a rank outside [0, n_valid). */
+int32_t spicey_ac_mc_reduce_device(int32_t device, int32_t n_inst, int64_t n_freq, const double *d_v, int32_t n_v, const uint8_t *valid,
+                                   const double *lo, const double *hi, const int64_t *ranks, int32_t n_rank, const SpiceyAcMcReq *req,
+                                   int64_t *d_sample, double *d_freq, void *d_work, int64_t work_bytes, void *stream);
+/* A Monte Carlo run on the handle, whose n_inst instances are the samples and whose rows are their nominal values: everything is
+ * judged first (a refusal — SPICEY_ERR_BAD_DESC, text in spicey_ac_last_error — runs nothing); the draw writes scratch value
+ * arrays (the handle's own are never written); ONE sweep, exactly that of spicey_ac_run in either engine and in every path a solve
+ * can take, the dense fallback included, reads them; its voltages stay on the device and currents are neither recorded nor
+ * allocated.  A sample is valid when none of its solves failed.  Per probability p in probs [n_prob], each in [0, 1], the ranks
+ * r = (int64) floor(p (double)(n_valid - 1)) and min(r + 1, n_valid - 1) are reduced, so n_rank = 2 n_prob and the host
+ * interpolates.  Back come freq_stats [n_freq][4 + 2 n_prob], sample [n_inst][2] (int64) and, with keep_first and nominal not
+ * NULL, nominal [n_freq][2]: the complex H of sample 0.  tol [nE], icdf, lo, hi (or NULL) and probs are HOST arrays.  The return
+ * value and spicey_ac_last_inst_status are as after spicey_ac_run.  When no sample is valid nothing is reduced and the outputs
+ * are untouched.  A later spicey_ac_run gives the bits it gave before. */
+int32_t spicey_ac_run_mc(SpiceyAcHandle *h, int64_t n_freq, const double *freqs, const double *vph, const SpiceyAcMcReq *req, const double *tol,
+                         const double *icdf, const double *lo, const double *hi, const double *probs, int32_t n_prob, double *freq_stats,
+                         int64_t *sample, double *nominal);
+/* Duration in ms of the last spicey_ac_run_mc's reduction, and of its draw, measured with HIP events. */
+double spicey_ac_last_mc_ms(SpiceyAcHandle *h);
+double spicey_ac_last_mc_draw_ms(SpiceyAcHandle *h);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Result formatting fast path (host code, no GPU): the CSV text of
  *   formatTranResult(tran)       /root/reference/lib/formatting/formatTranResult.ts:1-23
  * straight from the typed arrays spicey_run filled.  Every number is Number.prototype.toPrecision(6) exactly as

@@ -232,6 +232,22 @@ def ac_sens_req(out_p: int, out_n: int, nR: int, nC: int, nL: int, k_from: int =
     return SpiceyAcSensReq(C.sizeof(SpiceyAcSensReq), int(out_p), int(out_n), int(nR), int(nC), int(nL), 0, int(k_from), int(k_to))
 
 
+class SpiceyAcMcReq(C.Structure):
+    """The request of the Monte Carlo pass (include/spicey_hip.h); struct_bytes = C.sizeof(SpiceyAcMcReq)."""
+    _fields_ = [("struct_bytes", C.c_int64), ("out_p", C.c_int32), ("out_n", C.c_int32), ("log2K", C.c_int32), ("keep_first", C.c_int32),
+                ("seed", C.c_uint64), ("reserved", C.c_int64)]
+
+
+assert C.sizeof(SpiceyAcMcReq) == 40
+MC_FREQ_HEAD = 4    # doubles of a row of d_freq before the order statistics: n_valid, violating samples, sum q, sum q q
+MC_MAX_INST = 16384  # samples one workgroup sorts in LDS
+MC_MAX_LOG2K = 12
+
+
+def ac_mc_req(out_p: int, out_n: int, log2K: int, keep_first: bool = True, seed: int = 0) -> SpiceyAcMcReq:
+    return SpiceyAcMcReq(C.sizeof(SpiceyAcMcReq), int(out_p), int(out_n), int(log2K), int(bool(keep_first)), int(seed) & 0xFFFFFFFFFFFFFFFF, 0)
+
+
 def _i32(a) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.int32)
 

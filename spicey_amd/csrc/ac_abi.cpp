@@ -26,6 +26,7 @@
 #include "ac_sweep.h"
 #include "devbuf.h"
 #include "kernels.h"
+#include "mc.h"
 #include "noise.h"
 #include "sens.h"
 #include "symbolic.h"
@@ -75,7 +76,7 @@ struct SpiceyAcHandle {
   std::vector<double> R_host;    // R [n_inst][nR] in ohms, and on the device from the first noise pass on
   DevBuf<double> d_Rohm;
   bool have_Rohm = false;
-  double last_noise_ms = 0.0, last_sens_ms = 0.0;
+  double last_noise_ms = 0.0, last_sens_ms = 0.0, last_mc_ms = 0.0, last_mc_draw_ms = 0.0;
   int64_t last_slots = 0;        // (instance, frequency) slots of the last sweep
   double last_ms = 0.0, last_measure_ms = 0.0;
   SpiceyAcInstStatus ist;        // per instance of the last sweep (spicey_ac_last_inst_status)
@@ -361,8 +362,9 @@ static bool ac_judge_inject(SpiceyAcHandle *h, const SpiceyAcInject *inj) {
 // launched through the engine, o.status on the host, the stream idle.  The caller copies out or reduces.
 // *done: the call is answered without a sweep (nothing to do, or structurally singular).
 // inj: the current injection of this sweep (null: none; with one, a null vph means every phasor zero).
+// vals: three device arrays {1 / R, C, L} [n_inst][n<kind>] the sweep reads instead of the handle's (null: the handle's).
 static int32_t ac_sweep(SpiceyAcHandle *h, int64_t n_freq, const double *freqs, const double *vph, bool have_out, bool want_i, SpiceyAcSweep &o, bool *done,
-                        const SpiceyAcInject *inj = nullptr, DevBuf<double> *keep_freqs = nullptr) {
+                        const SpiceyAcInject *inj = nullptr, DevBuf<double> *keep_freqs = nullptr, const double *const *vals = nullptr) {
   *done = true;
   h->ist.forget();
   const AcDims &d = h->dims;
@@ -402,7 +404,7 @@ static int32_t ac_sweep(SpiceyAcHandle *h, int64_t n_freq, const double *freqs, 
   HIPCHK(h, hipMemcpyAsync(d_f, freqs, (size_t)n_freq * sizeof(double), hipMemcpyHostToDevice, st));
   if (d.n_v > 0 && vph) HIPCHK(h, hipMemcpyAsync(d_ph, vph, (size_t)d.n_inst * d.n_v * 2 * sizeof(double), hipMemcpyHostToDevice, st));
   else if (d.n_v > 0) HIPCHK(h, hipMemsetAsync(d_ph, 0, (size_t)d.n_inst * d.n_v * 2 * sizeof(double), st));
-  const AcBuffers b{h->d_R, h->d_C, h->d_L, d_f, d_ph, o.d_ov, o.d_oi, d_gW, d_status, n_freq};
+  const AcBuffers b{vals ? vals[0] : h->d_R, vals ? vals[1] : h->d_C, vals ? vals[2] : h->d_L, d_f, d_ph, o.d_ov, o.d_oi, d_gW, d_status, n_freq};
   if (const int32_t rc = h->eng->bind(h, b, st); rc != SPICEY_OK) return rc;
   HIPCHK(h, hipEventRecord(h->q.ev0, st));
   for (int64_t base = 0; base < slots; base += chunk) HIPCHK(h, h->eng->launch(base, std::min(chunk, slots - base), st));
@@ -599,3 +601,118 @@ extern "C" int32_t spicey_ac_run_sens(SpiceyAcHandle *h, int64_t n_freq, const d
 }
 
 extern "C" double spicey_ac_last_sens_ms(SpiceyAcHandle *h) { return h ? h->last_sens_ms : 0.0; }
+
+// The draw of mc.hip into scratch value arrays, ONE sweep of ac_sweep bound to them and left on the device, and the reduction
+// across the instances behind it.
+extern "C" int32_t spicey_ac_run_mc(SpiceyAcHandle *h, int64_t n_freq, const double *freqs, const double *vph, const SpiceyAcMcReq *req, const double *tol,
+                                    const double *icdf, const double *lo, const double *hi, const double *probs, int32_t n_prob, double *freq_stats,
+                                    int64_t *sample, double *nominal) {
+  if (!h) return SPICEY_ERR_BAD_DESC;
+  h->ist.forget();
+  h->last_mc_ms = h->last_mc_draw_ms = 0.0;
+  const AcDims &d = h->dims;
+  const int32_t nE = h->nR + h->nC + h->nL;
+  // (a refused request, tolerance list, table or probability runs nothing: judged on placeholder buffers first, the scratch
+  // arrays and the sweep's own are bound below; the ranks follow from n_valid, which only the sweep tells)
+  if (n_prob < 0 || n_prob > (1 << 20) || (n_prob && !probs)) { h->err = "mc: bad probabilities (n_prob >= 0, a list)"; return SPICEY_ERR_BAD_DESC; }
+  for (int32_t j = 0; j < n_prob; j++)
+    if (!(probs[j] >= 0.0 && probs[j] <= 1.0)) { h->err = "mc: a probability outside [0, 1]"; return SPICEY_ERR_BAD_DESC; }
+  const int32_t n_rank = 2 * n_prob;
+  const int64_t draw_bytes = req ? spicey_mc_draw_bytes(nE, req->log2K) : 0, red_bytes = spicey_mc_reduce_bytes(d.n_inst, n_freq, n_rank);
+  double *some = h->d_R;  // (any non-null pointer: the judges look at null-ness only)
+  SpiceyMcDrawArgs D;
+  SpiceyMcReduceArgs A;
+  if (!spicey_mc_draw_judge(d.n_inst, h->nR, h->nC, h->nL, some, some, some, tol, icdf, req, some, some, some, true, draw_bytes, D, h->err) ||
+      !spicey_mc_reduce_judge(d.n_inst, n_freq, some, d.n_out, nullptr, nullptr, 0, req, freq_stats && sample, red_bytes, A, h->err))
+    return SPICEY_ERR_BAD_DESC;
+  if (!freqs || (d.n_v > 0 && !vph)) { h->err = "bad run arguments"; return SPICEY_ERR_BAD_DESC; }
+  if (h->eng->structurally_singular()) {
+    h->err = "Singular matrix (complex): structurally singular";
+    h->ist.fill(d.n_inst, SPICEY_ERR_SINGULAR, 0);
+    return SPICEY_ERR_SINGULAR;
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  hipStream_t st = h->q.stream;
+  if (!h->have_Rohm) {
+    if (dev_upload(h->d_Rohm, h->R_host.size(), h->R_host.data()) != hipSuccess) { h->err = "upload of the resistances failed"; return SPICEY_ERR_HIP; }
+    h->have_Rohm = true;
+  }
+  const size_t ni = (size_t)d.n_inst;
+  DevBuf<double> d_sR, d_sC, d_sL;
+  DevBuf<uint8_t> d_work;
+  HIPCHK(h, d_sR.alloc(std::max<size_t>(1, ni * (size_t)h->nR)));
+  HIPCHK(h, d_sC.alloc(std::max<size_t>(1, ni * (size_t)h->nC)));
+  HIPCHK(h, d_sL.alloc(std::max<size_t>(1, ni * (size_t)h->nL)));
+  HIPCHK(h, d_work.alloc((size_t)std::max(draw_bytes, red_bytes)));
+  D.R = h->d_Rohm; D.C = h->d_C; D.L = h->d_L; D.oR = d_sR; D.oC = d_sC; D.oL = d_sL;
+  HIPCHK(h, hipEventRecord(h->q.ev0, st));
+  HIPCHK(h, spicey_launch_mc_draw(h->device, D, tol, icdf, d_work, st));
+  HIPCHK(h, hipEventRecord(h->q.ev1, st));
+  HIPCHK(h, hipStreamSynchronize(st));  // (ac_sweep records the same pair again)
+  StreamTimers::elapsed(h->q.ev0, h->q.ev1, &h->last_mc_draw_ms);
+  const double *vals[3] = {d_sR, d_sC, d_sL};
+  SpiceyAcSweep o;
+  bool done = false;
+  const int32_t rc = ac_sweep(h, n_freq, freqs, vph, true, false, o, &done, nullptr, nullptr, vals);
+  if (rc != SPICEY_OK || done) return rc;
+  std::vector<uint8_t> valid(ni, 1);
+  int64_t n_valid = 0;
+  for (size_t s = 0; s < ni; s++) {
+    for (int64_t k = 0; k < n_freq && valid[s]; k++) valid[s] = o.status[s * (size_t)n_freq + (size_t)k] == 0;
+    n_valid += valid[s];
+  }
+  const int32_t sweep_rc = h->ist.from_slots(o.status, d.n_inst, n_freq, h->err);
+  if (n_valid == 0) {
+    if (sweep_rc == SPICEY_OK) { h->err = "mc: no valid sample"; return SPICEY_ERR_SINGULAR; }
+    h->err += " (mc: no valid sample, nothing reduced)";
+    return sweep_rc;
+  }
+  std::vector<int64_t> ranks((size_t)n_rank);
+  for (int32_t j = 0; j < n_prob; j++) {
+    const int64_t r = (int64_t)std::floor(probs[j] * (double)(n_valid - 1));
+    ranks[2 * (size_t)j] = r;
+    ranks[2 * (size_t)j + 1] = std::min<int64_t>(r + 1, n_valid - 1);
+  }
+  std::string why;
+  if (!spicey_mc_reduce_judge(d.n_inst, n_freq, o.d_ov, d.n_out, valid.data(), ranks.data(), n_rank, req, true, red_bytes, A, why)) {
+    h->err = why;
+    return SPICEY_ERR_BAD_DESC;
+  }
+  HIPCHK(h, h->q.want_pass_events(PASS_MEASURE));
+  const hipEvent_t *ev = h->q.pass_ev[PASS_MEASURE];
+  const size_t n_fs = (size_t)n_freq * (size_t)(SPICEY_MC_FREQ_HEAD + n_rank);
+  DevBuf<double> d_fs;
+  DevBuf<int64_t> d_sample;
+  HIPCHK(h, d_fs.alloc(n_fs));
+  HIPCHK(h, d_sample.alloc(ni * 2));
+  HIPCHK(h, hipEventRecord(ev[0], st));
+  HIPCHK(h, spicey_launch_mc_reduce(h->device, A, n_valid == (int64_t)ni ? nullptr : valid.data(), lo, hi, ranks.data(), d_sample, d_fs, d_work, st));
+  HIPCHK(h, hipEventRecord(ev[1], st));
+  HIPCHK(h, hipMemcpyAsync(freq_stats, d_fs, n_fs * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(h, hipMemcpyAsync(sample, d_sample, ni * 2 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  std::vector<double> col_p, col_n;
+  const bool want_nom = nominal && req->keep_first;
+  if (want_nom) {  // (sample 0's columns of the pair: a strided copy of 16 bytes per frequency each, as the noise pass's gain)
+    for (int side = 0; side < 2; side++) {
+      const int32_t col = side ? req->out_n : req->out_p;
+      std::vector<double> &dst = side ? col_n : col_p;
+      if (col < 0) continue;
+      dst.resize((size_t)n_freq * 2);
+      HIPCHK(h, hipMemcpy2DAsync(dst.data(), 2 * sizeof(double), (const double *)o.d_ov + (size_t)col * 2, (size_t)d.n_out * 2 * sizeof(double), 2 * sizeof(double),
+                                 (size_t)n_freq, hipMemcpyDeviceToHost, st));
+    }
+  }
+  HIPCHK(h, hipStreamSynchronize(st));
+  StreamTimers::elapsed(ev[0], ev[1], &h->last_mc_ms);
+  if (want_nom)
+    for (size_t i = 0; i < (size_t)n_freq * 2; i++) {  // (H as spicey_mc_q forms it: one subtraction per part)
+      double x = 0.0;
+      if (!col_p.empty()) x = col_p[i];
+      if (!col_n.empty()) x = x - col_n[i];
+      nominal[i] = x;
+    }
+  return sweep_rc;
+}
+
+extern "C" double spicey_ac_last_mc_ms(SpiceyAcHandle *h) { return h ? h->last_mc_ms : 0.0; }
+extern "C" double spicey_ac_last_mc_draw_ms(SpiceyAcHandle *h) { return h ? h->last_mc_draw_ms : 0.0; }

@@ -27,6 +27,7 @@
 #include "measure.h"
 #include "measure_exec.h"
 #include "noise.h"
+#include "mc.h"
 #include "sens.h"
 #include "power.h"
 #include "values.h"
@@ -1123,6 +1124,30 @@ extern "C" int32_t spicey_ac_sens_device(int32_t device, int32_t n_inst, int64_t
   if (!spicey_sens_judge(n_inst, n_freq, d_v_dir, n_v, d_i_dir, d_i_adj, n_i, d_R, d_C, d_L, tol, d_freqs, req, d_spec && d_peak && d_work, work_bytes, A, g_err))
     return SPICEY_ERR_BAD_DESC;
   return launch_on_device(device, "spicey_launch_sens", [&]() { return spicey_launch_sens(device, A, tol, d_spec, d_peak, d_full, d_work, (hipStream_t)stream); });
+}
+
+extern "C" int64_t spicey_ac_mc_workspace_bytes(int32_t n_inst, int64_t n_freq, int32_t nE, int32_t log2K, int32_t n_rank) {
+  return spicey_mc_workspace_bytes(n_inst, n_freq, nE, log2K, n_rank);
+}
+
+extern "C" int32_t spicey_ac_mc_draw_device(int32_t device, int32_t n_inst, int32_t nR, int32_t nC, int32_t nL, const double *d_R, const double *d_C,
+                                            const double *d_L, const double *tol, const double *icdf, const SpiceyAcMcReq *req, double *d_Rinv_out,
+                                            double *d_C_out, double *d_L_out, void *d_work, int64_t work_bytes, void *stream) {
+  // (the call is judged before the device is touched: a refusal launches nothing)
+  SpiceyMcDrawArgs A;
+  if (!spicey_mc_draw_judge(n_inst, nR, nC, nL, d_R, d_C, d_L, tol, icdf, req, d_Rinv_out, d_C_out, d_L_out, d_work != nullptr, work_bytes, A, g_err))
+    return SPICEY_ERR_BAD_DESC;
+  return launch_on_device(device, "spicey_launch_mc_draw", [&]() { return spicey_launch_mc_draw(device, A, tol, icdf, d_work, (hipStream_t)stream); });
+}
+
+extern "C" int32_t spicey_ac_mc_reduce_device(int32_t device, int32_t n_inst, int64_t n_freq, const double *d_v, int32_t n_v, const uint8_t *valid,
+                                              const double *lo, const double *hi, const int64_t *ranks, int32_t n_rank, const SpiceyAcMcReq *req,
+                                              int64_t *d_sample, double *d_freq, void *d_work, int64_t work_bytes, void *stream) {
+  SpiceyMcReduceArgs A;
+  if (!spicey_mc_reduce_judge(n_inst, n_freq, d_v, n_v, valid, ranks, n_rank, req, d_sample && d_freq && d_work, work_bytes, A, g_err))
+    return SPICEY_ERR_BAD_DESC;
+  return launch_on_device(device, "spicey_launch_mc_reduce",
+                          [&]() { return spicey_launch_mc_reduce(device, A, valid, lo, hi, ranks, d_sample, d_freq, d_work, (hipStream_t)stream); });
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

@@ -107,6 +107,12 @@ SIGNATURES = {
     "spicey_ac_sens_device": (_i32, [_i32, _i32, _i64, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _f64p, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "spicey_ac_run_sens": (_i32, [_vp, _i64, _f64p, _f64p, _vp, _vp, _f64p, _f64p, _f64p, _f64p]),
     "spicey_ac_last_sens_ms": (_f64, [_vp]),
+    "spicey_ac_mc_workspace_bytes": (_i64, [_i32, _i64, _i32, _i32, _i32]),
+    "spicey_ac_mc_draw_device": (_i32, [_i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _f64p, _f64p, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "spicey_ac_mc_reduce_device": (_i32, [_i32, _i32, _i64, _vp, _i32, _vp, _f64p, _f64p, _i64p, _i32, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "spicey_ac_run_mc": (_i32, [_vp, _i64, _f64p, _f64p, _vp, _f64p, _f64p, _f64p, _f64p, _f64p, _i32, _f64p, _i64p, _f64p]),
+    "spicey_ac_last_mc_ms": (_f64, [_vp]),
+    "spicey_ac_last_mc_draw_ms": (_f64, [_vp]),
 }
 EXPORTS = list(SIGNATURES)
 
@@ -246,6 +252,43 @@ def ac_sens_device(n_inst: int, n_freq: int, d_v_dir: int, n_v: int, d_i_dir: in
                                  d_full or None, d_work or None, work_bytes, stream or None)
     if rc != abi.OK:
         _fail("spicey_ac_sens_device", rc, L.spicey_last_error(None))
+
+
+def ac_mc_workspace_bytes(n_inst: int, n_freq: int, nE: int, log2K: int, n_rank: int) -> int:
+    return load().spicey_ac_mc_workspace_bytes(n_inst, n_freq, nE, log2K, n_rank)
+
+
+def _host(a, dtype):
+    return None if a is None else np.ascontiguousarray(a, dtype=dtype)
+
+
+def ac_mc_draw_device(n_inst: int, nR: int, nC: int, nL: int, d_R: int, d_C: int, d_L: int, tol, icdf, req: abi.SpiceyAcMcReq, d_Rinv_out: int, d_C_out: int,
+                      d_L_out: int, d_work: int, work_bytes: int, device: int = 0, stream: int = 0) -> None:
+    """spicey_ac_mc_draw_device: the Monte Carlo draw alone on raw device pointers: d_R (ohms), d_C, d_L nominal [n_inst][n<kind>],
+    the three drawn arrays of the same shapes (the first as 1 / ohms), 0 where the count is 0, d_work of `work_bytes` >=
+    ac_mc_workspace_bytes(...).  tol [nE] and icdf [2^log2K + 1] are HOST arrays (None stands for a null pointer).  Enqueued on
+    `stream`, no synchronisation.  A refusal raises SpiceyNativeError whose `status` is abi.ERR_BAD_DESC."""
+    L = load()
+    t, tab = _host(tol, np.float64), _host(icdf, np.float64)
+    rc = L.spicey_ac_mc_draw_device(device, n_inst, nR, nC, nL, d_R or None, d_C or None, d_L or None, _p(t, C.c_double), _p(tab, C.c_double),
+                                    C.byref(req) if req is not None else None, d_Rinv_out or None, d_C_out or None, d_L_out or None, d_work or None, work_bytes,
+                                    stream or None)
+    if rc != abi.OK:
+        _fail("spicey_ac_mc_draw_device", rc, L.spicey_last_error(None))
+
+
+def ac_mc_reduce_device(n_inst: int, n_freq: int, d_v: int, n_v: int, valid, lo, hi, ranks, req: abi.SpiceyAcMcReq, d_sample: int, d_freq: int, d_work: int,
+                        work_bytes: int, device: int = 0, stream: int = 0) -> None:
+    """spicey_ac_mc_reduce_device: the reduction across instances alone on raw device pointers: d_v [n_inst][n_freq][n_v]
+    complex128, d_sample [n_inst][2] int64, d_freq [n_freq][4 + n_rank], d_work.  valid [n_inst] (bytes, None: all), lo / hi
+    [n_freq] (None: no limit) and ranks [n_rank] are HOST arrays.  Enqueued on `stream`, no synchronisation."""
+    L = load()
+    va, lo_, hi_, rk = _host(valid, np.uint8), _host(lo, np.float64), _host(hi, np.float64), _host(ranks, np.int64)
+    rc = L.spicey_ac_mc_reduce_device(device, n_inst, n_freq, d_v or None, n_v, va.ctypes.data if va is not None else None, _p(lo_, C.c_double),
+                                      _p(hi_, C.c_double), _p(rk, C.c_int64) if rk is not None and len(rk) else None, len(rk) if rk is not None else 0,
+                                      C.byref(req) if req is not None else None, d_sample or None, d_freq or None, d_work or None, work_bytes, stream or None)
+    if rc != abi.OK:
+        _fail("spicey_ac_mc_reduce_device", rc, L.spicey_last_error(None))
 
 
 def fourier_row_doubles(reqs) -> int:
@@ -864,6 +907,31 @@ class AcHandle:
                                        _p(t, C.c_double), _p(spec, C.c_double), _p(peak, C.c_double), _p(fl, C.c_double))
         return self._dress({"spec": spec, "peak": peak, "full": fl, "sens_ms": self.L.spicey_ac_last_sens_ms(self.h)}, rc)
 
+    def run_mc(self, freqs, vph, req: abi.SpiceyAcMcReq, tol, icdf, lo=None, hi=None, probs=()) -> dict:
+        """spicey_ac_run_mc: this handle's instances are the samples, its rows their nominal values.  The draw writes scratch
+        value arrays, one sweep reads them and stays on the device, the reduction across the instances runs behind it;
+        `freq_stats` [n_freq][4 + 2 n_prob], `sample` [n_inst][2] int64 and, with req.keep_first, `nominal` [n_freq] (the complex H
+        of sample 0) come back (include/spicey_hip.h).  tol [nE] in the order R, C, L; icdf [2^log2K + 1]; lo / hi [n_freq]
+        limits of |H|^2 or None; probs the probabilities whose two neighbouring order statistics are wanted."""
+        f = self.flat
+        freqs, ph = self._sweep_args(freqs, vph)
+        nf = len(freqs)
+        t, tab, lo_, hi_ = _host(tol, np.float64), _host(icdf, np.float64), _host(lo, np.float64), _host(hi, np.float64)
+        pr = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
+        for name, a, n in (("tol", t, f.nR + f.nC + f.nL), ("lo", lo_, nf), ("hi", hi_, nf)):
+            if a is not None and a.size != n:
+                raise ValueError(f"run_mc: {name} must have {n} entries, got {a.size}")
+        if tab is not None and req is not None and 0 <= req.log2K <= abi.MC_MAX_LOG2K and tab.size != (1 << req.log2K) + 1:
+            raise ValueError(f"run_mc: icdf must have 2^log2K + 1 = {(1 << req.log2K) + 1} entries, got {tab.size}")
+        stats = np.zeros((max(nf, 0), abi.MC_FREQ_HEAD + 2 * len(pr)))
+        sample = np.zeros((f.n_inst, 2), np.int64)
+        nominal = np.zeros(nf, np.complex128) if req is not None and req.keep_first else None
+        rc = self.L.spicey_ac_run_mc(self.h, nf, _p(freqs, C.c_double), _p(ph.view(np.float64), C.c_double), C.byref(req) if req is not None else None,
+                                     _p(t, C.c_double), _p(tab, C.c_double), _p(lo_, C.c_double), _p(hi_, C.c_double), _p(pr, C.c_double) if len(pr) else None,
+                                     len(pr), _p(stats, C.c_double), _p(sample, C.c_int64), _p(nominal.view(np.float64), C.c_double) if nominal is not None else None)
+        return self._dress({"freq_stats": stats, "sample": sample, "nominal": nominal, "mc_ms": self.L.spicey_ac_last_mc_ms(self.h),
+                            "draw_ms": self.L.spicey_ac_last_mc_draw_ms(self.h)}, rc)
+
     def close(self) -> None:
         if getattr(self, "h", None):
             self.L.spicey_ac_destroy(self.h)
@@ -909,6 +977,10 @@ class _AcCalls:
     def run_ac_sens(self, flat: abi.FlatCircuit, freqs, vph, node_p: int, node_n: int, req: abi.SpiceyAcSensReq, tol, full: bool = False) -> dict:
         """AcHandle.run_sens on a handle of its own: neither sweep's results leave the device."""
         return self._on_ac_handle(flat, lambda h: h.run_sens(freqs, vph, node_p, node_n, req, tol, full))
+
+    def run_ac_mc(self, flat: abi.FlatCircuit, freqs, vph, req: abi.SpiceyAcMcReq, tol, icdf, lo=None, hi=None, probs=()) -> dict:
+        """AcHandle.run_mc on a handle of its own: the samples' values and their sweep never leave the device."""
+        return self._on_ac_handle(flat, lambda h: h.run_mc(freqs, vph, req, tol, icdf, lo, hi, probs))
 
 
 class HipBackend(_AcCalls):
