@@ -993,6 +993,102 @@ double spicey_ac_last_mc_ms(SpiceyAcHandle *h);
 double spicey_ac_last_mc_draw_ms(SpiceyAcHandle *h);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Monte Carlo of transient runs: the distribution of measured scalars over n_inst samples whose R, C and L are drawn on the
+ * device, run as the instances of ONE transient, measured by the passes of spicey_run_reduced and reduced ACROSS the instances
+ * on the device.  Fixed operation order (tran_mc_exec.h), integer random numbers, no FMA contraction, no atomics: the CPU and
+ * the device agree on every bit.
+ *
+ * The draw is that of spicey_ac_mc_draw_device (counter, key, table, operations), except that a resistor's array gets R' = R g
+ * in ohms: the transient kernels form 1.0 / R themselves.
+ *
+ * A scalar is a program of at most 48 instructions over a stack of at most 4 doubles, run per sample on its rows of the passes
+ * with fixed rows — 0 measure [8], 1 timing [8], 2 power [SPICEY_POWER_ROW]:
+ *   FIELD (pass, row, field)   pushes rows_pass[s][row][field]
+ *   CONST (c)                  pushes c
+ *   ADD SUB MUL DIV            pop b, pop a, push a o b: one rounded operation
+ *   GUARD                      pops g; if !(g >= 0) the scalar is NaN whatever else the program computes
+ * and the one value left is x[s][j]; a NaN is stored as 0x7ff8000000000000, and so is every x of an invalid sample.
+ * There is no comparison other than GUARD's: "a > 0" is GUARD(a) followed by GUARD(0 / a), whose quotient is NaN exactly at a = 0.
+ *
+ * The reduction.  A violation of scalar j is !(x >= lo[j] && x <= hi[j]): a NaN violates (lo / hi NULL: -inf / +inf).
+ *   d_sample [n_inst][2] int64           {scalars the sample violates, the lowest such j or -1}; {-1, -1} if invalid
+ *   d_stat   [n_scalar][8 + 2 n_prob]    {n_valid, n_num, n_viol, sum x, sum x x, s_min, s_max, 0, q_(r0), q_(r0 + 1), q_(r1), ...}:
+ *                                        n_num the valid samples that are not NaN; the sums over those, sorted, lane l of 64
+ *                                        adding x[l], x[l + 64], ... from +0.0 and the partials meeting by s[l] += s[l + stride],
+ *                                        stride 32 .. 1; s_min / s_max the lowest sample index with the smallest / largest
+ *                                        value; per probability p the order statistics at r = (int64)(p (double)(n_num - 1))
+ *                                        and min(r + 1, n_num - 1).  n_num = 0: sums +0.0, indices -1, order statistics NaN.
+ * The values are ordered as unsigned integers (-inf < ... < -0 < +0 < ... < +inf < NaN < invalid) by one workgroup per scalar
+ * in LDS, so n_inst <= 16384. */
+#define SPICEY_MCOP_FIELD 1
+#define SPICEY_MCOP_CONST 2
+#define SPICEY_MCOP_ADD 3
+#define SPICEY_MCOP_SUB 4
+#define SPICEY_MCOP_MUL 5
+#define SPICEY_MCOP_DIV 6
+#define SPICEY_MCOP_GUARD 7
+#define SPICEY_MC_SCALAR_INS 48
+#define SPICEY_MC_SCALAR_STACK 4
+typedef struct SpiceyMcIns {
+  int32_t op;                /* SPICEY_MCOP_* */
+  int32_t pass, row, field;  /* FIELD; else 0 */
+  double c;                  /* CONST (finite); else 0 */
+} SpiceyMcIns;               /* 24 bytes */
+typedef struct SpiceyMcScalar {
+  int32_t n_ins;             /* 1 .. SPICEY_MC_SCALAR_INS */
+  int32_t reserved;          /* 0 */
+  SpiceyMcIns ins[SPICEY_MC_SCALAR_INS];
+} SpiceyMcScalar;            /* 1160 bytes */
+typedef struct SpiceyTranMcReq {
+  int64_t struct_bytes;
+  int32_t log2K;             /* the table has 2^log2K + 1 entries */
+  int32_t keep_first;        /* nonzero: sample 0 is the nominal circuit */
+  uint64_t seed;
+  int64_t reserved;          /* 0 */
+} SpiceyTranMcReq;
+/* The rows of one pass on the device: [n_inst][n_rows][stride] (d_rows NULL and n_rows 0: the pass did not run). */
+typedef struct SpiceyMcRows {
+  const double *d_rows;
+  int32_t n_rows, stride;
+} SpiceyMcRows;
+/* Bytes of device workspace that serve spicey_tran_mc_draw_device and spicey_tran_mc_reduce_device alike; -1 for arguments no
+ * launch accepts. */
+int64_t spicey_tran_mc_workspace_bytes(int32_t n_inst, int32_t n_scalar, int32_t nE, int32_t log2K, int32_t n_prob);
+/* The draw alone on any DEVICE buffers, as spicey_ac_mc_draw_device but with d_R_out in ohms.  Refusals are SPICEY_ERR_BAD_DESC
+ * with a text starting "tran mc: " in spicey_last_error(NULL), nothing launched. */
+int32_t spicey_tran_mc_draw_device(int32_t device, int32_t n_inst, int32_t nR, int32_t nC, int32_t nL, const double *d_R, const double *d_C,
+                                   const double *d_L, const double *tol, const double *icdf, const SpiceyTranMcReq *req, double *d_R_out,
+                                   double *d_C_out, double *d_L_out, void *d_work, int64_t work_bytes, void *stream);
+/* The scalars and the reduction alone on any DEVICE row buffers: rows [3] (measure, timing, power), scalars [n_scalar], valid
+ * [n_inst] (bytes, NULL: all), lo / hi [n_scalar] (or NULL) and probs [n_prob] (each in [0, 1]) are HOST data; d_x [n_inst][n_scalar],
+ * d_stat and d_sample as above.  Needs no handle; enqueued on `stream` without synchronising.  SPICEY_ERR_BAD_DESC, text
+ * starting "tran mc: ", nothing launched, for: a program whose stack underflows, exceeds 4 or does not end at depth 1; n_ins
+ * outside [1, 48]; an unknown opcode; a FIELD of a pass without rows, or whose pass, row or field is out of range; a CONST that
+ * is not finite; a nonzero reserved word or unused instruction word; n_inst <= 0 or > 16384; n_scalar <= 0; n_prob < 0; a
+ * probability outside [0, 1]; a NaN limit; a null buffer; a pass with n_rows < 0, stride <= 0 or rows without a pointer; a
+ * workspace that is too small. */
+int32_t spicey_tran_mc_reduce_device(int32_t device, int32_t n_inst, const SpiceyMcRows *rows, const SpiceyMcScalar *scalars, int32_t n_scalar,
+                                     const uint8_t *valid, const double *lo, const double *hi, const double *probs, int32_t n_prob, double *d_x,
+                                     double *d_stat, int64_t *d_sample, void *d_work, int64_t work_bytes, void *stream);
+/* A Monte Carlo run on the handle, whose n_inst instances are the samples and whose value rows are their nominal values.
+ * Everything is judged first (a refusal — SPICEY_ERR_BAD_DESC, text in spicey_last_error(h) — runs nothing); the draw writes
+ * scratch value arrays (the handle's own are never written); ONE transient, exactly that of spicey_run_reduced, reads them; the
+ * passes of `lists` run behind it as in spicey_run_reduced and their rows stay on the device (the result pointers of `lists`
+ * are ignored); a sample is valid iff its spicey_last_inst_status entry is 0; the scalars and the reduction run over the valid
+ * samples, and stat [n_scalar][8 + 2 n_prob], sample [n_inst][2], x [n_inst][n_scalar] (or NULL) and iters (or NULL) come
+ * back.  The spectrum, fourier and values lists are refused in this call.  With no valid sample nothing is reduced and the
+ * outputs are untouched.  The return value, the end state and spicey_last_inst_status are as after spicey_run_reduced of the
+ * drawn circuits; a later plain run binds the handle's own arrays and gives the bits it gave before.  tol [nE], icdf, scalars,
+ * lo, hi (or NULL) and probs are HOST arrays. */
+int32_t spicey_run_mc(SpiceyHandle *h, int64_t steps, double dt, const double *src_table, int32_t src_per_inst, const SpiceyReducedLists *lists,
+                      const SpiceyTranMcReq *req, const double *tol, const double *icdf, const SpiceyMcScalar *scalars, int32_t n_scalar,
+                      const double *lo, const double *hi, const double *probs, int32_t n_prob, double *stat, int64_t *sample, double *x,
+                      int32_t *iters);
+/* Duration in ms of the last spicey_run_mc's scalars and reduction, and of its draw, measured with HIP events. */
+double spicey_last_tran_mc_ms(SpiceyHandle *h);
+double spicey_last_tran_mc_draw_ms(SpiceyHandle *h);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Result formatting fast path (host code, no GPU): the CSV text of
  *   formatTranResult(tran)       /root/reference/lib/formatting/formatTranResult.ts:1-23
  * straight from the typed arrays spicey_run filled.  Every number is Number.prototype.toPrecision(6) exactly as

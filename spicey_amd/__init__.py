@@ -14,11 +14,14 @@ with a current injected at the output and reduce it on the device to output impe
 shares of it; simulateSens / simulateSensBatch (spicey_amd.sens) run that sweep and the plain one and reduce the two on the
 device to every element's first-order sensitivity of magnitude and phase and to worst-case and root-sum-square tolerance bounds;
 simulateMonteCarlo (spicey_amd.mc) draws the samples of a tolerance analysis on the device, sweeps them as the instances of one
-launch and reduces them across the instances to quantile bands, moments and the yield against a spec mask.
+launch and reduces them across the instances to quantile bands, moments and the yield against a spec mask;
+measureMonteCarlo (spicey_amd.tran_mc) does the same for transient runs: the samples are the instances of one transient, and the
+scalars of measureTRAN's measures are reduced across them to quantiles, moments, yields against limits and the worst samples.
 """
 from .ac_batch import simulateACBatch  # noqa: F401
 from .ac_measure import measureAC, measureACBatch  # noqa: F401
 from .noise import simulateNoise, simulateNoiseBatch  # noqa: F401
 from .sens import simulateSens, simulateSensBatch  # noqa: F401
 from .mc import mc_values, simulateMonteCarlo  # noqa: F401
+from .tran_mc import measureMonteCarlo  # noqa: F401
 from .measure import deriv, efficiency, find, measureTRAN, measureTRANBatch, power, sample, trace  # noqa: F401

@@ -248,6 +248,31 @@ def ac_mc_req(out_p: int, out_n: int, log2K: int, keep_first: bool = True, seed:
     return SpiceyAcMcReq(C.sizeof(SpiceyAcMcReq), int(out_p), int(out_n), int(log2K), int(bool(keep_first)), int(seed) & 0xFFFFFFFFFFFFFFFF, 0)
 
 
+class SpiceyTranMcReq(C.Structure):
+    """The request of a Monte Carlo of transient runs (include/spicey_hip.h); struct_bytes = C.sizeof(SpiceyTranMcReq)."""
+    _fields_ = [("struct_bytes", C.c_int64), ("log2K", C.c_int32), ("keep_first", C.c_int32), ("seed", C.c_uint64), ("reserved", C.c_int64)]
+
+
+class SpiceyMcRows(C.Structure):
+    """The device rows of one pass for spicey_tran_mc_reduce_device: [n_inst][n_rows][stride]."""
+    _fields_ = [("d_rows", C.c_void_p), ("n_rows", C.c_int32), ("stride", C.c_int32)]
+
+
+# one instruction of a scalar's program and the program (include/spicey_hip.h, SpiceyMcIns / SpiceyMcScalar; spicey_amd/tran_mc.py builds them)
+MC_INS_DTYPE = np.dtype([("op", "<i4"), ("pass", "<i4"), ("row", "<i4"), ("field", "<i4"), ("c", "<f8")])
+MC_SCALAR_INS, MC_SCALAR_STACK = 48, 4
+MC_SCALAR_DTYPE = np.dtype([("n_ins", "<i4"), ("reserved", "<i4"), ("ins", MC_INS_DTYPE, (MC_SCALAR_INS,))])
+assert C.sizeof(SpiceyTranMcReq) == 32 and C.sizeof(SpiceyMcRows) == 16 and MC_INS_DTYPE.itemsize == 24 and MC_SCALAR_DTYPE.itemsize == 1160
+MCOP_FIELD, MCOP_CONST, MCOP_ADD, MCOP_SUB, MCOP_MUL, MCOP_DIV, MCOP_GUARD = 1, 2, 3, 4, 5, 6, 7
+MC_PASS_MEASURE, MC_PASS_TIMING, MC_PASS_POWER = 0, 1, 2
+MC_PASS_STRIDE = (8, 8, POWER_ROW)
+TRAN_MC_STAT_HEAD = 8  # doubles of a row of d_stat before the order statistics: n_valid, n_num, n_viol, sum x, sum x x, s_min, s_max, 0
+
+
+def tran_mc_req(log2K: int, keep_first: bool = True, seed: int = 0) -> SpiceyTranMcReq:
+    return SpiceyTranMcReq(C.sizeof(SpiceyTranMcReq), int(log2K), int(bool(keep_first)), int(seed) & 0xFFFFFFFFFFFFFFFF, 0)
+
+
 def _i32(a) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.int32)
 

@@ -34,6 +34,7 @@
 #include "spectrum.h"
 #include "timing.h"
 #include "timing_exec.h"
+#include "tran_mc.h"
 #include "symbolic.h"
 #include "fronts_exec_consts.h"
 
@@ -104,6 +105,7 @@ struct SpiceyHandle {
   DevBuf<int32_t> d_status; DevBuf<unsigned long long> d_solves, d_prof;
   hipStream_t last_stream = nullptr;
   double last_pass_ms[N_PASS] = {};  // the reduction passes of the last spicey_run_measure* (0: the pass did not run)
+  double last_tran_mc_ms = 0.0, last_tran_mc_draw_ms = 0.0;  // the last spicey_run_mc: its scalars and reduction, its draw
   bool pending = false;
   int64_t last_solves = 0;
   double last_ms = 0.0;
@@ -404,8 +406,11 @@ static int32_t check_structure(SpiceyHandle *h) {
   return SPICEY_ERR_SINGULAR;
 }
 
-extern "C" int32_t spicey_run_device_src(SpiceyHandle *h, int64_t steps, double dt, const double *d_src_table, int32_t src_per_inst,
-                                         double *d_out_v, double *d_out_i, int32_t *d_iters, void *stream) {
+// The body of spicey_run_device_src.  vals: null, or the device arrays {R, C, L} ([n_inst][n<kind>]: ohms, farads, henries)
+// this run reads in the place of the handle's own (spicey_run_mc: the drawn values); the kernels derive everything they
+// keep about the values in their own prologue, so nothing else changes.
+static int32_t run_device_src(SpiceyHandle *h, int64_t steps, double dt, const double *d_src_table, int32_t src_per_inst, double *d_out_v, double *d_out_i,
+                              int32_t *d_iters, void *stream, const double *const *vals) {
   if (!h) return SPICEY_ERR_BAD_DESC;
   if (const int32_t rc0 = check_run_args(h, steps, d_out_v, d_src_table, src_per_inst); rc0 != SPICEY_OK) return rc0;
   if (const int32_t rc0 = check_structure(h); rc0 != SPICEY_OK) return rc0;
@@ -427,7 +432,7 @@ extern "C" int32_t spicey_run_device_src(SpiceyHandle *h, int64_t steps, double 
   R.no_reuse = (h->opt.debug >> 1) & 1;
   R.steps = steps;
   R.dt = dt;
-  R.R_val = h->d_R; R.C_val = h->d_C; R.L_val = h->d_L;
+  R.R_val = vals ? vals[0] : h->d_R; R.C_val = vals ? vals[1] : h->d_C; R.L_val = vals ? vals[2] : h->d_L;
   R.S_ron = h->d_Sron; R.S_roff = h->d_Sroff; R.S_von = h->d_Svon; R.S_voff = h->d_Svoff;
   R.D_is = h->d_Dis; R.D_n = h->d_Dn;
   R.C_vprev = h->state.Cv; R.L_iprev = h->state.Li; R.D_vdprev = h->state.Dv; R.S_ison = h->state.Son;
@@ -486,6 +491,11 @@ extern "C" int32_t spicey_run_device_src(SpiceyHandle *h, int64_t steps, double 
   h->pending = true;
   h->last_stream = st;
   return SPICEY_OK;
+}
+
+extern "C" int32_t spicey_run_device_src(SpiceyHandle *h, int64_t steps, double dt, const double *d_src_table, int32_t src_per_inst,
+                                         double *d_out_v, double *d_out_i, int32_t *d_iters, void *stream) {
+  return run_device_src(h, steps, dt, d_src_table, src_per_inst, d_out_v, d_out_i, d_iters, stream, nullptr);
 }
 
 extern "C" int32_t spicey_run_device(SpiceyHandle *h, int64_t steps, double dt, const double *d_src_table, double *d_out_v,
@@ -793,12 +803,38 @@ struct ReducedLists {
   int32_t values_stride = 0;
 };
 
-// What the five entry points share: one transient run into device buffers of this call's own, the reductions on the
-// handle's stream behind it, and only their results and `iters` on the way back.
-static int32_t run_reduced(SpiceyHandle *h, int64_t steps, double dt, const double *src_table, int32_t src_per_inst, const ReducedLists &a, int32_t *iters) {
+// What spicey_run_mc adds to a reduced run: the draw in front of the transient, which then reads the drawn values, and behind
+// the passes — whose rows stay on the device — the scalars and the reduction across the instances (tran_mc.hip).
+struct TranMcCall {
+  const SpiceyTranMcReq *req; const double *tol, *icdf;
+  const SpiceyMcScalar *scalars; int32_t n_scalar;
+  const double *lo, *hi, *probs; int32_t n_prob;
+  double *stat; int64_t *sample; double *x;
+};
+namespace {
+struct EventPair {  // (a call's own pair of timing events)
+  hipEvent_t a = nullptr, b = nullptr;
+  EventPair() = default;
+  EventPair(const EventPair &) = delete;
+  ~EventPair() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+  hipError_t create() { const hipError_t e = hipEventCreate(&a); return e != hipSuccess ? e : hipEventCreate(&b); }
+};
+}  // namespace
+
+// What the entry points share: one transient run into device buffers of this call's own, the reductions on the
+// handle's stream behind it, and only their results and `iters` on the way back.  mc: null, or what spicey_run_mc adds.
+static int32_t run_reduced(SpiceyHandle *h, int64_t steps, double dt, const double *src_table, int32_t src_per_inst, const ReducedLists &a, int32_t *iters,
+                           const TranMcCall *mc = nullptr) {
   if (!h) return SPICEY_ERR_BAD_DESC;
   double *const outs[N_PASS] = {a.meas, a.four, a.timing, a.spec, a.power, a.values};
   const int32_t counts[N_PASS] = {a.n_req, a.n_four, a.n_tim, a.n_spec, a.n_power, a.n_values};
+  if (mc) {
+    h->last_tran_mc_ms = h->last_tran_mc_draw_ms = 0.0;
+    const char *what = !mc->stat || !mc->sample ? "tran mc: null buffer"
+                       : a.n_four > 0 || a.n_spec > 0 || a.n_values > 0 ? "tran mc: the fourier, spectrum and values lists are not reduced by this call (measure, timing and power are)"
+                       : nullptr;
+    if (what) { forget_last_run(h); h->err = what; return SPICEY_ERR_BAD_DESC; }
+  }
   if (a.entry < 0) {
     int first_on = -1;
     for (int p = N_PASS - 1; p >= 0; p--) {
@@ -806,8 +842,10 @@ static int32_t run_reduced(SpiceyHandle *h, int64_t steps, double dt, const doub
       if (counts[p] > 0) first_on = p;
     }
     if (first_on < 0) { forget_last_run(h); h->err = "reduced: every list is empty (at least one count must be > 0)"; return SPICEY_ERR_BAD_DESC; }
-    if (const int32_t rc0 = check_run_args(h, steps, outs[first_on], src_table, src_per_inst); rc0 != SPICEY_OK) return rc0;
-    for (int p = 0; p < N_PASS; p++)
+    // (a Monte Carlo run leaves the passes' rows on the device: what it brings back is `stat`, and the lists' result pointers
+    // are not looked at)
+    if (const int32_t rc0 = check_run_args(h, steps, mc ? mc->stat : outs[first_on], src_table, src_per_inst); rc0 != SPICEY_OK) return rc0;
+    for (int p = 0; p < N_PASS && !mc; p++)
       if (counts[p] > 0 && !outs[p]) { h->err = "reduced: a result pointer is null where its count is > 0"; return SPICEY_ERR_BAD_DESC; }
   } else if (const int32_t rc0 = check_run_args(h, steps, outs[a.entry], src_table, src_per_inst); rc0 != SPICEY_OK) return rc0;
   if (a.entry == 1 && (a.n_req < 0 || (a.n_req > 0 && !a.meas))) { h->err = "fourier: n_req must be >= 0, and meas not null when n_req > 0"; return SPICEY_ERR_BAD_DESC; }
@@ -851,6 +889,23 @@ static int32_t run_reduced(SpiceyHandle *h, int64_t steps, double dt, const doub
   if (on[PASS_VALUES] && !spicey_val_judge(ni, np, dt, true, P.nOut, true, P.nCur, a.vreqs, a.n_values, a.pts, a.n_pts, on[PASS_TIMING], a.n_tim, true, a.values_stride,
                                            INT64_MAX, vplan, h->err))
     return SPICEY_ERR_BAD_DESC;
+  // (the Monte Carlo request, tolerances, table, programs, limits and probabilities, judged on placeholder buffers: the scratch
+  // arrays and the passes' rows are bound below)
+  SpiceyMcDrawArgs mcD{};
+  SpiceyTmcArgs mcA{};
+  int64_t mc_work_bytes = 0;
+  if (mc) {
+    double dummy = 0.0, *some = &dummy;  // (any non-null pointer: the judges look at null-ness only)
+    const int64_t draw_bytes = mc->req ? spicey_mc_draw_bytes(P.nR + P.nC + P.nL, mc->req->log2K) : 0;
+    const int64_t red_bytes = spicey_tmc_reduce_bytes(ni, mc->n_scalar, mc->n_prob);
+    const SpiceyMcRows jr[SPICEY_TMC_N_PASS] = {{on[PASS_MEASURE] ? some : nullptr, on[PASS_MEASURE] ? a.n_req : 0, 8},
+                                                {on[PASS_TIMING] ? some : nullptr, on[PASS_TIMING] ? a.n_tim : 0, 8},
+                                                {on[PASS_POWER] ? some : nullptr, on[PASS_POWER] ? a.n_power : 0, SPICEY_POWER_ROW}};
+    if (!spicey_tmc_draw_judge(ni, P.nR, P.nC, P.nL, some, some, some, mc->tol, mc->icdf, mc->req, some, some, some, true, draw_bytes, mcD, h->err) ||
+        !spicey_tmc_reduce_judge(ni, jr, mc->scalars, mc->n_scalar, mc->lo, mc->hi, mc->probs, mc->n_prob, true, red_bytes, mcA, h->err))
+      return SPICEY_ERR_BAD_DESC;
+    mc_work_bytes = std::max(draw_bytes, red_bytes);
+  }
   const auto names_a_current = [](const auto &list) { return std::any_of(list.begin(), list.end(), [](const auto &q) { return q.signal == 1; }); };
   const bool need_i = names_a_current(table) || names_a_current(fplan.table) || names_a_current(tplan.edges) || names_a_current(splan.table) ||
                       std::any_of(ptable.begin(), ptable.end(), [](const SpiceyPowerDevReq &q) { return q.a_signal == 1 || q.b_signal == 1; }) ||
@@ -910,7 +965,26 @@ static int32_t run_reduced(SpiceyHandle *h, int64_t steps, double dt, const doub
   }
   if (on[PASS_TIMING]) d_timing_rows = pass[PASS_TIMING].d_out;
   for (double &ms : h->last_pass_ms) ms = 0.0;
-  int32_t rc = spicey_run_device_src(h, steps, dt, r.d_src, src_per_inst, r.d_v, r.d_i, r.d_it, st);
+  // (a Monte Carlo run: the draw into scratch value arrays of this call's own, which the transient then reads; they live
+  // until the call returns, so a launch that spicey_sync repeats reads them again)
+  DevBuf<double> d_sR, d_sC, d_sL;
+  DevBuf<uint8_t> d_mc_work;
+  EventPair ev_draw, ev_red;
+  const double *mc_vals[3] = {nullptr, nullptr, nullptr};
+  if (mc) {
+    HIPCHK(h, d_sR.alloc(std::max<size_t>(1, (size_t)ni * (size_t)P.nR)));
+    HIPCHK(h, d_sC.alloc(std::max<size_t>(1, (size_t)ni * (size_t)P.nC)));
+    HIPCHK(h, d_sL.alloc(std::max<size_t>(1, (size_t)ni * (size_t)P.nL)));
+    HIPCHK(h, d_mc_work.alloc((size_t)mc_work_bytes));
+    HIPCHK(h, ev_draw.create());
+    HIPCHK(h, ev_red.create());
+    mcD.R = h->d_R; mcD.C = h->d_C; mcD.L = h->d_L; mcD.oR = d_sR; mcD.oC = d_sC; mcD.oL = d_sL;
+    HIPCHK(h, hipEventRecord(ev_draw.a, st));
+    HIPCHK(h, spicey_launch_tmc_draw(h->device, mcD, mc->tol, mc->icdf, d_mc_work, st));
+    HIPCHK(h, hipEventRecord(ev_draw.b, st));
+    mc_vals[0] = d_sR; mc_vals[1] = d_sC; mc_vals[2] = d_sL;
+  }
+  int32_t rc = run_device_src(h, steps, dt, r.d_src, src_per_inst, r.d_v, r.d_i, r.d_it, st, mc ? mc_vals : nullptr);
   if (rc != SPICEY_OK) return rc;
   const char *failed = "";
   auto reduce = [&]() {
@@ -934,13 +1008,65 @@ static int32_t run_reduced(SpiceyHandle *h, int64_t steps, double dt, const doub
   if (rc == SPICEY_OK || rc == SPICEY_ERR_SINGULAR) {
     for (int p = 0; p < N_PASS; p++)
       if (pass[p].on) StreamTimers::elapsed(h->q.pass_ev[p][0], h->q.pass_ev[p][1], &h->last_pass_ms[p]);
-    Roctx range_copy("spicey_run_measure:results");
-    for (const Pass &t : pass)
-      if (t.on) HIPCHK(h, hipMemcpy(t.out, t.d_out, t.n_out * sizeof(double), hipMemcpyDeviceToHost));
+    if (mc) {
+      StreamTimers::elapsed(ev_draw.a, ev_draw.b, &h->last_tran_mc_draw_ms);
+      // a sample is valid iff it finished; with none nothing is reduced and the outputs stay as they are
+      std::vector<int32_t> ist((size_t)ni);
+      std::vector<uint8_t> valid((size_t)ni);
+      spicey_last_inst_status(h, ist.data());
+      int32_t n_valid = 0;
+      for (int32_t s = 0; s < ni; s++) n_valid += valid[(size_t)s] = ist[(size_t)s] == 0;
+      if (n_valid > 0) {
+        // (the record was judged before anything ran, on placeholders: the passes' rows take their place)
+        const int row_pass[SPICEY_TMC_N_PASS] = {PASS_MEASURE, PASS_TIMING, PASS_POWER};
+        for (int p = 0; p < SPICEY_TMC_N_PASS; p++) mcA.rows[p] = mcA.n_rows[p] > 0 ? (const double *)pass[row_pass[p]].d_out : nullptr;
+        const size_t n_x = (size_t)ni * (size_t)mc->n_scalar, n_stat = (size_t)mc->n_scalar * (size_t)(SPICEY_TMC_STAT_HEAD + 2 * mc->n_prob);
+        DevBuf<double> d_x, d_stat;
+        DevBuf<int64_t> d_sample;
+        HIPCHK(h, d_x.alloc(n_x));
+        HIPCHK(h, d_stat.alloc(n_stat));
+        HIPCHK(h, d_sample.alloc((size_t)ni * 2));
+        HIPCHK(h, hipEventRecord(ev_red.a, st));
+        HIPCHK(h, spicey_launch_tmc_reduce(h->device, mcA, mc->scalars, n_valid == ni ? nullptr : valid.data(), mc->lo, mc->hi, mc->probs, d_x, d_stat, d_sample,
+                                           d_mc_work, st));
+        HIPCHK(h, hipEventRecord(ev_red.b, st));
+        HIPCHK(h, hipMemcpyAsync(mc->stat, d_stat, n_stat * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIPCHK(h, hipMemcpyAsync(mc->sample, d_sample, (size_t)ni * 2 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        if (mc->x) HIPCHK(h, hipMemcpyAsync(mc->x, d_x, n_x * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIPCHK(h, hipStreamSynchronize(st));
+        StreamTimers::elapsed(ev_red.a, ev_red.b, &h->last_tran_mc_ms);
+      } else if (rc == SPICEY_OK) {
+        h->err = "tran mc: no valid sample";
+        rc = SPICEY_ERR_SINGULAR;
+      } else h->err += " (tran mc: no valid sample, nothing reduced)";
+    } else {
+      Roctx range_copy("spicey_run_measure:results");
+      for (const Pass &t : pass)
+        if (t.on) HIPCHK(h, hipMemcpy(t.out, t.d_out, t.n_out * sizeof(double), hipMemcpyDeviceToHost));
+    }
     if (const int32_t rc0 = r.copy_out(h, nullptr, nullptr, iters); rc0 != SPICEY_OK) return rc0;
   }
   return rc;
 }
+
+extern "C" int32_t spicey_run_mc(SpiceyHandle *h, int64_t steps, double dt, const double *src_table, int32_t src_per_inst, const SpiceyReducedLists *l,
+                                 const SpiceyTranMcReq *req, const double *tol, const double *icdf, const SpiceyMcScalar *scalars, int32_t n_scalar,
+                                 const double *lo, const double *hi, const double *probs, int32_t n_prob, double *stat, int64_t *sample, double *x,
+                                 int32_t *iters) {
+  if (!h) return SPICEY_ERR_BAD_DESC;
+  const char *what = !l ? "tran mc: lists must not be null"
+                     : l->struct_bytes < (int64_t)sizeof(SpiceyReducedLists) ? "tran mc: lists.struct_bytes is smaller than sizeof(SpiceyReducedLists)"
+                     : l->reserved != 0 ? "tran mc: lists.reserved must be 0" : nullptr;
+  if (what) { forget_last_run(h); h->err = what; return SPICEY_ERR_BAD_DESC; }
+  ReducedLists a{-1, l->reqs, l->n_req, nullptr, l->freqs, l->n_four, nullptr, l->four_stride, l->treqs, l->n_timing, nullptr,
+                 l->sreqs, l->n_spec, nullptr, l->spec_stride, l->preqs, l->n_power, nullptr};
+  a.vreqs = l->vreqs; a.n_values = l->n_values; a.pts = l->pts; a.n_pts = l->n_pts; a.values_stride = l->values_stride;
+  const TranMcCall mc{req, tol, icdf, scalars, n_scalar, lo, hi, probs, n_prob, stat, sample, x};
+  return run_reduced(h, steps, dt, src_table, src_per_inst, a, iters, &mc);
+}
+
+extern "C" double spicey_last_tran_mc_ms(SpiceyHandle *h) { return h ? h->last_tran_mc_ms : 0.0; }
+extern "C" double spicey_last_tran_mc_draw_ms(SpiceyHandle *h) { return h ? h->last_tran_mc_draw_ms : 0.0; }
 
 extern "C" int32_t spicey_run_measure(SpiceyHandle *h, int64_t steps, double dt, const double *src_table, int32_t src_per_inst, const SpiceyMeasReq *reqs,
                                       int32_t n_req, double *meas, int32_t *iters) {
@@ -1148,6 +1274,32 @@ extern "C" int32_t spicey_ac_mc_reduce_device(int32_t device, int32_t n_inst, in
     return SPICEY_ERR_BAD_DESC;
   return launch_on_device(device, "spicey_launch_mc_reduce",
                           [&]() { return spicey_launch_mc_reduce(device, A, valid, lo, hi, ranks, d_sample, d_freq, d_work, (hipStream_t)stream); });
+}
+
+// Monte Carlo of transient runs (include/spicey_hip.h): the draw and the reduction of tran_mc.hip on any device buffers, no handle.
+extern "C" int64_t spicey_tran_mc_workspace_bytes(int32_t n_inst, int32_t n_scalar, int32_t nE, int32_t log2K, int32_t n_prob) {
+  return spicey_tmc_workspace_bytes(n_inst, n_scalar, nE, log2K, n_prob);
+}
+
+extern "C" int32_t spicey_tran_mc_draw_device(int32_t device, int32_t n_inst, int32_t nR, int32_t nC, int32_t nL, const double *d_R, const double *d_C,
+                                              const double *d_L, const double *tol, const double *icdf, const SpiceyTranMcReq *req, double *d_R_out,
+                                              double *d_C_out, double *d_L_out, void *d_work, int64_t work_bytes, void *stream) {
+  // (the call is judged before the device is touched: a refusal launches nothing)
+  SpiceyMcDrawArgs A;
+  if (!spicey_tmc_draw_judge(n_inst, nR, nC, nL, d_R, d_C, d_L, tol, icdf, req, d_R_out, d_C_out, d_L_out, d_work != nullptr, work_bytes, A, g_err))
+    return SPICEY_ERR_BAD_DESC;
+  return launch_on_device(device, "spicey_launch_tmc_draw", [&]() { return spicey_launch_tmc_draw(device, A, tol, icdf, d_work, (hipStream_t)stream); });
+}
+
+extern "C" int32_t spicey_tran_mc_reduce_device(int32_t device, int32_t n_inst, const SpiceyMcRows *rows, const SpiceyMcScalar *scalars, int32_t n_scalar,
+                                                const uint8_t *valid, const double *lo, const double *hi, const double *probs, int32_t n_prob, double *d_x,
+                                                double *d_stat, int64_t *d_sample, void *d_work, int64_t work_bytes, void *stream) {
+  SpiceyTmcArgs A;
+  if (!spicey_tmc_reduce_judge(n_inst, rows, scalars, n_scalar, lo, hi, probs, n_prob, d_x && d_stat && d_sample && d_work, work_bytes, A, g_err))
+    return SPICEY_ERR_BAD_DESC;
+  return launch_on_device(device, "spicey_launch_tmc_reduce", [&]() {
+    return spicey_launch_tmc_reduce(device, A, scalars, valid, lo, hi, probs, d_x, d_stat, d_sample, d_work, (hipStream_t)stream);
+  });
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

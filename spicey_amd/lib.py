@@ -113,6 +113,12 @@ SIGNATURES = {
     "spicey_ac_run_mc": (_i32, [_vp, _i64, _f64p, _f64p, _vp, _f64p, _f64p, _f64p, _f64p, _f64p, _i32, _f64p, _i64p, _f64p]),
     "spicey_ac_last_mc_ms": (_f64, [_vp]),
     "spicey_ac_last_mc_draw_ms": (_f64, [_vp]),
+    "spicey_tran_mc_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32, _i32]),
+    "spicey_tran_mc_draw_device": (_i32, [_i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _f64p, _f64p, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "spicey_tran_mc_reduce_device": (_i32, [_i32, _i32, _vp, _vp, _i32, _vp, _f64p, _f64p, _f64p, _i32, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "spicey_run_mc": (_i32, [_vp, _i64, _f64, _f64p, _i32, _vp, _vp, _f64p, _f64p, _vp, _i32, _f64p, _f64p, _f64p, _i32, _f64p, _i64p, _f64p, _i32p]),
+    "spicey_last_tran_mc_ms": (_f64, [_vp]),
+    "spicey_last_tran_mc_draw_ms": (_f64, [_vp]),
 }
 EXPORTS = list(SIGNATURES)
 
@@ -289,6 +295,52 @@ def ac_mc_reduce_device(n_inst: int, n_freq: int, d_v: int, n_v: int, valid, lo,
                                       C.byref(req) if req is not None else None, d_sample or None, d_freq or None, d_work or None, work_bytes, stream or None)
     if rc != abi.OK:
         _fail("spicey_ac_mc_reduce_device", rc, L.spicey_last_error(None))
+
+
+def tran_mc_workspace_bytes(n_inst: int, n_scalar: int, nE: int, log2K: int, n_prob: int) -> int:
+    return load().spicey_tran_mc_workspace_bytes(n_inst, n_scalar, nE, log2K, n_prob)
+
+
+def tran_mc_draw_device(n_inst: int, nR: int, nC: int, nL: int, d_R: int, d_C: int, d_L: int, tol, icdf, req: abi.SpiceyTranMcReq, d_R_out: int, d_C_out: int,
+                        d_L_out: int, d_work: int, work_bytes: int, device: int = 0, stream: int = 0) -> None:
+    """spicey_tran_mc_draw_device: ac_mc_draw_device's draw with the resistors left in ohms, as a transient run reads them."""
+    L = load()
+    t, tab = _host(tol, np.float64), _host(icdf, np.float64)
+    rc = L.spicey_tran_mc_draw_device(device, n_inst, nR, nC, nL, d_R or None, d_C or None, d_L or None, _p(t, C.c_double), _p(tab, C.c_double),
+                                      C.byref(req) if req is not None else None, d_R_out or None, d_C_out or None, d_L_out or None, d_work or None, work_bytes,
+                                      stream or None)
+    if rc != abi.OK:
+        _fail("spicey_tran_mc_draw_device", rc, L.spicey_last_error(None))
+
+
+def _mc_rows(rows):
+    """(abi.SpiceyMcRows * 3) of rows = [(device pointer, n_rows, stride)] for measure, timing, power."""
+    arr = (abi.SpiceyMcRows * 3)()
+    for k, (ptr, n_rows, stride) in enumerate(rows):
+        arr[k].d_rows, arr[k].n_rows, arr[k].stride = ptr or None, int(n_rows), int(stride)
+    return arr
+
+
+def _scalars(scalars) -> np.ndarray:
+    return np.ascontiguousarray(scalars, dtype=abi.MC_SCALAR_DTYPE).reshape(-1)
+
+
+def tran_mc_reduce_device(n_inst: int, rows, scalars, valid, lo, hi, probs, d_x: int, d_stat: int, d_sample: int, d_work: int, work_bytes: int,
+                          device: int = 0, stream: int = 0, n_scalar: Optional[int] = None) -> None:
+    """spicey_tran_mc_reduce_device: the scalars and the reduction across instances alone on raw device pointers.  rows: three
+    (device pointer, n_rows, stride) for the measure, timing and power rows (None stands for a null list); scalars: records of
+    abi.MC_SCALAR_DTYPE; valid [n_inst] (bytes, None: all), lo / hi [n_scalar] (None: no limit) and probs are HOST arrays; d_x
+    [n_inst][n_scalar], d_stat [n_scalar][8 + 2 n_prob], d_sample [n_inst][2] int64.  Enqueued on `stream`, no synchronisation."""
+    L = load()
+    sc = None if scalars is None else _scalars(scalars)
+    va, lo_, hi_, pr = _host(valid, np.uint8), _host(lo, np.float64), _host(hi, np.float64), _host(probs, np.float64)
+    mr = None if rows is None else _mc_rows(rows)
+    rc = L.spicey_tran_mc_reduce_device(device, n_inst, None if mr is None else C.addressof(mr), sc.ctypes.data if sc is not None and len(sc) else None,
+                                        (len(sc) if sc is not None else 0) if n_scalar is None else n_scalar, va.ctypes.data if va is not None else None,
+                                        _p(lo_, C.c_double), _p(hi_, C.c_double), _p(pr, C.c_double) if pr is not None and len(pr) else None,
+                                        len(pr) if pr is not None else 0, d_x or None, d_stat or None, d_sample or None, d_work or None, work_bytes, stream or None)
+    if rc != abi.OK:
+        _fail("spicey_tran_mc_reduce_device", rc, L.spicey_last_error(None))
 
 
 def fourier_row_doubles(reqs) -> int:
@@ -585,6 +637,44 @@ class Handle:
                                  ("timing_ms", self.L.spicey_last_timing_ms), ("spectrum_ms", self.L.spicey_last_spectrum_ms),
                                  ("power_ms", self.L.spicey_last_power_ms), ("values_ms", self.L.spicey_last_values_ms)):
                 res[key] = last_ms(self.h)
+        return self._dress(res, rc, kept, kept)
+
+    def run_mc(self, steps: int, dt: float, src: np.ndarray, req: abi.SpiceyTranMcReq, tol, icdf, scalars, lo=None, hi=None, probs=(), reqs=(), treqs=(),
+               preqs=(), freqs=(), sreqs=(), vreqs=(), want_x: bool = False, want_iters: bool = False) -> dict:
+        """spicey_run_mc: the handle's instances are the samples, its value rows their nominal values; R, C and L are drawn on the
+        device, ONE transient reads them, the measure / timing / power passes of reqs / treqs / preqs run behind it and stay on
+        the device, and `scalars` (records of abi.MC_SCALAR_DTYPE over those rows) are reduced across the samples.  tol [nE]
+        (out_i's column order: R, C, L), icdf [2^log2K + 1], lo / hi [n_scalar] (None: no limit) and probs are host arrays.
+        Returns `stat` [n_scalar][8 + 2 n_prob] and `sample` [n_inst][2] (include/spicey_hip.h), `x` [n_inst][n_scalar] with
+        want_x, `inst_status`, `state`, `mc_ms`, `draw_ms`.  freqs / sreqs / vreqs are there to be refused."""
+        f = self.flat
+        src = np.ascontiguousarray(src, dtype=np.float64)
+        per_inst = _src_layout(src, f, steps)
+        lists = {key: _reqs(r if len(r) else [], dtype) for key, r, dtype in (
+            ("meas", reqs, abi.MEAS_REQ_DTYPE), ("four", freqs, abi.FOUR_REQ_DTYPE), ("timing", treqs, abi.TIMING_REQ_DTYPE), ("spec", sreqs, abi.SPEC_REQ_DTYPE),
+            ("power", preqs, abi.POWER_REQ_DTYPE), ("values", vreqs, abi.VAL_REQ_DTYPE))}
+        a = abi.SpiceyReducedLists()
+        a.struct_bytes = C.sizeof(a)
+        for key, lst, cnt in (("meas", "reqs", "n_req"), ("four", "freqs", "n_four"), ("timing", "treqs", "n_timing"), ("spec", "sreqs", "n_spec"),
+                              ("power", "preqs", "n_power"), ("values", "vreqs", "n_values")):
+            setattr(a, lst, _reqs_ptr(lists[key]))
+            setattr(a, cnt, len(lists[key]))
+        a.four_stride, a.spec_stride, a.values_stride = fourier_row_doubles(lists["four"]), abi.spec_row_doubles(lists["spec"]), abi.val_row_doubles(lists["values"])
+        sc = _scalars(scalars)
+        t, tab = _host(tol, np.float64), _host(icdf, np.float64)
+        lo_, hi_, pr = _host(lo, np.float64), _host(hi, np.float64), np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
+        stat = np.zeros((len(sc), abi.TRAN_MC_STAT_HEAD + 2 * len(pr)))
+        sample = np.full((f.n_inst, 2), -1, np.int64)
+        x = np.full((f.n_inst, len(sc)), np.nan) if want_x else None
+        iters = np.zeros((f.n_inst, steps + 1), np.int32) if want_iters else None
+        rc = self.L.spicey_run_mc(self.h, steps, dt, _p(src, C.c_double), 1 if per_inst else 0, C.addressof(a), C.addressof(req) if req is not None else None,
+                                  _p(t, C.c_double), _p(tab, C.c_double), sc.ctypes.data if len(sc) else None, len(sc), _p(lo_, C.c_double), _p(hi_, C.c_double),
+                                  _p(pr, C.c_double) if len(pr) else None, len(pr), _p(stat, C.c_double), _p(sample, C.c_int64), _p(x, C.c_double),
+                                  _p(iters, C.c_int32))
+        res = {"status": rc, "detail": self.error() if rc != abi.OK else "", "stat": stat, "sample": sample, "x": x, "iters": iters, "partial": True}
+        kept = rc in (abi.OK, abi.ERR_SINGULAR)
+        if kept:
+            res["mc_ms"], res["draw_ms"] = self.L.spicey_last_tran_mc_ms(self.h), self.L.spicey_last_tran_mc_draw_ms(self.h)
         return self._dress(res, rc, kept, kept)
 
     def run_device(self, steps: int, dt: float, d_src: int, d_out_v: int, d_out_i: int = 0, d_iters: int = 0, stream: int = 0,
@@ -1037,6 +1127,11 @@ class HipBackend(_AcCalls):
     def run_reduced(self, flat: abi.FlatCircuit, steps: int, dt: float, src: np.ndarray, reqs=(), freqs=(), treqs=(), sreqs=(), preqs=(), vreqs=(), pts=(),
                     want_iters: bool = True) -> dict:
         return self._reduced("run_reduced", flat, steps, dt, src, reqs, freqs, treqs, sreqs, preqs, vreqs, pts, want_iters)
+
+    def run_tran_mc(self, flat: abi.FlatCircuit, steps: int, dt: float, src: np.ndarray, req: abi.SpiceyTranMcReq, tol, icdf, scalars, lo=None, hi=None,
+                    probs=(), reqs=(), treqs=(), preqs=(), want_x: bool = False) -> dict:
+        """Handle.run_mc on a handle of its own whose instances are the samples (flat: the nominal circuit replicated)."""
+        return self._on_handle(flat, lambda h: h.run_mc(steps, dt, src, req, tol, icdf, scalars, lo, hi, probs, reqs, treqs, preqs, want_x=want_x))
 
 
 class HipAcExactBackend(_AcCalls):
