@@ -273,6 +273,11 @@ int32_t spicey_top_regs_form(const SpiceyHandle *h, int64_t steps);
  * thread and nothing else, the circuit is not linear, SPICEY_NO_U0_RESIDENT not set when the handle was created); 0 = it
  * takes another kernel, or there is no handle.  The results are the same bits either way. */
 int32_t spicey_u0_resident_form(const SpiceyHandle *h, int64_t steps);
+/* Interpreter 2: 1 = a run of `steps` steps on this handle takes the form of that kernel in which the lanes of the tridiagonal
+ * top run the factor level right below it themselves (spicey_u0_resident_form says 1, that level is row records of the top's
+ * rows and nothing else, SPICEY_NO_TOP_FOLD not set when the handle was created); 0 = it takes another kernel, or there is
+ * no handle.  The results are the same bits either way. */
+int32_t spicey_top_fold_form(const SpiceyHandle *h, int64_t steps);
 /* Human-readable description of the last error ("singular at inst 0 step 3 iter 0", the
  * hipGetErrorString text, …).  Valid until the next call on the handle. NULL handle -> global. */
 const char *spicey_last_error(SpiceyHandle *h);

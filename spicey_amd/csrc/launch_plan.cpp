@@ -47,7 +47,7 @@ static const SpiceyV2Shape &v2_build(int threads, bool packed = false, bool hybr
 SpiceyKnobs spicey_read_knobs() {
   const char *ms = getenv("SPICEY_GROUP_TIMEOUT_MS");
   return {getenv("SPICEY_NO_HYBRID") != nullptr, getenv("SPICEY_FRONT_RIGHT_LOOKING") != nullptr, getenv("SPICEY_TEST_FORCE_GROUP_ABORT") != nullptr,
-          ms ? atoi(ms) : 0, getenv("SPICEY_NO_PHASE_TABLE") != nullptr, getenv("SPICEY_NO_FRESH_FILL") != nullptr, getenv("SPICEY_FRESH_FILL_LINEAR") != nullptr, getenv("SPICEY_NO_EARLY_PREFETCH") != nullptr, getenv("SPICEY_NO_OPERAND_SLOTS") != nullptr, getenv("SPICEY_NO_READY_ARGS") != nullptr, getenv("SPICEY_NO_OPERAND_ADDR") != nullptr, getenv("SPICEY_NO_TOP_REGS") != nullptr, getenv("SPICEY_NO_U0_RESIDENT") != nullptr};
+          ms ? atoi(ms) : 0, getenv("SPICEY_NO_PHASE_TABLE") != nullptr, getenv("SPICEY_NO_FRESH_FILL") != nullptr, getenv("SPICEY_FRESH_FILL_LINEAR") != nullptr, getenv("SPICEY_NO_EARLY_PREFETCH") != nullptr, getenv("SPICEY_NO_OPERAND_SLOTS") != nullptr, getenv("SPICEY_NO_READY_ARGS") != nullptr, getenv("SPICEY_NO_OPERAND_ADDR") != nullptr, getenv("SPICEY_NO_TOP_REGS") != nullptr, getenv("SPICEY_NO_U0_RESIDENT") != nullptr, getenv("SPICEY_NO_TOP_FOLD") != nullptr};
 }
 
 static int pick_threads(const HostProgram &hp, bool v2) {
@@ -302,6 +302,8 @@ int32_t spicey_plan(const SpiceyDesc *desc, const SpiceyOptions &opt, const Spic
     plan.top_regs = spicey_plan_top_regs(plan.addr, hp.hdr.pcr_n, shape, knobs);
     // (the resident level-0 record: level 0 streamed as row records, at most one per thread, and nothing else)
     plan.u0_resident = spicey_plan_u0_resident(plan.top_regs, hp.hdr, hres.st_desc.data(), plan.T, shape, knobs);
+    // (the fold of the last factor level into the top: that level is row records of the top's rows and nothing else)
+    plan.top_fold = spicey_plan_top_fold(plan.u0_resident, hp, hres.tail_n, shape, knobs);
   }
   if (!plan.lds) {
     // group mode: several CUs per instance when the batch leaves CUs idle and the circuit is large enough for the
@@ -356,11 +358,117 @@ bool spicey_plan_u0_resident(bool top_regs, const SpiceyProg &P, const uint32_t 
 }
 bool spicey_u0_resident_run(const LaunchPlan &plan, int64_t steps) { return plan.u0_resident && spicey_top_regs_run(plan, steps); }
 
+bool spicey_top_fold_table(const HostProgram &hp, int tail_n, std::vector<uint32_t> &table) {
+  table.clear();
+  const SpiceyProg &P = hp.hdr;
+  const bool linear = P.nD == 0 && P.nS == 0 && P.nDynEnt == 0;
+  if (!P.has16 || P.hybrid || !P.fresh_fill || linear || P.pcr_n <= 0 || P.pcr_n > 64 || P.pcr_level < 1 || !spicey_slots_fit(P, tail_n)) return false;
+  const int l = P.pcr_level - 1, n = P.pcr_n;
+  if (l >= (int)hp.ph_cnt.size() || hp.ph_cnt[l] == 0u || hp.pcr_tab.size() < (size_t)n * 4) return false;
+  if (((size_t)hp.ph_first[l] + hp.ph_cnt[l]) * 4 > hp.rec16.size()) return false;
+  const uint32_t none = 0xFFFFu, zs = spicey_slot_index(P);
+  // the level's tasks by top row and target: [0] sub-diagonal, [1] diagonal, [2] super-diagonal, [3] right-hand side
+  struct Task { bool have = false, fresh = false; uint32_t cnt = 0, ldu[2][3] = {}; };
+  std::vector<Task> task((size_t)n * 4);
+  for (uint32_t j = 0; j < hp.ph_cnt[l]; j++) {
+    const uint32_t *w = &hp.rec16[((size_t)hp.ph_first[l] + j) * 4];
+    const uint32_t tgt = w[0] & 0xffffu, cnt = (w[0] >> 16) & 0xffu, flags = w[0] >> 24;
+    if (!(flags & SPICEY_R16_VALID) || (flags & (SPICEY_R16_RECIP | SPICEY_R16_K)) || cnt < 1u || cnt > 2u || tgt == none) return false;
+    int at = -1;
+    for (int i = 0; i < n * 4; i++)
+      if (hp.pcr_tab[i] == tgt) { if (at >= 0) return false; at = i; }
+    if (at < 0 || task[at].have) return false;  // (a target outside the top, or a second task on one target)
+    Task &t = task[at];
+    t.have = true; t.fresh = (flags & SPICEY_R16_FRESH) != 0; t.cnt = cnt;
+    t.ldu[0][0] = w[1] & 0xffffu; t.ldu[0][1] = w[1] >> 16; t.ldu[0][2] = w[2] & 0xffffu;
+    t.ldu[1][0] = w[2] >> 16; t.ldu[1][1] = w[3] & 0xffffu; t.ldu[1][2] = w[3] >> 16;
+  }
+  std::vector<uint16_t> rec((size_t)64 * 16, 0);
+  for (int i = 0; i < n; i++) {
+    const uint16_t *tb = &hp.pcr_tab[(size_t)i * 4];
+    const Task &ts = task[(size_t)i * 4], &td = task[(size_t)i * 4 + 1], &tp = task[(size_t)i * 4 + 2], &ty = task[(size_t)i * 4 + 3];
+    uint16_t *r = &rec[(size_t)i * 16];
+    if (tb[0] != none && tb[0] == tb[2]) return false;
+    if (!td.have && !ty.have && !ts.have && !tp.have) {  // the level does not touch this row: its entries as they stand
+      r[0] = tb[1]; r[1] = (uint16_t)(SPICEY_R16_VALID << 8); r[2] = tb[3];
+      r[8] = tb[0] != none ? tb[0] : (uint16_t)zs; r[14] = tb[2] != none ? tb[2] : (uint16_t)zs;
+      continue;
+    }
+    // the diagonal's and the right-hand side's task run over the same pivots in the same order, with the same L_ik and d_k
+    if (!td.have || !ty.have || td.cnt != ty.cnt || ty.fresh) return false;
+    const uint32_t piv = td.cnt;
+    for (uint32_t q = 0; q < piv; q++)
+      if (td.ldu[q][0] != ty.ldu[q][0] || td.ldu[q][1] != ty.ldu[q][1]) return false;
+    if (piv == 2u && td.ldu[0][1] == td.ldu[1][1]) return false;
+    // a fill is one product with the L_ik and d_k of one of those pivots
+    int of[2] = {-1, -1};  // which side (0 sub, 2 super) pivot q's fill targets
+    for (int side : {0, 2}) {
+      const Task &tf = side ? tp : ts;
+      if (!tf.have) continue;
+      if (tf.cnt != 1u) return false;
+      int q = -1;
+      for (uint32_t k = 0; k < piv; k++)
+        if (tf.ldu[0][0] == td.ldu[k][0] && tf.ldu[0][1] == td.ldu[k][1]) q = (int)k;
+      if (q < 0 || of[q] >= 0) return false;
+      of[q] = side;
+    }
+    const bool sup0 = of[0] >= 0 ? of[0] == 2 : (of[1] >= 0 ? of[1] == 0 : false);  // pivot 0's side is the super-diagonal
+    const int side_of[2] = {sup0 ? 2 : 0, sup0 ? 0 : 2};
+    uint32_t meta = piv | ((SPICEY_R16_VALID | SPICEY_R16_FUSED) << 8);
+    r[0] = td.fresh ? (uint16_t)zs : tb[1];
+    if (td.fresh) meta |= SPICEY_ROW_FRESH_AII;
+    r[2] = tb[3];
+    for (uint32_t q = 0; q < 2; q++) {
+      uint16_t *f = r + 3 + 6 * q;  // L_ik, d_k, U_ki, y_k, U_k,o, where the side starts from
+      const Task &tf = side_of[q] ? tp : ts;
+      const uint32_t nb = tb[side_of[q]];
+      if (q < piv) { f[0] = (uint16_t)td.ldu[q][0]; f[1] = (uint16_t)td.ldu[q][1]; f[2] = (uint16_t)td.ldu[q][2]; f[3] = (uint16_t)ty.ldu[q][2]; }
+      if (q < piv && of[q] >= 0) {
+        f[4] = (uint16_t)tf.ldu[0][2];
+        f[5] = tf.fresh ? (uint16_t)zs : (uint16_t)nb;
+        meta |= 1u << (4 + q);
+        if (tf.fresh) meta |= q == 0 ? SPICEY_ROW_FRESH_O0 : SPICEY_ROW_FRESH_O1;
+      } else {
+        f[5] = nb != none ? (uint16_t)nb : (uint16_t)zs;
+      }
+    }
+    r[1] = (uint16_t)meta;
+    r[15] = sup0 ? 1u : 0u;
+  }
+  // nothing behind the top reads what the fold keeps out of W
+  std::vector<char> kept((size_t)P.nW + 1, 0);
+  for (int i = 0; i < n; i++)
+    for (int q = 0; q < 3; q++)
+      if (hp.pcr_tab[(size_t)i * 4 + q] != none && hp.pcr_tab[(size_t)i * 4 + q] < (uint32_t)P.nW) kept[hp.pcr_tab[(size_t)i * 4 + q]] = 1;
+  auto reads = [&](uint32_t idx) { return idx < kept.size() && kept[idx]; };
+  for (int p = P.nLevels; p < 2 * P.nLevels && p < (int)hp.ph_cnt.size(); p++)
+    for (uint32_t j = 0; j < hp.ph_cnt[p]; j++) {
+      const uint32_t *w = &hp.rec16[((size_t)hp.ph_first[p] + j) * 4];
+      const uint32_t cnt = (w[0] >> 16) & 0xffu;
+      if (reads(w[1] & 0xffffu)) return false;
+      if (cnt <= 2) {
+        if ((cnt >= 1 && reads(w[1] >> 16)) || (cnt == 2 && reads(w[2] >> 16))) return false;
+      } else {
+        for (uint32_t k = 0; k < cnt; k++)
+          if ((size_t)w[3] + 2 * k >= hp.ovf16.size() || reads(hp.ovf16[(size_t)w[3] + 2 * k])) return false;
+      }
+    }
+  table.assign(SPICEY_TOP_FOLD_WORDS, 0u);
+  memcpy(table.data(), rec.data(), (size_t)64 * 32);
+  return true;
+}
+bool spicey_plan_top_fold(bool u0_resident, const HostProgram &hp, int tail_n, int shape, const SpiceyKnobs &knobs) {
+  std::vector<uint32_t> table;
+  return u0_resident && shape >= 0 && shape < SPICEY_V2_NSHAPES && SPICEY_V2_SHAPES[shape].top_fold && !knobs.no_top_fold && hp.hdr.pcr_level >= 2 &&
+         spicey_top_fold_table(hp, tail_n, table);
+}
+bool spicey_top_fold_run(const LaunchPlan &plan, int64_t steps) { return plan.top_fold && spicey_u0_resident_run(plan, steps); }
+
 size_t spicey_zpar_doubles(const LaunchPlan &plan, const HostProgram &hp) {
   if (!plan.early || plan.interp != 2) return 0;
   const int shape = spicey_v2_shape(plan.T, plan.packed, hp.hdr.hybrid != 0, plan.packed && hp.hdr.fresh_fill != 0);
   if (shape < 0) return 0;
-  return (size_t)plan.n_inst * (size_t)SPICEY_V2_SHAPES[shape].nel * (size_t)plan.T * 5;
+  return spicey_zpar_record_doubles(plan.n_inst, SPICEY_V2_SHAPES[shape].nel, plan.T);
 }
 
 void fill_info(const LaunchPlan &plan, const HostProgram &hp, const HostResident &hres, const SpiceyOptions &opt, SpiceyInfo *info) {

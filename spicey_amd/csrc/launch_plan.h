@@ -6,10 +6,12 @@
 
 #include <functional>
 #include <string>
+#include <vector>
 
 #include "../../include/spicey_hip.h"
 #include "program.h"
 #include "symbolic.h"
+#include "tran_pt_layout.h"
 
 #define SPICEY_LDS_MAX 163840  // 160 KiB per CU on MI355X (MI355X_MICROARCH.md "Chip-level parameters")
 
@@ -49,11 +51,12 @@ struct SpiceyV2Shape {
   bool addr = false;   // ... and that form with operand addresses (tran_v2_run.h: OA), taken by a ready-argument run where spicey_addr_fits holds unless SPICEY_NO_OPERAND_ADDR is set
   bool top_regs = false;  // ... and that one with the register-exchange top (tran_v2_run.h: TR), taken by an operand-address run whose top has 1 .. 6 stages unless SPICEY_NO_TOP_REGS is set
   bool u0_resident = false;  // ... and that one with the resident level-0 record (tran_v2_run.h: UR), taken by a register-exchange-top run where spicey_u0_resident_fits holds unless SPICEY_NO_U0_RESIDENT is set
+  bool top_fold = false;  // ... and that one with the last factor level folded into the top (tran_v2_run.h: TF), taken by a resident-record run where spicey_top_fold_table holds unless SPICEY_NO_TOP_FOLD is set
 };
 // `early`: Z's element parameters come from one record per thread (SpiceyRun::zpar) and are fetched, with the next source
 // value, at the tail of the last factor phase.  The fresh packed build has it; the other builds were left as they are.
 // (spicey_launch_tran_v2 instantiates one kernel per entry; each kind in ascending threads)
-constexpr SpiceyV2Shape SPICEY_V2_SHAPES[] = {{true, false, 512, 4, 6, 2, 4},    {true, false, 512, 4, 2, 2, 4, true, true, true, true, true, true, true},
+constexpr SpiceyV2Shape SPICEY_V2_SHAPES[] = {{true, false, 512, 4, 6, 2, 4},    {true, false, 512, 4, 2, 2, 4, true, true, true, true, true, true, true, true},
                                               {false, true, 512, 16, 8, 2, 2},   {false, true, 1024, 4, 4, 1, 4},
                                               {false, false, 256, SPICEY_V2_RMAX256, 12, 4, 1},
                                               {false, false, 512, 16, 8, 2, 2},  {false, false, 1024, 8, 4, 1, 4}};
@@ -83,6 +86,7 @@ struct SpiceyKnobs {
   bool no_operand_addr = false;      // SPICEY_NO_OPERAND_ADDR: a ready-argument run keeps the kernel that addresses its LDS operands as W[field] (the in-library A/B switch)
   bool no_top_regs = false;          // SPICEY_NO_TOP_REGS: an operand-address run keeps the kernel whose tridiagonal top exchanges its rows through LDS (the in-library A/B switch)
   bool no_u0_resident = false;       // SPICEY_NO_U0_RESIDENT: a register-exchange-top run keeps the kernel that fetches level 0's row record in every step (the in-library A/B switch)
+  bool no_top_fold = false;          // SPICEY_NO_TOP_FOLD: a resident-record run keeps the kernel that runs the last factor level as a phase of its own (the in-library A/B switch)
 };
 SpiceyKnobs spicey_read_knobs();
 
@@ -148,6 +152,10 @@ struct LaunchPlan {
   // spicey_u0_resident_fits holds for the program and its resident layout and SPICEY_NO_U0_RESIDENT is not set: every
   // register-exchange-top run of the handle takes it (spicey_u0_resident_run)
   bool u0_resident = false;
+  // ... and a form of that kernel with the last factor level folded into the top (tran_v2_run.h: TF), where the plan says
+  // `u0_resident`, spicey_top_fold_table holds for the program and SPICEY_NO_TOP_FOLD is not set: every resident-record run
+  // of the handle takes it (spicey_top_fold_run)
+  bool top_fold = false;
   bool lds = true;       // workspace in LDS (else global memory)
   size_t lds_bytes = 0;
   int64_t algo_bytes = 0;
@@ -182,7 +190,41 @@ bool spicey_u0_resident_fits(const SpiceyProg &P, const uint32_t *st_desc, int T
 bool spicey_plan_u0_resident(bool top_regs, const SpiceyProg &P, const uint32_t *st_desc, int T, int shape, const SpiceyKnobs &knobs);
 // ... and whether that run takes the resident level-0 record: a register-exchange-top run of a plan that says `u0_resident`
 bool spicey_u0_resident_run(const LaunchPlan &plan, int64_t steps);
+// The fold of the last factor level into the tridiagonal top (tran_v2_run.h: TF): lane i of the top's wave runs the row
+// record of top row i itself and keeps a_ii, y_i and the two fills in registers as the row {a, b, c, d} of the cyclic
+// reduction; the level's phase, its barrier and the round trip of the four values through W are gone.
+// spicey_top_fold_table builds the table the kernel's prologue copies into the top's first (unused) row buffer — 64 records
+// of 8 words, kept behind the parameter record SpiceyRun::zpar (program.h) — and returns false unless ALL of this holds for the program hp (`tail_n`: its resident
+// layout's tail levels):
+//   - a fresh-fill program with a tridiagonal top at pcr_level >= 1 whose operand slots fit (spicey_slots_fit), not linear
+//     (a reused factorisation runs the right-hand-side column of the level alone, which no record of this table does);
+//   - every task of factor level pcr_level - 1 (rec16: the records the level's phase runs) is VALID, has one or two inline
+//     products (no overflow list), forms no reciprocal (SPICEY_R16_RECIP clear: the top judges its own pivots) and targets
+//     the sub-diagonal, diagonal, super-diagonal or right-hand-side entry of a top row (pcr_tab), each target at most once;
+//   - a row that has any task has both its diagonal's and its right-hand side's, over the same pivots — the same L_ik and
+//     d_k in the same order —, and each fill it has is ONE product with the L_ik and d_k of one of those pivots, two fills
+//     with different ones: the row's tasks are then exactly what one row record stands for (program.h: fus16 — where the
+//     program has that encoding of the level, the table's records are its records, tests/top_fold_host);
+//   - no backward record (rec16 / ovf16 of the phases below the top) names a sub-diagonal, diagonal or super-diagonal entry
+//     of a top row as its pivot's diagonal or as a U operand: nothing after the top misses the values that no longer reach
+//     W.  (A backward record's target and x operands are right-hand-side / solution slots, never matrix entries; the top's
+//     own x slots are written as ever.)
+// Beside the resident level-0 record: at pcr_level == 1 the folded level WOULD be level 0, the record's own.  The two never
+// meet — the record needs level 0 streamed (more than T x 4 slots of tasks), the fold at most 64 x 4 tasks on it — and
+// spicey_plan_top_fold does not rely on that: it refuses pcr_level < 2.
+// (No diagnostics phase reads W between the levels here: the packed shapes are never diagnostics builds, spicey_plan.)
+// A table record is the row's row record (program.h: fus16) with its four targets turned into READ operands — nothing of it is written:
+//   [0] a_ii's index, or the +0.0 slot's where the record creates the entry (SPICEY_ROW_FRESH_AII)   [1] meta as in fus16
+//   [2] y_i   [3..8], [9..14] the two pivots as in fus16, but the sixth field = where that pivot's side of the row starts
+//   from: the fill target, the +0.0 slot for a fresh one; without a fill, the neighbour entry of pcr_tab that the other
+//   pivot does not produce (+0.0 slot: no such neighbour)   [15] bit 0: pivot 0's side is the SUPER-diagonal (else the sub-).
+// A top row without a record gets one with no pivot (meta = VALID << 8): its four entries are read as they stand.
+bool spicey_top_fold_table(const HostProgram &hp, int tail_n, std::vector<uint32_t> &table);
+// LaunchPlan::top_fold of a plan whose `u0_resident` is decided, on build `shape`: what spicey_plan decides
+bool spicey_plan_top_fold(bool u0_resident, const HostProgram &hp, int tail_n, int shape, const SpiceyKnobs &knobs);
+// ... and whether that run takes the fold: a resident-record run of a plan that says `top_fold`
+bool spicey_top_fold_run(const LaunchPlan &plan, int64_t steps);
 // doubles of the parameter record SpiceyRun::zpar of a planned handle: five per resident item, NEL x T items per instance
-// (0: the plan runs a build without it)
+// (0: the plan runs a build without it); a plan that says `top_fold` keeps SPICEY_TOP_FOLD_WORDS words of table behind them
 size_t spicey_zpar_doubles(const LaunchPlan &plan, const HostProgram &hp);
 void fill_info(const LaunchPlan &plan, const HostProgram &hp, const HostResident &hres, const SpiceyOptions &opt, SpiceyInfo *info);

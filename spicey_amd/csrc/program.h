@@ -307,5 +307,9 @@ struct SpiceyRun {
   // Z's element parameters as one record per resident item (early-prefetch builds, TranPhases2::zpar_fill): five doubles
   // {1/R, C/dt, Is, 1/(N VT), Is/(N VT)} of item (thread t, j) at ((inst * NEL + j) * T + t) * 5, written by the prologue
   // of every launch, 0.0 where the item does not exist.  Null: no record — the build that reads gstat / D_is / dpar runs.
+  // A run with the last factor level folded into the tridiagonal top (tran_v2_run.h: TF) finds that form's record table —
+  // 64 records of 8 words, launch_plan.h: spicey_top_fold_table — right behind the n_inst x NEL x T x 5 doubles of the record,
+  // in the same allocation (read-only; the prologue copies it into the top's first row buffer).  This struct is a kernel
+  // argument of the one-workgroup and group kernels: a field of its own would move their hidden arguments.
   double *zpar;
 };

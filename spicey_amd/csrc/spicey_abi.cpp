@@ -101,6 +101,7 @@ struct SpiceyHandle {
   int64_t stale_polls = 0;  // group mode: waits that only the read-modify-write poll saw satisfied (spicey_group_stale_polls)
   bool gated = false;     // this handle is counted in its device's group-mode handles (DeviceGate)
   DevBuf<double> d_gstat, d_statv, d_rcoef, d_gW, d_dpar;
+  size_t zpar_doubles = 0;  // doubles allocated in d_zpar: the record, and behind it the table of the folded last factor level where the plan says top_fold
   DevBuf<double> d_zpar;  // early-prefetch builds: Z's parameter record (SpiceyRun::zpar), written by every launch's prologue; else null
   DevBuf<int32_t> d_status; DevBuf<unsigned long long> d_solves, d_prof;
   hipStream_t last_stream = nullptr;
@@ -288,7 +289,15 @@ static int32_t allocate(SpiceyHandle *h, const SpiceyDesc *desc) {
   HIPCHK(h, dev_upload(h->d_statv, ni * P.nLU));
   HIPCHK(h, dev_upload(h->d_rcoef, ni * (size_t)(P.nRhsIdx + 1)));
   HIPCHK(h, dev_upload(h->d_dpar, ni * (size_t)P.nD * 2));
-  if (const size_t nz = spicey_zpar_doubles(pl, h->hp)) HIPCHK(h, dev_upload(h->d_zpar, nz));
+  if (const size_t nz = spicey_zpar_doubles(pl, h->hp)) {
+    // (a plan that folds the last factor level keeps that form's record table behind the record: program.h)
+    std::vector<uint32_t> table;
+    if (pl.top_fold && !spicey_top_fold_table(h->hp, h->hres.tail_n, table)) { h->err = "internal: the plan folds the last factor level, but the program has no table for it"; return SPICEY_ERR_BAD_DESC; }
+    if (pl.top_fold && table.size() != SPICEY_TOP_FOLD_WORDS) { h->err = "internal: the table of the folded last factor level has the wrong size"; return SPICEY_ERR_BAD_DESC; }
+    h->zpar_doubles = nz + table.size() * sizeof(uint32_t) / sizeof(double);
+    HIPCHK(h, dev_upload(h->d_zpar, h->zpar_doubles));
+    if (!table.empty()) HIPCHK(h, hipMemcpy((double *)h->d_zpar + nz, table.data(), table.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+  }
   if (!pl.lds) HIPCHK(h, dev_upload(h->d_gW, (size_t)pl.grid * spicey_gw_doubles_per_wg(P, pl.K)));
   if (pl.G > 1) {
     HIPCHK(h, dev_upload(h->d_gsync, (size_t)pl.grid * SPICEY_GRP_SYNC_WORDS));
@@ -351,6 +360,10 @@ extern "C" int32_t spicey_get_info(SpiceyHandle *h, SpiceyInfo *info) {
 
 // enqueue the kernel of a prepared launch behind its device's admission gate; ev0 / ev1 bracket the kernel alone
 static int32_t enqueue_kernel(SpiceyHandle *h, const SpiceyRun &R, hipStream_t st) {
+  // (the folded kernel reads its table behind the record of R.n_inst instances: only where the allocation holds both)
+  const bool top_fold = h->plan.interp == 2 && spicey_top_fold_run(h->plan, R.steps) && R.n_inst == h->plan.n_inst &&
+                        h->zpar_doubles == spicey_zpar_doubles(h->plan, h->hp) + SPICEY_TOP_FOLD_WORDS * sizeof(uint32_t) / sizeof(double);
+  if (h->plan.interp == 2 && spicey_top_fold_run(h->plan, R.steps) && !top_fold) { h->err = "internal: the plan folds the last factor level, but the table is not behind the parameter record"; return SPICEY_ERR_BAD_DESC; }
   DeviceGate &g = device_gate(h->device);
   std::lock_guard<std::mutex> lk(g.mu);  // (wait, launch and record are one step with respect to other launches)
   const bool group = h->plan.G > 1;
@@ -360,7 +373,7 @@ static int32_t enqueue_kernel(SpiceyHandle *h, const SpiceyRun &R, hipStream_t s
   if (h->plan.interp == 3) {
     HIPCHK(h, spicey_launch_exact(h->d_xprog, h->d_Rstruct, h->plan.grid, h->plan.T, h->plan.lds ? h->plan.lds_bytes : 0, st));
   } else if (h->plan.interp == 2) {
-    HIPCHK(h, spicey_launch_tran_v2(h->dprog, h->dres, h->d_Pstruct, h->d_Qstruct, h->d_Rstruct, h->plan.K, h->plan.grid, h->plan.T, st, h->plan.packed, !h->knobs.no_phase_table, h->d_zpar != nullptr, h->plan.slots, spicey_ready_run(h->plan, R.steps), spicey_addr_run(h->plan, R.steps), spicey_top_regs_run(h->plan, R.steps), spicey_u0_resident_run(h->plan, R.steps)));
+    HIPCHK(h, spicey_launch_tran_v2(h->dprog, h->dres, h->d_Pstruct, h->d_Qstruct, h->d_Rstruct, h->plan.K, h->plan.grid, h->plan.T, st, h->plan.packed, !h->knobs.no_phase_table, h->d_zpar != nullptr, h->plan.slots, spicey_ready_run(h->plan, R.steps), spicey_addr_run(h->plan, R.steps), spicey_top_regs_run(h->plan, R.steps), spicey_u0_resident_run(h->plan, R.steps), top_fold));
   } else if (group) {
     HIPCHK(h, spicey_launch_tran_grp(h->dprog, R, h->plan.K, h->plan.grid, h->plan.T, st));
   } else {
@@ -574,6 +587,7 @@ extern "C" int32_t spicey_sync(SpiceyHandle *h) {
 extern "C" int32_t spicey_group_retries(const SpiceyHandle *h) { return h ? h->group_retries : 0; }
 extern "C" int32_t spicey_top_regs_form(const SpiceyHandle *h, int64_t steps) { return (h && h->plan.interp == 2 && spicey_top_regs_run(h->plan, steps)) ? 1 : 0; }
 extern "C" int32_t spicey_u0_resident_form(const SpiceyHandle *h, int64_t steps) { return (h && h->plan.interp == 2 && spicey_u0_resident_run(h->plan, steps)) ? 1 : 0; }
+extern "C" int32_t spicey_top_fold_form(const SpiceyHandle *h, int64_t steps) { return (h && h->plan.interp == 2 && spicey_top_fold_run(h->plan, steps)) ? 1 : 0; }
 extern "C" int64_t spicey_group_stale_polls(const SpiceyHandle *h) { return h ? h->stale_polls : 0; }
 
 // Per instance of the last run, from the status words {code, inst, step, iter} of its workgroups: workgroup (or group) g

@@ -45,6 +45,13 @@ SPICEY_LAYOUT_FN bool spicey_slots_fit(const SpiceyProg &P, int tail_n) {
 // it (spicey_abi.cpp: enqueue_kernel) and a run outside the condition takes the operand-slot kernel without ready arguments.
 #define SPICEY_READY_MAX_STEPS 0xFFFFFFFEll
 SPICEY_LAYOUT_FN bool spicey_ready_steps_ok(int64_t steps) { return steps >= 0 && steps <= SPICEY_READY_MAX_STEPS; }
+// ---- the parameter record and the fold's table behind it (tran_v2_run.h: EP, TF) ------------------------------------------
+// SpiceyRun::zpar holds five doubles per resident item, NEL x T items per instance; a run that folds the last factor level
+// into the top keeps that form's record table — SPICEY_TOP_FOLD_WORDS 32-bit words: 64 records of 8, the top's first 2 KB row
+// buffer — right behind them in the same allocation.  Host (allocation, upload) and kernel (prologue) both take the record's
+// size from here.
+#define SPICEY_TOP_FOLD_WORDS 512
+SPICEY_LAYOUT_FN size_t spicey_zpar_record_doubles(int n_inst, int nel, int threads) { return (size_t)n_inst * (size_t)nel * (size_t)threads * 5; }
 // ---- operand addresses (operand-address builds, tran_v2_run.h: OA) ---------------------------------------------------------
 // Such a build takes c.W for LDS address 0 (K = 1, LDS workspace, no hybrid layout: the dynamic array is the kernel's only
 // LDS object) and re-encodes the fields of B's resident descriptors — 14 bits each, indices into c.gd / c.u in the

@@ -69,6 +69,81 @@ SPICEY_HD void spicey_pcr_stage(const WgCtx<K> &c, double *buf, const uint16_t *
   }
   if (sing && lane < n && c.valid[0]) { c.flags[1] = 1; c.flags[2] = c.inst[0]; }
 }
+// TF (the fold of the last factor level into the top, a form of the resident-record build): on the packed chains the factor
+// level right below the top is nothing but row records whose targets ARE the top's rows — a_ii, y_i and the two fills toward
+// the neighbouring top rows.  As a phase it wrote the four values into W, met the workgroup at a barrier, and the top's lane
+// read the same four back as {b, d, a, c}.  Here lane i runs row i's record itself, at the head of the top, and keeps the
+// results: no phase, no barrier, no round trip, and nothing of the row reaches W but x.  The record comes from a table the
+// host has built (launch_plan.h: spicey_top_fold_table — its conditions are stated there) and the prologue has copied into
+// the top's first row buffer, which the register-exchange top leaves unused: every target of the program's row record has
+// become a read operand (a created entry reads the +0.0 slot, a side without a fill the entry as it stands), so the 14
+// operands are read unconditionally, in one round trip.  The arithmetic is spicey_exec_row16's, operation for operation:
+// m = -(l d), y = fma(m0, y0, y), a_ii = fma(m0, u0, a_ii), the second pivot under `two`, the fills fma(m, f, t).
+// none_a / none_c: the row has no neighbour on that side (pcr_tab: 0xFFFF); on: the lane holds a row of the top.
+template <int K, bool OA>
+SPICEY_HD void spicey_top_fold_row(const WgCtx<K> &c, const uint32_t *w, bool none_a, bool none_c, bool on, double &a, double &b, double &cc, double &d) {
+  static_assert(K == 1, "the fold is a form of the register-exchange top: one instance per workgroup");
+  typedef SpiceyOperand<OA> Op;
+  const uint32_t meta = w[0] >> 16;
+  const uint32_t iaa = Op::template half<0>(w[0]), iy = Op::template half<0>(w[1]);
+  const uint32_t l0 = Op::template half<1>(w[1]), d0 = Op::template half<0>(w[2]), u0 = Op::template half<1>(w[2]), y0 = Op::template half<0>(w[3]);
+  const uint32_t f0 = Op::template half<1>(w[3]), t0 = Op::template half<0>(w[4]);
+  const uint32_t l1 = Op::template half<1>(w[4]), d1 = Op::template half<0>(w[5]), u1 = Op::template half<1>(w[5]), y1 = Op::template half<0>(w[6]);
+  const uint32_t f1 = Op::template half<1>(w[6]), t1 = Op::template half<0>(w[7]);
+  const bool one = (meta & 3u) != 0u, two = (meta & 3u) == 2u, o0 = (meta >> 4) & 1u, o1 = (meta >> 5) & 1u, side = (w[7] >> 16) & 1u;
+  double aii = Op::template ld<K>(c.W, iaa, 0), yi = Op::template ld<K>(c.W, iy, 0);
+  const double vl0 = Op::template ld<K>(c.W, l0, 0), vd0 = Op::template ld<K>(c.W, d0, 0), vy0 = Op::template ld<K>(c.W, y0, 0), vu0 = Op::template ld<K>(c.W, u0, 0);
+  const double vl1 = Op::template ld<K>(c.W, l1, 0), vd1 = Op::template ld<K>(c.W, d1, 0), vy1 = Op::template ld<K>(c.W, y1, 0), vu1 = Op::template ld<K>(c.W, u1, 0);
+  const double vf0 = Op::template ld<K>(c.W, f0, 0), vt0 = Op::template ld<K>(c.W, t0, 0), vf1 = Op::template ld<K>(c.W, f1, 0), vt1 = Op::template ld<K>(c.W, t1, 0);
+  const double m0 = -(vl0 * vd0), m1 = -(vl1 * vd1);
+  const double ya = fma(m0, vy0, yi), aa = fma(m0, vu0, aii);
+  yi = one ? ya : yi;  // (a row without a record: its entries as they stand)
+  aii = one ? aa : aii;
+  const double y2 = fma(m1, vy1, yi), a2 = fma(m1, vu1, aii);
+  yi = two ? y2 : yi;
+  aii = two ? a2 : aii;
+  const double g0 = fma(m0, vf0, vt0), g1 = fma(m1, vf1, vt1);
+  const double e0 = (one && o0) ? g0 : vt0, e1 = (two && o1) ? g1 : vt1;
+  const double sub = side ? e1 : e0, sup = side ? e0 : e1;
+  a = (on && !none_a) ? sub : 0.0;
+  b = on ? aii : 1.0;  // rows past the end: identity
+  cc = (on && !none_c) ? sup : 0.0;
+  d = on ? yi : 0.0;
+}
+// The folded top of one wave as the host runs it: "record, then the stages" with the lane exchange of spicey_pcr_all_regs
+// as array indexing — the same operations in the same order, the same clamped neighbours, the pivots judged by their
+// running minimum.  `rec`: the 64 records of the table, `tab`: the top's index table.  Writes x and nothing else.
+template <int K>
+SPICEY_HD void spicey_top_fold_wave(const WgCtx<K> &c, const uint32_t *rec, const uint16_t *tab, int n, int S) {
+  double a[64], b[64], cc[64], d[64], r[64], pmin[64];
+  for (int lane = 0; lane < 64; lane++) {
+    const bool on = lane < n;
+    const uint16_t *t = tab + (on ? lane : 0) * 4;
+    spicey_top_fold_row<K, false>(c, rec + (size_t)lane * 8, t[0] == 0xFFFFu, t[2] == 0xFFFFu, on, a[lane], b[lane], cc[lane], d[lane]);
+    pmin[lane] = fabs(b[lane]);
+    r[lane] = spicey_rcp(b[lane]);
+  }
+  for (int st = 1; st <= S; st++) {
+    const int h = 1 << (st - 1);
+    double na[64], nb[64], nc[64], nd[64], nr[64];
+    for (int lane = 0; lane < 64; lane++) {
+      const int jm = lane - h < 0 ? 0 : lane - h, jp = lane + h > 63 ? 63 : lane + h;
+      const double al = -a[lane] * r[jm], ga = -cc[lane] * r[jp];
+      na[lane] = st < S ? al * a[jm] : 0.0;  // (dead in the last stage)
+      nc[lane] = st < S ? ga * cc[jp] : 0.0;
+      nb[lane] = fma(ga, a[jp], fma(al, cc[jm], b[lane]));
+      nd[lane] = fma(ga, d[jp], fma(al, d[jm], d[lane]));
+      pmin[lane] = fmin(pmin[lane], fabs(nb[lane]));
+      nr[lane] = spicey_rcp(nb[lane]);
+    }
+    for (int lane = 0; lane < 64; lane++) {
+      if (st < S) { a[lane] = na[lane]; b[lane] = nb[lane]; cc[lane] = nc[lane]; d[lane] = nd[lane]; r[lane] = nr[lane]; }
+      else if (lane < n) c.W[(size_t)tab[lane * 4 + 3] * K] = nd[lane] * nr[lane];
+    }
+  }
+  for (int lane = 0; lane < n && lane < 64; lane++)
+    if (pmin[lane] < SPICEY_EPS && c.valid[0]) { c.flags[1] = 1; c.flags[2] = c.inst[0]; }
+}
 #if defined(__HIP_DEVICE_COMPILE__)
 // All stages in one call for the GPU (the same arithmetic as spicey_pcr_stage, stage after stage): the stage loop is
 // unrolled — strides, buffer halves and the last-stage test are constants —, the pivots are judged once at the end by
@@ -122,7 +197,10 @@ static __device__ __forceinline__ double spicey_lane_f64(int byte_lane, double v
   const int hi = __builtin_amdgcn_ds_bpermute(byte_lane, __double2hiint(v));
   return __hiloint2double(hi, lo);
 }
-template <int K>
+// TF (above): the head runs the lane's fold record — read together with the index entry, which still says where x goes and
+// which neighbours exist — instead of gathering the row from W; and the last stage, whose na and nc are dead, issues no
+// exchange for them (the compiler does not sink the four ds_bpermute into the branch by itself).
+template <int K, bool TF = false>
 __device__ __forceinline__ void spicey_pcr_all_regs(const WgCtx<K> &c, const uint16_t *tab, int n, int S, int lane) {
   static_assert(K == 1, "the register-exchange top is a form of the operand-address build");
   typedef SpiceyOperand<true> Op;
@@ -130,12 +208,19 @@ __device__ __forceinline__ void spicey_pcr_all_regs(const WgCtx<K> &c, const uin
   const uint2 t = *(const uint2 *)(tab + (on ? lane : 0) * 4);  // {ia | ib << 16, ic | id << 16}: 8-byte aligned
   const uint32_t none = Op::index(0xFFFFu);
   const uint32_t ha = Op::template half<0>(t.x), hb = Op::template half<1>(t.x), hc = Op::template half<0>(t.y), hd = Op::template half<1>(t.y);
-  const double va = Op::template ld<K>(c.W, ha == none ? hb : ha, 0), vb = Op::template ld<K>(c.W, hb, 0), vc = Op::template ld<K>(c.W, hc == none ? hb : hc, 0),
-               vd = Op::template ld<K>(c.W, hd, 0);
-  double a = (on && ha != none) ? va : 0.0;
-  double b = on ? vb : 1.0;  // rows past the end: identity
-  double cc = (on && hc != none) ? vc : 0.0;
-  double d = on ? vd : 0.0;
+  double a, b, cc, d;
+  if constexpr (TF) {
+    const uint4 r0 = *(const uint4 *)(c.tail + lane * 8), r1 = *(const uint4 *)(c.tail + lane * 8 + 4);  // (64 records: a lane past n holds zeros)
+    const uint32_t w[8] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w};
+    spicey_top_fold_row<K, true>(c, w, ha == none, hc == none, on, a, b, cc, d);
+  } else {
+    const double va = Op::template ld<K>(c.W, ha == none ? hb : ha, 0), vb = Op::template ld<K>(c.W, hb, 0), vc = Op::template ld<K>(c.W, hc == none ? hb : hc, 0),
+                 vd = Op::template ld<K>(c.W, hd, 0);
+    a = (on && ha != none) ? va : 0.0;
+    b = on ? vb : 1.0;  // rows past the end: identity
+    cc = (on && hc != none) ? vc : 0.0;
+    d = on ? vd : 0.0;
+  }
   double pmin = fabs(b);
   double r = spicey_rcp(b);
 #pragma unroll
@@ -145,7 +230,9 @@ __device__ __forceinline__ void spicey_pcr_all_regs(const WgCtx<K> &c, const uin
     const int jm = max(lane - h, 0) << 2, jp = min(lane + h, 63) << 2;
     // (the operands of the pivot chain first)
     const double rm = spicey_lane_f64(jm, r), cm = spicey_lane_f64(jm, cc), rp = spicey_lane_f64(jp, r), ap = spicey_lane_f64(jp, a);
-    const double dm = spicey_lane_f64(jm, d), dp = spicey_lane_f64(jp, d), am = spicey_lane_f64(jm, a), cp = spicey_lane_f64(jp, cc);
+    const double dm = spicey_lane_f64(jm, d), dp = spicey_lane_f64(jp, d);
+    double am = 0.0, cp = 0.0;
+    if (!TF || st < S) { am = spicey_lane_f64(jm, a); cp = spicey_lane_f64(jp, cc); }  // (wave-uniform: all 64 lanes exchange, or none)
     const double al = -a * rm, ga = -cc * rp;
     const double na = al * am, nc = ga * cp;
     const double nb = fma(ga, ap, fma(al, cm, b));
@@ -206,7 +293,12 @@ struct SpiceyHasIdleWaves<E, decltype((void)E::idle_waves)> { static constexpr b
 // registers (spicey_u0_resident_phase: no table row, no loop, no streamed path) and no factor phase clears them or waits
 // for a fetch.  The caller has made sure that phase 0 is streamed in its row-record encoding, has at most T row records
 // and no generic remainder, and that the run never reuses a factorisation (launch_plan.h: spicey_plan_u0_resident).
-template <int K, int RMAX, int NSV, int NEL, bool HYB = false, int PT = -1, bool EP = false, bool OS = false, bool RA = false, bool OA = false, bool TR = false, bool UR = false, class Exec>
+// TF (the fold of the last factor level into the top, spicey_top_fold_row above; a form of the resident-record build): the
+// prologue copies the record table (behind R.zpar: program.h) into the top's first row buffer, the loop over the factor phases leaves phase pcr_level - 1
+// out — no phase, no barrier; its records stay in their slots and are never dispatched — and the top's head runs the row's
+// record.  The caller has made sure that spicey_top_fold_table holds for the program (launch_plan.h: spicey_plan_top_fold).
+// A host executor runs the whole folded top in one call (spicey_top_fold_wave) where the GPU runs spicey_pcr_all_regs.
+template <int K, int RMAX, int NSV, int NEL, bool HYB = false, int PT = -1, bool EP = false, bool OS = false, bool RA = false, bool OA = false, bool TR = false, bool UR = false, bool TF = false, class Exec>
 SPICEY_HD void spicey_tran_run_v2(Exec &ex, const SpiceyProg &P, const SpiceyResident &Q, const SpiceyRun &R, WgCtx<K> &c, int wg) {
   const int T = ex.threads();
   static_assert(!OS || PT != 0, "the operand slots lie behind the phase table");
@@ -214,6 +306,7 @@ SPICEY_HD void spicey_tran_run_v2(Exec &ex, const SpiceyProg &P, const SpiceyRes
   static_assert(!OA || RA, "the operand addresses are a form of the ready-argument build");
   static_assert(!TR || (OA && K == 1), "the register-exchange top is a form of the operand-address build");
   static_assert(!UR || (TR && !HYB && SpiceyShapeKind<RMAX, NSV, NEL>::fresh), "the resident level-0 record is a form of the register-exchange-top build of the fresh shape");
+  static_assert(!TF || UR, "the fold of the last factor level is a form of the resident-record build");
   typedef TranPhases2<K, RMAX, NSV, NEL, HYB, EP, OS, RA, OA> Ph2;
   uint32_t brem, zrem;
   {
@@ -236,6 +329,10 @@ SPICEY_HD void spicey_tran_run_v2(Exec &ex, const SpiceyProg &P, const SpiceyRes
     if (K == 1 && Pf.pcr_n > 0) {  // tridiagonal top: its index table sits behind the two 2 KB row buffers
       uint16_t *tab = (uint16_t *)(c.tail + 1024);
       for (int i = tid; i < Pf.pcr_n * 4; i += T) tab[i] = Pf.pcr_tab[i];
+      if constexpr (TF) {  // the fold's records: the first row buffer, unused by the register-exchange top
+        const uint32_t *fold = (const uint32_t *)(Rf.zpar + spicey_zpar_record_doubles(Rf.n_inst, NEL, T));  // (behind the parameter record: tran_pt_layout.h)
+        for (int i = tid; i < SPICEY_TOP_FOLD_WORDS; i += T) c.tail[i] = fold[i];
+      }
     }
     for (int i = tid; i < Qf.tail_n * 64; i += T) {  // tail records -> LDS (16 bytes each; no task = all zero)
       const int p = Qf.tail_first + (i >> 6), lane = i & 63;
@@ -353,6 +450,9 @@ SPICEY_HD void spicey_tran_run_v2(Exec &ex, const SpiceyProg &P, const SpiceyRes
       };
       for (int p = 0, u_gen = (z_early && !IDLE) ? u_end - 1 : u_end; p < u_gen; p++) {
         if (p < 64 ? !((active >> p) & 1) : P.ph_cnt[p] == 0) continue;
+        if constexpr (TF) {
+          if (p == u_end - 1) continue;  // (the top's head runs this level)
+        }
         if (HYB && p == 0) {
           // hybrid workspace: phase 0 eliminates the leaves, whose own entries are read from the global array (one L2 round
           // trip for the whole level; every target is in LDS)
@@ -375,7 +475,7 @@ SPICEY_HD void spicey_tran_run_v2(Exec &ex, const SpiceyProg &P, const SpiceyRes
       // tail even where it has no task)
       if (EP && !IDLE && z_early) {
         const int p = u_end - 1;
-        const bool act = p < 64 ? ((active >> p) & 1) != 0 : P.ph_cnt[p] != 0;
+        const bool act = !TF && (p < 64 ? ((active >> p) & 1) != 0 : P.ph_cnt[p] != 0);  // (TF: the top's head runs this level)
         ex.phase(SPICEY_PH_U0 + (p < 30 ? p : 30), [&](int tid) {
           bool u0_done = false;
           if constexpr (UR) {
@@ -395,9 +495,9 @@ SPICEY_HD void spicey_tran_run_v2(Exec &ex, const SpiceyProg &P, const SpiceyRes
           spicey_uk_phase<K, RMAX, NSV, NEL, true, false, OA>(P, Q, SpiceyPt{ptw, pt_on, u_end}, c, ex.template regs<Regs>(lane), lane, T, k_begin, false);
         };
 #if defined(__HIP_DEVICE_COMPILE__)
-        if (pcr_S >= 1 && pcr_S <= 6) {
+        if (TF || (pcr_S >= 1 && pcr_S <= 6)) {  // (TF: a register-exchange-top run, 1 .. 6 stages by its plan)
           auto top_all = [&](int lane, int, double *) {
-            if constexpr (TR) spicey_pcr_all_regs<K>(c, (const uint16_t *)(c.tail + 1024), pcr_n, pcr_S, lane);  // (all 64 lanes: nlanes = 64 below)
+            if constexpr (TR) spicey_pcr_all_regs<K, TF>(c, (const uint16_t *)(c.tail + 1024), pcr_n, pcr_S, lane);  // (all 64 lanes: nlanes = 64 below)
             else spicey_pcr_all<K>(c, (double *)c.tail, (const uint16_t *)(c.tail + 1024), pcr_n, pcr_S, lane);
             if (kmerge) {
               __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -411,6 +511,13 @@ SPICEY_HD void spicey_tran_run_v2(Exec &ex, const SpiceyProg &P, const SpiceyRes
 #endif
         {
           auto top_staged = [&](int lane, int st, double *own) {
+            if constexpr (TF) {  // (host executors only — the whole wave in one call, whichever lane the executor runs first)
+#if !defined(__HIP_DEVICE_COMPILE__)
+              if (st == 0 && lane == 0) spicey_top_fold_wave<K>(c, c.tail, (const uint16_t *)(c.tail + 1024), pcr_n, pcr_S);
+#endif
+              if (st > pcr_S) merged_k(lane);
+              return;
+            }
             if (st <= pcr_S) spicey_pcr_stage<K>(c, (double *)c.tail, (const uint16_t *)(c.tail + 1024), pcr_n, pcr_S, lane, st, own);
             else merged_k(lane);
           };

@@ -42,6 +42,7 @@ SIGNATURES = {
     "spicey_get_info": (_i32, [_vp, _infop]),
     "spicey_top_regs_form": (_i32, [_vp, _i64]),
     "spicey_u0_resident_form": (_i32, [_vp, _i64]),
+    "spicey_top_fold_form": (_i32, [_vp, _i64]),
     "spicey_last_error": (_str, [_vp]),
     "spicey_destroy": (None, [_vp]),
     "spicey_version": (_str, []),
@@ -479,6 +480,10 @@ class Handle:
     def u0_resident_form(self, steps: int) -> bool:
         """Whether a run of `steps` steps takes the kernel that keeps level 0's row record in registers (spicey_u0_resident_form)."""
         return bool(self.L.spicey_u0_resident_form(self.h, steps))
+
+    def top_fold_form(self, steps: int) -> bool:
+        """Whether a run of `steps` steps takes the kernel whose top runs the last factor level itself (spicey_top_fold_form)."""
+        return bool(self.L.spicey_top_fold_form(self.h, steps))
 
     def error(self) -> str:
         m = self.L.spicey_last_error(self.h)
