@@ -1094,6 +1094,83 @@ double spicey_last_tran_mc_ms(SpiceyHandle *h);
 double spicey_last_tran_mc_draw_ms(SpiceyHandle *h);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Sensitivities and corners of transient measurements: a deterministic design in the place of the Monte Carlo draw.  The
+ * n_inst instances of ONE transient are the variants of one topology; the passes of spicey_run_reduced measure them, the scalar
+ * programs above turn the rows into x [n_inst][n_scalar], and a reduction ACROSS the instances forms central differences.
+ * Fixed operation order (tran_sens_exec.h), no FMA contraction, no atomics: the CPU and the device agree on every bit.
+ *
+ * The design writes v' = v g (one product; resistors in ohms) for every element e of the nE = nR + nC + nL, order R, C, L:
+ *   SPICEY_TS_ONE_AT_A_TIME   act [nA] strictly ascending element indices, step [nA] finite in (0, 1); n_inst = 1 + 2 nA.
+ *                             Instance 0 is nominal; instance 1 + 2a has element act[a] at g = 1.0 + step[a], instance 2 + 2a
+ *                             has it at g = 1.0 - step[a]; every other g is 1.0.
+ *   SPICEY_TS_LEVELS          lvl [n_inst][nE] int8 in {-1, 0, +1}, tol [nE] finite in [0, 1): g = 1.0 + (double)lvl tol[e].
+ *
+ * The reduction, one wave per scalar j, lane l the elements a = l, l + 64, ...; with x0 = x[0][j], xp = x[1 + 2a][j],
+ * xm = x[2 + 2a][j], h = step[a], t = tol_act[a] (the tolerance of element act[a]), every operation rounded on its own:
+ *   d = (xp - xm) / (2.0 h)    c = ((xp - x0) + (xm - x0)) / (h h)    sign = +1 if d > 0, -1 if d < 0, else 0
+ * An element is a number iff its three instances are valid, none of x0, xp, xm is NaN and neither d nor c is NaN; otherwise
+ * d = c = 0x7ff8000000000000 and sign = 0.
+ *   d_sens  [n_scalar][nA][2]   {d, c}
+ *   d_sign  [n_scalar][nA]      int8
+ *   d_bound [n_scalar][8]       {x0, wc, rss2, n_num, a_max, contrib_max, n_interior, 0}: wc = sum |d| t and
+ *                               rss2 = sum (d t) (d t) over the numbers, lane l adding its elements in ascending a from +0.0
+ *                               and the partials meeting by s[l] += s[l + stride], stride 32 .. 1; n_num the numbers;
+ *                               a_max the lowest a with the largest |d| t (-1 without a number) and contrib_max that
+ *                               product (+0.0 without); n_interior = #{a : |d| < |c| t}, the elements whose fitted parabola
+ *                               has its vertex inside the tolerance interval.  x0 is NaN if instance 0 is invalid.
+ * Counts and indices are doubles.  No square root runs on the device. */
+#define SPICEY_TS_ONE_AT_A_TIME 0
+#define SPICEY_TS_LEVELS 1
+typedef struct SpiceyTranSensReq {
+  int64_t struct_bytes;
+  int32_t mode;              /* SPICEY_TS_ONE_AT_A_TIME or SPICEY_TS_LEVELS */
+  int32_t nA;                /* ONE_AT_A_TIME: the active elements (>= 1); LEVELS: 0 */
+  int64_t reserved[2];       /* 0 */
+} SpiceyTranSensReq;         /* 32 bytes */
+/* Bytes of device workspace that serve spicey_tran_sens_design_device (either mode) and spicey_tran_sens_reduce_device alike;
+ * -1 for arguments no launch accepts (n_inst < 1 or > 16384, n_scalar < 1, nE < 1, nA < 0). */
+int64_t spicey_tran_sens_workspace_bytes(int32_t n_inst, int32_t n_scalar, int32_t nE, int32_t nA);
+/* The design alone on any DEVICE buffers ([n_inst][n<kind>] each); req, act, step (ONE_AT_A_TIME) or lvl, tol (LEVELS) are HOST
+ * data.  Needs no handle; enqueued on `stream` without synchronising.  Refusals are SPICEY_ERR_BAD_DESC with a text starting
+ * "tran sens: " in spicey_last_error(NULL), nothing launched: a null request, struct_bytes, a nonzero reserved word, an unknown
+ * mode; n_inst < 1 or > 16384; negative counts or no element; ONE_AT_A_TIME with nA < 1, n_inst != 1 + 2 nA, act not strictly
+ * ascending or outside [0, nE), a step that is not finite or outside (0, 1); LEVELS with nA != 0, a tolerance that is negative,
+ * >= 1 or not finite, a level outside {-1, 0, 1}; a null buffer; a workspace that is too small. */
+int32_t spicey_tran_sens_design_device(int32_t device, int32_t n_inst, int32_t nR, int32_t nC, int32_t nL, const double *d_R, const double *d_C,
+                                       const double *d_L, const SpiceyTranSensReq *req, const int32_t *act, const double *step, const int8_t *lvl,
+                                       const double *tol, double *d_R_out, double *d_C_out, double *d_L_out, void *d_work, int64_t work_bytes, void *stream);
+/* The scalars (the kernel and the judge of spicey_tran_mc_reduce_device) and the reduction alone on any DEVICE row buffers:
+ * rows [3], scalars [n_scalar], valid [n_inst] (bytes, NULL: all), step [nA] and tol_act [nA] are HOST data; d_x
+ * [n_inst][n_scalar], d_sens, d_sign and d_bound as above.  Enqueued on `stream` without synchronising.  SPICEY_ERR_BAD_DESC,
+ * text starting "tran sens: ", nothing launched, for: everything the scalar judge refuses; nA < 1 or n_inst != 1 + 2 nA; a step
+ * outside (0, 1) or not finite; a tolerance negative, >= 1 or not finite; a null buffer; a workspace that is too small. */
+int32_t spicey_tran_sens_reduce_device(int32_t device, int32_t n_inst, const SpiceyMcRows *rows, const SpiceyMcScalar *scalars, int32_t n_scalar,
+                                       const uint8_t *valid, const double *step, const double *tol_act, int32_t nA, double *d_x, double *d_sens,
+                                       int8_t *d_sign, double *d_bound, void *d_work, int64_t work_bytes, void *stream);
+/* A sensitivity run on the handle, whose n_inst = 1 + 2 req->nA instances are the variants and whose value rows are their
+ * nominal values.  Everything is judged first (a refusal — SPICEY_ERR_BAD_DESC, text starting "tran sens: " in
+ * spicey_last_error(h) — runs nothing); the ONE_AT_A_TIME design writes scratch value arrays (the handle's own are never
+ * written); ONE transient, exactly that of spicey_run_reduced, reads them; the passes of `lists` run behind it and their rows
+ * stay on the device (the result pointers of `lists` are ignored); an instance is valid iff its spicey_last_inst_status entry
+ * is 0; the scalars and the reduction run, and sens [n_scalar][nA][2], sign [n_scalar][nA], bound [n_scalar][8], x
+ * [n_inst][n_scalar] (or NULL) and iters (or NULL) come back; the tolerance of active element a is tol[act[a]].  If instance 0
+ * is invalid nothing is reduced and the outputs are untouched.  The fourier, spectrum and values lists are refused.  The return
+ * value, the end state and spicey_last_inst_status are as after spicey_run_reduced of the variants; a later plain run binds the
+ * handle's own arrays and gives the bits it gave before.  act, step, tol [nE] and scalars are HOST arrays. */
+int32_t spicey_run_sens(SpiceyHandle *h, int64_t steps, double dt, const double *src_table, int32_t src_per_inst, const SpiceyReducedLists *lists,
+                        const SpiceyTranSensReq *req, const int32_t *act, const double *step, const double *tol, const SpiceyMcScalar *scalars,
+                        int32_t n_scalar, double *sens, int8_t *sign, double *bound, double *x, int32_t *iters);
+/* The same with the LEVELS design: lvl [n_inst][nE] and tol [nE] are HOST arrays; only x [n_inst][n_scalar] comes back, the
+ * NaN 0x7ff8000000000000 for an invalid instance.  With no valid instance nothing is written. */
+int32_t spicey_run_levels(SpiceyHandle *h, int64_t steps, double dt, const double *src_table, int32_t src_per_inst, const SpiceyReducedLists *lists,
+                          const SpiceyTranSensReq *req, const int8_t *lvl, const double *tol, const SpiceyMcScalar *scalars, int32_t n_scalar,
+                          double *x, int32_t *iters);
+/* Duration in ms of the last spicey_run_sens's / spicey_run_levels's scalars and reduction, and of its design, measured with
+ * HIP events. */
+double spicey_last_tran_sens_ms(SpiceyHandle *h);
+double spicey_last_tran_sens_design_ms(SpiceyHandle *h);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Result formatting fast path (host code, no GPU): the CSV text of
  *   formatTranResult(tran)       /root/reference/lib/formatting/formatTranResult.ts:1-23
  * straight from the typed arrays spicey_run filled.  Every number is Number.prototype.toPrecision(6) exactly as

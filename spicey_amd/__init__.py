@@ -16,7 +16,10 @@ device to every element's first-order sensitivity of magnitude and phase and to 
 simulateMonteCarlo (spicey_amd.mc) draws the samples of a tolerance analysis on the device, sweeps them as the instances of one
 launch and reduces them across the instances to quantile bands, moments and the yield against a spec mask;
 measureMonteCarlo (spicey_amd.tran_mc) does the same for transient runs: the samples are the instances of one transient, and the
-scalars of measureTRAN's measures are reduced across them to quantiles, moments, yields against limits and the worst samples.
+scalars of measureTRAN's measures are reduced across them to quantiles, moments, yields against limits and the worst samples;
+measureSens / measureWorstCase (spicey_amd.tran_sens) perturb one toleranced element at a time, as the instances of one transient,
+reduce the scalars across them to every element's first-order sensitivity and curvature and to worst-case and root-sum-square
+bounds, and run the tolerance corners the signs point to as the instances of a second one.
 """
 from .ac_batch import simulateACBatch  # noqa: F401
 from .ac_measure import measureAC, measureACBatch  # noqa: F401
@@ -24,4 +27,5 @@ from .noise import simulateNoise, simulateNoiseBatch  # noqa: F401
 from .sens import simulateSens, simulateSensBatch  # noqa: F401
 from .mc import mc_values, simulateMonteCarlo  # noqa: F401
 from .tran_mc import measureMonteCarlo  # noqa: F401
+from .tran_sens import design_circuit, measureSens, measureWorstCase  # noqa: F401
 from .measure import deriv, efficiency, find, measureTRAN, measureTRANBatch, power, sample, trace  # noqa: F401

@@ -273,6 +273,20 @@ def tran_mc_req(log2K: int, keep_first: bool = True, seed: int = 0) -> SpiceyTra
     return SpiceyTranMcReq(C.sizeof(SpiceyTranMcReq), int(log2K), int(bool(keep_first)), int(seed) & 0xFFFFFFFFFFFFFFFF, 0)
 
 
+class SpiceyTranSensReq(C.Structure):
+    """The request of a sensitivity or levels run of transient measurements (include/spicey_hip.h)."""
+    _fields_ = [("struct_bytes", C.c_int64), ("mode", C.c_int32), ("nA", C.c_int32), ("reserved", C.c_int64 * 2)]
+
+
+assert C.sizeof(SpiceyTranSensReq) == 32
+TS_ONE_AT_A_TIME, TS_LEVELS = 0, 1
+TRAN_SENS_BOUND_ROW = 8  # doubles of a row of d_bound: x0, wc, rss2, n_num, a_max, contrib_max, n_interior, 0
+
+
+def tran_sens_req(mode: int, nA: int = 0) -> SpiceyTranSensReq:
+    return SpiceyTranSensReq(C.sizeof(SpiceyTranSensReq), int(mode), int(nA))
+
+
 def _i32(a) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.int32)
 

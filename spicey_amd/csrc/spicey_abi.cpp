@@ -35,6 +35,7 @@
 #include "timing.h"
 #include "timing_exec.h"
 #include "tran_mc.h"
+#include "tran_sens.h"
 #include "symbolic.h"
 #include "fronts_exec_consts.h"
 
@@ -107,6 +108,7 @@ struct SpiceyHandle {
   hipStream_t last_stream = nullptr;
   double last_pass_ms[N_PASS] = {};  // the reduction passes of the last spicey_run_measure* (0: the pass did not run)
   double last_tran_mc_ms = 0.0, last_tran_mc_draw_ms = 0.0;  // the last spicey_run_mc: its scalars and reduction, its draw
+  double last_tran_sens_ms = 0.0, last_tran_sens_design_ms = 0.0;  // the last spicey_run_sens / spicey_run_levels: the same, its design
   bool pending = false;
   int64_t last_solves = 0;
   double last_ms = 0.0;
@@ -825,6 +827,14 @@ struct TranMcCall {
   const double *lo, *hi, *probs; int32_t n_prob;
   double *stat; int64_t *sample; double *x;
 };
+// What spicey_run_sens and spicey_run_levels add to a reduced run: the design in front of the transient, which then reads the
+// designed values, and behind the passes the scalars and — spicey_run_sens — the reduction across the instances (tran_sens.hip).
+struct TranSensCall {
+  int32_t mode;  // the design the entry point takes
+  const SpiceyTranSensReq *req; const int32_t *act; const double *step; const int8_t *lvl; const double *tol;
+  const SpiceyMcScalar *scalars; int32_t n_scalar;
+  double *sens; int8_t *sign; double *bound; double *x;
+};
 namespace {
 struct EventPair {  // (a call's own pair of timing events)
   hipEvent_t a = nullptr, b = nullptr;
@@ -836,16 +846,26 @@ struct EventPair {  // (a call's own pair of timing events)
 }  // namespace
 
 // What the entry points share: one transient run into device buffers of this call's own, the reductions on the
-// handle's stream behind it, and only their results and `iters` on the way back.  mc: null, or what spicey_run_mc adds.
+// handle's stream behind it, and only their results and `iters` on the way back.  mc: null, or what spicey_run_mc adds; ts: null,
+// or what spicey_run_sens / spicey_run_levels add (at most one of the two).
 static int32_t run_reduced(SpiceyHandle *h, int64_t steps, double dt, const double *src_table, int32_t src_per_inst, const ReducedLists &a, int32_t *iters,
-                           const TranMcCall *mc = nullptr) {
+                           const TranMcCall *mc = nullptr, const TranSensCall *ts = nullptr) {
   if (!h) return SPICEY_ERR_BAD_DESC;
+  const bool bound = mc || ts;  // the run reads scratch value arrays and its passes' rows stay on the device
   double *const outs[N_PASS] = {a.meas, a.four, a.timing, a.spec, a.power, a.values};
   const int32_t counts[N_PASS] = {a.n_req, a.n_four, a.n_tim, a.n_spec, a.n_power, a.n_values};
   if (mc) {
     h->last_tran_mc_ms = h->last_tran_mc_draw_ms = 0.0;
     const char *what = !mc->stat || !mc->sample ? "tran mc: null buffer"
                        : a.n_four > 0 || a.n_spec > 0 || a.n_values > 0 ? "tran mc: the fourier, spectrum and values lists are not reduced by this call (measure, timing and power are)"
+                       : nullptr;
+    if (what) { forget_last_run(h); h->err = what; return SPICEY_ERR_BAD_DESC; }
+  }
+  if (ts) {
+    h->last_tran_sens_ms = h->last_tran_sens_design_ms = 0.0;
+    const bool levels = ts->mode == SPICEY_TS_LEVELS;
+    const char *what = (levels ? !ts->x : (!ts->sens || !ts->sign || !ts->bound)) ? "tran sens: null buffer"
+                       : a.n_four > 0 || a.n_spec > 0 || a.n_values > 0 ? "tran sens: the fourier, spectrum and values lists are not reduced by this call (measure, timing and power are)"
                        : nullptr;
     if (what) { forget_last_run(h); h->err = what; return SPICEY_ERR_BAD_DESC; }
   }
@@ -858,8 +878,9 @@ static int32_t run_reduced(SpiceyHandle *h, int64_t steps, double dt, const doub
     if (first_on < 0) { forget_last_run(h); h->err = "reduced: every list is empty (at least one count must be > 0)"; return SPICEY_ERR_BAD_DESC; }
     // (a Monte Carlo run leaves the passes' rows on the device: what it brings back is `stat`, and the lists' result pointers
     // are not looked at)
-    if (const int32_t rc0 = check_run_args(h, steps, mc ? mc->stat : outs[first_on], src_table, src_per_inst); rc0 != SPICEY_OK) return rc0;
-    for (int p = 0; p < N_PASS && !mc; p++)
+    double *const some_out = mc ? mc->stat : ts ? (ts->mode == SPICEY_TS_LEVELS ? ts->x : ts->bound) : outs[first_on];
+    if (const int32_t rc0 = check_run_args(h, steps, some_out, src_table, src_per_inst); rc0 != SPICEY_OK) return rc0;
+    for (int p = 0; p < N_PASS && !bound; p++)
       if (counts[p] > 0 && !outs[p]) { h->err = "reduced: a result pointer is null where its count is > 0"; return SPICEY_ERR_BAD_DESC; }
   } else if (const int32_t rc0 = check_run_args(h, steps, outs[a.entry], src_table, src_per_inst); rc0 != SPICEY_OK) return rc0;
   if (a.entry == 1 && (a.n_req < 0 || (a.n_req > 0 && !a.meas))) { h->err = "fourier: n_req must be >= 0, and meas not null when n_req > 0"; return SPICEY_ERR_BAD_DESC; }
@@ -919,6 +940,31 @@ static int32_t run_reduced(SpiceyHandle *h, int64_t steps, double dt, const doub
         !spicey_tmc_reduce_judge(ni, jr, mc->scalars, mc->n_scalar, mc->lo, mc->hi, mc->probs, mc->n_prob, true, red_bytes, mcA, h->err))
       return SPICEY_ERR_BAD_DESC;
     mc_work_bytes = std::max(draw_bytes, red_bytes);
+  }
+  // (the same for a sensitivity or levels run: the design's request and arrays, the programs, the steps and tolerances)
+  SpiceyTsDesignArgs tsD{};
+  SpiceyTmcArgs tsT{};
+  SpiceyTsReduceArgs tsA{};
+  std::vector<double> ts_tol_act;
+  if (ts) {
+    double dummy = 0.0, *some = &dummy;
+    const int32_t nE = P.nR + P.nC + P.nL, nA = ts->req ? ts->req->nA : 0;
+    const SpiceyMcRows jr[SPICEY_TMC_N_PASS] = {{on[PASS_MEASURE] ? some : nullptr, on[PASS_MEASURE] ? a.n_req : 0, 8},
+                                                {on[PASS_TIMING] ? some : nullptr, on[PASS_TIMING] ? a.n_tim : 0, 8},
+                                                {on[PASS_POWER] ? some : nullptr, on[PASS_POWER] ? a.n_power : 0, SPICEY_POWER_ROW}};
+    if (!spicey_ts_design_judge(ni, P.nR, P.nC, P.nL, some, some, some, ts->req, ts->mode, ts->act, ts->step, ts->lvl, ts->tol, some, some, some, true, INT64_MAX, tsD,
+                                h->err))
+      return SPICEY_ERR_BAD_DESC;
+    if (ts->mode == SPICEY_TS_LEVELS) {
+      if (!spicey_ts_scalar_judge(ni, jr, ts->scalars, ts->n_scalar, true, tsT, h->err)) return SPICEY_ERR_BAD_DESC;
+    } else {
+      if (!ts->tol) { h->err = "tran sens: null buffer"; return SPICEY_ERR_BAD_DESC; }
+      if (const char *what = spicey_ts_judge_tol(ts->tol, nE)) { h->err = std::string("tran sens: ") + what; return SPICEY_ERR_BAD_DESC; }
+      ts_tol_act.resize((size_t)nA);
+      for (int32_t k = 0; k < nA; k++) ts_tol_act[(size_t)k] = ts->tol[ts->act[k]];
+      if (!spicey_ts_reduce_judge(ni, jr, ts->scalars, ts->n_scalar, ts->step, ts_tol_act.data(), nA, true, INT64_MAX, tsT, tsA, h->err)) return SPICEY_ERR_BAD_DESC;
+    }
+    mc_work_bytes = spicey_ts_workspace_bytes(ni, ts->n_scalar, nE, nA);
   }
   const auto names_a_current = [](const auto &list) { return std::any_of(list.begin(), list.end(), [](const auto &q) { return q.signal == 1; }); };
   const bool need_i = names_a_current(table) || names_a_current(fplan.table) || names_a_current(tplan.edges) || names_a_current(splan.table) ||
@@ -985,20 +1031,25 @@ static int32_t run_reduced(SpiceyHandle *h, int64_t steps, double dt, const doub
   DevBuf<uint8_t> d_mc_work;
   EventPair ev_draw, ev_red;
   const double *mc_vals[3] = {nullptr, nullptr, nullptr};
-  if (mc) {
+  if (bound) {
     HIPCHK(h, d_sR.alloc(std::max<size_t>(1, (size_t)ni * (size_t)P.nR)));
     HIPCHK(h, d_sC.alloc(std::max<size_t>(1, (size_t)ni * (size_t)P.nC)));
     HIPCHK(h, d_sL.alloc(std::max<size_t>(1, (size_t)ni * (size_t)P.nL)));
     HIPCHK(h, d_mc_work.alloc((size_t)mc_work_bytes));
     HIPCHK(h, ev_draw.create());
     HIPCHK(h, ev_red.create());
-    mcD.R = h->d_R; mcD.C = h->d_C; mcD.L = h->d_L; mcD.oR = d_sR; mcD.oC = d_sC; mcD.oL = d_sL;
     HIPCHK(h, hipEventRecord(ev_draw.a, st));
-    HIPCHK(h, spicey_launch_tmc_draw(h->device, mcD, mc->tol, mc->icdf, d_mc_work, st));
+    if (mc) {
+      mcD.R = h->d_R; mcD.C = h->d_C; mcD.L = h->d_L; mcD.oR = d_sR; mcD.oC = d_sC; mcD.oL = d_sL;
+      HIPCHK(h, spicey_launch_tmc_draw(h->device, mcD, mc->tol, mc->icdf, d_mc_work, st));
+    } else {
+      tsD.R = h->d_R; tsD.C = h->d_C; tsD.L = h->d_L; tsD.oR = d_sR; tsD.oC = d_sC; tsD.oL = d_sL;
+      HIPCHK(h, spicey_launch_ts_design(h->device, tsD, ts->act, ts->step, ts->lvl, ts->tol, d_mc_work, st));
+    }
     HIPCHK(h, hipEventRecord(ev_draw.b, st));
     mc_vals[0] = d_sR; mc_vals[1] = d_sC; mc_vals[2] = d_sL;
   }
-  int32_t rc = run_device_src(h, steps, dt, r.d_src, src_per_inst, r.d_v, r.d_i, r.d_it, st, mc ? mc_vals : nullptr);
+  int32_t rc = run_device_src(h, steps, dt, r.d_src, src_per_inst, r.d_v, r.d_i, r.d_it, st, bound ? mc_vals : nullptr);
   if (rc != SPICEY_OK) return rc;
   const char *failed = "";
   auto reduce = [&]() {
@@ -1053,6 +1104,44 @@ static int32_t run_reduced(SpiceyHandle *h, int64_t steps, double dt, const doub
         h->err = "tran mc: no valid sample";
         rc = SPICEY_ERR_SINGULAR;
       } else h->err += " (tran mc: no valid sample, nothing reduced)";
+    } else if (ts) {
+      StreamTimers::elapsed(ev_draw.a, ev_draw.b, &h->last_tran_sens_design_ms);
+      // an instance is valid iff it finished; a sensitivity needs the nominal instance, a levels run any instance
+      const bool levels = ts->mode == SPICEY_TS_LEVELS;
+      std::vector<int32_t> ist((size_t)ni);
+      std::vector<uint8_t> valid((size_t)ni);
+      spicey_last_inst_status(h, ist.data());
+      int32_t n_valid = 0;
+      for (int32_t s = 0; s < ni; s++) n_valid += valid[(size_t)s] = ist[(size_t)s] == 0;
+      if (levels ? n_valid > 0 : valid[0] != 0) {
+        const int row_pass[SPICEY_TMC_N_PASS] = {PASS_MEASURE, PASS_TIMING, PASS_POWER};
+        for (int p = 0; p < SPICEY_TMC_N_PASS; p++) tsT.rows[p] = tsT.n_rows[p] > 0 ? (const double *)pass[row_pass[p]].d_out : nullptr;
+        const uint8_t *va = n_valid == ni ? nullptr : valid.data();
+        const size_t n_x = (size_t)ni * (size_t)ts->n_scalar, n_el = levels ? 0 : (size_t)ts->n_scalar * (size_t)tsA.nA;
+        DevBuf<double> d_x, d_sens, d_bound;
+        DevBuf<int8_t> d_sign;
+        HIPCHK(h, d_x.alloc(n_x));
+        if (!levels) {
+          HIPCHK(h, d_sens.alloc(2 * n_el));
+          HIPCHK(h, d_sign.alloc(n_el));
+          HIPCHK(h, d_bound.alloc((size_t)ts->n_scalar * SPICEY_TS_BOUND_ROW));
+        }
+        HIPCHK(h, hipEventRecord(ev_red.a, st));
+        if (levels) HIPCHK(h, spicey_launch_tmc_scalars(h->device, tsT, ts->scalars, va, nullptr, nullptr, nullptr, d_x, d_mc_work, st));
+        else HIPCHK(h, spicey_launch_ts_reduce(h->device, tsT, tsA, ts->scalars, va, ts->step, ts_tol_act.data(), d_x, d_sens, d_sign, d_bound, d_mc_work, st));
+        HIPCHK(h, hipEventRecord(ev_red.b, st));
+        if (!levels) {
+          HIPCHK(h, hipMemcpyAsync(ts->sens, d_sens, 2 * n_el * sizeof(double), hipMemcpyDeviceToHost, st));
+          HIPCHK(h, hipMemcpyAsync(ts->sign, d_sign, n_el, hipMemcpyDeviceToHost, st));
+          HIPCHK(h, hipMemcpyAsync(ts->bound, d_bound, (size_t)ts->n_scalar * SPICEY_TS_BOUND_ROW * sizeof(double), hipMemcpyDeviceToHost, st));
+        }
+        if (ts->x) HIPCHK(h, hipMemcpyAsync(ts->x, d_x, n_x * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIPCHK(h, hipStreamSynchronize(st));
+        StreamTimers::elapsed(ev_red.a, ev_red.b, &h->last_tran_sens_ms);
+      } else if (rc == SPICEY_OK) {
+        h->err = levels ? "tran sens: no valid instance" : "tran sens: the nominal instance is not valid";
+        rc = SPICEY_ERR_SINGULAR;
+      } else h->err += levels ? " (tran sens: no valid instance, nothing reduced)" : " (tran sens: the nominal instance is not valid, nothing reduced)";
     } else {
       Roctx range_copy("spicey_run_measure:results");
       for (const Pass &t : pass)
@@ -1081,6 +1170,35 @@ extern "C" int32_t spicey_run_mc(SpiceyHandle *h, int64_t steps, double dt, cons
 
 extern "C" double spicey_last_tran_mc_ms(SpiceyHandle *h) { return h ? h->last_tran_mc_ms : 0.0; }
 extern "C" double spicey_last_tran_mc_draw_ms(SpiceyHandle *h) { return h ? h->last_tran_mc_draw_ms : 0.0; }
+
+// The lists of spicey_run_sens / spicey_run_levels, judged as spicey_run_mc's.
+static int32_t run_tran_sens(SpiceyHandle *h, int64_t steps, double dt, const double *src_table, int32_t src_per_inst, const SpiceyReducedLists *l, int32_t *iters,
+                             const TranSensCall &ts) {
+  if (!h) return SPICEY_ERR_BAD_DESC;
+  const char *what = !l ? "tran sens: lists must not be null"
+                     : l->struct_bytes < (int64_t)sizeof(SpiceyReducedLists) ? "tran sens: lists.struct_bytes is smaller than sizeof(SpiceyReducedLists)"
+                     : l->reserved != 0 ? "tran sens: lists.reserved must be 0" : nullptr;
+  if (what) { forget_last_run(h); h->err = what; return SPICEY_ERR_BAD_DESC; }
+  ReducedLists a{-1, l->reqs, l->n_req, nullptr, l->freqs, l->n_four, nullptr, l->four_stride, l->treqs, l->n_timing, nullptr,
+                 l->sreqs, l->n_spec, nullptr, l->spec_stride, l->preqs, l->n_power, nullptr};
+  a.vreqs = l->vreqs; a.n_values = l->n_values; a.pts = l->pts; a.n_pts = l->n_pts; a.values_stride = l->values_stride;
+  return run_reduced(h, steps, dt, src_table, src_per_inst, a, iters, nullptr, &ts);
+}
+
+extern "C" int32_t spicey_run_sens(SpiceyHandle *h, int64_t steps, double dt, const double *src_table, int32_t src_per_inst, const SpiceyReducedLists *l,
+                                   const SpiceyTranSensReq *req, const int32_t *act, const double *step, const double *tol, const SpiceyMcScalar *scalars,
+                                   int32_t n_scalar, double *sens, int8_t *sign, double *bound, double *x, int32_t *iters) {
+  return run_tran_sens(h, steps, dt, src_table, src_per_inst, l, iters, {SPICEY_TS_ONE_AT_A_TIME, req, act, step, nullptr, tol, scalars, n_scalar, sens, sign, bound, x});
+}
+
+extern "C" int32_t spicey_run_levels(SpiceyHandle *h, int64_t steps, double dt, const double *src_table, int32_t src_per_inst, const SpiceyReducedLists *l,
+                                     const SpiceyTranSensReq *req, const int8_t *lvl, const double *tol, const SpiceyMcScalar *scalars, int32_t n_scalar, double *x,
+                                     int32_t *iters) {
+  return run_tran_sens(h, steps, dt, src_table, src_per_inst, l, iters, {SPICEY_TS_LEVELS, req, nullptr, nullptr, lvl, tol, scalars, n_scalar, nullptr, nullptr, nullptr, x});
+}
+
+extern "C" double spicey_last_tran_sens_ms(SpiceyHandle *h) { return h ? h->last_tran_sens_ms : 0.0; }
+extern "C" double spicey_last_tran_sens_design_ms(SpiceyHandle *h) { return h ? h->last_tran_sens_design_ms : 0.0; }
 
 extern "C" int32_t spicey_run_measure(SpiceyHandle *h, int64_t steps, double dt, const double *src_table, int32_t src_per_inst, const SpiceyMeasReq *reqs,
                                       int32_t n_req, double *meas, int32_t *iters) {
@@ -1313,6 +1431,34 @@ extern "C" int32_t spicey_tran_mc_reduce_device(int32_t device, int32_t n_inst, 
     return SPICEY_ERR_BAD_DESC;
   return launch_on_device(device, "spicey_launch_tmc_reduce", [&]() {
     return spicey_launch_tmc_reduce(device, A, scalars, valid, lo, hi, probs, d_x, d_stat, d_sample, d_work, (hipStream_t)stream);
+  });
+}
+
+// Sensitivities and corners of transient measurements (include/spicey_hip.h): the design and the reduction of tran_sens.hip on any
+// device buffers, no handle.
+extern "C" int64_t spicey_tran_sens_workspace_bytes(int32_t n_inst, int32_t n_scalar, int32_t nE, int32_t nA) {
+  return spicey_ts_workspace_bytes(n_inst, n_scalar, nE, nA);
+}
+
+extern "C" int32_t spicey_tran_sens_design_device(int32_t device, int32_t n_inst, int32_t nR, int32_t nC, int32_t nL, const double *d_R, const double *d_C,
+                                                  const double *d_L, const SpiceyTranSensReq *req, const int32_t *act, const double *step, const int8_t *lvl,
+                                                  const double *tol, double *d_R_out, double *d_C_out, double *d_L_out, void *d_work, int64_t work_bytes,
+                                                  void *stream) {
+  SpiceyTsDesignArgs A;
+  if (!spicey_ts_design_judge(n_inst, nR, nC, nL, d_R, d_C, d_L, req, -1, act, step, lvl, tol, d_R_out, d_C_out, d_L_out, d_work != nullptr, work_bytes, A, g_err))
+    return SPICEY_ERR_BAD_DESC;
+  return launch_on_device(device, "spicey_launch_ts_design", [&]() { return spicey_launch_ts_design(device, A, act, step, lvl, tol, d_work, (hipStream_t)stream); });
+}
+
+extern "C" int32_t spicey_tran_sens_reduce_device(int32_t device, int32_t n_inst, const SpiceyMcRows *rows, const SpiceyMcScalar *scalars, int32_t n_scalar,
+                                                  const uint8_t *valid, const double *step, const double *tol_act, int32_t nA, double *d_x, double *d_sens,
+                                                  int8_t *d_sign, double *d_bound, void *d_work, int64_t work_bytes, void *stream) {
+  SpiceyTmcArgs T;
+  SpiceyTsReduceArgs A;
+  if (!spicey_ts_reduce_judge(n_inst, rows, scalars, n_scalar, step, tol_act, nA, d_x && d_sens && d_sign && d_bound && d_work, work_bytes, T, A, g_err))
+    return SPICEY_ERR_BAD_DESC;
+  return launch_on_device(device, "spicey_launch_ts_reduce", [&]() {
+    return spicey_launch_ts_reduce(device, T, A, scalars, valid, step, tol_act, d_x, d_sens, d_sign, d_bound, d_work, (hipStream_t)stream);
   });
 }
 

@@ -151,6 +151,10 @@ inline void spicey_tmc_head(const SpiceyTmcLayout &l, SpiceyTmcArgs &A, const Sp
 // The draw kernel, enqueued on `st` behind a copy of `A` (HOST, from spicey_tmc_draw_judge), tol (HOST [nE]) and icdf (HOST
 // [K + 1]) into the head of d_work.  The device must be current.  No synchronisation.
 hipError_t spicey_launch_tmc_draw(int device, const SpiceyMcDrawArgs &A, const double *tol, const double *icdf, void *d_work, hipStream_t st);
+// The scalar kernel alone, enqueued on `st` behind a copy of `A` and of the HOST arrays into d_work: d_x [n_inst][n_scalar] (what
+// spicey_launch_tmc_reduce runs first; tran_sens.hip runs it on its own).
+hipError_t spicey_launch_tmc_scalars(int device, const SpiceyTmcArgs &A, const SpiceyMcScalar *scalars, const uint8_t *valid, const double *lo, const double *hi,
+                                     const double *probs, double *d_x, void *d_work, hipStream_t st);
 // The three kernels of the reduction, enqueued on `st` behind a copy of `A` (HOST, from spicey_tmc_reduce_judge) and of the HOST
 // arrays into d_work.  d_x [n_inst][n_scalar], d_stat [n_scalar][8 + 2 n_prob], d_sample [n_inst][2] int64.
 hipError_t spicey_launch_tmc_reduce(int device, const SpiceyTmcArgs &A, const SpiceyMcScalar *scalars, const uint8_t *valid, const double *lo, const double *hi,

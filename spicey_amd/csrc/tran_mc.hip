@@ -109,8 +109,8 @@ hipError_t spicey_launch_tmc_draw(int device, const SpiceyMcDrawArgs &A0, const 
   return hipGetLastError();
 }
 
-hipError_t spicey_launch_tmc_reduce(int device, const SpiceyTmcArgs &A0, const SpiceyMcScalar *scalars, const uint8_t *valid, const double *lo, const double *hi,
-                                    const double *probs, double *d_x, double *d_stat, int64_t *d_sample, void *d_work, hipStream_t st) {
+hipError_t spicey_launch_tmc_scalars(int device, const SpiceyTmcArgs &A0, const SpiceyMcScalar *scalars, const uint8_t *valid, const double *lo, const double *hi,
+                                     const double *probs, double *d_x, void *d_work, hipStream_t st) {
   hipError_t e;
   SpiceyTmcLayout l;
   if (!spicey_tmc_layout(A0.n_inst, A0.n_scalar, A0.n_prob, l)) return hipErrorInvalidValue;
@@ -118,12 +118,19 @@ hipError_t spicey_launch_tmc_reduce(int device, const SpiceyTmcArgs &A0, const S
   std::vector<char> head((size_t)l.total_bytes);
   spicey_tmc_head(l, A, scalars, valid, lo, hi, probs, d_x, head.data(), (char *)d_work);
   if ((e = spicey_upload_table_async(device, d_work, head.data(), head.size(), st)) != hipSuccess) return e;
-  const SpiceyTmcArgs *d_A = (const SpiceyTmcArgs *)d_work;
   const int64_t total = (int64_t)A.n_inst * (int64_t)A.n_scalar;
   unsigned grid = 0;
   if ((e = spicey_meas_grid2(total, SPICEY_MC_THREADS, &grid)) != hipSuccess) return e;
-  hipLaunchKernelGGL(spicey_tmc_scalar_kernel, dim3(grid), dim3(SPICEY_MC_THREADS), 0, st, d_A, total);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
+  hipLaunchKernelGGL(spicey_tmc_scalar_kernel, dim3(grid), dim3(SPICEY_MC_THREADS), 0, st, (const SpiceyTmcArgs *)d_work, total);
+  return hipGetLastError();
+}
+
+hipError_t spicey_launch_tmc_reduce(int device, const SpiceyTmcArgs &A, const SpiceyMcScalar *scalars, const uint8_t *valid, const double *lo, const double *hi,
+                                    const double *probs, double *d_x, double *d_stat, int64_t *d_sample, void *d_work, hipStream_t st) {
+  hipError_t e;
+  if ((e = spicey_launch_tmc_scalars(device, A, scalars, valid, lo, hi, probs, d_x, d_work, st)) != hipSuccess) return e;
+  const SpiceyTmcArgs *d_A = (const SpiceyTmcArgs *)d_work;
+  unsigned grid = 0;
   if ((e = spicey_meas_grid2(A.n_inst, SPICEY_MC_THREADS, &grid)) != hipSuccess) return e;
   hipLaunchKernelGGL(spicey_tmc_sample_kernel, dim3(grid), dim3(SPICEY_MC_THREADS), 0, st, d_A, d_sample);
   if ((e = hipGetLastError()) != hipSuccess) return e;

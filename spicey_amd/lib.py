@@ -120,6 +120,13 @@ SIGNATURES = {
     "spicey_run_mc": (_i32, [_vp, _i64, _f64, _f64p, _i32, _vp, _vp, _f64p, _f64p, _vp, _i32, _f64p, _f64p, _f64p, _i32, _f64p, _i64p, _f64p, _i32p]),
     "spicey_last_tran_mc_ms": (_f64, [_vp]),
     "spicey_last_tran_mc_draw_ms": (_f64, [_vp]),
+    "spicey_tran_sens_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32]),
+    "spicey_tran_sens_design_device": (_i32, [_i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "spicey_tran_sens_reduce_device": (_i32, [_i32, _i32, _vp, _vp, _i32, _vp, _f64p, _f64p, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "spicey_run_sens": (_i32, [_vp, _i64, _f64, _f64p, _i32, _vp, _vp, _vp, _f64p, _f64p, _vp, _i32, _f64p, _vp, _f64p, _f64p, _i32p]),
+    "spicey_run_levels": (_i32, [_vp, _i64, _f64, _f64p, _i32, _vp, _vp, _vp, _f64p, _vp, _i32, _f64p, _i32p]),
+    "spicey_last_tran_sens_ms": (_f64, [_vp]),
+    "spicey_last_tran_sens_design_ms": (_f64, [_vp]),
 }
 EXPORTS = list(SIGNATURES)
 
@@ -342,6 +349,43 @@ def tran_mc_reduce_device(n_inst: int, rows, scalars, valid, lo, hi, probs, d_x:
                                         len(pr) if pr is not None else 0, d_x or None, d_stat or None, d_sample or None, d_work or None, work_bytes, stream or None)
     if rc != abi.OK:
         _fail("spicey_tran_mc_reduce_device", rc, L.spicey_last_error(None))
+
+
+def tran_sens_workspace_bytes(n_inst: int, n_scalar: int, nE: int, nA: int) -> int:
+    return load().spicey_tran_sens_workspace_bytes(n_inst, n_scalar, nE, nA)
+
+
+def _data(a):
+    return a.ctypes.data if a is not None and a.size else None
+
+
+def tran_sens_design_device(n_inst: int, nR: int, nC: int, nL: int, d_R: int, d_C: int, d_L: int, req: abi.SpiceyTranSensReq, act, step, lvl, tol, d_R_out: int,
+                            d_C_out: int, d_L_out: int, d_work: int, work_bytes: int, device: int = 0, stream: int = 0) -> None:
+    """spicey_tran_sens_design_device: the deterministic design — ONE_AT_A_TIME from act [nA] (int32) and step [nA], or LEVELS from
+    lvl [n_inst][nE] (int8) and tol [nE], HOST arrays — written into raw device value arrays, the resistors in ohms."""
+    L = load()
+    ac, st, lv, tl = _host(act, np.int32), _host(step, np.float64), _host(lvl, np.int8), _host(tol, np.float64)
+    rc = L.spicey_tran_sens_design_device(device, n_inst, nR, nC, nL, d_R or None, d_C or None, d_L or None, C.addressof(req) if req is not None else None, _data(ac),
+                                          _data(st), _data(lv), _data(tl), d_R_out or None, d_C_out or None, d_L_out or None, d_work or None, work_bytes, stream or None)
+    if rc != abi.OK:
+        _fail("spicey_tran_sens_design_device", rc, L.spicey_last_error(None))
+
+
+def tran_sens_reduce_device(n_inst: int, rows, scalars, valid, step, tol_act, d_x: int, d_sens: int, d_sign: int, d_bound: int, d_work: int, work_bytes: int,
+                            device: int = 0, stream: int = 0, nA: Optional[int] = None) -> None:
+    """spicey_tran_sens_reduce_device: the scalars and the reduction of a one-at-a-time design alone on raw device pointers.  rows,
+    scalars and valid as for tran_mc_reduce_device; step [nA] and tol_act [nA] are HOST arrays; d_x [n_inst][n_scalar], d_sens
+    [n_scalar][nA][2], d_sign [n_scalar][nA] int8, d_bound [n_scalar][8].  Enqueued on `stream`, no synchronisation."""
+    L = load()
+    sc = None if scalars is None else _scalars(scalars)
+    va, st, tl = _host(valid, np.uint8), _host(step, np.float64), _host(tol_act, np.float64)
+    mr = None if rows is None else _mc_rows(rows)
+    rc = L.spicey_tran_sens_reduce_device(device, n_inst, None if mr is None else C.addressof(mr), sc.ctypes.data if sc is not None and len(sc) else None,
+                                          len(sc) if sc is not None else 0, va.ctypes.data if va is not None else None, _p(st, C.c_double), _p(tl, C.c_double),
+                                          (len(st) if st is not None else 0) if nA is None else nA, d_x or None, d_sens or None, d_sign or None, d_bound or None,
+                                          d_work or None, work_bytes, stream or None)
+    if rc != abi.OK:
+        _fail("spicey_tran_sens_reduce_device", rc, L.spicey_last_error(None))
 
 
 def fourier_row_doubles(reqs) -> int:
@@ -680,6 +724,71 @@ class Handle:
         kept = rc in (abi.OK, abi.ERR_SINGULAR)
         if kept:
             res["mc_ms"], res["draw_ms"] = self.L.spicey_last_tran_mc_ms(self.h), self.L.spicey_last_tran_mc_draw_ms(self.h)
+        return self._dress(res, rc, kept, kept)
+
+    def _mc_lists(self, reqs, treqs, preqs, freqs=(), sreqs=(), vreqs=()):
+        """(abi.SpiceyReducedLists without result pointers, the arrays kept alive) as spicey_run_sens / spicey_run_levels take it."""
+        lists = {key: _reqs(r if len(r) else [], dtype) for key, r, dtype in (
+            ("meas", reqs, abi.MEAS_REQ_DTYPE), ("four", freqs, abi.FOUR_REQ_DTYPE), ("timing", treqs, abi.TIMING_REQ_DTYPE), ("spec", sreqs, abi.SPEC_REQ_DTYPE),
+            ("power", preqs, abi.POWER_REQ_DTYPE), ("values", vreqs, abi.VAL_REQ_DTYPE))}
+        a = abi.SpiceyReducedLists()
+        a.struct_bytes = C.sizeof(a)
+        for key, lst, cnt in (("meas", "reqs", "n_req"), ("four", "freqs", "n_four"), ("timing", "treqs", "n_timing"), ("spec", "sreqs", "n_spec"),
+                              ("power", "preqs", "n_power"), ("values", "vreqs", "n_values")):
+            setattr(a, lst, _reqs_ptr(lists[key]))
+            setattr(a, cnt, len(lists[key]))
+        a.four_stride, a.spec_stride, a.values_stride = fourier_row_doubles(lists["four"]), abi.spec_row_doubles(lists["spec"]), abi.val_row_doubles(lists["values"])
+        return a, lists
+
+    def run_sens(self, steps: int, dt: float, src: np.ndarray, req: abi.SpiceyTranSensReq, act, step, tol, scalars, reqs=(), treqs=(), preqs=(), freqs=(), sreqs=(),
+                 vreqs=(), want_x: bool = False, want_iters: bool = False) -> dict:
+        """spicey_run_sens: the handle's n_inst = 1 + 2 nA instances are the nominal circuit and, per active element act[a], the
+        variants with that element at 1 + step[a] and 1 - step[a] times its value; the design is written on the device, ONE
+        transient reads it, the measure / timing / power passes run behind it and stay on the device, and `scalars` are reduced
+        across the instances.  act [nA] (int32), step [nA], tol [nE] (order R, C, L) are host arrays.  Returns `sens`
+        [n_scalar][nA][2] = {d, c}, `sign` [n_scalar][nA] int8, `bound` [n_scalar][8] (include/spicey_hip.h), `x`
+        [n_inst][n_scalar] with want_x, `inst_status`, `state`, `sens_ms`, `design_ms`.  freqs / sreqs / vreqs are there to be refused."""
+        f = self.flat
+        src = np.ascontiguousarray(src, dtype=np.float64)
+        per_inst = _src_layout(src, f, steps)
+        a, keep = self._mc_lists(reqs, treqs, preqs, freqs, sreqs, vreqs)
+        sc = _scalars(scalars)
+        ac, st, tl = _host(act, np.int32), _host(step, np.float64), _host(tol, np.float64)
+        nA = int(req.nA) if req is not None else 0
+        sens = np.full((len(sc), max(nA, 0), 2), np.nan)
+        sign = np.zeros((len(sc), max(nA, 0)), np.int8)
+        bound = np.zeros((len(sc), abi.TRAN_SENS_BOUND_ROW))
+        x = np.full((f.n_inst, len(sc)), np.nan) if want_x else None
+        iters = np.zeros((f.n_inst, steps + 1), np.int32) if want_iters else None
+        rc = self.L.spicey_run_sens(self.h, steps, dt, _p(src, C.c_double), 1 if per_inst else 0, C.addressof(a), C.addressof(req) if req is not None else None,
+                                    _data(ac), _p(st, C.c_double), _p(tl, C.c_double), sc.ctypes.data if len(sc) else None, len(sc), _p(sens, C.c_double),
+                                    sign.ctypes.data, _p(bound, C.c_double), _p(x, C.c_double), _p(iters, C.c_int32))
+        del keep
+        res = {"status": rc, "detail": self.error() if rc != abi.OK else "", "sens": sens, "sign": sign, "bound": bound, "x": x, "iters": iters, "partial": True}
+        kept = rc in (abi.OK, abi.ERR_SINGULAR)
+        if kept:
+            res["sens_ms"], res["design_ms"] = self.L.spicey_last_tran_sens_ms(self.h), self.L.spicey_last_tran_sens_design_ms(self.h)
+        return self._dress(res, rc, kept, kept)
+
+    def run_levels(self, steps: int, dt: float, src: np.ndarray, req: abi.SpiceyTranSensReq, lvl, tol, scalars, reqs=(), treqs=(), preqs=(), freqs=(), sreqs=(),
+                   vreqs=(), want_iters: bool = False) -> dict:
+        """spicey_run_levels: run_sens with the LEVELS design — instance s has element e at 1 + lvl[s][e] tol[e] times its value,
+        lvl [n_inst][nE] int8 in {-1, 0, +1} — and no reduction: returns `x` [n_inst][n_scalar], NaN for an invalid instance."""
+        f = self.flat
+        src = np.ascontiguousarray(src, dtype=np.float64)
+        per_inst = _src_layout(src, f, steps)
+        a, keep = self._mc_lists(reqs, treqs, preqs, freqs, sreqs, vreqs)
+        sc = _scalars(scalars)
+        lv, tl = _host(lvl, np.int8), _host(tol, np.float64)
+        x = np.full((f.n_inst, len(sc)), np.nan)
+        iters = np.zeros((f.n_inst, steps + 1), np.int32) if want_iters else None
+        rc = self.L.spicey_run_levels(self.h, steps, dt, _p(src, C.c_double), 1 if per_inst else 0, C.addressof(a), C.addressof(req) if req is not None else None,
+                                      _data(lv), _p(tl, C.c_double), sc.ctypes.data if len(sc) else None, len(sc), _p(x, C.c_double), _p(iters, C.c_int32))
+        del keep
+        res = {"status": rc, "detail": self.error() if rc != abi.OK else "", "x": x, "iters": iters, "partial": True}
+        kept = rc in (abi.OK, abi.ERR_SINGULAR)
+        if kept:
+            res["sens_ms"], res["design_ms"] = self.L.spicey_last_tran_sens_ms(self.h), self.L.spicey_last_tran_sens_design_ms(self.h)
         return self._dress(res, rc, kept, kept)
 
     def run_device(self, steps: int, dt: float, d_src: int, d_out_v: int, d_out_i: int = 0, d_iters: int = 0, stream: int = 0,
@@ -1137,6 +1246,16 @@ class HipBackend(_AcCalls):
                     probs=(), reqs=(), treqs=(), preqs=(), want_x: bool = False) -> dict:
         """Handle.run_mc on a handle of its own whose instances are the samples (flat: the nominal circuit replicated)."""
         return self._on_handle(flat, lambda h: h.run_mc(steps, dt, src, req, tol, icdf, scalars, lo, hi, probs, reqs, treqs, preqs, want_x=want_x))
+
+    def run_tran_sens(self, flat: abi.FlatCircuit, steps: int, dt: float, src: np.ndarray, req: abi.SpiceyTranSensReq, act, step, tol, scalars, reqs=(), treqs=(),
+                      preqs=(), want_x: bool = False) -> dict:
+        """Handle.run_sens on a handle of its own whose instances are the variants (flat: the nominal circuit replicated 1 + 2 nA times)."""
+        return self._on_handle(flat, lambda h: h.run_sens(steps, dt, src, req, act, step, tol, scalars, reqs, treqs, preqs, want_x=want_x))
+
+    def run_tran_levels(self, flat: abi.FlatCircuit, steps: int, dt: float, src: np.ndarray, req: abi.SpiceyTranSensReq, lvl, tol, scalars, reqs=(), treqs=(),
+                        preqs=()) -> dict:
+        """Handle.run_levels on a handle of its own whose instances are the level rows (flat: the nominal circuit replicated)."""
+        return self._on_handle(flat, lambda h: h.run_levels(steps, dt, src, req, lvl, tol, scalars, reqs, treqs, preqs))
 
 
 class HipAcExactBackend(_AcCalls):
