@@ -278,6 +278,12 @@ int32_t spicey_u0_resident_form(const SpiceyHandle *h, int64_t steps);
  * rows and nothing else, SPICEY_NO_TOP_FOLD not set when the handle was created); 0 = it takes another kernel, or there is
  * no handle.  The results are the same bits either way. */
 int32_t spicey_top_fold_form(const SpiceyHandle *h, int64_t steps);
+/* Interpreter 2: 1 = a run of `steps` steps on this handle takes the form of that kernel whose update phase stamps the next
+ * step's matrix and right-hand side from registers, with no stamping phase in the time loop (spicey_top_fold_form says 1,
+ * every stamped entry and every row draws on values of one thread — no switch, no inductor, nothing beyond the resident
+ * capacity —, SPICEY_NO_STAMP_FUSE not set when the handle was created); 0 = it takes another kernel, or there is no
+ * handle.  The results are the same bits either way. */
+int32_t spicey_stamp_fuse_form(const SpiceyHandle *h, int64_t steps);
 /* Human-readable description of the last error ("singular at inst 0 step 3 iter 0", the
  * hipGetErrorString text, …).  Valid until the next call on the handle. NULL handle -> global. */
 const char *spicey_last_error(SpiceyHandle *h);

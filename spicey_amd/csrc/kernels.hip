@@ -540,6 +540,8 @@ struct GpuExecV2 {
 #define SPICEY_KERNEL_UR 64
 // PT, bit 7 (SPICEY_KERNEL_TF): the last factor level folded into the top of a resident-record kernel (tran_v2_run.h: TF)
 #define SPICEY_KERNEL_TF 128
+// PT, bit 8 (SPICEY_KERNEL_SF): the stamp fuse of a folded kernel — Z stamps the next step, no phase B in the time loop (tran_v2_run.h: SF)
+#define SPICEY_KERNEL_SF 256
 template <int K, int RMAX, int NSV, int NEL, int MAXT, int MINW, bool HYB = false, int PT = 0>
 __global__ void __launch_bounds__(MAXT, MINW) spicey_tran_kernel_v2(const SpiceyProg *__restrict__ Pg, const SpiceyResident *__restrict__ Qg,
                                                                     const SpiceyRun *__restrict__ Rg) {
@@ -589,7 +591,7 @@ __global__ void __launch_bounds__(MAXT, MINW) spicey_tran_kernel_v2(const Spicey
     // start stamps wait in their own slots (not in registers: nothing may stay live around the whole run)
     if (threadIdx.x == 0) { lprof[5] = (unsigned long long)clock64(); lprof[6] = (unsigned long long)wall_clock64(); }
   }
-  spicey_tran_run_v2<K, RMAX, NSV, NEL, HYB, PT & 1, (PT & SPICEY_KERNEL_EP) != 0, (PT & SPICEY_KERNEL_OS) != 0, (PT & SPICEY_KERNEL_RA) != 0, (PT & SPICEY_KERNEL_OA) != 0, (PT & SPICEY_KERNEL_TR) != 0, (PT & SPICEY_KERNEL_UR) != 0, (PT & SPICEY_KERNEL_TF) != 0>(ex, P, Q, R, c, wg);
+  spicey_tran_run_v2<K, RMAX, NSV, NEL, HYB, PT & 1, (PT & SPICEY_KERNEL_EP) != 0, (PT & SPICEY_KERNEL_OS) != 0, (PT & SPICEY_KERNEL_RA) != 0, (PT & SPICEY_KERNEL_OA) != 0, (PT & SPICEY_KERNEL_TR) != 0, (PT & SPICEY_KERNEL_UR) != 0, (PT & SPICEY_KERNEL_TF) != 0, (PT & SPICEY_KERNEL_SF) != 0>(ex, P, Q, R, c, wg);
   if constexpr ((PT & SPICEY_KERNEL_OA) != 0) {
     static_assert(K == 1 && !HYB, "operand addresses: one instance per workgroup on the LDS workspace");
     // The one condition of SpiceyOperand that the source does not show: `smem` at LDS address 0.  Tested here, behind the run
@@ -608,9 +610,9 @@ __global__ void __launch_bounds__(MAXT, MINW) spicey_tran_kernel_v2(const Spicey
   }
 }
 
-template <int K, int RMAX, int NSV, int NEL, int MAXT, int MINW, bool HYB = false, int PT = 0, bool EP = false, bool OS = false, bool RA = false, bool OA = false, bool TR = false, bool UR = false, bool TF = false>
+template <int K, int RMAX, int NSV, int NEL, int MAXT, int MINW, bool HYB = false, int PT = 0, bool EP = false, bool OS = false, bool RA = false, bool OA = false, bool TR = false, bool UR = false, bool TF = false, bool SF = false>
 hipError_t launch_v2_t(const SpiceyProg *P, const SpiceyResident *Q, const SpiceyRun *R, int grid, int threads, size_t lds, hipStream_t st) {
-  auto kern = spicey_tran_kernel_v2<K, RMAX, NSV, NEL, MAXT, MINW, HYB, PT | (EP ? SPICEY_KERNEL_EP : 0) | (OS ? SPICEY_KERNEL_OS : 0) | (RA ? SPICEY_KERNEL_RA : 0) | (OA ? SPICEY_KERNEL_OA : 0) | (TR ? SPICEY_KERNEL_TR : 0) | (UR ? SPICEY_KERNEL_UR : 0) | (TF ? SPICEY_KERNEL_TF : 0)>;
+  auto kern = spicey_tran_kernel_v2<K, RMAX, NSV, NEL, MAXT, MINW, HYB, PT | (EP ? SPICEY_KERNEL_EP : 0) | (OS ? SPICEY_KERNEL_OS : 0) | (RA ? SPICEY_KERNEL_RA : 0) | (OA ? SPICEY_KERNEL_OA : 0) | (TR ? SPICEY_KERNEL_TR : 0) | (UR ? SPICEY_KERNEL_UR : 0) | (TF ? SPICEY_KERNEL_TF : 0) | (SF ? SPICEY_KERNEL_SF : 0)>;
   if (const hipError_t e = spicey_allow_dyn_lds(kern, lds); e != hipSuccess) return e;
   hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, st, P, Q, R);
   return hipGetLastError();
@@ -685,7 +687,7 @@ hipError_t spicey_launch_tran(const SpiceyProg &P, const SpiceyRun &R, int K, bo
 }
 
 // one launcher per entry of SPICEY_V2_SHAPES (launch_plan.h)
-template <int I, int PT = 0, bool EP = false, bool OS = false, bool RA = false, bool OA = false, bool TR = false, bool UR = false, bool TF = false>
+template <int I, int PT = 0, bool EP = false, bool OS = false, bool RA = false, bool OA = false, bool TR = false, bool UR = false, bool TF = false, bool SF = false>
 static hipError_t launch_v2_shape(const SpiceyProg *P, const SpiceyResident *Q, const SpiceyRun *R, int grid, int threads, size_t lds, hipStream_t st) {
   constexpr SpiceyV2Shape s = SPICEY_V2_SHAPES[I];
   static_assert(!EP || s.early, "an early-prefetch kernel is built for the shapes that say so");
@@ -695,7 +697,8 @@ static hipError_t launch_v2_shape(const SpiceyProg *P, const SpiceyResident *Q, 
   static_assert(!TR || (s.top_regs && OA), "a register-exchange top is a form of the operand-address kernel, for the shapes that say so");
   static_assert(!UR || (s.u0_resident && TR), "a resident level-0 record is a form of the register-exchange-top kernel, for the shapes that say so");
   static_assert(!TF || (s.top_fold && UR), "a folded last factor level is a form of the resident-record kernel, for the shapes that say so");
-  return launch_v2_t<1, s.rmax, s.nsv, s.nel, s.threads, s.minw, s.hybrid, PT, EP, OS, RA, OA, TR, UR, TF>(P, Q, R, grid, threads, lds, st);
+  static_assert(!SF || (s.stamp_fuse && TF), "a stamp fuse is a form of the folded kernel, for the shapes that say so");
+  return launch_v2_t<1, s.rmax, s.nsv, s.nel, s.threads, s.minw, s.hybrid, PT, EP, OS, RA, OA, TR, UR, TF, SF>(P, Q, R, grid, threads, lds, st);
 }
 static decltype(&launch_v2_shape<0>) const launch_v2_by_shape[] = {launch_v2_shape<0>, launch_v2_shape<1>, launch_v2_shape<2>, launch_v2_shape<3>,
                                                                     launch_v2_shape<4>, launch_v2_shape<5>, launch_v2_shape<6>};
@@ -723,11 +726,14 @@ static decltype(&launch_v2_shape<0>) const launch_v2_u0_resident_by_shape[SPICEY
 
 // ... and that one with the last factor level folded into the top (SpiceyV2Shape::top_fold)
 static decltype(&launch_v2_shape<0>) const launch_v2_top_fold_by_shape[SPICEY_V2_NSHAPES] = {nullptr, launch_v2_shape<1, 1, true, true, true, true, true, true, true>, nullptr, nullptr, nullptr, nullptr, nullptr};
+// ... and that one whose Z stamps the next step (SpiceyV2Shape::stamp_fuse)
+static decltype(&launch_v2_shape<0>) const launch_v2_stamp_fuse_by_shape[SPICEY_V2_NSHAPES] = {nullptr, launch_v2_shape<1, 1, true, true, true, true, true, true, true, true>, nullptr, nullptr, nullptr, nullptr, nullptr};
 
 hipError_t spicey_launch_tran_v2(const SpiceyProg &Ph, const SpiceyResident &Qh, const SpiceyProg *P, const SpiceyResident *Q, const SpiceyRun *R, int K, int grid,
-                                 int threads, hipStream_t st, bool packed, bool phase_table, bool early, bool slots, bool ready, bool addr, bool top_regs, bool u0_resident, bool top_fold) {
+                                 int threads, hipStream_t st, bool packed, bool phase_table, bool early, bool slots, bool ready, bool addr, bool top_regs, bool u0_resident, bool top_fold, bool stamp_fuse) {
   const int shape = K == 1 ? spicey_v2_shape(threads, packed, Ph.hybrid != 0, packed && Ph.fresh_fill != 0) : -1;  // (a fresh-fill program runs on the build that decodes its flags: spicey_plan makes one for the packed geometry only)
   if (shape < 0) return hipErrorInvalidValue;
+  if (stamp_fuse && !(slots && ready && addr && top_regs && u0_resident && top_fold)) return hipErrorInvalidValue;  // (only a folded run has that form)
   // the table sits in the tail area behind the tridiagonal top's index table: only where it fits there (tran_exec.h)
   const bool pt = phase_table && launch_v2_pt_by_shape[shape] != nullptr && spicey_pt_fits(Ph.pcr_n, Ph.pcr_level, Qh.tail_n);
   if (slots) {  // (the plan found room for the operand slots: spicey_slots_fit — checked again, the kernel writes there)
@@ -742,6 +748,10 @@ hipError_t spicey_launch_tran_v2(const SpiceyProg &Ph, const SpiceyResident &Qh,
             if (launch_v2_u0_resident_by_shape[shape] == nullptr) return hipErrorInvalidValue;
             if (top_fold) {  // (the plan found the level below the top to be row records of the top's rows and built the table behind the run's parameter record: spicey_top_fold_table)
               if (launch_v2_top_fold_by_shape[shape] == nullptr) return hipErrorInvalidValue;
+              if (stamp_fuse) {  // (the plan found every sum of phase B to draw on one thread of Z and built the table behind the fold's: spicey_stamp_fuse_table)
+                if (launch_v2_stamp_fuse_by_shape[shape] == nullptr || threads != SPICEY_V2_SHAPES[shape].threads) return hipErrorInvalidValue;
+                return launch_v2_stamp_fuse_by_shape[shape](P, Q, R, grid, threads, spicey_lds_bytes(Ph, K, true, Qh.tail_n), st);
+              }
               return launch_v2_top_fold_by_shape[shape](P, Q, R, grid, threads, spicey_lds_bytes(Ph, K, true, Qh.tail_n), st);
             }
             return launch_v2_u0_resident_by_shape[shape](P, Q, R, grid, threads, spicey_lds_bytes(Ph, K, true, Qh.tail_n), st);

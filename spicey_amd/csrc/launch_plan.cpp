@@ -47,7 +47,7 @@ static const SpiceyV2Shape &v2_build(int threads, bool packed = false, bool hybr
 SpiceyKnobs spicey_read_knobs() {
   const char *ms = getenv("SPICEY_GROUP_TIMEOUT_MS");
   return {getenv("SPICEY_NO_HYBRID") != nullptr, getenv("SPICEY_FRONT_RIGHT_LOOKING") != nullptr, getenv("SPICEY_TEST_FORCE_GROUP_ABORT") != nullptr,
-          ms ? atoi(ms) : 0, getenv("SPICEY_NO_PHASE_TABLE") != nullptr, getenv("SPICEY_NO_FRESH_FILL") != nullptr, getenv("SPICEY_FRESH_FILL_LINEAR") != nullptr, getenv("SPICEY_NO_EARLY_PREFETCH") != nullptr, getenv("SPICEY_NO_OPERAND_SLOTS") != nullptr, getenv("SPICEY_NO_READY_ARGS") != nullptr, getenv("SPICEY_NO_OPERAND_ADDR") != nullptr, getenv("SPICEY_NO_TOP_REGS") != nullptr, getenv("SPICEY_NO_U0_RESIDENT") != nullptr, getenv("SPICEY_NO_TOP_FOLD") != nullptr};
+          ms ? atoi(ms) : 0, getenv("SPICEY_NO_PHASE_TABLE") != nullptr, getenv("SPICEY_NO_FRESH_FILL") != nullptr, getenv("SPICEY_FRESH_FILL_LINEAR") != nullptr, getenv("SPICEY_NO_EARLY_PREFETCH") != nullptr, getenv("SPICEY_NO_OPERAND_SLOTS") != nullptr, getenv("SPICEY_NO_READY_ARGS") != nullptr, getenv("SPICEY_NO_OPERAND_ADDR") != nullptr, getenv("SPICEY_NO_TOP_REGS") != nullptr, getenv("SPICEY_NO_U0_RESIDENT") != nullptr, getenv("SPICEY_NO_TOP_FOLD") != nullptr, getenv("SPICEY_NO_STAMP_FUSE") != nullptr};
 }
 
 static int pick_threads(const HostProgram &hp, bool v2) {
@@ -304,6 +304,8 @@ int32_t spicey_plan(const SpiceyDesc *desc, const SpiceyOptions &opt, const Spic
     plan.u0_resident = spicey_plan_u0_resident(plan.top_regs, hp.hdr, hres.st_desc.data(), plan.T, shape, knobs);
     // (the fold of the last factor level into the top: that level is row records of the top's rows and nothing else)
     plan.top_fold = spicey_plan_top_fold(plan.u0_resident, hp, hres.tail_n, shape, knobs);
+    // (the stamp fuse: every sum of phase B draws on values of one thread of Z)
+    plan.stamp_fuse = spicey_plan_stamp_fuse(plan.top_fold, hp, hres.tail_n, plan.T, shape, knobs);
   }
   if (!plan.lds) {
     // group mode: several CUs per instance when the batch leaves CUs idle and the circuit is large enough for the
@@ -463,6 +465,109 @@ bool spicey_plan_top_fold(bool u0_resident, const HostProgram &hp, int tail_n, i
          spicey_top_fold_table(hp, tail_n, table);
 }
 bool spicey_top_fold_run(const LaunchPlan &plan, int64_t steps) { return plan.top_fold && spicey_u0_resident_run(plan, steps); }
+
+bool spicey_stamp_fuse_table(const HostProgram &hp, int tail_n, int T, int nsv, int nel, std::vector<uint32_t> &table) {
+  table.clear();
+  const SpiceyProg &P = hp.hdr;
+  const bool linear = P.nD == 0 && P.nS == 0 && P.nDynEnt == 0;
+  if (T <= 0 || nsv != 2 || nel != 2 || !P.has16 || P.hybrid || !P.fresh_fill || linear || P.nS != 0 || P.nL != 0 || !spicey_addr_fits(P, tail_n)) return false;
+  // the beyond-capacity loops of B and Z (TranPhases2::set_remainders)
+  if (P.nKeep > nsv * T || P.nDynEnt > nsv * T || P.nDynX > 0 || P.n > nel * T || P.nRowX > 0) return false;
+  if (P.nOut > nel * T || P.nR > nel * T || P.nC > nel * T || P.nV > T || P.nD > nel * T) return false;
+  if (hp.ent_dd.size() < (size_t)P.nKeep || hp.row_desc.size() < (size_t)P.n * 2) return false;
+  if ((uint32_t)P.nKeep > 0x3FFFu || (uint32_t)(P.xoff + P.n) > 0x3FFFu) return false;
+  const int oV = P.nC + P.nL, oD = P.nC + P.nL + P.nV;
+  std::vector<uint32_t> ent((size_t)T * nsv, SPICEY_SF_NONE), row((size_t)T * nel, SPICEY_SF_NONE);  // [item][thread]
+  std::vector<uint32_t> free_ent, free_row;
+  for (int e = 0; e < P.nKeep; e++) {
+    const uint32_t dd = hp.ent_dd[e];
+    if (dd >> 31) return false;
+    const uint32_t f[2] = {dd & 0x7fffu, (dd >> 15) & 0x7fffu};
+    uint32_t w = (uint32_t)e | ((dd & (1u << 30)) ? SPICEY_SF_RECIP : 0u);
+    int item = -1;
+    for (int q = 0; q < 2; q++) {
+      if (!f[q]) continue;
+      const int i = (int)((f[q] & 0x3fffu) - 1u) - P.nS;
+      if (i < 0 || i >= P.nD || (item >= 0 && item != i)) return false;
+      item = i;
+      w |= (q ? SPICEY_SF_F1 : SPICEY_SF_F0) | ((f[q] & 0x4000u) ? (q ? SPICEY_SF_F1_NEG : SPICEY_SF_F0_NEG) : 0u);
+    }
+    if (item < 0) { free_ent.push_back(w); continue; }
+    uint32_t &slot = ent[(size_t)(item / T) * T + (size_t)(item % T)];
+    if (slot != SPICEY_SF_NONE) return false;
+    slot = w;
+  }
+  std::vector<uint32_t> src_row((size_t)P.nV, SPICEY_SF_NONE);
+  for (int r = 0; r < P.n; r++) {
+    const uint32_t d0 = hp.row_desc[(size_t)r * 2], d1 = hp.row_desc[(size_t)r * 2 + 1];
+    if (d1 == 0xFFFFFFFFu) return false;
+    const uint32_t f[4] = {d0 & 0xffffu, d0 >> 16, d1 & 0xffffu, d1 >> 16};
+    uint32_t w = (uint32_t)(P.xoff + r);
+    int item = -1, nfield = 0, source = -1;
+    for (int q = 0; q < 4; q++) {
+      if (!f[q]) continue;
+      nfield++;
+      const int ix = (int)((f[q] & 0x7fffu) - 1u);
+      const bool neg = (f[q] & 0x8000u) != 0;
+      int i;
+      if (ix < P.nC) {  // gc v of capacitor ix
+        i = ix;
+        if (w & SPICEY_SF_F0) return false;
+        w |= SPICEY_SF_F0 | (neg ? SPICEY_SF_F0_NEG : 0u);
+      } else if (ix >= oD && ix < oD + P.nD) {  // ieq of diode ix - oD
+        i = ix - oD;
+        if (w & SPICEY_SF_F1) return false;
+        w |= SPICEY_SF_F1 | (neg ? SPICEY_SF_F1_NEG : 0u) | ((w & SPICEY_SF_F0) ? 0u : SPICEY_SF_SWAP);
+      } else if (ix >= oV && ix < oV + P.nV) {
+        if (neg || source >= 0) return false;
+        source = ix - oV;
+        continue;
+      } else {
+        return false;
+      }
+      if (item >= 0 && item != i) return false;
+      item = i;
+    }
+    if (source >= 0) {
+      if (nfield != 1 || src_row[source] != SPICEY_SF_NONE) return false;
+      src_row[source] = (uint32_t)(P.xoff + r);
+      continue;
+    }
+    if (!(w & SPICEY_SF_F0)) w &= ~SPICEY_SF_SWAP;  // (a diode's field alone: there is no order to keep)
+    if (item < 0) { free_row.push_back(w); continue; }
+    uint32_t &slot = row[(size_t)(item / T) * T + (size_t)(item % T)];
+    if (slot != SPICEY_SF_NONE) return false;
+    slot = w;
+  }
+  for (int t = 0; t < P.nV; t++)
+    if (src_row[t] == SPICEY_SF_NONE) return false;
+  size_t at = 0;
+  for (uint32_t w : free_ent) {
+    while (at < ent.size() && ent[at] != SPICEY_SF_NONE) at++;
+    if (at == ent.size()) return false;
+    ent[at] = w;
+  }
+  at = 0;
+  for (uint32_t w : free_row) {
+    while (at < row.size() && row[at] != SPICEY_SF_NONE) at++;
+    if (at == row.size()) return false;
+    row[at] = w;
+  }
+  table.assign(spicey_stamp_fuse_words(T), SPICEY_SF_NONE);
+  for (int t = 0; t < T; t++)
+    for (int j = 0; j < 2; j++) {
+      table[(size_t)t * SPICEY_STAMP_FUSE_THREAD_WORDS + j] = ent[(size_t)j * T + t];
+      table[(size_t)t * SPICEY_STAMP_FUSE_THREAD_WORDS + 2 + j] = row[(size_t)j * T + t];
+    }
+  for (int t = 0; t < P.nV; t++) table[(size_t)t * SPICEY_STAMP_FUSE_THREAD_WORDS + 4] = src_row[t];
+  return true;
+}
+bool spicey_plan_stamp_fuse(bool top_fold, const HostProgram &hp, int tail_n, int T, int shape, const SpiceyKnobs &knobs) {
+  std::vector<uint32_t> table;
+  return top_fold && shape >= 0 && shape < SPICEY_V2_NSHAPES && SPICEY_V2_SHAPES[shape].stamp_fuse && T == SPICEY_V2_SHAPES[shape].threads && !knobs.no_stamp_fuse &&
+         spicey_stamp_fuse_table(hp, tail_n, T, SPICEY_V2_SHAPES[shape].nsv, SPICEY_V2_SHAPES[shape].nel, table);
+}
+bool spicey_stamp_fuse_run(const LaunchPlan &plan, int64_t steps) { return plan.stamp_fuse && spicey_top_fold_run(plan, steps); }
 
 size_t spicey_zpar_doubles(const LaunchPlan &plan, const HostProgram &hp) {
   if (!plan.early || plan.interp != 2) return 0;

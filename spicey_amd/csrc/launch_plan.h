@@ -52,11 +52,12 @@ struct SpiceyV2Shape {
   bool top_regs = false;  // ... and that one with the register-exchange top (tran_v2_run.h: TR), taken by an operand-address run whose top has 1 .. 6 stages unless SPICEY_NO_TOP_REGS is set
   bool u0_resident = false;  // ... and that one with the resident level-0 record (tran_v2_run.h: UR), taken by a register-exchange-top run where spicey_u0_resident_fits holds unless SPICEY_NO_U0_RESIDENT is set
   bool top_fold = false;  // ... and that one with the last factor level folded into the top (tran_v2_run.h: TF), taken by a resident-record run where spicey_top_fold_table holds unless SPICEY_NO_TOP_FOLD is set
+  bool stamp_fuse = false;  // ... and that one whose Z stamps the next step, with no phase B in the time loop (tran_v2_run.h: SF), taken by a folded run where spicey_stamp_fuse_table holds unless SPICEY_NO_STAMP_FUSE is set
 };
 // `early`: Z's element parameters come from one record per thread (SpiceyRun::zpar) and are fetched, with the next source
 // value, at the tail of the last factor phase.  The fresh packed build has it; the other builds were left as they are.
 // (spicey_launch_tran_v2 instantiates one kernel per entry; each kind in ascending threads)
-constexpr SpiceyV2Shape SPICEY_V2_SHAPES[] = {{true, false, 512, 4, 6, 2, 4},    {true, false, 512, 4, 2, 2, 4, true, true, true, true, true, true, true, true},
+constexpr SpiceyV2Shape SPICEY_V2_SHAPES[] = {{true, false, 512, 4, 6, 2, 4},    {true, false, 512, 4, 2, 2, 4, true, true, true, true, true, true, true, true, true},
                                               {false, true, 512, 16, 8, 2, 2},   {false, true, 1024, 4, 4, 1, 4},
                                               {false, false, 256, SPICEY_V2_RMAX256, 12, 4, 1},
                                               {false, false, 512, 16, 8, 2, 2},  {false, false, 1024, 8, 4, 1, 4}};
@@ -87,6 +88,7 @@ struct SpiceyKnobs {
   bool no_top_regs = false;          // SPICEY_NO_TOP_REGS: an operand-address run keeps the kernel whose tridiagonal top exchanges its rows through LDS (the in-library A/B switch)
   bool no_u0_resident = false;       // SPICEY_NO_U0_RESIDENT: a register-exchange-top run keeps the kernel that fetches level 0's row record in every step (the in-library A/B switch)
   bool no_top_fold = false;          // SPICEY_NO_TOP_FOLD: a resident-record run keeps the kernel that runs the last factor level as a phase of its own (the in-library A/B switch)
+  bool no_stamp_fuse = false;        // SPICEY_NO_STAMP_FUSE: a folded run keeps the kernel that stamps in a phase B of its own (the in-library A/B switch)
 };
 SpiceyKnobs spicey_read_knobs();
 
@@ -156,6 +158,10 @@ struct LaunchPlan {
   // `u0_resident`, spicey_top_fold_table holds for the program and SPICEY_NO_TOP_FOLD is not set: every resident-record run
   // of the handle takes it (spicey_top_fold_run)
   bool top_fold = false;
+  // ... and a form of that kernel whose Z stamps the next step (tran_v2_run.h: SF), where the plan says `top_fold`,
+  // spicey_stamp_fuse_table holds for the program and SPICEY_NO_STAMP_FUSE is not set: every folded run of the handle takes
+  // it (spicey_stamp_fuse_run)
+  bool stamp_fuse = false;
   bool lds = true;       // workspace in LDS (else global memory)
   size_t lds_bytes = 0;
   int64_t algo_bytes = 0;
@@ -224,6 +230,34 @@ bool spicey_top_fold_table(const HostProgram &hp, int tail_n, std::vector<uint32
 bool spicey_plan_top_fold(bool u0_resident, const HostProgram &hp, int tail_n, int shape, const SpiceyKnobs &knobs);
 // ... and whether that run takes the fold: a resident-record run of a plan that says `top_fold`
 bool spicey_top_fold_run(const LaunchPlan &plan, int64_t steps);
+// The stamp fuse (tran_v2_run.h: SF): Z forms the next step's matrix entries and right-hand-side rows from the conductances
+// and companion currents it has just computed, in registers, writes the entries straight into W and, behind one barrier,
+// the rows; the time loop holds no phase B, and c.gd / c.u are not written in it.  That needs every sum of phase B to draw on values of ONE
+// thread of Z.  spicey_stamp_fuse_table deals the stamped entries and the rows to the threads that produce their operands
+// — table[tid * 6 + {0, 1}]: entry slots, + {2, 3}: row slots, + 4: the row of source tid; slot j goes with the thread's
+// item j, diode and capacitor tid + j T — and returns false unless ALL of this holds for the fresh-fill program hp on T threads with
+// `nsv` entries and `nel` items per thread (`tail_n`: its resident layout's tail levels):
+//   - nsv == nel == 2, operand addresses fit (spicey_addr_fits: every W index is below 2^14), not linear (a reused
+//     factorisation stamps nothing), no switch (no re-iteration: a_reiterate is the other reader of c.gd / c.u), no inductor;
+//   - every beyond-capacity loop of B and Z is empty (TranPhases2::set_remainders: nKeep and nDynEnt <= nsv T, n, nOut, nR,
+//     nC, nD <= nel T, nV <= T, no entry with more than two dynamic stamps, no row with more than four contributions);
+//   - every dynamic field of a stamped entry (ent_dd, e < nKeep) names a diode, and both fields of one entry the same diode
+//     i: the entry takes entry slot i / T of thread i mod T, which no other entry may claim;
+//   - a row with a source's value has that one field alone, added; every source has exactly one such row.  The source's
+//     thread, t, writes it from the parked value: it is the thread's fifth word and takes none of the two row slots;
+//   - every other row with a contribution has at most one capacitor's and one diode's field, both of item i: it takes row
+//     slot i / T of thread i mod T, which no other row may claim;
+//   - entries and rows that depend on nothing (a kept static entry, a row that is 0.0 in every step) go to the free slots, in
+//     ascending (item, thread) order; there must be enough of them.
+// A slot word: bits 0-15 the target's index in W (an entry's id is its index: the static part is statv[id]), SPICEY_SF_*
+// flags above them (tran_pt_layout.h).  The operands enter in the order of the descriptor's fields today: an entry is
+// sv + (+-g) [+ (+-g)], a row 0.0 + first + second with SPICEY_SF_SWAP where the diode's field comes first; a field that the
+// descriptor leaves empty read -0.0, so leaving it out changes no bit.
+bool spicey_stamp_fuse_table(const HostProgram &hp, int tail_n, int T, int nsv, int nel, std::vector<uint32_t> &table);
+// LaunchPlan::stamp_fuse of a plan whose `top_fold` is decided, on build `shape`: what spicey_plan decides
+bool spicey_plan_stamp_fuse(bool top_fold, const HostProgram &hp, int tail_n, int T, int shape, const SpiceyKnobs &knobs);
+// ... and whether that run takes the fuse: a folded run of a plan that says `stamp_fuse`
+bool spicey_stamp_fuse_run(const LaunchPlan &plan, int64_t steps);
 // doubles of the parameter record SpiceyRun::zpar of a planned handle: five per resident item, NEL x T items per instance
 // (0: the plan runs a build without it); a plan that says `top_fold` keeps SPICEY_TOP_FOLD_WORDS words of table behind them
 size_t spicey_zpar_doubles(const LaunchPlan &plan, const HostProgram &hp);

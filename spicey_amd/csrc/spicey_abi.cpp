@@ -296,6 +296,14 @@ static int32_t allocate(SpiceyHandle *h, const SpiceyDesc *desc) {
     std::vector<uint32_t> table;
     if (pl.top_fold && !spicey_top_fold_table(h->hp, h->hres.tail_n, table)) { h->err = "internal: the plan folds the last factor level, but the program has no table for it"; return SPICEY_ERR_BAD_DESC; }
     if (pl.top_fold && table.size() != SPICEY_TOP_FOLD_WORDS) { h->err = "internal: the table of the folded last factor level has the wrong size"; return SPICEY_ERR_BAD_DESC; }
+    // (... and a plan whose Z stamps the next step keeps that form's table behind the fold's: tran_pt_layout.h)
+    if (pl.stamp_fuse) {
+      const int shape = spicey_v2_shape(pl.T, pl.packed, h->hp.hdr.hybrid != 0, pl.packed && h->hp.hdr.fresh_fill != 0);
+      std::vector<uint32_t> fuse;
+      if (!pl.top_fold || shape < 0 || !spicey_stamp_fuse_table(h->hp, h->hres.tail_n, pl.T, SPICEY_V2_SHAPES[shape].nsv, SPICEY_V2_SHAPES[shape].nel, fuse) ||
+          fuse.size() != spicey_stamp_fuse_words(pl.T) || (fuse.size() & 1)) { h->err = "internal: the plan fuses the stamps into Z, but the program has no table for it"; return SPICEY_ERR_BAD_DESC; }
+      table.insert(table.end(), fuse.begin(), fuse.end());
+    }
     h->zpar_doubles = nz + table.size() * sizeof(uint32_t) / sizeof(double);
     HIPCHK(h, dev_upload(h->d_zpar, h->zpar_doubles));
     if (!table.empty()) HIPCHK(h, hipMemcpy((double *)h->d_zpar + nz, table.data(), table.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
@@ -363,8 +371,10 @@ extern "C" int32_t spicey_get_info(SpiceyHandle *h, SpiceyInfo *info) {
 // enqueue the kernel of a prepared launch behind its device's admission gate; ev0 / ev1 bracket the kernel alone
 static int32_t enqueue_kernel(SpiceyHandle *h, const SpiceyRun &R, hipStream_t st) {
   // (the folded kernel reads its table behind the record of R.n_inst instances: only where the allocation holds both)
+  const size_t fuse_doubles = h->plan.stamp_fuse ? spicey_stamp_fuse_words(h->plan.T) * sizeof(uint32_t) / sizeof(double) : 0;  // (that form's table, behind the fold's)
   const bool top_fold = h->plan.interp == 2 && spicey_top_fold_run(h->plan, R.steps) && R.n_inst == h->plan.n_inst &&
-                        h->zpar_doubles == spicey_zpar_doubles(h->plan, h->hp) + SPICEY_TOP_FOLD_WORDS * sizeof(uint32_t) / sizeof(double);
+                        h->zpar_doubles == spicey_zpar_doubles(h->plan, h->hp) + SPICEY_TOP_FOLD_WORDS * sizeof(uint32_t) / sizeof(double) + fuse_doubles;
+  const bool stamp_fuse = top_fold && spicey_stamp_fuse_run(h->plan, R.steps);
   if (h->plan.interp == 2 && spicey_top_fold_run(h->plan, R.steps) && !top_fold) { h->err = "internal: the plan folds the last factor level, but the table is not behind the parameter record"; return SPICEY_ERR_BAD_DESC; }
   DeviceGate &g = device_gate(h->device);
   std::lock_guard<std::mutex> lk(g.mu);  // (wait, launch and record are one step with respect to other launches)
@@ -375,7 +385,7 @@ static int32_t enqueue_kernel(SpiceyHandle *h, const SpiceyRun &R, hipStream_t s
   if (h->plan.interp == 3) {
     HIPCHK(h, spicey_launch_exact(h->d_xprog, h->d_Rstruct, h->plan.grid, h->plan.T, h->plan.lds ? h->plan.lds_bytes : 0, st));
   } else if (h->plan.interp == 2) {
-    HIPCHK(h, spicey_launch_tran_v2(h->dprog, h->dres, h->d_Pstruct, h->d_Qstruct, h->d_Rstruct, h->plan.K, h->plan.grid, h->plan.T, st, h->plan.packed, !h->knobs.no_phase_table, h->d_zpar != nullptr, h->plan.slots, spicey_ready_run(h->plan, R.steps), spicey_addr_run(h->plan, R.steps), spicey_top_regs_run(h->plan, R.steps), spicey_u0_resident_run(h->plan, R.steps), top_fold));
+    HIPCHK(h, spicey_launch_tran_v2(h->dprog, h->dres, h->d_Pstruct, h->d_Qstruct, h->d_Rstruct, h->plan.K, h->plan.grid, h->plan.T, st, h->plan.packed, !h->knobs.no_phase_table, h->d_zpar != nullptr, h->plan.slots, spicey_ready_run(h->plan, R.steps), spicey_addr_run(h->plan, R.steps), spicey_top_regs_run(h->plan, R.steps), spicey_u0_resident_run(h->plan, R.steps), top_fold, stamp_fuse));
   } else if (group) {
     HIPCHK(h, spicey_launch_tran_grp(h->dprog, R, h->plan.K, h->plan.grid, h->plan.T, st));
   } else {
@@ -590,6 +600,7 @@ extern "C" int32_t spicey_group_retries(const SpiceyHandle *h) { return h ? h->g
 extern "C" int32_t spicey_top_regs_form(const SpiceyHandle *h, int64_t steps) { return (h && h->plan.interp == 2 && spicey_top_regs_run(h->plan, steps)) ? 1 : 0; }
 extern "C" int32_t spicey_u0_resident_form(const SpiceyHandle *h, int64_t steps) { return (h && h->plan.interp == 2 && spicey_u0_resident_run(h->plan, steps)) ? 1 : 0; }
 extern "C" int32_t spicey_top_fold_form(const SpiceyHandle *h, int64_t steps) { return (h && h->plan.interp == 2 && spicey_top_fold_run(h->plan, steps)) ? 1 : 0; }
+extern "C" int32_t spicey_stamp_fuse_form(const SpiceyHandle *h, int64_t steps) { return (h && h->plan.interp == 2 && spicey_stamp_fuse_run(h->plan, steps)) ? 1 : 0; }
 extern "C" int64_t spicey_group_stale_polls(const SpiceyHandle *h) { return h ? h->stale_polls : 0; }
 
 // Per instance of the last run, from the status words {code, inst, step, iter} of its workgroups: workgroup (or group) g

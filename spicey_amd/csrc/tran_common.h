@@ -99,6 +99,7 @@ static __device__ __forceinline__ double spicey_quad_bcast_f64(double v, int q) 
 #define SPICEY_PH_S 2
 #define SPICEY_PH_A 3
 #define SPICEY_PH_Z 4
+#define SPICEY_PH_Z2 3  // the second phase of a fused Z (tran_v2_run.h: SF) — A's slot: such a run has no switch and never re-iterates
 #define SPICEY_PH_U0 8
 #define SPICEY_PH_K0 40
 

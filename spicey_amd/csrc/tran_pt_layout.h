@@ -52,6 +52,19 @@ SPICEY_LAYOUT_FN bool spicey_ready_steps_ok(int64_t steps) { return steps >= 0 &
 // size from here.
 #define SPICEY_TOP_FOLD_WORDS 512
 SPICEY_LAYOUT_FN size_t spicey_zpar_record_doubles(int n_inst, int nel, int threads) { return (size_t)n_inst * (size_t)nel * (size_t)threads * 5; }
+// ---- the stamp fuse's table (tran_v2_run.h: SF), behind the fold's ----------------------------------------------------------
+// A run whose Z stamps the next step keeps that form's table — six 32-bit words per thread: its two entry slots, its two
+// row slots, the row of its source, one unused (launch_plan.h: spicey_stamp_fuse_table has the fields) — right behind the
+// fold's table, in the same allocation.  Topology only: one table for all instances.
+#define SPICEY_STAMP_FUSE_THREAD_WORDS 6
+#define SPICEY_SF_NONE 0x80000000u   // the slot holds nothing: nothing is written
+#define SPICEY_SF_RECIP 0x40000000u  // entry slot: the reciprocal is stored, and the pivot is held against SPICEY_EPS
+#define SPICEY_SF_F0 0x00010000u     // first operand present (entry: the entry's first field, + gd; row: gc v of the capacitor)
+#define SPICEY_SF_F0_NEG 0x00020000u // ... and subtracted
+#define SPICEY_SF_F1 0x00040000u     // second operand present (entry: the second field, + gd; row: ieq of the diode)
+#define SPICEY_SF_F1_NEG 0x00080000u // ... and subtracted
+#define SPICEY_SF_SWAP 0x00100000u   // row slot: the diode's field stands in front of the capacitor's
+SPICEY_LAYOUT_FN size_t spicey_stamp_fuse_words(int threads) { return (size_t)threads * SPICEY_STAMP_FUSE_THREAD_WORDS; }
 // ---- operand addresses (operand-address builds, tran_v2_run.h: OA) ---------------------------------------------------------
 // Such a build takes c.W for LDS address 0 (K = 1, LDS workspace, no hybrid layout: the dynamic array is the kernel's only
 // LDS object) and re-encodes the fields of B's resident descriptors — 14 bits each, indices into c.gd / c.u in the

@@ -43,8 +43,16 @@
 // index c.gd and c.u, which lie behind W in the same array, and become indices from the start of W, so that no scalar
 // base stands in their addresses either; spicey_addr_fits has made sure that the fields hold the largest of them, the
 // -0.0 slot.  Same operands, same order, same arithmetic as the RA build.
-template <int K, int RMAX, int NSV, int NEL, bool HYB = false, bool EP = false, bool OS = false, bool RA = false, bool OA = false>
+// SF: the stamp fuse (an operand-address build; tran_v2_run.h has where the phases stand) — Z is two phases.  The first is Z
+// as it stands, but its capacitors and diodes write nothing to LDS: it forms the next step's stamped entries and
+// right-hand-side rows from the thread's OWN conductances and companion currents, in the order of the descriptor's fields,
+// writes the entries straight into W and keeps the rows; the second (z_fuse), behind a barrier, writes the rows over the
+// solution.  The descriptor registers hold the slot words of the host's table (launch_plan.h: spicey_stamp_fuse_table;
+// sf_load), and what crosses the barrier between the two phases rides in registers that are dead there: pf[j][0] = row
+// slot j's sum, srcn = the row of the thread's source.  c.gd and c.u are not written in the time loop.
+template <int K, int RMAX, int NSV, int NEL, bool HYB = false, bool EP = false, bool OS = false, bool RA = false, bool OA = false, bool SF = false>
 struct TranPhases2 {
+  static_assert(!SF || (OA && NSV == 2 && NEL == 2 && ResRegs<K, RMAX, NSV, NEL>::NDD == 2), "the stamp fuse is built into the operand-address kernel of the fresh packed shape");
   static_assert(!EP || (K == 1 && !HYB), "the early prefetch is built for one instance per workgroup on the LDS workspace");
   static_assert(!OS || EP, "the operand slots are built into the early-prefetch kernels");
   static_assert(!RA || OS, "the ready arguments are built into the operand-slot kernels");
@@ -826,6 +834,14 @@ struct TranPhases2 {
     (void)st32;
     const int oL = P.nC, oV = P.nC + P.nL, oD = P.nC + P.nL + P.nV;
     const int cR = 0, cC = P.nR, cL = P.nR + P.nC, cV = cL + P.nL, cS = cV + P.nV, cD = cS + P.nS;
+    if constexpr (SF) {
+      // The early fetch is waited for HERE, on every path through this phase and in front of its first result store.  The wait
+      // below stands behind the test of `valid`; the path around it would leave the loads in flight for the compiler, and the
+      // second phase, which reads the same registers, would wait for vmcnt behind this phase's stores in every step.
+      for (int j = 0; j < NEL; j++)
+        for (int q = 0; q < 5; q++) SPICEY_OPAQUE(rr.pf[j][q]);
+      SPICEY_OPAQUE(rr.srcn);  // (fetched with them; this phase overwrites it with the row of the thread's source)
+    }
     // The instance loop is kept ROLLED here (one copy of the exp / store code, one instance's working set):
     // unrolled and interleaved it needs ~2x the VGPRs and the register-resident program spills.
     SPICEY_NOUNROLL
@@ -862,8 +878,12 @@ struct TranPhases2 {
         uint32_t vx = rr.ox[0];
         SPICEY_OPAQUE(vx);
         if (oi) oi[cV + tid] = OA ? volt_res<1>(vx) : c.W[(size_t)(vx >> 16) * K + k];
+        if constexpr (SF) {  // (the source's row, 0.0 + its next value as rhs_rows forms it, waits in the source register for the second phase)
+          if (!last) srcn = 0.0 + ((K == 1 && prefetched) ? c.u[(size_t)(oD + P.nD + tid) * K + k] : srcn);
+        } else
         if (!last) c.u[(size_t)(oV + tid) * K + k] = (K == 1 && prefetched) ? c.u[(size_t)(oD + P.nD + tid) * K + k] : srcn;
       }
+      if constexpr (SF) rr.srcn = srcn;  // (defined on every path; read by the second phase only where the thread has a source's row and a step follows)
       SPICEY_SCHED_FENCE;
       // resident items (element / row / output tid + j T).  All their terminal voltages are read first, back to
       // back (one LDS round trip), then class by class so that the parameter registers die early.
@@ -897,6 +917,58 @@ struct TranPhases2 {
       }
       SPICEY_SCHED_FENCE;
       SPICEY_MARK(c, 1);
+      if constexpr (SF) {
+        // every LDS read of the solution is done.  The capacitors and the diodes — z_cap_at and z_dio_at without their LDS
+        // writes (-0.0, the neutral operand, where there is no such element) —, and from their values, in registers, the
+        // next step's stamps: stamp_matrix's and rhs_rows' sums, operation for operation.  The entries go straight into W:
+        // nothing reads a matrix entry between K_0's barrier and U_0.  The rows wait in pf[j][0] for the second phase.  Nothing
+        // is stamped behind the last step: no flag is raised for a matrix that no step solves.
+        double gcv[NEL];
+        for (int j = 0; j < NEL; j++) {
+          const int i = tid + j * T;
+          gcv[j] = -0.0;
+          if (i < P.nC) {
+            if (oi) SPICEY_STREAM_STORE(row_at(oi + cC, i), pC[j] * (dC[j] - rr.vprev[j][0]));
+            rr.vprev[j][0] = dC[j];
+            gcv[j] = pC[j] * dC[j];
+            if (last) (RA ? spicey_pt_ptr<double>(ptab, SPICEY_PT_C_VPREV) : R.C_vprev)[in * P.nC + i] = dC[j];
+          }
+        }
+        SPICEY_SCHED_FENCE;
+        SPICEY_MARK(c, 2);
+        for (int j = 0; j < NEL; j++) {
+          const int i = tid + j * T;
+          double gg = -0.0, q = -0.0;
+          if (i < P.nD) {
+            double irec;
+            spicey_diode_k<FRESH>(dD[j], pIs[j], pD0[j], pD1[j], oi != nullptr, gg, q, irec);
+            if (oi) SPICEY_STREAM_STORE(row_at(oi + cD, i), irec);
+            if (last) (RA ? spicey_pt_ptr<double>(ptab, SPICEY_PT_D_VDPREV) : R.D_vdprev)[in * P.nD + i] = dD[j];
+          }
+          double acc = 0.0;
+          if (!last) {
+            uint32_t e = rr.dd[j], r = rr.rhs[j][0];
+            SPICEY_OPAQUE(e); SPICEY_OPAQUE(r);
+            double x = rr.sv[j][0] + sf_operand(gg, e, SPICEY_SF_F0);
+            x = x + sf_operand(gg, e, SPICEY_SF_F1);
+            if (!(e & SPICEY_SF_NONE)) {
+              if (e & SPICEY_SF_RECIP) {
+                if (fabs(x) < SPICEY_EPS && c.valid[0]) { c.flags[1] = 1; c.flags[2] = c.inst[0]; }
+                x = spicey_rcp(x);
+              }
+              Op::template st<1>(c.W, Op::template half<0>(e), 0, x);
+            }
+            const double a = sf_operand(gcv[j], r, SPICEY_SF_F0), b = sf_operand(q, r, SPICEY_SF_F1);
+            const bool swap = (r & SPICEY_SF_SWAP) != 0u;
+            acc = acc + (swap ? b : a);
+            acc = acc + (swap ? a : b);
+          }
+          rr.pf[j][0] = acc;
+          SPICEY_SCHED_FENCE;
+        }
+        SPICEY_MARK(c, 3);
+        continue;
+      }
       for (int j = 0; j < NEL; j++) {
         const int i = tid + j * T;
         if (i < P.nC && !(SPICEY_EXP & 4)) {
@@ -1035,5 +1107,45 @@ struct TranPhases2 {
       }
       SPICEY_SCHED_FENCE;
     }
+  }
+
+  // ---- SF: the stamp fuse ------------------------------------------------------------------------------------------------
+  // Prologue, behind the phase that stamped step 0 with today's B: the descriptor registers take the thread's four slot
+  // words of the host's table, the static values those of the entries the slots name (per instance, as ever: statv by
+  // entry id).  Nothing of the old dealing stays: the same registers, other contents.
+  SPICEY_HD void sf_load(int tid, Regs &rr, const uint32_t *table) const {
+    const uint32_t *w = table + (size_t)tid * SPICEY_STAMP_FUSE_THREAD_WORDS;
+    for (int j = 0; j < 2; j++) {
+      const uint32_t e = w[j], r = w[2 + j];
+      rr.dd[j] = e;
+      rr.rhs[j][0] = r;
+      rr.rhs[j][1] = j == 0 ? w[4] : 0u;  // ([0][1]: the row of source tid)
+      rr.sv[j][0] = (e & SPICEY_SF_NONE) ? 0.0 : R.statv[(size_t)c.inst[0] * P.nLU + (e & 0xffffu)];
+    }
+    // ... and all of them are WAITED for here, once per run.  Their first use is in the second phase of Z; a load that the
+    // compiler still counts as in flight there costs every step a wait for vmcnt, which by then holds the first phase's
+    // result stores (z_record has the story: ~1 us each time).
+    for (int j = 0; j < 2; j++) { SPICEY_OPAQUE(rr.dd[j]); SPICEY_OPAQUE(rr.rhs[j][0]); SPICEY_OPAQUE(rr.rhs[j][1]); SPICEY_OPAQUE(rr.sv[j][0]); }
+  }
+  // operand `g` as a slot word's two flag bits at `has` say: absent reads -0.0, the neutral element, as an empty field did
+  static SPICEY_HD double sf_operand(double g, uint32_t w, uint32_t has) {
+    const double s = signed_by(g, (w & (has << 1)) ? 0x80000000u : 0u);
+    return (w & has) ? s : -0.0;
+  }
+  // The second phase of Z, behind the barrier that follows the first: every reader of the solution has read, and the rows of
+  // the next right-hand side — formed by the first phase, waiting in registers — go over it.  No argument of the run is
+  // read here: the slot words say what the thread has to write.
+  SPICEY_HD void z_fuse(int tid, bool last, Regs &rr) const {
+    if (tid == 0) c.flags[0] = 0;
+    rr.cursor = 0;  // a new solve walks the resident slots from the start
+    if (last || !c.valid[0]) return;
+    for (int j = 0; j < 2; j++) {
+      uint32_t r = rr.rhs[j][0];
+      SPICEY_OPAQUE(r);
+      if (!(r & SPICEY_SF_NONE)) Op::template st<1>(c.W, Op::template half<0>(r), 0, rr.pf[j][0]);
+    }
+    uint32_t sr = rr.rhs[0][1];
+    SPICEY_OPAQUE(sr);
+    if (!(sr & SPICEY_SF_NONE)) Op::template st<1>(c.W, Op::template half<0>(sr), 0, rr.srcn);  // (source tid's row)
   }
 };

@@ -298,7 +298,16 @@ struct SpiceyHasIdleWaves<E, decltype((void)E::idle_waves)> { static constexpr b
 // out — no phase, no barrier; its records stay in their slots and are never dispatched — and the top's head runs the row's
 // record.  The caller has made sure that spicey_top_fold_table holds for the program (launch_plan.h: spicey_plan_top_fold).
 // A host executor runs the whole folded top in one call (spicey_top_fold_wave) where the GPU runs spicey_pcr_all_regs.
-template <int K, int RMAX, int NSV, int NEL, bool HYB = false, int PT = -1, bool EP = false, bool OS = false, bool RA = false, bool OA = false, bool TR = false, bool UR = false, bool TF = false, class Exec>
+// SF (the stamp fuse, TranPhases2; a form of the folded build): the time loop holds no phase B.  The prologue stamps step 0
+// with today's B, once, behind a0_initial's barrier, and then re-deals the descriptor registers from the host's table
+// (behind the fold's, behind R.zpar: tran_pt_layout.h); a pivot below SPICEY_EPS found there ends the run as step 0's B would
+// have ended it — code 1 at step 0, iteration 0, nothing recorded.  Z is two phases with one barrier between them: the first
+// is Z with the stamp arithmetic and writes the matrix entries, which have no reader between K_0's barrier and U_0; the
+// second writes the next right-hand side over the solution once every reader of it has read (a row's slot holds x_r until
+// then, and its readers sit in other waves) — three stores from registers and nothing else.  The
+// caller has made sure that spicey_stamp_fuse_table holds for the program (launch_plan.h: spicey_plan_stamp_fuse): no
+// switch — the loop below never re-iterates —, nothing beyond the resident capacity, not linear.
+template <int K, int RMAX, int NSV, int NEL, bool HYB = false, int PT = -1, bool EP = false, bool OS = false, bool RA = false, bool OA = false, bool TR = false, bool UR = false, bool TF = false, bool SF = false, class Exec>
 SPICEY_HD void spicey_tran_run_v2(Exec &ex, const SpiceyProg &P, const SpiceyResident &Q, const SpiceyRun &R, WgCtx<K> &c, int wg) {
   const int T = ex.threads();
   static_assert(!OS || PT != 0, "the operand slots lie behind the phase table");
@@ -307,7 +316,8 @@ SPICEY_HD void spicey_tran_run_v2(Exec &ex, const SpiceyProg &P, const SpiceyRes
   static_assert(!TR || (OA && K == 1), "the register-exchange top is a form of the operand-address build");
   static_assert(!UR || (TR && !HYB && SpiceyShapeKind<RMAX, NSV, NEL>::fresh), "the resident level-0 record is a form of the register-exchange-top build of the fresh shape");
   static_assert(!TF || UR, "the fold of the last factor level is a form of the resident-record build");
-  typedef TranPhases2<K, RMAX, NSV, NEL, HYB, EP, OS, RA, OA> Ph2;
+  static_assert(!SF || (TF && PT != 0), "the stamp fuse is a form of the folded build");
+  typedef TranPhases2<K, RMAX, NSV, NEL, HYB, EP, OS, RA, OA, SF> Ph2;
   uint32_t brem, zrem;
   {
     Ph2 p2{P, R, c, T, 0u, 0u};
@@ -343,6 +353,16 @@ SPICEY_HD void spicey_tran_run_v2(Exec &ex, const SpiceyProg &P, const SpiceyRes
   });
   ex.phase(SPICEY_PH_PRO, [&](int tid) { const SpiceyProg Pf = ex.fresh(P); const SpiceyRun Rf = ex.fresh(R); TranPhases<K> ph{Pf, Rf, c, T}; ph.p1_static(tid); });
   ex.phase(SPICEY_PH_PRO, [&](int tid) { const SpiceyProg Pf = ex.fresh(P); const SpiceyRun Rf = ex.fresh(R); Ph2 p2{Pf, Rf, c, T, brem, zrem}; p2.a0_initial(tid, ex.template regs<Regs>(tid)); if (EP) p2.zpar_fill(tid); });
+  if constexpr (SF) {  // step 0's stamps, by the phase B of every other form; then the fused form's slots into the same registers
+    ex.phase(SPICEY_PH_PRO, [&](int tid) {
+      const SpiceyProg Pf = ex.fresh(P); const SpiceyRun Rf = ex.fresh(R);
+      Ph2 p2{Pf, Rf, c, T, brem, zrem};
+      p2.b_stamp(tid, ex.template regs<Regs>(tid));
+      SPICEY_SCHED_FENCE;
+      const uint32_t *fuse = (const uint32_t *)(Rf.zpar + spicey_zpar_record_doubles(Rf.n_inst, NEL, T)) + SPICEY_TOP_FOLD_WORDS;
+      p2.sf_load(tid, ex.template regs<Regs>(tid), fuse);
+    });
+  }
   unsigned long long solves = 0;
   int32_t code = 0;
   int64_t err_step = 0;
@@ -395,6 +415,7 @@ SPICEY_HD void spicey_tran_run_v2(Exec &ex, const SpiceyProg &P, const SpiceyRes
       const bool pt_on = PT >= 0 ? PT == 1 : ((tp >> 20) & 1) != 0;
       const uint32_t *ptw = c.tail + spicey_pt_base_words(pcr_n);
       const bool pt_bz = !HYB && pt_on;  // (hybrid builds: B and Z read many more fields; they keep the scalar loads)
+      if constexpr (!SF)  // (SF: the previous step's Z, or the prologue, has stamped)
       ex.phase(SPICEY_PH_B, [&](int tid) {
         if (pt_bz) {
           SpiceyProg Pt{};
@@ -631,6 +652,12 @@ SPICEY_HD void spicey_tran_run_v2(Exec &ex, const SpiceyProg &P, const SpiceyRes
         p2.z_record(tid, step, ex.template regs<Regs>(tid), ((top_pack >> 16) & 1) != 0);
       }
     });
+    if constexpr (SF) {
+      ex.phase(SPICEY_PH_Z2, [&](int tid) {  // (the rows, from registers: no argument of the run is read)
+        Ph2 p2{P, R, c, T, brem, zrem};
+        p2.z_fuse(tid, step == steps, ex.template regs<Regs>(tid));
+      });
+    }
   }
   ex.phase(SPICEY_PH_PRO, [&](int tid) {
     if (tid == 0) {

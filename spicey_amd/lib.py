@@ -43,6 +43,7 @@ SIGNATURES = {
     "spicey_top_regs_form": (_i32, [_vp, _i64]),
     "spicey_u0_resident_form": (_i32, [_vp, _i64]),
     "spicey_top_fold_form": (_i32, [_vp, _i64]),
+    "spicey_stamp_fuse_form": (_i32, [_vp, _i64]),
     "spicey_last_error": (_str, [_vp]),
     "spicey_destroy": (None, [_vp]),
     "spicey_version": (_str, []),
@@ -528,6 +529,10 @@ class Handle:
     def top_fold_form(self, steps: int) -> bool:
         """Whether a run of `steps` steps takes the kernel whose top runs the last factor level itself (spicey_top_fold_form)."""
         return bool(self.L.spicey_top_fold_form(self.h, steps))
+
+    def stamp_fuse_form(self, steps: int) -> bool:
+        """Whether a run of `steps` steps takes the kernel whose Z stamps the next step, with no phase B in the loop (spicey_stamp_fuse_form)."""
+        return bool(self.L.spicey_stamp_fuse_form(self.h, steps))
 
     def error(self) -> str:
         m = self.L.spicey_last_error(self.h)

@@ -63,8 +63,9 @@ def main():
         if args.profile:
             pc = h.phase_cycles()
             per = lambda v: round(v / (steps + 1))  # noqa: E731
-            rec['cyc_per_step'] = dict(B=per(pc['B']), Z=per(pc['Z']), tail=per(pc['U'][31]), U=[per(x) for x in pc['U'][:info['n_levels']]],
-                                       K=[per(x) for x in pc['K'][:info['n_levels']]], total=per(pc['B'] + pc['Z'] + sum(pc['U']) + sum(pc['K'])),
+            # (Z2: the second phase of a fused Z, in the slot of the re-iteration phase A, which such a run never executes; 0 in every other run of a circuit without switches)
+            rec['cyc_per_step'] = dict(B=per(pc['B']), Z=per(pc['Z']), Z2=per(pc['A']), tail=per(pc['U'][31]), U=[per(x) for x in pc['U'][:info['n_levels']]],
+                                       K=[per(x) for x in pc['K'][:info['n_levels']]], total=per(pc['B'] + pc['Z'] + pc['A'] + sum(pc['U']) + sum(pc['K'])),
                                        gaps=per(pc['between_phases']), marks=[per(x) for x in pc['K'][16:31]], run=per(pc['run_cycles']), clock_GHz=round(pc['run_cycles'] / max(pc['run_wall_ticks_100MHz'], 1) * 0.1, 3))
         print(json.dumps(rec), flush=True)
         h.close()
