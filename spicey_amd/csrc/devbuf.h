@@ -54,7 +54,7 @@ inline int32_t spicey_open_device(int device, int *ncu, std::string &err) {
   return SPICEY_OK;
 }
 
-// The reduction passes behind a transient run, in the order they run (spicey_abi.cpp, run_reduced): the index of a pass's
+// The reduction passes behind a transient run, in the order they run (reduced_abi.cpp, run_reduced): the index of a pass's
 // event pair in StreamTimers and of its time in SpiceyHandle::last_pass_ms.
 enum SpiceyPass { PASS_MEASURE = 0, PASS_FOURIER = 1, PASS_TIMING = 2, PASS_SPECTRUM = 3, PASS_POWER = 4, PASS_VALUES = 5, N_PASS = 6 };
 

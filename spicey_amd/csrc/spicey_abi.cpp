@@ -1,51 +1,21 @@
-// spicey_abi.cpp — the C-ABI of include/spicey_hip.h: handle management, uploads, launches.
-// Host code only (HIP runtime API); the kernels are in kernels.hip, the symbolic phase in
-// symbolic.cpp.  There is NO CPU solve path in this library: without a HIP device every entry
+// spicey_abi.cpp — the C-ABI of include/spicey_hip.h: handle management, uploads, launches, state, diagnostics and the
+// multi-device handle (the reduced runs behind a launch are in reduced_abi.cpp, the handle-less device entry points in
+// device_abi.cpp, what the three share in tran_handle.h).  Host code only (HIP runtime API); the kernels are in kernels.hip,
+// the symbolic phase in symbolic.cpp.  There is NO CPU solve path in this library: without a HIP device every entry
 // point that would compute returns SPICEY_ERR_NO_DEVICE.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
 #include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <dlfcn.h>
-#include <functional>
 #include <map>
 #include <mutex>
 #include <string>
+#include <thread>
 #include <vector>
 
-#include "../../include/spicey_hip.h"
-#include "devbuf.h"
-#include "exact_plan.h"
-#include "kernels.h"
-#include "launch_plan.h"
-#include "ac_measure.h"
-#include "ac_measure_exec.h"
-#include "fourier.h"
-#include "fourier_exec.h"
-#include "measure.h"
-#include "measure_exec.h"
-#include "noise.h"
-#include "mc.h"
-#include "sens.h"
-#include "power.h"
-#include "values.h"
-#include "spectrum.h"
-#include "timing.h"
-#include "timing_exec.h"
-#include "tran_mc.h"
-#include "tran_sens.h"
-#include "symbolic.h"
+#include "tran_handle.h"
 #include "fronts_exec_consts.h"
 
-// The instance state a transient step carries: C_vprev, L_iprev, D_vdprev, S_ison ([n_inst][nC | nL | nD | nS] each).
-struct StatePtrs { double *Cv, *Li, *Dv; int32_t *Son; };
-struct StateBufs {
-  DevBuf<double> Cv, Li, Dv;
-  DevBuf<int32_t> Son;
-  StatePtrs ptrs() const { return {Cv, Li, Dv, Son}; }
-};
 // (d: the descriptor's state; null: zeros)
 static hipError_t upload_state(StateBufs &s, const SpiceyDesc *d, const SpiceyProg &P, size_t ni) {
   hipError_t e;
@@ -67,85 +37,7 @@ static hipError_t copy_state(const StatePtrs &dst, const StatePtrs &src, const S
   return hipSuccess;
 }
 
-struct SpiceyHandle {
-  HostProgram hp;
-  HostResident hres;
-  LaunchPlan plan;       // K, T, grid, G, interpreter, geometry, workspace (launch_plan.h)
-  SpiceyOptions opt{};
-  SpiceyKnobs knobs;     // environment, read once by spicey_create
-  SpiceyProg dprog{}; SpiceyResident dres{};
-  int device = 0;
-  DevBuf<uint8_t> d_blob, d_res;
-  // v2 kernels take their argument structs from device memory (scalar loads per phase instead of ~110 pointers in SGPRs)
-  DevBuf<SpiceyProg> d_Pstruct; DevBuf<SpiceyResident> d_Qstruct; DevBuf<SpiceyRun> d_Rstruct;
-  SpiceyRun run_args{};  // host copy of the last launch's SpiceyRun (source of the asynchronous upload)
-  DevBuf<double> d_R, d_C, d_L, d_Sron, d_Sroff, d_Svon, d_Svoff, d_Dis, d_Dn;
-  // live, the descriptor's (spicey_reset_state), and in group mode the state as it entered the launch in flight (a launch
-  // that ends in the bounded-spin abort is repeated once)
-  StateBufs state, state0, state_s;
-  // reference-order engine (interpreter 3): stamp lists and terminals, their device copy and descriptor, global workspace
-  HostExactProg xp;
-  DevBuf<uint32_t> d_xblob; DevBuf<SpiceyExactProg> d_xprog; DevBuf<double> d_xws;
-  DevBuf<unsigned int> d_gsync; DevBuf<int32_t> d_gflags;
-  // dense fronts: workspace [grid][front_ws], schedule of the G workgroups, done flags [grid][2 nFronts]
-  DevBuf<double> d_front_ws;
-  DevBuf<uint32_t> d_fs;  // first[G + 1] | list[nFronts] | owner[nFronts]
-  DevBuf<unsigned int> d_front_flags;
-  SpiceyRun grp_R{};      // group mode: the launch's arguments
-  int group_retries = 0;  // launches repeated so far (spicey_group_retries)
-  // diagnostics (SpiceyOptions.diagnostics): skip-risk counters [n_inst], linearisation points [n_inst][nD], per-step
-  // linearisation error [n_inst][steps + 1] of the last run (grown on demand)
-  DevBuf<double> d_hybG, d_hybUG;  // hybrid workspace: leaf-owned entries [n_inst][nLU], u | gd [n_inst][nU + nGdyn]
-  DevBuf<unsigned long long> d_skip, d_linerr; DevBuf<double> d_linvd;
-  size_t linerr_cap = 0;
-  int64_t last_steps = -1;
-  int64_t stale_polls = 0;  // group mode: waits that only the read-modify-write poll saw satisfied (spicey_group_stale_polls)
-  bool gated = false;     // this handle is counted in its device's group-mode handles (DeviceGate)
-  DevBuf<double> d_gstat, d_statv, d_rcoef, d_gW, d_dpar;
-  size_t zpar_doubles = 0;  // doubles allocated in d_zpar: the record, and behind it the table of the folded last factor level where the plan says top_fold
-  DevBuf<double> d_zpar;  // early-prefetch builds: Z's parameter record (SpiceyRun::zpar), written by every launch's prologue; else null
-  DevBuf<int32_t> d_status; DevBuf<unsigned long long> d_solves, d_prof;
-  hipStream_t last_stream = nullptr;
-  double last_pass_ms[N_PASS] = {};  // the reduction passes of the last spicey_run_measure* (0: the pass did not run)
-  double last_tran_mc_ms = 0.0, last_tran_mc_draw_ms = 0.0;  // the last spicey_run_mc: its scalars and reduction, its draw
-  double last_tran_sens_ms = 0.0, last_tran_sens_design_ms = 0.0;  // the last spicey_run_sens / spicey_run_levels: the same, its design
-  bool pending = false;
-  int64_t last_solves = 0;
-  double last_ms = 0.0;
-  // status words [grid][4] of the last finished launch (spicey_sync), and whether the last run was refused as structurally
-  // singular before any launch (every instance then fails): the per-instance answer of spicey_last_inst_status
-  std::vector<int32_t> last_status;
-  bool last_structural = false;
-  std::string err;
-  StreamTimers q;  // the owned stream of spicey_run and its events (last: they go before the device buffers)
-};
-
-static thread_local std::string g_err;  // message of the calling thread's last failed spicey_create (no handle to hang it on)
-
-// roctx ranges around the host-side phases (SURVEY §5 tracing hook): `rocprofv3 --marker-trace` shows symbolic phase, uploads,
-// kernel and result copies as named ranges.  The marker library is looked up at run time (no link dependency: without it,
-// or outside a profiler, the ranges cost one null check).
-namespace {
-struct Roctx {
-  typedef int (*push_t)(const char *);
-  typedef int (*pop_t)();
-  static push_t push_fn() {
-    static push_t f = []() -> push_t {
-      for (const char *lib : {"librocprofiler-sdk-roctx.so", "libroctx64.so"})
-        if (void *hnd = dlopen(lib, RTLD_LAZY | RTLD_GLOBAL))
-          if (void *sym = dlsym(hnd, "roctxRangePushA")) { pop_fn_ref() = (pop_t)dlsym(hnd, "roctxRangePop"); return (push_t)sym; }
-      return nullptr;
-    }();
-    return f;
-  }
-  static pop_t &pop_fn_ref() { static pop_t p = nullptr; return p; }
-  bool on;
-  explicit Roctx(const char *name) : on(false) {
-    if (push_t f = push_fn()) { f(name); on = pop_fn_ref() != nullptr; }
-  }
-  ~Roctx() { if (on) pop_fn_ref()(); }
-};
-}  // namespace
+thread_local std::string g_err;  // (tran_handle.h)
 
 // ---- launch admission per device (include/spicey_hip.h, "Launch admission") ------------------------------------------
 // A group-mode launch (G > 1 workgroups per instance that wait for one another inside the kernel) needs all its workgroups
@@ -411,20 +303,20 @@ static int32_t reset_launch_words(SpiceyHandle *h, hipStream_t st) {
 
 // A new run begins: what spicey_last_inst_status reported about the previous one no longer holds (until this run's launch
 // has finished, or it was refused as structurally singular, there is no per-instance answer).
-static void forget_last_run(SpiceyHandle *h) {
+void forget_last_run(SpiceyHandle *h) {
   h->last_status.clear();
   h->last_structural = false;
 }
 
 // The refusals of every transient entry point, in their order: the run arguments (out: the call's result buffer, src: its
 // source table), then a matrix that is singular by its structure (every instance then fails: spicey_last_inst_status).
-static int32_t check_run_args(SpiceyHandle *h, int64_t steps, const void *out, const void *src, int32_t src_per_inst) {
+int32_t check_run_args(SpiceyHandle *h, int64_t steps, const void *out, const void *src, int32_t src_per_inst) {
   forget_last_run(h);
   if (steps < 0 || !out || (h->hp.hdr.nV > 0 && !src)) { h->err = "bad run arguments"; return SPICEY_ERR_BAD_DESC; }
   if (src_per_inst != 0 && src_per_inst != 1) { h->err = "src_per_inst must be 0 (one shared table) or 1 (one table per instance)"; return SPICEY_ERR_BAD_DESC; }
   return SPICEY_OK;
 }
-static int32_t check_structure(SpiceyHandle *h) {
+int32_t check_structure(SpiceyHandle *h) {
   if (!h->hp.structurally_singular) return SPICEY_OK;
   h->err = "singular at inst 0 step 0 iter 0 (structurally singular matrix)";
   h->last_structural = true;
@@ -434,7 +326,7 @@ static int32_t check_structure(SpiceyHandle *h) {
 // The body of spicey_run_device_src.  vals: null, or the device arrays {R, C, L} ([n_inst][n<kind>]: ohms, farads, henries)
 // this run reads in the place of the handle's own (spicey_run_mc: the drawn values); the kernels derive everything they
 // keep about the values in their own prologue, so nothing else changes.
-static int32_t run_device_src(SpiceyHandle *h, int64_t steps, double dt, const double *d_src_table, int32_t src_per_inst, double *d_out_v, double *d_out_i,
+int32_t run_device_src(SpiceyHandle *h, int64_t steps, double dt, const double *d_src_table, int32_t src_per_inst, double *d_out_v, double *d_out_i,
                               int32_t *d_iters, void *stream, const double *const *vals) {
   if (!h) return SPICEY_ERR_BAD_DESC;
   if (const int32_t rc0 = check_run_args(h, steps, d_out_v, d_src_table, src_per_inst); rc0 != SPICEY_OK) return rc0;
@@ -627,32 +519,6 @@ extern "C" int32_t spicey_last_inst_status(SpiceyHandle *h, int32_t *status) {
   return bad;
 }
 
-// The device side of a run on host buffers (run_host, spicey_run_measure): the source table up on the handle's stream,
-// the buffers the run records into, and the way back.
-struct HostRun {
-  size_t np = 0, ni = 0;
-  DevBuf<double> d_src, d_v, d_i;
-  DevBuf<int32_t> d_it;
-  int32_t stage(SpiceyHandle *h, int64_t steps, const double *src_table, int32_t src_per_inst, bool want_i, bool want_iters) {
-    const SpiceyProg &P = h->hp.hdr;
-    np = (size_t)steps + 1, ni = (size_t)h->plan.n_inst;
-    const size_t ntab = src_per_inst ? ni : 1;
-    HIPCHK(h, d_src.alloc(std::max<size_t>(ntab * np * P.nV, 1)));
-    if (P.nV) HIPCHK(h, hipMemcpyAsync(d_src, src_table, ntab * np * P.nV * sizeof(double), hipMemcpyHostToDevice, h->q.stream));
-    HIPCHK(h, d_v.alloc(std::max<size_t>(ni * np * P.nOut, 1)));
-    if (want_i) HIPCHK(h, d_i.alloc(std::max<size_t>(ni * np * P.nCur, 1)));
-    if (want_iters) HIPCHK(h, d_it.alloc(ni * np));
-    return SPICEY_OK;
-  }
-  // (blocking copies behind a finished run; null: not wanted)
-  int32_t copy_out(SpiceyHandle *h, double *out_v, double *out_i, int32_t *iters) const {
-    const SpiceyProg &P = h->hp.hdr;
-    if (out_v) HIPCHK(h, hipMemcpy(out_v, d_v, ni * np * P.nOut * sizeof(double), hipMemcpyDeviceToHost));
-    if (out_i) HIPCHK(h, hipMemcpy(out_i, d_i, ni * np * P.nCur * sizeof(double), hipMemcpyDeviceToHost));
-    if (iters) HIPCHK(h, hipMemcpy(iters, d_it, ni * np * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return SPICEY_OK;
-  }
-};
 
 // keep_partial: the results also come back after SPICEY_ERR_SINGULAR (spicey_run_src: the instances that finished are complete)
 static int32_t run_host(SpiceyHandle *h, int64_t steps, double dt, const double *src_table, int32_t src_per_inst, double *out_v,
@@ -786,697 +652,7 @@ extern "C" int32_t spicey_debug_front_ticks(SpiceyHandle *h, int32_t grp, uint64
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Waveform measurements (include/spicey_hip.h): the reduction pass of measure.hip behind a transient run.
-
-extern "C" int64_t spicey_measure_workspace_bytes(int32_t n_inst, int64_t n_points, int32_t n_req) {
-  return spicey_meas_workspace_bytes(n_inst, n_points, n_req);
-}
-
-// The tail of the handle-less spicey_*_device entry points, behind their judge: the device opened, the launch enqueued, a
-// failure as "<launcher>: <the runtime's text>" in the calling thread's error.
-static int32_t launch_on_device(int32_t device, const char *launcher, const std::function<hipError_t()> &launch) {
-  int ncu = 0;
-  if (const int32_t rc = spicey_open_device(device, &ncu, g_err); rc != SPICEY_OK) return rc;
-  const hipError_t e = launch();
-  if (e != hipSuccess) { g_err = std::string(launcher) + ": " + hipGetErrorString(e); return SPICEY_ERR_HIP; }
-  return SPICEY_OK;
-}
-
-extern "C" int32_t spicey_measure_device(int32_t device, int32_t n_inst, int64_t n_points, double dt, const double *d_v, int32_t n_v, const double *d_i,
-                                         int32_t n_i, const SpiceyMeasReq *reqs, int32_t n_req, double *d_meas, void *d_work, int64_t work_bytes,
-                                         void *stream) {
-  // (the call is judged before the device is touched: a refusal launches nothing)
-  std::vector<SpiceyMeasDevReq> table;
-  if (const int32_t rc = spicey_judge_measure("measure", spicey_meas_plan, spicey_meas_workspace_bytes, n_inst, n_points, d_v != nullptr, n_v, d_i != nullptr, n_i, reqs,
-                                              n_req, d_meas && d_work, work_bytes, table, g_err); rc != SPICEY_OK)
-    return rc;
-  return launch_on_device(device, "spicey_launch_measure", [&]() {
-    return spicey_launch_measure(device, n_inst, n_points, dt, d_v, n_v, d_i, n_i, table.data(), n_req, d_meas, d_work, (hipStream_t)stream);
-  });
-}
-
-// The lists of spicey_run_measure, spicey_run_measure_fourier, spicey_run_measure_timing, spicey_run_measure_spectrum and spicey_run_measure_power: per pass
-// the caller's requests, their count and the out pointer.  entry = the entry point's own pass, its last: that list may not be empty, the lists
-// before it may, and there are none behind it.
-struct ReducedLists {
-  int entry;
-  const SpiceyMeasReq *reqs; int32_t n_req; double *meas;
-  const SpiceyFourReq *freqs; int32_t n_four; double *four; int32_t four_stride;
-  const SpiceyTimingReq *treqs; int32_t n_tim; double *timing;
-  const SpiceySpecReq *sreqs = nullptr; int32_t n_spec = 0; double *spec = nullptr; int32_t spec_stride = 0;
-  const SpiceyPowerReq *preqs = nullptr; int32_t n_power = 0; double *power = nullptr;
-  // (spicey_run_reduced only, entry = -1: every list may be empty but not all of them, and a pass runs iff its count is > 0)
-  const SpiceyValReq *vreqs = nullptr; int32_t n_values = 0; const SpiceyValPoint *pts = nullptr; int64_t n_pts = 0; double *values = nullptr;
-  int32_t values_stride = 0;
-};
-
-// What spicey_run_mc adds to a reduced run: the draw in front of the transient, which then reads the drawn values, and behind
-// the passes — whose rows stay on the device — the scalars and the reduction across the instances (tran_mc.hip).
-struct TranMcCall {
-  const SpiceyTranMcReq *req; const double *tol, *icdf;
-  const SpiceyMcScalar *scalars; int32_t n_scalar;
-  const double *lo, *hi, *probs; int32_t n_prob;
-  double *stat; int64_t *sample; double *x;
-};
-// What spicey_run_sens and spicey_run_levels add to a reduced run: the design in front of the transient, which then reads the
-// designed values, and behind the passes the scalars and — spicey_run_sens — the reduction across the instances (tran_sens.hip).
-struct TranSensCall {
-  int32_t mode;  // the design the entry point takes
-  const SpiceyTranSensReq *req; const int32_t *act; const double *step; const int8_t *lvl; const double *tol;
-  const SpiceyMcScalar *scalars; int32_t n_scalar;
-  double *sens; int8_t *sign; double *bound; double *x;
-};
-namespace {
-struct EventPair {  // (a call's own pair of timing events)
-  hipEvent_t a = nullptr, b = nullptr;
-  EventPair() = default;
-  EventPair(const EventPair &) = delete;
-  ~EventPair() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-  hipError_t create() { const hipError_t e = hipEventCreate(&a); return e != hipSuccess ? e : hipEventCreate(&b); }
-};
-}  // namespace
-
-// What the entry points share: one transient run into device buffers of this call's own, the reductions on the
-// handle's stream behind it, and only their results and `iters` on the way back.  mc: null, or what spicey_run_mc adds; ts: null,
-// or what spicey_run_sens / spicey_run_levels add (at most one of the two).
-static int32_t run_reduced(SpiceyHandle *h, int64_t steps, double dt, const double *src_table, int32_t src_per_inst, const ReducedLists &a, int32_t *iters,
-                           const TranMcCall *mc = nullptr, const TranSensCall *ts = nullptr) {
-  if (!h) return SPICEY_ERR_BAD_DESC;
-  const bool bound = mc || ts;  // the run reads scratch value arrays and its passes' rows stay on the device
-  double *const outs[N_PASS] = {a.meas, a.four, a.timing, a.spec, a.power, a.values};
-  const int32_t counts[N_PASS] = {a.n_req, a.n_four, a.n_tim, a.n_spec, a.n_power, a.n_values};
-  if (mc) {
-    h->last_tran_mc_ms = h->last_tran_mc_draw_ms = 0.0;
-    const char *what = !mc->stat || !mc->sample ? "tran mc: null buffer"
-                       : a.n_four > 0 || a.n_spec > 0 || a.n_values > 0 ? "tran mc: the fourier, spectrum and values lists are not reduced by this call (measure, timing and power are)"
-                       : nullptr;
-    if (what) { forget_last_run(h); h->err = what; return SPICEY_ERR_BAD_DESC; }
-  }
-  if (ts) {
-    h->last_tran_sens_ms = h->last_tran_sens_design_ms = 0.0;
-    const bool levels = ts->mode == SPICEY_TS_LEVELS;
-    const char *what = (levels ? !ts->x : (!ts->sens || !ts->sign || !ts->bound)) ? "tran sens: null buffer"
-                       : a.n_four > 0 || a.n_spec > 0 || a.n_values > 0 ? "tran sens: the fourier, spectrum and values lists are not reduced by this call (measure, timing and power are)"
-                       : nullptr;
-    if (what) { forget_last_run(h); h->err = what; return SPICEY_ERR_BAD_DESC; }
-  }
-  if (a.entry < 0) {
-    int first_on = -1;
-    for (int p = N_PASS - 1; p >= 0; p--) {
-      if (counts[p] < 0) { forget_last_run(h); h->err = "reduced: every count must be >= 0"; return SPICEY_ERR_BAD_DESC; }
-      if (counts[p] > 0) first_on = p;
-    }
-    if (first_on < 0) { forget_last_run(h); h->err = "reduced: every list is empty (at least one count must be > 0)"; return SPICEY_ERR_BAD_DESC; }
-    // (a Monte Carlo run leaves the passes' rows on the device: what it brings back is `stat`, and the lists' result pointers
-    // are not looked at)
-    double *const some_out = mc ? mc->stat : ts ? (ts->mode == SPICEY_TS_LEVELS ? ts->x : ts->bound) : outs[first_on];
-    if (const int32_t rc0 = check_run_args(h, steps, some_out, src_table, src_per_inst); rc0 != SPICEY_OK) return rc0;
-    for (int p = 0; p < N_PASS && !bound; p++)
-      if (counts[p] > 0 && !outs[p]) { h->err = "reduced: a result pointer is null where its count is > 0"; return SPICEY_ERR_BAD_DESC; }
-  } else if (const int32_t rc0 = check_run_args(h, steps, outs[a.entry], src_table, src_per_inst); rc0 != SPICEY_OK) return rc0;
-  if (a.entry == 1 && (a.n_req < 0 || (a.n_req > 0 && !a.meas))) { h->err = "fourier: n_req must be >= 0, and meas not null when n_req > 0"; return SPICEY_ERR_BAD_DESC; }
-  if (a.entry == 2 && (a.n_req < 0 || (a.n_req > 0 && !a.meas) || a.n_four < 0 || (a.n_four > 0 && !a.four))) {
-    h->err = "timing: n_req and n_four must be >= 0, and meas / four not null when their count is > 0";
-    return SPICEY_ERR_BAD_DESC;
-  }
-  if (a.entry == 3 && (a.n_req < 0 || (a.n_req > 0 && !a.meas) || a.n_four < 0 || (a.n_four > 0 && !a.four) || a.n_tim < 0 || (a.n_tim > 0 && !a.timing))) {
-    h->err = "spectrum: n_req, n_four and n_timing must be >= 0, and meas / four / timing not null when their count is > 0";
-    return SPICEY_ERR_BAD_DESC;
-  }
-  if (a.entry == 4 && (a.n_req < 0 || (a.n_req > 0 && !a.meas) || a.n_four < 0 || (a.n_four > 0 && !a.four) || a.n_tim < 0 || (a.n_tim > 0 && !a.timing) ||
-                       a.n_spec < 0 || (a.n_spec > 0 && !a.spec))) {
-    h->err = "power: n_req, n_four, n_timing and n_spec must be >= 0, and meas / four / timing / spec not null when their count is > 0";
-    return SPICEY_ERR_BAD_DESC;
-  }
-  // (a pass runs if it is the entry point's own, or an earlier one whose list is not empty)
-  bool on[N_PASS];
-  for (int p = 0; p < N_PASS; p++) on[p] = a.entry < 0 ? counts[p] > 0 : p == a.entry || (p < a.entry && counts[p] != 0);
-  const SpiceyProg &P = h->hp.hdr;
-  const int32_t ni = h->plan.n_inst;
-  const int64_t np = steps + 1;
-  // (a refused request list runs nothing; the buffers are this call's own)
-  const int64_t work_bytes = on[PASS_MEASURE] ? spicey_meas_workspace_bytes(ni, np, a.n_req) : 0;
-  std::vector<SpiceyMeasDevReq> table;
-  if (on[PASS_MEASURE])
-    if (const int32_t rc0 = spicey_judge_measure("measure", spicey_meas_plan, spicey_meas_workspace_bytes, ni, np, true, P.nOut, true, P.nCur, a.reqs, a.n_req, true,
-                                                 work_bytes, table, h->err); rc0 != SPICEY_OK)
-      return rc0;
-  SpiceyFourPlan fplan;
-  if (on[PASS_FOURIER] && !spicey_four_judge(ni, np, dt, true, P.nOut, true, P.nCur, a.freqs, a.n_four, true, a.four_stride, INT64_MAX, fplan, h->err))
-    return SPICEY_ERR_BAD_DESC;
-  SpiceyTimPlan tplan;
-  if (on[PASS_TIMING] && !spicey_tim_judge(ni, np, dt, true, P.nOut, true, P.nCur, a.treqs, a.n_tim, true, INT64_MAX, tplan, h->err)) return SPICEY_ERR_BAD_DESC;
-  SpiceySpecPlan splan;
-  if (on[PASS_SPECTRUM] && !spicey_spec_judge(ni, np, dt, true, P.nOut, true, P.nCur, a.sreqs, a.n_spec, true, a.spec_stride, INT64_MAX, splan, h->err))
-    return SPICEY_ERR_BAD_DESC;
-  std::vector<SpiceyPowerDevReq> ptable;
-  if (on[PASS_POWER] && !spicey_power_judge(ni, np, dt, true, P.nOut, true, P.nCur, a.preqs, a.n_power, true, INT64_MAX, ptable, h->err)) return SPICEY_ERR_BAD_DESC;
-  SpiceyValPlan vplan;
-  if (on[PASS_VALUES] && !spicey_val_judge(ni, np, dt, true, P.nOut, true, P.nCur, a.vreqs, a.n_values, a.pts, a.n_pts, on[PASS_TIMING], a.n_tim, true, a.values_stride,
-                                           INT64_MAX, vplan, h->err))
-    return SPICEY_ERR_BAD_DESC;
-  // (the Monte Carlo request, tolerances, table, programs, limits and probabilities, judged on placeholder buffers: the scratch
-  // arrays and the passes' rows are bound below)
-  SpiceyMcDrawArgs mcD{};
-  SpiceyTmcArgs mcA{};
-  int64_t mc_work_bytes = 0;
-  if (mc) {
-    double dummy = 0.0, *some = &dummy;  // (any non-null pointer: the judges look at null-ness only)
-    const int64_t draw_bytes = mc->req ? spicey_mc_draw_bytes(P.nR + P.nC + P.nL, mc->req->log2K) : 0;
-    const int64_t red_bytes = spicey_tmc_reduce_bytes(ni, mc->n_scalar, mc->n_prob);
-    const SpiceyMcRows jr[SPICEY_TMC_N_PASS] = {{on[PASS_MEASURE] ? some : nullptr, on[PASS_MEASURE] ? a.n_req : 0, 8},
-                                                {on[PASS_TIMING] ? some : nullptr, on[PASS_TIMING] ? a.n_tim : 0, 8},
-                                                {on[PASS_POWER] ? some : nullptr, on[PASS_POWER] ? a.n_power : 0, SPICEY_POWER_ROW}};
-    if (!spicey_tmc_draw_judge(ni, P.nR, P.nC, P.nL, some, some, some, mc->tol, mc->icdf, mc->req, some, some, some, true, draw_bytes, mcD, h->err) ||
-        !spicey_tmc_reduce_judge(ni, jr, mc->scalars, mc->n_scalar, mc->lo, mc->hi, mc->probs, mc->n_prob, true, red_bytes, mcA, h->err))
-      return SPICEY_ERR_BAD_DESC;
-    mc_work_bytes = std::max(draw_bytes, red_bytes);
-  }
-  // (the same for a sensitivity or levels run: the design's request and arrays, the programs, the steps and tolerances)
-  SpiceyTsDesignArgs tsD{};
-  SpiceyTmcArgs tsT{};
-  SpiceyTsReduceArgs tsA{};
-  std::vector<double> ts_tol_act;
-  if (ts) {
-    double dummy = 0.0, *some = &dummy;
-    const int32_t nE = P.nR + P.nC + P.nL, nA = ts->req ? ts->req->nA : 0;
-    const SpiceyMcRows jr[SPICEY_TMC_N_PASS] = {{on[PASS_MEASURE] ? some : nullptr, on[PASS_MEASURE] ? a.n_req : 0, 8},
-                                                {on[PASS_TIMING] ? some : nullptr, on[PASS_TIMING] ? a.n_tim : 0, 8},
-                                                {on[PASS_POWER] ? some : nullptr, on[PASS_POWER] ? a.n_power : 0, SPICEY_POWER_ROW}};
-    if (!spicey_ts_design_judge(ni, P.nR, P.nC, P.nL, some, some, some, ts->req, ts->mode, ts->act, ts->step, ts->lvl, ts->tol, some, some, some, true, INT64_MAX, tsD,
-                                h->err))
-      return SPICEY_ERR_BAD_DESC;
-    if (ts->mode == SPICEY_TS_LEVELS) {
-      if (!spicey_ts_scalar_judge(ni, jr, ts->scalars, ts->n_scalar, true, tsT, h->err)) return SPICEY_ERR_BAD_DESC;
-    } else {
-      if (!ts->tol) { h->err = "tran sens: null buffer"; return SPICEY_ERR_BAD_DESC; }
-      if (const char *what = spicey_ts_judge_tol(ts->tol, nE)) { h->err = std::string("tran sens: ") + what; return SPICEY_ERR_BAD_DESC; }
-      ts_tol_act.resize((size_t)nA);
-      for (int32_t k = 0; k < nA; k++) ts_tol_act[(size_t)k] = ts->tol[ts->act[k]];
-      if (!spicey_ts_reduce_judge(ni, jr, ts->scalars, ts->n_scalar, ts->step, ts_tol_act.data(), nA, true, INT64_MAX, tsT, tsA, h->err)) return SPICEY_ERR_BAD_DESC;
-    }
-    mc_work_bytes = spicey_ts_workspace_bytes(ni, ts->n_scalar, nE, nA);
-  }
-  const auto names_a_current = [](const auto &list) { return std::any_of(list.begin(), list.end(), [](const auto &q) { return q.signal == 1; }); };
-  const bool need_i = names_a_current(table) || names_a_current(fplan.table) || names_a_current(tplan.edges) || names_a_current(splan.table) ||
-                      std::any_of(ptable.begin(), ptable.end(), [](const SpiceyPowerDevReq &q) { return q.a_signal == 1 || q.b_signal == 1; }) ||
-                      names_a_current(vplan.traces) || std::any_of(vplan.points.begin(), vplan.points.end(), [](const SpiceyValDevPts &q) {
-                        return q.signal == 1 || (q.kind == SPICEY_VAL_FIND && q.x_signal == 1);
-                      });
-  if (const int32_t rc0 = check_structure(h); rc0 != SPICEY_OK) return rc0;
-  HIPCHK(h, hipSetDevice(h->device));
-  static const char *const entry_name[N_PASS] = {"spicey_run_measure", "spicey_run_measure_fourier", "spicey_run_measure_timing", "spicey_run_measure_spectrum",
-                                                 "spicey_run_measure_power", "spicey_run_reduced"};
-  Roctx range_run(entry_name[a.entry < 0 ? N_PASS - 1 : a.entry]);
-  HostRun r;
-  hipStream_t st = h->q.stream;
-  // The pass table: what the blocks below do per pass.  A further pass is one more entry here (and its judge above).
-  struct Pass {
-    bool on;
-    size_t n_out, work_bytes;  // doubles of the result, bytes of the workspace
-    double *out;               // the caller's
-    const char *failed;        // prefix of a launch error's text
-    std::function<hipError_t(double *d_out, void *d_work)> launch;
-    DevBuf<double> d_out;
-    DevBuf<uint8_t> d_work;
-  };
-  const double *d_timing_rows = nullptr;  // (the timing pass's device rows, once they are allocated: the values pass reads them)
-  Pass pass[N_PASS] = {
-      {on[PASS_MEASURE], (size_t)ni * (size_t)a.n_req * 8, (size_t)work_bytes, a.meas, "spicey_launch_measure: ", [&](double *d_out, void *d_work) {
-         return spicey_launch_measure(h->device, ni, np, dt, r.d_v, P.nOut, r.d_i, P.nCur, table.data(), a.n_req, d_out, d_work, st);
-       }},
-      {on[PASS_FOURIER], (size_t)ni * (size_t)a.n_four * (size_t)a.four_stride, (size_t)fplan.workspace_bytes(ni), a.four, "spicey_launch_fourier: ",
-       [&](double *d_out, void *d_work) {
-         return spicey_launch_fourier(h->device, ni, np, dt, r.d_v, P.nOut, r.d_i, P.nCur, fplan, d_out, a.four_stride, d_work, st);
-       }},
-      {on[PASS_TIMING], (size_t)ni * (size_t)a.n_tim * 8, (size_t)tplan.workspace_bytes(ni, np), a.timing, "spicey_launch_timing: ", [&](double *d_out, void *d_work) {
-         return spicey_launch_timing(h->device, ni, np, dt, r.d_v, P.nOut, r.d_i, P.nCur, tplan, d_out, d_work, st);
-       }},
-      {on[PASS_SPECTRUM], (size_t)ni * (size_t)a.n_spec * (size_t)a.spec_stride, (size_t)splan.workspace_bytes(), a.spec, "spicey_launch_spectrum: ",
-       [&](double *d_out, void *d_work) {
-         return spicey_launch_spectrum(h->device, ni, np, r.d_v, P.nOut, r.d_i, P.nCur, splan, d_out, a.spec_stride, d_work, st);
-       }},
-      {on[PASS_POWER], (size_t)ni * (size_t)a.n_power * SPICEY_POWER_ROW, on[PASS_POWER] ? (size_t)spicey_pow_workspace_bytes(ni, np, a.n_power) : 0, a.power,
-       "spicey_launch_power: ", [&](double *d_out, void *d_work) {
-         return spicey_launch_power(h->device, ni, np, r.d_v, P.nOut, r.d_i, P.nCur, ptable.data(), a.n_power, d_out, d_work, st);
-       }},
-      {on[PASS_VALUES], (size_t)ni * (size_t)a.n_values * (size_t)a.values_stride, on[PASS_VALUES] ? (size_t)vplan.workspace_bytes(ni) : 0, a.values,
-       "spicey_launch_values: ", [&](double *d_out, void *d_work) {
-         return spicey_launch_values(h->device, ni, np, dt, r.d_v, P.nOut, r.d_i, P.nCur, vplan, a.pts, d_timing_rows, a.n_tim, d_out, a.values_stride, d_work, st);
-       }},
-  };
-  for (int p = 0; p < N_PASS; p++)
-    if (pass[p].on) HIPCHK(h, h->q.want_pass_events(p));
-  // (no current request: the run records no currents)
-  if (const int32_t rc0 = r.stage(h, steps, src_table, src_per_inst, need_i, iters != nullptr); rc0 != SPICEY_OK) return rc0;
-  for (Pass &t : pass) {
-    if (!t.on) continue;
-    HIPCHK(h, t.d_out.alloc(t.n_out));
-    HIPCHK(h, t.d_work.alloc(t.work_bytes));
-  }
-  if (on[PASS_TIMING]) d_timing_rows = pass[PASS_TIMING].d_out;
-  for (double &ms : h->last_pass_ms) ms = 0.0;
-  // (a Monte Carlo run: the draw into scratch value arrays of this call's own, which the transient then reads; they live
-  // until the call returns, so a launch that spicey_sync repeats reads them again)
-  DevBuf<double> d_sR, d_sC, d_sL;
-  DevBuf<uint8_t> d_mc_work;
-  EventPair ev_draw, ev_red;
-  const double *mc_vals[3] = {nullptr, nullptr, nullptr};
-  if (bound) {
-    HIPCHK(h, d_sR.alloc(std::max<size_t>(1, (size_t)ni * (size_t)P.nR)));
-    HIPCHK(h, d_sC.alloc(std::max<size_t>(1, (size_t)ni * (size_t)P.nC)));
-    HIPCHK(h, d_sL.alloc(std::max<size_t>(1, (size_t)ni * (size_t)P.nL)));
-    HIPCHK(h, d_mc_work.alloc((size_t)mc_work_bytes));
-    HIPCHK(h, ev_draw.create());
-    HIPCHK(h, ev_red.create());
-    HIPCHK(h, hipEventRecord(ev_draw.a, st));
-    if (mc) {
-      mcD.R = h->d_R; mcD.C = h->d_C; mcD.L = h->d_L; mcD.oR = d_sR; mcD.oC = d_sC; mcD.oL = d_sL;
-      HIPCHK(h, spicey_launch_tmc_draw(h->device, mcD, mc->tol, mc->icdf, d_mc_work, st));
-    } else {
-      tsD.R = h->d_R; tsD.C = h->d_C; tsD.L = h->d_L; tsD.oR = d_sR; tsD.oC = d_sC; tsD.oL = d_sL;
-      HIPCHK(h, spicey_launch_ts_design(h->device, tsD, ts->act, ts->step, ts->lvl, ts->tol, d_mc_work, st));
-    }
-    HIPCHK(h, hipEventRecord(ev_draw.b, st));
-    mc_vals[0] = d_sR; mc_vals[1] = d_sC; mc_vals[2] = d_sL;
-  }
-  int32_t rc = run_device_src(h, steps, dt, r.d_src, src_per_inst, r.d_v, r.d_i, r.d_it, st, bound ? mc_vals : nullptr);
-  if (rc != SPICEY_OK) return rc;
-  const char *failed = "";
-  auto reduce = [&]() {
-    hipError_t e = hipSuccess;
-    for (int p = 0; p < N_PASS && e == hipSuccess; p++) {
-      Pass &t = pass[p];
-      if (!t.on) continue;
-      failed = t.failed;
-      e = hipEventRecord(h->q.pass_ev[p][0], st);
-      if (e == hipSuccess) e = t.launch(t.d_out, t.d_work);
-      if (e == hipSuccess) e = hipEventRecord(h->q.pass_ev[p][1], st);
-    }
-    return e;
-  };
-  const int retries = h->group_retries;
-  hipError_t e = reduce();
-  rc = spicey_sync(h);  // (the stream's end: the transient's status, with the reductions behind it; also before the buffers go)
-  // (group mode with group_retry: spicey_sync repeated the transient behind the reductions, so the reductions run again)
-  if (e == hipSuccess && h->group_retries != retries && rc == SPICEY_OK && (e = reduce()) == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) { h->err = std::string(failed) + hipGetErrorString(e); return SPICEY_ERR_HIP; }
-  if (rc == SPICEY_OK || rc == SPICEY_ERR_SINGULAR) {
-    for (int p = 0; p < N_PASS; p++)
-      if (pass[p].on) StreamTimers::elapsed(h->q.pass_ev[p][0], h->q.pass_ev[p][1], &h->last_pass_ms[p]);
-    if (mc) {
-      StreamTimers::elapsed(ev_draw.a, ev_draw.b, &h->last_tran_mc_draw_ms);
-      // a sample is valid iff it finished; with none nothing is reduced and the outputs stay as they are
-      std::vector<int32_t> ist((size_t)ni);
-      std::vector<uint8_t> valid((size_t)ni);
-      spicey_last_inst_status(h, ist.data());
-      int32_t n_valid = 0;
-      for (int32_t s = 0; s < ni; s++) n_valid += valid[(size_t)s] = ist[(size_t)s] == 0;
-      if (n_valid > 0) {
-        // (the record was judged before anything ran, on placeholders: the passes' rows take their place)
-        const int row_pass[SPICEY_TMC_N_PASS] = {PASS_MEASURE, PASS_TIMING, PASS_POWER};
-        for (int p = 0; p < SPICEY_TMC_N_PASS; p++) mcA.rows[p] = mcA.n_rows[p] > 0 ? (const double *)pass[row_pass[p]].d_out : nullptr;
-        const size_t n_x = (size_t)ni * (size_t)mc->n_scalar, n_stat = (size_t)mc->n_scalar * (size_t)(SPICEY_TMC_STAT_HEAD + 2 * mc->n_prob);
-        DevBuf<double> d_x, d_stat;
-        DevBuf<int64_t> d_sample;
-        HIPCHK(h, d_x.alloc(n_x));
-        HIPCHK(h, d_stat.alloc(n_stat));
-        HIPCHK(h, d_sample.alloc((size_t)ni * 2));
-        HIPCHK(h, hipEventRecord(ev_red.a, st));
-        HIPCHK(h, spicey_launch_tmc_reduce(h->device, mcA, mc->scalars, n_valid == ni ? nullptr : valid.data(), mc->lo, mc->hi, mc->probs, d_x, d_stat, d_sample,
-                                           d_mc_work, st));
-        HIPCHK(h, hipEventRecord(ev_red.b, st));
-        HIPCHK(h, hipMemcpyAsync(mc->stat, d_stat, n_stat * sizeof(double), hipMemcpyDeviceToHost, st));
-        HIPCHK(h, hipMemcpyAsync(mc->sample, d_sample, (size_t)ni * 2 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-        if (mc->x) HIPCHK(h, hipMemcpyAsync(mc->x, d_x, n_x * sizeof(double), hipMemcpyDeviceToHost, st));
-        HIPCHK(h, hipStreamSynchronize(st));
-        StreamTimers::elapsed(ev_red.a, ev_red.b, &h->last_tran_mc_ms);
-      } else if (rc == SPICEY_OK) {
-        h->err = "tran mc: no valid sample";
-        rc = SPICEY_ERR_SINGULAR;
-      } else h->err += " (tran mc: no valid sample, nothing reduced)";
-    } else if (ts) {
-      StreamTimers::elapsed(ev_draw.a, ev_draw.b, &h->last_tran_sens_design_ms);
-      // an instance is valid iff it finished; a sensitivity needs the nominal instance, a levels run any instance
-      const bool levels = ts->mode == SPICEY_TS_LEVELS;
-      std::vector<int32_t> ist((size_t)ni);
-      std::vector<uint8_t> valid((size_t)ni);
-      spicey_last_inst_status(h, ist.data());
-      int32_t n_valid = 0;
-      for (int32_t s = 0; s < ni; s++) n_valid += valid[(size_t)s] = ist[(size_t)s] == 0;
-      if (levels ? n_valid > 0 : valid[0] != 0) {
-        const int row_pass[SPICEY_TMC_N_PASS] = {PASS_MEASURE, PASS_TIMING, PASS_POWER};
-        for (int p = 0; p < SPICEY_TMC_N_PASS; p++) tsT.rows[p] = tsT.n_rows[p] > 0 ? (const double *)pass[row_pass[p]].d_out : nullptr;
-        const uint8_t *va = n_valid == ni ? nullptr : valid.data();
-        const size_t n_x = (size_t)ni * (size_t)ts->n_scalar, n_el = levels ? 0 : (size_t)ts->n_scalar * (size_t)tsA.nA;
-        DevBuf<double> d_x, d_sens, d_bound;
-        DevBuf<int8_t> d_sign;
-        HIPCHK(h, d_x.alloc(n_x));
-        if (!levels) {
-          HIPCHK(h, d_sens.alloc(2 * n_el));
-          HIPCHK(h, d_sign.alloc(n_el));
-          HIPCHK(h, d_bound.alloc((size_t)ts->n_scalar * SPICEY_TS_BOUND_ROW));
-        }
-        HIPCHK(h, hipEventRecord(ev_red.a, st));
-        if (levels) HIPCHK(h, spicey_launch_tmc_scalars(h->device, tsT, ts->scalars, va, nullptr, nullptr, nullptr, d_x, d_mc_work, st));
-        else HIPCHK(h, spicey_launch_ts_reduce(h->device, tsT, tsA, ts->scalars, va, ts->step, ts_tol_act.data(), d_x, d_sens, d_sign, d_bound, d_mc_work, st));
-        HIPCHK(h, hipEventRecord(ev_red.b, st));
-        if (!levels) {
-          HIPCHK(h, hipMemcpyAsync(ts->sens, d_sens, 2 * n_el * sizeof(double), hipMemcpyDeviceToHost, st));
-          HIPCHK(h, hipMemcpyAsync(ts->sign, d_sign, n_el, hipMemcpyDeviceToHost, st));
-          HIPCHK(h, hipMemcpyAsync(ts->bound, d_bound, (size_t)ts->n_scalar * SPICEY_TS_BOUND_ROW * sizeof(double), hipMemcpyDeviceToHost, st));
-        }
-        if (ts->x) HIPCHK(h, hipMemcpyAsync(ts->x, d_x, n_x * sizeof(double), hipMemcpyDeviceToHost, st));
-        HIPCHK(h, hipStreamSynchronize(st));
-        StreamTimers::elapsed(ev_red.a, ev_red.b, &h->last_tran_sens_ms);
-      } else if (rc == SPICEY_OK) {
-        h->err = levels ? "tran sens: no valid instance" : "tran sens: the nominal instance is not valid";
-        rc = SPICEY_ERR_SINGULAR;
-      } else h->err += levels ? " (tran sens: no valid instance, nothing reduced)" : " (tran sens: the nominal instance is not valid, nothing reduced)";
-    } else {
-      Roctx range_copy("spicey_run_measure:results");
-      for (const Pass &t : pass)
-        if (t.on) HIPCHK(h, hipMemcpy(t.out, t.d_out, t.n_out * sizeof(double), hipMemcpyDeviceToHost));
-    }
-    if (const int32_t rc0 = r.copy_out(h, nullptr, nullptr, iters); rc0 != SPICEY_OK) return rc0;
-  }
-  return rc;
-}
-
-extern "C" int32_t spicey_run_mc(SpiceyHandle *h, int64_t steps, double dt, const double *src_table, int32_t src_per_inst, const SpiceyReducedLists *l,
-                                 const SpiceyTranMcReq *req, const double *tol, const double *icdf, const SpiceyMcScalar *scalars, int32_t n_scalar,
-                                 const double *lo, const double *hi, const double *probs, int32_t n_prob, double *stat, int64_t *sample, double *x,
-                                 int32_t *iters) {
-  if (!h) return SPICEY_ERR_BAD_DESC;
-  const char *what = !l ? "tran mc: lists must not be null"
-                     : l->struct_bytes < (int64_t)sizeof(SpiceyReducedLists) ? "tran mc: lists.struct_bytes is smaller than sizeof(SpiceyReducedLists)"
-                     : l->reserved != 0 ? "tran mc: lists.reserved must be 0" : nullptr;
-  if (what) { forget_last_run(h); h->err = what; return SPICEY_ERR_BAD_DESC; }
-  ReducedLists a{-1, l->reqs, l->n_req, nullptr, l->freqs, l->n_four, nullptr, l->four_stride, l->treqs, l->n_timing, nullptr,
-                 l->sreqs, l->n_spec, nullptr, l->spec_stride, l->preqs, l->n_power, nullptr};
-  a.vreqs = l->vreqs; a.n_values = l->n_values; a.pts = l->pts; a.n_pts = l->n_pts; a.values_stride = l->values_stride;
-  const TranMcCall mc{req, tol, icdf, scalars, n_scalar, lo, hi, probs, n_prob, stat, sample, x};
-  return run_reduced(h, steps, dt, src_table, src_per_inst, a, iters, &mc);
-}
-
-extern "C" double spicey_last_tran_mc_ms(SpiceyHandle *h) { return h ? h->last_tran_mc_ms : 0.0; }
-extern "C" double spicey_last_tran_mc_draw_ms(SpiceyHandle *h) { return h ? h->last_tran_mc_draw_ms : 0.0; }
-
-// The lists of spicey_run_sens / spicey_run_levels, judged as spicey_run_mc's.
-static int32_t run_tran_sens(SpiceyHandle *h, int64_t steps, double dt, const double *src_table, int32_t src_per_inst, const SpiceyReducedLists *l, int32_t *iters,
-                             const TranSensCall &ts) {
-  if (!h) return SPICEY_ERR_BAD_DESC;
-  const char *what = !l ? "tran sens: lists must not be null"
-                     : l->struct_bytes < (int64_t)sizeof(SpiceyReducedLists) ? "tran sens: lists.struct_bytes is smaller than sizeof(SpiceyReducedLists)"
-                     : l->reserved != 0 ? "tran sens: lists.reserved must be 0" : nullptr;
-  if (what) { forget_last_run(h); h->err = what; return SPICEY_ERR_BAD_DESC; }
-  ReducedLists a{-1, l->reqs, l->n_req, nullptr, l->freqs, l->n_four, nullptr, l->four_stride, l->treqs, l->n_timing, nullptr,
-                 l->sreqs, l->n_spec, nullptr, l->spec_stride, l->preqs, l->n_power, nullptr};
-  a.vreqs = l->vreqs; a.n_values = l->n_values; a.pts = l->pts; a.n_pts = l->n_pts; a.values_stride = l->values_stride;
-  return run_reduced(h, steps, dt, src_table, src_per_inst, a, iters, nullptr, &ts);
-}
-
-extern "C" int32_t spicey_run_sens(SpiceyHandle *h, int64_t steps, double dt, const double *src_table, int32_t src_per_inst, const SpiceyReducedLists *l,
-                                   const SpiceyTranSensReq *req, const int32_t *act, const double *step, const double *tol, const SpiceyMcScalar *scalars,
-                                   int32_t n_scalar, double *sens, int8_t *sign, double *bound, double *x, int32_t *iters) {
-  return run_tran_sens(h, steps, dt, src_table, src_per_inst, l, iters, {SPICEY_TS_ONE_AT_A_TIME, req, act, step, nullptr, tol, scalars, n_scalar, sens, sign, bound, x});
-}
-
-extern "C" int32_t spicey_run_levels(SpiceyHandle *h, int64_t steps, double dt, const double *src_table, int32_t src_per_inst, const SpiceyReducedLists *l,
-                                     const SpiceyTranSensReq *req, const int8_t *lvl, const double *tol, const SpiceyMcScalar *scalars, int32_t n_scalar, double *x,
-                                     int32_t *iters) {
-  return run_tran_sens(h, steps, dt, src_table, src_per_inst, l, iters, {SPICEY_TS_LEVELS, req, nullptr, nullptr, lvl, tol, scalars, n_scalar, nullptr, nullptr, nullptr, x});
-}
-
-extern "C" double spicey_last_tran_sens_ms(SpiceyHandle *h) { return h ? h->last_tran_sens_ms : 0.0; }
-extern "C" double spicey_last_tran_sens_design_ms(SpiceyHandle *h) { return h ? h->last_tran_sens_design_ms : 0.0; }
-
-extern "C" int32_t spicey_run_measure(SpiceyHandle *h, int64_t steps, double dt, const double *src_table, int32_t src_per_inst, const SpiceyMeasReq *reqs,
-                                      int32_t n_req, double *meas, int32_t *iters) {
-  return run_reduced(h, steps, dt, src_table, src_per_inst, {0, reqs, n_req, meas, nullptr, 0, nullptr, 0, nullptr, 0, nullptr}, iters);
-}
-
-extern "C" int32_t spicey_run_measure_fourier(SpiceyHandle *h, int64_t steps, double dt, const double *src_table, int32_t src_per_inst, const SpiceyMeasReq *reqs,
-                                              int32_t n_req, double *meas, const SpiceyFourReq *freqs, int32_t n_four, double *four, int32_t four_stride,
-                                              int32_t *iters) {
-  return run_reduced(h, steps, dt, src_table, src_per_inst, {1, reqs, n_req, meas, freqs, n_four, four, four_stride, nullptr, 0, nullptr}, iters);
-}
-
-extern "C" int32_t spicey_run_measure_timing(SpiceyHandle *h, int64_t steps, double dt, const double *src_table, int32_t src_per_inst, const SpiceyMeasReq *reqs,
-                                             int32_t n_req, double *meas, const SpiceyFourReq *freqs, int32_t n_four, double *four, int32_t four_stride,
-                                             const SpiceyTimingReq *treqs, int32_t n_timing, double *timing, int32_t *iters) {
-  return run_reduced(h, steps, dt, src_table, src_per_inst, {2, reqs, n_req, meas, freqs, n_four, four, four_stride, treqs, n_timing, timing}, iters);
-}
-
-extern "C" int32_t spicey_run_measure_spectrum(SpiceyHandle *h, int64_t steps, double dt, const double *src_table, int32_t src_per_inst, const SpiceyMeasReq *reqs,
-                                               int32_t n_req, double *meas, const SpiceyFourReq *freqs, int32_t n_four, double *four, int32_t four_stride,
-                                               const SpiceyTimingReq *treqs, int32_t n_timing, double *timing, const SpiceySpecReq *sreqs, int32_t n_spec, double *spec,
-                                               int32_t spec_stride, int32_t *iters) {
-  return run_reduced(h, steps, dt, src_table, src_per_inst,
-                     {3, reqs, n_req, meas, freqs, n_four, four, four_stride, treqs, n_timing, timing, sreqs, n_spec, spec, spec_stride}, iters);
-}
-
-extern "C" int32_t spicey_run_measure_power(SpiceyHandle *h, int64_t steps, double dt, const double *src_table, int32_t src_per_inst, const SpiceyMeasReq *reqs,
-                                            int32_t n_req, double *meas, const SpiceyFourReq *freqs, int32_t n_four, double *four, int32_t four_stride,
-                                            const SpiceyTimingReq *treqs, int32_t n_timing, double *timing, const SpiceySpecReq *sreqs, int32_t n_spec, double *spec,
-                                            int32_t spec_stride, const SpiceyPowerReq *preqs, int32_t n_power, double *power, int32_t *iters) {
-  return run_reduced(h, steps, dt, src_table, src_per_inst,
-                     {4, reqs, n_req, meas, freqs, n_four, four, four_stride, treqs, n_timing, timing, sreqs, n_spec, spec, spec_stride, preqs, n_power, power}, iters);
-}
-
-extern "C" int32_t spicey_run_reduced(SpiceyHandle *h, int64_t steps, double dt, const double *src_table, int32_t src_per_inst, const SpiceyReducedLists *l,
-                                      int32_t *iters) {
-  if (!h) return SPICEY_ERR_BAD_DESC;
-  const char *what = !l ? "reduced: lists must not be null"
-                     : l->struct_bytes < (int64_t)sizeof(SpiceyReducedLists) ? "reduced: struct_bytes is smaller than sizeof(SpiceyReducedLists)"
-                     : l->reserved != 0 ? "reduced: reserved must be 0" : nullptr;
-  if (what) { forget_last_run(h); h->err = what; return SPICEY_ERR_BAD_DESC; }
-  ReducedLists a{-1, l->reqs, l->n_req, l->meas, l->freqs, l->n_four, l->four, l->four_stride, l->treqs, l->n_timing, l->timing,
-                 l->sreqs, l->n_spec, l->spec, l->spec_stride, l->preqs, l->n_power, l->power};
-  a.vreqs = l->vreqs; a.n_values = l->n_values; a.pts = l->pts; a.n_pts = l->n_pts; a.values = l->values; a.values_stride = l->values_stride;
-  return run_reduced(h, steps, dt, src_table, src_per_inst, a, iters);
-}
-
-extern "C" double spicey_last_measure_ms(SpiceyHandle *h) { return h ? h->last_pass_ms[PASS_MEASURE] : 0.0; }
-extern "C" double spicey_last_fourier_ms(SpiceyHandle *h) { return h ? h->last_pass_ms[PASS_FOURIER] : 0.0; }
-extern "C" double spicey_last_timing_ms(SpiceyHandle *h) { return h ? h->last_pass_ms[PASS_TIMING] : 0.0; }
-extern "C" double spicey_last_spectrum_ms(SpiceyHandle *h) { return h ? h->last_pass_ms[PASS_SPECTRUM] : 0.0; }
-extern "C" double spicey_last_power_ms(SpiceyHandle *h) { return h ? h->last_pass_ms[PASS_POWER] : 0.0; }
-extern "C" double spicey_last_values_ms(SpiceyHandle *h) { return h ? h->last_pass_ms[PASS_VALUES] : 0.0; }
-
-// Edge timing (include/spicey_hip.h): the reduction of timing.hip on any device buffers, no handle.
-extern "C" int64_t spicey_timing_workspace_bytes(int32_t n_inst, int64_t n_points, const SpiceyTimingReq *reqs, int32_t n_req) {
-  return spicey_tim_workspace_bytes(n_inst, n_points, reqs, n_req);
-}
-
-extern "C" int32_t spicey_timing_device(int32_t device, int32_t n_inst, int64_t n_points, double dt, const double *d_v, int32_t n_v, const double *d_i,
-                                        int32_t n_i, const SpiceyTimingReq *reqs, int32_t n_req, double *d_out, void *d_work, int64_t work_bytes,
-                                        void *stream) {
-  // (the call is judged before the device is touched: a refusal launches nothing)
-  SpiceyTimPlan plan;
-  if (!spicey_tim_judge(n_inst, n_points, dt, d_v != nullptr, n_v, d_i != nullptr, n_i, reqs, n_req, d_out && d_work, work_bytes, plan, g_err))
-    return SPICEY_ERR_BAD_DESC;
-  return launch_on_device(device, "spicey_launch_timing", [&]() {
-    return spicey_launch_timing(device, n_inst, n_points, dt, d_v, n_v, d_i, n_i, plan, d_out, d_work, (hipStream_t)stream);
-  });
-}
-
-// Spectrum (include/spicey_hip.h): the FFT pass of spectrum.hip on any device buffers, no handle.
-extern "C" int64_t spicey_spectrum_workspace_bytes(int32_t n_inst, int64_t n_points, const SpiceySpecReq *reqs, int32_t n_req) {
-  return spicey_spec_workspace_bytes(n_inst, n_points, reqs, n_req);
-}
-
-extern "C" int32_t spicey_spectrum_device(int32_t device, int32_t n_inst, int64_t n_points, double dt, const double *d_v, int32_t n_v, const double *d_i,
-                                          int32_t n_i, const SpiceySpecReq *reqs, int32_t n_req, double *d_out, int32_t out_stride, void *d_work,
-                                          int64_t work_bytes, void *stream) {
-  // (the call is judged before the device is touched: a refusal launches nothing)
-  SpiceySpecPlan plan;
-  if (!spicey_spec_judge(n_inst, n_points, dt, d_v != nullptr, n_v, d_i != nullptr, n_i, reqs, n_req, d_out && d_work, out_stride, work_bytes, plan, g_err))
-    return SPICEY_ERR_BAD_DESC;
-  return launch_on_device(device, "spicey_launch_spectrum", [&]() {
-    return spicey_launch_spectrum(device, n_inst, n_points, d_v, n_v, d_i, n_i, plan, d_out, out_stride, d_work, (hipStream_t)stream);
-  });
-}
-
-// Products of two signals (include/spicey_hip.h): the reduction of power.hip on any device buffers, no handle.
-extern "C" int64_t spicey_power_workspace_bytes(int32_t n_inst, int64_t n_points, int32_t n_req) {
-  return spicey_pow_workspace_bytes(n_inst, n_points, n_req);
-}
-
-extern "C" int32_t spicey_power_device(int32_t device, int32_t n_inst, int64_t n_points, double dt, const double *d_v, int32_t n_v, const double *d_i,
-                                       int32_t n_i, const SpiceyPowerReq *reqs, int32_t n_req, double *d_out, void *d_work, int64_t work_bytes,
-                                       void *stream) {
-  // (the call is judged before the device is touched: a refusal launches nothing)
-  std::vector<SpiceyPowerDevReq> table;
-  if (!spicey_power_judge(n_inst, n_points, dt, d_v != nullptr, n_v, d_i != nullptr, n_i, reqs, n_req, d_out && d_work, work_bytes, table, g_err))
-    return SPICEY_ERR_BAD_DESC;
-  return launch_on_device(device, "spicey_launch_power", [&]() {
-    return spicey_launch_power(device, n_inst, n_points, d_v, n_v, d_i, n_i, table.data(), n_req, d_out, d_work, (hipStream_t)stream);
-  });
-}
-
-// Waveform values (include/spicey_hip.h): the pass of values.hip on any device buffers, no handle.
-extern "C" int64_t spicey_values_workspace_bytes(int32_t n_inst, int64_t n_points, const SpiceyValReq *reqs, int32_t n_req, int64_t n_pts) {
-  return spicey_val_workspace_bytes(n_inst, n_points, reqs, n_req, n_pts);
-}
-
-extern "C" int32_t spicey_values_device(int32_t device, int32_t n_inst, int64_t n_points, double dt, const double *d_v, int32_t n_v, const double *d_i,
-                                        int32_t n_i, const SpiceyValReq *reqs, int32_t n_req, const SpiceyValPoint *pts, int64_t n_pts, const double *d_timing,
-                                        int32_t n_timing, double *d_out, int32_t out_stride, void *d_work, int64_t work_bytes, void *stream) {
-  // (the call is judged before the device is touched: a refusal launches nothing)
-  SpiceyValPlan plan;
-  if (!spicey_val_judge(n_inst, n_points, dt, d_v != nullptr, n_v, d_i != nullptr, n_i, reqs, n_req, pts, n_pts, d_timing != nullptr, n_timing, d_out && d_work,
-                        out_stride, work_bytes, plan, g_err))
-    return SPICEY_ERR_BAD_DESC;
-  return launch_on_device(device, "spicey_launch_values", [&]() {
-    return spicey_launch_values(device, n_inst, n_points, dt, d_v, n_v, d_i, n_i, plan, pts, d_timing, n_timing, d_out, out_stride, d_work, (hipStream_t)stream);
-  });
-}
-
-// Harmonics (include/spicey_hip.h): the reduction of fourier.hip on any device buffers, no handle.
-extern "C" int64_t spicey_fourier_workspace_bytes(int32_t n_inst, int64_t n_points, const SpiceyFourReq *reqs, int32_t n_req) {
-  return spicey_four_workspace_bytes(n_inst, n_points, reqs, n_req);
-}
-
-extern "C" int32_t spicey_fourier_device(int32_t device, int32_t n_inst, int64_t n_points, double dt, const double *d_v, int32_t n_v, const double *d_i,
-                                         int32_t n_i, const SpiceyFourReq *reqs, int32_t n_req, double *d_out, int32_t out_stride, void *d_work,
-                                         int64_t work_bytes, void *stream) {
-  // (the call is judged before the device is touched: a refusal launches nothing)
-  SpiceyFourPlan plan;
-  if (!spicey_four_judge(n_inst, n_points, dt, d_v != nullptr, n_v, d_i != nullptr, n_i, reqs, n_req, d_out && d_work, out_stride, work_bytes, plan, g_err))
-    return SPICEY_ERR_BAD_DESC;
-  return launch_on_device(device, "spicey_launch_fourier", [&]() {
-    return spicey_launch_fourier(device, n_inst, n_points, dt, d_v, n_v, d_i, n_i, plan, d_out, out_stride, d_work, (hipStream_t)stream);
-  });
-}
-
-// The same for an AC sweep's complex buffers (include/spicey_hip.h): the reduction of ac_measure.hip, no handle.
-extern "C" int64_t spicey_ac_measure_workspace_bytes(int32_t n_inst, int64_t n_freq, int32_t n_req) {
-  return spicey_acm_workspace_bytes(n_inst, n_freq, n_req);
-}
-
-extern "C" int32_t spicey_ac_measure_device(int32_t device, int32_t n_inst, int64_t n_freq, const double *d_v, int32_t n_v, const double *d_i, int32_t n_i,
-                                            const SpiceyAcMeasReq *reqs, int32_t n_req, double *d_meas, void *d_work, int64_t work_bytes, void *stream) {
-  // (the call is judged before the device is touched: a refusal launches nothing)
-  std::vector<SpiceyAcMeasDevReq> table;
-  if (const int32_t rc = spicey_judge_measure("ac measure", spicey_acm_plan, spicey_acm_workspace_bytes, n_inst, n_freq, d_v != nullptr, n_v, d_i != nullptr, n_i, reqs,
-                                              n_req, d_meas && d_work, work_bytes, table, g_err); rc != SPICEY_OK)
-    return rc;
-  return launch_on_device(device, "spicey_launch_ac_measure", [&]() {
-    return spicey_launch_ac_measure(device, n_inst, n_freq, d_v, n_v, d_i, n_i, table.data(), n_req, d_meas, d_work, (hipStream_t)stream);
-  });
-}
-
-// Thermal noise of an injected AC sweep (include/spicey_hip.h): the reduction of noise.hip on any device buffers, no handle.
-extern "C" int64_t spicey_ac_noise_workspace_bytes(int32_t n_inst, int64_t n_freq, int32_t nR) { return spicey_noise_workspace_bytes(n_inst, n_freq, nR); }
-
-extern "C" int32_t spicey_ac_noise_device(int32_t device, int32_t n_inst, int64_t n_freq, const double *d_v, int32_t n_v, const double *d_i, int32_t n_i,
-                                          const double *d_R, int32_t nR, const double *d_freqs, const SpiceyAcNoiseReq *req, double *d_spec, double *d_contrib,
-                                          double *d_total, void *d_work, int64_t work_bytes, void *stream) {
-  // (the call is judged before the device is touched: a refusal launches nothing)
-  SpiceyNoiseArgs A;
-  if (!spicey_noise_judge(n_inst, n_freq, d_v, n_v, d_i, n_i, d_R, nR, d_freqs, req, d_spec && d_contrib && d_total && d_work, work_bytes, A, g_err))
-    return SPICEY_ERR_BAD_DESC;
-  return launch_on_device(device, "spicey_launch_noise", [&]() { return spicey_launch_noise(device, A, d_spec, d_contrib, d_total, d_work, (hipStream_t)stream); });
-}
-
-// AC sensitivities of a direct and an adjoint sweep (include/spicey_hip.h): the reduction of sens.hip on any device buffers, no
-// handle.  tol is a HOST array: judged here, uploaded through the workspace.
-extern "C" int64_t spicey_ac_sens_workspace_bytes(int32_t n_inst, int64_t n_freq, int32_t nE) { return spicey_sens_workspace_bytes(n_inst, n_freq, nE); }
-
-extern "C" int32_t spicey_ac_sens_device(int32_t device, int32_t n_inst, int64_t n_freq, const double *d_v_dir, int32_t n_v, const double *d_i_dir,
-                                         const double *d_i_adj, int32_t n_i, const double *d_R, const double *d_C, const double *d_L, const double *tol,
-                                         const double *d_freqs, const SpiceyAcSensReq *req, double *d_spec, double *d_peak, double *d_full, void *d_work,
-                                         int64_t work_bytes, void *stream) {
-  // (the call is judged before the device is touched: a refusal launches nothing)
-  SpiceySensArgs A;
-  if (!spicey_sens_judge(n_inst, n_freq, d_v_dir, n_v, d_i_dir, d_i_adj, n_i, d_R, d_C, d_L, tol, d_freqs, req, d_spec && d_peak && d_work, work_bytes, A, g_err))
-    return SPICEY_ERR_BAD_DESC;
-  return launch_on_device(device, "spicey_launch_sens", [&]() { return spicey_launch_sens(device, A, tol, d_spec, d_peak, d_full, d_work, (hipStream_t)stream); });
-}
-
-extern "C" int64_t spicey_ac_mc_workspace_bytes(int32_t n_inst, int64_t n_freq, int32_t nE, int32_t log2K, int32_t n_rank) {
-  return spicey_mc_workspace_bytes(n_inst, n_freq, nE, log2K, n_rank);
-}
-
-extern "C" int32_t spicey_ac_mc_draw_device(int32_t device, int32_t n_inst, int32_t nR, int32_t nC, int32_t nL, const double *d_R, const double *d_C,
-                                            const double *d_L, const double *tol, const double *icdf, const SpiceyAcMcReq *req, double *d_Rinv_out,
-                                            double *d_C_out, double *d_L_out, void *d_work, int64_t work_bytes, void *stream) {
-  // (the call is judged before the device is touched: a refusal launches nothing)
-  SpiceyMcDrawArgs A;
-  if (!spicey_mc_draw_judge(n_inst, nR, nC, nL, d_R, d_C, d_L, tol, icdf, req, d_Rinv_out, d_C_out, d_L_out, d_work != nullptr, work_bytes, A, g_err))
-    return SPICEY_ERR_BAD_DESC;
-  return launch_on_device(device, "spicey_launch_mc_draw", [&]() { return spicey_launch_mc_draw(device, A, tol, icdf, d_work, (hipStream_t)stream); });
-}
-
-extern "C" int32_t spicey_ac_mc_reduce_device(int32_t device, int32_t n_inst, int64_t n_freq, const double *d_v, int32_t n_v, const uint8_t *valid,
-                                              const double *lo, const double *hi, const int64_t *ranks, int32_t n_rank, const SpiceyAcMcReq *req,
-                                              int64_t *d_sample, double *d_freq, void *d_work, int64_t work_bytes, void *stream) {
-  SpiceyMcReduceArgs A;
-  if (!spicey_mc_reduce_judge(n_inst, n_freq, d_v, n_v, valid, ranks, n_rank, req, d_sample && d_freq && d_work, work_bytes, A, g_err))
-    return SPICEY_ERR_BAD_DESC;
-  return launch_on_device(device, "spicey_launch_mc_reduce",
-                          [&]() { return spicey_launch_mc_reduce(device, A, valid, lo, hi, ranks, d_sample, d_freq, d_work, (hipStream_t)stream); });
-}
-
-// Monte Carlo of transient runs (include/spicey_hip.h): the draw and the reduction of tran_mc.hip on any device buffers, no handle.
-extern "C" int64_t spicey_tran_mc_workspace_bytes(int32_t n_inst, int32_t n_scalar, int32_t nE, int32_t log2K, int32_t n_prob) {
-  return spicey_tmc_workspace_bytes(n_inst, n_scalar, nE, log2K, n_prob);
-}
-
-extern "C" int32_t spicey_tran_mc_draw_device(int32_t device, int32_t n_inst, int32_t nR, int32_t nC, int32_t nL, const double *d_R, const double *d_C,
-                                              const double *d_L, const double *tol, const double *icdf, const SpiceyTranMcReq *req, double *d_R_out,
-                                              double *d_C_out, double *d_L_out, void *d_work, int64_t work_bytes, void *stream) {
-  // (the call is judged before the device is touched: a refusal launches nothing)
-  SpiceyMcDrawArgs A;
-  if (!spicey_tmc_draw_judge(n_inst, nR, nC, nL, d_R, d_C, d_L, tol, icdf, req, d_R_out, d_C_out, d_L_out, d_work != nullptr, work_bytes, A, g_err))
-    return SPICEY_ERR_BAD_DESC;
-  return launch_on_device(device, "spicey_launch_tmc_draw", [&]() { return spicey_launch_tmc_draw(device, A, tol, icdf, d_work, (hipStream_t)stream); });
-}
-
-extern "C" int32_t spicey_tran_mc_reduce_device(int32_t device, int32_t n_inst, const SpiceyMcRows *rows, const SpiceyMcScalar *scalars, int32_t n_scalar,
-                                                const uint8_t *valid, const double *lo, const double *hi, const double *probs, int32_t n_prob, double *d_x,
-                                                double *d_stat, int64_t *d_sample, void *d_work, int64_t work_bytes, void *stream) {
-  SpiceyTmcArgs A;
-  if (!spicey_tmc_reduce_judge(n_inst, rows, scalars, n_scalar, lo, hi, probs, n_prob, d_x && d_stat && d_sample && d_work, work_bytes, A, g_err))
-    return SPICEY_ERR_BAD_DESC;
-  return launch_on_device(device, "spicey_launch_tmc_reduce", [&]() {
-    return spicey_launch_tmc_reduce(device, A, scalars, valid, lo, hi, probs, d_x, d_stat, d_sample, d_work, (hipStream_t)stream);
-  });
-}
-
-// Sensitivities and corners of transient measurements (include/spicey_hip.h): the design and the reduction of tran_sens.hip on any
-// device buffers, no handle.
-extern "C" int64_t spicey_tran_sens_workspace_bytes(int32_t n_inst, int32_t n_scalar, int32_t nE, int32_t nA) {
-  return spicey_ts_workspace_bytes(n_inst, n_scalar, nE, nA);
-}
-
-extern "C" int32_t spicey_tran_sens_design_device(int32_t device, int32_t n_inst, int32_t nR, int32_t nC, int32_t nL, const double *d_R, const double *d_C,
-                                                  const double *d_L, const SpiceyTranSensReq *req, const int32_t *act, const double *step, const int8_t *lvl,
-                                                  const double *tol, double *d_R_out, double *d_C_out, double *d_L_out, void *d_work, int64_t work_bytes,
-                                                  void *stream) {
-  SpiceyTsDesignArgs A;
-  if (!spicey_ts_design_judge(n_inst, nR, nC, nL, d_R, d_C, d_L, req, -1, act, step, lvl, tol, d_R_out, d_C_out, d_L_out, d_work != nullptr, work_bytes, A, g_err))
-    return SPICEY_ERR_BAD_DESC;
-  return launch_on_device(device, "spicey_launch_ts_design", [&]() { return spicey_launch_ts_design(device, A, act, step, lvl, tol, d_work, (hipStream_t)stream); });
-}
-
-extern "C" int32_t spicey_tran_sens_reduce_device(int32_t device, int32_t n_inst, const SpiceyMcRows *rows, const SpiceyMcScalar *scalars, int32_t n_scalar,
-                                                  const uint8_t *valid, const double *step, const double *tol_act, int32_t nA, double *d_x, double *d_sens,
-                                                  int8_t *d_sign, double *d_bound, void *d_work, int64_t work_bytes, void *stream) {
-  SpiceyTmcArgs T;
-  SpiceyTsReduceArgs A;
-  if (!spicey_ts_reduce_judge(n_inst, rows, scalars, n_scalar, step, tol_act, nA, d_x && d_sens && d_sign && d_bound && d_work, work_bytes, T, A, g_err))
-    return SPICEY_ERR_BAD_DESC;
-  return launch_on_device(device, "spicey_launch_ts_reduce", [&]() {
-    return spicey_launch_ts_reduce(device, T, A, scalars, valid, step, tol_act, d_x, d_sens, d_sign, d_bound, d_work, (hipStream_t)stream);
-  });
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
 // Several devices behind one handle: instance shards, one SpiceyHandle per shard, host threads around the blocking runs.
-#include <thread>
-
 struct SpiceyMulti {
   struct Shard { SpiceyHandle *h = nullptr; int device = 0, first = 0, count = 0; };
   std::vector<Shard> shards;

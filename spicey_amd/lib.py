@@ -487,6 +487,27 @@ def values_device(n_inst: int, n_points: int, dt: float, d_v: int, n_v: int, d_i
         _fail("spicey_values_device", rc, L.spicey_last_error(None))
 
 
+# The reduction passes behind a transient run, in the order they run: result key, list and count field of abi.SpiceyReducedLists,
+# record dtype, doubles of a result row (a number, or the rule over the list's records), key and function of the pass's time.
+_PASSES = (
+    ("meas", "reqs", "n_req", abi.MEAS_REQ_DTYPE, 8, "measure_ms", "spicey_last_measure_ms"),
+    ("four", "freqs", "n_four", abi.FOUR_REQ_DTYPE, fourier_row_doubles, "fourier_ms", "spicey_last_fourier_ms"),
+    ("timing", "treqs", "n_timing", abi.TIMING_REQ_DTYPE, 8, "timing_ms", "spicey_last_timing_ms"),
+    ("spec", "sreqs", "n_spec", abi.SPEC_REQ_DTYPE, abi.spec_row_doubles, "spectrum_ms", "spicey_last_spectrum_ms"),
+    ("power", "preqs", "n_power", abi.POWER_REQ_DTYPE, abi.POWER_ROW, "power_ms", "spicey_last_power_ms"),
+    ("values", "vreqs", "n_values", abi.VAL_REQ_DTYPE, abi.val_row_doubles, "values_ms", "spicey_last_values_ms"),
+)
+_PASS_MS = tuple(p[5:] for p in _PASSES)
+_MC_MS = (("mc_ms", "spicey_last_tran_mc_ms"), ("draw_ms", "spicey_last_tran_mc_draw_ms"))
+_SENS_MS = (("sens_ms", "spicey_last_tran_sens_ms"), ("design_ms", "spicey_last_tran_sens_design_ms"))
+
+
+def _pass_list(r, dtype, row):
+    """A pass's request list as records of `dtype`, and the doubles of its result row."""
+    r = _reqs(r if len(r) else [], dtype)
+    return r, row(r) if callable(row) else row
+
+
 class Handle:
     """Owns one SpiceyHandle (one topology, n_inst instances, one device)."""
 
@@ -581,39 +602,59 @@ class Handle:
                 res["lin_err"] = le
         return res
 
+    def _reduced_lists(self, reqs, freqs, treqs, sreqs, preqs, vreqs, pts=(), outs=None, struct_bytes=None):
+        """(the filled abi.SpiceyReducedLists, the arrays to keep alive, the row lengths by result key).  outs: None (a study takes no
+        result pointers), or the dict that gets one zeroed result array per list, which the struct points to where the list is not
+        empty."""
+        a = abi.SpiceyReducedLists()
+        a.struct_bytes = C.sizeof(a) if struct_bytes is None else struct_bytes
+        keep, rows = {"pts": _reqs(pts if len(pts) else [], abi.VAL_POINT_DTYPE)}, {}
+        for (key, lst, cnt, dtype, row, _, _), r in zip(_PASSES, (reqs, freqs, treqs, sreqs, preqs, vreqs)):
+            keep[key], rows[key] = _pass_list(r, dtype, row)
+            setattr(a, lst, _reqs_ptr(keep[key]))
+            setattr(a, cnt, len(keep[key]))
+            if outs is not None:
+                outs[key] = np.zeros((self.flat.n_inst, len(keep[key]), rows[key]))
+                setattr(a, key, outs[key].ctypes.data if len(keep[key]) else None)
+        a.four_stride, a.spec_stride, a.values_stride = rows["four"], rows["spec"], rows["values"]
+        a.pts, a.n_pts = _reqs_ptr(keep["pts"]), len(keep["pts"])
+        return a, keep, rows
+
+    def _prologue(self, steps: int, src: np.ndarray, want_iters: bool):
+        """What every reduced run starts from: (src as one contiguous array, src_per_inst, the iters array or None)."""
+        src = np.ascontiguousarray(src, dtype=np.float64)
+        per_inst = _src_layout(src, self.flat, steps)
+        return src, 1 if per_inst else 0, np.zeros((self.flat.n_inst, steps + 1), np.int32) if want_iters else None
+
+    def _epilogue(self, res: dict, rc: int, iters, ms) -> dict:
+        """What every reduced run ends with: status, detail, iters and `partial` into res; after a run that was kept (OK or
+        singular) the time readouts `ms` ((result key, function), ...); the dressing."""
+        res.update(status=rc, detail=self.error() if rc != abi.OK else "", iters=iters, partial=True)
+        kept = rc in (abi.OK, abi.ERR_SINGULAR)
+        if kept:
+            for key, fn in ms:
+                res[key] = getattr(self.L, fn)(self.h)
+        return self._dress(res, rc, kept, kept)
+
     def _run_reduced(self, entry: int, steps: int, dt: float, src: np.ndarray, reqs, freqs, treqs, want_iters: bool, sreqs=None, preqs=None) -> dict:
         """What run_measure (entry 0), run_measure_fourier (1), run_measure_timing (2), run_measure_spectrum (3) and
         run_measure_power (4) share: the result arrays of the passes that entry has — an empty list of an earlier pass goes
         down as a null out pointer — its C function, and the dressing."""
-        f = self.flat
-        src = np.ascontiguousarray(src, dtype=np.float64)
-        per_inst = _src_layout(src, f, steps)
-        fr = _reqs(freqs, abi.FOUR_REQ_DTYPE)
-        stride = fourier_row_doubles(fr)
-        # per pass: result key, request list, row length
-        sr = _reqs([] if sreqs is None else sreqs, abi.SPEC_REQ_DTYPE)
-        strides = {"four": stride, "spec": abi.spec_row_doubles(sr)}
-        passes = [("meas", _reqs(reqs), 8), ("four", fr, stride), ("timing", _reqs(treqs, abi.TIMING_REQ_DTYPE), 8), ("spec", sr, strides["spec"]),
-                  ("power", _reqs([] if preqs is None else preqs, abi.POWER_REQ_DTYPE), abi.POWER_ROW)][:entry + 1]
+        src, per_inst, iters = self._prologue(steps, src, want_iters)
         res = {"status": 0, "detail": ""}
-        args = []
-        for k, (key, r, row) in enumerate(passes):
-            res[key] = np.zeros((f.n_inst, len(r), row))
+        args, keep = [], []
+        lists = (reqs, freqs, treqs, [] if sreqs is None else sreqs, [] if preqs is None else preqs)
+        for k, ((key, _, _, dtype, row, _, _), r) in enumerate(zip(_PASSES[:entry + 1], lists)):
+            r, n_row = _pass_list(r, dtype, row)
+            keep.append(r)
+            res[key] = np.zeros((self.flat.n_inst, len(r), n_row))
             args += [_reqs_ptr(r), len(r), _p(res[key], C.c_double) if len(r) or k == entry else None]
-            if key in strides:
-                args.append(strides[key])
-        iters = np.zeros((f.n_inst, steps + 1), np.int32) if want_iters else None
+            if callable(row):
+                args.append(n_row)
         fn = (self.L.spicey_run_measure, self.L.spicey_run_measure_fourier, self.L.spicey_run_measure_timing, self.L.spicey_run_measure_spectrum,
               self.L.spicey_run_measure_power)[entry]
-        rc = fn(self.h, steps, dt, _p(src, C.c_double), 1 if per_inst else 0, *args, _p(iters, C.c_int32))
-        res.update(status=rc, detail=self.error() if rc != abi.OK else "", iters=iters, partial=True)
-        kept = rc in (abi.OK, abi.ERR_SINGULAR)
-        if kept:
-            for key, last_ms in (("measure_ms", self.L.spicey_last_measure_ms), ("fourier_ms", self.L.spicey_last_fourier_ms),
-                                 ("timing_ms", self.L.spicey_last_timing_ms), ("spectrum_ms", self.L.spicey_last_spectrum_ms),
-                                 ("power_ms", self.L.spicey_last_power_ms))[:entry + 1]:
-                res[key] = last_ms(self.h)
-        return self._dress(res, rc, kept, kept)
+        rc = fn(self.h, steps, dt, _p(src, C.c_double), per_inst, *args, _p(iters, C.c_int32))
+        return self._epilogue(res, rc, iters, _PASS_MS[:entry + 1])
 
     def run_measure(self, steps: int, dt: float, src: np.ndarray, reqs, want_iters: bool = True) -> dict:
         """spicey_run_measure: the transient with its waveforms kept on the device and reduced there; only `meas`
@@ -661,37 +702,12 @@ class Handle:
         returns for the passes that ran (`meas`, `four`, `timing`, `spec`, `power` are there for every list, [n_inst][0][row]
         for an empty one) plus `values` [n_inst][n_values][abi.val_row_doubles(vreqs)] and `values_ms`.  struct_bytes: the
         size the struct claims (tests)."""
-        f = self.flat
-        src = np.ascontiguousarray(src, dtype=np.float64)
-        per_inst = _src_layout(src, f, steps)
-        lists = {key: _reqs(r if len(r) else [], dtype) for key, r, dtype in (
-            ("meas", reqs, abi.MEAS_REQ_DTYPE), ("four", freqs, abi.FOUR_REQ_DTYPE), ("timing", treqs, abi.TIMING_REQ_DTYPE), ("spec", sreqs, abi.SPEC_REQ_DTYPE),
-            ("power", preqs, abi.POWER_REQ_DTYPE), ("values", vreqs, abi.VAL_REQ_DTYPE))}
-        pt = _reqs(pts if len(pts) else [], abi.VAL_POINT_DTYPE)
-        rows = {"meas": 8, "four": fourier_row_doubles(lists["four"]), "timing": 8, "spec": abi.spec_row_doubles(lists["spec"]), "power": abi.POWER_ROW,
-                "values": abi.val_row_doubles(lists["values"])}
+        src, per_inst, iters = self._prologue(steps, src, want_iters)
         res = {"status": 0, "detail": ""}
-        for key, r in lists.items():
-            res[key] = np.zeros((f.n_inst, len(r), rows[key]))
-        a = abi.SpiceyReducedLists()
-        a.struct_bytes = C.sizeof(a) if struct_bytes is None else struct_bytes
-        for key, lst, cnt in (("meas", "reqs", "n_req"), ("four", "freqs", "n_four"), ("timing", "treqs", "n_timing"), ("spec", "sreqs", "n_spec"),
-                              ("power", "preqs", "n_power"), ("values", "vreqs", "n_values")):
-            setattr(a, lst, _reqs_ptr(lists[key]))
-            setattr(a, cnt, len(lists[key]))
-            setattr(a, key, res[key].ctypes.data if len(lists[key]) else None)
-        a.four_stride, a.spec_stride, a.values_stride = rows["four"], rows["spec"], rows["values"]
-        a.pts, a.n_pts = _reqs_ptr(pt), len(pt)
-        iters = np.zeros((f.n_inst, steps + 1), np.int32) if want_iters else None
-        rc = self.L.spicey_run_reduced(self.h, steps, dt, _p(src, C.c_double), 1 if per_inst else 0, C.byref(a), _p(iters, C.c_int32))
-        res.update(status=rc, detail=self.error() if rc != abi.OK else "", iters=iters, partial=True)
-        kept = rc in (abi.OK, abi.ERR_SINGULAR)
-        if kept:
-            for key, last_ms in (("measure_ms", self.L.spicey_last_measure_ms), ("fourier_ms", self.L.spicey_last_fourier_ms),
-                                 ("timing_ms", self.L.spicey_last_timing_ms), ("spectrum_ms", self.L.spicey_last_spectrum_ms),
-                                 ("power_ms", self.L.spicey_last_power_ms), ("values_ms", self.L.spicey_last_values_ms)):
-                res[key] = last_ms(self.h)
-        return self._dress(res, rc, kept, kept)
+        a, keep, _ = self._reduced_lists(reqs, freqs, treqs, sreqs, preqs, vreqs, pts, res, struct_bytes)
+        rc = self.L.spicey_run_reduced(self.h, steps, dt, _p(src, C.c_double), per_inst, C.byref(a), _p(iters, C.c_int32))
+        del keep
+        return self._epilogue(res, rc, iters, _PASS_MS)
 
     def run_mc(self, steps: int, dt: float, src: np.ndarray, req: abi.SpiceyTranMcReq, tol, icdf, scalars, lo=None, hi=None, probs=(), reqs=(), treqs=(),
                preqs=(), freqs=(), sreqs=(), vreqs=(), want_x: bool = False, want_iters: bool = False) -> dict:
@@ -702,48 +718,20 @@ class Handle:
         Returns `stat` [n_scalar][8 + 2 n_prob] and `sample` [n_inst][2] (include/spicey_hip.h), `x` [n_inst][n_scalar] with
         want_x, `inst_status`, `state`, `mc_ms`, `draw_ms`.  freqs / sreqs / vreqs are there to be refused."""
         f = self.flat
-        src = np.ascontiguousarray(src, dtype=np.float64)
-        per_inst = _src_layout(src, f, steps)
-        lists = {key: _reqs(r if len(r) else [], dtype) for key, r, dtype in (
-            ("meas", reqs, abi.MEAS_REQ_DTYPE), ("four", freqs, abi.FOUR_REQ_DTYPE), ("timing", treqs, abi.TIMING_REQ_DTYPE), ("spec", sreqs, abi.SPEC_REQ_DTYPE),
-            ("power", preqs, abi.POWER_REQ_DTYPE), ("values", vreqs, abi.VAL_REQ_DTYPE))}
-        a = abi.SpiceyReducedLists()
-        a.struct_bytes = C.sizeof(a)
-        for key, lst, cnt in (("meas", "reqs", "n_req"), ("four", "freqs", "n_four"), ("timing", "treqs", "n_timing"), ("spec", "sreqs", "n_spec"),
-                              ("power", "preqs", "n_power"), ("values", "vreqs", "n_values")):
-            setattr(a, lst, _reqs_ptr(lists[key]))
-            setattr(a, cnt, len(lists[key]))
-        a.four_stride, a.spec_stride, a.values_stride = fourier_row_doubles(lists["four"]), abi.spec_row_doubles(lists["spec"]), abi.val_row_doubles(lists["values"])
+        src, per_inst, iters = self._prologue(steps, src, want_iters)
+        a, keep, _ = self._reduced_lists(reqs, freqs, treqs, sreqs, preqs, vreqs)
         sc = _scalars(scalars)
         t, tab = _host(tol, np.float64), _host(icdf, np.float64)
         lo_, hi_, pr = _host(lo, np.float64), _host(hi, np.float64), np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
         stat = np.zeros((len(sc), abi.TRAN_MC_STAT_HEAD + 2 * len(pr)))
         sample = np.full((f.n_inst, 2), -1, np.int64)
         x = np.full((f.n_inst, len(sc)), np.nan) if want_x else None
-        iters = np.zeros((f.n_inst, steps + 1), np.int32) if want_iters else None
-        rc = self.L.spicey_run_mc(self.h, steps, dt, _p(src, C.c_double), 1 if per_inst else 0, C.addressof(a), C.addressof(req) if req is not None else None,
+        rc = self.L.spicey_run_mc(self.h, steps, dt, _p(src, C.c_double), per_inst, C.addressof(a), C.addressof(req) if req is not None else None,
                                   _p(t, C.c_double), _p(tab, C.c_double), sc.ctypes.data if len(sc) else None, len(sc), _p(lo_, C.c_double), _p(hi_, C.c_double),
                                   _p(pr, C.c_double) if len(pr) else None, len(pr), _p(stat, C.c_double), _p(sample, C.c_int64), _p(x, C.c_double),
                                   _p(iters, C.c_int32))
-        res = {"status": rc, "detail": self.error() if rc != abi.OK else "", "stat": stat, "sample": sample, "x": x, "iters": iters, "partial": True}
-        kept = rc in (abi.OK, abi.ERR_SINGULAR)
-        if kept:
-            res["mc_ms"], res["draw_ms"] = self.L.spicey_last_tran_mc_ms(self.h), self.L.spicey_last_tran_mc_draw_ms(self.h)
-        return self._dress(res, rc, kept, kept)
-
-    def _mc_lists(self, reqs, treqs, preqs, freqs=(), sreqs=(), vreqs=()):
-        """(abi.SpiceyReducedLists without result pointers, the arrays kept alive) as spicey_run_sens / spicey_run_levels take it."""
-        lists = {key: _reqs(r if len(r) else [], dtype) for key, r, dtype in (
-            ("meas", reqs, abi.MEAS_REQ_DTYPE), ("four", freqs, abi.FOUR_REQ_DTYPE), ("timing", treqs, abi.TIMING_REQ_DTYPE), ("spec", sreqs, abi.SPEC_REQ_DTYPE),
-            ("power", preqs, abi.POWER_REQ_DTYPE), ("values", vreqs, abi.VAL_REQ_DTYPE))}
-        a = abi.SpiceyReducedLists()
-        a.struct_bytes = C.sizeof(a)
-        for key, lst, cnt in (("meas", "reqs", "n_req"), ("four", "freqs", "n_four"), ("timing", "treqs", "n_timing"), ("spec", "sreqs", "n_spec"),
-                              ("power", "preqs", "n_power"), ("values", "vreqs", "n_values")):
-            setattr(a, lst, _reqs_ptr(lists[key]))
-            setattr(a, cnt, len(lists[key]))
-        a.four_stride, a.spec_stride, a.values_stride = fourier_row_doubles(lists["four"]), abi.spec_row_doubles(lists["spec"]), abi.val_row_doubles(lists["values"])
-        return a, lists
+        del keep
+        return self._epilogue({"status": 0, "detail": "", "stat": stat, "sample": sample, "x": x}, rc, iters, _MC_MS)
 
     def run_sens(self, steps: int, dt: float, src: np.ndarray, req: abi.SpiceyTranSensReq, act, step, tol, scalars, reqs=(), treqs=(), preqs=(), freqs=(), sreqs=(),
                  vreqs=(), want_x: bool = False, want_iters: bool = False) -> dict:
@@ -754,9 +742,8 @@ class Handle:
         [n_scalar][nA][2] = {d, c}, `sign` [n_scalar][nA] int8, `bound` [n_scalar][8] (include/spicey_hip.h), `x`
         [n_inst][n_scalar] with want_x, `inst_status`, `state`, `sens_ms`, `design_ms`.  freqs / sreqs / vreqs are there to be refused."""
         f = self.flat
-        src = np.ascontiguousarray(src, dtype=np.float64)
-        per_inst = _src_layout(src, f, steps)
-        a, keep = self._mc_lists(reqs, treqs, preqs, freqs, sreqs, vreqs)
+        src, per_inst, iters = self._prologue(steps, src, want_iters)
+        a, keep, _ = self._reduced_lists(reqs, freqs, treqs, sreqs, preqs, vreqs)
         sc = _scalars(scalars)
         ac, st, tl = _host(act, np.int32), _host(step, np.float64), _host(tol, np.float64)
         nA = int(req.nA) if req is not None else 0
@@ -764,37 +751,25 @@ class Handle:
         sign = np.zeros((len(sc), max(nA, 0)), np.int8)
         bound = np.zeros((len(sc), abi.TRAN_SENS_BOUND_ROW))
         x = np.full((f.n_inst, len(sc)), np.nan) if want_x else None
-        iters = np.zeros((f.n_inst, steps + 1), np.int32) if want_iters else None
-        rc = self.L.spicey_run_sens(self.h, steps, dt, _p(src, C.c_double), 1 if per_inst else 0, C.addressof(a), C.addressof(req) if req is not None else None,
+        rc = self.L.spicey_run_sens(self.h, steps, dt, _p(src, C.c_double), per_inst, C.addressof(a), C.addressof(req) if req is not None else None,
                                     _data(ac), _p(st, C.c_double), _p(tl, C.c_double), sc.ctypes.data if len(sc) else None, len(sc), _p(sens, C.c_double),
                                     sign.ctypes.data, _p(bound, C.c_double), _p(x, C.c_double), _p(iters, C.c_int32))
         del keep
-        res = {"status": rc, "detail": self.error() if rc != abi.OK else "", "sens": sens, "sign": sign, "bound": bound, "x": x, "iters": iters, "partial": True}
-        kept = rc in (abi.OK, abi.ERR_SINGULAR)
-        if kept:
-            res["sens_ms"], res["design_ms"] = self.L.spicey_last_tran_sens_ms(self.h), self.L.spicey_last_tran_sens_design_ms(self.h)
-        return self._dress(res, rc, kept, kept)
+        return self._epilogue({"status": 0, "detail": "", "sens": sens, "sign": sign, "bound": bound, "x": x}, rc, iters, _SENS_MS)
 
     def run_levels(self, steps: int, dt: float, src: np.ndarray, req: abi.SpiceyTranSensReq, lvl, tol, scalars, reqs=(), treqs=(), preqs=(), freqs=(), sreqs=(),
                    vreqs=(), want_iters: bool = False) -> dict:
         """spicey_run_levels: run_sens with the LEVELS design — instance s has element e at 1 + lvl[s][e] tol[e] times its value,
         lvl [n_inst][nE] int8 in {-1, 0, +1} — and no reduction: returns `x` [n_inst][n_scalar], NaN for an invalid instance."""
-        f = self.flat
-        src = np.ascontiguousarray(src, dtype=np.float64)
-        per_inst = _src_layout(src, f, steps)
-        a, keep = self._mc_lists(reqs, treqs, preqs, freqs, sreqs, vreqs)
+        src, per_inst, iters = self._prologue(steps, src, want_iters)
+        a, keep, _ = self._reduced_lists(reqs, freqs, treqs, sreqs, preqs, vreqs)
         sc = _scalars(scalars)
         lv, tl = _host(lvl, np.int8), _host(tol, np.float64)
-        x = np.full((f.n_inst, len(sc)), np.nan)
-        iters = np.zeros((f.n_inst, steps + 1), np.int32) if want_iters else None
-        rc = self.L.spicey_run_levels(self.h, steps, dt, _p(src, C.c_double), 1 if per_inst else 0, C.addressof(a), C.addressof(req) if req is not None else None,
+        x = np.full((self.flat.n_inst, len(sc)), np.nan)
+        rc = self.L.spicey_run_levels(self.h, steps, dt, _p(src, C.c_double), per_inst, C.addressof(a), C.addressof(req) if req is not None else None,
                                       _data(lv), _p(tl, C.c_double), sc.ctypes.data if len(sc) else None, len(sc), _p(x, C.c_double), _p(iters, C.c_int32))
         del keep
-        res = {"status": rc, "detail": self.error() if rc != abi.OK else "", "x": x, "iters": iters, "partial": True}
-        kept = rc in (abi.OK, abi.ERR_SINGULAR)
-        if kept:
-            res["sens_ms"], res["design_ms"] = self.L.spicey_last_tran_sens_ms(self.h), self.L.spicey_last_tran_sens_design_ms(self.h)
-        return self._dress(res, rc, kept, kept)
+        return self._epilogue({"status": 0, "detail": "", "x": x}, rc, iters, _SENS_MS)
 
     def run_device(self, steps: int, dt: float, d_src: int, d_out_v: int, d_out_i: int = 0, d_iters: int = 0, stream: int = 0,
                    src_per_inst: bool = False) -> None:
