@@ -1177,6 +1177,83 @@ double spicey_last_tran_sens_ms(SpiceyHandle *h);
 double spicey_last_tran_sens_design_ms(SpiceyHandle *h);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Periodic steady state by shooting Newton: a design over the STATE of the instances and a dense Newton update on the device.
+ * The state of one circuit is x = [C_vprev | L_iprev | D_vdprev], nX = nC + nL + nD; S_ison is carried, not differentiated.  The
+ * n_inst = n_ckt W instances of ONE transient over one period — W = 1 + nX (SPICEY_PSS_NEWTON) or 1 (SPICEY_PSS_SETTLE),
+ * instance c W + j belongs to circuit c, j = 0 nominal, j = 1 + a with entry a perturbed — give the period map and its finite
+ * differences.  Fixed operation order (pss_exec.h), no FMA contraction, no atomics: the CPU and the device agree on every bit.
+ *
+ * The design writes the instances' state arrays: s[c][j][a] = base[c][a], and for j == 1 + a the value
+ * sp = base[c][a] + rel_step max(|base[c][a]|, scale) with scale = v_scale (C, D entries) or i_scale (L entries), and
+ * h_eff[c][a] = sp - base[c][a]; every instance of circuit c gets base_on[c] as S_ison.
+ *
+ * The update, one 256-thread workgroup per circuit whose done[c] is 0, on the instances' END states e_j (e0 the nominal's):
+ *   r = e0 - base; res = max_a |r_a| / (reltol max(|base_a|, |e0_a|) + abstol), abstol = vabstol (C, D) or iabstol (L)
+ *   converged: res <= 1 and the nominal's end S_ison equals base_on[c]: done[c] = 1, the base stays, status 0
+ *   M[i][a] = (i == a) - (e_{1+a}[i] - e0[i]) / h_eff[a]; Gaussian elimination with partial pivoting, the LOWEST row of the
+ *   largest magnitude as pivot (|pivot| < 1e-12: status 3), column-oriented back substitution, every product, quotient and
+ *   difference rounded on its own; base[c] += damping d, base_on[c] = the nominal's end S_ison.  SETTLE: base[c] = e0, d = r.
+ *   rows [n_ckt][8] = {res, step, n_switch_mismatch, status, a_res, min |pivot|, n_pert_switch_diff, converged}: step the
+ *   scaled max-norm of d, max_a |d_a| / (reltol |base_a| + abstol); a_res the lowest entry of the largest residual; min |pivot|
+ *   -1 when no pivot was taken; n_pert_switch_diff the perturbed instances whose end S_ison differs from the nominal's (the
+ *   Jacobian is noisy then).  Status: 0 converged, 1 moved, 2 the nominal's run was singular, 3 singular Jacobian, 4 a value
+ *   that is not finite or a singular perturbed instance, 5 stopped by another circuit's failure.  A status >= 2 leaves the
+ *   base as it is and writes itself into done[c]: the circuit is frozen.  nX <= 128 with NEWTON: the matrix lives in LDS. */
+#define SPICEY_PSS_NEWTON 0
+#define SPICEY_PSS_SETTLE 1
+#define SPICEY_PSS_ROW 8
+typedef struct SpiceyPssReq {
+  int64_t struct_bytes;
+  int32_t n_ckt;             /* circuits; the instances are n_ckt W */
+  int32_t method;            /* SPICEY_PSS_NEWTON or SPICEY_PSS_SETTLE */
+  int32_t max_iter;          /* spicey_run_pss: Newton iterations at most (>= 1) */
+  int32_t pad;               /* 0 */
+  double damping;            /* a fixed factor in (0, 1] */
+  double reltol, vabstol, iabstol; /* > 0 */
+  double rel_step, v_scale, i_scale; /* > 0 */
+  int64_t reserved;          /* 0 */
+} SpiceyPssReq;              /* 88 bytes */
+/* Bytes of device workspace of spicey_pss_design_device and spicey_pss_update_device; -1 for arguments no launch accepts
+ * (n_ckt < 1, nX < 1, nX > 128 with NEWTON, an unknown method, more than 2^31 - 1 state entries). */
+int64_t spicey_pss_workspace_bytes(int32_t n_ckt, int32_t nX, int32_t method);
+/* The design alone on any DEVICE buffers: d_base [n_ckt][nX], d_base_on [n_ckt][nS], d_h [n_ckt][nX] (written; NEWTON), the
+ * state arrays d_Cv / d_Li / d_Dv / d_Son [n_inst][n<kind>] (written; NULL where the count is 0).  perturb = 0 writes the base
+ * into every instance and leaves d_h alone.  req is HOST data.  Needs no handle; enqueued on `stream` without synchronising.
+ * Refusals are SPICEY_ERR_BAD_DESC with a text starting "pss: " in spicey_last_error(NULL), nothing launched: a null request,
+ * struct_bytes, nonzero pad or reserved, an unknown method, n_ckt < 1, negative counts, nX = 0, nX > 128 with NEWTON (the text
+ * names method = "settle"), tolerances, steps or scales that are not > 0 and finite, damping outside (0, 1], a null buffer, a
+ * workspace that is too small. */
+int32_t spicey_pss_design_device(int32_t device, int32_t nC, int32_t nL, int32_t nD, int32_t nS, const SpiceyPssReq *req, int32_t perturb,
+                                 const double *d_base, const int32_t *d_base_on, double *d_h, double *d_Cv, double *d_Li, double *d_Dv, int32_t *d_Son,
+                                 void *d_work, int64_t work_bytes, void *stream);
+/* The update alone on any DEVICE buffers: the state arrays hold the END states; inst_status [n_inst] (HOST; NULL: all 0) the
+ * instances' spicey_last_inst_status; d_base, d_base_on, d_delta [n_ckt][nX] (or NULL), d_rows [n_ckt][8] and d_done [n_ckt]
+ * are written as above.  The same refusals. */
+int32_t spicey_pss_update_device(int32_t device, int32_t nC, int32_t nL, int32_t nD, int32_t nS, const SpiceyPssReq *req, const int32_t *inst_status,
+                                 double *d_base, int32_t *d_base_on, const double *d_h, const double *d_Cv, const double *d_Li, const double *d_Dv,
+                                 const int32_t *d_Son, double *d_delta, double *d_rows, int32_t *d_done, void *d_work, int64_t work_bytes, void *stream);
+/* The shooting-Newton loop on the handle, whose n_inst = req->n_ckt W instances are the circuits' nominal and perturbed copies and
+ * whose source table holds the m_steps rows of ONE period (per instance with src_per_inst = 1).  The base starts as instance
+ * c W's current state.  Per iteration: the design into the handle's own state arrays; one transient of m_steps - 1 steps from
+ * them, exactly that of spicey_run_device_src, into scratch outputs of this call; the update on the end states with the
+ * instances' spicey_last_inst_status; the [n_ckt][8] rows into history [max_iter][n_ckt][8] (a circuit that is done keeps its
+ * last row; iterations that did not run are not written).  The loop stops when every circuit is done or at max_iter.
+ * x [n_ckt][nX], on [n_ckt][nS] (NULL with nS = 0): the base on return; n_iter [n_ckt]: the updates the circuit took part in;
+ * status [n_ckt]: 0 converged, 1 max_iter reached, 2 the nominal's own solve was singular, 3 singular Jacobian, 4 a value that
+ * is not finite or a singular perturbed instance, 5 stopped by another circuit's failure in its workgroup.  A circuit with a
+ * status >= 2 is frozen, the others go on.  On return every instance of circuit c holds base[c] and base_on[c], so
+ * spicey_get_state is defined.  Returns SPICEY_OK unless a launch failed or the arguments are refused: SPICEY_ERR_BAD_DESC, text
+ * starting "pss: " in spicey_last_error(h), nothing run, the handle as it was — null buffers, n_inst != n_ckt W, nX = 0,
+ * nX > 128 with NEWTON, m_steps < 1, max_iter < 1, tolerances, steps or scales that are not > 0, damping outside (0, 1], a
+ * wrong struct_bytes, src_per_inst outside {0, 1}.  Every engine of spicey_create is served. */
+int32_t spicey_run_pss(SpiceyHandle *h, int64_t m_steps, double dt, const double *src_table, int32_t src_per_inst, const SpiceyPssReq *req, double *x,
+                       int32_t *on, double *history, int32_t *n_iter, int32_t *status);
+/* Duration in ms of the last spicey_run_pss's designs and updates, and of its transients' kernels, each summed over the
+ * iterations, measured with HIP events. */
+double spicey_last_pss_ms(SpiceyHandle *h);
+double spicey_last_pss_tran_ms(SpiceyHandle *h);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Result formatting fast path (host code, no GPU): the CSV text of
  *   formatTranResult(tran)       /root/reference/lib/formatting/formatTranResult.ts:1-23
  * straight from the typed arrays spicey_run filled.  Every number is Number.prototype.toPrecision(6) exactly as

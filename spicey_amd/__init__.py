@@ -19,7 +19,10 @@ measureMonteCarlo (spicey_amd.tran_mc) does the same for transient runs: the sam
 scalars of measureTRAN's measures are reduced across them to quantiles, moments, yields against limits and the worst samples;
 measureSens / measureWorstCase (spicey_amd.tran_sens) perturb one toleranced element at a time, as the instances of one transient,
 reduce the scalars across them to every element's first-order sensitivity and curvature and to worst-case and root-sum-square
-bounds, and run the tolerance corners the signs point to as the instances of a second one.
+bounds, and run the tolerance corners the signs point to as the instances of a second one;
+steadyState / steadyStateBatch (spicey_amd.pss) find the periodic steady state of a driven circuit by shooting Newton — the
+nominal and the state-perturbed copies are the instances of one transient over one period, the dense update runs on the device —
+and write it into the circuit, so that the next analysis starts there.
 """
 from .ac_batch import simulateACBatch  # noqa: F401
 from .ac_measure import measureAC, measureACBatch  # noqa: F401
@@ -28,4 +31,5 @@ from .sens import simulateSens, simulateSensBatch  # noqa: F401
 from .mc import mc_values, simulateMonteCarlo  # noqa: F401
 from .tran_mc import measureMonteCarlo  # noqa: F401
 from .tran_sens import design_circuit, measureSens, measureWorstCase  # noqa: F401
+from .pss import steadyState, steadyStateBatch  # noqa: F401
 from .measure import deriv, efficiency, find, measureTRAN, measureTRANBatch, power, sample, trace  # noqa: F401

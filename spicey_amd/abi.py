@@ -287,6 +287,35 @@ def tran_sens_req(mode: int, nA: int = 0) -> SpiceyTranSensReq:
     return SpiceyTranSensReq(C.sizeof(SpiceyTranSensReq), int(mode), int(nA))
 
 
+class SpiceyPssReq(C.Structure):
+    """The request of a periodic-steady-state design, update or run (include/spicey_hip.h)."""
+    _fields_ = [("struct_bytes", C.c_int64), ("n_ckt", C.c_int32), ("method", C.c_int32), ("max_iter", C.c_int32), ("pad", C.c_int32),
+                ("damping", C.c_double), ("reltol", C.c_double), ("vabstol", C.c_double), ("iabstol", C.c_double), ("rel_step", C.c_double),
+                ("v_scale", C.c_double), ("i_scale", C.c_double), ("reserved", C.c_int64)]
+
+
+assert C.sizeof(SpiceyPssReq) == 88
+PSS_NEWTON, PSS_SETTLE = 0, 1
+PSS_METHODS = {"newton": PSS_NEWTON, "settle": PSS_SETTLE}
+PSS_MAX_NX = 128  # states of one circuit the Newton update takes
+PSS_ROW = 8  # doubles of a row: res, step, n_switch_mismatch, status, a_res, min |pivot|, n_pert_switch_diff, converged
+PSS_ROW_KEYS = ("res", "step", "n_switch_mismatch", "status", "a_res", "min_pivot", "n_pert_switch_diff", "converged")
+# a circuit's status: converged, max_iter reached (a row: moved), the nominal's run singular, singular Jacobian, a value that is
+# not finite or a singular perturbed instance, stopped by another circuit's failure
+PSS_CONVERGED, PSS_MAX_ITER, PSS_NOMINAL_SINGULAR, PSS_SINGULAR_JACOBIAN, PSS_NOT_FINITE, PSS_STOPPED = 0, 1, 2, 3, 4, 5
+
+
+def pss_req(n_ckt: int, method: int = PSS_NEWTON, max_iter: int = 20, damping: float = 1.0, reltol: float = 1e-6, vabstol: float = 1e-9,
+            iabstol: float = 1e-12, rel_step: float = 1e-6, v_scale: float = 1.0, i_scale: float = 1e-3) -> SpiceyPssReq:
+    return SpiceyPssReq(C.sizeof(SpiceyPssReq), int(n_ckt), int(method), int(max_iter), 0, float(damping), float(reltol), float(vabstol), float(iabstol),
+                        float(rel_step), float(v_scale), float(i_scale), 0)
+
+
+def pss_width(method: int, nX: int) -> int:
+    """Instances per circuit: the nominal and, with Newton, one per perturbed state entry."""
+    return 1 if method == PSS_SETTLE else 1 + nX
+
+
 def _i32(a) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.int32)
 

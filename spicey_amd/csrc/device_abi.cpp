@@ -18,6 +18,7 @@
 #include "mc.h"
 #include "sens.h"
 #include "power.h"
+#include "pss.h"
 #include "values.h"
 #include "spectrum.h"
 #include "timing.h"
@@ -260,4 +261,29 @@ extern "C" int32_t spicey_tran_sens_reduce_device(int32_t device, int32_t n_inst
   return launch_on_device(device, "spicey_launch_ts_reduce", [&]() {
     return spicey_launch_ts_reduce(device, T, A, scalars, valid, step, tol_act, d_x, d_sens, d_sign, d_bound, d_work, (hipStream_t)stream);
   });
+}
+
+// Periodic steady state (include/spicey_hip.h): the design over the state and the Newton update of pss.hip on any device buffers,
+// no handle.
+extern "C" int64_t spicey_pss_workspace_bytes(int32_t n_ckt, int32_t nX, int32_t method) { return spicey_pss_bytes(n_ckt, nX, method); }
+
+extern "C" int32_t spicey_pss_design_device(int32_t device, int32_t nC, int32_t nL, int32_t nD, int32_t nS, const SpiceyPssReq *req, int32_t perturb,
+                                            const double *d_base, const int32_t *d_base_on, double *d_h, double *d_Cv, double *d_Li, double *d_Dv, int32_t *d_Son,
+                                            void *d_work, int64_t work_bytes, void *stream) {
+  // (the call is judged before the device is touched: a refusal launches nothing)
+  SpiceyPssArgs A;
+  if (!spicey_pss_judge(false, nC, nL, nD, nS, req, perturb, (double *)d_base, (int32_t *)d_base_on, d_h, d_Cv, d_Li, d_Dv, d_Son, nullptr, nullptr, nullptr,
+                        d_work != nullptr, work_bytes, A, g_err))
+    return SPICEY_ERR_BAD_DESC;
+  return launch_on_device(device, "spicey_launch_pss_design", [&]() { return spicey_launch_pss_design(device, A, d_work, (hipStream_t)stream); });
+}
+
+extern "C" int32_t spicey_pss_update_device(int32_t device, int32_t nC, int32_t nL, int32_t nD, int32_t nS, const SpiceyPssReq *req, const int32_t *inst_status,
+                                            double *d_base, int32_t *d_base_on, const double *d_h, const double *d_Cv, const double *d_Li, const double *d_Dv,
+                                            const int32_t *d_Son, double *d_delta, double *d_rows, int32_t *d_done, void *d_work, int64_t work_bytes, void *stream) {
+  SpiceyPssArgs A;
+  if (!spicey_pss_judge(true, nC, nL, nD, nS, req, 1, d_base, d_base_on, (double *)d_h, (double *)d_Cv, (double *)d_Li, (double *)d_Dv, (int32_t *)d_Son, d_delta,
+                        d_rows, d_done, d_work != nullptr, work_bytes, A, g_err))
+    return SPICEY_ERR_BAD_DESC;
+  return launch_on_device(device, "spicey_launch_pss_update", [&]() { return spicey_launch_pss_update(device, A, inst_status, d_work, (hipStream_t)stream); });
 }

@@ -128,6 +128,12 @@ SIGNATURES = {
     "spicey_run_levels": (_i32, [_vp, _i64, _f64, _f64p, _i32, _vp, _vp, _vp, _f64p, _vp, _i32, _f64p, _i32p]),
     "spicey_last_tran_sens_ms": (_f64, [_vp]),
     "spicey_last_tran_sens_design_ms": (_f64, [_vp]),
+    "spicey_pss_workspace_bytes": (_i64, [_i32, _i32, _i32]),
+    "spicey_pss_design_device": (_i32, [_i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "spicey_pss_update_device": (_i32, [_i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "spicey_run_pss": (_i32, [_vp, _i64, _f64, _f64p, _i32, _vp, _f64p, _i32p, _f64p, _i32p, _i32p]),
+    "spicey_last_pss_ms": (_f64, [_vp]),
+    "spicey_last_pss_tran_ms": (_f64, [_vp]),
 }
 EXPORTS = list(SIGNATURES)
 
@@ -387,6 +393,36 @@ def tran_sens_reduce_device(n_inst: int, rows, scalars, valid, step, tol_act, d_
                                           d_work or None, work_bytes, stream or None)
     if rc != abi.OK:
         _fail("spicey_tran_sens_reduce_device", rc, L.spicey_last_error(None))
+
+
+def pss_workspace_bytes(n_ckt: int, nX: int, method: int = abi.PSS_NEWTON) -> int:
+    return load().spicey_pss_workspace_bytes(n_ckt, nX, method)
+
+
+def pss_design_device(kinds, nS: int, req: abi.SpiceyPssReq, d_base: int, d_base_on: int, d_h: int, d_Cv: int, d_Li: int, d_Dv: int, d_Son: int, d_work: int,
+                      work_bytes: int, perturb: bool = True, device: int = 0, stream: int = 0) -> None:
+    """spicey_pss_design_device: the design over the state alone on raw device pointers: d_base [n_ckt][nX], d_base_on [n_ckt][nS],
+    d_h [n_ckt][nX] and the state arrays [n_ckt W][n<kind>] (0 where the count is 0); kinds = (nC, nL, nD).  Enqueued on `stream`,
+    no synchronisation.  A refusal raises SpiceyNativeError whose `status` is abi.ERR_BAD_DESC."""
+    L = load()
+    rc = L.spicey_pss_design_device(device, *kinds, nS, C.addressof(req) if req is not None else None, int(perturb), d_base or None, d_base_on or None, d_h or None,
+                                    d_Cv or None, d_Li or None, d_Dv or None, d_Son or None, d_work or None, work_bytes, stream or None)
+    if rc != abi.OK:
+        _fail("spicey_pss_design_device", rc, L.spicey_last_error(None))
+
+
+def pss_update_device(kinds, nS: int, req: abi.SpiceyPssReq, inst_status, d_base: int, d_base_on: int, d_h: int, d_Cv: int, d_Li: int, d_Dv: int, d_Son: int,
+                      d_delta: int, d_rows: int, d_done: int, d_work: int, work_bytes: int, device: int = 0, stream: int = 0) -> None:
+    """spicey_pss_update_device: the Newton update alone on raw device pointers; the state arrays hold the END states, inst_status
+    [n_ckt W] is a HOST array (None: all 0); d_base, d_base_on, d_delta [n_ckt][nX] (or 0), d_rows [n_ckt][8] and d_done [n_ckt]
+    are written.  Enqueued on `stream`, no synchronisation."""
+    L = load()
+    ist = _host(inst_status, np.int32)
+    rc = L.spicey_pss_update_device(device, *kinds, nS, C.addressof(req) if req is not None else None, _data(ist), d_base or None, d_base_on or None, d_h or None,
+                                    d_Cv or None, d_Li or None, d_Dv or None, d_Son or None, d_delta or None, d_rows or None, d_done or None, d_work or None, work_bytes,
+                                    stream or None)
+    if rc != abi.OK:
+        _fail("spicey_pss_update_device", rc, L.spicey_last_error(None))
 
 
 def fourier_row_doubles(reqs) -> int:
@@ -770,6 +806,32 @@ class Handle:
                                       _data(lv), _p(tl, C.c_double), sc.ctypes.data if len(sc) else None, len(sc), _p(x, C.c_double), _p(iters, C.c_int32))
         del keep
         return self._epilogue({"status": 0, "detail": "", "x": x}, rc, iters, _SENS_MS)
+
+    def run_pss(self, m_steps: int, dt: float, src: np.ndarray, req: abi.SpiceyPssReq) -> dict:
+        """spicey_run_pss: the shooting-Newton loop on this handle, whose n_inst = req.n_ckt W instances are the circuits' nominal and
+        perturbed copies; src holds the m_steps source rows of one period, [m_steps][nV] or [n_inst][m_steps][nV].  Returns `x`
+        [n_ckt][nX] and `on` [n_ckt][nS] (the base on return), `history` [iterations][n_ckt][8], `n_iter` and `ckt_status` [n_ckt]
+        (include/spicey_hip.h), `inst_status` of the last transient, `pss_ms` (designs and updates) and `tran_ms` (the transients'
+        kernels), summed over the iterations.  A refusal comes back as status abi.ERR_BAD_DESC with its text in `detail`."""
+        f = self.flat
+        src = np.ascontiguousarray(src, dtype=np.float64)
+        per_inst = _src_layout(src, f, m_steps - 1) if m_steps >= 1 else False
+        n_ckt, max_iter = max(int(req.n_ckt), 0) if req is not None else 0, max(int(req.max_iter), 0) if req is not None else 0
+        x = np.zeros((n_ckt, f.nC + f.nL + f.nD))
+        on = np.zeros((n_ckt, f.nS), np.int32)
+        history = np.zeros((max_iter, n_ckt, abi.PSS_ROW))
+        n_iter, st = np.zeros(max(n_ckt, 1), np.int32), np.ones(max(n_ckt, 1), np.int32)
+        rc = self.L.spicey_run_pss(self.h, m_steps, dt, _p(src, C.c_double), 1 if per_inst else 0, C.addressof(req) if req is not None else None, _p(x, C.c_double),
+                                   _p(on, C.c_int32), _p(history, C.c_double), _p(n_iter, C.c_int32), _p(st, C.c_int32))
+        res = {"status": rc, "detail": self.error(), "x": x, "on": on, "n_iter": n_iter[:n_ckt], "ckt_status": st[:n_ckt],
+               "history": history[:int(n_iter[:n_ckt].max()) if n_ckt else 0]}
+        if rc == abi.OK:
+            res["pss_ms"], res["tran_ms"] = self.L.spicey_last_pss_ms(self.h), self.L.spicey_last_pss_tran_ms(self.h)
+            try:
+                res["inst_status"] = self.inst_status()
+            except SpiceyNativeError:
+                res["inst_status"] = None  # (no transient ran)
+        return res
 
     def run_device(self, steps: int, dt: float, d_src: int, d_out_v: int, d_out_i: int = 0, d_iters: int = 0, stream: int = 0,
                    src_per_inst: bool = False) -> None:
@@ -1236,6 +1298,11 @@ class HipBackend(_AcCalls):
                         preqs=()) -> dict:
         """Handle.run_levels on a handle of its own whose instances are the level rows (flat: the nominal circuit replicated)."""
         return self._on_handle(flat, lambda h: h.run_levels(steps, dt, src, req, lvl, tol, scalars, reqs, treqs, preqs))
+
+
+    def run_pss(self, flat: abi.FlatCircuit, m_steps: int, dt: float, src: np.ndarray, req: abi.SpiceyPssReq) -> dict:
+        """Handle.run_pss on a handle of its own whose instances are the circuits' nominal and perturbed copies."""
+        return self._on_handle(flat, lambda h: h.run_pss(m_steps, dt, src, req))
 
 
 class HipAcExactBackend(_AcCalls):
