@@ -1254,6 +1254,101 @@ double spicey_last_pss_ms(SpiceyHandle *h);
 double spicey_last_pss_tran_ms(SpiceyHandle *h);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Sizing elements to measured goals: a damped least-squares (Levenberg-Marquardt) loop over element GAINS, updated on the device.
+ * One handle holds n_ckt circuits of one topology, independent problems; each has W = 1 + 2 nA instances — instance c W nominal,
+ * c W + 1 + 2a with active element a at +h_a, c W + 2 + 2a at -h_a — the one-at-a-time design of spicey_run_sens per circuit.
+ * act [nA] are strictly ascending element indices in the order R, C, L; the unknowns are g [n_ckt][nA], factors on the
+ * handle's own values (a resistor stays in ohms).  Fixed operation order (fit_exec.h), no FMA contraction, no atomics, no exp,
+ * log or sqrt: the CPU and the device agree on every bit.
+ *
+ * The design writes v' = v for an inactive element, v' = v (g_a (1.0 + h_a)) or v (g_a (1.0 - h_a)) for the active element of
+ * a perturbed instance and v' = v g_a otherwise, every product rounded on its own.
+ *
+ * The update, one 256-thread workgroup per circuit whose done[c] is 0, on x [n_inst][n_scalar] (the scalars of spicey_run_mc's
+ * programs), the instances' validity and goals [n_ckt][n_scalar]:
+ *   r_j = w_j (x0_j - lo_j) for EQ, else w_j times the amount by which x0_j exceeds its bound (negative below lo), else +0.0;
+ *   goal j is active iff it is EQ or r_j != 0; F = sum_j r_j r_j in ascending j from +0.0; an invalid nominal or a NaN x0_j makes
+ *   the point not evaluable, F = +inf.
+ *   accept iff first and F is finite, or not first and F < F_good: J[j][a] = w_j ((x+_j - x-_j) / (2.0 h_a)) over the active j — a
+ *   column with an invalid instance or a NaN entry is frozen: zeroed, counted —, A = J^T J, b = -(J^T r), g_good = g, F_good = F,
+ *   all kept in the workspace; lambda = lambda0 (first) or lambda lam_down.  An accepted F <= f_tol converges without a solve.
+ *   reject: lambda = lambda lam_up, the step is solved again from the kept A and b; lambda > lam_max: status 5.
+ *   solve M d = b, M = A with M[a][a] = A[a][a] + lambda A[a][a] (a zero diagonal becomes 1.0): Gaussian elimination with partial
+ *   pivoting, the LOWEST row of the largest magnitude as pivot (|pivot| < pivot_min: status 3), column-oriented back substitution.
+ *   d_a is clamped to +-max_step; an accepted point with max|d| <= x_tol converges; else g_a = g_good_a (1.0 + d_a), clamped to
+ *   [g_lo_a, g_hi_a].  With every status but 1, g[c] = g_good[c]: the gains always belong to a point that was evaluated.
+ *   rows [n_ckt][8] = {F, F_good, lambda, accepted, status, max|d|, n_frozen, n_clamped}.  Status: 0 converged (done[c] = 1),
+ *   1 moved, 2 the first nominal is not evaluable, 3 singular system, 4 a value that is not finite, 5 stalled; a status >= 2
+ *   writes itself into done[c]: the circuit is frozen, the others go on.  nA <= 128: the matrix lives in LDS (132 096 bytes). */
+#define SPICEY_FIT_EQ 0
+#define SPICEY_FIT_AT_MOST 1
+#define SPICEY_FIT_AT_LEAST 2
+#define SPICEY_FIT_BETWEEN 3
+#define SPICEY_FIT_ROW 8
+typedef struct SpiceyFitReq {
+  int64_t struct_bytes;
+  int32_t n_ckt;             /* circuits; the instances are n_ckt (1 + 2 nA) */
+  int32_t nA;                /* active elements, 1 .. 128 */
+  int32_t max_iter;          /* spicey_run_fit: updates at most (>= 1) */
+  int32_t pad;               /* 0 */
+  double lambda0;            /* >= 0 */
+  double lam_up, lam_down;   /* > 1; in (0, 1] */
+  double lam_max;            /* >= lambda0 */
+  double max_step;           /* > 0: the largest relative change of a gain in one step */
+  double x_tol, f_tol;       /* >= 0 */
+  double pivot_min;          /* > 0 */
+  int64_t reserved;          /* 0 */
+} SpiceyFitReq;              /* 96 bytes */
+typedef struct SpiceyFitGoal {
+  int32_t kind, pad;         /* SPICEY_FIT_*; 0 */
+  double lo, hi;             /* EQ: lo is the target; AT_MOST: hi; AT_LEAST: lo; BETWEEN: lo <= hi */
+  double weight;             /* finite, > 0 */
+} SpiceyFitGoal;             /* 32 bytes */
+/* Bytes of device workspace of spicey_fit_design_device and spicey_fit_update_device; -1 for arguments no launch accepts
+ * (n_ckt < 1, nA outside 1 .. 128, n_ckt (1 + 2 nA) > 16384, n_scalar < 1).  The workspace carries A, b, g_good, F_good
+ * and lambda from one update to the next: the same buffer serves the whole loop. */
+int64_t spicey_fit_workspace_bytes(int32_t n_ckt, int32_t nA, int32_t n_scalar);
+/* The design alone on any DEVICE buffers: d_R / d_C / d_L [n_inst][n<kind>] the nominal values, d_g [n_ckt][nA], the outputs
+ * d_*_out of the same shapes (NULL where the count is 0).  req, act [nA] and step [nA] are HOST data.  Needs no handle; enqueued
+ * on `stream` without synchronising.  Refusals are SPICEY_ERR_BAD_DESC with a text starting "fit: " in spicey_last_error(NULL),
+ * nothing launched: a null request, struct_bytes, nonzero pad or reserved, n_ckt < 1, nA outside 1 .. 128, more than 16384
+ * instances, active elements out of range or not strictly ascending, steps outside (0, 1), a null buffer, a workspace that is
+ * too small; the update's also n_scalar < 1, bounds that are not 0 < g_lo <= g_hi finite, a weight that is not finite and > 0, an
+ * unknown goal kind, a bound that is not finite or lo > hi, lam_down outside (0, 1], lam_up <= 1, the other numbers of the request. */
+int32_t spicey_fit_design_device(int32_t device, int32_t nR, int32_t nC, int32_t nL, const double *d_R, const double *d_C, const double *d_L,
+                                 const SpiceyFitReq *req, const int32_t *act, const double *step, const double *d_g, double *d_R_out, double *d_C_out,
+                                 double *d_L_out, void *d_work, int64_t work_bytes, void *stream);
+/* The update alone on any DEVICE buffers: d_x [n_inst][n_scalar], d_g [n_ckt][nA], d_rows [n_ckt][8] and d_done [n_ckt] are
+ * written as above; first != 0 marks the circuits' first update.  step [nA], g_lo / g_hi [n_ckt][nA], goals [n_ckt][n_scalar]
+ * and valid [n_inst] (bytes; NULL: every instance is valid) are HOST data.  The same refusals. */
+int32_t spicey_fit_update_device(int32_t device, const SpiceyFitReq *req, int32_t n_scalar, int32_t first, const double *step, const double *g_lo,
+                                 const double *g_hi, const SpiceyFitGoal *goals, const uint8_t *valid, const double *d_x, double *d_g, double *d_rows,
+                                 int32_t *d_done, void *d_work, int64_t work_bytes, void *stream);
+/* The loop on the handle, whose n_inst = req->n_ckt (1 + 2 nA) instances are the circuits' nominal and perturbed copies.  The
+ * handle's state at entry is kept; per iteration it is restored, the design goes into scratch value arrays of this call, ONE
+ * transient bound to them runs exactly as under spicey_run_sens, the measure / timing / power passes of `lists` leave their rows
+ * on the device, the scalar programs (spicey_run_mc's) turn them into x, and the update runs; only the [n_ckt][8] rows and the
+ * done flags come back, into history [max_iter][n_ckt][8] (a circuit that is done keeps its last row; iterations that did not
+ * run are not written).  The loop stops when every circuit is done or at max_iter.  g0 [n_ckt][nA] are the starting gains.
+ * On return g [n_ckt][nA] and F [n_ckt] are the best evaluated point, x [n_ckt][n_scalar] (or NULL) the nominals' scalars there,
+ * n_iter [n_ckt] the updates the circuit took part in, status [n_ckt]: 0 converged, 1 max_iter reached, 2 the first nominal
+ * not evaluable, 3 singular system, 4 a value that is not finite, 5 stalled.  The handle's own values are untouched and its
+ * state is the state at entry: a later plain run gives the bits it gave before.  The fourier, spectrum and values lists are
+ * refused.  A matrix that is singular by its structure gives every circuit status 2 and SPICEY_OK, nothing run, as
+ * spicey_run_pss does.  A launch or a transient that fails ends the call with its error and the outputs as far as they were
+ * written; the handle's state is the state at entry then too.  Refusals: SPICEY_ERR_BAD_DESC, text starting "fit: " in
+ * spicey_last_error(h), nothing run — the request's numbers, max_iter < 1, null buffers, n_inst != n_ckt (1 + 2 nA), a
+ * starting gain that is not finite and > 0, and the design's, the update's, the lists' and the scalars' own. */
+int32_t spicey_run_fit(SpiceyHandle *h, int64_t steps, double dt, const double *src_table, int32_t src_per_inst, const SpiceyReducedLists *lists,
+                       const SpiceyFitReq *req, const int32_t *act, const double *step, const double *g_lo, const double *g_hi, const double *g0,
+                       const SpiceyFitGoal *goals, const SpiceyMcScalar *scalars, int32_t n_scalar, double *g, double *F, double *history,
+                       int32_t *n_iter, int32_t *status, double *x, int32_t *iters);
+/* Duration in ms of the last spicey_run_fit's designs and updates, and of its transients' kernels, each summed over the
+ * iterations, measured with HIP events. */
+double spicey_last_fit_ms(SpiceyHandle *h);
+double spicey_last_fit_tran_ms(SpiceyHandle *h);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Result formatting fast path (host code, no GPU): the CSV text of
  *   formatTranResult(tran)       /root/reference/lib/formatting/formatTranResult.ts:1-23
  * straight from the typed arrays spicey_run filled.  Every number is Number.prototype.toPrecision(6) exactly as

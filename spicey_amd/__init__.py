@@ -22,7 +22,9 @@ reduce the scalars across them to every element's first-order sensitivity and cu
 bounds, and run the tolerance corners the signs point to as the instances of a second one;
 steadyState / steadyStateBatch (spicey_amd.pss) find the periodic steady state of a driven circuit by shooting Newton — the
 nominal and the state-perturbed copies are the instances of one transient over one period, the dense update runs on the device —
-and write it into the circuit, so that the next analysis starts there.
+and write it into the circuit, so that the next analysis starts there;
+optimizeTRAN / optimizeTRANBatch (spicey_amd.fit) size elements so that transient measurements meet goals: a damped
+least-squares loop over element gains whose Jacobian is the one-at-a-time design of measureSens, updated on the device.
 """
 from .ac_batch import simulateACBatch  # noqa: F401
 from .ac_measure import measureAC, measureACBatch  # noqa: F401
@@ -32,4 +34,5 @@ from .mc import mc_values, simulateMonteCarlo  # noqa: F401
 from .tran_mc import measureMonteCarlo  # noqa: F401
 from .tran_sens import design_circuit, measureSens, measureWorstCase  # noqa: F401
 from .pss import steadyState, steadyStateBatch  # noqa: F401
+from .fit import at_least, at_most, between, optimizeTRAN, optimizeTRANBatch, target  # noqa: F401
 from .measure import deriv, efficiency, find, measureTRAN, measureTRANBatch, power, sample, trace  # noqa: F401

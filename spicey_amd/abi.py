@@ -316,6 +316,40 @@ def pss_width(method: int, nX: int) -> int:
     return 1 if method == PSS_SETTLE else 1 + nX
 
 
+class SpiceyFitReq(C.Structure):
+    """The request of an element-sizing design, update or run (include/spicey_hip.h)."""
+    _fields_ = [("struct_bytes", C.c_int64), ("n_ckt", C.c_int32), ("nA", C.c_int32), ("max_iter", C.c_int32), ("pad", C.c_int32),
+                ("lambda0", C.c_double), ("lam_up", C.c_double), ("lam_down", C.c_double), ("lam_max", C.c_double), ("max_step", C.c_double),
+                ("x_tol", C.c_double), ("f_tol", C.c_double), ("pivot_min", C.c_double), ("reserved", C.c_int64)]
+
+
+assert C.sizeof(SpiceyFitReq) == 96
+# a goal on one scalar (include/spicey_hip.h, SpiceyFitGoal)
+FIT_GOAL_DTYPE = np.dtype([("kind", "<i4"), ("pad", "<i4"), ("lo", "<f8"), ("hi", "<f8"), ("weight", "<f8")])
+assert FIT_GOAL_DTYPE.itemsize == 32
+FIT_EQ, FIT_AT_MOST, FIT_AT_LEAST, FIT_BETWEEN = 0, 1, 2, 3
+FIT_MAX_NA = 128  # active elements of one circuit the update takes
+FIT_ROW = 8  # doubles of a row: F, F_good, lambda, accepted, status, max |d|, n_frozen, n_clamped
+FIT_ROW_KEYS = ("F", "F_good", "lambda", "accepted", "status", "max_step", "n_frozen", "n_clamped")
+# a circuit's status: converged, max_iter reached (a row: moved), the first nominal not evaluable, singular system, a value that is
+# not finite, stalled (lambda passed lam_max)
+FIT_CONVERGED, FIT_MAX_ITER, FIT_NOT_EVALUABLE, FIT_SINGULAR, FIT_NOT_FINITE, FIT_STALLED = 0, 1, 2, 3, 4, 5
+
+
+def fit_req(n_ckt: int, nA: int, max_iter: int = 30, lambda0: float = 1e-3, lam_up: float = 10.0, lam_down: float = 0.1, lam_max: float = 1e8,
+            max_step: float = 0.5, x_tol: float = 1e-6, f_tol: float = 1e-12, pivot_min: float = 1e-300) -> SpiceyFitReq:
+    return SpiceyFitReq(C.sizeof(SpiceyFitReq), int(n_ckt), int(nA), int(max_iter), 0, float(lambda0), float(lam_up), float(lam_down), float(lam_max),
+                        float(max_step), float(x_tol), float(f_tol), float(pivot_min), 0)
+
+
+def fit_goals(rows) -> np.ndarray:
+    """[(kind, lo, hi, weight)] as records of FIT_GOAL_DTYPE."""
+    out = np.zeros(len(rows), FIT_GOAL_DTYPE)
+    for k, (kind, lo, hi, w) in enumerate(rows):
+        out[k] = (int(kind), 0, float(lo), float(hi), float(w))
+    return out
+
+
 def _i32(a) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.int32)
 

@@ -10,6 +10,7 @@
 #include "tran_handle.h"
 #include "ac_measure.h"
 #include "ac_measure_exec.h"
+#include "fit.h"
 #include "fourier.h"
 #include "fourier_exec.h"
 #include "measure.h"
@@ -286,4 +287,28 @@ extern "C" int32_t spicey_pss_update_device(int32_t device, int32_t nC, int32_t 
                         d_rows, d_done, d_work != nullptr, work_bytes, A, g_err))
     return SPICEY_ERR_BAD_DESC;
   return launch_on_device(device, "spicey_launch_pss_update", [&]() { return spicey_launch_pss_update(device, A, inst_status, d_work, (hipStream_t)stream); });
+}
+
+// Sizing elements to measured goals (include/spicey_hip.h): the design over the gains and the damped least-squares update of
+// fit.hip on any device buffers, no handle.
+extern "C" int64_t spicey_fit_workspace_bytes(int32_t n_ckt, int32_t nA, int32_t n_scalar) { return spicey_fit_bytes(n_ckt, nA, n_scalar); }
+
+extern "C" int32_t spicey_fit_design_device(int32_t device, int32_t nR, int32_t nC, int32_t nL, const double *d_R, const double *d_C, const double *d_L,
+                                            const SpiceyFitReq *req, const int32_t *act, const double *step, const double *d_g, double *d_R_out, double *d_C_out,
+                                            double *d_L_out, void *d_work, int64_t work_bytes, void *stream) {
+  // (the call is judged before the device is touched: a refusal launches nothing)
+  SpiceyFitArgs A;
+  if (!spicey_fit_design_judge(nR, nC, nL, d_R, d_C, d_L, req, act, step, d_g, d_R_out, d_C_out, d_L_out, d_work != nullptr, work_bytes, A, g_err))
+    return SPICEY_ERR_BAD_DESC;
+  return launch_on_device(device, "spicey_launch_fit_design", [&]() { return spicey_launch_fit_design(device, A, act, step, d_work, (hipStream_t)stream); });
+}
+
+extern "C" int32_t spicey_fit_update_device(int32_t device, const SpiceyFitReq *req, int32_t n_scalar, int32_t first, const double *step, const double *g_lo,
+                                            const double *g_hi, const SpiceyFitGoal *goals, const uint8_t *valid, const double *d_x, double *d_g, double *d_rows,
+                                            int32_t *d_done, void *d_work, int64_t work_bytes, void *stream) {
+  SpiceyFitArgs A;
+  if (!spicey_fit_update_judge(req, n_scalar, first, step, g_lo, g_hi, goals, d_x, d_g, d_rows, d_done, d_work != nullptr, work_bytes, A, g_err))
+    return SPICEY_ERR_BAD_DESC;
+  return launch_on_device(device, "spicey_launch_fit_update",
+                          [&]() { return spicey_launch_fit_update(device, A, step, g_lo, g_hi, goals, valid, d_work, (hipStream_t)stream); });
 }

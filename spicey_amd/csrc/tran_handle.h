@@ -68,6 +68,7 @@ struct SpiceyHandle {
   double last_tran_mc_ms = 0.0, last_tran_mc_draw_ms = 0.0;  // the last spicey_run_mc: its scalars and reduction, its draw
   double last_tran_sens_ms = 0.0, last_tran_sens_design_ms = 0.0;  // the last spicey_run_sens / spicey_run_levels: the same, its design
   double last_pss_ms = 0.0, last_pss_tran_ms = 0.0;  // the last spicey_run_pss: its designs and updates, its transients, summed over the iterations
+  double last_fit_ms = 0.0, last_fit_tran_ms = 0.0;  // the last spicey_run_fit: its designs and updates, its transients, summed over the iterations
   bool pending = false;
   int64_t last_solves = 0;
   double last_ms = 0.0;

@@ -134,6 +134,13 @@ SIGNATURES = {
     "spicey_run_pss": (_i32, [_vp, _i64, _f64, _f64p, _i32, _vp, _f64p, _i32p, _f64p, _i32p, _i32p]),
     "spicey_last_pss_ms": (_f64, [_vp]),
     "spicey_last_pss_tran_ms": (_f64, [_vp]),
+    "spicey_fit_workspace_bytes": (_i64, [_i32, _i32, _i32]),
+    "spicey_fit_design_device": (_i32, [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "spicey_fit_update_device": (_i32, [_i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "spicey_run_fit": (_i32, [_vp, _i64, _f64, _f64p, _i32, _vp, _vp, _vp, _f64p, _f64p, _f64p, _f64p, _vp, _vp, _i32, _f64p, _f64p, _f64p, _i32p, _i32p,
+                              _f64p, _i32p]),
+    "spicey_last_fit_ms": (_f64, [_vp]),
+    "spicey_last_fit_tran_ms": (_f64, [_vp]),
 }
 EXPORTS = list(SIGNATURES)
 
@@ -423,6 +430,41 @@ def pss_update_device(kinds, nS: int, req: abi.SpiceyPssReq, inst_status, d_base
                                     stream or None)
     if rc != abi.OK:
         _fail("spicey_pss_update_device", rc, L.spicey_last_error(None))
+
+
+def fit_workspace_bytes(n_ckt: int, nA: int, n_scalar: int) -> int:
+    return load().spicey_fit_workspace_bytes(n_ckt, nA, n_scalar)
+
+
+def _goals(goals) -> Optional[np.ndarray]:
+    return None if goals is None else np.ascontiguousarray(goals, dtype=abi.FIT_GOAL_DTYPE).reshape(-1)
+
+
+def fit_design_device(nR: int, nC: int, nL: int, d_R: int, d_C: int, d_L: int, req: abi.SpiceyFitReq, act, step, d_g: int, d_R_out: int, d_C_out: int, d_L_out: int,
+                      d_work: int, work_bytes: int, device: int = 0, stream: int = 0) -> None:
+    """spicey_fit_design_device: the design over the gains d_g [n_ckt][nA] alone on raw device pointers; act [nA] (int32) and step
+    [nA] are HOST arrays, the value arrays [n_ckt (1 + 2 nA)][n<kind>] (0 where the count is 0), the resistors in ohms.  Enqueued
+    on `stream`, no synchronisation.  A refusal raises SpiceyNativeError whose `status` is abi.ERR_BAD_DESC."""
+    L = load()
+    ac, st = _host(act, np.int32), _host(step, np.float64)
+    rc = L.spicey_fit_design_device(device, nR, nC, nL, d_R or None, d_C or None, d_L or None, C.addressof(req) if req is not None else None, _data(ac), _data(st),
+                                    d_g or None, d_R_out or None, d_C_out or None, d_L_out or None, d_work or None, work_bytes, stream or None)
+    if rc != abi.OK:
+        _fail("spicey_fit_design_device", rc, L.spicey_last_error(None))
+
+
+def fit_update_device(req: abi.SpiceyFitReq, n_scalar: int, first: bool, step, g_lo, g_hi, goals, valid, d_x: int, d_g: int, d_rows: int, d_done: int, d_work: int,
+                      work_bytes: int, device: int = 0, stream: int = 0) -> None:
+    """spicey_fit_update_device: the damped least-squares update alone on raw device pointers: d_x [n_inst][n_scalar], d_g
+    [n_ckt][nA], d_rows [n_ckt][8], d_done [n_ckt]; step [nA], g_lo / g_hi [n_ckt][nA], goals [n_ckt][n_scalar] (records of
+    abi.FIT_GOAL_DTYPE) and valid [n_inst] (bytes, None: all) are HOST arrays.  d_work carries the circuits' state from one update to
+    the next.  Enqueued on `stream`, no synchronisation."""
+    L = load()
+    st, lo, hi, go, va = _host(step, np.float64), _host(g_lo, np.float64), _host(g_hi, np.float64), _goals(goals), _host(valid, np.uint8)
+    rc = L.spicey_fit_update_device(device, C.addressof(req) if req is not None else None, n_scalar, int(bool(first)), _data(st), _data(lo), _data(hi), _data(go),
+                                    _data(va), d_x or None, d_g or None, d_rows or None, d_done or None, d_work or None, work_bytes, stream or None)
+    if rc != abi.OK:
+        _fail("spicey_fit_update_device", rc, L.spicey_last_error(None))
 
 
 def fourier_row_doubles(reqs) -> int:
@@ -827,6 +869,41 @@ class Handle:
                "history": history[:int(n_iter[:n_ckt].max()) if n_ckt else 0]}
         if rc == abi.OK:
             res["pss_ms"], res["tran_ms"] = self.L.spicey_last_pss_ms(self.h), self.L.spicey_last_pss_tran_ms(self.h)
+            try:
+                res["inst_status"] = self.inst_status()
+            except SpiceyNativeError:
+                res["inst_status"] = None  # (no transient ran)
+        return res
+
+    def run_fit(self, steps: int, dt: float, src: np.ndarray, req: abi.SpiceyFitReq, act, step, g_lo, g_hi, g0, goals, scalars, reqs=(), treqs=(), preqs=(),
+                freqs=(), sreqs=(), vreqs=(), want_iters: bool = False) -> dict:
+        """spicey_run_fit: the damped least-squares loop on this handle, whose n_inst = req.n_ckt (1 + 2 nA) instances are the
+        circuits' nominal and perturbed copies.  act [nA] (int32), step [nA], g_lo / g_hi / g0 [n_ckt][nA], goals [n_ckt][n_scalar]
+        (abi.FIT_GOAL_DTYPE) are host arrays, scalars the programs of abi.MC_SCALAR_DTYPE over the rows of reqs / treqs / preqs.
+        Returns `g` [n_ckt][nA] and `F` [n_ckt] (the best evaluated point), `x` [n_ckt][n_scalar] (the nominals' scalars there),
+        `history` [iterations][n_ckt][8], `n_iter` and `ckt_status` [n_ckt] (include/spicey_hip.h), `inst_status` of the last
+        transient, `fit_ms` (designs and updates) and `tran_ms` (the transients' kernels), summed over the iterations.  A refusal
+        comes back as status abi.ERR_BAD_DESC with its text in `detail`.  freqs / sreqs / vreqs are there to be refused."""
+        src, per_inst, iters = self._prologue(steps, src, want_iters)
+        a, keep, _ = self._reduced_lists(reqs, freqs, treqs, sreqs, preqs, vreqs)
+        sc = _scalars(scalars)
+        ac, st = _host(act, np.int32), _host(step, np.float64)
+        lo, hi, g0_, go = _host(g_lo, np.float64), _host(g_hi, np.float64), _host(g0, np.float64), _goals(goals)
+        n_ckt, nA = (max(int(req.n_ckt), 0), max(int(req.nA), 0)) if req is not None else (0, 0)
+        max_iter = max(int(req.max_iter), 0) if req is not None else 0
+        g, F = np.zeros((n_ckt, nA)), np.full(max(n_ckt, 1), np.inf)
+        x = np.full((n_ckt, len(sc)), np.nan)
+        history = np.zeros((max_iter, n_ckt, abi.FIT_ROW))
+        n_iter, cst = np.zeros(max(n_ckt, 1), np.int32), np.ones(max(n_ckt, 1), np.int32)
+        rc = self.L.spicey_run_fit(self.h, steps, dt, _p(src, C.c_double), per_inst, C.addressof(a), C.addressof(req) if req is not None else None, _data(ac),
+                                   _p(st, C.c_double), _p(lo, C.c_double), _p(hi, C.c_double), _p(g0_, C.c_double), _data(go), sc.ctypes.data if len(sc) else None,
+                                   len(sc), _p(g, C.c_double), _p(F, C.c_double), _p(history, C.c_double), _p(n_iter, C.c_int32), _p(cst, C.c_int32),
+                                   _p(x, C.c_double), _p(iters, C.c_int32))
+        del keep
+        res = {"status": rc, "detail": self.error() if rc != abi.OK else "", "g": g, "F": F[:n_ckt], "x": x, "n_iter": n_iter[:n_ckt], "ckt_status": cst[:n_ckt],
+               "history": history[:int(n_iter[:n_ckt].max()) if n_ckt else 0], "iters": iters}
+        if rc == abi.OK:
+            res["fit_ms"], res["tran_ms"] = self.L.spicey_last_fit_ms(self.h), self.L.spicey_last_fit_tran_ms(self.h)
             try:
                 res["inst_status"] = self.inst_status()
             except SpiceyNativeError:
@@ -1299,10 +1376,14 @@ class HipBackend(_AcCalls):
         """Handle.run_levels on a handle of its own whose instances are the level rows (flat: the nominal circuit replicated)."""
         return self._on_handle(flat, lambda h: h.run_levels(steps, dt, src, req, lvl, tol, scalars, reqs, treqs, preqs))
 
-
     def run_pss(self, flat: abi.FlatCircuit, m_steps: int, dt: float, src: np.ndarray, req: abi.SpiceyPssReq) -> dict:
         """Handle.run_pss on a handle of its own whose instances are the circuits' nominal and perturbed copies."""
         return self._on_handle(flat, lambda h: h.run_pss(m_steps, dt, src, req))
+
+    def run_fit(self, flat: abi.FlatCircuit, steps: int, dt: float, src: np.ndarray, req: abi.SpiceyFitReq, act, step, g_lo, g_hi, g0, goals, scalars, reqs=(),
+                treqs=(), preqs=()) -> dict:
+        """Handle.run_fit on a handle of its own whose instances are the circuits' nominal and perturbed copies."""
+        return self._on_handle(flat, lambda h: h.run_fit(steps, dt, src, req, act, step, g_lo, g_hi, g0, goals, scalars, reqs, treqs, preqs))
 
 
 class HipAcExactBackend(_AcCalls):
