@@ -284,6 +284,12 @@ int32_t spicey_top_fold_form(const SpiceyHandle *h, int64_t steps);
  * capacity —, SPICEY_NO_STAMP_FUSE not set when the handle was created); 0 = it takes another kernel, or there is no
  * handle.  The results are the same bits either way. */
 int32_t spicey_stamp_fuse_form(const SpiceyHandle *h, int64_t steps);
+/* Interpreter 2: 1 = a run of `steps` steps on this handle takes the form of that kernel whose time loop is written out for
+ * what the plan holds (spicey_stamp_fuse_form says 1, every phase but factor level 0 is resident, no resident record uses the
+ * overflow list, the first backward phase runs in the top's wave, no empty diagnostics phases were asked for,
+ * SPICEY_NO_FIXED_SCHEDULE not set when the handle was created); 0 = it takes another kernel, or there is no handle.  The
+ * results are the same bits either way. */
+int32_t spicey_fixed_schedule_form(const SpiceyHandle *h, int64_t steps);
 /* Human-readable description of the last error ("singular at inst 0 step 3 iter 0", the
  * hipGetErrorString text, …).  Valid until the next call on the handle. NULL handle -> global. */
 const char *spicey_last_error(SpiceyHandle *h);

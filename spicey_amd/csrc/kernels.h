@@ -21,9 +21,11 @@ hipError_t spicey_launch_tran(const SpiceyProg &P, const SpiceyRun &R, int K, bo
 // top_regs: spicey_top_regs_run — that form with the register-exchange top, an error without `addr` or for a top outside 1 .. 6 stages;
 // u0_resident: spicey_u0_resident_run — that form with the resident level-0 record, an error without `top_regs`;
 // top_fold: spicey_top_fold_run and the record table stands behind R->zpar — that form with the last factor level folded into the top, an error without `u0_resident`;
+// fixed_schedule: spicey_fixed_schedule_run — the fused kernel with the time loop written out, an error without `stamp_fuse`; profile: the handle asked for
+// phase timers — that form's kernel with the profiling executor instead of the production one (every other form has one kernel for both);
 // stamp_fuse: spicey_stamp_fuse_run and that form's table stands behind the fold's — the folded kernel whose Z stamps the next step, an error without `top_fold`)
 hipError_t spicey_launch_tran_v2(const SpiceyProg &Ph, const SpiceyResident &Qh, const SpiceyProg *P, const SpiceyResident *Q, const SpiceyRun *R, int K, int grid,
-                                 int threads, hipStream_t st, bool packed = false, bool phase_table = true, bool early = false, bool slots = false, bool ready = false, bool addr = false, bool top_regs = false, bool u0_resident = false, bool top_fold = false, bool stamp_fuse = false);
+                                 int threads, hipStream_t st, bool packed = false, bool phase_table = true, bool early = false, bool slots = false, bool ready = false, bool addr = false, bool top_regs = false, bool u0_resident = false, bool top_fold = false, bool stamp_fuse = false, bool fixed_schedule = false, bool profile = false);
 
 // group mode: R.wgs_per_group workgroups per K instances, workspace in global memory (large circuits)
 hipError_t spicey_launch_tran_grp(const SpiceyProg &P, const SpiceyRun &R, int K, int n_groups, int threads, hipStream_t st);

@@ -435,7 +435,9 @@ __global__ void __launch_bounds__(FRONTS ? 512 : 1024) spicey_tran_kernel_grp(Sp
 // wave, a dependent chain), 2 for the narrow levels (backward levels, factor levels from the third on: one short task per
 // lane or none), 1 for the two wide factor levels, 0 for stamping and the update (wide, throughput-bound).  Measured on the
 // headline batch: 3.91e7 -> 4.05e7 solves/s; a lone workgroup per CU gains nothing (9.86 -> 10.1 us), so it is off there.
-template <class Regs, bool PRIO = false>
+// PROF: false = the executor holds no profiling code at all (the production kernel of the fixed schedule, tran_v2_run.h: FS —
+// its time loop has no timer read, no accumulator bump and no test of `prof`); every other kernel is built with true.
+template <class Regs, bool PRIO = false, bool PROF = true>
 struct GpuExecV2 {
   unsigned long long *prof;  // LDS accumulators [SPICEY_PH_SLOTS] when profiling, else null
   long long t_last = 0;      // profiling: end of the previous phase (slot 7 accumulates the time BETWEEN phases)
@@ -464,16 +466,16 @@ struct GpuExecV2 {
   template <class F>
   __device__ __forceinline__ void wave_lockstep(int nlanes, int nsteps, F f) {
     long long t0 = 0;
-    if (prof && threadIdx.x == 0) t0 = clock64();
+    if (PROF && prof && threadIdx.x == 0) t0 = clock64();
     gpu_wave_lockstep(nlanes, nsteps, f);
-    if (prof && threadIdx.x == 0) atomicAdd(&prof[SPICEY_PH_U0 + 31], (unsigned long long)(clock64() - t0));  // (the slot of the tail it replaces)
+    if (PROF && prof && threadIdx.x == 0) atomicAdd(&prof[SPICEY_PH_U0 + 31], (unsigned long long)(clock64() - t0));  // (the slot of the tail it replaces)
   }
   template <class F>
   __device__ __forceinline__ void wave_lockstep_keep(int nlanes, int nsteps, F f) {
     long long t0 = 0;
-    if (prof && threadIdx.x == 0) { t0 = clock64(); if (t_last) atomicAdd(&prof[7], (unsigned long long)(t0 - t_last)); }
+    if (PROF && prof && threadIdx.x == 0) { t0 = clock64(); if (t_last) atomicAdd(&prof[7], (unsigned long long)(t0 - t_last)); }
     gpu_wave_lockstep_keep(nlanes, nsteps, f, PRIO);
-    if (prof && threadIdx.x == 0) { t_last = clock64(); atomicAdd(&prof[SPICEY_PH_U0 + 31], (unsigned long long)(t_last - t0)); }
+    if (PROF && prof && threadIdx.x == 0) { t_last = clock64(); atomicAdd(&prof[SPICEY_PH_U0 + 31], (unsigned long long)(t_last - t0)); }
   }
   // early-prefetch builds (tran_v2_run.h): the waves beside the top's are idle for its whole length — what `g` fetches
   // there costs no issue slot that anything else wants, and no register beside the top's
@@ -481,14 +483,14 @@ struct GpuExecV2 {
   template <class F, class G>
   __device__ __forceinline__ void wave_lockstep_keep_then(int nlanes, int nsteps, F f, G g) {
     long long t0 = 0;
-    if (prof && threadIdx.x == 0) { t0 = clock64(); if (t_last) atomicAdd(&prof[7], (unsigned long long)(t0 - t_last)); }
+    if (PROF && prof && threadIdx.x == 0) { t0 = clock64(); if (t_last) atomicAdd(&prof[7], (unsigned long long)(t0 - t_last)); }
     gpu_wave_lockstep_keep_then(nlanes, nsteps, f, g, PRIO);
-    if (prof && threadIdx.x == 0) { t_last = clock64(); atomicAdd(&prof[SPICEY_PH_U0 + 31], (unsigned long long)(t_last - t0)); }
+    if (PROF && prof && threadIdx.x == 0) { t_last = clock64(); atomicAdd(&prof[SPICEY_PH_U0 + 31], (unsigned long long)(t_last - t0)); }
   }
   template <class L, class F>
   __device__ __forceinline__ void tail_phase(int tag, int nlev, L load, F f) {
     long long t0 = 0;
-    if (prof && threadIdx.x == 0) t0 = clock64();
+    if (PROF && prof && threadIdx.x == 0) t0 = clock64();
     int tid = (int)threadIdx.x;
     asm volatile("" : "+v"(tid));
     if (tid < 64) {
@@ -503,12 +505,12 @@ struct GpuExecV2 {
       }
     }
     __syncthreads();
-    if (prof && threadIdx.x == 0) atomicAdd(&prof[tag], (unsigned long long)(clock64() - t0));
+    if (PROF && prof && threadIdx.x == 0) atomicAdd(&prof[tag], (unsigned long long)(clock64() - t0));
   }
   template <class F>
   __device__ __forceinline__ void phase(int tag, F f) {
     long long t0 = 0;
-    if (prof && threadIdx.x == 0) { t0 = clock64(); if (t_last) atomicAdd(&prof[7], (unsigned long long)(t0 - t_last)); }
+    if (PROF && prof && threadIdx.x == 0) { t0 = clock64(); if (t_last) atomicAdd(&prof[7], (unsigned long long)(t0 - t_last)); }
     // The thread id is made opaque per phase: otherwise hipcc hoists every `base + tid * 8` address (a VGPR
     // pair per array and instance) out of the time loop and the register-resident program spills.
     int tid = (int)threadIdx.x;
@@ -519,7 +521,22 @@ struct GpuExecV2 {
     f(tid);
     if (pr) __builtin_amdgcn_s_setprio(0);
     __syncthreads();
-    if (prof && threadIdx.x == 0) { t_last = clock64(); atomicAdd(&prof[tag], (unsigned long long)(t_last - t0)); }  // LDS: no stall
+    if (PROF && prof && threadIdx.x == 0) { t_last = clock64(); atomicAdd(&prof[tag], (unsigned long long)(t_last - t0)); }  // LDS: no stall
+  }
+  // the same with the issue priority as a constant of the call (tran_v2_run.h: spicey_phase_at) — PR is what `phase` would
+  // derive from the tag, 0 = none; without PRIO no priority is set, as there
+  static constexpr bool fixed_priority = true;
+  template <int PR, class F>
+  __device__ __forceinline__ void phase_at(int tag, F f) {
+    long long t0 = 0;
+    if (PROF && prof && threadIdx.x == 0) { t0 = clock64(); if (t_last) atomicAdd(&prof[7], (unsigned long long)(t0 - t_last)); }
+    int tid = (int)threadIdx.x;
+    asm volatile("" : "+v"(tid));
+    if (PRIO && PR != 0) __builtin_amdgcn_s_setprio(PR);
+    f(tid);
+    if (PRIO && PR != 0) __builtin_amdgcn_s_setprio(0);
+    __syncthreads();
+    if (PROF && prof && threadIdx.x == 0) { t_last = clock64(); atomicAdd(&prof[tag], (unsigned long long)(t_last - t0)); }
   }
 };
 
@@ -542,6 +559,11 @@ struct GpuExecV2 {
 #define SPICEY_KERNEL_TF 128
 // PT, bit 8 (SPICEY_KERNEL_SF): the stamp fuse of a folded kernel — Z stamps the next step, no phase B in the time loop (tran_v2_run.h: SF)
 #define SPICEY_KERNEL_SF 256
+// PT, bit 9 (SPICEY_KERNEL_FS): the fixed schedule of a fused kernel — the time loop written out for what the plan holds, an
+// executor without profiling code (tran_v2_run.h: FS).  Bit 10 (SPICEY_KERNEL_FS_PROF): the same kernel with the profiling
+// executor, launched where the handle asked for phase timers, so that its phase table compares like for like.
+#define SPICEY_KERNEL_FS 512
+#define SPICEY_KERNEL_FS_PROF 1024
 template <int K, int RMAX, int NSV, int NEL, int MAXT, int MINW, bool HYB = false, int PT = 0>
 __global__ void __launch_bounds__(MAXT, MINW) spicey_tran_kernel_v2(const SpiceyProg *__restrict__ Pg, const SpiceyResident *__restrict__ Qg,
                                                                     const SpiceyRun *__restrict__ Rg) {
@@ -574,7 +596,7 @@ __global__ void __launch_bounds__(MAXT, MINW) spicey_tran_kernel_v2(const Spicey
     c.ison = (int32_t *)(c.gd + nG);
   }
   c.flags = c.ison + (size_t)P.nS * K;
-  GpuExecV2<ResRegs<K, RMAX, NSV, NEL>, (MINW * 256 >= 2 * MAXT)> ex;  // two workgroups per CU
+  GpuExecV2<ResRegs<K, RMAX, NSV, NEL>, (MINW * 256 >= 2 * MAXT), (PT & SPICEY_KERNEL_FS) == 0 || (PT & SPICEY_KERNEL_FS_PROF) != 0> ex;  // two workgroups per CU
   // profiling accumulators live in LDS behind the flags (576 B, reserved by spicey_lds_bytes)
   // (offsets from `smem`, no integer casts: the pointers must keep their LDS address space, or every access
   // becomes a flat_load)
@@ -591,7 +613,7 @@ __global__ void __launch_bounds__(MAXT, MINW) spicey_tran_kernel_v2(const Spicey
     // start stamps wait in their own slots (not in registers: nothing may stay live around the whole run)
     if (threadIdx.x == 0) { lprof[5] = (unsigned long long)clock64(); lprof[6] = (unsigned long long)wall_clock64(); }
   }
-  spicey_tran_run_v2<K, RMAX, NSV, NEL, HYB, PT & 1, (PT & SPICEY_KERNEL_EP) != 0, (PT & SPICEY_KERNEL_OS) != 0, (PT & SPICEY_KERNEL_RA) != 0, (PT & SPICEY_KERNEL_OA) != 0, (PT & SPICEY_KERNEL_TR) != 0, (PT & SPICEY_KERNEL_UR) != 0, (PT & SPICEY_KERNEL_TF) != 0, (PT & SPICEY_KERNEL_SF) != 0>(ex, P, Q, R, c, wg);
+  spicey_tran_run_v2<K, RMAX, NSV, NEL, HYB, PT & 1, (PT & SPICEY_KERNEL_EP) != 0, (PT & SPICEY_KERNEL_OS) != 0, (PT & SPICEY_KERNEL_RA) != 0, (PT & SPICEY_KERNEL_OA) != 0, (PT & SPICEY_KERNEL_TR) != 0, (PT & SPICEY_KERNEL_UR) != 0, (PT & SPICEY_KERNEL_TF) != 0, (PT & SPICEY_KERNEL_SF) != 0, (PT & SPICEY_KERNEL_FS) != 0>(ex, P, Q, R, c, wg);
   if constexpr ((PT & SPICEY_KERNEL_OA) != 0) {
     static_assert(K == 1 && !HYB, "operand addresses: one instance per workgroup on the LDS workspace");
     // The one condition of SpiceyOperand that the source does not show: `smem` at LDS address 0.  Tested here, behind the run
@@ -610,9 +632,9 @@ __global__ void __launch_bounds__(MAXT, MINW) spicey_tran_kernel_v2(const Spicey
   }
 }
 
-template <int K, int RMAX, int NSV, int NEL, int MAXT, int MINW, bool HYB = false, int PT = 0, bool EP = false, bool OS = false, bool RA = false, bool OA = false, bool TR = false, bool UR = false, bool TF = false, bool SF = false>
+template <int K, int RMAX, int NSV, int NEL, int MAXT, int MINW, bool HYB = false, int PT = 0, bool EP = false, bool OS = false, bool RA = false, bool OA = false, bool TR = false, bool UR = false, bool TF = false, bool SF = false, int FS = 0>
 hipError_t launch_v2_t(const SpiceyProg *P, const SpiceyResident *Q, const SpiceyRun *R, int grid, int threads, size_t lds, hipStream_t st) {
-  auto kern = spicey_tran_kernel_v2<K, RMAX, NSV, NEL, MAXT, MINW, HYB, PT | (EP ? SPICEY_KERNEL_EP : 0) | (OS ? SPICEY_KERNEL_OS : 0) | (RA ? SPICEY_KERNEL_RA : 0) | (OA ? SPICEY_KERNEL_OA : 0) | (TR ? SPICEY_KERNEL_TR : 0) | (UR ? SPICEY_KERNEL_UR : 0) | (TF ? SPICEY_KERNEL_TF : 0) | (SF ? SPICEY_KERNEL_SF : 0)>;
+  auto kern = spicey_tran_kernel_v2<K, RMAX, NSV, NEL, MAXT, MINW, HYB, PT | (EP ? SPICEY_KERNEL_EP : 0) | (OS ? SPICEY_KERNEL_OS : 0) | (RA ? SPICEY_KERNEL_RA : 0) | (OA ? SPICEY_KERNEL_OA : 0) | (TR ? SPICEY_KERNEL_TR : 0) | (UR ? SPICEY_KERNEL_UR : 0) | (TF ? SPICEY_KERNEL_TF : 0) | (SF ? SPICEY_KERNEL_SF : 0) | FS>;
   if (const hipError_t e = spicey_allow_dyn_lds(kern, lds); e != hipSuccess) return e;
   hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, st, P, Q, R);
   return hipGetLastError();
@@ -687,7 +709,7 @@ hipError_t spicey_launch_tran(const SpiceyProg &P, const SpiceyRun &R, int K, bo
 }
 
 // one launcher per entry of SPICEY_V2_SHAPES (launch_plan.h)
-template <int I, int PT = 0, bool EP = false, bool OS = false, bool RA = false, bool OA = false, bool TR = false, bool UR = false, bool TF = false, bool SF = false>
+template <int I, int PT = 0, bool EP = false, bool OS = false, bool RA = false, bool OA = false, bool TR = false, bool UR = false, bool TF = false, bool SF = false, int FS = 0>
 static hipError_t launch_v2_shape(const SpiceyProg *P, const SpiceyResident *Q, const SpiceyRun *R, int grid, int threads, size_t lds, hipStream_t st) {
   constexpr SpiceyV2Shape s = SPICEY_V2_SHAPES[I];
   static_assert(!EP || s.early, "an early-prefetch kernel is built for the shapes that say so");
@@ -698,7 +720,8 @@ static hipError_t launch_v2_shape(const SpiceyProg *P, const SpiceyResident *Q, 
   static_assert(!UR || (s.u0_resident && TR), "a resident level-0 record is a form of the register-exchange-top kernel, for the shapes that say so");
   static_assert(!TF || (s.top_fold && UR), "a folded last factor level is a form of the resident-record kernel, for the shapes that say so");
   static_assert(!SF || (s.stamp_fuse && TF), "a stamp fuse is a form of the folded kernel, for the shapes that say so");
-  return launch_v2_t<1, s.rmax, s.nsv, s.nel, s.threads, s.minw, s.hybrid, PT, EP, OS, RA, OA, TR, UR, TF, SF>(P, Q, R, grid, threads, lds, st);
+  static_assert(FS == 0 || ((FS & ~SPICEY_KERNEL_FS_PROF) == SPICEY_KERNEL_FS && s.fixed_schedule && SF), "a fixed schedule is a form of the fused kernel, for the shapes that say so");
+  return launch_v2_t<1, s.rmax, s.nsv, s.nel, s.threads, s.minw, s.hybrid, PT, EP, OS, RA, OA, TR, UR, TF, SF, FS>(P, Q, R, grid, threads, lds, st);
 }
 static decltype(&launch_v2_shape<0>) const launch_v2_by_shape[] = {launch_v2_shape<0>, launch_v2_shape<1>, launch_v2_shape<2>, launch_v2_shape<3>,
                                                                     launch_v2_shape<4>, launch_v2_shape<5>, launch_v2_shape<6>};
@@ -728,12 +751,17 @@ static decltype(&launch_v2_shape<0>) const launch_v2_u0_resident_by_shape[SPICEY
 static decltype(&launch_v2_shape<0>) const launch_v2_top_fold_by_shape[SPICEY_V2_NSHAPES] = {nullptr, launch_v2_shape<1, 1, true, true, true, true, true, true, true>, nullptr, nullptr, nullptr, nullptr, nullptr};
 // ... and that one whose Z stamps the next step (SpiceyV2Shape::stamp_fuse)
 static decltype(&launch_v2_shape<0>) const launch_v2_stamp_fuse_by_shape[SPICEY_V2_NSHAPES] = {nullptr, launch_v2_shape<1, 1, true, true, true, true, true, true, true, true>, nullptr, nullptr, nullptr, nullptr, nullptr};
+// ... and that one with the time loop written out (SpiceyV2Shape::fixed_schedule): [0] the production kernel, [1] the one with phase timers
+static decltype(&launch_v2_shape<0>) const launch_v2_fixed_schedule_by_shape[2][SPICEY_V2_NSHAPES] = {
+    {nullptr, launch_v2_shape<1, 1, true, true, true, true, true, true, true, true, SPICEY_KERNEL_FS>, nullptr, nullptr, nullptr, nullptr, nullptr},
+    {nullptr, launch_v2_shape<1, 1, true, true, true, true, true, true, true, true, SPICEY_KERNEL_FS | SPICEY_KERNEL_FS_PROF>, nullptr, nullptr, nullptr, nullptr, nullptr}};
 
 hipError_t spicey_launch_tran_v2(const SpiceyProg &Ph, const SpiceyResident &Qh, const SpiceyProg *P, const SpiceyResident *Q, const SpiceyRun *R, int K, int grid,
-                                 int threads, hipStream_t st, bool packed, bool phase_table, bool early, bool slots, bool ready, bool addr, bool top_regs, bool u0_resident, bool top_fold, bool stamp_fuse) {
+                                 int threads, hipStream_t st, bool packed, bool phase_table, bool early, bool slots, bool ready, bool addr, bool top_regs, bool u0_resident, bool top_fold, bool stamp_fuse, bool fixed_schedule, bool profile) {
   const int shape = K == 1 ? spicey_v2_shape(threads, packed, Ph.hybrid != 0, packed && Ph.fresh_fill != 0) : -1;  // (a fresh-fill program runs on the build that decodes its flags: spicey_plan makes one for the packed geometry only)
   if (shape < 0) return hipErrorInvalidValue;
   if (stamp_fuse && !(slots && ready && addr && top_regs && u0_resident && top_fold)) return hipErrorInvalidValue;  // (only a folded run has that form)
+  if (fixed_schedule && !stamp_fuse) return hipErrorInvalidValue;  // (only a fused run has that form)
   // the table sits in the tail area behind the tridiagonal top's index table: only where it fits there (tran_exec.h)
   const bool pt = phase_table && launch_v2_pt_by_shape[shape] != nullptr && spicey_pt_fits(Ph.pcr_n, Ph.pcr_level, Qh.tail_n);
   if (slots) {  // (the plan found room for the operand slots: spicey_slots_fit — checked again, the kernel writes there)
@@ -750,6 +778,10 @@ hipError_t spicey_launch_tran_v2(const SpiceyProg &Ph, const SpiceyResident &Qh,
               if (launch_v2_top_fold_by_shape[shape] == nullptr) return hipErrorInvalidValue;
               if (stamp_fuse) {  // (the plan found every sum of phase B to draw on one thread of Z and built the table behind the fold's: spicey_stamp_fuse_table)
                 if (launch_v2_stamp_fuse_by_shape[shape] == nullptr || threads != SPICEY_V2_SHAPES[shape].threads) return hipErrorInvalidValue;
+                if (fixed_schedule) {  // (the plan found every phase but level 0 resident, inline records only, the merged backward phase: spicey_fixed_schedule_fits)
+                  if (launch_v2_fixed_schedule_by_shape[profile][shape] == nullptr) return hipErrorInvalidValue;
+                  return launch_v2_fixed_schedule_by_shape[profile][shape](P, Q, R, grid, threads, spicey_lds_bytes(Ph, K, true, Qh.tail_n), st);
+                }
                 return launch_v2_stamp_fuse_by_shape[shape](P, Q, R, grid, threads, spicey_lds_bytes(Ph, K, true, Qh.tail_n), st);
               }
               return launch_v2_top_fold_by_shape[shape](P, Q, R, grid, threads, spicey_lds_bytes(Ph, K, true, Qh.tail_n), st);

@@ -47,7 +47,7 @@ static const SpiceyV2Shape &v2_build(int threads, bool packed = false, bool hybr
 SpiceyKnobs spicey_read_knobs() {
   const char *ms = getenv("SPICEY_GROUP_TIMEOUT_MS");
   return {getenv("SPICEY_NO_HYBRID") != nullptr, getenv("SPICEY_FRONT_RIGHT_LOOKING") != nullptr, getenv("SPICEY_TEST_FORCE_GROUP_ABORT") != nullptr,
-          ms ? atoi(ms) : 0, getenv("SPICEY_NO_PHASE_TABLE") != nullptr, getenv("SPICEY_NO_FRESH_FILL") != nullptr, getenv("SPICEY_FRESH_FILL_LINEAR") != nullptr, getenv("SPICEY_NO_EARLY_PREFETCH") != nullptr, getenv("SPICEY_NO_OPERAND_SLOTS") != nullptr, getenv("SPICEY_NO_READY_ARGS") != nullptr, getenv("SPICEY_NO_OPERAND_ADDR") != nullptr, getenv("SPICEY_NO_TOP_REGS") != nullptr, getenv("SPICEY_NO_U0_RESIDENT") != nullptr, getenv("SPICEY_NO_TOP_FOLD") != nullptr, getenv("SPICEY_NO_STAMP_FUSE") != nullptr};
+          ms ? atoi(ms) : 0, getenv("SPICEY_NO_PHASE_TABLE") != nullptr, getenv("SPICEY_NO_FRESH_FILL") != nullptr, getenv("SPICEY_FRESH_FILL_LINEAR") != nullptr, getenv("SPICEY_NO_EARLY_PREFETCH") != nullptr, getenv("SPICEY_NO_OPERAND_SLOTS") != nullptr, getenv("SPICEY_NO_READY_ARGS") != nullptr, getenv("SPICEY_NO_OPERAND_ADDR") != nullptr, getenv("SPICEY_NO_TOP_REGS") != nullptr, getenv("SPICEY_NO_U0_RESIDENT") != nullptr, getenv("SPICEY_NO_TOP_FOLD") != nullptr, getenv("SPICEY_NO_STAMP_FUSE") != nullptr, getenv("SPICEY_NO_FIXED_SCHEDULE") != nullptr};
 }
 
 static int pick_threads(const HostProgram &hp, bool v2) {
@@ -306,6 +306,8 @@ int32_t spicey_plan(const SpiceyDesc *desc, const SpiceyOptions &opt, const Spic
     plan.top_fold = spicey_plan_top_fold(plan.u0_resident, hp, hres.tail_n, shape, knobs);
     // (the stamp fuse: every sum of phase B draws on values of one thread of Z)
     plan.stamp_fuse = spicey_plan_stamp_fuse(plan.top_fold, hp, hres.tail_n, plan.T, shape, knobs);
+    // (the fixed schedule: every phase but level 0 resident, inline records only, the first backward phase in the top's wave)
+    plan.fixed_schedule = spicey_plan_fixed_schedule(plan.stamp_fuse, hp, hres, shape, opt.debug >> 8, knobs);
   }
   if (!plan.lds) {
     // group mode: several CUs per instance when the batch leaves CUs idle and the circuit is large enough for the
@@ -568,6 +570,41 @@ bool spicey_plan_stamp_fuse(bool top_fold, const HostProgram &hp, int tail_n, in
          spicey_stamp_fuse_table(hp, tail_n, T, SPICEY_V2_SHAPES[shape].nsv, SPICEY_V2_SHAPES[shape].nel, table);
 }
 bool spicey_stamp_fuse_run(const LaunchPlan &plan, int64_t steps) { return plan.stamp_fuse && spicey_top_fold_run(plan, steps); }
+
+bool spicey_fixed_schedule_fits(const HostProgram &hp, const HostResident &hres) {
+  const SpiceyProg &P = hp.hdr;
+  const int nL = P.nLevels, nPh = (int)hp.ph_cnt.size(), S = spicey_top_stages(P.pcr_n);
+  if (!P.has16 || P.hybrid || P.pcr_n <= 0 || P.pcr_n > 64 || S < 1 || S > 6 || P.pcr_level < 2 || P.pcr_level > nL || nPh != 2 * nL || nPh > 254) return false;
+  if (hres.tail_n != 0 || hres.rmax <= 0 || hres.T <= 0 || (hres.T & 63)) return false;
+  const int u_end = P.pcr_level, k_begin = 2 * nL - P.pcr_level;
+  if (k_begin >= 2 * nL - 1 || hres.k_merge != k_begin) return false;  // (a merged backward phase and a last one behind it)
+  if ((int)hres.st_cnt.size() < nPh || hres.st_cnt[0] == 0u) return false;
+  for (int p = 1; p < nPh; p++)
+    if (hres.st_cnt[p] != 0u) return false;
+  for (int p = 0; p < u_end - 1; p++)
+    if (hp.ph_cnt[p] == 0u) return false;  // (not unsafe, but a barrier per step for nothing: launch_plan.h)
+  // the resident records: slot s of wave w runs in phase res_phase[w][s]; 0xFE = the continuation of the row record before it
+  const int nW = hres.T / 64, rmax = hres.rmax;
+  if (hres.res_phase.size() < (size_t)nW * rmax || hres.res.size() < (size_t)rmax * hres.T * 4) return false;
+  for (int w = 0; w < nW; w++)
+    for (int s = 0; s < rmax; s++) {
+      const int ph = hres.res_phase[(size_t)w * rmax + s];
+      if (ph < 0 || ph == 0xFE) continue;
+      const bool factor = ph < nL;
+      if (factor ? ph >= u_end - 1 : ph < k_begin) continue;  // (the folded level, the top's own levels: never dispatched)
+      if (factor && s + 1 < rmax && hres.res_phase[(size_t)w * rmax + s + 1] == 0xFE) continue;  // (a row record: two pivots by its form)
+      for (int lane = 0; lane < 64; lane++) {
+        const uint32_t w0 = hres.res[((size_t)s * hres.T + (size_t)w * 64 + lane) * 4];
+        if (((w0 >> 24) & SPICEY_R16_VALID) && ((w0 >> 16) & 0xffu) > 2u) return false;
+      }
+    }
+  return true;
+}
+bool spicey_plan_fixed_schedule(bool stamp_fuse, const HostProgram &hp, const HostResident &hres, int shape, int debug_empty, const SpiceyKnobs &knobs) {
+  return stamp_fuse && shape >= 0 && shape < SPICEY_V2_NSHAPES && SPICEY_V2_SHAPES[shape].fixed_schedule && hres.T == SPICEY_V2_SHAPES[shape].threads &&
+         hres.rmax == SPICEY_V2_SHAPES[shape].rmax && debug_empty == 0 && !knobs.no_fixed_schedule && spicey_fixed_schedule_fits(hp, hres);
+}
+bool spicey_fixed_schedule_run(const LaunchPlan &plan, int64_t steps) { return plan.fixed_schedule && spicey_stamp_fuse_run(plan, steps); }
 
 size_t spicey_zpar_doubles(const LaunchPlan &plan, const HostProgram &hp) {
   if (!plan.early || plan.interp != 2) return 0;

@@ -53,11 +53,12 @@ struct SpiceyV2Shape {
   bool u0_resident = false;  // ... and that one with the resident level-0 record (tran_v2_run.h: UR), taken by a register-exchange-top run where spicey_u0_resident_fits holds unless SPICEY_NO_U0_RESIDENT is set
   bool top_fold = false;  // ... and that one with the last factor level folded into the top (tran_v2_run.h: TF), taken by a resident-record run where spicey_top_fold_table holds unless SPICEY_NO_TOP_FOLD is set
   bool stamp_fuse = false;  // ... and that one whose Z stamps the next step, with no phase B in the time loop (tran_v2_run.h: SF), taken by a folded run where spicey_stamp_fuse_table holds unless SPICEY_NO_STAMP_FUSE is set
+  bool fixed_schedule = false;  // ... and that one with the time loop written out for what the plan holds (tran_v2_run.h: FS), taken by a fused run where spicey_fixed_schedule_fits holds unless SPICEY_NO_FIXED_SCHEDULE is set
 };
 // `early`: Z's element parameters come from one record per thread (SpiceyRun::zpar) and are fetched, with the next source
 // value, at the tail of the last factor phase.  The fresh packed build has it; the other builds were left as they are.
 // (spicey_launch_tran_v2 instantiates one kernel per entry; each kind in ascending threads)
-constexpr SpiceyV2Shape SPICEY_V2_SHAPES[] = {{true, false, 512, 4, 6, 2, 4},    {true, false, 512, 4, 2, 2, 4, true, true, true, true, true, true, true, true, true},
+constexpr SpiceyV2Shape SPICEY_V2_SHAPES[] = {{true, false, 512, 4, 6, 2, 4},    {true, false, 512, 4, 2, 2, 4, true, true, true, true, true, true, true, true, true, true},
                                               {false, true, 512, 16, 8, 2, 2},   {false, true, 1024, 4, 4, 1, 4},
                                               {false, false, 256, SPICEY_V2_RMAX256, 12, 4, 1},
                                               {false, false, 512, 16, 8, 2, 2},  {false, false, 1024, 8, 4, 1, 4}};
@@ -89,6 +90,7 @@ struct SpiceyKnobs {
   bool no_u0_resident = false;       // SPICEY_NO_U0_RESIDENT: a register-exchange-top run keeps the kernel that fetches level 0's row record in every step (the in-library A/B switch)
   bool no_top_fold = false;          // SPICEY_NO_TOP_FOLD: a resident-record run keeps the kernel that runs the last factor level as a phase of its own (the in-library A/B switch)
   bool no_stamp_fuse = false;        // SPICEY_NO_STAMP_FUSE: a folded run keeps the kernel that stamps in a phase B of its own (the in-library A/B switch)
+  bool no_fixed_schedule = false;    // SPICEY_NO_FIXED_SCHEDULE: a fused run keeps the kernel whose time loop decides its schedule in every step (the in-library A/B switch)
 };
 SpiceyKnobs spicey_read_knobs();
 
@@ -162,6 +164,10 @@ struct LaunchPlan {
   // spicey_stamp_fuse_table holds for the program and SPICEY_NO_STAMP_FUSE is not set: every folded run of the handle takes
   // it (spicey_stamp_fuse_run)
   bool stamp_fuse = false;
+  // ... and a form of that kernel with the time loop written out (tran_v2_run.h: FS), where the plan says `stamp_fuse`,
+  // spicey_fixed_schedule_fits holds for the program and its resident layout, the handle asks for no empty diagnostics
+  // phases and SPICEY_NO_FIXED_SCHEDULE is not set: every fused run of the handle takes it (spicey_fixed_schedule_run)
+  bool fixed_schedule = false;
   bool lds = true;       // workspace in LDS (else global memory)
   size_t lds_bytes = 0;
   int64_t algo_bytes = 0;
@@ -258,6 +264,30 @@ bool spicey_stamp_fuse_table(const HostProgram &hp, int tail_n, int T, int nsv, 
 bool spicey_plan_stamp_fuse(bool top_fold, const HostProgram &hp, int tail_n, int T, int shape, const SpiceyKnobs &knobs);
 // ... and whether that run takes the fuse: a folded run of a plan that says `stamp_fuse`
 bool spicey_stamp_fuse_run(const LaunchPlan &plan, int64_t steps);
+// The fixed schedule (tran_v2_run.h: FS): the time loop of a fused run written out — U_0 from the resident record, the resident
+// factor levels 1 .. pcr_level - 2, the folded top with the merged backward phase and the early fetch, the remaining
+// backward phases, Z and its second phase — with no phase mask, no streamed path, no overflow list and no fork on the phase
+// table.  spicey_fixed_schedule_fits returns false unless ALL of this holds for the program hp and its resident layout hres
+// (the loop would mis-run anything else):
+//   - a tridiagonal top of 1 .. 6 stages at pcr_level >= 2 (the fold's own conditions, asked again) and at most 254 phases;
+//   - no phase of the run is streamed but level 0, whose record is resident in its own registers (UR): st_cnt[p] == 0 for
+//     every p > 0, st_cnt[0] > 0;
+//   - every factor phase the loop runs, 0 .. pcr_level - 2, has tasks, and the resident layout has no LDS tail (tail_n == 0:
+//     a top replaces it).  (An empty phase would not be mis-run — its compare chain matches no slot — but the loop has no
+//     mask to skip it by and would pay its barrier in every step, where the other form pays nothing: stricter than
+//     correctness needs, on purpose);
+//   - a backward phase exists below the top and the first of them is merged into the top's wave (k_merge == 2 nLevels -
+//     pcr_level < 2 nLevels - 1): with pcr_level > 0 that is the z-prefetch bit of the loop, and the source park has a last
+//     backward phase of its own to ride on;
+//   - every resident record of a phase the loop runs — factor or backward, row-record chunks apart, which have no count — has
+//     at most two products: none uses the overflow list.
+// (That Z has no beyond-capacity loop — zrem == 0 — and that nothing re-iterates is the fuse's: spicey_stamp_fuse_table.)
+bool spicey_fixed_schedule_fits(const HostProgram &hp, const HostResident &hres);
+// LaunchPlan::fixed_schedule of a plan whose `stamp_fuse` is decided, on build `shape`; debug_empty: the empty diagnostics
+// phases per solve that the handle's options ask for (SpiceyRun::debug_empty_phases — the written-out loop has none)
+bool spicey_plan_fixed_schedule(bool stamp_fuse, const HostProgram &hp, const HostResident &hres, int shape, int debug_empty, const SpiceyKnobs &knobs);
+// ... and whether that run takes the fixed schedule: a fused run of a plan that says `fixed_schedule`
+bool spicey_fixed_schedule_run(const LaunchPlan &plan, int64_t steps);
 // doubles of the parameter record SpiceyRun::zpar of a planned handle: five per resident item, NEL x T items per instance
 // (0: the plan runs a build without it); a plan that says `top_fold` keeps SPICEY_TOP_FOLD_WORDS words of table behind them
 size_t spicey_zpar_doubles(const LaunchPlan &plan, const HostProgram &hp);

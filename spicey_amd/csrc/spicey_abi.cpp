@@ -277,7 +277,7 @@ static int32_t enqueue_kernel(SpiceyHandle *h, const SpiceyRun &R, hipStream_t s
   if (h->plan.interp == 3) {
     HIPCHK(h, spicey_launch_exact(h->d_xprog, h->d_Rstruct, h->plan.grid, h->plan.T, h->plan.lds ? h->plan.lds_bytes : 0, st));
   } else if (h->plan.interp == 2) {
-    HIPCHK(h, spicey_launch_tran_v2(h->dprog, h->dres, h->d_Pstruct, h->d_Qstruct, h->d_Rstruct, h->plan.K, h->plan.grid, h->plan.T, st, h->plan.packed, !h->knobs.no_phase_table, h->d_zpar != nullptr, h->plan.slots, spicey_ready_run(h->plan, R.steps), spicey_addr_run(h->plan, R.steps), spicey_top_regs_run(h->plan, R.steps), spicey_u0_resident_run(h->plan, R.steps), top_fold, stamp_fuse));
+    HIPCHK(h, spicey_launch_tran_v2(h->dprog, h->dres, h->d_Pstruct, h->d_Qstruct, h->d_Rstruct, h->plan.K, h->plan.grid, h->plan.T, st, h->plan.packed, !h->knobs.no_phase_table, h->d_zpar != nullptr, h->plan.slots, spicey_ready_run(h->plan, R.steps), spicey_addr_run(h->plan, R.steps), spicey_top_regs_run(h->plan, R.steps), spicey_u0_resident_run(h->plan, R.steps), top_fold, stamp_fuse, stamp_fuse && spicey_fixed_schedule_run(h->plan, R.steps), h->d_prof != nullptr));
   } else if (group) {
     HIPCHK(h, spicey_launch_tran_grp(h->dprog, R, h->plan.K, h->plan.grid, h->plan.T, st));
   } else {
@@ -492,6 +492,7 @@ extern "C" int32_t spicey_group_retries(const SpiceyHandle *h) { return h ? h->g
 extern "C" int32_t spicey_top_regs_form(const SpiceyHandle *h, int64_t steps) { return (h && h->plan.interp == 2 && spicey_top_regs_run(h->plan, steps)) ? 1 : 0; }
 extern "C" int32_t spicey_u0_resident_form(const SpiceyHandle *h, int64_t steps) { return (h && h->plan.interp == 2 && spicey_u0_resident_run(h->plan, steps)) ? 1 : 0; }
 extern "C" int32_t spicey_top_fold_form(const SpiceyHandle *h, int64_t steps) { return (h && h->plan.interp == 2 && spicey_top_fold_run(h->plan, steps)) ? 1 : 0; }
+extern "C" int32_t spicey_fixed_schedule_form(const SpiceyHandle *h, int64_t steps) { return (h && h->plan.interp == 2 && spicey_fixed_schedule_run(h->plan, steps)) ? 1 : 0; }
 extern "C" int32_t spicey_stamp_fuse_form(const SpiceyHandle *h, int64_t steps) { return (h && h->plan.interp == 2 && spicey_stamp_fuse_run(h->plan, steps)) ? 1 : 0; }
 extern "C" int64_t spicey_group_stale_polls(const SpiceyHandle *h) { return h ? h->stale_polls : 0; }
 

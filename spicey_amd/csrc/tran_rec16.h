@@ -76,7 +76,9 @@ struct ResRegs {
 // read it (the entry's static value IS 0.0, so the fma chain and its bits are those of the unflagged task).
 // OA (operand-address builds, tran_common.h: SpiceyOperand): the operands of the inline case and the target are named by
 // handles — one instruction from the record word to the LDS address, the target's shared by its read and its write.
-template <int K, bool KTASK, bool OPG = false, bool FRESH = false, bool OA = false, class OV>
+// INL (the fixed-schedule build, tran_v2_run.h: FS): the host has made sure that no record this call can see has more than two
+// products (launch_plan.h: spicey_fixed_schedule_fits) — the overflow path is not compiled and `ovf` never asked.
+template <int K, bool KTASK, bool OPG = false, bool FRESH = false, bool OA = false, bool INL = false, class OV>
 SPICEY_HD void spicey_exec_rec16(const WgCtx<K> &c, OV ovf, uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3,
                                  uint32_t keep_from = 0u, uint32_t xoff = 0u) {
   static_assert(!OA || !OPG, "operand addresses: everything lives in the LDS workspace");
@@ -92,7 +94,7 @@ SPICEY_HD void spicey_exec_rec16(const WgCtx<K> &c, OV ovf, uint32_t w0, uint32_
   double acc[K];
   if (KTASK) {
     const uint32_t d = w1 & 0xffffu;
-    if (cnt <= 2) {
+    if (INL || cnt <= 2) {
       const uint32_t u0 = Op::template half<1>(w1), x0 = Op::template half<0>(w2), u1 = Op::template half<1>(w2), x1 = Op::template half<0>(w3);
       const uint32_t d_a = OA ? Op::template half<0>(w1) : d;
       const bool two = SPICEY_WAVE_ANY(cnt == 2);  // tasks are sorted by count: most waves are uniform
@@ -128,7 +130,7 @@ SPICEY_HD void spicey_exec_rec16(const WgCtx<K> &c, OV ovf, uint32_t w0, uint32_
     // right-hand-side target)
     const bool third_lds = !OPG || tgt >= xoff;
     const bool keep_old = !FRESH || !(meta & (SPICEY_R16_FRESH << 8));
-    if (cnt <= 2) {
+    if (INL || cnt <= 2) {
       const uint32_t l0 = Op::template half<0>(w1), d0 = Op::template half<1>(w1), u0 = Op::template half<0>(w2);
       const uint32_t l1 = Op::template half<1>(w2), d1 = Op::template half<0>(w3), u1 = Op::template half<1>(w3);
       const bool two = SPICEY_WAVE_ANY(cnt == 2);
@@ -407,6 +409,35 @@ SPICEY_HD void spicey_uk_phase(const SpiceyProg &P, const SpiceyResident &Q, con
     }
   }
   if (FRESH && !KTASK && !UR) for (int i = 0; i < 8; i++) rr.u0[FRESH ? i : 0] = 0u;  // (consumed, or not for this phase: dead until the next B)
+}
+
+// FS (the fixed-schedule build, tran_v2_run.h): a phase of a run in which every phase but level 0 is resident and no resident
+// record has more than two products — the slot compare chain of spicey_uk_phase and nothing else.  No streamed tail, no
+// descriptor, no phase-table read; no reused factorisation, so no `xoff`, `keep_from` or right-hand-side-only row; rr.u0 is
+// the resident level-0 record's and stays; no overflow list.  The records run through the same executors with those
+// arguments as constants: the arithmetic and its order are spicey_uk_phase's.
+template <int K, int RMAX, int NSV, int NEL, bool KTASK, bool OA>
+SPICEY_HD void spicey_uk_phase_fs(const WgCtx<K> &c, ResRegs<K, RMAX, NSV, NEL> &rr, int p) {
+  static_assert(RMAX <= 8, "the fixed schedule is a form of the packed build: a static compare chain over its few slots");
+  constexpr bool FRESH = SpiceyShapeKind<RMAX, NSV, NEL>::fresh;
+  auto ovf = []() -> const uint16_t * { return nullptr; };  // (never asked: INL)
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+  for (int s = 0; s < RMAX; s++) {
+    const int sp = SPICEY_UNIFORM((int)((rr.phv[s >> 2] >> ((s & 3) * 8)) & 0xffu));
+    if (sp == p) {
+      uint32_t w0 = rr.w0[s], w1 = rr.w1[s], w2 = rr.w2[s], w3 = rr.w3[s];
+      SPICEY_OPAQUE(w0); SPICEY_OPAQUE(w1); SPICEY_OPAQUE(w2); SPICEY_OPAQUE(w3);
+      if (!KTASK && s + 1 < RMAX && SPICEY_UNIFORM((int)((rr.phv[(s + 1) >> 2] >> (((s + 1) & 3) * 8)) & 0xffu)) == 0xFE) {  // a chunk of row records: this slot + its continuation
+        uint32_t w[8] = {w0, w1, w2, w3, rr.w0[s + 1 < RMAX ? s + 1 : s], rr.w1[s + 1 < RMAX ? s + 1 : s], rr.w2[s + 1 < RMAX ? s + 1 : s], rr.w3[s + 1 < RMAX ? s + 1 : s]};
+        SPICEY_OPAQUE(w[4]); SPICEY_OPAQUE(w[5]); SPICEY_OPAQUE(w[6]); SPICEY_OPAQUE(w[7]);
+        spicey_exec_row16<K, false, FRESH, OA>(c, w, false);
+      } else {
+        spicey_exec_rec16<K, KTASK, false, FRESH, OA, true>(c, ovf, w0, w1, w2, w3, 0u, 0u);
+      }
+    }
+  }
 }
 
 // UR: factor phase 0 of a run whose level 0 is nothing but row records, at most one per thread (the host has made sure:

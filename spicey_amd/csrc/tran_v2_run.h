@@ -307,8 +307,28 @@ struct SpiceyHasIdleWaves<E, decltype((void)E::idle_waves)> { static constexpr b
 // then, and its readers sit in other waves) — three stores from registers and nothing else.  The
 // caller has made sure that spicey_stamp_fuse_table holds for the program (launch_plan.h: spicey_plan_stamp_fuse): no
 // switch — the loop below never re-iterates —, nothing beyond the resident capacity, not linear.
-template <int K, int RMAX, int NSV, int NEL, bool HYB = false, int PT = -1, bool EP = false, bool OS = false, bool RA = false, bool OA = false, bool TR = false, bool UR = false, bool TF = false, bool SF = false, class Exec>
+// FS (the fixed schedule, a form of the fused build): the plan has decided, for the whole run, what the loop of every other
+// form decides again in every phase of every step — which phases exist and are resident, that the table is on, that nothing
+// re-iterates, that Z's parameters were fetched early — and the time loop is written out for it: U_0 from the resident
+// record, the resident factor levels 1 .. pcr_level - 2 (spicey_uk_phase_fs), the folded top with the merged backward phase
+// and the early fetch, the remaining backward phases, the last with the source park, Z, the second phase of Z.  No iteration
+// loop, no S, A or diagnostics phase, no phase masks, no fork on the table; issue priorities are constants of each call
+// (an executor with `fixed_priority`: phase_at) and an executor built without profiling holds no timer code.  The iteration
+// counts — always 1 — are written once, behind the loop, for the steps that were recorded.  The caller has made sure that
+// spicey_fixed_schedule_fits holds for the program and its resident layout (launch_plan.h: spicey_plan_fixed_schedule).
+template <class E, class = void>
+struct SpiceyHasFixedPriority { static constexpr bool value = false; };
+template <class E>
+struct SpiceyHasFixedPriority<E, decltype((void)E::fixed_priority)> { static constexpr bool value = true; };
+// a phase whose issue priority `PR` (0 = none) is a constant of the call; executors without priorities run a plain phase
+template <int PR, class Exec, class F>
+SPICEY_HD void spicey_phase_at(Exec &ex, int tag, F f) {
+  if constexpr (SpiceyHasFixedPriority<Exec>::value) ex.template phase_at<PR>(tag, f);
+  else ex.phase(tag, f);
+}
+template <int K, int RMAX, int NSV, int NEL, bool HYB = false, int PT = -1, bool EP = false, bool OS = false, bool RA = false, bool OA = false, bool TR = false, bool UR = false, bool TF = false, bool SF = false, bool FS = false, class Exec>
 SPICEY_HD void spicey_tran_run_v2(Exec &ex, const SpiceyProg &P, const SpiceyResident &Q, const SpiceyRun &R, WgCtx<K> &c, int wg) {
+  static_assert(!FS || (SF && K == 1 && !HYB), "the fixed schedule is a form of the fused build");
   const int T = ex.threads();
   static_assert(!OS || PT != 0, "the operand slots lie behind the phase table");
   static_assert(!RA || OS, "the ready arguments are a form of the operand-slot build");
@@ -404,6 +424,93 @@ SPICEY_HD void spicey_tran_run_v2(Exec &ex, const SpiceyProg &P, const SpiceyRes
   top_pack |= (K == 1 && pcr_n > 0 && Q.k_merge == k_begin && k_begin < 2 * nL - 1) ? 1 << 19 : 0;  // bit 19 = the first backward phase runs in the top's wave
   top_pack |= (PT < 0 && pt_run) ? 1 << 20 : 0;  // bit 20 = the phases take their arguments from the phase table (where that is a run-time choice)
   top_pack = SPICEY_UNIFORM(top_pack);
+  if constexpr (FS) {
+    static_assert(PT != 0 && EP && RA && OA && TR && UR && TF, "the fixed schedule: the table is on, every form below the fuse is taken");
+    constexpr int PR_WIDE = 1, PR_NARROW = 2;  // (the issue priorities of GpuExecV2::phase: the two wide factor levels, every narrow one)
+    constexpr bool IDLE = SpiceyHasIdleWaves<Exec>::value;
+    for (int64_t step = 0; step <= steps && code == 0; step++) {
+      int tp = top_pack;
+      SPICEY_OPAQUE_S(tp);
+      const int pcr_n = tp & 0xff, pcr_S = (tp >> 8) & 0xff;
+      const uint32_t *ptw = c.tail + spicey_pt_base_words(pcr_n);
+      // 1. U_0 from the resident record, 2. the resident factor levels below the folded one
+      spicey_phase_at<PR_WIDE>(ex, SPICEY_PH_U0, [&](int tid) { spicey_u0_resident_phase<K, RMAX, NSV, NEL, OA>(c, ex.template regs<Regs>(tid)); });
+      if (u_end > 2) spicey_phase_at<PR_WIDE>(ex, SPICEY_PH_U0 + 1, [&](int tid) { spicey_uk_phase_fs<K, RMAX, NSV, NEL, false, OA>(c, ex.template regs<Regs>(tid), 1); });
+      for (int p = 2; p < u_end - 1; p++)
+        spicey_phase_at<PR_NARROW>(ex, SPICEY_PH_U0 + (p < 30 ? p : 30), [&](int tid) { spicey_uk_phase_fs<K, RMAX, NSV, NEL, false, OA>(c, ex.template regs<Regs>(tid), p); });
+      // 3. the folded top, the first backward phase behind it in the same wave, and Z's early fetch beside them
+      auto early_fetch = [&](int tid) {
+        SpiceyProg Pt{};
+        SpiceyRun Rt{};
+        spicey_pt_args_early(SpiceyPtLanes::run_block(ptw, tid), Pt, Rt);
+        Rt.steps = steps;
+        Ph2 p2{Pt, Rt, c, T, 0u, 0u, &P, &R, ptw};
+        p2.z_early(tid, step, ex.template regs<Regs>(tid));
+      };
+      auto merged_k = [&](int lane) { spicey_uk_phase_fs<K, RMAX, NSV, NEL, true, OA>(c, ex.template regs<Regs>(lane), k_begin); };
+      if constexpr (!IDLE) ex.phase(SPICEY_PH_U0 + (u_end - 1 < 30 ? u_end - 1 : 30), early_fetch);  // (an executor without idle waves: a phase of its own, where the folded level's was)
+#if defined(__HIP_DEVICE_COMPILE__)
+      auto top_all = [&](int lane, int, double *) {
+        spicey_pcr_all_regs<K, true>(c, (const uint16_t *)(c.tail + 1024), pcr_n, pcr_S, lane);  // (all 64 lanes: nlanes = 64 below)
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        merged_k(lane);
+      };
+      if constexpr (IDLE) ex.wave_lockstep_keep_then(64, 1, top_all, early_fetch);
+      else ex.wave_lockstep_keep(64, 1, top_all);
+#else
+      auto top_staged = [&](int lane, int st, double *) {  // (the whole wave in one call, whichever lane the executor runs first)
+        if (st == 0 && lane == 0) spicey_top_fold_wave<K>(c, c.tail, (const uint16_t *)(c.tail + 1024), pcr_n, pcr_S);
+        if (st > pcr_S) merged_k(lane);
+      };
+      if constexpr (IDLE) ex.wave_lockstep_keep_then(64, pcr_S + 2, top_staged, early_fetch);
+      else ex.wave_lockstep_keep(64, pcr_S + 2, top_staged);
+#endif
+      // 4. the remaining backward phases; the last parks the source value that the early fetch left in a register
+      for (int p = k_begin + 1; p < 2 * nL - 1; p++) {
+        const int l = 2 * nL - 1 - p;
+        spicey_phase_at<PR_NARROW>(ex, SPICEY_PH_K0 + (l < 31 ? l : 31), [&](int tid) { spicey_uk_phase_fs<K, RMAX, NSV, NEL, true, OA>(c, ex.template regs<Regs>(tid), p); });
+      }
+      spicey_phase_at<PR_NARROW>(ex, SPICEY_PH_K0, [&](int tid) {
+        spicey_uk_phase_fs<K, RMAX, NSV, NEL, true, OA>(c, ex.template regs<Regs>(tid), 2 * nL - 1);  // (level 0: the leaves)
+        SPICEY_SCHED_FENCE;  // after the tasks, not among them: their registers are free by now
+        SpiceyProg Pt{};
+        SpiceyRun Rt{};
+        spicey_pt_args(ptw, tid, Pt, Rt);
+        Ph2 p2{Pt, Rt, c, T, 0u, 0u, &P, &R};
+        p2.z_src_park(tid, ex.template regs<Regs>(tid).srcn);
+      });
+      if (c.flags[1]) { code = 1; err_step = step; err_iter = 0; break; }
+      solves += (unsigned long long)c.valid[0];
+      // 5. Z with the stamp arithmetic, 6. its second phase
+      spicey_phase_at<0>(ex, SPICEY_PH_Z, [&](int tid) {
+        const uint32_t *ptz = c.tail + spicey_pt_base_words(top_pack & 0xff);
+        SpiceyProg Pt{};
+        SpiceyRun Rt{};
+        spicey_pt_args_z(SpiceyPtLanes::run_block(ptz, tid), Pt, Rt);
+        Rt.steps = steps;
+        Ph2 p2{Pt, Rt, c, T, 0u, 0u, &P, &R, ptz};
+        p2.z_record(tid, step, ex.template regs<Regs>(tid), true);  // (the iteration count: behind the loop)
+      });
+      spicey_phase_at<0>(ex, SPICEY_PH_Z2, [&](int tid) {
+        Ph2 p2{P, R, c, T, 0u, 0u};
+        p2.z_fuse(tid, step == steps, ex.template regs<Regs>(tid));
+      });
+    }
+    // the iteration counts of the recorded steps — 1 each: such a run never re-iterates — with all threads, and nothing at or
+    // behind a failing step
+    ex.phase(SPICEY_PH_PRO, [&](int tid) {
+      const SpiceyRun Rf = ex.fresh(R);
+      if (Rf.iters && c.valid[0]) {
+        int32_t *it = Rf.iters + (size_t)c.inst[0] * (size_t)(steps + 1);
+        const int64_t done = code ? err_step : steps + 1;
+        for (int64_t i = tid; i < done; i += T) it[i] = 1;
+      }
+    });
+  } else
+  // (The loop above is this loop written out for one plan: phase order, tags, priorities, the merged phase's id, the error
+  // break ahead of Z, the solve count and what `iters` holds after an error are copied by hand.  Whoever changes one of
+  // them here changes it there; tests/test_fixed_schedule.py and test_fixed_schedule_gpu.py hold the two against each other.)
   for (int64_t step = 0; step <= steps && code == 0; step++) {
     int iter = 0;
     for (;;) {

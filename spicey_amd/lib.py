@@ -44,6 +44,7 @@ SIGNATURES = {
     "spicey_u0_resident_form": (_i32, [_vp, _i64]),
     "spicey_top_fold_form": (_i32, [_vp, _i64]),
     "spicey_stamp_fuse_form": (_i32, [_vp, _i64]),
+    "spicey_fixed_schedule_form": (_i32, [_vp, _i64]),
     "spicey_last_error": (_str, [_vp]),
     "spicey_destroy": (None, [_vp]),
     "spicey_version": (_str, []),
@@ -632,6 +633,10 @@ class Handle:
     def stamp_fuse_form(self, steps: int) -> bool:
         """Whether a run of `steps` steps takes the kernel whose Z stamps the next step, with no phase B in the loop (spicey_stamp_fuse_form)."""
         return bool(self.L.spicey_stamp_fuse_form(self.h, steps))
+
+    def fixed_schedule_form(self, steps: int) -> bool:
+        """Whether a run of `steps` steps takes the fused kernel whose time loop is written out for the plan (spicey_fixed_schedule_form)."""
+        return bool(self.L.spicey_fixed_schedule_form(self.h, steps))
 
     def error(self) -> str:
         m = self.L.spicey_last_error(self.h)
